@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Gray-Scott step path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--grid RxC]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--grid RxC] [--dump-outputs DIR]
 
 One "step" = one simulation time step of the whole grid (the reference's own throughput
 unit is cells x steps, compute/shared/src/benchmark.rs:55-59; its "compute" workload is
@@ -19,7 +19,15 @@ N > 1 : one process per GPU (torchrun; `python bench.py --gpus N` without WORLD_
         --scaling strong: one grid for every N -- 32768 x 16384 (config 4 "across 2 then 4") for
             N <= 4, 65536 x 32768 (config 5) for N = 8; --grid overrides it.
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  `steps` is K, the steps of every timed region; `ms_per_step` is the wall time of one
+of them (the median region's).  --dump-outputs DIR (N = 1) also writes what the timed Species holds after its last timed
+step as DIR/*.npy.  The inputs depend on the arguments alone, and the planes on the step count the line records
+(`dump_outputs.steps`): every strict kernel variant the tuner may pick gives the same bits (the `verified` replay checks
+it).  Before the timed regions the timed Species takes up to 8 tuning calls of 400 steps, until the on-line tuner
+reports a choice for the grid (`dump_outputs.tuning_steps`), and the tuner's number of timed trials can vary.  So the
+count is the same from run to run when the tuner has reported before the first call -- the default 16384 x 16384 run,
+whose developed pattern (4000 steps) tunes the context first: tuning_steps = 0 -- or never reports (all 8 calls);
+otherwise, e.g. with --no-extra on a grid the tuner tunes, compare `dump_outputs.steps` before comparing planes.
 """
 from __future__ import annotations
 
@@ -80,7 +88,51 @@ def parse_args():
                          "binds a transport that accepts several ranks per device (tests/cpp/shm_transport.cpp, "
                          "built on the fly unless GS_RCCL_LIBRARY names one).  Checks the code path, the numbers "
                          "mean nothing")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="N = 1: after the timed regions, write the U and V planes the timed Species holds (and, unless "
+                         "--no-extra, those of the developed pattern after its timed regions) as DIR/<name>.npy, float32; "
+                         "grids above the size budget are written as a fixed, seeded sample of cells (DIR/index.npy: "
+                         "their row-major indices)")
     return ap.parse_args()
+
+
+# --dump-outputs: at most this many bytes in all; a larger grid is written as a sample of DUMP_SAMPLE_CELLS cells drawn
+# with DUMP_SEED, the same cells for every plane and every run of the same grid
+DUMP_MAX_BYTES = 64 * 10 ** 6
+DUMP_SAMPLE_CELLS = 1 << 21
+DUMP_SEED = 0
+DUMP_FILES = ("u.npy", "v.npy", "index.npy", "developed_u.npy", "developed_v.npy")
+
+
+def dump_index(rows, cols, planes):
+    """Row-major indices of the cells --dump-outputs writes of each plane (sorted, no repeats), or None when `planes`
+    whole planes of this grid fit the budget."""
+    import numpy as np
+
+    cells = rows * cols
+    if planes * cells * 4 + planes * 128 <= DUMP_MAX_BYTES:          # (128: the header of a .npy file)
+        return None
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.unique(rng.integers(0, cells, size=min(DUMP_SAMPLE_CELLS, cells), dtype=np.int64))
+    assert planes * idx.size * 4 + idx.size * 8 + (planes + 1) * 128 <= DUMP_MAX_BYTES
+    return idx
+
+
+def dump_planes(out_dir, prefix, species, ctx, index):
+    """Downloads the input (newest) planes of `species` -- what perform_steps hands its caller -- and writes them, or the
+    cells of `index`, as out_dir/<prefix>u.npy and <prefix>v.npy.  Returns the file names."""
+    import numpy as np
+
+    ctx.sync()
+    in_u, in_v, _, _ = species.in_out()
+    names = []
+    for name, plane in (("u", in_u), ("v", in_v)):
+        host = plane.make_scalar_view(ctx)
+        data = host if index is None else host.reshape(-1)[index]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(data, dtype=np.float32))
+        names.append(prefix + name + ".npy")
+        del host, data
+    return names
 
 
 def placement_report(ctx, species, sp_dev, place, slab_rows, cols):
@@ -104,6 +156,9 @@ def placement_report(ctx, species, sp_dev, place, slab_rows, cols):
 
 def main() -> int:
     args = parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        print("bench.py: --dump-outputs is for one GPU (--gpus 1)", file=sys.stderr)
+        return 2
     # N > 1 without a torchrun environment: this process is only the launcher of the torchrun CHILD -- decided
     # before torch.cuda, the process group or libgs_hip.so exist in this process.
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -213,7 +268,7 @@ def main() -> int:
                 sp_dev_s = upload_species(sim_s, u0, v0, 0)      # (the replay of the pattern is not timed)
             del u0, v0
             run(sp_dev, 4000)                            # develops the pattern; also tunes the context
-        tuned = (0, 0, 0, 0)
+        tuned, tuning_steps = (0, 0, 0, 0), 0
         if single:
             # gs_run chooses unit height / fused steps / columns per lane / tap sharing on line, from timed passes of
             # the simulation itself (per context and shape).  It finishes here, on passes of the timed Species, so
@@ -223,6 +278,7 @@ def main() -> int:
                 if tuned[0] > 0:
                     break
                 run(species, 400)
+                tuning_steps += 400
         else:
             # A slab chain does not tune on line: rank 0 tunes on a throw-away single slab of the slab's
             # shape and every rank is handed the same configuration (grayscott_amd/dist.py).
@@ -295,6 +351,24 @@ def main() -> int:
     wall, event_ms, passes = median_run(runs)
     walls = [r[0] for r in runs]
 
+    # ---- --dump-outputs: the planes of the timed Species as its last timed step left them (later legs step it on) ----
+    dumped = None
+    if args.dump_outputs:
+        with stage("dump", 300):
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name in DUMP_FILES:                     # nothing of an earlier dump stays beside this one
+                if os.path.exists(os.path.join(args.dump_outputs, name)):
+                    os.remove(os.path.join(args.dump_outputs, name))
+            dump_idx = dump_index(rows, cols, 4 if with_extra else 2)
+            dumped = {"dir": os.path.abspath(args.dump_outputs), "steps": species.steps_done, "tuning_steps": tuning_steps,
+                      "files": dump_planes(args.dump_outputs, "", species, ctx, dump_idx),
+                      "sampled_cells": None if dump_idx is None else int(dump_idx.size)}
+            if dump_idx is not None:
+                import numpy as np
+
+                np.save(os.path.join(args.dump_outputs, "index.npy"), dump_idx.astype(np.float64))
+                dumped["files"].append("index.npy")
+
     per_rank, rccl_ranks = [], None
     if world > 1:
         with stage("per-rank", 600):
@@ -322,6 +396,9 @@ def main() -> int:
             run(sp_dev, args.warmup)
             warm(sp_dev)
             runs_dev = repeated(sp_dev, args.steps, args.repeats)
+            if dumped is not None:
+                dumped["developed_steps"] = sp_dev.steps_done
+                dumped["files"] += dump_planes(args.dump_outputs, "developed_", sp_dev, ctx, dump_idx)
             w_dev, ms_dev, p_dev = median_run(runs_dev)
             developed = {"value": cells * args.steps / w_dev / 1e6,
                          "value_min": cells * args.steps / max(r[0] for r in runs_dev) / 1e6,
@@ -458,6 +535,8 @@ def main() -> int:
     for key, leg in (("fused_flavour", fused), ("single_step", single_step), ("verified", verified), ("peer_chain", peer_chain)):
         if leg is not None:
             result[key] = leg
+    if dumped is not None:
+        result["dump_outputs"] = dumped
     if ctx.stats().get("window_fallbacks"):
         result["window_fallbacks"] = ctx.stats()["window_fallbacks"]     # a timing that contains one measured a stall
     if rank == 0 and single and not args.no_cpu_baseline:

@@ -54,3 +54,20 @@ def test_gpus_n_without_torchrun_starts_a_torchrun_child():
                        cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
     assert r.returncode != 0
     assert r.stderr.count("no GPU visible") >= 2, r.stderr[-2000:]
+
+
+def test_dump_outputs_sample_is_fixed_and_within_budget():
+    """--dump-outputs: whole planes while they fit 64 MB, else the same seeded sample of cells for every run of a grid."""
+    import bench
+
+    assert bench.dump_index(1080, 1920, 4) is None and bench.dump_index(2000, 2000, 4) is not None
+    a, b = bench.dump_index(16384, 16384, 4), bench.dump_index(16384, 16384, 4)
+    assert a.tobytes() == b.tobytes() and a.size > (1 << 20)
+    assert (a[1:] > a[:-1]).all() and a[0] >= 0 and a[-1] < 16384 * 16384
+    assert 4 * a.size * 4 + a.size * 8 <= bench.DUMP_MAX_BYTES <= 64 * 10 ** 6
+
+
+def test_dump_outputs_is_refused_for_several_gpus():
+    r = _python("import sys, bench\nsys.argv = ['bench.py', '--gpus', '2', '--dump-outputs', 'out']\nsys.exit(bench.main())\n")
+    assert r.returncode == 2 and "--dump-outputs" in r.stderr, (r.returncode, r.stderr)
+    assert not os.path.exists(os.path.join(ROOT, "out"))

@@ -1,7 +1,10 @@
 """Static checks of the reference-side binding (rust/compute_hip), which this image cannot compile
 (no Rust toolchain): the FFI declarations agree with include/gs_hip.h, the manifest has what the
 reference's own backends need (compute/block/Cargo.toml:8,14-24), perform_steps is synchronous as in
-compute/shared/src/gpu/mod.rs:77-91, and the workspace patch applies to the reference checkout."""
+compute/shared/src/gpu/mod.rs:77-91, and the workspace patch applies to the reference
+(its hunks against stored hashes of the reference's lines, tests/golden/workspace_patch_hunks.json)."""
+import hashlib
+import json
 import os
 import re
 import shutil
@@ -13,7 +16,6 @@ from grayscott_amd import capi
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUST = os.path.join(ROOT, "rust", "compute_hip")
-REF = "/root/reference"
 
 
 def _read(*parts):
@@ -77,15 +79,52 @@ def test_perform_steps_waits_and_prepare_steps_does_not():
     assert "ffi::gs_run(" in prep and "gs_sync" not in prep
 
 
-@pytest.mark.skipif(not os.path.isdir(REF) or shutil.which("patch") is None, reason="needs the reference checkout and patch(1)")
+def _hunks(patch_text):
+    """{file: [(start, count, lines)]}: every hunk of the workspace patch with the old-side lines it records (context
+    and removals), which must be the reference's lines start .. start + count - 1."""
+    files, cur = {}, None
+    for raw in patch_text.splitlines():
+        m = re.match(r"^\+\+\+ b/(\S+)", raw)
+        if m:
+            cur = files.setdefault(m.group(1), [])
+            continue
+        m = re.match(r"^@@ -(\d+),(\d+) \+\d+,\d+ @@", raw)
+        if m:
+            cur.append((int(m.group(1)), int(m.group(2)), []))
+            continue
+        if cur and raw[:1] in (" ", "-") and not raw.startswith("--- ") and len(cur[-1][2]) < cur[-1][1]:
+            cur[-1][2].append(raw[1:])
+    return files
+
+
+@pytest.mark.skipif(shutil.which("patch") is None, reason="needs patch(1)")
 def test_workspace_patch_applies_to_the_reference(tmp_path):
+    """Every hunk's context and removed lines are the reference's lines at the range its header names -- checked
+    against tests/golden/workspace_patch_hunks.json, the sha256 of those ranges taken from the reference checkout
+    (tests/golden/make_patch_hunks.py) --, the patch applies exactly (no offset, no fuzz) to files that hold those
+    lines there, and the patched selector prefers compute_hip over every other backend."""
     patch = os.path.join(ROOT, "rust", "grayscott_compute_hip.patch")
-    files = re.findall(r"^\+\+\+ b/(\S+)", _read(patch), flags=re.M)
+    text = _read(patch)
+    files = re.findall(r"^\+\+\+ b/(\S+)", text, flags=re.M)
     assert "compute/selector/src/lib.rs" in files and "Cargo.toml" in files
-    for f in files:
+    hunks = _hunks(text)
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "workspace_patch_hunks.json")))
+    assert sorted(hunks) == sorted(files) == sorted(golden)
+    for f, hs in hunks.items():
+        assert sorted("%d,%d" % (start, count) for start, count, _ in hs) == sorted(golden[f]), f
+        pre = []
+        for start, count, lines in hs:
+            assert len(lines) == count and start > len(pre), (f, start)
+            digest = hashlib.sha256("".join(ln + "\n" for ln in lines).encode()).hexdigest()
+            assert digest == golden[f]["%d,%d" % (start, count)], f"{f} @@ -{start},{count}: not the reference's lines"
+            pre += ["-- line %d, not touched by the patch --" % n for n in range(len(pre) + 1, start)] + lines
         os.makedirs(os.path.join(tmp_path, os.path.dirname(f)), exist_ok=True)
-        shutil.copy(os.path.join(REF, f), os.path.join(tmp_path, f))
-    subprocess.run(["patch", "-p1", "--forward", "-i", patch], cwd=tmp_path, check=True, stdout=subprocess.DEVNULL)
+        with open(os.path.join(tmp_path, f), "w") as out:
+            out.write("\n".join(pre) + "\n")
+    p = subprocess.run(["patch", "-p1", "--forward", "--fuzz=0", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
+    assert p.returncode == 0 and "offset" not in p.stdout and "fuzz" not in p.stdout, p.stdout + p.stderr
     sel = _read(tmp_path, "compute/selector/src/lib.rs")
     assert sel.index('feature = "compute_hip"') < sel.index('feature = "compute_gpu_specialized"')
+    assert "pub type Simulation = compute_hip::Simulation;" in sel
     assert 'compute_hip.path = "compute/hip"' in _read(tmp_path, "Cargo.toml")
+    assert '"compute/hip",' in _read(tmp_path, "Cargo.toml")
