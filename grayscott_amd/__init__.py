@@ -8,6 +8,7 @@ has not been built (``__graft_entry__.build()``), and there is no CPU fallback.
 from . import capi  # noqa: F401
 from .capi import GsError  # noqa: F401
 from .simulation import (  # noqa: F401
+    Ensemble,
     Evolving,
     HipArgs,
     HipConcentration,
@@ -18,5 +19,5 @@ from .simulation import (  # noqa: F401
     pinned_empty,
 )
 
-__all__ = ["capi", "GsError", "Evolving", "HipArgs", "HipConcentration", "HipContext",
+__all__ = ["capi", "GsError", "Ensemble", "Evolving", "HipArgs", "HipConcentration", "HipContext",
            "Parameters", "Simulation", "Species", "pinned_empty"]

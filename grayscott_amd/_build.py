@@ -47,6 +47,7 @@ UNITS = [
     ("gs_tuner.cpp", "gs_tuner.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_window.cpp", "gs_window.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_rccl.cpp", "gs_rccl.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_ensemble.cpp", "gs_ensemble.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

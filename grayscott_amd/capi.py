@@ -41,6 +41,8 @@ EXPORTS = (
     "gs_runtime_info", "gs_fields_place", "gs_debug_dyn_lds_key", "gs_debug_window_plan",
     "gs_debug_place_stats", "gs_debug_exchange_probe_create", "gs_debug_exchange_probe_run",
     "gs_debug_exchange_probe_destroy", "gs_download_wait_but",
+    "gs_ensemble_create", "gs_ensemble_destroy", "gs_ensemble_shape", "gs_ensemble_set_params", "gs_ensemble_seed",
+    "gs_ensemble_upload", "gs_ensemble_download", "gs_ensemble_run",
 )
 
 
@@ -163,6 +165,14 @@ def load() -> ctypes.CDLL:
         "gs_debug_exchange_probe_create": (i32, [i32, i32, i32, u64, P(vp)]),
         "gs_debug_exchange_probe_run": (i32, [vp, P(f32), P(f32)]),
         "gs_debug_exchange_probe_destroy": (i32, [vp]),
+        "gs_ensemble_create": (i32, [vp, P(vp), u64, u64, u64]),
+        "gs_ensemble_destroy": (i32, [vp, vp]),
+        "gs_ensemble_shape": (i32, [vp, P(u64), P(u64), P(u64)]),
+        "gs_ensemble_set_params": (i32, [vp, vp, P(GsParams), u64]),
+        "gs_ensemble_seed": (i32, [vp, vp]),
+        "gs_ensemble_upload": (i32, [vp, vp, u64, u64, vp, vp]),
+        "gs_ensemble_download": (i32, [vp, vp, u64, u64, i32, vp]),
+        "gs_ensemble_run": (i32, [vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

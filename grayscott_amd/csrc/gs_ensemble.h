@@ -1,0 +1,158 @@
+// gs_ensemble.h -- ensembles: `members` independent grids of one shape, each with its own parameters, advanced in shared
+// launches (gs_ensemble_run, gs_ensemble.cpp).  Two forms, both made of the per-cell code of gs_lds_resident.h:
+//   gs_ens_resident_k  one workgroup per member for the whole call: the member is loaded into LDS once, advanced `steps`
+//                      times LDS -> LDS with one barrier per step, and stored once (gs_run_resident_k with a member
+//                      coordinate, up to 8 cells per thread and 160 KiB of LDS: gs_ens_resident_cpt);
+//   gs_ens_tile_k      K <= 8 steps per launch on LDS-resident windows (gs_run_tile_k with a member coordinate): grid =
+//                      members x windows per member; a window never reads across its member's edge -- cells outside
+//                      the member are zeros, exactly as cells outside the grid are for a lone Species.
+// A workgroup belongs to ONE member, so its parameters are wave-uniform: they are read from the device table with scalar
+// loads (constant address space) into SGPRs.  Member offsets are 64-bit.
+// Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED and the GS_SUFFIX / GS_TAP
+// macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
+#pragma once
+
+namespace {
+
+typedef __attribute__((address_space(4))) const GsEnsParams GsEnsParamsConst;
+
+// The GsStepArgs the per-cell code reads, for member `member` (rows, columns, boundary rule, parameters, planes).
+__device__ __forceinline__ GsStepArgs ens_member_args(const GsEnsArgs &e, int64_t member)
+{
+    GsStepArgs a{};
+    GsEnsParamsConst *q = (GsEnsParamsConst *)e.params + member; // s_load: member is wave-uniform
+    const int64_t off = member * ((int64_t)e.rows * e.cols);
+    a.in_u = e.in_u + off;
+    a.in_v = e.in_v + off;
+    a.out_u = e.out_u + off;
+    a.out_v = e.out_v + off;
+    a.rows = e.rows;
+    a.cols = e.cols;
+    a.pitch = e.cols;
+    a.zero_halo = e.zero_halo;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) a.w[i][j] = q->w[i][j];
+    a.du = q->du;
+    a.dv = q->dv;
+    a.feed = q->feed;
+    a.feed_plus_kill = q->feed_plus_kill;
+    a.dt = q->dt;
+    return a;
+}
+
+// Resident form.  The LDS layout and the step loop are gs_run_resident_k's: 4 planes of (rows + 2) x (cols + 2) floats
+// with a ring of zeros, thread t owning cells t, t + blockDim.x, ... (CPT of them at most).  The host sizes the
+// workgroup to the waves the member's cells need (an 8 x 16 member: 2 waves), so small members share a CU.
+template <int CPT, int FAST, int ZH>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_k)(GsEnsArgs e, int steps, int to_out)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const GsStepArgs a = ens_member_args(e, e.first + (int64_t)blockIdx.x);
+    const int cells = a.rows * a.cols, cols = a.cols, P = cols + 2, plane = (a.rows + 2) * P;
+    const int nthreads = (int)blockDim.x;
+    for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f; // the rings (and everything else)
+    __syncthreads();
+    int o[CPT];
+    bool live[CPT];
+    float E[CPT][8];
+#pragma unroll
+    for (int k = 0; k < CPT; ++k) {
+        const int idx = (int)threadIdx.x + k * nthreads;
+        live[k] = idx < cells;
+        const int r = live[k] ? idx / cols : 0, c = live[k] ? idx - r * cols : 0;
+        o[k] = (r + 1) * P + c + 1;
+        if (ZH == 0) border_weights(a, r, c, E[k]);
+        if (live[k]) {
+            lds[o[k]] = a.in_u[idx];
+            lds[2 * plane + o[k]] = a.in_v[idx];
+        }
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int s = 0; s < steps; ++s) {
+        const float *su = lds + cur * plane, *sv = lds + (2 + cur) * plane;
+        float *du = lds + (cur ^ 1) * plane, *dv = lds + (2 + (cur ^ 1)) * plane;
+#pragma unroll
+        for (int k = 0; k < CPT; ++k) {
+            if (!live[k]) continue;
+            Row3 R[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                const int q = o[k] + (i - 1) * P;
+                R[i].u[0] = su[q - 1]; R[i].u[1] = su[q]; R[i].u[2] = su[q + 1];
+                R[i].v[0] = sv[q - 1]; R[i].v[1] = sv[q]; R[i].v[2] = sv[q + 1];
+            }
+            float nu, nv;
+            if (ZH == 0)
+                cell_border<FAST>(a, E[k], R[0], R[1], R[2], nu, nv);
+            else
+                cell<false, FAST, Row3>(a, R[0], R[1], R[2], 1, true, true, 0u, 0u, nu, nv);
+            du[o[k]] = nu;
+            dv[o[k]] = nv;
+        }
+        __syncthreads();
+        cur ^= 1;
+    }
+    float *gu = to_out ? a.out_u : const_cast<float *>(a.in_u);
+    float *gv = to_out ? a.out_v : const_cast<float *>(a.in_v);
+#pragma unroll
+    for (int k = 0; k < CPT; ++k)
+        if (live[k]) {
+            const int idx = (int)threadIdx.x + k * nthreads;
+            gu[idx] = lds[cur * plane + o[k]];
+            gv[idx] = lds[(2 + cur) * plane + o[k]];
+        }
+}
+
+// Windowed form: gs_run_tile_k's load, K steps (tile_steps) and store, for window `blockIdx.x % windows` of member
+// `first + blockIdx.x / windows`.
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_k)(GsEnsArgs e, int K, int windows)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
+    const GsStepArgs a = ens_member_args(e, e.first + m);
+    constexpr int H = tile_rows(RPW);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int HO = H - 2 * K, WO = kTileCols - 2 * K; // output rows / columns per window
+    const int tiles_c = (a.cols + WO - 1) / WO;
+    const int tr = win / tiles_c, tc = win - tr * tiles_c;
+    const int gr0 = tr * HO - K, gc0 = tc * WO - K; // member coordinates of window cell (0, 0)
+    const int gr = gr0 + wave * RPW, gc = gc0 + lane; // this lane's first cell
+    // load; cells outside the member are zeros (and stay zeros: tile_steps)
+    float u[RPW], v[RPW];
+    const int cc = min(max(gc, 0), a.cols - 1);
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+        const ptrdiff_t g = (ptrdiff_t)min(max(gr + i, 0), a.rows - 1) * a.pitch + cc;
+        const bool in = gr + i >= 0 && gr + i < a.rows && gc >= 0 && gc < a.cols;
+        u[i] = in ? a.in_u[g] : 0.0f;
+        v[i] = in ? a.in_v[g] : 0.0f;
+    }
+    const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;
+    if (!edge)
+        tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
+    else if (a.zero_halo)
+        tile_steps<RPW, true, FAST, 1>(a, lds, K, gr, gc, wave, lane, u, v);
+    else
+        tile_steps<RPW, true, FAST, 0>(a, lds, K, gr, gc, wave, lane, u, v);
+    // store the window shrunk by K, where it lies in the member
+    if (lane >= K && lane < kTileCols - K && gc < a.cols) {
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) {
+            const int wr = wave * RPW + i;
+            if (wr >= K && wr < H - K && gr + i < a.rows) {
+                const ptrdiff_t g = (ptrdiff_t)(gr + i) * a.pitch + gc;
+                a.out_u[g] = u[i];
+                a.out_v[g] = v[i];
+            }
+        }
+    }
+}
+
+} // namespace

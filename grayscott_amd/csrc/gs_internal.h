@@ -5,6 +5,7 @@
 //   gs_tuner.cpp   kernel configuration: the launch-geometry model, the on-line tuner of gs_run, gs_ctx_get/set_tuned
 //   gs_window.cpp  the persistent window kernel's host side: tiling, exchange planes, give-up and replay
 //   gs_rccl.cpp    RCCL (loaded on first use), its self-test, gs_runtime_info, gs_last_error
+//   gs_ensemble.cpp ensembles: many grids of one shape, each with its own parameters, advanced in shared launches
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
@@ -219,6 +220,7 @@ namespace gsi {
 struct Run; // gs_run: state of one call (below)
 
 // gs_api.cpp
+int32_t check_math(const gs_params &p, int32_t math);
 int32_t same_shape(const gs_field *a, const gs_field *b);
 int32_t sync_all(gs_ctx *ctx);
 int32_t refresh_ghosts(gs_ctx *ctx, gs_field *f);
@@ -242,7 +244,7 @@ bool tuned_for(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse);
 int32_t pick_cols_per_lane(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse);
 int32_t pick_rows_per_unit(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse);
 int32_t model_rows_per_unit(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse, int cpl);
-void pick_tile_config(long rows, long cols, int *shape, int *k);
+void pick_tile_config(long rows, long cols, int *shape, int *k, long members = 1);
 uint64_t slab_rows_of(const gs_field *f);
 bool same_slab_shape(const gs_ctx *ctx, uint64_t rows_a, uint64_t cols_a, uint64_t rows_b, uint64_t cols_b);
 bool tuned_shape(const gs_ctx *ctx, const gs_field *f, int fuse);

@@ -102,6 +102,38 @@ struct GsWindowArgs {
     int32_t seq;               // this launch's number on its context (>= 1): what a workgroup that gives up leaves in *abort
 };
 
+// Ensembles (gs_ensemble.h): `members` independent grids of one shape, each with its own parameters, in dense planes
+// [members, rows, cols] (pitch = cols).  One entry per member in a device table, read with scalar loads: a workgroup
+// belongs to one member.  feed_plus_kill is the reference's f32 add (compute/naive/src/lib.rs:77), formed by the host.
+struct GsEnsParams {
+    float w[3][3];
+    float du, dv, feed, feed_plus_kill, dt;
+    int32_t pad[2]; // 64 B per member: two s_load_dwordx8
+};
+// Largest member the resident ensemble kernel takes: LDS (4 planes of (rows + 2) x (cols + 2) floats, at most 160 KiB per
+// workgroup) and cells per thread of a 1024-thread workgroup -- 8 under the zero-halo rule, 4 under the clipped rule,
+// whose cells carry their eight weights in registers (8 cells per thread spill at 128 VGPRs).
+constexpr size_t kGsEnsResidentMaxLds = 160 * 1024;
+// Cells per thread of the resident ensemble kernel for members of rows x cols (1, 2, 4 or 8), 0 = not resident.
+inline int gs_ens_resident_cpt(long rows, long cols, int zero_halo)
+{
+    const long cells = rows * cols;
+    if (rows <= 0 || cols <= 0 || (size_t)16 * (rows + 2) * (cols + 2) > kGsEnsResidentMaxLds) return 0;
+    const long need = (cells + 1023) / 1024;
+    return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : (need <= 8 && zero_halo) ? 8 : 0;
+}
+// Most workgroups one ensemble launch dispatches (grid x 1024 threads stays below 2^32); the launchers split above.
+constexpr long kGsEnsMaxGroups = 1L << 21;
+struct GsEnsArgs {
+    const float *in_u, *in_v; // member 0, row 0, column 0 of the input planes
+    float *out_u, *out_v;
+    const GsEnsParams *params; // members entries (device)
+    int64_t first;             // member of workgroup 0 of this launch (launches are split at kGsEnsMaxGroups)
+    int32_t members;           // members in this launch
+    int32_t rows, cols;
+    int32_t zero_halo;         // gs_boundary
+};
+
 // Launchers, one set per arithmetic flavour (see gs_math in include/gs_hip.h).  Each
 // returns the hipError_t of the launch.  `name` receives a static kernel-variant label.
 #define GS_DECLARE_LAUNCHERS(SUFFIX)                                                           \
@@ -112,7 +144,9 @@ struct GsWindowArgs {
     hipError_t gs_launch_tile_##SUFFIX(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name); \
     hipError_t gs_launch_lds_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name);  \
     hipError_t gs_launch_window_##SUFFIX(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name); \
-    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl);
+    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl);                                    \
+    hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
+    hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name);
 
 GS_DECLARE_LAUNCHERS(strict)
 GS_DECLARE_LAUNCHERS(fused)
@@ -131,3 +165,7 @@ hipError_t gs_launch_fill_rect(float *row0, int32_t pitch, int32_t r0, int32_t r
 hipError_t gs_launch_pack_rows(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float *dst, hipStream_t s);
 // gs_fields_place's probe: reads `bytes` (a multiple of 16, 16-byte aligned) of x and of y and writes them back unchanged.
 hipError_t gs_launch_pair_probe(void *x, void *y, size_t bytes, hipStream_t s);
+// Species::new's pattern in every member of dense [members, rows, cols] planes: U = 1, V = 0, and U = 0, V = 1 in
+// rows [r0, r1) x columns [c0, c1).
+hipError_t gs_launch_ens_seed(float *u, float *v, uint64_t members, int32_t rows, int32_t cols, int32_t r0, int32_t r1,
+                              int32_t c0, int32_t c1, hipStream_t s);

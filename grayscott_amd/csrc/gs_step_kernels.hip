@@ -73,6 +73,7 @@
 #if !GS_TB_OP_ONLY
 #include "gs_single_step.h"
 #include "gs_lds_resident.h"
+#include "gs_ensemble.h"
 #include "gs_window_kernel.h"
 #endif
 
@@ -203,6 +204,88 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
 
 // One persistent launch of gs_run_window_k: `x.steps` time steps of a single slab, in-planes -> out-planes.
 // rpw: rows per wave (a window is at most 16 rpw rows x 128 columns); x.desc holds the caller's tiling of the grid.
+// Ensembles (gs_ensemble.h).  `fast` = 3 when EVERY member has side weights 0.5 and dt == 1 (strict only), else 0.
+// Launches are split so that none dispatches more than kGsEnsMaxGroups workgroups.
+// Resident form: `steps` time steps of every member in one launch; the result is stored in the out-planes when steps is
+// odd, else back in the in-planes.
+hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name)
+{
+    static const char *const names[2] = {"ensemble-resident/" GS_MATH_NAME, "ensemble-resident/" GS_MATH_NAME ".op"};
+    const long cells = (long)e.rows * e.cols;
+    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0) return hipErrorInvalidValue;
+    const long threads = cells >= 1024 ? 1024 : ((cells + 63) / 64) * 64; // the waves that hold cells
+    const int cpt = gs_ens_resident_cpt(e.rows, e.cols, e.zero_halo);
+    const size_t lds = (size_t)4 * (e.rows + 2) * (e.cols + 2) * sizeof(float);
+    if (!cpt || lds > kGsEnsResidentMaxLds) return hipErrorInvalidValue;
+    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
+    if (name) *name = names[fast ? 1 : 0];
+    const int zh = e.zero_halo ? 1 : 0;
+    const void *fn = nullptr;
+#define GS_ENS_RES_FN(C)                                                                                                    \
+    case C: fn = fast ? (zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, GS_MATH_FUSED ? 0 : 3, 1>)        \
+                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, GS_MATH_FUSED ? 0 : 3, 0>))       \
+                      : (zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, 0, 1>)                             \
+                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, 0, 0>)); break;
+    switch (cpt) { GS_ENS_RES_FN(1) GS_ENS_RES_FN(2) GS_ENS_RES_FN(4) }
+#undef GS_ENS_RES_FN
+    if (cpt == 8) // zero-halo rule only (gs_ens_resident_cpt)
+        fn = fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, GS_MATH_FUSED ? 0 : 3, 1>)
+                  : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, 0, 1>);
+    if (!fn) return hipErrorInvalidValue;
+    { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
+        const hipError_t err = ensure_dyn_lds(fn, lds);
+        if (err != hipSuccess) return err;
+    }
+    int to_out = steps & 1;
+    for (long m0 = 0; m0 < e.members; m0 += kGsEnsMaxGroups) {
+        GsEnsArgs args = e;
+        args.first = e.first + m0;
+        args.members = (int32_t)(e.members - m0 < kGsEnsMaxGroups ? e.members - m0 : kGsEnsMaxGroups);
+        void *kargs[] = {&args, &steps, &to_out};
+        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)args.members), dim3((unsigned)threads), kargs, lds, s);
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
+// Windowed form: K <= kGsTileMaxSteps steps of every member (in-planes -> out-planes); `shape` as gs_launch_tile's.
+hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name)
+{
+    static const char *const names[3][2] = {{"ensemble-tile32x64/" GS_MATH_NAME, "ensemble-tile32x64/" GS_MATH_NAME ".op"},
+                                            {"ensemble-tile16x64/" GS_MATH_NAME, "ensemble-tile16x64/" GS_MATH_NAME ".op"},
+                                            {"ensemble-tile64x64/" GS_MATH_NAME, "ensemble-tile64x64/" GS_MATH_NAME ".op"}};
+    static const int rpw[3] = {2, 1, 4};
+    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]))
+        return hipErrorInvalidValue;
+    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
+    if (name) *name = names[shape][fast ? 1 : 0];
+    const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
+    const long windows = ((e.rows + ho - 1) / ho) * ((e.cols + wo - 1) / wo);
+    if (windows > kGsEnsMaxGroups) return hipErrorInvalidConfiguration;
+    const void *fn = nullptr;
+#define GS_ENS_TILE_FN(S, RPW_)                                                                                   \
+    case S: fn = fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, GS_MATH_FUSED ? 0 : 3>)  \
+                      : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, 0>); break;
+    switch (shape) { GS_ENS_TILE_FN(0, 2) GS_ENS_TILE_FN(1, 1) GS_ENS_TILE_FN(2, 4) }
+#undef GS_ENS_TILE_FN
+    const size_t lds = tile_lds_bytes(rpw[shape]);
+    {
+        const hipError_t err = ensure_dyn_lds(fn, lds);
+        if (err != hipSuccess) return err;
+    }
+    const long per_launch = kGsEnsMaxGroups / windows; // members per launch
+    int wins = (int)windows;
+    for (long m0 = 0; m0 < e.members; m0 += per_launch) {
+        GsEnsArgs args = e;
+        args.first = e.first + m0;
+        args.members = (int32_t)(e.members - m0 < per_launch ? e.members - m0 : per_launch);
+        void *kargs[] = {&args, &k, &wins};
+        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)(args.members * windows)), dim3(kTileWaves * 64), kargs, lds, s);
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
 hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name)
 {
     // (5 rows per wave: 80-row windows.  The 96-row form of round 4 -- 6 rows per wave, 12 cells per lane -- spilled 43

@@ -172,8 +172,9 @@ int32_t model_rows_per_unit(const gs_ctx *ctx, int32_t rows, int32_t cols, int f
 // (launch gap, weights, window load and store) plus K steps of 0.74 / 0.585 / 1.38 us for the 32 / 16 / 64-row
 // window while every workgroup has a CU to itself; beyond 256 workgroups they run in rounds (two share a CU
 // at 0.87 of the time of two turns).  The model is within ~15 % of the measured rates from 64 x 128 to 1024 x
-// 1024 and picks the measured-best or second-best configuration on every grid of that table.
-void pick_tile_config(long rows, long cols, int *shape, int *k)
+// 1024 and picks the measured-best or second-best configuration on every grid of that table.  For an ensemble the
+// workgroups of all `members` share the rounds (gs_ensemble_run).
+void pick_tile_config(long rows, long cols, int *shape, int *k, long members)
 {
     static const int window_rows[3] = {32, 16, 64};
     static const double launch_us[3] = {3.4, 2.6, 3.7}, step_us[3] = {0.74, 0.585, 1.38};
@@ -183,7 +184,7 @@ void pick_tile_config(long rows, long cols, int *shape, int *k)
         for (int kk : ks) {
             if (2 * kk >= window_rows[sh]) continue;
             const long ho = window_rows[sh] - 2 * kk, wo = 64 - 2 * kk;
-            const long wgs = ((rows + ho - 1) / ho) * ((cols + wo - 1) / wo);
+            const long wgs = members * ((rows + ho - 1) / ho) * ((cols + wo - 1) / wo); // over a whole ensemble
             const double rounds = wgs <= 256 ? 1.0 : 0.87 * (double)((wgs + 255) / 256);
             const double us_per_step = (launch_us[sh] + kk * step_us[sh] * rounds) / kk;
             if (best == 0.0 || us_per_step < best) { best = us_per_step; *shape = sh; *k = kk; }

@@ -61,7 +61,32 @@ __global__ __launch_bounds__(256) void gs_pair_probe_k(uint4 *x, uint4 *y, size_
         y[i] = b;
     }
 }
+// Species::new's pattern in every member of an ensemble (dense [members, rows, cols] planes; 64-bit indices).
+__global__ void gs_ens_seed_k(float *u, float *v, uint64_t total, int32_t rows, int32_t cols, int32_t r0, int32_t r1,
+                              int32_t c0, int32_t c1)
+{
+    const uint64_t cells = (uint64_t)rows * (uint64_t)cols;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (uint64_t)gridDim.x * blockDim.x) {
+        const uint32_t in = (uint32_t)(i % cells); // a member has < 2^31 cells
+        const int32_t r = (int32_t)(in / (uint32_t)cols), c = (int32_t)(in - (uint32_t)r * (uint32_t)cols);
+        const bool spot = r >= r0 && r < r1 && c >= c0 && c < c1;
+        u[i] = spot ? 0.0f : 1.0f;
+        v[i] = spot ? 1.0f : 0.0f;
+    }
+}
+
 } // namespace
+
+hipError_t gs_launch_ens_seed(float *u, float *v, uint64_t members, int32_t rows, int32_t cols, int32_t r0, int32_t r1,
+                              int32_t c0, int32_t c1, hipStream_t s)
+{
+    uint64_t total = members * (uint64_t)rows * (uint64_t)cols;
+    if (total == 0) return hipSuccess;
+    const uint64_t want = (total + 255) / 256;
+    const unsigned grid = (unsigned)(want < 65536 ? want : 65536);
+    void *kargs[] = {&u, &v, &total, &rows, &cols, &r0, &r1, &c0, &c1};
+    return hipLaunchKernel(reinterpret_cast<const void *>(&gs_ens_seed_k), dim3(grid), dim3(256), kargs, 0, s);
+}
 
 hipError_t gs_launch_pair_probe(void *x, void *y, size_t bytes, hipStream_t s)
 {

@@ -38,6 +38,12 @@ def parse(argv=None):
     ap.add_argument("-n", "--nbimage", type=int, default=1000)           # main.rs:29-31
     ap.add_argument("-o", "--output", default="output.h5")               # main.rs:33-35, ui/src/lib.rs:72-75
     ap.add_argument("--output-buffer", type=int, default=2)              # main.rs:37-43
+    add_backend_args(ap)
+    return ap.parse_args(argv)
+
+
+def add_backend_args(ap: argparse.ArgumentParser) -> None:
+    """The ``--hip-*`` group (shared with ``grayscott_amd.sweep``)."""
     # The backend's own parameters, flattened into the command line as the reference flattens
     # `Simulation::CliArgs` (ui/src/lib.rs:43-45, inside the SharedArgs that simulate/src/main.rs:25-27 flattens): the names, meanings and environment
     # variables of rust/compute_hip/src/lib.rs (HipArgs).  Defaults come from the environment (HipArgs' own).
@@ -58,7 +64,6 @@ def parse(argv=None):
     be.add_argument("--hip-use-graph", type=int, default=None, help="1 = replay batches of 16 passes through a hipGraph [GS_HIP_USE_GRAPH]")
     be.add_argument("--hip-tile-shape", type=int, default=None, help="window of the LDS-window kernel: 1 = 32x64, 2 = 16x64, 3 = 64x64 [GS_HIP_TILE_SHAPE]")
     be.add_argument("--hip-pitch-pad", type=int, default=None, help="extra f32 of row pitch [GS_HIP_PITCH_PAD]")
-    return ap.parse_args(argv)
 
 
 def backend_args(args) -> HipArgs:

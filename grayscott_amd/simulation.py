@@ -489,6 +489,92 @@ class Species:
         self.access_result(lambda v, ctx: v.write_scalar_view_after(ctx, target))
 
 
+class Ensemble:
+    """``members`` independent simulations of one shape on one context (``gs_ensemble``): each member has its own
+    ``Parameters`` and its own U and V, the context's math and boundary options apply to all.  Member i evolves bit for
+    bit as a lone ``Species`` with member i's parameters would.  The ensemble tracks its current slot itself (no flips).
+    Made by ``Simulation.make_ensemble``."""
+
+    def __init__(self, context: HipContext, members: int, shape: Sequence[int]):
+        self._ctx = context
+        self._h = ctypes.c_void_p()
+        rows, cols = int(shape[0]), int(shape[1])
+        capi.check(context._lib.gs_ensemble_create(context.handle, ctypes.byref(self._h), int(members), rows, cols))
+        self.members, self._shape = int(members), (rows, cols)
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise GsError(capi.GS_ERR_INVALID, "ensemble already destroyed")
+        return self._h
+
+    def shape(self) -> Tuple[int, int]:
+        return self._shape
+
+    def set_params(self, params) -> None:
+        """One ``Parameters`` for every member, or a sequence of one per member."""
+        plist = [params] if isinstance(params, Parameters) else list(params)
+        arr = (capi.GsParams * len(plist))(*[p.to_c() for p in plist])
+        capi.check(self._ctx._lib.gs_ensemble_set_params(self._ctx.handle, self.handle, arr, len(plist)))
+
+    def seed(self) -> None:
+        """``Species::new``'s pattern in every member."""
+        capi.check(self._ctx._lib.gs_ensemble_seed(self._ctx.handle, self.handle))
+
+    def _range(self, first: int, count: Optional[int]) -> Tuple[int, int]:
+        count = self.members - first if count is None else int(count)
+        return int(first), count
+
+    def upload(self, u: Optional[np.ndarray], v: Optional[np.ndarray], first: int = 0) -> None:
+        """Overwrite members ``[first, first + len)`` from dense float32 ``[count, rows, cols]`` arrays (either may be
+        None: that species stays as it is)."""
+        arrays = [None if a is None else np.ascontiguousarray(a, np.float32) for a in (u, v)]
+        given = [a for a in arrays if a is not None]
+        if not given:
+            raise ValueError("upload needs u or v")
+        count = given[0].shape[0]
+        for a in given:
+            if a.shape != (count,) + self._shape:
+                raise AssertionError(f"upload shape {a.shape} != {(count,) + self._shape}")
+        ptr = [None if a is None else a.ctypes.data_as(ctypes.c_void_p) for a in arrays]
+        capi.check(self._ctx._lib.gs_ensemble_upload(self._ctx.handle, self.handle, int(first), count, ptr[0], ptr[1]))
+
+    def _download(self, species: int, first: int, count: Optional[int]) -> np.ndarray:
+        first, count = self._range(first, count)
+        out = np.empty((count,) + self._shape, np.float32)
+        capi.check(self._ctx._lib.gs_ensemble_download(self._ctx.handle, self.handle, first, count, species,
+                                                       out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def result_views(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """V of members ``[first, first + count)`` as ``[count, rows, cols]`` (blocking)."""
+        return self._download(1, first, count)
+
+    def u_views(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """U of members ``[first, first + count)`` as ``[count, rows, cols]`` (blocking)."""
+        return self._download(0, first, count)
+
+    def prepare_steps(self, steps: int) -> None:
+        """Enqueue ``steps`` steps of every member and return (``gs_ensemble_run``); ``context.sync()`` waits."""
+        capi.check(self._ctx._lib.gs_ensemble_run(self._ctx.handle, self.handle, int(steps)))
+
+    def perform_steps(self, steps: int) -> None:
+        """``steps`` steps of every member, done on return."""
+        self.prepare_steps(steps)
+        self._ctx.sync()
+
+    def destroy(self) -> None:
+        if self._h and self._ctx._h:
+            self._ctx._lib.gs_ensemble_destroy(self._ctx._h, self._h)
+        self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
 class Simulation:
     """The backend: ``SimulateBase + SimulateCreate + Simulate``."""
 
@@ -515,6 +601,21 @@ class Simulation:
             cells = int(shape[0]) * int(shape[1]) // max(1, args.world)
             place_candidates = args.place_candidates if len(args.devices) == 1 and cells >= PLACE_MIN_CELLS else 0
         return Species.new(self.context, shape, place_candidates)
+
+    def make_ensemble(self, shape: Sequence[int], params, seed: bool = True, members: Optional[int] = None) -> Ensemble:
+        """An ``Ensemble`` of grids of ``shape``: ``params`` is a sequence of ``Parameters``, one per member, or one
+        ``Parameters`` for all ``members`` (default 1).  ``seed``: ``Species::new``'s pattern in every member, else zeros."""
+        plist = [params] if isinstance(params, Parameters) else list(params)
+        if not plist:
+            raise ValueError("an ensemble needs at least one member")
+        n = len(plist) if len(plist) > 1 or members is None else int(members)
+        if members is not None and n != int(members):
+            raise ValueError(f"{len(plist)} parameter sets for {members} members")
+        e = Ensemble(self.context, n, shape)
+        e.set_params(plist)
+        if seed:
+            e.seed()
+        return e
 
     def perform_steps(self, species: Species, steps: int) -> None:
         """``Simulate::perform_steps`` (lib.rs:48-58): ``steps`` steps; on return they are DONE and

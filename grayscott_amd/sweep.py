@@ -1,0 +1,108 @@
+"""Parameter sweep on the HIP backend: one ensemble member per (feed, kill) pair, all advanced in shared launches
+(``gs_ensemble_run``).
+
+    python -m grayscott_amd.sweep --feed 0.01:0.06:8 --kill 0.04:0.07:8 -r 256 -c 512 -s 2000 -o sweep.h5
+
+``--feed A:B:N`` / ``--kill A:B:N`` are N evenly spaced values from A to B (both included).  Members are in kill-major
+order: member ``i_kill * N_feed + i_feed``.  Every member starts from ``Species::new``'s pattern and runs ``-s`` steps
+with the shared flags of ``simulate`` that still apply (``-r -c -t`` and the ``--hip-*`` group).  Output: the final V of
+every member as the dataset ``matrix[members, rows, cols]`` f32 -- the layout the reference's ``simulate`` writes, one
+image per member, so its ``data-to-pics`` renders one picture per (F, k) pair -- and a JSON sidecar (``-o``'s name with
+``.json``) listing ``index``, ``feed`` and ``kill`` of every member.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+from typing import List, Tuple
+
+import numpy as np
+
+from . import hdf5_min
+from .simulate import add_backend_args, backend_args
+from .simulation import Parameters, Simulation
+
+
+def value_range(text: str) -> List[float]:
+    """``A:B:N`` -> N evenly spaced values from A to B (N = 1: A alone)."""
+    parts = text.split(":")
+    if len(parts) != 3:
+        raise argparse.ArgumentTypeError(f"expected A:B:N, got {text!r}")
+    a, b, n = float(parts[0]), float(parts[1]), int(parts[2])
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"N must be at least 1 in {text!r}")
+    return [a] if n == 1 else [float(x) for x in np.linspace(a, b, n)]
+
+
+def parse(argv=None):
+    ap = argparse.ArgumentParser(prog="sweep", description="Gray-Scott parameter sweep, one ensemble member per (feed, kill)")
+    ap.add_argument("--feed", type=value_range, required=True, metavar="A:B:N", help="feed rates")
+    ap.add_argument("--kill", type=value_range, required=True, metavar="A:B:N", help="kill rates")
+    ap.add_argument("-s", "--steps", type=int, default=1000, help="steps per member")
+    ap.add_argument("-r", "--nbrow", type=int, default=1080)
+    ap.add_argument("-c", "--nbcol", type=int, default=1920)
+    ap.add_argument("-t", "--deltat", type=float, default=None)
+    ap.add_argument("-o", "--output", default="sweep.h5")
+    add_backend_args(ap)
+    return ap.parse_args(argv)
+
+
+def members(args) -> List[Tuple[int, float, float]]:
+    """(index, feed, kill) of every member, kill-major."""
+    return [(i * len(args.feed) + j, f, k) for i, k in enumerate(args.kill) for j, f in enumerate(args.feed)]
+
+
+def member_params(args) -> List[Parameters]:
+    out = []
+    for _, feed, kill in members(args):
+        p = Parameters(feed_rate=feed, kill_rate=kill)
+        if args.deltat is not None:
+            p.time_step = args.deltat
+        out.append(p)
+    return out
+
+
+def sidecar_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".json"
+
+
+def run(args) -> dict:
+    if args.steps < 0:
+        raise ValueError("--steps must be at least 0")
+    shape = (args.nbrow, args.nbcol)
+    params = member_params(args)
+    sim = Simulation.new(params[0], backend_args(args))
+    ens = sim.make_ensemble(shape, params)
+    t0 = time.perf_counter()
+    ens.perform_steps(args.steps)
+    elapsed = time.perf_counter() - t0
+    out = hdf5_min.create(args.output, (len(params),) + shape)
+    per_chunk = max(1, (256 << 20) // (4 * shape[0] * shape[1]))  # download in pieces of ~256 MB
+    for first in range(0, len(params), per_chunk):
+        count = min(per_chunk, len(params) - first)
+        out[first:first + count] = ens.result_views(first, count)
+    out.flush()
+    del out
+    with open(sidecar_path(args.output), "w") as f:
+        json.dump({"shape": list(shape), "steps": args.steps,
+                   "members": [{"index": i, "feed": feed, "kill": kill} for i, feed, kill in members(args)]}, f, indent=1)
+    kernel, _ = sim.context.info()
+    ens.destroy()
+    sim.context.close()
+    cells = shape[0] * shape[1]
+    return {"members": len(params), "shape": shape, "steps": args.steps, "seconds": elapsed, "kernel": kernel,
+            "mcells_steps_per_s": len(params) * cells * args.steps / elapsed / 1e6 if elapsed > 0 else 0.0}
+
+
+def main(argv=None) -> int:
+    info = run(parse(argv))
+    print("sweep: {members} members x {steps} steps on {shape[0]}x{shape[1]} in {seconds:.3f} s with {kernel} "
+          "({mcells_steps_per_s:.0f} Mcells*steps/s)".format(**info), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

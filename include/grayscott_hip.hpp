@@ -300,6 +300,68 @@ class Species {
     Evolving u_, v_;
 };
 
+// Ensemble (gs_ensemble_*): `members` independent grids of one shape on one context, each with its own Parameters and its
+// own U and V; member i evolves bit for bit as a lone Species with its parameters would.  The ensemble tracks its current
+// slot itself.  Host arrays are dense [count, rows, cols].
+class Ensemble {
+  public:
+    // members with params[i] each (params.size() == members) or params[0] for all (params.size() == 1); seeded with
+    // Species::new's pattern when `seed`, else zeros
+    Ensemble(Context ctx, std::size_t members, Shape shape, const std::vector<Parameters> &params, bool seed = true)
+        : ctx_(std::move(ctx)), members_(members), shape_(shape)
+    {
+        check(gs_ensemble_create(ctx_->get(), &e_, members, shape[0], shape[1]));
+        try {
+            set_params(params);
+            if (seed) check(gs_ensemble_seed(ctx_->get(), e_));
+        } catch (...) {
+            gs_ensemble_destroy(ctx_->get(), e_);
+            throw;
+        }
+    }
+    ~Ensemble()
+    {
+        if (e_) gs_ensemble_destroy(ctx_->get(), e_);
+    }
+    Ensemble(const Ensemble &) = delete;
+    Ensemble &operator=(const Ensemble &) = delete;
+    Ensemble(Ensemble &&o) noexcept : ctx_(std::move(o.ctx_)), e_(o.e_), members_(o.members_), shape_(o.shape_) { o.e_ = nullptr; }
+
+    std::size_t members() const { return members_; }
+    Shape shape() const { return shape_; }
+    gs_ensemble *raw() const { return e_; }
+    void set_params(const std::vector<Parameters> &params)
+    {
+        std::vector<gs_params> c;
+        for (const Parameters &p : params) c.push_back(p.to_c());
+        check(gs_ensemble_set_params(ctx_->get(), e_, c.data(), c.size()));
+    }
+    // u or v may be null: that species stays as it is
+    void upload(std::size_t first, std::size_t count, const float *u, const float *v)
+    {
+        check(gs_ensemble_upload(ctx_->get(), e_, first, count, u, v));
+    }
+    // species 0 = U, 1 = V of members [first, first + count)
+    std::vector<float> download(std::size_t first, std::size_t count, int species = 1) const
+    {
+        std::vector<float> out(count * shape_[0] * shape_[1]);
+        check(gs_ensemble_download(ctx_->get(), e_, first, count, species, out.data()));
+        return out;
+    }
+    void prepare_steps(std::size_t steps) { check(gs_ensemble_run(ctx_->get(), e_, steps)); }
+    void perform_steps(std::size_t steps)
+    {
+        prepare_steps(steps);
+        ctx_->sync();
+    }
+
+  private:
+    Context ctx_;
+    gs_ensemble *e_ = nullptr;
+    std::size_t members_;
+    Shape shape_;
+};
+
 class Simulation {
   public:
     using CliArgs = HipArgs;
@@ -344,6 +406,11 @@ class Simulation {
         species.flip();
     }
     const Context &context() const { return context_; }
+    // an Ensemble of params.size() members (Species::new's pattern in each)
+    Ensemble make_ensemble(Shape shape, const std::vector<Parameters> &params) const
+    {
+        return Ensemble(context_, params.size(), shape, params);
+    }
 
   private:
     explicit Simulation(Context c) : context_(std::move(c)) {}

@@ -387,6 +387,32 @@ int32_t gs_ctx_set_pass_timing(gs_ctx *ctx, int32_t passes);
  * kernel launches so far. */
 int32_t gs_ctx_info(const gs_ctx *ctx, char *kernel_name, size_t cap, uint64_t *launches);
 
+/* Ensembles: `members` independent simulations of one shape rows x cols, advanced in shared launches -- a sweep over
+ * (feed, kill), diffusion rates, dt or stencils.  An ensemble lives on a context of ONE slab in one process
+ * (GS_ERR_UNSUPPORTED otherwise); every member has its own gs_params and its own U and V, the context's math and boundary
+ * options apply to all of them.  After gs_ensemble_run(steps), member i is bit for bit what gs_run makes of a lone
+ * Species with member i's parameters and initial state.  The ensemble owns its double buffer and tracks which slot
+ * holds the newest state: callers never flip.  Host arrays are dense [count, rows, cols] f32.
+ *   create        all members zero, every member with the context's parameters
+ *   set_params    `count` = members (one entry per member) or 1 (the same for all); GS_MATH_FUSED refuses weights that
+ *                 are not 0 or a power of two (GS_ERR_UNSUPPORTED), as gs_ctx_create does.  Waits for enqueued work.
+ *   seed          Species::new's pattern (data/src/concentration/mod.rs:36-59) in every member
+ *   upload        members [first, first + count); `u` or `v` may be NULL to leave that species as it is.  Blocking.
+ *   download      species 0 = U, 1 = V of members [first, first + count).  Blocking.
+ *   run           asynchronous, like gs_run (gs_sync waits).  Members of at most 4096 cells (8192 under the zero-halo
+ *                 rule, and 160 KiB of LDS) stay in one workgroup's LDS for the whole call ("ensemble-resident"); larger
+ *                 ones advance up to 8 steps per launch on LDS-resident windows ("ensemble-tile32x64" ...), with the
+ *                 window and steps per launch chosen over the workgroups of the whole ensemble.  gs_ctx_info names it. */
+typedef struct gs_ensemble gs_ensemble;
+int32_t gs_ensemble_create(gs_ctx *ctx, gs_ensemble **out, uint64_t members, uint64_t rows, uint64_t cols);
+int32_t gs_ensemble_destroy(gs_ctx *ctx, gs_ensemble *e);
+int32_t gs_ensemble_shape(const gs_ensemble *e, uint64_t *members, uint64_t *rows, uint64_t *cols);
+int32_t gs_ensemble_set_params(gs_ctx *ctx, gs_ensemble *e, const gs_params *params, uint64_t count);
+int32_t gs_ensemble_seed(gs_ctx *ctx, gs_ensemble *e);
+int32_t gs_ensemble_upload(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *u, const float *v);
+int32_t gs_ensemble_download(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, int32_t species, float *host);
+int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps);
+
 /* Measurement hook, not for bindings (tools/rccl_under_load.py): the ghost-row exchange's transport on ONE GPU while the
  * caller keeps the chip busy or idle.  mode 0: a one-rank RCCL communicator, `messages` ncclSend / ncclRecv pairs of
  * `floats` f32 to itself in one group; mode 1: the same bytes as device-to-device copies (the in-process chain's route);
