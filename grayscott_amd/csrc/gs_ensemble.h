@@ -6,6 +6,8 @@
 //   gs_ens_tile_k      K <= 8 steps per launch on LDS-resident windows (gs_run_tile_k with a member coordinate): grid =
 //                      members x windows per member; a window never reads across its member's edge -- cells outside
 //                      the member are zeros, exactly as cells outside the grid are for a lone Species.
+// Under the periodic rule (zero_halo = 2) the resident form keeps its ring filled with the opposite edge (ring_put) and
+// the windowed form is gs_ens_tile_pk, whose windows read their member's cells at wrapped coordinates.
 // A workgroup belongs to ONE member, so its parameters are wave-uniform: they are read from the device table with scalar
 // loads (constant address space) into SGPRs.  Member offsets are 64-bit.
 // Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED and the GS_SUFFIX / GS_TAP
@@ -45,67 +47,94 @@ __device__ __forceinline__ GsStepArgs ens_member_args(const GsEnsArgs &e, int64_
 // Resident form.  The LDS layout and the step loop are gs_run_resident_k's: 4 planes of (rows + 2) x (cols + 2) floats
 // with a ring of zeros, thread t owning cells t, t + blockDim.x, ... (CPT of them at most).  The host sizes the
 // workgroup to the waves the member's cells need (an 8 x 16 member: 2 waves), so small members share a CU.
+// (The body is a macro so that the kernel of the clipped and zero-halo rules keeps its code: as a function called from two
+// kernels it compiled one instruction apart.)
+#define GS_ENS_RESIDENT_BODY(CPT, FAST, ZH)                                                                                  \
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); /* half_diff: MODE.IEEE = 0 */             \
+    extern __shared__ float lds[];                                                                                           \
+    const GsStepArgs a = ens_member_args(e, e.first + (int64_t)blockIdx.x);                                                  \
+    const int cells = a.rows * a.cols, cols = a.cols, P = cols + 2, plane = (a.rows + 2) * P;                                \
+    const int nthreads = (int)blockDim.x;                                                                                    \
+    for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f; /* the rings (and everything else) */             \
+    __syncthreads();                                                                                                         \
+    int o[CPT], rc[CPT]; /* rc (ZH = 2, the periodic rule's ring: ring_put): row << 16 | column */                           \
+    bool live[CPT];                                                                                                          \
+    float E[CPT][8];                                                                                                         \
+_Pragma("unroll")                                                                                                            \
+    for (int k = 0; k < CPT; ++k) {                                                                                          \
+        const int idx = (int)threadIdx.x + k * nthreads;                                                                     \
+        live[k] = idx < cells;                                                                                               \
+        const int r = live[k] ? idx / cols : 0, c = live[k] ? idx - r * cols : 0;                                            \
+        o[k] = (r + 1) * P + c + 1;                                                                                          \
+        if (ZH == 0) border_weights(a, r, c, E[k]);                                                                          \
+        if constexpr (ZH == 2) rc[k] = r << 16 | c;                                                                          \
+        if (live[k]) {                                                                                                       \
+            lds[o[k]] = a.in_u[idx];                                                                                         \
+            lds[2 * plane + o[k]] = a.in_v[idx];                                                                             \
+            if (ZH == 2 && on_border(a.rows, cols, r, c)) {                                                                  \
+                ring_put(lds, P, a.rows, cols, r, c, lds[o[k]]);                                                             \
+                ring_put(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);                                     \
+            }                                                                                                                \
+        }                                                                                                                    \
+    }                                                                                                                        \
+    __syncthreads();                                                                                                         \
+    int cur = 0;                                                                                                             \
+    for (int s = 0; s < steps; ++s) {                                                                                        \
+        const float *su = lds + cur * plane, *sv = lds + (2 + cur) * plane;                                                  \
+        float *du = lds + (cur ^ 1) * plane, *dv = lds + (2 + (cur ^ 1)) * plane;                                            \
+_Pragma("unroll")                                                                                                            \
+        for (int k = 0; k < CPT; ++k) {                                                                                      \
+            if (!live[k]) continue;                                                                                          \
+            Row3 R[3];                                                                                                       \
+_Pragma("unroll")                                                                                                            \
+            for (int i = 0; i < 3; ++i) {                                                                                    \
+                const int q = o[k] + (i - 1) * P;                                                                            \
+                R[i].u[0] = su[q - 1]; R[i].u[1] = su[q]; R[i].u[2] = su[q + 1];                                             \
+                R[i].v[0] = sv[q - 1]; R[i].v[1] = sv[q]; R[i].v[2] = sv[q + 1];                                             \
+            }                                                                                                                \
+            float nu, nv;                                                                                                    \
+            if (ZH == 0)                                                                                                     \
+                cell_border<FAST>(a, E[k], R[0], R[1], R[2], nu, nv);                                                        \
+            else                                                                                                             \
+                cell<false, FAST, Row3>(a, R[0], R[1], R[2], 1, true, true, 0u, 0u, nu, nv);                                 \
+            du[o[k]] = nu;                                                                                                   \
+            dv[o[k]] = nv;                                                                                                   \
+            if constexpr (ZH == 2) {                                                                                         \
+                /* (opaque: the border tests of all CPT cells, hoisted out of the step loop, would hold SGPR lane masks) */  \
+                int x = rc[k];                                                                                               \
+                asm volatile("" : "+v"(x));                                                                                  \
+                const int r = x >> 16, c = x & 0xffff;                                                                       \
+                if (on_border(a.rows, cols, r, c)) {                                                                         \
+                    ring_put(du, P, a.rows, cols, r, c, nu);                                                                 \
+                    ring_put(dv, P, a.rows, cols, r, c, nv);                                                                 \
+                }                                                                                                            \
+            }                                                                                                                \
+        }                                                                                                                    \
+        __syncthreads();                                                                                                     \
+        cur ^= 1;                                                                                                            \
+    }                                                                                                                        \
+    float *gu = to_out ? a.out_u : const_cast<float *>(a.in_u);                                                              \
+    float *gv = to_out ? a.out_v : const_cast<float *>(a.in_v);                                                              \
+_Pragma("unroll")                                                                                                            \
+    for (int k = 0; k < CPT; ++k)                                                                                            \
+        if (live[k]) {                                                                                                       \
+            const int idx = (int)threadIdx.x + k * nthreads;                                                                 \
+            gu[idx] = lds[cur * plane + o[k]];                                                                               \
+            gv[idx] = lds[(2 + cur) * plane + o[k]];                                                                         \
+        }
+
 template <int CPT, int FAST, int ZH>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_k)(GsEnsArgs e, int steps, int to_out)
 {
-    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
-    extern __shared__ float lds[];
-    const GsStepArgs a = ens_member_args(e, e.first + (int64_t)blockIdx.x);
-    const int cells = a.rows * a.cols, cols = a.cols, P = cols + 2, plane = (a.rows + 2) * P;
-    const int nthreads = (int)blockDim.x;
-    for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f; // the rings (and everything else)
-    __syncthreads();
-    int o[CPT];
-    bool live[CPT];
-    float E[CPT][8];
-#pragma unroll
-    for (int k = 0; k < CPT; ++k) {
-        const int idx = (int)threadIdx.x + k * nthreads;
-        live[k] = idx < cells;
-        const int r = live[k] ? idx / cols : 0, c = live[k] ? idx - r * cols : 0;
-        o[k] = (r + 1) * P + c + 1;
-        if (ZH == 0) border_weights(a, r, c, E[k]);
-        if (live[k]) {
-            lds[o[k]] = a.in_u[idx];
-            lds[2 * plane + o[k]] = a.in_v[idx];
-        }
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int s = 0; s < steps; ++s) {
-        const float *su = lds + cur * plane, *sv = lds + (2 + cur) * plane;
-        float *du = lds + (cur ^ 1) * plane, *dv = lds + (2 + (cur ^ 1)) * plane;
-#pragma unroll
-        for (int k = 0; k < CPT; ++k) {
-            if (!live[k]) continue;
-            Row3 R[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int q = o[k] + (i - 1) * P;
-                R[i].u[0] = su[q - 1]; R[i].u[1] = su[q]; R[i].u[2] = su[q + 1];
-                R[i].v[0] = sv[q - 1]; R[i].v[1] = sv[q]; R[i].v[2] = sv[q + 1];
-            }
-            float nu, nv;
-            if (ZH == 0)
-                cell_border<FAST>(a, E[k], R[0], R[1], R[2], nu, nv);
-            else
-                cell<false, FAST, Row3>(a, R[0], R[1], R[2], 1, true, true, 0u, 0u, nu, nv);
-            du[o[k]] = nu;
-            dv[o[k]] = nv;
-        }
-        __syncthreads();
-        cur ^= 1;
-    }
-    float *gu = to_out ? a.out_u : const_cast<float *>(a.in_u);
-    float *gv = to_out ? a.out_v : const_cast<float *>(a.in_v);
-#pragma unroll
-    for (int k = 0; k < CPT; ++k)
-        if (live[k]) {
-            const int idx = (int)threadIdx.x + k * nthreads;
-            gu[idx] = lds[cur * plane + o[k]];
-            gv[idx] = lds[(2 + cur) * plane + o[k]];
-        }
+    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH)
 }
+// The periodic rule's instances (GsEnsArgs::zero_halo = 2), kernels of their own name.
+template <int CPT, int FAST>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_pk)(GsEnsArgs e, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 2)
+}
+#undef GS_ENS_RESIDENT_BODY
 
 // Windowed form: gs_run_tile_k's load, K steps (tile_steps) and store, for window `blockIdx.x % windows` of member
 // `first + blockIdx.x / windows`.
@@ -135,6 +164,7 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_k)(GsEn
         v[i] = in ? a.in_v[g] : 0.0f;
     }
     const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;
+    // (a.zero_halo is 0 or 1 here: the periodic rule runs gs_ens_tile_pk)
     if (!edge)
         tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
     else if (a.zero_halo)
@@ -153,6 +183,17 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_k)(GsEn
             }
         }
     }
+}
+
+// The periodic rule's windowed form (GsEnsArgs::zero_halo = 2): tile_window_periodic for window `blockIdx.x % windows`
+// of member `first + blockIdx.x / windows`; a window wraps around its own member only.
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_pk)(GsEnsArgs e, int K, int windows)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
+    tile_window_periodic<RPW, FAST>(ens_member_args(e, e.first + m), lds, K, win);
 }
 
 } // namespace

@@ -64,8 +64,10 @@ struct GsStepArgs {
     // workgroups is renumbered so that the xcd_m workgroups an XCD gets are consecutive ones -- neighbours in the
     // grid, whose overlapping rows and columns then meet in that XCD's L2.
     int32_t xcd_m, xcd_first;
-    // Boundary rule on global edges: 0 = naive's clipped window (weights anchored at the window's
-    // top-left corner), 1 = full window with zeros outside the grid (gs_boundary in gs_hip.h).
+    // Boundary rule on global edges (gs_boundary in gs_hip.h): 0 = naive's clipped window (weights anchored at the
+    // window's top-left corner), 1 = full window with zeros outside the grid, 2 = periodic (single slab only; the
+    // launchers run the rule's own kernels, gs_*_pk and the resident kernels' ZH = 2 instances: a kernel that tests
+    // this field for truth only ever sees 0 or 1).
     int32_t zero_halo;
     float w[3][3];         // stencil weights, row-major (parameters.rs:87-88)
     float du, dv, feed, feed_plus_kill, dt;
@@ -115,12 +117,13 @@ struct GsEnsParams {
 // whose cells carry their eight weights in registers (8 cells per thread spill at 128 VGPRs).
 constexpr size_t kGsEnsResidentMaxLds = 160 * 1024;
 // Cells per thread of the resident ensemble kernel for members of rows x cols (1, 2, 4 or 8), 0 = not resident.
-inline int gs_ens_resident_cpt(long rows, long cols, int zero_halo)
+// boundary: gs_boundary -- the periodic rule (2) has the zero-halo rule's capacity: no per-cell weights either.
+inline int gs_ens_resident_cpt(long rows, long cols, int boundary)
 {
     const long cells = rows * cols;
     if (rows <= 0 || cols <= 0 || (size_t)16 * (rows + 2) * (cols + 2) > kGsEnsResidentMaxLds) return 0;
     const long need = (cells + 1023) / 1024;
-    return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : (need <= 8 && zero_halo) ? 8 : 0;
+    return need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : (need <= 8 && boundary != 0) ? 8 : 0;
 }
 // Most workgroups one ensemble launch dispatches (grid x 1024 threads stays below 2^32); the launchers split above.
 constexpr long kGsEnsMaxGroups = 1L << 21;
@@ -131,7 +134,7 @@ struct GsEnsArgs {
     int64_t first;             // member of workgroup 0 of this launch (launches are split at kGsEnsMaxGroups)
     int32_t members;           // members in this launch
     int32_t rows, cols;
-    int32_t zero_halo;         // gs_boundary
+    int32_t zero_halo;         // gs_boundary: 0 clipped, 1 zero halo, 2 periodic
 };
 
 // Launchers, one set per arithmetic flavour (see gs_math in include/gs_hip.h).  Each
@@ -144,7 +147,7 @@ struct GsEnsArgs {
     hipError_t gs_launch_tile_##SUFFIX(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name); \
     hipError_t gs_launch_lds_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name);  \
     hipError_t gs_launch_window_##SUFFIX(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name); \
-    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl);                                    \
+    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary);                                    \
     hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
     hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name);
 
@@ -153,8 +156,9 @@ GS_DECLARE_LAUNCHERS(fused)
 
 // Entry points of the parameter-specialised temporal-blocking kernels (strict flavour only; their
 // own translation unit, see gs_step_kernels.hip: GS_TB_OP_ONLY).  nullptr for an unknown variant.
-// wg: waves per workgroup, 4 or 16 (the fair-progress form of one-round launches: K = 4, cpl 1 or 2 only).
-const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg);
+// wg: waves per workgroup, 4 or 16 (the fair-progress form of one-round launches: K = 4, cpl 1 or 2 only);
+// per: the periodic rule's form (gs_step_tb_pk and kin).
+const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, bool per = false);
 
 // Plane utilities (math-agnostic, defined once in gs_util_kernels.hip).
 hipError_t gs_launch_colormap(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float scale,

@@ -65,12 +65,33 @@ __device__ __forceinline__ void border_weights(const GsStepArgs &a, int r, int c
     }
 }
 
+// Periodic rule (ZH = 2) in an LDS plane with a ring around the grid (gs_run_resident_pk, gs_ens_resident_pk): the ring
+// holds copies of the opposite edge, so the interior code reads the wrapped neighbours at the same fixed offsets.  A
+// cell of the grid's first or last row or column (r, c; `x` its value, `p` the plane, P its pitch) writes itself into
+// the ring cells that copy it -- up to 8 of them on grids of one row or column, where the copies of a cell are its own
+// neighbours.  Every ring cell has exactly one source: no two lanes write one word.
+__device__ __forceinline__ void ring_put(float *p, int P, int rows, int cols, int r, int c, float x)
+{
+    const int rs[3] = {r + 1, r == 0 ? rows + 1 : -1, r == rows - 1 ? 0 : -1};
+    const int cs[3] = {c + 1, c == 0 ? cols + 1 : -1, c == cols - 1 ? 0 : -1};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if ((i || j) && rs[i] >= 0 && cs[j] >= 0) p[rs[i] * P + cs[j]] = x;
+}
+__device__ __forceinline__ bool on_border(int rows, int cols, int r, int c)
+{
+    return r == 0 || r == rows - 1 || c == 0 || c == cols - 1;
+}
+
 // The grid lives in LDS with a ring of zeros around it (pitch cols + 2, rows + 2 rows; two buffers per
 // species): every neighbour is addressable at a fixed offset and a neighbour outside the grid reads 0.
 // That IS the zero-halo rule (interior code for every cell, ZH = 1); for the clipped-window rule every cell
-// carries its own eight weights (cell_border).  No selects, no divergent branches in the step loop.
+// carries its own eight weights (cell_border); for the periodic rule (ZH = 2) the cells on the border keep the ring
+// filled with the opposite edge's values (ring_put).  No selects in the step loop.
 template <int FAST, int ZH>
-__global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_k)(GsStepArgs a, int steps, int to_out)
+__device__ __forceinline__ void run_resident(const GsStepArgs &a, int steps, int to_out)
 {
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
     extern __shared__ float lds[];
@@ -81,7 +102,7 @@ __global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_k)
     const int nthreads = (int)blockDim.x; // as many waves as hold cells, at most kResidentThreads (the launcher)
     for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f;               // the rings (and everything else)
     __syncthreads();
-    int o[CPT], g[CPT];
+    int o[CPT], g[CPT], rc[CPT]; // rc (ZH = 2): row << 16 | column
     bool live[CPT];
     float E[CPT][8];
 #pragma unroll
@@ -92,9 +113,14 @@ __global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_k)
         o[k] = (r + 1) * P + c + 1;
         g[k] = r * a.pitch + c;
         if (ZH == 0) border_weights(a, r, c, E[k]);
+        if (ZH == 2) rc[k] = r << 16 | c;
         if (live[k]) {
             lds[o[k]] = a.in_u[g[k]];
             lds[2 * plane + o[k]] = a.in_v[g[k]];
+            if (ZH == 2 && on_border(a.rows, cols, r, c)) {
+                ring_put(lds, P, a.rows, cols, r, c, lds[o[k]]);
+                ring_put(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);
+            }
         }
     }
     __syncthreads();
@@ -119,6 +145,16 @@ __global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_k)
                 cell<false, FAST, Row3>(a, R[0], R[1], R[2], 1, true, true, 0u, 0u, nu, nv);
             du[o[k]] = nu;
             dv[o[k]] = nv;
+            if (ZH == 2) {
+                // (opaque: the border tests of all CPT cells, hoisted out of the step loop, would hold SGPR lane masks)
+                int x = rc[k];
+                asm volatile("" : "+v"(x));
+                const int r = x >> 16, c = x & 0xffff;
+                if (on_border(a.rows, cols, r, c)) {
+                    ring_put(du, P, a.rows, cols, r, c, nu);
+                    ring_put(dv, P, a.rows, cols, r, c, nv);
+                }
+            }
         }
         __syncthreads();
         cur ^= 1;
@@ -131,6 +167,17 @@ __global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_k)
             gu[g[k]] = lds[cur * plane + o[k]];
             gv[g[k]] = lds[(2 + cur) * plane + o[k]];
         }
+}
+template <int FAST, int ZH>
+__global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_k)(GsStepArgs a, int steps, int to_out)
+{
+    run_resident<FAST, ZH>(a, steps, to_out);
+}
+// The periodic rule's instance (GsStepArgs::zero_halo = 2), a kernel of its own name.
+template <int FAST>
+__global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_pk)(GsStepArgs a, int steps, int to_out)
+{
+    run_resident<FAST, 2>(a, steps, to_out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -259,7 +306,8 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_run_tile_k)(GsSt
         v[i] = in ? a.in_v[g] : 0.0f;
     }
     // A window inside the grid runs code without any bounds logic; the others the general flavour, one
-    // instantiation per boundary rule (as gs_step_tb_k).
+    // instantiation per boundary rule (as gs_step_tb_k).  (a.zero_halo is 0 or 1 here: the periodic rule runs
+    // gs_run_tile_pk.)
     const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;
     if (!edge)
         tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
@@ -279,6 +327,53 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_run_tile_k)(GsSt
             }
         }
     }
+}
+
+// The periodic rule's form (GsStepArgs::zero_halo = 2) of window `win`: every cell of the window is loaded from its
+// coordinates modulo the grid's -- a window that crosses an edge holds a piece of the periodic extension of the grid, on
+// small grids the grid several times over -- and every cell runs the interior code (tile_steps<EDGE = false>).
+template <int RPW, int FAST>
+__device__ __forceinline__ void tile_window_periodic(const GsStepArgs &a, float *lds, int K, int win)
+{
+    constexpr int H = tile_rows(RPW);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int HO = H - 2 * K, WO = kTileCols - 2 * K; // output rows / columns per window
+    const int tiles_c = (a.cols + WO - 1) / WO;
+    const int tr = win / tiles_c, tc = win - tr * tiles_c;
+    const int gr0 = tr * HO - K, gc0 = tc * WO - K; // global coordinates of window cell (0, 0)
+    const int gr = gr0 + wave * RPW, gc = gc0 + lane; // this lane's first cell
+    float u[RPW], v[RPW];
+    int cc = gc % a.cols;
+    if (cc < 0) cc += a.cols;
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+        int rr = (gr + i) % a.rows;
+        if (rr < 0) rr += a.rows;
+        const ptrdiff_t g = (ptrdiff_t)rr * a.pitch + cc;
+        u[i] = a.in_u[g];
+        v[i] = a.in_v[g];
+    }
+    tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
+    // store the window shrunk by K, where it lies in the grid
+    if (lane >= K && lane < kTileCols - K && gc < a.cols) {
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) {
+            const int wr = wave * RPW + i;
+            if (wr >= K && wr < H - K && gr + i < a.rows) {
+                const ptrdiff_t g = (ptrdiff_t)(gr + i) * a.pitch + gc;
+                a.out_u[g] = u[i];
+                a.out_v[g] = v[i];
+            }
+        }
+    }
+}
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_run_tile_pk)(GsStepArgs a, int K)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    tile_window_periodic<RPW, FAST>(a, lds, K, (int)blockIdx.x);
 }
 
 } // namespace

@@ -323,7 +323,12 @@ __host__ __device__ constexpr int tb_halo_floats(int k, bool cross) { return cro
 
 // EDGE: 0 = interior unit; 1 = general path; 2 / 3 = strip on the grid's left / right edge that touches neither its
 // top nor its bottom (cell<2> / cell<3>); 4 = interior strip that touches the top or bottom edge: interior code for
-// every row but the grid's first / last, which take the general cell (wave-uniform branch per level-row).
+// every row but the grid's first / last, which take the general cell (wave-uniform branch per level-row); 5 = a unit
+// on an edge under the periodic rule: every level-0 row and column is read at its index modulo the grid's rows /
+// columns, so the unit's window holds a piece of the periodic extension of the grid and every cell runs the interior
+// code (no edge selects).  The row wrap is wave-uniform (a scalar base address per fetch); the column wrap is per lane,
+// computed once per unit, and a lane whose column group is not one aligned piece of a row after wrapping (cols %
+// CPL != 0: the group that straddles the wrap from cols - 1 to 0, and the lanes behind it) loads column by column.
 template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false>
 __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, int strip, int lane,
                                          const FairBoard &fb GS_TRACE_PARAM)
@@ -332,8 +337,9 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
     const int c = strip * W + (lane - S) * CPL; // first column of this lane (may be negative)
     constexpr bool COLS = EDGE == 1 || EDGE == 2 || EDGE == 3; // the strip may leave the grid's columns
     constexpr bool ROWS = EDGE == 1 || EDGE == 4;              // the unit may touch the grid's first / last row
+    constexpr bool PER = EDGE == 5;                            // periodic rule, wrapped addresses
     const bool load_ok = !COLS || (c >= 0 && c < a.pitch);
-    const bool store_ok = (lane >= S) && (lane < 64 - S) && (!COLS || c < a.pitch);
+    const bool store_ok = (lane >= S) && (lane < 64 - S) && (!(COLS || PER) || c < a.pitch);
     const ptrdiff_t pitch = a.pitch;
 
     // Level-0 rows needed: [ur0 - K, ur1 + K) clipped to the rows that exist: the slab's own
@@ -346,8 +352,40 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
     const __amdgpu_buffer_rsrc_t ru = plane_rsrc(a.in_u + (ptrdiff_t)row_lo * pitch), rv = plane_rsrc(a.in_v + (ptrdiff_t)row_lo * pitch);
     const __amdgpu_buffer_rsrc_t wu = plane_rsrc(a.out_u + (ptrdiff_t)ur0 * pitch), wv = plane_rsrc(a.out_v + (ptrdiff_t)ur0 * pitch);
     const int voff = c * (int)sizeof(float), pitch_bytes = a.pitch * (int)sizeof(float);
+    // PER: this lane's first column modulo the grid's columns, and whether its group is one aligned piece of a row
+    int pc0 = 0;
+    bool pvec = true;
+    if constexpr (PER) {
+        pc0 = c % a.cols;
+        if (pc0 < 0) pc0 += a.cols;
+        pvec = pc0 % CPL == 0 && pc0 + CPL <= a.cols;
+    }
     auto fetch = [&](int row) {
         RowQ<CPL> r;
+        if constexpr (PER) {
+            int rr = row; // wave-uniform
+            if (rr < 0) rr += a.rows;
+            if (rr >= a.rows) rr -= a.rows;
+            if (rr < 0 || rr >= a.rows) { rr = row % a.rows; if (rr < 0) rr += a.rows; } // grids of fewer rows than K
+            const __amdgpu_buffer_rsrc_t pu = plane_rsrc(a.in_u + (ptrdiff_t)rr * pitch), pv = plane_rsrc(a.in_v + (ptrdiff_t)rr * pitch);
+            if (pvec) {
+                load_cols_buf<CPL>(pu, pc0 * (int)sizeof(float), 0, r.u);
+                load_cols_buf<CPL>(pv, pc0 * (int)sizeof(float), 0, r.v);
+            } else {
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) {
+                    int cc = pc0 + i;
+                    if (cc >= a.cols) cc -= a.cols;
+                    if (cc >= a.cols) cc %= a.cols;
+                    float x[1];
+                    load_cols_buf<1>(pu, cc * (int)sizeof(float), 0, x);
+                    r.u[i] = x[0];
+                    load_cols_buf<1>(pv, cc * (int)sizeof(float), 0, x);
+                    r.v[i] = x[0];
+                }
+            }
+            return r;
+        }
         const int rr = min(max(row, row_lo), row_hi);
         if (load_ok) {
             load_cols_buf<CPL>(ru, voff, (rr - row_lo) * pitch_bytes, r.u);
@@ -548,7 +586,7 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
 #pragma unroll
                                 for (int k = 0; k < CPL; ++k) cell<1, FAST, RowT<CPL>, ZH>(a, m, z, p, k + 1, mrow, prow, 0u, 0u, nu[k], nv[k]);
                             }
-                        } else if constexpr (EDGE == 0) {
+                        } else if constexpr (EDGE == 0 || PER) {
                             cells_interior<FAST, CPL, ZH>(a, m, z, p, nu, nv);
                         } else {
 #pragma unroll
@@ -570,7 +608,8 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
 }
 
 // WG: waves per workgroup.  4 independent waves, or all 16 of a CU with the progress board of tb_march<FAIR>.
-template <int K, int FAST, int CPL, int WG>
+// PER: the periodic rule's kernels (GsStepArgs::zero_halo = 2; kernels of their own, gs_step_tb_pk and its kin).
+template <int K, int FAST, int CPL, int WG, bool PER = false>
 __device__ __forceinline__ void tb_unit(const GsStepArgs &a)
 {
     // half_diff needs MODE.IEEE = 0: hwreg(HW_REG_MODE, offset 9, width 1).  The bit only governs
@@ -693,10 +732,17 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a)
     // kinds (cell<2>, cell<3>, EDGE = 4) exist for the clipped rule with the default side weights in the strict
     // build; every other combination -- corners, a grid narrower than two strips, the zero-halo rule, general
     // weights -- takes the general path.  GsStepArgs::edge_kinds = 0 sends every edge unit there (A/B timing).
+    // Under the periodic rule every edge unit -- first and last strips, first and last row chunks -- is of one kind:
+    // wrapped addresses, interior cells (tb_march<EDGE = 5>).
     constexpr bool KINDS = (FAST & 1) && !GS_MATH_FUSED;
-    if (!edge)
+    if constexpr (PER) {
+        if (!edge)
+            tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        else
+            tb_march<K, 5, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+    } else if (!edge)
         tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
-    else if (a.zero_halo)
+    else if (a.zero_halo) // (0 or 1 in these kernels: gs_launch_tb sends the periodic rule to gs_step_tb_pk)
         tb_march<K, 1, FAST, CPL, 1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && left && !right && !ends)
         tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
@@ -741,6 +787,23 @@ template <int K, int WG = 4>
 __global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_dx_k)(GsStepArgs a)
 {
     tb_unit<K, 15, 2, WG>(a);
+}
+// The periodic rule's forms of the three (GsStepArgs::zero_halo = 2): separate kernels, so that the code of the ones above
+// does not change.
+template <int K, int FAST, int CPL, int WG = 4>
+__global__ __launch_bounds__(WG * 64) void GS_SUFFIX(gs_step_tb_pk)(GsStepArgs a)
+{
+    tb_unit<K, FAST, CPL, WG, true>(a);
+}
+template <int K, int WG = 4>
+__global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_ds_pk)(GsStepArgs a)
+{
+    tb_unit<K, 7, 2, WG, true>(a);
+}
+template <int K, int WG = 4>
+__global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_dx_pk)(GsStepArgs a)
+{
+    tb_unit<K, 15, 2, WG, true>(a);
 }
 
 } // namespace

@@ -26,7 +26,7 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_k)(GsStepArgs a)
     const float u = a.in_u[o], v = a.in_v[o];
 
     float acc_u = 0.0f, acc_v = 0.0f;
-    if (a.zero_halo) { // full window, centred weights, zeros outside the grid
+    if (a.zero_halo) { // full window, centred weights, zeros outside the grid (0 or 1 here: periodic = gs_step_simple_pk)
         for (int di = -1; di <= 1; ++di)
             for (int dj = -1; dj <= 1; ++dj) {
                 const bool inside = (di >= 0 || top) && (di <= 0 || bottom) && (dj >= 0 || left) && (dj <= 0 || right);
@@ -52,15 +52,45 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_k)(GsStepArgs a)
     a.out_v[o] = ov;
 }
 
-template <int G, bool EDGE>
+// The periodic rule (GsStepArgs::zero_halo = 2), literally: the nine taps of the zero-halo rule's interior cell, in its
+// order, with neighbour (r + i - 1, c + j - 1) read at ((r + i - 1) mod rows, (c + j - 1) mod cols).  A kernel of its own.
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_pk)(GsStepArgs a)
+{
+    const int bpr = (a.cols + 255) >> 8;
+    const int slot = blockIdx.x / bpr;
+    const int c = (blockIdx.x - slot * bpr) * 256 + threadIdx.x;
+    const int r = range_row(a, slot);
+    if (c >= a.cols) return;
+    const ptrdiff_t pitch = a.pitch;
+    const ptrdiff_t rows_at[3] = {(ptrdiff_t)(r > 0 ? r - 1 : a.rows - 1) * pitch, (ptrdiff_t)r * pitch,
+                                  (ptrdiff_t)(r + 1 < a.rows ? r + 1 : 0) * pitch};
+    const int cols_at[3] = {c > 0 ? c - 1 : a.cols - 1, c, c + 1 < a.cols ? c + 1 : 0};
+    const float u = a.in_u[rows_at[1] + c], v = a.in_v[rows_at[1] + c];
+    float acc_u = 0.0f, acc_v = 0.0f;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const float su = a.in_u[rows_at[i] + cols_at[j]], sv = a.in_v[rows_at[i] + cols_at[j]];
+            GS_TAP(acc_u, a.w[i][j], su, u);
+            GS_TAP(acc_v, a.w[i][j], sv, v);
+        }
+    float ou, ov;
+    react(a, u, v, acc_u, acc_v, ou, ov);
+    a.out_u[rows_at[1] + c] = ou;
+    a.out_v[rows_at[1] + c] = ov;
+}
+
+// PER: a unit on an edge under the periodic rule (gs_step_stream_pk): rows and columns are read at their index modulo
+// the grid's (a lane whose four columns are not one aligned piece of a row after wrapping loads them one by one), and
+// every cell runs the interior code.
+template <int G, bool EDGE, bool PER = false>
 __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int c0, int lane)
 {
     const int c = c0 + lane * 4;
     LaneCtx lc;
     lc.lane_ok = !EDGE || (c < a.pitch);
     lc.halo_off = (lane == 0) ? -1 : 4;
-    lc.halo_ok = EDGE ? ((lane == 0 && c0 > 0) || (lane == 63 && c + 4 < a.pitch))
-                      : (lane == 0 || lane == 63);
+    lc.halo_ok = EDGE && !PER ? ((lane == 0 && c0 > 0) || (lane == 63 && c + 4 < a.pitch))
+                              : (lane == 0 || lane == 63);
 
     const ptrdiff_t pitch = a.pitch;
     const float *bu = a.in_u + c, *bv = a.in_v + c; // row 0 of this lane's columns
@@ -70,8 +100,44 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
     // Rows are fetched one group (G rows) ahead of the group being computed.  Row indices
     // are clamped to ur1 (the row below the last output row, at most the bottom ghost
     // row), so every load is in bounds and the tail needs no branches around loads.
+    // PER: this lane's first column and its halo column modulo the grid's columns
+    int pc0 = 0, phalo = 0;
+    bool pvec = true;
+    if constexpr (PER) {
+        pc0 = c % a.cols;
+        pvec = pc0 % 4 == 0 && pc0 + 4 <= a.cols;
+        phalo = (lane == 0 ? c0 - 1 + a.cols : c + 4) % a.cols;
+    }
     auto fetch = [&](int row) {
         const int rr = row < ur1 ? row : ur1;
+        if constexpr (PER) {
+            const int wr = rr < 0 ? rr + a.rows : (rr >= a.rows ? rr - a.rows : rr); // |rr| stays within a row of the grid
+            const float *pu = a.in_u + (ptrdiff_t)wr * pitch, *pv = a.in_v + (ptrdiff_t)wr * pitch;
+            RowIn r;
+            if (pvec) {
+                r.u = *reinterpret_cast<const float4 *>(pu + pc0);
+                r.v = *reinterpret_cast<const float4 *>(pv + pc0);
+            } else {
+                float xu[4], xv[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    int cc = pc0 + i;
+                    if (cc >= a.cols) cc -= a.cols;
+                    if (cc >= a.cols) cc %= a.cols;
+                    xu[i] = pu[cc];
+                    xv[i] = pv[cc];
+                }
+                r.u = make_float4(xu[0], xu[1], xu[2], xu[3]);
+                r.v = make_float4(xv[0], xv[1], xv[2], xv[3]);
+            }
+            r.hu = 0.f;
+            r.hv = 0.f;
+            if (lc.halo_ok) {
+                r.hu = pu[phalo];
+                r.hv = pv[phalo];
+            }
+            return r;
+        }
         return load_row<EDGE>(bu + (ptrdiff_t)rr * pitch, bv + (ptrdiff_t)rr * pitch, lc);
     };
 
@@ -89,7 +155,7 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
     for (int k = 0; k < 4; ++k) {
         la[k] = (EDGE && k == 0 && c == 0) ? 0xffffffffu : 0u;
         ra[k] = (EDGE && (c + k + 1 >= a.cols)) ? 0xffffffffu : 0u;
-        if (EDGE) { // keep the masks opaque, or the compiler turns every blend back into v_cndmask
+        if (EDGE && !PER) { // keep the masks opaque, or the compiler turns every blend back into v_cndmask
             if (k == 0) asm volatile("" : "+v"(la[k]));
             asm volatile("" : "+v"(ra[k]));
         }
@@ -107,10 +173,11 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
                 const bool mrow = !EDGE || (row > 0) || a.top_present;
                 const bool prow = !EDGE || (row + 1 < a.rows) || a.bottom_present;
                 float4 nu, nv;
-                cell<EDGE>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x);
-                cell<EDGE>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y);
-                cell<EDGE>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z);
-                cell<EDGE>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w);
+                constexpr bool E = EDGE && !PER;
+                cell<E>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x);
+                cell<E>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y);
+                cell<E>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z);
+                cell<E>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w);
                 if (lc.lane_ok) {
                     *reinterpret_cast<float4 *>(ou) = nu;
                     *reinterpret_cast<float4 *>(ov) = nv;
@@ -160,6 +227,42 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_k)(GsStepArgs a)
                       (ur1 == a.rows && !a.bottom_present);
     if (edge)
         march<G, true>(a, ur0, ur1, c0, lane);
+    else
+        march<G, false>(a, ur0, ur1, c0, lane);
+}
+
+// The periodic rule's form (GsStepArgs::zero_halo = 2; a single slab): gs_step_stream_k's units, whose
+// edge units read wrapped rows and columns and run the interior cell code (march<PER>).
+template <int G>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_pk)(GsStepArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strips = (a.cols + 255) >> 8;
+    int block = (int)blockIdx.x;
+    if (a.xcd_m > 0) { // XCD-aware order (GsStepArgs::xcd_m)
+        const int per = 8 * a.xcd_m, g = block / per, o = block - g * per;
+        if ((g + 1) * per <= (int)gridDim.x) block = g * per + (o & 7) * a.xcd_m + (o >> 3);
+    }
+    const int unit = block * 4 + wave;
+    const int chunk = unit / strips;
+    const int strip = unit - chunk * strips;
+    const int rpu = a.rows_per_unit;
+    const int chunks_a = (a.ra1 - a.ra0 + rpu - 1) / rpu;
+    const int chunks_b = (a.rb1 - a.rb0 + rpu - 1) / rpu;
+    if (chunk >= chunks_a + chunks_b) return; // wave-uniform
+    int ur0, ur1;
+    if (chunk < chunks_a) {
+        ur0 = a.ra0 + chunk * rpu;
+        ur1 = min(ur0 + rpu, a.ra1);
+    } else {
+        ur0 = a.rb0 + (chunk - chunks_a) * rpu;
+        ur1 = min(ur0 + rpu, a.rb1);
+    }
+    const int c0 = strip << 8;
+    const bool edge = (c0 == 0) || (c0 + 256 >= a.cols) || (ur0 == 0) || (ur1 == a.rows);
+    if (edge)
+        march<G, true, true>(a, ur0, ur1, c0, lane);
     else
         march<G, false>(a, ur0, ur1, c0, lane);
 }

@@ -33,6 +33,10 @@
 //       (temporal blocking), K register-resident time levels per wave, sacrificial edge
 //       lanes instead of halo loads.  ~16 B of HBM traffic per cell for K steps;
 //       VALU-issue bound for K >= 3.  Bit-identical to K single steps.
+//   ..._pk             the periodic rule's forms (GsStepArgs::zero_halo = 2) of the simple, streaming, marching, tile and
+//       ensemble kernels: kernels of their own, so that the code of the others does not depend on the rule's existence.
+//       Units and windows on an edge read wrapped rows and columns and run the interior cell code; the resident kernels'
+//       periodic forms (gs_run_resident_pk, gs_ens_resident_pk: ZH = 2) keep their LDS ring filled with the opposite edge.
 //
 // This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
 // its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
@@ -49,7 +53,7 @@
 #error "compile with -DGS_MATH_FUSED=0 or 1"
 #endif
 // GS_TB_OP_ONLY=1: this translation unit provides nothing but the parameter-specialised (".op")
-// instances of gs_step_tb_k, through gs_tb_op_kernel_strict() (24 kernels: built apart from the
+// instances of gs_step_tb_k and of its periodic form, through gs_tb_op_kernel_strict() (built apart from the
 // rest so that the translation units compile in parallel; grayscott_amd/_build.py).
 #ifndef GS_TB_OP_ONLY
 #define GS_TB_OP_ONLY 0
@@ -124,15 +128,18 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 
 hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name)
 {
-    if (name) *name = "simple/" GS_MATH_NAME;
+    const bool per = a.zero_halo == 2; // the periodic rule: a kernel of its own
+    if (name) *name = per ? "simple/" GS_MATH_NAME "/periodic" : "simple/" GS_MATH_NAME;
     const long nrows = (long)(a.ra1 - a.ra0) + (a.rb1 - a.rb0);
     if (nrows <= 0 || a.cols <= 0) return hipSuccess;
+    if (per && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // (single slab only)
     const long bpr = (a.cols + 255) >> 8;
     const long blocks = nrows * bpr;
     if (blocks > 0x7fffffffL) return hipErrorInvalidConfiguration;
     GsStepArgs args = a;
     void *kargs[] = {&args};
-    return hipLaunchKernel(reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_k)),
+    return hipLaunchKernel(per ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_pk))
+                               : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_k)),
                            dim3((unsigned)blocks), dim3(256), kargs, 0, s);
 }
 
@@ -140,19 +147,22 @@ hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const
 // the result is stored in the out-planes when steps is odd, else back in the in-planes.
 hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStream_t s, const char **name)
 {
-    static const char *const names[2] = {"resident-lds/" GS_MATH_NAME, "resident-lds/" GS_MATH_NAME ".op"};
+    static const char *const names[2][2] = {{"resident-lds/" GS_MATH_NAME, "resident-lds/" GS_MATH_NAME ".op"},
+                                            {"resident-lds/" GS_MATH_NAME "/periodic", "resident-lds/" GS_MATH_NAME ".op/periodic"}};
     const long cells = (long)a.rows * a.cols;
     if (a.rows <= 0 || a.cols <= 0 || cells > kResidentCells || steps < 0 || a.top_present || a.bottom_present)
         return hipErrorInvalidValue;
     int fast = a.fast & (GS_MATH_FUSED ? 0 : 3);
     if (fast != 3) fast = 0; // only the variant for the default parameters is built besides the general one
-    if (name) *name = names[fast ? 1 : 0];
+    const int zh = a.zero_halo == 2 ? 2 : (a.zero_halo ? 1 : 0); // gs_boundary
+    if (name) *name = names[zh == 2][fast ? 1 : 0];
     const void *fn = nullptr;
-    const int zh = a.zero_halo ? 1 : 0;
 #define GS_RES_FN(F, Z) reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_resident_k)<F, Z>)
-    if (fast) fn = zh ? GS_RES_FN(GS_MATH_FUSED ? 0 : 3, 1) : GS_RES_FN(GS_MATH_FUSED ? 0 : 3, 0);
-    else fn = zh ? GS_RES_FN(0, 1) : GS_RES_FN(0, 0);
+#define GS_RES_PFN(F) reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_resident_pk)<F>)
+    if (fast) fn = zh == 2 ? GS_RES_PFN(GS_MATH_FUSED ? 0 : 3) : zh ? GS_RES_FN(GS_MATH_FUSED ? 0 : 3, 1) : GS_RES_FN(GS_MATH_FUSED ? 0 : 3, 0);
+    else fn = zh == 2 ? GS_RES_PFN(0) : zh ? GS_RES_FN(0, 1) : GS_RES_FN(0, 0);
 #undef GS_RES_FN
+#undef GS_RES_PFN
     const size_t lds = (size_t)4 * (a.rows + 2) * (a.cols + 2) * sizeof(float); // <= 74 KB (1 x 1536 cells)
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
         const hipError_t e = ensure_dyn_lds(fn, lds > 64 * 1024 ? (size_t)80 * 1024 : lds);
@@ -171,23 +181,30 @@ hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStre
 // 2K < window rows.
 hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name)
 {
-    static const char *const names[3][2] = {{"tile32x64/" GS_MATH_NAME, "tile32x64/" GS_MATH_NAME ".op"},
-                                            {"tile16x64/" GS_MATH_NAME, "tile16x64/" GS_MATH_NAME ".op"},
-                                            {"tile64x64/" GS_MATH_NAME, "tile64x64/" GS_MATH_NAME ".op"}};
+    static const char *const names[2][3][2] = {
+        {{"tile32x64/" GS_MATH_NAME, "tile32x64/" GS_MATH_NAME ".op"},
+         {"tile16x64/" GS_MATH_NAME, "tile16x64/" GS_MATH_NAME ".op"},
+         {"tile64x64/" GS_MATH_NAME, "tile64x64/" GS_MATH_NAME ".op"}},
+        {{"tile32x64/" GS_MATH_NAME "/periodic", "tile32x64/" GS_MATH_NAME ".op/periodic"},
+         {"tile16x64/" GS_MATH_NAME "/periodic", "tile16x64/" GS_MATH_NAME ".op/periodic"},
+         {"tile64x64/" GS_MATH_NAME "/periodic", "tile64x64/" GS_MATH_NAME ".op/periodic"}}};
     static const int rpw[3] = {2, 1, 4};
+    const bool per = a.zero_halo == 2; // the periodic rule: gs_run_tile_pk
     if (a.rows <= 0 || a.cols <= 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || a.top_present || a.bottom_present ||
         2 * k >= tile_rows(rpw[shape]))
         return hipErrorInvalidValue;
     int fast = a.fast & (GS_MATH_FUSED ? 0 : 3);
     if (fast != 3) fast = 0; // only the variant for the default parameters is built besides the general one
-    if (name) *name = names[shape][fast ? 1 : 0];
+    if (name) *name = names[per][shape][fast ? 1 : 0];
     const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
     const long tiles = ((a.rows + ho - 1) / ho) * ((a.cols + wo - 1) / wo);
     if (tiles > 0x7fffffffL) return hipErrorInvalidConfiguration;
     const void *fn = nullptr;
 #define GS_TILE_FN(S, RPW_)                                                                                   \
-    case S: fn = fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_k)<RPW_, GS_MATH_FUSED ? 0 : 3>)  \
-                      : reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_k)<RPW_, 0>); break;
+    case S: fn = per ? (fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_pk)<RPW_, GS_MATH_FUSED ? 0 : 3>) \
+                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_pk)<RPW_, 0>))                   \
+                     : fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_k)<RPW_, GS_MATH_FUSED ? 0 : 3>)  \
+                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_k)<RPW_, 0>); break;
     switch (shape) { GS_TILE_FN(0, 2) GS_TILE_FN(1, 1) GS_TILE_FN(2, 4) }
 #undef GS_TILE_FN
     size_t lds = tile_lds_bytes(rpw[shape]);
@@ -210,7 +227,8 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
 // odd, else back in the in-planes.
 hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[2] = {"ensemble-resident/" GS_MATH_NAME, "ensemble-resident/" GS_MATH_NAME ".op"};
+    static const char *const names[2][2] = {{"ensemble-resident/" GS_MATH_NAME, "ensemble-resident/" GS_MATH_NAME ".op"},
+                                            {"ensemble-resident/" GS_MATH_NAME "/periodic", "ensemble-resident/" GS_MATH_NAME ".op/periodic"}};
     const long cells = (long)e.rows * e.cols;
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0) return hipErrorInvalidValue;
     const long threads = cells >= 1024 ? 1024 : ((cells + 63) / 64) * 64; // the waves that hold cells
@@ -218,19 +236,23 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
     const size_t lds = (size_t)4 * (e.rows + 2) * (e.cols + 2) * sizeof(float);
     if (!cpt || lds > kGsEnsResidentMaxLds) return hipErrorInvalidValue;
     fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    if (name) *name = names[fast ? 1 : 0];
-    const int zh = e.zero_halo ? 1 : 0;
+    const int zh = e.zero_halo == 2 ? 2 : (e.zero_halo ? 1 : 0); // gs_boundary
+    if (name) *name = names[zh == 2][fast ? 1 : 0];
     const void *fn = nullptr;
 #define GS_ENS_RES_FN(C)                                                                                                    \
-    case C: fn = fast ? (zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, GS_MATH_FUSED ? 0 : 3, 1>)        \
+    case C: fn = fast ? (zh == 2 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<C, GS_MATH_FUSED ? 0 : 3>)   \
+                       : zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, GS_MATH_FUSED ? 0 : 3, 1>)        \
                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, GS_MATH_FUSED ? 0 : 3, 0>))       \
-                      : (zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, 0, 1>)                             \
+                      : (zh == 2 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<C, 0>)                        \
+                       : zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, 0, 1>)                             \
                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, 0, 0>)); break;
     switch (cpt) { GS_ENS_RES_FN(1) GS_ENS_RES_FN(2) GS_ENS_RES_FN(4) }
 #undef GS_ENS_RES_FN
-    if (cpt == 8) // zero-halo rule only (gs_ens_resident_cpt)
-        fn = fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, GS_MATH_FUSED ? 0 : 3, 1>)
-                  : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, 0, 1>);
+    if (cpt == 8) // zero-halo and periodic rules only (gs_ens_resident_cpt)
+        fn = zh == 2 ? (fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<8, GS_MATH_FUSED ? 0 : 3>)
+                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<8, 0>))
+                     : fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, GS_MATH_FUSED ? 0 : 3, 1>)
+                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, 0, 1>);
     if (!fn) return hipErrorInvalidValue;
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
         const hipError_t err = ensure_dyn_lds(fn, lds);
@@ -251,21 +273,28 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
 // Windowed form: K <= kGsTileMaxSteps steps of every member (in-planes -> out-planes); `shape` as gs_launch_tile's.
 hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[3][2] = {{"ensemble-tile32x64/" GS_MATH_NAME, "ensemble-tile32x64/" GS_MATH_NAME ".op"},
-                                            {"ensemble-tile16x64/" GS_MATH_NAME, "ensemble-tile16x64/" GS_MATH_NAME ".op"},
-                                            {"ensemble-tile64x64/" GS_MATH_NAME, "ensemble-tile64x64/" GS_MATH_NAME ".op"}};
+    static const char *const names[2][3][2] = {
+        {{"ensemble-tile32x64/" GS_MATH_NAME, "ensemble-tile32x64/" GS_MATH_NAME ".op"},
+         {"ensemble-tile16x64/" GS_MATH_NAME, "ensemble-tile16x64/" GS_MATH_NAME ".op"},
+         {"ensemble-tile64x64/" GS_MATH_NAME, "ensemble-tile64x64/" GS_MATH_NAME ".op"}},
+        {{"ensemble-tile32x64/" GS_MATH_NAME "/periodic", "ensemble-tile32x64/" GS_MATH_NAME ".op/periodic"},
+         {"ensemble-tile16x64/" GS_MATH_NAME "/periodic", "ensemble-tile16x64/" GS_MATH_NAME ".op/periodic"},
+         {"ensemble-tile64x64/" GS_MATH_NAME "/periodic", "ensemble-tile64x64/" GS_MATH_NAME ".op/periodic"}}};
     static const int rpw[3] = {2, 1, 4};
+    const bool per = e.zero_halo == 2; // the periodic rule: gs_ens_tile_pk
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]))
         return hipErrorInvalidValue;
     fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    if (name) *name = names[shape][fast ? 1 : 0];
+    if (name) *name = names[per][shape][fast ? 1 : 0];
     const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
     const long windows = ((e.rows + ho - 1) / ho) * ((e.cols + wo - 1) / wo);
     if (windows > kGsEnsMaxGroups) return hipErrorInvalidConfiguration;
     const void *fn = nullptr;
 #define GS_ENS_TILE_FN(S, RPW_)                                                                                   \
-    case S: fn = fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, GS_MATH_FUSED ? 0 : 3>)  \
-                      : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, 0>); break;
+    case S: fn = per ? (fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_pk)<RPW_, GS_MATH_FUSED ? 0 : 3>) \
+                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_pk)<RPW_, 0>))                   \
+                     : fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, GS_MATH_FUSED ? 0 : 3>)  \
+                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, 0>); break;
     switch (shape) { GS_ENS_TILE_FN(0, 2) GS_ENS_TILE_FN(1, 1) GS_ENS_TILE_FN(2, 4) }
 #undef GS_ENS_TILE_FN
     const size_t lds = tile_lds_bytes(rpw[shape]);
@@ -295,6 +324,7 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
         x.k > 8 || (x.k & 1) || 2 * x.k >= win_rows(rpw) || 2 * x.k + 2 > kWinCols || !x.flags || !x.abort || !x.xu[0] || !x.xu[1] || !x.xv[0] || !x.xv[1])
         return hipErrorInvalidValue;
     if (!x.desc || x.n_windows < 1 || x.seq < 1) return hipErrorInvalidValue;
+    if (a.zero_halo == 2) return hipErrorInvalidValue; // no periodic form (gs_api.cpp refuses the rule before this)
     // byte offsets inside a plane are 32-bit in the kernel
     if ((long)(a.rows + 8) * a.pitch * 4 > 0x7fffffffL) return hipErrorInvalidValue;
     int fast = a.fast & (GS_MATH_FUSED ? 0 : 7);
@@ -321,8 +351,9 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
 
 hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name)
 {
-    if (name) *name = "stream-g2/" GS_MATH_NAME;
-    if (a.cols <= 0 || a.rows_per_unit <= 0) return hipErrorInvalidValue;
+    const bool per = a.zero_halo == 2; // the periodic rule: gs_step_stream_pk (single slab)
+    if (name) *name = per ? "stream-g2/" GS_MATH_NAME "/periodic" : "stream-g2/" GS_MATH_NAME;
+    if (a.cols <= 0 || a.rows_per_unit <= 0 || (per && (a.top_present || a.bottom_present))) return hipErrorInvalidValue;
     const long rpu = a.rows_per_unit;
     const long chunks = ((long)(a.ra1 - a.ra0) + rpu - 1) / rpu + ((long)(a.rb1 - a.rb0) + rpu - 1) / rpu;
     if (chunks <= 0) return hipSuccess;
@@ -337,37 +368,40 @@ hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const
     static const int xcd_env = gs_env_int("GS_HIP_XCD_M_STREAM", -1, 0, kGsXcdGroupMax);
     args.xcd_m = xcd_env >= 0 ? xcd_env : 16;
     void *kargs[] = {&args};
-    return hipLaunchKernel(reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_k)<2>),
+    return hipLaunchKernel(per ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_pk)<2>)
+                               : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_k)<2>),
                            dim3((unsigned)blocks), dim3(256), kargs, 0, s);
 }
 
 // K fused steps over the row ranges of GsStepArgs; on slab seams the ghost rows must be K deep.
-// Kernel entry for k fused steps, specialisation `fast` (already reduced to {0, 1, 3}) and cpl columns per lane.
-static const void *tb_entry(int k, int fast, int cpl, int wg = 4)
+// Kernel entry for k fused steps, specialisation `fast` (already reduced to {0, 1, 3}) and cpl columns per lane; `per`:
+// the periodic rule's form (gs_step_tb_pk).
+static const void *tb_entry(int k, int fast, int cpl, int wg = 4, bool per = false)
 {
     const void *fn = nullptr;
+#define GS_TB_FN(KER, KK, F, CC, WG_) (per ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_pk)<KK, F, CC, WG_>) \
+                                           : reinterpret_cast<const void *>(&GS_SUFFIX(KER##_k)<KK, F, CC, WG_>))
 #define GS_TB_CASE(KK, CC)                                                                      \
-    case (KK) * 8 + (CC): fn = reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<KK, 0, CC>); break;
+    case (KK) * 8 + (CC): fn = GS_TB_FN(gs_step_tb, KK, 0, CC, 4); break;
     if (wg == 16) { // the fair-progress form: 4 fused steps, 1 or 2 columns per lane
         if (k != 4 || (cpl != 1 && cpl != 2)) return nullptr;
         if (fast) {
 #if !GS_MATH_FUSED
-            return gs_tb_op_kernel_strict(k, fast, cpl, 16);
+            return gs_tb_op_kernel_strict(k, fast, cpl, 16, per);
 #endif
         }
 #if GS_MATH_FUSED
         // (2 columns per lane need 129 registers in the fused flavour, one more than a wave of a 16-wave workgroup may have:
         // the variant spilled a register to scratch; one-round launches of the fused flavour run as 4-wave workgroups)
         if (cpl == 2) return nullptr;
-        return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<4, 0, 1, 16>);
+        return GS_TB_FN(gs_step_tb, 4, 0, 1, 16);
 #else
-        return cpl == 1 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<4, 0, 1, 16>)
-                        : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<4, 0, 2, 16>);
+        return cpl == 1 ? GS_TB_FN(gs_step_tb, 4, 0, 1, 16) : GS_TB_FN(gs_step_tb, 4, 0, 2, 16);
 #endif
     }
     if (fast) {
 #if !GS_MATH_FUSED
-        fn = gs_tb_op_kernel_strict(k, fast, cpl, 4);
+        fn = gs_tb_op_kernel_strict(k, fast, cpl, 4, per);
 #endif
     } else {
         switch (k * 8 + cpl) {
@@ -408,7 +442,7 @@ static int tb_waves_of(const void *f)
 // The variant that runs for GsStepArgs::fast = `fast` with k fused steps, cpl columns per lane and wg waves per
 // workgroup: 0 (general), 1 (side weights 0.5), 3 (and dt == 1), 7 (and full difference sharing: built for 2 columns
 // per lane, 2 to 4 fused steps) or 15 (and across lanes).
-static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4)
+static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, bool per = false)
 {
     // The fused build has no use for bit 0 (its taps are sub + fma already) and measured slower
     // with bit 1 (profiles/archive/r01_sweeps.md, runs 48/49): it always runs the general variant.  dt == 1
@@ -417,8 +451,8 @@ static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4)
     if (!(fast & 1)) return 0;
     if ((fast & 7) == 7) {
 #if !GS_MATH_FUSED
-        if ((fast & 8) && gs_tb_op_kernel_strict(k, 15, cpl, wg)) return 15;
-        if (gs_tb_op_kernel_strict(k, 7, cpl, wg)) return 7;
+        if ((fast & 8) && gs_tb_op_kernel_strict(k, 15, cpl, wg, per)) return 15;
+        if (gs_tb_op_kernel_strict(k, 7, cpl, wg, per)) return 7;
 #endif
         return 3;
     }
@@ -426,11 +460,12 @@ static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4)
 }
 
 // Wave slots of the chip for the kernel entry a launch with these parameters would use (the tuner's
-// "a launch of exactly r rounds" candidates, gs_tuner.cpp); 0 = no such entry.
-int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl)
+// "a launch of exactly r rounds" candidates, gs_tuner.cpp); 0 = no such entry.  `boundary`: gs_boundary.
+int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary)
 {
     if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4)) return 0;
-    const void *fn = tb_entry(k, tb_reduce_fast(fast, k, cpl), cpl);
+    const bool per = boundary == 2;
+    const void *fn = tb_entry(k, tb_reduce_fast(fast, k, cpl, 4, per), cpl, 4, per);
     return fn ? 1024 * tb_waves_of(fn) : 0;
 }
 
@@ -450,22 +485,37 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // ".op.dx": ... and across lanes (cells_xshare)
     static const char *const names[3][4][4] = {GS_TB_NAMES("c1"), GS_TB_NAMES("c2"), GS_TB_NAMES("")};
 #undef GS_TB_NAMES
+#define GS_TB_NAMES(C, M) {"tb-k1" C "/" GS_MATH_NAME M "/periodic", "tb-k2" C "/" GS_MATH_NAME M "/periodic", \
+                           "tb-k3" C "/" GS_MATH_NAME M "/periodic", "tb-k4" C "/" GS_MATH_NAME M "/periodic"}
+#define GS_TB_NAMES4(C) {GS_TB_NAMES(C, ""), GS_TB_NAMES(C, ".op"), GS_TB_NAMES(C, ".op.ds"), GS_TB_NAMES(C, ".op.dx")}
+    static const char *const names_p[3][4][4] = {GS_TB_NAMES4("c1"), GS_TB_NAMES4("c2"), GS_TB_NAMES4("")};
+#undef GS_TB_NAMES4
+#undef GS_TB_NAMES
     // "f": the fair-progress form (16-wave workgroups) of one-round launches
     static const char *const names16[2][4] = {
         {"tb-k4c1f/" GS_MATH_NAME, "tb-k4c1f/" GS_MATH_NAME ".op", "tb-k4c1f/" GS_MATH_NAME ".op.ds", "tb-k4c1f/" GS_MATH_NAME ".op.dx"},
         {"tb-k4c2f/" GS_MATH_NAME, "tb-k4c2f/" GS_MATH_NAME ".op", "tb-k4c2f/" GS_MATH_NAME ".op.ds", "tb-k4c2f/" GS_MATH_NAME ".op.dx"}};
+    static const char *const names16_p[2][4] = {
+        {"tb-k4c1f/" GS_MATH_NAME "/periodic", "tb-k4c1f/" GS_MATH_NAME ".op/periodic", "tb-k4c1f/" GS_MATH_NAME ".op.ds/periodic",
+         "tb-k4c1f/" GS_MATH_NAME ".op.dx/periodic"},
+        {"tb-k4c2f/" GS_MATH_NAME "/periodic", "tb-k4c2f/" GS_MATH_NAME ".op/periodic", "tb-k4c2f/" GS_MATH_NAME ".op.ds/periodic",
+         "tb-k4c2f/" GS_MATH_NAME ".op.dx/periodic"}};
     auto name_of = [](int f) { return f == 15 ? 3 : (f == 7 ? 2 : (f ? 1 : 0)); };
     if (k < 1 || k > 4 || a.cols <= 0 || a.rows_per_unit <= 0) return hipErrorInvalidValue;
+    if (a.zero_halo == 2 && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // periodic: single slab, no bands
     const int cpl = a.cpl == 0 ? 4 : a.cpl;
     if (cpl != 1 && cpl != 2 && cpl != 4) return hipErrorInvalidValue;
-    const int fast = tb_reduce_fast(a.fast, k, cpl);
-    if (name) *name = names[cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
+    // the periodic rule runs kernels of its own (gs_step_tb_pk and kin), named with a "/periodic" suffix
+    const bool per = a.zero_halo == 2;
+    const int fast = tb_reduce_fast(a.fast, k, cpl, 4, per);
+    if (name) *name = per ? names_p[cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1]
+                          : names[cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
     const long rpu = a.rows_per_unit;
     const long rows_a = (long)a.ra1 - a.ra0;
     const long W = tb_cols_per_wave(k, cpl);
     const long strips = (a.cols + W - 1) / W;
     // Kernel entry first: the taper below needs its occupancy.
-    const void *fn = tb_entry(k, fast, cpl);
+    const void *fn = tb_entry(k, fast, cpl, 4, per);
     if (!fn) return hipErrorInvalidValue;
     const int waves = tb_waves_of(fn);
     // Tapered tail (consecutive passes are dependent launches that cannot overlap, so the drain phase
@@ -548,13 +598,13 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // GS_HIP_FAIR = 0 / 1 forces it off / on.
     static const int fair_env = gs_env_int("GS_HIP_FAIR", -1, 0, 1);
     const bool fair = a.allow_fair && units <= 4096 && units > 1024 && (fair_env < 0 ? (cpl == 2 || rpu >= 20) : fair_env != 0);
-    const int fast16 = fair ? tb_reduce_fast(a.fast, k, cpl, 16) : 0;
-    const void *fair_fn = fair ? tb_entry(k, fast16, cpl, 16) : nullptr;
+    const int fast16 = fair ? tb_reduce_fast(a.fast, k, cpl, 16, per) : 0;
+    const void *fair_fn = fair ? tb_entry(k, fast16, cpl, 16, per) : nullptr;
     static const int fair_from_env = gs_env_int("GS_HIP_FAIR_FROM", -1, 0, 256);
     args.fair_from = fair_from_env >= 0 ? fair_from_env : 0;
     void *kargs[] = {&args};
     if (fair_fn) {
-        if (name) *name = names16[cpl == 1 ? 0 : 1][name_of(fast16)];
+        if (name) *name = (per ? names16_p : names16)[cpl == 1 ? 0 : 1][name_of(fast16)];
         return hipLaunchKernel(fair_fn, dim3((unsigned)((units + 15) / 16)), dim3(1024), kargs, 0, s);
     }
     const long blocks = (units + 3) / 4;
@@ -577,7 +627,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
 hipError_t GS_SUFFIX(gs_launch_lds)(const GsStepArgs &a, hipStream_t s, const char **name)
 {
     if (name) *name = "lds-tile16/" GS_MATH_NAME;
-    if (a.cols <= 0) return hipErrorInvalidValue;
+    if (a.cols <= 0 || a.zero_halo == 2) return hipErrorInvalidValue; // no periodic form (gs_api.cpp refuses it first)
     const long chunks = ((long)(a.ra1 - a.ra0) + kLdsTileRows - 1) / kLdsTileRows +
                         ((long)(a.rb1 - a.rb0) + kLdsTileRows - 1) / kLdsTileRows;
     if (chunks <= 0) return hipSuccess;
@@ -619,39 +669,40 @@ extern "C" int32_t GS_SUFFIX(gs_debug_trace_read)(unsigned long long *dst, int32
 
 #if GS_TB_OP_ONLY
 // Kernel entry of the specialised variant for K fused steps, `fast` in {1, 3} (GsStepArgs::fast)
-// and `cpl` columns per lane.
-const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg)
+// and `cpl` columns per lane; `per`: the periodic rule's form.
+template <bool PER>
+static const void *tb_op_kernel(int k, int fast, int cpl, int wg)
 {
+#define GS_OP_FN(KER, ...) (PER ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_pk)<__VA_ARGS__>) \
+                                : reinterpret_cast<const void *>(&GS_SUFFIX(KER##_k)<__VA_ARGS__>))
     if (fast == 7) { // full difference sharing: 2 columns per lane
         if (cpl != 2) return nullptr;
-        if (wg == 16) return k == 4 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_ds_k)<4, 16>) : nullptr;
+        if (wg == 16) return k == 4 ? GS_OP_FN(gs_step_tb_ds, 4, 16) : nullptr;
         switch (k) {
-        case 2: return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_ds_k)<2>);
-        case 3: return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_ds_k)<3>);
-        case 4: return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_ds_k)<4>);
+        case 2: return GS_OP_FN(gs_step_tb_ds, 2);
+        case 3: return GS_OP_FN(gs_step_tb_ds, 3);
+        case 4: return GS_OP_FN(gs_step_tb_ds, 4);
         default: return nullptr;
         }
     }
     if (fast == 15) { // ... and across lanes
         if (cpl != 2) return nullptr;
-        if (wg == 16) return k == 4 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_dx_k)<4, 16>) : nullptr;
+        if (wg == 16) return k == 4 ? GS_OP_FN(gs_step_tb_dx, 4, 16) : nullptr;
         switch (k) {
-        case 2: return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_dx_k)<2>);
-        case 3: return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_dx_k)<3>);
-        case 4: return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_dx_k)<4>);
+        case 2: return GS_OP_FN(gs_step_tb_dx, 2);
+        case 3: return GS_OP_FN(gs_step_tb_dx, 3);
+        case 4: return GS_OP_FN(gs_step_tb_dx, 4);
         default: return nullptr;
         }
     }
     if (wg == 16) {
         if (k != 4 || (cpl != 1 && cpl != 2) || (fast != 1 && fast != 3)) return nullptr;
         if (fast == 1)
-            return cpl == 1 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<4, 1, 1, 16>)
-                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<4, 1, 2, 16>);
-        return cpl == 1 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<4, 3, 1, 16>)
-                        : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<4, 3, 2, 16>);
+            return cpl == 1 ? GS_OP_FN(gs_step_tb, 4, 1, 1, 16) : GS_OP_FN(gs_step_tb, 4, 1, 2, 16);
+        return cpl == 1 ? GS_OP_FN(gs_step_tb, 4, 3, 1, 16) : GS_OP_FN(gs_step_tb, 4, 3, 2, 16);
     }
 #define GS_TB_CASE(KK, FF, CC)                                                                  \
-    case ((KK) * 4 + (FF)) * 8 + (CC): return reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_tb_k)<KK, FF, CC>);
+    case ((KK) * 4 + (FF)) * 8 + (CC): return GS_OP_FN(gs_step_tb, KK, FF, CC);
 #define GS_TB_CASES(FF, CC) GS_TB_CASE(1, FF, CC) GS_TB_CASE(2, FF, CC) GS_TB_CASE(3, FF, CC) GS_TB_CASE(4, FF, CC)
     switch ((k * 4 + fast) * 8 + cpl) {
         GS_TB_CASES(1, 4) GS_TB_CASES(3, 4)
@@ -661,5 +712,10 @@ const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg)
     }
 #undef GS_TB_CASES
 #undef GS_TB_CASE
+#undef GS_OP_FN
+}
+const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, bool per)
+{
+    return per ? tb_op_kernel<true>(k, fast, cpl, wg) : tb_op_kernel<false>(k, fast, cpl, wg);
 }
 #endif

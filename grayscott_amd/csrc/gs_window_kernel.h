@@ -686,6 +686,8 @@ __global__ __launch_bounds__(kWinWaves * 64) void GS_SUFFIX(gs_run_window_k)(GsS
     // One branch per workgroup, one instantiation per kind of window (as gs_step_tb_k): the cheap kinds exist for the
     // clipped rule with the default side weights in the strict build; a grid narrower than one window, general
     // weights and the fused build take the general path in their edge windows.
+    // (a.zero_halo is 0 or 1 here: the periodic rule has no form of this kernel -- gs_launch_window and gs_ctx_create
+    // refuse it.)
     const bool cheap = KINDS && a.edge_kinds;
     if (!edge) GS_WIN_RUN(0, -1);
     else if (a.zero_halo) GS_WIN_RUN(7, 1);

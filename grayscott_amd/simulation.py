@@ -78,7 +78,11 @@ def _env_int(name: str, default: int) -> int:
 class HipArgs:
     """Backend ``CliArgs``: every field has a default and an environment variable, as the
     reference requires so that its criterion harness can build a backend from the
-    environment alone (compute/shared/src/lib.rs:20-25, benchmark.rs:36-40)."""
+    environment alone (compute/shared/src/lib.rs:20-25, benchmark.rs:36-40).
+
+    ``boundary`` is the rule on the grid's edges (``gs_boundary``): ``capi.GS_BOUNDARY_CLIPPED`` (the parity
+    target), ``capi.GS_BOUNDARY_ZERO_HALO`` or ``capi.GS_BOUNDARY_PERIODIC`` -- the grid wraps around; one device
+    and one process only, and neither ``kernel`` = ``GS_KERNEL_WINDOW`` / ``GS_KERNEL_LDS`` nor ``split`` > 1."""
 
     devices: Sequence[int] = field(default_factory=lambda: [
         int(x) for x in os.environ.get("GS_HIP_DEVICES", "0").split(",") if x != ""])

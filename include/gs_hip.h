@@ -115,7 +115,9 @@ typedef enum gs_math { GS_MATH_STRICT = 0, GS_MATH_FUSED = 1 } gs_math;
  * is pinned: the LDS-resident whole-run kernel up to 1536 cells; WINDOW for calls of >= 32 steps on grids
  * from 0.8 M cells that one round of 80-row windows covers (one per compute unit; 8, 6, 4 or 2 steps per
  * exchange, as many as fit); TILE otherwise up to 1.5 M cells; TB with fuse_steps (default 4) otherwise, for
- * slab chains and whenever fuse_steps, rows_per_block, cols_per_lane, split or use_graph pin a schedule. */
+ * slab chains and whenever fuse_steps, rows_per_block, cols_per_lane, split or use_graph pin a schedule.
+ * Under GS_BOUNDARY_PERIODIC there is no WINDOW and no LDS form: pinning either is refused at gs_ctx_create
+ * (GS_ERR_UNSUPPORTED), and AUTO runs TB where it would have run WINDOW (1080 x 1920 in long calls, for one). */
 typedef enum gs_kernel {
     GS_KERNEL_AUTO = 0,    /* best measured variant for the shape                          */
     GS_KERNEL_SIMPLE = 1,  /* one thread per cell, global loads only (cross-check kernel)  */
@@ -147,8 +149,14 @@ typedef enum gs_kernel {
  *              (compute/naive/src/lib.rs:57-71);
  * ZERO_HALO -- the Vulkan and SIMD backends': full window, weights centred, cells outside the grid
  *              read as 0 (compute/gpu/naive/src/pipeline.rs:105-113, main.comp:37-44;
- *              data/src/concentration/simd/mod.rs:281-326), here with naive's operation order. */
-enum gs_boundary { GS_BOUNDARY_CLIPPED = 0, GS_BOUNDARY_ZERO_HALO = 1 };
+ *              data/src/concentration/simd/mod.rs:281-326), here with naive's operation order.
+ * PERIODIC  -- the grid wraps around (a torus), the usual setting of Gray-Scott studies: every cell takes the nine
+ *              taps of ZERO_HALO's interior cell, in its order, with neighbour (r + i - 1, c + j - 1) read at
+ *              ((r + i - 1) mod rows, (c + j - 1) mod cols) -- on 1 x N, N x 1 or 2 x 2 grids a neighbour can be
+ *              the cell itself.  Single slab in a single process only: a context of several slabs or processes,
+ *              a pinned GS_KERNEL_WINDOW or GS_KERNEL_LDS and split > 1 are refused at gs_ctx_create
+ *              (GS_ERR_UNSUPPORTED). */
+enum gs_boundary { GS_BOUNDARY_CLIPPED = 0, GS_BOUNDARY_ZERO_HALO = 1, GS_BOUNDARY_PERIODIC = 2 };
 
 /* Backend options: the C view of the Rust `CliArgs` (compute/shared/src/lib.rs:20-25 --
  * every field has a default; zero-initialise and override). */
@@ -383,8 +391,8 @@ int32_t gs_ctx_stats(gs_ctx *ctx, gs_stats *out);
 int32_t gs_ctx_set_pass_timing(gs_ctx *ctx, int32_t passes);
 
 /* Introspection for tests and the bench: name of the kernel variant last launched
- * ("tb-k4/strict@32x2" = 4 fused steps, strict math, tuned: 32-row units, 2 row bands) and the number of
- * kernel launches so far. */
+ * ("tb-k4/strict@32x2" = 4 fused steps, strict math, tuned: 32-row units, 2 row bands; the periodic rule's kernels
+ * carry "/periodic": "tb-k4c2/strict.op.dx/periodic@38x1") and the number of kernel launches so far. */
 int32_t gs_ctx_info(const gs_ctx *ctx, char *kernel_name, size_t cap, uint64_t *launches);
 
 /* Ensembles: `members` independent simulations of one shape rows x cols, advanced in shared launches -- a sweep over
@@ -400,7 +408,7 @@ int32_t gs_ctx_info(const gs_ctx *ctx, char *kernel_name, size_t cap, uint64_t *
  *   upload        members [first, first + count); `u` or `v` may be NULL to leave that species as it is.  Blocking.
  *   download      species 0 = U, 1 = V of members [first, first + count).  Blocking.
  *   run           asynchronous, like gs_run (gs_sync waits).  Members of at most 4096 cells (8192 under the zero-halo
- *                 rule, and 160 KiB of LDS) stay in one workgroup's LDS for the whole call ("ensemble-resident"); larger
+ *                 and periodic rules, and 160 KiB of LDS) stay in one workgroup's LDS for the whole call ("ensemble-resident"); larger
  *                 ones advance up to 8 steps per launch on LDS-resident windows ("ensemble-tile32x64" ...), with the
  *                 window and steps per launch chosen over the workgroups of the whole ensemble.  gs_ctx_info names it. */
 typedef struct gs_ensemble gs_ensemble;

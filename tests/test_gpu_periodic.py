@@ -1,0 +1,257 @@
+"""The periodic boundary rule on the MI355X: every kernel that kernel = AUTO or a pin reaches on a single slab, bit for bit
+against the pad-and-crop reference (tests/periodic_ref.py) in strict math and under the existing contract in fused math;
+translation invariance (which the clipped and zero-halo rules do not have, so a site that falls back to either fails
+it); ensembles against lone periodic Species; the refusals; and the simulate driver end to end."""
+from __future__ import annotations
+
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle
+from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi, hdf5_min
+
+from . import periodic_ref
+from .helpers import assert_bits_equal, gpu_run, oracle_params, species_from_arrays, stress_fields
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+P = capi.GS_BOUNDARY_PERIODIC
+
+
+def args(**kw):
+    kw.setdefault("devices", [0])
+    kw.setdefault("boundary", P)
+    return HipArgs(**kw)
+
+
+def fields(shape, seed):
+    """seed < 0: Species::new's pattern; else the stress fields."""
+    return oracle.init_species(*shape) if seed < 0 else stress_fields(shape, seed)
+
+
+# ---- AUTO: every path by shape; calls of 1, 2, 4, 26 and 67 steps = 1, 3, 7, 33 and 100 steps in all ----------------
+AUTO_SHAPES = [(1, 1), (1, 9), (7, 1), (2, 2), (3, 5),    # tiny and degenerate: the LDS-resident kernel
+               (40, 37),                                  # resident, 1480 cells
+               (256, 512), (1000, 1003),                  # LDS-resident windows
+               (1080, 1920), (777, 2049), (1500, 1503)]   # the marching kernel
+CALLS = (1, 2, 4, 26, 67)
+
+
+@pytest.mark.parametrize("shape", AUTO_SHAPES)
+@pytest.mark.parametrize("seed", [-1, 5])
+def test_auto_matches_the_reference(shape, seed):
+    u0, v0 = fields(shape, seed)
+    sim = Simulation.new(Parameters(), args())
+    species = species_from_arrays(sim, u0, v0)
+    ref_u, ref_v, done = u0, v0, 0
+    names = []
+    try:
+        for n in CALLS:
+            sim.perform_steps(species, n)
+            ref_u, ref_v = periodic_ref.run(ref_u, ref_v, n)
+            done += n
+            name = sim.context.info()[0]
+            names.append(name)
+            assert name.split("@")[0].endswith("/periodic"), name
+            iu, iv, _, _ = species.in_out()
+            assert_bits_equal(iu.make_scalar_view(sim.context), ref_u, f"U {shape} after {done} ({name})")
+            assert_bits_equal(iv.make_scalar_view(sim.context), ref_v, f"V {shape} after {done} ({name})")
+    finally:
+        sim.context.close()
+    cells = shape[0] * shape[1]
+    want = "resident-lds" if cells <= 1536 else ("tile" if cells < 1_500_000 else "tb-")
+    assert names[-1].startswith(want), (shape, names)
+
+
+# ---- pinned kernels --------------------------------------------------------------------------------------------------
+PIN_SHAPES = [(1, 1), (1, 9), (7, 1), (2, 2), (3, 5), (40, 37), (129, 250), (300, 701)]
+
+
+@pytest.mark.parametrize("kernel", [capi.GS_KERNEL_SIMPLE, capi.GS_KERNEL_STREAM])
+@pytest.mark.parametrize("shape", PIN_SHAPES + [(9, 257), (33, 255), (64, 1024)])
+def test_single_step_kernels(shape, kernel):
+    u0, v0 = stress_fields(shape, 11)
+    ref_u, ref_v = periodic_ref.run(u0, v0, 7)
+    got_u, got_v, info = gpu_run(u0, v0, 7, args=args(kernel=kernel), stepwise=True)
+    assert info[0].endswith("/periodic"), info
+    assert_bits_equal(got_u, ref_u, f"U {shape} {info[0]}")
+    assert_bits_equal(got_v, ref_v, f"V {shape} {info[0]}")
+
+
+TB_CONFIGS = ([dict(cols_per_lane=c, fuse_steps=k) for c in (1, 2, 4) for k in (1, 2, 3, 4)]
+              + [dict(cols_per_lane=2, fuse_steps=k, share_taps=s) for s in (1, 2, 3) for k in (2, 3, 4)]
+              + [dict(cols_per_lane=c, fuse_steps=4, general_kernels=1) for c in (1, 2, 4)]
+              + [dict(cols_per_lane=2, fuse_steps=4, use_graph=1), dict(fuse_steps=4, use_graph=1, rows_per_block=8)])
+
+
+@pytest.mark.parametrize("cfg", TB_CONFIGS, ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
+def test_marching_kernel_pinned(cfg):
+    for shape in PIN_SHAPES + [(1000, 1003)]:
+        u0, v0 = stress_fields(shape, 3)
+        steps = 37 if cfg.get("use_graph") else 11  # (a graph batch is 16 passes)
+        ref_u, ref_v = periodic_ref.run(u0, v0, steps)
+        got_u, got_v, info = gpu_run(u0, v0, steps, args=args(kernel=capi.GS_KERNEL_TB, no_tune=1, **cfg))
+        assert info[0].startswith("tb-") and info[0].split("@")[0].endswith("/periodic"), info
+        assert_bits_equal(got_u, ref_u, f"U {shape} {cfg} {info[0]}")
+        assert_bits_equal(got_v, ref_v, f"V {shape} {cfg} {info[0]}")
+
+
+@pytest.mark.parametrize("tile_shape", [1, 2, 3])
+@pytest.mark.parametrize("fuse", [0, 1, 3])
+def test_tile_kernel_pinned(tile_shape, fuse):
+    for shape in PIN_SHAPES + [(1000, 1003)]:
+        u0, v0 = stress_fields(shape, 4)
+        ref_u, ref_v = periodic_ref.run(u0, v0, 19)
+        got_u, got_v, info = gpu_run(u0, v0, 19, args=args(kernel=capi.GS_KERNEL_TILE, tile_shape=tile_shape, fuse_steps=fuse))
+        assert info[0].startswith("tile") and info[0].endswith("/periodic"), info
+        assert_bits_equal(got_u, ref_u, f"U {shape} {info[0]}")
+        assert_bits_equal(got_v, ref_v, f"V {shape} {info[0]}")
+
+
+def test_general_parameters():
+    """The general (non-.op) variants under AUTO: other weights, rates and dt."""
+    w = ((1 / 6, 4 / 6, 1 / 6), (4 / 6, 0.0, 4 / 6), (1 / 6, 4 / 6, 1 / 6))
+    p = Parameters(weights=w, feed_rate=0.03, kill_rate=0.06, time_step=0.5, diffusion_rate_u=0.12, diffusion_rate_v=0.06)
+    for shape in [(3, 5), (40, 37), (256, 512), (1080, 1920)]:
+        u0, v0 = stress_fields(shape, 8)
+        ref_u, ref_v = periodic_ref.run(u0, v0, 9, params=oracle_params(p))
+        got_u, got_v, info = gpu_run(u0, v0, 9, params=p, args=args())
+        assert ".op" not in info[0], info
+        assert_bits_equal(got_u, ref_u, f"U {shape} {info[0]}")
+        assert_bits_equal(got_v, ref_v, f"V {shape} {info[0]}")
+
+
+# ---- fused math: bit for bit where no intermediate is sub-normal, within 1e-37 where one is ---------------------------
+@pytest.mark.parametrize("shape", [(3, 5), (40, 37), (250, 130), (1080, 1920)])
+def test_fused_flavour(shape):
+    u0, v0 = stress_fields(shape, 1)
+    ref_u, ref_v = periodic_ref.run(u0, v0, 20)
+    got_u, got_v, info = gpu_run(u0, v0, 20, args=args(math=capi.GS_MATH_FUSED))
+    assert "fused" in info[0] and info[0].split("@")[0].endswith("/periodic"), info
+    assert_bits_equal(got_u, ref_u, f"fused U {shape}")
+    assert_bits_equal(got_v, ref_v, f"fused V {shape}")
+    u0, v0 = oracle.init_species(64, 128)
+    ref_u, ref_v = periodic_ref.run(u0, v0, 100)
+    got_u, got_v, _ = gpu_run(u0, v0, 100, args=args(math=capi.GS_MATH_FUSED))
+    assert_bits_equal(got_u, ref_u, "fused U with a sub-normal V front")
+    assert np.max(np.abs(got_v.astype(np.float64) - ref_v.astype(np.float64))) <= 1e-37
+
+
+# ---- translation invariance ------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("shape,steps", [((1080, 1920), 64), ((300, 701), 33)])
+def test_translation_invariance(shape, steps):
+    u0, v0 = oracle.init_species(*shape)
+    rng = np.random.default_rng(2)
+    u0 = (u0 - rng.random(shape, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
+    base_u, base_v, info = gpu_run(u0, v0, steps, args=args())
+    for dy, dx in [(1, 0), (0, 1), (-7, 5), (shape[0] // 2 + 3, -(shape[1] // 3) - 1)]:
+        su, sv, sinfo = gpu_run(np.roll(u0, (dy, dx), (0, 1)), np.roll(v0, (dy, dx), (0, 1)), steps, args=args())
+        assert_bits_equal(np.roll(su, (-dy, -dx), (0, 1)), base_u, f"U shifted by {(dy, dx)} ({sinfo[0]})")
+        assert_bits_equal(np.roll(sv, (-dy, -dx), (0, 1)), base_v, f"V shifted by {(dy, dx)} ({sinfo[0]})")
+    # ... which the other two rules do not have
+    for rule in (capi.GS_BOUNDARY_CLIPPED, capi.GS_BOUNDARY_ZERO_HALO):
+        cu, _, _ = gpu_run(u0, v0, steps, args=args(boundary=rule))
+        su, _, _ = gpu_run(np.roll(u0, (3, 4), (0, 1)), np.roll(v0, (3, 4), (0, 1)), steps, args=args(boundary=rule))
+        assert np.roll(su, (-3, -4), (0, 1)).tobytes() != cu.tobytes(), rule
+
+
+# ---- ensembles -------------------------------------------------------------------------------------------------------
+PARAMS = [Parameters(),
+          Parameters(feed_rate=0.030, kill_rate=0.060),
+          Parameters(feed_rate=0.022, kill_rate=0.051, diffusion_rate_u=0.12, diffusion_rate_v=0.06),
+          Parameters(feed_rate=0.018, kill_rate=0.049, diffusion_rate_v=0.03, time_step=2.0)]
+
+
+@pytest.mark.parametrize("math", [capi.GS_MATH_STRICT, capi.GS_MATH_FUSED])
+@pytest.mark.parametrize("shape,steps,form", [((16, 32), 37, "ensemble-resident"), ((1, 5), 9, "ensemble-resident"),
+                                              ((37, 53), 37, "ensemble-tile"), ((100, 300), 21, "ensemble-tile")])
+def test_ensemble_members_are_lone_species(shape, steps, form, math):
+    pairs = [stress_fields(shape, 100 + i) for i in range(len(PARAMS))]
+    u0, v0 = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+    sim = Simulation.new(PARAMS[0], args(math=math))
+    ens = sim.make_ensemble(shape, PARAMS, seed=False)
+    ens.upload(u0, v0)
+    for n in (steps // 3, steps - steps // 3):
+        ens.prepare_steps(n)
+    u, v = ens.u_views(), ens.result_views()
+    name = sim.context.info()[0]
+    ens.destroy()
+    sim.context.close()
+    assert name.startswith(form) and name.endswith("/periodic"), name
+    for i, p in enumerate(PARAMS):
+        lu, lv, info = gpu_run(u0[i], v0[i], steps, params=p, args=args(math=math))
+        assert_bits_equal(u[i], lu, f"U of member {i} ({name}) against a lone Species ({info[0]})")
+        assert_bits_equal(v[i], lv, f"V of member {i} ({name}) against a lone Species ({info[0]})")
+        if math == capi.GS_MATH_STRICT:
+            ref_u, ref_v = periodic_ref.run(u0[i], v0[i], steps, params=oracle_params(p))
+            assert_bits_equal(u[i], ref_u, f"U of member {i} ({name})")
+            assert_bits_equal(v[i], ref_v, f"V of member {i} ({name})")
+
+
+def test_resident_ensemble_takes_8192_cells():
+    """The resident form's capacity is the zero-halo rule's: 8 cells per thread."""
+    shape, members = (64, 120), 256
+    rng = np.random.default_rng(9)
+    u0 = rng.random((members,) + shape, dtype=np.float32)
+    v0 = (rng.random((members,) + shape, dtype=np.float32) * np.float32(0.5)).astype(np.float32)
+    sim = Simulation.new(Parameters(), args())
+    ens = sim.make_ensemble(shape, [Parameters()] * members, seed=False)
+    ens.upload(u0, v0)
+    ens.prepare_steps(6)
+    u, v = ens.u_views(), ens.result_views()
+    name = sim.context.info()[0]
+    ens.destroy()
+    sim.context.close()
+    assert name.startswith("ensemble-resident") and name.endswith("/periodic"), name
+    for i in (0, 77, members - 1):
+        ref_u, ref_v = periodic_ref.run(u0[i], v0[i], 6)
+        assert_bits_equal(u[i], ref_u, f"U of member {i}")
+        assert_bits_equal(v[i], ref_v, f"V of member {i}")
+
+
+# ---- refusals --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kw,what", [(dict(devices=[0, 0]), "single slab"), (dict(kernel=capi.GS_KERNEL_WINDOW), "window"),
+                                     (dict(kernel=capi.GS_KERNEL_LDS), "LDS-staged"), (dict(split=2), "row bands")])
+def test_refusals(kw, what):
+    with pytest.raises(GsError) as e:
+        Simulation.new(Parameters(), args(**kw))
+    assert e.value.code == capi.GS_ERR_UNSUPPORTED
+    assert "periodic" in str(e.value) and what in str(e.value), str(e.value)
+
+
+def test_auto_takes_the_marching_kernel_where_the_window_kernel_would_run():
+    u0, v0 = oracle.init_species(1080, 1920)
+    sim = Simulation.new(Parameters(), args())
+    species = species_from_arrays(sim, u0, v0)
+    for _ in range(3):
+        sim.perform_steps(species, 64)
+    name = sim.context.info()[0]
+    iu, iv, _, _ = species.in_out()
+    got_v = iv.make_scalar_view(sim.context)
+    sim.context.close()
+    assert name.startswith("tb-") and name.split("@")[0].endswith("/periodic"), name
+    assert_bits_equal(got_v, periodic_ref.run(u0, v0, 192)[1], "V after 3 x 64 steps")
+    # ... while the zero-halo rule's context runs the window kernel there
+    sim = Simulation.new(Parameters(), args(boundary=capi.GS_BOUNDARY_ZERO_HALO))
+    species = species_from_arrays(sim, u0, v0)
+    sim.perform_steps(species, 64)
+    assert sim.context.info()[0].startswith("window"), sim.context.info()
+    sim.context.close()
+
+
+# ---- the driver end to end -------------------------------------------------------------------------------------------
+def test_simulate_end_to_end(tmp_path):
+    out = tmp_path / "p.h5"
+    r = subprocess.run([sys.executable, "-m", "grayscott_amd.simulate", "--hip-boundary", "2", "-r", "64", "-c", "128",
+                        "-n", "3", "-e", "32", "-o", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    data = hdf5_min.read(str(out))
+    assert data.shape == (3, 64, 128)
+    u, v = oracle.init_species(64, 128)
+    for i in range(3):
+        u, v = periodic_ref.run(u, v, 32)
+        assert_bits_equal(np.asarray(data[i]), v, f"image {i} (after {32 * (i + 1)} steps)")
