@@ -126,6 +126,19 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 }
 #endif
 
+// Launch tables.  GS_FN: the entry of a kernel instance.  kOp: the FAST argument of the ".op" variant (the fused build
+// has none: its launchers reduce `fast` to 0).  GS_NAME: the name a launcher reports for kernel family BASE, variant V
+// ("", ".op", ...) under the boundary rule of suffix R; GS_RULES: a table of such names per rule ("" for the clipped
+// and zero-halo rules, which share their kernels, then "/periodic") from one macro M(BASE, R).
+#define GS_FN(KER, ...) reinterpret_cast<const void *>(&GS_SUFFIX(KER)<__VA_ARGS__>)
+constexpr int kOp = GS_MATH_FUSED ? 0 : 3;
+#define GS_NAME(BASE, V, R) BASE "/" GS_MATH_NAME V R
+#define GS_RULES(M, BASE) {M(BASE, ""), M(BASE, "/periodic")}
+#define GS_NAMES_OP(BASE, R) {GS_NAME(BASE, "", R), GS_NAME(BASE, ".op", R)}
+// [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
+#define GS_TILE_NAMES(BASE, R) {GS_NAMES_OP(BASE "tile32x64", R), GS_NAMES_OP(BASE "tile16x64", R), GS_NAMES_OP(BASE "tile64x64", R)}
+#define GS_TILE_FNS(KER) {{GS_FN(KER, 2, 0), GS_FN(KER, 2, kOp)}, {GS_FN(KER, 1, 0), GS_FN(KER, 1, kOp)}, {GS_FN(KER, 4, 0), GS_FN(KER, 4, kOp)}}
+
 hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name)
 {
     const bool per = a.zero_halo == 2; // the periodic rule: a kernel of its own
@@ -147,8 +160,11 @@ hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const
 // the result is stored in the out-planes when steps is odd, else back in the in-planes.
 hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStream_t s, const char **name)
 {
-    static const char *const names[2][2] = {{"resident-lds/" GS_MATH_NAME, "resident-lds/" GS_MATH_NAME ".op"},
-                                            {"resident-lds/" GS_MATH_NAME "/periodic", "resident-lds/" GS_MATH_NAME ".op/periodic"}};
+    static const char *const names[2][2] = GS_RULES(GS_NAMES_OP, "resident-lds");
+    // [rule][variant]
+    static const void *const fns[3][2] = {{GS_FN(gs_run_resident_k, 0, 0), GS_FN(gs_run_resident_k, kOp, 0)},
+                                          {GS_FN(gs_run_resident_k, 0, 1), GS_FN(gs_run_resident_k, kOp, 1)},
+                                          {GS_FN(gs_run_resident_pk, 0), GS_FN(gs_run_resident_pk, kOp)}};
     const long cells = (long)a.rows * a.cols;
     if (a.rows <= 0 || a.cols <= 0 || cells > kResidentCells || steps < 0 || a.top_present || a.bottom_present)
         return hipErrorInvalidValue;
@@ -156,13 +172,7 @@ hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStre
     if (fast != 3) fast = 0; // only the variant for the default parameters is built besides the general one
     const int zh = a.zero_halo == 2 ? 2 : (a.zero_halo ? 1 : 0); // gs_boundary
     if (name) *name = names[zh == 2][fast ? 1 : 0];
-    const void *fn = nullptr;
-#define GS_RES_FN(F, Z) reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_resident_k)<F, Z>)
-#define GS_RES_PFN(F) reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_resident_pk)<F>)
-    if (fast) fn = zh == 2 ? GS_RES_PFN(GS_MATH_FUSED ? 0 : 3) : zh ? GS_RES_FN(GS_MATH_FUSED ? 0 : 3, 1) : GS_RES_FN(GS_MATH_FUSED ? 0 : 3, 0);
-    else fn = zh == 2 ? GS_RES_PFN(0) : zh ? GS_RES_FN(0, 1) : GS_RES_FN(0, 0);
-#undef GS_RES_FN
-#undef GS_RES_PFN
+    const void *fn = fns[zh][fast ? 1 : 0];
     const size_t lds = (size_t)4 * (a.rows + 2) * (a.cols + 2) * sizeof(float); // <= 74 KB (1 x 1536 cells)
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
         const hipError_t e = ensure_dyn_lds(fn, lds > 64 * 1024 ? (size_t)80 * 1024 : lds);
@@ -181,13 +191,8 @@ hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStre
 // 2K < window rows.
 hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name)
 {
-    static const char *const names[2][3][2] = {
-        {{"tile32x64/" GS_MATH_NAME, "tile32x64/" GS_MATH_NAME ".op"},
-         {"tile16x64/" GS_MATH_NAME, "tile16x64/" GS_MATH_NAME ".op"},
-         {"tile64x64/" GS_MATH_NAME, "tile64x64/" GS_MATH_NAME ".op"}},
-        {{"tile32x64/" GS_MATH_NAME "/periodic", "tile32x64/" GS_MATH_NAME ".op/periodic"},
-         {"tile16x64/" GS_MATH_NAME "/periodic", "tile16x64/" GS_MATH_NAME ".op/periodic"},
-         {"tile64x64/" GS_MATH_NAME "/periodic", "tile64x64/" GS_MATH_NAME ".op/periodic"}}};
+    static const char *const names[2][3][2] = GS_RULES(GS_TILE_NAMES, "");
+    static const void *const fns[2][3][2] = {GS_TILE_FNS(gs_run_tile_k), GS_TILE_FNS(gs_run_tile_pk)};
     static const int rpw[3] = {2, 1, 4};
     const bool per = a.zero_halo == 2; // the periodic rule: gs_run_tile_pk
     if (a.rows <= 0 || a.cols <= 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || a.top_present || a.bottom_present ||
@@ -199,14 +204,7 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
     const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
     const long tiles = ((a.rows + ho - 1) / ho) * ((a.cols + wo - 1) / wo);
     if (tiles > 0x7fffffffL) return hipErrorInvalidConfiguration;
-    const void *fn = nullptr;
-#define GS_TILE_FN(S, RPW_)                                                                                   \
-    case S: fn = per ? (fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_pk)<RPW_, GS_MATH_FUSED ? 0 : 3>) \
-                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_pk)<RPW_, 0>))                   \
-                     : fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_k)<RPW_, GS_MATH_FUSED ? 0 : 3>)  \
-                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_run_tile_k)<RPW_, 0>); break;
-    switch (shape) { GS_TILE_FN(0, 2) GS_TILE_FN(1, 1) GS_TILE_FN(2, 4) }
-#undef GS_TILE_FN
+    const void *fn = fns[per][shape][fast ? 1 : 0];
     size_t lds = tile_lds_bytes(rpw[shape]);
     static const int lds_floor = gs_env_int("GS_HIP_TILE_LDS_FLOOR", 0, 0, 160 * 1024);
     if (lds < (size_t)lds_floor) lds = (size_t)lds_floor; // experiment: limit the workgroups per CU
@@ -227,8 +225,15 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
 // odd, else back in the in-planes.
 hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[2][2] = {{"ensemble-resident/" GS_MATH_NAME, "ensemble-resident/" GS_MATH_NAME ".op"},
-                                            {"ensemble-resident/" GS_MATH_NAME "/periodic", "ensemble-resident/" GS_MATH_NAME ".op/periodic"}};
+    static const char *const names[2][2] = GS_RULES(GS_NAMES_OP, "ensemble-resident");
+    // [rule][variant][cells per thread: 1, 2, 4, 8]; the clipped rule has no 8-cell form (gs_ens_resident_cpt)
+#define GS_CPT_FNS(KER, ...) {GS_FN(KER, 1, __VA_ARGS__), GS_FN(KER, 2, __VA_ARGS__), GS_FN(KER, 4, __VA_ARGS__), GS_FN(KER, 8, __VA_ARGS__)}
+    static const void *const fns[3][2][4] = {
+        {{GS_FN(gs_ens_resident_k, 1, 0, 0), GS_FN(gs_ens_resident_k, 2, 0, 0), GS_FN(gs_ens_resident_k, 4, 0, 0), nullptr},
+         {GS_FN(gs_ens_resident_k, 1, kOp, 0), GS_FN(gs_ens_resident_k, 2, kOp, 0), GS_FN(gs_ens_resident_k, 4, kOp, 0), nullptr}},
+        {GS_CPT_FNS(gs_ens_resident_k, 0, 1), GS_CPT_FNS(gs_ens_resident_k, kOp, 1)},
+        {GS_CPT_FNS(gs_ens_resident_pk, 0), GS_CPT_FNS(gs_ens_resident_pk, kOp)}};
+#undef GS_CPT_FNS
     const long cells = (long)e.rows * e.cols;
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0) return hipErrorInvalidValue;
     const long threads = cells >= 1024 ? 1024 : ((cells + 63) / 64) * 64; // the waves that hold cells
@@ -238,21 +243,7 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
     fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
     const int zh = e.zero_halo == 2 ? 2 : (e.zero_halo ? 1 : 0); // gs_boundary
     if (name) *name = names[zh == 2][fast ? 1 : 0];
-    const void *fn = nullptr;
-#define GS_ENS_RES_FN(C)                                                                                                    \
-    case C: fn = fast ? (zh == 2 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<C, GS_MATH_FUSED ? 0 : 3>)   \
-                       : zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, GS_MATH_FUSED ? 0 : 3, 1>)        \
-                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, GS_MATH_FUSED ? 0 : 3, 0>))       \
-                      : (zh == 2 ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<C, 0>)                        \
-                       : zh ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, 0, 1>)                             \
-                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<C, 0, 0>)); break;
-    switch (cpt) { GS_ENS_RES_FN(1) GS_ENS_RES_FN(2) GS_ENS_RES_FN(4) }
-#undef GS_ENS_RES_FN
-    if (cpt == 8) // zero-halo and periodic rules only (gs_ens_resident_cpt)
-        fn = zh == 2 ? (fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<8, GS_MATH_FUSED ? 0 : 3>)
-                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_pk)<8, 0>))
-                     : fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, GS_MATH_FUSED ? 0 : 3, 1>)
-                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_resident_k)<8, 0, 1>);
+    const void *fn = fns[zh][fast ? 1 : 0][__builtin_ctz(cpt)];
     if (!fn) return hipErrorInvalidValue;
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
         const hipError_t err = ensure_dyn_lds(fn, lds);
@@ -273,13 +264,8 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
 // Windowed form: K <= kGsTileMaxSteps steps of every member (in-planes -> out-planes); `shape` as gs_launch_tile's.
 hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[2][3][2] = {
-        {{"ensemble-tile32x64/" GS_MATH_NAME, "ensemble-tile32x64/" GS_MATH_NAME ".op"},
-         {"ensemble-tile16x64/" GS_MATH_NAME, "ensemble-tile16x64/" GS_MATH_NAME ".op"},
-         {"ensemble-tile64x64/" GS_MATH_NAME, "ensemble-tile64x64/" GS_MATH_NAME ".op"}},
-        {{"ensemble-tile32x64/" GS_MATH_NAME "/periodic", "ensemble-tile32x64/" GS_MATH_NAME ".op/periodic"},
-         {"ensemble-tile16x64/" GS_MATH_NAME "/periodic", "ensemble-tile16x64/" GS_MATH_NAME ".op/periodic"},
-         {"ensemble-tile64x64/" GS_MATH_NAME "/periodic", "ensemble-tile64x64/" GS_MATH_NAME ".op/periodic"}}};
+    static const char *const names[2][3][2] = GS_RULES(GS_TILE_NAMES, "ensemble-");
+    static const void *const fns[2][3][2] = {GS_TILE_FNS(gs_ens_tile_k), GS_TILE_FNS(gs_ens_tile_pk)};
     static const int rpw[3] = {2, 1, 4};
     const bool per = e.zero_halo == 2; // the periodic rule: gs_ens_tile_pk
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]))
@@ -289,14 +275,7 @@ hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, i
     const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
     const long windows = ((e.rows + ho - 1) / ho) * ((e.cols + wo - 1) / wo);
     if (windows > kGsEnsMaxGroups) return hipErrorInvalidConfiguration;
-    const void *fn = nullptr;
-#define GS_ENS_TILE_FN(S, RPW_)                                                                                   \
-    case S: fn = per ? (fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_pk)<RPW_, GS_MATH_FUSED ? 0 : 3>) \
-                             : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_pk)<RPW_, 0>))                   \
-                     : fast ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, GS_MATH_FUSED ? 0 : 3>)  \
-                            : reinterpret_cast<const void *>(&GS_SUFFIX(gs_ens_tile_k)<RPW_, 0>); break;
-    switch (shape) { GS_ENS_TILE_FN(0, 2) GS_ENS_TILE_FN(1, 1) GS_ENS_TILE_FN(2, 4) }
-#undef GS_ENS_TILE_FN
+    const void *fn = fns[per][shape][fast ? 1 : 0];
     const size_t lds = tile_lds_bytes(rpw[shape]);
     {
         const hipError_t err = ensure_dyn_lds(fn, lds);
@@ -378,40 +357,28 @@ hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const
 // the periodic rule's form (gs_step_tb_pk).
 static const void *tb_entry(int k, int fast, int cpl, int wg = 4, bool per = false)
 {
-    const void *fn = nullptr;
-#define GS_TB_FN(KER, KK, F, CC, WG_) (per ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_pk)<KK, F, CC, WG_>) \
-                                           : reinterpret_cast<const void *>(&GS_SUFFIX(KER##_k)<KK, F, CC, WG_>))
-#define GS_TB_CASE(KK, CC)                                                                      \
-    case (KK) * 8 + (CC): fn = GS_TB_FN(gs_step_tb, KK, 0, CC, 4); break;
-    if (wg == 16) { // the fair-progress form: 4 fused steps, 1 or 2 columns per lane
-        if (k != 4 || (cpl != 1 && cpl != 2)) return nullptr;
-        if (fast) {
-#if !GS_MATH_FUSED
-            return gs_tb_op_kernel_strict(k, fast, cpl, 16, per);
-#endif
-        }
+    // the general variant's entries: [rule][cpl 1, 2, 4][k - 1] of 4-wave workgroups, [rule][cpl 1, 2] of the
+    // fair-progress form (16-wave workgroups, 4 fused steps)
+#define GS_TB_FNS(KER, C) {GS_FN(KER, 1, 0, C, 4), GS_FN(KER, 2, 0, C, 4), GS_FN(KER, 3, 0, C, 4), GS_FN(KER, 4, 0, C, 4)}
+    static const void *const fns[2][3][4] = {{GS_TB_FNS(gs_step_tb_k, 1), GS_TB_FNS(gs_step_tb_k, 2), GS_TB_FNS(gs_step_tb_k, 4)},
+                                             {GS_TB_FNS(gs_step_tb_pk, 1), GS_TB_FNS(gs_step_tb_pk, 2), GS_TB_FNS(gs_step_tb_pk, 4)}};
+#undef GS_TB_FNS
 #if GS_MATH_FUSED
-        // (2 columns per lane need 129 registers in the fused flavour, one more than a wave of a 16-wave workgroup may have:
-        // the variant spilled a register to scratch; one-round launches of the fused flavour run as 4-wave workgroups)
-        if (cpl == 2) return nullptr;
-        return GS_TB_FN(gs_step_tb, 4, 0, 1, 16);
+    // (2 columns per lane need 129 registers in the fused flavour, one more than a wave of a 16-wave workgroup may have:
+    // the variant spilled a register to scratch; one-round launches of the fused flavour run as 4-wave workgroups)
+    static const void *const fns16[2][2] = {{GS_FN(gs_step_tb_k, 4, 0, 1, 16), nullptr}, {GS_FN(gs_step_tb_pk, 4, 0, 1, 16), nullptr}};
 #else
-        return cpl == 1 ? GS_TB_FN(gs_step_tb, 4, 0, 1, 16) : GS_TB_FN(gs_step_tb, 4, 0, 2, 16);
+    static const void *const fns16[2][2] = {{GS_FN(gs_step_tb_k, 4, 0, 1, 16), GS_FN(gs_step_tb_k, 4, 0, 2, 16)},
+                                            {GS_FN(gs_step_tb_pk, 4, 0, 1, 16), GS_FN(gs_step_tb_pk, 4, 0, 2, 16)}};
 #endif
-    }
+    if (wg == 16 && (k != 4 || (cpl != 1 && cpl != 2))) return nullptr;
     if (fast) {
 #if !GS_MATH_FUSED
-        fn = gs_tb_op_kernel_strict(k, fast, cpl, 4, per);
+        return gs_tb_op_kernel_strict(k, fast, cpl, wg, per);
 #endif
-    } else {
-        switch (k * 8 + cpl) {
-            GS_TB_CASE(1, 4) GS_TB_CASE(2, 4) GS_TB_CASE(3, 4) GS_TB_CASE(4, 4)
-            GS_TB_CASE(1, 2) GS_TB_CASE(2, 2) GS_TB_CASE(3, 2) GS_TB_CASE(4, 2)
-            GS_TB_CASE(1, 1) GS_TB_CASE(2, 1) GS_TB_CASE(3, 1) GS_TB_CASE(4, 1)
-        }
     }
-#undef GS_TB_CASE
-    return fn;
+    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4)) return nullptr;
+    return wg == 16 ? fns16[per][cpl - 1] : fns[per][cpl == 4 ? 2 : cpl - 1][k - 1];
 }
 
 // Waves per SIMD the register file allows a kernel entry: 512 registers per lane, allocated in steps
@@ -474,32 +441,20 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // "cN": N columns per lane (4 = the wide layout); ".op": the variant specialised for the
     // default (Oono-Puri) side weights, with or without dt == 1
     // ".op.ds": ... and with full difference sharing (cells_vshare)
-#define GS_TB_NAMES(C)                                                                          \
-    {{"tb-k1" C "/" GS_MATH_NAME, "tb-k2" C "/" GS_MATH_NAME, "tb-k3" C "/" GS_MATH_NAME, "tb-k4" C "/" GS_MATH_NAME}, \
-     {"tb-k1" C "/" GS_MATH_NAME ".op", "tb-k2" C "/" GS_MATH_NAME ".op", "tb-k3" C "/" GS_MATH_NAME ".op",            \
-      "tb-k4" C "/" GS_MATH_NAME ".op"},                                                        \
-     {"tb-k1" C "/" GS_MATH_NAME ".op.ds", "tb-k2" C "/" GS_MATH_NAME ".op.ds", "tb-k3" C "/" GS_MATH_NAME ".op.ds",   \
-      "tb-k4" C "/" GS_MATH_NAME ".op.ds"},                                                     \
-     {"tb-k1" C "/" GS_MATH_NAME ".op.dx", "tb-k2" C "/" GS_MATH_NAME ".op.dx", "tb-k3" C "/" GS_MATH_NAME ".op.dx",   \
-      "tb-k4" C "/" GS_MATH_NAME ".op.dx"}}
     // ".op.dx": ... and across lanes (cells_xshare)
-    static const char *const names[3][4][4] = {GS_TB_NAMES("c1"), GS_TB_NAMES("c2"), GS_TB_NAMES("")};
-#undef GS_TB_NAMES
-#define GS_TB_NAMES(C, M) {"tb-k1" C "/" GS_MATH_NAME M "/periodic", "tb-k2" C "/" GS_MATH_NAME M "/periodic", \
-                           "tb-k3" C "/" GS_MATH_NAME M "/periodic", "tb-k4" C "/" GS_MATH_NAME M "/periodic"}
-#define GS_TB_NAMES4(C) {GS_TB_NAMES(C, ""), GS_TB_NAMES(C, ".op"), GS_TB_NAMES(C, ".op.ds"), GS_TB_NAMES(C, ".op.dx")}
-    static const char *const names_p[3][4][4] = {GS_TB_NAMES4("c1"), GS_TB_NAMES4("c2"), GS_TB_NAMES4("")};
-#undef GS_TB_NAMES4
-#undef GS_TB_NAMES
     // "f": the fair-progress form (16-wave workgroups) of one-round launches
-    static const char *const names16[2][4] = {
-        {"tb-k4c1f/" GS_MATH_NAME, "tb-k4c1f/" GS_MATH_NAME ".op", "tb-k4c1f/" GS_MATH_NAME ".op.ds", "tb-k4c1f/" GS_MATH_NAME ".op.dx"},
-        {"tb-k4c2f/" GS_MATH_NAME, "tb-k4c2f/" GS_MATH_NAME ".op", "tb-k4c2f/" GS_MATH_NAME ".op.ds", "tb-k4c2f/" GS_MATH_NAME ".op.dx"}};
-    static const char *const names16_p[2][4] = {
-        {"tb-k4c1f/" GS_MATH_NAME "/periodic", "tb-k4c1f/" GS_MATH_NAME ".op/periodic", "tb-k4c1f/" GS_MATH_NAME ".op.ds/periodic",
-         "tb-k4c1f/" GS_MATH_NAME ".op.dx/periodic"},
-        {"tb-k4c2f/" GS_MATH_NAME "/periodic", "tb-k4c2f/" GS_MATH_NAME ".op/periodic", "tb-k4c2f/" GS_MATH_NAME ".op.ds/periodic",
-         "tb-k4c2f/" GS_MATH_NAME ".op.dx/periodic"}};
+#define GS_TB_KS(B, C, V, R) {GS_NAME(B "1" C, V, R), GS_NAME(B "2" C, V, R), GS_NAME(B "3" C, V, R), GS_NAME(B "4" C, V, R)}
+#define GS_TB_NAMES(B, C, R) {GS_TB_KS(B, C, "", R), GS_TB_KS(B, C, ".op", R), GS_TB_KS(B, C, ".op.ds", R), GS_TB_KS(B, C, ".op.dx", R)}
+#define GS_TB_LAYOUTS(B, R) {GS_TB_NAMES(B, "c1", R), GS_TB_NAMES(B, "c2", R), GS_TB_NAMES(B, "", R)}
+#define GS_TB_VARIANTS(B, R) {GS_NAME(B, "", R), GS_NAME(B, ".op", R), GS_NAME(B, ".op.ds", R), GS_NAME(B, ".op.dx", R)}
+#define GS_TB16_LAYOUTS(B, R) {GS_TB_VARIANTS(B "c1f", R), GS_TB_VARIANTS(B "c2f", R)}
+    static const char *const names[2][3][4][4] = GS_RULES(GS_TB_LAYOUTS, "tb-k");    // [rule][cpl 1, 2, 4][variant][k - 1]
+    static const char *const names16[2][2][4] = GS_RULES(GS_TB16_LAYOUTS, "tb-k4");  // [rule][cpl 1, 2][variant]
+#undef GS_TB16_LAYOUTS
+#undef GS_TB_VARIANTS
+#undef GS_TB_LAYOUTS
+#undef GS_TB_NAMES
+#undef GS_TB_KS
     auto name_of = [](int f) { return f == 15 ? 3 : (f == 7 ? 2 : (f ? 1 : 0)); };
     if (k < 1 || k > 4 || a.cols <= 0 || a.rows_per_unit <= 0) return hipErrorInvalidValue;
     if (a.zero_halo == 2 && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // periodic: single slab, no bands
@@ -508,8 +463,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // the periodic rule runs kernels of its own (gs_step_tb_pk and kin), named with a "/periodic" suffix
     const bool per = a.zero_halo == 2;
     const int fast = tb_reduce_fast(a.fast, k, cpl, 4, per);
-    if (name) *name = per ? names_p[cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1]
-                          : names[cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
+    if (name) *name = names[per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
     const long rpu = a.rows_per_unit;
     const long rows_a = (long)a.ra1 - a.ra0;
     const long W = tb_cols_per_wave(k, cpl);
@@ -604,7 +558,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     args.fair_from = fair_from_env >= 0 ? fair_from_env : 0;
     void *kargs[] = {&args};
     if (fair_fn) {
-        if (name) *name = (per ? names16_p : names16)[cpl == 1 ? 0 : 1][name_of(fast16)];
+        if (name) *name = names16[per][cpl == 1 ? 0 : 1][name_of(fast16)];
         return hipLaunchKernel(fair_fn, dim3((unsigned)((units + 15) / 16)), dim3(1024), kargs, 0, s);
     }
     const long blocks = (units + 3) / 4;
