@@ -220,7 +220,7 @@ GsStepArgs make_args(const gs_ctx *ctx, const gs_field *in_u, const gs_field *in
     a.allow_fair = ctx->total_slabs() == 1;
     static const bool edge_kinds = gs_env_int("GS_HIP_EDGE_KINDS", 1, 0, 1) != 0;
     a.edge_kinds = edge_kinds;
-    a.zero_halo = ctx->o.boundary; // gs_boundary: 0, 1 or 2 (gs_ctx_create admits no other value)
+    a.zero_halo = ctx->o.boundary; // gs_boundary: 0, 1, 2 or 3 (gs_ctx_create admits no other value)
     std::memcpy(a.w, ctx->p.w, sizeof a.w);
     a.du = ctx->p.du;
     a.dv = ctx->p.dv;
@@ -651,7 +651,7 @@ int32_t gs_ctx_create(gs_ctx **out, const gs_params *params, const gs_options *o
     if (st == GS_OK && (ctx->o.tile_shape < 0 || ctx->o.tile_shape > 3))
         st = fail(GS_ERR_INVALID, "tile_shape must be 0 (auto), 1 (32 x 64), 2 (16 x 64) or 3 (64 x 64), not %d", ctx->o.tile_shape);
     if (st == GS_OK && ctx->o.boundary != GS_BOUNDARY_CLIPPED && ctx->o.boundary != GS_BOUNDARY_ZERO_HALO &&
-        ctx->o.boundary != GS_BOUNDARY_PERIODIC)
+        ctx->o.boundary != GS_BOUNDARY_PERIODIC && ctx->o.boundary != GS_BOUNDARY_NEUMANN)
         st = fail(GS_ERR_INVALID, "unknown boundary rule %d", ctx->o.boundary);
     // The periodic rule exists on a single slab of a single process: a slab chain would need a ring of ghost-row
     // exchanges, row bands a first band that waits for the last one, and the persistent window kernel and the
@@ -667,6 +667,11 @@ int32_t gs_ctx_create(gs_ctx **out, const gs_params *params, const gs_options *o
             st = fail(GS_ERR_UNSUPPORTED, "the periodic boundary rule does not run a slab as row bands (split = %d): its "
                                           "first band depends on its last", ctx->o.split);
     }
+    // The zero-flux rule only changes the global edges (slab seams read ghost rows as under every rule): any slab count,
+    // process count and split.  The persistent window kernel and the LDS-staged single-step kernel have no form of it.
+    if (st == GS_OK && ctx->o.boundary == GS_BOUNDARY_NEUMANN && (ctx->o.kernel == GS_KERNEL_WINDOW || ctx->o.kernel == GS_KERNEL_LDS))
+        st = fail(GS_ERR_UNSUPPORTED, "the zero-flux (Neumann) boundary rule has no form of the %s kernel",
+                  ctx->o.kernel == GS_KERNEL_WINDOW ? "persistent window" : "LDS-staged single-step");
     if (st == GS_OK && (ctx->o.share_taps < 0 || ctx->o.share_taps > 3))
         st = fail(GS_ERR_INVALID, "share_taps must be 0 (chosen on line), 1 (within a lane), 2 (off) or 3 (across lanes too), not %d",
                   ctx->o.share_taps);
@@ -823,8 +828,10 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
     // GS_KERNEL_WINDOW forces it (fuse_steps = steps per exchange, rows_per_block = window rows: 80).
     // 640-660 k against 391-416 k Mcells x steps / s at 1080 x 1920, both boundary rules (profiles/r06_window_kernel.md).
     const uint64_t cells = u0->rows * u0->cols;
-    // (not under the periodic rule: the window kernel has no form for it, and kernel = auto takes the marching kernel)
-    if (allow_window && single && cells > 0 && steps > 0 && !ctx->win.disabled && ctx->o.boundary != GS_BOUNDARY_PERIODIC) {
+    // (not under the periodic and zero-flux rules: the window kernel has no form for them, and kernel = auto takes the
+    // marching kernel)
+    if (allow_window && single && cells > 0 && steps > 0 && !ctx->win.disabled && ctx->o.boundary != GS_BOUNDARY_PERIODIC &&
+        ctx->o.boundary != GS_BOUNDARY_NEUMANN) {
         const bool forced = ctx->o.kernel == GS_KERNEL_WINDOW;
         const bool automatic = ctx->o.kernel == GS_KERNEL_AUTO && ctx->o.fuse_steps == 0 && ctx->o.rows_per_block == 0 &&
                                ctx->o.cols_per_lane == 0 && ctx->o.split <= 1 && !ctx->o.use_graph && cells >= kWindowAutoCells &&

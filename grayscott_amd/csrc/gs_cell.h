@@ -193,6 +193,28 @@ __device__ __forceinline__ void cell(const GsStepArgs &a, const Row &m, const Ro
         GS_TAP(acc_u, a.w[2][0], p.u[k - 1], u); GS_TAP(acc_v, a.w[2][0], p.v[k - 1], v);
         GS_TAP(acc_u, a.w[2][1], p.u[k], u);     GS_TAP(acc_v, a.w[2][1], p.v[k], v);
         GS_TAP(acc_u, a.w[2][2], p.u[k + 1], u); GS_TAP(acc_v, a.w[2][2], p.v[k + 1], v);
+    } else if constexpr (ZH == 3) {
+        // GS_BOUNDARY_NEUMANN (zero flux): the interior fold over substituted operands.  A neighbour outside the grid is
+        // the nearest cell inside it: the row above / below := the cell's own row where it does not exist (mrow / prow,
+        // wave-uniform: an all-ones or all-zeros word), the left / right column := the cell's own column (la / ra).
+        const uint32_t mk = mrow ? 0xffffffffu : 0u, pk = prow ? 0xffffffffu : 0u;
+        float t[3][3], s[3][3]; // [row][column] operands of U and V
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            t[0][j] = blend(mk, m.u[k - 1 + j], z.u[k - 1 + j]); s[0][j] = blend(mk, m.v[k - 1 + j], z.v[k - 1 + j]);
+            t[1][j] = z.u[k - 1 + j];                             s[1][j] = z.v[k - 1 + j];
+            t[2][j] = blend(pk, p.u[k - 1 + j], z.u[k - 1 + j]); s[2][j] = blend(pk, p.v[k - 1 + j], z.v[k - 1 + j]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            t[i][0] = blend(la, t[i][1], t[i][0]); s[i][0] = blend(la, s[i][1], s[i][0]);
+            t[i][2] = blend(ra, t[i][1], t[i][2]); s[i][2] = blend(ra, s[i][1], s[i][2]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (i != 1 || j != 1) { GS_TAP(acc_u, a.w[i][j], t[i][j], u); GS_TAP(acc_v, a.w[i][j], s[i][j], v); }
     } else if (ZH < 0 ? a.zero_halo != 0 : ZH != 0) {
         // GS_BOUNDARY_ZERO_HALO: all nine taps, centred weights; a neighbour outside the grid reads
         // as 0: per-lane column masks, and for an absent row a wave-uniform all-zeros word ANDed in (a

@@ -213,7 +213,7 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
     a.members = (int32_t)std::min<uint64_t>(e->members, 0x7fffffff);
     a.rows = (int32_t)e->rows;
     a.cols = (int32_t)e->cols;
-    a.zero_halo = ctx->o.boundary; // gs_boundary: 0, 1 or 2 (gs_ctx_create admits no other value)
+    a.zero_halo = ctx->o.boundary; // gs_boundary: 0, 1, 2 or 3 (gs_ctx_create admits no other value)
     // The launchers split at kGsEnsMaxGroups workgroups; a `members` above 2^31 goes in slices here.
     auto for_slices = [&](auto &&launch) -> int32_t {
         for (uint64_t m0 = 0; m0 < e->members; m0 += 0x40000000ull) {

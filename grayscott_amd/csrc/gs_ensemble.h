@@ -7,7 +7,9 @@
 //                      members x windows per member; a window never reads across its member's edge -- cells outside
 //                      the member are zeros, exactly as cells outside the grid are for a lone Species.
 // Under the periodic rule (zero_halo = 2) the resident form keeps its ring filled with the opposite edge (ring_put) and
-// the windowed form is gs_ens_tile_pk, whose windows read their member's cells at wrapped coordinates.
+// the windowed form is gs_ens_tile_pk, whose windows read their member's cells at wrapped coordinates.  Under the zero-flux
+// rule (zero_halo = 3) the resident form keeps its ring filled with the edge cells' own values (ring_put_edge) and the
+// windowed form is gs_ens_tile_nk (tile_steps<ZH = 3>).
 // A workgroup belongs to ONE member, so its parameters are wave-uniform: they are read from the device table with scalar
 // loads (constant address space) into SGPRs.  Member offsets are 64-bit.
 // Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED and the GS_SUFFIX / GS_TAP
@@ -57,7 +59,7 @@ __device__ __forceinline__ GsStepArgs ens_member_args(const GsEnsArgs &e, int64_
     const int nthreads = (int)blockDim.x;                                                                                    \
     for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f; /* the rings (and everything else) */             \
     __syncthreads();                                                                                                         \
-    int o[CPT], rc[CPT]; /* rc (ZH = 2, the periodic rule's ring: ring_put): row << 16 | column */                           \
+    int o[CPT], rc[CPT]; /* rc (ZH = 2, 3: the ring of the periodic / zero-flux rule): row << 16 | column */               \
     bool live[CPT];                                                                                                          \
     float E[CPT][8];                                                                                                         \
 _Pragma("unroll")                                                                                                            \
@@ -67,13 +69,18 @@ _Pragma("unroll")                                                               
         const int r = live[k] ? idx / cols : 0, c = live[k] ? idx - r * cols : 0;                                            \
         o[k] = (r + 1) * P + c + 1;                                                                                          \
         if (ZH == 0) border_weights(a, r, c, E[k]);                                                                          \
-        if constexpr (ZH == 2) rc[k] = r << 16 | c;                                                                          \
+        if constexpr (ZH >= 2) rc[k] = r << 16 | c;                                                                          \
         if (live[k]) {                                                                                                       \
             lds[o[k]] = a.in_u[idx];                                                                                         \
             lds[2 * plane + o[k]] = a.in_v[idx];                                                                             \
-            if (ZH == 2 && on_border(a.rows, cols, r, c)) {                                                                  \
-                ring_put(lds, P, a.rows, cols, r, c, lds[o[k]]);                                                             \
-                ring_put(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);                                     \
+            if (ZH >= 2 && on_border(a.rows, cols, r, c)) {                                                                  \
+                if constexpr (ZH == 3) {                                                                                     \
+                    ring_put_edge(lds, P, a.rows, cols, r, c, lds[o[k]]);                                                    \
+                    ring_put_edge(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);                            \
+                } else {                                                                                                     \
+                    ring_put(lds, P, a.rows, cols, r, c, lds[o[k]]);                                                         \
+                    ring_put(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);                                 \
+                }                                                                                                            \
             }                                                                                                                \
         }                                                                                                                    \
     }                                                                                                                        \
@@ -99,14 +106,19 @@ _Pragma("unroll")                                                               
                 cell<false, FAST, Row3>(a, R[0], R[1], R[2], 1, true, true, 0u, 0u, nu, nv);                                 \
             du[o[k]] = nu;                                                                                                   \
             dv[o[k]] = nv;                                                                                                   \
-            if constexpr (ZH == 2) {                                                                                         \
+            if constexpr (ZH >= 2) {                                                                                         \
                 /* (opaque: the border tests of all CPT cells, hoisted out of the step loop, would hold SGPR lane masks) */  \
                 int x = rc[k];                                                                                               \
                 asm volatile("" : "+v"(x));                                                                                  \
                 const int r = x >> 16, c = x & 0xffff;                                                                       \
                 if (on_border(a.rows, cols, r, c)) {                                                                         \
-                    ring_put(du, P, a.rows, cols, r, c, nu);                                                                 \
-                    ring_put(dv, P, a.rows, cols, r, c, nv);                                                                 \
+                    if constexpr (ZH == 3) {                                                                                 \
+                        ring_put_edge(du, P, a.rows, cols, r, c, nu);                                                        \
+                        ring_put_edge(dv, P, a.rows, cols, r, c, nv);                                                        \
+                    } else {                                                                                                 \
+                        ring_put(du, P, a.rows, cols, r, c, nu);                                                             \
+                        ring_put(dv, P, a.rows, cols, r, c, nv);                                                             \
+                    }                                                                                                        \
                 }                                                                                                            \
             }                                                                                                                \
         }                                                                                                                    \
@@ -133,6 +145,12 @@ template <int CPT, int FAST>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_pk)(GsEnsArgs e, int steps, int to_out)
 {
     GS_ENS_RESIDENT_BODY(CPT, FAST, 2)
+}
+// The zero-flux rule's instances (GsEnsArgs::zero_halo = 3), kernels of their own name.
+template <int CPT, int FAST>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_nk)(GsEnsArgs e, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 3)
 }
 #undef GS_ENS_RESIDENT_BODY
 
@@ -194,6 +212,17 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_pk)(GsE
     extern __shared__ float lds[];
     const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
     tile_window_periodic<RPW, FAST>(ens_member_args(e, e.first + m), lds, K, win);
+}
+
+// The zero-flux rule's windowed form (GsEnsArgs::zero_halo = 3): tile_window_neumann for window `blockIdx.x % windows` of
+// member `first + blockIdx.x / windows`.
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_nk)(GsEnsArgs e, int K, int windows)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
+    tile_window_neumann<RPW, FAST>(ens_member_args(e, e.first + m), lds, K, win);
 }
 
 } // namespace

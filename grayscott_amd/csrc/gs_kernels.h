@@ -65,9 +65,10 @@ struct GsStepArgs {
     // grid, whose overlapping rows and columns then meet in that XCD's L2.
     int32_t xcd_m, xcd_first;
     // Boundary rule on global edges (gs_boundary in gs_hip.h): 0 = naive's clipped window (weights anchored at the
-    // window's top-left corner), 1 = full window with zeros outside the grid, 2 = periodic (single slab only; the
-    // launchers run the rule's own kernels, gs_*_pk and the resident kernels' ZH = 2 instances: a kernel that tests
-    // this field for truth only ever sees 0 or 1).
+    // window's top-left corner), 1 = full window with zeros outside the grid, 2 = periodic (single slab only), 3 = zero
+    // flux (a neighbour outside the grid is the nearest cell inside it).  The launchers run the last two rules' own
+    // kernels, gs_*_pk / gs_*_nk and the resident kernels' ZH = 2 / 3 instances: a kernel that tests this field for
+    // truth only ever sees 0 or 1.
     int32_t zero_halo;
     float w[3][3];         // stencil weights, row-major (parameters.rs:87-88)
     float du, dv, feed, feed_plus_kill, dt;
@@ -117,7 +118,9 @@ struct GsEnsParams {
 // whose cells carry their eight weights in registers (8 cells per thread spill at 128 VGPRs).
 constexpr size_t kGsEnsResidentMaxLds = 160 * 1024;
 // Cells per thread of the resident ensemble kernel for members of rows x cols (1, 2, 4 or 8), 0 = not resident.
-// boundary: gs_boundary -- the periodic rule (2) has the zero-halo rule's capacity: no per-cell weights either.
+// boundary: gs_boundary -- the periodic (2) and zero-flux (3) rules have the zero-halo rule's capacity: no per-cell
+// weights either.  (Their 8-cell forms hold 75 registers, 6 waves per SIMD where the zero-halo rule's run 8: members of
+// 4097 to about 4900 cells, whose LDS would let two workgroups share a CU, get one.)
 inline int gs_ens_resident_cpt(long rows, long cols, int boundary)
 {
     const long cells = rows * cols;
@@ -134,7 +137,7 @@ struct GsEnsArgs {
     int64_t first;             // member of workgroup 0 of this launch (launches are split at kGsEnsMaxGroups)
     int32_t members;           // members in this launch
     int32_t rows, cols;
-    int32_t zero_halo;         // gs_boundary: 0 clipped, 1 zero halo, 2 periodic
+    int32_t zero_halo;         // gs_boundary: 0 clipped, 1 zero halo, 2 periodic, 3 zero flux
 };
 
 // Launchers, one set per arithmetic flavour (see gs_math in include/gs_hip.h).  Each
@@ -157,8 +160,9 @@ GS_DECLARE_LAUNCHERS(fused)
 // Entry points of the parameter-specialised temporal-blocking kernels (strict flavour only; their
 // own translation unit, see gs_step_kernels.hip: GS_TB_OP_ONLY).  nullptr for an unknown variant.
 // wg: waves per workgroup, 4 or 16 (the fair-progress form of one-round launches: K = 4, cpl 1 or 2 only);
-// per: the periodic rule's form (gs_step_tb_pk and kin).
-const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, bool per = false);
+// rule: the kernel set of the boundary rule, 0 = the clipped and zero-halo rules' kernels, 1 = the periodic rule's
+// (gs_step_tb_pk and kin), 2 = the zero-flux rule's (gs_step_tb_nk and kin).
+const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule = 0);
 
 // Plane utilities (math-agnostic, defined once in gs_util_kernels.hip).
 hipError_t gs_launch_colormap(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float scale,

@@ -80,6 +80,20 @@ __device__ __forceinline__ void ring_put(float *p, int P, int rows, int cols, in
         for (int j = 0; j < 3; ++j)
             if ((i || j) && rs[i] >= 0 && cs[j] >= 0) p[rs[i] * P + cs[j]] = x;
 }
+// Zero-flux rule (ZH = 3) in the same layout (gs_run_resident_nk, gs_ens_resident_nk): the ring holds copies of the
+// nearest cell of the grid, so the interior code reads the clamped neighbours at the same fixed offsets.  A cell of the
+// grid's first or last row or column writes itself into the ring cells beside it -- up to 8 of them on grids of one row
+// or column.  Every ring cell has exactly one source: no two lanes write one word.
+__device__ __forceinline__ void ring_put_edge(float *p, int P, int rows, int cols, int r, int c, float x)
+{
+    const int rs[3] = {r + 1, r == 0 ? 0 : -1, r == rows - 1 ? rows + 1 : -1};
+    const int cs[3] = {c + 1, c == 0 ? 0 : -1, c == cols - 1 ? cols + 1 : -1};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if ((i || j) && rs[i] >= 0 && cs[j] >= 0) p[rs[i] * P + cs[j]] = x;
+}
 __device__ __forceinline__ bool on_border(int rows, int cols, int r, int c)
 {
     return r == 0 || r == rows - 1 || c == 0 || c == cols - 1;
@@ -89,7 +103,8 @@ __device__ __forceinline__ bool on_border(int rows, int cols, int r, int c)
 // species): every neighbour is addressable at a fixed offset and a neighbour outside the grid reads 0.
 // That IS the zero-halo rule (interior code for every cell, ZH = 1); for the clipped-window rule every cell
 // carries its own eight weights (cell_border); for the periodic rule (ZH = 2) the cells on the border keep the ring
-// filled with the opposite edge's values (ring_put).  No selects in the step loop.
+// filled with the opposite edge's values (ring_put), for the zero-flux rule (ZH = 3) with their own (ring_put_edge).
+// No selects in the step loop.
 template <int FAST, int ZH>
 __device__ __forceinline__ void run_resident(const GsStepArgs &a, int steps, int to_out)
 {
@@ -102,7 +117,7 @@ __device__ __forceinline__ void run_resident(const GsStepArgs &a, int steps, int
     const int nthreads = (int)blockDim.x; // as many waves as hold cells, at most kResidentThreads (the launcher)
     for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f;               // the rings (and everything else)
     __syncthreads();
-    int o[CPT], g[CPT], rc[CPT]; // rc (ZH = 2): row << 16 | column
+    int o[CPT], g[CPT], rc[CPT]; // rc (ZH = 2, 3): row << 16 | column
     bool live[CPT];
     float E[CPT][8];
 #pragma unroll
@@ -113,13 +128,18 @@ __device__ __forceinline__ void run_resident(const GsStepArgs &a, int steps, int
         o[k] = (r + 1) * P + c + 1;
         g[k] = r * a.pitch + c;
         if (ZH == 0) border_weights(a, r, c, E[k]);
-        if (ZH == 2) rc[k] = r << 16 | c;
+        if (ZH >= 2) rc[k] = r << 16 | c;
         if (live[k]) {
             lds[o[k]] = a.in_u[g[k]];
             lds[2 * plane + o[k]] = a.in_v[g[k]];
-            if (ZH == 2 && on_border(a.rows, cols, r, c)) {
-                ring_put(lds, P, a.rows, cols, r, c, lds[o[k]]);
-                ring_put(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);
+            if (ZH >= 2 && on_border(a.rows, cols, r, c)) {
+                if constexpr (ZH == 3) {
+                    ring_put_edge(lds, P, a.rows, cols, r, c, lds[o[k]]);
+                    ring_put_edge(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);
+                } else {
+                    ring_put(lds, P, a.rows, cols, r, c, lds[o[k]]);
+                    ring_put(lds + 2 * plane, P, a.rows, cols, r, c, lds[2 * plane + o[k]]);
+                }
             }
         }
     }
@@ -145,14 +165,19 @@ __device__ __forceinline__ void run_resident(const GsStepArgs &a, int steps, int
                 cell<false, FAST, Row3>(a, R[0], R[1], R[2], 1, true, true, 0u, 0u, nu, nv);
             du[o[k]] = nu;
             dv[o[k]] = nv;
-            if (ZH == 2) {
+            if (ZH >= 2) {
                 // (opaque: the border tests of all CPT cells, hoisted out of the step loop, would hold SGPR lane masks)
                 int x = rc[k];
                 asm volatile("" : "+v"(x));
                 const int r = x >> 16, c = x & 0xffff;
                 if (on_border(a.rows, cols, r, c)) {
-                    ring_put(du, P, a.rows, cols, r, c, nu);
-                    ring_put(dv, P, a.rows, cols, r, c, nv);
+                    if constexpr (ZH == 3) {
+                        ring_put_edge(du, P, a.rows, cols, r, c, nu);
+                        ring_put_edge(dv, P, a.rows, cols, r, c, nv);
+                    } else {
+                        ring_put(du, P, a.rows, cols, r, c, nu);
+                        ring_put(dv, P, a.rows, cols, r, c, nv);
+                    }
                 }
             }
         }
@@ -178,6 +203,12 @@ template <int FAST>
 __global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_pk)(GsStepArgs a, int steps, int to_out)
 {
     run_resident<FAST, 2>(a, steps, to_out);
+}
+// The zero-flux rule's instance (GsStepArgs::zero_halo = 3), a kernel of its own name.
+template <int FAST>
+__global__ __launch_bounds__(kResidentThreads) void GS_SUFFIX(gs_run_resident_nk)(GsStepArgs a, int steps, int to_out)
+{
+    run_resident<FAST, 3>(a, steps, to_out);
 }
 
 // ------------------------------------------------------------------------------------
@@ -215,7 +246,10 @@ __host__ __device__ constexpr size_t tile_lds_bytes(int rpw) { return (size_t)4 
 // and stay zeros; with the zero-halo rule (ZH = 1) that IS the rule and every cell runs the interior code;
 // with the clipped rule (ZH = 0) every cell runs cell_border with its own weights.  (The general flavour of
 // cell<>, per-tap selects, costs 1.57x an interior cell -- and while every workgroup has a CU to itself the
-// launch lasts as long as its slowest workgroup, a border window: this form costs 1.04x / 1.19x.)
+// launch lasts as long as its slowest workgroup, a border window: this form costs 1.04x / 1.19x.)  With the zero-flux
+// rule (ZH = 3) a cell in the grid's first / last column reads its own column in place of the missing one (a per-lane
+// LDS offset) and a cell in its first / last row its own row in place of the missing one (wave-uniform), at every step:
+// the cells outside the grid are never read by a cell inside it.
 template <int RPW, bool EDGE, int FAST, int ZH>
 __device__ __forceinline__ void tile_steps(const GsStepArgs &a, float *lds, int K, int gr, int gc, int wave, int lane,
                                            float (&u)[RPW], float (&v)[RPW])
@@ -224,6 +258,8 @@ __device__ __forceinline__ void tile_steps(const GsStepArgs &a, float *lds, int 
     // element (buffer b, species s, window row r, window column c) = (2 b + s) * plane + (r + 1) * P + c + 1;
     // `o` = this lane's first cell in species 0 of buffer 0
     const int o = (wave * RPW + 1) * P + lane + 1;
+    constexpr bool NEU = EDGE && ZH == 3;
+    const int dl = NEU && gc == 0 ? 0 : 1, dr = NEU && gc == a.cols - 1 ? 0 : 1; // LDS offsets of the left / right column
     bool inside[RPW];
     float E[RPW][8];
 #pragma unroll
@@ -257,8 +293,13 @@ __device__ __forceinline__ void tile_steps(const GsStepArgs &a, float *lds, int 
 #pragma unroll
         for (int i = 0; i < RPW + 2; ++i) {
             const int d = (i - 1) * P;
-            R[i].u[0] = su[d - 1]; R[i].u[2] = su[d + 1];
-            R[i].v[0] = sv[d - 1]; R[i].v[2] = sv[d + 1];
+            if constexpr (NEU) {
+                R[i].u[0] = su[d - dl]; R[i].u[2] = su[d + dr];
+                R[i].v[0] = sv[d - dl]; R[i].v[2] = sv[d + dr];
+            } else {
+                R[i].u[0] = su[d - 1]; R[i].u[2] = su[d + 1];
+                R[i].v[0] = sv[d - 1]; R[i].v[2] = sv[d + 1];
+            }
             if (i == 0 || i == RPW + 1) { R[i].u[1] = su[d]; R[i].v[1] = sv[d]; }
             else { R[i].u[1] = u[i - 1]; R[i].v[1] = v[i - 1]; }
         }
@@ -267,6 +308,9 @@ __device__ __forceinline__ void tile_steps(const GsStepArgs &a, float *lds, int 
         for (int i = 0; i < RPW; ++i) {
             if (EDGE && ZH == 0)
                 cell_border<FAST>(a, E[i], R[i], R[i + 1], R[i + 2], nu[i], nv[i]);
+            else if constexpr (NEU) // (rows are wave-uniform)
+                cell<false, FAST, Row3>(a, gr + i == 0 ? R[i + 1] : R[i], R[i + 1], gr + i == a.rows - 1 ? R[i + 1] : R[i + 2], 1, true,
+                                        true, 0u, 0u, nu[i], nv[i]);
             else
                 cell<false, FAST, Row3>(a, R[i], R[i + 1], R[i + 2], 1, true, true, 0u, 0u, nu[i], nv[i]);
         }
@@ -367,6 +411,54 @@ __device__ __forceinline__ void tile_window_periodic(const GsStepArgs &a, float 
             }
         }
     }
+}
+// The zero-flux rule's form (GsStepArgs::zero_halo = 3) of window `win`: gs_run_tile_k's load, steps and store, with the
+// rule's edge windows (tile_steps<ZH = 3>).
+template <int RPW, int FAST>
+__device__ __forceinline__ void tile_window_neumann(const GsStepArgs &a, float *lds, int K, int win)
+{
+    constexpr int H = tile_rows(RPW);
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int HO = H - 2 * K, WO = kTileCols - 2 * K; // output rows / columns per window
+    const int tiles_c = (a.cols + WO - 1) / WO;
+    const int tr = win / tiles_c, tc = win - tr * tiles_c;
+    const int gr0 = tr * HO - K, gc0 = tc * WO - K; // global coordinates of window cell (0, 0)
+    const int gr = gr0 + wave * RPW, gc = gc0 + lane; // this lane's first cell
+    // load; cells outside the grid are zeros (never read by a cell inside it)
+    float u[RPW], v[RPW];
+    const int cc = min(max(gc, 0), a.cols - 1);
+#pragma unroll
+    for (int i = 0; i < RPW; ++i) {
+        const ptrdiff_t g = (ptrdiff_t)min(max(gr + i, 0), a.rows - 1) * a.pitch + cc;
+        const bool in = gr + i >= 0 && gr + i < a.rows && gc >= 0 && gc < a.cols;
+        u[i] = in ? a.in_u[g] : 0.0f;
+        v[i] = in ? a.in_v[g] : 0.0f;
+    }
+    const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;
+    if (!edge)
+        tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
+    else
+        tile_steps<RPW, true, FAST, 3>(a, lds, K, gr, gc, wave, lane, u, v);
+    // store the window shrunk by K, where it lies in the grid
+    if (lane >= K && lane < kTileCols - K && gc < a.cols) {
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) {
+            const int wr = wave * RPW + i;
+            if (wr >= K && wr < H - K && gr + i < a.rows) {
+                const ptrdiff_t g = (ptrdiff_t)(gr + i) * a.pitch + gc;
+                a.out_u[g] = u[i];
+                a.out_v[g] = v[i];
+            }
+        }
+    }
+}
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_run_tile_nk)(GsStepArgs a, int K)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    tile_window_neumann<RPW, FAST>(a, lds, K, (int)blockIdx.x);
 }
 template <int RPW, int FAST>
 __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_run_tile_pk)(GsStepArgs a, int K)

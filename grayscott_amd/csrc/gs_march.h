@@ -323,7 +323,8 @@ __host__ __device__ constexpr int tb_halo_floats(int k, bool cross) { return cro
 
 // EDGE: 0 = interior unit; 1 = general path; 2 / 3 = strip on the grid's left / right edge that touches neither its
 // top nor its bottom (cell<2> / cell<3>); 4 = interior strip that touches the top or bottom edge: interior code for
-// every row but the grid's first / last, which take the general cell (wave-uniform branch per level-row); 5 = a unit
+// every row but the grid's first / last, which take the general cell (wave-uniform branch per level-row; the zero-flux
+// rule runs its edge units here as well, with ZH = 3); 5 = a unit
 // on an edge under the periodic rule: every level-0 row and column is read at its index modulo the grid's rows /
 // columns, so the unit's window holds a piece of the periodic extension of the grid and every cell runs the interior
 // code (no edge selects).  The row wrap is wave-uniform (a scalar base address per fetch); the column wrap is per lane,
@@ -609,7 +610,8 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
 
 // WG: waves per workgroup.  4 independent waves, or all 16 of a CU with the progress board of tb_march<FAIR>.
 // PER: the periodic rule's kernels (GsStepArgs::zero_halo = 2; kernels of their own, gs_step_tb_pk and its kin).
-template <int K, int FAST, int CPL, int WG, bool PER = false>
+// NEU: the zero-flux rule's kernels (GsStepArgs::zero_halo = 3; gs_step_tb_nk and its kin).
+template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false>
 __device__ __forceinline__ void tb_unit(const GsStepArgs &a)
 {
     // half_diff needs MODE.IEEE = 0: hwreg(HW_REG_MODE, offset 9, width 1).  The bit only governs
@@ -733,16 +735,23 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a)
     // build; every other combination -- corners, a grid narrower than two strips, the zero-halo rule, general
     // weights -- takes the general path.  GsStepArgs::edge_kinds = 0 sends every edge unit there (A/B timing).
     // Under the periodic rule every edge unit -- first and last strips, first and last row chunks -- is of one kind:
-    // wrapped addresses, interior cells (tb_march<EDGE = 5>).
+    // wrapped addresses, interior cells (tb_march<EDGE = 5>).  Under the zero-flux rule every edge unit takes the general
+    // path with the rule's cell (ZH = 3): at every level, a row on the grid's top or bottom edge stands in for the missing
+    // row and a cell in the first or last column for the missing column, so no row or column outside the grid is read.
     constexpr bool KINDS = (FAST & 1) && !GS_MATH_FUSED;
     if constexpr (PER) {
         if (!edge)
             tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
         else
             tb_march<K, 5, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+    } else if constexpr (NEU) {
+        if (!edge)
+            tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        else
+            tb_march<K, 1, FAST, CPL, 3, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
     } else if (!edge)
         tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
-    else if (a.zero_halo) // (0 or 1 in these kernels: gs_launch_tb sends the periodic rule to gs_step_tb_pk)
+    else if (a.zero_halo) // (0 or 1 in these kernels: gs_launch_tb sends the other rules to gs_step_tb_pk / _nk)
         tb_march<K, 1, FAST, CPL, 1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && left && !right && !ends)
         tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
@@ -804,6 +813,22 @@ template <int K, int WG = 4>
 __global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_dx_pk)(GsStepArgs a)
 {
     tb_unit<K, 15, 2, WG, true>(a);
+}
+// The zero-flux rule's forms of the three (GsStepArgs::zero_halo = 3), kernels of their own as well.
+template <int K, int FAST, int CPL, int WG = 4>
+__global__ __launch_bounds__(WG * 64) void GS_SUFFIX(gs_step_tb_nk)(GsStepArgs a)
+{
+    tb_unit<K, FAST, CPL, WG, false, true>(a);
+}
+template <int K, int WG = 4>
+__global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_ds_nk)(GsStepArgs a)
+{
+    tb_unit<K, 7, 2, WG, false, true>(a);
+}
+template <int K, int WG = 4>
+__global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_dx_nk)(GsStepArgs a)
+{
+    tb_unit<K, 15, 2, WG, false, true>(a);
 }
 
 } // namespace

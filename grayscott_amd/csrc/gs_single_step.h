@@ -79,10 +79,39 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_pk)(GsStepArgs a
     a.out_v[rows_at[1] + c] = ov;
 }
 
+// The zero-flux (Neumann) rule (GsStepArgs::zero_halo = 3), literally: the nine taps of the zero-halo rule's interior cell,
+// in its order, with neighbour (r + i - 1, c + j - 1) read at the nearest cell of the grid -- rows clamped at the global
+// edges only (a slab seam reads its ghost row), columns at 0 and cols - 1.  A kernel of its own.
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_nk)(GsStepArgs a)
+{
+    const int bpr = (a.cols + 255) >> 8;
+    const int slot = blockIdx.x / bpr;
+    const int c = (blockIdx.x - slot * bpr) * 256 + threadIdx.x;
+    const int r = range_row(a, slot);
+    if (c >= a.cols) return;
+    const ptrdiff_t pitch = a.pitch;
+    const ptrdiff_t rows_at[3] = {(ptrdiff_t)(r > 0 || a.top_present ? r - 1 : r) * pitch, (ptrdiff_t)r * pitch,
+                                  (ptrdiff_t)(r + 1 < a.rows || a.bottom_present ? r + 1 : r) * pitch};
+    const int cols_at[3] = {c > 0 ? c - 1 : c, c, c + 1 < a.cols ? c + 1 : c};
+    const float u = a.in_u[rows_at[1] + c], v = a.in_v[rows_at[1] + c];
+    float acc_u = 0.0f, acc_v = 0.0f;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const float su = a.in_u[rows_at[i] + cols_at[j]], sv = a.in_v[rows_at[i] + cols_at[j]];
+            GS_TAP(acc_u, a.w[i][j], su, u);
+            GS_TAP(acc_v, a.w[i][j], sv, v);
+        }
+    float ou, ov;
+    react(a, u, v, acc_u, acc_v, ou, ov);
+    a.out_u[rows_at[1] + c] = ou;
+    a.out_v[rows_at[1] + c] = ov;
+}
+
 // PER: a unit on an edge under the periodic rule (gs_step_stream_pk): rows and columns are read at their index modulo
 // the grid's (a lane whose four columns are not one aligned piece of a row after wrapping loads them one by one), and
-// every cell runs the interior code.
-template <int G, bool EDGE, bool PER = false>
+// every cell runs the interior code.  ZH: the boundary rule of the edge cells (cell<>; -1 = GsStepArgs::zero_halo, 3 = the
+// zero-flux rule of gs_step_stream_nk).
+template <int G, bool EDGE, bool PER = false, int ZH = -1>
 __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int c0, int lane)
 {
     const int c = c0 + lane * 4;
@@ -174,10 +203,10 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
                 const bool prow = !EDGE || (row + 1 < a.rows) || a.bottom_present;
                 float4 nu, nv;
                 constexpr bool E = EDGE && !PER;
-                cell<E>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x);
-                cell<E>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y);
-                cell<E>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z);
-                cell<E>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w);
+                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x);
+                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y);
+                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z);
+                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w);
                 if (lc.lane_ok) {
                     *reinterpret_cast<float4 *>(ou) = nu;
                     *reinterpret_cast<float4 *>(ov) = nv;
@@ -263,6 +292,43 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_pk)(GsStepArgs a
     const bool edge = (c0 == 0) || (c0 + 256 >= a.cols) || (ur0 == 0) || (ur1 == a.rows);
     if (edge)
         march<G, true, true>(a, ur0, ur1, c0, lane);
+    else
+        march<G, false>(a, ur0, ur1, c0, lane);
+}
+
+// The zero-flux rule's form (GsStepArgs::zero_halo = 3): gs_step_stream_k's units, whose edge units run the rule's edge
+// cell (cell<ZH = 3>: the missing row / column is the cell's own); slab seams read their ghost rows as in gs_step_stream_k.
+template <int G>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_nk)(GsStepArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strips = (a.cols + 255) >> 8;
+    int block = (int)blockIdx.x;
+    if (a.xcd_m > 0) { // XCD-aware order (GsStepArgs::xcd_m)
+        const int per = 8 * a.xcd_m, g = block / per, o = block - g * per;
+        if ((g + 1) * per <= (int)gridDim.x) block = g * per + (o & 7) * a.xcd_m + (o >> 3);
+    }
+    const int unit = block * 4 + wave;
+    const int chunk = unit / strips;
+    const int strip = unit - chunk * strips;
+    const int rpu = a.rows_per_unit;
+    const int chunks_a = (a.ra1 - a.ra0 + rpu - 1) / rpu;
+    const int chunks_b = (a.rb1 - a.rb0 + rpu - 1) / rpu;
+    if (chunk >= chunks_a + chunks_b) return; // wave-uniform
+    int ur0, ur1;
+    if (chunk < chunks_a) {
+        ur0 = a.ra0 + chunk * rpu;
+        ur1 = min(ur0 + rpu, a.ra1);
+    } else {
+        ur0 = a.rb0 + (chunk - chunks_a) * rpu;
+        ur1 = min(ur0 + rpu, a.rb1);
+    }
+    const int c0 = strip << 8;
+    const bool edge = (c0 == 0) || (c0 + 256 >= a.cols) || (ur0 == 0 && !a.top_present) ||
+                      (ur1 == a.rows && !a.bottom_present);
+    if (edge)
+        march<G, true, false, 3>(a, ur0, ur1, c0, lane);
     else
         march<G, false>(a, ur0, ur1, c0, lane);
 }

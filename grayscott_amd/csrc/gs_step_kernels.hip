@@ -37,6 +37,9 @@
 //       ensemble kernels: kernels of their own, so that the code of the others does not depend on the rule's existence.
 //       Units and windows on an edge read wrapped rows and columns and run the interior cell code; the resident kernels'
 //       periodic forms (gs_run_resident_pk, gs_ens_resident_pk: ZH = 2) keep their LDS ring filled with the opposite edge.
+//   ..._nk             the zero-flux (Neumann) rule's forms (GsStepArgs::zero_halo = 3) of the same kernels.  Edge units and
+//       windows run the rule's edge cell (cell<ZH = 3>: a missing row or column is the cell's own) at every fused level; the
+//       resident forms (ZH = 3) keep their LDS ring filled with the edge cells' own values.  Slab seams read ghost rows.
 //
 // This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
 // its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
@@ -128,12 +131,16 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 
 // Launch tables.  GS_FN: the entry of a kernel instance.  kOp: the FAST argument of the ".op" variant (the fused build
 // has none: its launchers reduce `fast` to 0).  GS_NAME: the name a launcher reports for kernel family BASE, variant V
-// ("", ".op", ...) under the boundary rule of suffix R; GS_RULES: a table of such names per rule ("" for the clipped
-// and zero-halo rules, which share their kernels, then "/periodic") from one macro M(BASE, R).
+// ("", ".op", ...) under the boundary rule of suffix R; GS_RULES: a table of such names per kernel set of a rule ("" for
+// the clipped and zero-halo rules, which share their kernels, then "/periodic" and "/neumann") from one macro M(BASE, R),
+// indexed by rule_set().
 #define GS_FN(KER, ...) reinterpret_cast<const void *>(&GS_SUFFIX(KER)<__VA_ARGS__>)
 constexpr int kOp = GS_MATH_FUSED ? 0 : 3;
 #define GS_NAME(BASE, V, R) BASE "/" GS_MATH_NAME V R
-#define GS_RULES(M, BASE) {M(BASE, ""), M(BASE, "/periodic")}
+#define GS_RULES(M, BASE) {M(BASE, ""), M(BASE, "/periodic"), M(BASE, "/neumann")}
+// The kernel set of boundary rule `boundary` (gs_boundary): 0 = the clipped and zero-halo rules' kernels (*_k), 1 = the
+// periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
+static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
 #define GS_NAMES_OP(BASE, R) {GS_NAME(BASE, "", R), GS_NAME(BASE, ".op", R)}
 // [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
 #define GS_TILE_NAMES(BASE, R) {GS_NAMES_OP(BASE "tile32x64", R), GS_NAMES_OP(BASE "tile16x64", R), GS_NAMES_OP(BASE "tile64x64", R)}
@@ -141,8 +148,8 @@ constexpr int kOp = GS_MATH_FUSED ? 0 : 3;
 
 hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name)
 {
-    const bool per = a.zero_halo == 2; // the periodic rule: a kernel of its own
-    if (name) *name = per ? "simple/" GS_MATH_NAME "/periodic" : "simple/" GS_MATH_NAME;
+    const bool per = a.zero_halo == 2, neu = a.zero_halo == 3; // the periodic and zero-flux rules: kernels of their own
+    if (name) *name = per ? "simple/" GS_MATH_NAME "/periodic" : (neu ? "simple/" GS_MATH_NAME "/neumann" : "simple/" GS_MATH_NAME);
     const long nrows = (long)(a.ra1 - a.ra0) + (a.rb1 - a.rb0);
     if (nrows <= 0 || a.cols <= 0) return hipSuccess;
     if (per && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // (single slab only)
@@ -151,8 +158,9 @@ hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const
     if (blocks > 0x7fffffffL) return hipErrorInvalidConfiguration;
     GsStepArgs args = a;
     void *kargs[] = {&args};
-    return hipLaunchKernel(per ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_pk))
-                               : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_k)),
+    return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_pk))
+                           : neu ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_nk))
+                                 : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_k)),
                            dim3((unsigned)blocks), dim3(256), kargs, 0, s);
 }
 
@@ -160,18 +168,19 @@ hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const
 // the result is stored in the out-planes when steps is odd, else back in the in-planes.
 hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStream_t s, const char **name)
 {
-    static const char *const names[2][2] = GS_RULES(GS_NAMES_OP, "resident-lds");
+    static const char *const names[3][2] = GS_RULES(GS_NAMES_OP, "resident-lds");
     // [rule][variant]
-    static const void *const fns[3][2] = {{GS_FN(gs_run_resident_k, 0, 0), GS_FN(gs_run_resident_k, kOp, 0)},
+    static const void *const fns[4][2] = {{GS_FN(gs_run_resident_k, 0, 0), GS_FN(gs_run_resident_k, kOp, 0)},
                                           {GS_FN(gs_run_resident_k, 0, 1), GS_FN(gs_run_resident_k, kOp, 1)},
-                                          {GS_FN(gs_run_resident_pk, 0), GS_FN(gs_run_resident_pk, kOp)}};
+                                          {GS_FN(gs_run_resident_pk, 0), GS_FN(gs_run_resident_pk, kOp)},
+                                          {GS_FN(gs_run_resident_nk, 0), GS_FN(gs_run_resident_nk, kOp)}};
     const long cells = (long)a.rows * a.cols;
     if (a.rows <= 0 || a.cols <= 0 || cells > kResidentCells || steps < 0 || a.top_present || a.bottom_present)
         return hipErrorInvalidValue;
     int fast = a.fast & (GS_MATH_FUSED ? 0 : 3);
     if (fast != 3) fast = 0; // only the variant for the default parameters is built besides the general one
-    const int zh = a.zero_halo == 2 ? 2 : (a.zero_halo ? 1 : 0); // gs_boundary
-    if (name) *name = names[zh == 2][fast ? 1 : 0];
+    const int zh = a.zero_halo >= 2 && a.zero_halo <= 3 ? a.zero_halo : (a.zero_halo ? 1 : 0); // gs_boundary
+    if (name) *name = names[rule_set(zh)][fast ? 1 : 0];
     const void *fn = fns[zh][fast ? 1 : 0];
     const size_t lds = (size_t)4 * (a.rows + 2) * (a.cols + 2) * sizeof(float); // <= 74 KB (1 x 1536 cells)
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
@@ -191,10 +200,10 @@ hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStre
 // 2K < window rows.
 hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name)
 {
-    static const char *const names[2][3][2] = GS_RULES(GS_TILE_NAMES, "");
-    static const void *const fns[2][3][2] = {GS_TILE_FNS(gs_run_tile_k), GS_TILE_FNS(gs_run_tile_pk)};
+    static const char *const names[3][3][2] = GS_RULES(GS_TILE_NAMES, "");
+    static const void *const fns[3][3][2] = {GS_TILE_FNS(gs_run_tile_k), GS_TILE_FNS(gs_run_tile_pk), GS_TILE_FNS(gs_run_tile_nk)};
     static const int rpw[3] = {2, 1, 4};
-    const bool per = a.zero_halo == 2; // the periodic rule: gs_run_tile_pk
+    const int per = rule_set(a.zero_halo); // the periodic and zero-flux rules: gs_run_tile_pk / _nk
     if (a.rows <= 0 || a.cols <= 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || a.top_present || a.bottom_present ||
         2 * k >= tile_rows(rpw[shape]))
         return hipErrorInvalidValue;
@@ -225,14 +234,15 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
 // odd, else back in the in-planes.
 hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[2][2] = GS_RULES(GS_NAMES_OP, "ensemble-resident");
+    static const char *const names[3][2] = GS_RULES(GS_NAMES_OP, "ensemble-resident");
     // [rule][variant][cells per thread: 1, 2, 4, 8]; the clipped rule has no 8-cell form (gs_ens_resident_cpt)
 #define GS_CPT_FNS(KER, ...) {GS_FN(KER, 1, __VA_ARGS__), GS_FN(KER, 2, __VA_ARGS__), GS_FN(KER, 4, __VA_ARGS__), GS_FN(KER, 8, __VA_ARGS__)}
-    static const void *const fns[3][2][4] = {
+    static const void *const fns[4][2][4] = {
         {{GS_FN(gs_ens_resident_k, 1, 0, 0), GS_FN(gs_ens_resident_k, 2, 0, 0), GS_FN(gs_ens_resident_k, 4, 0, 0), nullptr},
          {GS_FN(gs_ens_resident_k, 1, kOp, 0), GS_FN(gs_ens_resident_k, 2, kOp, 0), GS_FN(gs_ens_resident_k, 4, kOp, 0), nullptr}},
         {GS_CPT_FNS(gs_ens_resident_k, 0, 1), GS_CPT_FNS(gs_ens_resident_k, kOp, 1)},
-        {GS_CPT_FNS(gs_ens_resident_pk, 0), GS_CPT_FNS(gs_ens_resident_pk, kOp)}};
+        {GS_CPT_FNS(gs_ens_resident_pk, 0), GS_CPT_FNS(gs_ens_resident_pk, kOp)},
+        {GS_CPT_FNS(gs_ens_resident_nk, 0), GS_CPT_FNS(gs_ens_resident_nk, kOp)}};
 #undef GS_CPT_FNS
     const long cells = (long)e.rows * e.cols;
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0) return hipErrorInvalidValue;
@@ -241,8 +251,8 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
     const size_t lds = (size_t)4 * (e.rows + 2) * (e.cols + 2) * sizeof(float);
     if (!cpt || lds > kGsEnsResidentMaxLds) return hipErrorInvalidValue;
     fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    const int zh = e.zero_halo == 2 ? 2 : (e.zero_halo ? 1 : 0); // gs_boundary
-    if (name) *name = names[zh == 2][fast ? 1 : 0];
+    const int zh = e.zero_halo >= 2 && e.zero_halo <= 3 ? e.zero_halo : (e.zero_halo ? 1 : 0); // gs_boundary
+    if (name) *name = names[rule_set(zh)][fast ? 1 : 0];
     const void *fn = fns[zh][fast ? 1 : 0][__builtin_ctz(cpt)];
     if (!fn) return hipErrorInvalidValue;
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
@@ -264,10 +274,10 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
 // Windowed form: K <= kGsTileMaxSteps steps of every member (in-planes -> out-planes); `shape` as gs_launch_tile's.
 hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[2][3][2] = GS_RULES(GS_TILE_NAMES, "ensemble-");
-    static const void *const fns[2][3][2] = {GS_TILE_FNS(gs_ens_tile_k), GS_TILE_FNS(gs_ens_tile_pk)};
+    static const char *const names[3][3][2] = GS_RULES(GS_TILE_NAMES, "ensemble-");
+    static const void *const fns[3][3][2] = {GS_TILE_FNS(gs_ens_tile_k), GS_TILE_FNS(gs_ens_tile_pk), GS_TILE_FNS(gs_ens_tile_nk)};
     static const int rpw[3] = {2, 1, 4};
-    const bool per = e.zero_halo == 2; // the periodic rule: gs_ens_tile_pk
+    const int per = rule_set(e.zero_halo); // the periodic and zero-flux rules: gs_ens_tile_pk / _nk
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]))
         return hipErrorInvalidValue;
     fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
@@ -303,7 +313,7 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
         x.k > 8 || (x.k & 1) || 2 * x.k >= win_rows(rpw) || 2 * x.k + 2 > kWinCols || !x.flags || !x.abort || !x.xu[0] || !x.xu[1] || !x.xv[0] || !x.xv[1])
         return hipErrorInvalidValue;
     if (!x.desc || x.n_windows < 1 || x.seq < 1) return hipErrorInvalidValue;
-    if (a.zero_halo == 2) return hipErrorInvalidValue; // no periodic form (gs_api.cpp refuses the rule before this)
+    if (a.zero_halo >= 2) return hipErrorInvalidValue; // no periodic or zero-flux form (gs_api.cpp refuses them before this)
     // byte offsets inside a plane are 32-bit in the kernel
     if ((long)(a.rows + 8) * a.pitch * 4 > 0x7fffffffL) return hipErrorInvalidValue;
     int fast = a.fast & (GS_MATH_FUSED ? 0 : 7);
@@ -331,7 +341,8 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
 hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name)
 {
     const bool per = a.zero_halo == 2; // the periodic rule: gs_step_stream_pk (single slab)
-    if (name) *name = per ? "stream-g2/" GS_MATH_NAME "/periodic" : "stream-g2/" GS_MATH_NAME;
+    const bool neu = a.zero_halo == 3; // the zero-flux rule: gs_step_stream_nk
+    if (name) *name = per ? "stream-g2/" GS_MATH_NAME "/periodic" : (neu ? "stream-g2/" GS_MATH_NAME "/neumann" : "stream-g2/" GS_MATH_NAME);
     if (a.cols <= 0 || a.rows_per_unit <= 0 || (per && (a.top_present || a.bottom_present))) return hipErrorInvalidValue;
     const long rpu = a.rows_per_unit;
     const long chunks = ((long)(a.ra1 - a.ra0) + rpu - 1) / rpu + ((long)(a.rb1 - a.rb0) + rpu - 1) / rpu;
@@ -347,29 +358,33 @@ hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const
     static const int xcd_env = gs_env_int("GS_HIP_XCD_M_STREAM", -1, 0, kGsXcdGroupMax);
     args.xcd_m = xcd_env >= 0 ? xcd_env : 16;
     void *kargs[] = {&args};
-    return hipLaunchKernel(per ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_pk)<2>)
-                               : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_k)<2>),
+    return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_pk)<2>)
+                           : neu ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_nk)<2>)
+                                 : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_k)<2>),
                            dim3((unsigned)blocks), dim3(256), kargs, 0, s);
 }
 
 // K fused steps over the row ranges of GsStepArgs; on slab seams the ghost rows must be K deep.
 // Kernel entry for k fused steps, specialisation `fast` (already reduced to {0, 1, 3}) and cpl columns per lane; `per`:
-// the periodic rule's form (gs_step_tb_pk).
-static const void *tb_entry(int k, int fast, int cpl, int wg = 4, bool per = false)
+// the kernel set of the boundary rule (rule_set: 1 = the periodic rule's gs_step_tb_pk, 2 = the zero-flux rule's _nk).
+static const void *tb_entry(int k, int fast, int cpl, int wg = 4, int per = 0)
 {
     // the general variant's entries: [rule][cpl 1, 2, 4][k - 1] of 4-wave workgroups, [rule][cpl 1, 2] of the
     // fair-progress form (16-wave workgroups, 4 fused steps)
 #define GS_TB_FNS(KER, C) {GS_FN(KER, 1, 0, C, 4), GS_FN(KER, 2, 0, C, 4), GS_FN(KER, 3, 0, C, 4), GS_FN(KER, 4, 0, C, 4)}
-    static const void *const fns[2][3][4] = {{GS_TB_FNS(gs_step_tb_k, 1), GS_TB_FNS(gs_step_tb_k, 2), GS_TB_FNS(gs_step_tb_k, 4)},
-                                             {GS_TB_FNS(gs_step_tb_pk, 1), GS_TB_FNS(gs_step_tb_pk, 2), GS_TB_FNS(gs_step_tb_pk, 4)}};
+    static const void *const fns[3][3][4] = {{GS_TB_FNS(gs_step_tb_k, 1), GS_TB_FNS(gs_step_tb_k, 2), GS_TB_FNS(gs_step_tb_k, 4)},
+                                             {GS_TB_FNS(gs_step_tb_pk, 1), GS_TB_FNS(gs_step_tb_pk, 2), GS_TB_FNS(gs_step_tb_pk, 4)},
+                                             {GS_TB_FNS(gs_step_tb_nk, 1), GS_TB_FNS(gs_step_tb_nk, 2), GS_TB_FNS(gs_step_tb_nk, 4)}};
 #undef GS_TB_FNS
 #if GS_MATH_FUSED
     // (2 columns per lane need 129 registers in the fused flavour, one more than a wave of a 16-wave workgroup may have:
     // the variant spilled a register to scratch; one-round launches of the fused flavour run as 4-wave workgroups)
-    static const void *const fns16[2][2] = {{GS_FN(gs_step_tb_k, 4, 0, 1, 16), nullptr}, {GS_FN(gs_step_tb_pk, 4, 0, 1, 16), nullptr}};
+    static const void *const fns16[3][2] = {{GS_FN(gs_step_tb_k, 4, 0, 1, 16), nullptr}, {GS_FN(gs_step_tb_pk, 4, 0, 1, 16), nullptr},
+                                            {GS_FN(gs_step_tb_nk, 4, 0, 1, 16), nullptr}};
 #else
-    static const void *const fns16[2][2] = {{GS_FN(gs_step_tb_k, 4, 0, 1, 16), GS_FN(gs_step_tb_k, 4, 0, 2, 16)},
-                                            {GS_FN(gs_step_tb_pk, 4, 0, 1, 16), GS_FN(gs_step_tb_pk, 4, 0, 2, 16)}};
+    static const void *const fns16[3][2] = {{GS_FN(gs_step_tb_k, 4, 0, 1, 16), GS_FN(gs_step_tb_k, 4, 0, 2, 16)},
+                                            {GS_FN(gs_step_tb_pk, 4, 0, 1, 16), GS_FN(gs_step_tb_pk, 4, 0, 2, 16)},
+                                            {GS_FN(gs_step_tb_nk, 4, 0, 1, 16), GS_FN(gs_step_tb_nk, 4, 0, 2, 16)}};
 #endif
     if (wg == 16 && (k != 4 || (cpl != 1 && cpl != 2))) return nullptr;
     if (fast) {
@@ -409,7 +424,7 @@ static int tb_waves_of(const void *f)
 // The variant that runs for GsStepArgs::fast = `fast` with k fused steps, cpl columns per lane and wg waves per
 // workgroup: 0 (general), 1 (side weights 0.5), 3 (and dt == 1), 7 (and full difference sharing: built for 2 columns
 // per lane, 2 to 4 fused steps) or 15 (and across lanes).
-static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, bool per = false)
+static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, int per = 0)
 {
     // The fused build has no use for bit 0 (its taps are sub + fma already) and measured slower
     // with bit 1 (profiles/archive/r01_sweeps.md, runs 48/49): it always runs the general variant.  dt == 1
@@ -431,7 +446,7 @@ static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, bool per
 int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary)
 {
     if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4)) return 0;
-    const bool per = boundary == 2;
+    const int per = rule_set(boundary);
     const void *fn = tb_entry(k, tb_reduce_fast(fast, k, cpl, 4, per), cpl, 4, per);
     return fn ? 1024 * tb_waves_of(fn) : 0;
 }
@@ -448,8 +463,8 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
 #define GS_TB_LAYOUTS(B, R) {GS_TB_NAMES(B, "c1", R), GS_TB_NAMES(B, "c2", R), GS_TB_NAMES(B, "", R)}
 #define GS_TB_VARIANTS(B, R) {GS_NAME(B, "", R), GS_NAME(B, ".op", R), GS_NAME(B, ".op.ds", R), GS_NAME(B, ".op.dx", R)}
 #define GS_TB16_LAYOUTS(B, R) {GS_TB_VARIANTS(B "c1f", R), GS_TB_VARIANTS(B "c2f", R)}
-    static const char *const names[2][3][4][4] = GS_RULES(GS_TB_LAYOUTS, "tb-k");    // [rule][cpl 1, 2, 4][variant][k - 1]
-    static const char *const names16[2][2][4] = GS_RULES(GS_TB16_LAYOUTS, "tb-k4");  // [rule][cpl 1, 2][variant]
+    static const char *const names[3][3][4][4] = GS_RULES(GS_TB_LAYOUTS, "tb-k");    // [rule][cpl 1, 2, 4][variant][k - 1]
+    static const char *const names16[3][2][4] = GS_RULES(GS_TB16_LAYOUTS, "tb-k4");  // [rule][cpl 1, 2][variant]
 #undef GS_TB16_LAYOUTS
 #undef GS_TB_VARIANTS
 #undef GS_TB_LAYOUTS
@@ -460,8 +475,9 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     if (a.zero_halo == 2 && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // periodic: single slab, no bands
     const int cpl = a.cpl == 0 ? 4 : a.cpl;
     if (cpl != 1 && cpl != 2 && cpl != 4) return hipErrorInvalidValue;
-    // the periodic rule runs kernels of its own (gs_step_tb_pk and kin), named with a "/periodic" suffix
-    const bool per = a.zero_halo == 2;
+    // the periodic and zero-flux rules run kernels of their own (gs_step_tb_pk / _nk and kin), named with a "/periodic" /
+    // "/neumann" suffix
+    const int per = rule_set(a.zero_halo);
     const int fast = tb_reduce_fast(a.fast, k, cpl, 4, per);
     if (name) *name = names[per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
     const long rpu = a.rows_per_unit;
@@ -581,7 +597,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
 hipError_t GS_SUFFIX(gs_launch_lds)(const GsStepArgs &a, hipStream_t s, const char **name)
 {
     if (name) *name = "lds-tile16/" GS_MATH_NAME;
-    if (a.cols <= 0 || a.zero_halo == 2) return hipErrorInvalidValue; // no periodic form (gs_api.cpp refuses it first)
+    if (a.cols <= 0 || a.zero_halo >= 2) return hipErrorInvalidValue; // no periodic or zero-flux form (gs_api.cpp refuses them first)
     const long chunks = ((long)(a.ra1 - a.ra0) + kLdsTileRows - 1) / kLdsTileRows +
                         ((long)(a.rb1 - a.rb0) + kLdsTileRows - 1) / kLdsTileRows;
     if (chunks <= 0) return hipSuccess;
@@ -623,12 +639,14 @@ extern "C" int32_t GS_SUFFIX(gs_debug_trace_read)(unsigned long long *dst, int32
 
 #if GS_TB_OP_ONLY
 // Kernel entry of the specialised variant for K fused steps, `fast` in {1, 3} (GsStepArgs::fast)
-// and `cpl` columns per lane; `per`: the periodic rule's form.
-template <bool PER>
+// and `cpl` columns per lane; RULE: the kernel set of the boundary rule (1 = the periodic rule's form, 2 = the zero-flux
+// rule's).
+template <int RULE>
 static const void *tb_op_kernel(int k, int fast, int cpl, int wg)
 {
-#define GS_OP_FN(KER, ...) (PER ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_pk)<__VA_ARGS__>) \
-                                : reinterpret_cast<const void *>(&GS_SUFFIX(KER##_k)<__VA_ARGS__>))
+#define GS_OP_FN(KER, ...) (RULE == 1 ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_pk)<__VA_ARGS__>) \
+                            : RULE == 2 ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_nk)<__VA_ARGS__>) \
+                                        : reinterpret_cast<const void *>(&GS_SUFFIX(KER##_k)<__VA_ARGS__>))
     if (fast == 7) { // full difference sharing: 2 columns per lane
         if (cpl != 2) return nullptr;
         if (wg == 16) return k == 4 ? GS_OP_FN(gs_step_tb_ds, 4, 16) : nullptr;
@@ -668,8 +686,8 @@ static const void *tb_op_kernel(int k, int fast, int cpl, int wg)
 #undef GS_TB_CASE
 #undef GS_OP_FN
 }
-const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, bool per)
+const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule)
 {
-    return per ? tb_op_kernel<true>(k, fast, cpl, wg) : tb_op_kernel<false>(k, fast, cpl, wg);
+    return rule == 1 ? tb_op_kernel<1>(k, fast, cpl, wg) : (rule == 2 ? tb_op_kernel<2>(k, fast, cpl, wg) : tb_op_kernel<0>(k, fast, cpl, wg));
 }
 #endif

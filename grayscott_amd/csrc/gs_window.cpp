@@ -216,10 +216,11 @@ int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *la
     gs_field *u0 = r.u[0];
     SlabRt &sl = ctx->slabs[0];
     *launched = 0;
-    // no periodic form of this kernel: gs_ctx_create refuses a pinned GS_KERNEL_WINDOW under that rule and kernel = auto
-    // does not come here (run_steps)
-    if (ctx->o.boundary == GS_BOUNDARY_PERIODIC)
-        return fail(GS_ERR_UNSUPPORTED, "the persistent window kernel has no form for the periodic boundary rule");
+    // no periodic or zero-flux form of this kernel: gs_ctx_create refuses a pinned GS_KERNEL_WINDOW under those rules and
+    // kernel = auto does not come here (run_steps)
+    if (ctx->o.boundary == GS_BOUNDARY_PERIODIC || ctx->o.boundary == GS_BOUNDARY_NEUMANN)
+        return fail(GS_ERR_UNSUPPORTED, "the persistent window kernel has no form for the %s boundary rule",
+                    ctx->o.boundary == GS_BOUNDARY_PERIODIC ? "periodic" : "zero-flux (Neumann)");
     GS_HIP(hipSetDevice(sl.device));
     // the tiling of this grid (made once per shape and configuration, kept on the device)
     // (kernel = auto only takes grids that 80-row windows cover: with 96-row windows -- 1200 x 2000: 450 k against the

@@ -56,7 +56,7 @@ def add_backend_args(ap: argparse.ArgumentParser) -> None:
     be.add_argument("--hip-cols-per-lane", type=int, default=None, help="columns per lane: 4, 2 or 1, 0 = chosen on line [GS_HIP_COLS_PER_LANE]")
     be.add_argument("--hip-no-tune", type=int, default=None, help="1 = never time candidate configurations inside perform_steps [GS_HIP_NO_TUNE]")
     be.add_argument("--hip-kernel", type=int, default=None, help="step kernel (gs_kernel in gs_hip.h), 0 = by grid size and call length [GS_HIP_KERNEL]")
-    be.add_argument("--hip-boundary", type=int, default=None, help="0 = compute_naive's clipped window, 1 = zero halo (the SIMD / Vulkan backends' rule), 2 = periodic (single GPU, one process) [GS_HIP_BOUNDARY]")
+    be.add_argument("--hip-boundary", type=int, default=None, help="0 = compute_naive's clipped window, 1 = zero halo (the SIMD / Vulkan backends' rule), 2 = periodic (single GPU, one process), 3 = zero flux (Neumann: a neighbour outside the grid is the nearest cell inside it) [GS_HIP_BOUNDARY]")
     be.add_argument("--hip-general-kernels", type=int, default=None, help="1 = never run the variants specialised for the default stencil and time step [GS_HIP_GENERAL_KERNELS]")
     be.add_argument("--hip-share-taps", type=int, default=None, help="full difference sharing: 0 = on (form 3) unless measured slower, 1 = within a lane only, 2 = off, 3 = across lanes too [GS_HIP_SHARE_TAPS]")
     be.add_argument("--hip-place-candidates", type=int, default=None, help="most extra blocks gs_fields_place may draw when a Species of >= 2^26 cells is placed by measurement (default 12; 0 = planes as hipMalloc hands them out) [GS_HIP_PLACE_CANDIDATES]")

@@ -81,8 +81,10 @@ class HipArgs:
     environment alone (compute/shared/src/lib.rs:20-25, benchmark.rs:36-40).
 
     ``boundary`` is the rule on the grid's edges (``gs_boundary``): ``capi.GS_BOUNDARY_CLIPPED`` (the parity
-    target), ``capi.GS_BOUNDARY_ZERO_HALO`` or ``capi.GS_BOUNDARY_PERIODIC`` -- the grid wraps around; one device
-    and one process only, and neither ``kernel`` = ``GS_KERNEL_WINDOW`` / ``GS_KERNEL_LDS`` nor ``split`` > 1."""
+    target), ``capi.GS_BOUNDARY_ZERO_HALO``, ``capi.GS_BOUNDARY_PERIODIC`` -- the grid wraps around; one device
+    and one process only, and neither ``kernel`` = ``GS_KERNEL_WINDOW`` / ``GS_KERNEL_LDS`` nor ``split`` > 1 -- or
+    ``capi.GS_BOUNDARY_NEUMANN`` -- zero flux: a neighbour outside the grid is the nearest cell inside it; any devices,
+    processes and ``split``, but neither ``kernel`` = ``GS_KERNEL_WINDOW`` nor ``GS_KERNEL_LDS``."""
 
     devices: Sequence[int] = field(default_factory=lambda: [
         int(x) for x in os.environ.get("GS_HIP_DEVICES", "0").split(",") if x != ""])

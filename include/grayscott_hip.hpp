@@ -72,7 +72,7 @@ struct Parameters {
 struct HipArgs {
     std::vector<int32_t> devices{0};
     int32_t math = GS_MATH_STRICT, kernel = GS_KERNEL_AUTO, rows_per_block = 0, fuse_steps = 0, cols_per_lane = 0;
-    // boundary: any gs_boundary of gs_hip.h, GS_BOUNDARY_PERIODIC included (one device, one process)
+    // boundary: any gs_boundary of gs_hip.h, GS_BOUNDARY_PERIODIC (one device, one process) and GS_BOUNDARY_NEUMANN included
     int32_t boundary = GS_BOUNDARY_CLIPPED, no_tune = 0, share_taps = 0, general_kernels = 0;
     // not a gs_options field: the most extra blocks gs_fields_place may draw when make_species places a Species by
     // measurement -- every Species of >= 2^26 cells on a context with one slab (0 = planes as hipMalloc hands them out)

@@ -117,7 +117,8 @@ typedef enum gs_math { GS_MATH_STRICT = 0, GS_MATH_FUSED = 1 } gs_math;
  * exchange, as many as fit); TILE otherwise up to 1.5 M cells; TB with fuse_steps (default 4) otherwise, for
  * slab chains and whenever fuse_steps, rows_per_block, cols_per_lane, split or use_graph pin a schedule.
  * Under GS_BOUNDARY_PERIODIC there is no WINDOW and no LDS form: pinning either is refused at gs_ctx_create
- * (GS_ERR_UNSUPPORTED), and AUTO runs TB where it would have run WINDOW (1080 x 1920 in long calls, for one). */
+ * (GS_ERR_UNSUPPORTED), and AUTO runs TB where it would have run WINDOW (1080 x 1920 in long calls, for one).
+ * The same holds under GS_BOUNDARY_NEUMANN. */
 typedef enum gs_kernel {
     GS_KERNEL_AUTO = 0,    /* best measured variant for the shape                          */
     GS_KERNEL_SIMPLE = 1,  /* one thread per cell, global loads only (cross-check kernel)  */
@@ -143,7 +144,7 @@ typedef enum gs_kernel {
                               planes, which no launch writes), and the context stays with TB  */
 } gs_kernel;
 
-/* Rule on the edges of the global grid.  The reference has two:
+/* Rule on the edges of the global grid.  The reference has the first two:
  * CLIPPED   -- compute_naive's, the parity target: the 3x3 window is clipped to the grid and the
  *              weights are indexed from the clipped window's top-left corner
  *              (compute/naive/src/lib.rs:57-71);
@@ -155,8 +156,15 @@ typedef enum gs_kernel {
  *              ((r + i - 1) mod rows, (c + j - 1) mod cols) -- on 1 x N, N x 1 or 2 x 2 grids a neighbour can be
  *              the cell itself.  Single slab in a single process only: a context of several slabs or processes,
  *              a pinned GS_KERNEL_WINDOW or GS_KERNEL_LDS and split > 1 are refused at gs_ctx_create
- *              (GS_ERR_UNSUPPORTED). */
-enum gs_boundary { GS_BOUNDARY_CLIPPED = 0, GS_BOUNDARY_ZERO_HALO = 1, GS_BOUNDARY_PERIODIC = 2 };
+ *              (GS_ERR_UNSUPPORTED).
+ * NEUMANN   -- zero flux through the edges, the closed domain of most reaction-diffusion work on a finite grid:
+ *              every cell takes the nine taps of ZERO_HALO's interior cell, in its order, with neighbour
+ *              (r + i - 1, c + j - 1) read at (clamp(r + i - 1, 0, rows - 1), clamp(c + j - 1, 0, cols - 1)), the
+ *              nearest cell inside the grid (np.pad(x, 1, mode="edge")); on 1 x N, N x 1 or 1 x 1 grids a neighbour
+ *              can be the cell itself.  With F = k = 0 the sum of U + V is conserved up to rounding.  Only the global
+ *              edges change, so any slab count, process count and split is accepted; a pinned GS_KERNEL_WINDOW or
+ *              GS_KERNEL_LDS is refused at gs_ctx_create (GS_ERR_UNSUPPORTED). */
+enum gs_boundary { GS_BOUNDARY_CLIPPED = 0, GS_BOUNDARY_ZERO_HALO = 1, GS_BOUNDARY_PERIODIC = 2, GS_BOUNDARY_NEUMANN = 3 };
 
 /* Backend options: the C view of the Rust `CliArgs` (compute/shared/src/lib.rs:20-25 --
  * every field has a default; zero-initialise and override). */

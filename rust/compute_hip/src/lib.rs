@@ -82,7 +82,8 @@ pub struct HipArgs {
 
     /// Rule on the edges of the grid (`gs_boundary`): 0 = compute_naive's clipped window, 1 = zero halo
     /// (what the SIMD and Vulkan backends compute: data/src/concentration/simd/mod.rs:281-326), 2 = periodic
-    /// (the grid wraps around; single GPU, one process)
+    /// (the grid wraps around; single GPU, one process), 3 = zero flux (Neumann: a neighbour outside the grid is the
+    /// nearest cell inside it)
     #[arg(long, env = "GS_HIP_BOUNDARY", default_value_t = 0)]
     pub hip_boundary: i32,
 

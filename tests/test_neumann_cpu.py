@@ -1,0 +1,185 @@
+"""The zero-flux (Neumann) boundary rule without a GPU: the constant in capi and the header, the --hip-boundary 3 flag of
+simulate and sweep, the pad-and-crop reference against a literal per-cell clamp loop, the trap of fusing steps on a pad
+of the input only, conservation of U + V with F = k = 0, and the rule's kernels in the code objects (present,
+spill-free, scratch-free, float modes as the contract says, the register budget of their twins)."""
+from __future__ import annotations
+
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+
+import oracle
+from oracle import numpy_ref
+
+from . import neumann_ref
+from .helpers import stress_fields
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+import codeobj  # noqa: E402
+
+
+def test_the_constant_is_in_capi_and_in_the_header():
+    from grayscott_amd import capi
+
+    assert capi.GS_BOUNDARY_NEUMANN == 3
+    header = open(os.path.join(ROOT, "include", "gs_hip.h")).read()
+    assert re.search(r"enum gs_boundary \{[^}]*GS_BOUNDARY_NEUMANN = 3", header)
+
+
+def test_the_flag_goes_through_simulate_and_sweep(tmp_path):
+    from grayscott_amd import simulate, sweep
+
+    args = simulate.parse(["--hip-boundary", "3", "-r", "64", "-c", "128", "-n", "3", "-e", "32", "-o", str(tmp_path / "p.h5")])
+    assert simulate.backend_args(args).boundary == 3
+    args = sweep.parse(["--feed", "0.01:0.03:3", "--kill", "0.05:0.06:2", "-r", "40", "-c", "64", "-s", "50",
+                        "--hip-boundary", "3", "-o", str(tmp_path / "s.h5")])
+    assert sweep.backend_args(args).boundary == 3
+
+
+def test_the_help_text_names_the_rule(capsys):
+    from grayscott_amd import simulate
+
+    with pytest.raises(SystemExit):
+        simulate.parse(["--help"])
+    assert "3 = zero flux" in " ".join(capsys.readouterr().out.split())
+
+
+SKEW = np.array([[0.1, 0.3, 0.2], [0.6, 0.0, 0.4], [0.05, 0.25, 0.15]], np.float32)
+
+
+def skew_params():
+    p = numpy_ref.default_params()
+    p["w"] = SKEW.copy()
+    q = oracle.default_params()
+    q.set_weights(SKEW.tolist())
+    return p, q
+
+
+@pytest.mark.parametrize("stencil", ["default", "skew"])
+@pytest.mark.parametrize("shape", [(1, 1), (1, 9), (7, 1), (2, 2), (5, 3), (17, 23)])
+def test_pad_and_crop_is_the_clamp_rule(shape, stencil):
+    p, q = skew_params() if stencil == "skew" else (None, None)
+    u, v = stress_fields(shape, 7 + shape[0] * 10 + shape[1])
+    cu, cv = u, v
+    for n in range(1, 5):
+        cu, cv = neumann_ref.clamp_step(cu, cv, p)
+        for got, what in ((neumann_ref.run_numpy(u, v, n, p), "numpy"), (neumann_ref.run(u, v, n, params=q), "C oracle")):
+            assert got[0].tobytes() == cu.tobytes() and got[1].tobytes() == cv.tobytes(), (shape, n, what)
+
+
+def test_a_pad_of_k_cells_is_not_k_steps():
+    """The trap the kernels avoid by clamping at every fused level: cells of an edge pad evolve from their own
+    neighbourhoods and stop being copies of the edge, so a K-cell pad, K zero-halo steps and a crop are not K steps."""
+    u, v = stress_fields((24, 40), 5)
+    su, sv = neumann_ref.run(u, v, 1)
+    pu, pv = neumann_ref.run_padded(u, v, 1)
+    assert pu.tobytes() == su.tobytes() and pv.tobytes() == sv.tobytes()
+    ku, kv = neumann_ref.run(u, v, 4)
+    pu, pv = neumann_ref.run_padded(u, v, 4)
+    differ = np.count_nonzero(pu != ku) + np.count_nonzero(pv != kv)
+    assert differ > 100, differ
+
+
+def test_u_plus_v_is_conserved_without_reaction():
+    """With F = k = 0 the reaction moves mass between U and V only and zero flux lets none out: sum(U + V) stays put up
+    to rounding.  The clipped and zero-halo rules lose mass on the same input."""
+    u, v = stress_fields((24, 40), 0)
+    q = oracle.default_params()
+    q.feed, q.kill = 0.0, 0.0
+    total = float(u.astype(np.float64).sum() + v.astype(np.float64).sum())
+
+    def drift(uu, vv):
+        return abs(float(uu.astype(np.float64).sum() + vv.astype(np.float64).sum()) - total) / total
+
+    assert drift(*neumann_ref.run(u, v, 200, params=q)) < 1e-6
+    for rule in (oracle.CLIPPED, oracle.ZERO_HALO):
+        assert drift(*oracle.run(u, v, 200, params=q, ftz=True, boundary=rule)) > 1e-5, rule
+
+
+# ---- the kernels in the code objects ----------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def kernels(built):
+    return {k.name: k for k in codeobj.kernels()}
+
+
+NEUMANN = re.compile(r"^gs_[a-z_]+_nk_(strict|fused)\b")
+
+
+def neumann_kernels(kernels, flavour):
+    return {n: k for n, k in kernels.items() if NEUMANN.match(n) and f"_nk_{flavour}" in n}
+
+
+def test_every_neumann_kernel_is_there(kernels):
+    strict, fused = neumann_kernels(kernels, "strict"), neumann_kernels(kernels, "fused")
+    for n in ("gs_step_simple_nk_strict", "gs_step_stream_nk_strict<2>", "gs_run_resident_nk_strict<3>",
+              "gs_run_resident_nk_strict<0>", "gs_run_tile_nk_strict<2, 3>", "gs_run_tile_nk_strict<1, 0>",
+              "gs_run_tile_nk_strict<4, 0>", "gs_ens_resident_nk_strict<8, 3>", "gs_ens_resident_nk_strict<1, 0>",
+              "gs_ens_tile_nk_strict<2, 3>", "gs_ens_tile_nk_strict<4, 0>",
+              "gs_step_simple_nk_fused", "gs_step_stream_nk_fused<2>", "gs_run_resident_nk_fused<0>",
+              "gs_run_tile_nk_fused<1, 0>", "gs_ens_resident_nk_fused<8, 0>", "gs_ens_tile_nk_fused<2, 0>",
+              "gs_step_tb_nk_fused<4, 0, 1, 16>"):
+        assert any(k == n or k.startswith(n + "(") for k in kernels), n
+    for k in range(1, 5):
+        for cpl in (1, 2, 4):
+            for fast in (0, 1, 3):
+                assert f"gs_step_tb_nk_strict<{k}, {fast}, {cpl}, 4>" in strict, (k, fast, cpl)
+            assert f"gs_step_tb_nk_fused<{k}, 0, {cpl}, 4>" in fused, (k, cpl)
+    for fast in (0, 1, 3):
+        for cpl in (1, 2):
+            assert f"gs_step_tb_nk_strict<4, {fast}, {cpl}, 16>" in strict
+    for form in ("ds", "dx"):
+        for k in (2, 3, 4):
+            assert f"gs_step_tb_{form}_nk_strict<{k}, 4>" in kernels
+        assert f"gs_step_tb_{form}_nk_strict<4, 16>" in kernels
+    assert len(strict) == 74 and len(fused) == 26, (len(strict), len(fused))
+
+
+@pytest.mark.parametrize("flavour", ["strict", "fused"])
+def test_neumann_kernels_do_not_spill(kernels, flavour):
+    ks = neumann_kernels(kernels, flavour)
+    assert ks
+    for name, k in ks.items():
+        assert k.vgpr_spill == 0 and k.sgpr_spill == 0 and k.scratch == 0 and not k.dynamic_stack, (name, k.vgpr_spill, k.sgpr_spill)
+        assert k.count(r"^scratch_") == 0, name
+        assert k.count(r"^v_(readlane|writelane)_b32") == 0, name
+        if flavour == "strict":
+            assert k.count(codeobj.FLOAT_FMA) == 0, (name, k.matching(codeobj.FLOAT_FMA)[:3])
+            assert k.denorm_mode_32 == 1, name
+        else:
+            assert k.denorm_mode_32 == 3, name
+
+
+def twin_of(name):
+    """The clipped / zero-halo rules' kernel with the same template arguments (the resident kernels': their zero-halo
+    instance, ZH = 1)."""
+    twin = name.replace("_nk_", "_k_")
+    m = re.match(r"^(gs_run_resident_k_\w+<\d+|gs_ens_resident_k_\w+<\d+, \d+)>(.*)$", twin)
+    return m.group(1) + ", 1>" + m.group(2) if m else twin
+
+
+def test_neumann_kernels_keep_the_register_budget_of_their_twins(kernels):
+    """Every form runs as many waves per SIMD as its twin (512 registers, allocated in steps of 8); the forms built for
+    four waves per SIMD, and those whose twin fits 128 registers, stay at 128.  The one exception is the resident
+    ensemble at 8 cells per thread, as under the periodic rule: its ring writes need the cells' coordinates in 8 more
+    registers (75: 6 waves per SIMD against 8), which only matters where two of its 1024-thread workgroups would share a
+    CU's LDS -- members of 4097 to about 4900 cells."""
+    def waves(vgpr):
+        return min(8, 512 // ((vgpr + 7) // 8 * 8))
+
+    seen = 0
+    for name, k in kernels.items():
+        if not NEUMANN.match(name):
+            continue
+        twin = kernels[twin_of(name)]
+        if re.match(r"^gs_ens_resident_nk_\w+<8,", name):
+            assert waves(k.vgpr) >= 6 and k.vgpr <= kernels[name.replace("_nk_", "_pk_")].vgpr, (name, k.vgpr)
+        else:
+            assert waves(k.vgpr) >= waves(twin.vgpr), (name, k.vgpr, twin.vgpr)
+        if "_ds_" in name or "_dx_" in name or twin.vgpr <= 128:
+            assert k.vgpr <= 128, (name, k.vgpr)
+        seen += 1
+    assert seen == 100, seen
