@@ -55,6 +55,31 @@ def gpu_run(u0, v0, steps, params: Parameters | None = None, args: HipArgs | Non
     return out + (info,)
 
 
+def rule_run(u, v, steps: int, params=None, boundary: int = capi.GS_BOUNDARY_CLIPPED, ftz: bool = True):
+    """``steps`` steps of boundary rule ``boundary`` (gs_boundary) on the CPU: the C oracle for the clipped (0) and
+    zero-halo (1) rules, the pad-and-crop references of tests/periodic_ref.py (2) and tests/neumann_ref.py (3)."""
+    from . import neumann_ref, periodic_ref
+
+    if boundary in (capi.GS_BOUNDARY_CLIPPED, capi.GS_BOUNDARY_ZERO_HALO):
+        return oracle.run(u, v, steps, params=params, ftz=ftz, boundary=boundary)
+    if boundary == capi.GS_BOUNDARY_PERIODIC:
+        return periodic_ref.run(u, v, steps, params=params, ftz=ftz)
+    if boundary == capi.GS_BOUNDARY_NEUMANN:
+        return neumann_ref.run(u, v, steps, params=params, ftz=ftz)
+    raise ValueError(f"unknown boundary rule {boundary}")
+
+
+def rule_of(name: str) -> int:
+    """The boundary rule a reported kernel name carries: ``/periodic`` or ``/neumann`` before any ``@`` suffix, else
+    the clipped or zero-halo rules' kernel set (returned as GS_BOUNDARY_CLIPPED: their names are the same)."""
+    base = name.split("@")[0]
+    if base.endswith("/periodic"):
+        return capi.GS_BOUNDARY_PERIODIC
+    if base.endswith("/neumann"):
+        return capi.GS_BOUNDARY_NEUMANN
+    return capi.GS_BOUNDARY_CLIPPED
+
+
 def assert_bits_equal(got: np.ndarray, ref: np.ndarray, what: str):
     if got.tobytes() != ref.tobytes():
         bad = np.flatnonzero(got.view(np.uint32).ravel() != ref.view(np.uint32).ravel())

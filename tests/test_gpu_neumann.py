@@ -18,6 +18,7 @@ from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi, hdf5_m
 
 from . import neumann_ref
 from .helpers import assert_bits_equal, gpu_run, oracle_params, species_from_arrays, stress_fields
+from .test_gpu_property import tb_cols_per_wave
 from .test_gpu_multiprocess import shm_transport  # noqa: F401  (the fixture: the librccl test double)
 
 pytestmark = pytest.mark.gpu
@@ -94,14 +95,26 @@ TB_CONFIGS = ([dict(cols_per_lane=c, fuse_steps=k) for c in (1, 2, 4) for k in (
               + [dict(cols_per_lane=2, fuse_steps=4, use_graph=1), dict(fuse_steps=4, use_graph=1, rows_per_block=8)])
 
 
-@pytest.mark.parametrize("cfg", TB_CONFIGS, ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
+def edge_shapes(cfg):
+    """Grids whose last strip of the marching kernel is 1 or K columns wide after a full one (cols = W + 1, W + K with
+    W = tb_cols_per_wave(K, CPL), every CPL where the configuration leaves it to the library): the wrap or clamp of
+    the last strip reaches past the strip before it."""
+    k = cfg["fuse_steps"]
+    return [s for c in ([cfg["cols_per_lane"]] if "cols_per_lane" in cfg else [1, 2, 4])
+            for s in ((19, tb_cols_per_wave(k, c) + 1), (37, tb_cols_per_wave(k, c) + k))]
+
+
+# every configuration in both flavours (the fused ones: the fused build's own marching kernels, its .op-less forms)
+@pytest.mark.parametrize("cfg", TB_CONFIGS + [dict(c, math=capi.GS_MATH_FUSED) for c in TB_CONFIGS],
+                         ids=lambda c: "-".join(f"{k}{v}" for k, v in c.items()))
 def test_marching_kernel_pinned(cfg):
-    for shape in PIN_SHAPES + [(1000, 1003)]:
+    for shape in PIN_SHAPES + [(1000, 1003)] + edge_shapes(cfg):
         u0, v0 = stress_fields(shape, 3)
         steps = 37 if cfg.get("use_graph") else 11  # (a graph batch is 16 passes)
         ref_u, ref_v = neumann_ref.run(u0, v0, steps)
         got_u, got_v, info = gpu_run(u0, v0, steps, args=args(kernel=capi.GS_KERNEL_TB, no_tune=1, **cfg))
         assert info[0].startswith("tb-") and is_neumann(info[0]), info
+        assert ("/fused" in info[0]) == (cfg.get("math") == capi.GS_MATH_FUSED), info
         assert_bits_equal(got_u, ref_u, f"U {shape} {cfg} {info[0]}")
         assert_bits_equal(got_v, ref_v, f"V {shape} {cfg} {info[0]}")
 
@@ -123,18 +136,30 @@ def test_fair_progress_form(cpl, monkeypatch):
     assert r.returncode == 0, r.stdout + r.stderr
 
 
+def tile_edge_shapes(tile_shape, fuse):
+    """Grids one row and one column past a whole window's output, at the steps per launch the pinned form runs
+    (gs_run: fuse_steps, else 8, or 4 for 16-row windows; 2K below the window's rows)."""
+    rows = {1: 32, 2: 16, 3: 64}[tile_shape]
+    k = min(fuse or (4 if rows == 16 else 8), rows // 2 - 1)
+    return [(rows - 2 * k + 1, 64 - 2 * k + 1), (2 * (rows - 2 * k) + k, 2 * (64 - 2 * k) + k)]
+
+
 @pytest.mark.parametrize("tile_shape", [1, 2, 3])
 @pytest.mark.parametrize("fuse", [0, 1, 3, 8])
 def test_tile_kernel_pinned(tile_shape, fuse):
-    for shape in PIN_SHAPES + [(1000, 1003)]:
+    for shape, math in ([(s, capi.GS_MATH_STRICT) for s in PIN_SHAPES + [(1000, 1003)]]
+                        + [(s, m) for s in tile_edge_shapes(tile_shape, fuse) for m in (capi.GS_MATH_STRICT, capi.GS_MATH_FUSED)]
+                        + [(s, capi.GS_MATH_FUSED) for s in PIN_SHAPES + [(1000, 1003)]]):
         u0, v0 = stress_fields(shape, 4)
         ref_u, ref_v = neumann_ref.run(u0, v0, 19)
         try:
-            got_u, got_v, info = gpu_run(u0, v0, 19, args=args(kernel=capi.GS_KERNEL_TILE, tile_shape=tile_shape, fuse_steps=fuse))
+            got_u, got_v, info = gpu_run(u0, v0, 19, args=args(kernel=capi.GS_KERNEL_TILE, tile_shape=tile_shape, fuse_steps=fuse,
+                                                                math=math))
         except GsError as e:  # (K = 8 does not fit the 16-row windows: refused for every rule)
             assert fuse == 8 and tile_shape == 2 and e.code == capi.GS_ERR_INVALID, e
             return
         assert info[0].startswith("tile") and info[0].endswith("/neumann"), info
+        assert ("/fused" in info[0]) == (math == capi.GS_MATH_FUSED), info
         assert_bits_equal(got_u, ref_u, f"U {shape} {info[0]}")
         assert_bits_equal(got_v, ref_v, f"V {shape} {info[0]}")
 
