@@ -39,6 +39,9 @@ UNITS = [
     # the parameter-specialised strict variants: their own translation unit, compiled in parallel
     ("gs_step_kernels.hip", "gs_step_strict_op.o", STRICT + ["-DGS_TB_OP_ONLY=1"] + KERNEL_FLAGS),
     ("gs_step_kernels.hip", "gs_step_fused.o", ["-DGS_MATH_FUSED=1"] + KERNEL_FLAGS),
+    # the parameter map's forms of the marching kernel (gs_step_tb_mk), one translation unit per flavour
+    ("gs_step_kernels.hip", "gs_step_strict_map.o", STRICT + ["-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
+    ("gs_step_kernels.hip", "gs_step_fused_map.o", ["-DGS_MATH_FUSED=1", "-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
     ("gs_util_kernels.hip", "gs_util.o", []),
     # the host side (contexts and schedule, planes, kernel configuration, the window kernel's runtime, RCCL): only the
     # C ABI of include/gs_hip.h is visible outside the library
@@ -48,6 +51,7 @@ UNITS = [
     ("gs_window.cpp", "gs_window.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_rccl.cpp", "gs_rccl.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_ensemble.cpp", "gs_ensemble.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_param_map.cpp", "gs_param_map.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

@@ -43,6 +43,7 @@ EXPORTS = (
     "gs_debug_exchange_probe_destroy", "gs_download_wait_but",
     "gs_ensemble_create", "gs_ensemble_destroy", "gs_ensemble_shape", "gs_ensemble_set_params", "gs_ensemble_seed",
     "gs_ensemble_upload", "gs_ensemble_download", "gs_ensemble_run",
+    "gs_ctx_set_param_map",
 )
 
 
@@ -129,6 +130,7 @@ def load() -> ctypes.CDLL:
         "gs_ctx_create": (i32, [P(vp), P(GsParams), P(GsOptions), P(i32), i32, i32, i32, vp]),
         "gs_ctx_destroy": (i32, [vp]),
         "gs_ctx_set_params": (i32, [vp, P(GsParams)]),
+        "gs_ctx_set_param_map": (i32, [vp, vp, vp]),
         "gs_field_create": (i32, [vp, P(vp), u64, u64]),
         "gs_field_destroy": (i32, [vp, vp]),
         "gs_field_shape": (i32, [vp, P(u64), P(u64)]),

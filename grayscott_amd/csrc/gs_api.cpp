@@ -163,24 +163,26 @@ int32_t refresh_ghosts(gs_ctx *ctx, gs_field *f)
     return GS_OK;
 }
 
-int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fuse)
+int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fuse, const GsMapPlanes *map)
 {
     int32_t kernel = ctx->o.kernel;
     if (kernel == GS_KERNEL_AUTO || kernel == GS_KERNEL_TILE || kernel == GS_KERNEL_WINDOW) kernel = fuse > 1 ? GS_KERNEL_TB : GS_KERNEL_STREAM;
     if (fuse > 1 && kernel != GS_KERNEL_TB)
         return fail(GS_ERR_UNSUPPORTED, "only the temporally blocked kernel fuses steps");
     const bool fused = ctx->o.math == GS_MATH_FUSED;
+    if (map && kernel == GS_KERNEL_LDS) // (gs_ctx_set_param_map refuses such a context first)
+        return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no parameter-map form");
     const char *name = nullptr;
     hipError_t e;
     switch (kernel) {
     case GS_KERNEL_TB:
-        e = fused ? gs_launch_tb_fused(a, fuse, stream, &name) : gs_launch_tb_strict(a, fuse, stream, &name);
+        e = fused ? gs_launch_tb_fused(a, fuse, stream, &name, map) : gs_launch_tb_strict(a, fuse, stream, &name, map);
         break;
     case GS_KERNEL_SIMPLE:
-        e = fused ? gs_launch_simple_fused(a, stream, &name) : gs_launch_simple_strict(a, stream, &name);
+        e = fused ? gs_launch_simple_fused(a, stream, &name, map) : gs_launch_simple_strict(a, stream, &name, map);
         break;
     case GS_KERNEL_STREAM:
-        e = fused ? gs_launch_stream_fused(a, stream, &name) : gs_launch_stream_strict(a, stream, &name);
+        e = fused ? gs_launch_stream_fused(a, stream, &name, map) : gs_launch_stream_strict(a, stream, &name, map);
         break;
     case GS_KERNEL_LDS:
         e = fused ? gs_launch_lds_fused(a, stream, &name) : gs_launch_lds_strict(a, stream, &name);
@@ -231,6 +233,17 @@ GsStepArgs make_args(const gs_ctx *ctx, const gs_field *in_u, const gs_field *in
     a.dt = ctx->p.dt;
     a.fast = fast_of(ctx);
     return a;
+}
+
+// The parameter map's planes of local slab i, rows from `row` on (a row band's first row), for launch_rows: nullptr
+// without a map (the launchers then run the uniform kernels).
+static const GsMapPlanes *map_planes(const gs_ctx *ctx, int i, int row, GsMapPlanes &out)
+{
+    if (!ctx->mapped()) return nullptr;
+    const ptrdiff_t off = (ptrdiff_t)row * ctx->map.feed->pitch;
+    out.feed = ctx->map.feed->s[i].row0 + off;
+    out.fpk = ctx->map.fpk->s[i].row0 + off;
+    return &out;
 }
 
 // ---- in-place row bands of a single slab -------------------------------------------------
@@ -312,6 +325,8 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         a.allow_fair = 0; // several launches share the chip
         const ptrdiff_t off = (ptrdiff_t)r0 * full.pitch;
         a.in_u += off; a.in_v += off; a.out_u += off; a.out_v += off;
+        GsMapPlanes mp;
+        const GsMapPlanes *map = map_planes(ctx, 0, r0, mp);
         a.rows = r1 - r0;
         a.top_present = k > 0;
         a.bottom_present = k < V - 1;
@@ -327,14 +342,14 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         e.rb0 = nk <= 2 * fuse ? 0 : nk - fuse;
         e.rb1 = nk <= 2 * fuse ? 0 : nk;
         e.rows_per_unit = fuse;
-        GS_TRY(launch_rows(ctx, e, b.halo, fuse));
+        GS_TRY(launch_rows(ctx, e, b.halo, fuse, map));
         GS_HIP(hipEventRecord(b.halod[p], b.halo));
         GS_HIP(hipStreamWaitEvent(b.compute, ctx->band_join, 0));
         GS_HIP(hipStreamWaitEvent(b.compute, b.halod[q], 0));
         if (nk > 2 * fuse) {
             a.ra0 = fuse;
             a.ra1 = nk - fuse;
-            GS_TRY(launch_rows(ctx, a, b.compute, fuse));
+            GS_TRY(launch_rows(ctx, a, b.compute, fuse, map));
         }
         GS_HIP(hipEventRecord(b.done[p], b.compute));
     }
@@ -367,7 +382,8 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
         GsStepArgs a = make_args(ctx, in_u, in_v, out_u, out_v, 0, fuse);
         a.ra0 = 0;
         a.ra1 = a.rows;
-        GS_TRY(launch_rows(ctx, a, sl.compute, fuse));
+        GsMapPlanes mp;
+        GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map_planes(ctx, 0, 0, mp)));
     } else {
         if (fuse > kGhostRows || fuse > min_slab_rows(ctx, in_u))
             return fail(GS_ERR_INVALID, "cannot fuse %d steps over slabs of %d rows", fuse, min_slab_rows(ctx, in_u));
@@ -385,6 +401,8 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             SlabRt &sl = ctx->slabs[i];
             GS_HIP(hipSetDevice(sl.device));
             GsStepArgs a = make_args(ctx, in_u, in_v, out_u, out_v, i, fuse);
+            GsMapPlanes mp;
+            const GsMapPlanes *map = map_planes(ctx, i, 0, mp);
             const int n = a.rows;
             // gs_ctx_set_pass_timing: events around this pass's halo-stream work and interior kernel
             const bool timed = sl.timed < ctx->pass_timing;
@@ -404,7 +422,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             b.rb0 = n <= 2 * depth ? 0 : n - depth;
             b.rb1 = n <= 2 * depth ? 0 : n;
             b.rows_per_unit = depth; // one unit per boundary band and strip
-            GS_TRY(launch_rows(ctx, b, sl.halo, fuse));
+            GS_TRY(launch_rows(ctx, b, sl.halo, fuse, map));
             GS_TRY(push_halo(ctx, outs, 2, i, sl.halo, depth));
             GS_HIP(hipEventRecord(sl.halod[p], sl.halo));
             if (timed) GS_HIP(hipEventRecord(sl.th1[sl.timed], sl.halo));
@@ -414,7 +432,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             if (n > 2 * depth) {
                 a.ra0 = depth;
                 a.ra1 = n - depth;
-                GS_TRY(launch_rows(ctx, a, sl.compute, fuse));
+                GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map));
             }
             GS_HIP(hipEventRecord(sl.done[p], sl.compute));
             if (timed) {
@@ -469,6 +487,7 @@ int32_t replay_graph_batches(Run &r, int kk)
     key.cpl = pick_cols_per_lane(ctx, (int32_t)f->rows, (int32_t)f->cols, kk);
     key.batch = kGraphBatch;
     key.p = ctx->p;
+    key.map_gen = ctx->map.gen;
     if (!ctx->graph_exec || !(ctx->graph_key == key)) {
         if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
         if (ctx->graph) { (void)hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
@@ -548,6 +567,7 @@ int32_t gs_device_count(int32_t *out)
 int32_t gs_ctx_destroy(gs_ctx *ctx)
 {
     if (!ctx) return GS_OK;
+    destroy_param_map(ctx);
     for (auto &sl : ctx->slabs) {
         if (!sl.compute && !sl.halo) continue; // never initialised (creation failed early)
         if (hipSetDevice(sl.device) != hipSuccess) continue;
@@ -598,10 +618,11 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     if (ctx->band_join) (void)hipEventDestroy(ctx->band_join);
-    if (!ctx->tunings.empty() && !ctx->slabs.empty() && hipSetDevice(ctx->slabs[0].device) == hipSuccess)
-        for (auto &t : ctx->tunings)
-            for (auto e : t.events)
-                if (e) (void)hipEventDestroy(e);
+    if ((!ctx->tunings.empty() || !ctx->map.tunings.empty()) && !ctx->slabs.empty() && hipSetDevice(ctx->slabs[0].device) == hipSuccess)
+        for (auto *tunings : {&ctx->tunings, &ctx->map.tunings}) // (the other kernel set's, gs_param_map.cpp)
+            for (auto &t : *tunings)
+                for (auto e : t.events)
+                    if (e) (void)hipEventDestroy(e);
     (void)hipGetLastError(); // teardown failures must not leak into later calls' status
     delete ctx;
     return GS_OK;
@@ -760,6 +781,7 @@ int32_t gs_ctx_set_params(gs_ctx *ctx, const gs_params *params)
 int32_t gs_step(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, gs_field *out_v)
 {
     GS_TRY(check_step_fields(ctx, in_u, in_v, out_u, out_v));
+    GS_TRY(check_map_shape(ctx, in_u));
     GS_TRY(resolve_window(ctx));
     return step_impl(ctx, in_u, in_v, out_u, out_v);
 }
@@ -779,6 +801,7 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
                   bool allow_window)
 {
     GS_TRY(check_step_fields(ctx, u0, v0, u1, v1));
+    GS_TRY(check_map_shape(ctx, u0));
     Run r{ctx, {u0, u1}, {v0, v1}};
     r.steps = steps;
     // Temporal blocking: `fuse` steps per pass over HBM (default 4, the measured optimum);
@@ -792,10 +815,12 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
         if (fuse < 1) fuse = 1;
     }
     const bool single = ctx->total_slabs() == 1;
+    // With a parameter map every grid runs the marching kernel: the resident, tile and window kernels have no map form.
+    const bool mapped = ctx->mapped();
     // Small grids (single slab, kernel = auto): the whole run is one launch with the grid resident
     // in LDS (gs_run_resident_k) -- up to kGsResidentCells = 1536 cells; above, the window kernel is faster (1536
     // cells: 1630 against 1558 Mcells x steps / s; 2048: 1596 against 2062; 4096: 1695 against 4153; run 48).
-    if (single && ctx->o.kernel == GS_KERNEL_AUTO && u0->rows * u0->cols > 0 && steps > 0 &&
+    if (single && !mapped && ctx->o.kernel == GS_KERNEL_AUTO && u0->rows * u0->cols > 0 && steps > 0 &&
         u0->rows * u0->cols <= (uint64_t)kGsResidentCells) {
         SlabRt &sl = ctx->slabs[0];
         GS_HIP(hipSetDevice(sl.device));
@@ -830,7 +855,7 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
     const uint64_t cells = u0->rows * u0->cols;
     // (not under the periodic and zero-flux rules: the window kernel has no form for them, and kernel = auto takes the
     // marching kernel)
-    if (allow_window && single && cells > 0 && steps > 0 && !ctx->win.disabled && ctx->o.boundary != GS_BOUNDARY_PERIODIC &&
+    if (allow_window && single && !mapped && cells > 0 && steps > 0 && !ctx->win.disabled && ctx->o.boundary != GS_BOUNDARY_PERIODIC &&
         ctx->o.boundary != GS_BOUNDARY_NEUMANN) {
         const bool forced = ctx->o.kernel == GS_KERNEL_WINDOW;
         const bool automatic = ctx->o.kernel == GS_KERNEL_AUTO && ctx->o.fuse_steps == 0 && ctx->o.rows_per_block == 0 &&
@@ -852,11 +877,11 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
     // kernel is ahead again); GS_KERNEL_TILE forces it (tile_shape and fuse_steps then choose the window
     // and the steps per launch).
     int auto_shape = -1, auto_k = 0;
-    if (single && ctx->o.kernel == GS_KERNEL_AUTO && ctx->o.fuse_steps == 0 && ctx->o.rows_per_block == 0 &&
+    if (single && !mapped && ctx->o.kernel == GS_KERNEL_AUTO && ctx->o.fuse_steps == 0 && ctx->o.rows_per_block == 0 &&
         ctx->o.cols_per_lane == 0 && ctx->o.split <= 1 && !ctx->o.use_graph && cells > (uint64_t)kGsResidentCells &&
         cells < kTileAutoCells)
         pick_tile_config((long)u0->rows, (long)u0->cols, &auto_shape, &auto_k);
-    if (single && cells > 0 && steps > 0 && (ctx->o.kernel == GS_KERNEL_TILE || auto_shape >= 0)) {
+    if (single && !mapped && cells > 0 && steps > 0 && (ctx->o.kernel == GS_KERNEL_TILE || auto_shape >= 0)) {
         SlabRt &sl = ctx->slabs[0];
         GS_HIP(hipSetDevice(sl.device));
         GS_TRY(join_bands(ctx, sl.compute));

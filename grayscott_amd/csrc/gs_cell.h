@@ -18,6 +18,18 @@ __device__ __forceinline__ void react(const GsStepArgs &a, float u, float v, flo
     out_u = DT1 ? u + du : u + du * a.dt;
     out_v = DT1 ? v + dv : v + dv * a.dt;
 }
+// The parameter map's form (gs_ctx_set_param_map): this cell's feed and feed_plus_kill (F[r, c] and the f32 sum
+// F[r, c] + K[r, c], formed once when the map is attached), the same operations in the same order.
+template <bool DT1 = false>
+__device__ __forceinline__ void react(const GsStepArgs &a, float feed, float feed_plus_kill, float u, float v, float acc_u,
+                                      float acc_v, float &out_u, float &out_v)
+{
+    const float uv_square = (u * v) * v;
+    const float du = (a.du * acc_u - uv_square) + feed * (1.0f - u);
+    const float dv = (a.dv * acc_v + uv_square) - feed_plus_kill * v;
+    out_u = DT1 ? u + du : u + du * a.dt;
+    out_v = DT1 ? v + dv : v + dv * a.dt;
+}
 
 // (s - c) * 0.5f in ONE instruction: v_sub_f32 with the VOP3 output modifier div:2.  The hardware
 // applies the modifier to the rounded difference, so the result has the bits of the two-operation
@@ -145,10 +157,11 @@ __device__ __forceinline__ RowW widen(const RowIn &r)
 // 6 (right) or 18 (left, first cell of a lane only) selects on top of the interior's 53 instructions, where the
 // general path needs 83: the edge strips -- 8 % of the units of a 4096^2 launch -- cost 1.1-1.2x an interior
 // strip instead of 1.57x.
-template <int EDGE, int FAST = 0, typename Row = RowW, int ZH = -1>
+// MAP: the reaction takes the cell's own rates, `mf` (feed) and `mfk` (feed_plus_kill), from the parameter map.
+template <int EDGE, int FAST = 0, typename Row = RowW, int ZH = -1, bool MAP = false>
 __device__ __forceinline__ void cell(const GsStepArgs &a, const Row &m, const Row &z,
                                      const Row &p, int k, bool mrow, bool prow, uint32_t la, uint32_t ra,
-                                     float &out_u, float &out_v)
+                                     float &out_u, float &out_v, float mf = 0.0f, float mfk = 0.0f)
 {
     const float u = z.u[k], v = z.v[k];
     float acc_u = 0.0f, acc_v = 0.0f;
@@ -259,7 +272,10 @@ __device__ __forceinline__ void cell(const GsStepArgs &a, const Row &m, const Ro
         if (prow) GS_ROW_TAPS(p, 2, true)
 #undef GS_ROW_TAPS
     }
-    react<(FAST & 2) != 0>(a, u, v, acc_u, acc_v, out_u, out_v);
+    if constexpr (MAP)
+        react<(FAST & 2) != 0>(a, mf, mfk, u, v, acc_u, acc_v, out_u, out_v);
+    else
+        react<(FAST & 2) != 0>(a, u, v, acc_u, acc_v, out_u, out_v);
 }
 
 } // namespace

@@ -6,6 +6,7 @@
 //   gs_window.cpp  the persistent window kernel's host side: tiling, exchange planes, give-up and replay
 //   gs_rccl.cpp    RCCL (loaded on first use), its self-test, gs_runtime_info, gs_last_error
 //   gs_ensemble.cpp ensembles: many grids of one shape, each with its own parameters, advanced in shared launches
+//   gs_param_map.cpp parameter maps: per-cell feed and kill rates on one grid (gs_ctx_set_param_map)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
@@ -157,10 +158,12 @@ struct gs_ctx {
         uint64_t rows = 0, cols = 0;
         int k = 0, rpu = 0, cpl = 0, batch = 0;
         gs_params p{};
+        uint64_t map_gen = 0; // the parameter map in force (gs_ctx::ParamMap::gen)
         bool operator==(const GraphKey &o) const
         {
             return std::memcmp(planes, o.planes, sizeof planes) == 0 && rows == o.rows && cols == o.cols && k == o.k &&
-                   rpu == o.rpu && cpl == o.cpl && batch == o.batch && std::memcmp(&p, &o.p, sizeof p) == 0;
+                   rpu == o.rpu && cpl == o.cpl && batch == o.batch && std::memcmp(&p, &o.p, sizeof p) == 0 &&
+                   map_gen == o.map_gen;
         }
     } graph_key;
     hipGraph_t graph = nullptr;
@@ -196,6 +199,20 @@ struct gs_ctx {
     } win;
     int share_now = kShareDefault; // form of difference sharing in force when gs_options.share_taps leaves the choice open (share_mode)
     int cu_count = 0; // compute units of the first slab's device
+    // gs_ctx_set_param_map: the map's planes, owned by the context (F and F + K in the field layout of the species, ghost
+    // rows filled), nullptr without a map; `gen` advances with every attachment, replacement and detachment (GraphKey).
+    struct ParamMap {
+        gs_field *feed = nullptr, *fpk = nullptr;
+        uint64_t gen = 0;
+        // The tuner's choices and tunings of the OTHER kernel set -- the uniform kernels' while a map is attached, the map
+        // kernels' otherwise -- exchanged with the context's own ones when a map is attached or detached (gs_param_map.cpp)
+        uint64_t tuned_rows = 0, tuned_cols = 0;
+        int tuned_fuse = 0, tuned_rpu = 0, tuned_split = 0, tuned_k = 0, tuned_cpl = 0;
+        int tuned_share = kShareDefault, share_now = kShareDefault;
+        std::vector<Tuned> tuned_cache;
+        std::vector<Tuning> tunings;
+    } map;
+    bool mapped() const { return map.feed != nullptr; }
     int total_slabs() const { return world * (int)slabs.size(); }
     int global_index(int i) const { return rank * (int)slabs.size() + i; }
 };
@@ -266,6 +283,10 @@ std::vector<GsWindowDesc> plan_windows(int cu_count, bool zero_halo, bool cheap,
 int32_t ensure_window_rt(gs_ctx *ctx, const gs_field *f);
 int32_t resolve_window(gs_ctx *ctx);
 int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *launched, int32_t *result_slot);
+
+// gs_param_map.cpp
+int32_t check_map_shape(const gs_ctx *ctx, const gs_field *f);
+void destroy_param_map(gs_ctx *ctx);
 
 // ---- gs_run: state of one call -------------------------------------------------------------------------------------
 // ---- gs_run: state of one call, on-line tuning, graph replay ---------------------------------

@@ -73,6 +73,12 @@ struct GsStepArgs {
     float w[3][3];         // stencil weights, row-major (parameters.rs:87-88)
     float du, dv, feed, feed_plus_kill, dt;
 };
+// Parameter map (gs_ctx_set_param_map): local row 0, column 0 of one slab's F and F + K planes, laid out like the species'
+// planes (same pitch, ghost rows and guards), so that a map load reuses the byte offset of the U load at the same cell.
+// The second argument of the map kernels (gs_*_mk): GsStepArgs, and with it every other kernel's code, stays as it is.
+struct GsMapPlanes {
+    const float *feed, *fpk;
+};
 
 // gs_launch_window_*: one persistent launch for a whole gs_run on grids of ONE round of register-resident windows.
 // Every workgroup owns a rectangle of the grid (GsWindowDesc; the rectangles tile the grid) and keeps it plus a k-cell
@@ -141,16 +147,19 @@ struct GsEnsArgs {
 };
 
 // Launchers, one set per arithmetic flavour (see gs_math in include/gs_hip.h).  Each
-// returns the hipError_t of the launch.  `name` receives a static kernel-variant label.
+// returns the hipError_t of the launch.  `name` receives a static kernel-variant label.  `map` (simple, stream and
+// marching kernels): the slab's parameter-map planes -- the launch then runs the map form -- or nullptr.
 #define GS_DECLARE_LAUNCHERS(SUFFIX)                                                           \
-    hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name); \
-    hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name); \
+    hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr); \
+    hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr); \
     hipError_t gs_launch_resident_##SUFFIX(const GsStepArgs &a, int steps, hipStream_t s, const char **name); \
-    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name); \
+    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr); \
     hipError_t gs_launch_tile_##SUFFIX(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name); \
     hipError_t gs_launch_lds_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name);  \
     hipError_t gs_launch_window_##SUFFIX(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name); \
-    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary);                                    \
+    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary, bool map = false);                  \
+    hipError_t gs_launch_map_rates_##SUFFIX(const float *feed, const float *kill, float *fpk, size_t n, hipStream_t s); \
+    const void *gs_tb_map_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                                \
     hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
     hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name);
 
@@ -163,6 +172,10 @@ GS_DECLARE_LAUNCHERS(fused)
 // rule: the kernel set of the boundary rule, 0 = the clipped and zero-halo rules' kernels, 1 = the periodic rule's
 // (gs_step_tb_pk and kin), 2 = the zero-flux rule's (gs_step_tb_nk and kin).
 const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule = 0);
+// gs_launch_map_rates_*: fpk[i] = feed[i] + kill[i] over n floats, one f32 add in the flavour's float mode (strict: a
+// sub-normal sum is flushed, as the reference's DenormalsFlusher does).  gs_tb_map_kernel_*: the entry of the marching
+// kernel's map form (gs_step_tb_mk: its own translation unit, GS_TB_MAP_ONLY) for k fused steps, fast in {0, 3} (3: the
+// .op variant, strict only), cpl columns per lane and rule = rule_set(boundary); nullptr for a form that is not built.
 
 // Plane utilities (math-agnostic, defined once in gs_util_kernels.hip).
 hipError_t gs_launch_colormap(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float scale,

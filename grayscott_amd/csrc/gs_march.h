@@ -96,9 +96,11 @@ __device__ __forceinline__ RowT<CPL> widen_tb(const float (&u)[CPL], const float
 // bit for bit except that a zero comes out as +0 on both sides, and the accumulator, never -0, does not tell +0
 // from -0 (see half_diff).  So the right-hand tap of a cell is kept and SUBTRACTED as the left-hand tap of the next
 // cell: one instruction less per pair of neighbours, the reference's order of additions unchanged.
-template <int FAST, int CPL, int ZH>
+// MAP: the cells' own rates from the parameter map, mf[i] / mfk[i] for cell i (react's map form).
+template <int FAST, int CPL, int ZH, bool MAP = false>
 __device__ __forceinline__ void cells_interior(const GsStepArgs &a, const RowT<CPL> &m, const RowT<CPL> &z, const RowT<CPL> &p,
-                                               float (&nu)[CPL], float (&nv)[CPL])
+                                               float (&nu)[CPL], float (&nv)[CPL], const float *mf = nullptr,
+                                               const float *mfk = nullptr)
 {
     if constexpr (GS_TB_HSHARE && CPL > 1 && (FAST & 1) && !GS_MATH_FUSED) {
         float hu = 0.0f, hv = 0.0f; // the previous cell's right-hand tap
@@ -119,11 +121,16 @@ __device__ __forceinline__ void cells_interior(const GsStepArgs &a, const RowT<C
             GS_TAP(acc_u, a.w[2][0], p.u[k - 1], u); GS_TAP(acc_v, a.w[2][0], p.v[k - 1], v);
             GS_TAP_HALF(acc_u, p.u[k], u);           GS_TAP_HALF(acc_v, p.v[k], v);
             GS_TAP(acc_u, a.w[2][2], p.u[k + 1], u); GS_TAP(acc_v, a.w[2][2], p.v[k + 1], v);
-            react<(FAST & 2) != 0>(a, u, v, acc_u, acc_v, nu[k - 1], nv[k - 1]);
+            if constexpr (MAP)
+                react<(FAST & 2) != 0>(a, mf[k - 1], mfk[k - 1], u, v, acc_u, acc_v, nu[k - 1], nv[k - 1]);
+            else
+                react<(FAST & 2) != 0>(a, u, v, acc_u, acc_v, nu[k - 1], nv[k - 1]);
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < CPL; ++k) cell<0, FAST, RowT<CPL>, ZH>(a, m, z, p, k + 1, true, true, 0u, 0u, nu[k], nv[k]);
+        for (int k = 0; k < CPL; ++k)
+            cell<0, FAST, RowT<CPL>, ZH, MAP>(a, m, z, p, k + 1, true, true, 0u, 0u, nu[k], nv[k], MAP ? mf[k] : 0.0f,
+                                              MAP ? mfk[k] : 0.0f);
     }
 }
 
@@ -330,8 +337,14 @@ __host__ __device__ constexpr int tb_halo_floats(int k, bool cross) { return cro
 // code (no edge selects).  The row wrap is wave-uniform (a scalar base address per fetch); the column wrap is per lane,
 // computed once per unit, and a lane whose column group is not one aligned piece of a row after wrapping (cols %
 // CPL != 0: the group that straddles the wrap from cols - 1 to 0, and the lanes behind it) loads column by column.
-template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false>
-__device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, int strip, int lane,
+// MAP: the parameter map's form (gs_step_tb_mk).  At the start of every tick the lane loads, for each level j, the map's
+// values at the row that level computes in the tick (l0 - j) and at its own columns: the byte offsets of the U loads
+// (the map planes share the species' layout), the row clamped into the rows the U loads may touch -- wrapped with
+// them under the periodic rule -- so every address is one the U loads may form.  A level's row was fetched by the
+// level below it one tick earlier, so the reloads hit in the caches; the K loads are issued together, ahead of the
+// levels' arithmetic.
+template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false, bool MAP = false>
+__device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, int strip, int lane, const GsMapPlanes &mp,
                                          const FairBoard &fb GS_TRACE_PARAM)
 {
     constexpr int S = tb_sacrificial_lanes(K, CPL), W = tb_cols_per_wave(K, CPL);
@@ -391,6 +404,44 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
         if (load_ok) {
             load_cols_buf<CPL>(ru, voff, (rr - row_lo) * pitch_bytes, r.u);
             load_cols_buf<CPL>(rv, voff, (rr - row_lo) * pitch_bytes, r.v);
+        } else {
+#pragma unroll
+            for (int i = 0; i < CPL; ++i) { r.u[i] = 0.f; r.v[i] = 0.f; }
+        }
+        return r;
+    };
+    // MAP: (F, F + K) at this lane's columns of `row`, the addresses of fetch(row) in the map planes (RowQ::u = F, ::v = F + K)
+    auto fetch_map = [&](int row) {
+        RowQ<CPL> r;
+        if constexpr (PER) {
+            int rr = row; // wave-uniform
+            if (rr < 0) rr += a.rows;
+            if (rr >= a.rows) rr -= a.rows;
+            if (rr < 0 || rr >= a.rows) { rr = row % a.rows; if (rr < 0) rr += a.rows; }
+            const __amdgpu_buffer_rsrc_t pf = plane_rsrc(mp.feed + (ptrdiff_t)rr * pitch), pk = plane_rsrc(mp.fpk + (ptrdiff_t)rr * pitch);
+            if (pvec) {
+                load_cols_buf<CPL>(pf, pc0 * (int)sizeof(float), 0, r.u);
+                load_cols_buf<CPL>(pk, pc0 * (int)sizeof(float), 0, r.v);
+            } else {
+#pragma unroll
+                for (int i = 0; i < CPL; ++i) {
+                    int cc = pc0 + i;
+                    if (cc >= a.cols) cc -= a.cols;
+                    if (cc >= a.cols) cc %= a.cols;
+                    float x[1];
+                    load_cols_buf<1>(pf, cc * (int)sizeof(float), 0, x);
+                    r.u[i] = x[0];
+                    load_cols_buf<1>(pk, cc * (int)sizeof(float), 0, x);
+                    r.v[i] = x[0];
+                }
+            }
+            return r;
+        }
+        const int rr = min(max(row, row_lo), row_hi);
+        if (load_ok) {
+            const __amdgpu_buffer_rsrc_t mf = plane_rsrc(mp.feed + (ptrdiff_t)row_lo * pitch), mk = plane_rsrc(mp.fpk + (ptrdiff_t)row_lo * pitch);
+            load_cols_buf<CPL>(mf, voff, (rr - row_lo) * pitch_bytes, r.u);
+            load_cols_buf<CPL>(mk, voff, (rr - row_lo) * pitch_bytes, r.v);
         } else {
 #pragma unroll
             for (int i = 0; i < CPL; ++i) { r.u[i] = 0.f; r.v[i] = 0.f; }
@@ -567,6 +618,11 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
                 fair_tick(tick);
                 w[0][s3] = widen_tb<CPL>(q[s3].u, q[s3].v);
                 if constexpr (!LATE) q[s3] = fetch(l0 + 3);
+                RowQ<CPL> rates[K]; // MAP: (F, F + K) of the row level j computes in this tick, in rates[j - 1]
+                if constexpr (MAP) {
+#pragma unroll
+                    for (int j = 1; j <= K; ++j) rates[j - 1] = fetch_map(l0 - j);
+                }
 #pragma unroll
                 for (int j = 1; j <= K; ++j) {
                     const int row = l0 - j; // level-j row produced in this tick
@@ -580,19 +636,23 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
                         const bool mrow = !ROWS || (row > 0) || a.top_present;
                         const bool prow = !ROWS || (row + 1 < a.rows) || a.bottom_present;
                         float nu[CPL], nv[CPL];
+                        const float *mf = MAP ? rates[j - 1].u : nullptr, *mfk = MAP ? rates[j - 1].v : nullptr;
                         if constexpr (EDGE == 4) {
                             if (mrow && prow) {
-                                cells_interior<FAST, CPL, ZH>(a, m, z, p, nu, nv);
+                                cells_interior<FAST, CPL, ZH, MAP>(a, m, z, p, nu, nv, mf, mfk);
                             } else {
 #pragma unroll
-                                for (int k = 0; k < CPL; ++k) cell<1, FAST, RowT<CPL>, ZH>(a, m, z, p, k + 1, mrow, prow, 0u, 0u, nu[k], nv[k]);
+                                for (int k = 0; k < CPL; ++k)
+                                    cell<1, FAST, RowT<CPL>, ZH, MAP>(a, m, z, p, k + 1, mrow, prow, 0u, 0u, nu[k], nv[k],
+                                                                      MAP ? mf[k] : 0.0f, MAP ? mfk[k] : 0.0f);
                             }
                         } else if constexpr (EDGE == 0 || PER) {
-                            cells_interior<FAST, CPL, ZH>(a, m, z, p, nu, nv);
+                            cells_interior<FAST, CPL, ZH, MAP>(a, m, z, p, nu, nv, mf, mfk);
                         } else {
 #pragma unroll
                             for (int k = 0; k < CPL; ++k)
-                                cell<EDGE, FAST, RowT<CPL>, ZH>(a, m, z, p, k + 1, mrow, prow, la[k], ra[k], nu[k], nv[k]);
+                                cell<EDGE, FAST, RowT<CPL>, ZH, MAP>(a, m, z, p, k + 1, mrow, prow, la[k], ra[k], nu[k], nv[k],
+                                                                     MAP ? mf[k] : 0.0f, MAP ? mfk[k] : 0.0f);
                         }
                         if (j < K) {
                             w[j][s3] = widen_tb<CPL>(nu, nv);
@@ -611,9 +671,11 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
 // WG: waves per workgroup.  4 independent waves, or all 16 of a CU with the progress board of tb_march<FAIR>.
 // PER: the periodic rule's kernels (GsStepArgs::zero_halo = 2; kernels of their own, gs_step_tb_pk and its kin).
 // NEU: the zero-flux rule's kernels (GsStepArgs::zero_halo = 3; gs_step_tb_nk and its kin).
-template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false>
-__device__ __forceinline__ void tb_unit(const GsStepArgs &a)
+// MAP: the parameter map's forms (gs_step_tb_mk): 4-wave workgroups, no difference sharing.
+template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false>
+__device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
 {
+    static_assert(!MAP || (WG == 4 && (FAST & 4) == 0), "the map forms are 4-wave marches without difference sharing");
     // half_diff needs MODE.IEEE = 0: hwreg(HW_REG_MODE, offset 9, width 1).  The bit only governs
     // the quieting of signalling NaNs otherwise, which parity does not cover.
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0);
@@ -741,26 +803,26 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a)
     constexpr bool KINDS = (FAST & 1) && !GS_MATH_FUSED;
     if constexpr (PER) {
         if (!edge)
-            tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
         else
-            tb_march<K, 5, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+            tb_march<K, 5, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     } else if constexpr (NEU) {
         if (!edge)
-            tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
         else
-            tb_march<K, 1, FAST, CPL, 3, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+            tb_march<K, 1, FAST, CPL, 3, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     } else if (!edge)
-        tb_march<K, 0, FAST, CPL, -1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        tb_march<K, 0, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (a.zero_halo) // (0 or 1 in these kernels: gs_launch_tb sends the other rules to gs_step_tb_pk / _nk)
-        tb_march<K, 1, FAST, CPL, 1, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        tb_march<K, 1, FAST, CPL, 1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && left && !right && !ends)
-        tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && right && !left && !ends)
-        tb_march<K, KINDS ? 3 : 1, FAST, CPL, 0, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 3 : 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && ends && !left && !right)
-        tb_march<K, KINDS ? 4 : 1, FAST, CPL, 0, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 4 : 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else
-        tb_march<K, 1, FAST, CPL, 0, FAIR>(a, ur0, ur1, strip, lane, fb GS_TRACE_ARG);
+        tb_march<K, 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     if constexpr (FAIR) { if (lane == 0) fb.progress[wave] = 0x7fffffff; }
 #undef GS_TB_LEAVE
 #if defined(GS_TB_TRACE)
@@ -829,6 +891,14 @@ template <int K, int WG = 4>
 __global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_dx_nk)(GsStepArgs a)
 {
     tb_unit<K, 15, 2, WG, false, true>(a);
+}
+// The parameter map's forms (the planes of GsMapPlanes): RULE = the kernel set of the boundary rule (0 = clipped and
+// zero halo, 1 = periodic, 2 = zero flux), FAST 0 (general) or 3 (.op, strict only).  Kernels of their own, 4-wave
+// workgroups; the register allocator is left to itself (the launcher derives the occupancy from the registers used).
+template <int K, int FAST, int CPL, int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_tb_mk)(GsStepArgs a, GsMapPlanes mp)
+{
+    tb_unit<K, FAST, CPL, 4, RULE == 1, RULE == 2, true>(a, mp);
 }
 
 } // namespace

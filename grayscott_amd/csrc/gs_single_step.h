@@ -9,7 +9,20 @@ namespace {
 // ------------------------------------------------------------------------------------
 // Cross-check kernel: literal restatement, one thread per cell.
 // ------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_k)(GsStepArgs a)
+// The reaction of cell (r, c) at plane offset o: the context's rates, or the parameter map's at the cell (MAP, the
+// planes of `mp` at the same offset as the cell's U).
+template <bool MAP>
+__device__ __forceinline__ void simple_react(const GsStepArgs &a, const GsMapPlanes &mp, ptrdiff_t o, float u, float v,
+                                             float acc_u, float acc_v, float &ou, float &ov)
+{
+    if constexpr (MAP)
+        react(a, mp.feed[o], mp.fpk[o], u, v, acc_u, acc_v, ou, ov);
+    else
+        react(a, u, v, acc_u, acc_v, ou, ov);
+}
+
+template <bool MAP = false>
+__device__ __forceinline__ void simple_cell(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -47,14 +60,16 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_k)(GsStepArgs a)
             }
     }
     float ou, ov;
-    react(a, u, v, acc_u, acc_v, ou, ov);
+    simple_react<MAP>(a, mp, o, u, v, acc_u, acc_v, ou, ov);
     a.out_u[o] = ou;
     a.out_v[o] = ov;
 }
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_k)(GsStepArgs a) { simple_cell(a); }
 
 // The periodic rule (GsStepArgs::zero_halo = 2), literally: the nine taps of the zero-halo rule's interior cell, in its
 // order, with neighbour (r + i - 1, c + j - 1) read at ((r + i - 1) mod rows, (c + j - 1) mod cols).  A kernel of its own.
-__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_pk)(GsStepArgs a)
+template <bool MAP = false>
+__device__ __forceinline__ void simple_cell_periodic(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -74,15 +89,17 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_pk)(GsStepArgs a
             GS_TAP(acc_v, a.w[i][j], sv, v);
         }
     float ou, ov;
-    react(a, u, v, acc_u, acc_v, ou, ov);
+    simple_react<MAP>(a, mp, rows_at[1] + c, u, v, acc_u, acc_v, ou, ov);
     a.out_u[rows_at[1] + c] = ou;
     a.out_v[rows_at[1] + c] = ov;
 }
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_pk)(GsStepArgs a) { simple_cell_periodic(a); }
 
 // The zero-flux (Neumann) rule (GsStepArgs::zero_halo = 3), literally: the nine taps of the zero-halo rule's interior cell,
 // in its order, with neighbour (r + i - 1, c + j - 1) read at the nearest cell of the grid -- rows clamped at the global
 // edges only (a slab seam reads its ghost row), columns at 0 and cols - 1.  A kernel of its own.
-__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_nk)(GsStepArgs a)
+template <bool MAP = false>
+__device__ __forceinline__ void simple_cell_neumann(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -102,17 +119,31 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_nk)(GsStepArgs a
             GS_TAP(acc_v, a.w[i][j], sv, v);
         }
     float ou, ov;
-    react(a, u, v, acc_u, acc_v, ou, ov);
+    simple_react<MAP>(a, mp, rows_at[1] + c, u, v, acc_u, acc_v, ou, ov);
     a.out_u[rows_at[1] + c] = ou;
     a.out_v[rows_at[1] + c] = ov;
+}
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_nk)(GsStepArgs a) { simple_cell_neumann(a); }
+
+// The parameter map's form of the three (the planes of GsMapPlanes), the replay check of mapped runs.  RULE = the kernel
+// set of the boundary rule: 0 = clipped and zero halo (GsStepArgs::zero_halo read at run time), 1 = periodic, 2 = zero flux.
+template <int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_mk)(GsStepArgs a, GsMapPlanes mp)
+{
+    if constexpr (RULE == 1) simple_cell_periodic<true>(a, mp);
+    else if constexpr (RULE == 2) simple_cell_neumann<true>(a, mp);
+    else simple_cell<true>(a, mp);
 }
 
 // PER: a unit on an edge under the periodic rule (gs_step_stream_pk): rows and columns are read at their index modulo
 // the grid's (a lane whose four columns are not one aligned piece of a row after wrapping loads them one by one), and
 // every cell runs the interior code.  ZH: the boundary rule of the edge cells (cell<>; -1 = GsStepArgs::zero_halo, 3 = the
-// zero-flux rule of gs_step_stream_nk).
-template <int G, bool EDGE, bool PER = false, int ZH = -1>
-__device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int c0, int lane)
+// zero-flux rule of gs_step_stream_nk).  MAP: the parameter map's form (gs_step_stream_mk): a cell's rates are read at the
+// cell itself -- the rows of the unit, this lane's four columns, the addresses of its stores -- one group ahead, like
+// the rows of the species.
+template <int G, bool EDGE, bool PER = false, int ZH = -1, bool MAP = false>
+__device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int c0, int lane,
+                                      const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
 {
     const int c = c0 + lane * 4;
     LaneCtx lc;
@@ -170,12 +201,28 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
         return load_row<EDGE>(bu + (ptrdiff_t)rr * pitch, bv + (ptrdiff_t)rr * pitch, lc);
     };
 
+    // MAP: (F, F + K) of this lane's four cells of `row` (rows past ur1 are not computed: clamped like fetch's)
+    auto fetch_rates = [&](int row, float4 &f, float4 &fk) {
+        const ptrdiff_t o = (ptrdiff_t)(row < ur1 ? row : ur1 - 1) * pitch + c;
+        f = make_float4(0.f, 0.f, 0.f, 0.f);
+        fk = f;
+        if (lc.lane_ok) {
+            f = *reinterpret_cast<const float4 *>(mp.feed + o);
+            fk = *reinterpret_cast<const float4 *>(mp.fpk + o);
+        }
+    };
+
     RowW q[G + 2];
     RowIn n[G];
+    float4 mf[G] = {}, mk[G] = {}; // MAP: the rates of the group being computed
     q[0] = widen(fetch(ur0 - 1));
     q[1] = widen(fetch(ur0));
 #pragma unroll
     for (int g = 0; g < G; ++g) n[g] = fetch(ur0 + 1 + g);
+    if constexpr (MAP) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) fetch_rates(ur0 + g, mf[g], mk[g]);
+    }
 
     // per-lane masks (all ones = that neighbour column is clipped away).  c is a multiple of 4,
     // so only the first of a lane's four cells can sit on the global left edge.
@@ -203,10 +250,10 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
                 const bool prow = !EDGE || (row + 1 < a.rows) || a.bottom_present;
                 float4 nu, nv;
                 constexpr bool E = EDGE && !PER;
-                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x);
-                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y);
-                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z);
-                cell<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w);
+                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x, mf[g].x, mk[g].x);
+                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y, mf[g].y, mk[g].y);
+                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z, mf[g].z, mk[g].z);
+                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w, mf[g].w, mk[g].w);
                 if (lc.lane_ok) {
                     *reinterpret_cast<float4 *>(ou) = nu;
                     *reinterpret_cast<float4 *>(ov) = nv;
@@ -217,6 +264,10 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
         }
         q[0] = q[G];
         q[1] = q[G + 1];
+        if constexpr (MAP) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) fetch_rates(r + G + g, mf[g], mk[g]);
+        }
     }
 }
 
@@ -331,6 +382,47 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_nk)(GsStepArgs a
         march<G, true, false, 3>(a, ur0, ur1, c0, lane);
     else
         march<G, false>(a, ur0, ur1, c0, lane);
+}
+
+// The parameter map's form of the three (the planes of GsMapPlanes): their units, edge tests and marches, with the map's
+// rates.  RULE = the kernel set of the boundary rule: 0 = clipped and zero halo, 1 = periodic, 2 = zero flux.
+template <int G, int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_mk)(GsStepArgs a, GsMapPlanes mp)
+{
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strips = (a.cols + 255) >> 8;
+    int block = (int)blockIdx.x;
+    if (a.xcd_m > 0) { // XCD-aware order (GsStepArgs::xcd_m)
+        const int per = 8 * a.xcd_m, g = block / per, o = block - g * per;
+        if ((g + 1) * per <= (int)gridDim.x) block = g * per + (o & 7) * a.xcd_m + (o >> 3);
+    }
+    const int unit = block * 4 + wave;
+    const int chunk = unit / strips;
+    const int strip = unit - chunk * strips;
+    const int rpu = a.rows_per_unit;
+    const int chunks_a = (a.ra1 - a.ra0 + rpu - 1) / rpu;
+    const int chunks_b = (a.rb1 - a.rb0 + rpu - 1) / rpu;
+    if (chunk >= chunks_a + chunks_b) return; // wave-uniform
+    int ur0, ur1;
+    if (chunk < chunks_a) {
+        ur0 = a.ra0 + chunk * rpu;
+        ur1 = min(ur0 + rpu, a.ra1);
+    } else {
+        ur0 = a.rb0 + (chunk - chunks_a) * rpu;
+        ur1 = min(ur0 + rpu, a.rb1);
+    }
+    const int c0 = strip << 8;
+    const bool edge = (c0 == 0) || (c0 + 256 >= a.cols) || (ur0 == 0 && !a.top_present) ||
+                      (ur1 == a.rows && !a.bottom_present);
+    if (!edge)
+        march<G, false, false, -1, true>(a, ur0, ur1, c0, lane, mp);
+    else if constexpr (RULE == 1)
+        march<G, true, true, -1, true>(a, ur0, ur1, c0, lane, mp);
+    else if constexpr (RULE == 2)
+        march<G, true, false, 3, true>(a, ur0, ur1, c0, lane, mp);
+    else
+        march<G, true, false, -1, true>(a, ur0, ur1, c0, lane, mp);
 }
 
 // ------------------------------------------------------------------------------------

@@ -40,6 +40,12 @@
 //   ..._nk             the zero-flux (Neumann) rule's forms (GsStepArgs::zero_halo = 3) of the same kernels.  Edge units and
 //       windows run the rule's edge cell (cell<ZH = 3>: a missing row or column is the cell's own) at every fused level; the
 //       resident forms (ZH = 3) keep their LDS ring filled with the edge cells' own values.  Slab seams read ghost rows.
+//   ..._mk<..., RULE>  the parameter map's forms (second argument GsMapPlanes, gs_ctx_set_param_map) of the simple,
+//       streaming and marching kernels, one instance per kernel set of a boundary rule (RULE = rule_set()): the reaction
+//       takes F[r, c] and F[r, c] + K[r, c] of the cell it updates (react's map form); the Laplacian is the rule's own.  The
+//       marching kernel's map forms (K = 1..4, 1, 2 and 4 columns per lane, the general variant and, strict only, .op) are
+//       built in a translation unit of their own (GS_TB_MAP_ONLY).  The difference-sharing, fair-progress, tile, resident,
+//       window, LDS-staged and ensemble kernels have none.
 //
 // This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
 // its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
@@ -64,6 +70,14 @@
 #if GS_TB_OP_ONLY && GS_MATH_FUSED
 #error "the fused build has no specialised variants"
 #endif
+// GS_TB_MAP_ONLY=1: this translation unit provides nothing but the parameter map's forms of gs_step_tb_k
+// (gs_step_tb_mk), through gs_tb_map_kernel_<flavour>(), in either flavour.
+#ifndef GS_TB_MAP_ONLY
+#define GS_TB_MAP_ONLY 0
+#endif
+#if GS_TB_OP_ONLY && GS_TB_MAP_ONLY
+#error "GS_TB_OP_ONLY and GS_TB_MAP_ONLY are translation units of their own"
+#endif
 
 #if GS_MATH_FUSED
 #define GS_SUFFIX(x) x##_fused
@@ -77,14 +91,27 @@
 
 #include "gs_cell.h"
 #include "gs_march.h"
-#if !GS_TB_OP_ONLY
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
 #include "gs_single_step.h"
 #include "gs_lds_resident.h"
 #include "gs_ensemble.h"
 #include "gs_window_kernel.h"
 #endif
 
-#if !GS_TB_OP_ONLY
+// Launch tables.  GS_FN: the entry of a kernel instance.  kOp: the FAST argument of the ".op" variant (the fused build
+// has none: its launchers reduce `fast` to 0).  GS_NAME: the name a launcher reports for kernel family BASE, variant V
+// ("", ".op", ...) under the boundary rule of suffix R; GS_RULES: a table of such names per kernel set of a rule ("" for
+// the clipped and zero-halo rules, which share their kernels, then "/periodic" and "/neumann") from one macro M(BASE, R),
+// indexed by rule_set().
+#define GS_FN(KER, ...) reinterpret_cast<const void *>(&GS_SUFFIX(KER)<__VA_ARGS__>)
+[[maybe_unused]] constexpr int kOp = GS_MATH_FUSED ? 0 : 3;
+#define GS_NAME(BASE, V, R) BASE "/" GS_MATH_NAME V R
+#define GS_RULES(M, BASE) {M(BASE, ""), M(BASE, "/periodic"), M(BASE, "/neumann")}
+// The kernel set of boundary rule `boundary` (gs_boundary): 0 = the clipped and zero-halo rules' kernels (*_k), 1 = the
+// periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
+static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
+
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
 // Opt-in for more than 64 KB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize).  The attribute
 // belongs to the device function ON THE CURRENT DEVICE, so what has been set is remembered per (device,
 // function): a process that drives several GPUs (device_ids = 0, 1, ...; two contexts) opts in on each.
@@ -129,27 +156,21 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 }
 #endif
 
-// Launch tables.  GS_FN: the entry of a kernel instance.  kOp: the FAST argument of the ".op" variant (the fused build
-// has none: its launchers reduce `fast` to 0).  GS_NAME: the name a launcher reports for kernel family BASE, variant V
-// ("", ".op", ...) under the boundary rule of suffix R; GS_RULES: a table of such names per kernel set of a rule ("" for
-// the clipped and zero-halo rules, which share their kernels, then "/periodic" and "/neumann") from one macro M(BASE, R),
-// indexed by rule_set().
-#define GS_FN(KER, ...) reinterpret_cast<const void *>(&GS_SUFFIX(KER)<__VA_ARGS__>)
-constexpr int kOp = GS_MATH_FUSED ? 0 : 3;
-#define GS_NAME(BASE, V, R) BASE "/" GS_MATH_NAME V R
-#define GS_RULES(M, BASE) {M(BASE, ""), M(BASE, "/periodic"), M(BASE, "/neumann")}
-// The kernel set of boundary rule `boundary` (gs_boundary): 0 = the clipped and zero-halo rules' kernels (*_k), 1 = the
-// periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
-static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
 #define GS_NAMES_OP(BASE, R) {GS_NAME(BASE, "", R), GS_NAME(BASE, ".op", R)}
+// ... and of the parameter map's kernel sets (the same rules, a "/map" suffix behind the rule's)
+#define GS_RULES_MAP(M, BASE) {M(BASE, "/map"), M(BASE, "/periodic/map"), M(BASE, "/neumann/map")}
+#define GS_NAME1(BASE, R) GS_NAME(BASE, "", R)
 // [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
 #define GS_TILE_NAMES(BASE, R) {GS_NAMES_OP(BASE "tile32x64", R), GS_NAMES_OP(BASE "tile16x64", R), GS_NAMES_OP(BASE "tile64x64", R)}
 #define GS_TILE_FNS(KER) {{GS_FN(KER, 2, 0), GS_FN(KER, 2, kOp)}, {GS_FN(KER, 1, 0), GS_FN(KER, 1, kOp)}, {GS_FN(KER, 4, 0), GS_FN(KER, 4, kOp)}}
 
-hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name)
+hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes)
 {
     const bool per = a.zero_halo == 2, neu = a.zero_halo == 3; // the periodic and zero-flux rules: kernels of their own
-    if (name) *name = per ? "simple/" GS_MATH_NAME "/periodic" : (neu ? "simple/" GS_MATH_NAME "/neumann" : "simple/" GS_MATH_NAME);
+    const bool map = map_planes != nullptr;                    // the parameter map: gs_step_simple_mk
+    static const char *const map_names[3] = GS_RULES_MAP(GS_NAME1, "simple");
+    if (name) *name = map ? map_names[rule_set(a.zero_halo)]
+                          : per ? "simple/" GS_MATH_NAME "/periodic" : (neu ? "simple/" GS_MATH_NAME "/neumann" : "simple/" GS_MATH_NAME);
     const long nrows = (long)(a.ra1 - a.ra0) + (a.rb1 - a.rb0);
     if (nrows <= 0 || a.cols <= 0) return hipSuccess;
     if (per && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // (single slab only)
@@ -158,6 +179,13 @@ hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const
     if (blocks > 0x7fffffffL) return hipErrorInvalidConfiguration;
     GsStepArgs args = a;
     void *kargs[] = {&args};
+    if (map) {
+        static const void *const fns[3] = {GS_FN(gs_step_simple_mk, 0), GS_FN(gs_step_simple_mk, 1), GS_FN(gs_step_simple_mk, 2)};
+        GsMapPlanes mp = *map_planes;
+        if (!mp.feed || !mp.fpk) return hipErrorInvalidValue;
+        void *margs[] = {&args, &mp};
+        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
+    }
     return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_pk))
                            : neu ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_nk))
                                  : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_k)),
@@ -338,11 +366,15 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
     return hipLaunchKernel(fn, dim3((unsigned)x.n_windows), dim3(kWinWaves * 64), kargs, lds, s);
 }
 
-hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name)
+hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes)
 {
     const bool per = a.zero_halo == 2; // the periodic rule: gs_step_stream_pk (single slab)
     const bool neu = a.zero_halo == 3; // the zero-flux rule: gs_step_stream_nk
-    if (name) *name = per ? "stream-g2/" GS_MATH_NAME "/periodic" : (neu ? "stream-g2/" GS_MATH_NAME "/neumann" : "stream-g2/" GS_MATH_NAME);
+    const bool map = map_planes != nullptr; // the parameter map: gs_step_stream_mk
+    static const char *const map_names[3] = GS_RULES_MAP(GS_NAME1, "stream-g2");
+    if (name) *name = map ? map_names[rule_set(a.zero_halo)]
+                          : per ? "stream-g2/" GS_MATH_NAME "/periodic" : (neu ? "stream-g2/" GS_MATH_NAME "/neumann" : "stream-g2/" GS_MATH_NAME);
+    if (map && (!map_planes->feed || !map_planes->fpk)) return hipErrorInvalidValue;
     if (a.cols <= 0 || a.rows_per_unit <= 0 || (per && (a.top_present || a.bottom_present))) return hipErrorInvalidValue;
     const long rpu = a.rows_per_unit;
     const long chunks = ((long)(a.ra1 - a.ra0) + rpu - 1) / rpu + ((long)(a.rb1 - a.rb0) + rpu - 1) / rpu;
@@ -358,6 +390,12 @@ hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const
     static const int xcd_env = gs_env_int("GS_HIP_XCD_M_STREAM", -1, 0, kGsXcdGroupMax);
     args.xcd_m = xcd_env >= 0 ? xcd_env : 16;
     void *kargs[] = {&args};
+    if (map) {
+        static const void *const fns[3] = {GS_FN(gs_step_stream_mk, 2, 0), GS_FN(gs_step_stream_mk, 2, 1), GS_FN(gs_step_stream_mk, 2, 2)};
+        GsMapPlanes mp = *map_planes;
+        void *margs[] = {&args, &mp};
+        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
+    }
     return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_pk)<2>)
                            : neu ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_nk)<2>)
                                  : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_k)<2>),
@@ -443,15 +481,20 @@ static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, int per 
 
 // Wave slots of the chip for the kernel entry a launch with these parameters would use (the tuner's
 // "a launch of exactly r rounds" candidates, gs_tuner.cpp); 0 = no such entry.  `boundary`: gs_boundary.
-int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary)
+// The parameter map's variant for GsStepArgs::fast = `fast`: .op (3) where the side weights are 0.5 and dt == 1 in the
+// strict flavour, else the general one.
+static int tb_map_fast(int fast) { return !GS_MATH_FUSED && (fast & 3) == 3 ? 3 : 0; }
+
+int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, bool map)
 {
     if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4)) return 0;
     const int per = rule_set(boundary);
-    const void *fn = tb_entry(k, tb_reduce_fast(fast, k, cpl, 4, per), cpl, 4, per);
+    const void *fn = map ? GS_SUFFIX(gs_tb_map_kernel)(k, tb_map_fast(fast), cpl, per)
+                         : tb_entry(k, tb_reduce_fast(fast, k, cpl, 4, per), cpl, 4, per);
     return fn ? 1024 * tb_waves_of(fn) : 0;
 }
 
-hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name)
+hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map_planes)
 {
     // "cN": N columns per lane (4 = the wide layout); ".op": the variant specialised for the
     // default (Oono-Puri) side weights, with or without dt == 1
@@ -465,6 +508,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
 #define GS_TB16_LAYOUTS(B, R) {GS_TB_VARIANTS(B "c1f", R), GS_TB_VARIANTS(B "c2f", R)}
     static const char *const names[3][3][4][4] = GS_RULES(GS_TB_LAYOUTS, "tb-k");    // [rule][cpl 1, 2, 4][variant][k - 1]
     static const char *const names16[3][2][4] = GS_RULES(GS_TB16_LAYOUTS, "tb-k4");  // [rule][cpl 1, 2][variant]
+    static const char *const names_map[3][3][4][4] = GS_RULES_MAP(GS_TB_LAYOUTS, "tb-k"); // the parameter map's kernels (gs_step_tb_mk)
 #undef GS_TB16_LAYOUTS
 #undef GS_TB_VARIANTS
 #undef GS_TB_LAYOUTS
@@ -478,14 +522,17 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // the periodic and zero-flux rules run kernels of their own (gs_step_tb_pk / _nk and kin), named with a "/periodic" /
     // "/neumann" suffix
     const int per = rule_set(a.zero_halo);
-    const int fast = tb_reduce_fast(a.fast, k, cpl, 4, per);
-    if (name) *name = names[per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
+    // the parameter map (map_planes): its own kernels, the general or the .op variant, 4-wave workgroups only
+    const bool map = map_planes != nullptr;
+    if (map && (!map_planes->feed || !map_planes->fpk)) return hipErrorInvalidValue;
+    const int fast = map ? tb_map_fast(a.fast) : tb_reduce_fast(a.fast, k, cpl, 4, per);
+    if (name) *name = (map ? names_map : names)[per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
     const long rpu = a.rows_per_unit;
     const long rows_a = (long)a.ra1 - a.ra0;
     const long W = tb_cols_per_wave(k, cpl);
     const long strips = (a.cols + W - 1) / W;
     // Kernel entry first: the taper below needs its occupancy.
-    const void *fn = tb_entry(k, fast, cpl, 4, per);
+    const void *fn = map ? GS_SUFFIX(gs_tb_map_kernel)(k, fast, cpl, per) : tb_entry(k, fast, cpl, 4, per);
     if (!fn) return hipErrorInvalidValue;
     const int waves = tb_waves_of(fn);
     // Tapered tail (consecutive passes are dependent launches that cannot overlap, so the drain phase
@@ -567,7 +614,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // 2 columns per lane, 10 rows 523 k / 537 k, 15 rows 615 k / 633 k, 19 rows 687 k / 738 k, 38 rows 782 k / 865 k.
     // GS_HIP_FAIR = 0 / 1 forces it off / on.
     static const int fair_env = gs_env_int("GS_HIP_FAIR", -1, 0, 1);
-    const bool fair = a.allow_fair && units <= 4096 && units > 1024 && (fair_env < 0 ? (cpl == 2 || rpu >= 20) : fair_env != 0);
+    const bool fair = !map && a.allow_fair && units <= 4096 && units > 1024 && (fair_env < 0 ? (cpl == 2 || rpu >= 20) : fair_env != 0);
     const int fast16 = fair ? tb_reduce_fast(a.fast, k, cpl, 16, per) : 0;
     const void *fair_fn = fair ? tb_entry(k, fast16, cpl, 16, per) : nullptr;
     static const int fair_from_env = gs_env_int("GS_HIP_FAIR_FROM", -1, 0, 256);
@@ -591,6 +638,11 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     args.xcd_m = xcd_env >= 0 ? xcd_env : (units >= 2 * slots ? 16 : 0);
     // the edge units at the head of the dispatch order stay dealt over all XCDs (they are the slow ones)
     args.xcd_first = (int32_t)(((chunks * ne * (args.edge_split == 2 ? 2 : 1) + 3) / 4 + 7) / 8 * 8);
+    if (map) {
+        GsMapPlanes mp = *map_planes;
+        void *margs[] = {&args, &mp};
+        return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), margs, 0, s);
+    }
     return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, 0, s);
 }
 
@@ -609,16 +661,40 @@ hipError_t GS_SUFFIX(gs_launch_lds)(const GsStepArgs &a, hipStream_t s, const ch
     return hipLaunchKernel(reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_lds_k)), dim3((unsigned)blocks),
                            dim3(256), kargs, 0, s);
 }
-#endif // !GS_TB_OP_ONLY
 
-#if defined(GS_WIN_TRACE) && !GS_TB_OP_ONLY
+// F + K of the parameter map (gs_ctx_set_param_map): compute/naive/src/lib.rs:77's `feed_rate + kill_rate`, one f32 add
+// per cell in this translation unit's float mode -- strict: a sub-normal sum is flushed (the DenormalsFlusher); fused:
+// kept.  (Named without the flavour suffix: it is no step kernel, and tests/test_isa_guard.py holds those to their size.)
+#if GS_MATH_FUSED
+#define GS_MAP_RATES_K gs_map_rates_keep_k
+#else
+#define GS_MAP_RATES_K gs_map_rates_flush_k
+#endif
+namespace {
+__global__ __launch_bounds__(256) void GS_MAP_RATES_K(const float *feed, const float *kill, float *fpk, size_t n)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        fpk[i] = feed[i] + kill[i];
+}
+} // namespace
+hipError_t GS_SUFFIX(gs_launch_map_rates)(const float *feed, const float *kill, float *fpk, size_t n, hipStream_t s)
+{
+    if (n == 0) return hipSuccess;
+    const size_t blocks = (n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536;
+    GS_MAP_RATES_K<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(feed, kill, fpk, n);
+    return hipGetLastError();
+}
+#undef GS_MAP_RATES_K
+#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
+
+#if defined(GS_WIN_TRACE) && !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
 extern "C" int32_t GS_SUFFIX(gs_debug_win_trace_read)(unsigned long long *dst)
 {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(gs_win_trace), sizeof(unsigned long long) * 1024 * 8 * 8) == hipSuccess ? 0 : -1;
 }
 #endif
 
-#if defined(GS_TB_TRACE)
+#if defined(GS_TB_TRACE) && !GS_TB_MAP_ONLY
 // Copies the trace buffer of THIS translation unit's kernels out (diagnostic builds only).
 #if GS_TB_OP_ONLY
 extern "C" int32_t gs_debug_trace_read_op(unsigned long long *dst, int32_t units, int32_t clear)
@@ -689,5 +765,31 @@ static const void *tb_op_kernel(int k, int fast, int cpl, int wg)
 const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule)
 {
     return rule == 1 ? tb_op_kernel<1>(k, fast, cpl, wg) : (rule == 2 ? tb_op_kernel<2>(k, fast, cpl, wg) : tb_op_kernel<0>(k, fast, cpl, wg));
+}
+#endif
+
+#if GS_TB_MAP_ONLY
+// Kernel entry of the marching kernel's parameter-map form (gs_kernels.h: gs_tb_map_kernel_*): K = 1..4 fused steps,
+// `fast` 0 (general) or 3 (.op: side weights 0.5, dt == 1; strict only), 1, 2 or 4 columns per lane, `rule` the kernel set
+// of the boundary rule (rule_set).
+const void *GS_SUFFIX(gs_tb_map_kernel)(int k, int fast, int cpl, int rule)
+{
+#define GS_MAP_KS(F, C, R) {GS_FN(gs_step_tb_mk, 1, F, C, R), GS_FN(gs_step_tb_mk, 2, F, C, R), GS_FN(gs_step_tb_mk, 3, F, C, R), GS_FN(gs_step_tb_mk, 4, F, C, R)}
+#define GS_MAP_CPLS(F, R) {GS_MAP_KS(F, 1, R), GS_MAP_KS(F, 2, R), GS_MAP_KS(F, 4, R)}
+#define GS_MAP_RULES(F) {GS_MAP_CPLS(F, 0), GS_MAP_CPLS(F, 1), GS_MAP_CPLS(F, 2)}
+    static const void *const general[3][3][4] = GS_MAP_RULES(0); // [rule][cpl 1, 2, 4][k - 1]
+#if !GS_MATH_FUSED
+    static const void *const op[3][3][4] = GS_MAP_RULES(3);
+#endif
+#undef GS_MAP_RULES
+#undef GS_MAP_CPLS
+#undef GS_MAP_KS
+    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || rule < 0 || rule > 2) return nullptr;
+    const int c = cpl == 4 ? 2 : cpl - 1;
+    if (fast == 0) return general[rule][c][k - 1];
+#if !GS_MATH_FUSED
+    if (fast == 3) return op[rule][c][k - 1];
+#endif
+    return nullptr;
 }
 #endif

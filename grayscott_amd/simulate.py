@@ -12,10 +12,19 @@ Output: the reference writes an HDF5 dataset ``matrix[nbimage, rows, cols]`` f32
 (data/src/hdf5.rs:36-63).  ``-o name.h5`` (or ``.hdf5``) writes that dataset through the minimal
 HDF5 writer of ``grayscott_amd/hdf5_min.py`` (libhdf5 / h5py are not in this image: see the status
 note there); any other name gives a ``.npy`` file (numpy format 1.0, C order) with the same array.
+
+Parameter maps (``gs_ctx_set_param_map``): ``--hip-feed-map F0:F1`` makes F vary linearly along the rows,
+``--hip-kill-map K0:K1`` makes k vary linearly along the columns (Munafo's (F, k) map), ``--hip-param-map FILE.npz``
+takes arrays ``feed`` and ``kill`` of the grid's shape.  The linear value of index i out of n is
+``np.float32(a + (b - a) * i / (n - 1))`` computed in float64, a single row or column taking ``a``; a rate without a
+map option is the uniform ``-f`` / ``-k`` value.  The output keeps the reference's format; the map's definition goes
+into a JSON sidecar, ``-o``'s name with ``.param_map.json``.
 """
 from __future__ import annotations
 
 import argparse
+import json
+import os
 import queue
 import sys
 import threading
@@ -39,6 +48,7 @@ def parse(argv=None):
     ap.add_argument("-o", "--output", default="output.h5")               # main.rs:33-35, ui/src/lib.rs:72-75
     ap.add_argument("--output-buffer", type=int, default=2)              # main.rs:37-43
     add_backend_args(ap)
+    add_param_map_args(ap)
     return ap.parse_args(argv)
 
 
@@ -64,6 +74,69 @@ def add_backend_args(ap: argparse.ArgumentParser) -> None:
     be.add_argument("--hip-use-graph", type=int, default=None, help="1 = replay batches of 16 passes through a hipGraph [GS_HIP_USE_GRAPH]")
     be.add_argument("--hip-tile-shape", type=int, default=None, help="window of the LDS-window kernel: 1 = 32x64, 2 = 16x64, 3 = 64x64 [GS_HIP_TILE_SHAPE]")
     be.add_argument("--hip-pitch-pad", type=int, default=None, help="extra f32 of row pitch [GS_HIP_PITCH_PAD]")
+
+
+def add_param_map_args(ap: argparse.ArgumentParser) -> None:
+    """The parameter map's options of the ``--hip-*`` group (simulate only)."""
+    pm = ap.add_argument_group("HIP backend: parameter map")
+    pm.add_argument("--hip-feed-map", default=None, metavar="F0:F1", help="feed rate varying linearly along the rows, F0 on the first, F1 on the last")
+    pm.add_argument("--hip-kill-map", default=None, metavar="K0:K1", help="kill rate varying linearly along the columns, K0 on the first, K1 on the last")
+    pm.add_argument("--hip-param-map", default=None, metavar="FILE.npz", help="arrays `feed` and `kill` of the grid's shape")
+
+
+def linear_values(a: float, b: float, n: int) -> np.ndarray:
+    """The linear map's values: ``np.float32(a + (b - a) * i / (n - 1))`` in float64 for i = 0 .. n - 1; n == 1 gives a."""
+    if n == 1:
+        return np.array([a], np.float32)
+    i = np.arange(n, dtype=np.float64)
+    return (float(a) + (float(b) - float(a)) * i / (n - 1)).astype(np.float32)
+
+
+def _range(text: str, flag: str):
+    try:
+        a, b = (float(x) for x in text.split(":"))
+    except ValueError:
+        raise ValueError(f"{flag} wants FROM:TO, got {text!r}") from None
+    return a, b
+
+
+def param_map(args, shape, params: Parameters):
+    """(feed, kill, definition) of the parameter map the options ask for, or None.  ``feed`` / ``kill``: float32
+    [rows, cols] arrays or scalars (uniform planes); ``definition``: what the JSON sidecar records."""
+    feed_map, kill_map, path = (getattr(args, n, None) for n in ("hip_feed_map", "hip_kill_map", "hip_param_map"))
+    if feed_map is None and kill_map is None and path is None:
+        return None
+    rows, cols = shape
+    if path is not None:
+        if feed_map is not None or kill_map is not None:
+            raise ValueError("--hip-param-map excludes --hip-feed-map and --hip-kill-map")
+        with np.load(path) as z:
+            feed, kill = (np.asarray(z[n], np.float32) for n in ("feed", "kill"))
+        for name, a in (("feed", feed), ("kill", kill)):
+            if a.shape != (rows, cols):
+                raise ValueError(f"{path}: `{name}` is {a.shape}, the grid is {(rows, cols)}")
+        return feed, kill, {"shape": [rows, cols], "file": os.path.abspath(path)}
+    definition = {"shape": [rows, cols], "formula": "float32(a + (b - a) * i / (n - 1)), float64 arithmetic"}
+    if feed_map is not None:
+        a, b = _range(feed_map, "--hip-feed-map")
+        feed = np.repeat(linear_values(a, b, rows)[:, None], cols, axis=1)
+        definition["feed"] = {"along": "rows", "from": a, "to": b}
+    else:
+        feed = np.float32(params.feed_rate)
+        definition["feed"] = {"value": float(params.feed_rate)}
+    if kill_map is not None:
+        a, b = _range(kill_map, "--hip-kill-map")
+        kill = np.repeat(linear_values(a, b, cols)[None, :], rows, axis=0)
+        definition["kill"] = {"along": "columns", "from": a, "to": b}
+    else:
+        kill = np.float32(params.kill_rate)
+        definition["kill"] = {"value": float(params.kill_rate)}
+    return feed, kill, definition
+
+
+def sidecar_path(output: str) -> str:
+    """The parameter map's JSON sidecar next to the output file."""
+    return os.path.splitext(output)[0] + ".param_map.json"
 
 
 def backend_args(args) -> HipArgs:
@@ -97,9 +170,16 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     shape = (args.nbrow, args.nbcol)
     if args.output_buffer < 1:
         raise ValueError("--output-buffer must be at least 1")
-    sim = Simulation.new(simulation_parameters(args), hip_args if hip_args is not None else backend_args(args))
+    params = simulation_parameters(args)
+    pmap = param_map(args, shape, params)
+    sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)
     ctx = sim.context
+    if pmap is not None:
+        sim.set_param_map(pmap[0], pmap[1], shape=shape)
+        if getattr(args, "rank", 0) == 0:
+            with open(sidecar_path(args.output), "w") as f:
+                json.dump(pmap[2], f, indent=1)
     if out is None and args.output.lower().endswith((".h5", ".hdf5")):
         out = hdf5_min.create(args.output, (args.nbimage,) + shape)       # dataset "matrix" (hdf5.rs:24)
     elif out is None:

@@ -645,6 +645,41 @@ class Simulation:
             species.u._pair.reverse()
             species.v._pair.reverse()
 
+    def set_param_map(self, feed, kill, shape: Optional[Sequence[int]] = None) -> None:
+        """Attach a parameter map (``gs_ctx_set_param_map``): from now on every step takes feed = ``feed[r, c]`` and
+        kill = ``kill[r, c]`` at cell (r, c) instead of ``params.feed`` / ``params.kill``.  ``feed`` and ``kill`` are
+        global ``[rows, cols]`` arrays or scalars (a scalar is a uniform plane; ``shape`` is needed when both are);
+        each process uploads only its own rows.  The library copies them (F + K is formed on the device in the
+        context's float mode), so the arrays may change afterwards; a new call replaces the map.  Collective in a
+        multi-process run.  The species stepped while it is attached must have its shape."""
+        if shape is None:
+            arrays = [np.shape(x) for x in (feed, kill) if np.ndim(x) != 0]
+            if not arrays:
+                raise ValueError("a parameter map of two scalars needs its shape")
+            shape = arrays[0]
+        rows, cols = int(shape[0]), int(shape[1])
+        planes = []
+        try:
+            for value in (feed, kill):
+                c = HipConcentration(self.context, (rows, cols))
+                planes.append(c)
+                r0, r1 = c.local_rows()
+                if np.ndim(value) == 0:
+                    capi.check(self.context._lib.gs_field_fill(self.context.handle, c.handle, float(value)))
+                else:
+                    a = np.asarray(value, np.float32)
+                    if a.shape != (rows, cols):
+                        raise ValueError(f"parameter map of shape {a.shape}, species of {(rows, cols)}")
+                    c.upload(self.context, a[r0:r1])
+            capi.check(self.context._lib.gs_ctx_set_param_map(self.context.handle, planes[0].handle, planes[1].handle))
+        finally:
+            for c in planes:
+                c.destroy()
+
+    def clear_param_map(self) -> None:
+        """Detach the parameter map: the steps take ``params.feed`` / ``params.kill`` again."""
+        capi.check(self.context._lib.gs_ctx_set_param_map(self.context.handle, None, None))
+
     def perform_step(self, species: Species) -> None:
         """One ``gs_step`` then ``species.flip()`` -- the ``SimulateStep`` form (cpu.rs:21-42)."""
         in_u, in_v, out_u, out_v = species.in_out()

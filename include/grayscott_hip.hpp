@@ -406,6 +406,19 @@ class Simulation {
                       species.v().out().raw()));
         species.flip();
     }
+    // Parameter map (gs_ctx_set_param_map): feed and kill of every cell, dense row-major [rows, cols] arrays of the GLOBAL
+    // grid (each process uploads its own rows); the library copies them.  clear_param_map() detaches it.
+    void set_param_map(Shape shape, const float *feed, const float *kill) const
+    {
+        Context c = context_;
+        HipConcentration f = HipConcentration::zeros(c, shape), k = HipConcentration::zeros(c, shape);
+        uint64_t r0 = 0, r1 = 0;
+        check(gs_field_local_rows(f.raw(), &r0, &r1));
+        check(gs_field_upload(context_->get(), f.raw(), feed + r0 * shape[1]));
+        check(gs_field_upload(context_->get(), k.raw(), kill + r0 * shape[1]));
+        check(gs_ctx_set_param_map(context_->get(), f.raw(), k.raw()));
+    }
+    void clear_param_map() const { check(gs_ctx_set_param_map(context_->get(), nullptr, nullptr)); }
     const Context &context() const { return context_; }
     // an Ensemble of params.size() members (Species::new's pattern in each)
     Ensemble make_ensemble(Shape shape, const std::vector<Parameters> &params) const

@@ -248,6 +248,24 @@ int32_t gs_ctx_create(gs_ctx **out, const gs_params *params, const gs_options *o
 int32_t gs_ctx_destroy(gs_ctx *ctx);
 int32_t gs_ctx_set_params(gs_ctx *ctx, const gs_params *params);
 
+/* Parameter map: feed and kill rates that vary from cell to cell on one grid (Munafo's (F, k) map, feed masks, gradients).
+ * While a map is attached, every step of gs_step / gs_run is the reference step with feed = F[r, c] and kill = K[r, c]
+ * for cell (r, c); du, dv, dt and the weights still come from gs_params, whose feed and kill are ignored.  F + K is one
+ * f32 add per cell in the context's float mode (GS_MATH_STRICT flushes a sub-normal sum), and the arithmetic contract of
+ * gs_math is unchanged.  Under the periodic rule a cell computed at a wrapped position takes the map at that position.
+ *   feed, kill : ordinary fields of this context with the species' global shape, created and uploaded the usual way (in a
+ *                multi-process run each process uploads its own rows).  The call COPIES them into two planes the library
+ *                owns (F, and F + K formed on the device) and fills their ghost rows once: the caller may change or
+ *                destroy its fields afterwards.  feed == kill == NULL detaches the map.
+ * The call waits for enqueued work; in a multi-process run it is collective.  gs_step / gs_run on species of another
+ * shape than the map's: GS_ERR_INVALID.  A context whose pinned kernel has no map form (GS_KERNEL_WINDOW, _LDS, _TILE):
+ * GS_ERR_UNSUPPORTED.  With a map, gs_run runs the marching kernel at every grid size (never the resident, tile or window
+ * kernel) and gs_step the streaming one; their map forms carry a "/map" suffix in gs_ctx_info (e.g.
+ * "tb-k4c2/strict.op/map", "tb-k4c2/strict/periodic/map").  Graph replay and the on-line tuner keep mapped and uniform
+ * runs apart: gs_ctx_get_tuned / gs_ctx_set_tuned act on the choices of the kernel set in force.  Ensembles keep their
+ * own per-member parameters and ignore the map. */
+int32_t gs_ctx_set_param_map(gs_ctx *ctx, gs_field *feed, gs_field *kill);
+
 /* Concentration::default / zeros / ones (concentration/mod.rs:205-218) = create (+ fill).
  * `rows`, `cols` are the GLOBAL shape; every process passes the same values. */
 int32_t gs_field_create(gs_ctx *ctx, gs_field **out, uint64_t rows, uint64_t cols);
