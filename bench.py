@@ -1,15 +1,21 @@
 #!/usr/bin/env python3
 """Benchmark of the Gray-Scott step path on MI355X (contract: see the task statement).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling weak|strong] [--grid RxC] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--scaling weak|strong] [--grid RxC] [--dump-outputs DIR]
 
 One "step" = one simulation time step of the whole grid (the reference's own throughput
 unit is cells x steps, compute/shared/src/benchmark.rs:55-59; its "compute" workload is
 perform_steps only, :77-83).  Inputs are resident in HBM before the timed region starts.
 
+A plain run does what `value` needs: the set-up (on one GPU the developed pattern's 4000 steps tune the context), the
+timed regions, --dump-outputs, the line.  --full adds every other leg: on one GPU the developed-pattern co-headline, the
+same launches on unplaced planes, clock / power / energy samples, the replay that verifies the timed planes (with the
+single-step HBM leg in it) and the CPU baseline; on N > 1 the per-rank report, the whole-grid check and the peer chain.
+Only a --full run can fail its replay (exit code 3).
+
 N = 1 : BASELINE.json's headline workload, 16384 x 16384 f32 (config 3), Species::new init,
-        default feed/kill.  Rank 0 also times the same kernel on a developed spot pattern, the
-        fused-tap flavour, and the CPU ports on the host cores on a bounded sample.
+        default feed/kill.  With --full rank 0 also times the same kernel on a developed spot pattern and
+        the CPU ports on the host cores on a bounded sample; --extra adds the fused-tap flavour.
 N > 1 : one process per GPU (torchrun; `python bench.py --gpus N` without WORLD_SIZE starts that torchrun
         itself, as a CHILD process, before anything touches a GPU), row slabs with ghost-row exchange
         through RCCL send/recv inside libgs_hip.so.  Every rank runs a watchdog: a stage that exceeds its
@@ -60,11 +66,15 @@ def parse_args():
     ap.add_argument("--cols", type=int, default=0)
     ap.add_argument("--repeats", type=int, default=5,
                     help="timed regions of --steps steps each, back to back; `value` is their median")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the timed regions (see the module's docstring); a plain run times the "
+                         "headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--extra", action="store_true",
                     help="N = 1: also the fused-tap flavour and the single-step kernel on two more sets of planes")
     ap.add_argument("--no-extra", action="store_true",
-                    help="N = 1: skip the developed-pattern co-headline and the clock / power / energy samples")
+                    help="N = 1: no developed pattern (the timed Species then tunes the context), hence no developed-pattern "
+                         "co-headline and no clock / power / energy samples under --full")
     ap.add_argument("--no-verify", action="store_true",
                     help="skip the replay that compares the timed planes with an independent run (and, on one GPU, "
                          "the single-step HBM leg that is part of it)")
@@ -90,7 +100,8 @@ def parse_args():
                          "mean nothing")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="N = 1: after the timed regions, write the U and V planes the timed Species holds (and, unless "
-                         "--no-extra, those of the developed pattern after its timed regions) as DIR/<name>.npy, float32; "
+                         "--no-extra, those of the developed pattern after the steps of its timed regions, which a plain "
+                         "run takes untimed) as DIR/<name>.npy, float32; "
                          "grids above the size budget are written as a fixed, seeded sample of cells (DIR/index.npy: "
                          "their row-major indices)")
     return ap.parse_args()
@@ -211,8 +222,8 @@ def main() -> int:
     cells = rows * cols
     cells_per_gpu = cells / world
     single = world == 1
-    with_extra = single and not args.no_extra
-    verify = not args.no_verify
+    with_extra = single and not args.no_extra       # the developed pattern: it tunes the context in every run
+    verify = args.full and not args.no_verify
 
     # ---- N > 1: the process group, rank 0's RCCL unique id, ncclCommInitRank inside gs_ctx_create ----------------
     with stage("init", 300):
@@ -370,7 +381,7 @@ def main() -> int:
                 dumped["files"].append("index.npy")
 
     per_rank, rccl_ranks = [], None
-    if world > 1:
+    if world > 1 and args.full:
         with stage("per-rank", 600):
             per_rank, rccl_ranks = per_rank_report(sim, species, args.steps, timed_run, world, local_rank, red_dev)
 
@@ -388,26 +399,33 @@ def main() -> int:
         return roofline_object(ms, n_passes, steps_per_launch, cells_per_gpu, pmc_d, insts_d, how_d, kernel_name)
 
     roofline = roofline_of(event_ms, passes)
-    fused, developed, clocks, clocks_dev = None, None, None, None
-    if with_extra:
+    fused, developed, clocks, clocks_dev, unplaced = None, None, None, None, None
+    if with_extra and (args.full or dumped is not None):
         with stage("developed", 900):
-            # co-headline: the same kernel, same context, same launches on a developed spot pattern (the chip
-            # sustains a lower clock on non-trivial operands; BASELINE.md asks for "random/real data not zeros")
+            # co-headline (--full): the same kernel, same context, same launches on a developed spot pattern (the chip
+            # sustains a lower clock on non-trivial operands; BASELINE.md asks for "random/real data not zeros").  A plain
+            # run that dumps takes the same steps untimed, so that it writes the planes a --full run writes.
             run(sp_dev, args.warmup)
             warm(sp_dev)
-            runs_dev = repeated(sp_dev, args.steps, args.repeats)
+            if args.full:
+                runs_dev = repeated(sp_dev, args.steps, args.repeats)
+            else:
+                for _ in range(args.repeats):
+                    run(sp_dev, args.steps)
             if dumped is not None:
                 dumped["developed_steps"] = sp_dev.steps_done
                 dumped["files"] += dump_planes(args.dump_outputs, "developed_", sp_dev, ctx, dump_idx)
-            w_dev, ms_dev, p_dev = median_run(runs_dev)
-            developed = {"value": cells * args.steps / w_dev / 1e6,
-                         "value_min": cells * args.steps / max(r[0] for r in runs_dev) / 1e6,
-                         "value_max": cells * args.steps / min(r[0] for r in runs_dev) / 1e6,
-                         "repeats": len(runs_dev),
-                         "roofline": {k: v for k, v in roofline_of(ms_dev, p_dev, "developed").items()
-                                      if k in ("bound", "achieved", "peak", "unit", "frac", "frac_source", "valu", "valu_source", "useful_valu",
-                                               "hbm_physical", "traffic", "algorithmic_GBps", "launch_ms", "counters_source")}}
-        unplaced = None
+            if args.full:
+                w_dev, ms_dev, p_dev = median_run(runs_dev)
+                developed = {"value": cells * args.steps / w_dev / 1e6,
+                             "value_min": cells * args.steps / max(r[0] for r in runs_dev) / 1e6,
+                             "value_max": cells * args.steps / min(r[0] for r in runs_dev) / 1e6,
+                             "repeats": len(runs_dev),
+                             "roofline": {k: v for k, v in roofline_of(ms_dev, p_dev, "developed").items()
+                                          if k in ("bound", "achieved", "peak", "unit", "frac", "frac_source", "valu", "valu_source",
+                                                   "useful_valu", "hbm_physical", "traffic", "algorithmic_GBps", "launch_ms",
+                                                   "counters_source")}}
+    if with_extra and args.full:
         if getattr(species, "placement", None):
             with stage("unplaced", 600):
                 # the same launches on a Species::new whose planes lie where hipMalloc put them (placement switched off)
@@ -441,7 +459,7 @@ def main() -> int:
                     verified = verify_slab_chain(sim, species, rows, cols, rank, world, local_rank, args.rehearsal)
             except Exception as e:                      # the line is still worth printing
                 verified = {"error": f"{type(e).__name__}: {e}"}
-    if world > 1 and not args.no_peer_chain:
+    if world > 1 and args.full and not args.no_peer_chain:
         # the other ranks wait at the barrier (their GPUs idle but for rank 0's slabs)
         with stage("peer-chain", 900):
             if rank == 0:
@@ -539,7 +557,7 @@ def main() -> int:
         result["dump_outputs"] = dumped
     if ctx.stats().get("window_fallbacks"):
         result["window_fallbacks"] = ctx.stats()["window_fallbacks"]     # a timing that contains one measured a stall
-    if rank == 0 and single and not args.no_cpu_baseline:
+    if rank == 0 and single and args.full and not args.no_cpu_baseline:
         with stage("cpu_baseline", 600):
             result["cpu_baseline"] = cpu_baseline()
     result["stage_seconds"] = stage_s

@@ -71,3 +71,10 @@ def test_dump_outputs_is_refused_for_several_gpus():
     r = _python("import sys, bench\nsys.argv = ['bench.py', '--gpus', '2', '--dump-outputs', 'out']\nsys.exit(bench.main())\n")
     assert r.returncode == 2 and "--dump-outputs" in r.stderr, (r.returncode, r.stderr)
     assert not os.path.exists(os.path.join(ROOT, "out"))
+
+
+def test_full_is_off_by_default():
+    """A plain run times the headline only; every other leg waits for --full."""
+    r = _python("import sys, bench\nsys.argv = ['bench.py', '--gpus', '1', '--steps', '4', '--warmup', '0']\n"
+                "print(bench.parse_args().full)\nsys.argv.append('--full')\nprint(bench.parse_args().full)\n")
+    assert r.returncode == 0 and r.stdout.split() == ["False", "True"], (r.returncode, r.stdout, r.stderr)

@@ -3,7 +3,8 @@ the shared-memory transport double instead of librccl, torch.distributed runs on
 might start it: `python bench.py --gpus N` with no torchrun around it.
 
 * the launcher path: the parent starts torchrun as a child and relays the one JSON line;
-* the line's `verified` object: rank 0 replays the whole grid alone and the ranks' row-block checksums match;
+* with --full, the line's `verified` object: rank 0 replays the whole grid alone and the ranks' row-block checksums
+  match;
 * a forced stall of one rank inside the timed stage: the watchdog prints an error line and the job exits non-zero
   (instead of hanging until the driver's limit).
 
@@ -32,7 +33,7 @@ def _bench(args, env=None, timeout=900):
 def test_gpus_2_rehearsal_without_torchrun_prints_a_verified_line(built):
     # (--place-candidates 3: every rank places its slab's planes by measurement, as the full-size run does)
     r = _bench(["--gpus", "2", "--rehearsal", "--steps", "24", "--warmup", "5", "--repeats", "3", "--grid", "4096x2048",
-                "--place-candidates", "3"])
+                "--place-candidates", "3", "--full"])
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["rccl_ranks"] == 2 and len(line["ranks"]) == 2

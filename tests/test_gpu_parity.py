@@ -927,7 +927,7 @@ def test_slab_chain_never_refreshes_between_runs():
 
 
 def test_pass_timing_reports_halo_and_interior_times():
-    """gs_ctx_set_pass_timing / gs_ctx_stats on a slab chain: what bench.py prints per rank for N > 1."""
+    """gs_ctx_set_pass_timing / gs_ctx_stats on a slab chain: what bench.py --full prints per rank for N > 1."""
     sim = Simulation.new(Parameters(), args(devices=[0, 0]))
     sp = sim.make_species([4096, 2048])
     sim.perform_steps(sp, 40)

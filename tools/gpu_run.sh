@@ -8,7 +8,7 @@
 #   smoke           __graft_entry__.build() + smoke(), as the driver runs them
 #   newtests        this round's new GPU tests first (fast failure)
 #   tests           the whole GPU suite
-#   bench           bench.py as the driver runs it (--steps 20 --warmup 5) and with its defaults
+#   bench           a plain bench.py run (--steps 20 --warmup 5), then a --full one at the default steps
 #   timeline:RxC[:key=value,...]   tools/wave_timeline.py on the diagnostic build (variants/libgs_hip_trace.so)
 #   sweep:RxC:STEPS:VARIANT;VARIANT...   tools/sweep.py (VARIANT = key=value,key=value)
 #   libsweep:NAME:RxC:STEPS:VARIANT;...  the same against grayscott_amd/variants/libgs_hip_NAME.so
@@ -51,7 +51,7 @@ for stage in "$@"; do
       timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_driver_style.json" 2> "$OUT/bench_driver_style.err"; rc=$?
       tail -c 3000 "$OUT/bench_driver_style.json"; tail -3 "$OUT/bench_driver_style.err"
       if [ $rc -eq 0 ]; then
-        timeout -k 10 600 python bench.py > "$OUT/bench_unprofiled.json" 2> "$OUT/bench_unprofiled.err"; rc=$?
+        timeout -k 10 600 python bench.py --full > "$OUT/bench_unprofiled.json" 2> "$OUT/bench_unprofiled.err"; rc=$?
         tail -c 3000 "$OUT/bench_unprofiled.json"
       fi ;;
     timeline)

@@ -17,7 +17,7 @@ for mode in "2 weak" "4 weak" "2 strong" "4 strong"; do
   set -- $mode
   port=$((port + 1))
   timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$1" --master-addr 127.0.0.1 --master-port $port \
-      bench.py --gpus "$1" --steps "$STEPS" --warmup 12 --scaling "$2" --rehearsal > "$OUT/bench_n$1_$2.json" 2> "$OUT/bench_n$1_$2.log" \
+      bench.py --gpus "$1" --steps "$STEPS" --warmup 12 --scaling "$2" --rehearsal --full > "$OUT/bench_n$1_$2.json" 2> "$OUT/bench_n$1_$2.log" \
       || { tail -20 "$OUT/bench_n$1_$2.log"; exit 1; }
   tail -1 "$OUT/bench_n$1_$2.json"
 done
