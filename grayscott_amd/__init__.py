@@ -16,8 +16,9 @@ from .simulation import (  # noqa: F401
     Parameters,
     Simulation,
     Species,
+    Summary,
     pinned_empty,
 )
 
 __all__ = ["capi", "GsError", "Ensemble", "Evolving", "HipArgs", "HipConcentration", "HipContext",
-           "Parameters", "Simulation", "Species", "pinned_empty"]
+           "Parameters", "Simulation", "Species", "Summary", "pinned_empty"]

@@ -43,6 +43,8 @@ UNITS = [
     ("gs_step_kernels.hip", "gs_step_strict_map.o", STRICT + ["-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
     ("gs_step_kernels.hip", "gs_step_fused_map.o", ["-DGS_MATH_FUSED=1", "-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
     ("gs_util_kernels.hip", "gs_util.o", []),
+    # summaries of planes (row records, the ensembles' fold): hipcc's default float mode, sub-normal cells kept
+    ("gs_summary.hip", "gs_summary_k.o", []),
     # the host side (contexts and schedule, planes, kernel configuration, the window kernel's runtime, RCCL): only the
     # C ABI of include/gs_hip.h is visible outside the library
     ("gs_api.cpp", "gs_api.o", ["-x", "hip", "-fvisibility=hidden"]),
@@ -52,6 +54,7 @@ UNITS = [
     ("gs_rccl.cpp", "gs_rccl.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_ensemble.cpp", "gs_ensemble.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_param_map.cpp", "gs_param_map.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_summary.cpp", "gs_summary.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

@@ -44,6 +44,7 @@ EXPORTS = (
     "gs_ensemble_create", "gs_ensemble_destroy", "gs_ensemble_shape", "gs_ensemble_set_params", "gs_ensemble_seed",
     "gs_ensemble_upload", "gs_ensemble_download", "gs_ensemble_run",
     "gs_ctx_set_param_map",
+    "gs_fields_summarize", "gs_members_summarize",
 )
 
 
@@ -102,6 +103,19 @@ class GsStats(ctypes.Structure):
         ("halo_exposed_ms", ctypes.c_float),
         ("reserved", ctypes.c_float),
         ("window_fallbacks", ctypes.c_uint64),
+    ]
+
+
+class GsSummary(ctypes.Structure):
+    """``gs_summary`` (include/gs_hip.h): one plane's sum, sum of squares, min and max of its finite cells, and its
+    count of non-finite cells -- 32 bytes."""
+
+    _fields_ = [
+        ("sum", ctypes.c_double),
+        ("sum_sq", ctypes.c_double),
+        ("min", ctypes.c_float),
+        ("max", ctypes.c_float),
+        ("nonfinite", ctypes.c_uint64),
     ]
 
 
@@ -175,6 +189,8 @@ def load() -> ctypes.CDLL:
         "gs_ensemble_upload": (i32, [vp, vp, u64, u64, vp, vp]),
         "gs_ensemble_download": (i32, [vp, vp, u64, u64, i32, vp]),
         "gs_ensemble_run": (i32, [vp, vp, u64]),
+        "gs_fields_summarize": (i32, [vp, P(vp), i32, P(GsSummary)]),
+        "gs_members_summarize": (i32, [vp, vp, u64, u64, P(GsSummary)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -568,6 +568,7 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
 {
     if (!ctx) return GS_OK;
     destroy_param_map(ctx);
+    destroy_summary_buffers(ctx);
     for (auto &sl : ctx->slabs) {
         if (!sl.compute && !sl.halo) continue; // never initialised (creation failed early)
         if (hipSetDevice(sl.device) != hipSuccess) continue;

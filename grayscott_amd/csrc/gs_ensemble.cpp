@@ -6,15 +6,6 @@
 
 using namespace gsi;
 
-struct gs_ensemble {
-    gs_ctx *ctx = nullptr;
-    uint64_t members = 0, rows = 0, cols = 0;
-    float *u[2] = {nullptr, nullptr}, *v[2] = {nullptr, nullptr};
-    GsEnsParams *params = nullptr; // members entries (device)
-    int fast = 0;                  // 3 when every member has side weights 0.5 and dt == 1: the .op kernels
-    int cur = 0;                   // slot that holds the newest state
-};
-
 namespace {
 
 // A member's cells are indexed with 32-bit integers in the kernels (and its windows must fit one launch).

@@ -7,6 +7,7 @@
 //   gs_rccl.cpp    RCCL (loaded on first use), its self-test, gs_runtime_info, gs_last_error
 //   gs_ensemble.cpp ensembles: many grids of one shape, each with its own parameters, advanced in shared launches
 //   gs_param_map.cpp parameter maps: per-cell feed and kill rates on one grid (gs_ctx_set_param_map)
+//   gs_summary.cpp summaries of planes and ensemble members (gs_fields_summarize, gs_members_summarize)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
@@ -105,6 +106,10 @@ struct SlabRt {
     // ghost-row exchange: th0, th1) and around the interior kernel on the compute stream (tc0, tc1)
     std::vector<hipEvent_t> th0, th1, tc0, tc1;
     int timed = 0; // passes recorded since the timing was switched on
+    // summaries (gs_summary.cpp): the row records of this slab's planes -- on slab 0 also what a multi-process summary
+    // exchanges, and an ensemble's records --, grown on demand, freed with the context
+    void *summary = nullptr;
+    size_t summary_bytes = 0;
 };
 
 // The form of difference sharing (share_mode, gs_tuner.cpp) of runs that have not been tuned: across lanes too -- never
@@ -224,6 +229,16 @@ struct FieldSlab {
     int32_t rows = 0;
 };
 
+// An ensemble (gs_ensemble.cpp): dense [members, rows, cols] planes on the context's one slab, two slots per species.
+struct gs_ensemble {
+    gs_ctx *ctx = nullptr;
+    uint64_t members = 0, rows = 0, cols = 0;
+    float *u[2] = {nullptr, nullptr}, *v[2] = {nullptr, nullptr};
+    GsEnsParams *params = nullptr; // members entries (device)
+    int fast = 0;                  // 3 when every member has side weights 0.5 and dt == 1: the .op kernels
+    int cur = 0;                   // slot that holds the newest state
+};
+
 struct gs_field {
     gs_ctx *ctx = nullptr;
     uint64_t rows = 0, cols = 0;
@@ -287,6 +302,13 @@ int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *la
 // gs_param_map.cpp
 int32_t check_map_shape(const gs_ctx *ctx, const gs_field *f);
 void destroy_param_map(gs_ctx *ctx);
+
+// gs_summary.cpp
+void destroy_summary_buffers(gs_ctx *ctx);
+// gs_rccl.cpp: every rank's `bytes[q]` bytes (rank q's share, the same table on every rank) into `all` at the offsets of the
+// table's prefix sums, this rank's own share from `mine`; device buffers on slab 0's device, on `stream`.  Messages of at
+// most 1 MiB, one per peer and direction in each group (real RCCL has no such limits; the tests' transport double does).
+int32_t allgather_bytes(gs_ctx *ctx, const void *mine, void *all, const std::vector<size_t> &bytes, hipStream_t stream);
 
 // ---- gs_run: state of one call -------------------------------------------------------------------------------------
 // ---- gs_run: state of one call, on-line tuning, graph replay ---------------------------------

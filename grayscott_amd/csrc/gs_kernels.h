@@ -190,3 +190,19 @@ hipError_t gs_launch_pair_probe(void *x, void *y, size_t bytes, hipStream_t s);
 // rows [r0, r1) x columns [c0, c1).
 hipError_t gs_launch_ens_seed(float *u, float *v, uint64_t members, int32_t rows, int32_t cols, int32_t r0, int32_t r1,
                               int32_t c0, int32_t c1, hipStream_t s);
+
+// Summaries (gs_summary.hip; include/gs_hip.h: gs_fields_summarize).  One record per (plane, row): the row partial of the
+// fold order in gs_hip.h -- 64 lane accumulators over columns 256 k + 4 l + j, halved down to one -- with the row's
+// minimum, maximum and count of non-finite cells.  32 bytes.
+struct GsRowSummary {
+    double sum, sum_sq;
+    float min, max;
+    uint32_t nonfinite, pad;
+};
+// Records of rows [0, rows) of n (1..4) planes that share a row pitch of `pitch` floats (rows may be 64-bit: the dense
+// [members x rows, cols] layout of an ensemble is one tall plane): out[p * rows + r] for plane p, row r.
+hipError_t gs_launch_row_summary(const float *const *planes, int n, int64_t pitch, int64_t rows, int32_t cols,
+                                 GsRowSummary *out, hipStream_t s);
+// The field fold of gs_hip.h over the records gs_launch_row_summary wrote for the two species of `count` ensemble members
+// of `rows` rows each (rec[s * count * rows + i * rows + r]): out[2 i + s], the rows added one after the other in order.
+hipError_t gs_launch_summary_fold(const GsRowSummary *rec, int64_t count, int64_t rows, GsRowSummary *out, hipStream_t s);

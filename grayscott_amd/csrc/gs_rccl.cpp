@@ -65,6 +65,43 @@ Rccl *rccl()
     return instance;
 }
 
+// All-gather of byte blocks of different sizes (the row records of gs_fields_summarize) with the entry points the ghost-row
+// exchange binds: in round c every rank sends chunk c of its block to every peer and receives chunk c of every peer's,
+// in one group.  Chunks of at most 1 MiB, one message per peer and direction per group.
+int32_t allgather_bytes(gs_ctx *ctx, const void *mine, void *all, const std::vector<size_t> &bytes, hipStream_t stream)
+{
+    constexpr size_t kChunk = size_t(1) << 20;
+    Rccl *R = rccl();
+    if (!R || !ctx->comm) return fail(GS_ERR_RCCL, "RCCL communicator missing");
+    const int world = ctx->world, me = ctx->rank;
+    std::vector<size_t> off((size_t)world + 1, 0);
+    size_t rounds = 0;
+    for (int q = 0; q < world; ++q) {
+        off[q + 1] = off[q] + bytes[q];
+        rounds = std::max(rounds, (bytes[q] + kChunk - 1) / kChunk);
+    }
+    unsigned char *dst = static_cast<unsigned char *>(all);
+    const unsigned char *src = static_cast<const unsigned char *>(mine);
+    if (bytes[me] > 0)
+        GS_HIP(hipMemcpyAsync(dst + off[me], src, bytes[me], hipMemcpyDeviceToDevice, stream));
+    for (size_t c = 0; c < rounds; ++c) {
+        GS_NCCL(R, R->GroupStart());
+        ncclResult_t r = ncclSuccess;
+        for (int q = 0; q < world && r == ncclSuccess; ++q) {
+            if (q == me) continue;
+            const size_t at = c * kChunk;
+            if (at < bytes[me])
+                r = R->Send(src + at, std::min(kChunk, bytes[me] - at), ncclUint8, q, ctx->comm, stream);
+            if (r == ncclSuccess && at < bytes[q])
+                r = R->Recv(dst + off[q] + at, std::min(kChunk, bytes[q] - at), ncclUint8, q, ctx->comm, stream);
+        }
+        const ncclResult_t e = R->GroupEnd();
+        if (r == ncclSuccess) r = e;
+        if (r != ncclSuccess) return fail(GS_ERR_RCCL, "all-gather of %zu bytes failed: %s", off[world], R->GetErrorString(r));
+    }
+    return GS_OK;
+}
+
 } // namespace gsi
 
 using namespace gsi;

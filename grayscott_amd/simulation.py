@@ -225,6 +225,56 @@ class HipContext:
             pass
 
 
+# ``gs_summary`` as a numpy record: what ``Ensemble.summaries`` returns (32 bytes, the C layout, filled in place).
+SUMMARY_DTYPE = np.dtype([("sum", "<f8"), ("sum_sq", "<f8"), ("min", "<f4"), ("max", "<f4"), ("nonfinite", "<u8")])
+
+
+@dataclass(frozen=True)
+class Summary:
+    """A plane's summary computed on the device (``gs_summary``, include/gs_hip.h): ``sum`` and ``sum_sq`` of its finite
+    cells (f64, in the fixed fold order the header defines: bit-reproducible), their ``min`` and ``max`` (+inf / -inf when
+    there are none), the count of non-finite cells, and ``size``, the plane's number of cells."""
+
+    sum: float
+    sum_sq: float
+    min: float
+    max: float
+    nonfinite: int
+    size: int
+
+    @classmethod
+    def from_c(cls, s, size: int) -> "Summary":
+        return cls(float(s.sum), float(s.sum_sq), float(s.min), float(s.max), int(s.nonfinite), int(size))
+
+    @property
+    def cells(self) -> int:
+        """Finite cells: the ones the sums, the mean and the standard deviation cover."""
+        return self.size - self.nonfinite
+
+    @property
+    def mean(self) -> float:
+        return self.sum / self.cells if self.cells else float("nan")
+
+    @property
+    def std(self) -> float:
+        """Population standard deviation of the finite cells, from the two sums."""
+        if not self.cells:
+            return float("nan")
+        m = self.mean
+        return float(np.sqrt(max(self.sum_sq / self.cells - m * m, 0.0)))
+
+
+def summarize_fields(context: "HipContext", fields: Sequence["HipConcentration"]) -> List[Summary]:
+    """``gs_fields_summarize``: summaries of 1..4 planes of one shape over the whole global grid, in one call (collective
+    in a multi-process context)."""
+    n = len(fields)
+    arr = (ctypes.c_void_p * max(n, 1))(*[f.handle for f in fields])
+    out = (capi.GsSummary * max(n, 1))()
+    capi.check(context._lib.gs_fields_summarize(context.handle, arr, n, out))
+    rows, cols = fields[0].shape()
+    return [Summary.from_c(out[i], rows * cols) for i in range(n)]
+
+
 def pinned_empty(shape: Sequence[int]) -> np.ndarray:
     """float32 array in page-locked host memory (``gs_host_alloc``) for overlapped downloads.
     The allocation is released when the last view of it is garbage-collected."""
@@ -377,6 +427,11 @@ class HipConcentration:
                                                   out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def summary(self, context: HipContext) -> Summary:
+        """Sum, sum of squares, min and max of the finite cells and the non-finite count of this plane over the whole
+        global grid, computed on the device (blocking; collective in a multi-process context)."""
+        return summarize_fields(context, [self])[0]
+
     def destroy(self) -> None:
         if self._h and self._ctx._h:
             self._ctx._lib.gs_field_destroy(self._ctx._h, self._h)
@@ -481,6 +536,13 @@ class Species:
         self.u.flip(self._context)
         self.v.flip(self._context)
 
+    def summary(self) -> Tuple[Summary, Summary]:
+        """(U, V) summaries of the current state in one call (``gs_fields_summarize``; blocking, collective in a
+        multi-process context)."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = summarize_fields(self._context, [in_u, in_v])
+        return u, v
+
     def access_result(self, f: Callable):
         return f(self.v._pair[0], self._context)
 
@@ -559,6 +621,16 @@ class Ensemble:
     def u_views(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """U of members ``[first, first + count)`` as ``[count, rows, cols]`` (blocking)."""
         return self._download(0, first, count)
+
+    def summaries(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """Summaries of members ``[first, first + count)`` computed on the device (``gs_members_summarize``, blocking):
+        a structured array of ``SUMMARY_DTYPE`` with shape ``(count, 2)``, column 0 = U, 1 = V -- bit for bit what
+        ``Species.summary`` gives for a lone Species in the member's state."""
+        first, count = self._range(first, count)
+        out = np.zeros((max(count, 0), 2), SUMMARY_DTYPE)
+        capi.check(self._ctx._lib.gs_members_summarize(self._ctx.handle, self.handle, first, count,
+                                                        out.ctypes.data_as(ctypes.POINTER(capi.GsSummary))))
+        return out
 
     def prepare_steps(self, steps: int) -> None:
         """Enqueue ``steps`` steps of every member and return (``gs_ensemble_run``); ``context.sync()`` waits."""

@@ -9,6 +9,12 @@ with the shared flags of ``simulate`` that still apply (``-r -c -t`` and the ``-
 every member as the dataset ``matrix[members, rows, cols]`` f32 -- the layout the reference's ``simulate`` writes, one
 image per member, so its ``data-to-pics`` renders one picture per (F, k) pair -- and a JSON sidecar (``-o``'s name with
 ``.json``) listing ``index``, ``feed`` and ``kill`` of every member.
+
+``--summary-every N`` also records, every N steps and after the last one, the summaries of every member computed on the
+device (``Ensemble.summaries``: sum, sum of squares, min and max of the finite cells, non-finite count, for U and V) into
+``<output stem>.summary.npz``: ``steps[samples]`` and ``sum``, ``sum_sq``, ``min``, ``max``, ``nonfinite``, each
+``[members, samples, 2]`` (last axis: U, V).  ``--no-fields`` skips the HDF5 file of final V planes (the JSON sidecar
+is still written).  Neither changes the states: the HDF5 file is byte for byte the same with or without summaries.
 """
 from __future__ import annotations
 
@@ -46,8 +52,14 @@ def parse(argv=None):
     ap.add_argument("-c", "--nbcol", type=int, default=1920)
     ap.add_argument("-t", "--deltat", type=float, default=None)
     ap.add_argument("-o", "--output", default="sweep.h5")
+    ap.add_argument("--summary-every", type=int, default=0, metavar="N",
+                    help="record every member's summaries every N steps and at the end (<output stem>.summary.npz)")
+    ap.add_argument("--no-fields", action="store_true", help="do not write the HDF5 file of final V planes")
     add_backend_args(ap)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.summary_every < 0:
+        ap.error("--summary-every must be at least 1 (0 = off)")
+    return args
 
 
 def members(args) -> List[Tuple[int, float, float]]:
@@ -69,6 +81,24 @@ def sidecar_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".json"
 
 
+def summary_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".summary.npz"
+
+
+def sample_steps(steps: int, every: int) -> List[int]:
+    """Steps after which the summaries are taken: every ``every`` steps and after the last one."""
+    out = list(range(every, steps + 1, every))
+    if not out or out[-1] != steps:
+        out.append(steps)
+    return out
+
+
+def write_summaries(path: str, steps: List[int], samples: List[np.ndarray]) -> None:
+    rec = np.stack(samples, axis=1)  # [members, samples, 2] of SUMMARY_DTYPE
+    np.savez(path, steps=np.asarray(steps, np.int64),
+             **{name: np.ascontiguousarray(rec[name]) for name in rec.dtype.names})
+
+
 def run(args) -> dict:
     if args.steps < 0:
         raise ValueError("--steps must be at least 0")
@@ -77,15 +107,24 @@ def run(args) -> dict:
     sim = Simulation.new(params[0], backend_args(args))
     ens = sim.make_ensemble(shape, params)
     t0 = time.perf_counter()
-    ens.perform_steps(args.steps)
+    if args.summary_every:
+        done, steps, samples = 0, sample_steps(args.steps, args.summary_every), []
+        for at in steps:
+            ens.prepare_steps(at - done)
+            done = at
+            samples.append(ens.summaries())  # (waits for the steps)
+        write_summaries(summary_path(args.output), steps, samples)
+    else:
+        ens.perform_steps(args.steps)
     elapsed = time.perf_counter() - t0
-    out = hdf5_min.create(args.output, (len(params),) + shape)
-    per_chunk = max(1, (256 << 20) // (4 * shape[0] * shape[1]))  # download in pieces of ~256 MB
-    for first in range(0, len(params), per_chunk):
-        count = min(per_chunk, len(params) - first)
-        out[first:first + count] = ens.result_views(first, count)
-    out.flush()
-    del out
+    if not args.no_fields:
+        out = hdf5_min.create(args.output, (len(params),) + shape)
+        per_chunk = max(1, (256 << 20) // (4 * shape[0] * shape[1]))  # download in pieces of ~256 MB
+        for first in range(0, len(params), per_chunk):
+            count = min(per_chunk, len(params) - first)
+            out[first:first + count] = ens.result_views(first, count)
+        out.flush()
+        del out
     with open(sidecar_path(args.output), "w") as f:
         json.dump({"shape": list(shape), "steps": args.steps,
                    "members": [{"index": i, "feed": feed, "kill": kill} for i, feed, kill in members(args)]}, f, indent=1)

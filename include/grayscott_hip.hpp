@@ -13,6 +13,7 @@
 #include "gs_hip.h"
 
 #include <array>
+#include <cmath>
 #include <cstddef>
 #include <memory>
 #include <stdexcept>
@@ -34,6 +35,26 @@ inline void check(int32_t status)
 {
     if (status != GS_OK) throw HipError(status, gs_last_error());
 }
+
+// A plane's summary computed on the device (gs_summary): sum, sum of squares, min and max of its finite cells (fold order
+// of gs_hip.h: bit-reproducible), the count of its non-finite cells, and `size`, its number of cells.
+struct Summary {
+    double sum = 0.0, sum_sq = 0.0;
+    float min = 0.0f, max = 0.0f;
+    uint64_t nonfinite = 0, size = 0;
+    static Summary from_c(const gs_summary &s, uint64_t size)
+    {
+        return Summary{s.sum, s.sum_sq, s.min, s.max, s.nonfinite, size};
+    }
+    uint64_t cells() const { return size - nonfinite; } // the finite ones
+    double mean() const { return cells() ? sum / (double)cells() : std::nan(""); }
+    double std() const
+    {
+        if (!cells()) return std::nan("");
+        const double m = mean(), var = sum_sq / (double)cells() - m * m;
+        return var > 0.0 ? std::sqrt(var) : 0.0;
+    }
+};
 
 struct Parameters {
     std::array<std::array<Precision, 3>, 3> weights{{{0.25f, 0.5f, 0.25f}, {0.5f, 0.0f, 0.5f}, {0.25f, 0.5f, 0.25f}}};
@@ -285,6 +306,16 @@ class Species {
     }
     Evolving &u() { return u_; }
     Evolving &v() { return v_; }
+    // (U, V) summaries of the current state over the whole global grid, in one call (gs_fields_summarize; blocking,
+    // collective in a multi-process context)
+    std::pair<Summary, Summary> summary()
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        gs_summary out[2];
+        check(gs_fields_summarize(context_->get(), planes, 2, out));
+        const Shape s = shape();
+        return {Summary::from_c(out[0], s[0] * s[1]), Summary::from_c(out[1], s[0] * s[1])};
+    }
     std::vector<Precision> make_result_view() { return v_.in().make_scalar_view(context_); }
     void write_result_view(Precision *target, Shape target_shape)
     {
@@ -354,6 +385,16 @@ class Ensemble {
     {
         prepare_steps(steps);
         ctx_->sync();
+    }
+    // summaries of members [first, first + count) from the newest state (gs_members_summarize, blocking): element
+    // 2 i = U, 2 i + 1 = V of member first + i, bit for bit what Species::summary gives for a lone Species in that state
+    std::vector<Summary> summaries(std::size_t first, std::size_t count) const
+    {
+        std::vector<gs_summary> c(2 * count);
+        check(gs_members_summarize(ctx_->get(), e_, first, count, c.data()));
+        std::vector<Summary> out;
+        for (const gs_summary &s : c) out.push_back(Summary::from_c(s, shape_[0] * shape_[1]));
+        return out;
     }
 
   private:

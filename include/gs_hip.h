@@ -447,6 +447,34 @@ int32_t gs_ensemble_upload(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t
 int32_t gs_ensemble_download(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, int32_t species, float *host);
 int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps);
 
+/* Summaries computed on the device: for one plane of the WHOLE global grid, the sum and sum of squares of its finite
+ * cells, their minimum and maximum, and the count of non-finite cells (NaN, +-inf) -- without downloading the plane.
+ *   gs_fields_summarize    out[i] for fields[i], i < n (1..4 fields of one shape, e.g. U and V of a Species): one wait for
+ *                          enqueued work (as gs_field_download does: a persistent window launch that gave up is run again
+ *                          first), one launch per slab, one exchange.  In a multi-process context the call is collective,
+ *                          like gs_run, and every rank receives the summary of the global grid.
+ *   gs_members_summarize  out[2 i] (U) and out[2 i + 1] (V) of members first + i, i < count, from the newest slot.
+ * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID: a
+ * null or foreign handle, mixed shapes, n outside 1..4, members outside the ensemble.  An empty plane: sums +0, min +inf,
+ * max -inf, nonfinite 0.
+ * Fold order -- a function of (rows, cols) alone, so that the results are bit-reproducible whatever the slab count, the
+ * process count or the step kernel, and a member's summary is bit for bit that of a lone Species in the same state:
+ *   1. row partial: each of 64 lanes holds an f64 accumulator starting at +0.0; lane l adds, in this order, the cells at
+ *      columns 256 k + 4 l + j for k = 0, 1, ... and j = 0..3 (x as f64; for sum_sq the product x * x formed in f64,
+ *      which is exact).  A column >= cols or a non-finite cell adds nothing;
+ *   2. lane combine: the 64 partials are halved repeatedly, p[0:32] + p[32:64], then p[0:16] + p[16:32], ... down to one;
+ *   3. field fold: the row partials are added one after the other in f64, in ascending GLOBAL row order, from +0.0.
+ * min and max are order-free (the sign of a zero extreme is not specified); sub-normal cells count as the values they
+ * are (never flushed). */
+typedef struct gs_summary {
+    double sum;         /* of the finite cells, in the fold order above                   */
+    double sum_sq;      /* of x * x over the finite cells (formed in f64: exact), same order */
+    float min, max;     /* of the finite cells; +inf / -inf when there are none           */
+    uint64_t nonfinite; /* NaN and +-inf cells                                            */
+} gs_summary;           /* 32 bytes */
+int32_t gs_fields_summarize(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_summary *out);
+int32_t gs_members_summarize(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, gs_summary *out);
+
 /* Measurement hook, not for bindings (tools/rccl_under_load.py): the ghost-row exchange's transport on ONE GPU while the
  * caller keeps the chip busy or idle.  mode 0: a one-rank RCCL communicator, `messages` ncclSend / ncclRecv pairs of
  * `floats` f32 to itself in one group; mode 1: the same bytes as device-to-device copies (the in-process chain's route);

@@ -45,6 +45,21 @@ pub struct gs_ctx {
 pub struct gs_field {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct gs_ensemble {
+    _private: [u8; 0],
+}
+
+/// A plane's summary computed on the device (32 bytes; fold order in include/gs_hip.h).
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default)]
+pub struct gs_summary {
+    pub sum: f64,
+    pub sum_sq: f64,
+    pub min: f32,
+    pub max: f32,
+    pub nonfinite: u64,
+}
 
 extern "C" {
     pub fn gs_abi_version() -> i32;
@@ -112,5 +127,13 @@ extern "C" {
         palette_rgb: *const u8,
         n_colors: i32,
         host_rgb: *mut u8,
+    ) -> i32;
+    pub fn gs_fields_summarize(ctx: *mut gs_ctx, fields: *const *mut gs_field, n: i32, out: *mut gs_summary) -> i32;
+    pub fn gs_members_summarize(
+        ctx: *mut gs_ctx,
+        e: *mut gs_ensemble,
+        first: u64,
+        count: u64,
+        out: *mut gs_summary,
     ) -> i32;
 }
