@@ -36,6 +36,37 @@ def plane(x, shape) -> np.ndarray:
     return np.full(shape, np.float32(x), np.float32) if np.ndim(x) == 0 else np.asarray(x, np.float32)
 
 
+def params_of(p) -> dict:
+    """``grayscott_amd.Parameters`` as the reference's parameter dict (every value rounded once to float32, as the C ABI's
+    ``gs_params`` holds it)."""
+    f = np.float32
+    return dict(w=np.array(p.weights, np.float32), du=f(p.diffusion_rate_u), dv=f(p.diffusion_rate_v), feed=f(p.feed_rate),
+                kill=f(p.kill_rate), dt=f(p.time_step))
+
+
+# (F, K) pairs at the edges of the rates' range: +-0 feed, zero kill, a sub-normal feed, and feed + kill rounding to a
+# sub-normal -- from two normal rates (3e-38 - 2.5e-38) and from two sub-normal ones -- which strict math must flush
+EDGE_RATES = [(0.0, 0.06), (-0.0, 0.06), (0.03, 0.0), (0.03, -0.0), (0.0, 0.0), (-0.0, -0.0), (1e-39, 0.05), (-1e-39, 0.05),
+              (3e-38, -2.5e-38), (1e-39, 2e-39)]
+
+
+def planted_map(shape, rng, share: float = 0.3):
+    """A random map (F in [0.01, 0.06], K in [0.04, 0.07]) with EDGE_RATES planted in about ``share`` of its cells."""
+    feed = rng.uniform(0.01, 0.06, shape).astype(np.float32)
+    kill = rng.uniform(0.04, 0.07, shape).astype(np.float32)
+    pick = rng.integers(0, len(EDGE_RATES), shape)
+    where = rng.random(shape) < share
+    edge = np.array(EDGE_RATES, np.float32)
+    feed[where], kill[where] = edge[pick[where], 0], edge[pick[where], 1]
+    return feed, kill
+
+
+def has_subnormal(*planes) -> bool:
+    """Does any of the planes hold a sub-normal f32 (non-zero, below the smallest normal one)?"""
+    tiny = np.finfo(np.float32).tiny
+    return any(bool(np.any((x != 0) & (np.abs(x) < tiny))) for x in planes)
+
+
 def _params(params, feed, kill):
     p = dict(params or numpy_ref.default_params())
     p["feed"], p["kill"] = feed, kill

@@ -2,7 +2,8 @@
 reference of tests/param_map_ref.py under every boundary rule, in the strict flavour and in the fused one on states
 without sub-normals; every form of the marching kernel (K = 1..4, 1, 2 and 4 columns per lane, general and .op), the
 single-step kernels of gs_step, slab chains, row bands and two processes; a uniform map changes no bit; the map's
-lifecycle (replace, detach, the caller's planes destroyed, graph replay) never replays stale state; the refusals;
+lifecycle (replace, detach, the caller's planes destroyed, graph replay, set_params switching between the .op and the
+general form, the two kernel sets' tuned choices) never replays stale state; the refusals;
 ensembles ignore the map; the simulate driver end to end."""
 from __future__ import annotations
 
@@ -233,6 +234,91 @@ def test_attach_replace_detach(use_graph, boundary):
             assert name.split("@")[0].endswith("/map") == (phase != "none"), (phase, name)
             assert_bits_equal(iu.make_scalar_view(sim.context), ref[0], f"U after {phase} ({name})")
             assert_bits_equal(iv.make_scalar_view(sim.context), ref[1], f"V after {phase} ({name})")
+    finally:
+        sim.context.close()
+
+
+# dt = 0.5 and power-of-two weights that are not the default ones, a centre weight included: the general map form
+SKEWED = Parameters(weights=((0.25, 0.5, 0.125), (1.0, 0.5, 0.25), (0.0, 0.125, 0.5)), time_step=0.5)
+
+
+@pytest.mark.parametrize("use_graph", [0, 1])
+@pytest.mark.parametrize("boundary", [capi.GS_BOUNDARY_CLIPPED, capi.GS_BOUNDARY_PERIODIC])
+def test_map_across_set_params(use_graph, boundary):
+    """set_params with a map attached switches the map form between .op and the general one (and back); detaching and
+    re-attaching keeps the parameters in force.  Each phase continues from the state the last one left."""
+    shape = (300, 701)
+    default = Parameters()
+    u0, v0 = stress_fields(shape, 10)
+    feed, kill = random_map(shape, 21)
+    sim = Simulation.new(default, HipArgs(devices=[0], boundary=boundary, use_graph=use_graph, fuse_steps=4))
+    try:
+        species = species_from_arrays(sim, u0, v0)
+        sim.set_param_map(feed, kill)
+        ref = (u0, v0)
+        for phase, p in (("defaults", default), ("skewed", SKEWED), ("defaults again", default), ("detached", default),
+                         ("re-attached", default)):
+            mapped = phase != "detached"
+            if phase == "detached":
+                sim.clear_param_map()
+            elif phase == "re-attached":
+                sim.set_param_map(feed, kill)
+            else:
+                sim.context.set_params(p)
+            sim.perform_steps(species, 70)  # 17 passes + 2: graph batches of 16 passes and a remainder
+            ref = R.run(ref[0], ref[1], 70, feed if mapped else p.feed_rate, kill if mapped else p.kill_rate,
+                        params=R.params_of(p), boundary=boundary)
+            iu, iv, _, _ = species.in_out()
+            name = sim.context.info()[0]
+            assert name.split("@")[0].endswith("/map") == mapped, (phase, name)
+            if mapped:
+                assert name.split("@")[0].endswith(RULE_SUFFIX[boundary]), (phase, name)
+                assert name.startswith("tb-k4") and (".op" in name) == (p is default), (phase, name)
+            assert_bits_equal(iu.make_scalar_view(sim.context), ref[0], f"U after {phase} ({name})")
+            assert_bits_equal(iv.make_scalar_view(sim.context), ref[1], f"V after {phase} ({name})")
+    finally:
+        sim.context.close()
+
+
+def test_tuned_choices_of_each_kernel_set():
+    """gs_ctx_set_tuned with a map attached pins the mapped run (K and CPL in its name); gs_ctx_get_tuned returns the
+    uniform set's choice after a detach and the map set's after re-attaching."""
+    shape = (200, 300)
+    u0, v0 = stress_fields(shape, 11)
+    feed, kill = random_map(shape, 24)
+    p = Parameters()
+    sim = Simulation.new(p, HipArgs(devices=[0], kernel=capi.GS_KERNEL_TB, no_tune=1))
+    try:
+        ctx = sim.context
+        species = species_from_arrays(sim, u0, v0)
+        ref = (u0, v0)
+
+        def steps(mapped, prefix):
+            nonlocal ref
+            sim.perform_steps(species, 9)
+            ref = R.run(ref[0], ref[1], 9, feed if mapped else p.feed_rate, kill if mapped else p.kill_rate)
+            name = ctx.info()[0]
+            assert name.startswith(prefix) and name.split("@")[0].endswith("/map") == mapped, (prefix, name)
+            iu, iv, _, _ = species.in_out()
+            assert_bits_equal(iu.make_scalar_view(ctx), ref[0], f"U ({name})")
+            assert_bits_equal(iv.make_scalar_view(ctx), ref[1], f"V ({name})")
+
+        ctx.set_tuned(shape[0], shape[1], 8, 3, 2)
+        uniform = ctx.get_tuned(*shape)
+        assert uniform[:3] == (8, 3, 2), uniform
+        steps(False, "tb-k3c2/")
+        sim.set_param_map(feed, kill)
+        assert ctx.get_tuned(*shape) == (0, 0, 0, 0)   # nothing chosen for the map's kernels yet
+        ctx.set_tuned(shape[0], shape[1], 16, 2, 1)
+        mapped = ctx.get_tuned(*shape)
+        assert mapped[:3] == (16, 2, 1), mapped
+        steps(True, "tb-k2c1/")
+        sim.clear_param_map()
+        assert ctx.get_tuned(*shape) == uniform
+        steps(False, "tb-k3c2/")
+        sim.set_param_map(feed, kill)
+        assert ctx.get_tuned(*shape) == mapped
+        steps(True, "tb-k2c1/")
     finally:
         sim.context.close()
 
