@@ -42,6 +42,9 @@ UNITS = [
     # the parameter map's forms of the marching kernel (gs_step_tb_mk), one translation unit per flavour
     ("gs_step_kernels.hip", "gs_step_strict_map.o", STRICT + ["-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
     ("gs_step_kernels.hip", "gs_step_fused_map.o", ["-DGS_MATH_FUSED=1", "-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
+    # the domain mask's forms of the marching kernel (gs_step_tb_wk), likewise
+    ("gs_step_kernels.hip", "gs_step_strict_mask.o", STRICT + ["-DGS_TB_MASK_ONLY=1"] + KERNEL_FLAGS),
+    ("gs_step_kernels.hip", "gs_step_fused_mask.o", ["-DGS_MATH_FUSED=1", "-DGS_TB_MASK_ONLY=1"] + KERNEL_FLAGS),
     ("gs_util_kernels.hip", "gs_util.o", []),
     # summaries of planes (row records, the ensembles' fold): hipcc's default float mode, sub-normal cells kept
     ("gs_summary.hip", "gs_summary_k.o", []),
@@ -54,6 +57,7 @@ UNITS = [
     ("gs_rccl.cpp", "gs_rccl.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_ensemble.cpp", "gs_ensemble.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_param_map.cpp", "gs_param_map.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_mask.cpp", "gs_mask.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_summary.cpp", "gs_summary.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 

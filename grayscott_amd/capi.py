@@ -44,6 +44,7 @@ EXPORTS = (
     "gs_ensemble_create", "gs_ensemble_destroy", "gs_ensemble_shape", "gs_ensemble_set_params", "gs_ensemble_seed",
     "gs_ensemble_upload", "gs_ensemble_download", "gs_ensemble_run",
     "gs_ctx_set_param_map",
+    "gs_ctx_set_mask",
     "gs_fields_summarize", "gs_members_summarize",
 )
 
@@ -145,6 +146,7 @@ def load() -> ctypes.CDLL:
         "gs_ctx_destroy": (i32, [vp]),
         "gs_ctx_set_params": (i32, [vp, P(GsParams)]),
         "gs_ctx_set_param_map": (i32, [vp, vp, vp]),
+        "gs_ctx_set_mask": (i32, [vp, vp]),
         "gs_field_create": (i32, [vp, P(vp), u64, u64]),
         "gs_field_destroy": (i32, [vp, vp]),
         "gs_field_shape": (i32, [vp, P(u64), P(u64)]),

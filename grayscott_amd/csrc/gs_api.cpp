@@ -163,7 +163,8 @@ int32_t refresh_ghosts(gs_ctx *ctx, gs_field *f)
     return GS_OK;
 }
 
-int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fuse, const GsMapPlanes *map)
+int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fuse, const GsMapPlanes *map,
+                    const GsMaskPlanes *mask = nullptr)
 {
     int32_t kernel = ctx->o.kernel;
     if (kernel == GS_KERNEL_AUTO || kernel == GS_KERNEL_TILE || kernel == GS_KERNEL_WINDOW) kernel = fuse > 1 ? GS_KERNEL_TB : GS_KERNEL_STREAM;
@@ -172,17 +173,19 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
     const bool fused = ctx->o.math == GS_MATH_FUSED;
     if (map && kernel == GS_KERNEL_LDS) // (gs_ctx_set_param_map refuses such a context first)
         return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no parameter-map form");
+    if (mask && kernel == GS_KERNEL_LDS) // (gs_ctx_set_mask refuses such a context first)
+        return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no domain-mask form");
     const char *name = nullptr;
     hipError_t e;
     switch (kernel) {
     case GS_KERNEL_TB:
-        e = fused ? gs_launch_tb_fused(a, fuse, stream, &name, map) : gs_launch_tb_strict(a, fuse, stream, &name, map);
+        e = fused ? gs_launch_tb_fused(a, fuse, stream, &name, map, mask) : gs_launch_tb_strict(a, fuse, stream, &name, map, mask);
         break;
     case GS_KERNEL_SIMPLE:
-        e = fused ? gs_launch_simple_fused(a, stream, &name, map) : gs_launch_simple_strict(a, stream, &name, map);
+        e = fused ? gs_launch_simple_fused(a, stream, &name, map, mask) : gs_launch_simple_strict(a, stream, &name, map, mask);
         break;
     case GS_KERNEL_STREAM:
-        e = fused ? gs_launch_stream_fused(a, stream, &name, map) : gs_launch_stream_strict(a, stream, &name, map);
+        e = fused ? gs_launch_stream_fused(a, stream, &name, map, mask) : gs_launch_stream_strict(a, stream, &name, map, mask);
         break;
     case GS_KERNEL_LDS:
         e = fused ? gs_launch_lds_fused(a, stream, &name) : gs_launch_lds_strict(a, stream, &name);
@@ -243,6 +246,13 @@ static const GsMapPlanes *map_planes(const gs_ctx *ctx, int i, int row, GsMapPla
     const ptrdiff_t off = (ptrdiff_t)row * ctx->map.feed->pitch;
     out.feed = ctx->map.feed->s[i].row0 + off;
     out.fpk = ctx->map.fpk->s[i].row0 + off;
+    return &out;
+}
+// ... and the domain mask's link plane (nullptr without a mask)
+static const GsMaskPlanes *mask_planes(const gs_ctx *ctx, int i, int row, GsMaskPlanes &out)
+{
+    if (!ctx->masked()) return nullptr;
+    out.link = ctx->mask.link->s[i].row0 + (ptrdiff_t)row * ctx->mask.link->pitch;
     return &out;
 }
 
@@ -327,6 +337,8 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         a.in_u += off; a.in_v += off; a.out_u += off; a.out_v += off;
         GsMapPlanes mp;
         const GsMapPlanes *map = map_planes(ctx, 0, r0, mp);
+        GsMaskPlanes kp;
+        const GsMaskPlanes *mask = mask_planes(ctx, 0, r0, kp);
         a.rows = r1 - r0;
         a.top_present = k > 0;
         a.bottom_present = k < V - 1;
@@ -342,14 +354,14 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         e.rb0 = nk <= 2 * fuse ? 0 : nk - fuse;
         e.rb1 = nk <= 2 * fuse ? 0 : nk;
         e.rows_per_unit = fuse;
-        GS_TRY(launch_rows(ctx, e, b.halo, fuse, map));
+        GS_TRY(launch_rows(ctx, e, b.halo, fuse, map, mask));
         GS_HIP(hipEventRecord(b.halod[p], b.halo));
         GS_HIP(hipStreamWaitEvent(b.compute, ctx->band_join, 0));
         GS_HIP(hipStreamWaitEvent(b.compute, b.halod[q], 0));
         if (nk > 2 * fuse) {
             a.ra0 = fuse;
             a.ra1 = nk - fuse;
-            GS_TRY(launch_rows(ctx, a, b.compute, fuse, map));
+            GS_TRY(launch_rows(ctx, a, b.compute, fuse, map, mask));
         }
         GS_HIP(hipEventRecord(b.done[p], b.compute));
     }
@@ -383,7 +395,8 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
         a.ra0 = 0;
         a.ra1 = a.rows;
         GsMapPlanes mp;
-        GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map_planes(ctx, 0, 0, mp)));
+        GsMaskPlanes kp;
+        GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map_planes(ctx, 0, 0, mp), mask_planes(ctx, 0, 0, kp)));
     } else {
         if (fuse > kGhostRows || fuse > min_slab_rows(ctx, in_u))
             return fail(GS_ERR_INVALID, "cannot fuse %d steps over slabs of %d rows", fuse, min_slab_rows(ctx, in_u));
@@ -403,6 +416,8 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             GsStepArgs a = make_args(ctx, in_u, in_v, out_u, out_v, i, fuse);
             GsMapPlanes mp;
             const GsMapPlanes *map = map_planes(ctx, i, 0, mp);
+            GsMaskPlanes kp;
+            const GsMaskPlanes *mask = mask_planes(ctx, i, 0, kp);
             const int n = a.rows;
             // gs_ctx_set_pass_timing: events around this pass's halo-stream work and interior kernel
             const bool timed = sl.timed < ctx->pass_timing;
@@ -422,7 +437,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             b.rb0 = n <= 2 * depth ? 0 : n - depth;
             b.rb1 = n <= 2 * depth ? 0 : n;
             b.rows_per_unit = depth; // one unit per boundary band and strip
-            GS_TRY(launch_rows(ctx, b, sl.halo, fuse, map));
+            GS_TRY(launch_rows(ctx, b, sl.halo, fuse, map, mask));
             GS_TRY(push_halo(ctx, outs, 2, i, sl.halo, depth));
             GS_HIP(hipEventRecord(sl.halod[p], sl.halo));
             if (timed) GS_HIP(hipEventRecord(sl.th1[sl.timed], sl.halo));
@@ -432,7 +447,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             if (n > 2 * depth) {
                 a.ra0 = depth;
                 a.ra1 = n - depth;
-                GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map));
+                GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map, mask));
             }
             GS_HIP(hipEventRecord(sl.done[p], sl.compute));
             if (timed) {
@@ -488,6 +503,7 @@ int32_t replay_graph_batches(Run &r, int kk)
     key.batch = kGraphBatch;
     key.p = ctx->p;
     key.map_gen = ctx->map.gen;
+    key.mask_gen = ctx->mask.gen;
     if (!ctx->graph_exec || !(ctx->graph_key == key)) {
         if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
         if (ctx->graph) { (void)hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
@@ -568,6 +584,7 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
 {
     if (!ctx) return GS_OK;
     destroy_param_map(ctx);
+    destroy_mask(ctx);
     destroy_summary_buffers(ctx);
     for (auto &sl : ctx->slabs) {
         if (!sl.compute && !sl.halo) continue; // never initialised (creation failed early)
@@ -619,8 +636,9 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     if (ctx->band_join) (void)hipEventDestroy(ctx->band_join);
-    if ((!ctx->tunings.empty() || !ctx->map.tunings.empty()) && !ctx->slabs.empty() && hipSetDevice(ctx->slabs[0].device) == hipSuccess)
-        for (auto *tunings : {&ctx->tunings, &ctx->map.tunings}) // (the other kernel set's, gs_param_map.cpp)
+    if ((!ctx->tunings.empty() || !ctx->map.tunings.empty() || !ctx->mask.tunings.empty()) && !ctx->slabs.empty() &&
+        hipSetDevice(ctx->slabs[0].device) == hipSuccess)
+        for (auto *tunings : {&ctx->tunings, &ctx->map.tunings, &ctx->mask.tunings}) // (the other kernel sets', gs_param_map.cpp, gs_mask.cpp)
             for (auto &t : *tunings)
                 for (auto e : t.events)
                     if (e) (void)hipEventDestroy(e);
@@ -783,6 +801,7 @@ int32_t gs_step(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, gs
 {
     GS_TRY(check_step_fields(ctx, in_u, in_v, out_u, out_v));
     GS_TRY(check_map_shape(ctx, in_u));
+    GS_TRY(check_mask_shape(ctx, in_u));
     GS_TRY(resolve_window(ctx));
     return step_impl(ctx, in_u, in_v, out_u, out_v);
 }
@@ -803,6 +822,7 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
 {
     GS_TRY(check_step_fields(ctx, u0, v0, u1, v1));
     GS_TRY(check_map_shape(ctx, u0));
+    GS_TRY(check_mask_shape(ctx, u0));
     Run r{ctx, {u0, u1}, {v0, v1}};
     r.steps = steps;
     // Temporal blocking: `fuse` steps per pass over HBM (default 4, the measured optimum);
@@ -816,8 +836,9 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
         if (fuse < 1) fuse = 1;
     }
     const bool single = ctx->total_slabs() == 1;
-    // With a parameter map every grid runs the marching kernel: the resident, tile and window kernels have no map form.
-    const bool mapped = ctx->mapped();
+    // With a parameter map or a domain mask every grid runs the marching kernel: the resident, tile and window kernels
+    // have no map or mask form.
+    const bool mapped = ctx->mapped() || ctx->masked();
     // Small grids (single slab, kernel = auto): the whole run is one launch with the grid resident
     // in LDS (gs_run_resident_k) -- up to kGsResidentCells = 1536 cells; above, the window kernel is faster (1536
     // cells: 1630 against 1558 Mcells x steps / s; 2048: 1596 against 2062; 4096: 1695 against 4153; run 48).

@@ -278,4 +278,48 @@ __device__ __forceinline__ void cell(const GsStepArgs &a, const Row &m, const Ro
         react<(FAST & 2) != 0>(a, u, v, acc_u, acc_v, out_u, out_v);
 }
 
+// ---- domain masks (gs_ctx_set_mask) --------------------------------------------------------------------------------
+// A cell's link word (the library's link plane, formed at attach time by gs_mask_links_k): bit (i * 3 + j) is set when
+// the cell at (row + i - 1, column + j - 1) is a wall -- the position as the march reads it: wrapped under the periodic
+// rule, never set outside the grid under the other rules -- and bit kWallSelf when the cell itself is a wall.
+constexpr int kWallSelf = 9;
+// bit B of a link word as an all-ones / all-zeros word, for blend(): one v_bfe_i32 the compiler cannot see through -- a
+// plain shift pair it turns into a compare and v_cndmask_b32, and the lane masks of nine such compares per cell, held in
+// SGPR pairs across a fused level, spill.
+template <int B>
+__device__ __forceinline__ uint32_t link_bit(uint32_t link)
+{
+    uint32_t r;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(r) : "v"(link), "i"(B));
+    return r;
+}
+
+// cell<> of a masked grid.  Each of the eight neighbour operands of the cell at position k is replaced by the cell's own
+// value where that neighbour is a wall (two v_bfi_b32 per neighbour), before the rule's edge handling of cell<> sees
+// them: that handling only ever picks, drops or clamps positions, so each tap of the reference window that reads a wall
+// then reads the centre value instead and contributes w * (u - u), in the reference's order.  A wall cell keeps its
+// input bits.  The operands are copies: a neighbour shared with the next cell of the row keeps its own value there.
+template <int EDGE, int FAST, typename Row, int ZH>
+__device__ __forceinline__ void cell_masked(const GsStepArgs &a, const Row &m, const Row &z, const Row &p, int k, bool mrow,
+                                            bool prow, uint32_t la, uint32_t ra, uint32_t link, float &out_u, float &out_v)
+{
+    const float u = z.u[k], v = z.v[k];
+    Row mm = m, zz = z, pp = p;
+#define GS_WALL(R, I, J)                                                                       \
+    {                                                                                          \
+        const uint32_t w = link_bit<(I) * 3 + (J)>(link);                                      \
+        R.u[k - 1 + (J)] = blend(w, u, R.u[k - 1 + (J)]);                                      \
+        R.v[k - 1 + (J)] = blend(w, v, R.v[k - 1 + (J)]);                                      \
+    }
+    GS_WALL(mm, 0, 0) GS_WALL(mm, 0, 1) GS_WALL(mm, 0, 2)
+    GS_WALL(zz, 1, 0)                   GS_WALL(zz, 1, 2)
+    GS_WALL(pp, 2, 0) GS_WALL(pp, 2, 1) GS_WALL(pp, 2, 2)
+#undef GS_WALL
+    float nu, nv;
+    cell<EDGE, FAST, Row, ZH>(a, mm, zz, pp, k, mrow, prow, la, ra, nu, nv);
+    const uint32_t self = link_bit<kWallSelf>(link);
+    out_u = blend(self, u, nu);
+    out_v = blend(self, v, nv);
+}
+
 } // namespace

@@ -7,6 +7,7 @@
 //   gs_rccl.cpp    RCCL (loaded on first use), its self-test, gs_runtime_info, gs_last_error
 //   gs_ensemble.cpp ensembles: many grids of one shape, each with its own parameters, advanced in shared launches
 //   gs_param_map.cpp parameter maps: per-cell feed and kill rates on one grid (gs_ctx_set_param_map)
+//   gs_mask.cpp    domain masks: wall cells that block diffusion on one grid (gs_ctx_set_mask)
 //   gs_summary.cpp summaries of planes and ensemble members (gs_fields_summarize, gs_members_summarize)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
@@ -164,11 +165,12 @@ struct gs_ctx {
         int k = 0, rpu = 0, cpl = 0, batch = 0;
         gs_params p{};
         uint64_t map_gen = 0; // the parameter map in force (gs_ctx::ParamMap::gen)
+        uint64_t mask_gen = 0; // the domain mask in force (gs_ctx::Mask::gen)
         bool operator==(const GraphKey &o) const
         {
             return std::memcmp(planes, o.planes, sizeof planes) == 0 && rows == o.rows && cols == o.cols && k == o.k &&
                    rpu == o.rpu && cpl == o.cpl && batch == o.batch && std::memcmp(&p, &o.p, sizeof p) == 0 &&
-                   map_gen == o.map_gen;
+                   map_gen == o.map_gen && mask_gen == o.mask_gen;
         }
     } graph_key;
     hipGraph_t graph = nullptr;
@@ -218,6 +220,20 @@ struct gs_ctx {
         std::vector<Tuning> tunings;
     } map;
     bool mapped() const { return map.feed != nullptr; }
+    // gs_ctx_set_mask: the link plane of the domain mask, owned by the context (a u32 link word per cell in the field layout
+    // of the species, ghost rows filled; gs_cell.h: link_bit), nullptr without a mask; `gen` as the map's.  The tuner's
+    // choices of the OTHER kernel set -- the uniform kernels' while a mask is attached, the mask kernels' otherwise --
+    // as ParamMap keeps them (a mask and a map are never attached together, gs_mask.cpp).
+    struct Mask {
+        gs_field *link = nullptr;
+        uint64_t gen = 0;
+        uint64_t tuned_rows = 0, tuned_cols = 0;
+        int tuned_fuse = 0, tuned_rpu = 0, tuned_split = 0, tuned_k = 0, tuned_cpl = 0;
+        int tuned_share = kShareDefault, share_now = kShareDefault;
+        std::vector<Tuned> tuned_cache;
+        std::vector<Tuning> tunings;
+    } mask;
+    bool masked() const { return mask.link != nullptr; }
     int total_slabs() const { return world * (int)slabs.size(); }
     int global_index(int i) const { return rank * (int)slabs.size() + i; }
 };
@@ -302,6 +318,26 @@ int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *la
 // gs_param_map.cpp
 int32_t check_map_shape(const gs_ctx *ctx, const gs_field *f);
 void destroy_param_map(gs_ctx *ctx);
+// The tuner's state of the kernel set in force <-> the other set's, kept in `o` (gs_ctx::ParamMap or gs_ctx::Mask).
+template <typename Set>
+void swap_tuner_sets(gs_ctx *ctx, Set &o)
+{
+    std::swap(ctx->tuned_rows, o.tuned_rows);
+    std::swap(ctx->tuned_cols, o.tuned_cols);
+    std::swap(ctx->tuned_fuse, o.tuned_fuse);
+    std::swap(ctx->tuned_rpu, o.tuned_rpu);
+    std::swap(ctx->tuned_split, o.tuned_split);
+    std::swap(ctx->tuned_k, o.tuned_k);
+    std::swap(ctx->tuned_cpl, o.tuned_cpl);
+    std::swap(ctx->tuned_share, o.tuned_share);
+    std::swap(ctx->share_now, o.share_now);
+    std::swap(ctx->tuned_cache, o.tuned_cache);
+    std::swap(ctx->tunings, o.tunings);
+}
+
+// gs_mask.cpp
+int32_t check_mask_shape(const gs_ctx *ctx, const gs_field *f);
+void destroy_mask(gs_ctx *ctx);
 
 // gs_summary.cpp
 void destroy_summary_buffers(gs_ctx *ctx);

@@ -79,6 +79,11 @@ struct GsStepArgs {
 struct GsMapPlanes {
     const float *feed, *fpk;
 };
+// Domain mask (gs_ctx_set_mask): local row 0, column 0 of one slab's link plane -- a u32 link word per cell (gs_cell.h:
+// link_bit), in the species' layout like the map planes.  The second argument of the mask kernels (gs_*_wk).
+struct GsMaskPlanes {
+    const float *link;
+};
 
 // gs_launch_window_*: one persistent launch for a whole gs_run on grids of ONE round of register-resident windows.
 // Every workgroup owns a rectangle of the grid (GsWindowDesc; the rectangles tile the grid) and keeps it plus a k-cell
@@ -150,16 +155,20 @@ struct GsEnsArgs {
 // returns the hipError_t of the launch.  `name` receives a static kernel-variant label.  `map` (simple, stream and
 // marching kernels): the slab's parameter-map planes -- the launch then runs the map form -- or nullptr.
 #define GS_DECLARE_LAUNCHERS(SUFFIX)                                                           \
-    hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr); \
-    hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr); \
+    hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr, \
+                                         const GsMaskPlanes *mask = nullptr); \
+    hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr, \
+                                         const GsMaskPlanes *mask = nullptr); \
     hipError_t gs_launch_resident_##SUFFIX(const GsStepArgs &a, int steps, hipStream_t s, const char **name); \
-    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr); \
+    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr, \
+                                     const GsMaskPlanes *mask = nullptr); \
     hipError_t gs_launch_tile_##SUFFIX(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name); \
     hipError_t gs_launch_lds_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name);  \
     hipError_t gs_launch_window_##SUFFIX(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name); \
-    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary, bool map = false);                  \
+    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary, bool map = false, bool mask = false); \
     hipError_t gs_launch_map_rates_##SUFFIX(const float *feed, const float *kill, float *fpk, size_t n, hipStream_t s); \
     const void *gs_tb_map_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                                \
+    const void *gs_tb_mask_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                               \
     hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
     hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name);
 
@@ -176,6 +185,7 @@ const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule = 
 // sub-normal sum is flushed, as the reference's DenormalsFlusher does).  gs_tb_map_kernel_*: the entry of the marching
 // kernel's map form (gs_step_tb_mk: its own translation unit, GS_TB_MAP_ONLY) for k fused steps, fast in {0, 3} (3: the
 // .op variant, strict only), cpl columns per lane and rule = rule_set(boundary); nullptr for a form that is not built.
+// gs_tb_mask_kernel_*: the same for the domain mask's forms (gs_step_tb_wk, GS_TB_MASK_ONLY).
 
 // Plane utilities (math-agnostic, defined once in gs_util_kernels.hip).
 hipError_t gs_launch_colormap(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float scale,
@@ -186,6 +196,12 @@ hipError_t gs_launch_fill_rect(float *row0, int32_t pitch, int32_t r0, int32_t r
 hipError_t gs_launch_pack_rows(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float *dst, hipStream_t s);
 // gs_fields_place's probe: reads `bytes` (a multiple of 16, 16-byte aligned) of x and of y and writes them back unchanged.
 hipError_t gs_launch_pair_probe(void *x, void *y, size_t bytes, hipStream_t s);
+// gs_ctx_set_mask: the link words (gs_cell.h: link_bit) of one slab's rows [0, rows) x columns [0, cols) from the mask
+// plane `mask` (a wall: != 0.0f, NaN included), whose ghost rows hold the neighbouring slabs' rows where `top` / `bottom`
+// (a slab above / below exists); `periodic`: neighbours outside the grid wrap (single slab), else they are no walls.
+// Only those cells are written (the caller zeroes the rest of the plane).
+hipError_t gs_launch_mask_links(const float *mask, uint32_t *link, int32_t pitch, int32_t rows, int32_t cols, int32_t top,
+                                int32_t bottom, int32_t periodic, hipStream_t s);
 // Species::new's pattern in every member of dense [members, rows, cols] planes: U = 1, V = 0, and U = 0, V = 1 in
 // rows [r0, r1) x columns [c0, c1).
 hipError_t gs_launch_ens_seed(float *u, float *v, uint64_t members, int32_t rows, int32_t cols, int32_t r0, int32_t r1,

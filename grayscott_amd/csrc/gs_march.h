@@ -343,7 +343,9 @@ __host__ __device__ constexpr int tb_halo_floats(int k, bool cross) { return cro
 // them under the periodic rule -- so every address is one the U loads may form.  A level's row was fetched by the
 // level below it one tick earlier, so the reloads hit in the caches; the K loads are issued together, ahead of the
 // levels' arithmetic.
-template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false, bool MAP = false>
+// MASK: the domain mask's form (gs_step_tb_wk), mp.feed = the link plane (a u32 word per cell in the species' layout):
+// fetch_map's loads of that one plane, the cells computed by cell_masked.
+template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false, bool MAP = false, bool MASK = false>
 __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, int strip, int lane, const GsMapPlanes &mp,
                                          const FairBoard &fb GS_TRACE_PARAM)
 {
@@ -418,10 +420,10 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
             if (rr < 0) rr += a.rows;
             if (rr >= a.rows) rr -= a.rows;
             if (rr < 0 || rr >= a.rows) { rr = row % a.rows; if (rr < 0) rr += a.rows; }
-            const __amdgpu_buffer_rsrc_t pf = plane_rsrc(mp.feed + (ptrdiff_t)rr * pitch), pk = plane_rsrc(mp.fpk + (ptrdiff_t)rr * pitch);
+            const __amdgpu_buffer_rsrc_t pf = plane_rsrc(mp.feed + (ptrdiff_t)rr * pitch), pk = plane_rsrc(MAP ? mp.fpk + (ptrdiff_t)rr * pitch : mp.feed);
             if (pvec) {
                 load_cols_buf<CPL>(pf, pc0 * (int)sizeof(float), 0, r.u);
-                load_cols_buf<CPL>(pk, pc0 * (int)sizeof(float), 0, r.v);
+                if constexpr (MAP) load_cols_buf<CPL>(pk, pc0 * (int)sizeof(float), 0, r.v);
             } else {
 #pragma unroll
                 for (int i = 0; i < CPL; ++i) {
@@ -431,17 +433,19 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
                     float x[1];
                     load_cols_buf<1>(pf, cc * (int)sizeof(float), 0, x);
                     r.u[i] = x[0];
-                    load_cols_buf<1>(pk, cc * (int)sizeof(float), 0, x);
-                    r.v[i] = x[0];
+                    if constexpr (MAP) {
+                        load_cols_buf<1>(pk, cc * (int)sizeof(float), 0, x);
+                        r.v[i] = x[0];
+                    }
                 }
             }
             return r;
         }
         const int rr = min(max(row, row_lo), row_hi);
         if (load_ok) {
-            const __amdgpu_buffer_rsrc_t mf = plane_rsrc(mp.feed + (ptrdiff_t)row_lo * pitch), mk = plane_rsrc(mp.fpk + (ptrdiff_t)row_lo * pitch);
+            const __amdgpu_buffer_rsrc_t mf = plane_rsrc(mp.feed + (ptrdiff_t)row_lo * pitch), mk = plane_rsrc(MAP ? mp.fpk + (ptrdiff_t)row_lo * pitch : mp.feed);
             load_cols_buf<CPL>(mf, voff, (rr - row_lo) * pitch_bytes, r.u);
-            load_cols_buf<CPL>(mk, voff, (rr - row_lo) * pitch_bytes, r.v);
+            if constexpr (MAP) load_cols_buf<CPL>(mk, voff, (rr - row_lo) * pitch_bytes, r.v);
         } else {
 #pragma unroll
             for (int i = 0; i < CPL; ++i) { r.u[i] = 0.f; r.v[i] = 0.f; }
@@ -618,8 +622,8 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
                 fair_tick(tick);
                 w[0][s3] = widen_tb<CPL>(q[s3].u, q[s3].v);
                 if constexpr (!LATE) q[s3] = fetch(l0 + 3);
-                RowQ<CPL> rates[K]; // MAP: (F, F + K) of the row level j computes in this tick, in rates[j - 1]
-                if constexpr (MAP) {
+                RowQ<CPL> rates[K]; // MAP: (F, F + K) of the row level j computes in this tick, in rates[j - 1]; MASK: its link words in .u
+                if constexpr (MAP || MASK) {
 #pragma unroll
                     for (int j = 1; j <= K; ++j) rates[j - 1] = fetch_map(l0 - j);
                 }
@@ -637,7 +641,20 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
                         const bool prow = !ROWS || (row + 1 < a.rows) || a.bottom_present;
                         float nu[CPL], nv[CPL];
                         const float *mf = MAP ? rates[j - 1].u : nullptr, *mfk = MAP ? rates[j - 1].v : nullptr;
-                        if constexpr (EDGE == 4) {
+                        if constexpr (MASK) {
+                            // the mask's form: every cell through cell_masked, the general cell where a row may be missing
+                            constexpr int E = EDGE == 0 || PER ? 0 : EDGE;
+#pragma unroll
+                            for (int k = 0; k < CPL; ++k) {
+                                const uint32_t lk = __builtin_bit_cast(uint32_t, rates[j - 1].u[k]);
+                                if (E == 4 && (mrow && prow))
+                                    cell_masked<0, FAST, RowT<CPL>, ZH>(a, m, z, p, k + 1, true, true, 0u, 0u, lk, nu[k], nv[k]);
+                                else if constexpr (E == 4)
+                                    cell_masked<1, FAST, RowT<CPL>, ZH>(a, m, z, p, k + 1, mrow, prow, 0u, 0u, lk, nu[k], nv[k]);
+                                else
+                                    cell_masked<E, FAST, RowT<CPL>, ZH>(a, m, z, p, k + 1, mrow, prow, la[k], ra[k], lk, nu[k], nv[k]);
+                            }
+                        } else if constexpr (EDGE == 4) {
                             if (mrow && prow) {
                                 cells_interior<FAST, CPL, ZH, MAP>(a, m, z, p, nu, nv, mf, mfk);
                             } else {
@@ -671,11 +688,13 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
 // WG: waves per workgroup.  4 independent waves, or all 16 of a CU with the progress board of tb_march<FAIR>.
 // PER: the periodic rule's kernels (GsStepArgs::zero_halo = 2; kernels of their own, gs_step_tb_pk and its kin).
 // NEU: the zero-flux rule's kernels (GsStepArgs::zero_halo = 3; gs_step_tb_nk and its kin).
-// MAP: the parameter map's forms (gs_step_tb_mk): 4-wave workgroups, no difference sharing.
-template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false>
+// MAP: the parameter map's forms (gs_step_tb_mk): 4-wave workgroups, no difference sharing.  MASK: the domain mask's
+// (gs_step_tb_wk), likewise; mp.feed is the link plane.
+template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false, bool MASK = false>
 __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
 {
     static_assert(!MAP || (WG == 4 && (FAST & 4) == 0), "the map forms are 4-wave marches without difference sharing");
+    static_assert(!MASK || (!MAP && WG == 4 && (FAST & 4) == 0), "the mask forms are 4-wave marches without difference sharing");
     // half_diff needs MODE.IEEE = 0: hwreg(HW_REG_MODE, offset 9, width 1).  The bit only governs
     // the quieting of signalling NaNs otherwise, which parity does not cover.
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0);
@@ -803,26 +822,26 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &
     constexpr bool KINDS = (FAST & 1) && !GS_MATH_FUSED;
     if constexpr (PER) {
         if (!edge)
-            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
         else
-            tb_march<K, 5, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 5, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     } else if constexpr (NEU) {
         if (!edge)
-            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
         else
-            tb_march<K, 1, FAST, CPL, 3, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 1, FAST, CPL, 3, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     } else if (!edge)
-        tb_march<K, 0, FAST, CPL, -1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (a.zero_halo) // (0 or 1 in these kernels: gs_launch_tb sends the other rules to gs_step_tb_pk / _nk)
-        tb_march<K, 1, FAST, CPL, 1, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, 1, FAST, CPL, 1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && left && !right && !ends)
-        tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && right && !left && !ends)
-        tb_march<K, KINDS ? 3 : 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 3 : 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else if (KINDS && a.edge_kinds && ends && !left && !right)
-        tb_march<K, KINDS ? 4 : 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 4 : 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     else
-        tb_march<K, 1, FAST, CPL, 0, FAIR, MAP>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
     if constexpr (FAIR) { if (lane == 0) fb.progress[wave] = 0x7fffffff; }
 #undef GS_TB_LEAVE
 #if defined(GS_TB_TRACE)
@@ -899,6 +918,12 @@ template <int K, int FAST, int CPL, int RULE>
 __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_tb_mk)(GsStepArgs a, GsMapPlanes mp)
 {
     tb_unit<K, FAST, CPL, 4, RULE == 1, RULE == 2, true>(a, mp);
+}
+// The domain mask's forms (gs_ctx_set_mask; the link plane of GsMaskPlanes), with the parameters of the map forms.
+template <int K, int FAST, int CPL, int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_tb_wk)(GsStepArgs a, GsMaskPlanes mk)
+{
+    tb_unit<K, FAST, CPL, 4, RULE == 1, RULE == 2, false, true>(a, GsMapPlanes{mk.link, nullptr});
 }
 
 } // namespace

@@ -17,23 +17,6 @@ int32_t check_map_shape(const gs_ctx *ctx, const gs_field *f)
     return GS_OK;
 }
 
-// The tuner's state of the kernel set in force <-> the other set's (gs_ctx::ParamMap).
-static void swap_tuner_sets(gs_ctx *ctx)
-{
-    gs_ctx::ParamMap &o = ctx->map;
-    std::swap(ctx->tuned_rows, o.tuned_rows);
-    std::swap(ctx->tuned_cols, o.tuned_cols);
-    std::swap(ctx->tuned_fuse, o.tuned_fuse);
-    std::swap(ctx->tuned_rpu, o.tuned_rpu);
-    std::swap(ctx->tuned_split, o.tuned_split);
-    std::swap(ctx->tuned_k, o.tuned_k);
-    std::swap(ctx->tuned_cpl, o.tuned_cpl);
-    std::swap(ctx->tuned_share, o.tuned_share);
-    std::swap(ctx->share_now, o.share_now);
-    std::swap(ctx->tuned_cache, o.tuned_cache);
-    std::swap(ctx->tunings, o.tunings);
-}
-
 void destroy_param_map(gs_ctx *ctx)
 {
     if (ctx->map.feed) (void)gs_field_destroy(ctx, ctx->map.feed);
@@ -55,6 +38,8 @@ int32_t gs_ctx_set_param_map(gs_ctx *ctx, gs_field *feed, gs_field *kill)
         if (feed->ctx != ctx || kill->ctx != ctx) return fail(GS_ERR_INVALID, "field belongs to another context");
         GS_TRY(same_shape(feed, kill));
         if (feed == kill) return fail(GS_ERR_INVALID, "the feed and kill planes must be distinct fields");
+        if (ctx->masked())
+            return fail(GS_ERR_UNSUPPORTED, "a parameter map and a domain mask cannot be attached together: detach the mask first");
         const int32_t k = ctx->o.kernel;
         if (k == GS_KERNEL_WINDOW || k == GS_KERNEL_LDS || k == GS_KERNEL_TILE)
             return fail(GS_ERR_UNSUPPORTED, "the %s kernel has no parameter-map form",
@@ -64,7 +49,7 @@ int32_t gs_ctx_set_param_map(gs_ctx *ctx, gs_field *feed, gs_field *kill)
     const bool was = ctx->mapped();
     if (!feed) {
         destroy_param_map(ctx);
-        if (was) swap_tuner_sets(ctx);
+        if (was) swap_tuner_sets(ctx, ctx->map);
         ctx->map.gen++;
         return GS_OK;
     }
@@ -99,7 +84,7 @@ int32_t gs_ctx_set_param_map(gs_ctx *ctx, gs_field *feed, gs_field *kill)
     ctx->map.fpk->ghost_depth = 0;
     GS_TRY(refresh_ghosts(ctx, ctx->map.feed)); // (collective in a multi-process run)
     GS_TRY(refresh_ghosts(ctx, ctx->map.fpk));
-    if (!was) swap_tuner_sets(ctx);
+    if (!was) swap_tuner_sets(ctx, ctx->map);
     ctx->map.gen++;
     return GS_OK;
 }

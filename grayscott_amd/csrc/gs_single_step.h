@@ -21,8 +21,17 @@ __device__ __forceinline__ void simple_react(const GsStepArgs &a, const GsMapPla
         react(a, u, v, acc_u, acc_v, ou, ov);
 }
 
-template <bool MAP = false>
-__device__ __forceinline__ void simple_cell(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
+// MASK (the simple kernels' domain-mask forms, gs_step_simple_wk): a tap whose neighbour the cell's link word marks as a wall
+// reads the cell's own value (bit (di + 1) * 3 + (dj + 1) for the neighbour at offset (di, dj), after the rule has clamped
+// or wrapped it); a wall cell stores its input.
+__device__ __forceinline__ bool simple_wall(const GsMaskPlanes &mk, ptrdiff_t o, int bit)
+{
+    return (reinterpret_cast<const uint32_t *>(mk.link)[o] >> bit) & 1u;
+}
+
+template <bool MAP = false, bool MASK = false>
+__device__ __forceinline__ void simple_cell(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
+                                            const GsMaskPlanes &mk = GsMaskPlanes{nullptr})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -43,8 +52,9 @@ __device__ __forceinline__ void simple_cell(const GsStepArgs &a, const GsMapPlan
         for (int di = -1; di <= 1; ++di)
             for (int dj = -1; dj <= 1; ++dj) {
                 const bool inside = (di >= 0 || top) && (di <= 0 || bottom) && (dj >= 0 || left) && (dj <= 0 || right);
-                const float su = inside ? a.in_u[o + di * pitch + dj] : 0.0f;
-                const float sv = inside ? a.in_v[o + di * pitch + dj] : 0.0f;
+                float su = inside ? a.in_u[o + di * pitch + dj] : 0.0f;
+                float sv = inside ? a.in_v[o + di * pitch + dj] : 0.0f;
+                if (MASK && inside && simple_wall(mk, o, (di + 1) * 3 + dj + 1)) { su = u; sv = v; }
                 GS_TAP(acc_u, a.w[di + 1][dj + 1], su, u);
                 GS_TAP(acc_v, a.w[di + 1][dj + 1], sv, v);
             }
@@ -53,14 +63,16 @@ __device__ __forceinline__ void simple_cell(const GsStepArgs &a, const GsMapPlan
         for (int di = top ? -1 : 0; di <= (bottom ? 1 : 0); ++di)
             for (int dj = left ? -1 : 0; dj <= (right ? 1 : 0); ++dj) {
                 const float w = a.w[di + i_off][dj + j_off];
-                const float su = a.in_u[o + di * pitch + dj];
-                const float sv = a.in_v[o + di * pitch + dj];
+                float su = a.in_u[o + di * pitch + dj];
+                float sv = a.in_v[o + di * pitch + dj];
+                if (MASK && simple_wall(mk, o, (di + 1) * 3 + dj + 1)) { su = u; sv = v; }
                 GS_TAP(acc_u, w, su, u);
                 GS_TAP(acc_v, w, sv, v);
             }
     }
     float ou, ov;
     simple_react<MAP>(a, mp, o, u, v, acc_u, acc_v, ou, ov);
+    if (MASK && simple_wall(mk, o, kWallSelf)) { ou = u; ov = v; }
     a.out_u[o] = ou;
     a.out_v[o] = ov;
 }
@@ -68,8 +80,9 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_k)(GsStepArgs a)
 
 // The periodic rule (GsStepArgs::zero_halo = 2), literally: the nine taps of the zero-halo rule's interior cell, in its
 // order, with neighbour (r + i - 1, c + j - 1) read at ((r + i - 1) mod rows, (c + j - 1) mod cols).  A kernel of its own.
-template <bool MAP = false>
-__device__ __forceinline__ void simple_cell_periodic(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
+template <bool MAP = false, bool MASK = false>
+__device__ __forceinline__ void simple_cell_periodic(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
+                                                     const GsMaskPlanes &mk = GsMaskPlanes{nullptr})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -80,16 +93,21 @@ __device__ __forceinline__ void simple_cell_periodic(const GsStepArgs &a, const 
     const ptrdiff_t rows_at[3] = {(ptrdiff_t)(r > 0 ? r - 1 : a.rows - 1) * pitch, (ptrdiff_t)r * pitch,
                                   (ptrdiff_t)(r + 1 < a.rows ? r + 1 : 0) * pitch};
     const int cols_at[3] = {c > 0 ? c - 1 : a.cols - 1, c, c + 1 < a.cols ? c + 1 : 0};
+    constexpr bool NEU = false; // MASK: a wrapped neighbour's bit is that of its position
     const float u = a.in_u[rows_at[1] + c], v = a.in_v[rows_at[1] + c];
     float acc_u = 0.0f, acc_v = 0.0f;
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {
-            const float su = a.in_u[rows_at[i] + cols_at[j]], sv = a.in_v[rows_at[i] + cols_at[j]];
+            float su = a.in_u[rows_at[i] + cols_at[j]], sv = a.in_v[rows_at[i] + cols_at[j]];
+            // (the offset of the cell read, after the rule: a clamped row or column is the cell's own)
+            const int ri = rows_at[i] == rows_at[1] ? 1 : i, cj = cols_at[j] == c ? 1 : j;
+            if (MASK && !(ri == 1 && cj == 1) && simple_wall(mk, rows_at[1] + c, NEU ? ri * 3 + cj : i * 3 + j)) { su = u; sv = v; }
             GS_TAP(acc_u, a.w[i][j], su, u);
             GS_TAP(acc_v, a.w[i][j], sv, v);
         }
     float ou, ov;
     simple_react<MAP>(a, mp, rows_at[1] + c, u, v, acc_u, acc_v, ou, ov);
+    if (MASK && simple_wall(mk, rows_at[1] + c, kWallSelf)) { ou = u; ov = v; }
     a.out_u[rows_at[1] + c] = ou;
     a.out_v[rows_at[1] + c] = ov;
 }
@@ -98,8 +116,9 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_pk)(GsStepArgs a
 // The zero-flux (Neumann) rule (GsStepArgs::zero_halo = 3), literally: the nine taps of the zero-halo rule's interior cell,
 // in its order, with neighbour (r + i - 1, c + j - 1) read at the nearest cell of the grid -- rows clamped at the global
 // edges only (a slab seam reads its ghost row), columns at 0 and cols - 1.  A kernel of its own.
-template <bool MAP = false>
-__device__ __forceinline__ void simple_cell_neumann(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
+template <bool MAP = false, bool MASK = false>
+__device__ __forceinline__ void simple_cell_neumann(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
+                                                    const GsMaskPlanes &mk = GsMaskPlanes{nullptr})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -110,16 +129,21 @@ __device__ __forceinline__ void simple_cell_neumann(const GsStepArgs &a, const G
     const ptrdiff_t rows_at[3] = {(ptrdiff_t)(r > 0 || a.top_present ? r - 1 : r) * pitch, (ptrdiff_t)r * pitch,
                                   (ptrdiff_t)(r + 1 < a.rows || a.bottom_present ? r + 1 : r) * pitch};
     const int cols_at[3] = {c > 0 ? c - 1 : c, c, c + 1 < a.cols ? c + 1 : c};
+    constexpr bool NEU = true; // MASK: a clamped neighbour's bit is that of the cell read
     const float u = a.in_u[rows_at[1] + c], v = a.in_v[rows_at[1] + c];
     float acc_u = 0.0f, acc_v = 0.0f;
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) {
-            const float su = a.in_u[rows_at[i] + cols_at[j]], sv = a.in_v[rows_at[i] + cols_at[j]];
+            float su = a.in_u[rows_at[i] + cols_at[j]], sv = a.in_v[rows_at[i] + cols_at[j]];
+            // (the offset of the cell read, after the rule: a clamped row or column is the cell's own)
+            const int ri = rows_at[i] == rows_at[1] ? 1 : i, cj = cols_at[j] == c ? 1 : j;
+            if (MASK && !(ri == 1 && cj == 1) && simple_wall(mk, rows_at[1] + c, NEU ? ri * 3 + cj : i * 3 + j)) { su = u; sv = v; }
             GS_TAP(acc_u, a.w[i][j], su, u);
             GS_TAP(acc_v, a.w[i][j], sv, v);
         }
     float ou, ov;
     simple_react<MAP>(a, mp, rows_at[1] + c, u, v, acc_u, acc_v, ou, ov);
+    if (MASK && simple_wall(mk, rows_at[1] + c, kWallSelf)) { ou = u; ov = v; }
     a.out_u[rows_at[1] + c] = ou;
     a.out_v[rows_at[1] + c] = ov;
 }
@@ -134,16 +158,27 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_mk)(GsStepArgs a
     else if constexpr (RULE == 2) simple_cell_neumann<true>(a, mp);
     else simple_cell<true>(a, mp);
 }
+// ... and the domain mask's (the link plane of GsMaskPlanes), the replay check of masked runs.
+template <int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_wk)(GsStepArgs a, GsMaskPlanes mk)
+{
+    const GsMapPlanes none{nullptr, nullptr};
+    if constexpr (RULE == 1) simple_cell_periodic<false, true>(a, none, mk);
+    else if constexpr (RULE == 2) simple_cell_neumann<false, true>(a, none, mk);
+    else simple_cell<false, true>(a, none, mk);
+}
 
 // PER: a unit on an edge under the periodic rule (gs_step_stream_pk): rows and columns are read at their index modulo
 // the grid's (a lane whose four columns are not one aligned piece of a row after wrapping loads them one by one), and
 // every cell runs the interior code.  ZH: the boundary rule of the edge cells (cell<>; -1 = GsStepArgs::zero_halo, 3 = the
 // zero-flux rule of gs_step_stream_nk).  MAP: the parameter map's form (gs_step_stream_mk): a cell's rates are read at the
 // cell itself -- the rows of the unit, this lane's four columns, the addresses of its stores -- one group ahead, like
-// the rows of the species.
-template <int G, bool EDGE, bool PER = false, int ZH = -1, bool MAP = false>
+// the rows of the species.  MASK: the domain mask's form (gs_step_stream_wk): the link words of the cells, read like MAP's
+// rates (in mf), and every cell computed by cell_masked.
+template <int G, bool EDGE, bool PER = false, int ZH = -1, bool MAP = false, bool MASK = false>
 __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int c0, int lane,
-                                      const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
+                                      const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
+                                      const GsMaskPlanes &mkp = GsMaskPlanes{nullptr})
 {
     const int c = c0 + lane * 4;
     LaneCtx lc;
@@ -207,8 +242,12 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
         f = make_float4(0.f, 0.f, 0.f, 0.f);
         fk = f;
         if (lc.lane_ok) {
-            f = *reinterpret_cast<const float4 *>(mp.feed + o);
-            fk = *reinterpret_cast<const float4 *>(mp.fpk + o);
+            if constexpr (MASK) {
+                f = *reinterpret_cast<const float4 *>(mkp.link + o);
+            } else {
+                f = *reinterpret_cast<const float4 *>(mp.feed + o);
+                fk = *reinterpret_cast<const float4 *>(mp.fpk + o);
+            }
         }
     };
 
@@ -219,7 +258,7 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
     q[1] = widen(fetch(ur0));
 #pragma unroll
     for (int g = 0; g < G; ++g) n[g] = fetch(ur0 + 1 + g);
-    if constexpr (MAP) {
+    if constexpr (MAP || MASK) {
 #pragma unroll
         for (int g = 0; g < G; ++g) fetch_rates(ur0 + g, mf[g], mk[g]);
     }
@@ -250,10 +289,18 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
                 const bool prow = !EDGE || (row + 1 < a.rows) || a.bottom_present;
                 float4 nu, nv;
                 constexpr bool E = EDGE && !PER;
-                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x, mf[g].x, mk[g].x);
-                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y, mf[g].y, mk[g].y);
-                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z, mf[g].z, mk[g].z);
-                cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w, mf[g].w, mk[g].w);
+                if constexpr (MASK) {
+                    auto w = [](float x) { return __builtin_bit_cast(uint32_t, x); };
+                    cell_masked<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], w(mf[g].x), nu.x, nv.x);
+                    cell_masked<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], w(mf[g].y), nu.y, nv.y);
+                    cell_masked<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], w(mf[g].z), nu.z, nv.z);
+                    cell_masked<E, 0, RowW, ZH>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], w(mf[g].w), nu.w, nv.w);
+                } else {
+                    cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 1, mrow, prow, la[0], ra[0], nu.x, nv.x, mf[g].x, mk[g].x);
+                    cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y, mf[g].y, mk[g].y);
+                    cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z, mf[g].z, mk[g].z);
+                    cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w, mf[g].w, mk[g].w);
+                }
                 if (lc.lane_ok) {
                     *reinterpret_cast<float4 *>(ou) = nu;
                     *reinterpret_cast<float4 *>(ov) = nv;
@@ -264,7 +311,7 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
         }
         q[0] = q[G];
         q[1] = q[G + 1];
-        if constexpr (MAP) {
+        if constexpr (MAP || MASK) {
 #pragma unroll
             for (int g = 0; g < G; ++g) fetch_rates(r + G + g, mf[g], mk[g]);
         }
@@ -423,6 +470,47 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_mk)(GsStepArgs a
         march<G, true, false, 3, true>(a, ur0, ur1, c0, lane, mp);
     else
         march<G, true, false, -1, true>(a, ur0, ur1, c0, lane, mp);
+}
+
+// ... and the domain mask's (the link plane of GsMaskPlanes): the same units, every cell through cell_masked.
+template <int G, int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_wk)(GsStepArgs a, GsMaskPlanes mk)
+{
+    const GsMapPlanes none{nullptr, nullptr};
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strips = (a.cols + 255) >> 8;
+    int block = (int)blockIdx.x;
+    if (a.xcd_m > 0) { // XCD-aware order (GsStepArgs::xcd_m)
+        const int per = 8 * a.xcd_m, g = block / per, o = block - g * per;
+        if ((g + 1) * per <= (int)gridDim.x) block = g * per + (o & 7) * a.xcd_m + (o >> 3);
+    }
+    const int unit = block * 4 + wave;
+    const int chunk = unit / strips;
+    const int strip = unit - chunk * strips;
+    const int rpu = a.rows_per_unit;
+    const int chunks_a = (a.ra1 - a.ra0 + rpu - 1) / rpu;
+    const int chunks_b = (a.rb1 - a.rb0 + rpu - 1) / rpu;
+    if (chunk >= chunks_a + chunks_b) return; // wave-uniform
+    int ur0, ur1;
+    if (chunk < chunks_a) {
+        ur0 = a.ra0 + chunk * rpu;
+        ur1 = min(ur0 + rpu, a.ra1);
+    } else {
+        ur0 = a.rb0 + (chunk - chunks_a) * rpu;
+        ur1 = min(ur0 + rpu, a.rb1);
+    }
+    const int c0 = strip << 8;
+    const bool edge = (c0 == 0) || (c0 + 256 >= a.cols) || (ur0 == 0 && !a.top_present) ||
+                      (ur1 == a.rows && !a.bottom_present);
+    if (!edge)
+        march<G, false, false, -1, false, true>(a, ur0, ur1, c0, lane, none, mk);
+    else if constexpr (RULE == 1)
+        march<G, true, true, -1, false, true>(a, ur0, ur1, c0, lane, none, mk);
+    else if constexpr (RULE == 2)
+        march<G, true, false, 3, false, true>(a, ur0, ur1, c0, lane, none, mk);
+    else
+        march<G, true, false, -1, false, true>(a, ur0, ur1, c0, lane, none, mk);
 }
 
 // ------------------------------------------------------------------------------------

@@ -46,6 +46,10 @@
 //       marching kernel's map forms (K = 1..4, 1, 2 and 4 columns per lane, the general variant and, strict only, .op) are
 //       built in a translation unit of their own (GS_TB_MAP_ONLY).  The difference-sharing, fair-progress, tile, resident,
 //       window, LDS-staged and ensemble kernels have none.
+//   ..._wk<..., RULE>  the domain mask's forms (second argument GsMaskPlanes, gs_ctx_set_mask) of the same three kernels:
+//       every cell through cell_masked (a tap that reads a wall reads the cell's own value; a wall keeps its input), from
+//       the link words formed at attach time.  The marching forms, the same set as the map's, are built in a translation
+//       unit of their own (GS_TB_MASK_ONLY).  No difference sharing: a wall breaks it.
 //
 // This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
 // its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
@@ -78,6 +82,13 @@
 #if GS_TB_OP_ONLY && GS_TB_MAP_ONLY
 #error "GS_TB_OP_ONLY and GS_TB_MAP_ONLY are translation units of their own"
 #endif
+// GS_TB_MASK_ONLY=1: ... and the domain mask's forms (gs_step_tb_wk), through gs_tb_mask_kernel_<flavour>().
+#ifndef GS_TB_MASK_ONLY
+#define GS_TB_MASK_ONLY 0
+#endif
+#if GS_TB_MASK_ONLY && (GS_TB_OP_ONLY || GS_TB_MAP_ONLY)
+#error "GS_TB_MASK_ONLY is a translation unit of its own"
+#endif
 
 #if GS_MATH_FUSED
 #define GS_SUFFIX(x) x##_fused
@@ -91,7 +102,7 @@
 
 #include "gs_cell.h"
 #include "gs_march.h"
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
 #include "gs_single_step.h"
 #include "gs_lds_resident.h"
 #include "gs_ensemble.h"
@@ -111,7 +122,7 @@
 // periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
 static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
 
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
 // Opt-in for more than 64 KB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize).  The attribute
 // belongs to the device function ON THE CURRENT DEVICE, so what has been set is remembered per (device,
 // function): a process that drives several GPUs (device_ids = 0, 1, ...; two contexts) opts in on each.
@@ -160,16 +171,22 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 // ... and of the parameter map's kernel sets (the same rules, a "/map" suffix behind the rule's)
 #define GS_RULES_MAP(M, BASE) {M(BASE, "/map"), M(BASE, "/periodic/map"), M(BASE, "/neumann/map")}
 #define GS_NAME1(BASE, R) GS_NAME(BASE, "", R)
+// ... and of the domain mask's (a "/mask" suffix)
+#define GS_RULES_MASK(M, BASE) {M(BASE, "/mask"), M(BASE, "/periodic/mask"), M(BASE, "/neumann/mask")}
 // [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
 #define GS_TILE_NAMES(BASE, R) {GS_NAMES_OP(BASE "tile32x64", R), GS_NAMES_OP(BASE "tile16x64", R), GS_NAMES_OP(BASE "tile64x64", R)}
 #define GS_TILE_FNS(KER) {{GS_FN(KER, 2, 0), GS_FN(KER, 2, kOp)}, {GS_FN(KER, 1, 0), GS_FN(KER, 1, kOp)}, {GS_FN(KER, 4, 0), GS_FN(KER, 4, kOp)}}
 
-hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes)
+hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes,
+                                       const GsMaskPlanes *mask_planes)
 {
     const bool per = a.zero_halo == 2, neu = a.zero_halo == 3; // the periodic and zero-flux rules: kernels of their own
     const bool map = map_planes != nullptr;                    // the parameter map: gs_step_simple_mk
+    const bool mask = mask_planes != nullptr;                  // the domain mask: gs_step_simple_wk
     static const char *const map_names[3] = GS_RULES_MAP(GS_NAME1, "simple");
-    if (name) *name = map ? map_names[rule_set(a.zero_halo)]
+    static const char *const mask_names[3] = GS_RULES_MASK(GS_NAME1, "simple");
+    if (map && mask) return hipErrorInvalidValue;
+    if (name) *name = map ? map_names[rule_set(a.zero_halo)] : mask ? mask_names[rule_set(a.zero_halo)]
                           : per ? "simple/" GS_MATH_NAME "/periodic" : (neu ? "simple/" GS_MATH_NAME "/neumann" : "simple/" GS_MATH_NAME);
     const long nrows = (long)(a.ra1 - a.ra0) + (a.rb1 - a.rb0);
     if (nrows <= 0 || a.cols <= 0) return hipSuccess;
@@ -184,6 +201,13 @@ hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const
         GsMapPlanes mp = *map_planes;
         if (!mp.feed || !mp.fpk) return hipErrorInvalidValue;
         void *margs[] = {&args, &mp};
+        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
+    }
+    if (mask) {
+        static const void *const fns[3] = {GS_FN(gs_step_simple_wk, 0), GS_FN(gs_step_simple_wk, 1), GS_FN(gs_step_simple_wk, 2)};
+        GsMaskPlanes mk = *mask_planes;
+        if (!mk.link) return hipErrorInvalidValue;
+        void *margs[] = {&args, &mk};
         return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
     }
     return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_pk))
@@ -366,13 +390,17 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
     return hipLaunchKernel(fn, dim3((unsigned)x.n_windows), dim3(kWinWaves * 64), kargs, lds, s);
 }
 
-hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes)
+hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes,
+                                       const GsMaskPlanes *mask_planes)
 {
     const bool per = a.zero_halo == 2; // the periodic rule: gs_step_stream_pk (single slab)
     const bool neu = a.zero_halo == 3; // the zero-flux rule: gs_step_stream_nk
     const bool map = map_planes != nullptr; // the parameter map: gs_step_stream_mk
+    const bool mask = mask_planes != nullptr; // the domain mask: gs_step_stream_wk
     static const char *const map_names[3] = GS_RULES_MAP(GS_NAME1, "stream-g2");
-    if (name) *name = map ? map_names[rule_set(a.zero_halo)]
+    static const char *const mask_names[3] = GS_RULES_MASK(GS_NAME1, "stream-g2");
+    if ((map && mask) || (mask && !mask_planes->link)) return hipErrorInvalidValue;
+    if (name) *name = map ? map_names[rule_set(a.zero_halo)] : mask ? mask_names[rule_set(a.zero_halo)]
                           : per ? "stream-g2/" GS_MATH_NAME "/periodic" : (neu ? "stream-g2/" GS_MATH_NAME "/neumann" : "stream-g2/" GS_MATH_NAME);
     if (map && (!map_planes->feed || !map_planes->fpk)) return hipErrorInvalidValue;
     if (a.cols <= 0 || a.rows_per_unit <= 0 || (per && (a.top_present || a.bottom_present))) return hipErrorInvalidValue;
@@ -394,6 +422,12 @@ hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const
         static const void *const fns[3] = {GS_FN(gs_step_stream_mk, 2, 0), GS_FN(gs_step_stream_mk, 2, 1), GS_FN(gs_step_stream_mk, 2, 2)};
         GsMapPlanes mp = *map_planes;
         void *margs[] = {&args, &mp};
+        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
+    }
+    if (mask) {
+        static const void *const fns[3] = {GS_FN(gs_step_stream_wk, 2, 0), GS_FN(gs_step_stream_wk, 2, 1), GS_FN(gs_step_stream_wk, 2, 2)};
+        GsMaskPlanes mk = *mask_planes;
+        void *margs[] = {&args, &mk};
         return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
     }
     return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_pk)<2>)
@@ -484,17 +518,25 @@ static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, int per 
 // The parameter map's variant for GsStepArgs::fast = `fast`: .op (3) where the side weights are 0.5 and dt == 1 in the
 // strict flavour, else the general one.
 static int tb_map_fast(int fast) { return !GS_MATH_FUSED && (fast & 3) == 3 ? 3 : 0; }
+// ... and the domain mask's, where its .op form is built (gs_tb_mask_kernel_*), else the general one
+static int tb_mask_fast(int fast, int k, int cpl, int rule)
+{
+    const int f = tb_map_fast(fast);
+    return f && !GS_SUFFIX(gs_tb_mask_kernel)(k, f, cpl, rule) ? 0 : f;
+}
 
-int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, bool map)
+int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, bool map, bool mask)
 {
     if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4)) return 0;
     const int per = rule_set(boundary);
-    const void *fn = map ? GS_SUFFIX(gs_tb_map_kernel)(k, tb_map_fast(fast), cpl, per)
-                         : tb_entry(k, tb_reduce_fast(fast, k, cpl, 4, per), cpl, 4, per);
+    const void *fn = map    ? GS_SUFFIX(gs_tb_map_kernel)(k, tb_map_fast(fast), cpl, per)
+                     : mask ? GS_SUFFIX(gs_tb_mask_kernel)(k, tb_mask_fast(fast, k, cpl, per), cpl, per)
+                            : tb_entry(k, tb_reduce_fast(fast, k, cpl, 4, per), cpl, 4, per);
     return fn ? 1024 * tb_waves_of(fn) : 0;
 }
 
-hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map_planes)
+hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map_planes,
+                                   const GsMaskPlanes *mask_planes)
 {
     // "cN": N columns per lane (4 = the wide layout); ".op": the variant specialised for the
     // default (Oono-Puri) side weights, with or without dt == 1
@@ -509,6 +551,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     static const char *const names[3][3][4][4] = GS_RULES(GS_TB_LAYOUTS, "tb-k");    // [rule][cpl 1, 2, 4][variant][k - 1]
     static const char *const names16[3][2][4] = GS_RULES(GS_TB16_LAYOUTS, "tb-k4");  // [rule][cpl 1, 2][variant]
     static const char *const names_map[3][3][4][4] = GS_RULES_MAP(GS_TB_LAYOUTS, "tb-k"); // the parameter map's kernels (gs_step_tb_mk)
+    static const char *const names_mask[3][3][4][4] = GS_RULES_MASK(GS_TB_LAYOUTS, "tb-k"); // the domain mask's (gs_step_tb_wk)
 #undef GS_TB16_LAYOUTS
 #undef GS_TB_VARIANTS
 #undef GS_TB_LAYOUTS
@@ -525,14 +568,19 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // the parameter map (map_planes): its own kernels, the general or the .op variant, 4-wave workgroups only
     const bool map = map_planes != nullptr;
     if (map && (!map_planes->feed || !map_planes->fpk)) return hipErrorInvalidValue;
-    const int fast = map ? tb_map_fast(a.fast) : tb_reduce_fast(a.fast, k, cpl, 4, per);
-    if (name) *name = (map ? names_map : names)[per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
+    // the domain mask (mask_planes): likewise, kernels of its own
+    const bool mask = mask_planes != nullptr;
+    if ((map && mask) || (mask && !mask_planes->link)) return hipErrorInvalidValue;
+    const int fast = map ? tb_map_fast(a.fast) : mask ? tb_mask_fast(a.fast, k, cpl, per) : tb_reduce_fast(a.fast, k, cpl, 4, per);
+    if (name) *name = (map ? names_map : mask ? names_mask : names)[per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
     const long rpu = a.rows_per_unit;
     const long rows_a = (long)a.ra1 - a.ra0;
     const long W = tb_cols_per_wave(k, cpl);
     const long strips = (a.cols + W - 1) / W;
     // Kernel entry first: the taper below needs its occupancy.
-    const void *fn = map ? GS_SUFFIX(gs_tb_map_kernel)(k, fast, cpl, per) : tb_entry(k, fast, cpl, 4, per);
+    const void *fn = map    ? GS_SUFFIX(gs_tb_map_kernel)(k, fast, cpl, per)
+                     : mask ? GS_SUFFIX(gs_tb_mask_kernel)(k, fast, cpl, per)
+                            : tb_entry(k, fast, cpl, 4, per);
     if (!fn) return hipErrorInvalidValue;
     const int waves = tb_waves_of(fn);
     // Tapered tail (consecutive passes are dependent launches that cannot overlap, so the drain phase
@@ -614,7 +662,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // 2 columns per lane, 10 rows 523 k / 537 k, 15 rows 615 k / 633 k, 19 rows 687 k / 738 k, 38 rows 782 k / 865 k.
     // GS_HIP_FAIR = 0 / 1 forces it off / on.
     static const int fair_env = gs_env_int("GS_HIP_FAIR", -1, 0, 1);
-    const bool fair = !map && a.allow_fair && units <= 4096 && units > 1024 && (fair_env < 0 ? (cpl == 2 || rpu >= 20) : fair_env != 0);
+    const bool fair = !map && !mask && a.allow_fair && units <= 4096 && units > 1024 && (fair_env < 0 ? (cpl == 2 || rpu >= 20) : fair_env != 0);
     const int fast16 = fair ? tb_reduce_fast(a.fast, k, cpl, 16, per) : 0;
     const void *fair_fn = fair ? tb_entry(k, fast16, cpl, 16, per) : nullptr;
     static const int fair_from_env = gs_env_int("GS_HIP_FAIR_FROM", -1, 0, 256);
@@ -641,6 +689,11 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     if (map) {
         GsMapPlanes mp = *map_planes;
         void *margs[] = {&args, &mp};
+        return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), margs, 0, s);
+    }
+    if (mask) {
+        GsMaskPlanes mk = *mask_planes;
+        void *margs[] = {&args, &mk};
         return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), margs, 0, s);
     }
     return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, 0, s);
@@ -685,16 +738,16 @@ hipError_t GS_SUFFIX(gs_launch_map_rates)(const float *feed, const float *kill, 
     return hipGetLastError();
 }
 #undef GS_MAP_RATES_K
-#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
+#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
 
-#if defined(GS_WIN_TRACE) && !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY
+#if defined(GS_WIN_TRACE) && !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
 extern "C" int32_t GS_SUFFIX(gs_debug_win_trace_read)(unsigned long long *dst)
 {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(gs_win_trace), sizeof(unsigned long long) * 1024 * 8 * 8) == hipSuccess ? 0 : -1;
 }
 #endif
 
-#if defined(GS_TB_TRACE) && !GS_TB_MAP_ONLY
+#if defined(GS_TB_TRACE) && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
 // Copies the trace buffer of THIS translation unit's kernels out (diagnostic builds only).
 #if GS_TB_OP_ONLY
 extern "C" int32_t gs_debug_trace_read_op(unsigned long long *dst, int32_t units, int32_t clear)
@@ -784,6 +837,35 @@ const void *GS_SUFFIX(gs_tb_map_kernel)(int k, int fast, int cpl, int rule)
 #undef GS_MAP_RULES
 #undef GS_MAP_CPLS
 #undef GS_MAP_KS
+    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || rule < 0 || rule > 2) return nullptr;
+    const int c = cpl == 4 ? 2 : cpl - 1;
+    if (fast == 0) return general[rule][c][k - 1];
+#if !GS_MATH_FUSED
+    if (fast == 3) return op[rule][c][k - 1];
+#endif
+    return nullptr;
+}
+#endif
+
+#if GS_TB_MASK_ONLY
+// Kernel entry of the marching kernel's domain-mask form (gs_kernels.h: gs_tb_mask_kernel_*), the parameters of
+// gs_tb_map_kernel_*.  Not built: the .op form of the clipped and zero-halo rules' kernels with 4 columns per lane and 3 or
+// 4 fused steps -- the selects of their left and right edge cells on top of the masks' keep a stack frame in scratch;
+// gs_launch_tb runs the general form there.
+const void *GS_SUFFIX(gs_tb_mask_kernel)(int k, int fast, int cpl, int rule)
+{
+#define GS_MASK_KS(F, C, R) {GS_FN(gs_step_tb_wk, 1, F, C, R), GS_FN(gs_step_tb_wk, 2, F, C, R), GS_FN(gs_step_tb_wk, 3, F, C, R), GS_FN(gs_step_tb_wk, 4, F, C, R)}
+#define GS_MASK_CPLS(F, R) {GS_MASK_KS(F, 1, R), GS_MASK_KS(F, 2, R), GS_MASK_KS(F, 4, R)}
+#define GS_MASK_RULES(F) {GS_MASK_CPLS(F, 0), GS_MASK_CPLS(F, 1), GS_MASK_CPLS(F, 2)}
+    static const void *const general[3][3][4] = GS_MASK_RULES(0); // [rule][cpl 1, 2, 4][k - 1]
+#if !GS_MATH_FUSED
+    static const void *const op[3][3][4] = {
+        {GS_MASK_KS(3, 1, 0), GS_MASK_KS(3, 2, 0), {GS_FN(gs_step_tb_wk, 1, 3, 4, 0), GS_FN(gs_step_tb_wk, 2, 3, 4, 0), nullptr, nullptr}},
+        GS_MASK_CPLS(3, 1), GS_MASK_CPLS(3, 2)};
+#endif
+#undef GS_MASK_RULES
+#undef GS_MASK_CPLS
+#undef GS_MASK_KS
     if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || rule < 0 || rule > 2) return nullptr;
     const int c = cpl == 4 ? 2 : cpl - 1;
     if (fast == 0) return general[rule][c][k - 1];

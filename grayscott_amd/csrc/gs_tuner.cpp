@@ -43,7 +43,7 @@ static int fast_possible(const gs_ctx *ctx)
 int fast_of(const gs_ctx *ctx)
 {
     const int fast = fast_possible(ctx), mode = share_mode(ctx);
-    if (!(fast & 4) || mode == 0 || ctx->mapped()) return fast & 3; // (the parameter map's kernels share no differences)
+    if (!(fast & 4) || mode == 0 || ctx->mapped() || ctx->masked()) return fast & 3; // (the map's and the mask's kernels share no differences)
     return mode == 2 ? fast | 8 : fast;
 }
 
@@ -56,8 +56,8 @@ int fast_of(const gs_ctx *ctx)
 // Writes up to `max` heights (the single-round one first); returns their number.
 int fit_heights(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse, int cpl, int fast, int *out, int max, bool partial)
 {
-    const int slots = ctx->o.math == GS_MATH_FUSED ? gs_tb_wave_slots_fused(fuse, fast, cpl, ctx->o.boundary, ctx->mapped())
-                                                     : gs_tb_wave_slots_strict(fuse, fast, cpl, ctx->o.boundary, ctx->mapped());
+    const int slots = ctx->o.math == GS_MATH_FUSED ? gs_tb_wave_slots_fused(fuse, fast, cpl, ctx->o.boundary, ctx->mapped(), ctx->masked())
+                                                     : gs_tb_wave_slots_strict(fuse, fast, cpl, ctx->o.boundary, ctx->mapped(), ctx->masked());
     const long strips = tb_strips(cols, fuse, cpl);
     if (slots <= 0 || strips <= 0) return 0;
     const long per_round = slots / strips; // chunks per round
@@ -315,7 +315,7 @@ int32_t tune_online(Run &r, int fuse)
     // it wins and 3-5 % behind on every developed pattern once the power cap has set the clock -- which a timing window of
     // a few passes on a chip that was idle a moment ago does not show (at 4096^2 the windows preferred it on every input
     // and the run then lost 5 %, profiles/r05_cross_lane.md, section 3).
-    const bool share_open = ctx->o.share_taps == 0 && (fast_possible(ctx) & 4) != 0 && !ctx->mapped();
+    const bool share_open = ctx->o.share_taps == 0 && (fast_possible(ctx) & 4) != 0 && !ctx->mapped() && !ctx->masked();
     const int ne = share_open ? 1 : 0;
     // timed passes per candidate: short passes need more of them for a stable comparison
     const int reps = cells >= (1ull << 27) ? 2 : (cells >= (1ull << 24) ? 6 : 8);
@@ -533,7 +533,7 @@ int32_t gs_ctx_get_tuned(const gs_ctx *ctx, uint64_t slab_rows, uint64_t cols, i
             rpu = t.rpu; k = t.k; cpl = t.cpl;
             // the EFFECTIVE form: only 2 columns per lane with 2 to 4 fused steps, strict math and a stencil whose diagonal
             // weights pair up have a sharing variant -- everything else runs without, whatever the entry carries
-            const bool has_variant = t.cpl == 2 && t.k >= 2 && (fast_possible(ctx) & 4) && !ctx->mapped();
+            const bool has_variant = t.cpl == 2 && t.k >= 2 && (fast_possible(ctx) & 4) && !ctx->mapped() && !ctx->masked();
             share = !has_variant ? 2 : (t.share == 1 ? 1 : (t.share ? 3 : 2));
         }
     if (rows_per_block) *rows_per_block = rpu;

@@ -146,3 +146,50 @@ hipError_t gs_launch_fill_rect(float *row0, int32_t pitch, int32_t r0, int32_t r
     }
     return hipSuccess;
 }
+
+// Link words of a domain mask (gs_ctx_set_mask; the bits of gs_cell.h: link_bit): bit (i * 3 + j) when the cell at
+// (r + i - 1, c + j - 1) is a wall, bit 9 when (r, c) is.  A wall is a mask value != 0.0f (NaN included, +-0 is fluid).
+// A neighbour outside the slab's rows is its ghost row where a slab lies above / below (`top` / `bottom`); outside the
+// grid it wraps under the periodic rule and is no wall under the others -- the clipped, zero-halo and zero-flux edge
+// cells never read that position, or read one the word already covers (the zero-flux rule's clamped neighbour).
+namespace {
+__global__ __launch_bounds__(256) void gs_mask_links_k(const float *mask, uint32_t *link, int pitch, int rows, int cols,
+                                                       int top, int bottom, int periodic)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= cols) return;
+    for (int r = blockIdx.y; r < rows; r += gridDim.y) {
+        uint32_t w = mask[(ptrdiff_t)r * pitch + c] != 0.0f ? 1u << 9 : 0u;
+        for (int i = 0; i < 3; ++i) {
+            int rr = r + i - 1;
+            if (rr < 0 && !top) {
+                if (!periodic) continue;
+                rr += rows;
+            }
+            if (rr >= rows && !bottom) {
+                if (!periodic) continue;
+                rr -= rows;
+            }
+            for (int j = 0; j < 3; ++j) {
+                if (i == 1 && j == 1) continue;
+                int cc = c + j - 1;
+                if (cc < 0 || cc >= cols) {
+                    if (!periodic) continue;
+                    cc = cc < 0 ? cc + cols : cc - cols;
+                }
+                if (mask[(ptrdiff_t)rr * pitch + cc] != 0.0f) w |= 1u << (i * 3 + j);
+            }
+        }
+        link[(ptrdiff_t)r * pitch + c] = w;
+    }
+}
+} // namespace
+
+hipError_t gs_launch_mask_links(const float *mask, uint32_t *link, int32_t pitch, int32_t rows, int32_t cols, int32_t top,
+                                int32_t bottom, int32_t periodic, hipStream_t s)
+{
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((cols + 255) / 256), (unsigned)(rows < 65535 ? rows : 65535));
+    void *kargs[] = {&mask, &link, &pitch, &rows, &cols, &top, &bottom, &periodic};
+    return hipLaunchKernel(reinterpret_cast<const void *>(&gs_mask_links_k), grid, dim3(256), kargs, 0, s);
+}

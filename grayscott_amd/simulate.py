@@ -19,6 +19,10 @@ takes arrays ``feed`` and ``kill`` of the grid's shape.  The linear value of ind
 ``np.float32(a + (b - a) * i / (n - 1))`` computed in float64, a single row or column taking ``a``; a rate without a
 map option is the uniform ``-f`` / ``-k`` value.  The output keeps the reference's format; the map's definition goes
 into a JSON sidecar, ``-o``'s name with ``.param_map.json``.
+
+Domain masks (``gs_ctx_set_mask``): ``--hip-mask FILE.npy`` (or ``FILE.npz`` with an array ``mask``) of the grid's shape
+makes the cells where it is nonzero walls.  It combines with every other option but the parameter map's, which it
+refuses.
 """
 from __future__ import annotations
 
@@ -49,6 +53,7 @@ def parse(argv=None):
     ap.add_argument("--output-buffer", type=int, default=2)              # main.rs:37-43
     add_backend_args(ap)
     add_param_map_args(ap)
+    add_mask_args(ap)
     return ap.parse_args(argv)
 
 
@@ -82,6 +87,33 @@ def add_param_map_args(ap: argparse.ArgumentParser) -> None:
     pm.add_argument("--hip-feed-map", default=None, metavar="F0:F1", help="feed rate varying linearly along the rows, F0 on the first, F1 on the last")
     pm.add_argument("--hip-kill-map", default=None, metavar="K0:K1", help="kill rate varying linearly along the columns, K0 on the first, K1 on the last")
     pm.add_argument("--hip-param-map", default=None, metavar="FILE.npz", help="arrays `feed` and `kill` of the grid's shape")
+
+
+def add_mask_args(ap: argparse.ArgumentParser) -> None:
+    """The domain mask's option of the ``--hip-*`` group (simulate only)."""
+    mk = ap.add_argument_group("HIP backend: domain mask")
+    mk.add_argument("--hip-mask", default=None, metavar="FILE.npy",
+                    help="walls where the array (.npy, or array `mask` of a .npz) is nonzero; not with a parameter map")
+
+
+def domain_mask(args, shape):
+    """The wall array ``--hip-mask`` asks for (any dtype, the grid's shape), or None."""
+    path = getattr(args, "hip_mask", None)
+    if path is None:
+        return None
+    if any(getattr(args, n, None) is not None for n in ("hip_feed_map", "hip_kill_map", "hip_param_map")):
+        raise ValueError("--hip-mask excludes --hip-feed-map, --hip-kill-map and --hip-param-map "
+                         "(a domain mask and a parameter map cannot be attached together)")
+    if path.lower().endswith(".npz"):
+        with np.load(path) as z:
+            if "mask" not in z:
+                raise ValueError(f"{path}: no array `mask`")
+            mask = np.asarray(z["mask"])
+    else:
+        mask = np.load(path)
+    if mask.shape != tuple(shape):
+        raise ValueError(f"{path}: the mask is {mask.shape}, the grid is {tuple(shape)}")
+    return mask
 
 
 def linear_values(a: float, b: float, n: int) -> np.ndarray:
@@ -172,6 +204,7 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
         raise ValueError("--output-buffer must be at least 1")
     params = simulation_parameters(args)
     pmap = param_map(args, shape, params)
+    mask = domain_mask(args, shape)
     sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)
     ctx = sim.context
@@ -180,6 +213,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
         if getattr(args, "rank", 0) == 0:
             with open(sidecar_path(args.output), "w") as f:
                 json.dump(pmap[2], f, indent=1)
+    if mask is not None:
+        sim.set_mask(mask)
     if out is None and args.output.lower().endswith((".h5", ".hdf5")):
         out = hdf5_min.create(args.output, (args.nbimage,) + shape)       # dataset "matrix" (hdf5.rs:24)
     elif out is None:

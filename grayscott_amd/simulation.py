@@ -752,6 +752,35 @@ class Simulation:
         """Detach the parameter map: the steps take ``params.feed`` / ``params.kill`` again."""
         capi.check(self.context._lib.gs_ctx_set_param_map(self.context.handle, None, None))
 
+    def set_mask(self, mask, shape: Optional[Sequence[int]] = None) -> None:
+        """Attach a domain mask (``gs_ctx_set_mask``): from now on the cells where ``mask`` is nonzero (NaN included) are
+        walls -- they keep their values, and a tap of a fluid cell that reads a wall reads the cell's own value instead.
+        ``mask`` is a global ``[rows, cols]`` array of any dtype, or a scalar (a uniform plane; ``shape`` is then needed);
+        each process uploads only its own rows.  The library copies it, so the array may change afterwards; a new call
+        replaces the mask.  Collective in a multi-process run.  The species stepped while it is attached must have its
+        shape."""
+        if np.ndim(mask) == 0:
+            if shape is None:
+                raise ValueError("a scalar mask needs its shape")
+            rows, cols = int(shape[0]), int(shape[1])
+            walls = np.full((rows, cols), 1.0 if mask != 0 else 0.0, np.float32)
+        else:
+            walls = (np.asarray(mask) != 0).astype(np.float32)
+            if walls.ndim != 2 or (shape is not None and walls.shape != (int(shape[0]), int(shape[1]))):
+                raise ValueError(f"mask of shape {walls.shape}, species of {tuple(shape) if shape is not None else '?'}")
+            rows, cols = walls.shape
+        c = HipConcentration(self.context, (rows, cols))
+        try:
+            r0, r1 = c.local_rows()
+            c.upload(self.context, np.ascontiguousarray(walls[r0:r1]))
+            capi.check(self.context._lib.gs_ctx_set_mask(self.context.handle, c.handle))
+        finally:
+            c.destroy()
+
+    def clear_mask(self) -> None:
+        """Detach the domain mask: every cell is fluid again."""
+        capi.check(self.context._lib.gs_ctx_set_mask(self.context.handle, None))
+
     def perform_step(self, species: Species) -> None:
         """One ``gs_step`` then ``species.flip()`` -- the ``SimulateStep`` form (cpu.rs:21-42)."""
         in_u, in_v, out_u, out_v = species.in_out()

@@ -460,6 +460,18 @@ class Simulation {
         check(gs_ctx_set_param_map(context_->get(), f.raw(), k.raw()));
     }
     void clear_param_map() const { check(gs_ctx_set_param_map(context_->get(), nullptr, nullptr)); }
+    // Domain mask (gs_ctx_set_mask): a dense row-major [rows, cols] array of the GLOBAL grid, nonzero (NaN included) =
+    // wall (each process uploads its own rows); the library copies it.  clear_mask() detaches it.
+    void set_mask(Shape shape, const float *mask) const
+    {
+        Context c = context_;
+        HipConcentration m = HipConcentration::zeros(c, shape);
+        uint64_t r0 = 0, r1 = 0;
+        check(gs_field_local_rows(m.raw(), &r0, &r1));
+        check(gs_field_upload(context_->get(), m.raw(), mask + r0 * shape[1]));
+        check(gs_ctx_set_mask(context_->get(), m.raw()));
+    }
+    void clear_mask() const { check(gs_ctx_set_mask(context_->get(), nullptr)); }
     const Context &context() const { return context_; }
     // an Ensemble of params.size() members (Species::new's pattern in each)
     Ensemble make_ensemble(Shape shape, const std::vector<Parameters> &params) const

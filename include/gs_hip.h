@@ -266,6 +266,31 @@ int32_t gs_ctx_set_params(gs_ctx *ctx, const gs_params *params);
  * own per-member parameters and ignore the map. */
 int32_t gs_ctx_set_param_map(gs_ctx *ctx, gs_field *feed, gs_field *kill);
 
+/* Domain mask: wall cells that are not part of the medium (obstacles, channels, mazes, patterns grown inside a shape).
+ * Cell (r, c) is a wall when M[r, c] != 0.0f -- NaN is a wall, +-0 is fluid.  While a mask is attached, every step of
+ * gs_step / gs_run is the reference step with two changes:
+ *   1. a wall cell is held: its outputs are its inputs bit for bit, NaN payloads included (in fused passes at every level);
+ *   2. each tap of a fluid cell reads one cell of the window as the boundary rule resolves it (the clipped rule's clipped
+ *      and shifted window, the zero-halo rule's 0 outside the grid -- never a wall --, the periodic rule's wrapped cell,
+ *      the zero-flux rule's clamped cell); where that cell is a wall the tap reads the centre cell's own u / v instead,
+ *      so its difference is u - u.  The taps, their order and every rounding stay the reference's.
+ * So no flux crosses a link into a wall, a wall's stored values never reach another cell, and with F = k = 0 under the
+ * zero-flux rule the sum of U + V over the fluid cells is conserved up to rounding.  An all-fluid mask changes no bit; the
+ * arithmetic contract of gs_math is unchanged.
+ *   mask : an ordinary field of this context with the species' global shape (in a multi-process run each process uploads
+ *          its own rows).  The call COPIES it: the library forms a plane of its own, one word per cell naming the walls
+ *          among the cell's neighbours under the context's boundary rule, and fills its ghost rows once; the caller may
+ *          change or destroy its field afterwards.  NULL detaches the mask; a second call replaces it.
+ * The call waits for enqueued work; in a multi-process run it is collective.  gs_step / gs_run on species of another
+ * shape than the mask's: GS_ERR_INVALID.  A context whose pinned kernel has no mask form (GS_KERNEL_WINDOW, _LDS, _TILE),
+ * or one with a parameter map attached: GS_ERR_UNSUPPORTED (gs_ctx_set_param_map likewise refuses a masked context).
+ * With a mask, gs_run runs the marching kernel at every grid size (never the resident, tile or window kernel), gs_step the
+ * streaming one and a pinned GS_KERNEL_SIMPLE the simple one; their mask forms carry a "/mask" suffix in gs_ctx_info (e.g.
+ * "tb-k4c2/strict.op/mask", "tb-k4c1/strict/periodic/mask") and share no differences (no ".ds" / ".dx").  Graph replay and
+ * the on-line tuner keep masked runs apart from uniform and mapped ones: gs_ctx_get_tuned / gs_ctx_set_tuned act on the
+ * choices of the kernel set in force.  Ensembles ignore the mask; summaries include wall cells. */
+int32_t gs_ctx_set_mask(gs_ctx *ctx, gs_field *mask);
+
 /* Concentration::default / zeros / ones (concentration/mod.rs:205-218) = create (+ fill).
  * `rows`, `cols` are the GLOBAL shape; every process passes the same values. */
 int32_t gs_field_create(gs_ctx *ctx, gs_field **out, uint64_t rows, uint64_t cols);

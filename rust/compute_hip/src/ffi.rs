@@ -78,6 +78,7 @@ extern "C" {
     ) -> i32;
     pub fn gs_ctx_destroy(ctx: *mut gs_ctx) -> i32;
     pub fn gs_ctx_set_param_map(ctx: *mut gs_ctx, feed: *mut gs_field, kill: *mut gs_field) -> i32;
+    pub fn gs_ctx_set_mask(ctx: *mut gs_ctx, mask: *mut gs_field) -> i32;
     pub fn gs_field_create(ctx: *mut gs_ctx, out: *mut *mut gs_field, rows: u64, cols: u64) -> i32;
     pub fn gs_field_destroy(ctx: *mut gs_ctx, f: *mut gs_field) -> i32;
     pub fn gs_field_raw_shape(f: *const gs_field, raw_rows: *mut u64, pitch: *mut u64) -> i32;
