@@ -48,6 +48,8 @@ UNITS = [
     ("gs_util_kernels.hip", "gs_util.o", []),
     # summaries of planes (row records, the ensembles' fold): hipcc's default float mode, sub-normal cells kept
     ("gs_summary.hip", "gs_summary_k.o", []),
+    # reduced result images (block averages in f64): the same float mode, a sub-normal pixel is kept
+    ("gs_reduce.hip", "gs_reduce_k.o", []),
     # the host side (contexts and schedule, planes, kernel configuration, the window kernel's runtime, RCCL): only the
     # C ABI of include/gs_hip.h is visible outside the library
     ("gs_api.cpp", "gs_api.o", ["-x", "hip", "-fvisibility=hidden"]),

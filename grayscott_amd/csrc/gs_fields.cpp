@@ -474,9 +474,53 @@ int32_t gs_host_free(void *p)
     return GS_OK;
 }
 
-int32_t gs_field_download_async(gs_ctx *ctx, gs_field *f, float *host)
+} // extern "C"
+
+namespace {
+
+// The reduced image of include/gs_hip.h: global shape, this process's rows of it, and the verdict on the slabs.
+struct ReducedShape {
+    uint64_t rows = 0, cols = 0, row0 = 0, row1 = 0;
+};
+
+int32_t reduced_shape(const gs_field *f, int32_t factor, ReducedShape *out)
 {
-    if (!ctx || !f || f->ctx != ctx) return fail(GS_ERR_INVALID, "bad argument");
+    if (!f || !f->ctx || f->s.empty()) return fail(GS_ERR_INVALID, "null field");
+    if (factor < 1 || factor > 64) return fail(GS_ERR_INVALID, "a reduction factor is 1 to 64, not %d", factor);
+    const uint64_t q = (uint64_t)factor, S = (uint64_t)f->ctx->total_slabs();
+    // every slab of the global grid, other processes' too (the split of gs_field_create): every rank reaches the same verdict
+    for (uint64_t k = 1; k < S; ++k)
+        if ((k * f->rows / S) % q != 0)
+            return fail(GS_ERR_UNSUPPORTED, "slab %llu begins at row %llu, which is not a multiple of the reduction factor %d "
+                                            "(a block of a reduced image may not straddle two slabs)",
+                        (unsigned long long)k, (unsigned long long)(k * f->rows / S), factor);
+    const uint64_t first = f->s.front().g_row0, last = f->s.back().g_row0 + (uint64_t)f->s.back().rows;
+    out->rows = (f->rows + q - 1) / q;
+    out->cols = (f->cols + q - 1) / q;
+    out->row0 = first / q;
+    out->row1 = (last + q - 1) / q;
+    return GS_OK;
+}
+
+// Staging buffer k of a slab, at least `need` floats (the image that last used it has left it or is waited for here).
+int32_t ensure_stage(SlabRt &sl, int k, size_t need)
+{
+    if (sl.stage_floats[k] >= need) return GS_OK;
+    GS_HIP(hipStreamSynchronize(sl.image_stream(k)));
+    if (sl.stage[k]) GS_HIP(hipFree(sl.stage[k]));
+    sl.stage[k] = nullptr;
+    sl.stage_floats[k] = 0;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&sl.stage[k]), need * sizeof(float));
+    if (e != hipSuccess) return fail(GS_ERR_NOMEM, "staging buffer: %s", hipGetErrorString(e));
+    sl.stage_floats[k] = need;
+    return GS_OK;
+}
+
+// gs_field_download_async and gs_field_download_reduced_async: the image of `f` reduced by `factor` (1: the plane itself,
+// staged by gs_pack_rows_k; more: by gs_launch_reduce) enqueued behind the work already enqueued.  The caller has checked
+// the handles, the factor and the slabs.
+int32_t enqueue_image(gs_ctx *ctx, gs_field *f, int32_t factor, float *host)
+{
     if (f->rows == 0 || f->cols == 0) return GS_OK; // nothing to copy (host may be null)
     if (!host) return fail(GS_ERR_INVALID, "bad argument");
     // A persistent window launch in flight may still give up (its workgroups not all resident): the copy is enqueued
@@ -489,44 +533,144 @@ int32_t gs_field_download_async(gs_ctx *ctx, gs_field *f, float *host)
             GS_HIP(hipHostMalloc(reinterpret_cast<void **>(&w.seen), 2 * sizeof(int32_t), hipHostMallocDefault));
             w.seen[0] = w.seen[1] = 0;
         }
-        w.images.push_back(gs_ctx::WindowRt::Image{f, host, w.seq});
+        w.images.push_back(gs_ctx::WindowRt::Image{f, host, w.seq, factor});
     }
-    const uint64_t first = f->s.front().g_row0;
+    const uint64_t q = (uint64_t)factor;
+    const uint64_t ocols = (f->cols + q - 1) / q; // (factor 1: the plane's own rows and columns)
+    const uint64_t first = f->s.front().g_row0 / q;
     const int last = (int)((ctx->step_no + 1) & 1); // parity of the most recent pass
     const int k = (int)(ctx->downloads & 1);        // the staging buffer of this image
     for (size_t i = 0; i < f->s.size(); ++i) {
         SlabRt &sl = ctx->slabs[i];
         const FieldSlab &fs = f->s[i];
         GS_HIP(hipSetDevice(sl.device));
-        const size_t need = (size_t)fs.rows * f->cols;
-        if (sl.stage_floats[k] < need) {
-            GS_HIP(hipStreamSynchronize(sl.image_stream(k)));
-            if (sl.stage[k]) GS_HIP(hipFree(sl.stage[k]));
-            sl.stage[k] = nullptr;
-            sl.stage_floats[k] = 0;
-            hipError_t e = hipMalloc(reinterpret_cast<void **>(&sl.stage[k]), need * sizeof(float));
-            if (e != hipSuccess) return fail(GS_ERR_NOMEM, "staging buffer: %s", hipGetErrorString(e));
-            sl.stage_floats[k] = need;
-        }
+        const size_t need = (size_t)(((uint64_t)fs.rows + q - 1) / q) * ocols;
+        GS_TRY(ensure_stage(sl, k, need));
         // the image before the previous one must have left this staging buffer (a wait on the GPU, not on the host: the
         // previous image's host copy goes on meanwhile); on a slab chain the boundary rows of the newest plane come from
         // the halo stream
         GS_HIP(hipStreamWaitEvent(sl.compute, sl.copied[k], 0));
         if (ctx->total_slabs() > 1 && ctx->step_no > 0) GS_HIP(hipStreamWaitEvent(sl.compute, sl.halod[last], 0));
         if (i == 0) GS_TRY(join_bands(ctx, sl.compute));
-        GS_HIP(gs_launch_pack_rows(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, sl.stage[k], sl.compute));
+        if (factor == 1)
+            GS_HIP(gs_launch_pack_rows(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, sl.stage[k], sl.compute));
+        else
+            GS_HIP(gs_launch_reduce(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, factor, sl.stage[k], sl.compute));
         GS_HIP(hipEventRecord(sl.staged, sl.compute));
         // (every other image on a stream of its own: behind one another on ONE stream two host copies leave 13 us of the link
         // unused between them -- an 8.3 MB image every 168 us where the link takes 152, tools/ubench/d2h_probe.hip)
         const hipStream_t cs = sl.image_stream(k);
         GS_HIP(hipStreamWaitEvent(cs, sl.staged, 0));
-        GS_HIP(hipMemcpyAsync(host + (fs.g_row0 - first) * f->cols, sl.stage[k], need * sizeof(float),
+        GS_HIP(hipMemcpyAsync(host + (fs.g_row0 / q - first) * ocols, sl.stage[k], need * sizeof(float),
                               hipMemcpyDeviceToHost, cs));
         if (w.pending && i == 0) // the abort word as it stands once the launches this image depends on have ended
             GS_HIP(hipMemcpyAsync(w.seen + k, w.words + kWindowMaxTiles, sizeof(int32_t), hipMemcpyDeviceToHost, cs));
         GS_HIP(hipEventRecord(sl.copied[k], cs));
     }
     ctx->downloads++;
+    return GS_OK;
+}
+
+} // namespace
+
+namespace gsi {
+
+int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host)
+{
+    const uint64_t q = (uint64_t)factor;
+    const uint64_t ocols = (f->cols + q - 1) / q, first = f->s.front().g_row0 / q;
+    for (size_t i = 0; i < f->s.size(); ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        const FieldSlab &fs = f->s[i];
+        GS_HIP(hipSetDevice(sl.device));
+        const size_t need = (size_t)(((uint64_t)fs.rows + q - 1) / q) * ocols;
+        GS_TRY(ensure_stage(sl, 0, need));
+        GS_HIP(gs_launch_reduce(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, factor, sl.stage[0], sl.compute));
+        GS_HIP(hipMemcpyAsync(host + (fs.g_row0 / q - first) * ocols, sl.stage[0], need * sizeof(float), hipMemcpyDeviceToHost,
+                              sl.compute));
+    }
+    for (auto &sl : ctx->slabs) {
+        GS_HIP(hipSetDevice(sl.device));
+        GS_HIP(hipStreamSynchronize(sl.compute));
+    }
+    return GS_OK;
+}
+
+} // namespace gsi
+
+extern "C" {
+
+int32_t gs_field_download_async(gs_ctx *ctx, gs_field *f, float *host)
+{
+    if (!ctx || !f || f->ctx != ctx) return fail(GS_ERR_INVALID, "bad argument");
+    return enqueue_image(ctx, f, 1, host);
+}
+
+int32_t gs_field_reduced_shape(const gs_field *f, int32_t factor, uint64_t *rows, uint64_t *cols, uint64_t *local_row0,
+                               uint64_t *local_row1)
+{
+    ReducedShape r;
+    GS_TRY(reduced_shape(f, factor, &r));
+    if (rows) *rows = r.rows;
+    if (cols) *cols = r.cols;
+    if (local_row0) *local_row0 = r.row0;
+    if (local_row1) *local_row1 = r.row1;
+    return GS_OK;
+}
+
+int32_t gs_field_download_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host)
+{
+    if (!ctx || !f || f->ctx != ctx) return fail(GS_ERR_INVALID, "bad argument");
+    ReducedShape r;
+    GS_TRY(reduced_shape(f, factor, &r));
+    if (factor == 1) return gs_field_download(ctx, f, host);
+    GS_TRY(sync_all(ctx));
+    if (f->rows == 0 || f->cols == 0) return GS_OK; // nothing to copy (host may be null)
+    if (!host) return fail(GS_ERR_INVALID, "bad argument");
+    return fetch_reduced(ctx, f, factor, host);
+}
+
+int32_t gs_field_download_reduced_async(gs_ctx *ctx, gs_field *f, int32_t factor, float *host)
+{
+    if (!ctx || !f || f->ctx != ctx) return fail(GS_ERR_INVALID, "bad argument");
+    ReducedShape r;
+    GS_TRY(reduced_shape(f, factor, &r));
+    return enqueue_image(ctx, f, factor, host);
+}
+
+int32_t gs_field_colormap_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float scale, const uint8_t *palette_rgb,
+                                  int32_t n_colors, uint8_t *host_rgb)
+{
+    if (!ctx || !f || f->ctx != ctx) return fail(GS_ERR_INVALID, "bad argument");
+    ReducedShape r;
+    GS_TRY(reduced_shape(f, factor, &r));
+    if (factor == 1) return gs_field_colormap(ctx, f, scale, palette_rgb, n_colors, host_rgb);
+    if (!palette_rgb || n_colors < 1 || n_colors > 65536) return fail(GS_ERR_INVALID, "bad palette (%d colours)", n_colors);
+    GS_TRY(sync_all(ctx));
+    if (f->rows == 0 || f->cols == 0) return GS_OK; // nothing to paint (host may be null)
+    if (!host_rgb) return fail(GS_ERR_INVALID, "bad argument");
+    const uint64_t q = (uint64_t)factor;
+    for (size_t i = 0; i < f->s.size(); ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        const FieldSlab &fs = f->s[i];
+        GS_HIP(hipSetDevice(sl.device));
+        const int32_t orows = (int32_t)(((uint64_t)fs.rows + q - 1) / q);
+        const size_t bytes = (size_t)orows * r.cols * 3;
+        GS_TRY(ensure_stage(sl, 0, (size_t)orows * r.cols)); // (every stream is idle: the wait above)
+        uint8_t *dev = nullptr;
+        GS_HIP(hipMalloc(reinterpret_cast<void **>(&dev), bytes + (size_t)n_colors * 3));
+        uint8_t *pal = dev + bytes;
+        hipError_t e = hipMemcpyAsync(pal, palette_rgb, (size_t)n_colors * 3, hipMemcpyHostToDevice, sl.compute);
+        if (e == hipSuccess)
+            e = gs_launch_reduce(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, factor, sl.stage[0], sl.compute);
+        if (e == hipSuccess) // the dense staging buffer is a plane whose pitch is its width
+            e = gs_launch_colormap(sl.stage[0], (int32_t)r.cols, orows, (int32_t)r.cols, scale, pal, n_colors, dev, sl.compute);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(host_rgb + (fs.g_row0 / q - r.row0) * r.cols * 3, dev, bytes, hipMemcpyDeviceToHost, sl.compute);
+        if (e == hipSuccess) e = hipStreamSynchronize(sl.compute);
+        (void)hipFree(dev);
+        if (e != hipSuccess) return fail(GS_ERR_HIP, "colour mapping failed: %s", hipGetErrorString(e));
+    }
     return GS_OK;
 }
 

@@ -9,6 +9,7 @@
 //   gs_param_map.cpp parameter maps: per-cell feed and kill rates on one grid (gs_ctx_set_param_map)
 //   gs_mask.cpp    domain masks: wall cells that block diffusion on one grid (gs_ctx_set_mask)
 //   gs_summary.cpp summaries of planes and ensemble members (gs_fields_summarize, gs_members_summarize)
+//   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
 #pragma GCC visibility push(default)
@@ -199,8 +200,9 @@ struct gs_ctx {
         // Images requested with gs_field_download_async while launches were pending: the copy is enqueued behind the
         // launch (nothing waits), and whether the launch gave up is only known when the image is WAITED for -- the abort
         // word travels to `seen` (pinned host memory) behind the image.  If launch `after_seq` or an earlier one gave up,
-        // resolve_window fetches the image again right after it has run that launch again.
-        struct Image { gs_field *f; float *host; int32_t after_seq; };
+        // resolve_window fetches the image again right after it has run that launch again -- a reduced image (factor > 1) is
+        // formed again from the plane, not copied.
+        struct Image { gs_field *f; float *host; int32_t after_seq; int32_t factor; };
         std::vector<Image> images;
         int32_t *seen = nullptr; // pinned, two words: the abort word as either image stream last saw it
     } win;
@@ -338,6 +340,10 @@ void swap_tuner_sets(gs_ctx *ctx, Set &o)
 // gs_mask.cpp
 int32_t check_mask_shape(const gs_ctx *ctx, const gs_field *f);
 void destroy_mask(gs_ctx *ctx);
+
+// gs_fields.cpp: this process's rows of the image of `f` reduced by `factor` (>= 2) into `host`, on a context whose streams
+// are idle (the blocking download after its wait; resolve_window after a replay): through staging buffer 0, done on return.
+int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);
 
 // gs_summary.cpp
 void destroy_summary_buffers(gs_ctx *ctx);

@@ -194,6 +194,10 @@ hipError_t gs_launch_fill_rect(float *row0, int32_t pitch, int32_t r0, int32_t r
                                int32_t c1, float value, hipStream_t s);
 // rows x cols of a plane (row pitch `pitch` floats) to a dense array: gs_field_download_async's staging copy.
 hipError_t gs_launch_pack_rows(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float *dst, hipStream_t s);
+// Reduced result images (gs_reduce.hip; include/gs_hip.h: gs_field_download_reduced): rows x cols of a plane averaged over
+// f x f blocks (2 <= f <= 64, blocks anchored at row 0 and column 0, edge blocks over the cells that exist) into the dense
+// [ceil(rows / f), ceil(cols / f)] array `dst`, in the header's fold order.
+hipError_t gs_launch_reduce(const float *row0, int32_t pitch, int32_t rows, int32_t cols, int32_t f, float *dst, hipStream_t s);
 // gs_fields_place's probe: reads `bytes` (a multiple of 16, 16-byte aligned) of x and of y and writes them back unchanged.
 hipError_t gs_launch_pair_probe(void *x, void *y, size_t bytes, hipStream_t s);
 // gs_ctx_set_mask: the link words (gs_cell.h: link_bit) of one slab's rows [0, rows) x columns [0, cols) from the mask

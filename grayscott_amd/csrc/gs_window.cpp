@@ -199,6 +199,10 @@ int32_t resolve_window(gs_ctx *ctx)
                 GS_HIP(hipStreamSynchronize(sl.compute));
                 GS_HIP(hipStreamSynchronize(sl.copy));
                 GS_HIP(hipStreamSynchronize(sl.copy2));
+                if (im.factor > 1) { // a reduced image: formed again from the replayed plane
+                    GS_TRY(fetch_reduced(ctx, im.f, im.factor, im.host));
+                    continue;
+                }
                 const FieldSlab &fs = im.f->s[0];
                 GS_HIP(hipMemcpy2D(im.host, (size_t)im.f->cols * sizeof(float), fs.row0, (size_t)im.f->pitch * sizeof(float),
                                    (size_t)im.f->cols * sizeof(float), (size_t)fs.rows, hipMemcpyDeviceToHost));

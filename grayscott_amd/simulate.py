@@ -20,6 +20,11 @@ takes arrays ``feed`` and ``kill`` of the grid's shape.  The linear value of ind
 map option is the uniform ``-f`` / ``-k`` value.  The output keeps the reference's format; the map's definition goes
 into a JSON sidecar, ``-o``'s name with ``.param_map.json``.
 
+Reduced images (``gs_field_download_reduced_async``): ``--hip-image-reduce F`` (1..64, default 1) writes every image
+averaged over F x F blocks on the device -- the dataset becomes ``matrix[nbimage, ceil(rows / F), ceil(cols / F)]`` and
+1 / F^2 of the bytes cross the link and reach the file; the steps are untouched.  With F = 1 the output is byte for byte
+what it is without the option.
+
 Domain masks (``gs_ctx_set_mask``): ``--hip-mask FILE.npy`` (or ``FILE.npz`` with an array ``mask``) of the grid's shape
 makes the cells where it is nonzero walls.  It combines with every other option but the parameter map's, which it
 refuses.
@@ -54,6 +59,7 @@ def parse(argv=None):
     add_backend_args(ap)
     add_param_map_args(ap)
     add_mask_args(ap)
+    add_image_args(ap)
     return ap.parse_args(argv)
 
 
@@ -94,6 +100,30 @@ def add_mask_args(ap: argparse.ArgumentParser) -> None:
     mk = ap.add_argument_group("HIP backend: domain mask")
     mk.add_argument("--hip-mask", default=None, metavar="FILE.npy",
                     help="walls where the array (.npy, or array `mask` of a .npz) is nonzero; not with a parameter map")
+
+
+def _reduce_factor(text: str) -> int:
+    try:
+        value = int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"an integer from 1 to 64, not {text!r}") from None
+    if not 1 <= value <= 64:
+        raise argparse.ArgumentTypeError(f"an integer from 1 to 64, not {value}")
+    return value
+
+
+def add_image_args(ap: argparse.ArgumentParser) -> None:
+    """The result images' option of the ``--hip-*`` group (simulate only)."""
+    im = ap.add_argument_group("HIP backend: result images")
+    im.add_argument("--hip-image-reduce", type=_reduce_factor, default=1, metavar="F",
+                    help="write every image averaged over F x F blocks on the device (1..64): matrix[nbimage, ceil(rows / F), "
+                         "ceil(cols / F)], 1 / F^2 of the bytes; 1 = the full planes")
+
+
+def image_shape(args):
+    """Shape of one image of the output dataset: the grid's, reduced by ``--hip-image-reduce``."""
+    f = int(getattr(args, "hip_image_reduce", 1) or 1)
+    return (-(-args.nbrow // f), -(-args.nbcol // f))
 
 
 def domain_mask(args, shape):
@@ -200,6 +230,8 @@ def simulation_parameters(args) -> Parameters:
 def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     steps_per_image = args.nbextrastep if args.nbextrastep is not None else 32
     shape = (args.nbrow, args.nbcol)
+    reduce = int(getattr(args, "hip_image_reduce", 1) or 1)
+    img_shape = image_shape(args)
     if args.output_buffer < 1:
         raise ValueError("--output-buffer must be at least 1")
     params = simulation_parameters(args)
@@ -216,16 +248,16 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     if mask is not None:
         sim.set_mask(mask)
     if out is None and args.output.lower().endswith((".h5", ".hdf5")):
-        out = hdf5_min.create(args.output, (args.nbimage,) + shape)       # dataset "matrix" (hdf5.rs:24)
+        out = hdf5_min.create(args.output, (args.nbimage,) + img_shape)   # dataset "matrix" (hdf5.rs:24)
     elif out is None:
         out = np.lib.format.open_memmap(args.output, mode="w+", dtype=np.float32,
-                                        shape=(args.nbimage,) + shape)
+                                        shape=(args.nbimage,) + img_shape)
 
     # I/O thread: writes images down and recycles their buffers (main.rs:73-87)
     full: "queue.Queue" = queue.Queue(maxsize=args.output_buffer)
     free: "queue.Queue" = queue.Queue()
     for _ in range(args.output_buffer + 2):            # +2: the two images on their way from the device
-        free.put(pinned_empty(shape))
+        free.put(pinned_empty(img_shape))
     errors = []
     failed = threading.Event()
 
@@ -259,7 +291,7 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
             if failed.is_set() or image is None:
                 break
             sim.prepare_steps(species, steps_per_image)     # enqueued; nothing here waits for the device
-            species.write_result_view_after(image)          # this image: staged + copied behind those steps while we go on
+            species.write_result_view_after(image, reduce)  # this image: staged + copied behind those steps while we go on
             pending.append(image)
             if len(pending) == 2:
                 # two images in flight (the library stages them in two buffers in turn): the host copy of the newer one
@@ -280,10 +312,12 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     if hasattr(out, "flush"):
         out.flush()
     cells = shape[0] * shape[1]
+    image_bytes = img_shape[0] * img_shape[1] * 4          # what really crossed the link per image
     info = {
         "images": args.nbimage, "steps_per_image": steps_per_image, "shape": shape, "seconds": elapsed,
         "mcells_steps_per_s": cells * steps_per_image * args.nbimage / elapsed / 1e6,
-        "image_MB_per_s": cells * 4 * args.nbimage / elapsed / 1e6,
+        "image_MB_per_s": image_bytes * args.nbimage / elapsed / 1e6,
+        "image_reduce": reduce, "image_shape": img_shape, "image_bytes": image_bytes * args.nbimage,
     }
     ctx.close()
     return info
@@ -292,8 +326,10 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
 def main(argv=None) -> int:
     args = parse(argv)
     info = run(args)
+    reduced = "" if info["image_reduce"] == 1 else (", images reduced by {image_reduce} to {image_shape[0]}x{image_shape[1]}: "
+                                                    "{image_bytes} bytes moved".format(**info))
     print("simulate: {images} images x {steps_per_image} steps on {shape[0]}x{shape[1]} in {seconds:.3f} s "
-          "({mcells_steps_per_s:.0f} Mcells*steps/s, {image_MB_per_s:.0f} MB/s of images)".format(**info),
+          "({mcells_steps_per_s:.0f} Mcells*steps/s, {image_MB_per_s:.0f} MB/s of images{reduced})".format(reduced=reduced, **info),
           file=sys.stderr)
     return 0
 

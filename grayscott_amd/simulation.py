@@ -387,39 +387,80 @@ class HipConcentration:
         """``gs_field_mark_written``: cells were written through ``device_slabs`` addresses."""
         capi.check(context._lib.gs_field_mark_written(context.handle, self.handle))
 
-    def make_scalar_view(self, context: HipContext) -> np.ndarray:
-        """Owned dense copy of this process's rows (mod.rs:261-275)."""
+    def reduced_shape(self, factor: int) -> Tuple[int, int]:
+        """``gs_field_reduced_shape``: this process's rows x the columns of the image reduced by ``factor`` (the plane
+        averaged over ``factor`` x ``factor`` blocks on the device, include/gs_hip.h).  Raises ``GsError`` for a factor
+        outside 1..64 (``GS_ERR_INVALID``) and for a slab chain some slab of which does not begin at a multiple of the
+        factor (``GS_ERR_UNSUPPORTED``); the device is not touched."""
+        cols, r0, r1 = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        capi.check(self._ctx._lib.gs_field_reduced_shape(self.handle, int(factor), None, ctypes.byref(cols),
+                                                         ctypes.byref(r0), ctypes.byref(r1)))
+        return int(r1.value) - int(r0.value), int(cols.value)
+
+    def _reduced_target(self, target: np.ndarray, reduce: int) -> None:
+        want = self.reduced_shape(reduce)
+        if tuple(target.shape) != want:
+            raise ValueError(f"a target of shape {tuple(target.shape)} cannot take the image reduced by {reduce}: {want}")
+        if target.dtype != np.float32 or not target.flags.c_contiguous:
+            raise ValueError("a target is a C-contiguous float32 array")
+
+    def make_scalar_view(self, context: HipContext, reduce: int = 1) -> np.ndarray:
+        """Owned dense copy of this process's rows (mod.rs:261-275); ``reduce`` > 1: of the reduced image."""
+        if reduce != 1:
+            out = np.empty(self.reduced_shape(reduce), np.float32)
+            self.write_scalar_view(context, out, reduce)
+            return out
         r0, r1 = self.local_rows()
         out = np.empty((r1 - r0, self._shape[1]), np.float32)
         self.write_scalar_view(context, out)
         return out
 
-    def write_scalar_view(self, context: HipContext, target: np.ndarray) -> None:
+    def write_scalar_view(self, context: HipContext, target: np.ndarray, reduce: int = 1) -> None:
         """``write_scalar_view``; like ``validate_write`` (mod.rs:291-295) a shape mismatch is
-        a programming error and asserts."""
+        a programming error and asserts.  ``reduce`` > 1 (``gs_field_download_reduced``): ``target`` takes the image
+        reduced by that factor; one of the wrong shape raises ``ValueError``."""
+        if reduce != 1:
+            self._reduced_target(target, reduce)
+            capi.check(context._lib.gs_field_download_reduced(context.handle, self.handle, int(reduce),
+                                                              target.ctypes.data_as(ctypes.c_void_p)))
+            return
         r0, r1 = self.local_rows()
         assert target.shape == (r1 - r0, self._shape[1]), (target.shape, (r1 - r0, self._shape[1]))
         assert target.dtype == np.float32 and target.flags.c_contiguous
         capi.check(context._lib.gs_field_download(context.handle, self.handle,
                                                   target.ctypes.data_as(ctypes.c_void_p)))
 
-    def write_scalar_view_after(self, context: HipContext, target: np.ndarray) -> None:
+    def write_scalar_view_after(self, context: HipContext, target: np.ndarray, reduce: int = 1) -> None:
         """``write_scalar_view_after`` (data/src/concentration/gpu/image/mod.rs:196-206): enqueue
         the download behind the steps already enqueued and return at once; ``target`` (ideally
-        from ``pinned_empty``) is valid after ``context.download_wait()``."""
+        from ``pinned_empty``) is valid after ``context.download_wait()``.  ``reduce`` > 1
+        (``gs_field_download_reduced_async``): the image reduced by that factor, 1 / reduce^2 of the bytes; a target of
+        the wrong shape raises ``ValueError`` before anything is enqueued."""
+        if reduce != 1:
+            self._reduced_target(target, reduce)
+            capi.check(context._lib.gs_field_download_reduced_async(context.handle, self.handle, int(reduce),
+                                                                    target.ctypes.data_as(ctypes.c_void_p)))
+            return
         r0, r1 = self.local_rows()
         assert target.shape == (r1 - r0, self._shape[1]), (target.shape, (r1 - r0, self._shape[1]))
         assert target.dtype == np.float32 and target.flags.c_contiguous
         capi.check(context._lib.gs_field_download_async(context.handle, self.handle,
                                                         target.ctypes.data_as(ctypes.c_void_p)))
 
-    def colormap(self, context: HipContext, palette: np.ndarray, scale: float = 2.0) -> np.ndarray:
+    def colormap(self, context: HipContext, palette: np.ndarray, scale: float = 2.0, reduce: int = 1) -> np.ndarray:
         """The pixels ``data-to-pics`` makes of this plane (data-to-pics/src/main.rs:139-144):
         ``palette[clamp(floor(scale * value * n), 0, n - 1)]`` as uint8 ``[rows, cols, 3]``; ``palette`` is
         ``[n, 3]`` uint8 (the reference: the 256 colours of ``colorous::INFERNO``), ``scale`` its
-        ``AMPLITUDE_SCALE`` = 1 / 0.5 (ui/src/lib.rs:117-123)."""
+        ``AMPLITUDE_SCALE`` = 1 / 0.5 (ui/src/lib.rs:117-123).  ``reduce`` > 1 (``gs_field_colormap_reduced``): the
+        pixels of the image reduced by that factor, 3 bytes per ``reduce`` x ``reduce`` cells."""
         palette = np.ascontiguousarray(palette, np.uint8)
         assert palette.ndim == 2 and palette.shape[1] == 3 and len(palette) >= 1
+        if reduce != 1:
+            out = np.empty(self.reduced_shape(reduce) + (3,), np.uint8)
+            capi.check(context._lib.gs_field_colormap_reduced(context.handle, self.handle, int(reduce), scale,
+                                                              palette.ctypes.data_as(ctypes.c_void_p), len(palette),
+                                                              out.ctypes.data_as(ctypes.c_void_p)))
+            return out
         r0, r1 = self.local_rows()
         out = np.empty((r1 - r0, self._shape[1], 3), np.uint8)
         capi.check(context._lib.gs_field_colormap(context.handle, self.handle, scale,
@@ -546,15 +587,16 @@ class Species:
     def access_result(self, f: Callable):
         return f(self.v._pair[0], self._context)
 
-    def make_result_view(self) -> np.ndarray:
-        return self.access_result(lambda v, ctx: v.make_scalar_view(ctx))
+    def make_result_view(self, reduce: int = 1) -> np.ndarray:
+        """The V plane (``reduce`` > 1: averaged over ``reduce`` x ``reduce`` blocks on the device, gs_hip.h)."""
+        return self.access_result(lambda v, ctx: v.make_scalar_view(ctx, reduce))
 
-    def write_result_view(self, target: np.ndarray) -> None:
-        self.access_result(lambda v, ctx: v.write_scalar_view(ctx, target))
+    def write_result_view(self, target: np.ndarray, reduce: int = 1) -> None:
+        self.access_result(lambda v, ctx: v.write_scalar_view(ctx, target, reduce))
 
-    def write_result_view_after(self, target: np.ndarray) -> None:
+    def write_result_view_after(self, target: np.ndarray, reduce: int = 1) -> None:
         """Asynchronous form used by the driver loop (simulate/src/main.rs:99-106)."""
-        self.access_result(lambda v, ctx: v.write_scalar_view_after(ctx, target))
+        self.access_result(lambda v, ctx: v.write_scalar_view_after(ctx, target, reduce))
 
 
 class Ensemble:

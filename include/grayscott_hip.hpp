@@ -206,6 +206,40 @@ class HipConcentration {
         if (target_shape != shape_) throw std::logic_error("write_scalar_view_after: target shape mismatch");
         check(gs_field_download_async(c->get(), f_, target));
     }
+    // Reduced result images (gs_hip.h: gs_field_download_reduced): the plane averaged over reduce x reduce blocks on the
+    // device.  reduced_shape: this process's rows of the image x its columns (throws HipError for a factor outside 1..64
+    // and for a slab chain whose slabs do not begin at multiples of the factor).
+    Shape reduced_shape(int32_t reduce) const
+    {
+        uint64_t cols = 0, r0 = 0, r1 = 0;
+        check(gs_field_reduced_shape(f_, reduce, nullptr, &cols, &r0, &r1));
+        return Shape{(std::size_t)(r1 - r0), (std::size_t)cols};
+    }
+    std::vector<Precision> make_scalar_view(Context &c, int32_t reduce)
+    {
+        const Shape s = reduced_shape(reduce);
+        std::vector<Precision> out(s[0] * s[1]);
+        check(gs_field_download_reduced(c->get(), f_, reduce, out.data()));
+        return out;
+    }
+    void write_scalar_view(Context &c, Precision *target, Shape target_shape, int32_t reduce)
+    {
+        if (target_shape != reduced_shape(reduce)) throw std::logic_error("write_scalar_view: target shape mismatch");
+        check(gs_field_download_reduced(c->get(), f_, reduce, target));
+    }
+    void write_scalar_view_after(Context &c, Precision *target, Shape target_shape, int32_t reduce)
+    {
+        if (target_shape != reduced_shape(reduce)) throw std::logic_error("write_scalar_view_after: target shape mismatch");
+        check(gs_field_download_reduced_async(c->get(), f_, reduce, target));
+    }
+    // gs_field_colormap_reduced: RGB8 [reduced rows, reduced cols, 3] through a palette of n_colors RGB triples
+    std::vector<uint8_t> colormap(Context &c, const uint8_t *palette_rgb, int32_t n_colors, float scale, int32_t reduce)
+    {
+        const Shape s = reduced_shape(reduce);
+        std::vector<uint8_t> out(s[0] * s[1] * 3);
+        check(gs_field_colormap_reduced(c->get(), f_, reduce, scale, palette_rgb, n_colors, out.data()));
+        return out;
+    }
     gs_field *raw() const { return f_; }
     // a zero-copy producer wrote cells through gs_field_device_ptr: ghost rows of neighbouring slabs are stale
     void mark_written(Context &c) { check(gs_field_mark_written(c->get(), f_)); }

@@ -396,6 +396,47 @@ int32_t gs_download_wait_but(gs_ctx *ctx, int32_t in_flight);
 int32_t gs_field_colormap(gs_ctx *ctx, gs_field *f, float scale, const uint8_t *palette_rgb, int32_t n_colors,
                           uint8_t *host_rgb);
 
+/* Reduced result images: a plane averaged over factor x factor blocks ON THE DEVICE, so that only 1 / factor^2 of its bytes
+ * are staged, copied and written -- what a live view, a monitoring loop and a long run at a large grid want of a result.
+ *
+ * Definition.  For a field of global shape [rows, cols] and an integer factor f, 1 <= f <= 64, the reduced image has shape
+ * [ceil(rows / f), ceil(cols / f)], f32.  Pixel (R, C) covers the cells r in [R f, min((R + 1) f, rows)),
+ * c in [C f, min((C + 1) f, cols)) (blocks are anchored at GLOBAL row 0 and column 0; edge blocks hold the cells that exist):
+ *   1. row partial p_r: an f64 accumulator starting at +0.0 to which the block's cells of row r are added as f64 in
+ *      ascending column order;
+ *   2. block sum: an f64 accumulator starting at +0.0 to which p_r is added in ascending row order;
+ *   3. pixel = (float)(block sum / (double)count), count = number of cells in the block, both roundings to nearest even.
+ * Sub-normal cells count as what they are and a sub-normal result is kept.  Non-finite cells are not skipped: NaN and
+ * infinities propagate by IEEE rules (a NaN pixel is any NaN).  The result is a function of the plane and f alone: the same
+ * bits whatever the slab count, the process count, the step kernel that produced the plane, and whether the blocking or the
+ * overlapped call fetched it.  factor == 1 is the plain call (gs_field_download, _download_async, _colormap): same bits, same
+ * cost.
+ *
+ * Slabs.  A block never straddles two slabs: a context in which some slab -- local or, in a multi-process run, any rank's --
+ * begins at a global row that is not a multiple of f refuses the call with GS_ERR_UNSUPPORTED and a message that names the
+ * slab's first row and f.  The split is k * rows / S, so the verdict is a function of (rows, S, f) and every rank reaches the
+ * same one without talking.  In a multi-process run each process receives its own output rows, [row0 / f, ceil(row1 / f))
+ * of its rows [row0, row1), as the full-size calls hand it its own rows.
+ *
+ *   gs_field_reduced_shape           global reduced shape and this process's output rows [local_row0, local_row1) (each
+ *                                    pointer may be null); the GS_ERR_UNSUPPORTED verdict without touching the device
+ *   gs_field_download_reduced        blocking, like gs_field_download: waits for enqueued work (a persistent window
+ *                                    launch that gave up is run again first), `host` holds the image on return
+ *   gs_field_download_reduced_async  the overlapped form: gs_field_download_async with the reduction in the place of the
+ *                                    staging copy.  Same two staging buffers (of which it needs 1 / f^2), same streams, same
+ *                                    waits (gs_download_wait, gs_download_wait_but); full and reduced images may be mixed
+ *                                    freely in one stream of calls.  Behind a persistent window launch that gives up the
+ *                                    image is formed again from the replayed plane
+ *   gs_field_colormap_reduced        gs_field_colormap's palette rule applied to the reduced image: dense RGB8
+ *                                    [ceil(rows / f), ceil(cols / f), 3], this process's rows; blocking
+ * factor outside 1..64, a null or foreign handle: GS_ERR_INVALID.  An empty field: GS_OK, nothing written. */
+int32_t gs_field_reduced_shape(const gs_field *f, int32_t factor, uint64_t *rows, uint64_t *cols, uint64_t *local_row0,
+                               uint64_t *local_row1);
+int32_t gs_field_download_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);
+int32_t gs_field_download_reduced_async(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);
+int32_t gs_field_colormap_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float scale, const uint8_t *palette_rgb,
+                                  int32_t n_colors, uint8_t *host_rgb);
+
 /* Device-side stopwatch on the context's compute stream(s) (HIP events): start/stop
  * bracket enqueued work; elapsed is the maximum over local slabs, in milliseconds. */
 int32_t gs_timer_start(gs_ctx *ctx);

@@ -129,6 +129,26 @@ extern "C" {
         n_colors: i32,
         host_rgb: *mut u8,
     ) -> i32;
+    // reduced result images: the plane averaged over factor x factor blocks on the device (gs_hip.h)
+    pub fn gs_field_reduced_shape(
+        f: *const gs_field,
+        factor: i32,
+        rows: *mut u64,
+        cols: *mut u64,
+        local_row0: *mut u64,
+        local_row1: *mut u64,
+    ) -> i32;
+    pub fn gs_field_download_reduced(ctx: *mut gs_ctx, f: *mut gs_field, factor: i32, host: *mut f32) -> i32;
+    pub fn gs_field_download_reduced_async(ctx: *mut gs_ctx, f: *mut gs_field, factor: i32, host: *mut f32) -> i32;
+    pub fn gs_field_colormap_reduced(
+        ctx: *mut gs_ctx,
+        f: *mut gs_field,
+        factor: i32,
+        scale: f32,
+        palette_rgb: *const u8,
+        n_colors: i32,
+        host_rgb: *mut u8,
+    ) -> i32;
     pub fn gs_fields_summarize(ctx: *mut gs_ctx, fields: *const *mut gs_field, n: i32, out: *mut gs_summary) -> i32;
     pub fn gs_members_summarize(
         ctx: *mut gs_ctx,
