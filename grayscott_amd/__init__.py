@@ -11,6 +11,7 @@ from .simulation import (  # noqa: F401
     Ensemble,
     Evolving,
     HipArgs,
+    Histogram,
     HipConcentration,
     HipContext,
     Parameters,
@@ -20,5 +21,5 @@ from .simulation import (  # noqa: F401
     pinned_empty,
 )
 
-__all__ = ["capi", "GsError", "Ensemble", "Evolving", "HipArgs", "HipConcentration", "HipContext",
+__all__ = ["capi", "GsError", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
            "Parameters", "Simulation", "Species", "Summary", "pinned_empty"]

@@ -48,6 +48,8 @@ UNITS = [
     ("gs_util_kernels.hip", "gs_util.o", []),
     # summaries of planes (row records, the ensembles' fold): hipcc's default float mode, sub-normal cells kept
     ("gs_summary.hip", "gs_summary_k.o", []),
+    # histograms of planes (counts in LDS, flushed to u64 counters): the same float mode, a sub-normal cell is binned as it is
+    ("gs_histogram.hip", "gs_histogram_k.o", []),
     # reduced result images (block averages in f64): the same float mode, a sub-normal pixel is kept
     ("gs_reduce.hip", "gs_reduce_k.o", []),
     # the host side (contexts and schedule, planes, kernel configuration, the window kernel's runtime, RCCL): only the
@@ -61,6 +63,7 @@ UNITS = [
     ("gs_param_map.cpp", "gs_param_map.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_mask.cpp", "gs_mask.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_summary.cpp", "gs_summary.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_histogram.cpp", "gs_histogram.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

@@ -46,6 +46,7 @@ EXPORTS = (
     "gs_ctx_set_param_map",
     "gs_ctx_set_mask",
     "gs_fields_summarize", "gs_members_summarize",
+    "gs_fields_histogram", "gs_members_histogram",
     "gs_field_reduced_shape", "gs_field_download_reduced", "gs_field_download_reduced_async", "gs_field_colormap_reduced",
 )
 
@@ -194,6 +195,8 @@ def load() -> ctypes.CDLL:
         "gs_ensemble_run": (i32, [vp, vp, u64]),
         "gs_fields_summarize": (i32, [vp, P(vp), i32, P(GsSummary)]),
         "gs_members_summarize": (i32, [vp, vp, u64, u64, P(GsSummary)]),
+        "gs_fields_histogram": (i32, [vp, P(vp), i32, P(f32), P(f32), i32, P(u64)]),
+        "gs_members_histogram": (i32, [vp, vp, u64, u64, P(f32), P(f32), i32, P(u64)]),
         "gs_field_reduced_shape": (i32, [vp, i32, P(u64), P(u64), P(u64), P(u64)]),
         "gs_field_download_reduced": (i32, [vp, vp, i32, vp]),
         "gs_field_download_reduced_async": (i32, [vp, vp, i32, vp]),

@@ -586,6 +586,7 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
     destroy_param_map(ctx);
     destroy_mask(ctx);
     destroy_summary_buffers(ctx);
+    destroy_histogram_buffers(ctx);
     for (auto &sl : ctx->slabs) {
         if (!sl.compute && !sl.halo) continue; // never initialised (creation failed early)
         if (hipSetDevice(sl.device) != hipSuccess) continue;

@@ -1,0 +1,194 @@
+// gs_histogram.hip -- histograms of planes on the device (include/gs_hip.h: gs_fields_histogram, gs_members_histogram).
+//
+// gs_plane_hist_k counts every cell of a plane into one of bins + 3 slots -- counts[0, bins), below, above, nan, by the rule
+// of gs_hip.h -- in u32 words of LDS shared by the workgroup, and adds the slots that are not zero to the plane's u64
+// counters in global memory once, at its end.  Counts are integers: no order matters, so neither the launch shape nor the
+// slab layout shows in the result.
+//
+// Reading: as gs_row_summary_k does -- a wave owns a row at a time, its lanes read 16 B each, eight loads ahead of their use.
+// Counting: for each of the wave's loads of 64 cells the slot of the first lane is broadcast (readfirstlane), the lanes that
+// hold the same slot are counted with one ballot, and only the OTHER lanes add 1 to their slot in LDS.  What the first
+// lane's slot gained goes to a run kept in scalar registers -- (slot, count) -- which is written to LDS when another slot
+// takes over.  On one-valued data (Species::new, and everything off the pattern: U exactly 1, V exactly 0) a wave so issues
+// no LDS atomic per load at all, and where a pattern begins the background value of a wave still costs none; without this all
+// 64 lanes would add to one word, and adds to one address are served one after the other.  All of it is wave-uniform control
+// flow: the loop bounds are scalar, and a column outside the row counts into a spare slot that nobody reads.
+//
+// Built with hipcc's default float mode (f32 denormals kept) and -ffp-contract=off, as gs_summary.hip is: the rule's
+// subtraction and multiplication are one f32 operation each, and a sub-normal cell or product is the value it is.
+#include "gs_kernels.h"
+
+namespace {
+
+constexpr int kHistUnroll = 8;        // blocks of 256 columns whose loads a wave issues before it counts them
+constexpr int kHistSegment = 1 << 20; // columns of a row that make one unit of work (a multiple of 256 * kHistUnroll)
+// A workgroup takes at most kHistUnitsPerGroup units (the launcher sizes the grid for it) of at most kHistSegment cells
+// each between zeroing its LDS words and flushing them: 2^11 * 2^20 = 2^31 cells, so no u32 word can wrap whatever the
+// plane -- the spare slot included, which gains fewer than 2048 per unit.
+constexpr int64_t kHistUnitsPerGroup = 2048;
+
+struct GsHistArgs {
+    const float *p[4];   // the first `np` planes; plane y of the launch is p[y % np] + (y / np) * stride
+    float lo[4], hi[4], scale[4]; // per p[]
+    int32_t np;
+    int64_t stride;      // floats between one group of np planes and the next (ensembles: a member's cells)
+    int64_t pitch, rows; // of every plane
+    int32_t cols, bins;
+    int64_t groups;      // workgroups per plane
+    unsigned long long *out; // [planes][bins + 3], zeroed by the caller
+};
+
+// The slot of one cell (gs_hip.h): [0, bins) the bins, bins = below, bins + 1 = above, bins + 2 = nan; bins + 3 for a
+// column outside the row.
+__device__ __forceinline__ int slot_of(float x, bool valid, float lo, float hi, float scale, int bins)
+{
+    const bool isnan = x != x, below = x < lo, above = x > hi;
+    const float in = (isnan || below || above) ? lo : x; // (keeps the conversion below defined; the slot is replaced)
+    const float t = (in - lo) * scale;
+    int b = (int)t;
+    b = b < bins - 1 ? b : bins - 1;
+    b = below ? bins : b;
+    b = above ? bins + 1 : b;
+    b = isnan ? bins + 2 : b;
+    return valid ? b : bins + 3;
+}
+
+// The wave's run: `n` cells that belong to slot `slot` and are not in LDS yet.  Both are wave-uniform.
+struct Run {
+    int slot, n;
+};
+
+// GS_HIST_FORM: the forms of `count` that were measured against the one that ships (0) -- 1: every lane adds 1 to its slot
+// in LDS; 2: the run only when all 64 lanes hold one slot, else every lane adds (profiles/histogram.md).
+#ifndef GS_HIST_FORM
+#define GS_HIST_FORM 0
+#endif
+
+// 64 cells, one per lane (every lane active): the lanes whose slot is the first lane's go to the run, the others to LDS.
+__device__ __forceinline__ void count(unsigned *h, Run &run, int s, int lane)
+{
+#if GS_HIST_FORM == 1
+    atomicAdd(&h[s], 1u);
+    (void)run;
+    (void)lane;
+    return;
+#endif
+    const int first = __builtin_amdgcn_readfirstlane(s);
+    const int same = __popcll(__ballot(s == first));
+#if GS_HIST_FORM == 2
+    if (same != 64) {
+        atomicAdd(&h[s], 1u);
+        return;
+    }
+#endif
+    if (s != first) atomicAdd(&h[s], 1u);
+    if (first == run.slot) {
+        run.n += same;
+    } else {
+        if (lane == 0) atomicAdd(&h[run.slot], (unsigned)run.n);
+        run.slot = first;
+        run.n = same;
+    }
+}
+
+// 1-D grid of planes x groups workgroups of 4 waves; dynamic LDS: (bins + 4) u32.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gs_plane_hist_k(GsHistArgs a)
+{
+    extern __shared__ unsigned h[];
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    const int bins = a.bins, slots = bins + 4;
+    const int64_t y = (int64_t)blockIdx.x / a.groups, g = (int64_t)blockIdx.x % a.groups;
+    const int which = (int)(y % a.np);
+    const float *plane = a.p[which] + (y / a.np) * a.stride;
+    const float lo = a.lo[which], hi = a.hi[which], scale = a.scale[which];
+    for (int i = (int)threadIdx.x; i < slots; i += 256) h[i] = 0u;
+    __syncthreads();
+
+    const int cols = a.cols;
+    const int64_t segs = ((int64_t)cols + kHistSegment - 1) / kHistSegment, units = a.rows * segs;
+    Run run{bins + 3, 0};
+    for (int64_t u = g * 4 + wave; u < units; u += a.groups * 4) {
+        // the unit: columns [0, c_end) of `row`, which begins at the segment's first column (a multiple of 2^20)
+        const float *row = plane + (u / segs) * a.pitch + (u % segs) * kHistSegment;
+        const int64_t left = (int64_t)cols - (u % segs) * kHistSegment;
+        const int c_end = (int)(left < kHistSegment ? left : kHistSegment);
+        for (int base = 0; base < c_end; base += 256 * kHistUnroll) { // (scalar: no lane leaves early)
+            float4 x[kHistUnroll];
+            const int c0 = base + 4 * lane;
+#pragma unroll
+            for (int k = 0; k < kHistUnroll; ++k) {
+                const int c = c0 + 256 * k;
+                if (VEC && c + 3 < c_end) {
+                    x[k] = *reinterpret_cast<const float4 *>(row + c);
+                } else { // (a column outside the row reads the row's last cell instead -- c_end > base >= 0 -- and is not counted)
+                    const int last = c_end - 1;
+                    x[k].x = row[c < last ? c : last];
+                    x[k].y = row[c + 1 < last ? c + 1 : last];
+                    x[k].z = row[c + 2 < last ? c + 2 : last];
+                    x[k].w = row[c + 3 < last ? c + 3 : last];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kHistUnroll; ++k) {
+                const int c = c0 + 256 * k;
+                if (base + 256 * k >= c_end) break; // (scalar) no lane of the wave has a column here
+                count(h, run, slot_of(x[k].x, c < c_end, lo, hi, scale, bins), lane);
+                count(h, run, slot_of(x[k].y, c + 1 < c_end, lo, hi, scale, bins), lane);
+                count(h, run, slot_of(x[k].z, c + 2 < c_end, lo, hi, scale, bins), lane);
+                count(h, run, slot_of(x[k].w, c + 3 < c_end, lo, hi, scale, bins), lane);
+            }
+        }
+    }
+    if (lane == 0) atomicAdd(&h[run.slot], (unsigned)run.n);
+    __syncthreads();
+    unsigned long long *out = a.out + y * (int64_t)(bins + 3);
+    for (int i = (int)threadIdx.x; i < bins + 3; i += 256) {
+        const unsigned n = h[i];
+        if (n) atomicAdd(&out[i], (unsigned long long)n);
+    }
+}
+
+} // namespace
+
+hipError_t gs_launch_histogram(const float *const *planes, int np, int64_t repeat, int64_t stride, int64_t pitch, int64_t rows,
+                               int32_t cols, const float *lo, const float *hi, const float *scale, int32_t bins,
+                               int64_t max_groups, unsigned long long *out, hipStream_t s)
+{
+    if (np < 1 || np > 4 || repeat < 1 || bins < 1 || bins > 4096) return hipErrorInvalidValue;
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    GsHistArgs a{};
+    bool vec = pitch % 4 == 0 && (repeat == 1 || stride % 4 == 0);
+    for (int i = 0; i < np; ++i) {
+        a.p[i] = planes[i];
+        a.lo[i] = lo[i];
+        a.hi[i] = hi[i];
+        a.scale[i] = scale[i];
+        vec = vec && reinterpret_cast<uintptr_t>(planes[i]) % 16 == 0;
+    }
+    a.np = np;
+    a.stride = stride;
+    a.pitch = pitch;
+    a.rows = rows;
+    a.cols = cols;
+    a.bins = bins;
+    a.out = out;
+    const int64_t nplanes = (int64_t)np * repeat;
+    const int64_t segs = ((int64_t)cols + kHistSegment - 1) / kHistSegment, units = rows * segs;
+    // as many workgroups per plane as there are units for (4 waves each), at most the caller's share of the chip per plane
+    // -- fewer workgroups, fewer flushes --, and never so few that one takes more than kHistUnitsPerGroup units
+    int64_t groups = (units + 3) / 4;
+    const int64_t share = max_groups / nplanes > 1 ? max_groups / nplanes : 1;
+    if (groups > share) groups = share;
+    const int64_t least = (units + kHistUnitsPerGroup - 1) / kHistUnitsPerGroup;
+    if (groups < least) groups = least;
+    if (groups * nplanes > INT32_MAX) return hipErrorInvalidValue;
+    a.groups = groups;
+    const dim3 grid((unsigned)(groups * nplanes));
+    const size_t lds = (size_t)(bins + 4) * sizeof(unsigned);
+    if (vec)
+        hipLaunchKernelGGL(gs_plane_hist_k<true>, grid, dim3(256), lds, s, a);
+    else
+        hipLaunchKernelGGL(gs_plane_hist_k<false>, grid, dim3(256), lds, s, a);
+    return hipGetLastError();
+}

@@ -9,6 +9,7 @@
 //   gs_param_map.cpp parameter maps: per-cell feed and kill rates on one grid (gs_ctx_set_param_map)
 //   gs_mask.cpp    domain masks: wall cells that block diffusion on one grid (gs_ctx_set_mask)
 //   gs_summary.cpp summaries of planes and ensemble members (gs_fields_summarize, gs_members_summarize)
+//   gs_histogram.cpp histograms of planes and ensemble members (gs_fields_histogram, gs_members_histogram)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
@@ -112,6 +113,10 @@ struct SlabRt {
     // exchanges, and an ensemble's records --, grown on demand, freed with the context
     void *summary = nullptr;
     size_t summary_bytes = 0;
+    // histograms (gs_histogram.cpp): this slab's u64 counters -- on slab 0 also what a multi-process histogram exchanges,
+    // and an ensemble's counters --, grown on demand, freed with the context
+    void *hist = nullptr;
+    size_t hist_bytes = 0;
 };
 
 // The form of difference sharing (share_mode, gs_tuner.cpp) of runs that have not been tuned: across lanes too -- never
@@ -347,6 +352,8 @@ int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);
 
 // gs_summary.cpp
 void destroy_summary_buffers(gs_ctx *ctx);
+// gs_histogram.cpp
+void destroy_histogram_buffers(gs_ctx *ctx);
 // gs_rccl.cpp: every rank's `bytes[q]` bytes (rank q's share, the same table on every rank) into `all` at the offsets of the
 // table's prefix sums, this rank's own share from `mine`; device buffers on slab 0's device, on `stream`.  Messages of at
 // most 1 MiB, one per peer and direction in each group (real RCCL has no such limits; the tests' transport double does).

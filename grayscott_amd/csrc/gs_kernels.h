@@ -226,3 +226,12 @@ hipError_t gs_launch_row_summary(const float *const *planes, int n, int64_t pitc
 // The field fold of gs_hip.h over the records gs_launch_row_summary wrote for the two species of `count` ensemble members
 // of `rows` rows each (rec[s * count * rows + i * rows + r]): out[2 i + s], the rows added one after the other in order.
 hipError_t gs_launch_summary_fold(const GsRowSummary *rec, int64_t count, int64_t rows, GsRowSummary *out, hipStream_t s);
+
+// Histograms (gs_histogram.hip; include/gs_hip.h: gs_fields_histogram).  np (1..4) planes of one shape -- rows [0, rows) of
+// `pitch` floats, `cols` columns -- repeated `repeat` times `stride` floats apart (ensembles: np = 2, a member's cells;
+// else repeat = 1): plane y = r * np + i is planes[i] + r * stride and is counted by the rule of gs_hip.h with lo[i], hi[i],
+// scale[i] into out[y * (bins + 3) ...]: counts[bins], below, above, nan.  `out` must hold zeros (the kernel adds to it);
+// max_groups: workgroups the launch may use when the planes offer more work than that (some multiple of the CU count).
+hipError_t gs_launch_histogram(const float *const *planes, int np, int64_t repeat, int64_t stride, int64_t pitch, int64_t rows,
+                               int32_t cols, const float *lo, const float *hi, const float *scale, int32_t bins,
+                               int64_t max_groups, unsigned long long *out, hipStream_t s);

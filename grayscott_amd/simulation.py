@@ -275,6 +275,90 @@ def summarize_fields(context: "HipContext", fields: Sequence["HipConcentration"]
     return [Summary.from_c(out[i], rows * cols) for i in range(n)]
 
 
+@dataclass(frozen=True, eq=False)
+class Histogram:
+    """A plane's histogram computed on the device (``gs_fields_histogram``; the binning rule is include/gs_hip.h's, in
+    f32 -- not ``numpy.histogram``'s).  ``counts[i]`` is the number of cells in bin i of ``bins`` equal bins of
+    ``[lo, hi]`` (the last bin is closed: a cell equal to ``hi`` is in it), ``below`` / ``above`` those outside the
+    range (infinities included), ``nan`` the NaN cells, ``size`` the plane's number of cells -- the sum of all of them.
+
+    ``fraction_above`` and ``quantile`` work at bin resolution and over the in-range cells (``counts``) alone: cells
+    below, above and NaN take no part."""
+
+    counts: np.ndarray
+    below: int
+    above: int
+    nan: int
+    lo: float
+    hi: float
+    size: int
+
+    @classmethod
+    def from_counters(cls, c: np.ndarray, lo: float, hi: float, size: int) -> "Histogram":
+        """From ``bins + 3`` counters as the C ABI writes them: counts, below, above, nan."""
+        c = np.asarray(c, np.uint64)
+        return cls(c[:-3].copy(), int(c[-3]), int(c[-2]), int(c[-1]), float(lo), float(hi), int(size))
+
+    @property
+    def bins(self) -> int:
+        return len(self.counts)
+
+    @property
+    def in_range(self) -> int:
+        """Cells inside ``[lo, hi]``: the ones ``counts`` holds."""
+        return int(self.counts.sum(dtype=np.uint64))
+
+    def edges(self) -> np.ndarray:
+        """The ``bins + 1`` nominal bin edges ``lo + i (hi - lo) / bins`` in f64.  The true edges -- where the f32 rule
+        steps -- lie within rounding of them."""
+        return self.lo + (self.hi - self.lo) * np.arange(self.bins + 1, dtype=np.float64) / self.bins
+
+    def fraction_above(self, x: float) -> float:
+        """Share of the in-range cells that lie in bins whose nominal lower edge is at least ``x``, i.e. in bins
+        ``i >= ceil((x - lo) / (hi - lo) * bins)``: exact when ``x`` is an edge, else the bin that contains ``x`` counts
+        as not above.  1.0 for ``x <= lo``, 0.0 for ``x > hi``; NaN when no cell is in range."""
+        total = self.in_range
+        if not total:
+            return float("nan")
+        first = int(np.searchsorted(self.edges()[:-1], x, side="left"))  # bins [first, bins) have lower edge >= x
+        return int(self.counts[first:].sum(dtype=np.uint64)) / total
+
+    def quantile(self, q: float) -> float:
+        """The nominal upper edge of the first bin at which the cumulative count of in-range cells reaches ``q`` times
+        their number (at least one cell): an upper bound of the q-quantile of the in-range cells, at most one bin width
+        above it.  ``0 <= q <= 1``; NaN when no cell is in range."""
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"quantile {q} outside [0, 1]")
+        total = self.in_range
+        if not total:
+            return float("nan")
+        need = max(1, int(np.ceil(q * total)))
+        cum = np.cumsum(self.counts, dtype=np.uint64)
+        return float(self.edges()[int(np.searchsorted(cum, need, side="left")) + 1])
+
+
+def _f32_pairs(ranges) -> Tuple["ctypes.Array", "ctypes.Array"]:
+    lo = (ctypes.c_float * len(ranges))(*[float(r[0]) for r in ranges])
+    hi = (ctypes.c_float * len(ranges))(*[float(r[1]) for r in ranges])
+    return lo, hi
+
+
+def histogram_fields(context: "HipContext", fields: Sequence["HipConcentration"], bins: int,
+                     ranges: Sequence[Tuple[float, float]]) -> List[Histogram]:
+    """``gs_fields_histogram``: histograms of 1..4 planes of one shape over the whole global grid, plane i over
+    ``ranges[i]``, in one call (collective in a multi-process context)."""
+    n, bins = len(fields), int(bins)
+    if len(ranges) != n:
+        raise ValueError("one (lo, hi) range per field")
+    arr = (ctypes.c_void_p * max(n, 1))(*[f.handle for f in fields])
+    lo, hi = _f32_pairs(ranges)
+    out = np.zeros((max(n, 1), max(bins, 0) + 3), np.uint64)
+    capi.check(context._lib.gs_fields_histogram(context.handle, arr, n, lo, hi, bins,
+                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    rows, cols = fields[0].shape()
+    return [Histogram.from_counters(out[i], lo[i], hi[i], rows * cols) for i in range(n)]
+
+
 def pinned_empty(shape: Sequence[int]) -> np.ndarray:
     """float32 array in page-locked host memory (``gs_host_alloc``) for overlapped downloads.
     The allocation is released when the last view of it is garbage-collected."""
@@ -473,6 +557,11 @@ class HipConcentration:
         global grid, computed on the device (blocking; collective in a multi-process context)."""
         return summarize_fields(context, [self])[0]
 
+    def histogram(self, context: HipContext, bins: int = 256, range: Tuple[float, float] = (0.0, 1.0)) -> Histogram:
+        """How this plane's values are distributed over ``bins`` equal bins of ``range`` over the whole global grid,
+        counted on the device (blocking; collective in a multi-process context)."""
+        return histogram_fields(context, [self], bins, [range])[0]
+
     def destroy(self) -> None:
         if self._h and self._ctx._h:
             self._ctx._lib.gs_field_destroy(self._ctx._h, self._h)
@@ -584,6 +673,14 @@ class Species:
         u, v = summarize_fields(self._context, [in_u, in_v])
         return u, v
 
+    def histogram(self, bins: int = 256, u_range: Tuple[float, float] = (0.0, 1.0),
+                  v_range: Tuple[float, float] = (0.0, 0.5)) -> Tuple[Histogram, Histogram]:
+        """(U, V) histograms of the current state in one call (``gs_fields_histogram``; blocking, collective in a
+        multi-process context): ``bins`` equal bins of ``u_range`` for U and of ``v_range`` for V."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = histogram_fields(self._context, [in_u, in_v], bins, [u_range, v_range])
+        return u, v
+
     def access_result(self, f: Callable):
         return f(self.v._pair[0], self._context)
 
@@ -672,6 +769,20 @@ class Ensemble:
         out = np.zeros((max(count, 0), 2), SUMMARY_DTYPE)
         capi.check(self._ctx._lib.gs_members_summarize(self._ctx.handle, self.handle, first, count,
                                                         out.ctypes.data_as(ctypes.POINTER(capi.GsSummary))))
+        return out
+
+    def histograms(self, first: int = 0, count: Optional[int] = None, bins: int = 256,
+                   u_range: Tuple[float, float] = (0.0, 1.0), v_range: Tuple[float, float] = (0.0, 0.5)) -> np.ndarray:
+        """Histograms of members ``[first, first + count)`` counted on the device (``gs_members_histogram``, blocking): a
+        ``uint64`` array ``[count, 2, bins + 3]`` -- axis 1: U over ``u_range``, V over ``v_range``; last axis: the
+        ``bins`` counts, then below, above, nan -- what ``Species.histogram`` gives for a lone Species in the member's
+        state (``Histogram.from_counters`` makes the object)."""
+        first, count = self._range(first, count)
+        bins = int(bins)
+        lo, hi = _f32_pairs([u_range, v_range])
+        out = np.zeros((max(count, 0), 2, max(bins, 0) + 3), np.uint64)
+        capi.check(self._ctx._lib.gs_members_histogram(self._ctx.handle, self.handle, first, count, lo, hi, bins,
+                                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out
 
     def prepare_steps(self, steps: int) -> None:

@@ -15,6 +15,13 @@ device (``Ensemble.summaries``: sum, sum of squares, min and max of the finite c
 ``<output stem>.summary.npz``: ``steps[samples]`` and ``sum``, ``sum_sq``, ``min``, ``max``, ``nonfinite``, each
 ``[members, samples, 2]`` (last axis: U, V).  ``--no-fields`` skips the HDF5 file of final V planes (the JSON sidecar
 is still written).  Neither changes the states: the HDF5 file is byte for byte the same with or without summaries.
+
+``--histogram-every N`` records, at the same steps (every N steps and after the last one), the histograms of every member
+counted on the device (``Ensemble.histograms``; the binning rule is include/gs_hip.h's) into ``<output stem>.hist.npz``:
+``steps[samples]``, ``counts[members, samples, 2, bins]`` (axis 2: U, V), ``outside[members, samples, 2, 3]`` (below,
+above, nan), ``lo[2]`` and ``hi[2]``.  ``--hist-bins B`` (default 256), ``--hist-range-u A:B`` (default 0:1) and
+``--hist-range-v A:B`` (default 0:0.5) set the bins.  It works together with ``--summary-every`` and ``--no-fields`` and
+leaves the HDF5 file as it is without it.
 """
 from __future__ import annotations
 
@@ -43,6 +50,17 @@ def value_range(text: str) -> List[float]:
     return [a] if n == 1 else [float(x) for x in np.linspace(a, b, n)]
 
 
+def value_pair(text: str) -> Tuple[float, float]:
+    """``A:B`` -> (A, B) with A < B."""
+    parts = text.split(":")
+    if len(parts) != 2:
+        raise argparse.ArgumentTypeError(f"expected A:B, got {text!r}")
+    a, b = float(parts[0]), float(parts[1])
+    if not a < b:
+        raise argparse.ArgumentTypeError(f"A must be below B in {text!r}")
+    return a, b
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(prog="sweep", description="Gray-Scott parameter sweep, one ensemble member per (feed, kill)")
     ap.add_argument("--feed", type=value_range, required=True, metavar="A:B:N", help="feed rates")
@@ -55,10 +73,19 @@ def parse(argv=None):
     ap.add_argument("--summary-every", type=int, default=0, metavar="N",
                     help="record every member's summaries every N steps and at the end (<output stem>.summary.npz)")
     ap.add_argument("--no-fields", action="store_true", help="do not write the HDF5 file of final V planes")
+    ap.add_argument("--histogram-every", type=int, default=0, metavar="N",
+                    help="record every member's histograms every N steps and at the end (<output stem>.hist.npz)")
+    ap.add_argument("--hist-bins", type=int, default=256, metavar="B", help="bins of the histograms (1..4096)")
+    ap.add_argument("--hist-range-u", type=value_pair, default=(0.0, 1.0), metavar="A:B", help="range of U's histogram")
+    ap.add_argument("--hist-range-v", type=value_pair, default=(0.0, 0.5), metavar="A:B", help="range of V's histogram")
     add_backend_args(ap)
     args = ap.parse_args(argv)
     if args.summary_every < 0:
         ap.error("--summary-every must be at least 1 (0 = off)")
+    if args.histogram_every < 0:
+        ap.error("--histogram-every must be at least 1 (0 = off)")
+    if not 1 <= args.hist_bins <= 4096:
+        ap.error("--hist-bins must be in 1..4096")
     return args
 
 
@@ -85,6 +112,10 @@ def summary_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".summary.npz"
 
 
+def hist_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".hist.npz"
+
+
 def sample_steps(steps: int, every: int) -> List[int]:
     """Steps after which the summaries are taken: every ``every`` steps and after the last one."""
     out = list(range(every, steps + 1, every))
@@ -99,6 +130,13 @@ def write_summaries(path: str, steps: List[int], samples: List[np.ndarray]) -> N
              **{name: np.ascontiguousarray(rec[name]) for name in rec.dtype.names})
 
 
+def write_histograms(path: str, steps: List[int], samples: List[np.ndarray], u_range, v_range) -> None:
+    h = np.stack(samples, axis=1)  # [members, samples, 2, bins + 3]
+    np.savez(path, steps=np.asarray(steps, np.int64), counts=np.ascontiguousarray(h[..., :-3]),
+             outside=np.ascontiguousarray(h[..., -3:]), lo=np.asarray([u_range[0], v_range[0]], np.float32),
+             hi=np.asarray([u_range[1], v_range[1]], np.float32))
+
+
 def run(args) -> dict:
     if args.steps < 0:
         raise ValueError("--steps must be at least 0")
@@ -107,13 +145,21 @@ def run(args) -> dict:
     sim = Simulation.new(params[0], backend_args(args))
     ens = sim.make_ensemble(shape, params)
     t0 = time.perf_counter()
-    if args.summary_every:
-        done, steps, samples = 0, sample_steps(args.steps, args.summary_every), []
-        for at in steps:
+    summary_at = sample_steps(args.steps, args.summary_every) if args.summary_every else []
+    hist_at = sample_steps(args.steps, args.histogram_every) if args.histogram_every else []
+    if summary_at or hist_at:
+        done, summaries, hists = 0, [], []
+        for at in sorted(set(summary_at) | set(hist_at)):
             ens.prepare_steps(at - done)
             done = at
-            samples.append(ens.summaries())  # (waits for the steps)
-        write_summaries(summary_path(args.output), steps, samples)
+            if at in summary_at:
+                summaries.append(ens.summaries())  # (waits for the steps)
+            if at in hist_at:
+                hists.append(ens.histograms(bins=args.hist_bins, u_range=args.hist_range_u, v_range=args.hist_range_v))
+        if summary_at:
+            write_summaries(summary_path(args.output), summary_at, summaries)
+        if hist_at:
+            write_histograms(hist_path(args.output), hist_at, hists, args.hist_range_u, args.hist_range_v)
     else:
         ens.perform_steps(args.steps)
     elapsed = time.perf_counter() - t0

@@ -56,6 +56,35 @@ struct Summary {
     }
 };
 
+// A plane's histogram computed on the device (gs_fields_histogram; the binning rule is gs_hip.h's): `counts[i]` cells in
+// bin i of `counts.size()` equal bins of [lo, hi] (the last one closed), `below` / `above` the range, `nan`; `size` = the
+// plane's number of cells = the sum of all of them.
+struct Histogram {
+    std::vector<uint64_t> counts;
+    uint64_t below = 0, above = 0, nan = 0;
+    float lo = 0.0f, hi = 0.0f;
+    uint64_t size = 0;
+    // from bins + 3 counters as the C ABI writes them
+    static Histogram from_c(const uint64_t *c, int32_t bins, float lo, float hi, uint64_t size)
+    {
+        Histogram h;
+        h.counts.assign(c, c + bins);
+        h.below = c[bins];
+        h.above = c[bins + 1];
+        h.nan = c[bins + 2];
+        h.lo = lo;
+        h.hi = hi;
+        h.size = size;
+        return h;
+    }
+    uint64_t in_range() const
+    {
+        uint64_t n = 0;
+        for (uint64_t c : counts) n += c;
+        return n;
+    }
+};
+
 struct Parameters {
     std::array<std::array<Precision, 3>, 3> weights{{{0.25f, 0.5f, 0.25f}, {0.5f, 0.0f, 0.5f}, {0.25f, 0.5f, 0.25f}}};
     Precision diffusion_rate_u = 0.1f, diffusion_rate_v = 0.05f;
@@ -350,6 +379,19 @@ class Species {
         const Shape s = shape();
         return {Summary::from_c(out[0], s[0] * s[1]), Summary::from_c(out[1], s[0] * s[1])};
     }
+    // (U, V) histograms of the current state over the whole global grid, in one call (gs_fields_histogram; blocking,
+    // collective in a multi-process context): `bins` equal bins of u_range for U and of v_range for V
+    std::pair<Histogram, Histogram> histogram(int32_t bins = 256, std::array<float, 2> u_range = {0.0f, 1.0f},
+                                              std::array<float, 2> v_range = {0.0f, 0.5f})
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const float lo[2] = {u_range[0], v_range[0]}, hi[2] = {u_range[1], v_range[1]};
+        std::vector<uint64_t> out(2 * (std::size_t)(bins > 0 ? bins + 3 : 3));
+        check(gs_fields_histogram(context_->get(), planes, 2, lo, hi, bins, out.data()));
+        const Shape s = shape();
+        return {Histogram::from_c(out.data(), bins, lo[0], hi[0], s[0] * s[1]),
+                Histogram::from_c(out.data() + bins + 3, bins, lo[1], hi[1], s[0] * s[1])};
+    }
     std::vector<Precision> make_result_view() { return v_.in().make_scalar_view(context_); }
     void write_result_view(Precision *target, Shape target_shape)
     {
@@ -428,6 +470,22 @@ class Ensemble {
         check(gs_members_summarize(ctx_->get(), e_, first, count, c.data()));
         std::vector<Summary> out;
         for (const gs_summary &s : c) out.push_back(Summary::from_c(s, shape_[0] * shape_[1]));
+        return out;
+    }
+    // histograms of members [first, first + count) from the newest state (gs_members_histogram, blocking): element
+    // 2 i = U over u_range, 2 i + 1 = V over v_range of member first + i, what Species::histogram gives for a lone Species
+    // in that state
+    std::vector<Histogram> histograms(std::size_t first, std::size_t count, int32_t bins = 256,
+                                      std::array<float, 2> u_range = {0.0f, 1.0f},
+                                      std::array<float, 2> v_range = {0.0f, 0.5f}) const
+    {
+        const float lo[2] = {u_range[0], v_range[0]}, hi[2] = {u_range[1], v_range[1]};
+        const std::size_t each = (std::size_t)(bins > 0 ? bins + 3 : 3);
+        std::vector<uint64_t> c(2 * count * each);
+        check(gs_members_histogram(ctx_->get(), e_, first, count, lo, hi, bins, c.data()));
+        std::vector<Histogram> out;
+        for (std::size_t i = 0; i < 2 * count; ++i)
+            out.push_back(Histogram::from_c(c.data() + i * each, bins, lo[i & 1], hi[i & 1], shape_[0] * shape_[1]));
         return out;
     }
 

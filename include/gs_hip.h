@@ -541,6 +541,40 @@ typedef struct gs_summary {
 int32_t gs_fields_summarize(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_summary *out);
 int32_t gs_members_summarize(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, gs_summary *out);
 
+/* Histograms computed on the device: how the values of one plane of the WHOLE global grid are distributed over `bins`
+ * (1..4096) equal bins of a range lo < hi (finite f32) -- without downloading the plane.  A result is bins + 3 unsigned
+ * 64-bit counters: counts[0 .. bins), then below, above, nan.  Every cell x lands in exactly one of them:
+ *   1. x is NaN            -> nan;
+ *   2. x < lo (-inf too)   -> below;
+ *   3. x > hi (+inf too)   -> above;
+ *   4. otherwise           -> counts[b], b = min((int)t, bins - 1), t = (x - lo) * scale.
+ * The subtraction and the multiplication are one f32 operation each, rounded to nearest even, never contracted; sub-normal
+ * inputs and results are kept; the conversion truncates (t >= 0 here).  scale = (float)bins / (hi - lo) is formed once on
+ * the host in f32: one subtraction, one division.  What follows:
+ *   - the last bin is closed: x == hi counts in bin bins - 1 (U is exactly 1.0 over most of a fresh Species: [0, 1] holds it);
+ *   - -0.0 with lo == 0 is in bin 0;
+ *   - t is monotone in x, so every bin is an interval; its edges are where the formula steps: within rounding of
+ *     lo + i (hi - lo) / bins, but not defined by that expression;
+ *   - the counters sum to rows x cols;
+ *   - counts are integers: the result is the same bits for any slab count, process count, step kernel or launch shape,
+ *     and a member's is that of a lone Species in the same state;
+ *   - this is the library's own rule, not numpy.histogram's, which bins in f64 and differs in cells next to an edge.
+ *   gs_fields_histogram   out[i * (bins + 3) ...] for fields[i] with the range lo[i], hi[i], i < n (1..4 fields of one
+ *                         shape; U and V live on different ranges): one wait for enqueued work (as gs_fields_summarize: a
+ *                         persistent window launch that gave up is run again first), one launch per slab.  In a
+ *                         multi-process context the call is collective, like gs_run, and every rank receives the counts
+ *                         of the global grid.
+ *   gs_members_histogram  out[(2 i + s) * (bins + 3) ...] for species s (0 = U with lo[0], hi[0]; 1 = V with lo[1], hi[1])
+ *                         of member first + i, i < count, from the newest slot: one launch, one copy.
+ * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID, all
+ * decided before any device work: lo or hi not finite, or lo >= hi; hi - lo or scale not a finite, normal, positive f32;
+ * bins outside 1..4096; a null or foreign handle, mixed shapes, n outside 1..4, members outside the ensemble.  An empty
+ * plane: GS_OK, every counter 0. */
+int32_t gs_fields_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *lo, const float *hi, int32_t bins,
+                            uint64_t *out);
+int32_t gs_members_histogram(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float lo[2], const float hi[2],
+                             int32_t bins, uint64_t *out);
+
 /* Measurement hook, not for bindings (tools/rccl_under_load.py): the ghost-row exchange's transport on ONE GPU while the
  * caller keeps the chip busy or idle.  mode 0: a one-rank RCCL communicator, `messages` ncclSend / ncclRecv pairs of
  * `floats` f32 to itself in one group; mode 1: the same bytes as device-to-device copies (the in-process chain's route);

@@ -157,4 +157,25 @@ extern "C" {
         count: u64,
         out: *mut gs_summary,
     ) -> i32;
+    /// `out`: n x (bins + 3) counters -- counts[bins], below, above, nan -- by the rule of include/gs_hip.h.
+    pub fn gs_fields_histogram(
+        ctx: *mut gs_ctx,
+        fields: *const *mut gs_field,
+        n: i32,
+        lo: *const f32,
+        hi: *const f32,
+        bins: i32,
+        out: *mut u64,
+    ) -> i32;
+    /// `lo`, `hi`: two values each (U, V); `out`: count x 2 x (bins + 3) counters.
+    pub fn gs_members_histogram(
+        ctx: *mut gs_ctx,
+        e: *mut gs_ensemble,
+        first: u64,
+        count: u64,
+        lo: *const f32,
+        hi: *const f32,
+        bins: i32,
+        out: *mut u64,
+    ) -> i32;
 }
