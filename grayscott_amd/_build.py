@@ -60,8 +60,7 @@ UNITS = [
     ("gs_window.cpp", "gs_window.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_rccl.cpp", "gs_rccl.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_ensemble.cpp", "gs_ensemble.o", ["-x", "hip", "-fvisibility=hidden"]),
-    ("gs_param_map.cpp", "gs_param_map.o", ["-x", "hip", "-fvisibility=hidden"]),
-    ("gs_mask.cpp", "gs_mask.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_attached.cpp", "gs_attached.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_summary.cpp", "gs_summary.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_histogram.cpp", "gs_histogram.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]

@@ -163,29 +163,26 @@ int32_t refresh_ghosts(gs_ctx *ctx, gs_field *f)
     return GS_OK;
 }
 
-int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fuse, const GsMapPlanes *map,
-                    const GsMaskPlanes *mask = nullptr)
+int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fuse, const GsAttached &at)
 {
     int32_t kernel = ctx->o.kernel;
     if (kernel == GS_KERNEL_AUTO || kernel == GS_KERNEL_TILE || kernel == GS_KERNEL_WINDOW) kernel = fuse > 1 ? GS_KERNEL_TB : GS_KERNEL_STREAM;
     if (fuse > 1 && kernel != GS_KERNEL_TB)
         return fail(GS_ERR_UNSUPPORTED, "only the temporally blocked kernel fuses steps");
     const bool fused = ctx->o.math == GS_MATH_FUSED;
-    if (map && kernel == GS_KERNEL_LDS) // (gs_ctx_set_param_map refuses such a context first)
-        return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no parameter-map form");
-    if (mask && kernel == GS_KERNEL_LDS) // (gs_ctx_set_mask refuses such a context first)
-        return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no domain-mask form");
+    if (at.kind != GS_ATTACH_NONE && kernel == GS_KERNEL_LDS) // (gs_ctx_set_param_map / gs_ctx_set_mask refuse such a context first)
+        return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no %s form", at.kind == GS_ATTACH_MAP ? "parameter-map" : "domain-mask");
     const char *name = nullptr;
     hipError_t e;
     switch (kernel) {
     case GS_KERNEL_TB:
-        e = fused ? gs_launch_tb_fused(a, fuse, stream, &name, map, mask) : gs_launch_tb_strict(a, fuse, stream, &name, map, mask);
+        e = fused ? gs_launch_tb_fused(a, fuse, stream, &name, at) : gs_launch_tb_strict(a, fuse, stream, &name, at);
         break;
     case GS_KERNEL_SIMPLE:
-        e = fused ? gs_launch_simple_fused(a, stream, &name, map, mask) : gs_launch_simple_strict(a, stream, &name, map, mask);
+        e = fused ? gs_launch_simple_fused(a, stream, &name, at) : gs_launch_simple_strict(a, stream, &name, at);
         break;
     case GS_KERNEL_STREAM:
-        e = fused ? gs_launch_stream_fused(a, stream, &name, map, mask) : gs_launch_stream_strict(a, stream, &name, map, mask);
+        e = fused ? gs_launch_stream_fused(a, stream, &name, at) : gs_launch_stream_strict(a, stream, &name, at);
         break;
     case GS_KERNEL_LDS:
         e = fused ? gs_launch_lds_fused(a, stream, &name) : gs_launch_lds_strict(a, stream, &name);
@@ -238,22 +235,15 @@ GsStepArgs make_args(const gs_ctx *ctx, const gs_field *in_u, const gs_field *in
     return a;
 }
 
-// The parameter map's planes of local slab i, rows from `row` on (a row band's first row), for launch_rows: nullptr
-// without a map (the launchers then run the uniform kernels).
-static const GsMapPlanes *map_planes(const gs_ctx *ctx, int i, int row, GsMapPlanes &out)
+// The context's attachment as launch_rows takes it: its kind and its planes of local slab i, from row `row` on (a row
+// band's first row).  Without a map or a mask: GS_ATTACH_NONE, and the launchers run the uniform kernels.
+static GsAttached attached_at(const gs_ctx *ctx, int i, int row)
 {
-    if (!ctx->mapped()) return nullptr;
-    const ptrdiff_t off = (ptrdiff_t)row * ctx->map.feed->pitch;
-    out.feed = ctx->map.feed->s[i].row0 + off;
-    out.fpk = ctx->map.fpk->s[i].row0 + off;
-    return &out;
-}
-// ... and the domain mask's link plane (nullptr without a mask)
-static const GsMaskPlanes *mask_planes(const gs_ctx *ctx, int i, int row, GsMaskPlanes &out)
-{
-    if (!ctx->masked()) return nullptr;
-    out.link = ctx->mask.link->s[i].row0 + (ptrdiff_t)row * ctx->mask.link->pitch;
-    return &out;
+    GsAttached at;
+    at.kind = ctx->attached.kind;
+    for (int j = 0; j < 2; ++j)
+        if (const gs_field *f = ctx->attached.plane[j]) at.plane[j] = f->s[i].row0 + (ptrdiff_t)row * f->pitch;
+    return at;
 }
 
 // ---- in-place row bands of a single slab -------------------------------------------------
@@ -335,10 +325,7 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         a.allow_fair = 0; // several launches share the chip
         const ptrdiff_t off = (ptrdiff_t)r0 * full.pitch;
         a.in_u += off; a.in_v += off; a.out_u += off; a.out_v += off;
-        GsMapPlanes mp;
-        const GsMapPlanes *map = map_planes(ctx, 0, r0, mp);
-        GsMaskPlanes kp;
-        const GsMaskPlanes *mask = mask_planes(ctx, 0, r0, kp);
+        const GsAttached at = attached_at(ctx, 0, r0);
         a.rows = r1 - r0;
         a.top_present = k > 0;
         a.bottom_present = k < V - 1;
@@ -354,14 +341,14 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         e.rb0 = nk <= 2 * fuse ? 0 : nk - fuse;
         e.rb1 = nk <= 2 * fuse ? 0 : nk;
         e.rows_per_unit = fuse;
-        GS_TRY(launch_rows(ctx, e, b.halo, fuse, map, mask));
+        GS_TRY(launch_rows(ctx, e, b.halo, fuse, at));
         GS_HIP(hipEventRecord(b.halod[p], b.halo));
         GS_HIP(hipStreamWaitEvent(b.compute, ctx->band_join, 0));
         GS_HIP(hipStreamWaitEvent(b.compute, b.halod[q], 0));
         if (nk > 2 * fuse) {
             a.ra0 = fuse;
             a.ra1 = nk - fuse;
-            GS_TRY(launch_rows(ctx, a, b.compute, fuse, map, mask));
+            GS_TRY(launch_rows(ctx, a, b.compute, fuse, at));
         }
         GS_HIP(hipEventRecord(b.done[p], b.compute));
     }
@@ -394,9 +381,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
         GsStepArgs a = make_args(ctx, in_u, in_v, out_u, out_v, 0, fuse);
         a.ra0 = 0;
         a.ra1 = a.rows;
-        GsMapPlanes mp;
-        GsMaskPlanes kp;
-        GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map_planes(ctx, 0, 0, mp), mask_planes(ctx, 0, 0, kp)));
+        GS_TRY(launch_rows(ctx, a, sl.compute, fuse, attached_at(ctx, 0, 0)));
     } else {
         if (fuse > kGhostRows || fuse > min_slab_rows(ctx, in_u))
             return fail(GS_ERR_INVALID, "cannot fuse %d steps over slabs of %d rows", fuse, min_slab_rows(ctx, in_u));
@@ -414,10 +399,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             SlabRt &sl = ctx->slabs[i];
             GS_HIP(hipSetDevice(sl.device));
             GsStepArgs a = make_args(ctx, in_u, in_v, out_u, out_v, i, fuse);
-            GsMapPlanes mp;
-            const GsMapPlanes *map = map_planes(ctx, i, 0, mp);
-            GsMaskPlanes kp;
-            const GsMaskPlanes *mask = mask_planes(ctx, i, 0, kp);
+            const GsAttached at = attached_at(ctx, i, 0);
             const int n = a.rows;
             // gs_ctx_set_pass_timing: events around this pass's halo-stream work and interior kernel
             const bool timed = sl.timed < ctx->pass_timing;
@@ -437,7 +419,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             b.rb0 = n <= 2 * depth ? 0 : n - depth;
             b.rb1 = n <= 2 * depth ? 0 : n;
             b.rows_per_unit = depth; // one unit per boundary band and strip
-            GS_TRY(launch_rows(ctx, b, sl.halo, fuse, map, mask));
+            GS_TRY(launch_rows(ctx, b, sl.halo, fuse, at));
             GS_TRY(push_halo(ctx, outs, 2, i, sl.halo, depth));
             GS_HIP(hipEventRecord(sl.halod[p], sl.halo));
             if (timed) GS_HIP(hipEventRecord(sl.th1[sl.timed], sl.halo));
@@ -447,7 +429,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             if (n > 2 * depth) {
                 a.ra0 = depth;
                 a.ra1 = n - depth;
-                GS_TRY(launch_rows(ctx, a, sl.compute, fuse, map, mask));
+                GS_TRY(launch_rows(ctx, a, sl.compute, fuse, at));
             }
             GS_HIP(hipEventRecord(sl.done[p], sl.compute));
             if (timed) {
@@ -502,8 +484,7 @@ int32_t replay_graph_batches(Run &r, int kk)
     key.cpl = pick_cols_per_lane(ctx, (int32_t)f->rows, (int32_t)f->cols, kk);
     key.batch = kGraphBatch;
     key.p = ctx->p;
-    key.map_gen = ctx->map.gen;
-    key.mask_gen = ctx->mask.gen;
+    key.attached_gen = ctx->attached.gen;
     if (!ctx->graph_exec || !(ctx->graph_key == key)) {
         if (ctx->graph_exec) { (void)hipGraphExecDestroy(ctx->graph_exec); ctx->graph_exec = nullptr; }
         if (ctx->graph) { (void)hipGraphDestroy(ctx->graph); ctx->graph = nullptr; }
@@ -583,8 +564,7 @@ int32_t gs_device_count(int32_t *out)
 int32_t gs_ctx_destroy(gs_ctx *ctx)
 {
     if (!ctx) return GS_OK;
-    destroy_param_map(ctx);
-    destroy_mask(ctx);
+    destroy_attached(ctx);
     destroy_summary_buffers(ctx);
     destroy_histogram_buffers(ctx);
     for (auto &sl : ctx->slabs) {
@@ -637,10 +617,11 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     if (ctx->band_join) (void)hipEventDestroy(ctx->band_join);
-    if ((!ctx->tunings.empty() || !ctx->map.tunings.empty() || !ctx->mask.tunings.empty()) && !ctx->slabs.empty() &&
-        hipSetDevice(ctx->slabs[0].device) == hipSuccess)
-        for (auto *tunings : {&ctx->tunings, &ctx->map.tunings, &ctx->mask.tunings}) // (the other kernel sets', gs_param_map.cpp, gs_mask.cpp)
-            for (auto &t : *tunings)
+    const bool tuning = std::any_of(std::begin(ctx->tuner_of), std::end(ctx->tuner_of),
+                                    [](const gs_ctx::TunerState &ts) { return !ts.tunings.empty(); });
+    if (tuning && !ctx->slabs.empty() && hipSetDevice(ctx->slabs[0].device) == hipSuccess)
+        for (auto &ts : ctx->tuner_of) // (every kernel set's)
+            for (auto &t : ts.tunings)
                 for (auto e : t.events)
                     if (e) (void)hipEventDestroy(e);
     (void)hipGetLastError(); // teardown failures must not leak into later calls' status
@@ -801,8 +782,7 @@ int32_t gs_ctx_set_params(gs_ctx *ctx, const gs_params *params)
 int32_t gs_step(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, gs_field *out_v)
 {
     GS_TRY(check_step_fields(ctx, in_u, in_v, out_u, out_v));
-    GS_TRY(check_map_shape(ctx, in_u));
-    GS_TRY(check_mask_shape(ctx, in_u));
+    GS_TRY(check_attached_shape(ctx, in_u));
     GS_TRY(resolve_window(ctx));
     return step_impl(ctx, in_u, in_v, out_u, out_v);
 }
@@ -822,8 +802,7 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
                   bool allow_window)
 {
     GS_TRY(check_step_fields(ctx, u0, v0, u1, v1));
-    GS_TRY(check_map_shape(ctx, u0));
-    GS_TRY(check_mask_shape(ctx, u0));
+    GS_TRY(check_attached_shape(ctx, u0));
     Run r{ctx, {u0, u1}, {v0, v1}};
     r.steps = steps;
     // Temporal blocking: `fuse` steps per pass over HBM (default 4, the measured optimum);
@@ -839,7 +818,7 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
     const bool single = ctx->total_slabs() == 1;
     // With a parameter map or a domain mask every grid runs the marching kernel: the resident, tile and window kernels
     // have no map or mask form.
-    const bool mapped = ctx->mapped() || ctx->masked();
+    const bool mapped = ctx->attached.kind != GS_ATTACH_NONE;
     // Small grids (single slab, kernel = auto): the whole run is one launch with the grid resident
     // in LDS (gs_run_resident_k) -- up to kGsResidentCells = 1536 cells; above, the window kernel is faster (1536
     // cells: 1630 against 1558 Mcells x steps / s; 2048: 1596 against 2062; 4096: 1695 against 4153; run 48).
@@ -947,14 +926,14 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
     // a remainder pass at the end costs nothing.
     recall_tuned(ctx, u0, fuse);
     {
-        const int kk0 = tuned_shape(ctx, u0, fuse) && ctx->tuned_k > 0 && ctx->tuned_k <= fuse ? ctx->tuned_k : fuse;
+        const int kk0 = tuned_shape(ctx, u0, fuse) && ctx->tuner().tuned.k > 0 && ctx->tuner().tuned.k <= fuse ? ctx->tuner().tuned.k : fuse;
         if (steps % (uint64_t)kk0) GS_TRY(r.advance(1, (int)(steps % (uint64_t)kk0)));
     }
     if (single && fuse > 1 && ctx->o.rows_per_block == 0 && !ctx->o.no_tune && !tuned_shape(ctx, u0, fuse))
         GS_TRY(tune_online(r, fuse));
     // Steps per full pass: the tuned value -- on a slab chain every process must have been given the
     // same one (gs_ctx_set_tuned), since the ghost-row exchange is K rows deep.
-    const int kk = tuned_shape(ctx, u0, fuse) && ctx->tuned_k > 0 && ctx->tuned_k <= fuse ? ctx->tuned_k : fuse;
+    const int kk = tuned_shape(ctx, u0, fuse) && ctx->tuner().tuned.k > 0 && ctx->tuner().tuned.k <= fuse ? ctx->tuner().tuned.k : fuse;
     const int V = bands_for(ctx, u0, kk);
     if (ctx->o.use_graph && single && V == 1 && kk > 1) GS_TRY(replay_graph_batches(r, kk));
     const char *full_pass = nullptr;
@@ -1059,9 +1038,9 @@ int32_t gs_ctx_info(const gs_ctx *ctx, char *kernel_name, size_t cap, uint64_t *
 {
     if (!ctx) return fail(GS_ERR_INVALID, "null context");
     if (kernel_name && cap) {
-        if (ctx->tuned_rpu > 0)
-            std::snprintf(kernel_name, cap, "%s@%dx%d", ctx->last_kernel, ctx->tuned_rpu,
-                          ctx->tuned_split > 0 ? ctx->tuned_split : 1); // tuned unit height x row bands
+        const gs_ctx::Tuned &t = ctx->tuner().tuned;
+        if (t.rpu > 0)
+            std::snprintf(kernel_name, cap, "%s@%dx%d", ctx->last_kernel, t.rpu, t.split > 0 ? t.split : 1); // tuned unit height x row bands
         else
             std::snprintf(kernel_name, cap, "%s", ctx->last_kernel);
     }

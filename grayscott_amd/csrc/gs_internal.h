@@ -6,8 +6,8 @@
 //   gs_window.cpp  the persistent window kernel's host side: tiling, exchange planes, give-up and replay
 //   gs_rccl.cpp    RCCL (loaded on first use), its self-test, gs_runtime_info, gs_last_error
 //   gs_ensemble.cpp ensembles: many grids of one shape, each with its own parameters, advanced in shared launches
-//   gs_param_map.cpp parameter maps: per-cell feed and kill rates on one grid (gs_ctx_set_param_map)
-//   gs_mask.cpp    domain masks: wall cells that block diffusion on one grid (gs_ctx_set_mask)
+//   gs_attached.cpp a context's per-cell data: parameter maps (per-cell feed and kill rates, gs_ctx_set_param_map) and
+//                  domain masks (wall cells that block diffusion, gs_ctx_set_mask) on one grid
 //   gs_summary.cpp summaries of planes and ensemble members (gs_fields_summarize, gs_members_summarize)
 //   gs_histogram.cpp histograms of planes and ensemble members (gs_fields_histogram, gs_members_histogram)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
@@ -141,16 +141,13 @@ struct gs_ctx {
     uint64_t downloads = 0;                                   // images enqueued with gs_field_download_async so far
     uint64_t place_probes = 0, place_drawn = 0;               // gs_fields_place: pair probes timed, extra blocks drawn (gs_debug_place_stats)
     int pass_timing = 0;                                      // passes per slab still to be timed (0 = off)
-    // Configuration of the temporally blocked kernel in force (tuned_rpu > 0): unit height, fused steps
-    // per pass and columns per lane for slabs of tuned_rows x tuned_cols -- chosen by gs_run's on-line
-    // tuner (single-slab contexts) or handed in through gs_ctx_set_tuned (slab chains).
-    uint64_t tuned_rows = 0, tuned_cols = 0;
-    int tuned_fuse = 0, tuned_rpu = 0, tuned_split = 0, tuned_k = 0; // tuned_k: fused steps per pass chosen
-    int tuned_cpl = 0;                                               // columns per lane chosen
-    int tuned_share = kShareDefault;                                 // difference sharing chosen (share_mode: 0 / 1 / 2)
-    // every finished choice (a context that alternates between grids does not re-tune)
-    struct Tuned { uint64_t rows, cols; int fuse, rpu, split, k, cpl, share; };
-    std::vector<Tuned> tuned_cache;
+    // A configuration of the temporally blocked kernel (rpu > 0): unit height, row bands, fused steps per pass (k), columns
+    // per lane and difference sharing (share_mode: 0 / 1 / 2) for slabs of rows x cols in runs asked to fuse `fuse` steps --
+    // chosen by gs_run's on-line tuner (single-slab contexts) or handed in through gs_ctx_set_tuned (slab chains).
+    struct Tuned {
+        uint64_t rows = 0, cols = 0;
+        int fuse = 0, rpu = 0, split = 0, k = 0, cpl = 0, share = kShareDefault;
+    };
     // Tunings in progress, one per shape (each may span several gs_run calls; two grids driven
     // alternately advance independently).  `batch` / `nb`: timing windows enqueued but not read yet.
     struct Trial { int rpu, V, k, cpl, reps, share; };
@@ -162,7 +159,15 @@ struct gs_ctx {
         int nb = 0;
         std::vector<hipEvent_t> events; // 3 per window (created on first use)
     };
-    std::vector<Tuning> tunings;
+    // The tuner's state of one kernel set: the configuration in force, the form of difference sharing in force when
+    // gs_options.share_taps leaves the choice open (share_mode), every finished choice (a context that alternates between
+    // grids does not re-tune) and the tunings in progress.
+    struct TunerState {
+        Tuned tuned;
+        int share_now = kShareDefault;
+        std::vector<Tuned> cache;
+        std::vector<Tuning> tunings;
+    };
     // gs_options.use_graph: a batch of passes captured once and replayed (single slab, no bands).
     // The captured launches carry plane addresses and parameters, so the key holds all of them.
     struct GraphKey {
@@ -170,13 +175,12 @@ struct gs_ctx {
         uint64_t rows = 0, cols = 0;
         int k = 0, rpu = 0, cpl = 0, batch = 0;
         gs_params p{};
-        uint64_t map_gen = 0; // the parameter map in force (gs_ctx::ParamMap::gen)
-        uint64_t mask_gen = 0; // the domain mask in force (gs_ctx::Mask::gen)
+        uint64_t attached_gen = 0; // the parameter map or domain mask in force (gs_ctx::Attached::gen)
         bool operator==(const GraphKey &o) const
         {
             return std::memcmp(planes, o.planes, sizeof planes) == 0 && rows == o.rows && cols == o.cols && k == o.k &&
                    rpu == o.rpu && cpl == o.cpl && batch == o.batch && std::memcmp(&p, &o.p, sizeof p) == 0 &&
-                   map_gen == o.map_gen && mask_gen == o.mask_gen;
+                   attached_gen == o.attached_gen;
         }
     } graph_key;
     hipGraph_t graph = nullptr;
@@ -211,36 +215,23 @@ struct gs_ctx {
         std::vector<Image> images;
         int32_t *seen = nullptr; // pinned, two words: the abort word as either image stream last saw it
     } win;
-    int share_now = kShareDefault; // form of difference sharing in force when gs_options.share_taps leaves the choice open (share_mode)
     int cu_count = 0; // compute units of the first slab's device
-    // gs_ctx_set_param_map: the map's planes, owned by the context (F and F + K in the field layout of the species, ghost
-    // rows filled), nullptr without a map; `gen` advances with every attachment, replacement and detachment (GraphKey).
-    struct ParamMap {
-        gs_field *feed = nullptr, *fpk = nullptr;
+    // The context's per-cell data (gs_attached.cpp), one kind at a time: a parameter map (gs_ctx_set_param_map: plane[0] = F,
+    // plane[1] = F + K) or a domain mask (gs_ctx_set_mask: plane[0] = a u32 link word per cell, gs_cell.h: link_bit).  The
+    // planes are owned by the context, in the field layout of the species with their ghost rows filled.  `gen` advances with
+    // every attachment, replacement and detachment of either kind (GraphKey).
+    struct Attached {
+        int kind = GS_ATTACH_NONE;
+        gs_field *plane[2] = {nullptr, nullptr};
         uint64_t gen = 0;
-        // The tuner's choices and tunings of the OTHER kernel set -- the uniform kernels' while a map is attached, the map
-        // kernels' otherwise -- exchanged with the context's own ones when a map is attached or detached (gs_param_map.cpp)
-        uint64_t tuned_rows = 0, tuned_cols = 0;
-        int tuned_fuse = 0, tuned_rpu = 0, tuned_split = 0, tuned_k = 0, tuned_cpl = 0;
-        int tuned_share = kShareDefault, share_now = kShareDefault;
-        std::vector<Tuned> tuned_cache;
-        std::vector<Tuning> tunings;
-    } map;
-    bool mapped() const { return map.feed != nullptr; }
-    // gs_ctx_set_mask: the link plane of the domain mask, owned by the context (a u32 link word per cell in the field layout
-    // of the species, ghost rows filled; gs_cell.h: link_bit), nullptr without a mask; `gen` as the map's.  The tuner's
-    // choices of the OTHER kernel set -- the uniform kernels' while a mask is attached, the mask kernels' otherwise --
-    // as ParamMap keeps them (a mask and a map are never attached together, gs_mask.cpp).
-    struct Mask {
-        gs_field *link = nullptr;
-        uint64_t gen = 0;
-        uint64_t tuned_rows = 0, tuned_cols = 0;
-        int tuned_fuse = 0, tuned_rpu = 0, tuned_split = 0, tuned_k = 0, tuned_cpl = 0;
-        int tuned_share = kShareDefault, share_now = kShareDefault;
-        std::vector<Tuned> tuned_cache;
-        std::vector<Tuning> tunings;
-    } mask;
-    bool masked() const { return mask.link != nullptr; }
+    } attached;
+    bool mapped() const { return attached.kind == GS_ATTACH_MAP; }
+    bool masked() const { return attached.kind == GS_ATTACH_MASK; }
+    // The simple, streaming and marching kernels run the kernel set of the attachment's kind, and the tuner keeps its
+    // choices and tunings per kernel set: attaching and detaching select the state, nothing is copied.
+    TunerState tuner_of[3]; // [GsAttached::kind]
+    TunerState &tuner() { return tuner_of[attached.kind]; }
+    const TunerState &tuner() const { return tuner_of[attached.kind]; }
     int total_slabs() const { return world * (int)slabs.size(); }
     int global_index(int i) const { return rank * (int)slabs.size() + i; }
 };
@@ -322,29 +313,9 @@ int32_t ensure_window_rt(gs_ctx *ctx, const gs_field *f);
 int32_t resolve_window(gs_ctx *ctx);
 int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *launched, int32_t *result_slot);
 
-// gs_param_map.cpp
-int32_t check_map_shape(const gs_ctx *ctx, const gs_field *f);
-void destroy_param_map(gs_ctx *ctx);
-// The tuner's state of the kernel set in force <-> the other set's, kept in `o` (gs_ctx::ParamMap or gs_ctx::Mask).
-template <typename Set>
-void swap_tuner_sets(gs_ctx *ctx, Set &o)
-{
-    std::swap(ctx->tuned_rows, o.tuned_rows);
-    std::swap(ctx->tuned_cols, o.tuned_cols);
-    std::swap(ctx->tuned_fuse, o.tuned_fuse);
-    std::swap(ctx->tuned_rpu, o.tuned_rpu);
-    std::swap(ctx->tuned_split, o.tuned_split);
-    std::swap(ctx->tuned_k, o.tuned_k);
-    std::swap(ctx->tuned_cpl, o.tuned_cpl);
-    std::swap(ctx->tuned_share, o.tuned_share);
-    std::swap(ctx->share_now, o.share_now);
-    std::swap(ctx->tuned_cache, o.tuned_cache);
-    std::swap(ctx->tunings, o.tunings);
-}
-
-// gs_mask.cpp
-int32_t check_mask_shape(const gs_ctx *ctx, const gs_field *f);
-void destroy_mask(gs_ctx *ctx);
+// gs_attached.cpp
+int32_t check_attached_shape(const gs_ctx *ctx, const gs_field *f);
+void destroy_attached(gs_ctx *ctx);
 
 // gs_fields.cpp: this process's rows of the image of `f` reduced by `factor` (>= 2) into `host`, on a context whose streams
 // are idle (the blocking download after its wait; resolve_window after a replay): through staging buffer 0, done on return.

@@ -1,4 +1,5 @@
-// gs_kernels.h -- host/device contract between the host side (gs_api.cpp, gs_tuner.cpp, gs_window.cpp, gs_fields.cpp) and the gfx950 kernels.
+// gs_kernels.h -- host/device contract between the host side (gs_api.cpp, gs_tuner.cpp, gs_window.cpp, gs_fields.cpp,
+// gs_attached.cpp) and the gfx950 kernels.
 //
 // One "plane" is a row-major f32 array of one species in one slot for one row slab:
 //   element (r, c) of the slab, r in [-ghost, rows + ghost) (rows outside [0, rows) = ghost rows),
@@ -84,6 +85,14 @@ struct GsMapPlanes {
 struct GsMaskPlanes {
     const float *link;
 };
+// What a context's per-cell data (a map or a mask, never both) is to the launchers of the simple, streaming and marching
+// kernels: the kernel set it selects -- GS_ATTACH_NONE: the uniform kernels -- and one slab's planes, local row 0, column 0:
+// the map's F and F + K, or the mask's link plane.  The launchers hand them to the kernels as GsMapPlanes / GsMaskPlanes.
+enum { GS_ATTACH_NONE = 0, GS_ATTACH_MAP = 1, GS_ATTACH_MASK = 2 };
+struct GsAttached {
+    int kind = GS_ATTACH_NONE;
+    const float *plane[2] = {nullptr, nullptr};
+};
 
 // gs_launch_window_*: one persistent launch for a whole gs_run on grids of ONE round of register-resident windows.
 // Every workgroup owns a rectangle of the grid (GsWindowDesc; the rectangles tile the grid) and keeps it plus a k-cell
@@ -152,20 +161,17 @@ struct GsEnsArgs {
 };
 
 // Launchers, one set per arithmetic flavour (see gs_math in include/gs_hip.h).  Each
-// returns the hipError_t of the launch.  `name` receives a static kernel-variant label.  `map` (simple, stream and
-// marching kernels): the slab's parameter-map planes -- the launch then runs the map form -- or nullptr.
+// returns the hipError_t of the launch.  `name` receives a static kernel-variant label.  `at` (simple, stream and
+// marching kernels): the slab's attachment -- the launch then runs the kernel set of its kind.
 #define GS_DECLARE_LAUNCHERS(SUFFIX)                                                           \
-    hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr, \
-                                         const GsMaskPlanes *mask = nullptr); \
-    hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr, \
-                                         const GsMaskPlanes *mask = nullptr); \
+    hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
+    hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
     hipError_t gs_launch_resident_##SUFFIX(const GsStepArgs &a, int steps, hipStream_t s, const char **name); \
-    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map = nullptr, \
-                                     const GsMaskPlanes *mask = nullptr); \
+    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
     hipError_t gs_launch_tile_##SUFFIX(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name); \
     hipError_t gs_launch_lds_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name);  \
     hipError_t gs_launch_window_##SUFFIX(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name); \
-    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary, bool map = false, bool mask = false); \
+    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary, int kind = GS_ATTACH_NONE); \
     hipError_t gs_launch_map_rates_##SUFFIX(const float *feed, const float *kill, float *fpk, size_t n, hipStream_t s); \
     const void *gs_tb_map_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                                \
     const void *gs_tb_mask_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                               \

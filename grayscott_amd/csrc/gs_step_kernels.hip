@@ -53,7 +53,9 @@
 //
 // This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
 // its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
-// and LDS-window kernels), gs_window_kernel.h (the persistent window kernel) -- and holds their launchers.
+// and LDS-window kernels), gs_window_kernel.h (the persistent window kernel) -- and holds their launchers.  The launchers
+// of the simple, streaming and marching kernels take the slab's attachment (GsAttached: none, a parameter map or a domain
+// mask), index one table of names and one of entries by its kind, and hand its planes on as the kernel's second argument.
 // Build-time switches of A/B and diagnostic builds (none is set in the shipped build) and the run-time
 // GS_HIP_* switches of the launchers live in gs_experiments.h.
 #include "gs_kernels.h"
@@ -117,7 +119,8 @@
 #define GS_FN(KER, ...) reinterpret_cast<const void *>(&GS_SUFFIX(KER)<__VA_ARGS__>)
 [[maybe_unused]] constexpr int kOp = GS_MATH_FUSED ? 0 : 3;
 #define GS_NAME(BASE, V, R) BASE "/" GS_MATH_NAME V R
-#define GS_RULES(M, BASE) {M(BASE, ""), M(BASE, "/periodic"), M(BASE, "/neumann")}
+#define GS_RULES_OF(M, BASE, A) {M(BASE, A), M(BASE, "/periodic" A), M(BASE, "/neumann" A)}
+#define GS_RULES(M, BASE) GS_RULES_OF(M, BASE, "")
 // The kernel set of boundary rule `boundary` (gs_boundary): 0 = the clipped and zero-halo rules' kernels (*_k), 1 = the
 // periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
 static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
@@ -168,52 +171,50 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 #endif
 
 #define GS_NAMES_OP(BASE, R) {GS_NAME(BASE, "", R), GS_NAME(BASE, ".op", R)}
-// ... and of the parameter map's kernel sets (the same rules, a "/map" suffix behind the rule's)
-#define GS_RULES_MAP(M, BASE) {M(BASE, "/map"), M(BASE, "/periodic/map"), M(BASE, "/neumann/map")}
+// ... per kind of attachment (GsAttached::kind): the uniform kernels' names, then the parameter map's kernel sets' (the same
+// rules, a "/map" suffix behind the rule's) and the domain mask's (a "/mask" suffix)
+#define GS_KINDS(M, BASE) {GS_RULES_OF(M, BASE, ""), GS_RULES_OF(M, BASE, "/map"), GS_RULES_OF(M, BASE, "/mask")}
 #define GS_NAME1(BASE, R) GS_NAME(BASE, "", R)
-// ... and of the domain mask's (a "/mask" suffix)
-#define GS_RULES_MASK(M, BASE) {M(BASE, "/mask"), M(BASE, "/periodic/mask"), M(BASE, "/neumann/mask")}
+#define GS_PLAIN_FN(KER) reinterpret_cast<const void *>(&GS_SUFFIX(KER))
 // [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
 #define GS_TILE_NAMES(BASE, R) {GS_NAMES_OP(BASE "tile32x64", R), GS_NAMES_OP(BASE "tile16x64", R), GS_NAMES_OP(BASE "tile64x64", R)}
 #define GS_TILE_FNS(KER) {{GS_FN(KER, 2, 0), GS_FN(KER, 2, kOp)}, {GS_FN(KER, 1, 0), GS_FN(KER, 1, kOp)}, {GS_FN(KER, 4, 0), GS_FN(KER, 4, kOp)}}
 
-hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes,
-                                       const GsMaskPlanes *mask_planes)
+// The attachment as a launcher takes it: a known kind with its planes in place.
+static bool attached_ok(const GsAttached &at)
 {
-    const bool per = a.zero_halo == 2, neu = a.zero_halo == 3; // the periodic and zero-flux rules: kernels of their own
-    const bool map = map_planes != nullptr;                    // the parameter map: gs_step_simple_mk
-    const bool mask = mask_planes != nullptr;                  // the domain mask: gs_step_simple_wk
-    static const char *const map_names[3] = GS_RULES_MAP(GS_NAME1, "simple");
-    static const char *const mask_names[3] = GS_RULES_MASK(GS_NAME1, "simple");
-    if (map && mask) return hipErrorInvalidValue;
-    if (name) *name = map ? map_names[rule_set(a.zero_halo)] : mask ? mask_names[rule_set(a.zero_halo)]
-                          : per ? "simple/" GS_MATH_NAME "/periodic" : (neu ? "simple/" GS_MATH_NAME "/neumann" : "simple/" GS_MATH_NAME);
+    return at.kind == GS_ATTACH_NONE || (at.kind == GS_ATTACH_MAP && at.plane[0] && at.plane[1]) || (at.kind == GS_ATTACH_MASK && at.plane[0]);
+}
+// Launches entry `fn` of the attachment's kernel set (256-thread workgroups, no LDS): the uniform kernels take `args` alone,
+// the map's and the mask's forms the slab's planes as their second argument.
+static hipError_t launch_attached(const void *fn, long blocks, GsStepArgs &args, const GsAttached &at, hipStream_t s)
+{
+    GsMapPlanes mp{at.plane[0], at.plane[1]};
+    GsMaskPlanes mk{at.plane[0]};
+    void *kargs[] = {&args, at.kind == GS_ATTACH_MAP ? static_cast<void *>(&mp) : static_cast<void *>(&mk)};
+    return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, 0, s);
+}
+
+hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at)
+{
+    // [kind][rule]: the periodic and zero-flux rules run kernels of their own, and so do the parameter map (gs_step_simple_mk)
+    // and the domain mask (gs_step_simple_wk)
+    static const char *const names[3][3] = GS_KINDS(GS_NAME1, "simple");
+    static const void *const fns[3][3] = {
+        {GS_PLAIN_FN(gs_step_simple_k), GS_PLAIN_FN(gs_step_simple_pk), GS_PLAIN_FN(gs_step_simple_nk)},
+        {GS_FN(gs_step_simple_mk, 0), GS_FN(gs_step_simple_mk, 1), GS_FN(gs_step_simple_mk, 2)},
+        {GS_FN(gs_step_simple_wk, 0), GS_FN(gs_step_simple_wk, 1), GS_FN(gs_step_simple_wk, 2)}};
+    if (!attached_ok(at)) return hipErrorInvalidValue;
+    const int per = rule_set(a.zero_halo);
+    if (name) *name = names[at.kind][per];
     const long nrows = (long)(a.ra1 - a.ra0) + (a.rb1 - a.rb0);
     if (nrows <= 0 || a.cols <= 0) return hipSuccess;
-    if (per && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // (single slab only)
+    if (per == 1 && (a.top_present || a.bottom_present)) return hipErrorInvalidValue; // (periodic: single slab only)
     const long bpr = (a.cols + 255) >> 8;
     const long blocks = nrows * bpr;
     if (blocks > 0x7fffffffL) return hipErrorInvalidConfiguration;
     GsStepArgs args = a;
-    void *kargs[] = {&args};
-    if (map) {
-        static const void *const fns[3] = {GS_FN(gs_step_simple_mk, 0), GS_FN(gs_step_simple_mk, 1), GS_FN(gs_step_simple_mk, 2)};
-        GsMapPlanes mp = *map_planes;
-        if (!mp.feed || !mp.fpk) return hipErrorInvalidValue;
-        void *margs[] = {&args, &mp};
-        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
-    }
-    if (mask) {
-        static const void *const fns[3] = {GS_FN(gs_step_simple_wk, 0), GS_FN(gs_step_simple_wk, 1), GS_FN(gs_step_simple_wk, 2)};
-        GsMaskPlanes mk = *mask_planes;
-        if (!mk.link) return hipErrorInvalidValue;
-        void *margs[] = {&args, &mk};
-        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
-    }
-    return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_pk))
-                           : neu ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_nk))
-                                 : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_simple_k)),
-                           dim3((unsigned)blocks), dim3(256), kargs, 0, s);
+    return launch_attached(fns[at.kind][per], blocks, args, at, s);
 }
 
 // `steps` time steps of a grid of at most kResidentCells cells in one launch (gs_run_resident_k);
@@ -390,20 +391,19 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
     return hipLaunchKernel(fn, dim3((unsigned)x.n_windows), dim3(kWinWaves * 64), kargs, lds, s);
 }
 
-hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name, const GsMapPlanes *map_planes,
-                                       const GsMaskPlanes *mask_planes)
+hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at)
 {
-    const bool per = a.zero_halo == 2; // the periodic rule: gs_step_stream_pk (single slab)
-    const bool neu = a.zero_halo == 3; // the zero-flux rule: gs_step_stream_nk
-    const bool map = map_planes != nullptr; // the parameter map: gs_step_stream_mk
-    const bool mask = mask_planes != nullptr; // the domain mask: gs_step_stream_wk
-    static const char *const map_names[3] = GS_RULES_MAP(GS_NAME1, "stream-g2");
-    static const char *const mask_names[3] = GS_RULES_MASK(GS_NAME1, "stream-g2");
-    if ((map && mask) || (mask && !mask_planes->link)) return hipErrorInvalidValue;
-    if (name) *name = map ? map_names[rule_set(a.zero_halo)] : mask ? mask_names[rule_set(a.zero_halo)]
-                          : per ? "stream-g2/" GS_MATH_NAME "/periodic" : (neu ? "stream-g2/" GS_MATH_NAME "/neumann" : "stream-g2/" GS_MATH_NAME);
-    if (map && (!map_planes->feed || !map_planes->fpk)) return hipErrorInvalidValue;
-    if (a.cols <= 0 || a.rows_per_unit <= 0 || (per && (a.top_present || a.bottom_present))) return hipErrorInvalidValue;
+    // [kind][rule]: gs_step_stream_pk (the periodic rule, single slab) and _nk (the zero-flux rule), the parameter map's
+    // gs_step_stream_mk and the domain mask's gs_step_stream_wk
+    static const char *const names[3][3] = GS_KINDS(GS_NAME1, "stream-g2");
+    static const void *const fns[3][3] = {
+        {GS_FN(gs_step_stream_k, 2), GS_FN(gs_step_stream_pk, 2), GS_FN(gs_step_stream_nk, 2)},
+        {GS_FN(gs_step_stream_mk, 2, 0), GS_FN(gs_step_stream_mk, 2, 1), GS_FN(gs_step_stream_mk, 2, 2)},
+        {GS_FN(gs_step_stream_wk, 2, 0), GS_FN(gs_step_stream_wk, 2, 1), GS_FN(gs_step_stream_wk, 2, 2)}};
+    if (!attached_ok(at)) return hipErrorInvalidValue;
+    const int per = rule_set(a.zero_halo);
+    if (name) *name = names[at.kind][per];
+    if (a.cols <= 0 || a.rows_per_unit <= 0 || (per == 1 && (a.top_present || a.bottom_present))) return hipErrorInvalidValue;
     const long rpu = a.rows_per_unit;
     const long chunks = ((long)(a.ra1 - a.ra0) + rpu - 1) / rpu + ((long)(a.rb1 - a.rb0) + rpu - 1) / rpu;
     if (chunks <= 0) return hipSuccess;
@@ -417,23 +417,7 @@ hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const
     // Groups of 8 x 64 workgroups lose 6 % (profiles/archive/r03_sweeps.md, section 12).  GS_HIP_XCD_M_STREAM = 0 / n: off / 8 n.
     static const int xcd_env = gs_env_int("GS_HIP_XCD_M_STREAM", -1, 0, kGsXcdGroupMax);
     args.xcd_m = xcd_env >= 0 ? xcd_env : 16;
-    void *kargs[] = {&args};
-    if (map) {
-        static const void *const fns[3] = {GS_FN(gs_step_stream_mk, 2, 0), GS_FN(gs_step_stream_mk, 2, 1), GS_FN(gs_step_stream_mk, 2, 2)};
-        GsMapPlanes mp = *map_planes;
-        void *margs[] = {&args, &mp};
-        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
-    }
-    if (mask) {
-        static const void *const fns[3] = {GS_FN(gs_step_stream_wk, 2, 0), GS_FN(gs_step_stream_wk, 2, 1), GS_FN(gs_step_stream_wk, 2, 2)};
-        GsMaskPlanes mk = *mask_planes;
-        void *margs[] = {&args, &mk};
-        return hipLaunchKernel(fns[rule_set(a.zero_halo)], dim3((unsigned)blocks), dim3(256), margs, 0, s);
-    }
-    return hipLaunchKernel(per   ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_pk)<2>)
-                           : neu ? reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_nk)<2>)
-                                 : reinterpret_cast<const void *>(&GS_SUFFIX(gs_step_stream_k)<2>),
-                           dim3((unsigned)blocks), dim3(256), kargs, 0, s);
+    return launch_attached(fns[at.kind][per], blocks, args, at, s);
 }
 
 // K fused steps over the row ranges of GsStepArgs; on slab seams the ghost rows must be K deep.
@@ -515,28 +499,32 @@ static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, int per 
 
 // Wave slots of the chip for the kernel entry a launch with these parameters would use (the tuner's
 // "a launch of exactly r rounds" candidates, gs_tuner.cpp); 0 = no such entry.  `boundary`: gs_boundary.
-// The parameter map's variant for GsStepArgs::fast = `fast`: .op (3) where the side weights are 0.5 and dt == 1 in the
-// strict flavour, else the general one.
-static int tb_map_fast(int fast) { return !GS_MATH_FUSED && (fast & 3) == 3 ? 3 : 0; }
-// ... and the domain mask's, where its .op form is built (gs_tb_mask_kernel_*), else the general one
-static int tb_mask_fast(int fast, int k, int cpl, int rule)
+// Kernel entry of the marching kernel in the kernel set of an attachment of `kind` (4-wave workgroups; `fast` reduced).
+static const void *tb_entry_of(int kind, int k, int fast, int cpl, int per)
 {
-    const int f = tb_map_fast(fast);
-    return f && !GS_SUFFIX(gs_tb_mask_kernel)(k, f, cpl, rule) ? 0 : f;
+    return kind == GS_ATTACH_MAP    ? GS_SUFFIX(gs_tb_map_kernel)(k, fast, cpl, per)
+           : kind == GS_ATTACH_MASK ? GS_SUFFIX(gs_tb_mask_kernel)(k, fast, cpl, per)
+                                    : tb_entry(k, fast, cpl, 4, per);
+}
+// ... and the variant that runs there for GsStepArgs::fast = `fast`.  The parameter map's and the domain mask's kernels:
+// .op (3) where the side weights are 0.5 and dt == 1 in the strict flavour and that form is built (gs_tb_mask_kernel_*
+// lacks two), else the general one.
+static int tb_fast_of(int kind, int fast, int k, int cpl, int per)
+{
+    if (kind == GS_ATTACH_NONE) return tb_reduce_fast(fast, k, cpl, 4, per);
+    const int f = !GS_MATH_FUSED && (fast & 3) == 3 ? 3 : 0;
+    return f && !tb_entry_of(kind, k, f, cpl, per) ? 0 : f;
 }
 
-int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, bool map, bool mask)
+int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, int kind)
 {
-    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4)) return 0;
+    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || kind < GS_ATTACH_NONE || kind > GS_ATTACH_MASK) return 0;
     const int per = rule_set(boundary);
-    const void *fn = map    ? GS_SUFFIX(gs_tb_map_kernel)(k, tb_map_fast(fast), cpl, per)
-                     : mask ? GS_SUFFIX(gs_tb_mask_kernel)(k, tb_mask_fast(fast, k, cpl, per), cpl, per)
-                            : tb_entry(k, tb_reduce_fast(fast, k, cpl, 4, per), cpl, 4, per);
+    const void *fn = tb_entry_of(kind, k, tb_fast_of(kind, fast, k, cpl, per), cpl, per);
     return fn ? 1024 * tb_waves_of(fn) : 0;
 }
 
-hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsMapPlanes *map_planes,
-                                   const GsMaskPlanes *mask_planes)
+hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at)
 {
     // "cN": N columns per lane (4 = the wide layout); ".op": the variant specialised for the
     // default (Oono-Puri) side weights, with or without dt == 1
@@ -548,10 +536,9 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
 #define GS_TB_LAYOUTS(B, R) {GS_TB_NAMES(B, "c1", R), GS_TB_NAMES(B, "c2", R), GS_TB_NAMES(B, "", R)}
 #define GS_TB_VARIANTS(B, R) {GS_NAME(B, "", R), GS_NAME(B, ".op", R), GS_NAME(B, ".op.ds", R), GS_NAME(B, ".op.dx", R)}
 #define GS_TB16_LAYOUTS(B, R) {GS_TB_VARIANTS(B "c1f", R), GS_TB_VARIANTS(B "c2f", R)}
-    static const char *const names[3][3][4][4] = GS_RULES(GS_TB_LAYOUTS, "tb-k");    // [rule][cpl 1, 2, 4][variant][k - 1]
+    // [kind][rule][cpl 1, 2, 4][variant][k - 1]: the uniform kernels, the parameter map's (gs_step_tb_mk), the domain mask's (gs_step_tb_wk)
+    static const char *const names[3][3][3][4][4] = GS_KINDS(GS_TB_LAYOUTS, "tb-k");
     static const char *const names16[3][2][4] = GS_RULES(GS_TB16_LAYOUTS, "tb-k4");  // [rule][cpl 1, 2][variant]
-    static const char *const names_map[3][3][4][4] = GS_RULES_MAP(GS_TB_LAYOUTS, "tb-k"); // the parameter map's kernels (gs_step_tb_mk)
-    static const char *const names_mask[3][3][4][4] = GS_RULES_MASK(GS_TB_LAYOUTS, "tb-k"); // the domain mask's (gs_step_tb_wk)
 #undef GS_TB16_LAYOUTS
 #undef GS_TB_VARIANTS
 #undef GS_TB_LAYOUTS
@@ -565,22 +552,17 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // the periodic and zero-flux rules run kernels of their own (gs_step_tb_pk / _nk and kin), named with a "/periodic" /
     // "/neumann" suffix
     const int per = rule_set(a.zero_halo);
-    // the parameter map (map_planes): its own kernels, the general or the .op variant, 4-wave workgroups only
-    const bool map = map_planes != nullptr;
-    if (map && (!map_planes->feed || !map_planes->fpk)) return hipErrorInvalidValue;
-    // the domain mask (mask_planes): likewise, kernels of its own
-    const bool mask = mask_planes != nullptr;
-    if ((map && mask) || (mask && !mask_planes->link)) return hipErrorInvalidValue;
-    const int fast = map ? tb_map_fast(a.fast) : mask ? tb_mask_fast(a.fast, k, cpl, per) : tb_reduce_fast(a.fast, k, cpl, 4, per);
-    if (name) *name = (map ? names_map : mask ? names_mask : names)[per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
+    // the parameter map and the domain mask (at.kind): kernels of their own, the general or the .op variant, 4-wave
+    // workgroups only
+    if (!attached_ok(at)) return hipErrorInvalidValue;
+    const int fast = tb_fast_of(at.kind, a.fast, k, cpl, per);
+    if (name) *name = names[at.kind][per][cpl == 1 ? 0 : (cpl == 2 ? 1 : 2)][name_of(fast)][k - 1];
     const long rpu = a.rows_per_unit;
     const long rows_a = (long)a.ra1 - a.ra0;
     const long W = tb_cols_per_wave(k, cpl);
     const long strips = (a.cols + W - 1) / W;
     // Kernel entry first: the taper below needs its occupancy.
-    const void *fn = map    ? GS_SUFFIX(gs_tb_map_kernel)(k, fast, cpl, per)
-                     : mask ? GS_SUFFIX(gs_tb_mask_kernel)(k, fast, cpl, per)
-                            : tb_entry(k, fast, cpl, 4, per);
+    const void *fn = tb_entry_of(at.kind, k, fast, cpl, per);
     if (!fn) return hipErrorInvalidValue;
     const int waves = tb_waves_of(fn);
     // Tapered tail (consecutive passes are dependent launches that cannot overlap, so the drain phase
@@ -662,7 +644,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // 2 columns per lane, 10 rows 523 k / 537 k, 15 rows 615 k / 633 k, 19 rows 687 k / 738 k, 38 rows 782 k / 865 k.
     // GS_HIP_FAIR = 0 / 1 forces it off / on.
     static const int fair_env = gs_env_int("GS_HIP_FAIR", -1, 0, 1);
-    const bool fair = !map && !mask && a.allow_fair && units <= 4096 && units > 1024 && (fair_env < 0 ? (cpl == 2 || rpu >= 20) : fair_env != 0);
+    const bool fair = at.kind == GS_ATTACH_NONE && a.allow_fair && units <= 4096 && units > 1024 && (fair_env < 0 ? (cpl == 2 || rpu >= 20) : fair_env != 0);
     const int fast16 = fair ? tb_reduce_fast(a.fast, k, cpl, 16, per) : 0;
     const void *fair_fn = fair ? tb_entry(k, fast16, cpl, 16, per) : nullptr;
     static const int fair_from_env = gs_env_int("GS_HIP_FAIR_FROM", -1, 0, 256);
@@ -686,17 +668,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     args.xcd_m = xcd_env >= 0 ? xcd_env : (units >= 2 * slots ? 16 : 0);
     // the edge units at the head of the dispatch order stay dealt over all XCDs (they are the slow ones)
     args.xcd_first = (int32_t)(((chunks * ne * (args.edge_split == 2 ? 2 : 1) + 3) / 4 + 7) / 8 * 8);
-    if (map) {
-        GsMapPlanes mp = *map_planes;
-        void *margs[] = {&args, &mp};
-        return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), margs, 0, s);
-    }
-    if (mask) {
-        GsMaskPlanes mk = *mask_planes;
-        void *margs[] = {&args, &mk};
-        return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), margs, 0, s);
-    }
-    return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, 0, s);
+    return launch_attached(fn, blocks, args, at, s);
 }
 
 hipError_t GS_SUFFIX(gs_launch_lds)(const GsStepArgs &a, hipStream_t s, const char **name)
@@ -821,29 +793,34 @@ const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule)
 }
 #endif
 
+#if GS_TB_MAP_ONLY || GS_TB_MASK_ONLY
+// Entry tables of the marching kernel's per-cell form KER (gs_step_tb_mk, gs_step_tb_wk), variant F (0: general, 3: .op):
+// [k - 1], [cpl 1, 2, 4][k - 1] and [rule][cpl 1, 2, 4][k - 1]
+#define GS_CELL_KS(KER, F, C, R) {GS_FN(KER, 1, F, C, R), GS_FN(KER, 2, F, C, R), GS_FN(KER, 3, F, C, R), GS_FN(KER, 4, F, C, R)}
+#define GS_CELL_CPLS(KER, F, R) {GS_CELL_KS(KER, F, 1, R), GS_CELL_KS(KER, F, 2, R), GS_CELL_KS(KER, F, 4, R)}
+#define GS_CELL_RULES(KER, F) {GS_CELL_CPLS(KER, F, 0), GS_CELL_CPLS(KER, F, 1), GS_CELL_CPLS(KER, F, 2)}
+// ... and the entry for K = 1..4 fused steps, `fast` 0 (general) or 3 (.op: side weights 0.5, dt == 1; `op` is nullptr in the
+// fused flavour, which has none), 1, 2 or 4 columns per lane, `rule` the kernel set of the boundary rule (rule_set);
+// nullptr for a form that is not built.
+static const void *tb_cell_entry(const void *const (*general)[3][4], const void *const (*op)[3][4], int k, int fast, int cpl, int rule)
+{
+    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || rule < 0 || rule > 2) return nullptr;
+    const void *const(*table)[3][4] = fast == 0 ? general : (fast == 3 ? op : nullptr);
+    return table ? table[rule][cpl == 4 ? 2 : cpl - 1][k - 1] : nullptr;
+}
+#endif
+
 #if GS_TB_MAP_ONLY
-// Kernel entry of the marching kernel's parameter-map form (gs_kernels.h: gs_tb_map_kernel_*): K = 1..4 fused steps,
-// `fast` 0 (general) or 3 (.op: side weights 0.5, dt == 1; strict only), 1, 2 or 4 columns per lane, `rule` the kernel set
-// of the boundary rule (rule_set).
+// Kernel entry of the marching kernel's parameter-map form (gs_kernels.h: gs_tb_map_kernel_*).
 const void *GS_SUFFIX(gs_tb_map_kernel)(int k, int fast, int cpl, int rule)
 {
-#define GS_MAP_KS(F, C, R) {GS_FN(gs_step_tb_mk, 1, F, C, R), GS_FN(gs_step_tb_mk, 2, F, C, R), GS_FN(gs_step_tb_mk, 3, F, C, R), GS_FN(gs_step_tb_mk, 4, F, C, R)}
-#define GS_MAP_CPLS(F, R) {GS_MAP_KS(F, 1, R), GS_MAP_KS(F, 2, R), GS_MAP_KS(F, 4, R)}
-#define GS_MAP_RULES(F) {GS_MAP_CPLS(F, 0), GS_MAP_CPLS(F, 1), GS_MAP_CPLS(F, 2)}
-    static const void *const general[3][3][4] = GS_MAP_RULES(0); // [rule][cpl 1, 2, 4][k - 1]
-#if !GS_MATH_FUSED
-    static const void *const op[3][3][4] = GS_MAP_RULES(3);
+    static const void *const general[3][3][4] = GS_CELL_RULES(gs_step_tb_mk, 0);
+#if GS_MATH_FUSED
+    return tb_cell_entry(general, nullptr, k, fast, cpl, rule);
+#else
+    static const void *const op[3][3][4] = GS_CELL_RULES(gs_step_tb_mk, 3);
+    return tb_cell_entry(general, op, k, fast, cpl, rule);
 #endif
-#undef GS_MAP_RULES
-#undef GS_MAP_CPLS
-#undef GS_MAP_KS
-    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || rule < 0 || rule > 2) return nullptr;
-    const int c = cpl == 4 ? 2 : cpl - 1;
-    if (fast == 0) return general[rule][c][k - 1];
-#if !GS_MATH_FUSED
-    if (fast == 3) return op[rule][c][k - 1];
-#endif
-    return nullptr;
 }
 #endif
 
@@ -854,24 +831,15 @@ const void *GS_SUFFIX(gs_tb_map_kernel)(int k, int fast, int cpl, int rule)
 // gs_launch_tb runs the general form there.
 const void *GS_SUFFIX(gs_tb_mask_kernel)(int k, int fast, int cpl, int rule)
 {
-#define GS_MASK_KS(F, C, R) {GS_FN(gs_step_tb_wk, 1, F, C, R), GS_FN(gs_step_tb_wk, 2, F, C, R), GS_FN(gs_step_tb_wk, 3, F, C, R), GS_FN(gs_step_tb_wk, 4, F, C, R)}
-#define GS_MASK_CPLS(F, R) {GS_MASK_KS(F, 1, R), GS_MASK_KS(F, 2, R), GS_MASK_KS(F, 4, R)}
-#define GS_MASK_RULES(F) {GS_MASK_CPLS(F, 0), GS_MASK_CPLS(F, 1), GS_MASK_CPLS(F, 2)}
-    static const void *const general[3][3][4] = GS_MASK_RULES(0); // [rule][cpl 1, 2, 4][k - 1]
-#if !GS_MATH_FUSED
+    static const void *const general[3][3][4] = GS_CELL_RULES(gs_step_tb_wk, 0);
+#if GS_MATH_FUSED
+    return tb_cell_entry(general, nullptr, k, fast, cpl, rule);
+#else
     static const void *const op[3][3][4] = {
-        {GS_MASK_KS(3, 1, 0), GS_MASK_KS(3, 2, 0), {GS_FN(gs_step_tb_wk, 1, 3, 4, 0), GS_FN(gs_step_tb_wk, 2, 3, 4, 0), nullptr, nullptr}},
-        GS_MASK_CPLS(3, 1), GS_MASK_CPLS(3, 2)};
+        {GS_CELL_KS(gs_step_tb_wk, 3, 1, 0), GS_CELL_KS(gs_step_tb_wk, 3, 2, 0),
+         {GS_FN(gs_step_tb_wk, 1, 3, 4, 0), GS_FN(gs_step_tb_wk, 2, 3, 4, 0), nullptr, nullptr}},
+        GS_CELL_CPLS(gs_step_tb_wk, 3, 1), GS_CELL_CPLS(gs_step_tb_wk, 3, 2)};
+    return tb_cell_entry(general, op, k, fast, cpl, rule);
 #endif
-#undef GS_MASK_RULES
-#undef GS_MASK_CPLS
-#undef GS_MASK_KS
-    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || rule < 0 || rule > 2) return nullptr;
-    const int c = cpl == 4 ? 2 : cpl - 1;
-    if (fast == 0) return general[rule][c][k - 1];
-#if !GS_MATH_FUSED
-    if (fast == 3) return op[rule][c][k - 1];
-#endif
-    return nullptr;
 }
 #endif

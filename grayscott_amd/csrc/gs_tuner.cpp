@@ -14,14 +14,14 @@ long tb_strips(int32_t cols, int fuse, int cpl)
 
 // The form of difference sharing in force (when the parameters allow it): 0 = none, 1 = within a lane (the halo-board
 // march), 2 = also across lanes.  Pinned by gs_options.share_taps (1 / 2 / 3 = within / none / across), else what the
-// on-line tuner last chose or is trying (gs_ctx::share_now), else 2 (kShareDefault).
+// on-line tuner last chose or is trying (gs_ctx::TunerState::share_now), else 2 (kShareDefault).
 int share_mode(const gs_ctx *ctx)
 {
     switch (ctx->o.share_taps) {
     case 1: return 1;
     case 2: return 0;
     case 3: return 2;
-    default: return ctx->share_now;
+    default: return ctx->tuner().share_now;
     }
 }
 
@@ -43,7 +43,7 @@ static int fast_possible(const gs_ctx *ctx)
 int fast_of(const gs_ctx *ctx)
 {
     const int fast = fast_possible(ctx), mode = share_mode(ctx);
-    if (!(fast & 4) || mode == 0 || ctx->mapped() || ctx->masked()) return fast & 3; // (the map's and the mask's kernels share no differences)
+    if (!(fast & 4) || mode == 0 || ctx->attached.kind != GS_ATTACH_NONE) return fast & 3; // (the map's and the mask's kernels share no differences)
     return mode == 2 ? fast | 8 : fast;
 }
 
@@ -56,8 +56,8 @@ int fast_of(const gs_ctx *ctx)
 // Writes up to `max` heights (the single-round one first); returns their number.
 int fit_heights(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse, int cpl, int fast, int *out, int max, bool partial)
 {
-    const int slots = ctx->o.math == GS_MATH_FUSED ? gs_tb_wave_slots_fused(fuse, fast, cpl, ctx->o.boundary, ctx->mapped(), ctx->masked())
-                                                     : gs_tb_wave_slots_strict(fuse, fast, cpl, ctx->o.boundary, ctx->mapped(), ctx->masked());
+    const int slots = ctx->o.math == GS_MATH_FUSED ? gs_tb_wave_slots_fused(fuse, fast, cpl, ctx->o.boundary, ctx->attached.kind)
+                                                     : gs_tb_wave_slots_strict(fuse, fast, cpl, ctx->o.boundary, ctx->attached.kind);
     const long strips = tb_strips(cols, fuse, cpl);
     if (slots <= 0 || strips <= 0) return 0;
     const long per_round = slots / strips; // chunks per round
@@ -100,8 +100,9 @@ int fit_heights(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse, int cpl
 bool tuned_for(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse)
 {
     const uint64_t r = (uint64_t)rows;
-    return ctx->tuned_rpu > 0 && ctx->tuned_k == fuse && ctx->tuned_cols == (uint64_t)cols &&
-           (ctx->tuned_rows == r || (ctx->total_slabs() > 1 && (ctx->tuned_rows == r + 1 || ctx->tuned_rows + 1 == r)));
+    const gs_ctx::Tuned &t = ctx->tuner().tuned;
+    return t.rpu > 0 && t.k == fuse && t.cols == (uint64_t)cols &&
+           (t.rows == r || (ctx->total_slabs() > 1 && (t.rows == r + 1 || t.rows + 1 == r)));
 }
 
 // Columns per lane of the temporally blocked kernel when nothing was tuned on line: 2 (measured
@@ -110,7 +111,7 @@ bool tuned_for(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse)
 int32_t pick_cols_per_lane(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse)
 {
     if (ctx->o.cols_per_lane > 0) return ctx->o.cols_per_lane;
-    if (tuned_for(ctx, rows, cols, fuse) && ctx->tuned_cpl > 0) return ctx->tuned_cpl;
+    if (tuned_for(ctx, rows, cols, fuse) && ctx->tuner().tuned.cpl > 0) return ctx->tuner().tuned.cpl;
     if (fuse < 2) return 2;
     return (long)rows * tb_strips(cols, fuse, 2) / (8L * fuse) >= 2048 ? 2 : 1;
 }
@@ -118,7 +119,7 @@ int32_t pick_cols_per_lane(const gs_ctx *ctx, int32_t rows, int32_t cols, int fu
 int32_t pick_rows_per_unit(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse)
 {
     if (ctx->o.rows_per_block > 0) return ctx->o.rows_per_block;
-    if (tuned_for(ctx, rows, cols, fuse)) return ctx->tuned_rpu;
+    if (tuned_for(ctx, rows, cols, fuse)) return ctx->tuner().tuned.rpu;
     const int cpl = pick_cols_per_lane(ctx, rows, cols, fuse);
     const int32_t own = model_rows_per_unit(ctx, rows, cols, fuse, cpl);
     // Several slabs of one process on ONE device share its wave slots: their launches run side by side and
@@ -206,8 +207,8 @@ bool same_slab_shape(const gs_ctx *ctx, uint64_t rows_a, uint64_t cols_a, uint64
 
 bool tuned_shape(const gs_ctx *ctx, const gs_field *f, int fuse)
 {
-    return ctx->tuned_rpu > 0 && ctx->tuned_fuse == fuse &&
-           same_slab_shape(ctx, ctx->tuned_rows, ctx->tuned_cols, slab_rows_of(f), f->cols);
+    const gs_ctx::Tuned &t = ctx->tuner().tuned;
+    return t.rpu > 0 && t.fuse == fuse && same_slab_shape(ctx, t.rows, t.cols, slab_rows_of(f), f->cols);
 }
 
 // Make the remembered choice for this shape (if any) the active one.
@@ -215,26 +216,26 @@ void recall_tuned(gs_ctx *ctx, const gs_field *f, int fuse)
 {
     if (tuned_shape(ctx, f, fuse)) return;
     const uint64_t rows = slab_rows_of(f);
-    for (const gs_ctx::Tuned &t : ctx->tuned_cache)
+    gs_ctx::TunerState &ts = ctx->tuner();
+    for (const gs_ctx::Tuned &t : ts.cache)
         if (same_slab_shape(ctx, t.rows, t.cols, rows, f->cols) && t.fuse == fuse) {
-            ctx->tuned_rows = t.rows; ctx->tuned_cols = t.cols; ctx->tuned_fuse = t.fuse;
-            ctx->tuned_rpu = t.rpu; ctx->tuned_split = t.split; ctx->tuned_k = t.k; ctx->tuned_cpl = t.cpl;
-            ctx->tuned_share = t.share;
-            ctx->share_now = t.share;
+            ts.tuned = t;
+            ts.share_now = t.share;
             return;
         }
     // nothing chosen for this shape yet: its untuned passes and its tuning start from the default form, not from the
-    // form another shape of this context was tuned to (share_now is the context's, the choices are per shape)
-    ctx->share_now = kShareDefault;
+    // form another shape of this context was tuned to (share_now is the kernel set's, the choices are per shape)
+    ts.share_now = kShareDefault;
 }
 
 void remember_tuned(gs_ctx *ctx, const gs_ctx::Tuned &t)
 {
-    for (auto it = ctx->tuned_cache.begin(); it != ctx->tuned_cache.end(); ++it)
-        if (it->rows == t.rows && it->cols == t.cols && it->fuse == t.fuse) { ctx->tuned_cache.erase(it); break; }
-    if (ctx->tuned_cache.size() >= 64) ctx->tuned_cache.erase(ctx->tuned_cache.begin());
-    ctx->tuned_cache.push_back(t);
-    if (ctx->tuned_rows == t.rows && ctx->tuned_cols == t.cols && ctx->tuned_fuse == t.fuse) ctx->tuned_rpu = 0; // re-recall
+    gs_ctx::TunerState &ts = ctx->tuner();
+    for (auto it = ts.cache.begin(); it != ts.cache.end(); ++it)
+        if (it->rows == t.rows && it->cols == t.cols && it->fuse == t.fuse) { ts.cache.erase(it); break; }
+    if (ts.cache.size() >= 64) ts.cache.erase(ts.cache.begin());
+    ts.cache.push_back(t);
+    if (ts.tuned.rows == t.rows && ts.tuned.cols == t.cols && ts.tuned.fuse == t.fuse) ts.tuned.rpu = 0; // re-recall
 }
 
 // On-line choice of unit height, fused steps per pass and columns per lane (single slab, fused
@@ -315,7 +316,7 @@ int32_t tune_online(Run &r, int fuse)
     // it wins and 3-5 % behind on every developed pattern once the power cap has set the clock -- which a timing window of
     // a few passes on a chip that was idle a moment ago does not show (at 4096^2 the windows preferred it on every input
     // and the run then lost 5 %, profiles/r05_cross_lane.md, section 3).
-    const bool share_open = ctx->o.share_taps == 0 && (fast_possible(ctx) & 4) != 0 && !ctx->mapped() && !ctx->masked();
+    const bool share_open = ctx->o.share_taps == 0 && (fast_possible(ctx) & 4) != 0 && ctx->attached.kind == GS_ATTACH_NONE;
     const int ne = share_open ? 1 : 0;
     // timed passes per candidate: short passes need more of them for a stable comparison
     const int reps = cells >= (1ull << 27) ? 2 : (cells >= (1ull << 24) ? 6 : 8);
@@ -325,17 +326,18 @@ int32_t tune_online(Run &r, int fuse)
     // few passes per image -- never wait: their windows are read by a later gs_run.
     constexpr uint64_t kWaitPasses = 16;
 
+    std::vector<gs_ctx::Tuning> &tunings = ctx->tuner().tunings;
     gs_ctx::Tuning *tu = nullptr;
-    for (auto &t : ctx->tunings)
+    for (auto &t : tunings)
         if (t.rows == f->rows && t.cols == f->cols && t.fuse == fuse) tu = &t;
     if (!tu) {
-        if (ctx->tunings.size() >= 16) { // the oldest unfinished tuning makes room
-            for (auto e : ctx->tunings.front().events)
+        if (tunings.size() >= 16) { // the oldest unfinished tuning makes room
+            for (auto e : tunings.front().events)
                 if (e) (void)hipEventDestroy(e);
-            ctx->tunings.erase(ctx->tunings.begin());
+            tunings.erase(tunings.begin());
         }
-        ctx->tunings.emplace_back();
-        tu = &ctx->tunings.back();
+        tunings.emplace_back();
+        tu = &tunings.back();
         tu->rows = f->rows;
         tu->cols = f->cols;
         tu->fuse = fuse;
@@ -478,7 +480,7 @@ int32_t tune_online(Run &r, int fuse)
             }
             ctx->o.rows_per_block = t.rpu;
             ctx->o.cols_per_lane = t.cpl;
-            ctx->share_now = t.share;
+            ctx->tuner().share_now = t.share;
             if (t.cpl != warm_cpl || t.k != warm_k || t.share != warm_share) { // another kernel: one untimed pass first
                 st = r.advance(t.V, t.k);
                 warm_cpl = t.cpl;
@@ -491,7 +493,7 @@ int32_t tune_online(Run &r, int fuse)
             }
             ctx->o.rows_per_block = 0;
             ctx->o.cols_per_lane = user_cpl;
-            ctx->share_now = kShareDefault;
+            ctx->tuner().share_now = kShareDefault;
             tu->batch[nb++] = t;
         }
         if (st != GS_OK) return st;
@@ -512,7 +514,7 @@ int32_t tune_online(Run &r, int fuse)
                          done.share == 2 ? "shared, across lanes too" : (done.share ? "shared within lanes" : "not shared"));
         for (auto e : tu->events)
             if (e) (void)hipEventDestroy(e);
-        ctx->tunings.erase(ctx->tunings.begin() + (tu - ctx->tunings.data()));
+        tunings.erase(tunings.begin() + (tu - tunings.data()));
     }
     return GS_OK;
 }
@@ -528,12 +530,12 @@ int32_t gs_ctx_get_tuned(const gs_ctx *ctx, uint64_t slab_rows, uint64_t cols, i
 {
     if (!ctx) return fail(GS_ERR_INVALID, "null context");
     int rpu = 0, k = 0, cpl = 0, share = 0;
-    for (const gs_ctx::Tuned &t : ctx->tuned_cache)
+    for (const gs_ctx::Tuned &t : ctx->tuner().cache)
         if (t.rows == slab_rows && t.cols == cols) { // the newest entry wins
             rpu = t.rpu; k = t.k; cpl = t.cpl;
             // the EFFECTIVE form: only 2 columns per lane with 2 to 4 fused steps, strict math and a stencil whose diagonal
             // weights pair up have a sharing variant -- everything else runs without, whatever the entry carries
-            const bool has_variant = t.cpl == 2 && t.k >= 2 && (fast_possible(ctx) & 4) && !ctx->mapped() && !ctx->masked();
+            const bool has_variant = t.cpl == 2 && t.k >= 2 && (fast_possible(ctx) & 4) && ctx->attached.kind == GS_ATTACH_NONE;
             share = !has_variant ? 2 : (t.share == 1 ? 1 : (t.share ? 3 : 2));
         }
     if (rows_per_block) *rows_per_block = rpu;

@@ -309,6 +309,23 @@ def test_tuned_choices_of_the_mask_set():
         assert ctx.get_tuned(*shape) == uniform
         sim.set_mask(mask)
         assert ctx.get_tuned(*shape) == masked
+        # ... and a parameter map's kernels keep a third choice on the same context: map attached -> detached -> mask
+        # attached -> detached, each set answering with its own
+        sim.clear_mask()
+        rates = np.full(shape, 0.03, np.float32), np.full(shape, 0.06, np.float32)
+        sim.set_param_map(*rates)
+        assert ctx.get_tuned(*shape) == (0, 0, 0, 0)   # nothing chosen for the map's kernels yet
+        ctx.set_tuned(shape[0], shape[1], 12, 4, 4)
+        mapped = ctx.get_tuned(*shape)
+        assert len({uniform, masked, mapped}) == 3
+        sim.clear_param_map()
+        assert ctx.get_tuned(*shape) == uniform
+        sim.set_mask(mask)
+        assert ctx.get_tuned(*shape) == masked
+        sim.clear_mask()
+        assert ctx.get_tuned(*shape) == uniform
+        sim.set_param_map(*rates)
+        assert ctx.get_tuned(*shape) == mapped
     finally:
         sim.context.close()
 
