@@ -61,8 +61,7 @@ UNITS = [
     ("gs_rccl.cpp", "gs_rccl.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_ensemble.cpp", "gs_ensemble.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_attached.cpp", "gs_attached.o", ["-x", "hip", "-fvisibility=hidden"]),
-    ("gs_summary.cpp", "gs_summary.o", ["-x", "hip", "-fvisibility=hidden"]),
-    ("gs_histogram.cpp", "gs_histogram.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_observe.cpp", "gs_observe.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

@@ -77,6 +77,15 @@ int32_t sync_all(gs_ctx *ctx)
     return GS_OK;
 }
 
+int32_t sync_compute(gs_ctx *ctx)
+{
+    for (auto &sl : ctx->slabs) {
+        GS_HIP(hipSetDevice(sl.device));
+        GS_HIP(hipStreamSynchronize(sl.compute));
+    }
+    return GS_OK;
+}
+
 int32_t copy_row(gs_ctx *ctx, int src_slab, const float *src, int dst_slab, float *dst, size_t bytes,
                  hipStream_t stream)
 {
@@ -565,8 +574,7 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
 {
     if (!ctx) return GS_OK;
     destroy_attached(ctx);
-    destroy_summary_buffers(ctx);
-    destroy_histogram_buffers(ctx);
+    destroy_scratch(ctx);
     for (auto &sl : ctx->slabs) {
         if (!sl.compute && !sl.halo) continue; // never initialised (creation failed early)
         if (hipSetDevice(sl.device) != hipSuccess) continue;

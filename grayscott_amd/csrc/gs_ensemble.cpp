@@ -6,6 +6,14 @@
 
 using namespace gsi;
 
+int32_t gsi::check_member_range(const gs_ensemble *e, uint64_t first, uint64_t count)
+{
+    if (count == 0 || first >= e->members || count > e->members - first)
+        return fail(GS_ERR_INVALID, "members [%llu, %llu + %llu) outside the ensemble's %llu", (unsigned long long)first,
+                    (unsigned long long)first, (unsigned long long)count, (unsigned long long)e->members);
+    return GS_OK;
+}
+
 namespace {
 
 // A member's cells are indexed with 32-bit integers in the kernels (and its windows must fit one launch).
@@ -15,14 +23,6 @@ int32_t check_ensemble(const gs_ctx *ctx, const gs_ensemble *e)
 {
     if (!ctx || !e) return fail(GS_ERR_INVALID, "null argument");
     if (e->ctx != ctx) return fail(GS_ERR_INVALID, "ensemble belongs to another context");
-    return GS_OK;
-}
-
-int32_t check_members(const gs_ensemble *e, uint64_t first, uint64_t count)
-{
-    if (count == 0 || first >= e->members || count > e->members - first)
-        return fail(GS_ERR_INVALID, "members [%llu, %llu + %llu) outside the ensemble's %llu", (unsigned long long)first,
-                    (unsigned long long)first, (unsigned long long)count, (unsigned long long)e->members);
     return GS_OK;
 }
 
@@ -165,7 +165,7 @@ int32_t gs_ensemble_upload(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t
 {
     GS_TRY(check_ensemble(ctx, e));
     if (!u && !v) return fail(GS_ERR_INVALID, "null host arrays");
-    GS_TRY(check_members(e, first, count));
+    GS_TRY(check_member_range(e, first, count));
     const size_t cells = (size_t)(e->rows * e->cols), off = (size_t)first * cells, bytes = (size_t)count * cells * sizeof(float);
     SlabRt &sl = ctx->slabs[0];
     GS_HIP(hipSetDevice(sl.device));
@@ -180,7 +180,7 @@ int32_t gs_ensemble_download(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64
     GS_TRY(check_ensemble(ctx, e));
     if (!host) return fail(GS_ERR_INVALID, "null host array");
     if (species != 0 && species != 1) return fail(GS_ERR_INVALID, "species %d (0 = U, 1 = V)", species);
-    GS_TRY(check_members(e, first, count));
+    GS_TRY(check_member_range(e, first, count));
     const size_t cells = (size_t)(e->rows * e->cols), off = (size_t)first * cells, bytes = (size_t)count * cells * sizeof(float);
     SlabRt &sl = ctx->slabs[0];
     GS_HIP(hipSetDevice(sl.device));

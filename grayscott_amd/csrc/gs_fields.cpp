@@ -516,6 +516,21 @@ int32_t ensure_stage(SlabRt &sl, int k, size_t need)
     return GS_OK;
 }
 
+// Slab i's part of the image of `f` reduced by `factor` (1: the plane's own rows and columns): its rows and columns, its
+// floats (what a dense staging buffer must hold) and where they begin in this process's host image.
+struct ImagePart {
+    int32_t rows;
+    uint64_t cols;
+    size_t floats, at;
+};
+
+ImagePart image_part(const gs_field *f, size_t i, int32_t factor)
+{
+    const uint64_t q = (uint64_t)factor, cols = (f->cols + q - 1) / q;
+    const uint64_t rows = ((uint64_t)f->s[i].rows + q - 1) / q;
+    return ImagePart{(int32_t)rows, cols, (size_t)rows * cols, (size_t)((f->s[i].g_row0 / q - f->s.front().g_row0 / q) * cols)};
+}
+
 // gs_field_download_async and gs_field_download_reduced_async: the image of `f` reduced by `factor` (1: the plane itself,
 // staged by gs_pack_rows_k; more: by gs_launch_reduce) enqueued behind the work already enqueued.  The caller has checked
 // the handles, the factor and the slabs.
@@ -535,17 +550,14 @@ int32_t enqueue_image(gs_ctx *ctx, gs_field *f, int32_t factor, float *host)
         }
         w.images.push_back(gs_ctx::WindowRt::Image{f, host, w.seq, factor});
     }
-    const uint64_t q = (uint64_t)factor;
-    const uint64_t ocols = (f->cols + q - 1) / q; // (factor 1: the plane's own rows and columns)
-    const uint64_t first = f->s.front().g_row0 / q;
     const int last = (int)((ctx->step_no + 1) & 1); // parity of the most recent pass
     const int k = (int)(ctx->downloads & 1);        // the staging buffer of this image
     for (size_t i = 0; i < f->s.size(); ++i) {
         SlabRt &sl = ctx->slabs[i];
         const FieldSlab &fs = f->s[i];
         GS_HIP(hipSetDevice(sl.device));
-        const size_t need = (size_t)(((uint64_t)fs.rows + q - 1) / q) * ocols;
-        GS_TRY(ensure_stage(sl, k, need));
+        const ImagePart part = image_part(f, i, factor);
+        GS_TRY(ensure_stage(sl, k, part.floats));
         // the image before the previous one must have left this staging buffer (a wait on the GPU, not on the host: the
         // previous image's host copy goes on meanwhile); on a slab chain the boundary rows of the newest plane come from
         // the halo stream
@@ -561,13 +573,48 @@ int32_t enqueue_image(gs_ctx *ctx, gs_field *f, int32_t factor, float *host)
         // unused between them -- an 8.3 MB image every 168 us where the link takes 152, tools/ubench/d2h_probe.hip)
         const hipStream_t cs = sl.image_stream(k);
         GS_HIP(hipStreamWaitEvent(cs, sl.staged, 0));
-        GS_HIP(hipMemcpyAsync(host + (fs.g_row0 / q - first) * ocols, sl.stage[k], need * sizeof(float),
-                              hipMemcpyDeviceToHost, cs));
+        GS_HIP(hipMemcpyAsync(host + part.at, sl.stage[k], part.floats * sizeof(float), hipMemcpyDeviceToHost, cs));
         if (w.pending && i == 0) // the abort word as it stands once the launches this image depends on have ended
             GS_HIP(hipMemcpyAsync(w.seen + k, w.words + kWindowMaxTiles, sizeof(int32_t), hipMemcpyDeviceToHost, cs));
         GS_HIP(hipEventRecord(sl.copied[k], cs));
     }
     ctx->downloads++;
+    return GS_OK;
+}
+
+// gs_field_colormap and gs_field_colormap_reduced behind their handle (and factor and slab) checks: this process's rows of
+// the image of `f` reduced by `factor`, painted with the palette.  Factor 1 reads the plane with its pitch; a larger one
+// reduces into staging buffer 0 first.  The RGB image and the palette live on the device for this call alone.
+int32_t paint(gs_ctx *ctx, gs_field *f, int32_t factor, float scale, const uint8_t *palette_rgb, int32_t n_colors,
+              uint8_t *host_rgb)
+{
+    if (!palette_rgb || n_colors < 1 || n_colors > 65536) return fail(GS_ERR_INVALID, "bad palette (%d colours)", n_colors);
+    GS_TRY(sync_all(ctx));
+    if (f->rows == 0 || f->cols == 0) return GS_OK; // nothing to paint (host may be null)
+    if (!host_rgb) return fail(GS_ERR_INVALID, "bad argument");
+    for (size_t i = 0; i < f->s.size(); ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        const FieldSlab &fs = f->s[i];
+        GS_HIP(hipSetDevice(sl.device));
+        const ImagePart part = image_part(f, i, factor);
+        const size_t bytes = part.floats * 3;
+        if (factor > 1) GS_TRY(ensure_stage(sl, 0, part.floats)); // (every stream is idle: the wait above)
+        // (the dense staging buffer is a plane whose pitch is its width)
+        const float *src = factor > 1 ? sl.stage[0] : fs.row0;
+        const int32_t pitch = factor > 1 ? (int32_t)part.cols : f->pitch;
+        uint8_t *dev = nullptr;
+        GS_HIP(hipMalloc(reinterpret_cast<void **>(&dev), bytes + (size_t)n_colors * 3));
+        uint8_t *pal = dev + bytes;
+        hipError_t e = hipMemcpyAsync(pal, palette_rgb, (size_t)n_colors * 3, hipMemcpyHostToDevice, sl.compute);
+        if (e == hipSuccess && factor > 1)
+            e = gs_launch_reduce(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, factor, sl.stage[0], sl.compute);
+        if (e == hipSuccess)
+            e = gs_launch_colormap(src, pitch, part.rows, (int32_t)part.cols, scale, pal, n_colors, dev, sl.compute);
+        if (e == hipSuccess) e = hipMemcpyAsync(host_rgb + part.at * 3, dev, bytes, hipMemcpyDeviceToHost, sl.compute);
+        if (e == hipSuccess) e = hipStreamSynchronize(sl.compute);
+        (void)hipFree(dev);
+        if (e != hipSuccess) return fail(GS_ERR_HIP, "colour mapping failed: %s", hipGetErrorString(e));
+    }
     return GS_OK;
 }
 
@@ -577,23 +624,16 @@ namespace gsi {
 
 int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host)
 {
-    const uint64_t q = (uint64_t)factor;
-    const uint64_t ocols = (f->cols + q - 1) / q, first = f->s.front().g_row0 / q;
     for (size_t i = 0; i < f->s.size(); ++i) {
         SlabRt &sl = ctx->slabs[i];
         const FieldSlab &fs = f->s[i];
         GS_HIP(hipSetDevice(sl.device));
-        const size_t need = (size_t)(((uint64_t)fs.rows + q - 1) / q) * ocols;
-        GS_TRY(ensure_stage(sl, 0, need));
+        const ImagePart part = image_part(f, i, factor);
+        GS_TRY(ensure_stage(sl, 0, part.floats));
         GS_HIP(gs_launch_reduce(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, factor, sl.stage[0], sl.compute));
-        GS_HIP(hipMemcpyAsync(host + (fs.g_row0 / q - first) * ocols, sl.stage[0], need * sizeof(float), hipMemcpyDeviceToHost,
-                              sl.compute));
+        GS_HIP(hipMemcpyAsync(host + part.at, sl.stage[0], part.floats * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
     }
-    for (auto &sl : ctx->slabs) {
-        GS_HIP(hipSetDevice(sl.device));
-        GS_HIP(hipStreamSynchronize(sl.compute));
-    }
-    return GS_OK;
+    return sync_compute(ctx);
 }
 
 } // namespace gsi
@@ -644,63 +684,14 @@ int32_t gs_field_colormap_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, floa
     if (!ctx || !f || f->ctx != ctx) return fail(GS_ERR_INVALID, "bad argument");
     ReducedShape r;
     GS_TRY(reduced_shape(f, factor, &r));
-    if (factor == 1) return gs_field_colormap(ctx, f, scale, palette_rgb, n_colors, host_rgb);
-    if (!palette_rgb || n_colors < 1 || n_colors > 65536) return fail(GS_ERR_INVALID, "bad palette (%d colours)", n_colors);
-    GS_TRY(sync_all(ctx));
-    if (f->rows == 0 || f->cols == 0) return GS_OK; // nothing to paint (host may be null)
-    if (!host_rgb) return fail(GS_ERR_INVALID, "bad argument");
-    const uint64_t q = (uint64_t)factor;
-    for (size_t i = 0; i < f->s.size(); ++i) {
-        SlabRt &sl = ctx->slabs[i];
-        const FieldSlab &fs = f->s[i];
-        GS_HIP(hipSetDevice(sl.device));
-        const int32_t orows = (int32_t)(((uint64_t)fs.rows + q - 1) / q);
-        const size_t bytes = (size_t)orows * r.cols * 3;
-        GS_TRY(ensure_stage(sl, 0, (size_t)orows * r.cols)); // (every stream is idle: the wait above)
-        uint8_t *dev = nullptr;
-        GS_HIP(hipMalloc(reinterpret_cast<void **>(&dev), bytes + (size_t)n_colors * 3));
-        uint8_t *pal = dev + bytes;
-        hipError_t e = hipMemcpyAsync(pal, palette_rgb, (size_t)n_colors * 3, hipMemcpyHostToDevice, sl.compute);
-        if (e == hipSuccess)
-            e = gs_launch_reduce(fs.row0, f->pitch, (int32_t)fs.rows, (int32_t)f->cols, factor, sl.stage[0], sl.compute);
-        if (e == hipSuccess) // the dense staging buffer is a plane whose pitch is its width
-            e = gs_launch_colormap(sl.stage[0], (int32_t)r.cols, orows, (int32_t)r.cols, scale, pal, n_colors, dev, sl.compute);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(host_rgb + (fs.g_row0 / q - r.row0) * r.cols * 3, dev, bytes, hipMemcpyDeviceToHost, sl.compute);
-        if (e == hipSuccess) e = hipStreamSynchronize(sl.compute);
-        (void)hipFree(dev);
-        if (e != hipSuccess) return fail(GS_ERR_HIP, "colour mapping failed: %s", hipGetErrorString(e));
-    }
-    return GS_OK;
+    return paint(ctx, f, factor, scale, palette_rgb, n_colors, host_rgb);
 }
 
 int32_t gs_field_colormap(gs_ctx *ctx, gs_field *f, float scale, const uint8_t *palette_rgb, int32_t n_colors,
                           uint8_t *host_rgb)
 {
     if (!ctx || !f || f->ctx != ctx) return fail(GS_ERR_INVALID, "bad argument");
-    if (!palette_rgb || n_colors < 1 || n_colors > 65536) return fail(GS_ERR_INVALID, "bad palette (%d colours)", n_colors);
-    GS_TRY(sync_all(ctx));
-    if (f->rows == 0 || f->cols == 0) return GS_OK; // nothing to paint (host may be null)
-    if (!host_rgb) return fail(GS_ERR_INVALID, "bad argument");
-    const uint64_t first = f->s.front().g_row0;
-    for (size_t i = 0; i < f->s.size(); ++i) {
-        SlabRt &sl = ctx->slabs[i];
-        const FieldSlab &fs = f->s[i];
-        GS_HIP(hipSetDevice(sl.device));
-        const size_t bytes = (size_t)fs.rows * f->cols * 3;
-        uint8_t *dev = nullptr;
-        GS_HIP(hipMalloc(reinterpret_cast<void **>(&dev), bytes + (size_t)n_colors * 3));
-        uint8_t *pal = dev + bytes;
-        hipError_t e = hipMemcpyAsync(pal, palette_rgb, (size_t)n_colors * 3, hipMemcpyHostToDevice, sl.compute);
-        if (e == hipSuccess)
-            e = gs_launch_colormap(fs.row0, f->pitch, fs.rows, (int32_t)f->cols, scale, pal, n_colors, dev, sl.compute);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(host_rgb + (fs.g_row0 - first) * f->cols * 3, dev, bytes, hipMemcpyDeviceToHost, sl.compute);
-        if (e == hipSuccess) e = hipStreamSynchronize(sl.compute);
-        (void)hipFree(dev);
-        if (e != hipSuccess) return fail(GS_ERR_HIP, "colour mapping failed: %s", hipGetErrorString(e));
-    }
-    return GS_OK;
+    return paint(ctx, f, 1, scale, palette_rgb, n_colors, host_rgb);
 }
 
 // Wait until at most `in_flight` (0 or 1) of the images enqueued so far are still on their way.  1 is what a driver

@@ -8,8 +8,8 @@
 //   gs_ensemble.cpp ensembles: many grids of one shape, each with its own parameters, advanced in shared launches
 //   gs_attached.cpp a context's per-cell data: parameter maps (per-cell feed and kill rates, gs_ctx_set_param_map) and
 //                  domain masks (wall cells that block diffusion, gs_ctx_set_mask) on one grid
-//   gs_summary.cpp summaries of planes and ensemble members (gs_fields_summarize, gs_members_summarize)
-//   gs_histogram.cpp histograms of planes and ensemble members (gs_fields_histogram, gs_members_histogram)
+//   gs_observe.cpp results formed on the device from planes and ensemble members: summaries (gs_fields_summarize,
+//                  gs_members_summarize) and histograms (gs_fields_histogram, gs_members_histogram)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
@@ -109,14 +109,12 @@ struct SlabRt {
     // ghost-row exchange: th0, th1) and around the interior kernel on the compute stream (tc0, tc1)
     std::vector<hipEvent_t> th0, th1, tc0, tc1;
     int timed = 0; // passes recorded since the timing was switched on
-    // summaries (gs_summary.cpp): the row records of this slab's planes -- on slab 0 also what a multi-process summary
-    // exchanges, and an ensemble's records --, grown on demand, freed with the context
-    void *summary = nullptr;
-    size_t summary_bytes = 0;
-    // histograms (gs_histogram.cpp): this slab's u64 counters -- on slab 0 also what a multi-process histogram exchanges,
-    // and an ensemble's counters --, grown on demand, freed with the context
-    void *hist = nullptr;
-    size_t hist_bytes = 0;
+    // What a result formed on the device leaves before the host fetches it (gs_observe.cpp): a summary's row records or a
+    // histogram's u64 counters of this slab's planes -- on slab 0 also what a multi-process call exchanges, and an
+    // ensemble's records or counters --, grown on demand (ensure_scratch), freed with the context.  One buffer serves every
+    // user because each of them synchronises the stream it used before it returns: no two are ever live at the same time.
+    void *scratch = nullptr;
+    size_t scratch_bytes = 0;
 };
 
 // The form of difference sharing (share_mode, gs_tuner.cpp) of runs that have not been tuned: across lanes too -- never
@@ -269,6 +267,7 @@ struct Run; // gs_run: state of one call (below)
 int32_t check_math(const gs_params &p, int32_t math);
 int32_t same_shape(const gs_field *a, const gs_field *b);
 int32_t sync_all(gs_ctx *ctx);
+int32_t sync_compute(gs_ctx *ctx); // every slab's compute stream alone: what a call enqueued there itself has ended
 int32_t refresh_ghosts(gs_ctx *ctx, gs_field *f);
 int min_slab_rows(const gs_ctx *ctx, const gs_field *f);
 GsStepArgs make_args(const gs_ctx *ctx, const gs_field *in_u, const gs_field *in_v,
@@ -321,10 +320,16 @@ void destroy_attached(gs_ctx *ctx);
 // are idle (the blocking download after its wait; resolve_window after a replay): through staging buffer 0, done on return.
 int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);
 
-// gs_summary.cpp
-void destroy_summary_buffers(gs_ctx *ctx);
-// gs_histogram.cpp
-void destroy_histogram_buffers(gs_ctx *ctx);
+// gs_ensemble.cpp: the refusal of a member range that is empty or leaves the ensemble
+int32_t check_member_range(const gs_ensemble *e, uint64_t first, uint64_t count);
+
+// gs_observe.cpp: slab i's scratch buffer (SlabRt::scratch) of at least `bytes` bytes -- `what` names the user in the
+// refusal ("summary", "histogram") --, and its end
+int32_t ensure_scratch(gs_ctx *ctx, int i, size_t bytes, const char *what);
+void destroy_scratch(gs_ctx *ctx);
+// ... and what a call on a list of planes checks first: 1 to 4 of them, all of this context and of one shape, then every
+// stream idle (sync_all)
+int32_t check_planes(gs_ctx *ctx, gs_field *const *fields, int32_t n);
 // gs_rccl.cpp: every rank's `bytes[q]` bytes (rank q's share, the same table on every rank) into `all` at the offsets of the
 // table's prefix sums, this rank's own share from `mine`; device buffers on slab 0's device, on `stream`.  Messages of at
 // most 1 MiB, one per peer and direction in each group (real RCCL has no such limits; the tests' transport double does).

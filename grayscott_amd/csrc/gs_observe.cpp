@@ -1,0 +1,302 @@
+// gs_observe.cpp -- results formed on the device from planes and ensemble members, without downloading them
+// (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize) and histograms (gs_fields_histogram,
+// gs_members_histogram).  Both observe a field list with one launch per slab on its compute stream into that slab's scratch
+// buffer, fetch what the launches left and combine it here on the host, after the results of every slab -- and, in a
+// multi-process context, of every rank (exchange) -- have met; an ensemble's members are observed in one launch on slab 0.
+//   summaries   row records from gs_row_summary_k (gs_summary.hip); the field fold -- rows added in ascending global row
+//               order -- is done on the host.  Ensembles fold on the device (gs_summary_fold_k): two records per member travel.
+//   histograms  zeroed u64 counters filled by gs_plane_hist_k (gs_histogram.hip) and added on the host.  Integers: the
+//               order of the additions does not show.
+// Nothing here touches ghost rows, the tuner, graphs or the context's counters.
+#include "gs_internal.h"
+
+using namespace gsi;
+
+namespace gsi {
+
+int32_t ensure_scratch(gs_ctx *ctx, int i, size_t bytes, const char *what)
+{
+    SlabRt &sl = ctx->slabs[(size_t)i];
+    if (sl.scratch_bytes >= bytes) return GS_OK;
+    GS_HIP(hipSetDevice(sl.device));
+    if (sl.scratch) GS_HIP(hipFree(sl.scratch));
+    sl.scratch = nullptr;
+    sl.scratch_bytes = 0;
+    const hipError_t e = hipMalloc(&sl.scratch, bytes);
+    if (e != hipSuccess) return fail(GS_ERR_NOMEM, "%s buffer of %zu bytes: %s", what, bytes, hipGetErrorString(e));
+    sl.scratch_bytes = bytes;
+    return GS_OK;
+}
+
+void destroy_scratch(gs_ctx *ctx)
+{
+    for (auto &sl : ctx->slabs) {
+        if (!sl.scratch) continue;
+        if (hipSetDevice(sl.device) == hipSuccess) (void)hipFree(sl.scratch);
+        sl.scratch = nullptr;
+        sl.scratch_bytes = 0;
+    }
+}
+
+int32_t check_planes(gs_ctx *ctx, gs_field *const *fields, int32_t n)
+{
+    if (n < 1 || n > 4) return fail(GS_ERR_INVALID, "%d fields (1..4)", n);
+    for (int32_t p = 0; p < n; ++p) {
+        if (!fields[p] || fields[p]->ctx != ctx) return fail(GS_ERR_INVALID, "field %d: null or of another context", p);
+        if (p > 0) GS_TRY(same_shape(fields[0], fields[p]));
+    }
+    return sync_all(ctx); // (also runs again a persistent window launch that gave up: no stale plane is read)
+}
+
+} // namespace gsi
+
+namespace {
+
+// An ensemble of this context, a member range inside it, and then every stream idle.
+int32_t check_members(gs_ctx *ctx, const gs_ensemble *e, uint64_t first, uint64_t count)
+{
+    if (!e) return fail(GS_ERR_INVALID, "null argument");
+    if (e->ctx != ctx) return fail(GS_ERR_INVALID, "ensemble belongs to another context");
+    GS_TRY(check_member_range(e, first, count));
+    return sync_all(ctx);
+}
+
+// Several processes: every rank's bytes to every rank's host.  `bytes[q]` is rank q's share (the same table on every
+// rank), `mine` this rank's own; `all` receives the shares in rank order.  Through slab 0's scratch buffer as send | recv,
+// on its compute stream, which is idle again on return.
+int32_t exchange(gs_ctx *ctx, const void *mine, const std::vector<size_t> &bytes, const char *what, void *all)
+{
+    size_t total = 0;
+    for (const size_t b : bytes) total += b;
+    const size_t own = bytes[(size_t)ctx->rank];
+    SlabRt &sl = ctx->slabs[0];
+    GS_TRY(ensure_scratch(ctx, 0, own + total, what));
+    GS_HIP(hipSetDevice(sl.device));
+    unsigned char *send = static_cast<unsigned char *>(sl.scratch), *recv = send + own;
+    GS_HIP(hipMemcpyAsync(send, mine, own, hipMemcpyHostToDevice, sl.compute));
+    GS_TRY(allgather_bytes(ctx, send, recv, bytes, sl.compute));
+    GS_HIP(hipMemcpyAsync(all, recv, total, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
+    return GS_OK;
+}
+
+// ---- summaries -------------------------------------------------------------------------------------------------------
+static_assert(sizeof(GsRowSummary) == 32, "row record layout");
+static_assert(sizeof(gs_summary) == 32 && offsetof(gs_summary, min) == 16 && offsetof(gs_summary, nonfinite) == 24,
+              "gs_summary layout");
+
+gs_summary empty_summary()
+{
+    gs_summary s;
+    s.sum = 0.0;
+    s.sum_sq = 0.0;
+    s.min = HUGE_VALF;
+    s.max = -HUGE_VALF;
+    s.nonfinite = 0;
+    return s;
+}
+
+// Rows added one after the other in the order given, from +0.0.
+gs_summary fold_rows(const GsRowSummary *rec, size_t rows)
+{
+    gs_summary s = empty_summary();
+    for (size_t r = 0; r < rows; ++r) {
+        const GsRowSummary &x = rec[r];
+        s.sum = s.sum + x.sum;
+        s.sum_sq = s.sum_sq + x.sum_sq;
+        s.min = std::fmin(s.min, x.min);
+        s.max = std::fmax(s.max, x.max);
+        s.nonfinite += x.nonfinite;
+    }
+    return s;
+}
+
+gs_summary from_record(const GsRowSummary &x)
+{
+    gs_summary s;
+    s.sum = x.sum;
+    s.sum_sq = x.sum_sq;
+    s.min = x.min;
+    s.max = x.max;
+    s.nonfinite = x.nonfinite;
+    return s;
+}
+
+// ---- histograms ------------------------------------------------------------------------------------------------------
+constexpr int kHistGroupsPerCu = 8; // workgroups of 4 waves a launch may put on a CU: 8 x (4096 + 4) u32 of LDS fit in 160 KiB
+
+// The rule's scale for n ranges, (float)bins / (hi - lo) in f32, or the refusal of gs_hip.h.  No handle is looked at.
+int32_t check_ranges(const float *lo, const float *hi, int32_t n, int32_t bins, float *scale)
+{
+    if (bins < 1 || bins > 4096) return fail(GS_ERR_INVALID, "%d bins (1..4096)", bins);
+    for (int32_t i = 0; i < n; ++i) {
+        if (!std::isfinite(lo[i]) || !std::isfinite(hi[i]) || !(lo[i] < hi[i]))
+            return fail(GS_ERR_INVALID, "range %d: [%g, %g] is not lo < hi, both finite", i, (double)lo[i], (double)hi[i]);
+        const volatile float width = hi[i] - lo[i]; // (volatile: one f32 subtraction, one f32 division, whatever the host's flags)
+        const volatile float s = (float)bins / width;
+        if (!std::isnormal(width) || !(width > 0.0f) || !std::isnormal(s) || !(s > 0.0f))
+            return fail(GS_ERR_INVALID, "range %d: the width %g of [%g, %g] or the scale %g for %d bins is no normal positive f32",
+                        i, (double)width, (double)lo[i], (double)hi[i], (double)s, bins);
+        scale[i] = s;
+    }
+    return GS_OK;
+}
+
+int64_t max_groups(const gs_ctx *ctx)
+{
+    return (int64_t)kHistGroupsPerCu * (ctx->cu_count > 0 ? ctx->cu_count : 256);
+}
+
+} // namespace
+
+extern "C" {
+
+int32_t gs_fields_summarize(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_summary *out)
+{
+    if (!ctx || !fields || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    if (f0->rows == 0 || f0->cols == 0) { // the same shape on every rank: nobody exchanges anything
+        for (int32_t p = 0; p < n; ++p) out[p] = empty_summary();
+        return GS_OK;
+    }
+    // records of this process's rows, [plane][local row]
+    const size_t nslab = ctx->slabs.size();
+    size_t local_rows = 0;
+    for (const FieldSlab &fs : f0->s) local_rows += (size_t)fs.rows;
+    std::vector<GsRowSummary> local((size_t)n * local_rows);
+    size_t row_at = 0;
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        const size_t rows = (size_t)f0->s[i].rows;
+        GS_TRY(ensure_scratch(ctx, (int)i, (size_t)n * rows * sizeof(GsRowSummary), "summary"));
+        GS_HIP(hipSetDevice(sl.device));
+        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int32_t p = 0; p < n; ++p) planes[p] = fields[p]->s[i].row0;
+        GsRowSummary *rec = static_cast<GsRowSummary *>(sl.scratch);
+        GS_HIP(gs_launch_row_summary(planes, n, f0->pitch, (int64_t)rows, (int32_t)f0->cols, rec, sl.compute));
+        for (int32_t p = 0; p < n; ++p)
+            GS_HIP(hipMemcpyAsync(local.data() + (size_t)p * local_rows + row_at, rec + (size_t)p * rows,
+                                  rows * sizeof(GsRowSummary), hipMemcpyDeviceToHost, sl.compute));
+        row_at += rows;
+    }
+    GS_TRY(sync_compute(ctx));
+    if (ctx->world == 1) {
+        for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(local.data() + (size_t)p * local_rows, local_rows);
+        return GS_OK;
+    }
+    // Several processes: every rank's records to every rank (rank q holds global rows [q L R / S, (q + 1) L R / S) of
+    // S = world x L slabs, the partition of gs_field_create), then the same fold everywhere.
+    const uint64_t S = (uint64_t)ctx->total_slabs(), L = (uint64_t)nslab, R = f0->rows;
+    std::vector<size_t> bytes((size_t)ctx->world);
+    for (int q = 0; q < ctx->world; ++q) {
+        const uint64_t r0 = (uint64_t)q * L * R / S, r1 = (uint64_t)(q + 1) * L * R / S;
+        bytes[(size_t)q] = (size_t)n * (size_t)(r1 - r0) * sizeof(GsRowSummary);
+    }
+    if (bytes[(size_t)ctx->rank] != local.size() * sizeof(GsRowSummary))
+        return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
+    std::vector<GsRowSummary> all((size_t)n * (size_t)R);
+    GS_TRY(exchange(ctx, local.data(), bytes, "summary", all.data()));
+    // rank blocks in rank order, each [plane][its rows]: plane p's records in global row order, then the one fold
+    std::vector<GsRowSummary> plane((size_t)R);
+    for (int32_t p = 0; p < n; ++p) {
+        size_t at = 0, row = 0;
+        for (int q = 0; q < ctx->world; ++q) {
+            const size_t rows = bytes[(size_t)q] / sizeof(GsRowSummary) / (size_t)n;
+            std::memcpy(plane.data() + row, all.data() + at + (size_t)p * rows, rows * sizeof(GsRowSummary));
+            at += (size_t)n * rows;
+            row += rows;
+        }
+        out[p] = fold_rows(plane.data(), plane.size());
+    }
+    return GS_OK;
+}
+
+int32_t gs_members_summarize(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, gs_summary *out)
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_members(ctx, e, first, count));
+    const uint64_t cells = e->rows * e->cols, rows = count * e->rows;
+    const size_t rec_bytes = (size_t)(2 * rows) * sizeof(GsRowSummary), out_bytes = (size_t)(2 * count) * sizeof(GsRowSummary);
+    GS_TRY(ensure_scratch(ctx, 0, rec_bytes + out_bytes, "summary"));
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    GsRowSummary *rec = static_cast<GsRowSummary *>(sl.scratch), *folded = rec + 2 * rows;
+    // the members' rows one after the other: one plane of count x rows rows, pitch cols
+    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
+    GS_HIP(gs_launch_row_summary(planes, 2, (int64_t)e->cols, (int64_t)rows, (int32_t)e->cols, rec, sl.compute));
+    GS_HIP(gs_launch_summary_fold(rec, (int64_t)count, (int64_t)e->rows, folded, sl.compute));
+    std::vector<GsRowSummary> host((size_t)(2 * count));
+    GS_HIP(hipMemcpyAsync(host.data(), folded, out_bytes, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
+    for (size_t i = 0; i < host.size(); ++i) out[i] = from_record(host[i]);
+    return GS_OK;
+}
+
+int32_t gs_fields_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *lo, const float *hi, int32_t bins,
+                            uint64_t *out)
+{
+    if (!ctx || !fields || !lo || !hi || !out) return fail(GS_ERR_INVALID, "null argument");
+    // the ranges before any handle is looked at; a count that is no 1..4 is check_planes' first refusal
+    float scale[4];
+    if (n >= 1 && n <= 4) GS_TRY(check_ranges(lo, hi, n, bins, scale));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    const size_t words = (size_t)n * (size_t)(bins + 3), bytes = words * sizeof(uint64_t);
+    std::fill(out, out + words, (uint64_t)0);
+    if (f0->rows == 0 || f0->cols == 0) return GS_OK; // the same shape on every rank: nobody exchanges anything
+    const size_t nslab = ctx->slabs.size();
+    std::vector<uint64_t> part(nslab * words);
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        GS_TRY(ensure_scratch(ctx, (int)i, bytes, "histogram"));
+        GS_HIP(hipSetDevice(sl.device));
+        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int32_t p = 0; p < n; ++p) planes[p] = fields[p]->s[i].row0;
+        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+        GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+        GS_HIP(gs_launch_histogram(planes, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, lo, hi, scale, bins,
+                                   max_groups(ctx), dev, sl.compute));
+        GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    for (size_t i = 0; i < nslab; ++i)
+        for (size_t w = 0; w < words; ++w) out[w] += part[i * words + w];
+    if (ctx->world == 1) return GS_OK;
+    // Several processes: every rank's counters to every rank, added in the same way everywhere.
+    std::vector<uint64_t> all((size_t)ctx->world * words);
+    GS_TRY(exchange(ctx, out, std::vector<size_t>((size_t)ctx->world, bytes), "histogram", all.data()));
+    std::fill(out, out + words, (uint64_t)0);
+    for (int q = 0; q < ctx->world; ++q)
+        for (size_t w = 0; w < words; ++w) out[w] += all[(size_t)q * words + w];
+    return GS_OK;
+}
+
+int32_t gs_members_histogram(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float lo[2], const float hi[2],
+                             int32_t bins, uint64_t *out)
+{
+    if (!ctx || !lo || !hi || !out) return fail(GS_ERR_INVALID, "null argument");
+    float scale[2];
+    GS_TRY(check_ranges(lo, hi, 2, bins, scale)); // before the ensemble is looked at
+    GS_TRY(check_members(ctx, e, first, count));
+    const uint64_t cells = e->rows * e->cols;
+    const size_t words = (size_t)(2 * count) * (size_t)(bins + 3), bytes = words * sizeof(uint64_t);
+    if (cells == 0) {
+        std::fill(out, out + words, (uint64_t)0);
+        return GS_OK;
+    }
+    GS_TRY(ensure_scratch(ctx, 0, bytes, "histogram"));
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+    // member first + i's U and V are planes 2 i and 2 i + 1 of the launch: `cells` floats from one member to the next
+    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
+    GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+    GS_HIP(gs_launch_histogram(planes, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows, (int32_t)e->cols,
+                               lo, hi, scale, bins, max_groups(ctx), dev, sl.compute));
+    GS_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
+    return GS_OK;
+}
+
+} // extern "C"

@@ -264,11 +264,15 @@ class Summary:
         return float(np.sqrt(max(self.sum_sq / self.cells - m * m, 0.0)))
 
 
+def _handle_array(fields: Sequence["HipConcentration"]):
+    """The planes' handles as the C ABI's field lists take them (an empty list as one null: the library refuses it)."""
+    return (ctypes.c_void_p * max(len(fields), 1))(*[f.handle for f in fields])
+
+
 def summarize_fields(context: "HipContext", fields: Sequence["HipConcentration"]) -> List[Summary]:
     """``gs_fields_summarize``: summaries of 1..4 planes of one shape over the whole global grid, in one call (collective
     in a multi-process context)."""
-    n = len(fields)
-    arr = (ctypes.c_void_p * max(n, 1))(*[f.handle for f in fields])
+    n, arr = len(fields), _handle_array(fields)
     out = (capi.GsSummary * max(n, 1))()
     capi.check(context._lib.gs_fields_summarize(context.handle, arr, n, out))
     rows, cols = fields[0].shape()
@@ -350,7 +354,7 @@ def histogram_fields(context: "HipContext", fields: Sequence["HipConcentration"]
     n, bins = len(fields), int(bins)
     if len(ranges) != n:
         raise ValueError("one (lo, hi) range per field")
-    arr = (ctypes.c_void_p * max(n, 1))(*[f.handle for f in fields])
+    arr = _handle_array(fields)
     lo, hi = _f32_pairs(ranges)
     out = np.zeros((max(n, 1), max(bins, 0) + 3), np.uint64)
     capi.check(context._lib.gs_fields_histogram(context.handle, arr, n, lo, hi, bins,

@@ -32,30 +32,20 @@ def _free_port():
 
 def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, seed, local_slabs=1):
     sys.path.insert(0, ROOT)
-    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
-                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                      HSA_ENABLE_IPC_MODE_LEGACY="0")
-    if transport_lib:
-        os.environ["GS_RCCL_LIBRARY"] = transport_lib
     import torch.distributed as dist
 
-    from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi
+    from grayscott_amd import GsError, Parameters, Simulation
     from grayscott_amd import dist as gsd
+    from tests.helpers import join_ranks
 
-    info = gsd.bootstrap(backend="gloo", device="cpu")     # unique id travels over gloo
-    ndev = capi.device_count()
-    device = rank if ndev >= world else 0
+    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, local_slabs, own_device=True)
     try:
-        sim = Simulation.new(Parameters(), HipArgs(devices=[device] * local_slabs, rank=info.rank, world=info.world,
-                                                   unique_id=info.unique_id))
+        sim = Simulation.new(Parameters(), args)
     except GsError as e:
         if transport_lib:
             raise                      # the double has no reason to refuse
         open(os.path.join(out_dir, f"skip{rank}"), "w").write(str(e))
         return
-    r0, r1 = gsd.slab_range(rows, world, rank) if local_slabs == 1 else \
-        (gsd.slab_range(rows, world * local_slabs, rank * local_slabs)[0],
-         gsd.slab_range(rows, world * local_slabs, (rank + 1) * local_slabs - 1)[1])
     if seed is None:
         species = sim.make_species([rows, cols])
     else:                              # stress fields: every slab boundary carries signal from step 1
@@ -79,17 +69,10 @@ def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, seed, 
 
 @pytest.fixture(scope="module")
 def shm_transport(built):
-    """Compile the librccl test double (host code only; hipcc for the HIP runtime headers)."""
-    from grayscott_amd import _build
+    """The librccl test double (tests/cpp/shm_transport.cpp), compiled on first use."""
+    from tests.helpers import build_shm_transport
 
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    lib = os.path.join(out_dir, "libshm_transport.so")
-    src = os.path.join(ROOT, "tests", "cpp", "shm_transport.cpp")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < os.path.getmtime(src):
-        subprocess.run([_build.hipcc(), "-O2", "-fPIC", "-shared", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                        src, "-o", lib, "-lrt", "-lpthread"], check=True)
-    return lib
+    return build_shm_transport()
 
 
 def _selftest_worker(out_dir):

@@ -3,7 +3,6 @@ grid, bit for bit the single-process one.  All ranks share device 0 through the 
 (tests/cpp/shm_transport.cpp, built as tests/test_gpu_multiprocess.py builds it), whose messages hold at most 1 MiB: one
 grid's row records exceed that per rank, so the all-gather goes in chunks."""
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -16,36 +15,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def shm_transport(built):
-    from grayscott_amd import _build
+    from tests.helpers import build_shm_transport
 
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    lib = os.path.join(out_dir, "libshm_transport.so")
-    src = os.path.join(ROOT, "tests", "cpp", "shm_transport.cpp")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < os.path.getmtime(src):
-        subprocess.run([_build.hipcc(), "-O2", "-fPIC", "-shared", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                        src, "-o", lib, "-lrt", "-lpthread"], check=True)
-    return lib
+    return build_shm_transport()
 
 
 def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, local_slabs):
     sys.path.insert(0, ROOT)
-    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
-                      MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0",
-                      GS_RCCL_LIBRARY=transport_lib)
     import torch.distributed as dist
 
-    from grayscott_amd import HipArgs, Parameters, Simulation
-    from grayscott_amd import dist as gsd
+    from grayscott_amd import Parameters, Simulation
     from grayscott_amd.simulation import SUMMARY_DTYPE
-    from tests.helpers import species_from_arrays, stress_fields
+    from tests.helpers import join_ranks, species_from_arrays, stress_fields
 
-    info = gsd.bootstrap(backend="gloo", device="cpu")
-    sim = Simulation.new(Parameters(), HipArgs(devices=[0] * local_slabs, rank=info.rank, world=info.world,
-                                               unique_id=info.unique_id))
-    S = world * local_slabs
-    r0 = gsd.slab_range(rows, S, rank * local_slabs)[0]
-    r1 = gsd.slab_range(rows, S, (rank + 1) * local_slabs - 1)[1]
+    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, local_slabs)
+    sim = Simulation.new(Parameters(), args)
     u0, v0 = stress_fields((rows, cols), 4)
     species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
     sim.perform_steps(species, steps)
