@@ -8,6 +8,7 @@ has not been built (``__graft_entry__.build()``), and there is no CPU fallback.
 from . import capi  # noqa: F401
 from .capi import GsError  # noqa: F401
 from .simulation import (  # noqa: F401
+    Change,
     Ensemble,
     Evolving,
     HipArgs,
@@ -16,10 +17,11 @@ from .simulation import (  # noqa: F401
     HipContext,
     Parameters,
     Simulation,
+    Snapshot,
     Species,
     Summary,
     pinned_empty,
 )
 
-__all__ = ["capi", "GsError", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "Parameters", "Simulation", "Species", "Summary", "pinned_empty"]
+__all__ = ["capi", "GsError", "Change", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
+           "Parameters", "Simulation", "Snapshot", "Species", "Summary", "pinned_empty"]

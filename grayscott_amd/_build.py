@@ -52,6 +52,8 @@ UNITS = [
     ("gs_histogram.hip", "gs_histogram_k.o", []),
     # reduced result images (block averages in f64): the same float mode, a sub-normal pixel is kept
     ("gs_reduce.hip", "gs_reduce_k.o", []),
+    # two planes compared (row records of |a - b| in f64, the ensembles' fold): the same float mode, sub-normal cells kept
+    ("gs_change.hip", "gs_change_k.o", []),
     # the host side (contexts and schedule, planes, kernel configuration, the window kernel's runtime, RCCL): only the
     # C ABI of include/gs_hip.h is visible outside the library
     ("gs_api.cpp", "gs_api.o", ["-x", "hip", "-fvisibility=hidden"]),

@@ -48,6 +48,7 @@ EXPORTS = (
     "gs_fields_summarize", "gs_members_summarize",
     "gs_fields_histogram", "gs_members_histogram",
     "gs_field_reduced_shape", "gs_field_download_reduced", "gs_field_download_reduced_async", "gs_field_colormap_reduced",
+    "gs_fields_compare", "gs_members_compare", "gs_fields_copy", "gs_members_copy",
 )
 
 
@@ -118,6 +119,20 @@ class GsSummary(ctypes.Structure):
         ("sum_sq", ctypes.c_double),
         ("min", ctypes.c_float),
         ("max", ctypes.c_float),
+        ("nonfinite", ctypes.c_uint64),
+    ]
+
+
+class GsChange(ctypes.Structure):
+    """``gs_change`` (include/gs_hip.h): how far one plane is from another -- the sums of |d| and d * d and the largest |d|
+    over the cells where both are finite (d = a - b in f64), the count of cells whose bits differ and the count of cells
+    where either is not finite -- 40 bytes."""
+
+    _fields_ = [
+        ("sum_abs", ctypes.c_double),
+        ("sum_sq", ctypes.c_double),
+        ("max_abs", ctypes.c_double),
+        ("differing", ctypes.c_uint64),
         ("nonfinite", ctypes.c_uint64),
     ]
 
@@ -201,6 +216,10 @@ def load() -> ctypes.CDLL:
         "gs_field_download_reduced": (i32, [vp, vp, i32, vp]),
         "gs_field_download_reduced_async": (i32, [vp, vp, i32, vp]),
         "gs_field_colormap_reduced": (i32, [vp, vp, i32, f32, vp, i32, vp]),
+        "gs_fields_compare": (i32, [vp, P(vp), P(vp), i32, P(GsChange)]),
+        "gs_members_compare": (i32, [vp, vp, vp, u64, u64, P(GsChange)]),
+        "gs_fields_copy": (i32, [vp, P(vp), P(vp), i32]),
+        "gs_members_copy": (i32, [vp, vp, vp, u64, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -9,7 +9,8 @@
 //   gs_attached.cpp a context's per-cell data: parameter maps (per-cell feed and kill rates, gs_ctx_set_param_map) and
 //                  domain masks (wall cells that block diffusion, gs_ctx_set_mask) on one grid
 //   gs_observe.cpp results formed on the device from planes and ensemble members: summaries (gs_fields_summarize,
-//                  gs_members_summarize) and histograms (gs_fields_histogram, gs_members_histogram)
+//                  gs_members_summarize), histograms (gs_fields_histogram, gs_members_histogram), comparisons of two states
+//                  (gs_fields_compare, gs_members_compare) and the device copies behind snapshots (gs_fields_copy, gs_members_copy)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
@@ -324,12 +325,12 @@ int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);
 int32_t check_member_range(const gs_ensemble *e, uint64_t first, uint64_t count);
 
 // gs_observe.cpp: slab i's scratch buffer (SlabRt::scratch) of at least `bytes` bytes -- `what` names the user in the
-// refusal ("summary", "histogram") --, and its end
+// refusal ("summary", "histogram", "comparison") --, and its end
 int32_t ensure_scratch(gs_ctx *ctx, int i, size_t bytes, const char *what);
 void destroy_scratch(gs_ctx *ctx);
 // ... and what a call on a list of planes checks first: 1 to 4 of them, all of this context and of one shape, then every
-// stream idle (sync_all)
-int32_t check_planes(gs_ctx *ctx, gs_field *const *fields, int32_t n);
+// stream idle (sync_all); `others`, if given: n more planes held to the same (the second planes of a comparison or copy)
+int32_t check_planes(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_field *const *others = nullptr);
 // gs_rccl.cpp: every rank's `bytes[q]` bytes (rank q's share, the same table on every rank) into `all` at the offsets of the
 // table's prefix sums, this rank's own share from `mine`; device buffers on slab 0's device, on `stream`.  Messages of at
 // most 1 MiB, one per peer and direction in each group (real RCCL has no such limits; the tests' transport double does).

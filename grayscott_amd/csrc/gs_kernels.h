@@ -241,3 +241,23 @@ hipError_t gs_launch_summary_fold(const GsRowSummary *rec, int64_t count, int64_
 hipError_t gs_launch_histogram(const float *const *planes, int np, int64_t repeat, int64_t stride, int64_t pitch, int64_t rows,
                                int32_t cols, const float *lo, const float *hi, const float *scale, int32_t bins,
                                int64_t max_groups, unsigned long long *out, hipStream_t s);
+
+// Two planes compared (gs_change.hip; include/gs_hip.h: gs_fields_compare).  One record per (pair, row): the row partials of
+// sum |d| and sum d * d, d = (double)a - (double)b over the cells where both are finite, in the summaries' fold order, with
+// the row's largest |d|, the count of cells whose 32 bits differ (all cells) and of cells where a or b is not finite.  32 bytes.
+struct GsRowChange {
+    double sum_abs, sum_sq, max_abs;
+    uint32_t differing, nonfinite;
+};
+// The fold of a member's row records: gs_change's layout (40 bytes).
+struct GsChangeTotal {
+    double sum_abs, sum_sq, max_abs;
+    uint64_t differing, nonfinite;
+};
+// Records of rows [0, rows) of n (1..4) pairs (a[p], b[p]) of planes that share a row pitch of `pitch` floats (rows may be
+// 64-bit, as for gs_launch_row_summary): out[p * rows + r] for pair p, row r.
+hipError_t gs_launch_row_change(const float *const *a, const float *const *b, int n, int64_t pitch, int64_t rows, int32_t cols,
+                                GsRowChange *out, hipStream_t s);
+// The field fold of gs_hip.h over the records gs_launch_row_change wrote for the two species of `count` ensemble members of
+// `rows` rows each (rec[s * count * rows + i * rows + r]): out[2 i + s], the rows added one after the other in order.
+hipError_t gs_launch_change_fold(const GsRowChange *rec, int64_t count, int64_t rows, GsChangeTotal *out, hipStream_t s);

@@ -1,13 +1,16 @@
 // gs_observe.cpp -- results formed on the device from planes and ensemble members, without downloading them
-// (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize) and histograms (gs_fields_histogram,
-// gs_members_histogram).  Both observe a field list with one launch per slab on its compute stream into that slab's scratch
+// (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize), histograms (gs_fields_histogram,
+// gs_members_histogram) and comparisons of two states (gs_fields_compare, gs_members_compare).  All observe a field list with one launch per slab on its compute stream into that slab's scratch
 // buffer, fetch what the launches left and combine it here on the host, after the results of every slab -- and, in a
 // multi-process context, of every rank (exchange) -- have met; an ensemble's members are observed in one launch on slab 0.
 //   summaries   row records from gs_row_summary_k (gs_summary.hip); the field fold -- rows added in ascending global row
 //               order -- is done on the host.  Ensembles fold on the device (gs_summary_fold_k): two records per member travel.
 //   histograms  zeroed u64 counters filled by gs_plane_hist_k (gs_histogram.hip) and added on the host.  Integers: the
 //               order of the additions does not show.
-// Nothing here touches ghost rows, the tuner, graphs or the context's counters.
+//   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
+//               (row_records); ensembles fold on the device (gs_change_fold_k).
+// The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
+// No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
 
 using namespace gsi;
@@ -38,12 +41,16 @@ void destroy_scratch(gs_ctx *ctx)
     }
 }
 
-int32_t check_planes(gs_ctx *ctx, gs_field *const *fields, int32_t n)
+int32_t check_planes(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_field *const *others)
 {
     if (n < 1 || n > 4) return fail(GS_ERR_INVALID, "%d fields (1..4)", n);
     for (int32_t p = 0; p < n; ++p) {
         if (!fields[p] || fields[p]->ctx != ctx) return fail(GS_ERR_INVALID, "field %d: null or of another context", p);
         if (p > 0) GS_TRY(same_shape(fields[0], fields[p]));
+    }
+    for (int32_t p = 0; others && p < n; ++p) {
+        if (!others[p] || others[p]->ctx != ctx) return fail(GS_ERR_INVALID, "second field %d: null or of another context", p);
+        GS_TRY(same_shape(fields[0], others[p]));
     }
     return sync_all(ctx); // (also runs again a persistent window launch that gave up: no stale plane is read)
 }
@@ -52,12 +59,18 @@ int32_t check_planes(gs_ctx *ctx, gs_field *const *fields, int32_t n)
 
 namespace {
 
-// An ensemble of this context, a member range inside it, and then every stream idle.
-int32_t check_members(gs_ctx *ctx, const gs_ensemble *e, uint64_t first, uint64_t count)
+// An ensemble of this context, a member range inside it -- `other`, if given: a second ensemble of this context with the
+// same shape and member count -- and then every stream idle.
+int32_t check_members(gs_ctx *ctx, const gs_ensemble *e, uint64_t first, uint64_t count, const gs_ensemble *other = nullptr,
+                      bool two = false)
 {
-    if (!e) return fail(GS_ERR_INVALID, "null argument");
-    if (e->ctx != ctx) return fail(GS_ERR_INVALID, "ensemble belongs to another context");
+    if (!e || (two && !other)) return fail(GS_ERR_INVALID, "null argument");
+    if (e->ctx != ctx || (other && other->ctx != ctx)) return fail(GS_ERR_INVALID, "ensemble belongs to another context");
     GS_TRY(check_member_range(e, first, count));
+    if (other && (other->members != e->members || other->rows != e->rows || other->cols != e->cols))
+        return fail(GS_ERR_INVALID, "ensembles of %llu x [%llu, %llu] and %llu x [%llu, %llu]", (unsigned long long)e->members,
+                    (unsigned long long)e->rows, (unsigned long long)e->cols, (unsigned long long)other->members,
+                    (unsigned long long)other->rows, (unsigned long long)other->cols);
     return sync_all(ctx);
 }
 
@@ -77,6 +90,62 @@ int32_t exchange(gs_ctx *ctx, const void *mine, const std::vector<size_t> &bytes
     GS_TRY(allgather_bytes(ctx, send, recv, bytes, sl.compute));
     GS_HIP(hipMemcpyAsync(all, recv, total, hipMemcpyDeviceToHost, sl.compute));
     GS_HIP(hipStreamSynchronize(sl.compute));
+    return GS_OK;
+}
+
+// Row records of n planes (or pairs of planes) of f0's shape over the WHOLE global grid, as [plane][global row]: one launch
+// per slab on its compute stream into the slab's scratch buffer (`launch(slab, rows, records, stream)` writes
+// records[p * rows + r]), and, in a multi-process context, every rank's records to every rank (rank q holds global rows
+// [q L R / S, (q + 1) L R / S) of S = world x L slabs, the partition of gs_field_create).  What folds row records in
+// ascending global row order -- summaries, comparisons -- folds `all` plane by plane.
+template <typename Rec, typename Launch>
+int32_t row_records(gs_ctx *ctx, const gs_field *f0, int32_t n, const char *what, std::vector<Rec> &all, Launch launch)
+{
+    static_assert(sizeof(Rec) == 32, "row record layout");
+    // records of this process's rows, [plane][local row]
+    const size_t nslab = ctx->slabs.size();
+    size_t local_rows = 0;
+    for (const FieldSlab &fs : f0->s) local_rows += (size_t)fs.rows;
+    std::vector<Rec> local((size_t)n * local_rows);
+    size_t row_at = 0;
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        const size_t rows = (size_t)f0->s[i].rows;
+        GS_TRY(ensure_scratch(ctx, (int)i, (size_t)n * rows * sizeof(Rec), what));
+        GS_HIP(hipSetDevice(sl.device));
+        Rec *rec = static_cast<Rec *>(sl.scratch);
+        GS_HIP(launch(i, (int64_t)rows, rec, sl.compute));
+        for (int32_t p = 0; p < n; ++p)
+            GS_HIP(hipMemcpyAsync(local.data() + (size_t)p * local_rows + row_at, rec + (size_t)p * rows, rows * sizeof(Rec),
+                                  hipMemcpyDeviceToHost, sl.compute));
+        row_at += rows;
+    }
+    GS_TRY(sync_compute(ctx));
+    if (ctx->world == 1) {
+        all.swap(local);
+        return GS_OK;
+    }
+    const uint64_t S = (uint64_t)ctx->total_slabs(), L = (uint64_t)nslab, R = f0->rows;
+    std::vector<size_t> bytes((size_t)ctx->world);
+    for (int q = 0; q < ctx->world; ++q) {
+        const uint64_t r0 = (uint64_t)q * L * R / S, r1 = (uint64_t)(q + 1) * L * R / S;
+        bytes[(size_t)q] = (size_t)n * (size_t)(r1 - r0) * sizeof(Rec);
+    }
+    if (bytes[(size_t)ctx->rank] != local.size() * sizeof(Rec))
+        return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
+    std::vector<Rec> blocks((size_t)n * (size_t)R);
+    GS_TRY(exchange(ctx, local.data(), bytes, what, blocks.data()));
+    // rank blocks in rank order, each [plane][its rows]: plane p's records in global row order
+    all.resize((size_t)n * (size_t)R);
+    for (int32_t p = 0; p < n; ++p) {
+        size_t at = 0, row = 0;
+        for (int q = 0; q < ctx->world; ++q) {
+            const size_t rows = bytes[(size_t)q] / sizeof(Rec) / (size_t)n;
+            std::memcpy(all.data() + (size_t)p * (size_t)R + row, blocks.data() + at + (size_t)p * rows, rows * sizeof(Rec));
+            at += (size_t)n * rows;
+            row += rows;
+        }
+    }
     return GS_OK;
 }
 
@@ -122,6 +191,38 @@ gs_summary from_record(const GsRowSummary &x)
     return s;
 }
 
+// ---- comparisons -----------------------------------------------------------------------------------------------------
+static_assert(sizeof(GsRowChange) == 32, "row record layout");
+static_assert(sizeof(gs_change) == 40 && sizeof(GsChangeTotal) == 40 && offsetof(gs_change, max_abs) == 16 &&
+                  offsetof(gs_change, differing) == 24 && offsetof(gs_change, nonfinite) == 32,
+              "gs_change layout");
+
+gs_change no_change()
+{
+    gs_change c;
+    c.sum_abs = 0.0;
+    c.sum_sq = 0.0;
+    c.max_abs = 0.0;
+    c.differing = 0;
+    c.nonfinite = 0;
+    return c;
+}
+
+// Rows added one after the other in the order given, from +0.0.
+gs_change fold_rows(const GsRowChange *rec, size_t rows)
+{
+    gs_change c = no_change();
+    for (size_t r = 0; r < rows; ++r) {
+        const GsRowChange &x = rec[r];
+        c.sum_abs = c.sum_abs + x.sum_abs;
+        c.sum_sq = c.sum_sq + x.sum_sq;
+        c.max_abs = std::fmax(c.max_abs, x.max_abs);
+        c.differing += x.differing;
+        c.nonfinite += x.nonfinite;
+    }
+    return c;
+}
+
 // ---- histograms ------------------------------------------------------------------------------------------------------
 constexpr int kHistGroupsPerCu = 8; // workgroups of 4 waves a launch may put on a CU: 8 x (4096 + 4) u32 of LDS fit in 160 KiB
 
@@ -160,55 +261,13 @@ int32_t gs_fields_summarize(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_
         for (int32_t p = 0; p < n; ++p) out[p] = empty_summary();
         return GS_OK;
     }
-    // records of this process's rows, [plane][local row]
-    const size_t nslab = ctx->slabs.size();
-    size_t local_rows = 0;
-    for (const FieldSlab &fs : f0->s) local_rows += (size_t)fs.rows;
-    std::vector<GsRowSummary> local((size_t)n * local_rows);
-    size_t row_at = 0;
-    for (size_t i = 0; i < nslab; ++i) {
-        SlabRt &sl = ctx->slabs[i];
-        const size_t rows = (size_t)f0->s[i].rows;
-        GS_TRY(ensure_scratch(ctx, (int)i, (size_t)n * rows * sizeof(GsRowSummary), "summary"));
-        GS_HIP(hipSetDevice(sl.device));
+    std::vector<GsRowSummary> rec;
+    GS_TRY(row_records<GsRowSummary>(ctx, f0, n, "summary", rec, [&](size_t i, int64_t rows, GsRowSummary *dev, hipStream_t s) {
         const float *planes[4] = {nullptr, nullptr, nullptr, nullptr};
         for (int32_t p = 0; p < n; ++p) planes[p] = fields[p]->s[i].row0;
-        GsRowSummary *rec = static_cast<GsRowSummary *>(sl.scratch);
-        GS_HIP(gs_launch_row_summary(planes, n, f0->pitch, (int64_t)rows, (int32_t)f0->cols, rec, sl.compute));
-        for (int32_t p = 0; p < n; ++p)
-            GS_HIP(hipMemcpyAsync(local.data() + (size_t)p * local_rows + row_at, rec + (size_t)p * rows,
-                                  rows * sizeof(GsRowSummary), hipMemcpyDeviceToHost, sl.compute));
-        row_at += rows;
-    }
-    GS_TRY(sync_compute(ctx));
-    if (ctx->world == 1) {
-        for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(local.data() + (size_t)p * local_rows, local_rows);
-        return GS_OK;
-    }
-    // Several processes: every rank's records to every rank (rank q holds global rows [q L R / S, (q + 1) L R / S) of
-    // S = world x L slabs, the partition of gs_field_create), then the same fold everywhere.
-    const uint64_t S = (uint64_t)ctx->total_slabs(), L = (uint64_t)nslab, R = f0->rows;
-    std::vector<size_t> bytes((size_t)ctx->world);
-    for (int q = 0; q < ctx->world; ++q) {
-        const uint64_t r0 = (uint64_t)q * L * R / S, r1 = (uint64_t)(q + 1) * L * R / S;
-        bytes[(size_t)q] = (size_t)n * (size_t)(r1 - r0) * sizeof(GsRowSummary);
-    }
-    if (bytes[(size_t)ctx->rank] != local.size() * sizeof(GsRowSummary))
-        return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
-    std::vector<GsRowSummary> all((size_t)n * (size_t)R);
-    GS_TRY(exchange(ctx, local.data(), bytes, "summary", all.data()));
-    // rank blocks in rank order, each [plane][its rows]: plane p's records in global row order, then the one fold
-    std::vector<GsRowSummary> plane((size_t)R);
-    for (int32_t p = 0; p < n; ++p) {
-        size_t at = 0, row = 0;
-        for (int q = 0; q < ctx->world; ++q) {
-            const size_t rows = bytes[(size_t)q] / sizeof(GsRowSummary) / (size_t)n;
-            std::memcpy(plane.data() + row, all.data() + at + (size_t)p * rows, rows * sizeof(GsRowSummary));
-            at += (size_t)n * rows;
-            row += rows;
-        }
-        out[p] = fold_rows(plane.data(), plane.size());
-    }
+        return gs_launch_row_summary(planes, n, f0->pitch, rows, (int32_t)f0->cols, dev, s);
+    }));
+    for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(rec.data() + (size_t)p * (size_t)f0->rows, (size_t)f0->rows);
     return GS_OK;
 }
 
@@ -230,6 +289,92 @@ int32_t gs_members_summarize(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64
     GS_HIP(hipMemcpyAsync(host.data(), folded, out_bytes, hipMemcpyDeviceToHost, sl.compute));
     GS_HIP(hipStreamSynchronize(sl.compute));
     for (size_t i = 0; i < host.size(); ++i) out[i] = from_record(host[i]);
+    return GS_OK;
+}
+
+int32_t gs_fields_compare(gs_ctx *ctx, gs_field *const *a, gs_field *const *b, int32_t n, gs_change *out)
+{
+    if (!ctx || !a || !b || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_planes(ctx, a, n, b));
+    const gs_field *f0 = a[0];
+    for (int32_t p = 0; p < n; ++p) out[p] = no_change();
+    if (f0->rows == 0 || f0->cols == 0) return GS_OK; // the same shape on every rank: nobody exchanges anything
+    std::vector<GsRowChange> rec;
+    GS_TRY(row_records<GsRowChange>(ctx, f0, n, "comparison", rec, [&](size_t i, int64_t rows, GsRowChange *dev, hipStream_t s) {
+        const float *pa[4] = {nullptr, nullptr, nullptr, nullptr}, *pb[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int32_t p = 0; p < n; ++p) {
+            pa[p] = a[p]->s[i].row0;
+            pb[p] = b[p]->s[i].row0;
+        }
+        return gs_launch_row_change(pa, pb, n, f0->pitch, rows, (int32_t)f0->cols, dev, s);
+    }));
+    for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(rec.data() + (size_t)p * (size_t)f0->rows, (size_t)f0->rows);
+    return GS_OK;
+}
+
+int32_t gs_members_compare(gs_ctx *ctx, gs_ensemble *e, gs_ensemble *ref, uint64_t first, uint64_t count, gs_change *out)
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_members(ctx, e, first, count, ref, true));
+    const uint64_t cells = e->rows * e->cols, rows = count * e->rows;
+    if (cells == 0) {
+        for (uint64_t i = 0; i < 2 * count; ++i) out[i] = no_change();
+        return GS_OK;
+    }
+    const size_t rec_bytes = (size_t)(2 * rows) * sizeof(GsRowChange), out_bytes = (size_t)(2 * count) * sizeof(GsChangeTotal);
+    GS_TRY(ensure_scratch(ctx, 0, rec_bytes + out_bytes, "comparison"));
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    GsRowChange *rec = static_cast<GsRowChange *>(sl.scratch);
+    GsChangeTotal *folded = reinterpret_cast<GsChangeTotal *>(rec + 2 * rows);
+    // the members' rows one after the other: one plane of count x rows rows, pitch cols
+    const float *pa[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
+    const float *pb[2] = {ref->u[ref->cur] + first * cells, ref->v[ref->cur] + first * cells};
+    GS_HIP(gs_launch_row_change(pa, pb, 2, (int64_t)e->cols, (int64_t)rows, (int32_t)e->cols, rec, sl.compute));
+    GS_HIP(gs_launch_change_fold(rec, (int64_t)count, (int64_t)e->rows, folded, sl.compute));
+    // (GsChangeTotal is gs_change's layout)
+    GS_HIP(hipMemcpyAsync(out, folded, out_bytes, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
+    return GS_OK;
+}
+
+int32_t gs_fields_copy(gs_ctx *ctx, gs_field *const *dst, gs_field *const *src, int32_t n)
+{
+    if (!ctx || !dst || !src) return fail(GS_ERR_INVALID, "null argument");
+    if (n >= 1 && n <= 4) // (a count that is no 1..4 is check_planes' first refusal)
+        for (int32_t p = 0; p < n; ++p) {
+            if (dst[p] && dst[p] == src[p]) return fail(GS_ERR_INVALID, "field %d would be copied onto itself", p);
+            for (int32_t q = 0; q < p; ++q)
+                if (dst[p] && dst[p] == dst[q]) return fail(GS_ERR_INVALID, "fields %d and %d: one target named twice", q, p);
+        }
+    GS_TRY(check_planes(ctx, dst, n, src));
+    const gs_field *f0 = dst[0];
+    if (f0->rows == 0 || f0->cols == 0) return GS_OK;
+    const size_t pitch_bytes = (size_t)f0->pitch * sizeof(float), row_bytes = (size_t)f0->cols * sizeof(float);
+    for (size_t i = 0; i < ctx->slabs.size(); ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        GS_HIP(hipSetDevice(sl.device));
+        for (int32_t p = 0; p < n; ++p)
+            GS_HIP(hipMemcpy2DAsync(dst[p]->s[i].row0, pitch_bytes, src[p]->s[i].row0, pitch_bytes, row_bytes,
+                                    (size_t)f0->s[i].rows, hipMemcpyDeviceToDevice, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    for (int32_t p = 0; p < n; ++p) dst[p]->ghost_depth = 0; // as after gs_field_upload: the next step refreshes the ghost rows
+    return GS_OK;
+}
+
+int32_t gs_members_copy(gs_ctx *ctx, gs_ensemble *dst, gs_ensemble *src, uint64_t first, uint64_t count)
+{
+    if (!ctx) return fail(GS_ERR_INVALID, "null argument");
+    if (dst && dst == src) return fail(GS_ERR_INVALID, "an ensemble would be copied onto itself");
+    GS_TRY(check_members(ctx, dst, first, count, src, true));
+    const size_t cells = (size_t)(dst->rows * dst->cols), off = (size_t)first * cells, bytes = (size_t)count * cells * sizeof(float);
+    if (bytes == 0) return GS_OK;
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    GS_HIP(hipMemcpyAsync(dst->u[dst->cur] + off, src->u[src->cur] + off, bytes, hipMemcpyDeviceToDevice, sl.compute));
+    GS_HIP(hipMemcpyAsync(dst->v[dst->cur] + off, src->v[src->cur] + off, bytes, hipMemcpyDeviceToDevice, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
     return GS_OK;
 }
 

@@ -279,6 +279,68 @@ def summarize_fields(context: "HipContext", fields: Sequence["HipConcentration"]
     return [Summary.from_c(out[i], rows * cols) for i in range(n)]
 
 
+# ``gs_change`` as a numpy record: what ``Ensemble.changes_since`` returns (40 bytes, the C layout, filled in place).
+CHANGE_DTYPE = np.dtype([("sum_abs", "<f8"), ("sum_sq", "<f8"), ("max_abs", "<f8"), ("differing", "<u8"), ("nonfinite", "<u8")])
+
+
+@dataclass(frozen=True)
+class Change:
+    """How far one plane is from another of the same shape, computed on the device (``gs_change``, include/gs_hip.h):
+    with d = a - b formed in f64 per cell, ``sum_abs`` = sum |d|, ``sum_sq`` = sum d * d (in the summaries' fixed fold order:
+    bit-reproducible) and ``max_abs`` = max |d| over the comparable cells -- those where both planes are finite --,
+    ``differing`` the cells whose 32 bits differ (all cells), ``nonfinite`` the cells where either plane is NaN or
+    infinite, and ``cells``, the planes' number of cells."""
+
+    sum_abs: float
+    sum_sq: float
+    max_abs: float
+    differing: int
+    nonfinite: int
+    cells: int
+
+    @classmethod
+    def from_c(cls, c, cells: int) -> "Change":
+        return cls(float(c.sum_abs), float(c.sum_sq), float(c.max_abs), int(c.differing), int(c.nonfinite), int(cells))
+
+    @property
+    def comparable(self) -> int:
+        """Cells where both planes are finite: the ones the sums and the maximum cover."""
+        return self.cells - self.nonfinite
+
+    @property
+    def equal(self) -> bool:
+        """The two planes hold the same bits in every cell."""
+        return self.differing == 0
+
+    @property
+    def mean_abs(self) -> float:
+        return self.sum_abs / self.comparable if self.comparable else float("nan")
+
+    @property
+    def rms(self) -> float:
+        return float(np.sqrt(self.sum_sq / self.comparable)) if self.comparable else float("nan")
+
+
+def compare_fields(context: "HipContext", a: Sequence["HipConcentration"], b: Sequence["HipConcentration"]) -> List[Change]:
+    """``gs_fields_compare``: plane ``a[i]`` against ``b[i]`` for 1..4 pairs of one shape over the whole global grid, in one
+    call (blocking; collective in a multi-process context)."""
+    if len(a) != len(b):
+        raise ValueError("one second plane per first plane")
+    n = len(a)
+    out = (capi.GsChange * max(n, 1))()
+    capi.check(context._lib.gs_fields_compare(context.handle, _handle_array(a), _handle_array(b), n, out))
+    rows, cols = a[0].shape()
+    return [Change.from_c(out[i], rows * cols) for i in range(n)]
+
+
+def copy_fields(context: "HipContext", dst: Sequence["HipConcentration"], src: Sequence["HipConcentration"]) -> None:
+    """``gs_fields_copy``: ``dst[i]`` receives the cells of ``src[i]`` on the device (1..4 pairs of one shape; blocking).
+    The targets are left as an upload leaves them."""
+    if len(dst) != len(src):
+        raise ValueError("one source per target")
+    capi.check(context._lib.gs_fields_copy(context.handle, _handle_array(dst), _handle_array(src), len(dst)))
+
+
 @dataclass(frozen=True, eq=False)
 class Histogram:
     """A plane's histogram computed on the device (``gs_fields_histogram``; the binning rule is include/gs_hip.h's, in
@@ -566,6 +628,11 @@ class HipConcentration:
         counted on the device (blocking; collective in a multi-process context)."""
         return histogram_fields(context, [self], bins, [range])[0]
 
+    def change_from(self, context: HipContext, other: "HipConcentration") -> Change:
+        """How far this plane is from ``other`` (this minus other, cell by cell in f64) over the whole global grid,
+        computed on the device (``gs_fields_compare``; blocking, collective in a multi-process context)."""
+        return compare_fields(context, [self], [other])[0]
+
     def destroy(self) -> None:
         if self._h and self._ctx._h:
             self._ctx._lib.gs_field_destroy(self._ctx._h, self._h)
@@ -607,6 +674,28 @@ class Evolving:
     def flip(self, context) -> None:
         self._pair[1].finalize(context)
         self._pair.reverse()
+
+
+class Snapshot:
+    """A state of a ``Species`` kept on the device: one U and one V plane of the snapshot's own, filled by a device copy
+    (``gs_fields_copy``) of the species' current in-planes.  Made by ``Species.snapshot``; ``Species.change_since``
+    compares with it, ``Species.restore`` goes back to it."""
+
+    def __init__(self, species: "Species"):
+        self._context = species.context()
+        shape = species.shape()
+        self.u = HipConcentration(self._context, shape)
+        self.v = HipConcentration(self._context, shape)
+        self.update(species)
+
+    def update(self, species: "Species") -> None:
+        """Take the species' current state (blocking: waits for the steps enqueued)."""
+        in_u, in_v, _, _ = species.in_out()
+        copy_fields(self._context, [self.u, self.v], [in_u, in_v])
+
+    def close(self) -> None:
+        self.u.destroy()
+        self.v.destroy()
 
 
 class Species:
@@ -684,6 +773,23 @@ class Species:
         in_u, in_v, _, _ = self.in_out()
         u, v = histogram_fields(self._context, [in_u, in_v], bins, [u_range, v_range])
         return u, v
+
+    def snapshot(self) -> Snapshot:
+        """The current state copied into planes of its own on the device (``gs_fields_copy``; blocking)."""
+        return Snapshot(self)
+
+    def change_since(self, snapshot: Snapshot) -> Tuple[Change, Change]:
+        """(U, V): how far the current state is from ``snapshot`` (current minus snapshot), in one call
+        (``gs_fields_compare``; blocking, collective in a multi-process context)."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = compare_fields(self._context, [in_u, in_v], [snapshot.u, snapshot.v])
+        return u, v
+
+    def restore(self, snapshot: Snapshot) -> None:
+        """Go back to ``snapshot``: its planes are copied into the current in-planes (``gs_fields_copy``; blocking), and
+        the next ``perform_steps`` continues from the snapshot's bits."""
+        in_u, in_v, _, _ = self.in_out()
+        copy_fields(self._context, [in_u, in_v], [snapshot.u, snapshot.v])
 
     def access_result(self, f: Callable):
         return f(self.v._pair[0], self._context)
@@ -787,6 +893,30 @@ class Ensemble:
         out = np.zeros((max(count, 0), 2, max(bins, 0) + 3), np.uint64)
         capi.check(self._ctx._lib.gs_members_histogram(self._ctx.handle, self.handle, first, count, lo, hi, bins,
                                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out
+
+    def snapshot(self) -> "Ensemble":
+        """An ensemble of the same shape and member count on the same context whose members hold this one's current states
+        (``gs_members_copy``; blocking): what ``changes_since`` compares with and ``copy_from`` brings back.  It carries
+        the context's parameters, not this ensemble's: it is a store of states, not something to advance."""
+        snap = Ensemble(self._ctx, self.members, self._shape)
+        snap.copy_from(self)
+        return snap
+
+    def copy_from(self, src: "Ensemble", first: int = 0, count: Optional[int] = None) -> None:
+        """Members ``[first, first + count)`` of ``src``'s current state into the same members of this ensemble
+        (``gs_members_copy``, device to device, blocking); the other members stay as they are."""
+        first, count = self._range(first, count)
+        capi.check(self._ctx._lib.gs_members_copy(self._ctx.handle, self.handle, src.handle, first, count))
+
+    def changes_since(self, ref: "Ensemble", first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """How far members ``[first, first + count)`` are from the same members of ``ref`` (``gs_members_compare``,
+        blocking): a structured array of ``CHANGE_DTYPE`` with shape ``(count, 2)``, column 0 = U, 1 = V -- bit for bit
+        what ``Species.change_since`` gives for lone Species in the members' states."""
+        first, count = self._range(first, count)
+        out = np.zeros((max(count, 0), 2), CHANGE_DTYPE)
+        capi.check(self._ctx._lib.gs_members_compare(self._ctx.handle, self.handle, ref.handle, first, count,
+                                                     out.ctypes.data_as(ctypes.POINTER(capi.GsChange))))
         return out
 
     def prepare_steps(self, steps: int) -> None:

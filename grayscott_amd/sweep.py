@@ -22,6 +22,21 @@ counted on the device (``Ensemble.histograms``; the binning rule is include/gs_h
 above, nan), ``lo[2]`` and ``hi[2]``.  ``--hist-bins B`` (default 256), ``--hist-range-u A:B`` (default 0:1) and
 ``--hist-range-v A:B`` (default 0:0.5) set the bins.  It works together with ``--summary-every`` and ``--no-fields`` and
 leaves the HDF5 file as it is without it.
+
+``--steady-every N`` asks of every member "has it stopped changing?".  A snapshot of the ensemble is kept on the device
+(``Ensemble.snapshot``), taken at step 0; after every N steps and after the last one every member is compared with it on the
+device (``Ensemble.changes_since``: with d = now - snapshot per cell in f64, the sum of |d|, the sum of d * d and the largest
+|d| over the cells finite in both, the count of cells whose bits differ and of cells not finite, for U and V), then the
+snapshot is brought up to date (``gs_members_copy``).  The records go to ``<output stem>.steady.npz``: ``steps[samples]``,
+``max_abs``, ``sum_abs``, ``sum_sq``, ``differing``, ``nonfinite``, each ``[members, samples, 2]`` (last axis: U, V), and
+``settled_step[members]``: the first sampled step at which ``max_abs <= T`` held for both U and V, else -1, with T from
+``--steady-tol T`` (default 0: not one bit's worth of change in value).  The flags merge with the sampling loop of
+``--summary-every`` and ``--histogram-every`` and change no state: the HDF5 file is byte for byte the same with and without
+them.  ``--steady-stop`` ends the run after the first check at which EVERY member is settled: the JSON sidecar's ``steps``
+is then the number of steps taken, and (with or without an early end) its member list carries each member's
+``settled_step``.  What the rule cannot see: it compares states N steps apart, so a pattern whose period divides N --
+an oscillating spot, a rotating spiral that returns onto itself -- looks steady; choose N that is no multiple of a period
+you expect, or run twice with coprime N.  Members do not stop one by one: all advance until all have settled.
 """
 from __future__ import annotations
 
@@ -78,8 +93,20 @@ def parse(argv=None):
     ap.add_argument("--hist-bins", type=int, default=256, metavar="B", help="bins of the histograms (1..4096)")
     ap.add_argument("--hist-range-u", type=value_pair, default=(0.0, 1.0), metavar="A:B", help="range of U's histogram")
     ap.add_argument("--hist-range-v", type=value_pair, default=(0.0, 0.5), metavar="A:B", help="range of V's histogram")
+    ap.add_argument("--steady-every", type=int, default=0, metavar="N",
+                    help="compare every member with its state N steps before, every N steps and at the end "
+                         "(<output stem>.steady.npz)")
+    ap.add_argument("--steady-tol", type=float, default=0.0, metavar="T",
+                    help="a member is settled when max |change| over N steps is at most T for U and V (default 0)")
+    ap.add_argument("--steady-stop", action="store_true", help="end the run once every member is settled")
     add_backend_args(ap)
     args = ap.parse_args(argv)
+    if args.steady_every < 0:
+        ap.error("--steady-every must be at least 1 (0 = off)")
+    if not args.steady_tol >= 0.0:
+        ap.error("--steady-tol must be at least 0")
+    if args.steady_stop and not args.steady_every:
+        ap.error("--steady-stop needs --steady-every")
     if args.summary_every < 0:
         ap.error("--summary-every must be at least 1 (0 = off)")
     if args.histogram_every < 0:
@@ -116,6 +143,10 @@ def hist_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".hist.npz"
 
 
+def steady_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".steady.npz"
+
+
 def sample_steps(steps: int, every: int) -> List[int]:
     """Steps after which the summaries are taken: every ``every`` steps and after the last one."""
     out = list(range(every, steps + 1, every))
@@ -137,6 +168,23 @@ def write_histograms(path: str, steps: List[int], samples: List[np.ndarray], u_r
              hi=np.asarray([u_range[1], v_range[1]], np.float32))
 
 
+def settled_steps(steps: List[int], max_abs: np.ndarray, tol: float) -> np.ndarray:
+    """``settled_step[members]``: the first of ``steps`` at which ``max_abs[member, sample]`` is at most ``tol`` for both U
+    and V, else -1.  ``max_abs``: ``[members, samples, 2]``."""
+    ok = np.all(max_abs <= tol, axis=2)
+    first = np.argmax(ok, axis=1)
+    at = np.asarray(steps, np.int64)
+    return np.where(ok.any(axis=1), at[first] if len(at) else -1, -1).astype(np.int64)
+
+
+def write_steady(path: str, steps: List[int], samples: List[np.ndarray], tol: float) -> np.ndarray:
+    rec = np.stack(samples, axis=1)  # [members, samples, 2] of CHANGE_DTYPE
+    settled = settled_steps(steps, rec["max_abs"], tol)
+    np.savez(path, steps=np.asarray(steps, np.int64), settled_step=settled,
+             **{name: np.ascontiguousarray(rec[name]) for name in rec.dtype.names})
+    return settled
+
+
 def run(args) -> dict:
     if args.steps < 0:
         raise ValueError("--steps must be at least 0")
@@ -147,21 +195,34 @@ def run(args) -> dict:
     t0 = time.perf_counter()
     summary_at = sample_steps(args.steps, args.summary_every) if args.summary_every else []
     hist_at = sample_steps(args.steps, args.histogram_every) if args.histogram_every else []
-    if summary_at or hist_at:
-        done, summaries, hists = 0, [], []
-        for at in sorted(set(summary_at) | set(hist_at)):
+    steady_at = sample_steps(args.steps, args.steady_every) if args.steady_every else []
+    done, settled = 0, None
+    if summary_at or hist_at or steady_at:
+        summaries, hists, changes = [], [], []
+        snap = ens.snapshot() if steady_at else None
+        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at)):
             ens.prepare_steps(at - done)
             done = at
             if at in summary_at:
                 summaries.append(ens.summaries())  # (waits for the steps)
             if at in hist_at:
                 hists.append(ens.histograms(bins=args.hist_bins, u_range=args.hist_range_u, v_range=args.hist_range_v))
+            if at in steady_at:
+                changes.append(ens.changes_since(snap))
+                snap.copy_from(ens)
+                if args.steady_stop and np.all(settled_steps(steady_at[:len(changes)], np.stack(changes, axis=1)["max_abs"],
+                                                             args.steady_tol) >= 0):
+                    break
         if summary_at:
-            write_summaries(summary_path(args.output), summary_at, summaries)
+            write_summaries(summary_path(args.output), summary_at[:len(summaries)], summaries)
         if hist_at:
-            write_histograms(hist_path(args.output), hist_at, hists, args.hist_range_u, args.hist_range_v)
+            write_histograms(hist_path(args.output), hist_at[:len(hists)], hists, args.hist_range_u, args.hist_range_v)
+        if steady_at:
+            settled = write_steady(steady_path(args.output), steady_at[:len(changes)], changes, args.steady_tol)
+            snap.destroy()
     else:
         ens.perform_steps(args.steps)
+        done = args.steps
     elapsed = time.perf_counter() - t0
     if not args.no_fields:
         out = hdf5_min.create(args.output, (len(params),) + shape)
@@ -172,14 +233,17 @@ def run(args) -> dict:
         out.flush()
         del out
     with open(sidecar_path(args.output), "w") as f:
-        json.dump({"shape": list(shape), "steps": args.steps,
-                   "members": [{"index": i, "feed": feed, "kill": kill} for i, feed, kill in members(args)]}, f, indent=1)
+        listed = [{"index": i, "feed": feed, "kill": kill} for i, feed, kill in members(args)]
+        if settled is not None:
+            for m in listed:
+                m["settled_step"] = int(settled[m["index"]])
+        json.dump({"shape": list(shape), "steps": done, "members": listed}, f, indent=1)
     kernel, _ = sim.context.info()
     ens.destroy()
     sim.context.close()
     cells = shape[0] * shape[1]
-    return {"members": len(params), "shape": shape, "steps": args.steps, "seconds": elapsed, "kernel": kernel,
-            "mcells_steps_per_s": len(params) * cells * args.steps / elapsed / 1e6 if elapsed > 0 else 0.0}
+    return {"members": len(params), "shape": shape, "steps": done, "seconds": elapsed, "kernel": kernel,
+            "mcells_steps_per_s": len(params) * cells * done / elapsed / 1e6 if elapsed > 0 else 0.0}
 
 
 def main(argv=None) -> int:

@@ -56,6 +56,23 @@ struct Summary {
     }
 };
 
+// How far one plane is from another of the same shape, computed on the device (gs_change, gs_hip.h): with d = a - b formed
+// in f64 per cell, the sums of |d| and d * d (the summaries' fold order: bit-reproducible) and the largest |d| over the
+// comparable cells -- those finite in both planes --, the cells whose 32 bits differ (all cells), the cells not finite in
+// either plane, and `cells`, the planes' number of cells.
+struct Change {
+    double sum_abs = 0.0, sum_sq = 0.0, max_abs = 0.0;
+    uint64_t differing = 0, nonfinite = 0, cells = 0;
+    static Change from_c(const gs_change &c, uint64_t cells)
+    {
+        return Change{c.sum_abs, c.sum_sq, c.max_abs, c.differing, c.nonfinite, cells};
+    }
+    uint64_t comparable() const { return cells - nonfinite; }
+    bool equal() const { return differing == 0; } // the same bits in every cell
+    double mean_abs() const { return comparable() ? sum_abs / (double)comparable() : std::nan(""); }
+    double rms() const { return comparable() ? std::sqrt(sum_sq / (double)comparable()) : std::nan(""); }
+};
+
 // A plane's histogram computed on the device (gs_fields_histogram; the binning rule is gs_hip.h's): `counts[i]` cells in
 // bin i of `counts.size()` equal bins of [lo, hi] (the last one closed), `below` / `above` the range, `nan`; `size` = the
 // plane's number of cells = the sum of all of them.
@@ -330,6 +347,24 @@ class Evolving {
     std::array<HipConcentration, 2> pair_;
 };
 
+class Species;
+
+// A state of a Species kept on the device: one U and one V plane of its own, filled by a device copy (gs_fields_copy) of the
+// species' current in-planes.  Made by Species::snapshot; Species::change_since compares with it, Species::restore goes
+// back to it.
+class Snapshot {
+  public:
+    inline void update(Species &species); // take the species' current state (blocking)
+    HipConcentration &u() { return u_; }
+    HipConcentration &v() { return v_; }
+
+  private:
+    friend class Species;
+    Snapshot(Context &c, Shape s) : context_(c), u_(HipConcentration::default_(c, s)), v_(HipConcentration::default_(c, s)) {}
+    Context context_;
+    HipConcentration u_, v_;
+};
+
 class Species {
   public:
     // Species::new (concentration/mod.rs:36-59)
@@ -392,6 +427,30 @@ class Species {
         return {Histogram::from_c(out.data(), bins, lo[0], hi[0], s[0] * s[1]),
                 Histogram::from_c(out.data() + bins + 3, bins, lo[1], hi[1], s[0] * s[1])};
     }
+    // the current state copied into planes of its own on the device (gs_fields_copy; blocking)
+    Snapshot snapshot()
+    {
+        Snapshot s(context_, shape());
+        s.update(*this);
+        return s;
+    }
+    // (U, V): how far the current state is from the snapshot (current minus snapshot), in one call (gs_fields_compare;
+    // blocking, collective in a multi-process context)
+    std::pair<Change, Change> change_since(Snapshot &snap)
+    {
+        gs_field *a[2] = {u_.in().raw(), v_.in().raw()}, *b[2] = {snap.u().raw(), snap.v().raw()};
+        gs_change out[2];
+        check(gs_fields_compare(context_->get(), a, b, 2, out));
+        const Shape s = shape();
+        return {Change::from_c(out[0], s[0] * s[1]), Change::from_c(out[1], s[0] * s[1])};
+    }
+    // go back to the snapshot: its planes are copied into the current in-planes (gs_fields_copy; blocking), and the next
+    // perform_steps continues from the snapshot's bits
+    void restore(Snapshot &snap)
+    {
+        gs_field *dst[2] = {u_.in().raw(), v_.in().raw()}, *src[2] = {snap.u().raw(), snap.v().raw()};
+        check(gs_fields_copy(context_->get(), dst, src, 2));
+    }
     std::vector<Precision> make_result_view() { return v_.in().make_scalar_view(context_); }
     void write_result_view(Precision *target, Shape target_shape)
     {
@@ -407,6 +466,12 @@ class Species {
     Context context_;
     Evolving u_, v_;
 };
+
+inline void Snapshot::update(Species &species)
+{
+    gs_field *dst[2] = {u_.raw(), v_.raw()}, *src[2] = {species.u().in().raw(), species.v().in().raw()};
+    check(gs_fields_copy(context_->get(), dst, src, 2));
+}
 
 // Ensemble (gs_ensemble_*): `members` independent grids of one shape on one context, each with its own Parameters and its
 // own U and V; member i evolves bit for bit as a lone Species with its parameters would.  The ensemble tracks its current
@@ -488,8 +553,37 @@ class Ensemble {
             out.push_back(Histogram::from_c(c.data() + i * each, bins, lo[i & 1], hi[i & 1], shape_[0] * shape_[1]));
         return out;
     }
+    // an ensemble of the same shape and member count on the same context whose members hold this one's current states
+    // (gs_members_copy; blocking): a store of states for changes_since and copy_from, with the context's parameters
+    Ensemble snapshot() const
+    {
+        Ensemble snap(ctx_, members_, shape_);
+        snap.copy_from(*this, 0, members_);
+        return snap;
+    }
+    // members [first, first + count) of src's newest state into the same members of this ensemble (gs_members_copy,
+    // device to device, blocking)
+    void copy_from(const Ensemble &src, std::size_t first, std::size_t count)
+    {
+        check(gs_members_copy(ctx_->get(), e_, src.e_, first, count));
+    }
+    // how far members [first, first + count) are from the same members of ref (gs_members_compare, blocking): element
+    // 2 i = U, 2 i + 1 = V of member first + i, bit for bit what Species::change_since gives for lone Species in those states
+    std::vector<Change> changes_since(const Ensemble &ref, std::size_t first, std::size_t count) const
+    {
+        std::vector<gs_change> c(2 * count);
+        check(gs_members_compare(ctx_->get(), e_, ref.e_, first, count, c.data()));
+        std::vector<Change> out;
+        for (const gs_change &x : c) out.push_back(Change::from_c(x, shape_[0] * shape_[1]));
+        return out;
+    }
 
   private:
+    // all members zero, every member with the context's parameters (snapshot)
+    Ensemble(Context ctx, std::size_t members, Shape shape) : ctx_(std::move(ctx)), members_(members), shape_(shape)
+    {
+        check(gs_ensemble_create(ctx_->get(), &e_, members, shape[0], shape[1]));
+    }
     Context ctx_;
     gs_ensemble *e_ = nullptr;
     std::size_t members_;

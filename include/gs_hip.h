@@ -575,6 +575,59 @@ int32_t gs_fields_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t n, con
 int32_t gs_members_histogram(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float lo[2], const float hi[2],
                              int32_t bins, uint64_t *out);
 
+/* Two states compared on the device: how far one plane of the WHOLE global grid is from another of the same shape -- "has
+ * this run stopped changing?" -- without downloading either, and the device copies that give a state to compare with
+ * (snapshots) or to go back to (restores).
+ *
+ * The difference.  Per cell, d = (double)a - (double)b: ONE f64 subtraction of the two f32 cells, rounded to nearest even
+ * (exact unless the exponents lie more than about 29 binades apart).  |d| is exact; d * d is one f64 multiplication, which
+ * cannot overflow for f32 inputs.  Sub-normal cells count as the values they are (never flushed).
+ * Comparable cells.  A cell is comparable when a AND b are finite there.  Any other cell (NaN or +-inf in either) counts in
+ * `nonfinite` and adds +0.0 to the sums and nothing to the maximum.
+ * `differing` compares the cells' 32-bit patterns, over EVERY cell, comparable or not: differing == 0 means that the two
+ * planes are memcmp-equal over their cells; +0 against -0 differs (with d = 0); two NaNs of one bit pattern do not differ,
+ * two of different payloads do.
+ * Fold order -- exactly the summaries', a function of (rows, cols) alone, so that the results are bit-reproducible whatever
+ * the slab count, the process count, the step kernel or the call form, and a member's result is bit for bit that of two
+ * lone Species in the same states:
+ *   1. row partial: each of 64 lanes holds an f64 accumulator starting at +0.0; lane l adds, in this order, |d| (for
+ *      sum_sq: d * d) of the cells at columns 256 k + 4 l + j for k = 0, 1, ... and j = 0..3.  A column >= cols or a cell
+ *      that is not comparable adds nothing;
+ *   2. lane combine: the 64 partials are halved repeatedly, p[0:32] + p[32:64], then p[0:16] + p[16:32], ... down to one;
+ *   3. field fold: the row partials are added one after the other in f64, in ascending GLOBAL row order, from +0.0.
+ * max_abs and the two counts are order-free.
+ *   gs_fields_compare   out[i] for the pair (a[i], b[i]), i < n (1..4 pairs, all planes of one shape on this context, e.g. a
+ *                       Species' U and V against a snapshot's).  a[i] == b[i] is allowed: all zeros.  One wait for enqueued
+ *                       work (as gs_fields_summarize: a persistent window launch that gave up is run again first), one
+ *                       launch per slab, one exchange.  In a multi-process context the call is collective, like gs_run,
+ *                       and every rank receives the result of the global grid.
+ *   gs_members_compare  out[2 i] (U) and out[2 i + 1] (V): member first + i of `e` against member first + i of `ref`, i <
+ *                       count, each ensemble's newest slot.  `ref` is an ensemble of the same context, shape and member
+ *                       count (e itself is allowed: all zeros).
+ * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  An empty plane: all
+ * zeros.
+ *   gs_fields_copy      dst[i] receives the cells of src[i], i < n (1..4), device to device on the slabs' compute streams,
+ *                       in the order of i.  Blocking (it waits for enqueued work first, then for the copies).  dst[i] is
+ *                       left exactly as gs_field_upload leaves a plane: its ghost rows count as stale and the next gs_step /
+ *                       gs_run (or gs_field_finalize) refreshes them, so a run that follows is right under every boundary
+ *                       rule and slab layout.  In a multi-process context every process copies its own rows.
+ *   gs_members_copy     members [first, first + count) of `src`'s newest slot into the same members of `dst`'s newest slot;
+ *                       the other members, both parameter tables and src stay as they are.  Blocking.
+ * GS_ERR_INVALID, all decided before any device work: a null or foreign handle, mixed shapes, n outside 1..4, members
+ * outside the ensemble, ensembles of different shapes or member counts, dst[i] == src[i] (or dst == src), a field named
+ * twice in dst. */
+typedef struct gs_change {
+    double   sum_abs;    /* sum of |d| over the comparable cells, in the summaries' fold order      */
+    double   sum_sq;     /* sum of d * d over the same cells, same order                            */
+    double   max_abs;    /* largest |d|; +0.0 when no cell is comparable                            */
+    uint64_t differing;  /* cells whose 32 bits differ -- ALL cells, non-finite ones included       */
+    uint64_t nonfinite;  /* cells where a or b is NaN or +-inf (they add nothing to the sums / max) */
+} gs_change;             /* 40 bytes */
+int32_t gs_fields_compare(gs_ctx *ctx, gs_field *const *a, gs_field *const *b, int32_t n, gs_change *out);
+int32_t gs_members_compare(gs_ctx *ctx, gs_ensemble *e, gs_ensemble *ref, uint64_t first, uint64_t count, gs_change *out);
+int32_t gs_fields_copy(gs_ctx *ctx, gs_field *const *dst, gs_field *const *src, int32_t n);
+int32_t gs_members_copy(gs_ctx *ctx, gs_ensemble *dst, gs_ensemble *src, uint64_t first, uint64_t count);
+
 /* Measurement hook, not for bindings (tools/rccl_under_load.py): the ghost-row exchange's transport on ONE GPU while the
  * caller keeps the chip busy or idle.  mode 0: a one-rank RCCL communicator, `messages` ncclSend / ncclRecv pairs of
  * `floats` f32 to itself in one group; mode 1: the same bytes as device-to-device copies (the in-process chain's route);

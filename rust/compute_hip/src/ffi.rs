@@ -61,6 +61,18 @@ pub struct gs_summary {
     pub nonfinite: u64,
 }
 
+/// `gs_change` (include/gs_hip.h): how far one plane is from another -- sums of |d| and d * d and the largest |d| over the
+/// cells finite in both (d = a - b in f64), cells whose bits differ, cells not finite in either.  40 bytes.
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default)]
+pub struct gs_change {
+    pub sum_abs: f64,
+    pub sum_sq: f64,
+    pub max_abs: f64,
+    pub differing: u64,
+    pub nonfinite: u64,
+}
+
 extern "C" {
     pub fn gs_abi_version() -> i32;
     pub fn gs_last_error() -> *const c_char;
@@ -157,6 +169,26 @@ extern "C" {
         count: u64,
         out: *mut gs_summary,
     ) -> i32;
+    /// Pair i: `a[i]` against `b[i]`, n = 1..4 pairs of one shape; `out`: n records.
+    pub fn gs_fields_compare(
+        ctx: *mut gs_ctx,
+        a: *const *mut gs_field,
+        b: *const *mut gs_field,
+        n: i32,
+        out: *mut gs_change,
+    ) -> i32;
+    /// `out`: count x 2 records (U, V) of members first + i of `e` against the same members of `reference`.
+    pub fn gs_members_compare(
+        ctx: *mut gs_ctx,
+        e: *mut gs_ensemble,
+        reference: *mut gs_ensemble,
+        first: u64,
+        count: u64,
+        out: *mut gs_change,
+    ) -> i32;
+    /// Device copies: `dst[i]` receives the cells of `src[i]` (snapshots and restores); blocking.
+    pub fn gs_fields_copy(ctx: *mut gs_ctx, dst: *const *mut gs_field, src: *const *mut gs_field, n: i32) -> i32;
+    pub fn gs_members_copy(ctx: *mut gs_ctx, dst: *mut gs_ensemble, src: *mut gs_ensemble, first: u64, count: u64) -> i32;
     /// `out`: n x (bins + 3) counters -- counts[bins], below, above, nan -- by the rule of include/gs_hip.h.
     pub fn gs_fields_histogram(
         ctx: *mut gs_ctx,
