@@ -49,6 +49,7 @@ EXPORTS = (
     "gs_fields_histogram", "gs_members_histogram",
     "gs_field_reduced_shape", "gs_field_download_reduced", "gs_field_download_reduced_async", "gs_field_colormap_reduced",
     "gs_fields_compare", "gs_members_compare", "gs_fields_copy", "gs_members_copy",
+    "gs_members_set_active", "gs_members_get_active",
 )
 
 
@@ -220,6 +221,8 @@ def load() -> ctypes.CDLL:
         "gs_members_compare": (i32, [vp, vp, vp, u64, u64, P(GsChange)]),
         "gs_fields_copy": (i32, [vp, P(vp), P(vp), i32]),
         "gs_members_copy": (i32, [vp, vp, vp, u64, u64]),
+        "gs_members_set_active": (i32, [vp, vp, u64, u64, vp]),
+        "gs_members_get_active": (i32, [vp, vp, u64, u64, vp, vp, P(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -2,6 +2,10 @@
 // advanced in shared launches of the kernels of gs_ensemble.h.  The planes are dense [members, rows, cols] (pitch = cols,
 // no ghost rows: an ensemble lives on one slab), two slots per species; the ensemble tracks which slot is current.
 // Everything is enqueued on the context's compute stream, so gs_sync and the blocking calls see it in order.
+// Active sets (gs_members_set_active): gs_ensemble_run advances the active members only, through the listed forms of the
+// kernels and a device list of their indices.  `cur` flips for the whole ensemble, so an inactive member must read the same
+// through either slot: before its first launch a run copies every inactive member whose newest slot has changed since the
+// last run (retired, or written while inactive) into the other slot, in one launch of gs_members_mirror_k.
 #include "gs_internal.h"
 
 using namespace gsi;
@@ -12,6 +16,16 @@ int32_t gsi::check_member_range(const gs_ensemble *e, uint64_t first, uint64_t c
         return fail(GS_ERR_INVALID, "members [%llu, %llu + %llu) outside the ensemble's %llu", (unsigned long long)first,
                     (unsigned long long)first, (unsigned long long)count, (unsigned long long)e->members);
     return GS_OK;
+}
+
+void gsi::mark_members_written(gs_ensemble *e, uint64_t first, uint64_t count)
+{
+    if (e->all_active()) return;
+    for (uint64_t i = first; i < first + count; ++i)
+        if (!e->active[i] && !e->stale[i]) {
+            e->stale[i] = 1;
+            e->stale_count++;
+        }
 }
 
 namespace {
@@ -34,7 +48,29 @@ void free_planes(gs_ensemble *e)
         e->u[s] = e->v[s] = nullptr;
     }
     if (e->params) (void)hipFree(e->params);
+    if (e->active_list) (void)hipFree(e->active_list);
+    if (e->mirror_list) (void)hipFree(e->mirror_list);
     e->params = nullptr;
+    e->active_list = e->mirror_list = nullptr;
+}
+
+// What a run does first when members are inactive: slot cur of every stale member into slot cur ^ 1, in one launch behind
+// the enqueued work.  (The list travels from the host: the call waits for the stream first, because an earlier mirror
+// launch may still read the buffer.)
+int32_t mirror_stale(gs_ensemble *e, SlabRt &sl)
+{
+    if (e->stale_count == 0) return GS_OK;
+    std::vector<uint32_t> list;
+    list.reserve((size_t)e->stale_count);
+    for (uint64_t i = 0; i < e->members; ++i)
+        if (e->stale[i]) list.push_back((uint32_t)i);
+    GS_HIP(hipStreamSynchronize(sl.compute));
+    GS_HIP(hipMemcpy(e->mirror_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    GS_HIP(gs_launch_members_mirror(e->mirror_list, list.size(), e->u[e->cur], e->v[e->cur], e->u[e->cur ^ 1], e->v[e->cur ^ 1],
+                                    e->rows * e->cols, sl.compute));
+    for (uint32_t i : list) e->stale[i] = 0;
+    e->stale_count = 0;
+    return GS_OK;
 }
 
 GsEnsParams to_device(const gs_params &p)
@@ -158,6 +194,7 @@ int32_t gs_ensemble_seed(gs_ctx *ctx, gs_ensemble *e)
     GS_HIP(hipSetDevice(sl.device));
     GS_HIP(gs_launch_ens_seed(e->u[e->cur], e->v[e->cur], e->members, (int32_t)rows, (int32_t)cols, (int32_t)r0, (int32_t)r1,
                               (int32_t)c0, (int32_t)c1, sl.compute));
+    mark_members_written(e, 0, e->members);
     return GS_OK;
 }
 
@@ -171,6 +208,7 @@ int32_t gs_ensemble_upload(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t
     GS_HIP(hipSetDevice(sl.device));
     if (u) GS_HIP(hipMemcpyAsync(e->u[e->cur] + off, u, bytes, hipMemcpyHostToDevice, sl.compute));
     if (v) GS_HIP(hipMemcpyAsync(e->v[e->cur] + off, v, bytes, hipMemcpyHostToDevice, sl.compute));
+    mark_members_written(e, first, count);
     GS_HIP(hipStreamSynchronize(sl.compute));
     return GS_OK;
 }
@@ -205,12 +243,19 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
     a.rows = (int32_t)e->rows;
     a.cols = (int32_t)e->cols;
     a.zero_halo = ctx->o.boundary; // gs_boundary: 0, 1, 2 or 3 (gs_ctx_create admits no other value)
+    // With an active set: the members that run, through the listed launchers and the list of their indices (GsEnsArgs::first
+    // is then a position in the list); with every member active, today's launchers exactly.
+    const bool listed = !e->all_active();
+    const uint64_t running = listed ? e->active_count : e->members;
+    if (running == 0) return GS_OK; // nobody advances: no launch, no flip
+    if (listed) GS_TRY(mirror_stale(e, sl));
+    const uint32_t *list = e->active_list;
     // The launchers split at kGsEnsMaxGroups workgroups; a `members` above 2^31 goes in slices here.
     auto for_slices = [&](auto &&launch) -> int32_t {
-        for (uint64_t m0 = 0; m0 < e->members; m0 += 0x40000000ull) {
+        for (uint64_t m0 = 0; m0 < running; m0 += 0x40000000ull) {
             GsEnsArgs s = a;
             s.first = (int64_t)m0;
-            s.members = (int32_t)std::min<uint64_t>(e->members - m0, 0x40000000ull);
+            s.members = (int32_t)std::min<uint64_t>(running - m0, 0x40000000ull);
             const hipError_t err = launch(s);
             if (err != hipSuccess) return fail(GS_ERR_HIP, "ensemble kernel launch failed: %s", hipGetErrorString(err));
         }
@@ -222,7 +267,7 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
     const int cpt = gs_ens_resident_cpt((long)e->rows, (long)e->cols, a.zero_halo);
     const uint64_t cells = e->rows * e->cols;
     const uint64_t cus = ctx->cu_count > 0 ? (uint64_t)ctx->cu_count : 256;
-    if (cpt && (cells <= (uint64_t)kGsResidentCells || e->members >= cus)) {
+    if (cpt && (cells <= (uint64_t)kGsResidentCells || running >= cus)) {
         uint64_t left = steps;
         while (left > 0) { // the step count is an int in the kernel
             const int n = left > 0x40000000ull ? 0x40000000 : (int)left;
@@ -232,19 +277,23 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
             a.out_u = e->u[e->cur ^ 1];
             a.out_v = e->v[e->cur ^ 1];
             GS_TRY(for_slices([&](const GsEnsArgs &s) {
+                if (listed)
+                    return fused ? gs_launch_ens_resident_listed_fused(s, list, n, e->fast, sl.compute, &name)
+                                 : gs_launch_ens_resident_listed_strict(s, list, n, e->fast, sl.compute, &name);
                 return fused ? gs_launch_ens_resident_fused(s, n, e->fast, sl.compute, &name)
                              : gs_launch_ens_resident_strict(s, n, e->fast, sl.compute, &name);
             }));
             ctx->last_kernel = name;
             ctx->launches++;
             e->cur ^= n & 1;
+            e->run_steps += (uint64_t)n;
             left -= (uint64_t)n;
         }
         return GS_OK;
     }
     // Windowed form: window shape and steps per launch from gs_run's cost model, counting the workgroups of every member.
     int shape = 0, kmax = 8;
-    pick_tile_config((long)e->rows, (long)e->cols, &shape, &kmax, (long)e->members);
+    pick_tile_config((long)e->rows, (long)e->cols, &shape, &kmax, (long)running);
     uint64_t left = steps;
     const char *full_name = nullptr;
     while (left > 0) { // the short launch first, then full ones
@@ -255,15 +304,92 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
         a.out_u = e->u[e->cur ^ 1];
         a.out_v = e->v[e->cur ^ 1];
         GS_TRY(for_slices([&](const GsEnsArgs &s) {
+            if (listed)
+                return fused ? gs_launch_ens_tile_listed_fused(s, list, n, shape, e->fast, sl.compute, &name)
+                             : gs_launch_ens_tile_listed_strict(s, list, n, shape, e->fast, sl.compute, &name);
             return fused ? gs_launch_ens_tile_fused(s, n, shape, e->fast, sl.compute, &name)
                          : gs_launch_ens_tile_strict(s, n, shape, e->fast, sl.compute, &name);
         }));
         if (!full_name || n == kmax) full_name = name;
         ctx->launches++;
         e->cur ^= 1;
+        e->run_steps += (uint64_t)n;
         left -= (uint64_t)n;
     }
     ctx->last_kernel = full_name;
+    return GS_OK;
+}
+
+int32_t gs_members_set_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const uint8_t *active)
+{
+    GS_TRY(check_ensemble(ctx, e));
+    if (!active) return fail(GS_ERR_INVALID, "null active flags");
+    GS_TRY(check_member_range(e, first, count));
+    if (e->members > 0x80000000ull)
+        return fail(GS_ERR_UNSUPPORTED, "an active set on more than 2^31 members (the list of active members holds 32-bit indices)");
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    GS_HIP(hipStreamSynchronize(sl.compute)); // launches in flight read the list
+    std::vector<uint32_t> list;
+    try {
+        list.reserve((size_t)e->members);
+        if (e->active.empty()) { // the first call: every member active so far (`active` last: the ensemble is as before if one throws)
+            e->missed.assign((size_t)e->members, 0);
+            e->retired_at.assign((size_t)e->members, 0);
+            e->stale.assign((size_t)e->members, 0);
+            e->active.assign((size_t)e->members, 1);
+            e->active_count = e->members;
+        }
+    } catch (const std::bad_alloc &) {
+        return fail(GS_ERR_NOMEM, "out of host memory");
+    }
+    for (int b = 0; b < 2; ++b) {
+        uint32_t *&buf = b ? e->mirror_list : e->active_list;
+        if (buf) continue;
+        const hipError_t err = hipMalloc(reinterpret_cast<void **>(&buf), (size_t)e->members * sizeof(uint32_t));
+        if (err != hipSuccess) {
+            buf = nullptr;
+            return fail(err == hipErrorOutOfMemory ? GS_ERR_NOMEM : GS_ERR_HIP, "active list allocation failed: %s", hipGetErrorString(err));
+        }
+    }
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint64_t m = first + i;
+        const uint8_t want = active[i] ? 1 : 0;
+        if (want == e->active[m]) continue;
+        e->active[m] = want;
+        if (want) { // reactivated: its newest slot is valid as it is; the steps it sat out are settled
+            e->active_count++;
+            e->missed[m] += e->run_steps - e->retired_at[m];
+            e->stale_count -= e->stale[m];
+            e->stale[m] = 0;
+        } else { // retired: the other slot holds an older state (or none) until the next run mirrors it
+            e->active_count--;
+            e->retired_at[m] = e->run_steps;
+            e->stale[m] = 1;
+            e->stale_count++;
+        }
+    }
+    for (uint64_t i = 0; i < e->members; ++i)
+        if (e->active[i]) list.push_back((uint32_t)i);
+    if (!list.empty()) GS_HIP(hipMemcpy(e->active_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return GS_OK;
+}
+
+int32_t gs_members_get_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, uint8_t *active, uint64_t *steps_taken,
+                              uint64_t *active_total)
+{
+    GS_TRY(check_ensemble(ctx, e));
+    if (!active && !steps_taken && !active_total) return fail(GS_ERR_INVALID, "null outputs");
+    GS_TRY(check_member_range(e, first, count));
+    const bool untouched = e->active.empty();
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint64_t m = first + i;
+        const bool on = untouched || e->active[m];
+        if (active) active[i] = on ? 1 : 0;
+        if (steps_taken)
+            steps_taken[i] = untouched ? e->run_steps : e->run_steps - e->missed[m] - (on ? 0 : e->run_steps - e->retired_at[m]);
+    }
+    if (active_total) *active_total = untouched ? e->members : e->active_count;
     return GS_OK;
 }
 

@@ -12,6 +12,10 @@
 // windowed form is gs_ens_tile_nk (tile_steps<ZH = 3>).
 // A workgroup belongs to ONE member, so its parameters are wave-uniform: they are read from the device table with scalar
 // loads (constant address space) into SGPRs.  Member offsets are 64-bit.
+// Listed forms (gs_ens_resident_lk / _lpk / _lnk, gs_ens_tile_lk / _lpk / _lnk): the same bodies for an ensemble with an
+// active set (gs_members_set_active).  The grid covers the ACTIVE members only, and a workgroup takes its member from a
+// device list of their indices (u32, ascending; the kernels' second argument) with one scalar load, where its twin
+// computes it from the workgroup index: the member stays wave-uniform.  GsEnsArgs::first is then a position in the list.
 // Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED and the GS_SUFFIX / GS_TAP
 // macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
 #pragma once
@@ -50,11 +54,16 @@ __device__ __forceinline__ GsStepArgs ens_member_args(const GsEnsArgs &e, int64_
 // with a ring of zeros, thread t owning cells t, t + blockDim.x, ... (CPT of them at most).  The host sizes the
 // workgroup to the waves the member's cells need (an 8 x 16 member: 2 waves), so small members share a CU.
 // (The body is a macro so that the kernel of the clipped and zero-halo rules keeps its code: as a function called from two
-// kernels it compiled one instruction apart.)
-#define GS_ENS_RESIDENT_BODY(CPT, FAST, ZH)                                                                                  \
+// kernels it compiled one instruction apart.)  MEMBER: the workgroup's member, GS_ENS_MEMBER_OF_GROUP or GS_ENS_MEMBER_LISTED.
+typedef __attribute__((address_space(4))) const uint32_t GsEnsListConst;
+// The member of workgroup (or window group) G of a launch: counted from GsEnsArgs::first, or entry first + G of the list of
+// active members (one s_load_dword: G is wave-uniform).
+#define GS_ENS_MEMBER_OF_GROUP(G) (e.first + (int64_t)(G))
+#define GS_ENS_MEMBER_LISTED(G) ((int64_t)((GsEnsListConst *)list)[e.first + (int64_t)(G)])
+#define GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, MEMBER)                                                                          \
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); /* half_diff: MODE.IEEE = 0 */             \
     extern __shared__ float lds[];                                                                                           \
-    const GsStepArgs a = ens_member_args(e, e.first + (int64_t)blockIdx.x);                                                  \
+    const GsStepArgs a = ens_member_args(e, MEMBER);                                                                         \
     const int cells = a.rows * a.cols, cols = a.cols, P = cols + 2, plane = (a.rows + 2) * P;                                \
     const int nthreads = (int)blockDim.x;                                                                                    \
     for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f; /* the rings (and everything else) */             \
@@ -138,70 +147,95 @@ _Pragma("unroll")                                                               
 template <int CPT, int FAST, int ZH>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_k)(GsEnsArgs e, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH)
+    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, GS_ENS_MEMBER_OF_GROUP(blockIdx.x))
 }
 // The periodic rule's instances (GsEnsArgs::zero_halo = 2), kernels of their own name.
 template <int CPT, int FAST>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_pk)(GsEnsArgs e, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, 2)
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 2, GS_ENS_MEMBER_OF_GROUP(blockIdx.x))
 }
 // The zero-flux rule's instances (GsEnsArgs::zero_halo = 3), kernels of their own name.
 template <int CPT, int FAST>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_nk)(GsEnsArgs e, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, 3)
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 3, GS_ENS_MEMBER_OF_GROUP(blockIdx.x))
+}
+// The listed forms: the member from the list of active members (the second argument).
+template <int CPT, int FAST, int ZH>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_lk)(GsEnsArgs e, const uint32_t *list, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, GS_ENS_MEMBER_LISTED(blockIdx.x))
+}
+template <int CPT, int FAST>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_lpk)(GsEnsArgs e, const uint32_t *list, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 2, GS_ENS_MEMBER_LISTED(blockIdx.x))
+}
+template <int CPT, int FAST>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_lnk)(GsEnsArgs e, const uint32_t *list, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 3, GS_ENS_MEMBER_LISTED(blockIdx.x))
 }
 #undef GS_ENS_RESIDENT_BODY
 
 // Windowed form: gs_run_tile_k's load, K steps (tile_steps) and store, for window `blockIdx.x % windows` of member
 // `first + blockIdx.x / windows`.
+// (The body is a macro, like the resident form's, so that gs_ens_tile_k keeps its code beside its listed twin.)
+#define GS_ENS_TILE_BODY(RPW, FAST, MEMBER)                                                                                  \
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); /* half_diff: MODE.IEEE = 0 */             \
+    extern __shared__ float lds[];                                                                                           \
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;                                \
+    const GsStepArgs a = ens_member_args(e, MEMBER(m));                                                                      \
+    constexpr int H = tile_rows(RPW);                                                                                        \
+    const int lane = threadIdx.x & 63;                                                                                       \
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                                       \
+    const int HO = H - 2 * K, WO = kTileCols - 2 * K; /* output rows / columns per window */                                 \
+    const int tiles_c = (a.cols + WO - 1) / WO;                                                                              \
+    const int tr = win / tiles_c, tc = win - tr * tiles_c;                                                                   \
+    const int gr0 = tr * HO - K, gc0 = tc * WO - K; /* member coordinates of window cell (0, 0) */                           \
+    const int gr = gr0 + wave * RPW, gc = gc0 + lane; /* this lane's first cell */                                           \
+    /* load; cells outside the member are zeros (and stay zeros: tile_steps) */                                              \
+    float u[RPW], v[RPW];                                                                                                    \
+    const int cc = min(max(gc, 0), a.cols - 1);                                                                              \
+_Pragma("unroll")                                                                                                            \
+    for (int i = 0; i < RPW; ++i) {                                                                                          \
+        const ptrdiff_t g = (ptrdiff_t)min(max(gr + i, 0), a.rows - 1) * a.pitch + cc;                                       \
+        const bool in = gr + i >= 0 && gr + i < a.rows && gc >= 0 && gc < a.cols;                                            \
+        u[i] = in ? a.in_u[g] : 0.0f;                                                                                        \
+        v[i] = in ? a.in_v[g] : 0.0f;                                                                                        \
+    }                                                                                                                        \
+    const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;                                \
+    /* (a.zero_halo is 0 or 1 here: the periodic rule runs gs_ens_tile_pk) */                                                \
+    if (!edge)                                                                                                               \
+        tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);                                               \
+    else if (a.zero_halo)                                                                                                    \
+        tile_steps<RPW, true, FAST, 1>(a, lds, K, gr, gc, wave, lane, u, v);                                                 \
+    else                                                                                                                     \
+        tile_steps<RPW, true, FAST, 0>(a, lds, K, gr, gc, wave, lane, u, v);                                                 \
+    /* store the window shrunk by K, where it lies in the member */                                                          \
+    if (lane >= K && lane < kTileCols - K && gc < a.cols) {                                                                  \
+_Pragma("unroll")                                                                                                            \
+        for (int i = 0; i < RPW; ++i) {                                                                                      \
+            const int wr = wave * RPW + i;                                                                                   \
+            if (wr >= K && wr < H - K && gr + i < a.rows) {                                                                  \
+                const ptrdiff_t g = (ptrdiff_t)(gr + i) * a.pitch + gc;                                                      \
+                a.out_u[g] = u[i];                                                                                           \
+                a.out_v[g] = v[i];                                                                                           \
+            }                                                                                                                \
+        }                                                                                                                    \
+    }
 template <int RPW, int FAST>
 __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_k)(GsEnsArgs e, int K, int windows)
 {
-    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
-    extern __shared__ float lds[];
-    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
-    const GsStepArgs a = ens_member_args(e, e.first + m);
-    constexpr int H = tile_rows(RPW);
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int HO = H - 2 * K, WO = kTileCols - 2 * K; // output rows / columns per window
-    const int tiles_c = (a.cols + WO - 1) / WO;
-    const int tr = win / tiles_c, tc = win - tr * tiles_c;
-    const int gr0 = tr * HO - K, gc0 = tc * WO - K; // member coordinates of window cell (0, 0)
-    const int gr = gr0 + wave * RPW, gc = gc0 + lane; // this lane's first cell
-    // load; cells outside the member are zeros (and stay zeros: tile_steps)
-    float u[RPW], v[RPW];
-    const int cc = min(max(gc, 0), a.cols - 1);
-#pragma unroll
-    for (int i = 0; i < RPW; ++i) {
-        const ptrdiff_t g = (ptrdiff_t)min(max(gr + i, 0), a.rows - 1) * a.pitch + cc;
-        const bool in = gr + i >= 0 && gr + i < a.rows && gc >= 0 && gc < a.cols;
-        u[i] = in ? a.in_u[g] : 0.0f;
-        v[i] = in ? a.in_v[g] : 0.0f;
-    }
-    const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;
-    // (a.zero_halo is 0 or 1 here: the periodic rule runs gs_ens_tile_pk)
-    if (!edge)
-        tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
-    else if (a.zero_halo)
-        tile_steps<RPW, true, FAST, 1>(a, lds, K, gr, gc, wave, lane, u, v);
-    else
-        tile_steps<RPW, true, FAST, 0>(a, lds, K, gr, gc, wave, lane, u, v);
-    // store the window shrunk by K, where it lies in the member
-    if (lane >= K && lane < kTileCols - K && gc < a.cols) {
-#pragma unroll
-        for (int i = 0; i < RPW; ++i) {
-            const int wr = wave * RPW + i;
-            if (wr >= K && wr < H - K && gr + i < a.rows) {
-                const ptrdiff_t g = (ptrdiff_t)(gr + i) * a.pitch + gc;
-                a.out_u[g] = u[i];
-                a.out_v[g] = v[i];
-            }
-        }
-    }
+    GS_ENS_TILE_BODY(RPW, FAST, GS_ENS_MEMBER_OF_GROUP)
 }
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_lk)(GsEnsArgs e, const uint32_t *list, int K, int windows)
+{
+    GS_ENS_TILE_BODY(RPW, FAST, GS_ENS_MEMBER_LISTED)
+}
+#undef GS_ENS_TILE_BODY
 
 // The periodic rule's windowed form (GsEnsArgs::zero_halo = 2): tile_window_periodic for window `blockIdx.x % windows`
 // of member `first + blockIdx.x / windows`; a window wraps around its own member only.
@@ -211,7 +245,7 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_pk)(GsE
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
     extern __shared__ float lds[];
     const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
-    tile_window_periodic<RPW, FAST>(ens_member_args(e, e.first + m), lds, K, win);
+    tile_window_periodic<RPW, FAST>(ens_member_args(e, GS_ENS_MEMBER_OF_GROUP(m)), lds, K, win);
 }
 
 // The zero-flux rule's windowed form (GsEnsArgs::zero_halo = 3): tile_window_neumann for window `blockIdx.x % windows` of
@@ -222,7 +256,27 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_nk)(GsE
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
     extern __shared__ float lds[];
     const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
-    tile_window_neumann<RPW, FAST>(ens_member_args(e, e.first + m), lds, K, win);
+    tile_window_neumann<RPW, FAST>(ens_member_args(e, GS_ENS_MEMBER_OF_GROUP(m)), lds, K, win);
 }
+
+// The listed forms of the two: window `blockIdx.x % windows` of member list[first + blockIdx.x / windows].
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_lpk)(GsEnsArgs e, const uint32_t *list, int K, int windows)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
+    tile_window_periodic<RPW, FAST>(ens_member_args(e, GS_ENS_MEMBER_LISTED(m)), lds, K, win);
+}
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_lnk)(GsEnsArgs e, const uint32_t *list, int K, int windows)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
+    tile_window_neumann<RPW, FAST>(ens_member_args(e, GS_ENS_MEMBER_LISTED(m)), lds, K, win);
+}
+#undef GS_ENS_MEMBER_OF_GROUP
+#undef GS_ENS_MEMBER_LISTED
 
 } // namespace

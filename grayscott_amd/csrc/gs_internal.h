@@ -250,6 +250,20 @@ struct gs_ensemble {
     GsEnsParams *params = nullptr; // members entries (device)
     int fast = 0;                  // 3 when every member has side weights 0.5 and dt == 1: the .op kernels
     int cur = 0;                   // slot that holds the newest state
+    // The active set (gs_members_set_active).  The vectors stay empty until the first set_active: every member is active.
+    // Invariant gs_ensemble_run relies on: before any of its launches an inactive member holds the same bits in both slots,
+    // so the slot flips of the members that run leave its newest state readable through `cur`.
+    std::vector<uint8_t> active;      // per member: 1 = gs_ensemble_run advances it
+    std::vector<uint8_t> stale;       // per member: inactive, and slot cur ^ 1 does not hold slot cur's bits yet (retired, or
+                                      // written by upload / seed / gs_members_copy since): the next run mirrors it first
+    std::vector<uint64_t> missed;     // per member: steps of gs_ensemble_run it sat out while inactive, up to its last reactivation
+    std::vector<uint64_t> retired_at; // per member: `run_steps` when it was last retired (read while it is inactive)
+    uint64_t run_steps = 0;           // steps gs_ensemble_run has advanced its active members by, over all calls
+    uint64_t active_count = 0;        // members with active[i] != 0 (read when `active` is not empty)
+    uint64_t stale_count = 0;
+    uint32_t *active_list = nullptr;  // device: indices of the active members, ascending (active_count entries)
+    uint32_t *mirror_list = nullptr;  // device: room for `members` indices of members to mirror
+    bool all_active() const { return active.empty() || active_count == members; }
 };
 
 struct gs_field {
@@ -323,6 +337,9 @@ int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);
 
 // gs_ensemble.cpp: the refusal of a member range that is empty or leaves the ensemble
 int32_t check_member_range(const gs_ensemble *e, uint64_t first, uint64_t count);
+// ... and what a call that has written members [first, first + count) of e's newest slot (upload, seed, gs_members_copy) does
+// for the inactive ones among them: they are mirrored into the other slot before the next run
+void mark_members_written(gs_ensemble *e, uint64_t first, uint64_t count);
 
 // gs_observe.cpp: slab i's scratch buffer (SlabRt::scratch) of at least `bytes` bytes -- `what` names the user in the
 // refusal ("summary", "histogram", "comparison") --, and its end

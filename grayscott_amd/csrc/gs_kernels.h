@@ -154,7 +154,8 @@ struct GsEnsArgs {
     const float *in_u, *in_v; // member 0, row 0, column 0 of the input planes
     float *out_u, *out_v;
     const GsEnsParams *params; // members entries (device)
-    int64_t first;             // member of workgroup 0 of this launch (launches are split at kGsEnsMaxGroups)
+    int64_t first;             // member of workgroup 0 of this launch (launches are split at kGsEnsMaxGroups); the listed
+                               // forms (gs_launch_ens_*_listed_*): its position in the list of active members
     int32_t members;           // members in this launch
     int32_t rows, cols;
     int32_t zero_halo;         // gs_boundary: 0 clipped, 1 zero halo, 2 periodic, 3 zero flux
@@ -176,7 +177,9 @@ struct GsEnsArgs {
     const void *gs_tb_map_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                                \
     const void *gs_tb_mask_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                               \
     hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
-    hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name);
+    hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name); \
+    hipError_t gs_launch_ens_resident_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name); \
+    hipError_t gs_launch_ens_tile_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name);
 
 GS_DECLARE_LAUNCHERS(strict)
 GS_DECLARE_LAUNCHERS(fused)
@@ -216,6 +219,11 @@ hipError_t gs_launch_mask_links(const float *mask, uint32_t *link, int32_t pitch
 // rows [r0, r1) x columns [c0, c1).
 hipError_t gs_launch_ens_seed(float *u, float *v, uint64_t members, int32_t rows, int32_t cols, int32_t r0, int32_t r1,
                               int32_t c0, int32_t c1, hipStream_t s);
+// gs_members_mirror_k: U and V of the `n` members list[0 .. n) (device list of member indices) of dense [members, cells]
+// planes copied from (src_u, src_v) to (dst_u, dst_v) -- the two slots of an ensemble -- in launches over (listed member,
+// chunk); 16 bytes per lane when cells % 4 == 0 (every member then starts on a 16-byte boundary), else a dword each.
+hipError_t gs_launch_members_mirror(const uint32_t *list, uint64_t n, const float *src_u, const float *src_v, float *dst_u,
+                                    float *dst_v, uint64_t cells, hipStream_t s);
 
 // Summaries (gs_summary.hip; include/gs_hip.h: gs_fields_summarize).  One record per (plane, row): the row partial of the
 // fold order in gs_hip.h -- 64 lane accumulators over columns 256 k + 4 l + j, halved down to one -- with the row's

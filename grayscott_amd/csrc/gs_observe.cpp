@@ -374,6 +374,7 @@ int32_t gs_members_copy(gs_ctx *ctx, gs_ensemble *dst, gs_ensemble *src, uint64_
     GS_HIP(hipSetDevice(sl.device));
     GS_HIP(hipMemcpyAsync(dst->u[dst->cur] + off, src->u[src->cur] + off, bytes, hipMemcpyDeviceToDevice, sl.compute));
     GS_HIP(hipMemcpyAsync(dst->v[dst->cur] + off, src->v[src->cur] + off, bytes, hipMemcpyDeviceToDevice, sl.compute));
+    mark_members_written(dst, first, count);
     GS_HIP(hipStreamSynchronize(sl.compute));
     return GS_OK;
 }

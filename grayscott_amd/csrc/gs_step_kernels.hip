@@ -285,17 +285,23 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
 // Launches are split so that none dispatches more than kGsEnsMaxGroups workgroups.
 // Resident form: `steps` time steps of every member in one launch; the result is stored in the out-planes when steps is
 // odd, else back in the in-planes.
-hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name)
+// `list` (the listed forms, gs_ensemble.h): device list of the active members' indices -- the launch covers entries
+// [e.first, e.first + e.members) of it and runs the kernels' listed twins, named with a "/listed" suffix; nullptr: members
+// [e.first, e.first + e.members) themselves.
+static hipError_t launch_ens_resident(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[3][2] = GS_RULES(GS_NAMES_OP, "ensemble-resident");
+    static const char *const names[2][3][2] = {GS_RULES(GS_NAMES_OP, "ensemble-resident"), GS_RULES_OF(GS_NAMES_OP, "ensemble-resident", "/listed")};
     // [rule][variant][cells per thread: 1, 2, 4, 8]; the clipped rule has no 8-cell form (gs_ens_resident_cpt)
 #define GS_CPT_FNS(KER, ...) {GS_FN(KER, 1, __VA_ARGS__), GS_FN(KER, 2, __VA_ARGS__), GS_FN(KER, 4, __VA_ARGS__), GS_FN(KER, 8, __VA_ARGS__)}
-    static const void *const fns[4][2][4] = {
-        {{GS_FN(gs_ens_resident_k, 1, 0, 0), GS_FN(gs_ens_resident_k, 2, 0, 0), GS_FN(gs_ens_resident_k, 4, 0, 0), nullptr},
-         {GS_FN(gs_ens_resident_k, 1, kOp, 0), GS_FN(gs_ens_resident_k, 2, kOp, 0), GS_FN(gs_ens_resident_k, 4, kOp, 0), nullptr}},
-        {GS_CPT_FNS(gs_ens_resident_k, 0, 1), GS_CPT_FNS(gs_ens_resident_k, kOp, 1)},
-        {GS_CPT_FNS(gs_ens_resident_pk, 0), GS_CPT_FNS(gs_ens_resident_pk, kOp)},
-        {GS_CPT_FNS(gs_ens_resident_nk, 0), GS_CPT_FNS(gs_ens_resident_nk, kOp)}};
+#define GS_ENS_RESIDENT_FNS(K, PK, NK)                                                                \
+    {{{GS_FN(K, 1, 0, 0), GS_FN(K, 2, 0, 0), GS_FN(K, 4, 0, 0), nullptr},                             \
+      {GS_FN(K, 1, kOp, 0), GS_FN(K, 2, kOp, 0), GS_FN(K, 4, kOp, 0), nullptr}},                      \
+     {GS_CPT_FNS(K, 0, 1), GS_CPT_FNS(K, kOp, 1)},                                                    \
+     {GS_CPT_FNS(PK, 0), GS_CPT_FNS(PK, kOp)},                                                        \
+     {GS_CPT_FNS(NK, 0), GS_CPT_FNS(NK, kOp)}}
+    static const void *const fns[2][4][2][4] = {GS_ENS_RESIDENT_FNS(gs_ens_resident_k, gs_ens_resident_pk, gs_ens_resident_nk),
+                                                GS_ENS_RESIDENT_FNS(gs_ens_resident_lk, gs_ens_resident_lpk, gs_ens_resident_lnk)};
+#undef GS_ENS_RESIDENT_FNS
 #undef GS_CPT_FNS
     const long cells = (long)e.rows * e.cols;
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0) return hipErrorInvalidValue;
@@ -305,8 +311,8 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
     if (!cpt || lds > kGsEnsResidentMaxLds) return hipErrorInvalidValue;
     fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
     const int zh = e.zero_halo >= 2 && e.zero_halo <= 3 ? e.zero_halo : (e.zero_halo ? 1 : 0); // gs_boundary
-    if (name) *name = names[rule_set(zh)][fast ? 1 : 0];
-    const void *fn = fns[zh][fast ? 1 : 0][__builtin_ctz(cpt)];
+    if (name) *name = names[list ? 1 : 0][rule_set(zh)][fast ? 1 : 0];
+    const void *fn = fns[list ? 1 : 0][zh][fast ? 1 : 0][__builtin_ctz(cpt)];
     if (!fn) return hipErrorInvalidValue;
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
         const hipError_t err = ensure_dyn_lds(fn, lds);
@@ -317,28 +323,39 @@ hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int 
         GsEnsArgs args = e;
         args.first = e.first + m0;
         args.members = (int32_t)(e.members - m0 < kGsEnsMaxGroups ? e.members - m0 : kGsEnsMaxGroups);
-        void *kargs[] = {&args, &steps, &to_out};
-        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)args.members), dim3((unsigned)threads), kargs, lds, s);
+        void *kargs[] = {&args, &steps, &to_out}, *largs[] = {&args, &list, &steps, &to_out};
+        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)args.members), dim3((unsigned)threads), list ? largs : kargs, lds, s);
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
 }
-
-// Windowed form: K <= kGsTileMaxSteps steps of every member (in-planes -> out-planes); `shape` as gs_launch_tile's.
-hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name)
+hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name)
 {
-    static const char *const names[3][3][2] = GS_RULES(GS_TILE_NAMES, "ensemble-");
-    static const void *const fns[3][3][2] = {GS_TILE_FNS(gs_ens_tile_k), GS_TILE_FNS(gs_ens_tile_pk), GS_TILE_FNS(gs_ens_tile_nk)};
+    return launch_ens_resident(e, nullptr, steps, fast, s, name);
+}
+hipError_t GS_SUFFIX(gs_launch_ens_resident_listed)(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s,
+                                                    const char **name)
+{
+    return list ? launch_ens_resident(e, list, steps, fast, s, name) : hipErrorInvalidValue;
+}
+
+// Windowed form: K <= kGsTileMaxSteps steps of every member (in-planes -> out-planes); `shape` as gs_launch_tile's; `list` as
+// the resident form's.
+static hipError_t launch_ens_tile(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name)
+{
+    static const char *const names[2][3][3][2] = {GS_RULES(GS_TILE_NAMES, "ensemble-"), GS_RULES_OF(GS_TILE_NAMES, "ensemble-", "/listed")};
+    static const void *const fns[2][3][3][2] = {{GS_TILE_FNS(gs_ens_tile_k), GS_TILE_FNS(gs_ens_tile_pk), GS_TILE_FNS(gs_ens_tile_nk)},
+                                                {GS_TILE_FNS(gs_ens_tile_lk), GS_TILE_FNS(gs_ens_tile_lpk), GS_TILE_FNS(gs_ens_tile_lnk)}};
     static const int rpw[3] = {2, 1, 4};
     const int per = rule_set(e.zero_halo); // the periodic and zero-flux rules: gs_ens_tile_pk / _nk
     if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]))
         return hipErrorInvalidValue;
     fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    if (name) *name = names[per][shape][fast ? 1 : 0];
+    if (name) *name = names[list ? 1 : 0][per][shape][fast ? 1 : 0];
     const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
     const long windows = ((e.rows + ho - 1) / ho) * ((e.cols + wo - 1) / wo);
     if (windows > kGsEnsMaxGroups) return hipErrorInvalidConfiguration;
-    const void *fn = fns[per][shape][fast ? 1 : 0];
+    const void *fn = fns[list ? 1 : 0][per][shape][fast ? 1 : 0];
     const size_t lds = tile_lds_bytes(rpw[shape]);
     {
         const hipError_t err = ensure_dyn_lds(fn, lds);
@@ -350,11 +367,20 @@ hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, i
         GsEnsArgs args = e;
         args.first = e.first + m0;
         args.members = (int32_t)(e.members - m0 < per_launch ? e.members - m0 : per_launch);
-        void *kargs[] = {&args, &k, &wins};
-        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)(args.members * windows)), dim3(kTileWaves * 64), kargs, lds, s);
+        void *kargs[] = {&args, &k, &wins}, *largs[] = {&args, &list, &k, &wins};
+        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)(args.members * windows)), dim3(kTileWaves * 64), list ? largs : kargs, lds, s);
         if (err != hipSuccess) return err;
     }
     return hipSuccess;
+}
+hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name)
+{
+    return launch_ens_tile(e, nullptr, k, shape, fast, s, name);
+}
+hipError_t GS_SUFFIX(gs_launch_ens_tile_listed)(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s,
+                                                const char **name)
+{
+    return list ? launch_ens_tile(e, list, k, shape, fast, s, name) : hipErrorInvalidValue;
 }
 
 hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name)

@@ -74,8 +74,47 @@ __global__ void gs_ens_seed_k(float *u, float *v, uint64_t total, int32_t rows, 
         v[i] = spot ? 1.0f : 0.0f;
     }
 }
+// Ensembles with an active set (gs_members_set_active): U and V of the listed members from one slot of the ensemble to the
+// other, so that a member that no longer advances holds the same bits in both.  T = uint4 (16 bytes per lane; `per` and
+// member offsets in units of T) when a member's cell count is a multiple of 4, else uint32_t.  Workgroup b copies chunk
+// b % chunks -- kMirrorChunk elements of T per plane -- of member list[b / chunks]; member offsets are 64-bit.
+constexpr uint32_t kMirrorChunk = 1024;
+template <typename T>
+__global__ __launch_bounds__(256) void gs_members_mirror_k(const uint32_t *list, const T *su, const T *sv, T *du, T *dv,
+                                                           uint32_t per, uint32_t chunks)
+{
+    const uint32_t m = blockIdx.x / chunks, chunk = blockIdx.x - m * chunks;
+    const uint64_t off = (uint64_t)list[m] * per;
+    const uint32_t i0 = chunk * kMirrorChunk, i1 = i0 + kMirrorChunk < per ? i0 + kMirrorChunk : per;
+    for (uint32_t i = i0 + threadIdx.x; i < i1; i += 256) {
+        du[off + i] = su[off + i];
+        dv[off + i] = sv[off + i];
+    }
+}
 
 } // namespace
+
+hipError_t gs_launch_members_mirror(const uint32_t *list, uint64_t n, const float *src_u, const float *src_v, float *dst_u,
+                                    float *dst_v, uint64_t cells, hipStream_t s)
+{
+    if (n == 0 || cells == 0) return hipSuccess;
+    if (!list || cells > 0x7fffffffull) return hipErrorInvalidValue;
+    const bool wide = cells % 4 == 0 && (reinterpret_cast<uintptr_t>(src_u) | reinterpret_cast<uintptr_t>(src_v) |
+                                         reinterpret_cast<uintptr_t>(dst_u) | reinterpret_cast<uintptr_t>(dst_v)) % 16 == 0;
+    uint32_t per = (uint32_t)(wide ? cells / 4 : cells), chunks = (per + kMirrorChunk - 1) / kMirrorChunk;
+    const void *fn = wide ? reinterpret_cast<const void *>(&gs_members_mirror_k<uint4>)
+                          : reinterpret_cast<const void *>(&gs_members_mirror_k<uint32_t>);
+    const uint64_t per_launch = (uint64_t)kGsEnsMaxGroups / chunks; // members per launch (chunks <= 2^21: cells < 2^31)
+    if (per_launch == 0) return hipErrorInvalidConfiguration;
+    for (uint64_t m0 = 0; m0 < n; m0 += per_launch) {
+        const uint32_t *l = list + m0;
+        const uint64_t count = n - m0 < per_launch ? n - m0 : per_launch;
+        void *kargs[] = {&l, &src_u, &src_v, &dst_u, &dst_v, &per, &chunks};
+        const hipError_t e = hipLaunchKernel(fn, dim3((unsigned)(count * chunks)), dim3(256), kargs, 0, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
 
 hipError_t gs_launch_ens_seed(float *u, float *v, uint64_t members, int32_t rows, int32_t cols, int32_t r0, int32_t r1,
                               int32_t c0, int32_t c1, hipStream_t s)

@@ -898,7 +898,8 @@ class Ensemble:
     def snapshot(self) -> "Ensemble":
         """An ensemble of the same shape and member count on the same context whose members hold this one's current states
         (``gs_members_copy``; blocking): what ``changes_since`` compares with and ``copy_from`` brings back.  It carries
-        the context's parameters, not this ensemble's: it is a store of states, not something to advance."""
+        the context's parameters, not this ensemble's: it is a store of states, not something to advance.  All its members
+        are active and their step counts start at 0, whatever this ensemble's are."""
         snap = Ensemble(self._ctx, self.members, self._shape)
         snap.copy_from(self)
         return snap
@@ -919,12 +920,68 @@ class Ensemble:
                                                      out.ctypes.data_as(ctypes.POINTER(capi.GsChange))))
         return out
 
+    def set_active(self, mask, first: int = 0) -> None:
+        """Active flags of members ``[first, first + len(mask))`` from a bool or uint8 array (``gs_members_set_active``;
+        blocking): ``prepare_steps`` advances the active members only, an inactive member keeps its state -- every reader
+        (``result_views``, ``summaries``, ...) sees it -- and its step count.  The other members keep their flags."""
+        m = np.asarray(mask)
+        if m.dtype != np.bool_ and m.dtype != np.uint8:
+            raise TypeError(f"an active mask is a bool or uint8 array, not {m.dtype}")
+        first = int(first)
+        if m.ndim != 1 or m.size == 0 or first < 0 or first + m.size > self.members:
+            raise ValueError(f"an active mask of shape {m.shape} at member {first} of {self.members}")
+        flags = np.ascontiguousarray(m != 0, np.uint8)
+        capi.check(self._ctx._lib.gs_members_set_active(self._ctx.handle, self.handle, first, flags.size,
+                                                         flags.ctypes.data_as(ctypes.c_void_p)))
+
+    def _flag(self, indices, value: bool) -> None:
+        idx = np.unique(np.asarray(indices, np.int64).ravel())
+        if idx.size == 0:
+            return
+        if idx[0] < 0 or idx[-1] >= self.members:
+            raise IndexError(f"member {int(idx[0] if idx[0] < 0 else idx[-1])} of {self.members}")
+        lo, hi = int(idx[0]), int(idx[-1]) + 1
+        mask = self.active(lo, hi - lo)
+        mask[idx - lo] = value
+        self.set_active(mask, lo)
+
+    def retire(self, indices) -> None:
+        """The members ``indices`` stop advancing (``set_active`` with the others' flags as they are)."""
+        self._flag(indices, False)
+
+    def reactivate(self, indices) -> None:
+        """The members ``indices`` advance again, each from the state it holds."""
+        self._flag(indices, True)
+
+    def _get_active(self, first: int, count: Optional[int], flags: bool, steps: bool):
+        first, count = self._range(first, count)
+        a = np.zeros(max(count, 0), np.uint8) if flags else None
+        t = np.zeros(max(count, 0), np.uint64) if steps else None
+        total = ctypes.c_uint64()
+        capi.check(self._ctx._lib.gs_members_get_active(
+            self._ctx.handle, self.handle, first, count, None if a is None else a.ctypes.data_as(ctypes.c_void_p),
+            None if t is None else t.ctypes.data_as(ctypes.c_void_p), ctypes.byref(total)))
+        return a, t, total.value
+
+    def active(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The active flags of members ``[first, first + count)`` as a bool array."""
+        return self._get_active(first, count, True, False)[0].astype(np.bool_)
+
+    def steps_taken(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """The steps each of members ``[first, first + count)`` has been advanced by since the ensemble was made (int64):
+        a retired member's count stands still."""
+        return self._get_active(first, count, False, True)[1].astype(np.int64)
+
+    def active_count(self) -> int:
+        """How many members of the whole ensemble are active."""
+        return int(self._get_active(0, 1, False, False)[2])
+
     def prepare_steps(self, steps: int) -> None:
-        """Enqueue ``steps`` steps of every member and return (``gs_ensemble_run``); ``context.sync()`` waits."""
+        """Enqueue ``steps`` steps of every active member and return (``gs_ensemble_run``); ``context.sync()`` waits."""
         capi.check(self._ctx._lib.gs_ensemble_run(self._ctx.handle, self.handle, int(steps)))
 
     def perform_steps(self, steps: int) -> None:
-        """``steps`` steps of every member, done on return."""
+        """``steps`` steps of every active member, done on return."""
         self.prepare_steps(steps)
         self._ctx.sync()
 

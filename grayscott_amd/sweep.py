@@ -36,7 +36,17 @@ them.  ``--steady-stop`` ends the run after the first check at which EVERY membe
 is then the number of steps taken, and (with or without an early end) its member list carries each member's
 ``settled_step``.  What the rule cannot see: it compares states N steps apart, so a pattern whose period divides N --
 an oscillating spot, a rotating spiral that returns onto itself -- looks steady; choose N that is no multiple of a period
-you expect, or run twice with coprime N.  Members do not stop one by one: all advance until all have settled.
+you expect, or run twice with coprime N.  Without ``--steady-retire`` members do not stop one by one: all advance until
+all have settled (or to the last step).
+
+``--steady-retire`` (needs ``--steady-every``) stops them one by one: after each check every member with ``max_abs <= T``
+for both U and V is retired (``Ensemble.set_active``) -- it keeps its state, the launches that follow cover the other
+members only, and the run ends when no member is active or the steps are used up.  The snapshot is brought up to date and
+the records go on as before: a retired member equals its snapshot, so its later records are zeros, and ``settled_step``
+keeps its meaning.  The JSON sidecar then carries ``steps_taken`` per member and its top-level ``steps`` is their maximum;
+``<stem>.steady.npz`` gains ``steps_taken[members]``; the HDF5 file holds each member's V after its own ``steps_taken``
+steps -- bit for bit what that member is after as many steps in a run without the flag.  Without the flag every output file is
+what it was.
 """
 from __future__ import annotations
 
@@ -99,6 +109,8 @@ def parse(argv=None):
     ap.add_argument("--steady-tol", type=float, default=0.0, metavar="T",
                     help="a member is settled when max |change| over N steps is at most T for U and V (default 0)")
     ap.add_argument("--steady-stop", action="store_true", help="end the run once every member is settled")
+    ap.add_argument("--steady-retire", action="store_true",
+                    help="retire every member at the check that finds it settled: it keeps its state and stops advancing")
     add_backend_args(ap)
     args = ap.parse_args(argv)
     if args.steady_every < 0:
@@ -107,6 +119,8 @@ def parse(argv=None):
         ap.error("--steady-tol must be at least 0")
     if args.steady_stop and not args.steady_every:
         ap.error("--steady-stop needs --steady-every")
+    if args.steady_retire and not args.steady_every:
+        ap.error("--steady-retire needs --steady-every")
     if args.summary_every < 0:
         ap.error("--summary-every must be at least 1 (0 = off)")
     if args.histogram_every < 0:
@@ -177,11 +191,18 @@ def settled_steps(steps: List[int], max_abs: np.ndarray, tol: float) -> np.ndarr
     return np.where(ok.any(axis=1), at[first] if len(at) else -1, -1).astype(np.int64)
 
 
-def write_steady(path: str, steps: List[int], samples: List[np.ndarray], tol: float) -> np.ndarray:
+def retire_mask(changes: np.ndarray, tol: float) -> np.ndarray:
+    """``bool[members]``: the members one steady check finds settled -- ``max_abs <= tol`` for both U and V.  ``changes``:
+    the ``[members, 2]`` record of ``Ensemble.changes_since``.  (A NaN ``tol`` or ``max_abs`` settles nobody.)"""
+    return np.all(changes["max_abs"] <= tol, axis=1)
+
+
+def write_steady(path: str, steps: List[int], samples: List[np.ndarray], tol: float, steps_taken=None) -> np.ndarray:
     rec = np.stack(samples, axis=1)  # [members, samples, 2] of CHANGE_DTYPE
     settled = settled_steps(steps, rec["max_abs"], tol)
+    extra = {} if steps_taken is None else {"steps_taken": np.asarray(steps_taken, np.int64)}
     np.savez(path, steps=np.asarray(steps, np.int64), settled_step=settled,
-             **{name: np.ascontiguousarray(rec[name]) for name in rec.dtype.names})
+             **{name: np.ascontiguousarray(rec[name]) for name in rec.dtype.names}, **extra)
     return settled
 
 
@@ -196,7 +217,7 @@ def run(args) -> dict:
     summary_at = sample_steps(args.steps, args.summary_every) if args.summary_every else []
     hist_at = sample_steps(args.steps, args.histogram_every) if args.histogram_every else []
     steady_at = sample_steps(args.steps, args.steady_every) if args.steady_every else []
-    done, settled = 0, None
+    done, settled, taken = 0, None, None
     if summary_at or hist_at or steady_at:
         summaries, hists, changes = [], [], []
         snap = ens.snapshot() if steady_at else None
@@ -210,6 +231,12 @@ def run(args) -> dict:
             if at in steady_at:
                 changes.append(ens.changes_since(snap))
                 snap.copy_from(ens)
+                if args.steady_retire:
+                    resting = retire_mask(changes[-1], args.steady_tol)
+                    if np.any(resting & ens.active()):
+                        ens.set_active(~resting)  # (a retired member equals its snapshot: it stays in the mask)
+                    if resting.all():
+                        break
                 if args.steady_stop and np.all(settled_steps(steady_at[:len(changes)], np.stack(changes, axis=1)["max_abs"],
                                                              args.steady_tol) >= 0):
                     break
@@ -218,7 +245,11 @@ def run(args) -> dict:
         if hist_at:
             write_histograms(hist_path(args.output), hist_at[:len(hists)], hists, args.hist_range_u, args.hist_range_v)
         if steady_at:
-            settled = write_steady(steady_path(args.output), steady_at[:len(changes)], changes, args.steady_tol)
+            if args.steady_retire:
+                sim.context.sync()
+                taken = ens.steps_taken()
+                done = int(taken.max())
+            settled = write_steady(steady_path(args.output), steady_at[:len(changes)], changes, args.steady_tol, taken)
             snap.destroy()
     else:
         ens.perform_steps(args.steps)
@@ -237,13 +268,17 @@ def run(args) -> dict:
         if settled is not None:
             for m in listed:
                 m["settled_step"] = int(settled[m["index"]])
+        if taken is not None:
+            for m in listed:
+                m["steps_taken"] = int(taken[m["index"]])
         json.dump({"shape": list(shape), "steps": done, "members": listed}, f, indent=1)
     kernel, _ = sim.context.info()
     ens.destroy()
     sim.context.close()
     cells = shape[0] * shape[1]
+    member_steps = len(params) * done if taken is None else int(taken.sum())  # (retired members took fewer)
     return {"members": len(params), "shape": shape, "steps": done, "seconds": elapsed, "kernel": kernel,
-            "mcells_steps_per_s": len(params) * cells * done / elapsed / 1e6 if elapsed > 0 else 0.0}
+            "mcells_steps_per_s": member_steps * cells / elapsed / 1e6 if elapsed > 0 else 0.0}
 
 
 def main(argv=None) -> int:

@@ -527,6 +527,26 @@ class Ensemble {
         prepare_steps(steps);
         ctx_->sync();
     }
+    // active flags of members [first, first + mask.size()) (gs_members_set_active, blocking; nonzero = active): the steps
+    // advance the active members only, an inactive member keeps its state -- every reader sees it -- and its step count
+    void set_active(const std::vector<uint8_t> &mask, std::size_t first = 0)
+    {
+        check(gs_members_set_active(ctx_->get(), e_, first, mask.size(), mask.data()));
+    }
+    // the active flags (0 or 1) of all members
+    std::vector<uint8_t> active() const
+    {
+        std::vector<uint8_t> out(members_);
+        check(gs_members_get_active(ctx_->get(), e_, 0, members_, out.data(), nullptr, nullptr));
+        return out;
+    }
+    // the steps every member has been advanced by since the ensemble was made
+    std::vector<uint64_t> steps_taken() const
+    {
+        std::vector<uint64_t> out(members_);
+        check(gs_members_get_active(ctx_->get(), e_, 0, members_, nullptr, out.data(), nullptr));
+        return out;
+    }
     // summaries of members [first, first + count) from the newest state (gs_members_summarize, blocking): element
     // 2 i = U, 2 i + 1 = V of member first + i, bit for bit what Species::summary gives for a lone Species in that state
     std::vector<Summary> summaries(std::size_t first, std::size_t count) const

@@ -513,6 +513,35 @@ int32_t gs_ensemble_upload(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t
 int32_t gs_ensemble_download(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, int32_t species, float *host);
 int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps);
 
+/* Active sets: members that have settled stop advancing.  Every member of an ensemble has an ACTIVE flag (set at creation)
+ * and a STEP COUNT: the steps gs_ensemble_run has advanced it by since the ensemble was created.
+ *   gs_members_set_active  active[i] != 0: member first + i is active, i < count; the other members keep their flags.
+ *                          Blocking: it waits for enqueued work.  It touches neither parameters nor cells as seen through
+ *                          the newest slot.
+ *   gs_members_get_active  active[i] (0 or 1) and steps_taken[i] of member first + i, i < count, and *active_total: the
+ *                          number of active members of the WHOLE ensemble.  Any of the three may be NULL, not all.  No device
+ *                          work: steps that are enqueued count as taken.
+ * Inactive means: gs_ensemble_run(steps) advances the active members only -- an inactive member keeps its bits and its step
+ * count, whatever the number and parity of the runs; an active member is still bit for bit what gs_run makes of a lone
+ * Species with its parameters and initial state after its OWN step count.  With no active member gs_ensemble_run is GS_OK
+ * and launches nothing.  With a proper subset active it runs the listed forms of the ensemble kernels -- their workgroups
+ * take their member from a device list of the active members' indices --, gs_ctx_info names them with a "/listed" suffix
+ * ("ensemble-resident/strict.op/listed"), and the kernel form and its configuration are chosen for the members that run;
+ * with every member active (again) it runs exactly what an ensemble without an active set runs.
+ * What readers see: every call that reads the newest slot -- gs_ensemble_download, gs_members_summarize, gs_members_histogram,
+ * gs_members_compare, gs_members_copy as source -- returns the held state of an inactive member.
+ * What writers do: gs_ensemble_seed, gs_ensemble_upload, gs_ensemble_set_params and gs_members_copy (as destination) work on
+ * inactive members as before, and the written state is what readers see afterwards and what the member holds from then on;
+ * a reactivated member continues from it (no copy is made).  Step counts are neither copied by gs_members_copy nor reset by
+ * anything.  The first gs_ensemble_run after members were retired, or written while inactive, waits for enqueued work and
+ * copies those members into the ensemble's other slot (one launch) before it advances the rest.
+ * GS_ERR_INVALID, all decided before any device work: a null or foreign handle, members outside the ensemble, a null
+ * `active` (set_active), all three outputs null (get_active).  GS_ERR_UNSUPPORTED: set_active on an ensemble of more than
+ * 2^31 members (the list holds 32-bit indices). */
+int32_t gs_members_set_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const uint8_t *active);
+int32_t gs_members_get_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, uint8_t *active, uint64_t *steps_taken,
+                              uint64_t *active_total);
+
 /* Summaries computed on the device: for one plane of the WHOLE global grid, the sum and sum of squares of its finite
  * cells, their minimum and maximum, and the count of non-finite cells (NaN, +-inf) -- without downloading the plane.
  *   gs_fields_summarize    out[i] for fields[i], i < n (1..4 fields of one shape, e.g. U and V of a Species): one wait for
