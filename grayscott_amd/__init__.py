@@ -15,6 +15,7 @@ from .simulation import (  # noqa: F401
     Histogram,
     HipConcentration,
     HipContext,
+    Morphology,
     Parameters,
     Simulation,
     Snapshot,
@@ -24,4 +25,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "Parameters", "Simulation", "Snapshot", "Species", "Summary", "pinned_empty"]
+           "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "pinned_empty"]

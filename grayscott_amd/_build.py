@@ -50,6 +50,9 @@ UNITS = [
     ("gs_summary.hip", "gs_summary_k.o", []),
     # histograms of planes (counts in LDS, flushed to u64 counters): the same float mode, a sub-normal cell is binned as it is
     ("gs_histogram.hip", "gs_histogram_k.o", []),
+    # bit-quad counts of thresholded planes (one pass for up to four thresholds): the same float mode, a sub-normal cell is
+    # compared as it is
+    ("gs_morphology.hip", "gs_morphology_k.o", []),
     # reduced result images (block averages in f64): the same float mode, a sub-normal pixel is kept
     ("gs_reduce.hip", "gs_reduce_k.o", []),
     # two planes compared (row records of |a - b| in f64, the ensembles' fold): the same float mode, sub-normal cells kept

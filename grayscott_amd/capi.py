@@ -50,6 +50,7 @@ EXPORTS = (
     "gs_field_reduced_shape", "gs_field_download_reduced", "gs_field_download_reduced_async", "gs_field_colormap_reduced",
     "gs_fields_compare", "gs_members_compare", "gs_fields_copy", "gs_members_copy",
     "gs_members_set_active", "gs_members_get_active",
+    "gs_fields_morphology", "gs_members_morphology",
 )
 
 
@@ -138,6 +139,13 @@ class GsChange(ctypes.Structure):
     ]
 
 
+class GsMorphology(ctypes.Structure):
+    """``gs_morphology`` (include/gs_hip.h): the bit-quad counts of one thresholded plane -- Q0, Q1, Q2, Q3, Q4, QD -- 48
+    bytes."""
+
+    _fields_ = [("quads", ctypes.c_uint64 * 6)]
+
+
 _lib = None
 
 
@@ -223,6 +231,8 @@ def load() -> ctypes.CDLL:
         "gs_members_copy": (i32, [vp, vp, vp, u64, u64]),
         "gs_members_set_active": (i32, [vp, vp, u64, u64, vp]),
         "gs_members_get_active": (i32, [vp, vp, u64, u64, vp, vp, P(u64)]),
+        "gs_fields_morphology": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, P(GsMorphology)]),
+        "gs_members_morphology": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, P(GsMorphology)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -9,7 +9,8 @@
 //   gs_attached.cpp a context's per-cell data: parameter maps (per-cell feed and kill rates, gs_ctx_set_param_map) and
 //                  domain masks (wall cells that block diffusion, gs_ctx_set_mask) on one grid
 //   gs_observe.cpp results formed on the device from planes and ensemble members: summaries (gs_fields_summarize,
-//                  gs_members_summarize), histograms (gs_fields_histogram, gs_members_histogram), comparisons of two states
+//                  gs_members_summarize), histograms (gs_fields_histogram, gs_members_histogram), bit-quad counts
+//                  (gs_fields_morphology, gs_members_morphology), comparisons of two states
 //                  (gs_fields_compare, gs_members_compare) and the device copies behind snapshots (gs_fields_copy, gs_members_copy)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once
@@ -284,6 +285,8 @@ int32_t same_shape(const gs_field *a, const gs_field *b);
 int32_t sync_all(gs_ctx *ctx);
 int32_t sync_compute(gs_ctx *ctx); // every slab's compute stream alone: what a call enqueued there itself has ended
 int32_t refresh_ghosts(gs_ctx *ctx, gs_field *f);
+// `bytes` bytes from slab src_slab's device to slab dst_slab's, enqueued on `stream` (a peer copy between two devices)
+int32_t copy_row(gs_ctx *ctx, int src_slab, const float *src, int dst_slab, float *dst, size_t bytes, hipStream_t stream);
 int min_slab_rows(const gs_ctx *ctx, const gs_field *f);
 GsStepArgs make_args(const gs_ctx *ctx, const gs_field *in_u, const gs_field *in_v,
                      const gs_field *out_u, const gs_field *out_v, int i, int fuse);

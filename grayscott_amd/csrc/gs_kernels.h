@@ -269,3 +269,15 @@ hipError_t gs_launch_row_change(const float *const *a, const float *const *b, in
 // The field fold of gs_hip.h over the records gs_launch_row_change wrote for the two species of `count` ensemble members of
 // `rows` rows each (rec[s * count * rows + i * rows + r]): out[2 i + s], the rows added one after the other in order.
 hipError_t gs_launch_change_fold(const GsRowChange *rec, int64_t count, int64_t rows, GsChangeTotal *out, hipStream_t s);
+
+// Bit-quad counts (gs_morphology.hip; include/gs_hip.h: gs_fields_morphology).  np (1..4) planes of one shape -- rows [0, rows)
+// of `pitch` floats, `cols` columns -- repeated `repeat` times `stride` floats apart, as for gs_launch_histogram: plane
+// y = r * np + i is planes[i] + r * stride, thresholded at thresholds[i * nt + k], k < nt (1..4), with sense[i] (!= 0: a cell
+// is set when it is above the threshold, 0: when it is below).  The launch counts the quad rows whose LOWER row is one of the
+// plane's rows [0, rows) -- the upper row of the first of them is above[i]: `cols` floats (`pitch` readable), or unset when
+// above or above[i] is null (always when repeat > 1) -- and, with `bottom`, the quad row below the last row, whose lower half
+// is padding; the columns run from the padding left of column 0 to the padding right of column cols - 1.  It adds Q1, Q2, Q3,
+// Q4, QD to out[(y * nt + k) * 5 ...], which must hold zeros; Q0 is the complement.  max_groups: as for gs_launch_histogram.
+hipError_t gs_launch_quads(const float *const *planes, const float *const *above, int np, int64_t repeat, int64_t stride,
+                           int64_t pitch, int64_t rows, int32_t cols, int bottom, const float *thresholds, const int32_t *sense,
+                           int32_t nt, int64_t max_groups, unsigned long long *out, hipStream_t s);

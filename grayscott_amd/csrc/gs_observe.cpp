@@ -1,12 +1,15 @@
 // gs_observe.cpp -- results formed on the device from planes and ensemble members, without downloading them
 // (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize), histograms (gs_fields_histogram,
-// gs_members_histogram) and comparisons of two states (gs_fields_compare, gs_members_compare).  All observe a field list with one launch per slab on its compute stream into that slab's scratch
+// gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology) and comparisons of two states
+// (gs_fields_compare, gs_members_compare).  All observe a field list with one launch per slab on its compute stream into that slab's scratch
 // buffer, fetch what the launches left and combine it here on the host, after the results of every slab -- and, in a
 // multi-process context, of every rank (exchange) -- have met; an ensemble's members are observed in one launch on slab 0.
 //   summaries   row records from gs_row_summary_k (gs_summary.hip); the field fold -- rows added in ascending global row
 //               order -- is done on the host.  Ensembles fold on the device (gs_summary_fold_k): two records per member travel.
 //   histograms  zeroed u64 counters filled by gs_plane_hist_k (gs_histogram.hip) and added on the host.  Integers: the
 //               order of the additions does not show.
+//   morphology  zeroed u64 counters filled by gs_plane_quads_k (gs_morphology.hip) -- a stencil: the row above a slab's
+//               first row is staged into the slab's scratch buffer, never read from ghost rows -- and added on the host.
 //   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
 //               (row_records); ensembles fold on the device (gs_change_fold_k).
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
@@ -248,6 +251,28 @@ int64_t max_groups(const gs_ctx *ctx)
     return (int64_t)kHistGroupsPerCu * (ctx->cu_count > 0 ? ctx->cu_count : 256);
 }
 
+// ---- morphology ------------------------------------------------------------------------------------------------------
+static_assert(sizeof(gs_morphology) == 48, "gs_morphology layout");
+constexpr size_t kQuadCounted = 5; // the classes gs_plane_quads_k counts: Q1, Q2, Q3, Q4, QD
+
+// nt thresholds for each of n planes, or the refusal of gs_hip.h.  No handle is looked at.
+int32_t check_thresholds(const float *thresholds, int32_t n, int32_t nt)
+{
+    if (nt < 1 || nt > 4) return fail(GS_ERR_INVALID, "%d thresholds (1..4)", nt);
+    for (int32_t i = 0; i < n * nt; ++i)
+        if (std::isnan(thresholds[i])) return fail(GS_ERR_INVALID, "threshold %d of plane %d is NaN", i % nt, i / nt);
+    return GS_OK;
+}
+
+// The counted classes of one (plane, threshold) and the complement Q0 of a plane of rows x cols cells.
+gs_morphology from_counted(const uint64_t *c, uint64_t rows, uint64_t cols)
+{
+    gs_morphology m;
+    for (size_t k = 0; k < kQuadCounted; ++k) m.quads[1 + k] = c[k];
+    m.quads[0] = (rows + 1) * (cols + 1) - (c[0] + c[1] + c[2] + c[3] + c[4]);
+    return m;
+}
+
 } // namespace
 
 extern "C" {
@@ -442,6 +467,113 @@ int32_t gs_members_histogram(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64
                                lo, hi, scale, bins, max_groups(ctx), dev, sl.compute));
     GS_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
     GS_HIP(hipStreamSynchronize(sl.compute));
+    return GS_OK;
+}
+
+int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
+                             int32_t nt, gs_morphology *out)
+{
+    if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    // the thresholds before any handle is looked at; a count that is no 1..4 is check_planes' first refusal
+    GS_TRY(check_thresholds(thresholds, n >= 1 && n <= 4 ? n : 0, nt));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    const size_t words = (size_t)n * (size_t)nt * kQuadCounted, bytes = words * sizeof(uint64_t);
+    if (f0->rows == 0 || f0->cols == 0) { // the same shape on every rank: nobody exchanges anything
+        std::memset(out, 0, (size_t)n * (size_t)nt * sizeof(gs_morphology));
+        return GS_OK;
+    }
+    // The quad rows are split into consecutive runs, one per slab: the slab of global rows [r0, r1) counts those whose lower
+    // row is r0 .. r1 - 1, the last slab also the one below row R - 1.  A slab with r0 > 0 needs row r0 - 1: it is STAGED into
+    // the slab's scratch buffer behind the counters -- ghost rows are never read, whatever ghost_depth says.
+    const size_t nslab = ctx->slabs.size(), pitch = (size_t)f0->pitch, row_bytes = pitch * sizeof(float);
+    const size_t counters = (bytes + 255) / 256 * 256; // (the staged rows start on a 256-byte boundary)
+    std::vector<float> upper; // several processes: the last rows of the rank above, [plane][cols]
+    if (ctx->world > 1) {
+        // every rank's last rows (n x cols floats) to every rank; this one keeps those of the rank above
+        const size_t cols = (size_t)f0->cols, share = (size_t)n * cols * sizeof(float);
+        std::vector<float> mine((size_t)n * cols), all((size_t)ctx->world * (size_t)n * cols);
+        SlabRt &sl = ctx->slabs[nslab - 1];
+        GS_HIP(hipSetDevice(sl.device));
+        for (int32_t p = 0; p < n; ++p) {
+            const FieldSlab &fs = fields[p]->s[nslab - 1];
+            GS_HIP(hipMemcpyAsync(mine.data() + (size_t)p * cols, fs.row0 + (ptrdiff_t)(fs.rows - 1) * (ptrdiff_t)pitch,
+                                  cols * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
+        }
+        GS_HIP(hipStreamSynchronize(sl.compute));
+        GS_TRY(exchange(ctx, mine.data(), std::vector<size_t>((size_t)ctx->world, share), "morphology", all.data()));
+        if (ctx->rank > 0) upper.assign(all.begin() + (ptrdiff_t)((size_t)(ctx->rank - 1) * (size_t)n * cols),
+                                        all.begin() + (ptrdiff_t)((size_t)ctx->rank * (size_t)n * cols));
+    }
+    std::vector<uint64_t> part(nslab * words);
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        GS_TRY(ensure_scratch(ctx, (int)i, counters + (size_t)n * row_bytes, "morphology"));
+        GS_HIP(hipSetDevice(sl.device));
+        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+        float *staged = reinterpret_cast<float *>(static_cast<unsigned char *>(sl.scratch) + counters);
+        const bool first = f0->s[i].g_row0 == 0, last = f0->s[i].g_row0 + (uint64_t)f0->s[i].rows == f0->rows;
+        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr}, *row_above[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int32_t p = 0; p < n; ++p) {
+            planes[p] = fields[p]->s[i].row0;
+            if (first) continue;
+            row_above[p] = staged + (size_t)p * pitch;
+            if (i > 0) { // (every stream is idle: the row is final, and nobody else uses this slab's scratch buffer)
+                const FieldSlab &up = fields[p]->s[i - 1];
+                GS_TRY(copy_row(ctx, (int)i - 1, up.row0 + (ptrdiff_t)(up.rows - 1) * (ptrdiff_t)pitch, (int)i, staged + (size_t)p * pitch,
+                                (size_t)f0->cols * sizeof(float), sl.compute));
+            } else {
+                GS_HIP(hipMemcpyAsync(staged + (size_t)p * pitch, upper.data() + (size_t)p * (size_t)f0->cols,
+                                      (size_t)f0->cols * sizeof(float), hipMemcpyHostToDevice, sl.compute));
+            }
+        }
+        GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+        GS_HIP(gs_launch_quads(planes, row_above, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, last ? 1 : 0,
+                               thresholds, above, nt, max_groups(ctx), dev, sl.compute));
+        GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    std::vector<uint64_t> sum(words, (uint64_t)0);
+    for (size_t i = 0; i < nslab; ++i)
+        for (size_t w = 0; w < words; ++w) sum[w] += part[i * words + w];
+    if (ctx->world > 1) {
+        // Several processes: every rank's counters to every rank, added in the same way everywhere.
+        std::vector<uint64_t> all((size_t)ctx->world * words);
+        GS_TRY(exchange(ctx, sum.data(), std::vector<size_t>((size_t)ctx->world, bytes), "morphology", all.data()));
+        std::fill(sum.begin(), sum.end(), (uint64_t)0);
+        for (int q = 0; q < ctx->world; ++q)
+            for (size_t w = 0; w < words; ++w) sum[w] += all[(size_t)q * words + w];
+    }
+    for (size_t j = 0; j < (size_t)n * (size_t)nt; ++j) out[j] = from_counted(sum.data() + j * kQuadCounted, f0->rows, f0->cols);
+    return GS_OK;
+}
+
+int32_t gs_members_morphology(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
+                              const int32_t above[2], int32_t nt, gs_morphology *out)
+{
+    if (!ctx || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_thresholds(thresholds, 2, nt)); // before the ensemble is looked at
+    GS_TRY(check_members(ctx, e, first, count));
+    const uint64_t cells = e->rows * e->cols;
+    const size_t results = (size_t)(2 * count) * (size_t)nt, words = results * kQuadCounted, bytes = words * sizeof(uint64_t);
+    if (cells == 0) {
+        std::memset(out, 0, results * sizeof(gs_morphology));
+        return GS_OK;
+    }
+    GS_TRY(ensure_scratch(ctx, 0, bytes, "morphology"));
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+    // member first + i's U and V are planes 2 i and 2 i + 1 of the launch, `cells` floats from one member to the next; each
+    // is a plane of its own: nothing above its first row, padding below its last -- it never sees its neighbours' rows
+    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
+    std::vector<uint64_t> host(words);
+    GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+    GS_HIP(gs_launch_quads(planes, nullptr, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows, (int32_t)e->cols,
+                           1, thresholds, above, nt, max_groups(ctx), dev, sl.compute));
+    GS_HIP(hipMemcpyAsync(host.data(), dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
+    for (size_t j = 0; j < results; ++j) out[j] = from_counted(host.data() + j * kQuadCounted, e->rows, e->cols);
     return GS_OK;
 }
 

@@ -425,6 +425,88 @@ def histogram_fields(context: "HipContext", fields: Sequence["HipConcentration"]
     return [Histogram.from_counters(out[i], lo[i], hi[i], rows * cols) for i in range(n)]
 
 
+def quad_measures(quads) -> Tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """``(area, perimeter, euler4, euler8)`` as int64 arrays from bit-quad counts whose LAST axis is the six classes Q0, Q1,
+    Q2, Q3, Q4, QD (include/gs_hip.h) -- a ``Morphology.quads`` vector, or what ``Ensemble.morphologies`` returns.  All exact:
+    area = (Q1 + 2 Q2 + 2 QD + 3 Q3 + 4 Q4) / 4 set cells, perimeter = Q1 + Q2 + 2 QD + Q3 cell sides between a set and an
+    unset cell (the padding ring included), euler8 = (Q1 - Q3 - 2 QD) / 4 and euler4 = (Q1 - Q3 + 2 QD) / 4: components minus
+    holes under 8- and 4-connectivity."""
+    q = np.asarray(quads).astype(np.int64)
+    q1, q2, q3, q4, qd = q[..., 1], q[..., 2], q[..., 3], q[..., 4], q[..., 5]
+    area = (q1 + 2 * q2 + 2 * qd + 3 * q3 + 4 * q4) // 4
+    perimeter = q1 + q2 + 2 * qd + q3
+    return area, perimeter, (q1 - q3 + 2 * qd) // 4, (q1 - q3 - 2 * qd) // 4
+
+
+@dataclass(frozen=True, eq=False)
+class Morphology:
+    """The bit-quad counts of one thresholded plane, counted on the device (``gs_fields_morphology``; the rule is
+    include/gs_hip.h's): a cell is set when it is above ``threshold`` (``above``) or below it (one f32 comparison; NaN and
+    equal cells are not set), the image is padded with one ring of unset cells, and ``quads`` holds how many of its
+    ``(rows + 1)(cols + 1)`` 2 x 2 blocks have no, one, two side-sharing, three, four, or two diagonal set cells (Q0, Q1, Q2,
+    Q3, Q4, QD).  The derived quantities are exact integers; ``cells`` is the plane's number of cells."""
+
+    quads: np.ndarray
+    threshold: float
+    above: bool
+    cells: int
+
+    @classmethod
+    def from_quads(cls, quads, threshold: float, above: bool, cells: int) -> "Morphology":
+        return cls(np.array(quads, np.uint64).reshape(6), float(threshold), bool(above), int(cells))
+
+    @property
+    def area(self) -> int:
+        """Set cells."""
+        return int(quad_measures(self.quads)[0])
+
+    @property
+    def area_fraction(self) -> float:
+        return self.area / self.cells if self.cells else float("nan")
+
+    @property
+    def perimeter(self) -> int:
+        """Cell sides between a set and an unset cell (4-connected boundary length), the padding ring included."""
+        return int(quad_measures(self.quads)[1])
+
+    @property
+    def euler4(self) -> int:
+        """4-connected components minus their holes."""
+        return int(quad_measures(self.quads)[2])
+
+    @property
+    def euler8(self) -> int:
+        """8-connected components minus their holes: large and positive for spots, about 0 for stripes and labyrinths,
+        negative for hole patterns."""
+        return int(quad_measures(self.quads)[3])
+
+
+def _thresholds(values) -> List[float]:
+    return [float(values)] if np.isscalar(values) else [float(x) for x in values]
+
+
+def morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"], thresholds: Sequence[Sequence[float]],
+                      above: Sequence[bool]) -> List[List[Morphology]]:
+    """``gs_fields_morphology``: bit-quad counts of 1..4 planes of one shape over the whole global grid in one call
+    (collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number for
+    every plane; all counted in one pass) with the sense ``above[i]``.  Returns one list of ``Morphology`` per plane."""
+    n = len(fields)
+    if len(thresholds) != n or len(above) != n:
+        raise ValueError("one list of thresholds and one sense per field")
+    lists = [_thresholds(t) for t in thresholds]
+    nt = len(lists[0]) if lists else 0
+    if any(len(t) != nt for t in lists):
+        raise ValueError("the same number of thresholds for every field")
+    flat = [x for t in lists for x in t]
+    thr = (ctypes.c_float * max(len(flat), 1))(*flat)
+    sense = (ctypes.c_int32 * max(n, 1))(*[1 if a else 0 for a in above])
+    out = np.zeros((max(n, 1), max(nt, 1), 6), np.uint64)
+    capi.check(context._lib.gs_fields_morphology(context.handle, _handle_array(fields), n, thr, sense, nt,
+                                                 out.ctypes.data_as(ctypes.POINTER(capi.GsMorphology))))
+    rows, cols = fields[0].shape()
+    return [[Morphology.from_quads(out[i, k], thr[i * nt + k], above[i], rows * cols) for k in range(nt)] for i in range(n)]
+
+
 def pinned_empty(shape: Sequence[int]) -> np.ndarray:
     """float32 array in page-locked host memory (``gs_host_alloc``) for overlapped downloads.
     The allocation is released when the last view of it is garbage-collected."""
@@ -628,6 +710,12 @@ class HipConcentration:
         counted on the device (blocking; collective in a multi-process context)."""
         return histogram_fields(context, [self], bins, [range])[0]
 
+    def morphology(self, context: HipContext, thresholds, above: bool = True) -> List[Morphology]:
+        """The bit-quad counts of this plane thresholded at each of ``thresholds`` (1..4, one pass) over the whole global
+        grid, counted on the device (``gs_fields_morphology``; blocking, collective in a multi-process context): a cell
+        is set when it is above (``above``) or below the threshold."""
+        return morphology_fields(context, [self], [thresholds], [above])[0]
+
     def change_from(self, context: HipContext, other: "HipConcentration") -> Change:
         """How far this plane is from ``other`` (this minus other, cell by cell in f64) over the whole global grid,
         computed on the device (``gs_fields_compare``; blocking, collective in a multi-process context)."""
@@ -774,6 +862,18 @@ class Species:
         u, v = histogram_fields(self._context, [in_u, in_v], bins, [u_range, v_range])
         return u, v
 
+    def morphology(self, v_thresholds=(0.25,), u_thresholds=None, v_above: bool = True,
+                   u_above: bool = False) -> Tuple[List[Morphology], List[Morphology]]:
+        """(U, V) bit-quad counts of the current state in one call (``gs_fields_morphology``; blocking, collective in a
+        multi-process context): one ``Morphology`` per threshold (1..4 per species, the same number for both).  V carries
+        the pattern where it is high and U where it is low, hence the default senses; without ``u_thresholds`` only V is
+        looked at and the U list is empty."""
+        in_u, in_v, _, _ = self.in_out()
+        if u_thresholds is None:
+            return [], morphology_fields(self._context, [in_v], [v_thresholds], [v_above])[0]
+        u, v = morphology_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], [u_above, v_above])
+        return u, v
+
     def snapshot(self) -> Snapshot:
         """The current state copied into planes of its own on the device (``gs_fields_copy``; blocking)."""
         return Snapshot(self)
@@ -893,6 +993,25 @@ class Ensemble:
         out = np.zeros((max(count, 0), 2, max(bins, 0) + 3), np.uint64)
         capi.check(self._ctx._lib.gs_members_histogram(self._ctx.handle, self.handle, first, count, lo, hi, bins,
                                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return out
+
+    def morphologies(self, first: int = 0, count: Optional[int] = None, v_thresholds=(0.25,), u_thresholds=(0.5,),
+                     v_above: bool = True, u_above: bool = False) -> np.ndarray:
+        """Bit-quad counts of members ``[first, first + count)`` counted on the device (``gs_members_morphology``, blocking):
+        a ``uint64`` array ``[count, 2, nt, 6]`` -- axis 1: U at ``u_thresholds`` with the sense ``u_above``, V at
+        ``v_thresholds`` with ``v_above`` (1..4 thresholds, the same number for both); last axis: Q0, Q1, Q2, Q3, Q4, QD -- what
+        ``Species.morphology`` gives for a lone Species in the member's state.  ``quad_measures`` turns it into areas,
+        perimeters and Euler numbers, ``Morphology.from_quads`` one entry into the object."""
+        first, count = self._range(first, count)
+        tu, tv = _thresholds(u_thresholds), _thresholds(v_thresholds)
+        if len(tu) != len(tv):
+            raise ValueError("the same number of thresholds for U and V")
+        nt = len(tu)
+        thr = (ctypes.c_float * max(2 * nt, 1))(*(tu + tv))
+        sense = (ctypes.c_int32 * 2)(1 if u_above else 0, 1 if v_above else 0)
+        out = np.zeros((max(count, 0), 2, max(nt, 1), 6), np.uint64)
+        capi.check(self._ctx._lib.gs_members_morphology(self._ctx.handle, self.handle, first, count, thr, sense, nt,
+                                                         out.ctypes.data_as(ctypes.POINTER(capi.GsMorphology))))
         return out
 
     def snapshot(self) -> "Ensemble":

@@ -23,6 +23,14 @@ above, nan), ``lo[2]`` and ``hi[2]``.  ``--hist-bins B`` (default 256), ``--hist
 ``--hist-range-v A:B`` (default 0:0.5) set the bins.  It works together with ``--summary-every`` and ``--no-fields`` and
 leaves the HDF5 file as it is without it.
 
+``--morphology-every N`` records, at the same steps again, the bit-quad counts of every member's thresholded planes counted
+on the device (``Ensemble.morphologies``; the rule is include/gs_hip.h's) -- "spots, stripes or holes?" -- into
+``<output stem>.morphology.npz``.  ``--morph-threshold-v A[,B,...]`` (1 to 4 values, required with the flag) thresholds V
+from above, ``--morph-threshold-u A[,B,...]`` (as many values; default 0.5 for each) thresholds U from below.  The file holds
+``steps[samples]``, ``thresholds_u[nt]``, ``thresholds_v[nt]``, ``quads[samples, members, 2, nt, 6]`` (axis 2: U, V; last
+axis: Q0, Q1, Q2, Q3, Q4, QD) and, derived from them, ``area_fraction``, ``perimeter``, ``euler4``, ``euler8``, each
+``[samples, members, 2, nt]``.  It changes no state either: the HDF5 file is byte for byte the same without it.
+
 ``--steady-every N`` asks of every member "has it stopped changing?".  A snapshot of the ensemble is kept on the device
 (``Ensemble.snapshot``), taken at step 0; after every N steps and after the last one every member is compared with it on the
 device (``Ensemble.changes_since``: with d = now - snapshot per cell in f64, the sum of |d|, the sum of d * d and the largest
@@ -61,7 +69,7 @@ import numpy as np
 
 from . import hdf5_min
 from .simulate import add_backend_args, backend_args
-from .simulation import Parameters, Simulation
+from .simulation import Parameters, Simulation, quad_measures
 
 
 def value_range(text: str) -> List[float]:
@@ -86,6 +94,17 @@ def value_pair(text: str) -> Tuple[float, float]:
     return a, b
 
 
+def threshold_list(text: str) -> List[float]:
+    """``A[,B,...]`` -> 1 to 4 thresholds, none of them NaN."""
+    try:
+        out = [float(x) for x in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected A[,B,...], got {text!r}")
+    if not 1 <= len(out) <= 4 or any(x != x for x in out):
+        raise argparse.ArgumentTypeError(f"1 to 4 thresholds that are numbers, got {text!r}")
+    return out
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(prog="sweep", description="Gray-Scott parameter sweep, one ensemble member per (feed, kill)")
     ap.add_argument("--feed", type=value_range, required=True, metavar="A:B:N", help="feed rates")
@@ -103,6 +122,12 @@ def parse(argv=None):
     ap.add_argument("--hist-bins", type=int, default=256, metavar="B", help="bins of the histograms (1..4096)")
     ap.add_argument("--hist-range-u", type=value_pair, default=(0.0, 1.0), metavar="A:B", help="range of U's histogram")
     ap.add_argument("--hist-range-v", type=value_pair, default=(0.0, 0.5), metavar="A:B", help="range of V's histogram")
+    ap.add_argument("--morphology-every", type=int, default=0, metavar="N",
+                    help="record every member's bit-quad counts every N steps and at the end (<output stem>.morphology.npz)")
+    ap.add_argument("--morph-threshold-v", type=threshold_list, default=None, metavar="A[,B,...]",
+                    help="1 to 4 thresholds: V is set where it is above them")
+    ap.add_argument("--morph-threshold-u", type=threshold_list, default=None, metavar="A[,B,...]",
+                    help="as many thresholds: U is set where it is below them (default 0.5 each)")
     ap.add_argument("--steady-every", type=int, default=0, metavar="N",
                     help="compare every member with its state N steps before, every N steps and at the end "
                          "(<output stem>.steady.npz)")
@@ -127,6 +152,14 @@ def parse(argv=None):
         ap.error("--histogram-every must be at least 1 (0 = off)")
     if not 1 <= args.hist_bins <= 4096:
         ap.error("--hist-bins must be in 1..4096")
+    if args.morphology_every < 0:
+        ap.error("--morphology-every must be at least 1 (0 = off)")
+    if args.morphology_every and args.morph_threshold_v is None:
+        ap.error("--morphology-every needs --morph-threshold-v")
+    if args.morph_threshold_u is None and args.morph_threshold_v is not None:
+        args.morph_threshold_u = [0.5] * len(args.morph_threshold_v)
+    if args.morph_threshold_v is not None and len(args.morph_threshold_u) != len(args.morph_threshold_v):
+        ap.error("--morph-threshold-u needs as many values as --morph-threshold-v")
     return args
 
 
@@ -157,6 +190,10 @@ def hist_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".hist.npz"
 
 
+def morphology_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".morphology.npz"
+
+
 def steady_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".steady.npz"
 
@@ -180,6 +217,15 @@ def write_histograms(path: str, steps: List[int], samples: List[np.ndarray], u_r
     np.savez(path, steps=np.asarray(steps, np.int64), counts=np.ascontiguousarray(h[..., :-3]),
              outside=np.ascontiguousarray(h[..., -3:]), lo=np.asarray([u_range[0], v_range[0]], np.float32),
              hi=np.asarray([u_range[1], v_range[1]], np.float32))
+
+
+def write_morphologies(path: str, steps: List[int], samples: List[np.ndarray], thresholds_u, thresholds_v, cells: int) -> None:
+    q = np.stack(samples, axis=0)  # [samples, members, 2, nt, 6]
+    area, perimeter, euler4, euler8 = quad_measures(q)
+    np.savez(path, steps=np.asarray(steps, np.int64), thresholds_u=np.asarray(thresholds_u, np.float32),
+             thresholds_v=np.asarray(thresholds_v, np.float32), quads=np.ascontiguousarray(q),
+             area_fraction=area / cells if cells else np.full(area.shape, np.nan), perimeter=perimeter, euler4=euler4,
+             euler8=euler8)
 
 
 def settled_steps(steps: List[int], max_abs: np.ndarray, tol: float) -> np.ndarray:
@@ -217,17 +263,20 @@ def run(args) -> dict:
     summary_at = sample_steps(args.steps, args.summary_every) if args.summary_every else []
     hist_at = sample_steps(args.steps, args.histogram_every) if args.histogram_every else []
     steady_at = sample_steps(args.steps, args.steady_every) if args.steady_every else []
+    morph_at = sample_steps(args.steps, args.morphology_every) if args.morphology_every else []
     done, settled, taken = 0, None, None
-    if summary_at or hist_at or steady_at:
-        summaries, hists, changes = [], [], []
+    if summary_at or hist_at or steady_at or morph_at:
+        summaries, hists, changes, morphs = [], [], [], []
         snap = ens.snapshot() if steady_at else None
-        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at)):
+        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at)):
             ens.prepare_steps(at - done)
             done = at
             if at in summary_at:
                 summaries.append(ens.summaries())  # (waits for the steps)
             if at in hist_at:
                 hists.append(ens.histograms(bins=args.hist_bins, u_range=args.hist_range_u, v_range=args.hist_range_v))
+            if at in morph_at:
+                morphs.append(ens.morphologies(v_thresholds=args.morph_threshold_v, u_thresholds=args.morph_threshold_u))
             if at in steady_at:
                 changes.append(ens.changes_since(snap))
                 snap.copy_from(ens)
@@ -244,6 +293,9 @@ def run(args) -> dict:
             write_summaries(summary_path(args.output), summary_at[:len(summaries)], summaries)
         if hist_at:
             write_histograms(hist_path(args.output), hist_at[:len(hists)], hists, args.hist_range_u, args.hist_range_v)
+        if morph_at:
+            write_morphologies(morphology_path(args.output), morph_at[:len(morphs)], morphs, args.morph_threshold_u,
+                               args.morph_threshold_v, shape[0] * shape[1])
         if steady_at:
             if args.steady_retire:
                 sim.context.sync()

@@ -102,6 +102,33 @@ struct Histogram {
     }
 };
 
+// The bit-quad counts of one thresholded plane, counted on the device (gs_fields_morphology; the rule is gs_hip.h's): a cell
+// is set when it is above `threshold` (`above`) or below it, the image is padded with one ring of unset cells, and `quads`
+// counts its (rows + 1)(cols + 1) 2 x 2 blocks by class: Q0, Q1, Q2, Q3, Q4, QD.  What follows is exact.
+struct Morphology {
+    std::array<uint64_t, 6> quads{};
+    float threshold = 0.0f;
+    bool above = true;
+    uint64_t cells = 0;
+    static Morphology from_c(const gs_morphology &m, float threshold, bool above, uint64_t cells)
+    {
+        Morphology o;
+        for (std::size_t i = 0; i < 6; ++i) o.quads[i] = m.quads[i];
+        o.threshold = threshold;
+        o.above = above;
+        o.cells = cells;
+        return o;
+    }
+    // set cells
+    uint64_t area() const { return (quads[1] + 2 * quads[2] + 2 * quads[5] + 3 * quads[3] + 4 * quads[4]) / 4; }
+    double area_fraction() const { return cells ? (double)area() / (double)cells : std::nan(""); }
+    // cell sides between a set and an unset cell (4-connected boundary length), the padding ring included
+    uint64_t perimeter() const { return quads[1] + quads[2] + 2 * quads[5] + quads[3]; }
+    // components minus holes under 4- and 8-connectivity
+    int64_t euler4() const { return ((int64_t)quads[1] - (int64_t)quads[3] + 2 * (int64_t)quads[5]) / 4; }
+    int64_t euler8() const { return ((int64_t)quads[1] - (int64_t)quads[3] - 2 * (int64_t)quads[5]) / 4; }
+};
+
 struct Parameters {
     std::array<std::array<Precision, 3>, 3> weights{{{0.25f, 0.5f, 0.25f}, {0.5f, 0.0f, 0.5f}, {0.25f, 0.5f, 0.25f}}};
     Precision diffusion_rate_u = 0.1f, diffusion_rate_v = 0.05f;
@@ -427,6 +454,30 @@ class Species {
         return {Histogram::from_c(out.data(), bins, lo[0], hi[0], s[0] * s[1]),
                 Histogram::from_c(out.data() + bins + 3, bins, lo[1], hi[1], s[0] * s[1])};
     }
+    // (U, V) bit-quad counts of the current state over the whole global grid, in one call (gs_fields_morphology; blocking,
+    // collective in a multi-process context): one Morphology per threshold (1..4 per species, the same number for both), U
+    // set where it is below its thresholds and V where it is above, unless the senses say otherwise
+    std::pair<std::vector<Morphology>, std::vector<Morphology>> morphology(const std::vector<float> &v_thresholds,
+                                                                           const std::vector<float> &u_thresholds,
+                                                                           bool v_above = true, bool u_above = false)
+    {
+        if (u_thresholds.size() != v_thresholds.size())
+            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t nt = v_thresholds.size();
+        std::vector<float> t(u_thresholds);
+        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
+        std::vector<gs_morphology> out(2 * nt + 1);
+        check(gs_fields_morphology(context_->get(), planes, 2, t.data(), sense, (int32_t)nt, out.data()));
+        const Shape s = shape();
+        std::pair<std::vector<Morphology>, std::vector<Morphology>> uv;
+        for (std::size_t k = 0; k < nt; ++k) {
+            uv.first.push_back(Morphology::from_c(out[k], t[k], u_above, s[0] * s[1]));
+            uv.second.push_back(Morphology::from_c(out[nt + k], t[nt + k], v_above, s[0] * s[1]));
+        }
+        return uv;
+    }
     // the current state copied into planes of its own on the device (gs_fields_copy; blocking)
     Snapshot snapshot()
     {
@@ -571,6 +622,27 @@ class Ensemble {
         std::vector<Histogram> out;
         for (std::size_t i = 0; i < 2 * count; ++i)
             out.push_back(Histogram::from_c(c.data() + i * each, bins, lo[i & 1], hi[i & 1], shape_[0] * shape_[1]));
+        return out;
+    }
+    // bit-quad counts of members [first, first + count) from the newest state (gs_members_morphology, blocking): element
+    // (2 i + s) * nt + k = species s (0 = U, 1 = V) of member first + i at that species' threshold k, what
+    // Species::morphology gives for a lone Species in that state
+    std::vector<Morphology> morphologies(std::size_t first, std::size_t count, const std::vector<float> &v_thresholds,
+                                         const std::vector<float> &u_thresholds, bool v_above = true, bool u_above = false) const
+    {
+        if (u_thresholds.size() != v_thresholds.size())
+            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
+        const std::size_t nt = v_thresholds.size();
+        std::vector<float> t(u_thresholds);
+        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
+        std::vector<gs_morphology> c(2 * count * nt + 1);
+        check(gs_members_morphology(ctx_->get(), e_, first, count, t.data(), sense, (int32_t)nt, c.data()));
+        std::vector<Morphology> out;
+        for (std::size_t i = 0; i < 2 * count * nt; ++i) {
+            const std::size_t species = (i / nt) & 1, k = i % nt;
+            out.push_back(Morphology::from_c(c[i], t[species * nt + k], sense[species] != 0, shape_[0] * shape_[1]));
+        }
         return out;
     }
     // an ensemble of the same shape and member count on the same context whose members hold this one's current states

@@ -604,6 +604,46 @@ int32_t gs_fields_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t n, con
 int32_t gs_members_histogram(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float lo[2], const float hi[2],
                              int32_t bins, uint64_t *out);
 
+/* Morphology computed on the device: the bit-quad counts (Gray) of one plane of the WHOLE global grid after thresholding --
+ * from which the area, the boundary length and the Euler number of the pattern follow exactly (the Minkowski functionals of
+ * integral geometry: "spots, stripes or holes?") -- without downloading the plane.  For a plane x of R x C cells, a threshold
+ * t and a sense `above`:
+ *   - a cell is SET iff x > t (above != 0) or x < t (above == 0): one f32 comparison.  A NaN cell is never set, a cell equal
+ *     to t is not set, infinities compare as they do, a sub-normal cell is the value it is (never flushed);
+ *   - the binary image is padded with one ring of UNSET cells, under every boundary rule: a spot that crosses a periodic
+ *     edge counts as two pieces (quads that wrap are not formed);
+ *   - every 2 x 2 block of the padded image is a quad; its top-left corner runs over rows -1 .. R - 1 and columns
+ *     -1 .. C - 1: (R + 1)(C + 1) quads.  A quad falls into one of six classes by its set cells, in this order in `quads`:
+ *       Q0 none, Q1 one, Q2 two that share a side, Q3 three, Q4 four, QD two on a diagonal.
+ *   The six counts sum to (R + 1)(C + 1).  An empty plane (R = 0 or C = 0): GS_OK, six zeros.
+ * What the hosts derive, all exact integers:
+ *   set cells                       A      = (Q1 + 2 Q2 + 2 QD + 3 Q3 + 4 Q4) / 4
+ *   4-connected boundary length     P      = Q1 + Q2 + 2 QD + Q3   (cell sides between a set and an unset cell, the padding
+ *                                                                   ring included)
+ *   8-connected components - holes  euler8 = (Q1 - Q3 - 2 QD) / 4
+ *   4-connected components - holes  euler4 = (Q1 - Q3 + 2 QD) / 4
+ * Counts are integers and additive over any partition of the quads: the result is the same bits for any slab count, process
+ * count, step kernel or launch shape, and a member's is that of a lone Species in the same state.
+ *   gs_fields_morphology   out[i * nt + k] for fields[i] thresholded at thresholds[i * nt + k] with the sense above[i], i < n
+ *                          (1..4 fields of one shape), k < nt (1..4 thresholds per field, all counted in one pass over the
+ *                          plane): one wait for enqueued work (as gs_fields_summarize: a persistent window launch that gave up
+ *                          is run again first), one launch per slab.  The row above a slab's first row is staged from the
+ *                          slab (or process) above into a buffer of its own: ghost rows are never read.  In a multi-process
+ *                          context the call is collective, like gs_run, and every rank receives the counts of the global grid.
+ *   gs_members_morphology  out[(2 i + s) * nt + k] for species s (0 = U with thresholds[k] and above[0]; 1 = V with
+ *                          thresholds[nt + k] and above[1]) of member first + i, i < count, from the newest slot: one launch,
+ *                          one copy.  A member never sees its neighbours' rows.
+ * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID: a null
+ * argument, nt outside 1..4 or a NaN threshold -- decided before any handle is looked at --, a null or foreign handle, mixed
+ * shapes, n outside 1..4, members outside the ensemble. */
+typedef struct gs_morphology {
+    uint64_t quads[6]; /* Q0, Q1, Q2, Q3, Q4, QD */
+} gs_morphology;       /* 48 bytes */
+int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
+                             int32_t nt, gs_morphology *out);
+int32_t gs_members_morphology(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
+                              const int32_t above[2], int32_t nt, gs_morphology *out);
+
 /* Two states compared on the device: how far one plane of the WHOLE global grid is from another of the same shape -- "has
  * this run stopped changing?" -- without downloading either, and the device copies that give a state to compare with
  * (snapshots) or to go back to (restores).
