@@ -9,6 +9,7 @@ from . import capi  # noqa: F401
 from .capi import GsError  # noqa: F401
 from .simulation import (  # noqa: F401
     Change,
+    Correlation,
     Ensemble,
     Evolving,
     HipArgs,
@@ -21,8 +22,9 @@ from .simulation import (  # noqa: F401
     Snapshot,
     Species,
     Summary,
+    correlation_fields,
     pinned_empty,
 )
 
-__all__ = ["capi", "GsError", "Change", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "pinned_empty"]
+__all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
+           "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]

@@ -51,6 +51,7 @@ EXPORTS = (
     "gs_fields_compare", "gs_members_compare", "gs_fields_copy", "gs_members_copy",
     "gs_members_set_active", "gs_members_get_active",
     "gs_fields_morphology", "gs_members_morphology",
+    "gs_fields_correlation", "gs_members_correlation",
 )
 
 
@@ -233,6 +234,8 @@ def load() -> ctypes.CDLL:
         "gs_members_get_active": (i32, [vp, vp, u64, u64, vp, vp, P(u64)]),
         "gs_fields_morphology": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, P(GsMorphology)]),
         "gs_members_morphology": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, P(GsMorphology)]),
+        "gs_fields_correlation": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(u64)]),
+        "gs_members_correlation": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

@@ -281,3 +281,15 @@ hipError_t gs_launch_change_fold(const GsRowChange *rec, int64_t count, int64_t 
 hipError_t gs_launch_quads(const float *const *planes, const float *const *above, int np, int64_t repeat, int64_t stride,
                            int64_t pitch, int64_t rows, int32_t cols, int bottom, const float *thresholds, const int32_t *sense,
                            int32_t nt, int64_t max_groups, unsigned long long *out, hipStream_t s);
+
+// Two-point pair counts (gs_correlation.hip; include/gs_hip.h: gs_fields_correlation).  Planes, thresholds and senses as for
+// gs_launch_quads.  The launch counts, for every lag d = 0 .. max_lag (1..64) and the unit steps e_0 = (0, 1), e_1 = (1, 0),
+// e_2 = (1, 1), e_3 = (1, -1), the pairs {p, p + d e_k} of set cells whose LOWER cell lies in the plane's rows [0, rows) -- the
+// upper cell may lie in one of the `nabove` rows above row 0, which above[i] holds `pitch` floats apart, the farthest first;
+// with above or above[i] null or nabove == 0 (always when repeat > 1) nothing above row 0 is set -- and adds them to
+// out[((y * nt + j) * 4 + k) * (max_lag + 1) + d], which must hold zeros.  Pairs never wrap.  max_groups: as for
+// gs_launch_histogram.
+hipError_t gs_launch_pairs(const float *const *planes, const float *const *above, int32_t nabove, int np, int64_t repeat,
+                           int64_t stride, int64_t pitch, int64_t rows, int32_t cols, const float *thresholds,
+                           const int32_t *sense, int32_t nt, int32_t max_lag, int64_t max_groups, unsigned long long *out,
+                           hipStream_t s);

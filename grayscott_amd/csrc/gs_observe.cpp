@@ -1,6 +1,7 @@
 // gs_observe.cpp -- results formed on the device from planes and ensemble members, without downloading them
 // (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize), histograms (gs_fields_histogram,
-// gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology) and comparisons of two states
+// gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology), two-point pair counts (gs_fields_correlation,
+// gs_members_correlation) and comparisons of two states
 // (gs_fields_compare, gs_members_compare).  All observe a field list with one launch per slab on its compute stream into that slab's scratch
 // buffer, fetch what the launches left and combine it here on the host, after the results of every slab -- and, in a
 // multi-process context, of every rank (exchange) -- have met; an ensemble's members are observed in one launch on slab 0.
@@ -10,6 +11,8 @@
 //               order of the additions does not show.
 //   morphology  zeroed u64 counters filled by gs_plane_quads_k (gs_morphology.hip) -- a stencil: the row above a slab's
 //               first row is staged into the slab's scratch buffer, never read from ghost rows -- and added on the host.
+//   correlations zeroed u64 counters filled by gs_plane_pairs_k (gs_correlation.hip) -- a stencil L rows tall: the L rows above
+//               a slab's first row are staged the way morphology's one row is (stage_rows_above) -- and added on the host.
 //   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
 //               (row_records); ensembles fold on the device (gs_change_fold_k).
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
@@ -264,6 +267,13 @@ int32_t check_thresholds(const float *thresholds, int32_t n, int32_t nt)
     return GS_OK;
 }
 
+// The largest lag of a correlation, or the refusal of gs_hip.h.  No handle is looked at.
+int32_t check_max_lag(int32_t max_lag)
+{
+    if (max_lag < 1 || max_lag > 64) return fail(GS_ERR_INVALID, "a largest lag of %d (1..64)", max_lag);
+    return GS_OK;
+}
+
 // The counted classes of one (plane, threshold) and the complement Q0 of a plane of rows x cols cells.
 gs_morphology from_counted(const uint64_t *c, uint64_t rows, uint64_t cols)
 {
@@ -271,6 +281,74 @@ gs_morphology from_counted(const uint64_t *c, uint64_t rows, uint64_t cols)
     for (size_t k = 0; k < kQuadCounted; ++k) m.quads[1 + k] = c[k];
     m.quads[0] = (rows + 1) * (cols + 1) - (c[0] + c[1] + c[2] + c[3] + c[4]);
     return m;
+}
+
+// ---- stencils over slabs: morphology, correlation ------------------------------------------------------------------
+// The `depth` global rows above the first row of every slab of this process, of each of n planes, STAGED into the slab's
+// scratch buffer behind `counters` bytes (a multiple of 256) as [plane][depth rows][pitch] -- from the slab above inside the
+// process (copy_row), from the rank above through `exchange` (every rank's last `depth` rows travel; each rank uploads those
+// of the rank above) -- on the slab's compute stream.  Ghost rows are never read, whatever ghost_depth says.  The slab
+// that begins at global row 0 has nothing staged.  Every slab above another holds at least `depth` rows (the caller's
+// check).  The scratch buffers hold counters + n * depth * pitch floats on return.
+int32_t stage_rows_above(gs_ctx *ctx, gs_field *const *fields, int32_t n, size_t depth, size_t counters, const char *what)
+{
+    const gs_field *f0 = fields[0];
+    const size_t nslab = ctx->slabs.size(), pitch = (size_t)f0->pitch, cols = (size_t)f0->cols;
+    const size_t block = depth * pitch; // floats of one plane's staged rows
+    std::vector<float> upper;           // several processes: the last rows of the rank above, [plane][depth][cols]
+    if (ctx->world > 1) {
+        const size_t each = (size_t)n * depth * cols, share = each * sizeof(float);
+        std::vector<float> mine(each), all((size_t)ctx->world * each);
+        SlabRt &sl = ctx->slabs[nslab - 1];
+        GS_HIP(hipSetDevice(sl.device));
+        for (int32_t p = 0; p < n; ++p) {
+            const FieldSlab &fs = fields[p]->s[nslab - 1];
+            GS_HIP(hipMemcpy2DAsync(mine.data() + (size_t)p * depth * cols, cols * sizeof(float),
+                                    fs.row0 + ((ptrdiff_t)fs.rows - (ptrdiff_t)depth) * (ptrdiff_t)pitch, pitch * sizeof(float),
+                                    cols * sizeof(float), depth, hipMemcpyDeviceToHost, sl.compute));
+        }
+        GS_HIP(hipStreamSynchronize(sl.compute));
+        GS_TRY(exchange(ctx, mine.data(), std::vector<size_t>((size_t)ctx->world, share), what, all.data()));
+        if (ctx->rank > 0) upper.assign(all.begin() + (ptrdiff_t)((size_t)(ctx->rank - 1) * each),
+                                        all.begin() + (ptrdiff_t)((size_t)ctx->rank * each));
+    }
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        GS_TRY(ensure_scratch(ctx, (int)i, counters + (size_t)n * block * sizeof(float), what));
+        if (f0->s[i].g_row0 == 0) continue;
+        GS_HIP(hipSetDevice(sl.device));
+        float *staged = reinterpret_cast<float *>(static_cast<unsigned char *>(sl.scratch) + counters);
+        for (int32_t p = 0; p < n; ++p) {
+            if (i > 0) { // (every stream is idle: the rows are final, and nobody else uses this slab's scratch buffer)
+                // the rows are `pitch` apart on both sides: one copy from the first cell to the last
+                const FieldSlab &up = fields[p]->s[i - 1];
+                GS_TRY(copy_row(ctx, (int)i - 1, up.row0 + ((ptrdiff_t)up.rows - (ptrdiff_t)depth) * (ptrdiff_t)pitch, (int)i,
+                                staged + (size_t)p * block, ((depth - 1) * pitch + cols) * sizeof(float), sl.compute));
+            } else {
+                GS_HIP(hipMemcpy2DAsync(staged + (size_t)p * block, pitch * sizeof(float), upper.data() + (size_t)p * depth * cols,
+                                        cols * sizeof(float), cols * sizeof(float), depth, hipMemcpyHostToDevice, sl.compute));
+            }
+        }
+        // `upper` is pageable and dies with this call: its rows are on the device before it does
+        if (i == 0) GS_HIP(hipStreamSynchronize(sl.compute));
+    }
+    return GS_OK;
+}
+
+// `words` u64 counters per slab, [slab][words], added over the slabs and, in a multi-process context, over the ranks
+// (every rank's sums to every rank, added in the same way everywhere).  Integers: the order does not show.
+int32_t add_counters(gs_ctx *ctx, const std::vector<uint64_t> &part, size_t words, const char *what, std::vector<uint64_t> &sum)
+{
+    sum.assign(words, (uint64_t)0);
+    for (size_t i = 0; i < ctx->slabs.size(); ++i)
+        for (size_t w = 0; w < words; ++w) sum[w] += part[i * words + w];
+    if (ctx->world == 1) return GS_OK;
+    std::vector<uint64_t> all((size_t)ctx->world * words);
+    GS_TRY(exchange(ctx, sum.data(), std::vector<size_t>((size_t)ctx->world, words * sizeof(uint64_t)), what, all.data()));
+    std::fill(sum.begin(), sum.end(), (uint64_t)0);
+    for (int q = 0; q < ctx->world; ++q)
+        for (size_t w = 0; w < words; ++w) sum[w] += all[(size_t)q * words + w];
+    return GS_OK;
 }
 
 } // namespace
@@ -486,29 +564,12 @@ int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
     // The quad rows are split into consecutive runs, one per slab: the slab of global rows [r0, r1) counts those whose lower
     // row is r0 .. r1 - 1, the last slab also the one below row R - 1.  A slab with r0 > 0 needs row r0 - 1: it is STAGED into
     // the slab's scratch buffer behind the counters -- ghost rows are never read, whatever ghost_depth says.
-    const size_t nslab = ctx->slabs.size(), pitch = (size_t)f0->pitch, row_bytes = pitch * sizeof(float);
+    const size_t nslab = ctx->slabs.size(), pitch = (size_t)f0->pitch;
     const size_t counters = (bytes + 255) / 256 * 256; // (the staged rows start on a 256-byte boundary)
-    std::vector<float> upper; // several processes: the last rows of the rank above, [plane][cols]
-    if (ctx->world > 1) {
-        // every rank's last rows (n x cols floats) to every rank; this one keeps those of the rank above
-        const size_t cols = (size_t)f0->cols, share = (size_t)n * cols * sizeof(float);
-        std::vector<float> mine((size_t)n * cols), all((size_t)ctx->world * (size_t)n * cols);
-        SlabRt &sl = ctx->slabs[nslab - 1];
-        GS_HIP(hipSetDevice(sl.device));
-        for (int32_t p = 0; p < n; ++p) {
-            const FieldSlab &fs = fields[p]->s[nslab - 1];
-            GS_HIP(hipMemcpyAsync(mine.data() + (size_t)p * cols, fs.row0 + (ptrdiff_t)(fs.rows - 1) * (ptrdiff_t)pitch,
-                                  cols * sizeof(float), hipMemcpyDeviceToHost, sl.compute));
-        }
-        GS_HIP(hipStreamSynchronize(sl.compute));
-        GS_TRY(exchange(ctx, mine.data(), std::vector<size_t>((size_t)ctx->world, share), "morphology", all.data()));
-        if (ctx->rank > 0) upper.assign(all.begin() + (ptrdiff_t)((size_t)(ctx->rank - 1) * (size_t)n * cols),
-                                        all.begin() + (ptrdiff_t)((size_t)ctx->rank * (size_t)n * cols));
-    }
+    GS_TRY(stage_rows_above(ctx, fields, n, 1, counters, "morphology"));
     std::vector<uint64_t> part(nslab * words);
     for (size_t i = 0; i < nslab; ++i) {
         SlabRt &sl = ctx->slabs[i];
-        GS_TRY(ensure_scratch(ctx, (int)i, counters + (size_t)n * row_bytes, "morphology"));
         GS_HIP(hipSetDevice(sl.device));
         unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
         float *staged = reinterpret_cast<float *>(static_cast<unsigned char *>(sl.scratch) + counters);
@@ -516,16 +577,7 @@ int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
         const float *planes[4] = {nullptr, nullptr, nullptr, nullptr}, *row_above[4] = {nullptr, nullptr, nullptr, nullptr};
         for (int32_t p = 0; p < n; ++p) {
             planes[p] = fields[p]->s[i].row0;
-            if (first) continue;
-            row_above[p] = staged + (size_t)p * pitch;
-            if (i > 0) { // (every stream is idle: the row is final, and nobody else uses this slab's scratch buffer)
-                const FieldSlab &up = fields[p]->s[i - 1];
-                GS_TRY(copy_row(ctx, (int)i - 1, up.row0 + (ptrdiff_t)(up.rows - 1) * (ptrdiff_t)pitch, (int)i, staged + (size_t)p * pitch,
-                                (size_t)f0->cols * sizeof(float), sl.compute));
-            } else {
-                GS_HIP(hipMemcpyAsync(staged + (size_t)p * pitch, upper.data() + (size_t)p * (size_t)f0->cols,
-                                      (size_t)f0->cols * sizeof(float), hipMemcpyHostToDevice, sl.compute));
-            }
+            if (!first) row_above[p] = staged + (size_t)p * pitch;
         }
         GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
         GS_HIP(gs_launch_quads(planes, row_above, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, last ? 1 : 0,
@@ -533,17 +585,8 @@ int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
         GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
     }
     GS_TRY(sync_compute(ctx));
-    std::vector<uint64_t> sum(words, (uint64_t)0);
-    for (size_t i = 0; i < nslab; ++i)
-        for (size_t w = 0; w < words; ++w) sum[w] += part[i * words + w];
-    if (ctx->world > 1) {
-        // Several processes: every rank's counters to every rank, added in the same way everywhere.
-        std::vector<uint64_t> all((size_t)ctx->world * words);
-        GS_TRY(exchange(ctx, sum.data(), std::vector<size_t>((size_t)ctx->world, bytes), "morphology", all.data()));
-        std::fill(sum.begin(), sum.end(), (uint64_t)0);
-        for (int q = 0; q < ctx->world; ++q)
-            for (size_t w = 0; w < words; ++w) sum[w] += all[(size_t)q * words + w];
-    }
+    std::vector<uint64_t> sum;
+    GS_TRY(add_counters(ctx, part, words, "morphology", sum));
     for (size_t j = 0; j < (size_t)n * (size_t)nt; ++j) out[j] = from_counted(sum.data() + j * kQuadCounted, f0->rows, f0->cols);
     return GS_OK;
 }
@@ -574,6 +617,83 @@ int32_t gs_members_morphology(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
     GS_HIP(hipMemcpyAsync(host.data(), dev, bytes, hipMemcpyDeviceToHost, sl.compute));
     GS_HIP(hipStreamSynchronize(sl.compute));
     for (size_t j = 0; j < results; ++j) out[j] = from_counted(host.data() + j * kQuadCounted, e->rows, e->cols);
+    return GS_OK;
+}
+
+int32_t gs_fields_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
+                              int32_t nt, int32_t max_lag, uint64_t *out)
+{
+    if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    // the thresholds and the lag before any handle is looked at; a count that is no 1..4 is check_planes' first refusal
+    GS_TRY(check_thresholds(thresholds, n >= 1 && n <= 4 ? n : 0, nt));
+    GS_TRY(check_max_lag(max_lag));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    const size_t depth = (size_t)max_lag;
+    const size_t words = (size_t)n * (size_t)nt * 4 * (depth + 1), bytes = words * sizeof(uint64_t);
+    std::fill(out, out + words, (uint64_t)0);
+    if (f0->rows == 0 || f0->cols == 0) return GS_OK; // the same shape on every rank: nobody exchanges anything
+    // A pair belongs to its LOWER row: the slab of global rows [r0, r1) counts the pairs whose lower cell lies in it and needs
+    // the min(L, r0) rows above r0.  With several slabs these are the L last rows of the slab above, so every slab -- other
+    // processes' too (the split of gs_field_create): every rank reaches the same verdict -- must hold L rows.
+    const uint64_t S = (uint64_t)ctx->total_slabs();
+    for (uint64_t k = 0; S > 1 && k < S; ++k)
+        if ((k + 1) * f0->rows / S - k * f0->rows / S < (uint64_t)max_lag)
+            return fail(GS_ERR_UNSUPPORTED, "slab %llu holds %llu rows, fewer than the largest lag %d (the rows above a slab "
+                                            "come from the one slab above it)",
+                        (unsigned long long)k, (unsigned long long)((k + 1) * f0->rows / S - k * f0->rows / S), max_lag);
+    const size_t nslab = ctx->slabs.size(), pitch = (size_t)f0->pitch;
+    const size_t counters = (bytes + 255) / 256 * 256; // (the staged rows start on a 256-byte boundary)
+    GS_TRY(stage_rows_above(ctx, fields, n, depth, counters, "correlation"));
+    std::vector<uint64_t> part(nslab * words);
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        GS_HIP(hipSetDevice(sl.device));
+        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+        float *staged = reinterpret_cast<float *>(static_cast<unsigned char *>(sl.scratch) + counters);
+        const bool first = f0->s[i].g_row0 == 0;
+        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr}, *rows_above[4] = {nullptr, nullptr, nullptr, nullptr};
+        for (int32_t p = 0; p < n; ++p) {
+            planes[p] = fields[p]->s[i].row0;
+            if (!first) rows_above[p] = staged + (size_t)p * depth * pitch;
+        }
+        GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+        GS_HIP(gs_launch_pairs(planes, rows_above, first ? 0 : max_lag, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows,
+                               (int32_t)f0->cols, thresholds, above, nt, max_lag, max_groups(ctx), dev, sl.compute));
+        GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    std::vector<uint64_t> sum;
+    GS_TRY(add_counters(ctx, part, words, "correlation", sum));
+    std::copy(sum.begin(), sum.end(), out);
+    return GS_OK;
+}
+
+int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
+                               const int32_t above[2], int32_t nt, int32_t max_lag, uint64_t *out)
+{
+    if (!ctx || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_thresholds(thresholds, 2, nt)); // before the ensemble is looked at
+    GS_TRY(check_max_lag(max_lag));
+    GS_TRY(check_members(ctx, e, first, count));
+    const uint64_t cells = e->rows * e->cols;
+    const size_t words = (size_t)(2 * count) * (size_t)nt * 4 * (size_t)(max_lag + 1), bytes = words * sizeof(uint64_t);
+    if (cells == 0) {
+        std::fill(out, out + words, (uint64_t)0);
+        return GS_OK;
+    }
+    GS_TRY(ensure_scratch(ctx, 0, bytes, "correlation"));
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+    // member first + i's U and V are planes 2 i and 2 i + 1 of the launch, `cells` floats from one member to the next; each
+    // is a plane of its own: nothing above its first row -- it never sees its neighbours' rows
+    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
+    GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+    GS_HIP(gs_launch_pairs(planes, nullptr, 0, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows,
+                           (int32_t)e->cols, thresholds, above, nt, max_lag, max_groups(ctx), dev, sl.compute));
+    GS_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
     return GS_OK;
 }
 

@@ -507,6 +507,131 @@ def morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"
     return [[Morphology.from_quads(out[i, k], thr[i * nt + k], above[i], rows * cols) for k in range(nt)] for i in range(n)]
 
 
+CORRELATION_STEPS = ((0, 1), (1, 0), (1, 1), (1, -1))  # e_k = (dr, dc): along a row, down a column, diagonal, anti-diagonal
+
+
+def pairs_total(rows: int, cols: int, max_lag: int) -> np.ndarray:
+    """``N[k, d]``, the number of cell pairs {p, p + d e_k} inside a grid of rows x cols cells, d = 0 .. max_lag: geometry,
+    ``max(rows - d dr, 0) * max(cols - d |dc|, 0)`` (include/gs_hip.h)."""
+    d = np.arange(max_lag + 1, dtype=np.int64)
+    return np.stack([np.maximum(rows - d * dr, 0) * np.maximum(cols - d * abs(dc), 0) for dr, dc in CORRELATION_STEPS])
+
+
+@dataclass(frozen=True, eq=False)
+class Correlation:
+    """The two-point pair counts of one thresholded plane, counted on the device (``gs_fields_correlation``; the rule is
+    include/gs_hip.h's): a cell is set when it is above ``threshold`` (``above``) or below it, and ``pairs[k, d]`` is the
+    number of cell pairs {p, p + d e_k}, d = 0 .. ``max_lag``, inside the grid with both cells set, for the four unit steps
+    e_k of ``CORRELATION_STEPS``.  Pairs never wrap.  Everything else is computed here from these integers."""
+
+    pairs: np.ndarray
+    threshold: float
+    above: bool
+    rows: int
+    cols: int
+
+    @classmethod
+    def from_pairs(cls, pairs, threshold: float, above: bool, rows: int, cols: int) -> "Correlation":
+        p = np.array(pairs, np.uint64)
+        return cls(p.reshape(4, p.size // 4), float(threshold), bool(above), int(rows), int(cols))
+
+    @property
+    def max_lag(self) -> int:
+        return self.pairs.shape[1] - 1
+
+    @property
+    def lags(self) -> np.ndarray:
+        return np.arange(self.max_lag + 1, dtype=np.int64)
+
+    def pairs_set(self, k: int) -> np.ndarray:
+        """Pairs along e_k with both cells set, by lag (uint64)."""
+        return self.pairs[k]
+
+    def pairs_total(self, k: int) -> np.ndarray:
+        """Pairs along e_k that exist inside the grid, by lag (int64)."""
+        return pairs_total(self.rows, self.cols, self.max_lag)[k]
+
+    @property
+    def fraction(self) -> float:
+        """Set cells over cells."""
+        cells = self.rows * self.cols
+        return int(self.pairs[0, 0]) / cells if cells else float("nan")
+
+    def s2(self, k: int) -> np.ndarray:
+        """The two-point probability along e_k: set pairs over pairs, f64; NaN where no pair exists."""
+        total = self.pairs_total(k).astype(np.float64)
+        out = np.full(total.shape, np.nan)
+        np.divide(self.pairs[k].astype(np.float64), total, out=out, where=total > 0)
+        return out
+
+    def autocovariance(self, k: int) -> np.ndarray:
+        """``s2(k) - fraction ** 2``: positive where cells that far apart tend to be alike, 0 where they are unrelated."""
+        return self.s2(k) - self.fraction ** 2
+
+    def distance(self, k: int) -> np.ndarray:
+        """The length of d e_k in cells: d along rows and columns, d sqrt(2) along the diagonals."""
+        return self.lags * (1.0 if k < 2 else float(np.sqrt(2.0)))
+
+    def first_zero_crossing(self, k: int) -> Optional[float]:
+        """The lag (in steps of e_k, linearly interpolated) at which the autocovariance first reaches 0 from above."""
+        c = self.autocovariance(k)
+        for d in range(1, c.size):
+            if np.isnan(c[d]) or np.isnan(c[d - 1]):
+                return None
+            if c[d - 1] > 0.0 and c[d] <= 0.0:
+                return (d - 1) + c[d - 1] / (c[d - 1] - c[d])
+        return None
+
+    def first_minimum(self, k: int) -> Optional[int]:
+        """The first lag d >= 1 whose autocovariance is below that of d - 1 and not above that of d + 1 -- half the
+        pattern's wavelength along e_k -- or None when there is none inside the lags."""
+        c = self.autocovariance(k)
+        for d in range(1, c.size - 1):
+            if np.isnan(c[d + 1]):
+                return None
+            if c[d] < c[d - 1] and c[d] <= c[d + 1]:
+                return d
+        return None
+
+    def first_maximum_after_minimum(self, k: int) -> Optional[int]:
+        """The first lag beyond ``first_minimum`` whose autocovariance is above that of d - 1 and not below that of d + 1 --
+        the pattern's wavelength along e_k -- or None."""
+        m = self.first_minimum(k)
+        if m is None:
+            return None
+        c = self.autocovariance(k)
+        for d in range(m + 1, c.size - 1):
+            if np.isnan(c[d + 1]):
+                return None
+            if c[d] > c[d - 1] and c[d] >= c[d + 1]:
+                return d
+        return None
+
+
+def correlation_fields(context: "HipContext", fields: Sequence["HipConcentration"], thresholds: Sequence[Sequence[float]],
+                       above: Sequence[bool], max_lag: int = 32) -> List[List[Correlation]]:
+    """``gs_fields_correlation``: two-point pair counts of 1..4 planes of one shape over the whole global grid in one call
+    (collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number for
+    every plane; all counted in one pass) with the sense ``above[i]``, lags 0 .. ``max_lag`` (1..64).  Returns one list of
+    ``Correlation`` per plane."""
+    n = len(fields)
+    if len(thresholds) != n or len(above) != n:
+        raise ValueError("one list of thresholds and one sense per field")
+    lists = [_thresholds(t) for t in thresholds]
+    nt = len(lists[0]) if lists else 0
+    if any(len(t) != nt for t in lists):
+        raise ValueError("the same number of thresholds for every field")
+    flat = [x for t in lists for x in t]
+    thr = (ctypes.c_float * max(len(flat), 1))(*flat)
+    sense = (ctypes.c_int32 * max(n, 1))(*[1 if a else 0 for a in above])
+    lags = max_lag + 1 if 1 <= max_lag <= 64 else 1
+    out = np.zeros((max(n, 1), max(nt, 1), 4, lags), np.uint64)
+    capi.check(context._lib.gs_fields_correlation(context.handle, _handle_array(fields), n, thr, sense, nt, max_lag,
+                                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    rows, cols = fields[0].shape()
+    return [[Correlation.from_pairs(out[i, k], thr[i * nt + k], above[i], rows, cols) for k in range(nt)] for i in range(n)]
+
+
 def pinned_empty(shape: Sequence[int]) -> np.ndarray:
     """float32 array in page-locked host memory (``gs_host_alloc``) for overlapped downloads.
     The allocation is released when the last view of it is garbage-collected."""
@@ -716,6 +841,12 @@ class HipConcentration:
         is set when it is above (``above``) or below the threshold."""
         return morphology_fields(context, [self], [thresholds], [above])[0]
 
+    def correlation(self, context: HipContext, thresholds, max_lag: int = 32, above: bool = True) -> List[Correlation]:
+        """The two-point pair counts of this plane thresholded at each of ``thresholds`` (1..4, one pass), lags 0 ..
+        ``max_lag`` along four directions over the whole global grid, counted on the device (``gs_fields_correlation``;
+        blocking, collective in a multi-process context)."""
+        return correlation_fields(context, [self], [thresholds], [above], max_lag)[0]
+
     def change_from(self, context: HipContext, other: "HipConcentration") -> Change:
         """How far this plane is from ``other`` (this minus other, cell by cell in f64) over the whole global grid,
         computed on the device (``gs_fields_compare``; blocking, collective in a multi-process context)."""
@@ -874,6 +1005,18 @@ class Species:
         u, v = morphology_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], [u_above, v_above])
         return u, v
 
+    def correlation(self, v_thresholds=(0.25,), u_thresholds=None, max_lag: int = 32,
+                    above: Tuple[bool, bool] = (False, True)) -> Tuple[List[Correlation], List[Correlation]]:
+        """(U, V) two-point pair counts of the current state in one call (``gs_fields_correlation``; blocking, collective in
+        a multi-process context): one ``Correlation`` per threshold (1..4 per species, the same number for both), lags 0 ..
+        ``max_lag`` (1..64).  ``above`` = (U's sense, V's sense): V carries the pattern where it is high and U where it is
+        low; without ``u_thresholds`` only V is looked at and the U list is empty."""
+        in_u, in_v, _, _ = self.in_out()
+        if u_thresholds is None:
+            return [], correlation_fields(self._context, [in_v], [v_thresholds], [above[1]], max_lag)[0]
+        u, v = correlation_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], list(above), max_lag)
+        return u, v
+
     def snapshot(self) -> Snapshot:
         """The current state copied into planes of its own on the device (``gs_fields_copy``; blocking)."""
         return Snapshot(self)
@@ -1012,6 +1155,26 @@ class Ensemble:
         out = np.zeros((max(count, 0), 2, max(nt, 1), 6), np.uint64)
         capi.check(self._ctx._lib.gs_members_morphology(self._ctx.handle, self.handle, first, count, thr, sense, nt,
                                                          out.ctypes.data_as(ctypes.POINTER(capi.GsMorphology))))
+        return out
+
+    def correlations(self, first: int = 0, count: Optional[int] = None, v_thresholds=(0.25,), u_thresholds=(0.5,),
+                     max_lag: int = 32, above: Tuple[bool, bool] = (False, True)) -> np.ndarray:
+        """Two-point pair counts of members ``[first, first + count)`` counted on the device (``gs_members_correlation``,
+        blocking): a ``uint64`` array ``[count, 2, nt, 4, max_lag + 1]`` -- axis 1: U at ``u_thresholds`` with the sense
+        ``above[0]``, V at ``v_thresholds`` with ``above[1]`` (1..4 thresholds, the same number for both); axis 3: the unit
+        steps of ``CORRELATION_STEPS``; last axis: the lag -- what ``Species.correlation`` gives for a lone Species in the
+        member's state.  ``Correlation.from_pairs`` turns one ``[4, max_lag + 1]`` entry into the object."""
+        first, count = self._range(first, count)
+        tu, tv = _thresholds(u_thresholds), _thresholds(v_thresholds)
+        if len(tu) != len(tv):
+            raise ValueError("the same number of thresholds for U and V")
+        nt = len(tu)
+        thr = (ctypes.c_float * max(2 * nt, 1))(*(tu + tv))
+        sense = (ctypes.c_int32 * 2)(1 if above[0] else 0, 1 if above[1] else 0)
+        lags = max_lag + 1 if 1 <= max_lag <= 64 else 1
+        out = np.zeros((max(count, 0), 2, max(nt, 1), 4, lags), np.uint64)
+        capi.check(self._ctx._lib.gs_members_correlation(self._ctx.handle, self.handle, first, count, thr, sense, nt, max_lag,
+                                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out
 
     def snapshot(self) -> "Ensemble":

@@ -31,6 +31,15 @@ from above, ``--morph-threshold-u A[,B,...]`` (as many values; default 0.5 for e
 axis: Q0, Q1, Q2, Q3, Q4, QD) and, derived from them, ``area_fraction``, ``perimeter``, ``euler4``, ``euler8``, each
 ``[samples, members, 2, nt]``.  It changes no state either: the HDF5 file is byte for byte the same without it.
 
+``--correlation-every N`` records, at the same steps again, the two-point pair counts of every member's thresholded planes
+counted on the device (``Ensemble.correlations``; the rule is include/gs_hip.h's) -- "how far apart are the spots, which way
+do the stripes run?" -- into ``<output stem>.correlation.npz``.  ``--corr-threshold-v A[,B,...]`` (1 to 4 values, required
+with the flag) thresholds V from above, ``--corr-threshold-u A[,B,...]`` (as many values; default 0.5 for each) thresholds U
+from below, ``--corr-lags L`` (1..64, default 32) is the largest lag.  The file holds ``steps[samples]``,
+``thresholds_u[nt]``, ``thresholds_v[nt]``, ``max_lag``, ``shape[2]``, ``pairs[samples, members, 2, nt, 4, L + 1]`` (axis 2: U,
+V; axis 4: the unit steps (0, 1), (1, 0), (1, 1), (1, -1); last axis: the lag) and ``pairs_total[4, L + 1]``, the pairs that
+exist.  It changes no state either: the HDF5 file is byte for byte the same without it.
+
 ``--steady-every N`` asks of every member "has it stopped changing?".  A snapshot of the ensemble is kept on the device
 (``Ensemble.snapshot``), taken at step 0; after every N steps and after the last one every member is compared with it on the
 device (``Ensemble.changes_since``: with d = now - snapshot per cell in f64, the sum of |d|, the sum of d * d and the largest
@@ -69,7 +78,7 @@ import numpy as np
 
 from . import hdf5_min
 from .simulate import add_backend_args, backend_args
-from .simulation import Parameters, Simulation, quad_measures
+from .simulation import Parameters, Simulation, pairs_total, quad_measures
 
 
 def value_range(text: str) -> List[float]:
@@ -128,6 +137,14 @@ def parse(argv=None):
                     help="1 to 4 thresholds: V is set where it is above them")
     ap.add_argument("--morph-threshold-u", type=threshold_list, default=None, metavar="A[,B,...]",
                     help="as many thresholds: U is set where it is below them (default 0.5 each)")
+    ap.add_argument("--correlation-every", type=int, default=0, metavar="N",
+                    help="record every member's two-point pair counts every N steps and at the end "
+                         "(<output stem>.correlation.npz)")
+    ap.add_argument("--corr-threshold-v", type=threshold_list, default=None, metavar="A[,B,...]",
+                    help="1 to 4 thresholds: V is set where it is above them")
+    ap.add_argument("--corr-threshold-u", type=threshold_list, default=None, metavar="A[,B,...]",
+                    help="as many thresholds: U is set where it is below them (default 0.5 each)")
+    ap.add_argument("--corr-lags", type=int, default=32, metavar="L", help="the largest lag (1..64)")
     ap.add_argument("--steady-every", type=int, default=0, metavar="N",
                     help="compare every member with its state N steps before, every N steps and at the end "
                          "(<output stem>.steady.npz)")
@@ -160,6 +177,16 @@ def parse(argv=None):
         args.morph_threshold_u = [0.5] * len(args.morph_threshold_v)
     if args.morph_threshold_v is not None and len(args.morph_threshold_u) != len(args.morph_threshold_v):
         ap.error("--morph-threshold-u needs as many values as --morph-threshold-v")
+    if args.correlation_every < 0:
+        ap.error("--correlation-every must be at least 1 (0 = off)")
+    if args.correlation_every and args.corr_threshold_v is None:
+        ap.error("--correlation-every needs --corr-threshold-v")
+    if args.corr_threshold_u is None and args.corr_threshold_v is not None:
+        args.corr_threshold_u = [0.5] * len(args.corr_threshold_v)
+    if args.corr_threshold_v is not None and len(args.corr_threshold_u) != len(args.corr_threshold_v):
+        ap.error("--corr-threshold-u needs as many values as --corr-threshold-v")
+    if not 1 <= args.corr_lags <= 64:
+        ap.error("--corr-lags must be in 1..64")
     return args
 
 
@@ -194,6 +221,10 @@ def morphology_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".morphology.npz"
 
 
+def correlation_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".correlation.npz"
+
+
 def steady_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".steady.npz"
 
@@ -226,6 +257,13 @@ def write_morphologies(path: str, steps: List[int], samples: List[np.ndarray], t
              thresholds_v=np.asarray(thresholds_v, np.float32), quads=np.ascontiguousarray(q),
              area_fraction=area / cells if cells else np.full(area.shape, np.nan), perimeter=perimeter, euler4=euler4,
              euler8=euler8)
+
+
+def write_correlations(path: str, steps: List[int], samples: List[np.ndarray], thresholds_u, thresholds_v, max_lag: int,
+                       shape) -> None:
+    np.savez(path, steps=np.asarray(steps, np.int64), thresholds_u=np.asarray(thresholds_u, np.float32),
+             thresholds_v=np.asarray(thresholds_v, np.float32), max_lag=np.int64(max_lag), shape=np.asarray(shape, np.int64),
+             pairs=np.ascontiguousarray(np.stack(samples, axis=0)), pairs_total=pairs_total(shape[0], shape[1], max_lag))
 
 
 def settled_steps(steps: List[int], max_abs: np.ndarray, tol: float) -> np.ndarray:
@@ -264,11 +302,12 @@ def run(args) -> dict:
     hist_at = sample_steps(args.steps, args.histogram_every) if args.histogram_every else []
     steady_at = sample_steps(args.steps, args.steady_every) if args.steady_every else []
     morph_at = sample_steps(args.steps, args.morphology_every) if args.morphology_every else []
+    corr_at = sample_steps(args.steps, args.correlation_every) if args.correlation_every else []
     done, settled, taken = 0, None, None
-    if summary_at or hist_at or steady_at or morph_at:
-        summaries, hists, changes, morphs = [], [], [], []
+    if summary_at or hist_at or steady_at or morph_at or corr_at:
+        summaries, hists, changes, morphs, corrs = [], [], [], [], []
         snap = ens.snapshot() if steady_at else None
-        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at)):
+        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at)):
             ens.prepare_steps(at - done)
             done = at
             if at in summary_at:
@@ -277,6 +316,9 @@ def run(args) -> dict:
                 hists.append(ens.histograms(bins=args.hist_bins, u_range=args.hist_range_u, v_range=args.hist_range_v))
             if at in morph_at:
                 morphs.append(ens.morphologies(v_thresholds=args.morph_threshold_v, u_thresholds=args.morph_threshold_u))
+            if at in corr_at:
+                corrs.append(ens.correlations(v_thresholds=args.corr_threshold_v, u_thresholds=args.corr_threshold_u,
+                                              max_lag=args.corr_lags))
             if at in steady_at:
                 changes.append(ens.changes_since(snap))
                 snap.copy_from(ens)
@@ -296,6 +338,9 @@ def run(args) -> dict:
         if morph_at:
             write_morphologies(morphology_path(args.output), morph_at[:len(morphs)], morphs, args.morph_threshold_u,
                                args.morph_threshold_v, shape[0] * shape[1])
+        if corr_at:
+            write_correlations(correlation_path(args.output), corr_at[:len(corrs)], corrs, args.corr_threshold_u,
+                               args.corr_threshold_v, args.corr_lags, shape)
         if steady_at:
             if args.steady_retire:
                 sim.context.sync()

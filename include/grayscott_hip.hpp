@@ -129,6 +129,46 @@ struct Morphology {
     int64_t euler8() const { return ((int64_t)quads[1] - (int64_t)quads[3] - 2 * (int64_t)quads[5]) / 4; }
 };
 
+// The two-point pair counts of one thresholded plane, counted on the device (gs_fields_correlation; the rule is gs_hip.h's):
+// pairs[k][d] is the number of cell pairs {p, p + d e_k}, d = 0 .. max_lag, inside the grid with both cells set, for the unit
+// steps e_0 = (0, 1), e_1 = (1, 0), e_2 = (1, 1), e_3 = (1, -1).  Pairs never wrap.  What follows is computed from the integers.
+struct Correlation {
+    std::array<std::vector<uint64_t>, 4> pairs;
+    float threshold = 0.0f;
+    bool above = true;
+    uint64_t rows = 0, cols = 0;
+    // `c`: [4][max_lag + 1], the layout of gs_fields_correlation for one plane and threshold
+    static Correlation from_c(const uint64_t *c, int32_t max_lag, float threshold, bool above, uint64_t rows, uint64_t cols)
+    {
+        Correlation o;
+        for (std::size_t k = 0; k < 4; ++k) o.pairs[k].assign(c + k * (std::size_t)(max_lag + 1), c + (k + 1) * (std::size_t)(max_lag + 1));
+        o.threshold = threshold;
+        o.above = above;
+        o.rows = rows;
+        o.cols = cols;
+        return o;
+    }
+    int32_t max_lag() const { return (int32_t)pairs[0].size() - 1; }
+    uint64_t pairs_set(std::size_t k, std::size_t d) const { return pairs[k][d]; }
+    // the pairs {p, p + d e_k} that exist inside the grid: geometry
+    uint64_t pairs_total(std::size_t k, std::size_t d) const
+    {
+        const uint64_t dr = k == 0 ? 0 : d, dc = k == 1 ? 0 : d;
+        return (rows > dr ? rows - dr : 0) * (cols > dc ? cols - dc : 0);
+    }
+    // set cells over cells
+    double fraction() const { return rows * cols != 0 ? (double)pairs[0][0] / (double)(rows * cols) : std::nan(""); }
+    // the two-point probability: set pairs over pairs; NaN where no pair exists
+    double s2(std::size_t k, std::size_t d) const
+    {
+        const uint64_t total = pairs_total(k, d);
+        return total ? (double)pairs[k][d] / (double)total : std::nan("");
+    }
+    double autocovariance(std::size_t k, std::size_t d) const { return s2(k, d) - fraction() * fraction(); }
+    // the length of d e_k in cells
+    double distance(std::size_t k, std::size_t d) const { return (double)d * (k < 2 ? 1.0 : std::sqrt(2.0)); }
+};
+
 struct Parameters {
     std::array<std::array<Precision, 3>, 3> weights{{{0.25f, 0.5f, 0.25f}, {0.5f, 0.0f, 0.5f}, {0.25f, 0.5f, 0.25f}}};
     Precision diffusion_rate_u = 0.1f, diffusion_rate_v = 0.05f;
@@ -478,6 +518,32 @@ class Species {
         }
         return uv;
     }
+    // (U, V) two-point pair counts of the current state over the whole global grid, in one call (gs_fields_correlation;
+    // blocking, collective in a multi-process context): one Correlation per threshold (1..4 per species, the same number for
+    // both), lags 0 .. max_lag (1..64), U set where it is below its thresholds and V where it is above, unless the senses say
+    // otherwise
+    std::pair<std::vector<Correlation>, std::vector<Correlation>> correlation(const std::vector<float> &v_thresholds,
+                                                                             const std::vector<float> &u_thresholds,
+                                                                             int32_t max_lag = 32, bool v_above = true,
+                                                                             bool u_above = false)
+    {
+        if (u_thresholds.size() != v_thresholds.size())
+            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t nt = v_thresholds.size(), lags = max_lag >= 1 && max_lag <= 64 ? (std::size_t)max_lag + 1 : 1;
+        std::vector<float> t(u_thresholds);
+        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
+        std::vector<uint64_t> out(2 * nt * 4 * lags + 1);
+        check(gs_fields_correlation(context_->get(), planes, 2, t.data(), sense, (int32_t)nt, max_lag, out.data()));
+        const Shape s = shape();
+        std::pair<std::vector<Correlation>, std::vector<Correlation>> uv;
+        for (std::size_t k = 0; k < nt; ++k) {
+            uv.first.push_back(Correlation::from_c(out.data() + k * 4 * lags, max_lag, t[k], u_above, s[0], s[1]));
+            uv.second.push_back(Correlation::from_c(out.data() + (nt + k) * 4 * lags, max_lag, t[nt + k], v_above, s[0], s[1]));
+        }
+        return uv;
+    }
     // the current state copied into planes of its own on the device (gs_fields_copy; blocking)
     Snapshot snapshot()
     {
@@ -642,6 +708,29 @@ class Ensemble {
         for (std::size_t i = 0; i < 2 * count * nt; ++i) {
             const std::size_t species = (i / nt) & 1, k = i % nt;
             out.push_back(Morphology::from_c(c[i], t[species * nt + k], sense[species] != 0, shape_[0] * shape_[1]));
+        }
+        return out;
+    }
+    // two-point pair counts of members [first, first + count) from the newest state (gs_members_correlation, blocking):
+    // element (2 i + s) * nt + j = species s (0 = U, 1 = V) of member first + i at that species' threshold j, what
+    // Species::correlation gives for a lone Species in that state
+    std::vector<Correlation> correlations(std::size_t first, std::size_t count, const std::vector<float> &v_thresholds,
+                                          const std::vector<float> &u_thresholds, int32_t max_lag = 32, bool v_above = true,
+                                          bool u_above = false) const
+    {
+        if (u_thresholds.size() != v_thresholds.size())
+            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
+        const std::size_t nt = v_thresholds.size(), lags = max_lag >= 1 && max_lag <= 64 ? (std::size_t)max_lag + 1 : 1;
+        std::vector<float> t(u_thresholds);
+        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
+        std::vector<uint64_t> c(2 * count * nt * 4 * lags + 1);
+        check(gs_members_correlation(ctx_->get(), e_, first, count, t.data(), sense, (int32_t)nt, max_lag, c.data()));
+        std::vector<Correlation> out;
+        for (std::size_t i = 0; i < 2 * count * nt; ++i) {
+            const std::size_t species = (i / nt) & 1, j = i % nt;
+            out.push_back(Correlation::from_c(c.data() + i * 4 * lags, max_lag, t[species * nt + j], sense[species] != 0, shape_[0],
+                                              shape_[1]));
         }
         return out;
     }

@@ -644,6 +644,46 @@ int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
 int32_t gs_members_morphology(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
                               const int32_t above[2], int32_t nt, gs_morphology *out);
 
+/* Two-point correlations computed on the device: the two-point probability function of one plane of the WHOLE global grid
+ * after thresholding -- for a lag vector, the number of cell pairs that far apart which are both set; from it the pattern's
+ * wavelength and the direction of its stripes follow ("how far apart are the spots?") -- without downloading the plane.  For
+ * a plane x of R x C cells, a threshold t, a sense `above` and a largest lag L, 1 <= L <= 64:
+ *   - a cell is SET by morphology's rule: iff x > t (above != 0) or x < t (above == 0), one f32 comparison.  A NaN cell is
+ *     never set, a cell equal to t is not set, infinities compare as they do, a sub-normal cell is the value it is (never
+ *     flushed);
+ *   - four unit steps e_k = (dr, dc):  k = 0: (0, 1) along a row;  k = 1: (1, 0) down a column;  k = 2: (1, 1) the diagonal;
+ *     k = 3: (1, -1) the anti-diagonal;
+ *   - pairs[k][d], d = 0 .. L, is the number of unordered cell pairs {p, p + d e_k} with both cells inside the grid and both
+ *     set.  d = 0 is the number of set cells, the same for all four k: morphology's area A.  Pairs NEVER wrap, under every
+ *     boundary rule, as morphology's quads never do: a pair across a periodic edge is not formed.  A lag that does not fit
+ *     the grid counts 0.
+ * The number of pairs that exist, N_k(d) = max(R - d dr, 0) max(C - d |dc|, 0), is geometry: the hosts compute it -- and from
+ * both S2_k(d) = pairs / N, the autocovariance S2 - (A / (R C))^2, its first minimum (half the wavelength) and the maximum
+ * after it (the wavelength) --, the device does not.  An empty plane (R = 0 or C = 0): GS_OK, all zeros.
+ * Counts are integers and additive over any partition of the pairs: the result is the same bits for any slab count, process
+ * count, step kernel or launch shape, and a member's is that of a lone Species in the same state.
+ *   gs_fields_correlation   out[((i * nt + j) * 4 + k) * (L + 1) + d] for fields[i] thresholded at thresholds[i * nt + j] with
+ *                           the sense above[i], i < n (1..4 fields of one shape), j < nt (1..4 thresholds per field, all
+ *                           counted in one pass over the plane), L = max_lag: one wait for enqueued work (as
+ *                           gs_fields_summarize: a persistent window launch that gave up is run again first), one launch per
+ *                           slab.  A pair belongs to its lower row; the min(L, r0) rows above a slab's first row r0 are staged
+ *                           from the slab (or process) above into a buffer of its own: ghost rows are never read.  A context
+ *                           of more than one slab in which some slab -- any rank's -- holds fewer than L rows:
+ *                           GS_ERR_UNSUPPORTED, on every rank alike.  In a multi-process context the call is collective, like
+ *                           gs_run, and every rank receives the counts of the global grid.
+ *   gs_members_correlation  the same layout with i = 2 m + s for species s (0 = U with thresholds[j] and above[0]; 1 = V with
+ *                           thresholds[nt + j] and above[1]) of member first + m, m < count, from the newest slot: one launch,
+ *                           one copy.  A member is a plane of its own: nothing is above it, its neighbours' rows are never seen.
+ * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID: a null
+ * argument, nt outside 1..4, a NaN threshold or max_lag outside 1..64 -- decided in this order before any handle is looked
+ * at --, a null or foreign handle, mixed shapes, n outside 1..4, members outside the ensemble.
+ * Not done: pairs wrapped under the periodic rule; the full 2-D lag window and lags beyond 64; real-valued autocorrelation
+ * and spectra; cross-correlation of U with V; slabs shorter than L. */
+int32_t gs_fields_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
+                              int32_t nt, int32_t max_lag, uint64_t *out);
+int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
+                               const int32_t above[2], int32_t nt, int32_t max_lag, uint64_t *out);
+
 /* Two states compared on the device: how far one plane of the WHOLE global grid is from another of the same shape -- "has
  * this run stopped changing?" -- without downloading either, and the device copies that give a state to compare with
  * (snapshots) or to go back to (restores).
