@@ -16,6 +16,7 @@ from .simulation import (  # noqa: F401
     Histogram,
     HipConcentration,
     HipContext,
+    Components,
     Morphology,
     Parameters,
     Simulation,
@@ -27,4 +28,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]
+           "Components", "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]

@@ -56,6 +56,9 @@ UNITS = [
     # two-point pair counts of thresholded planes (lags 0..64 along four directions, one pass for up to four thresholds):
     # the same float mode
     ("gs_correlation.hip", "gs_correlation_k.o", []),
+    # connected components of thresholded planes (union-find over a u32 parent per cell; tile, border, flatten and tally
+    # launches): the same float mode
+    ("gs_components.hip", "gs_components_k.o", []),
     # reduced result images (block averages in f64): the same float mode, a sub-normal pixel is kept
     ("gs_reduce.hip", "gs_reduce_k.o", []),
     # two planes compared (row records of |a - b| in f64, the ensembles' fold): the same float mode, sub-normal cells kept

@@ -52,6 +52,7 @@ EXPORTS = (
     "gs_members_set_active", "gs_members_get_active",
     "gs_fields_morphology", "gs_members_morphology",
     "gs_fields_correlation", "gs_members_correlation",
+    "gs_fields_components", "gs_members_components",
 )
 
 
@@ -147,6 +148,18 @@ class GsMorphology(ctypes.Structure):
     _fields_ = [("quads", ctypes.c_uint64 * 6)]
 
 
+class GsComponents(ctypes.Structure):
+    """``gs_components`` (include/gs_hip.h): the connected components of one thresholded plane -- their number, the sum of
+    their sizes, the largest, and how many fall into each power-of-two size bin -- 280 bytes."""
+
+    _fields_ = [
+        ("components", ctypes.c_uint64),
+        ("set_cells", ctypes.c_uint64),
+        ("largest", ctypes.c_uint64),
+        ("by_size", ctypes.c_uint64 * 32),
+    ]
+
+
 _lib = None
 
 
@@ -234,6 +247,8 @@ def load() -> ctypes.CDLL:
         "gs_members_get_active": (i32, [vp, vp, u64, u64, vp, vp, P(u64)]),
         "gs_fields_morphology": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, P(GsMorphology)]),
         "gs_members_morphology": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, P(GsMorphology)]),
+        "gs_fields_components": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(GsComponents)]),
+        "gs_members_components": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(GsComponents)]),
         "gs_fields_correlation": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(u64)]),
         "gs_members_correlation": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(u64)]),
     }

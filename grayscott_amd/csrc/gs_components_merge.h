@@ -1,0 +1,102 @@
+// gs_components_merge.h -- the seam merge of gs_fields_components (gs_observe.cpp) as a function of plain arrays: no
+// device, no context, so that it can be tested on its own (tests/cpp/components_merge.cpp).
+//
+// Every slab has labelled its own rows as if it were alone: `part[s]` is its result, and for its first and its last row it
+// names, per column, the root of the cell's component inside the slab (kCompUnset for an unset cell) and that component's
+// size.  A component that touches neither row is final.  One that does is OPEN: it is taken out of its slab's `components`
+// and `by_size`, united with the open components it touches across the seams -- by the connectivity rule on the two facing
+// rows --, and what the unions leave is added back with the summed sizes.  A component may cross one seam many times, span
+// several slabs, or touch a slab's first and last row (one node: the root names it); a one-row slab hands the same row in
+// twice.  set_cells is the plain sum; largest is the maximum of the slabs' maxima and the merged sizes, because a merged
+// component is never smaller than its parts.  Integers throughout: every rank that merges the same arrays gets the same bits.
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <utility>
+#include <vector>
+
+#include "../../include/gs_hip.h"
+
+namespace gsi {
+
+constexpr uint32_t kCompUnset = 0xffffffffu;
+
+struct CompSeamRows { // of one slab, `cols` entries each
+    const uint32_t *first_root, *first_size, *last_root, *last_size;
+};
+
+// The bin of gs_components.by_size for a component of `size` >= 1 cells: floor(log2(size)), at most 31.
+inline int comp_size_bin(uint64_t size)
+{
+    int b = 0;
+    while (b < 31 && (size >> (b + 1)) != 0) ++b;
+    return b;
+}
+
+// The slabs in ascending global row order; none is empty.  connectivity: 4 or 8.
+inline gs_components merge_components(const gs_components *part, const CompSeamRows *seam, size_t nslab, size_t cols,
+                                      int connectivity)
+{
+    gs_components out{};
+    for (size_t s = 0; s < nslab; ++s) {
+        out.components += part[s].components;
+        out.set_cells += part[s].set_cells;
+        out.largest = std::max(out.largest, part[s].largest);
+        for (int b = 0; b < 32; ++b) out.by_size[b] += part[s].by_size[b];
+    }
+    if (nslab < 2) return out;
+    // the open components: (slab, root) -> node, each taken once
+    struct Open {
+        uint64_t key; // slab << 32 | root
+        uint32_t size;
+    };
+    std::vector<Open> open;
+    for (size_t s = 0; s < nslab; ++s)
+        for (size_t c = 0; c < cols; ++c) {
+            if (seam[s].first_root[c] != kCompUnset) open.push_back({(uint64_t)s << 32 | seam[s].first_root[c], seam[s].first_size[c]});
+            if (seam[s].last_root[c] != kCompUnset) open.push_back({(uint64_t)s << 32 | seam[s].last_root[c], seam[s].last_size[c]});
+        }
+    std::sort(open.begin(), open.end(), [](const Open &a, const Open &b) { return a.key < b.key; });
+    open.erase(std::unique(open.begin(), open.end(), [](const Open &a, const Open &b) { return a.key == b.key; }), open.end());
+    auto node_of = [&](size_t s, uint32_t root) -> size_t {
+        const uint64_t key = (uint64_t)s << 32 | root;
+        return (size_t)(std::lower_bound(open.begin(), open.end(), key, [](const Open &a, uint64_t k) { return a.key < k; }) -
+                        open.begin());
+    };
+    for (const Open &o : open) {
+        out.components -= 1;
+        out.by_size[comp_size_bin(o.size)] -= 1;
+    }
+    // unions across every seam: the cell below with the cells above it
+    std::vector<size_t> up(open.size());
+    for (size_t i = 0; i < up.size(); ++i) up[i] = i;
+    auto find = [&](size_t x) {
+        while (up[x] != x) x = up[x] = up[up[x]];
+        return x;
+    };
+    for (size_t s = 0; s + 1 < nslab; ++s) {
+        const uint32_t *above = seam[s].last_root, *below = seam[s + 1].first_root;
+        for (size_t c = 0; c < cols; ++c) {
+            if (below[c] == kCompUnset) continue;
+            const size_t me = node_of(s + 1, below[c]);
+            const size_t c0 = (connectivity == 8 && c > 0) ? c - 1 : c, c1 = (connectivity == 8 && c + 1 < cols) ? c + 1 : c;
+            for (size_t k = c0; k <= c1; ++k) {
+                if (above[k] == kCompUnset) continue;
+                const size_t a = find(me), b = find(node_of(s, above[k]));
+                if (a != b) up[std::max(a, b)] = std::min(a, b);
+            }
+        }
+    }
+    std::vector<uint64_t> merged(open.size(), (uint64_t)0);
+    for (size_t i = 0; i < open.size(); ++i) merged[find(i)] += open[i].size;
+    for (size_t i = 0; i < open.size(); ++i) {
+        if (up[i] != i) continue;
+        out.components += 1;
+        out.by_size[comp_size_bin(merged[i])] += 1;
+        out.largest = std::max(out.largest, merged[i]);
+    }
+    return out;
+}
+
+} // namespace gsi

@@ -293,3 +293,16 @@ hipError_t gs_launch_pairs(const float *const *planes, const float *const *above
                            int64_t stride, int64_t pitch, int64_t rows, int32_t cols, const float *thresholds,
                            const int32_t *sense, int32_t nt, int32_t max_lag, int64_t max_groups, unsigned long long *out,
                            hipStream_t s);
+
+// Connected components (gs_components.hip; include/gs_hip.h: gs_fields_components).  `planes` planes of rows x cols cells,
+// `stride` floats apart, rows `pitch` floats apart, thresholded at `threshold` with `sense` as for gs_launch_quads and
+// labelled under `connectivity` (4 or 8); a component never leaves its plane.  parent and size hold one u32 per cell of all
+// planes, planes * rows * cols < 2^32, and need no initial contents.  The launches -- tile, border, flatten, tally, each its
+// own, none waiting for another workgroup -- add every plane's counters, in gs_components' layout (35 u64), to
+// out[y * 35 ...], which must hold zeros.  With `seams` (planes == 1): 4 * cols u32 -- the first row's roots, the sizes of
+// those roots, the last row's roots and their sizes; 0xffffffff and 0 for an unset cell.  max_groups: as for
+// gs_launch_histogram.
+constexpr int kCompTileRows = 16, kCompTileCols = 256;
+hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows, int32_t cols,
+                                float threshold, int32_t sense, int32_t connectivity, int64_t max_groups, uint32_t *parent,
+                                uint32_t *size, unsigned long long *out, uint32_t *seams, hipStream_t s);

@@ -1,8 +1,9 @@
 // gs_observe.cpp -- results formed on the device from planes and ensemble members, without downloading them
 // (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize), histograms (gs_fields_histogram,
-// gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology), two-point pair counts (gs_fields_correlation,
-// gs_members_correlation) and comparisons of two states
-// (gs_fields_compare, gs_members_compare).  All observe a field list with one launch per slab on its compute stream into that slab's scratch
+// gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology), two-point pair counts
+// (gs_fields_correlation, gs_members_correlation), connected components (gs_fields_components, gs_members_components) and
+// comparisons of two states (gs_fields_compare, gs_members_compare).  All observe a field list with launches per slab on its
+// compute stream -- one, or for components four per plane and threshold -- into that slab's scratch
 // buffer, fetch what the launches left and combine it here on the host, after the results of every slab -- and, in a
 // multi-process context, of every rank (exchange) -- have met; an ensemble's members are observed in one launch on slab 0.
 //   summaries   row records from gs_row_summary_k (gs_summary.hip); the field fold -- rows added in ascending global row
@@ -13,11 +14,15 @@
 //               first row is staged into the slab's scratch buffer, never read from ghost rows -- and added on the host.
 //   correlations zeroed u64 counters filled by gs_plane_pairs_k (gs_correlation.hip) -- a stencil L rows tall: the L rows above
 //               a slab's first row are staged the way morphology's one row is (stage_rows_above) -- and added on the host.
+//   components  labelled slab by slab (gs_components.hip) in label memory that lives for the call alone; the counters and the
+//               (root, size) of every slab's first and last row meet on the host, which joins what crosses the seams
+//               (gs_components_merge.h).
 //   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
 //               (row_records); ensembles fold on the device (gs_change_fold_k).
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
+#include "gs_components_merge.h"
 
 using namespace gsi;
 
@@ -350,6 +355,47 @@ int32_t add_counters(gs_ctx *ctx, const std::vector<uint64_t> &part, size_t word
         for (size_t w = 0; w < words; ++w) sum[w] += all[(size_t)q * words + w];
     return GS_OK;
 }
+
+// ---- connected components ------------------------------------------------------------------------------------------------
+static_assert(sizeof(gs_components) == 280 && offsetof(gs_components, by_size) == 24, "gs_components layout");
+constexpr size_t kCompWords = sizeof(gs_components) / sizeof(uint64_t); // the counters gs_comp_tally_k adds to
+
+int32_t check_connectivity(int32_t connectivity)
+{
+    if (connectivity != 4 && connectivity != 8) return fail(GS_ERR_INVALID, "a connectivity of %d (4 or 8)", connectivity);
+    return GS_OK;
+}
+
+// Label memory of one call: a u32 parent and a u32 size per cell, freed when the call returns, however it returns.
+struct LabelMemory {
+    struct Block {
+        int device;
+        uint32_t *parent, *size;
+    };
+    std::vector<Block> blocks;
+    ~LabelMemory()
+    {
+        for (const Block &b : blocks)
+            if (b.parent && hipSetDevice(b.device) == hipSuccess) (void)hipFree(b.parent);
+    }
+    int32_t add(int device, uint64_t cells)
+    {
+        Block b{device, nullptr, nullptr};
+        if (cells > 0) {
+            GS_HIP(hipSetDevice(device));
+            void *p = nullptr;
+            const hipError_t e = hipMalloc(&p, (size_t)cells * 8);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(GS_ERR_NOMEM, "label memory of %llu bytes: %s", (unsigned long long)cells * 8, hipGetErrorString(e));
+            }
+            b.parent = static_cast<uint32_t *>(p);
+            b.size = b.parent + cells;
+        }
+        blocks.push_back(b);
+        return GS_OK;
+    }
+};
 
 } // namespace
 
@@ -694,6 +740,135 @@ int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint
                            (int32_t)e->cols, thresholds, above, nt, max_lag, max_groups(ctx), dev, sl.compute));
     GS_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
     GS_HIP(hipStreamSynchronize(sl.compute));
+    return GS_OK;
+}
+
+int32_t gs_fields_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
+                             int32_t nt, int32_t connectivity, gs_components *out)
+{
+    if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    // the thresholds and the connectivity before any handle is looked at; a count that is no 1..4 is check_planes' first refusal
+    GS_TRY(check_thresholds(thresholds, n >= 1 && n <= 4 ? n : 0, nt));
+    GS_TRY(check_connectivity(connectivity));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    const size_t results = (size_t)n * (size_t)nt;
+    if (f0->rows == 0 || f0->cols == 0) { // the same shape on every rank: nobody exchanges anything
+        std::memset(out, 0, results * sizeof(gs_components));
+        return GS_OK;
+    }
+    // every slab of the global grid (the split of gs_field_create): every rank reaches the same verdict
+    const uint64_t S = (uint64_t)ctx->total_slabs(), R = f0->rows;
+    auto slab_rows = [&](uint64_t k) { return (k + 1) * R / S - k * R / S; };
+    for (uint64_t k = 0; k < S; ++k)
+        if (slab_rows(k) > 0 && slab_rows(k) >= ((uint64_t)1 << 32) / f0->cols + ((((uint64_t)1 << 32) % f0->cols) ? 1 : 0))
+            return fail(GS_ERR_UNSUPPORTED, "slab %llu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab",
+                        (unsigned long long)k, (unsigned long long)slab_rows(k), (unsigned long long)f0->cols);
+    const size_t nslab = ctx->slabs.size(), cols = (size_t)f0->cols;
+    for (size_t i = 0; i < nslab; ++i)
+        if ((uint64_t)f0->s[i].rows != slab_rows((uint64_t)ctx->global_index((int)i)))
+            return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
+    // per slab and (field, threshold): the counters, then the first row's roots and sizes and the last row's (u32 each)
+    const size_t rec_words = kCompWords + 2 * cols, slab_words = results * rec_words;
+    LabelMemory labels;
+    int32_t had = GS_OK;
+    for (size_t i = 0; i < nslab && had == GS_OK; ++i) had = labels.add(ctx->slabs[i].device, (uint64_t)f0->s[i].rows * (uint64_t)cols);
+    if (ctx->world > 1) { // the ranks agree on the verdict before anything else is exchanged: nobody waits for a rank that left
+        const uint64_t mine = had == GS_OK ? 0 : 1;
+        std::vector<uint64_t> verdicts((size_t)ctx->world);
+        GS_TRY(exchange(ctx, &mine, std::vector<size_t>((size_t)ctx->world, sizeof mine), "components", verdicts.data()));
+        for (int q = 0; q < ctx->world && had == GS_OK; ++q)
+            if (verdicts[(size_t)q]) had = fail(GS_ERR_NOMEM, "rank %d could not have its label memory", q);
+    }
+    if (had != GS_OK) return had;
+    for (size_t i = 0; i < nslab; ++i) GS_TRY(ensure_scratch(ctx, (int)i, slab_words * sizeof(uint64_t), "components"));
+    std::vector<uint64_t> local(nslab * slab_words, (uint64_t)0);
+    for (size_t i = 0; i < nslab; ++i) {
+        if (f0->s[i].rows == 0) continue;
+        SlabRt &sl = ctx->slabs[i];
+        GS_HIP(hipSetDevice(sl.device));
+        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+        GS_HIP(hipMemsetAsync(dev, 0, slab_words * sizeof(uint64_t), sl.compute));
+        for (size_t j = 0; j < results; ++j) {
+            unsigned long long *rec = dev + j * rec_words;
+            GS_HIP(gs_launch_components(fields[j / (size_t)nt]->s[i].row0, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols,
+                                        thresholds[j], above[j / (size_t)nt], connectivity, max_groups(ctx), labels.blocks[i].parent,
+                                        labels.blocks[i].size, rec, S > 1 ? reinterpret_cast<uint32_t *>(rec + kCompWords) : nullptr,
+                                        sl.compute));
+        }
+        GS_HIP(hipMemcpyAsync(local.data() + i * slab_words, dev, slab_words * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    std::vector<uint64_t> all;
+    if (ctx->world == 1) {
+        all.swap(local);
+    } else { // every rank's slabs to every rank, in rank order: global slab order
+        all.resize((size_t)S * slab_words);
+        GS_TRY(exchange(ctx, local.data(), std::vector<size_t>((size_t)ctx->world, nslab * slab_words * sizeof(uint64_t)),
+                        "components", all.data()));
+    }
+    std::vector<gs_components> part;
+    std::vector<CompSeamRows> seam;
+    for (size_t j = 0; j < results; ++j) {
+        part.clear();
+        seam.clear();
+        for (uint64_t k = 0; k < S; ++k) {
+            if (slab_rows(k) == 0) continue;
+            const uint64_t *rec = all.data() + (size_t)k * slab_words + j * rec_words;
+            gs_components c;
+            std::memcpy(&c, rec, sizeof c);
+            part.push_back(c);
+            const uint32_t *rows = reinterpret_cast<const uint32_t *>(rec + kCompWords);
+            seam.push_back(CompSeamRows{rows, rows + cols, rows + 2 * cols, rows + 3 * cols});
+        }
+        out[j] = merge_components(part.data(), seam.data(), part.size(), cols, connectivity);
+    }
+    return GS_OK;
+}
+
+int32_t gs_members_components(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
+                              const int32_t above[2], int32_t nt, int32_t connectivity, gs_components *out)
+{
+    if (!ctx || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_thresholds(thresholds, 2, nt)); // before the ensemble is looked at
+    GS_TRY(check_connectivity(connectivity));
+    GS_TRY(check_members(ctx, e, first, count));
+    const uint64_t cells = e->rows * e->cols;
+    const size_t passes = 2 * (size_t)nt, results = (size_t)count * passes;
+    std::memset(out, 0, results * sizeof(gs_components));
+    if (cells == 0 || count == 0) return GS_OK;
+    if (cells >= ((uint64_t)1 << 32))
+        return fail(GS_ERR_UNSUPPORTED, "a member holds %llu cells: labels are 32-bit, fewer than 2^32 cells", (unsigned long long)cells);
+    // batches of whole members in one block of label memory: as many as fit the budget, at least one
+    uint64_t batch = (uint64_t)GS_COMPONENTS_BATCH_BYTES / 8 / cells;
+    batch = batch < 1 ? 1 : (batch > count ? count : batch);
+    SlabRt &sl = ctx->slabs[0];
+    LabelMemory labels;
+    GS_TRY(labels.add(sl.device, batch * cells));
+    const size_t words = (size_t)batch * passes * kCompWords;
+    GS_TRY(ensure_scratch(ctx, 0, words * sizeof(uint64_t), "components"));
+    GS_HIP(hipSetDevice(sl.device));
+    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+    std::vector<uint64_t> host(words);
+    for (uint64_t b0 = 0; b0 < count; b0 += batch) {
+        const uint64_t nb = count - b0 < batch ? count - b0 : batch;
+        GS_HIP(hipMemsetAsync(dev, 0, words * sizeof(uint64_t), sl.compute));
+        // pass q = s * nt + k: species s of the batch's members at threshold k, each member a plane of its own -- `cells` floats
+        // from one to the next; it never sees its neighbours' rows
+        for (size_t q = 0; q < passes; ++q) {
+            const int s = (int)(q / (size_t)nt);
+            const float *plane = (s ? e->v[e->cur] : e->u[e->cur]) + (first + b0) * cells;
+            GS_HIP(gs_launch_components(plane, (int64_t)nb, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows, (int32_t)e->cols,
+                                        thresholds[q], above[s], connectivity, max_groups(ctx), labels.blocks[0].parent,
+                                        labels.blocks[0].size, dev + q * (size_t)nb * kCompWords, nullptr, sl.compute));
+        }
+        GS_HIP(hipMemcpyAsync(host.data(), dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, sl.compute));
+        GS_HIP(hipStreamSynchronize(sl.compute));
+        for (size_t q = 0; q < passes; ++q)
+            for (uint64_t i = 0; i < nb; ++i)
+                std::memcpy(&out[(size_t)(b0 + i) * passes + q], host.data() + (q * (size_t)nb + (size_t)i) * kCompWords,
+                            sizeof(gs_components));
+    }
     return GS_OK;
 }
 

@@ -507,6 +507,68 @@ def morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"
     return [[Morphology.from_quads(out[i, k], thr[i * nt + k], above[i], rows * cols) for k in range(nt)] for i in range(n)]
 
 
+@dataclass(frozen=True, eq=False)
+class Components:
+    """The connected components of one thresholded plane, labelled on the device (``gs_fields_components``; the rule is
+    include/gs_hip.h's): a cell is set by ``Morphology``'s rule, set cells are neighbours across a side or, under
+    ``connectivity`` 8, also across a corner, and components never wrap.  ``by_size[b]`` counts the components of
+    ``2^b <= size < 2^(b+1)`` cells (the last bin takes every larger one).  All exact integers."""
+
+    count: int
+    set_cells: int
+    largest: int
+    by_size: np.ndarray
+    threshold: float
+    above: bool
+    connectivity: int
+
+    @classmethod
+    def from_counters(cls, words, threshold: float, above: bool, connectivity: int) -> "Components":
+        """From the 35 u64 words of a ``gs_components``: components, set_cells, largest, by_size[32]."""
+        w = np.array(words, np.uint64).reshape(35)
+        return cls(int(w[0]), int(w[1]), int(w[2]), w[3:].copy(), float(threshold), bool(above), int(connectivity))
+
+    @property
+    def mean_size(self) -> float:
+        """Cells per component; NaN when there is none."""
+        return self.set_cells / self.count if self.count else float("nan")
+
+    @property
+    def largest_fraction(self) -> float:
+        """The largest component's share of the set cells; NaN when none is set."""
+        return self.largest / self.set_cells if self.set_cells else float("nan")
+
+    def holes(self, morphology: "Morphology") -> int:
+        """Holes of the pattern: components minus the Euler number of the same connectivity, from a ``Morphology`` of the
+        same plane, threshold and sense (another threshold or sense is refused)."""
+        if np.float32(morphology.threshold) != np.float32(self.threshold) or bool(morphology.above) != self.above:
+            raise ValueError("a Morphology of threshold %r (above=%r) for Components of threshold %r (above=%r)"
+                             % (morphology.threshold, morphology.above, self.threshold, self.above))
+        return self.count - (morphology.euler8 if self.connectivity == 8 else morphology.euler4)
+
+
+def components_fields(context: "HipContext", fields: Sequence["HipConcentration"], thresholds: Sequence[Sequence[float]],
+                      above: Sequence[bool], connectivity: int = 8) -> List[List[Components]]:
+    """``gs_fields_components``: the connected components of 1..4 planes of one shape over the whole global grid in one call
+    (collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number for
+    every plane) with the sense ``above[i]`` under ``connectivity`` 4 or 8.  Returns one list of ``Components`` per plane."""
+    n = len(fields)
+    if len(thresholds) != n or len(above) != n:
+        raise ValueError("one list of thresholds and one sense per field")
+    lists = [_thresholds(t) for t in thresholds]
+    nt = len(lists[0]) if lists else 0
+    if any(len(t) != nt for t in lists):
+        raise ValueError("the same number of thresholds for every field")
+    flat = [x for t in lists for x in t]
+    thr = (ctypes.c_float * max(len(flat), 1))(*flat)
+    sense = (ctypes.c_int32 * max(n, 1))(*[1 if a else 0 for a in above])
+    out = np.zeros((max(n, 1), max(nt, 1), 35), np.uint64)
+    capi.check(context._lib.gs_fields_components(context.handle, _handle_array(fields), n, thr, sense, nt, int(connectivity),
+                                                 out.ctypes.data_as(ctypes.POINTER(capi.GsComponents))))
+    return [[Components.from_counters(out[i, k], thr[i * nt + k], above[i], connectivity) for k in range(nt)]
+            for i in range(n)]
+
+
 CORRELATION_STEPS = ((0, 1), (1, 0), (1, 1), (1, -1))  # e_k = (dr, dc): along a row, down a column, diagonal, anti-diagonal
 
 
@@ -841,6 +903,12 @@ class HipConcentration:
         is set when it is above (``above``) or below the threshold."""
         return morphology_fields(context, [self], [thresholds], [above])[0]
 
+    def components(self, context: HipContext, thresholds, above: bool = True, connectivity: int = 8) -> List[Components]:
+        """The connected components of this plane thresholded at each of ``thresholds`` (1..4) over the whole global grid,
+        labelled on the device (``gs_fields_components``; blocking, collective in a multi-process context): a cell is set
+        when it is above (``above``) or below the threshold; ``connectivity`` 4 or 8."""
+        return components_fields(context, [self], [thresholds], [above], connectivity)[0]
+
     def correlation(self, context: HipContext, thresholds, max_lag: int = 32, above: bool = True) -> List[Correlation]:
         """The two-point pair counts of this plane thresholded at each of ``thresholds`` (1..4, one pass), lags 0 ..
         ``max_lag`` along four directions over the whole global grid, counted on the device (``gs_fields_correlation``;
@@ -1005,6 +1073,18 @@ class Species:
         u, v = morphology_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], [u_above, v_above])
         return u, v
 
+    def components(self, v_thresholds=(0.25,), u_thresholds=None,
+                   connectivity: int = 8) -> Tuple[List[Components], List[Components]]:
+        """(U, V) connected components of the current state in one call (``gs_fields_components``; blocking, collective in a
+        multi-process context): one ``Components`` per threshold (1..4 per species, the same number for both).  V is set
+        above its thresholds and U below, as ``morphology`` has it; without ``u_thresholds`` only V is looked at and the U
+        list is empty."""
+        in_u, in_v, _, _ = self.in_out()
+        if u_thresholds is None:
+            return [], components_fields(self._context, [in_v], [v_thresholds], [True], connectivity)[0]
+        u, v = components_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], [False, True], connectivity)
+        return u, v
+
     def correlation(self, v_thresholds=(0.25,), u_thresholds=None, max_lag: int = 32,
                     above: Tuple[bool, bool] = (False, True)) -> Tuple[List[Correlation], List[Correlation]]:
         """(U, V) two-point pair counts of the current state in one call (``gs_fields_correlation``; blocking, collective in
@@ -1155,6 +1235,25 @@ class Ensemble:
         out = np.zeros((max(count, 0), 2, max(nt, 1), 6), np.uint64)
         capi.check(self._ctx._lib.gs_members_morphology(self._ctx.handle, self.handle, first, count, thr, sense, nt,
                                                          out.ctypes.data_as(ctypes.POINTER(capi.GsMorphology))))
+        return out
+
+    def components(self, first: int = 0, count: Optional[int] = None, v_thresholds=(0.25,), u_thresholds=(0.5,),
+                   connectivity: int = 8) -> np.ndarray:
+        """Connected components of members ``[first, first + count)`` labelled on the device (``gs_members_components``,
+        blocking): a ``uint64`` array ``[count, 2, nt, 35]`` -- axis 1: U below ``u_thresholds``, V above ``v_thresholds``
+        (1..4 thresholds, the same number for both); last axis: components, set_cells, largest, by_size[32] -- what
+        ``Species.components`` gives for a lone Species in the member's state.  ``Components.from_counters`` turns one entry
+        into the object."""
+        first, count = self._range(first, count)
+        tu, tv = _thresholds(u_thresholds), _thresholds(v_thresholds)
+        if len(tu) != len(tv):
+            raise ValueError("the same number of thresholds for U and V")
+        nt = len(tu)
+        thr = (ctypes.c_float * max(2 * nt, 1))(*(tu + tv))
+        sense = (ctypes.c_int32 * 2)(0, 1)
+        out = np.zeros((max(count, 0), 2, max(nt, 1), 35), np.uint64)
+        capi.check(self._ctx._lib.gs_members_components(self._ctx.handle, self.handle, first, count, thr, sense, nt,
+                                                         int(connectivity), out.ctypes.data_as(ctypes.POINTER(capi.GsComponents))))
         return out
 
     def correlations(self, first: int = 0, count: Optional[int] = None, v_thresholds=(0.25,), u_thresholds=(0.5,),

@@ -40,6 +40,15 @@ from below, ``--corr-lags L`` (1..64, default 32) is the largest lag.  The file 
 V; axis 4: the unit steps (0, 1), (1, 0), (1, 1), (1, -1); last axis: the lag) and ``pairs_total[4, L + 1]``, the pairs that
 exist.  It changes no state either: the HDF5 file is byte for byte the same without it.
 
+``--components-every N`` records, at the same steps again, the connected components of every member's thresholded planes
+labelled on the device (``Ensemble.components``; the rule is include/gs_hip.h's) -- "how many spots, how large?" -- into
+``<output stem>.components.npz``.  ``--comp-threshold-v A[,B,...]`` (1 to 4 values, required with the flag) thresholds V from
+above, ``--comp-threshold-u A[,B,...]`` (as many values; default 0.5 for each) thresholds U from below,
+``--comp-connectivity 4|8`` (default 8) says whether cells that share only a corner are neighbours.  The file holds
+``steps[samples]``, ``thresholds_u[nt]``, ``thresholds_v[nt]``, ``connectivity``, and ``components``, ``set_cells``, ``largest``,
+each ``[samples, members, 2, nt]`` (axis 2: U, V), and ``by_size[samples, members, 2, nt, 32]``.  It changes no state either and
+works with ``--no-fields``.
+
 ``--steady-every N`` asks of every member "has it stopped changing?".  A snapshot of the ensemble is kept on the device
 (``Ensemble.snapshot``), taken at step 0; after every N steps and after the last one every member is compared with it on the
 device (``Ensemble.changes_since``: with d = now - snapshot per cell in f64, the sum of |d|, the sum of d * d and the largest
@@ -133,6 +142,14 @@ def parse(argv=None):
     ap.add_argument("--hist-range-v", type=value_pair, default=(0.0, 0.5), metavar="A:B", help="range of V's histogram")
     ap.add_argument("--morphology-every", type=int, default=0, metavar="N",
                     help="record every member's bit-quad counts every N steps and at the end (<output stem>.morphology.npz)")
+    ap.add_argument("--components-every", type=int, default=0, metavar="N",
+                    help="record every member's connected components every N steps and at the end (<output stem>.components.npz)")
+    ap.add_argument("--comp-threshold-v", type=threshold_list, default=None, metavar="A[,B,...]",
+                    help="1 to 4 thresholds above which a V cell is set (required with --components-every)")
+    ap.add_argument("--comp-threshold-u", type=threshold_list, default=None, metavar="A[,B,...]",
+                    help="as many thresholds below which a U cell is set (default 0.5 for each)")
+    ap.add_argument("--comp-connectivity", type=int, default=8, choices=(4, 8),
+                    help="cells are neighbours across a side (4) or also across a corner (8, the default)")
     ap.add_argument("--morph-threshold-v", type=threshold_list, default=None, metavar="A[,B,...]",
                     help="1 to 4 thresholds: V is set where it is above them")
     ap.add_argument("--morph-threshold-u", type=threshold_list, default=None, metavar="A[,B,...]",
@@ -169,6 +186,14 @@ def parse(argv=None):
         ap.error("--histogram-every must be at least 1 (0 = off)")
     if not 1 <= args.hist_bins <= 4096:
         ap.error("--hist-bins must be in 1..4096")
+    if args.components_every < 0:
+        ap.error("--components-every must be at least 1 (0 = off)")
+    if args.components_every and args.comp_threshold_v is None:
+        ap.error("--components-every needs --comp-threshold-v")
+    if args.comp_threshold_u is None and args.comp_threshold_v is not None:
+        args.comp_threshold_u = [0.5] * len(args.comp_threshold_v)
+    if args.comp_threshold_v is not None and len(args.comp_threshold_u) != len(args.comp_threshold_v):
+        ap.error("--comp-threshold-u needs as many values as --comp-threshold-v")
     if args.morphology_every < 0:
         ap.error("--morphology-every must be at least 1 (0 = off)")
     if args.morphology_every and args.morph_threshold_v is None:
@@ -250,6 +275,18 @@ def write_histograms(path: str, steps: List[int], samples: List[np.ndarray], u_r
              hi=np.asarray([u_range[1], v_range[1]], np.float32))
 
 
+def components_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".components.npz"
+
+
+def write_components(path: str, steps: List[int], samples: List[np.ndarray], thresholds_u, thresholds_v, connectivity: int) -> None:
+    c = np.stack(samples, axis=0)  # [samples, members, 2, nt, 35]: components, set_cells, largest, by_size[32]
+    np.savez(path, steps=np.asarray(steps, np.int64), thresholds_u=np.asarray(thresholds_u, np.float32),
+             thresholds_v=np.asarray(thresholds_v, np.float32), connectivity=np.int64(connectivity),
+             components=np.ascontiguousarray(c[..., 0]), set_cells=np.ascontiguousarray(c[..., 1]),
+             largest=np.ascontiguousarray(c[..., 2]), by_size=np.ascontiguousarray(c[..., 3:]))
+
+
 def write_morphologies(path: str, steps: List[int], samples: List[np.ndarray], thresholds_u, thresholds_v, cells: int) -> None:
     q = np.stack(samples, axis=0)  # [samples, members, 2, nt, 6]
     area, perimeter, euler4, euler8 = quad_measures(q)
@@ -303,11 +340,12 @@ def run(args) -> dict:
     steady_at = sample_steps(args.steps, args.steady_every) if args.steady_every else []
     morph_at = sample_steps(args.steps, args.morphology_every) if args.morphology_every else []
     corr_at = sample_steps(args.steps, args.correlation_every) if args.correlation_every else []
+    comp_at = sample_steps(args.steps, args.components_every) if args.components_every else []
     done, settled, taken = 0, None, None
-    if summary_at or hist_at or steady_at or morph_at or corr_at:
-        summaries, hists, changes, morphs, corrs = [], [], [], [], []
+    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at:
+        summaries, hists, changes, morphs, corrs, comps = [], [], [], [], [], []
         snap = ens.snapshot() if steady_at else None
-        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at)):
+        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at) | set(comp_at)):
             ens.prepare_steps(at - done)
             done = at
             if at in summary_at:
@@ -316,6 +354,9 @@ def run(args) -> dict:
                 hists.append(ens.histograms(bins=args.hist_bins, u_range=args.hist_range_u, v_range=args.hist_range_v))
             if at in morph_at:
                 morphs.append(ens.morphologies(v_thresholds=args.morph_threshold_v, u_thresholds=args.morph_threshold_u))
+            if at in comp_at:
+                comps.append(ens.components(v_thresholds=args.comp_threshold_v, u_thresholds=args.comp_threshold_u,
+                                            connectivity=args.comp_connectivity))
             if at in corr_at:
                 corrs.append(ens.correlations(v_thresholds=args.corr_threshold_v, u_thresholds=args.corr_threshold_u,
                                               max_lag=args.corr_lags))
@@ -338,6 +379,9 @@ def run(args) -> dict:
         if morph_at:
             write_morphologies(morphology_path(args.output), morph_at[:len(morphs)], morphs, args.morph_threshold_u,
                                args.morph_threshold_v, shape[0] * shape[1])
+        if comp_at:
+            write_components(components_path(args.output), comp_at[:len(comps)], comps, args.comp_threshold_u,
+                             args.comp_threshold_v, args.comp_connectivity)
         if corr_at:
             write_correlations(correlation_path(args.output), corr_at[:len(corrs)], corrs, args.corr_threshold_u,
                                args.corr_threshold_v, args.corr_lags, shape)

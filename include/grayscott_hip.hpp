@@ -129,6 +129,40 @@ struct Morphology {
     int64_t euler8() const { return ((int64_t)quads[1] - (int64_t)quads[3] - 2 * (int64_t)quads[5]) / 4; }
 };
 
+// The connected components of one thresholded plane, labelled on the device (gs_fields_components; the rule is gs_hip.h's): a
+// cell is set by Morphology's rule, set cells are neighbours across a side or, under connectivity 8, also across a corner;
+// components never wrap.  by_size[b] counts the components of 2^b <= size < 2^(b+1) cells (the last bin takes every larger
+// one).  All exact integers.
+struct Components {
+    uint64_t count = 0, set_cells = 0, largest = 0;
+    std::array<uint64_t, 32> by_size{};
+    float threshold = 0.0f;
+    bool above = true;
+    int32_t connectivity = 8;
+    static Components from_c(const gs_components &c, float threshold, bool above, int32_t connectivity)
+    {
+        Components o;
+        o.count = c.components;
+        o.set_cells = c.set_cells;
+        o.largest = c.largest;
+        for (std::size_t b = 0; b < 32; ++b) o.by_size[b] = c.by_size[b];
+        o.threshold = threshold;
+        o.above = above;
+        o.connectivity = connectivity;
+        return o;
+    }
+    double mean_size() const { return count ? (double)set_cells / (double)count : std::nan(""); }
+    double largest_fraction() const { return set_cells ? (double)largest / (double)set_cells : std::nan(""); }
+    // holes of the pattern: components minus the Euler number of the same connectivity, from a Morphology of the same plane,
+    // threshold and sense (another threshold or sense is refused)
+    int64_t holes(const Morphology &m) const
+    {
+        if (m.threshold != threshold || m.above != above)
+            throw HipError(GS_ERR_INVALID, "a Morphology of another threshold or sense");
+        return (int64_t)count - (connectivity == 8 ? m.euler8() : m.euler4());
+    }
+};
+
 // The two-point pair counts of one thresholded plane, counted on the device (gs_fields_correlation; the rule is gs_hip.h's):
 // pairs[k][d] is the number of cell pairs {p, p + d e_k}, d = 0 .. max_lag, inside the grid with both cells set, for the unit
 // steps e_0 = (0, 1), e_1 = (1, 0), e_2 = (1, 1), e_3 = (1, -1).  Pairs never wrap.  What follows is computed from the integers.
@@ -518,6 +552,29 @@ class Species {
         }
         return uv;
     }
+    // (U, V) connected components of the current state over the whole global grid, in one call (gs_fields_components; blocking,
+    // collective in a multi-process context): one Components per threshold (1..4 per species, the same number for both), U set
+    // where it is below its thresholds and V where it is above, as morphology() has it; connectivity 4 or 8
+    std::pair<std::vector<Components>, std::vector<Components>> components(const std::vector<float> &v_thresholds,
+                                                                           const std::vector<float> &u_thresholds,
+                                                                           int32_t connectivity = 8)
+    {
+        if (u_thresholds.size() != v_thresholds.size())
+            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t nt = v_thresholds.size();
+        std::vector<float> t(u_thresholds);
+        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const int32_t sense[2] = {0, 1};
+        std::vector<gs_components> out(2 * nt + 1);
+        check(gs_fields_components(context_->get(), planes, 2, t.data(), sense, (int32_t)nt, connectivity, out.data()));
+        std::pair<std::vector<Components>, std::vector<Components>> uv;
+        for (std::size_t k = 0; k < nt; ++k) {
+            uv.first.push_back(Components::from_c(out[k], t[k], false, connectivity));
+            uv.second.push_back(Components::from_c(out[nt + k], t[nt + k], true, connectivity));
+        }
+        return uv;
+    }
     // (U, V) two-point pair counts of the current state over the whole global grid, in one call (gs_fields_correlation;
     // blocking, collective in a multi-process context): one Correlation per threshold (1..4 per species, the same number for
     // both), lags 0 .. max_lag (1..64), U set where it is below its thresholds and V where it is above, unless the senses say
@@ -708,6 +765,27 @@ class Ensemble {
         for (std::size_t i = 0; i < 2 * count * nt; ++i) {
             const std::size_t species = (i / nt) & 1, k = i % nt;
             out.push_back(Morphology::from_c(c[i], t[species * nt + k], sense[species] != 0, shape_[0] * shape_[1]));
+        }
+        return out;
+    }
+    // connected components of members [first, first + count) from the newest state (gs_members_components, blocking): element
+    // (2 i + s) * nt + k = species s (0 = U, set below; 1 = V, set above) of member first + i at that species' threshold k,
+    // what Species::components gives for a lone Species in that state
+    std::vector<Components> components(std::size_t first, std::size_t count, const std::vector<float> &v_thresholds,
+                                       const std::vector<float> &u_thresholds, int32_t connectivity = 8) const
+    {
+        if (u_thresholds.size() != v_thresholds.size())
+            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
+        const std::size_t nt = v_thresholds.size();
+        std::vector<float> t(u_thresholds);
+        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const int32_t sense[2] = {0, 1};
+        std::vector<gs_components> c(2 * count * nt + 1);
+        check(gs_members_components(ctx_->get(), e_, first, count, t.data(), sense, (int32_t)nt, connectivity, c.data()));
+        std::vector<Components> out;
+        for (std::size_t i = 0; i < 2 * count * nt; ++i) {
+            const std::size_t species = (i / nt) & 1, k = i % nt;
+            out.push_back(Components::from_c(c[i], t[species * nt + k], species != 0, connectivity));
         }
         return out;
     }

@@ -684,6 +684,55 @@ int32_t gs_fields_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, c
 int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
                                const int32_t above[2], int32_t nt, int32_t max_lag, uint64_t *out);
 
+/* Connected components computed on the device: how many spots one plane of the WHOLE global grid has after thresholding, and
+ * how large they are -- what the bit quads cannot say, which give only components - holes -- without downloading the plane.
+ * For a plane x of R x C cells, a threshold t, a sense `above` and a connectivity of 4 or 8:
+ *   - a cell is SET by morphology's rule: iff x > t (above != 0) or x < t (above == 0), one f32 comparison.  A NaN cell is
+ *     never set, a cell equal to t is not set, infinities compare as they do, a sub-normal cell is the value it is (never
+ *     flushed);
+ *   - two set cells are neighbours when they share a side, under connectivity 8 also when they share a corner; a component is
+ *     a largest set of set cells joined by chains of neighbours.  Components NEVER wrap, under every boundary rule, as
+ *     morphology's quads and correlation's pairs never do: a spot across a periodic edge counts as two;
+ *   - the result counts the components, adds up and bins their sizes (cells) and names the largest.  An empty plane (R = 0 or
+ *     C = 0): GS_OK, all zeros.
+ * What the hosts derive: the mean size set_cells / components, the largest's share largest / set_cells, and with
+ * morphology's Euler number of the same threshold and sense the holes: components - euler8 (connectivity 8) or - euler4 (4).
+ * All fields are integers, and the same bits for any slab count, process count, step kernel or launch shape; a member's
+ * result is that of a lone Species in the same state.
+ *   gs_fields_components   out[i * nt + k] for fields[i] thresholded at thresholds[i * nt + k] with the sense above[i], i < n
+ *                          (1..4 fields of one shape), k < nt (1..4 thresholds per field): one wait for enqueued work (as
+ *                          gs_fields_summarize: a persistent window launch that gave up is run again first); then every
+ *                          (field, threshold) is labelled one after the other, slab by slab on the slab's compute stream.  A
+ *                          slab labels its own rows as if it were alone and hands the (root, size) of its first and last row
+ *                          to the host, which joins the components that meet across the seams; ghost rows are never read.  In
+ *                          a multi-process context the call is collective, like gs_run: every rank's seam rows and counters
+ *                          travel to every rank, and every rank does the same merge.
+ *   gs_members_components  out[(2 i + s) * nt + k] for species s (0 = U with thresholds[k] and above[0]; 1 = V with
+ *                          thresholds[nt + k] and above[1]) of member first + i, i < count, from the newest slot (a retired
+ *                          member: its held state).  A member is a plane of its own: it never joins its neighbours' rows.
+ * Label memory: a u32 parent and a u32 size per cell, 8 bytes per cell of the slab (2 GiB at 16384 x 16384) or of the batch of
+ * members being labelled, allocated for the call and freed before it returns; every (plane, threshold) is labelled in the
+ * same memory.  Members are labelled in batches of as many whole members as fit GS_COMPONENTS_BATCH_BYTES of label memory (at
+ * least one).
+ * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID, decided
+ * in this order before any handle is looked at: a null argument, nt outside 1..4, a NaN threshold, a connectivity that is
+ * neither 4 nor 8; then a null or foreign handle, mixed shapes, n outside 1..4, members outside the ensemble.
+ * GS_ERR_UNSUPPORTED: a slab (or a member) of 2^32 cells or more -- labels are 32-bit.  GS_ERR_NOMEM: the label memory cannot
+ * be had; nothing is changed.  In a multi-process context the ranks agree on that verdict before anything else travels: if
+ * one rank cannot have its memory, every rank returns GS_ERR_NOMEM.
+ * Not done: components wrapped under the periodic rule; centroids or bounding boxes; label planes for the caller. */
+#define GS_COMPONENTS_BATCH_BYTES (256u << 20)
+typedef struct gs_components {
+    uint64_t components;  /* connected components of set cells                                   */
+    uint64_t set_cells;   /* sum of their sizes: morphology's area A                             */
+    uint64_t largest;     /* cells of the largest one; 0 when there is none                      */
+    uint64_t by_size[32]; /* by_size[b]: components with 2^b <= size < 2^(b+1); b = 31 also takes */
+} gs_components;          /*             every larger one.  280 bytes                            */
+int32_t gs_fields_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
+                             int32_t nt, int32_t connectivity, gs_components *out);
+int32_t gs_members_components(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
+                              const int32_t above[2], int32_t nt, int32_t connectivity, gs_components *out);
+
 /* Two states compared on the device: how far one plane of the WHOLE global grid is from another of the same shape -- "has
  * this run stopped changing?" -- without downloading either, and the device copies that give a state to compare with
  * (snapshots) or to go back to (restores).
