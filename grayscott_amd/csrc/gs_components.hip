@@ -26,6 +26,7 @@
 // Built with hipcc's default float mode (f32 denormals kept), as gs_morphology.hip is: a sub-normal cell is compared as the
 // value it is.
 #include "gs_kernels.h"
+#include "gs_plane_scan.h"
 
 #define GS_UF_FN __device__ __forceinline__
 #define GS_UF_LOAD(p) __atomic_load_n((p), __ATOMIC_RELAXED)
@@ -39,11 +40,11 @@ static_assert(kCols == 256 && kRows % 4 == 0, "a lane holds four columns of a 25
 constexpr int kCounters = 35; // gs_components in u64 words: components, set_cells, largest, by_size[32]
 
 struct GsCompArgs {
-    const float *p;   // plane y at p + y * stride
+    const float *p;   // plane y at p + y * stride (no GsPlaneSet: it costs gs_comp_tile_k two waits, profiles/plane_scan_refactor.md)
     int64_t stride, pitch, rows, planes;
     int32_t cols;
-    float t;          // the threshold, negated where the sense is "below" ...
-    uint32_t flip;    // ... and the sign bit that is then flipped in every cell (gs_morphology.hip)
+    float t;          // the threshold and ...
+    uint32_t flip;    // ... the sign flip of gs_is_set
     int32_t eight;    // 8-connectivity
     uint32_t *parent, *size;
     unsigned long long *out; // [planes][kCounters], zeroed by the caller
@@ -63,10 +64,7 @@ __global__ __launch_bounds__(256) void gs_comp_tile_k(GsCompArgs a)
     const int c0 = (int)(tile % tiles_c) * kCols, c = c0 + 4 * lane;
     const float *plane = a.p + y * a.stride;
     const unsigned own = (c < cols ? 1u : 0u) | (c + 1 < cols ? 2u : 0u) | (c + 2 < cols ? 4u : 0u) | (c + 3 < cols ? 8u : 0u);
-    const int last = cols - 1;
-    const int cv = c < cols ? c : 0;
-    const int l0 = c < last ? c : last, l1 = c + 1 < last ? c + 1 : last, l2 = c + 2 < last ? c + 2 : last,
-              l3 = c + 3 < last ? c + 3 : last;
+    const GsLaneColumns at = gs_lane_columns(c, cols);
 
     // threshold: the lane's four cells of rows wave, wave + 4, ... of the tile; a set cell starts as its run's first cell
 #pragma unroll
@@ -74,19 +72,9 @@ __global__ __launch_bounds__(256) void gs_comp_tile_k(GsCompArgs a)
         const int lr = wave + 4 * i;
         const int64_t r = r0 + lr;
         const float *row = plane + (r < rows ? r : rows - 1) * a.pitch; // (an address that exists; masked below)
-        float4 x;
-        if (VEC) {
-            x = *reinterpret_cast<const float4 *>(row + cv);
-        } else {
-            x.x = row[l0];
-            x.y = row[l1];
-            x.z = row[l2];
-            x.w = row[l3];
-        }
-        unsigned m = (__uint_as_float(__float_as_uint(x.x) ^ a.flip) > a.t ? 1u : 0u) |
-                     (__uint_as_float(__float_as_uint(x.y) ^ a.flip) > a.t ? 2u : 0u) |
-                     (__uint_as_float(__float_as_uint(x.z) ^ a.flip) > a.t ? 4u : 0u) |
-                     (__uint_as_float(__float_as_uint(x.w) ^ a.flip) > a.t ? 8u : 0u);
+        const float4 x = gs_load_columns<VEC>(row, at);
+        unsigned m = (gs_is_set(x.x, a.flip, a.t) ? 1u : 0u) | (gs_is_set(x.y, a.flip, a.t) ? 2u : 0u) |
+                     (gs_is_set(x.z, a.flip, a.t) ? 4u : 0u) | (gs_is_set(x.w, a.flip, a.t) ? 8u : 0u);
         m &= r < rows ? own : 0u;
         // the run that reaches the lane's column 0 from the left: the lanes below this one that are full (all four set) up
         // to lane j, the nearest that is not; it begins in lane j if that one's column 3 is set, else in lane j + 1
@@ -275,13 +263,12 @@ hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stri
     a.rows = rows;
     a.planes = planes;
     a.cols = cols;
-    a.t = sense ? threshold : -threshold;
-    a.flip = sense ? 0u : 0x80000000u;
+    const bool vec = gs_reads_16_bytes(&plane, 1, planes, stride, pitch);
+    gs_set_rule(threshold, sense, a.t, a.flip);
     a.eight = connectivity == 8 ? 1 : 0;
     a.parent = parent;
     a.size = size;
     a.out = out;
-    const bool vec = pitch % 4 == 0 && (planes == 1 || stride % 4 == 0) && reinterpret_cast<uintptr_t>(plane) % 16 == 0;
 
     const int64_t tiles = (((int64_t)cols + kCols - 1) / kCols) * ((rows + kRows - 1) / kRows) * planes;
     if (tiles > INT32_MAX) return hipErrorInvalidValue;
@@ -297,11 +284,11 @@ hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stri
 
     hipLaunchKernelGGL(gs_comp_flatten_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, total);
 
-    // as many workgroups per plane as it has stretches of 256 entries, at most the caller's share of the chip per plane
-    int64_t groups = (int64_t)(((uint64_t)rows * (uint64_t)cols + 255) / 256);
-    const int64_t share = max_groups / planes > 1 ? max_groups / planes : 1;
-    if (groups > share) groups = share;
-    if (groups * planes > INT32_MAX) return hipErrorInvalidValue;
+    // As many workgroups per plane as it has stretches of 256 entries, at most the caller's share, and no floor: there are fewer
+    // than 2^32 entries.  gs_scan_groups divides its units by 4, and ceil(ceil(n / 64) / 4) = ceil(n / 256).
+    int64_t groups;
+    if (!gs_scan_groups((int64_t)(((uint64_t)rows * (uint64_t)cols + 63) / 64), 0, max_groups, planes, groups))
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(gs_comp_tally_k, dim3((unsigned)(groups * planes)), dim3(256), 0, s, a, groups);
 
     if (seams) hipLaunchKernelGGL(gs_comp_seam_k, dim3((unsigned)((cols + 255) / 256)), dim3(256), 0, s, a, seams);

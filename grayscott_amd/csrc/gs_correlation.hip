@@ -26,6 +26,7 @@
 // Built with hipcc's default float mode (f32 denormals kept), as gs_morphology.hip is: a sub-normal cell is compared as the
 // value it is.
 #include "gs_kernels.h"
+#include "gs_plane_scan.h"
 
 namespace {
 
@@ -47,8 +48,9 @@ struct GsPairArgs {
     const float *p[4];     // the first `np` planes; plane y of the launch is p[y % np] + (y / np) * stride
     const float *above[4]; // per p[]: the `nabove` rows above the plane's row 0, `pitch` floats apart, the farthest first, or
                            // null: unset (repeat == 1 only)
-    float t[4][4];         // per p[]: the thresholds, negated where the sense is "below" ...
-    uint32_t flip[4];      // ... and the sign bit that is then flipped in every cell: x < t <=> -x > -t, NaN never
+    float t[4][4];         // per p[]: the thresholds and ...
+    uint32_t flip[4];      // ... the sign flip of gs_is_set
+    // (no GsPlaneSet: it splits the one load of the next four and costs a wave a wait, profiles/plane_scan_refactor.md)
     int32_t np;
     int32_t nabove;
     int32_t max_lag;       // L, 1 .. 64
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(256) void gs_plane_pairs_k(GsPairArgs a)
                     uint64_t cur[kPairWords];
 #pragma unroll
                     for (int w = 0; w < kPairWords; ++w)
-                        cur[w] = __ballot(__uint_as_float(__float_as_uint(x[i][w]) ^ flip) > t[k]) & inside[w] & live;
+                        cur[w] = __ballot(gs_is_set(x[i][w], flip, t[k])) & inside[w] & live;
                     if (counted) {
                         n0[k] += popc64(cur[1]) + popc64(cur[2]) + popc64(cur[3]) + popc64(cur[4]);
 #pragma unroll
@@ -197,29 +199,20 @@ hipError_t gs_launch_pairs(const float *const *planes, const float *const *above
     for (int i = 0; i < np; ++i) {
         a.p[i] = planes[i];
         a.above[i] = (above && repeat == 1 && nabove > 0) ? above[i] : nullptr;
-        a.flip[i] = sense[i] ? 0u : 0x80000000u;
-        for (int k = 0; k < nt; ++k) a.t[i][k] = sense[i] ? thresholds[i * nt + k] : -thresholds[i * nt + k];
     }
+    gs_set_rules(a.t, a.flip, thresholds, sense, np, nt);
     a.np = np;
     a.nabove = nabove;
     a.max_lag = max_lag;
+    a.cols = cols;
     a.stride = stride;
     a.pitch = pitch;
     a.rows = rows;
-    a.cols = cols;
     a.out = out;
     const int64_t nplanes = (int64_t)np * repeat;
     const int64_t units = (((int64_t)cols + 255) / 256) * ((rows + kPairRows - 1) / kPairRows);
-    // as many workgroups per plane as there are units for (4 waves each), at most the caller's share of the chip per plane
-    // -- fewer workgroups, fewer flushes --, and never so few that a wave takes more than kPairUnitsPerWave units
-    int64_t groups = (units + 3) / 4;
-    const int64_t share = max_groups / nplanes > 1 ? max_groups / nplanes : 1;
-    if (groups > share) groups = share;
-    const int64_t least = (units + 4 * kPairUnitsPerWave - 1) / (4 * kPairUnitsPerWave);
-    if (groups < least) groups = least;
-    if (groups * nplanes > INT32_MAX) return hipErrorInvalidValue;
-    a.groups = groups;
-    const dim3 grid((unsigned)(groups * nplanes));
+    if (!gs_scan_groups(units, 4 * kPairUnitsPerWave, max_groups, nplanes, a.groups)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(a.groups * nplanes));
     switch (nt) {
     case 1: hipLaunchKernelGGL((gs_plane_pairs_k<1>), grid, dim3(256), 0, s, a); break;
     case 2: hipLaunchKernelGGL((gs_plane_pairs_k<2>), grid, dim3(256), 0, s, a); break;

@@ -17,6 +17,7 @@
 // Built with hipcc's default float mode (f32 denormals kept) and -ffp-contract=off, as gs_summary.hip is: the rule's
 // subtraction and multiplication are one f32 operation each, and a sub-normal cell or product is the value it is.
 #include "gs_kernels.h"
+#include "gs_plane_scan.h"
 
 namespace {
 
@@ -28,12 +29,9 @@ constexpr int kHistSegment = 1 << 20; // columns of a row that make one unit of 
 constexpr int64_t kHistUnitsPerGroup = 2048;
 
 struct GsHistArgs {
-    const float *p[4];   // the first `np` planes; plane y of the launch is p[y % np] + (y / np) * stride
-    float lo[4], hi[4], scale[4]; // per p[]
-    int32_t np;
-    int64_t stride;      // floats between one group of np planes and the next (ensembles: a member's cells)
-    int64_t pitch, rows; // of every plane
-    int32_t cols, bins;
+    float lo[4], hi[4], scale[4]; // per set.p[]
+    GsPlaneSet set;
+    int32_t bins;
     int64_t groups;      // workgroups per plane
     unsigned long long *out; // [planes][bins + 3], zeroed by the caller
 };
@@ -99,18 +97,18 @@ __global__ __launch_bounds__(256) void gs_plane_hist_k(GsHistArgs a)
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
     const int bins = a.bins, slots = bins + 4;
     const int64_t y = (int64_t)blockIdx.x / a.groups, g = (int64_t)blockIdx.x % a.groups;
-    const int which = (int)(y % a.np);
-    const float *plane = a.p[which] + (y / a.np) * a.stride;
+    int which;
+    const float *plane = gs_plane_at(a.set, y, which);
     const float lo = a.lo[which], hi = a.hi[which], scale = a.scale[which];
     for (int i = (int)threadIdx.x; i < slots; i += 256) h[i] = 0u;
     __syncthreads();
 
-    const int cols = a.cols;
-    const int64_t segs = ((int64_t)cols + kHistSegment - 1) / kHistSegment, units = a.rows * segs;
+    const int cols = a.set.cols;
+    const int64_t segs = ((int64_t)cols + kHistSegment - 1) / kHistSegment, units = a.set.rows * segs;
     Run run{bins + 3, 0};
     for (int64_t u = g * 4 + wave; u < units; u += a.groups * 4) {
         // the unit: columns [0, c_end) of `row`, which begins at the segment's first column (a multiple of 2^20)
-        const float *row = plane + (u / segs) * a.pitch + (u % segs) * kHistSegment;
+        const float *row = plane + (u / segs) * a.set.pitch + (u % segs) * kHistSegment;
         const int64_t left = (int64_t)cols - (u % segs) * kHistSegment;
         const int c_end = (int)(left < kHistSegment ? left : kHistSegment);
         for (int base = 0; base < c_end; base += 256 * kHistUnroll) { // (scalar: no lane leaves early)
@@ -158,33 +156,18 @@ hipError_t gs_launch_histogram(const float *const *planes, int np, int64_t repea
     if (np < 1 || np > 4 || repeat < 1 || bins < 1 || bins > 4096) return hipErrorInvalidValue;
     if (rows <= 0 || cols <= 0) return hipSuccess;
     GsHistArgs a{};
-    bool vec = pitch % 4 == 0 && (repeat == 1 || stride % 4 == 0);
+    const bool vec = gs_plane_set(a.set, planes, np, repeat, stride, pitch, rows, cols);
     for (int i = 0; i < np; ++i) {
-        a.p[i] = planes[i];
         a.lo[i] = lo[i];
         a.hi[i] = hi[i];
         a.scale[i] = scale[i];
-        vec = vec && reinterpret_cast<uintptr_t>(planes[i]) % 16 == 0;
     }
-    a.np = np;
-    a.stride = stride;
-    a.pitch = pitch;
-    a.rows = rows;
-    a.cols = cols;
     a.bins = bins;
     a.out = out;
     const int64_t nplanes = (int64_t)np * repeat;
     const int64_t segs = ((int64_t)cols + kHistSegment - 1) / kHistSegment, units = rows * segs;
-    // as many workgroups per plane as there are units for (4 waves each), at most the caller's share of the chip per plane
-    // -- fewer workgroups, fewer flushes --, and never so few that one takes more than kHistUnitsPerGroup units
-    int64_t groups = (units + 3) / 4;
-    const int64_t share = max_groups / nplanes > 1 ? max_groups / nplanes : 1;
-    if (groups > share) groups = share;
-    const int64_t least = (units + kHistUnitsPerGroup - 1) / kHistUnitsPerGroup;
-    if (groups < least) groups = least;
-    if (groups * nplanes > INT32_MAX) return hipErrorInvalidValue;
-    a.groups = groups;
-    const dim3 grid((unsigned)(groups * nplanes));
+    if (!gs_scan_groups(units, kHistUnitsPerGroup, max_groups, nplanes, a.groups)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(a.groups * nplanes));
     const size_t lds = (size_t)(bins + 4) * sizeof(unsigned);
     if (vec)
         hipLaunchKernelGGL(gs_plane_hist_k<true>, grid, dim3(256), lds, s, a);

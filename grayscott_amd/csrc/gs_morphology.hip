@@ -24,6 +24,7 @@
 // Built with hipcc's default float mode (f32 denormals kept), as gs_histogram.hip is: a sub-normal cell is compared as the
 // value it is.
 #include "gs_kernels.h"
+#include "gs_plane_scan.h"
 
 namespace {
 
@@ -36,14 +37,10 @@ constexpr int64_t kQuadUnitsPerWave = 1 << 16;
 constexpr int kQuadClasses = 5; // Q1, Q2, Q3, Q4, QD
 
 struct GsQuadArgs {
-    const float *p[4];     // the first `np` planes; plane y of the launch is p[y % np] + (y / np) * stride
-    const float *above[4]; // per p[]: columns [0, cols) of the row above the plane's row 0, or null: unset (repeat == 1 only)
-    float t[4][4];         // per p[]: the thresholds, negated where the sense is "below" ...
-    uint32_t flip[4];      // ... and the sign bit that is then flipped in every cell: x < t <=> -x > -t, NaN never
-    int32_t np;
-    int64_t stride;        // floats between one group of np planes and the next (ensembles: a member's cells)
-    int64_t pitch, rows;   // of every plane
-    int32_t cols;
+    float t[4][4];         // per set.p[]: the thresholds and ...
+    uint32_t flip[4];      // ... the sign flip of gs_is_set
+    const float *above[4]; // per set.p[]: columns [0, cols) of the row above the plane's row 0, or null: unset (repeat == 1 only)
+    GsPlaneSet set;        // (in this order a wave fetches its arguments in the fewest loads and waits: gs_plane_scan.h)
     int32_t bottom;        // 1: the quad row below the last row (its lower half is padding) is counted too
     int64_t groups;        // workgroups per plane
     unsigned long long *out; // [planes][nt][kQuadClasses], zeroed by the caller
@@ -59,15 +56,13 @@ __device__ __forceinline__ unsigned from_right(unsigned w, unsigned last)
 template <int NT>
 __device__ __forceinline__ unsigned bits_of(float4 x, const float *t, uint32_t flip)
 {
-    const float a = __uint_as_float(__float_as_uint(x.x) ^ flip), b = __uint_as_float(__float_as_uint(x.y) ^ flip);
-    const float c = __uint_as_float(__float_as_uint(x.z) ^ flip), d = __uint_as_float(__float_as_uint(x.w) ^ flip);
     unsigned w = 0u;
 #pragma unroll
     for (int k = 0; k < NT; ++k) {
-        w |= (a > t[k] ? 2u : 0u) << (8 * k);
-        w |= (b > t[k] ? 4u : 0u) << (8 * k);
-        w |= (c > t[k] ? 8u : 0u) << (8 * k);
-        w |= (d > t[k] ? 16u : 0u) << (8 * k);
+        w |= (gs_is_set(x.x, flip, t[k]) ? 2u : 0u) << (8 * k);
+        w |= (gs_is_set(x.y, flip, t[k]) ? 4u : 0u) << (8 * k);
+        w |= (gs_is_set(x.z, flip, t[k]) ? 8u : 0u) << (8 * k);
+        w |= (gs_is_set(x.w, flip, t[k]) ? 16u : 0u) << (8 * k);
     }
     return w;
 }
@@ -79,8 +74,8 @@ __global__ __launch_bounds__(256) void gs_plane_quads_k(GsQuadArgs a)
     __shared__ unsigned total[NT * kQuadClasses];
     const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
     const int64_t y = (int64_t)blockIdx.x / a.groups, g = (int64_t)blockIdx.x % a.groups;
-    const int which = (int)(y % a.np);
-    const float *plane = a.p[which] + (y / a.np) * a.stride;
+    int which;
+    const float *plane = gs_plane_at(a.set, y, which);
     const float *above = a.above[which];
     const uint32_t flip = a.flip[which];
     float t[NT];
@@ -89,8 +84,8 @@ __global__ __launch_bounds__(256) void gs_plane_quads_k(GsQuadArgs a)
     if (threadIdx.x < NT * kQuadClasses) total[threadIdx.x] = 0u;
     __syncthreads();
 
-    const int cols = a.cols;
-    const int64_t rows = a.rows, pitch = a.pitch;
+    const int cols = a.set.cols;
+    const int64_t rows = a.set.rows, pitch = a.set.pitch;
     const int64_t quad_rows = rows + (a.bottom ? 1 : 0); // quad row q: the plane's rows q - 1 and q
     const int64_t strips = ((int64_t)cols + 255) / 256, chunks = (quad_rows + kQuadRows - 1) / kQuadRows;
     const int64_t units = strips * chunks;
@@ -119,24 +114,12 @@ __global__ __launch_bounds__(256) void gs_plane_quads_k(GsQuadArgs a)
         own *= 0x01010101u;
         const unsigned extra_live = c0 + 256 < cols ? 0x02020202u : 0u;
         const int ce = c0 + 256 < cols ? c0 + 256 : cols - 1;
-        // columns the lane loads: the VEC form needs c + 3 < pitch only (what lies beyond cols is masked), the ragged one
-        // clamps every column
-        const int last = cols - 1;
-        const int cv = c < cols ? c : 0;
-        const int l0 = c < last ? c : last, l1 = c + 1 < last ? c + 1 : last, l2 = c + 2 < last ? c + 2 : last,
-                  l3 = c + 3 < last ? c + 3 : last;
+        const GsLaneColumns at = gs_lane_columns(c, cols);
         // the right corners of quad 0 count in the plane's first lane alone: there the column to the left is the padding
         const unsigned right = (c == 0) ? 0x1f1f1f1fu : 0x1e1e1e1eu;
 
         auto load = [&](const float *row, float4 &x, float &xe) {
-            if (VEC) {
-                x = *reinterpret_cast<const float4 *>(row + cv);
-            } else {
-                x.x = row[l0];
-                x.y = row[l1];
-                x.z = row[l2];
-                x.w = row[l3];
-            }
+            x = gs_load_columns<VEC>(row, at);
             xe = row[ce];
         };
         // the row's word: bits 1..4 the lane's columns, bit 5 the column to its right, of every threshold's byte
@@ -215,34 +198,16 @@ hipError_t gs_launch_quads(const float *const *planes, const float *const *above
     if (np < 1 || np > 4 || repeat < 1 || nt < 1 || nt > 4) return hipErrorInvalidValue;
     if (rows <= 0 || cols <= 0) return hipSuccess;
     GsQuadArgs a{};
-    bool vec = pitch % 4 == 0 && (repeat == 1 || stride % 4 == 0);
-    for (int i = 0; i < np; ++i) {
-        a.p[i] = planes[i];
-        a.above[i] = (above && repeat == 1) ? above[i] : nullptr;
-        a.flip[i] = sense[i] ? 0u : 0x80000000u;
-        for (int k = 0; k < nt; ++k) a.t[i][k] = sense[i] ? thresholds[i * nt + k] : -thresholds[i * nt + k];
-        vec = vec && reinterpret_cast<uintptr_t>(planes[i]) % 16 == 0 && reinterpret_cast<uintptr_t>(a.above[i]) % 16 == 0;
-    }
-    a.np = np;
-    a.stride = stride;
-    a.pitch = pitch;
-    a.rows = rows;
-    a.cols = cols;
+    for (int i = 0; i < np; ++i) a.above[i] = (above && repeat == 1) ? above[i] : nullptr;
+    const bool vec = gs_plane_set(a.set, planes, np, repeat, stride, pitch, rows, cols, a.above);
+    gs_set_rules(a.t, a.flip, thresholds, sense, np, nt);
     a.bottom = bottom ? 1 : 0;
     a.out = out;
     const int64_t nplanes = (int64_t)np * repeat;
     const int64_t quad_rows = rows + a.bottom;
     const int64_t units = (((int64_t)cols + 255) / 256) * ((quad_rows + kQuadRows - 1) / kQuadRows);
-    // as many workgroups per plane as there are units for (4 waves each), at most the caller's share of the chip per plane
-    // -- fewer workgroups, fewer flushes --, and never so few that a wave takes more than kQuadUnitsPerWave units
-    int64_t groups = (units + 3) / 4;
-    const int64_t share = max_groups / nplanes > 1 ? max_groups / nplanes : 1;
-    if (groups > share) groups = share;
-    const int64_t least = (units + 4 * kQuadUnitsPerWave - 1) / (4 * kQuadUnitsPerWave);
-    if (groups < least) groups = least;
-    if (groups * nplanes > INT32_MAX) return hipErrorInvalidValue;
-    a.groups = groups;
-    const dim3 grid((unsigned)(groups * nplanes));
+    if (!gs_scan_groups(units, 4 * kQuadUnitsPerWave, max_groups, nplanes, a.groups)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(a.groups * nplanes));
     switch (nt) {
     case 1: launch_quads<1>(vec, grid, s, a); break;
     case 2: launch_quads<2>(vec, grid, s, a); break;

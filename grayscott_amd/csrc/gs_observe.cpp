@@ -3,17 +3,21 @@
 // gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology), two-point pair counts
 // (gs_fields_correlation, gs_members_correlation), connected components (gs_fields_components, gs_members_components) and
 // comparisons of two states (gs_fields_compare, gs_members_compare).  All observe a field list with launches per slab on its
-// compute stream -- one, or for components four per plane and threshold -- into that slab's scratch
-// buffer, fetch what the launches left and combine it here on the host, after the results of every slab -- and, in a
-// multi-process context, of every rank (exchange) -- have met; an ensemble's members are observed in one launch on slab 0.
+// compute stream into that slab's scratch buffer, fetch what the launches left and combine it here on the host, after the
+// results of every slab -- and, in a multi-process context, of every rank (exchange) -- have met; an ensemble's members are
+// observed in one launch on slab 0.  Two shapes of result, each with one path:
+//   row records   one record per (plane, row), gathered in global row order and folded on the host (row_records): summaries,
+//                 comparisons.
+//   u64 counters  zeroed, added to by the launch (the plane scans of gs_plane_scan.h), fetched and added over slabs and ranks
+//                 (slab_counters; an ensemble's member range: member_counters) -- integers, so the order of the additions
+//                 does not show: histograms, morphology, correlations.  A stencil's rows above a slab's first row are staged
+//                 into the slab's scratch buffer behind the counters (stage_rows_above), never read from ghost rows.
+// Components keep a slab loop of their own (label memory, seam rows, the ranks' verdict) over the same small helpers.
 //   summaries   row records from gs_row_summary_k (gs_summary.hip); the field fold -- rows added in ascending global row
 //               order -- is done on the host.  Ensembles fold on the device (gs_summary_fold_k): two records per member travel.
-//   histograms  zeroed u64 counters filled by gs_plane_hist_k (gs_histogram.hip) and added on the host.  Integers: the
-//               order of the additions does not show.
-//   morphology  zeroed u64 counters filled by gs_plane_quads_k (gs_morphology.hip) -- a stencil: the row above a slab's
-//               first row is staged into the slab's scratch buffer, never read from ghost rows -- and added on the host.
-//   correlations zeroed u64 counters filled by gs_plane_pairs_k (gs_correlation.hip) -- a stencil L rows tall: the L rows above
-//               a slab's first row are staged the way morphology's one row is (stage_rows_above) -- and added on the host.
+//   histograms  counters of gs_plane_hist_k (gs_histogram.hip).
+//   morphology  counters of gs_plane_quads_k (gs_morphology.hip), a stencil with one row staged above a slab.
+//   correlations counters of gs_plane_pairs_k (gs_correlation.hip), a stencil with L rows staged above a slab.
 //   components  labelled slab by slab (gs_components.hip) in label memory that lives for the call alone; the counters and the
 //               (root, size) of every slab's first and last row meet on the host, which joins what crosses the seams
 //               (gs_components_merge.h).
@@ -85,6 +89,27 @@ int32_t check_members(gs_ctx *ctx, const gs_ensemble *e, uint64_t first, uint64_
     return sync_all(ctx);
 }
 
+// Slab i's planes of a field list.
+void slab_planes(gs_field *const *fields, int32_t n, size_t i, const float *out[4])
+{
+    for (int32_t p = 0; p < 4; ++p) out[p] = p < n ? fields[p]->s[i].row0 : nullptr;
+}
+
+// U and V of member `first` in the newest state: member first + i's are `cells` floats further on, each a plane of its own.
+void member_planes(const gs_ensemble *e, uint64_t first, const float *out[2])
+{
+    const uint64_t cells = e->rows * e->cols;
+    out[0] = e->u[e->cur] + first * cells;
+    out[1] = e->v[e->cur] + first * cells;
+}
+
+// Rows of slab k of the S slabs of all processes that R global rows are split into (the partition of gs_field_create).
+uint64_t global_slab_rows(const gs_ctx *ctx, uint64_t R, uint64_t k)
+{
+    const uint64_t S = (uint64_t)ctx->total_slabs();
+    return (k + 1) * R / S - k * R / S;
+}
+
 // Several processes: every rank's bytes to every rank's host.  `bytes[q]` is rank q's share (the same table on every
 // rank), `mine` this rank's own; `all` receives the shares in rank order.  Through slab 0's scratch buffer as send | recv,
 // on its compute stream, which is idle again on return.
@@ -106,8 +131,8 @@ int32_t exchange(gs_ctx *ctx, const void *mine, const std::vector<size_t> &bytes
 
 // Row records of n planes (or pairs of planes) of f0's shape over the WHOLE global grid, as [plane][global row]: one launch
 // per slab on its compute stream into the slab's scratch buffer (`launch(slab, rows, records, stream)` writes
-// records[p * rows + r]), and, in a multi-process context, every rank's records to every rank (rank q holds global rows
-// [q L R / S, (q + 1) L R / S) of S = world x L slabs, the partition of gs_field_create).  What folds row records in
+// records[p * rows + r]), and, in a multi-process context, every rank's records to every rank (rank q holds the rows of
+// global slabs [q L, (q + 1) L)).  What folds row records in
 // ascending global row order -- summaries, comparisons -- folds `all` plane by plane.
 template <typename Rec, typename Launch>
 int32_t row_records(gs_ctx *ctx, const gs_field *f0, int32_t n, const char *what, std::vector<Rec> &all, Launch launch)
@@ -136,12 +161,10 @@ int32_t row_records(gs_ctx *ctx, const gs_field *f0, int32_t n, const char *what
         all.swap(local);
         return GS_OK;
     }
-    const uint64_t S = (uint64_t)ctx->total_slabs(), L = (uint64_t)nslab, R = f0->rows;
-    std::vector<size_t> bytes((size_t)ctx->world);
-    for (int q = 0; q < ctx->world; ++q) {
-        const uint64_t r0 = (uint64_t)q * L * R / S, r1 = (uint64_t)(q + 1) * L * R / S;
-        bytes[(size_t)q] = (size_t)n * (size_t)(r1 - r0) * sizeof(Rec);
-    }
+    const uint64_t L = (uint64_t)nslab, R = f0->rows;
+    std::vector<size_t> bytes((size_t)ctx->world, (size_t)0);
+    for (uint64_t k = 0; k < (uint64_t)ctx->world * L; ++k)
+        bytes[(size_t)(k / L)] += (size_t)n * (size_t)global_slab_rows(ctx, R, k) * sizeof(Rec);
     if (bytes[(size_t)ctx->rank] != local.size() * sizeof(Rec))
         return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
     std::vector<Rec> blocks((size_t)n * (size_t)R);
@@ -263,10 +286,12 @@ int64_t max_groups(const gs_ctx *ctx)
 static_assert(sizeof(gs_morphology) == 48, "gs_morphology layout");
 constexpr size_t kQuadCounted = 5; // the classes gs_plane_quads_k counts: Q1, Q2, Q3, Q4, QD
 
-// nt thresholds for each of n planes, or the refusal of gs_hip.h.  No handle is looked at.
+// nt thresholds for each of n planes, or the refusal of gs_hip.h: what every thresholded observable checks first.  No handle
+// is looked at; a count of planes that is no 1..4 is left to check_planes, whose first refusal it is.
 int32_t check_thresholds(const float *thresholds, int32_t n, int32_t nt)
 {
     if (nt < 1 || nt > 4) return fail(GS_ERR_INVALID, "%d thresholds (1..4)", nt);
+    if (n < 1 || n > 4) n = 0;
     for (int32_t i = 0; i < n * nt; ++i)
         if (std::isnan(thresholds[i])) return fail(GS_ERR_INVALID, "threshold %d of plane %d is NaN", i % nt, i / nt);
     return GS_OK;
@@ -342,17 +367,69 @@ int32_t stage_rows_above(gs_ctx *ctx, gs_field *const *fields, int32_t n, size_t
 
 // `words` u64 counters per slab, [slab][words], added over the slabs and, in a multi-process context, over the ranks
 // (every rank's sums to every rank, added in the same way everywhere).  Integers: the order does not show.
-int32_t add_counters(gs_ctx *ctx, const std::vector<uint64_t> &part, size_t words, const char *what, std::vector<uint64_t> &sum)
+int32_t add_counters(gs_ctx *ctx, const std::vector<uint64_t> &part, size_t words, const char *what, uint64_t *sum)
 {
-    sum.assign(words, (uint64_t)0);
+    std::fill(sum, sum + words, (uint64_t)0);
     for (size_t i = 0; i < ctx->slabs.size(); ++i)
         for (size_t w = 0; w < words; ++w) sum[w] += part[i * words + w];
     if (ctx->world == 1) return GS_OK;
     std::vector<uint64_t> all((size_t)ctx->world * words);
-    GS_TRY(exchange(ctx, sum.data(), std::vector<size_t>((size_t)ctx->world, words * sizeof(uint64_t)), what, all.data()));
-    std::fill(sum.begin(), sum.end(), (uint64_t)0);
+    GS_TRY(exchange(ctx, sum, std::vector<size_t>((size_t)ctx->world, words * sizeof(uint64_t)), what, all.data()));
+    std::fill(sum, sum + words, (uint64_t)0);
     for (int q = 0; q < ctx->world; ++q)
         for (size_t w = 0; w < words; ++w) sum[w] += all[(size_t)q * words + w];
+    return GS_OK;
+}
+
+// `words` u64 counters of the planes of a field list, added over the slabs and ranks into `out`: per slab its scratch buffer
+// is made large enough -- with `depth` > 0 (a stencil) by stage_rows_above, which also leaves the `depth` rows above the
+// slab's first row behind the counters --, the counters are zeroed, `launch(i, counters, staged, stream)` adds to them
+// (`staged`: [plane][depth rows][pitch], null where nothing is above the slab or depth is 0) and they are fetched.
+template <typename Launch>
+int32_t slab_counters(gs_ctx *ctx, gs_field *const *fields, int32_t n, size_t words, size_t depth, const char *what,
+                      uint64_t *out, Launch launch)
+{
+    const size_t nslab = ctx->slabs.size(), bytes = words * sizeof(uint64_t);
+    const size_t counters = (bytes + 255) / 256 * 256; // (the staged rows start on a 256-byte boundary)
+    if (depth) GS_TRY(stage_rows_above(ctx, fields, n, depth, counters, what));
+    std::vector<uint64_t> part(nslab * words);
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        if (!depth) GS_TRY(ensure_scratch(ctx, (int)i, bytes, what));
+        GS_HIP(hipSetDevice(sl.device));
+        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+        const float *staged = depth && fields[0]->s[i].g_row0 != 0
+                                  ? reinterpret_cast<const float *>(static_cast<unsigned char *>(sl.scratch) + counters)
+                                  : nullptr;
+        GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+        GS_HIP(launch(i, dev, staged, sl.compute));
+        GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    return add_counters(ctx, part, words, what, out);
+}
+
+// `words` u64 counters of members [first, ...) of an ensemble into `host`: one launch on slab 0 -- `launch(planes, counters,
+// stream)` with member_planes' planes -- into its scratch buffer, zeroed before and fetched after; zeros for members of no cells.
+template <typename Launch>
+int32_t member_counters(gs_ctx *ctx, const gs_ensemble *e, uint64_t first, size_t words, const char *what, uint64_t *host,
+                        Launch launch)
+{
+    const size_t bytes = words * sizeof(uint64_t);
+    if (e->rows * e->cols == 0) {
+        std::fill(host, host + words, (uint64_t)0);
+        return GS_OK;
+    }
+    GS_TRY(ensure_scratch(ctx, 0, bytes, what));
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+    const float *planes[2];
+    member_planes(e, first, planes);
+    GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
+    GS_HIP(launch(planes, dev, sl.compute));
+    GS_HIP(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
     return GS_OK;
 }
 
@@ -412,8 +489,8 @@ int32_t gs_fields_summarize(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_
     }
     std::vector<GsRowSummary> rec;
     GS_TRY(row_records<GsRowSummary>(ctx, f0, n, "summary", rec, [&](size_t i, int64_t rows, GsRowSummary *dev, hipStream_t s) {
-        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int32_t p = 0; p < n; ++p) planes[p] = fields[p]->s[i].row0;
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
         return gs_launch_row_summary(planes, n, f0->pitch, rows, (int32_t)f0->cols, dev, s);
     }));
     for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(rec.data() + (size_t)p * (size_t)f0->rows, (size_t)f0->rows);
@@ -424,14 +501,15 @@ int32_t gs_members_summarize(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64
 {
     if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
     GS_TRY(check_members(ctx, e, first, count));
-    const uint64_t cells = e->rows * e->cols, rows = count * e->rows;
+    const uint64_t rows = count * e->rows;
     const size_t rec_bytes = (size_t)(2 * rows) * sizeof(GsRowSummary), out_bytes = (size_t)(2 * count) * sizeof(GsRowSummary);
     GS_TRY(ensure_scratch(ctx, 0, rec_bytes + out_bytes, "summary"));
     SlabRt &sl = ctx->slabs[0];
     GS_HIP(hipSetDevice(sl.device));
     GsRowSummary *rec = static_cast<GsRowSummary *>(sl.scratch), *folded = rec + 2 * rows;
     // the members' rows one after the other: one plane of count x rows rows, pitch cols
-    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
+    const float *planes[2];
+    member_planes(e, first, planes);
     GS_HIP(gs_launch_row_summary(planes, 2, (int64_t)e->cols, (int64_t)rows, (int32_t)e->cols, rec, sl.compute));
     GS_HIP(gs_launch_summary_fold(rec, (int64_t)count, (int64_t)e->rows, folded, sl.compute));
     std::vector<GsRowSummary> host((size_t)(2 * count));
@@ -450,11 +528,9 @@ int32_t gs_fields_compare(gs_ctx *ctx, gs_field *const *a, gs_field *const *b, i
     if (f0->rows == 0 || f0->cols == 0) return GS_OK; // the same shape on every rank: nobody exchanges anything
     std::vector<GsRowChange> rec;
     GS_TRY(row_records<GsRowChange>(ctx, f0, n, "comparison", rec, [&](size_t i, int64_t rows, GsRowChange *dev, hipStream_t s) {
-        const float *pa[4] = {nullptr, nullptr, nullptr, nullptr}, *pb[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int32_t p = 0; p < n; ++p) {
-            pa[p] = a[p]->s[i].row0;
-            pb[p] = b[p]->s[i].row0;
-        }
+        const float *pa[4], *pb[4];
+        slab_planes(a, n, i, pa);
+        slab_planes(b, n, i, pb);
         return gs_launch_row_change(pa, pb, n, f0->pitch, rows, (int32_t)f0->cols, dev, s);
     }));
     for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(rec.data() + (size_t)p * (size_t)f0->rows, (size_t)f0->rows);
@@ -477,8 +553,9 @@ int32_t gs_members_compare(gs_ctx *ctx, gs_ensemble *e, gs_ensemble *ref, uint64
     GsRowChange *rec = static_cast<GsRowChange *>(sl.scratch);
     GsChangeTotal *folded = reinterpret_cast<GsChangeTotal *>(rec + 2 * rows);
     // the members' rows one after the other: one plane of count x rows rows, pitch cols
-    const float *pa[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
-    const float *pb[2] = {ref->u[ref->cur] + first * cells, ref->v[ref->cur] + first * cells};
+    const float *pa[2], *pb[2];
+    member_planes(e, first, pa);
+    member_planes(ref, first, pb);
     GS_HIP(gs_launch_row_change(pa, pb, 2, (int64_t)e->cols, (int64_t)rows, (int32_t)e->cols, rec, sl.compute));
     GS_HIP(gs_launch_change_fold(rec, (int64_t)count, (int64_t)e->rows, folded, sl.compute));
     // (GsChangeTotal is gs_change's layout)
@@ -537,34 +614,16 @@ int32_t gs_fields_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t n, con
     if (n >= 1 && n <= 4) GS_TRY(check_ranges(lo, hi, n, bins, scale));
     GS_TRY(check_planes(ctx, fields, n));
     const gs_field *f0 = fields[0];
-    const size_t words = (size_t)n * (size_t)(bins + 3), bytes = words * sizeof(uint64_t);
+    const size_t words = (size_t)n * (size_t)(bins + 3);
     std::fill(out, out + words, (uint64_t)0);
     if (f0->rows == 0 || f0->cols == 0) return GS_OK; // the same shape on every rank: nobody exchanges anything
-    const size_t nslab = ctx->slabs.size();
-    std::vector<uint64_t> part(nslab * words);
-    for (size_t i = 0; i < nslab; ++i) {
-        SlabRt &sl = ctx->slabs[i];
-        GS_TRY(ensure_scratch(ctx, (int)i, bytes, "histogram"));
-        GS_HIP(hipSetDevice(sl.device));
-        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int32_t p = 0; p < n; ++p) planes[p] = fields[p]->s[i].row0;
-        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
-        GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
-        GS_HIP(gs_launch_histogram(planes, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, lo, hi, scale, bins,
-                                   max_groups(ctx), dev, sl.compute));
-        GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
-    }
-    GS_TRY(sync_compute(ctx));
-    for (size_t i = 0; i < nslab; ++i)
-        for (size_t w = 0; w < words; ++w) out[w] += part[i * words + w];
-    if (ctx->world == 1) return GS_OK;
-    // Several processes: every rank's counters to every rank, added in the same way everywhere.
-    std::vector<uint64_t> all((size_t)ctx->world * words);
-    GS_TRY(exchange(ctx, out, std::vector<size_t>((size_t)ctx->world, bytes), "histogram", all.data()));
-    std::fill(out, out + words, (uint64_t)0);
-    for (int q = 0; q < ctx->world; ++q)
-        for (size_t w = 0; w < words; ++w) out[w] += all[(size_t)q * words + w];
-    return GS_OK;
+    return slab_counters(ctx, fields, n, words, 0, "histogram", out,
+                         [&](size_t i, unsigned long long *dev, const float *, hipStream_t s) {
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
+        return gs_launch_histogram(planes, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, lo, hi, scale, bins,
+                                   max_groups(ctx), dev, s);
+    });
 }
 
 int32_t gs_members_histogram(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float lo[2], const float hi[2],
@@ -575,65 +634,40 @@ int32_t gs_members_histogram(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64
     GS_TRY(check_ranges(lo, hi, 2, bins, scale)); // before the ensemble is looked at
     GS_TRY(check_members(ctx, e, first, count));
     const uint64_t cells = e->rows * e->cols;
-    const size_t words = (size_t)(2 * count) * (size_t)(bins + 3), bytes = words * sizeof(uint64_t);
-    if (cells == 0) {
-        std::fill(out, out + words, (uint64_t)0);
-        return GS_OK;
-    }
-    GS_TRY(ensure_scratch(ctx, 0, bytes, "histogram"));
-    SlabRt &sl = ctx->slabs[0];
-    GS_HIP(hipSetDevice(sl.device));
-    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+    const size_t words = (size_t)(2 * count) * (size_t)(bins + 3);
     // member first + i's U and V are planes 2 i and 2 i + 1 of the launch: `cells` floats from one member to the next
-    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
-    GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
-    GS_HIP(gs_launch_histogram(planes, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows, (int32_t)e->cols,
-                               lo, hi, scale, bins, max_groups(ctx), dev, sl.compute));
-    GS_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
-    GS_HIP(hipStreamSynchronize(sl.compute));
-    return GS_OK;
+    return member_counters(ctx, e, first, words, "histogram", out,
+                           [&](const float *const *planes, unsigned long long *dev, hipStream_t s) {
+        return gs_launch_histogram(planes, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows,
+                                   (int32_t)e->cols, lo, hi, scale, bins, max_groups(ctx), dev, s);
+    });
 }
 
 int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
                              int32_t nt, gs_morphology *out)
 {
     if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
-    // the thresholds before any handle is looked at; a count that is no 1..4 is check_planes' first refusal
-    GS_TRY(check_thresholds(thresholds, n >= 1 && n <= 4 ? n : 0, nt));
+    GS_TRY(check_thresholds(thresholds, n, nt));
     GS_TRY(check_planes(ctx, fields, n));
     const gs_field *f0 = fields[0];
-    const size_t words = (size_t)n * (size_t)nt * kQuadCounted, bytes = words * sizeof(uint64_t);
+    const size_t results = (size_t)n * (size_t)nt;
     if (f0->rows == 0 || f0->cols == 0) { // the same shape on every rank: nobody exchanges anything
-        std::memset(out, 0, (size_t)n * (size_t)nt * sizeof(gs_morphology));
+        std::memset(out, 0, results * sizeof(gs_morphology));
         return GS_OK;
     }
     // The quad rows are split into consecutive runs, one per slab: the slab of global rows [r0, r1) counts those whose lower
-    // row is r0 .. r1 - 1, the last slab also the one below row R - 1.  A slab with r0 > 0 needs row r0 - 1: it is STAGED into
-    // the slab's scratch buffer behind the counters -- ghost rows are never read, whatever ghost_depth says.
-    const size_t nslab = ctx->slabs.size(), pitch = (size_t)f0->pitch;
-    const size_t counters = (bytes + 255) / 256 * 256; // (the staged rows start on a 256-byte boundary)
-    GS_TRY(stage_rows_above(ctx, fields, n, 1, counters, "morphology"));
-    std::vector<uint64_t> part(nslab * words);
-    for (size_t i = 0; i < nslab; ++i) {
-        SlabRt &sl = ctx->slabs[i];
-        GS_HIP(hipSetDevice(sl.device));
-        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
-        float *staged = reinterpret_cast<float *>(static_cast<unsigned char *>(sl.scratch) + counters);
-        const bool first = f0->s[i].g_row0 == 0, last = f0->s[i].g_row0 + (uint64_t)f0->s[i].rows == f0->rows;
-        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr}, *row_above[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int32_t p = 0; p < n; ++p) {
-            planes[p] = fields[p]->s[i].row0;
-            if (!first) row_above[p] = staged + (size_t)p * pitch;
-        }
-        GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
-        GS_HIP(gs_launch_quads(planes, row_above, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, last ? 1 : 0,
-                               thresholds, above, nt, max_groups(ctx), dev, sl.compute));
-        GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
-    }
-    GS_TRY(sync_compute(ctx));
-    std::vector<uint64_t> sum;
-    GS_TRY(add_counters(ctx, part, words, "morphology", sum));
-    for (size_t j = 0; j < (size_t)n * (size_t)nt; ++j) out[j] = from_counted(sum.data() + j * kQuadCounted, f0->rows, f0->cols);
+    // row is r0 .. r1 - 1, the last slab also the one below row R - 1.  A slab with r0 > 0 needs row r0 - 1, which is staged.
+    std::vector<uint64_t> sum(results * kQuadCounted);
+    GS_TRY(slab_counters(ctx, fields, n, sum.size(), 1, "morphology", sum.data(),
+                         [&](size_t i, unsigned long long *dev, const float *staged, hipStream_t s) {
+        const bool last = f0->s[i].g_row0 + (uint64_t)f0->s[i].rows == f0->rows;
+        const float *planes[4], *row_above[4];
+        slab_planes(fields, n, i, planes);
+        for (int32_t p = 0; p < 4; ++p) row_above[p] = staged && p < n ? staged + (size_t)p * (size_t)f0->pitch : nullptr;
+        return gs_launch_quads(planes, row_above, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, last ? 1 : 0,
+                               thresholds, above, nt, max_groups(ctx), dev, s);
+    }));
+    for (size_t j = 0; j < results; ++j) out[j] = from_counted(sum.data() + j * kQuadCounted, f0->rows, f0->cols);
     return GS_OK;
 }
 
@@ -644,24 +678,19 @@ int32_t gs_members_morphology(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
     GS_TRY(check_thresholds(thresholds, 2, nt)); // before the ensemble is looked at
     GS_TRY(check_members(ctx, e, first, count));
     const uint64_t cells = e->rows * e->cols;
-    const size_t results = (size_t)(2 * count) * (size_t)nt, words = results * kQuadCounted, bytes = words * sizeof(uint64_t);
+    const size_t results = (size_t)(2 * count) * (size_t)nt;
     if (cells == 0) {
         std::memset(out, 0, results * sizeof(gs_morphology));
         return GS_OK;
     }
-    GS_TRY(ensure_scratch(ctx, 0, bytes, "morphology"));
-    SlabRt &sl = ctx->slabs[0];
-    GS_HIP(hipSetDevice(sl.device));
-    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
     // member first + i's U and V are planes 2 i and 2 i + 1 of the launch, `cells` floats from one member to the next; each
     // is a plane of its own: nothing above its first row, padding below its last -- it never sees its neighbours' rows
-    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
-    std::vector<uint64_t> host(words);
-    GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
-    GS_HIP(gs_launch_quads(planes, nullptr, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows, (int32_t)e->cols,
-                           1, thresholds, above, nt, max_groups(ctx), dev, sl.compute));
-    GS_HIP(hipMemcpyAsync(host.data(), dev, bytes, hipMemcpyDeviceToHost, sl.compute));
-    GS_HIP(hipStreamSynchronize(sl.compute));
+    std::vector<uint64_t> host(results * kQuadCounted);
+    GS_TRY(member_counters(ctx, e, first, host.size(), "morphology", host.data(),
+                           [&](const float *const *planes, unsigned long long *dev, hipStream_t s) {
+        return gs_launch_quads(planes, nullptr, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows,
+                               (int32_t)e->cols, 1, thresholds, above, nt, max_groups(ctx), dev, s);
+    }));
     for (size_t j = 0; j < results; ++j) out[j] = from_counted(host.data() + j * kQuadCounted, e->rows, e->cols);
     return GS_OK;
 }
@@ -670,49 +699,31 @@ int32_t gs_fields_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, c
                               int32_t nt, int32_t max_lag, uint64_t *out)
 {
     if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
-    // the thresholds and the lag before any handle is looked at; a count that is no 1..4 is check_planes' first refusal
-    GS_TRY(check_thresholds(thresholds, n >= 1 && n <= 4 ? n : 0, nt));
-    GS_TRY(check_max_lag(max_lag));
+    GS_TRY(check_thresholds(thresholds, n, nt));
+    GS_TRY(check_max_lag(max_lag)); // before any handle is looked at, too
     GS_TRY(check_planes(ctx, fields, n));
     const gs_field *f0 = fields[0];
     const size_t depth = (size_t)max_lag;
-    const size_t words = (size_t)n * (size_t)nt * 4 * (depth + 1), bytes = words * sizeof(uint64_t);
+    const size_t words = (size_t)n * (size_t)nt * 4 * (depth + 1);
     std::fill(out, out + words, (uint64_t)0);
     if (f0->rows == 0 || f0->cols == 0) return GS_OK; // the same shape on every rank: nobody exchanges anything
     // A pair belongs to its LOWER row: the slab of global rows [r0, r1) counts the pairs whose lower cell lies in it and needs
     // the min(L, r0) rows above r0.  With several slabs these are the L last rows of the slab above, so every slab -- other
-    // processes' too (the split of gs_field_create): every rank reaches the same verdict -- must hold L rows.
+    // processes' too: every rank reaches the same verdict -- must hold L rows.
     const uint64_t S = (uint64_t)ctx->total_slabs();
     for (uint64_t k = 0; S > 1 && k < S; ++k)
-        if ((k + 1) * f0->rows / S - k * f0->rows / S < (uint64_t)max_lag)
+        if (global_slab_rows(ctx, f0->rows, k) < (uint64_t)max_lag)
             return fail(GS_ERR_UNSUPPORTED, "slab %llu holds %llu rows, fewer than the largest lag %d (the rows above a slab "
                                             "come from the one slab above it)",
-                        (unsigned long long)k, (unsigned long long)((k + 1) * f0->rows / S - k * f0->rows / S), max_lag);
-    const size_t nslab = ctx->slabs.size(), pitch = (size_t)f0->pitch;
-    const size_t counters = (bytes + 255) / 256 * 256; // (the staged rows start on a 256-byte boundary)
-    GS_TRY(stage_rows_above(ctx, fields, n, depth, counters, "correlation"));
-    std::vector<uint64_t> part(nslab * words);
-    for (size_t i = 0; i < nslab; ++i) {
-        SlabRt &sl = ctx->slabs[i];
-        GS_HIP(hipSetDevice(sl.device));
-        unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
-        float *staged = reinterpret_cast<float *>(static_cast<unsigned char *>(sl.scratch) + counters);
-        const bool first = f0->s[i].g_row0 == 0;
-        const float *planes[4] = {nullptr, nullptr, nullptr, nullptr}, *rows_above[4] = {nullptr, nullptr, nullptr, nullptr};
-        for (int32_t p = 0; p < n; ++p) {
-            planes[p] = fields[p]->s[i].row0;
-            if (!first) rows_above[p] = staged + (size_t)p * depth * pitch;
-        }
-        GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
-        GS_HIP(gs_launch_pairs(planes, rows_above, first ? 0 : max_lag, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows,
-                               (int32_t)f0->cols, thresholds, above, nt, max_lag, max_groups(ctx), dev, sl.compute));
-        GS_HIP(hipMemcpyAsync(part.data() + i * words, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
-    }
-    GS_TRY(sync_compute(ctx));
-    std::vector<uint64_t> sum;
-    GS_TRY(add_counters(ctx, part, words, "correlation", sum));
-    std::copy(sum.begin(), sum.end(), out);
-    return GS_OK;
+                        (unsigned long long)k, (unsigned long long)global_slab_rows(ctx, f0->rows, k), max_lag);
+    return slab_counters(ctx, fields, n, words, depth, "correlation", out,
+                         [&](size_t i, unsigned long long *dev, const float *staged, hipStream_t s) {
+        const float *planes[4], *rows_above[4];
+        slab_planes(fields, n, i, planes);
+        for (int32_t p = 0; p < 4; ++p) rows_above[p] = staged && p < n ? staged + (size_t)p * depth * (size_t)f0->pitch : nullptr;
+        return gs_launch_pairs(planes, rows_above, staged ? max_lag : 0, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows,
+                               (int32_t)f0->cols, thresholds, above, nt, max_lag, max_groups(ctx), dev, s);
+    });
 }
 
 int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
@@ -723,33 +734,22 @@ int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint
     GS_TRY(check_max_lag(max_lag));
     GS_TRY(check_members(ctx, e, first, count));
     const uint64_t cells = e->rows * e->cols;
-    const size_t words = (size_t)(2 * count) * (size_t)nt * 4 * (size_t)(max_lag + 1), bytes = words * sizeof(uint64_t);
-    if (cells == 0) {
-        std::fill(out, out + words, (uint64_t)0);
-        return GS_OK;
-    }
-    GS_TRY(ensure_scratch(ctx, 0, bytes, "correlation"));
-    SlabRt &sl = ctx->slabs[0];
-    GS_HIP(hipSetDevice(sl.device));
-    unsigned long long *dev = static_cast<unsigned long long *>(sl.scratch);
+    const size_t words = (size_t)(2 * count) * (size_t)nt * 4 * (size_t)(max_lag + 1);
     // member first + i's U and V are planes 2 i and 2 i + 1 of the launch, `cells` floats from one member to the next; each
     // is a plane of its own: nothing above its first row -- it never sees its neighbours' rows
-    const float *planes[2] = {e->u[e->cur] + first * cells, e->v[e->cur] + first * cells};
-    GS_HIP(hipMemsetAsync(dev, 0, bytes, sl.compute));
-    GS_HIP(gs_launch_pairs(planes, nullptr, 0, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows,
-                           (int32_t)e->cols, thresholds, above, nt, max_lag, max_groups(ctx), dev, sl.compute));
-    GS_HIP(hipMemcpyAsync(out, dev, bytes, hipMemcpyDeviceToHost, sl.compute));
-    GS_HIP(hipStreamSynchronize(sl.compute));
-    return GS_OK;
+    return member_counters(ctx, e, first, words, "correlation", out,
+                           [&](const float *const *planes, unsigned long long *dev, hipStream_t s) {
+        return gs_launch_pairs(planes, nullptr, 0, 2, (int64_t)count, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows,
+                               (int32_t)e->cols, thresholds, above, nt, max_lag, max_groups(ctx), dev, s);
+    });
 }
 
 int32_t gs_fields_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
                              int32_t nt, int32_t connectivity, gs_components *out)
 {
     if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
-    // the thresholds and the connectivity before any handle is looked at; a count that is no 1..4 is check_planes' first refusal
-    GS_TRY(check_thresholds(thresholds, n >= 1 && n <= 4 ? n : 0, nt));
-    GS_TRY(check_connectivity(connectivity));
+    GS_TRY(check_thresholds(thresholds, n, nt));
+    GS_TRY(check_connectivity(connectivity)); // before any handle is looked at, too
     GS_TRY(check_planes(ctx, fields, n));
     const gs_field *f0 = fields[0];
     const size_t results = (size_t)n * (size_t)nt;
@@ -757,9 +757,9 @@ int32_t gs_fields_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
         std::memset(out, 0, results * sizeof(gs_components));
         return GS_OK;
     }
-    // every slab of the global grid (the split of gs_field_create): every rank reaches the same verdict
-    const uint64_t S = (uint64_t)ctx->total_slabs(), R = f0->rows;
-    auto slab_rows = [&](uint64_t k) { return (k + 1) * R / S - k * R / S; };
+    // every slab of the global grid: every rank reaches the same verdict
+    const uint64_t S = (uint64_t)ctx->total_slabs();
+    auto slab_rows = [&](uint64_t k) { return global_slab_rows(ctx, f0->rows, k); };
     for (uint64_t k = 0; k < S; ++k)
         if (slab_rows(k) > 0 && slab_rows(k) >= ((uint64_t)1 << 32) / f0->cols + ((((uint64_t)1 << 32) % f0->cols) ? 1 : 0))
             return fail(GS_ERR_UNSUPPORTED, "slab %llu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab",

@@ -485,11 +485,8 @@ def _thresholds(values) -> List[float]:
     return [float(values)] if np.isscalar(values) else [float(x) for x in values]
 
 
-def morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"], thresholds: Sequence[Sequence[float]],
-                      above: Sequence[bool]) -> List[List[Morphology]]:
-    """``gs_fields_morphology``: bit-quad counts of 1..4 planes of one shape over the whole global grid in one call
-    (collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number for
-    every plane; all counted in one pass) with the sense ``above[i]``.  Returns one list of ``Morphology`` per plane."""
+def _field_thresholds(fields, thresholds, above):
+    """``(n, nt, thresholds as c_float[n * nt], senses as c_int32[n])`` for the thresholded observables of a field list."""
     n = len(fields)
     if len(thresholds) != n or len(above) != n:
         raise ValueError("one list of thresholds and one sense per field")
@@ -498,8 +495,25 @@ def morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"
     if any(len(t) != nt for t in lists):
         raise ValueError("the same number of thresholds for every field")
     flat = [x for t in lists for x in t]
-    thr = (ctypes.c_float * max(len(flat), 1))(*flat)
-    sense = (ctypes.c_int32 * max(n, 1))(*[1 if a else 0 for a in above])
+    return (n, nt, (ctypes.c_float * max(len(flat), 1))(*flat),
+            (ctypes.c_int32 * max(n, 1))(*[1 if a else 0 for a in above]))
+
+
+def _member_thresholds(u_thresholds, v_thresholds, above):
+    """``(nt, U's then V's thresholds as c_float[2 * nt], (U's, V's) senses as c_int32[2])`` for an ensemble's observables."""
+    tu, tv = _thresholds(u_thresholds), _thresholds(v_thresholds)
+    if len(tu) != len(tv):
+        raise ValueError("the same number of thresholds for U and V")
+    return (len(tu), (ctypes.c_float * max(2 * len(tu), 1))(*(tu + tv)),
+            (ctypes.c_int32 * 2)(1 if above[0] else 0, 1 if above[1] else 0))
+
+
+def morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"], thresholds: Sequence[Sequence[float]],
+                      above: Sequence[bool]) -> List[List[Morphology]]:
+    """``gs_fields_morphology``: bit-quad counts of 1..4 planes of one shape over the whole global grid in one call
+    (collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number for
+    every plane; all counted in one pass) with the sense ``above[i]``.  Returns one list of ``Morphology`` per plane."""
+    n, nt, thr, sense = _field_thresholds(fields, thresholds, above)
     out = np.zeros((max(n, 1), max(nt, 1), 6), np.uint64)
     capi.check(context._lib.gs_fields_morphology(context.handle, _handle_array(fields), n, thr, sense, nt,
                                                  out.ctypes.data_as(ctypes.POINTER(capi.GsMorphology))))
@@ -552,16 +566,7 @@ def components_fields(context: "HipContext", fields: Sequence["HipConcentration"
     """``gs_fields_components``: the connected components of 1..4 planes of one shape over the whole global grid in one call
     (collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number for
     every plane) with the sense ``above[i]`` under ``connectivity`` 4 or 8.  Returns one list of ``Components`` per plane."""
-    n = len(fields)
-    if len(thresholds) != n or len(above) != n:
-        raise ValueError("one list of thresholds and one sense per field")
-    lists = [_thresholds(t) for t in thresholds]
-    nt = len(lists[0]) if lists else 0
-    if any(len(t) != nt for t in lists):
-        raise ValueError("the same number of thresholds for every field")
-    flat = [x for t in lists for x in t]
-    thr = (ctypes.c_float * max(len(flat), 1))(*flat)
-    sense = (ctypes.c_int32 * max(n, 1))(*[1 if a else 0 for a in above])
+    n, nt, thr, sense = _field_thresholds(fields, thresholds, above)
     out = np.zeros((max(n, 1), max(nt, 1), 35), np.uint64)
     capi.check(context._lib.gs_fields_components(context.handle, _handle_array(fields), n, thr, sense, nt, int(connectivity),
                                                  out.ctypes.data_as(ctypes.POINTER(capi.GsComponents))))
@@ -676,16 +681,7 @@ def correlation_fields(context: "HipContext", fields: Sequence["HipConcentration
     (collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number for
     every plane; all counted in one pass) with the sense ``above[i]``, lags 0 .. ``max_lag`` (1..64).  Returns one list of
     ``Correlation`` per plane."""
-    n = len(fields)
-    if len(thresholds) != n or len(above) != n:
-        raise ValueError("one list of thresholds and one sense per field")
-    lists = [_thresholds(t) for t in thresholds]
-    nt = len(lists[0]) if lists else 0
-    if any(len(t) != nt for t in lists):
-        raise ValueError("the same number of thresholds for every field")
-    flat = [x for t in lists for x in t]
-    thr = (ctypes.c_float * max(len(flat), 1))(*flat)
-    sense = (ctypes.c_int32 * max(n, 1))(*[1 if a else 0 for a in above])
+    n, nt, thr, sense = _field_thresholds(fields, thresholds, above)
     lags = max_lag + 1 if 1 <= max_lag <= 64 else 1
     out = np.zeros((max(n, 1), max(nt, 1), 4, lags), np.uint64)
     capi.check(context._lib.gs_fields_correlation(context.handle, _handle_array(fields), n, thr, sense, nt, max_lag,
@@ -1061,17 +1057,22 @@ class Species:
         u, v = histogram_fields(self._context, [in_u, in_v], bins, [u_range, v_range])
         return u, v
 
+    def _v_or_both(self, observe, u_thresholds, v_thresholds, above, *more):
+        """``observe`` (one of the ``*_fields`` functions) of the current state as (U's list, V's list), ``above`` = (U's
+        sense, V's sense): without ``u_thresholds`` only V is looked at and the U list is empty."""
+        in_u, in_v, _, _ = self.in_out()
+        if u_thresholds is None:
+            return [], observe(self._context, [in_v], [v_thresholds], [above[1]], *more)[0]
+        u, v = observe(self._context, [in_u, in_v], [u_thresholds, v_thresholds], list(above), *more)
+        return u, v
+
     def morphology(self, v_thresholds=(0.25,), u_thresholds=None, v_above: bool = True,
                    u_above: bool = False) -> Tuple[List[Morphology], List[Morphology]]:
         """(U, V) bit-quad counts of the current state in one call (``gs_fields_morphology``; blocking, collective in a
         multi-process context): one ``Morphology`` per threshold (1..4 per species, the same number for both).  V carries
         the pattern where it is high and U where it is low, hence the default senses; without ``u_thresholds`` only V is
         looked at and the U list is empty."""
-        in_u, in_v, _, _ = self.in_out()
-        if u_thresholds is None:
-            return [], morphology_fields(self._context, [in_v], [v_thresholds], [v_above])[0]
-        u, v = morphology_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], [u_above, v_above])
-        return u, v
+        return self._v_or_both(morphology_fields, u_thresholds, v_thresholds, (u_above, v_above))
 
     def components(self, v_thresholds=(0.25,), u_thresholds=None,
                    connectivity: int = 8) -> Tuple[List[Components], List[Components]]:
@@ -1079,11 +1080,7 @@ class Species:
         multi-process context): one ``Components`` per threshold (1..4 per species, the same number for both).  V is set
         above its thresholds and U below, as ``morphology`` has it; without ``u_thresholds`` only V is looked at and the U
         list is empty."""
-        in_u, in_v, _, _ = self.in_out()
-        if u_thresholds is None:
-            return [], components_fields(self._context, [in_v], [v_thresholds], [True], connectivity)[0]
-        u, v = components_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], [False, True], connectivity)
-        return u, v
+        return self._v_or_both(components_fields, u_thresholds, v_thresholds, (False, True), connectivity)
 
     def correlation(self, v_thresholds=(0.25,), u_thresholds=None, max_lag: int = 32,
                     above: Tuple[bool, bool] = (False, True)) -> Tuple[List[Correlation], List[Correlation]]:
@@ -1091,11 +1088,7 @@ class Species:
         a multi-process context): one ``Correlation`` per threshold (1..4 per species, the same number for both), lags 0 ..
         ``max_lag`` (1..64).  ``above`` = (U's sense, V's sense): V carries the pattern where it is high and U where it is
         low; without ``u_thresholds`` only V is looked at and the U list is empty."""
-        in_u, in_v, _, _ = self.in_out()
-        if u_thresholds is None:
-            return [], correlation_fields(self._context, [in_v], [v_thresholds], [above[1]], max_lag)[0]
-        u, v = correlation_fields(self._context, [in_u, in_v], [u_thresholds, v_thresholds], list(above), max_lag)
-        return u, v
+        return self._v_or_both(correlation_fields, u_thresholds, v_thresholds, above, max_lag)
 
     def snapshot(self) -> Snapshot:
         """The current state copied into planes of its own on the device (``gs_fields_copy``; blocking)."""
@@ -1226,12 +1219,7 @@ class Ensemble:
         ``Species.morphology`` gives for a lone Species in the member's state.  ``quad_measures`` turns it into areas,
         perimeters and Euler numbers, ``Morphology.from_quads`` one entry into the object."""
         first, count = self._range(first, count)
-        tu, tv = _thresholds(u_thresholds), _thresholds(v_thresholds)
-        if len(tu) != len(tv):
-            raise ValueError("the same number of thresholds for U and V")
-        nt = len(tu)
-        thr = (ctypes.c_float * max(2 * nt, 1))(*(tu + tv))
-        sense = (ctypes.c_int32 * 2)(1 if u_above else 0, 1 if v_above else 0)
+        nt, thr, sense = _member_thresholds(u_thresholds, v_thresholds, (u_above, v_above))
         out = np.zeros((max(count, 0), 2, max(nt, 1), 6), np.uint64)
         capi.check(self._ctx._lib.gs_members_morphology(self._ctx.handle, self.handle, first, count, thr, sense, nt,
                                                          out.ctypes.data_as(ctypes.POINTER(capi.GsMorphology))))
@@ -1245,12 +1233,7 @@ class Ensemble:
         ``Species.components`` gives for a lone Species in the member's state.  ``Components.from_counters`` turns one entry
         into the object."""
         first, count = self._range(first, count)
-        tu, tv = _thresholds(u_thresholds), _thresholds(v_thresholds)
-        if len(tu) != len(tv):
-            raise ValueError("the same number of thresholds for U and V")
-        nt = len(tu)
-        thr = (ctypes.c_float * max(2 * nt, 1))(*(tu + tv))
-        sense = (ctypes.c_int32 * 2)(0, 1)
+        nt, thr, sense = _member_thresholds(u_thresholds, v_thresholds, (False, True))
         out = np.zeros((max(count, 0), 2, max(nt, 1), 35), np.uint64)
         capi.check(self._ctx._lib.gs_members_components(self._ctx.handle, self.handle, first, count, thr, sense, nt,
                                                          int(connectivity), out.ctypes.data_as(ctypes.POINTER(capi.GsComponents))))
@@ -1264,12 +1247,7 @@ class Ensemble:
         steps of ``CORRELATION_STEPS``; last axis: the lag -- what ``Species.correlation`` gives for a lone Species in the
         member's state.  ``Correlation.from_pairs`` turns one ``[4, max_lag + 1]`` entry into the object."""
         first, count = self._range(first, count)
-        tu, tv = _thresholds(u_thresholds), _thresholds(v_thresholds)
-        if len(tu) != len(tv):
-            raise ValueError("the same number of thresholds for U and V")
-        nt = len(tu)
-        thr = (ctypes.c_float * max(2 * nt, 1))(*(tu + tv))
-        sense = (ctypes.c_int32 * 2)(1 if above[0] else 0, 1 if above[1] else 0)
+        nt, thr, sense = _member_thresholds(u_thresholds, v_thresholds, above)
         lags = max_lag + 1 if 1 <= max_lag <= 64 else 1
         out = np.zeros((max(count, 0), 2, max(nt, 1), 4, lags), np.uint64)
         capi.check(self._ctx._lib.gs_members_correlation(self._ctx.handle, self.handle, first, count, thr, sense, nt, max_lag,

@@ -123,6 +123,10 @@ def threshold_list(text: str) -> List[float]:
     return out
 
 
+# The thresholded observables, in the order their flags are checked: (name of --NAME-every, prefix of --PREFIX-threshold-v / -u).
+THRESHOLDED = (("components", "comp"), ("morphology", "morph"), ("correlation", "corr"))
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser(prog="sweep", description="Gray-Scott parameter sweep, one ensemble member per (feed, kill)")
     ap.add_argument("--feed", type=value_range, required=True, metavar="A:B:N", help="feed rates")
@@ -186,30 +190,18 @@ def parse(argv=None):
         ap.error("--histogram-every must be at least 1 (0 = off)")
     if not 1 <= args.hist_bins <= 4096:
         ap.error("--hist-bins must be in 1..4096")
-    if args.components_every < 0:
-        ap.error("--components-every must be at least 1 (0 = off)")
-    if args.components_every and args.comp_threshold_v is None:
-        ap.error("--components-every needs --comp-threshold-v")
-    if args.comp_threshold_u is None and args.comp_threshold_v is not None:
-        args.comp_threshold_u = [0.5] * len(args.comp_threshold_v)
-    if args.comp_threshold_v is not None and len(args.comp_threshold_u) != len(args.comp_threshold_v):
-        ap.error("--comp-threshold-u needs as many values as --comp-threshold-v")
-    if args.morphology_every < 0:
-        ap.error("--morphology-every must be at least 1 (0 = off)")
-    if args.morphology_every and args.morph_threshold_v is None:
-        ap.error("--morphology-every needs --morph-threshold-v")
-    if args.morph_threshold_u is None and args.morph_threshold_v is not None:
-        args.morph_threshold_u = [0.5] * len(args.morph_threshold_v)
-    if args.morph_threshold_v is not None and len(args.morph_threshold_u) != len(args.morph_threshold_v):
-        ap.error("--morph-threshold-u needs as many values as --morph-threshold-v")
-    if args.correlation_every < 0:
-        ap.error("--correlation-every must be at least 1 (0 = off)")
-    if args.correlation_every and args.corr_threshold_v is None:
-        ap.error("--correlation-every needs --corr-threshold-v")
-    if args.corr_threshold_u is None and args.corr_threshold_v is not None:
-        args.corr_threshold_u = [0.5] * len(args.corr_threshold_v)
-    if args.corr_threshold_v is not None and len(args.corr_threshold_u) != len(args.corr_threshold_v):
-        ap.error("--corr-threshold-u needs as many values as --corr-threshold-v")
+    for name, short in THRESHOLDED:
+        every, tv, tu = (getattr(args, f"{name}_every"), getattr(args, f"{short}_threshold_v"),
+                         getattr(args, f"{short}_threshold_u"))
+        if every < 0:
+            ap.error(f"--{name}-every must be at least 1 (0 = off)")
+        if every and tv is None:
+            ap.error(f"--{name}-every needs --{short}-threshold-v")
+        if tu is None and tv is not None:
+            tu = [0.5] * len(tv)
+            setattr(args, f"{short}_threshold_u", tu)
+        if tv is not None and len(tu) != len(tv):
+            ap.error(f"--{short}-threshold-u needs as many values as --{short}-threshold-v")
     if not 1 <= args.corr_lags <= 64:
         ap.error("--corr-lags must be in 1..64")
     return args

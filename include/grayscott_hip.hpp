@@ -36,6 +36,18 @@ inline void check(int32_t status)
     if (status != GS_OK) throw HipError(status, gs_last_error());
 }
 
+namespace detail {
+// U's thresholds, then V's -- the C ABI's order for (U, V) -- or the refusal when their numbers differ.
+inline std::vector<float> uv_thresholds(const std::vector<float> &u_thresholds, const std::vector<float> &v_thresholds)
+{
+    if (u_thresholds.size() != v_thresholds.size())
+        throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
+    std::vector<float> t(u_thresholds);
+    t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+    return t;
+}
+} // namespace detail
+
 // A plane's summary computed on the device (gs_summary): sum, sum of squares, min and max of its finite cells (fold order
 // of gs_hip.h: bit-reproducible), the count of its non-finite cells, and `size`, its number of cells.
 struct Summary {
@@ -535,12 +547,9 @@ class Species {
                                                                            const std::vector<float> &u_thresholds,
                                                                            bool v_above = true, bool u_above = false)
     {
-        if (u_thresholds.size() != v_thresholds.size())
-            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
         gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
         const std::size_t nt = v_thresholds.size();
-        std::vector<float> t(u_thresholds);
-        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
         const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
         std::vector<gs_morphology> out(2 * nt + 1);
         check(gs_fields_morphology(context_->get(), planes, 2, t.data(), sense, (int32_t)nt, out.data()));
@@ -559,12 +568,9 @@ class Species {
                                                                            const std::vector<float> &u_thresholds,
                                                                            int32_t connectivity = 8)
     {
-        if (u_thresholds.size() != v_thresholds.size())
-            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
         gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
         const std::size_t nt = v_thresholds.size();
-        std::vector<float> t(u_thresholds);
-        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
         const int32_t sense[2] = {0, 1};
         std::vector<gs_components> out(2 * nt + 1);
         check(gs_fields_components(context_->get(), planes, 2, t.data(), sense, (int32_t)nt, connectivity, out.data()));
@@ -584,12 +590,9 @@ class Species {
                                                                              int32_t max_lag = 32, bool v_above = true,
                                                                              bool u_above = false)
     {
-        if (u_thresholds.size() != v_thresholds.size())
-            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
         gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
         const std::size_t nt = v_thresholds.size(), lags = max_lag >= 1 && max_lag <= 64 ? (std::size_t)max_lag + 1 : 1;
-        std::vector<float> t(u_thresholds);
-        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
         const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
         std::vector<uint64_t> out(2 * nt * 4 * lags + 1);
         check(gs_fields_correlation(context_->get(), planes, 2, t.data(), sense, (int32_t)nt, max_lag, out.data()));
@@ -753,11 +756,8 @@ class Ensemble {
     std::vector<Morphology> morphologies(std::size_t first, std::size_t count, const std::vector<float> &v_thresholds,
                                          const std::vector<float> &u_thresholds, bool v_above = true, bool u_above = false) const
     {
-        if (u_thresholds.size() != v_thresholds.size())
-            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
         const std::size_t nt = v_thresholds.size();
-        std::vector<float> t(u_thresholds);
-        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
         const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
         std::vector<gs_morphology> c(2 * count * nt + 1);
         check(gs_members_morphology(ctx_->get(), e_, first, count, t.data(), sense, (int32_t)nt, c.data()));
@@ -774,11 +774,8 @@ class Ensemble {
     std::vector<Components> components(std::size_t first, std::size_t count, const std::vector<float> &v_thresholds,
                                        const std::vector<float> &u_thresholds, int32_t connectivity = 8) const
     {
-        if (u_thresholds.size() != v_thresholds.size())
-            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
         const std::size_t nt = v_thresholds.size();
-        std::vector<float> t(u_thresholds);
-        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
         const int32_t sense[2] = {0, 1};
         std::vector<gs_components> c(2 * count * nt + 1);
         check(gs_members_components(ctx_->get(), e_, first, count, t.data(), sense, (int32_t)nt, connectivity, c.data()));
@@ -796,11 +793,8 @@ class Ensemble {
                                           const std::vector<float> &u_thresholds, int32_t max_lag = 32, bool v_above = true,
                                           bool u_above = false) const
     {
-        if (u_thresholds.size() != v_thresholds.size())
-            throw HipError(GS_ERR_INVALID, "the same number of thresholds for U and V");
         const std::size_t nt = v_thresholds.size(), lags = max_lag >= 1 && max_lag <= 64 ? (std::size_t)max_lag + 1 : 1;
-        std::vector<float> t(u_thresholds);
-        t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
         const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
         std::vector<uint64_t> c(2 * count * nt * 4 * lags + 1);
         check(gs_members_correlation(ctx_->get(), e_, first, count, t.data(), sense, (int32_t)nt, max_lag, c.data()));
