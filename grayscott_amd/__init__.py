@@ -16,6 +16,7 @@ from .simulation import (  # noqa: F401
     Histogram,
     HipConcentration,
     HipContext,
+    ComponentList,
     Components,
     Morphology,
     Parameters,
@@ -28,4 +29,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "Components", "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]
+           "ComponentList", "Components", "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]

@@ -59,6 +59,9 @@ UNITS = [
     # connected components of thresholded planes (union-find over a u32 parent per cell; tile, border, flatten and tally
     # launches): the same float mode
     ("gs_components.hip", "gs_components_k.o", []),
+    # component lists: one record per component behind that labelling (count, scan, write, gather launches; integer atomics):
+    # the same float mode
+    ("gs_component_list.hip", "gs_component_list_k.o", []),
     # reduced result images (block averages in f64): the same float mode, a sub-normal pixel is kept
     ("gs_reduce.hip", "gs_reduce_k.o", []),
     # two planes compared (row records of |a - b| in f64, the ensembles' fold): the same float mode, sub-normal cells kept

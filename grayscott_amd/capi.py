@@ -53,6 +53,7 @@ EXPORTS = (
     "gs_fields_morphology", "gs_members_morphology",
     "gs_fields_correlation", "gs_members_correlation",
     "gs_fields_components", "gs_members_components",
+    "gs_field_component_list", "gs_members_component_list", "gs_component_list_view", "gs_component_list_destroy",
 )
 
 
@@ -160,6 +161,23 @@ class GsComponents(ctypes.Structure):
     ]
 
 
+class GsComponentRecord(ctypes.Structure):
+    """``gs_component_record`` (include/gs_hip.h): one connected component of a thresholded plane -- its cells, the sums of
+    their row and column indices, its first cell in row-major order and its bounding box (inclusive) -- 48 bytes."""
+
+    _fields_ = [
+        ("size", ctypes.c_uint64),
+        ("sum_row", ctypes.c_uint64),
+        ("sum_col", ctypes.c_uint64),
+        ("first_row", ctypes.c_uint32),
+        ("first_col", ctypes.c_uint32),
+        ("row_min", ctypes.c_uint32),
+        ("row_max", ctypes.c_uint32),
+        ("col_min", ctypes.c_uint32),
+        ("col_max", ctypes.c_uint32),
+    ]
+
+
 _lib = None
 
 
@@ -249,6 +267,10 @@ def load() -> ctypes.CDLL:
         "gs_members_morphology": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, P(GsMorphology)]),
         "gs_fields_components": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(GsComponents)]),
         "gs_members_components": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(GsComponents)]),
+        "gs_field_component_list": (i32, [vp, vp, f32, i32, i32, u64, P(vp)]),
+        "gs_members_component_list": (i32, [vp, vp, u64, u64, i32, f32, i32, i32, u64, P(vp)]),
+        "gs_component_list_view": (i32, [vp, P(u64), P(P(u64)), P(P(GsComponentRecord))]),
+        "gs_component_list_destroy": (i32, [vp]),
         "gs_fields_correlation": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(u64)]),
         "gs_members_correlation": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(u64)]),
     }

@@ -25,6 +25,9 @@
 //
 // Built with hipcc's default float mode (f32 denormals kept), as gs_morphology.hip is: a sub-normal cell is compared as the
 // value it is.
+//
+// The component lists (gs_component_list.hip) run the tile, border and flatten launches alone (gs_launch_component_labels) and
+// continue from parent[] and size[] on the same stream.
 #include "gs_kernels.h"
 #include "gs_plane_scan.h"
 
@@ -248,15 +251,15 @@ __global__ __launch_bounds__(256) void gs_comp_seam_k(GsCompArgs a, uint32_t *se
 
 } // namespace
 
-hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows, int32_t cols,
-                                float threshold, int32_t sense, int32_t connectivity, int64_t max_groups, uint32_t *parent,
-                                uint32_t *size, unsigned long long *out, uint32_t *seams, hipStream_t s)
+// The tile, border and flatten launches: on return (of the launches) parent[cell] is the root of the cell's component, its
+// first cell in row-major order (kUfUnset: the cell is not set), and size[root] the component's cells.
+static hipError_t launch_labels(GsCompArgs &a, const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows,
+                                int32_t cols, float threshold, int32_t sense, int32_t connectivity, uint32_t *parent,
+                                uint32_t *size, hipStream_t s)
 {
-    if (planes < 1 || (connectivity != 4 && connectivity != 8) || (seams && planes != 1)) return hipErrorInvalidValue;
-    if (rows <= 0 || cols <= 0) return hipSuccess;
     const uint64_t total = (uint64_t)planes * (uint64_t)rows * (uint64_t)cols;
     if (total >= (1ull << 32)) return hipErrorInvalidValue;
-    GsCompArgs a{};
+    a = GsCompArgs{};
     a.p = plane;
     a.stride = stride;
     a.pitch = pitch;
@@ -268,7 +271,6 @@ hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stri
     a.eight = connectivity == 8 ? 1 : 0;
     a.parent = parent;
     a.size = size;
-    a.out = out;
 
     const int64_t tiles = (((int64_t)cols + kCols - 1) / kCols) * ((rows + kRows - 1) / kRows) * planes;
     if (tiles > INT32_MAX) return hipErrorInvalidValue;
@@ -283,6 +285,30 @@ hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stri
         hipLaunchKernelGGL(gs_comp_border_k, dim3((unsigned)((border + 255) / 256)), dim3(256), 0, s, a, per_plane, border);
 
     hipLaunchKernelGGL(gs_comp_flatten_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, total);
+    return hipSuccess;
+}
+
+hipError_t gs_launch_component_labels(const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows, int32_t cols,
+                                      float threshold, int32_t sense, int32_t connectivity, uint32_t *parent, uint32_t *size,
+                                      hipStream_t s)
+{
+    if (planes < 1 || (connectivity != 4 && connectivity != 8)) return hipErrorInvalidValue;
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    GsCompArgs a;
+    const hipError_t e = launch_labels(a, plane, planes, stride, pitch, rows, cols, threshold, sense, connectivity, parent, size, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows, int32_t cols,
+                                float threshold, int32_t sense, int32_t connectivity, int64_t max_groups, uint32_t *parent,
+                                uint32_t *size, unsigned long long *out, uint32_t *seams, hipStream_t s)
+{
+    if (planes < 1 || (connectivity != 4 && connectivity != 8) || (seams && planes != 1)) return hipErrorInvalidValue;
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    GsCompArgs a;
+    const hipError_t e = launch_labels(a, plane, planes, stride, pitch, rows, cols, threshold, sense, connectivity, parent, size, s);
+    if (e != hipSuccess) return e;
+    a.out = out;
 
     // As many workgroups per plane as it has stretches of 256 entries, at most the caller's share, and no floor: there are fewer
     // than 2^32 entries.  gs_scan_groups divides its units by 4, and ceil(ceil(n / 64) / 4) = ceil(n / 256).

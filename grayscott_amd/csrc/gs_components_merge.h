@@ -9,6 +9,12 @@
 // several slabs, or touch a slab's first and last row (one node: the root names it); a one-row slab hands the same row in
 // twice.  set_cells is the plain sum; largest is the maximum of the slabs' maxima and the merged sizes, because a merged
 // component is never smaller than its parts.  Integers throughout: every rank that merges the same arrays gets the same bits.
+//
+// merge_component_lists is the same merge for gs_field_component_list's records: every slab hands in its records, rows
+// already global, and for its first and its last row the index of every cell's record (kCompUnset for an unset cell) -- a slab
+// of a chain lists every component that touches either row, whatever its size.  Records united across the seams become one:
+// sizes and sums added, the boxes united, the first cell the smallest in row-major order.  min_size is applied to what the
+// unions leave, and the result is in ascending order of the first cell.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -96,6 +102,66 @@ inline gs_components merge_components(const gs_components *part, const CompSeamR
         out.by_size[comp_size_bin(merged[i])] += 1;
         out.largest = std::max(out.largest, merged[i]);
     }
+    return out;
+}
+
+struct ListSeamRows { // of one slab, `cols` entries each: the index of the cell's record among the slab's records
+    const uint32_t *first_index, *last_index;
+};
+
+inline bool comp_first_cell_before(const gs_component_record &a, const gs_component_record &b)
+{
+    return a.first_row != b.first_row ? a.first_row < b.first_row : a.first_col < b.first_col;
+}
+
+// The slabs in ascending global row order; none is empty.  part[s]: slab s's records, n[s] of them.  connectivity: 4 or 8.
+inline std::vector<gs_component_record> merge_component_lists(const gs_component_record *const *part, const size_t *n,
+                                                              const ListSeamRows *seam, size_t nslab, size_t cols,
+                                                              int connectivity, uint64_t min_size)
+{
+    std::vector<size_t> base(nslab + 1, 0);
+    for (size_t s = 0; s < nslab; ++s) base[s + 1] = base[s] + n[s];
+    std::vector<gs_component_record> all;
+    all.reserve(base[nslab]);
+    for (size_t s = 0; s < nslab; ++s) all.insert(all.end(), part[s], part[s] + n[s]);
+    std::vector<size_t> up(all.size());
+    for (size_t i = 0; i < up.size(); ++i) up[i] = i;
+    auto find = [&](size_t x) {
+        while (up[x] != x) x = up[x] = up[up[x]];
+        return x;
+    };
+    // unions across every seam: the cell below with the cells above it
+    for (size_t s = 0; s + 1 < nslab; ++s) {
+        const uint32_t *above = seam[s].last_index, *below = seam[s + 1].first_index;
+        for (size_t c = 0; c < cols; ++c) {
+            if (below[c] == kCompUnset) continue;
+            const size_t c0 = (connectivity == 8 && c > 0) ? c - 1 : c, c1 = (connectivity == 8 && c + 1 < cols) ? c + 1 : c;
+            for (size_t k = c0; k <= c1; ++k) {
+                if (above[k] == kCompUnset) continue;
+                const size_t a = find(base[s + 1] + below[c]), b = find(base[s] + above[k]);
+                if (a != b) up[std::max(a, b)] = std::min(a, b);
+            }
+        }
+    }
+    for (size_t i = 0; i < all.size(); ++i) {
+        const size_t r = find(i);
+        if (r == i) continue;
+        gs_component_record &to = all[r];
+        const gs_component_record &x = all[i];
+        to.size += x.size;
+        to.sum_row += x.sum_row;
+        to.sum_col += x.sum_col;
+        if (comp_first_cell_before(x, to)) to.first_row = x.first_row, to.first_col = x.first_col;
+        to.row_min = std::min(to.row_min, x.row_min);
+        to.row_max = std::max(to.row_max, x.row_max);
+        to.col_min = std::min(to.col_min, x.col_min);
+        to.col_max = std::max(to.col_max, x.col_max);
+    }
+    std::vector<gs_component_record> out;
+    for (size_t i = 0; i < all.size(); ++i)
+        if (up[i] == i && all[i].size >= min_size) out.push_back(all[i]);
+    // (every slab's records come in first-cell order and the slabs in row order: only merged records can be out of place)
+    if (!std::is_sorted(out.begin(), out.end(), comp_first_cell_before)) std::sort(out.begin(), out.end(), comp_first_cell_before);
     return out;
 }
 

@@ -306,3 +306,30 @@ constexpr int kCompTileRows = 16, kCompTileCols = 256;
 hipError_t gs_launch_components(const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows, int32_t cols,
                                 float threshold, int32_t sense, int32_t connectivity, int64_t max_groups, uint32_t *parent,
                                 uint32_t *size, unsigned long long *out, uint32_t *seams, hipStream_t s);
+// The tile, border and flatten launches of gs_launch_components alone: parent[cell] = the root of the cell's component, its
+// first cell in row-major order (0xffffffff: not set), size[root] = its cells.  What the component lists start from.
+hipError_t gs_launch_component_labels(const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows, int32_t cols,
+                                      float threshold, int32_t sense, int32_t connectivity, uint32_t *parent, uint32_t *size,
+                                      hipStream_t s);
+
+// Component lists (gs_component_list.hip; include/gs_hip.h: gs_field_component_list), behind gs_launch_component_labels on the
+// same stream.  A record is gs_component_record's layout; first_row counts over all planes (plane * rows + row), the sums and
+// the box are the plane's own rows.  A component is listed if it has at least min_size cells or, with `open` (planes == 1: a
+// slab of a chain), touches the first or last row.
+struct GsComponentRecord {
+    uint64_t size, sum_row, sum_col;
+    uint32_t first_row, first_col, row_min, row_max, col_min, col_max;
+};
+struct GsListWork {
+    uint32_t *open;     // ceil(entries / 32) words, or null
+    uint32_t *counts;   // gs_list_groups(entries) words
+    uint32_t *selected; // one word: the number of records
+};
+uint64_t gs_list_groups(uint64_t entries);
+// count: leaves *selected.  fill (records: *selected of them, at least one): writes the records in ascending order of their
+// first cell, adds every listed cell to its record and, with `seams`, leaves 2 * cols u32: the record index of every cell of
+// the first row, then of the last (0xffffffff: not set).  size[] holds record indices afterwards.
+hipError_t gs_launch_list_count(const uint32_t *parent, uint32_t *size, int64_t planes, int64_t rows, int32_t cols, uint64_t min_size,
+                                const GsListWork &w, hipStream_t s);
+hipError_t gs_launch_list_fill(const uint32_t *parent, uint32_t *size, int64_t planes, int64_t rows, int32_t cols, uint64_t min_size,
+                               const GsListWork &w, GsComponentRecord *records, uint32_t *seams, hipStream_t s);

@@ -2,7 +2,8 @@
 // (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize), histograms (gs_fields_histogram,
 // gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology), two-point pair counts
 // (gs_fields_correlation, gs_members_correlation), connected components (gs_fields_components, gs_members_components) and
-// comparisons of two states (gs_fields_compare, gs_members_compare).  All observe a field list with launches per slab on its
+// component lists (gs_field_component_list, gs_members_component_list) and comparisons of two states (gs_fields_compare,
+// gs_members_compare).  All observe a field list with launches per slab on its
 // compute stream into that slab's scratch buffer, fetch what the launches left and combine it here on the host, after the
 // results of every slab -- and, in a multi-process context, of every rank (exchange) -- have met; an ensemble's members are
 // observed in one launch on slab 0.  Two shapes of result, each with one path:
@@ -21,6 +22,9 @@
 //   components  labelled slab by slab (gs_components.hip) in label memory that lives for the call alone; the counters and the
 //               (root, size) of every slab's first and last row meet on the host, which joins what crosses the seams
 //               (gs_components_merge.h).
+//   component lists  the same labelling, then one record per component formed behind it (gs_component_list.hip) in record
+//               memory that lives for the call alone; the records and the record indices of every slab's first and last row
+//               meet on the host, which joins what crosses the seams (gs_components_merge.h).  Single-process contexts only.
 //   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
 //               (row_records); ensembles fold on the device (gs_change_fold_k).
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
@@ -28,7 +32,16 @@
 #include "gs_internal.h"
 #include "gs_components_merge.h"
 
+#include <memory>
+
 using namespace gsi;
+
+// What gs_field_component_list and gs_members_component_list return: host memory, independent of the context.
+struct gs_component_list {
+    uint64_t planes = 0;
+    std::vector<uint64_t> offsets; // planes + 1
+    std::vector<gs_component_record> records;
+};
 
 namespace gsi {
 
@@ -443,11 +456,12 @@ int32_t check_connectivity(int32_t connectivity)
     return GS_OK;
 }
 
-// Label memory of one call: a u32 parent and a u32 size per cell, freed when the call returns, however it returns.
+// Label memory of one call: a u32 parent and a u32 size per cell -- and, where a component list asks for them, `marks` u32
+// words behind them --, freed when the call returns, however it returns.
 struct LabelMemory {
     struct Block {
         int device;
-        uint32_t *parent, *size;
+        uint32_t *parent, *size, *marks;
     };
     std::vector<Block> blocks;
     ~LabelMemory()
@@ -455,24 +469,99 @@ struct LabelMemory {
         for (const Block &b : blocks)
             if (b.parent && hipSetDevice(b.device) == hipSuccess) (void)hipFree(b.parent);
     }
-    int32_t add(int device, uint64_t cells)
+    int32_t add(int device, uint64_t cells, uint64_t marks = 0)
     {
-        Block b{device, nullptr, nullptr};
+        Block b{device, nullptr, nullptr, nullptr};
         if (cells > 0) {
             GS_HIP(hipSetDevice(device));
             void *p = nullptr;
-            const hipError_t e = hipMalloc(&p, (size_t)cells * 8);
+            const uint64_t bytes = cells * 8 + marks * 4;
+            const hipError_t e = hipMalloc(&p, (size_t)bytes);
             if (e != hipSuccess) {
                 (void)hipGetLastError();
-                return fail(GS_ERR_NOMEM, "label memory of %llu bytes: %s", (unsigned long long)cells * 8, hipGetErrorString(e));
+                return fail(GS_ERR_NOMEM, "label memory of %llu bytes: %s", (unsigned long long)bytes, hipGetErrorString(e));
             }
             b.parent = static_cast<uint32_t *>(p);
             b.size = b.parent + cells;
+            b.marks = marks ? b.size + cells : nullptr;
         }
         blocks.push_back(b);
         return GS_OK;
     }
 };
+
+
+// ---- component lists ---------------------------------------------------------------------------------------------------
+static_assert(sizeof(gs_component_record) == 48 && sizeof(GsComponentRecord) == 48 && offsetof(gs_component_record, first_row) == 24 &&
+                  offsetof(GsComponentRecord, first_row) == 24 && offsetof(gs_component_record, row_min) == 32 &&
+                  offsetof(GsComponentRecord, row_min) == 32 && offsetof(gs_component_record, col_max) == 44 &&
+                  offsetof(GsComponentRecord, col_max) == 44,
+              "gs_component_record layout");
+
+// What a component list checks before any handle is looked at, in the header's order.
+int32_t check_list_rule(float threshold, int32_t connectivity, uint64_t min_size)
+{
+    if (std::isnan(threshold)) return fail(GS_ERR_INVALID, "the threshold is NaN");
+    GS_TRY(check_connectivity(connectivity));
+    if (min_size == 0) return fail(GS_ERR_INVALID, "a min_size of 0 (at least 1)");
+    return GS_OK;
+}
+
+// rows * rows * cols or rows * cols * cols >= 2^64: a record's sum of row or column indices could wrap.
+bool list_sums_could_wrap(uint64_t rows, uint64_t cols)
+{
+    const unsigned __int128 cells = (unsigned __int128)rows * cols; // (< 2^128)
+    if (cells >> 64) return rows != 0 && cols != 0;
+    return ((cells * rows) >> 64) != 0 || ((cells * cols) >> 64) != 0;
+}
+
+int32_t refuse_world(const gs_ctx *ctx)
+{
+    if (ctx->world > 1)
+        return fail(GS_ERR_UNSUPPORTED, "component lists in a multi-process context (%d processes): the ranks' record lists are "
+                                        "not exchanged", ctx->world);
+    return GS_OK;
+}
+
+// Record memory of one call, freed when the call returns, however it returns.
+struct RecordMemory {
+    struct Block {
+        int device;
+        void *p;
+    };
+    std::vector<Block> blocks;
+    ~RecordMemory() { release(); }
+    void release()
+    {
+        for (const Block &b : blocks)
+            if (b.p && hipSetDevice(b.device) == hipSuccess) (void)hipFree(b.p);
+        blocks.clear();
+    }
+    int32_t add(int device, uint64_t records, GsComponentRecord **out)
+    {
+        GS_HIP(hipSetDevice(device));
+        void *p = nullptr;
+        const hipError_t e = hipMalloc(&p, (size_t)records * sizeof(GsComponentRecord));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(GS_ERR_NOMEM, "record memory of %llu bytes: %s", (unsigned long long)records * sizeof(GsComponentRecord),
+                        hipGetErrorString(e));
+        }
+        blocks.push_back(Block{device, p});
+        *out = static_cast<GsComponentRecord *>(p);
+        return GS_OK;
+    }
+};
+
+// A slab's (or batch's) scratch buffer as a list's work memory: the number of records, the counts of `entries` entries, then
+// room for the record indices of two rows of `cols` cells.
+size_t list_work_bytes(uint64_t entries, size_t cols) { return (4 + (size_t)gs_list_groups(entries) + 2 * cols) * sizeof(uint32_t); }
+GsListWork list_work(void *scratch, uint32_t *marks)
+{
+    uint32_t *w = static_cast<uint32_t *>(scratch);
+    return GsListWork{marks, w + 4, w};
+}
+uint32_t *list_seams(void *scratch, uint64_t entries) { return static_cast<uint32_t *>(scratch) + 4 + gs_list_groups(entries); }
 
 } // namespace
 
@@ -869,6 +958,181 @@ int32_t gs_members_components(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
                 std::memcpy(&out[(size_t)(b0 + i) * passes + q], host.data() + (q * (size_t)nb + (size_t)i) * kCompWords,
                             sizeof(gs_components));
     }
+    return GS_OK;
+}
+
+int32_t gs_field_component_list(gs_ctx *ctx, gs_field *f, float threshold, int32_t above, int32_t connectivity, uint64_t min_size,
+                                gs_component_list **out)
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_list_rule(threshold, connectivity, min_size)); // before any handle is looked at
+    if (!f || f->ctx != ctx) return fail(GS_ERR_INVALID, "field: null or of another context");
+    GS_TRY(refuse_world(ctx)); // every rank alone, before anything is allocated or sent
+    GS_TRY(sync_all(ctx));
+    std::unique_ptr<gs_component_list> list(new (std::nothrow) gs_component_list);
+    if (!list) return fail(GS_ERR_NOMEM, "a component list");
+    list->planes = 1;
+    list->offsets.assign(2, (uint64_t)0);
+    if (f->rows == 0 || f->cols == 0) {
+        *out = list.release();
+        return GS_OK;
+    }
+    if (list_sums_could_wrap(f->rows, f->cols))
+        return fail(GS_ERR_UNSUPPORTED, "a grid of %llu x %llu cells: a sum of row or column indices could pass 2^64",
+                    (unsigned long long)f->rows, (unsigned long long)f->cols);
+    const size_t nslab = ctx->slabs.size(), cols = (size_t)f->cols;
+    for (size_t i = 0; i < nslab; ++i)
+        if ((uint64_t)f->s[i].rows * (uint64_t)cols >= ((uint64_t)1 << 32))
+            return fail(GS_ERR_UNSUPPORTED, "slab %zu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab", i,
+                        (unsigned long long)f->s[i].rows, (unsigned long long)cols);
+    // In a chain a component that touches a slab's first or last row is listed whatever its size: min_size comes after the merge.
+    const bool chain = nslab > 1;
+    LabelMemory labels;
+    for (size_t i = 0; i < nslab; ++i) {
+        const uint64_t cells = (uint64_t)f->s[i].rows * (uint64_t)cols;
+        GS_TRY(labels.add(ctx->slabs[i].device, cells, chain ? (cells + 31) / 32 : 0));
+        GS_TRY(ensure_scratch(ctx, (int)i, list_work_bytes(cells, cols), "component list"));
+    }
+    std::vector<uint32_t> selected(nslab, 0u);
+    for (size_t i = 0; i < nslab; ++i) {
+        if (f->s[i].rows == 0) continue;
+        SlabRt &sl = ctx->slabs[i];
+        const LabelMemory::Block &lb = labels.blocks[i];
+        GS_HIP(hipSetDevice(sl.device));
+        GS_HIP(gs_launch_component_labels(f->s[i].row0, 1, 0, f->pitch, (int64_t)f->s[i].rows, (int32_t)cols, threshold, above,
+                                          connectivity, lb.parent, lb.size, sl.compute));
+        const GsListWork work = list_work(sl.scratch, lb.marks);
+        GS_HIP(gs_launch_list_count(lb.parent, lb.size, 1, (int64_t)f->s[i].rows, (int32_t)cols, min_size, work, sl.compute));
+        GS_HIP(hipMemcpyAsync(&selected[i], work.selected, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx)); // the one read-back: the record memory is sized exactly
+    RecordMemory memory;
+    std::vector<std::vector<gs_component_record>> part(nslab);
+    std::vector<std::vector<uint32_t>> seam(nslab);
+    for (size_t i = 0; i < nslab; ++i) {
+        if (f->s[i].rows == 0) continue;
+        if (chain) seam[i].assign(2 * cols, kCompUnset);
+        if (selected[i] == 0) continue; // (no set cell in its first or last row either)
+        SlabRt &sl = ctx->slabs[i];
+        const LabelMemory::Block &lb = labels.blocks[i];
+        const uint64_t cells = (uint64_t)f->s[i].rows * (uint64_t)cols;
+        GsComponentRecord *records = nullptr;
+        GS_TRY(memory.add(sl.device, selected[i], &records));
+        part[i].resize(selected[i]);
+        uint32_t *seams = chain ? list_seams(sl.scratch, cells) : nullptr;
+        GS_HIP(gs_launch_list_fill(lb.parent, lb.size, 1, (int64_t)f->s[i].rows, (int32_t)cols, min_size, list_work(sl.scratch, lb.marks),
+                                   records, seams, sl.compute));
+        GS_HIP(hipMemcpyAsync(part[i].data(), records, part[i].size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
+        if (chain) GS_HIP(hipMemcpyAsync(seam[i].data(), seams, 2 * cols * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    // local rows to rows of the global grid
+    for (size_t i = 0; i < nslab; ++i) {
+        const uint64_t g = f->s[i].g_row0;
+        for (gs_component_record &r : part[i]) {
+            r.first_row += (uint32_t)g;
+            r.row_min += (uint32_t)g;
+            r.row_max += (uint32_t)g;
+            r.sum_row += r.size * g;
+        }
+    }
+    if (!chain) {
+        list->records.swap(part[0]);
+    } else {
+        std::vector<const gs_component_record *> recs;
+        std::vector<size_t> counts;
+        std::vector<ListSeamRows> rows;
+        for (size_t i = 0; i < nslab; ++i) {
+            if (f->s[i].rows == 0) continue;
+            recs.push_back(part[i].data());
+            counts.push_back(part[i].size());
+            rows.push_back(ListSeamRows{seam[i].data(), seam[i].data() + cols});
+        }
+        list->records = merge_component_lists(recs.data(), counts.data(), rows.data(), recs.size(), cols, connectivity, min_size);
+    }
+    list->offsets[1] = list->records.size();
+    *out = list.release();
+    return GS_OK;
+}
+
+int32_t gs_members_component_list(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, int32_t species, float threshold,
+                                  int32_t above, int32_t connectivity, uint64_t min_size, gs_component_list **out)
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_list_rule(threshold, connectivity, min_size)); // before the ensemble is looked at
+    if (species < 0 || species > 1) return fail(GS_ERR_INVALID, "species %d (0 = U, 1 = V)", species);
+    if (e && e->ctx == ctx) GS_TRY(refuse_world(ctx)); // (before check_members waits for anything)
+    GS_TRY(check_members(ctx, e, first, count));
+    std::unique_ptr<gs_component_list> list(new (std::nothrow) gs_component_list);
+    if (!list) return fail(GS_ERR_NOMEM, "a component list");
+    list->planes = count;
+    list->offsets.assign((size_t)count + 1, (uint64_t)0);
+    const uint64_t cells = e->rows * e->cols;
+    if (cells == 0 || count == 0) {
+        *out = list.release();
+        return GS_OK;
+    }
+    if (cells >= ((uint64_t)1 << 32))
+        return fail(GS_ERR_UNSUPPORTED, "a member holds %llu cells: labels are 32-bit, fewer than 2^32 cells", (unsigned long long)cells);
+    if (list_sums_could_wrap(e->rows, e->cols))
+        return fail(GS_ERR_UNSUPPORTED, "members of %llu x %llu cells: a sum of row or column indices could pass 2^64",
+                    (unsigned long long)e->rows, (unsigned long long)e->cols);
+    // batches of whole members in one block of label memory, as gs_members_components takes them
+    uint64_t batch = (uint64_t)GS_COMPONENTS_BATCH_BYTES / 8 / cells;
+    batch = batch < 1 ? 1 : (batch > count ? count : batch);
+    SlabRt &sl = ctx->slabs[0];
+    LabelMemory labels;
+    GS_TRY(labels.add(sl.device, batch * cells));
+    GS_TRY(ensure_scratch(ctx, 0, list_work_bytes(batch * cells, 0), "component list"));
+    GS_HIP(hipSetDevice(sl.device));
+    const LabelMemory::Block &lb = labels.blocks[0];
+    const GsListWork work = list_work(sl.scratch, nullptr);
+    std::vector<gs_component_record> host;
+    for (uint64_t b0 = 0; b0 < count; b0 += batch) {
+        const uint64_t nb = count - b0 < batch ? count - b0 : batch;
+        // each member a plane of its own, `cells` floats from one to the next: it never sees its neighbours' rows
+        const float *plane = (species ? e->v[e->cur] : e->u[e->cur]) + (first + b0) * cells;
+        GS_HIP(gs_launch_component_labels(plane, (int64_t)nb, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows, (int32_t)e->cols,
+                                          threshold, above, connectivity, lb.parent, lb.size, sl.compute));
+        GS_HIP(gs_launch_list_count(lb.parent, lb.size, (int64_t)nb, (int64_t)e->rows, (int32_t)e->cols, min_size, work, sl.compute));
+        uint32_t selected = 0;
+        GS_HIP(hipMemcpyAsync(&selected, work.selected, sizeof selected, hipMemcpyDeviceToHost, sl.compute));
+        GS_HIP(hipStreamSynchronize(sl.compute));
+        if (selected == 0) continue;
+        RecordMemory memory; // (of this batch)
+        GsComponentRecord *records = nullptr;
+        GS_TRY(memory.add(sl.device, selected, &records));
+        host.resize(selected);
+        GS_HIP(gs_launch_list_fill(lb.parent, lb.size, (int64_t)nb, (int64_t)e->rows, (int32_t)e->cols, min_size, work, records, nullptr,
+                                   sl.compute));
+        GS_HIP(hipMemcpyAsync(host.data(), records, host.size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
+        GS_HIP(hipStreamSynchronize(sl.compute));
+        // the records come in first-cell order over the batch's planes, one after the other: a record's plane follows from its root
+        for (gs_component_record &r : host) {
+            const uint64_t plane_of = r.first_row / e->rows;
+            r.first_row = (uint32_t)(r.first_row % e->rows);
+            list->offsets[(size_t)(b0 + plane_of) + 1] += 1;
+        }
+        list->records.insert(list->records.end(), host.begin(), host.end());
+    }
+    for (size_t i = 0; i < (size_t)count; ++i) list->offsets[i + 1] += list->offsets[i];
+    *out = list.release();
+    return GS_OK;
+}
+
+int32_t gs_component_list_view(const gs_component_list *list, uint64_t *planes, const uint64_t **offsets,
+                               const gs_component_record **records)
+{
+    if (!list || !planes || !offsets || !records) return fail(GS_ERR_INVALID, "null argument");
+    *planes = list->planes;
+    *offsets = list->offsets.data();
+    *records = list->records.data();
+    return GS_OK;
+}
+
+int32_t gs_component_list_destroy(gs_component_list *list)
+{
+    delete list;
     return GS_OK;
 }
 

@@ -574,6 +574,90 @@ def components_fields(context: "HipContext", fields: Sequence["HipConcentration"
             for i in range(n)]
 
 
+COMPONENT_RECORD_DTYPE = np.dtype([("size", np.uint64), ("sum_row", np.uint64), ("sum_col", np.uint64),
+                                   ("first_row", np.uint32), ("first_col", np.uint32), ("row_min", np.uint32),
+                                   ("row_max", np.uint32), ("col_min", np.uint32), ("col_max", np.uint32)])  # gs_component_record
+
+
+@dataclass(frozen=True, eq=False)
+class ComponentList:
+    """One record per connected component of one thresholded plane, formed on the device (``gs_field_component_list``; the
+    rule is include/gs_hip.h's, that of ``Components``): ``records`` is a structured array of ``COMPONENT_RECORD_DTYPE`` --
+    cells, sums of the cells' row and column indices, first cell in row-major order, bounding box (inclusive) -- of the
+    components of at least ``min_size`` cells, in ascending (first_row, first_col) order: the order in which
+    ``scipy.ndimage.label`` numbers them.  All exact integers."""
+
+    records: np.ndarray
+    rows: int
+    cols: int
+    threshold: float
+    above: bool
+    connectivity: int
+    min_size: int
+
+    @property
+    def count(self) -> int:
+        return int(self.records.shape[0])
+
+    @property
+    def sizes(self) -> np.ndarray:
+        return self.records["size"]
+
+    def centroids(self) -> np.ndarray:
+        """``(n, 2)`` float64: (row, column) = sum / size."""
+        size = self.records["size"].astype(np.float64)
+        return np.stack([self.records["sum_row"] / size, self.records["sum_col"] / size], axis=1).reshape(-1, 2)
+
+    def boxes(self) -> np.ndarray:
+        """``(n, 4)`` int64: row_min, row_max, col_min, col_max, inclusive."""
+        return np.stack([self.records[k].astype(np.int64) for k in ("row_min", "row_max", "col_min", "col_max")], axis=1).reshape(-1, 4)
+
+    def first_cells(self) -> np.ndarray:
+        """``(n, 2)`` int64: every component's first cell in row-major order."""
+        return np.stack([self.records["first_row"].astype(np.int64), self.records["first_col"].astype(np.int64)], axis=1).reshape(-1, 2)
+
+    def touches_edge(self) -> np.ndarray:
+        """``(n,)`` bool: the bounding box reaches the first or last row or column of the plane."""
+        r = self.records
+        return ((r["row_min"] == 0) | (r["col_min"] == 0) | (r["row_max"] == max(self.rows - 1, 0)) |
+                (r["col_max"] == max(self.cols - 1, 0)))
+
+
+def _species_plane(species: str, u, v):
+    if species not in ("u", "v"):
+        raise ValueError("species %r (\"u\" or \"v\")" % (species,))
+    return u if species == "u" else v
+
+
+def _component_lists(lib, handle, shape, threshold, above, connectivity, min_size) -> List[ComponentList]:
+    """The planes of a ``gs_component_list`` copied out; the handle is destroyed at once."""
+    try:
+        planes, offsets = ctypes.c_uint64(0), ctypes.POINTER(ctypes.c_uint64)()
+        records = ctypes.POINTER(capi.GsComponentRecord)()
+        capi.check(lib.gs_component_list_view(handle, ctypes.byref(planes), ctypes.byref(offsets), ctypes.byref(records)))
+        off = np.ctypeslib.as_array(offsets, shape=(planes.value + 1,)).astype(np.int64) if planes.value else np.zeros(1, np.int64)
+        n = int(off[-1])
+        rec = np.zeros(n, COMPONENT_RECORD_DTYPE)
+        if n:
+            ctypes.memmove(rec.ctypes.data, records, n * COMPONENT_RECORD_DTYPE.itemsize)
+    finally:
+        lib.gs_component_list_destroy(handle)
+    thr = float(np.float32(threshold))
+    return [ComponentList(rec[off[i]:off[i + 1]].copy(), int(shape[0]), int(shape[1]), thr, bool(above), int(connectivity),
+                          int(min_size)) for i in range(planes.value)]
+
+
+def component_list_field(context: "HipContext", field: "HipConcentration", threshold: float, above: bool = True,
+                         connectivity: int = 8, min_size: int = 1) -> ComponentList:
+    """``gs_field_component_list``: one record per connected component of at least ``min_size`` cells of one plane over the
+    whole global grid (single-process contexts), thresholded at ``threshold`` with the sense ``above`` under ``connectivity``
+    4 or 8."""
+    h = ctypes.c_void_p()
+    capi.check(context._lib.gs_field_component_list(context.handle, field.handle, float(threshold), 1 if above else 0,
+                                                    int(connectivity), int(min_size), ctypes.byref(h)))
+    return _component_lists(context._lib, h, field.shape(), threshold, above, connectivity, min_size)[0]
+
+
 CORRELATION_STEPS = ((0, 1), (1, 0), (1, 1), (1, -1))  # e_k = (dr, dc): along a row, down a column, diagonal, anti-diagonal
 
 
@@ -905,6 +989,13 @@ class HipConcentration:
         when it is above (``above``) or below the threshold; ``connectivity`` 4 or 8."""
         return components_fields(context, [self], [thresholds], [above], connectivity)[0]
 
+    def component_list(self, context: HipContext, threshold: float, above: bool = True, connectivity: int = 8,
+                       min_size: int = 1) -> ComponentList:
+        """One record per connected component of at least ``min_size`` cells of this plane thresholded at ``threshold`` over
+        the whole global grid -- size, coordinate sums (the centroid), first cell, bounding box --, formed on the device
+        (``gs_field_component_list``; blocking, single-process contexts)."""
+        return component_list_field(context, self, threshold, above, connectivity, min_size)
+
     def correlation(self, context: HipContext, thresholds, max_lag: int = 32, above: bool = True) -> List[Correlation]:
         """The two-point pair counts of this plane thresholded at each of ``thresholds`` (1..4, one pass), lags 0 ..
         ``max_lag`` along four directions over the whole global grid, counted on the device (``gs_fields_correlation``;
@@ -1082,6 +1173,14 @@ class Species:
         list is empty."""
         return self._v_or_both(components_fields, u_thresholds, v_thresholds, (False, True), connectivity)
 
+    def component_list(self, threshold: float = 0.25, species: str = "v", above: bool = True, connectivity: int = 8,
+                       min_size: int = 1) -> ComponentList:
+        """Where the spots of the current state are: one record per connected component of at least ``min_size`` cells of
+        ``species`` ("u" or "v") thresholded at ``threshold`` (``gs_field_component_list``; blocking, single-process
+        contexts)."""
+        in_u, in_v, _, _ = self.in_out()
+        return component_list_field(self._context, _species_plane(species, in_u, in_v), threshold, above, connectivity, min_size)
+
     def correlation(self, v_thresholds=(0.25,), u_thresholds=None, max_lag: int = 32,
                     above: Tuple[bool, bool] = (False, True)) -> Tuple[List[Correlation], List[Correlation]]:
         """(U, V) two-point pair counts of the current state in one call (``gs_fields_correlation``; blocking, collective in
@@ -1238,6 +1337,18 @@ class Ensemble:
         capi.check(self._ctx._lib.gs_members_components(self._ctx.handle, self.handle, first, count, thr, sense, nt,
                                                          int(connectivity), out.ctypes.data_as(ctypes.POINTER(capi.GsComponents))))
         return out
+
+    def component_lists(self, first: int = 0, count: Optional[int] = None, species: str = "v", threshold: float = 0.25,
+                        above: bool = True, connectivity: int = 8, min_size: int = 1) -> List[ComponentList]:
+        """Component lists of members ``[first, first + count)`` formed on the device (``gs_members_component_list``,
+        blocking): one ``ComponentList`` per member -- what ``Species.component_list`` gives for a lone Species in the
+        member's state; rows are the member's own."""
+        first, count = self._range(first, count)
+        h = ctypes.c_void_p()
+        capi.check(self._ctx._lib.gs_members_component_list(self._ctx.handle, self.handle, first, count,
+                                                            _species_plane(species, 0, 1), float(threshold), 1 if above else 0,
+                                                            int(connectivity), int(min_size), ctypes.byref(h)))
+        return _component_lists(self._ctx._lib, h, self._shape, threshold, above, connectivity, min_size)
 
     def correlations(self, first: int = 0, count: Optional[int] = None, v_thresholds=(0.25,), u_thresholds=(0.5,),
                      max_lag: int = 32, above: Tuple[bool, bool] = (False, True)) -> np.ndarray:

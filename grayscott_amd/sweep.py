@@ -49,6 +49,15 @@ above, ``--comp-threshold-u A[,B,...]`` (as many values; default 0.5 for each) t
 each ``[samples, members, 2, nt]`` (axis 2: U, V), and ``by_size[samples, members, 2, nt, 32]``.  It changes no state either and
 works with ``--no-fields``.
 
+``--spots-every N`` records, at the same steps again, WHERE every member's spots are: one record per connected component of
+V above ``--spot-threshold-v T`` (required with the flag) formed on the device (``Ensemble.component_lists``; the rule is
+include/gs_hip.h's) -- size, coordinate sums (the centroid), first cell, bounding box -- of the components of at least
+``--spot-min-size M`` cells (default 1) under ``--spot-connectivity 4|8`` (default 8), into ``<output stem>.spots.npz``:
+``steps[samples]``, ``threshold``, ``connectivity``, ``min_size``, ``offsets[samples * members + 1]`` and ``records``, the
+lists one after the other as a structured array -- member m's records at sample s are
+``records[offsets[s * members + m] : offsets[s * members + m + 1]]``.  It changes no state either and works with
+``--no-fields``.
+
 ``--steady-every N`` asks of every member "has it stopped changing?".  A snapshot of the ensemble is kept on the device
 (``Ensemble.snapshot``), taken at step 0; after every N steps and after the last one every member is compared with it on the
 device (``Ensemble.changes_since``: with d = now - snapshot per cell in f64, the sum of |d|, the sum of d * d and the largest
@@ -87,7 +96,7 @@ import numpy as np
 
 from . import hdf5_min
 from .simulate import add_backend_args, backend_args
-from .simulation import Parameters, Simulation, pairs_total, quad_measures
+from .simulation import COMPONENT_RECORD_DTYPE, Parameters, Simulation, pairs_total, quad_measures
 
 
 def value_range(text: str) -> List[float]:
@@ -154,6 +163,13 @@ def parse(argv=None):
                     help="as many thresholds below which a U cell is set (default 0.5 for each)")
     ap.add_argument("--comp-connectivity", type=int, default=8, choices=(4, 8),
                     help="cells are neighbours across a side (4) or also across a corner (8, the default)")
+    ap.add_argument("--spots-every", type=int, default=0, metavar="N",
+                    help="record every member's component list of V every N steps and at the end (<output stem>.spots.npz)")
+    ap.add_argument("--spot-threshold-v", type=float, default=None, metavar="T",
+                    help="the threshold above which a V cell is set (required with --spots-every)")
+    ap.add_argument("--spot-min-size", type=int, default=1, metavar="M", help="list the components of at least M cells (default 1)")
+    ap.add_argument("--spot-connectivity", type=int, default=8, choices=(4, 8),
+                    help="cells are neighbours across a side (4) or also across a corner (8, the default)")
     ap.add_argument("--morph-threshold-v", type=threshold_list, default=None, metavar="A[,B,...]",
                     help="1 to 4 thresholds: V is set where it is above them")
     ap.add_argument("--morph-threshold-u", type=threshold_list, default=None, metavar="A[,B,...]",
@@ -204,6 +220,14 @@ def parse(argv=None):
             ap.error(f"--{short}-threshold-u needs as many values as --{short}-threshold-v")
     if not 1 <= args.corr_lags <= 64:
         ap.error("--corr-lags must be in 1..64")
+    if args.spots_every < 0:
+        ap.error("--spots-every must be at least 1 (0 = off)")
+    if args.spots_every and args.spot_threshold_v is None:
+        ap.error("--spots-every needs --spot-threshold-v")
+    if args.spot_threshold_v is not None and args.spot_threshold_v != args.spot_threshold_v:
+        ap.error("--spot-threshold-v must be a number")
+    if args.spot_min_size < 1:
+        ap.error("--spot-min-size must be at least 1")
     return args
 
 
@@ -279,6 +303,19 @@ def write_components(path: str, steps: List[int], samples: List[np.ndarray], thr
              largest=np.ascontiguousarray(c[..., 2]), by_size=np.ascontiguousarray(c[..., 3:]))
 
 
+def spots_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".spots.npz"
+
+
+def write_spots(path: str, steps: List[int], samples: List[list], threshold: float, connectivity: int, min_size: int) -> None:
+    lists = [member for sample in samples for member in sample]  # [samples * members] of ComponentList
+    offsets = np.zeros(len(lists) + 1, np.int64)
+    offsets[1:] = np.cumsum([c.count for c in lists])
+    records = np.concatenate([c.records for c in lists]) if lists else np.zeros(0, COMPONENT_RECORD_DTYPE)
+    np.savez(path, steps=np.asarray(steps, np.int64), threshold=np.float32(threshold), connectivity=np.int64(connectivity),
+             min_size=np.int64(min_size), offsets=offsets, records=records)
+
+
 def write_morphologies(path: str, steps: List[int], samples: List[np.ndarray], thresholds_u, thresholds_v, cells: int) -> None:
     q = np.stack(samples, axis=0)  # [samples, members, 2, nt, 6]
     area, perimeter, euler4, euler8 = quad_measures(q)
@@ -333,11 +370,13 @@ def run(args) -> dict:
     morph_at = sample_steps(args.steps, args.morphology_every) if args.morphology_every else []
     corr_at = sample_steps(args.steps, args.correlation_every) if args.correlation_every else []
     comp_at = sample_steps(args.steps, args.components_every) if args.components_every else []
+    spots_at = sample_steps(args.steps, args.spots_every) if args.spots_every else []
     done, settled, taken = 0, None, None
-    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at:
-        summaries, hists, changes, morphs, corrs, comps = [], [], [], [], [], []
+    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at or spots_at:
+        summaries, hists, changes, morphs, corrs, comps, spots = [], [], [], [], [], [], []
         snap = ens.snapshot() if steady_at else None
-        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at) | set(comp_at)):
+        for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at) | set(comp_at)
+                         | set(spots_at)):
             ens.prepare_steps(at - done)
             done = at
             if at in summary_at:
@@ -349,6 +388,9 @@ def run(args) -> dict:
             if at in comp_at:
                 comps.append(ens.components(v_thresholds=args.comp_threshold_v, u_thresholds=args.comp_threshold_u,
                                             connectivity=args.comp_connectivity))
+            if at in spots_at:
+                spots.append(ens.component_lists(species="v", threshold=args.spot_threshold_v, connectivity=args.spot_connectivity,
+                                                 min_size=args.spot_min_size))
             if at in corr_at:
                 corrs.append(ens.correlations(v_thresholds=args.corr_threshold_v, u_thresholds=args.corr_threshold_u,
                                               max_lag=args.corr_lags))
@@ -374,6 +416,9 @@ def run(args) -> dict:
         if comp_at:
             write_components(components_path(args.output), comp_at[:len(comps)], comps, args.comp_threshold_u,
                              args.comp_threshold_v, args.comp_connectivity)
+        if spots_at:
+            write_spots(spots_path(args.output), spots_at[:len(spots)], spots, args.spot_threshold_v, args.spot_connectivity,
+                        args.spot_min_size)
         if corr_at:
             write_correlations(correlation_path(args.output), corr_at[:len(corrs)], corrs, args.corr_threshold_u,
                                args.corr_threshold_v, args.corr_lags, shape)

@@ -37,6 +37,20 @@ inline void check(int32_t status)
 }
 
 namespace detail {
+// The planes of a gs_component_list copied out, one vector of records per plane; the list is destroyed at once.
+inline std::vector<std::vector<gs_component_record>> take_component_lists(gs_component_list *list)
+{
+    uint64_t planes = 0;
+    const uint64_t *offsets = nullptr;
+    const gs_component_record *records = nullptr;
+    const int32_t status = gs_component_list_view(list, &planes, &offsets, &records);
+    std::vector<std::vector<gs_component_record>> out;
+    if (status == GS_OK)
+        for (uint64_t i = 0; i < planes; ++i) out.emplace_back(records + offsets[i], records + offsets[i + 1]);
+    gs_component_list_destroy(list);
+    check(status);
+    return out;
+}
 // U's thresholds, then V's -- the C ABI's order for (U, V) -- or the refusal when their numbers differ.
 inline std::vector<float> uv_thresholds(const std::vector<float> &u_thresholds, const std::vector<float> &v_thresholds)
 {
@@ -581,6 +595,18 @@ class Species {
         }
         return uv;
     }
+    // where the spots are: one record per connected component of at least min_size cells of species (0 = U, 1 = V) of the
+    // current state thresholded at `threshold`, over the whole global grid, in ascending order of the first cell
+    // (gs_field_component_list; blocking, single-process contexts)
+    std::vector<gs_component_record> component_list(float threshold = 0.25f, int32_t species = 1, bool above = true,
+                                                    int32_t connectivity = 8, uint64_t min_size = 1)
+    {
+        if (species != 0 && species != 1) throw HipError(GS_ERR_INVALID, "species must be 0 (U) or 1 (V)");
+        gs_component_list *list = nullptr;
+        check(gs_field_component_list(context_->get(), species ? v_.in().raw() : u_.in().raw(), threshold, above ? 1 : 0,
+                                      connectivity, min_size, &list));
+        return detail::take_component_lists(list).at(0);
+    }
     // (U, V) two-point pair counts of the current state over the whole global grid, in one call (gs_fields_correlation;
     // blocking, collective in a multi-process context): one Correlation per threshold (1..4 per species, the same number for
     // both), lags 0 .. max_lag (1..64), U set where it is below its thresholds and V where it is above, unless the senses say
@@ -785,6 +811,18 @@ class Ensemble {
             out.push_back(Components::from_c(c[i], t[species * nt + k], species != 0, connectivity));
         }
         return out;
+    }
+    // component lists of members [first, first + count) from the newest state (gs_members_component_list, blocking): element i
+    // = the records of species (0 = U, 1 = V) of member first + i, what Species::component_list gives for a lone Species in that
+    // state; rows are the member's own
+    std::vector<std::vector<gs_component_record>> component_lists(std::size_t first, std::size_t count, float threshold = 0.25f,
+                                                                  int32_t species = 1, bool above = true,
+                                                                  int32_t connectivity = 8, uint64_t min_size = 1) const
+    {
+        gs_component_list *list = nullptr;
+        check(gs_members_component_list(ctx_->get(), e_, first, count, species, threshold, above ? 1 : 0, connectivity, min_size,
+                                        &list));
+        return detail::take_component_lists(list);
     }
     // two-point pair counts of members [first, first + count) from the newest state (gs_members_correlation, blocking):
     // element (2 i + s) * nt + j = species s (0 = U, 1 = V) of member first + i at that species' threshold j, what

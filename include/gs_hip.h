@@ -720,7 +720,8 @@ int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint
  * GS_ERR_UNSUPPORTED: a slab (or a member) of 2^32 cells or more -- labels are 32-bit.  GS_ERR_NOMEM: the label memory cannot
  * be had; nothing is changed.  In a multi-process context the ranks agree on that verdict before anything else travels: if
  * one rank cannot have its memory, every rank returns GS_ERR_NOMEM.
- * Not done: components wrapped under the periodic rule; centroids or bounding boxes; label planes for the caller. */
+ * Not done: components wrapped under the periodic rule; label planes for the caller.  (Centroids and bounding boxes: the
+ * component lists below.) */
 #define GS_COMPONENTS_BATCH_BYTES (256u << 20)
 typedef struct gs_components {
     uint64_t components;  /* connected components of set cells                                   */
@@ -732,6 +733,68 @@ int32_t gs_fields_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
                              int32_t nt, int32_t connectivity, gs_components *out);
 int32_t gs_members_components(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
                               const int32_t above[2], int32_t nt, int32_t connectivity, gs_components *out);
+
+/* Component lists computed on the device: WHERE the spots of one plane of the WHOLE global grid are after thresholding -- one
+ * record per connected component with its size, the sums of its cells' coordinates (the centroid), its first cell and its
+ * bounding box -- without downloading the plane: whether a spot pattern is a lattice (distances between centroids), whether
+ * the spots move from one sample to the next, how elongated a component is, which ones touch the edge of the domain.
+ * For a plane x of R x C cells, a threshold t, a sense `above`, a connectivity of 4 or 8 and a min_size >= 1:
+ *   - cells are SET and joined into components exactly by the rule of gs_fields_components: a NaN cell is never set, a cell
+ *     equal to t is not set, a sub-normal cell is the value it is, and components NEVER wrap, under every boundary rule;
+ *   - every component of at least min_size cells is LISTED as one gs_component_record.  Rows of a field are rows of the whole
+ *     global grid, rows of a member are the member's own.  The centroid is (sum_row / size, sum_col / size); the first cell
+ *     is the component's first in row-major order;
+ *   - within a plane the records are in ascending (first_row, first_col) order -- the order in which a row-major labelling
+ *     (scipy.ndimage.label) numbers components.
+ * The result is integers only: the same bits for any slab count, step kernel or launch shape, and for a member and a lone
+ * Species in the same state.  With min_size = 1 the list agrees with gs_fields_components for the same arguments: the number
+ * of records is `components`, the sizes add up to `set_cells`, their maximum is `largest`, their floor(log2) bins are `by_size`.
+ * An empty plane (R = 0 or C = 0, or no cell set): GS_OK and a list without records.
+ *   gs_field_component_list    one plane; the list has 1 plane.  One wait for enqueued work (as gs_fields_components), then
+ *                              slab by slab on the slab's compute stream: the labelling of gs_fields_components, then the
+ *                              components to list are counted -- in a slab chain those that touch a slab's first or last row
+ *                              are listed whatever their size, because min_size can only be applied after the seam merge --,
+ *                              the count is read back once, the records are written in first-cell order and every set cell
+ *                              adds its coordinates to its record (integer atomics, one set per run of cells).  The host
+ *                              makes the rows global, joins the records that meet across the seams (sizes and sums added, the
+ *                              boxes united, the first cell the smallest), applies min_size and orders by first cell; ghost
+ *                              rows are never read.
+ *   gs_members_component_list  species (0 = U, 1 = V) of members first .. first + count - 1 from the newest slot (a retired
+ *                              member: its held state); the list has `count` planes.  A member is a plane of its own: it never
+ *                              joins its neighbours' rows.  Members are labelled in the batches of gs_members_components.
+ *   gs_component_list_view     *planes, and the records of plane i: records[offsets[i] .. offsets[i + 1]); offsets has
+ *                              planes + 1 entries.  The pointers stay valid until the list is destroyed.
+ *   gs_component_list_destroy  frees the list; NULL: GS_OK.  A list is host memory owned by the library and independent of the
+ *                              context: it may outlive it.
+ * Label memory: as for gs_fields_components, 8 bytes per cell of the slab or batch -- the u32 size of a root is replaced by
+ * its record's index once the record holds the size --, in a slab chain 1 bit per cell more (the marks of the components that
+ * touch a seam row), and 48 bytes per record; all allocated for the call and freed before it returns.  One u32 per 256 cells of
+ * the slab's scratch buffer holds the counts.
+ * Both calls block like gs_fields_components (one wait for enqueued work, then the slabs' compute streams) and have no side
+ * effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID, decided in this order: a null
+ * argument (ctx, out), a NaN threshold, a connectivity that is neither 4 nor 8, min_size == 0, a species outside 0..1 --
+ * all before any handle is looked at --; then a null or foreign handle, members outside the ensemble.  GS_ERR_UNSUPPORTED: a
+ * slab or a batch of members of 2^32 cells or more; a grid for which a sum could overflow, rows * rows * cols or
+ * rows * cols * cols >= 2^64; a multi-process context (world > 1) -- every rank reaches that verdict alone, before anything
+ * is allocated or sent: exchanging record lists of variable length between ranks is a follow-up.  GS_ERR_NOMEM: label or
+ * record memory cannot be had; nothing is changed and no list is returned.  On any refusal *out is left as it was.
+ * Not done: multi-process contexts; components wrapped under the periodic rule; label planes for the caller;
+ * intensity-weighted centroids or any float accumulation; matching of spots across time; several thresholds or fields in
+ * one call. */
+typedef struct gs_component_record {
+    uint64_t size;                               /* cells                                                              */
+    uint64_t sum_row, sum_col;                   /* sums of the cells' row / column indices: centroid = sum / size    */
+    uint32_t first_row, first_col;               /* its first cell in row-major order                                  */
+    uint32_t row_min, row_max, col_min, col_max; /* bounding box, inclusive                                            */
+} gs_component_record;                           /* 48 bytes, all integers */
+typedef struct gs_component_list gs_component_list; /* host memory owned by the library, independent of the context */
+int32_t gs_field_component_list(gs_ctx *ctx, gs_field *f, float threshold, int32_t above, int32_t connectivity, uint64_t min_size,
+                                gs_component_list **out);
+int32_t gs_members_component_list(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, int32_t species, float threshold,
+                                  int32_t above, int32_t connectivity, uint64_t min_size, gs_component_list **out);
+int32_t gs_component_list_view(const gs_component_list *list, uint64_t *planes, const uint64_t **offsets,
+                               const gs_component_record **records);
+int32_t gs_component_list_destroy(gs_component_list *list);
 
 /* Two states compared on the device: how far one plane of the WHOLE global grid is from another of the same shape -- "has
  * this run stopped changing?" -- without downloading either, and the device copies that give a state to compare with
