@@ -4,7 +4,9 @@ every form of the marching kernel (K = 1..4, 1, 2 and 4 columns per lane, genera
 kernel auto at sizes that run the resident, tile and window kernels without a mask, slab chains, row bands and graph
 replay; an all-fluid mask changes no bit, walls keep their bits; a sealed box stays sealed; the fluid's mass is conserved
 under the zero-flux rule without reaction; the mask's lifecycle and refusals; ensembles ignore the mask; the simulate
-driver end to end.  (Two processes: tests/test_gpu_mask_multiprocess.py.)"""
+driver end to end.  The masks go through Simulation.set_mask, which uploads 0 and 1: the values random_mask writes (1,
+-3, NaN, -0) reach the device's own classification in test_caller_field_may_change_and_go only.  (Raw mask values, drawn
+schedules and aimed wall layouts: tests/test_gpu_mask_property.py.  Two processes: tests/test_gpu_mask_multiprocess.py.)"""
 from __future__ import annotations
 
 import os
@@ -26,7 +28,10 @@ RULE_SUFFIX = {0: "/mask", 1: "/mask", 2: "/periodic/mask", 3: "/neumann/mask"}
 
 
 def random_mask(shape, seed, share=0.25):
-    """Walls (1, -3 or NaN) in about ``share`` of the cells, fluid +0 or -0."""
+    """Walls (1, -3 or NaN) in about ``share`` of the cells, fluid +0 or -0.  The reference classifies these values;
+    the device sees them only where a test hands the field to gs_ctx_set_mask itself (test_caller_field_may_change_and_go):
+    Simulation.set_mask turns the plane into 0 and 1 on the host before it uploads it.  Raw mask values of every class on
+    the device: tests/test_gpu_mask_property.py."""
     rng = np.random.default_rng(seed)
     m = np.where(rng.random(shape) < 0.5, np.float32(0.0), np.float32(-0.0)).astype(np.float32)
     walls = rng.random(shape) < share
