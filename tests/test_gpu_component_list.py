@@ -12,6 +12,7 @@ from tests import component_list_ref as ref
 from tests import components_ref
 from tests import morph_ref
 from tests.helpers import species_from_arrays, stress_fields
+from tests.observe_cases import seam_rows
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -138,10 +139,6 @@ def test_nan_infinite_and_zero_cells(built):
 
 
 # ---- slab layouts -------------------------------------------------------------------------------------------------------
-
-def seam_rows(rows, slabs):
-    return sorted({i * rows // slabs for i in range(1, slabs)} - {0})
-
 
 def layout_planes(shape, slabs):
     rows, cols = shape

@@ -11,6 +11,7 @@ from grayscott_amd.simulation import components_fields
 from tests import components_ref as ref
 from tests import morph_ref
 from tests.helpers import species_from_arrays, stress_fields
+from tests.observe_cases import seam_rows
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -243,10 +244,6 @@ def test_components_have_no_side_effects(built, shape):
 
 
 # ---- slab layout --------------------------------------------------------------------------------------------------------
-
-def seam_rows(rows, slabs):
-    return sorted({i * rows // slabs for i in range(1, slabs)})
-
 
 def layout_planes(shape, slabs):
     """(U, V) pairs: V set above 0.25 carries the pattern, U set below 0.5 carries it too (U = 1 - pattern)."""
