@@ -21,25 +21,23 @@ Needs the MI355X: there is no CPU path.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import os
 import statistics
 import sys
-import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from components_rate import _fill, _label, _medians, _wall  # noqa: E402  (the same inputs and the same clock)
+import ratekit  # noqa: E402
+from ratekit import ENSEMBLE  # noqa: E402
+from components_rate import fill, scipy_ndimage  # noqa: E402  (the same inputs)
 
-GRIDS = "16384x16384,4096x4096,1080x1920"
-ENSEMBLE = (512, 64, 128)  # members, rows, cols
 KINDS = ("new", "developed", "full", "random")
 TV = 0.25
+HEADER = ["| grid | input | records | largest (cells) | list (ms) | list, min_size 5 (ms) | components (ms) | list / components | "
+          "download + label + measure (ms) | host / list |",
+          "|---|---|---|---|---|---|---|---|---|---|"]
 
 
 def _develop(sim, species, rows, cols):
@@ -67,108 +65,81 @@ def _host_list(ndimage, plane, threshold, structure):
     return n, int(sizes.max())
 
 
-def time_species(rows, cols, kind, calls, label_calls):
-    from grayscott_amd import HipArgs, Parameters, Simulation
+def _columns(m):
+    return {"list_ms": m["list"][0], "list_min5_ms": m["list5"][0], "components_ms": m["comp"][0], "list_event_ms": m["list"][1],
+            "list_min5_event_ms": m["list5"][1], "components_event_ms": m["comp"][1], "download_label_ms": None}
 
-    sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
-    ctx = sim.context
-    species = sim.make_species((rows, cols))
-    _, in_v, _, _ = species.in_out()
-    if kind == "full":
-        in_v.upload(ctx, np.full((rows, cols), 0.5, np.float32))
-    elif kind == "developed":
-        _develop(sim, species, rows, cols)
-    else:
-        _fill(sim, species, kind, rows, cols)
-    _, in_v, _, _ = species.in_out()
-    got = in_v.component_list(ctx, TV, True, 8)
-    largest = int(got.sizes.max()) if got.count else 0
-    m = _medians(ctx, {"list": lambda: in_v.component_list(ctx, TV, True, 8), "list5": lambda: in_v.component_list(ctx, TV, True, 8, 5),
-                       "comp": lambda: in_v.components(ctx, [TV], True, 8)}, calls)
-    out = {"grid": f"{rows}x{cols}", "input": kind, "cells": rows * cols, "records": got.count, "largest": largest,
-           "list_ms": m["list"][0], "list_min5_ms": m["list5"][0], "components_ms": m["comp"][0], "list_event_ms": m["list"][1],
-           "list_min5_event_ms": m["list5"][1], "components_event_ms": m["comp"][1], "download_label_ms": None}
-    ndimage = _label()
-    if ndimage is not None and label_calls > 0:
-        eight = ndimage.generate_binary_structure(2, 2)
-        host = []
-        out["download_label_ms"] = statistics.median(
-            _wall(lambda: host.append(_host_list(ndimage, in_v.make_scalar_view(ctx), TV, eight))) for _ in range(label_calls))
-        if host[-1] != (got.count, largest):
-            raise RuntimeError(f"{out['grid']} {kind}: the device lists {(got.count, largest)}, scipy {host[-1]}")
-    ctx.close()
-    return out
+
+def time_species(rows, cols, kind, calls, label_calls):
+    with ratekit.species_subject(rows, cols) as (sim, ctx, species):
+        if kind == "full":
+            species.in_out()[1].upload(ctx, np.full((rows, cols), 0.5, np.float32))
+        elif kind == "developed":
+            _develop(sim, species, rows, cols)
+        else:
+            fill(sim, species, kind)
+        _, in_v, _, _ = species.in_out()
+        got = in_v.component_list(ctx, TV, True, 8)
+        largest = int(got.sizes.max()) if got.count else 0
+        m = ratekit.medians(ctx, {"list": lambda: in_v.component_list(ctx, TV, True, 8),
+                                  "list5": lambda: in_v.component_list(ctx, TV, True, 8, 5),
+                                  "comp": lambda: in_v.components(ctx, [TV], True, 8)}, calls, both=True)
+        out = {"grid": f"{rows}x{cols}", "input": kind, "cells": rows * cols, "records": got.count, "largest": largest, **_columns(m)}
+        ndimage = scipy_ndimage(label_calls)
+        if ndimage is not None:
+            eight = ndimage.generate_binary_structure(2, 2)
+            host = []
+            out["download_label_ms"] = statistics.median(
+                ratekit.wall_ms(lambda: host.append(_host_list(ndimage, in_v.make_scalar_view(ctx), TV, eight)))
+                for _ in range(label_calls))
+            if host[-1] != (got.count, largest):
+                raise RuntimeError(f"{out['grid']} {kind}: the device lists {(got.count, largest)}, scipy {host[-1]}")
+        return out
 
 
 def time_ensemble(members, rows, cols, calls, label_calls):
-    from grayscott_amd import HipArgs, Parameters, Simulation
+    with ratekit.ensemble_subject(members, rows, cols) as (sim, ctx, ens):
+        ens.perform_steps(16)
+        lists = ens.component_lists(threshold=TV)
+        m = ratekit.medians(ctx, {"list": lambda: ens.component_lists(threshold=TV),
+                                  "list5": lambda: ens.component_lists(threshold=TV, min_size=5),
+                                  "comp": lambda: ens.components(v_thresholds=[TV], u_thresholds=[0.5])}, calls, both=True)
+        out = {"grid": f"{members} x {rows}x{cols}", "input": "new + 16 steps, V (components: U and V)",
+               "cells": members * rows * cols, "records": sum(c.count for c in lists),
+               "largest": max([int(c.sizes.max()) for c in lists if c.count] or [0]), **_columns(m)}
+        ndimage = scipy_ndimage(label_calls)
+        if ndimage is not None:
+            eight = ndimage.generate_binary_structure(2, 2)
 
-    sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
-    ctx = sim.context
-    ens = sim.make_ensemble((rows, cols), Parameters(), members=members)
-    ens.perform_steps(16)
-    lists = ens.component_lists(threshold=TV)
-    m = _medians(ctx, {"list": lambda: ens.component_lists(threshold=TV), "list5": lambda: ens.component_lists(threshold=TV, min_size=5),
-                       "comp": lambda: ens.components(v_thresholds=[TV], u_thresholds=[0.5])}, calls)
-    out = {"grid": f"{members} x {rows}x{cols}", "input": "new + 16 steps, V (components: U and V)", "cells": members * rows * cols,
-           "records": sum(c.count for c in lists), "largest": max([int(c.sizes.max()) for c in lists if c.count] or [0]),
-           "list_ms": m["list"][0], "list_min5_ms": m["list5"][0], "components_ms": m["comp"][0], "list_event_ms": m["list"][1],
-           "list_min5_event_ms": m["list5"][1], "components_event_ms": m["comp"][1], "download_label_ms": None}
-    ndimage = _label()
-    if ndimage is not None and label_calls > 0:
-        eight = ndimage.generate_binary_structure(2, 2)
+            def host():
+                v = ens.result_views()
+                for i in range(members):
+                    _host_list(ndimage, v[i], TV, eight)
 
-        def host():
-            v = ens.result_views()
-            for i in range(members):
-                _host_list(ndimage, v[i], TV, eight)
+            out["download_label_ms"] = statistics.median(ratekit.wall_ms(host) for _ in range(label_calls))
+        return out
 
-        out["download_label_ms"] = statistics.median(_wall(host) for _ in range(label_calls))
-    ens.destroy()
-    ctx.close()
-    return out
+
+def _flags(ap):
+    ap.add_argument("--label-calls", type=int, default=1, help="timed runs of the download + scipy route (0: none)")
+    ap.add_argument("--kinds", default=",".join(KINDS))
 
 
 def main(argv=None) -> int:
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--calls", type=int, default=9)
-    ap.add_argument("--label-calls", type=int, default=1, help="timed runs of the download + scipy route (0: none)")
-    ap.add_argument("--grids", default=GRIDS)
-    ap.add_argument("--kinds", default=",".join(KINDS))
-    ap.add_argument("--no-ensemble", action="store_true")
-    ap.add_argument("--json", default=None, help="also write the rows as a JSON list")
-    ap.add_argument("--md", default=None, help="also write the table as markdown")
-    args = ap.parse_args(argv)
-    import torch  # noqa: F401  (the process's HIP runtime is torch's, as in bench.py and the tests)
-
-    rows = []
-
-    def keep(row):
-        rows.append(row)
-        print(json.dumps(row), flush=True)
-        if args.json:  # (after every row: a run that is cut short leaves what it measured)
-            os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
-            with open(args.json, "w") as f:
-                json.dump(rows, f, indent=1)
-
-    for grid in [g for g in args.grids.split(",") if g]:
-        r, c = (int(x) for x in grid.split("x"))
-        for kind in [k for k in args.kinds.split(",") if k]:
-            keep(time_species(r, c, kind, args.calls, args.label_calls))
+    args = ratekit.observable_args(__doc__, argv, calls=9, add=_flags)
+    report = ratekit.Report(args.json, args.md)
+    for r, c in ratekit.parse_grids(args.grids):
+        for kind in filter(None, args.kinds.split(",")):
+            report.row(time_species(r, c, kind, args.calls, args.label_calls))
     if not args.no_ensemble:
-        keep(time_ensemble(*ENSEMBLE, args.calls, args.label_calls))
-    lines = ["| grid | input | records | largest (cells) | list (ms) | list, min_size 5 (ms) | components (ms) | list / components | "
-             "download + label + measure (ms) | host / list |",
-             "|---|---|---|---|---|---|---|---|---|---|"]
-    for r in rows:
+        report.row(time_ensemble(*ENSEMBLE, args.calls, args.label_calls))
+    report.table(*HEADER)
+    for r in report.rows:
         label = f"{r['download_label_ms']:.1f}" if r["download_label_ms"] else "-"
         ratio = f"{r['download_label_ms'] / r['list_ms']:.1f}" if r["download_label_ms"] else "-"
-        lines.append(f"| {r['grid']} | {r['input']} | {r['records']} | {r['largest']} | {r['list_ms']:.3f} | {r['list_min5_ms']:.3f} | "
+        report.table(f"| {r['grid']} | {r['input']} | {r['records']} | {r['largest']} | {r['list_ms']:.3f} | {r['list_min5_ms']:.3f} | "
                      f"{r['components_ms']:.3f} | {r['list_ms'] / r['components_ms']:.2f} | {label} | {ratio} |")
-    print("\n".join(lines))
-    if args.md:
-        with open(args.md, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.finish()
     return 0
 
 

@@ -17,17 +17,14 @@ Needs the MI355X: there is no CPU path.
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import re
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-GRIDS = [(16384, 16384, 1), (4096, 4096, 1), (1080, 1920, 1), (512, 1024, 1), (16384, 16384, 2)]  # rows, cols, slabs
+import ratekit  # noqa: E402
+
+GRIDS = "16384x16384,4096x4096,1080x1920,512x1024,16384x16384x2"  # rows x cols [x slabs]
 
 
 def munafo(rows, cols):
@@ -37,76 +34,6 @@ def munafo(rows, cols):
     feed = np.repeat(linear_values(0.01, 0.06, rows)[:, None], cols, axis=1)
     kill = np.repeat(linear_values(0.045, 0.07, cols)[None, :], rows, axis=0)
     return feed, kill
-
-
-def time_grid(rows, cols, steps, calls, mapped, kernel=0, slabs=1, prove=True):
-    import numpy as np
-
-    from grayscott_amd import HipArgs, Parameters, Simulation, capi
-
-    devices = [0] * slabs
-    fmap = munafo(rows, cols) if mapped else None
-    sim = Simulation.new(Parameters(), HipArgs(devices=devices, kernel=kernel))
-    ctx = sim.context
-    species = sim.make_species((rows, cols))
-    if mapped:
-        sim.set_param_map(*fmap)
-    warm = 0
-    while True:  # warm-up: until the on-line tuner has settled on the marching kernel's configuration
-        sim.perform_steps(species, steps)
-        warm += 1
-        name = ctx.info()[0]
-        if warm >= 40 or not name.startswith("tb-") or "@" in name:
-            break
-    times = []
-    for _ in range(calls):
-        ctx.timer_start()
-        sim.prepare_steps(species, steps)
-        times.append(ctx.timer_stop())
-    ctx.sync()
-    kernel_name = ctx.info()[0]
-    total = steps * (calls + warm)
-    out = {"rows": rows, "cols": cols, "slabs": slabs, "mapped": mapped, "pinned_kernel": kernel, "steps_per_call": steps,
-           "calls": calls, "warmup_calls": warm, "kernel": kernel_name, "ms": statistics.median(times), "ms_all": times}
-    out["rate"] = rows * cols * steps / (out["ms"] * 1e3)
-    if prove:
-        iu, iv, _, _ = species.in_out()
-        got_u, got_v = iu.make_scalar_view(ctx), iv.make_scalar_view(ctx)
-    for c in species.in_out():
-        c.destroy()
-    ctx.close()
-    if not prove:
-        return out
-    # the proof: the same steps on the same slabs, one gs_step of the (mapped) cross-check kernel at a time
-    ref = Simulation.new(Parameters(), HipArgs(devices=devices, kernel=capi.GS_KERNEL_SIMPLE))
-    rs = ref.make_species((rows, cols))
-    if mapped:
-        ref.set_param_map(*fmap)
-    for _ in range(total):
-        ref.perform_step(rs)
-    ru, rv, _, _ = rs.in_out()
-    ref_u, ref_v = ru.make_scalar_view(ref.context), rv.make_scalar_view(ref.context)
-    out.update(replay_kernel=ref.context.info()[0], replay_steps=total,
-               proof=bool(got_u.tobytes() == ref_u.tobytes() and got_v.tobytes() == ref_v.tobytes()),
-               sum_v=float(np.sum(got_v, dtype=np.float64)))
-    for c in rs.in_out():
-        c.destroy()
-    ref.context.close()
-    return out
-
-
-def entry_of(name):
-    """The kernel instance behind a reported name of the marching kernel's map form, e.g. tb-k4c2/strict.op/map@.. ->
-    gs_step_tb_mk_strict<4, 3, 2, 0>."""
-    m = re.match(r"tb-k(\d)(c\d)?/(strict|fused)(\.op)?(/periodic|/neumann)?/map", name)
-    if not m:
-        return None
-    k, c, flavour, op, rule = m.groups()
-    cpl = int(c[1:]) if c else 4
-    return f"gs_step_tb_mk_{flavour}<{k}, {3 if op else 0}, {cpl}, {RULE_SET.get(rule, 0)}>"
-
-
-RULE_SET = {"/periodic": 1, "/neumann": 2}
 
 
 def main(argv=None) -> int:
@@ -120,38 +47,31 @@ def main(argv=None) -> int:
     import codeobj
 
     kernels = {k.name: k for k in codeobj.kernels()}
-    grids = GRIDS
-    if args.grids:
-        grids = [tuple(int(x) for x in g.split("x")) for g in args.grids.split(",")]
-        grids = [g if len(g) == 3 else g + (1,) for g in grids]
-    lines = ["| grid | uniform: kernel | Mcells x steps / s | mapped: kernel | Mcells x steps / s | mapped / uniform | "
-             "mapped streaming kernel | marching / streaming | VGPRs | waves per SIMD | replay (mapped simple kernel) |",
-             "|---|---|---|---|---|---|---|---|---|---|---|"]
-    print("\n".join(lines), flush=True)
+    report = ratekit.Report(args.json, args.md, json_lines=True)
+    report.table("| grid | uniform: kernel | Mcells x steps / s | mapped: kernel | Mcells x steps / s | mapped / uniform | "
+                 "mapped streaming kernel | marching / streaming | VGPRs | waves per SIMD | replay (mapped simple kernel) |",
+                 "|---|---|---|---|---|---|---|---|---|---|---|")
     ok = True
-    for rows, cols, slabs in grids:
-        recs = [time_grid(rows, cols, args.steps, args.calls, False, slabs=slabs, prove=False),
-                time_grid(rows, cols, args.steps, args.calls, True, slabs=slabs),
-                time_grid(rows, cols, max(16, args.steps // 4), args.calls, True, kernel=2, slabs=slabs, prove=False)]
+    for rows, cols, slabs in ratekit.parse_grids(args.grids or GRIDS, slabs=True):
+        fmap = munafo(rows, cols)
+        attach = lambda sim: sim.set_param_map(*fmap)  # noqa: E731
+
+        def timed(steps, mapped, kernel=0, prove=False):
+            r = ratekit.timed_steps(rows, cols, steps, args.calls, kernel=kernel, slabs=slabs, attach=attach if mapped else None,
+                                    prove=prove)
+            return dict(r, slabs=slabs, mapped=mapped, pinned_kernel=kernel)
+
+        recs = [timed(args.steps, False), timed(args.steps, True, prove=True), timed(max(16, args.steps // 4), True, kernel=2)]
         uni, mp, st = recs
         ok = ok and mp["proof"]
-        entry = entry_of(mp["kernel"].split("@")[0])
-        k = kernels.get(entry) if entry else None
-        vgpr = k.vgpr if k else None
-        waves = min(8, 512 // (((vgpr + 7) // 8) * 8)) if vgpr else None
+        entry, vgpr, waves = ratekit.registers(kernels, mp["kernel"], "map")
         grid = f"{rows} x {cols}" + (f", {slabs} slabs" if slabs > 1 else "")
-        line = (f"| {grid} | {uni['kernel']} | {uni['rate']:.0f} | {mp['kernel']} | {mp['rate']:.0f} | "
-                f"{mp['rate'] / uni['rate']:.3f} | {st['kernel']}: {st['rate']:.0f} | {mp['rate'] / st['rate']:.2f}x | "
-                f"{vgpr} | {waves} | {mp['replay_steps']} steps: {'identical' if mp['proof'] else 'DIFFERS'} |")
-        lines.append(line)
-        print(line, flush=True)
-        if args.json:
-            with open(args.json, "a") as f:
-                for r in recs:
-                    f.write(json.dumps(dict(r, entry=entry, vgpr=vgpr, waves_per_simd=waves)) + "\n")
-    if args.md:
-        with open(args.md, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        report.table(f"| {grid} | {uni['kernel']} | {uni['rate']:.0f} | {mp['kernel']} | {mp['rate']:.0f} | "
+                     f"{mp['rate'] / uni['rate']:.3f} | {st['kernel']}: {st['rate']:.0f} | {mp['rate'] / st['rate']:.2f}x | "
+                     f"{vgpr} | {waves} | {mp['replay_steps']} steps: {'identical' if mp['proof'] else 'DIFFERS'} |")
+        for r in recs:
+            report.row(dict(r, entry=entry, vgpr=vgpr, waves_per_simd=waves))
+    report.finish()
     return 0 if ok else 1
 
 

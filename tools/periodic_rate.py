@@ -16,111 +16,15 @@ Needs the MI355X: there is no CPU path.
 from __future__ import annotations
 
 import argparse
-import json
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-GRIDS = [(16384, 16384), (4096, 4096), (1080, 1920), (512, 1024)]
+import ratekit  # noqa: E402
+
+GRIDS = "16384x16384,4096x4096,1080x1920,512x1024"
 RULES = [("clipped", 0), ("zero halo", 1), ("periodic", 2)]
-
-
-def time_grid(rows, cols, boundary, steps, calls, kernel=0):
-    import numpy as np
-
-    from grayscott_amd import HipArgs, Parameters, Simulation, capi
-
-    sim = Simulation.new(Parameters(), HipArgs(devices=[0], boundary=boundary, kernel=kernel))
-    ctx = sim.context
-    species = sim.make_species((rows, cols))
-    warm = 0
-    while True:  # warm-up: until the on-line tuner has settled on the marching kernel's configuration
-        sim.perform_steps(species, steps)
-        warm += 1
-        name = ctx.info()[0]
-        if warm >= 40 or not name.startswith("tb-") or "@" in name:
-            break
-    times = []
-    for _ in range(calls):
-        ctx.timer_start()
-        sim.prepare_steps(species, steps)
-        times.append(ctx.timer_stop())
-    ctx.sync()
-    kernel_name = ctx.info()[0]
-    total = steps * (calls + warm)
-    iu, iv, _, _ = species.in_out()
-    got_u, got_v = iu.make_scalar_view(ctx), iv.make_scalar_view(ctx)
-    for c in species.in_out():
-        c.destroy()
-    ctx.close()
-    # the proof: the same steps, one gs_step of the cross-check kernel at a time
-    ref = Simulation.new(Parameters(), HipArgs(devices=[0], boundary=boundary, kernel=capi.GS_KERNEL_SIMPLE))
-    rs = ref.make_species((rows, cols))
-    for _ in range(total):
-        ref.perform_step(rs)
-    ru, rv, _, _ = rs.in_out()
-    ref_u, ref_v = ru.make_scalar_view(ref.context), rv.make_scalar_view(ref.context)
-    replay = ref.context.info()[0]
-    for c in rs.in_out():
-        c.destroy()
-    ref.context.close()
-    ms = statistics.median(times)
-    return {"rows": rows, "cols": cols, "boundary": boundary, "steps_per_call": steps, "calls": calls, "warmup_calls": warm,
-            "kernel": kernel_name,
-            "ms": ms, "ms_all": times, "rate": rows * cols * steps / (ms * 1e3), "replay_kernel": replay, "replay_steps": total,
-            "proof": bool(got_u.tobytes() == ref_u.tobytes() and got_v.tobytes() == ref_v.tobytes()),
-            "sum_v": float(np.sum(got_v, dtype=np.float64))}
-
-
-def time_ensemble(members, rows, cols, steps, calls, sample):
-    import numpy as np
-
-    from ensemble_rate import member_params
-    from grayscott_amd import HipArgs, Simulation
-
-    params = member_params(members)
-    sim = Simulation.new(params[0], HipArgs(devices=[0], boundary=2))
-    ctx = sim.context
-    ens = sim.make_ensemble((rows, cols), params)
-    ens.perform_steps(steps)
-    times = []
-    for _ in range(calls):
-        ctx.timer_start()
-        ens.prepare_steps(steps)
-        times.append(ctx.timer_stop())
-    ctx.sync()
-    kernel = ctx.info()[0]
-    idx = sorted({int(round(i * (members - 1) / max(1, sample - 1))) for i in range(sample)})
-    solo = [sim.make_species((rows, cols)) for _ in idx]
-    seq, solo_kernel = [], None
-    for call in range(calls + 1):  # the first call of every member is its warm-up
-        ctx.timer_start()
-        for j, i in enumerate(idx):
-            ctx.set_params(params[i])
-            sim.prepare_steps(solo[j], steps)
-        ms = ctx.timer_stop()
-        if call:
-            seq.append(ms)
-        solo_kernel = ctx.info()[0]
-    ctx.sync()
-    j = len(idx) // 2
-    got, ref = ens.result_views(idx[j], 1)[0], solo[j].make_result_view()
-    out = {"members": members, "rows": rows, "cols": cols, "kernel": kernel, "sequential_kernel": solo_kernel,
-           "ensemble_rate": members * rows * cols * steps / (statistics.median(times) * 1e3),
-           "sequential_rate": rows * cols * steps / (statistics.median(seq) / len(idx) * 1e3),
-           "bitcheck_member": idx[j], "bitcheck": bool(got.tobytes() == ref.tobytes()),
-           "bitcheck_max_abs_diff": float(np.max(np.abs(got.astype(np.float64) - ref)))}
-    out["speedup"] = out["ensemble_rate"] / out["sequential_rate"]
-    for s in solo:
-        for c in s.in_out():
-            c.destroy()
-    ens.destroy()
-    ctx.close()
-    return out
 
 
 def main(argv=None) -> int:
@@ -133,43 +37,25 @@ def main(argv=None) -> int:
     ap.add_argument("--md", default=None, help="also write the tables to this file")
     ap.add_argument("--json", default=None, help="append one JSON line per measurement to this file")
     args = ap.parse_args(argv)
-    grids = GRIDS if not args.grids else [tuple(int(x) for x in g.split("x")) for g in args.grids.split(",")]
-    lines = ["| grid | rule | kernel | Mcells x steps / s | / clipped | replay (simple kernel) |", "|---|---|---|---|---|---|"]
-    print("\n".join(lines), flush=True)
+    report = ratekit.Report(args.json, args.md, json_lines=True)
+    report.table("| grid | rule | kernel | Mcells x steps / s | / clipped | replay (simple kernel) |", "|---|---|---|---|---|---|")
     ok = True
-
-    def emit(line, rec):
-        lines.append(line)
-        print(line, flush=True)
-        if args.json:
-            with open(args.json, "a") as f:
-                f.write(json.dumps(rec) + "\n")
-
-    for rows, cols in grids:
-        base = None
-        todo = [(label, rule, 0) for label, rule in RULES]  # (label, gs_boundary, pinned gs_kernel)
-        i = 0
-        while i < len(todo):
-            label, rule, pin = todo[i]
-            i += 1
-            r = time_grid(rows, cols, rule, args.steps, args.calls, kernel=pin)
-            base = r["rate"] if (rule == 0 and pin == 0) else base
-            if rule == 0 and pin == 0 and not r["kernel"].startswith("tb-"):
-                todo.insert(i, ("clipped, kernel = TB", 0, 3))
+    for rows, cols in ratekit.parse_grids(args.grids or GRIDS):
+        for label, r, over_clipped in ratekit.rules_in_turn(RULES, lambda rule, pin: dict(
+                ratekit.timed_steps(rows, cols, args.steps, args.calls, boundary=rule, kernel=pin), boundary=rule)):
             ok = ok and r["proof"]
-            emit(f"| {rows} x {cols} | {label} | {r['kernel']} | {r['rate']:.0f} | {r['rate'] / base:.3f} | "
-                 f"{r['replay_steps']} steps: {'identical' if r['proof'] else 'DIFFERS'} |", r)
+            report.table(f"| {rows} x {cols} | {label} | {r['kernel']} | {r['rate']:.0f} | {over_clipped:.3f} | "
+                         f"{r['replay_steps']} steps: {'identical' if r['proof'] else 'DIFFERS'} |")
+            report.row(r)
     if not args.no_ensemble:
-        e = time_ensemble(512, 64, 128, args.steps, args.calls, args.sample)
+        e = ratekit.ensemble_against_sequential(512, 64, 128, args.steps, args.calls, args.sample, boundary=2)
         ok = ok and e["bitcheck"]
-        lines += ["", "| periodic ensemble | kernel | ensemble Mcells x steps / s | sequential Mcells x steps / s | speed-up | bit-check |",
-                  "|---|---|---|---|---|---|"]
-        print("\n".join(lines[-3:]), flush=True)
-        emit(f"| 512 x 64x128 | {e['kernel']} | {e['ensemble_rate']:.0f} | {e['sequential_rate']:.0f} ({e['sequential_kernel']}) | "
-             f"{e['speedup']:.1f}x | member {e['bitcheck_member']}: {'identical' if e['bitcheck'] else 'DIFFERS'} |", e)
-    if args.md:
-        with open(args.md, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        report.table("", "| periodic ensemble | kernel | ensemble Mcells x steps / s | sequential Mcells x steps / s | speed-up | bit-check |",
+                     "|---|---|---|---|---|---|")
+        report.table(f"| 512 x 64x128 | {e['kernel']} | {e['ensemble_rate']:.0f} | {e['sequential_rate']:.0f} ({e['sequential_kernel']}) | "
+                     f"{e['speedup']:.1f}x | member {e['bitcheck_member']}: {'identical' if e['bitcheck'] else 'DIFFERS'} |")
+        report.row(e)
+    report.finish()
     return 0 if ok else 1
 
 
