@@ -17,6 +17,7 @@ from .simulation import (  # noqa: F401
     HipConcentration,
     HipContext,
     ComponentList,
+    ComponentMatch,
     Components,
     Morphology,
     Parameters,
@@ -29,4 +30,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "Components", "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]

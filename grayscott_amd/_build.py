@@ -62,6 +62,9 @@ UNITS = [
     # component lists: one record per component behind that labelling (count, scan, write, gather launches; integer atomics):
     # the same float mode
     ("gs_component_list.hip", "gs_component_list_k.o", []),
+    # component matches: one overlap per piece that two labellings share (one launch behind the lists'; no atomics): the same
+    # float mode
+    ("gs_match.hip", "gs_match_k.o", []),
     # reduced result images (block averages in f64): the same float mode, a sub-normal pixel is kept
     ("gs_reduce.hip", "gs_reduce_k.o", []),
     # two planes compared (row records of |a - b| in f64, the ensembles' fold): the same float mode, sub-normal cells kept

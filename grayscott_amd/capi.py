@@ -54,6 +54,7 @@ EXPORTS = (
     "gs_fields_correlation", "gs_members_correlation",
     "gs_fields_components", "gs_members_components",
     "gs_field_component_list", "gs_members_component_list", "gs_component_list_view", "gs_component_list_destroy",
+    "gs_fields_match", "gs_members_match", "gs_component_match_view", "gs_component_match_destroy",
 )
 
 
@@ -178,6 +179,17 @@ class GsComponentRecord(ctypes.Structure):
     ]
 
 
+class GsComponentOverlap(ctypes.Structure):
+    """``gs_component_overlap`` (include/gs_hip.h): a before-record and an after-record of a ``gs_component_match`` that
+    share ``cells`` grid cells -- 16 bytes."""
+
+    _fields_ = [
+        ("before", ctypes.c_uint32),
+        ("after", ctypes.c_uint32),
+        ("cells", ctypes.c_uint64),
+    ]
+
+
 _lib = None
 
 
@@ -271,6 +283,10 @@ def load() -> ctypes.CDLL:
         "gs_members_component_list": (i32, [vp, vp, u64, u64, i32, f32, i32, i32, u64, P(vp)]),
         "gs_component_list_view": (i32, [vp, P(u64), P(P(u64)), P(P(GsComponentRecord))]),
         "gs_component_list_destroy": (i32, [vp]),
+        "gs_fields_match": (i32, [vp, vp, vp, f32, i32, i32, u64, P(vp)]),
+        "gs_members_match": (i32, [vp, vp, vp, u64, u64, i32, f32, i32, i32, u64, P(vp)]),
+        "gs_component_match_view": (i32, [vp, P(vp), P(vp), P(u64), P(P(u64)), P(P(GsComponentOverlap))]),
+        "gs_component_match_destroy": (i32, [vp]),
         "gs_fields_correlation": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(u64)]),
         "gs_members_correlation": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(u64)]),
     }

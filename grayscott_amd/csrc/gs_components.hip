@@ -27,7 +27,9 @@
 // value it is.
 //
 // The component lists (gs_component_list.hip) run the tile, border and flatten launches alone (gs_launch_component_labels) and
-// continue from parent[] and size[] on the same stream.
+// continue from parent[] and size[] on the same stream.  The match of two planes (gs_match.hip) labels a third time: the cells
+// set in both, read from the two label arrays (gs_launch_piece_labels: the tile kernel's BOTH form, then border and flatten as
+// they are).
 #include "gs_kernels.h"
 #include "gs_plane_scan.h"
 
@@ -43,17 +45,25 @@ static_assert(kCols == 256 && kRows % 4 == 0, "a lane holds four columns of a 25
 constexpr int kCounters = 35; // gs_components in u64 words: components, set_cells, largest, by_size[32]
 
 struct GsCompArgs {
-    const float *p;   // plane y at p + y * stride (no GsPlaneSet: it costs gs_comp_tile_k two waits, profiles/plane_scan_refactor.md)
+    union {
+        const float *p; // plane y at p + y * stride (no GsPlaneSet: it costs gs_comp_tile_k two waits, profiles/plane_scan_refactor.md)
+        const uint32_t *both_b; // gs_comp_tile_k's BOTH form reads two label arrays in place of the plane, t and flip: the first
+    };
     int64_t stride, pitch, rows, planes;
     int32_t cols;
     float t;          // the threshold and ...
     uint32_t flip;    // ... the sign flip of gs_is_set
     int32_t eight;    // 8-connectivity
     uint32_t *parent, *size;
-    unsigned long long *out; // [planes][kCounters], zeroed by the caller
+    union {
+        unsigned long long *out; // [planes][kCounters], zeroed by the caller (the tally alone)
+        const uint32_t *both_a;  // the BOTH form's second label array: the pieces are never tallied, and the struct keeps its size
+    };
 };
 
-template <bool VEC>
+// BOTH: the source is not a plane but two label arrays of the same dense layout as parent[] -- a cell is set where both hold
+// a label (gs_match.hip: the pieces that two planes' components share).
+template <bool VEC, bool BOTH = false>
 __global__ __launch_bounds__(256) void gs_comp_tile_k(GsCompArgs a)
 {
     __shared__ uint32_t lab[kRows * kCols];
@@ -75,9 +85,18 @@ __global__ __launch_bounds__(256) void gs_comp_tile_k(GsCompArgs a)
         const int lr = wave + 4 * i;
         const int64_t r = r0 + lr;
         const float *row = plane + (r < rows ? r : rows - 1) * a.pitch; // (an address that exists; masked below)
-        const float4 x = gs_load_columns<VEC>(row, at);
-        unsigned m = (gs_is_set(x.x, a.flip, a.t) ? 1u : 0u) | (gs_is_set(x.y, a.flip, a.t) ? 2u : 0u) |
-                     (gs_is_set(x.z, a.flip, a.t) ? 4u : 0u) | (gs_is_set(x.w, a.flip, a.t) ? 8u : 0u);
+        unsigned m;
+        if constexpr (BOTH) {
+            const uint64_t e = ((uint64_t)y * (uint64_t)rows + (uint64_t)(r < rows ? r : rows - 1)) * (uint64_t)cols + (uint64_t)c;
+            m = 0u;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) // (own: an entry past the row's end belongs to the next row, or to nobody)
+                if (((own >> k) & 1u) && a.both_b[e + k] != kUfUnset && a.both_a[e + k] != kUfUnset) m |= 1u << k;
+        } else {
+            const float4 x = gs_load_columns<VEC>(row, at);
+            m = (gs_is_set(x.x, a.flip, a.t) ? 1u : 0u) | (gs_is_set(x.y, a.flip, a.t) ? 2u : 0u) |
+                (gs_is_set(x.z, a.flip, a.t) ? 4u : 0u) | (gs_is_set(x.w, a.flip, a.t) ? 8u : 0u);
+        }
         m &= r < rows ? own : 0u;
         // the run that reaches the lane's column 0 from the left: the lanes below this one that are full (all four set) up
         // to lane j, the nearest that is not; it begins in lane j if that one's column 3 is set, else in lane j + 1
@@ -255,7 +274,7 @@ __global__ __launch_bounds__(256) void gs_comp_seam_k(GsCompArgs a, uint32_t *se
 // first cell in row-major order (kUfUnset: the cell is not set), and size[root] the component's cells.
 static hipError_t launch_labels(GsCompArgs &a, const float *plane, int64_t planes, int64_t stride, int64_t pitch, int64_t rows,
                                 int32_t cols, float threshold, int32_t sense, int32_t connectivity, uint32_t *parent,
-                                uint32_t *size, hipStream_t s)
+                                uint32_t *size, hipStream_t s, const uint32_t *both_b = nullptr, const uint32_t *both_a = nullptr)
 {
     const uint64_t total = (uint64_t)planes * (uint64_t)rows * (uint64_t)cols;
     if (total >= (1ull << 32)) return hipErrorInvalidValue;
@@ -266,15 +285,18 @@ static hipError_t launch_labels(GsCompArgs &a, const float *plane, int64_t plane
     a.rows = rows;
     a.planes = planes;
     a.cols = cols;
-    const bool vec = gs_reads_16_bytes(&plane, 1, planes, stride, pitch);
+    const bool vec = !both_b && gs_reads_16_bytes(&plane, 1, planes, stride, pitch);
     gs_set_rule(threshold, sense, a.t, a.flip);
     a.eight = connectivity == 8 ? 1 : 0;
     a.parent = parent;
     a.size = size;
+    if (both_b) a.both_b = both_b, a.both_a = both_a;
 
     const int64_t tiles = (((int64_t)cols + kCols - 1) / kCols) * ((rows + kRows - 1) / kRows) * planes;
     if (tiles > INT32_MAX) return hipErrorInvalidValue;
-    if (vec)
+    if (both_b)
+        hipLaunchKernelGGL((gs_comp_tile_k<false, true>), dim3((unsigned)tiles), dim3(256), 0, s, a);
+    else if (vec)
         hipLaunchKernelGGL((gs_comp_tile_k<true>), dim3((unsigned)tiles), dim3(256), 0, s, a);
     else
         hipLaunchKernelGGL((gs_comp_tile_k<false>), dim3((unsigned)tiles), dim3(256), 0, s, a);
@@ -296,6 +318,16 @@ hipError_t gs_launch_component_labels(const float *plane, int64_t planes, int64_
     if (rows <= 0 || cols <= 0) return hipSuccess;
     GsCompArgs a;
     const hipError_t e = launch_labels(a, plane, planes, stride, pitch, rows, cols, threshold, sense, connectivity, parent, size, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+
+hipError_t gs_launch_piece_labels(const uint32_t *both_b, const uint32_t *both_a, int64_t planes, int64_t rows, int32_t cols,
+                                  int32_t connectivity, uint32_t *parent, uint32_t *size, hipStream_t s)
+{
+    if (planes < 1 || (connectivity != 4 && connectivity != 8) || !both_b || !both_a) return hipErrorInvalidValue;
+    if (rows <= 0 || cols <= 0) return hipSuccess;
+    GsCompArgs a;
+    const hipError_t e = launch_labels(a, nullptr, planes, 0, 0, rows, cols, 0.0f, 1, connectivity, parent, size, s, both_b, both_a);
     return e != hipSuccess ? e : hipGetLastError();
 }
 

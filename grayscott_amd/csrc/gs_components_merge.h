@@ -14,7 +14,10 @@
 // already global, and for its first and its last row the index of every cell's record (kCompUnset for an unset cell) -- a slab
 // of a chain lists every component that touches either row, whatever its size.  Records united across the seams become one:
 // sizes and sums added, the boxes united, the first cell the smallest in row-major order.  min_size is applied to what the
-// unions leave, and the result is in ascending order of the first cell.
+// unions leave, and the result is in ascending order of the first cell.  With `where` (the match of two planes,
+// gs_match_merge.h) the caller also learns what became of every record handed in: where[base(s) + k] is the index in the
+// result of slab s's record k -- base(s) the number of records of the slabs before s -- or kCompUnset if the merged record
+// fell below min_size.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -117,7 +120,8 @@ inline bool comp_first_cell_before(const gs_component_record &a, const gs_compon
 // The slabs in ascending global row order; none is empty.  part[s]: slab s's records, n[s] of them.  connectivity: 4 or 8.
 inline std::vector<gs_component_record> merge_component_lists(const gs_component_record *const *part, const size_t *n,
                                                               const ListSeamRows *seam, size_t nslab, size_t cols,
-                                                              int connectivity, uint64_t min_size)
+                                                              int connectivity, uint64_t min_size,
+                                                              std::vector<uint32_t> *where = nullptr)
 {
     std::vector<size_t> base(nslab + 1, 0);
     for (size_t s = 0; s < nslab; ++s) base[s + 1] = base[s] + n[s];
@@ -162,6 +166,14 @@ inline std::vector<gs_component_record> merge_component_lists(const gs_component
         if (up[i] == i && all[i].size >= min_size) out.push_back(all[i]);
     // (every slab's records come in first-cell order and the slabs in row order: only merged records can be out of place)
     if (!std::is_sorted(out.begin(), out.end(), comp_first_cell_before)) std::sort(out.begin(), out.end(), comp_first_cell_before);
+    if (where) { // first cells are distinct: a kept root is found again by its own
+        where->assign(all.size(), kCompUnset);
+        for (size_t i = 0; i < all.size(); ++i) {
+            const gs_component_record &root = all[find(i)];
+            if (root.size < min_size) continue;
+            (*where)[i] = (uint32_t)(std::lower_bound(out.begin(), out.end(), root, comp_first_cell_before) - out.begin());
+        }
+    }
     return out;
 }
 

@@ -333,3 +333,20 @@ hipError_t gs_launch_list_count(const uint32_t *parent, uint32_t *size, int64_t 
                                 const GsListWork &w, hipStream_t s);
 hipError_t gs_launch_list_fill(const uint32_t *parent, uint32_t *size, int64_t planes, int64_t rows, int32_t cols, uint64_t min_size,
                                const GsListWork &w, GsComponentRecord *records, uint32_t *seams, hipStream_t s);
+
+// Component matching (gs_match.hip; include/gs_hip.h: gs_fields_match).  gs_launch_piece_labels (gs_components.hip) labels the
+// cells that are set in BOTH of two label arrays -- the parent arrays of two labellings of planes of one shape, dense entries,
+// 0xffffffff for an unset cell -- exactly as gs_launch_component_labels labels a thresholded plane: the tile kernel reads the
+// two arrays in place of a plane, border and flatten run as they are.  gs_launch_match_pairs, behind the pieces' count and
+// scan (gs_launch_list_count with min_size 1, which leaves `counts`) and behind both lists' fill (index_*[root] = the root's
+// record index, 0xffffffff: not listed), writes one overlap per piece, in ascending order of the pieces' first cells:
+// (before, after) = the record indices of the two components the piece lies in, both 0xffffffff where either is not listed.
+struct GsMatchOverlap { // gs_component_overlap's layout
+    uint32_t before, after;
+    uint64_t cells;
+};
+hipError_t gs_launch_piece_labels(const uint32_t *both_b, const uint32_t *both_a, int64_t planes, int64_t rows, int32_t cols,
+                                  int32_t connectivity, uint32_t *parent, uint32_t *size, hipStream_t s);
+hipError_t gs_launch_match_pairs(const uint32_t *parent_b, const uint32_t *index_b, const uint32_t *parent_a, const uint32_t *index_a,
+                                 const uint32_t *parent_p, const uint32_t *size_p, const uint32_t *counts, int64_t planes,
+                                 int64_t rows, int32_t cols, GsMatchOverlap *overlaps, hipStream_t s);

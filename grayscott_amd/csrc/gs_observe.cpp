@@ -2,8 +2,8 @@
 // (include/gs_hip.h): summaries (gs_fields_summarize, gs_members_summarize), histograms (gs_fields_histogram,
 // gs_members_histogram), bit-quad counts (gs_fields_morphology, gs_members_morphology), two-point pair counts
 // (gs_fields_correlation, gs_members_correlation), connected components (gs_fields_components, gs_members_components) and
-// component lists (gs_field_component_list, gs_members_component_list) and comparisons of two states (gs_fields_compare,
-// gs_members_compare).  All observe a field list with launches per slab on its
+// component lists (gs_field_component_list, gs_members_component_list), component matches of two states (gs_fields_match,
+// gs_members_match) and comparisons of two states (gs_fields_compare, gs_members_compare).  All observe a field list with launches per slab on its
 // compute stream into that slab's scratch buffer, fetch what the launches left and combine it here on the host, after the
 // results of every slab -- and, in a multi-process context, of every rank (exchange) -- have met; an ensemble's members are
 // observed in one launch on slab 0.  Two shapes of result, each with one path:
@@ -25,12 +25,16 @@
 //   component lists  the same labelling, then one record per component formed behind it (gs_component_list.hip) in record
 //               memory that lives for the call alone; the records and the record indices of every slab's first and last row
 //               meet on the host, which joins what crosses the seams (gs_components_merge.h).  Single-process contexts only.
+//   component matches  both planes labelled and listed as above, each in label memory of its own, then the pieces they share
+//               labelled from the two label arrays and one overlap written per piece (gs_match.hip); the host makes the
+//               indices global and adds the cells of equal pairs (gs_match_merge.h).  Single-process contexts only.
 //   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
 //               (row_records); ensembles fold on the device (gs_change_fold_k).
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
 #include "gs_components_merge.h"
+#include "gs_match_merge.h"
 
 #include <memory>
 
@@ -41,6 +45,13 @@ struct gs_component_list {
     uint64_t planes = 0;
     std::vector<uint64_t> offsets; // planes + 1
     std::vector<gs_component_record> records;
+};
+
+// What gs_fields_match and gs_members_match return: the two lists and the overlaps, host memory as a list is.
+struct gs_component_match {
+    gs_component_list before, after;
+    std::vector<uint64_t> offsets; // planes + 1
+    std::vector<gs_component_overlap> overlaps;
 };
 
 namespace gsi {
@@ -515,11 +526,11 @@ bool list_sums_could_wrap(uint64_t rows, uint64_t cols)
     return ((cells * rows) >> 64) != 0 || ((cells * cols) >> 64) != 0;
 }
 
-int32_t refuse_world(const gs_ctx *ctx)
+int32_t refuse_world(const gs_ctx *ctx, const char *what = "component lists")
 {
     if (ctx->world > 1)
-        return fail(GS_ERR_UNSUPPORTED, "component lists in a multi-process context (%d processes): the ranks' record lists are "
-                                        "not exchanged", ctx->world);
+        return fail(GS_ERR_UNSUPPORTED, "%s in a multi-process context (%d processes): the ranks' record lists are "
+                                        "not exchanged", what, ctx->world);
     return GS_OK;
 }
 
@@ -537,19 +548,26 @@ struct RecordMemory {
             if (b.p && hipSetDevice(b.device) == hipSuccess) (void)hipFree(b.p);
         blocks.clear();
     }
-    int32_t add(int device, uint64_t records, GsComponentRecord **out)
+    int32_t add_bytes(int device, uint64_t bytes, const char *what, void **out)
     {
         GS_HIP(hipSetDevice(device));
         void *p = nullptr;
-        const hipError_t e = hipMalloc(&p, (size_t)records * sizeof(GsComponentRecord));
+        const hipError_t e = hipMalloc(&p, (size_t)bytes);
         if (e != hipSuccess) {
             (void)hipGetLastError();
-            return fail(GS_ERR_NOMEM, "record memory of %llu bytes: %s", (unsigned long long)records * sizeof(GsComponentRecord),
-                        hipGetErrorString(e));
+            return fail(GS_ERR_NOMEM, "%s memory of %llu bytes: %s", what, (unsigned long long)bytes, hipGetErrorString(e));
         }
         blocks.push_back(Block{device, p});
-        *out = static_cast<GsComponentRecord *>(p);
+        *out = p;
         return GS_OK;
+    }
+    int32_t add(int device, uint64_t records, GsComponentRecord **out)
+    {
+        return add_bytes(device, records * sizeof(GsComponentRecord), "record", reinterpret_cast<void **>(out));
+    }
+    int32_t add(int device, uint64_t pieces, GsMatchOverlap **out) // (a match's overlaps: one per piece)
+    {
+        return add_bytes(device, pieces * sizeof(GsMatchOverlap), "overlap", reinterpret_cast<void **>(out));
     }
 };
 
@@ -562,6 +580,20 @@ GsListWork list_work(void *scratch, uint32_t *marks)
     return GsListWork{marks, w + 4, w};
 }
 uint32_t *list_seams(void *scratch, uint64_t entries) { return static_cast<uint32_t *>(scratch) + 4 + gs_list_groups(entries); }
+
+// ---- component matches -------------------------------------------------------------------------------------------------
+static_assert(sizeof(gs_component_overlap) == 16 && sizeof(GsMatchOverlap) == 16 && offsetof(gs_component_overlap, after) == 4 &&
+                  offsetof(GsMatchOverlap, after) == 4 && offsetof(gs_component_overlap, cells) == 8 &&
+                  offsetof(GsMatchOverlap, cells) == 8,
+              "gs_component_overlap layout");
+
+// A match's work memory in a slab's (or batch's) scratch buffer: three lists' work memories one after the other -- before,
+// after, the pieces.
+size_t match_work_bytes(uint64_t entries, size_t cols) { return 3 * list_work_bytes(entries, cols); }
+void *match_work(void *scratch, uint64_t entries, size_t cols, int k)
+{
+    return static_cast<unsigned char *>(scratch) + (size_t)k * list_work_bytes(entries, cols);
+}
 
 } // namespace
 
@@ -1133,6 +1165,278 @@ int32_t gs_component_list_view(const gs_component_list *list, uint64_t *planes, 
 int32_t gs_component_list_destroy(gs_component_list *list)
 {
     delete list;
+    return GS_OK;
+}
+
+int32_t gs_fields_match(gs_ctx *ctx, gs_field *before, gs_field *after, float threshold, int32_t above, int32_t connectivity,
+                        uint64_t min_size, gs_component_match **out)
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_list_rule(threshold, connectivity, min_size)); // before any handle is looked at
+    if (!before || before->ctx != ctx || !after || after->ctx != ctx) return fail(GS_ERR_INVALID, "field: null or of another context");
+    GS_TRY(same_shape(before, after));
+    GS_TRY(refuse_world(ctx, "component matches")); // every rank alone, before anything is allocated or sent
+    GS_TRY(sync_all(ctx));
+    std::unique_ptr<gs_component_match> match(new (std::nothrow) gs_component_match);
+    if (!match) return fail(GS_ERR_NOMEM, "a component match");
+    gs_field *const side[2] = {before, after};
+    gs_component_list *const lists[2] = {&match->before, &match->after};
+    for (gs_component_list *l : lists) {
+        l->planes = 1;
+        l->offsets.assign(2, (uint64_t)0);
+    }
+    match->offsets.assign(2, (uint64_t)0);
+    const gs_field *f = before;
+    if (f->rows == 0 || f->cols == 0) {
+        *out = match.release();
+        return GS_OK;
+    }
+    if (list_sums_could_wrap(f->rows, f->cols))
+        return fail(GS_ERR_UNSUPPORTED, "a grid of %llu x %llu cells: a sum of row or column indices could pass 2^64",
+                    (unsigned long long)f->rows, (unsigned long long)f->cols);
+    const size_t nslab = ctx->slabs.size(), cols = (size_t)f->cols;
+    for (size_t i = 0; i < nslab; ++i)
+        if ((uint64_t)f->s[i].rows * (uint64_t)cols >= ((uint64_t)1 << 32))
+            return fail(GS_ERR_UNSUPPORTED, "slab %zu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab", i,
+                        (unsigned long long)f->s[i].rows, (unsigned long long)cols);
+    const bool chain = nslab > 1;
+    // label memory: 0 before, 1 after, 2 the pieces (no marks: a piece is listed whatever its size)
+    LabelMemory labels[3];
+    for (size_t i = 0; i < nslab; ++i) {
+        const uint64_t cells = (uint64_t)f->s[i].rows * (uint64_t)cols;
+        for (int k = 0; k < 3; ++k) GS_TRY(labels[k].add(ctx->slabs[i].device, cells, chain && k < 2 ? (cells + 31) / 32 : 0));
+        GS_TRY(ensure_scratch(ctx, (int)i, match_work_bytes(cells, cols), "component match"));
+    }
+    std::vector<uint32_t> selected(3 * nslab, 0u);
+    for (size_t i = 0; i < nslab; ++i) {
+        if (f->s[i].rows == 0) continue;
+        SlabRt &sl = ctx->slabs[i];
+        const int64_t rows = (int64_t)f->s[i].rows;
+        const uint64_t cells = (uint64_t)rows * (uint64_t)cols;
+        GS_HIP(hipSetDevice(sl.device));
+        for (int k = 0; k < 3; ++k) {
+            const LabelMemory::Block &lb = labels[k].blocks[i];
+            if (k < 2)
+                GS_HIP(gs_launch_component_labels(side[k]->s[i].row0, 1, 0, side[k]->pitch, rows, (int32_t)cols, threshold, above,
+                                                  connectivity, lb.parent, lb.size, sl.compute));
+            else
+                GS_HIP(gs_launch_piece_labels(labels[0].blocks[i].parent, labels[1].blocks[i].parent, 1, rows, (int32_t)cols,
+                                              connectivity, lb.parent, lb.size, sl.compute));
+            const GsListWork work = list_work(match_work(sl.scratch, cells, cols, k), lb.marks);
+            GS_HIP(gs_launch_list_count(lb.parent, lb.size, 1, rows, (int32_t)cols, k < 2 ? min_size : 1, work, sl.compute));
+            GS_HIP(hipMemcpyAsync(&selected[3 * i + (size_t)k], work.selected, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+        }
+    }
+    GS_TRY(sync_compute(ctx)); // the one read-back: record and overlap memory are sized exactly
+    RecordMemory memory; // (the records and the overlaps)
+    std::vector<std::vector<gs_component_record>> part[2];
+    std::vector<std::vector<uint32_t>> seam[2];
+    std::vector<std::vector<gs_component_overlap>> raw(nslab);
+    for (int k = 0; k < 2; ++k) part[k].resize(nslab), seam[k].resize(nslab);
+    for (size_t i = 0; i < nslab; ++i) {
+        if (f->s[i].rows == 0) continue;
+        SlabRt &sl = ctx->slabs[i];
+        const int64_t rows = (int64_t)f->s[i].rows;
+        const uint64_t cells = (uint64_t)rows * (uint64_t)cols;
+        GS_HIP(hipSetDevice(sl.device));
+        for (int k = 0; k < 2; ++k) {
+            if (chain) seam[k][i].assign(2 * cols, kCompUnset);
+            const uint32_t n = selected[3 * i + (size_t)k];
+            if (n == 0) continue; // (no set cell in its first or last row either)
+            const LabelMemory::Block &lb = labels[k].blocks[i];
+            void *w = match_work(sl.scratch, cells, cols, k);
+            GsComponentRecord *records = nullptr;
+            GS_TRY(memory.add(sl.device, n, &records));
+            part[k][i].resize(n);
+            uint32_t *seams = chain ? list_seams(w, cells) : nullptr;
+            GS_HIP(gs_launch_list_fill(lb.parent, lb.size, 1, rows, (int32_t)cols, min_size, list_work(w, lb.marks), records, seams,
+                                       sl.compute));
+            GS_HIP(hipMemcpyAsync(part[k][i].data(), records, (size_t)n * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
+            if (chain) GS_HIP(hipMemcpyAsync(seam[k][i].data(), seams, 2 * cols * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+        }
+        // a piece names records only where both lists have some: otherwise every piece of the slab is dropped
+        const uint32_t np = selected[3 * i + 2];
+        if (np == 0 || selected[3 * i] == 0 || selected[3 * i + 1] == 0) continue;
+        GsMatchOverlap *dev = nullptr;
+        GS_TRY(memory.add(sl.device, np, &dev));
+        raw[i].resize(np);
+        const GsListWork work = list_work(match_work(sl.scratch, cells, cols, 2), nullptr);
+        GS_HIP(gs_launch_match_pairs(labels[0].blocks[i].parent, labels[0].blocks[i].size, labels[1].blocks[i].parent,
+                                     labels[1].blocks[i].size, labels[2].blocks[i].parent, labels[2].blocks[i].size, work.counts, 1,
+                                     rows, (int32_t)cols, dev, sl.compute));
+        GS_HIP(hipMemcpyAsync(raw[i].data(), dev, (size_t)np * sizeof(gs_component_overlap), hipMemcpyDeviceToHost, sl.compute));
+    }
+    GS_TRY(sync_compute(ctx));
+    std::vector<uint32_t> where[2];
+    for (int k = 0; k < 2; ++k) {
+        // local rows to rows of the global grid
+        for (size_t i = 0; i < nslab; ++i) {
+            const uint64_t g = f->s[i].g_row0;
+            for (gs_component_record &r : part[k][i]) {
+                r.first_row += (uint32_t)g;
+                r.row_min += (uint32_t)g;
+                r.row_max += (uint32_t)g;
+                r.sum_row += r.size * g;
+            }
+        }
+        if (!chain) {
+            lists[k]->records.swap(part[k][0]);
+        } else {
+            std::vector<const gs_component_record *> recs;
+            std::vector<size_t> counts;
+            std::vector<ListSeamRows> rows;
+            for (size_t i = 0; i < nslab; ++i) {
+                if (f->s[i].rows == 0) continue;
+                recs.push_back(part[k][i].data());
+                counts.push_back(part[k][i].size());
+                rows.push_back(ListSeamRows{seam[k][i].data(), seam[k][i].data() + cols});
+            }
+            lists[k]->records =
+                merge_component_lists(recs.data(), counts.data(), rows.data(), recs.size(), cols, connectivity, min_size, &where[k]);
+        }
+        lists[k]->offsets[1] = lists[k]->records.size();
+    }
+    // slab-local record indices to those of the two lists; then one overlap per pair
+    std::vector<gs_component_overlap> all;
+    int64_t base[2] = {0, 0};
+    for (size_t i = 0; i < nslab; ++i) {
+        if (chain)
+            map_overlaps(raw[i].data(), raw[i].size(), where[0].data(), base[0], where[1].data(), base[1]);
+        all.insert(all.end(), raw[i].begin(), raw[i].end());
+        for (int k = 0; k < 2; ++k) base[k] += (int64_t)selected[3 * i + (size_t)k];
+    }
+    match->overlaps = fold_overlaps(all.data(), all.size());
+    match->offsets[1] = match->overlaps.size();
+    *out = match.release();
+    return GS_OK;
+}
+
+int32_t gs_members_match(gs_ctx *ctx, gs_ensemble *before, gs_ensemble *after, uint64_t first, uint64_t count, int32_t species,
+                         float threshold, int32_t above, int32_t connectivity, uint64_t min_size, gs_component_match **out)
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_list_rule(threshold, connectivity, min_size)); // before the ensembles are looked at
+    if (species < 0 || species > 1) return fail(GS_ERR_INVALID, "species %d (0 = U, 1 = V)", species);
+    if (before && after && before->ctx == ctx && after->ctx == ctx) GS_TRY(refuse_world(ctx, "component matches")); // (before check_members waits)
+    GS_TRY(check_members(ctx, after, first, count, before, true));
+    std::unique_ptr<gs_component_match> match(new (std::nothrow) gs_component_match);
+    if (!match) return fail(GS_ERR_NOMEM, "a component match");
+    const gs_ensemble *const side[2] = {before, after};
+    gs_component_list *const lists[2] = {&match->before, &match->after};
+    for (gs_component_list *l : lists) {
+        l->planes = count;
+        l->offsets.assign((size_t)count + 1, (uint64_t)0);
+    }
+    match->offsets.assign((size_t)count + 1, (uint64_t)0);
+    const gs_ensemble *e = after;
+    const uint64_t cells = e->rows * e->cols;
+    if (cells == 0 || count == 0) {
+        *out = match.release();
+        return GS_OK;
+    }
+    if (cells >= ((uint64_t)1 << 32))
+        return fail(GS_ERR_UNSUPPORTED, "a member holds %llu cells: labels are 32-bit, fewer than 2^32 cells", (unsigned long long)cells);
+    if (list_sums_could_wrap(e->rows, e->cols))
+        return fail(GS_ERR_UNSUPPORTED, "members of %llu x %llu cells: a sum of row or column indices could pass 2^64",
+                    (unsigned long long)e->rows, (unsigned long long)e->cols);
+    // batches of whole members, as gs_members_component_list takes them: each of the three labellings within the budget
+    uint64_t batch = (uint64_t)GS_COMPONENTS_BATCH_BYTES / 8 / cells;
+    batch = batch < 1 ? 1 : (batch > count ? count : batch);
+    SlabRt &sl = ctx->slabs[0];
+    LabelMemory labels; // blocks 0 before, 1 after, 2 the pieces
+    for (int k = 0; k < 3; ++k) GS_TRY(labels.add(sl.device, batch * cells));
+    GS_TRY(ensure_scratch(ctx, 0, match_work_bytes(batch * cells, 0), "component match"));
+    GS_HIP(hipSetDevice(sl.device));
+    const int64_t rows = (int64_t)e->rows;
+    const int32_t cols = (int32_t)e->cols;
+    std::vector<gs_component_record> host;
+    std::vector<gs_component_overlap> raw;
+    std::vector<uint64_t> local[2]; // the records of the batch's planes before plane p, per list
+    for (uint64_t b0 = 0; b0 < count; b0 += batch) {
+        const uint64_t nb = count - b0 < batch ? count - b0 : batch;
+        uint32_t selected[3] = {0u, 0u, 0u};
+        GsListWork work[3];
+        for (int k = 0; k < 3; ++k) {
+            const LabelMemory::Block &lb = labels.blocks[(size_t)k];
+            work[k] = list_work(match_work(sl.scratch, batch * cells, 0, k), nullptr);
+            if (k < 2) {
+                // each member a plane of its own, `cells` floats from one to the next: it never sees its neighbours' rows
+                const gs_ensemble *m = side[k];
+                const float *plane = (species ? m->v[m->cur] : m->u[m->cur]) + (first + b0) * cells;
+                GS_HIP(gs_launch_component_labels(plane, (int64_t)nb, (int64_t)cells, (int64_t)cols, rows, cols, threshold, above,
+                                                  connectivity, lb.parent, lb.size, sl.compute));
+            } else {
+                GS_HIP(gs_launch_piece_labels(labels.blocks[0].parent, labels.blocks[1].parent, (int64_t)nb, rows, cols, connectivity,
+                                              lb.parent, lb.size, sl.compute));
+            }
+            GS_HIP(gs_launch_list_count(lb.parent, lb.size, (int64_t)nb, rows, cols, k < 2 ? min_size : 1, work[k], sl.compute));
+            GS_HIP(hipMemcpyAsync(&selected[k], work[k].selected, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+        }
+        GS_HIP(hipStreamSynchronize(sl.compute));
+        RecordMemory memory; // (of this batch: the records and the overlaps)
+        for (int k = 0; k < 2; ++k) {
+            local[k].assign((size_t)nb + 1, (uint64_t)0);
+            if (selected[k] == 0) continue;
+            const LabelMemory::Block &lb = labels.blocks[(size_t)k];
+            GsComponentRecord *records = nullptr;
+            GS_TRY(memory.add(sl.device, selected[k], &records));
+            host.resize(selected[k]);
+            GS_HIP(gs_launch_list_fill(lb.parent, lb.size, (int64_t)nb, rows, cols, min_size, work[k], records, nullptr, sl.compute));
+            GS_HIP(hipMemcpyAsync(host.data(), records, host.size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
+            GS_HIP(hipStreamSynchronize(sl.compute));
+            // the records come in first-cell order over the batch's planes, one after the other: a record's plane follows from its root
+            for (gs_component_record &r : host) {
+                const uint64_t plane_of = r.first_row / e->rows;
+                r.first_row = (uint32_t)(r.first_row % e->rows);
+                lists[k]->offsets[(size_t)(b0 + plane_of) + 1] += 1;
+                local[k][(size_t)plane_of + 1] += 1;
+            }
+            for (size_t p = 0; p < (size_t)nb; ++p) local[k][p + 1] += local[k][p];
+            lists[k]->records.insert(lists[k]->records.end(), host.begin(), host.end());
+        }
+        if (selected[2] == 0 || selected[0] == 0 || selected[1] == 0) continue; // (no piece names a record)
+        GsMatchOverlap *dev = nullptr;
+        GS_TRY(memory.add(sl.device, selected[2], &dev));
+        raw.resize(selected[2]);
+        GS_HIP(gs_launch_match_pairs(labels.blocks[0].parent, labels.blocks[0].size, labels.blocks[1].parent, labels.blocks[1].size,
+                                     labels.blocks[2].parent, labels.blocks[2].size, work[2].counts, (int64_t)nb, rows, cols, dev,
+                                     sl.compute));
+        GS_HIP(hipMemcpyAsync(raw.data(), dev, raw.size() * sizeof(gs_component_overlap), hipMemcpyDeviceToHost, sl.compute));
+        GS_HIP(hipStreamSynchronize(sl.compute));
+        // the pieces come in first-cell order, so plane after plane; a kept piece's plane is that of its before-record
+        size_t at = 0;
+        for (size_t p = 0; p < (size_t)nb; ++p) {
+            const size_t from = at;
+            while (at < raw.size() && (raw[at].before == kCompUnset || raw[at].before < local[0][p + 1])) ++at;
+            map_overlaps(raw.data() + from, at - from, nullptr, (int64_t)local[0][p], nullptr, (int64_t)local[1][p]);
+            const std::vector<gs_component_overlap> folded = fold_overlaps(raw.data() + from, at - from);
+            match->overlaps.insert(match->overlaps.end(), folded.begin(), folded.end());
+            match->offsets[(size_t)b0 + p + 1] += folded.size();
+        }
+    }
+    for (size_t i = 0; i < (size_t)count; ++i) {
+        for (gs_component_list *l : lists) l->offsets[i + 1] += l->offsets[i];
+        match->offsets[i + 1] += match->offsets[i];
+    }
+    *out = match.release();
+    return GS_OK;
+}
+
+int32_t gs_component_match_view(const gs_component_match *match, const gs_component_list **before, const gs_component_list **after,
+                                uint64_t *planes, const uint64_t **offsets, const gs_component_overlap **overlaps)
+{
+    if (!match || !before || !after || !planes || !offsets || !overlaps) return fail(GS_ERR_INVALID, "null argument");
+    *before = &match->before;
+    *after = &match->after;
+    *planes = match->before.planes;
+    *offsets = match->offsets.data();
+    *overlaps = match->overlaps.data();
+    return GS_OK;
+}
+
+int32_t gs_component_match_destroy(gs_component_match *match)
+{
+    delete match;
     return GS_OK;
 }
 

@@ -629,22 +629,33 @@ def _species_plane(species: str, u, v):
     return u if species == "u" else v
 
 
-def _component_lists(lib, handle, shape, threshold, above, connectivity, min_size) -> List[ComponentList]:
-    """The planes of a ``gs_component_list`` copied out; the handle is destroyed at once."""
-    try:
-        planes, offsets = ctypes.c_uint64(0), ctypes.POINTER(ctypes.c_uint64)()
-        records = ctypes.POINTER(capi.GsComponentRecord)()
-        capi.check(lib.gs_component_list_view(handle, ctypes.byref(planes), ctypes.byref(offsets), ctypes.byref(records)))
-        off = np.ctypeslib.as_array(offsets, shape=(planes.value + 1,)).astype(np.int64) if planes.value else np.zeros(1, np.int64)
-        n = int(off[-1])
-        rec = np.zeros(n, COMPONENT_RECORD_DTYPE)
-        if n:
-            ctypes.memmove(rec.ctypes.data, records, n * COMPONENT_RECORD_DTYPE.itemsize)
-    finally:
-        lib.gs_component_list_destroy(handle)
+def _copy_planes(planes, offsets, items, dtype) -> Tuple[np.ndarray, np.ndarray]:
+    """(offsets as int64, the items as a structured array of ``dtype``) of a list's or a match's view, copied out."""
+    off = np.ctypeslib.as_array(offsets, shape=(planes.value + 1,)).astype(np.int64) if planes.value else np.zeros(1, np.int64)
+    n = int(off[-1])
+    out = np.zeros(n, dtype)
+    if n:
+        ctypes.memmove(out.ctypes.data, items, n * dtype.itemsize)
+    return off, out
+
+
+def _copy_lists(lib, handle, shape, threshold, above, connectivity, min_size) -> List[ComponentList]:
+    """The planes of a ``gs_component_list`` copied out; the handle stays the caller's."""
+    planes, offsets = ctypes.c_uint64(0), ctypes.POINTER(ctypes.c_uint64)()
+    records = ctypes.POINTER(capi.GsComponentRecord)()
+    capi.check(lib.gs_component_list_view(handle, ctypes.byref(planes), ctypes.byref(offsets), ctypes.byref(records)))
+    off, rec = _copy_planes(planes, offsets, records, COMPONENT_RECORD_DTYPE)
     thr = float(np.float32(threshold))
     return [ComponentList(rec[off[i]:off[i + 1]].copy(), int(shape[0]), int(shape[1]), thr, bool(above), int(connectivity),
                           int(min_size)) for i in range(planes.value)]
+
+
+def _component_lists(lib, handle, shape, threshold, above, connectivity, min_size) -> List[ComponentList]:
+    """The planes of a ``gs_component_list`` copied out; the handle is destroyed at once."""
+    try:
+        return _copy_lists(lib, handle, shape, threshold, above, connectivity, min_size)
+    finally:
+        lib.gs_component_list_destroy(handle)
 
 
 def component_list_field(context: "HipContext", field: "HipConcentration", threshold: float, above: bool = True,
@@ -656,6 +667,97 @@ def component_list_field(context: "HipContext", field: "HipConcentration", thres
     capi.check(context._lib.gs_field_component_list(context.handle, field.handle, float(threshold), 1 if above else 0,
                                                     int(connectivity), int(min_size), ctypes.byref(h)))
     return _component_lists(context._lib, h, field.shape(), threshold, above, connectivity, min_size)[0]
+
+
+COMPONENT_OVERLAP_DTYPE = np.dtype([("before", np.uint32), ("after", np.uint32), ("cells", np.uint64)])  # gs_component_overlap
+
+
+@dataclass(frozen=True, eq=False)
+class ComponentMatch:
+    """What became of the components of one thresholded plane between two states, formed on the device (``gs_fields_match``;
+    the rule is include/gs_hip.h's, that of ``ComponentList``): ``before`` and ``after`` are the two states' component lists
+    and ``overlaps`` a structured array of ``COMPONENT_OVERLAP_DTYPE`` -- (before, after, cells): record ``before`` of the
+    first list and record ``after`` of the second share ``cells`` grid cells -- with one entry per pair that shares a cell,
+    in ascending (before, after) order.  A record's DEGREE is the number of its partners.  All exact integers but
+    ``displacements``."""
+
+    before: ComponentList
+    after: ComponentList
+    overlaps: np.ndarray
+
+    def degree_before(self) -> np.ndarray:
+        """``(before.count,)`` int64: the after-records every before-record overlaps."""
+        return np.bincount(self.overlaps["before"].astype(np.int64), minlength=self.before.count).astype(np.int64)
+
+    def degree_after(self) -> np.ndarray:
+        """``(after.count,)`` int64: the before-records every after-record overlaps."""
+        return np.bincount(self.overlaps["after"].astype(np.int64), minlength=self.after.count).astype(np.int64)
+
+    def continued(self) -> np.ndarray:
+        """``(k, 2)`` int64: the pairs (before, after) that have no other partner on either side."""
+        b, a = self.overlaps["before"].astype(np.int64), self.overlaps["after"].astype(np.int64)
+        keep = (self.degree_before()[b] == 1) & (self.degree_after()[a] == 1)
+        return np.stack([b[keep], a[keep]], axis=1).reshape(-1, 2)
+
+    def split(self) -> np.ndarray:
+        """int64: the before-records with two partners or more."""
+        return np.flatnonzero(self.degree_before() >= 2).astype(np.int64)
+
+    def merged(self) -> np.ndarray:
+        """int64: the after-records with two partners or more."""
+        return np.flatnonzero(self.degree_after() >= 2).astype(np.int64)
+
+    def born(self) -> np.ndarray:
+        """int64: the after-records without a partner."""
+        return np.flatnonzero(self.degree_after() == 0).astype(np.int64)
+
+    def died(self) -> np.ndarray:
+        """int64: the before-records without a partner."""
+        return np.flatnonzero(self.degree_before() == 0).astype(np.int64)
+
+    def children(self, i: int) -> np.ndarray:
+        """int64: the after-records that before-record ``i`` overlaps, ascending."""
+        return self.overlaps["after"][self.overlaps["before"] == int(i)].astype(np.int64)
+
+    def parents(self, j: int) -> np.ndarray:
+        """int64: the before-records that after-record ``j`` overlaps, ascending."""
+        return self.overlaps["before"][self.overlaps["after"] == int(j)].astype(np.int64)
+
+    def displacements(self) -> np.ndarray:
+        """``(k, 2)`` float64: the after centroid minus the before centroid, (rows, columns), of the ``continued`` pairs."""
+        pairs = self.continued()
+        return (self.after.centroids()[pairs[:, 1]] - self.before.centroids()[pairs[:, 0]]).reshape(-1, 2)
+
+    def counts(self) -> dict:
+        """The five event counts: continued pairs, split before-records, merged after-records, born, died."""
+        return {"continued": int(self.continued().shape[0]), "split": int(self.split().size), "merged": int(self.merged().size),
+                "born": int(self.born().size), "died": int(self.died().size)}
+
+
+def _component_matches(lib, handle, shape, threshold, above, connectivity, min_size) -> List[ComponentMatch]:
+    """The planes of a ``gs_component_match`` copied out; the handle is destroyed at once, and its two lists with it."""
+    try:
+        before, after = ctypes.c_void_p(), ctypes.c_void_p()
+        planes, offsets = ctypes.c_uint64(0), ctypes.POINTER(ctypes.c_uint64)()
+        overlaps = ctypes.POINTER(capi.GsComponentOverlap)()
+        capi.check(lib.gs_component_match_view(handle, ctypes.byref(before), ctypes.byref(after), ctypes.byref(planes),
+                                               ctypes.byref(offsets), ctypes.byref(overlaps)))
+        off, ov = _copy_planes(planes, offsets, overlaps, COMPONENT_OVERLAP_DTYPE)
+        rule = (shape, threshold, above, connectivity, min_size)
+        lists_b, lists_a = _copy_lists(lib, before, *rule), _copy_lists(lib, after, *rule)
+    finally:
+        lib.gs_component_match_destroy(handle)
+    return [ComponentMatch(lists_b[i], lists_a[i], ov[off[i]:off[i + 1]].copy()) for i in range(planes.value)]
+
+
+def match_fields(context: "HipContext", before: "HipConcentration", after: "HipConcentration", threshold: float,
+                 above: bool = True, connectivity: int = 8, min_size: int = 1) -> ComponentMatch:
+    """``gs_fields_match``: the component lists of two planes of one shape under one rule and the overlaps of their
+    components, over the whole global grid (single-process contexts)."""
+    h = ctypes.c_void_p()
+    capi.check(context._lib.gs_fields_match(context.handle, before.handle, after.handle, float(threshold), 1 if above else 0,
+                                            int(connectivity), int(min_size), ctypes.byref(h)))
+    return _component_matches(context._lib, h, after.shape(), threshold, above, connectivity, min_size)[0]
 
 
 CORRELATION_STEPS = ((0, 1), (1, 0), (1, 1), (1, -1))  # e_k = (dr, dc): along a row, down a column, diagonal, anti-diagonal
@@ -996,6 +1098,13 @@ class HipConcentration:
         (``gs_field_component_list``; blocking, single-process contexts)."""
         return component_list_field(context, self, threshold, above, connectivity, min_size)
 
+    def match(self, context: HipContext, before: "HipConcentration", threshold: float, above: bool = True,
+              connectivity: int = 8, min_size: int = 1) -> ComponentMatch:
+        """What became of the components of ``before`` -- a plane of the same shape, an earlier state -- in this plane: both
+        planes' component lists under one rule and the overlaps of their components, formed on the device
+        (``gs_fields_match``; blocking, single-process contexts)."""
+        return match_fields(context, before, self, threshold, above, connectivity, min_size)
+
     def correlation(self, context: HipContext, thresholds, max_lag: int = 32, above: bool = True) -> List[Correlation]:
         """The two-point pair counts of this plane thresholded at each of ``thresholds`` (1..4, one pass), lags 0 ..
         ``max_lag`` along four directions over the whole global grid, counted on the device (``gs_fields_correlation``;
@@ -1181,6 +1290,15 @@ class Species:
         in_u, in_v, _, _ = self.in_out()
         return component_list_field(self._context, _species_plane(species, in_u, in_v), threshold, above, connectivity, min_size)
 
+    def match_since(self, snapshot: "Snapshot", threshold: float = 0.25, species: str = "v", above: bool = True,
+                    connectivity: int = 8, min_size: int = 1) -> ComponentMatch:
+        """What became of the spots since ``snapshot``: the component lists of ``species`` ("u" or "v") in the snapshot and
+        in the current state, thresholded at ``threshold``, and the overlaps of their components (``gs_fields_match``;
+        blocking, single-process contexts)."""
+        in_u, in_v, _, _ = self.in_out()
+        return match_fields(self._context, _species_plane(species, snapshot.u, snapshot.v), _species_plane(species, in_u, in_v),
+                            threshold, above, connectivity, min_size)
+
     def correlation(self, v_thresholds=(0.25,), u_thresholds=None, max_lag: int = 32,
                     above: Tuple[bool, bool] = (False, True)) -> Tuple[List[Correlation], List[Correlation]]:
         """(U, V) two-point pair counts of the current state in one call (``gs_fields_correlation``; blocking, collective in
@@ -1349,6 +1467,20 @@ class Ensemble:
                                                             _species_plane(species, 0, 1), float(threshold), 1 if above else 0,
                                                             int(connectivity), int(min_size), ctypes.byref(h)))
         return _component_lists(self._ctx._lib, h, self._shape, threshold, above, connectivity, min_size)
+
+    def matches_since(self, ref: "Ensemble", first: int = 0, count: Optional[int] = None, species: str = "v",
+                      threshold: float = 0.25, above: bool = True, connectivity: int = 8,
+                      min_size: int = 1) -> List[ComponentMatch]:
+        """What became of the spots of members ``[first, first + count)`` since the same members of ``ref`` -- a
+        ``snapshot()``, say -- (``gs_members_match``, blocking): one ``ComponentMatch`` per member, ``ref``'s member the
+        ``before`` and this ensemble's the ``after`` -- what ``Species.match_since`` gives for lone Species in the members'
+        states."""
+        first, count = self._range(first, count)
+        h = ctypes.c_void_p()
+        capi.check(self._ctx._lib.gs_members_match(self._ctx.handle, ref.handle, self.handle, first, count,
+                                                   _species_plane(species, 0, 1), float(threshold), 1 if above else 0,
+                                                   int(connectivity), int(min_size), ctypes.byref(h)))
+        return _component_matches(self._ctx._lib, h, self._shape, threshold, above, connectivity, min_size)
 
     def correlations(self, first: int = 0, count: Optional[int] = None, v_thresholds=(0.25,), u_thresholds=(0.5,),
                      max_lag: int = 32, above: Tuple[bool, bool] = (False, True)) -> np.ndarray:

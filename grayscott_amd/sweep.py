@@ -58,6 +58,18 @@ lists one after the other as a structured array -- member m's records at sample 
 ``records[offsets[s * members + m] : offsets[s * members + m + 1]]``.  It changes no state either and works with
 ``--no-fields``.
 
+``--track-every N`` records WHAT BECAME of every member's spots between one sample and the next: a snapshot of the ensemble is
+kept on the device (``Ensemble.snapshot``), taken at step 0; after every N steps and after the last one every member's V
+above ``--track-threshold-v T`` (required with the flag) is matched with its state at the previous sample on the device
+(``Ensemble.matches_since``; the rule is include/gs_hip.h's, gs_fields_match), and the snapshot is brought up to date
+(``gs_members_copy``).  Components of at least ``--track-min-size M`` cells (default 1) under ``--track-connectivity 4|8``
+(default 8) count.  Into ``<output stem>.tracks.npz``: ``steps[samples]``, ``threshold``, ``connectivity``, ``min_size``, the
+five event counts ``continued``, ``split``, ``merged``, ``born``, ``died``, each ``[samples, members]``,
+``offsets[samples * members + 1]`` and ``overlaps`` -- member m's overlaps at sample s are
+``overlaps[offsets[s * members + m] : offsets[s * members + m + 1]]``, record indices as in a ``.spots.npz`` taken at the same
+steps with the same rule --, and ``displacement_offsets`` and ``displacements[k, 2]`` (float64; after centroid minus before
+centroid of the continued pairs) laid out the same way.  It changes no state either and works with ``--no-fields``.
+
 ``--steady-every N`` asks of every member "has it stopped changing?".  A snapshot of the ensemble is kept on the device
 (``Ensemble.snapshot``), taken at step 0; after every N steps and after the last one every member is compared with it on the
 device (``Ensemble.changes_since``: with d = now - snapshot per cell in f64, the sum of |d|, the sum of d * d and the largest
@@ -96,7 +108,7 @@ import numpy as np
 
 from . import hdf5_min
 from .simulate import add_backend_args, backend_args
-from .simulation import COMPONENT_RECORD_DTYPE, Parameters, Simulation, pairs_total, quad_measures
+from .simulation import COMPONENT_OVERLAP_DTYPE, COMPONENT_RECORD_DTYPE, Parameters, Simulation, pairs_total, quad_measures
 
 
 def value_range(text: str) -> List[float]:
@@ -182,6 +194,14 @@ def parse(argv=None):
     ap.add_argument("--corr-threshold-u", type=threshold_list, default=None, metavar="A[,B,...]",
                     help="as many thresholds: U is set where it is below them (default 0.5 each)")
     ap.add_argument("--corr-lags", type=int, default=32, metavar="L", help="the largest lag (1..64)")
+    ap.add_argument("--track-every", type=int, default=0, metavar="N",
+                    help="match every member's components of V with those of the previous sample every N steps and at the end "
+                         "(<output stem>.tracks.npz)")
+    ap.add_argument("--track-threshold-v", type=float, default=None, metavar="T",
+                    help="the threshold above which a V cell is set (required with --track-every)")
+    ap.add_argument("--track-min-size", type=int, default=1, metavar="M", help="match the components of at least M cells (default 1)")
+    ap.add_argument("--track-connectivity", type=int, default=8, choices=(4, 8),
+                    help="4: cells join along edges; 8: also across corners (default 8)")
     ap.add_argument("--steady-every", type=int, default=0, metavar="N",
                     help="compare every member with its state N steps before, every N steps and at the end "
                          "(<output stem>.steady.npz)")
@@ -220,6 +240,14 @@ def parse(argv=None):
             ap.error(f"--{short}-threshold-u needs as many values as --{short}-threshold-v")
     if not 1 <= args.corr_lags <= 64:
         ap.error("--corr-lags must be in 1..64")
+    if args.track_every < 0:
+        ap.error("--track-every must be at least 1 (0 = off)")
+    if args.track_every and args.track_threshold_v is None:
+        ap.error("--track-every needs --track-threshold-v")
+    if args.track_threshold_v is not None and args.track_threshold_v != args.track_threshold_v:
+        ap.error("--track-threshold-v must be a number")
+    if args.track_min_size < 1:
+        ap.error("--track-min-size must be at least 1")
     if args.spots_every < 0:
         ap.error("--spots-every must be at least 1 (0 = off)")
     if args.spots_every and args.spot_threshold_v is None:
@@ -316,6 +344,28 @@ def write_spots(path: str, steps: List[int], samples: List[list], threshold: flo
              min_size=np.int64(min_size), offsets=offsets, records=records)
 
 
+def tracks_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".tracks.npz"
+
+
+def write_tracks(path: str, steps: List[int], samples: List[list], threshold: float, connectivity: int, min_size: int) -> None:
+    matches = [member for sample in samples for member in sample]  # [samples * members] of ComponentMatch
+    members = len(samples[0]) if samples else 0
+    offsets = np.zeros(len(matches) + 1, np.int64)
+    offsets[1:] = np.cumsum([m.overlaps.shape[0] for m in matches])
+    moves = [m.displacements() for m in matches]
+    move_offsets = np.zeros(len(matches) + 1, np.int64)
+    move_offsets[1:] = np.cumsum([d.shape[0] for d in moves])
+    counts = [m.counts() for m in matches]
+    events = {name: np.array([c[name] for c in counts], np.int64).reshape(len(samples), members)
+              for name in ("continued", "split", "merged", "born", "died")}
+    np.savez(path, steps=np.asarray(steps, np.int64), threshold=np.float32(threshold), connectivity=np.int64(connectivity),
+             min_size=np.int64(min_size), offsets=offsets,
+             overlaps=np.concatenate([m.overlaps for m in matches]) if matches else np.zeros(0, COMPONENT_OVERLAP_DTYPE),
+             displacement_offsets=move_offsets,
+             displacements=np.concatenate(moves).reshape(-1, 2) if moves else np.zeros((0, 2), np.float64), **events)
+
+
 def write_morphologies(path: str, steps: List[int], samples: List[np.ndarray], thresholds_u, thresholds_v, cells: int) -> None:
     q = np.stack(samples, axis=0)  # [samples, members, 2, nt, 6]
     area, perimeter, euler4, euler8 = quad_measures(q)
@@ -371,12 +421,14 @@ def run(args) -> dict:
     corr_at = sample_steps(args.steps, args.correlation_every) if args.correlation_every else []
     comp_at = sample_steps(args.steps, args.components_every) if args.components_every else []
     spots_at = sample_steps(args.steps, args.spots_every) if args.spots_every else []
+    track_at = sample_steps(args.steps, args.track_every) if args.track_every else []
     done, settled, taken = 0, None, None
-    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at or spots_at:
-        summaries, hists, changes, morphs, corrs, comps, spots = [], [], [], [], [], [], []
+    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at or spots_at or track_at:
+        summaries, hists, changes, morphs, corrs, comps, spots, tracks = [], [], [], [], [], [], [], []
         snap = ens.snapshot() if steady_at else None
+        last = ens.snapshot() if track_at else None  # (of its own: the steady checks move theirs at other steps)
         for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at) | set(comp_at)
-                         | set(spots_at)):
+                         | set(spots_at) | set(track_at)):
             ens.prepare_steps(at - done)
             done = at
             if at in summary_at:
@@ -391,6 +443,10 @@ def run(args) -> dict:
             if at in spots_at:
                 spots.append(ens.component_lists(species="v", threshold=args.spot_threshold_v, connectivity=args.spot_connectivity,
                                                  min_size=args.spot_min_size))
+            if at in track_at:
+                tracks.append(ens.matches_since(last, species="v", threshold=args.track_threshold_v,
+                                                connectivity=args.track_connectivity, min_size=args.track_min_size))
+                last.copy_from(ens)
             if at in corr_at:
                 corrs.append(ens.correlations(v_thresholds=args.corr_threshold_v, u_thresholds=args.corr_threshold_u,
                                               max_lag=args.corr_lags))
@@ -419,6 +475,10 @@ def run(args) -> dict:
         if spots_at:
             write_spots(spots_path(args.output), spots_at[:len(spots)], spots, args.spot_threshold_v, args.spot_connectivity,
                         args.spot_min_size)
+        if track_at:
+            write_tracks(tracks_path(args.output), track_at[:len(tracks)], tracks, args.track_threshold_v, args.track_connectivity,
+                         args.track_min_size)
+            last.destroy()
         if corr_at:
             write_correlations(correlation_path(args.output), corr_at[:len(corrs)], corrs, args.corr_threshold_u,
                                args.corr_threshold_v, args.corr_lags, shape)

@@ -36,7 +36,34 @@ inline void check(int32_t status)
     if (status != GS_OK) throw HipError(status, gs_last_error());
 }
 
+// What became of the components of one thresholded plane between two states (gs_fields_match): the two states' component
+// lists and, in ascending (before, after) order, every pair of records that shares a cell with the number of shared cells.
+struct ComponentMatch {
+    std::vector<gs_component_record> before, after;
+    std::vector<gs_component_overlap> overlaps;
+};
+
 namespace detail {
+// The planes of a gs_component_match copied out, one ComponentMatch per plane; the match is destroyed at once, its lists with it.
+inline std::vector<ComponentMatch> take_component_matches(gs_component_match *match)
+{
+    const gs_component_list *lists[2] = {nullptr, nullptr};
+    uint64_t planes = 0, list_planes = 0;
+    const uint64_t *offsets = nullptr, *list_offsets = nullptr;
+    const gs_component_overlap *overlaps = nullptr;
+    const gs_component_record *records = nullptr;
+    int32_t status = gs_component_match_view(match, &lists[0], &lists[1], &planes, &offsets, &overlaps);
+    std::vector<ComponentMatch> out((std::size_t)(status == GS_OK ? planes : 0));
+    for (uint64_t i = 0; status == GS_OK && i < planes; ++i) out[i].overlaps.assign(overlaps + offsets[i], overlaps + offsets[i + 1]);
+    for (int k = 0; status == GS_OK && k < 2; ++k) {
+        status = gs_component_list_view(lists[k], &list_planes, &list_offsets, &records);
+        for (uint64_t i = 0; status == GS_OK && i < planes; ++i)
+            (k ? out[i].after : out[i].before).assign(records + list_offsets[i], records + list_offsets[i + 1]);
+    }
+    gs_component_match_destroy(match);
+    check(status);
+    return out;
+}
 // The planes of a gs_component_list copied out, one vector of records per plane; the list is destroyed at once.
 inline std::vector<std::vector<gs_component_record>> take_component_lists(gs_component_list *list)
 {
@@ -607,6 +634,17 @@ class Species {
                                       connectivity, min_size, &list));
         return detail::take_component_lists(list).at(0);
     }
+    // what became of the spots since the snapshot: the component lists of species (0 = U, 1 = V) in the snapshot and in the
+    // current state under one rule, and the overlaps of their components (gs_fields_match; blocking, single-process contexts)
+    ComponentMatch match_since(Snapshot &snap, float threshold = 0.25f, int32_t species = 1, bool above = true,
+                               int32_t connectivity = 8, uint64_t min_size = 1)
+    {
+        if (species != 0 && species != 1) throw HipError(GS_ERR_INVALID, "species must be 0 (U) or 1 (V)");
+        gs_component_match *match = nullptr;
+        check(gs_fields_match(context_->get(), species ? snap.v().raw() : snap.u().raw(), species ? v_.in().raw() : u_.in().raw(),
+                              threshold, above ? 1 : 0, connectivity, min_size, &match));
+        return detail::take_component_matches(match).at(0);
+    }
     // (U, V) two-point pair counts of the current state over the whole global grid, in one call (gs_fields_correlation;
     // blocking, collective in a multi-process context): one Correlation per threshold (1..4 per species, the same number for
     // both), lags 0 .. max_lag (1..64), U set where it is below its thresholds and V where it is above, unless the senses say
@@ -823,6 +861,18 @@ class Ensemble {
         check(gs_members_component_list(ctx_->get(), e_, first, count, species, threshold, above ? 1 : 0, connectivity, min_size,
                                         &list));
         return detail::take_component_lists(list);
+    }
+    // what became of the spots of members [first, first + count) since the same members of ref (gs_members_match, blocking):
+    // element i = member first + i of ref as `before` against member first + i of this ensemble as `after`, what
+    // Species::match_since gives for lone Species in those states
+    std::vector<ComponentMatch> matches_since(const Ensemble &ref, std::size_t first, std::size_t count, float threshold = 0.25f,
+                                              int32_t species = 1, bool above = true, int32_t connectivity = 8,
+                                              uint64_t min_size = 1) const
+    {
+        gs_component_match *match = nullptr;
+        check(gs_members_match(ctx_->get(), ref.e_, e_, first, count, species, threshold, above ? 1 : 0, connectivity, min_size,
+                               &match));
+        return detail::take_component_matches(match);
     }
     // two-point pair counts of members [first, first + count) from the newest state (gs_members_correlation, blocking):
     // element (2 i + s) * nt + j = species s (0 = U, 1 = V) of member first + i at that species' threshold j, what

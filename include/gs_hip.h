@@ -779,8 +779,8 @@ int32_t gs_members_components(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
  * is allocated or sent: exchanging record lists of variable length between ranks is a follow-up.  GS_ERR_NOMEM: label or
  * record memory cannot be had; nothing is changed and no list is returned.  On any refusal *out is left as it was.
  * Not done: multi-process contexts; components wrapped under the periodic rule; label planes for the caller;
- * intensity-weighted centroids or any float accumulation; matching of spots across time; several thresholds or fields in
- * one call. */
+ * intensity-weighted centroids or any float accumulation; several thresholds or fields in one call.  (What became of the
+ * spots between two states: gs_fields_match below.) */
 typedef struct gs_component_record {
     uint64_t size;                               /* cells                                                              */
     uint64_t sum_row, sum_col;                   /* sums of the cells' row / column indices: centroid = sum / size    */
@@ -795,6 +795,65 @@ int32_t gs_members_component_list(gs_ctx *ctx, gs_ensemble *e, uint64_t first, u
 int32_t gs_component_list_view(const gs_component_list *list, uint64_t *planes, const uint64_t **offsets,
                                const gs_component_record **records);
 int32_t gs_component_list_destroy(gs_component_list *list);
+
+/* Component matching computed on the device: WHAT BECAME of the spots between two states -- which ones continued, split,
+ * merged, were born or died, and how far the continuing ones moved -- without downloading either plane.  Two planes of one
+ * shape, `before` (a snapshot's plane, say: gs_fields_copy) and `after`, and ONE rule for both: threshold, above, connectivity
+ * 4 or 8, min_size >= 1, exactly as in gs_field_component_list (a NaN cell is never set, a cell equal to the threshold is not
+ * set, a sub-normal cell is the value it is, components never wrap).
+ *   - the match holds the component list of `before` and that of `after`: each equals, record for record, what
+ *     gs_field_component_list (gs_members_component_list) returns for that plane and rule;
+ *   - an OVERLAP is (before, after, cells): the index of a record in before's list within its plane, the index of a record in
+ *     after's list, and cells >= 1, the number of grid cells set in both planes that belong to both components;
+ *   - every pair of listed components that shares at least one cell appears exactly once; within a plane the overlaps are in
+ *     ascending (before, after) order.  A component below min_size is in neither list and in no overlap;
+ *   - with min_size 1 the cells of all overlaps add up to the number of cells set in both planes; the overlaps of one record
+ *     add up to at most its size.  before == after (the same handle) is allowed: its overlaps are (i, i, size_i).
+ * Integers only: the same bits for any slab count, step kernel or launch shape, and for a member and a lone Species.
+ *   gs_fields_match          one pair of planes of this context and one shape; the match has 1 plane.  One wait for enqueued
+ *                            work, then slab by slab on the slab's compute stream: `before` labelled and counted, `after`
+ *                            labelled and counted, each in label memory of its own; the PIECES -- the cells set in both --
+ *                            labelled from the two label arrays under the same connectivity (a connected piece lies inside
+ *                            exactly one component of each plane) and counted; the three counts are read back once; the
+ *                            records are written and one overlap per piece, which names its two records through the piece's
+ *                            first cell.  The host makes rows and indices global, joins what crosses the seams as the lists
+ *                            do, drops the pairs of which a partner fell below min_size, sorts, and adds the cells of equal
+ *                            pairs: two pieces of one pair, and pieces cut by a seam, become one overlap.
+ *   gs_members_match         species (0 = U, 1 = V) of member first + i of `after` against member first + i of `before`, i <
+ *                            count, each from its ensemble's newest slot (a retired member: its held state) -- the pairing of
+ *                            gs_members_compare; the match has `count` planes.  Both ensembles belong to this context and
+ *                            have one shape and member count; before == after is allowed.  Members go in batches of whole
+ *                            members such that each of the three labellings stays within GS_COMPONENTS_BATCH_BYTES.
+ *   gs_component_match_view  the two lists -- ordinary gs_component_lists OWNED BY THE MATCH: gs_component_list_view works
+ *                            on them, they die with the match and must not be destroyed --, *planes, and the overlaps of
+ *                            plane i: overlaps[offsets[i] .. offsets[i + 1]); offsets has planes + 1 entries.  The pointers
+ *                            stay valid until the match is destroyed.
+ *   gs_component_match_destroy  frees the match and its lists; NULL: GS_OK.  Host memory owned by the library, independent of
+ *                            the context: it may outlive it.
+ * Label memory: 24 bytes per cell of the slab or batch (three labellings of 8), in a slab chain 1 bit per cell more for each
+ * of the two lists, 48 bytes per record and 16 per piece; all allocated for the call and freed before it returns, however it
+ * returns.  Three u32 per 256 cells of the slab's scratch buffer hold the counts.
+ * Both calls block like the list calls (one wait for enqueued work, then the slabs' compute streams) and have no side effects
+ * (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID, decided in this order: a null argument (ctx,
+ * out), a NaN threshold, a connectivity that is neither 4 nor 8, min_size == 0, a species outside 0..1 -- all before any
+ * handle is looked at --; then a null or foreign handle, planes of different shapes, members outside the ensemble.
+ * GS_ERR_UNSUPPORTED: a multi-process context (world > 1) -- every rank reaches that verdict alone, before anything is
+ * allocated or sent --; a slab or a batch of members of 2^32 cells or more; the lists' sum-overflow shapes.  GS_ERR_NOMEM:
+ * label or record memory cannot be had; nothing is changed and no match is returned.  On any refusal *out is left as it was.
+ * Not done: multi-process contexts; wrapped components; matching by distance where nothing overlaps; tracks over more than
+ * two states; float-weighted overlaps. */
+typedef struct gs_component_overlap {
+    uint32_t before, after; /* record indices within the plane's two lists      */
+    uint64_t cells;         /* cells set in both planes that belong to both     */
+} gs_component_overlap;     /* 16 bytes */
+typedef struct gs_component_match gs_component_match; /* host memory owned by the library, independent of the context */
+int32_t gs_fields_match(gs_ctx *ctx, gs_field *before, gs_field *after, float threshold, int32_t above, int32_t connectivity,
+                        uint64_t min_size, gs_component_match **out);
+int32_t gs_members_match(gs_ctx *ctx, gs_ensemble *before, gs_ensemble *after, uint64_t first, uint64_t count, int32_t species,
+                         float threshold, int32_t above, int32_t connectivity, uint64_t min_size, gs_component_match **out);
+int32_t gs_component_match_view(const gs_component_match *match, const gs_component_list **before, const gs_component_list **after,
+                                uint64_t *planes, const uint64_t **offsets, const gs_component_overlap **overlaps);
+int32_t gs_component_match_destroy(gs_component_match *match);
 
 /* Two states compared on the device: how far one plane of the WHOLE global grid is from another of the same shape -- "has
  * this run stopped changing?" -- without downloading either, and the device copies that give a state to compare with

@@ -50,6 +50,26 @@ pub struct gs_ensemble {
     _private: [u8; 0],
 }
 
+/// A component list owned by the library (of a `gs_component_match` here: it dies with the match).
+#[repr(C)]
+pub struct gs_component_list {
+    _private: [u8; 0],
+}
+/// What `gs_fields_match` / `gs_members_match` return: host memory owned by the library.
+#[repr(C)]
+pub struct gs_component_match {
+    _private: [u8; 0],
+}
+
+/// A before-record and an after-record of a match that share `cells` grid cells (16 bytes).
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default, PartialEq, Eq)]
+pub struct gs_component_overlap {
+    pub before: u32,
+    pub after: u32,
+    pub cells: u64,
+}
+
 /// A plane's summary computed on the device (32 bytes; fold order in include/gs_hip.h).
 #[repr(C)]
 #[derive(Copy, Clone, Debug, Default)]
@@ -210,4 +230,40 @@ extern "C" {
         bins: i32,
         out: *mut u64,
     ) -> i32;
+    /// What became of the components of `before` in `after` (two planes of one shape, one rule): `out` receives a match.
+    pub fn gs_fields_match(
+        ctx: *mut gs_ctx,
+        before: *mut gs_field,
+        after: *mut gs_field,
+        threshold: f32,
+        above: i32,
+        connectivity: i32,
+        min_size: u64,
+        out: *mut *mut gs_component_match,
+    ) -> i32;
+    /// Member first + i of `after` against member first + i of `before`; the match has `count` planes.
+    pub fn gs_members_match(
+        ctx: *mut gs_ctx,
+        before: *mut gs_ensemble,
+        after: *mut gs_ensemble,
+        first: u64,
+        count: u64,
+        species: i32,
+        threshold: f32,
+        above: i32,
+        connectivity: i32,
+        min_size: u64,
+        out: *mut *mut gs_component_match,
+    ) -> i32;
+    /// The two lists (owned by the match), the planes, `planes + 1` offsets and the overlaps; valid until the match is destroyed.
+    pub fn gs_component_match_view(
+        m: *const gs_component_match,
+        before: *mut *const gs_component_list,
+        after: *mut *const gs_component_list,
+        planes: *mut u64,
+        offsets: *mut *const u64,
+        overlaps: *mut *const gs_component_overlap,
+    ) -> i32;
+    /// Null: `GS_OK`.
+    pub fn gs_component_match_destroy(m: *mut gs_component_match) -> i32;
 }
