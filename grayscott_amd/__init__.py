@@ -21,6 +21,8 @@ from .simulation import (  # noqa: F401
     Components,
     Morphology,
     Parameters,
+    RegionMorphology,
+    RegionSummaries,
     Simulation,
     Snapshot,
     Species,
@@ -30,4 +32,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]

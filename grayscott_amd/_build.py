@@ -53,6 +53,9 @@ UNITS = [
     # bit-quad counts of thresholded planes (one pass for up to four thresholds): the same float mode, a sub-normal cell is
     # compared as it is
     ("gs_morphology.hip", "gs_morphology_k.o", []),
+    # regional observables (summaries and bit-quad counts per region of one plane): the same float mode as their whole-grid
+    # twins, sub-normal cells kept
+    ("gs_regions.hip", "gs_regions_k.o", []),
     # two-point pair counts of thresholded planes (lags 0..64 along four directions, one pass for up to four thresholds):
     # the same float mode
     ("gs_correlation.hip", "gs_correlation_k.o", []),

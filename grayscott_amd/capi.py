@@ -51,6 +51,7 @@ EXPORTS = (
     "gs_fields_compare", "gs_members_compare", "gs_fields_copy", "gs_members_copy",
     "gs_members_set_active", "gs_members_get_active",
     "gs_fields_morphology", "gs_members_morphology",
+    "gs_region_grid", "gs_fields_region_summaries", "gs_fields_region_morphology",
     "gs_fields_correlation", "gs_members_correlation",
     "gs_fields_components", "gs_members_components",
     "gs_field_component_list", "gs_members_component_list", "gs_component_list_view", "gs_component_list_destroy",
@@ -277,6 +278,9 @@ def load() -> ctypes.CDLL:
         "gs_members_get_active": (i32, [vp, vp, u64, u64, vp, vp, P(u64)]),
         "gs_fields_morphology": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, P(GsMorphology)]),
         "gs_members_morphology": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, P(GsMorphology)]),
+        "gs_region_grid": (i32, [u64, u64, i32, i32, P(u64), P(u64)]),
+        "gs_fields_region_summaries": (i32, [vp, P(vp), i32, i32, i32, P(GsSummary)]),
+        "gs_fields_region_morphology": (i32, [vp, P(vp), i32, i32, i32, P(f32), P(i32), i32, P(GsMorphology)]),
         "gs_fields_components": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(GsComponents)]),
         "gs_members_components": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(GsComponents)]),
         "gs_field_component_list": (i32, [vp, vp, f32, i32, i32, u64, P(vp)]),

@@ -13,7 +13,8 @@
 //                  (gs_fields_morphology, gs_members_morphology), two-point pair counts (gs_fields_correlation,
 //                  gs_members_correlation), connected components and component lists (gs_fields_components,
 //                  gs_field_component_list and their member forms), component matches of two states (gs_fields_match,
-//                  gs_members_match), comparisons of two states
+//                  gs_members_match), summaries and bit-quad counts per region of one grid (gs_fields_region_summaries,
+//                  gs_fields_region_morphology), comparisons of two states
 //                  (gs_fields_compare, gs_members_compare) and the device copies behind snapshots (gs_fields_copy, gs_members_copy)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once

@@ -282,6 +282,28 @@ hipError_t gs_launch_quads(const float *const *planes, const float *const *above
                            int64_t pitch, int64_t rows, int32_t cols, int bottom, const float *thresholds, const int32_t *sense,
                            int32_t nt, int64_t max_groups, unsigned long long *out, hipStream_t s);
 
+// Regional observables (gs_regions.hip; include/gs_hip.h: gs_fields_region_summaries, gs_fields_region_morphology).  n (1..4)
+// planes of one shape -- rows [0, rows) of `pitch` floats, `cols` columns -- cut into regions of rh x rw cells (rw a multiple
+// of 4, at least 16; rh >= 1) anchored at row 0 and column 0, ragged ones at the lower and right edge kept: rr = ceil(rows / rh)
+// by rc = ceil(cols / rw) of them.
+// gs_launch_region_summary writes out[(p * rr + i) * rc + j]: the whole summary of region (i, j) of plane p -- the fold order
+// of gs_hip.h with columns counted from the region's first column, its rows added in ascending order from +0.0.
+// A region's record is gs_summary's layout, 32 bytes: a region's count of non-finite cells is 64-bit, as a plane's is.
+struct GsRegionSummary {
+    double sum, sum_sq;
+    float min, max;
+    uint64_t nonfinite;
+};
+// gs_launch_region_quads adds Q1, Q2, Q3, Q4, QD of region (i, j) of plane p, padded with its own ring of unset cells and
+// thresholded as for gs_launch_quads, to out[(((p * rr + i) * rc + j) * nt + k) * 6 + 1 ...], which must hold zeros: a
+// result is gs_morphology's six words, so that it travels to the caller's memory as it is, and word 0 (Q0, the complement)
+// is the host's.  max_groups: as for gs_launch_histogram.
+hipError_t gs_launch_region_summary(const float *const *planes, int n, int64_t pitch, int64_t rows, int32_t cols, int32_t rh,
+                                    int32_t rw, GsRegionSummary *out, hipStream_t s);
+hipError_t gs_launch_region_quads(const float *const *planes, int np, int64_t pitch, int64_t rows, int32_t cols, int32_t rh,
+                                  int32_t rw, const float *thresholds, const int32_t *sense, int32_t nt, int64_t max_groups,
+                                  unsigned long long *out, hipStream_t s);
+
 // Two-point pair counts (gs_correlation.hip; include/gs_hip.h: gs_fields_correlation).  Planes, thresholds and senses as for
 // gs_launch_quads.  The launch counts, for every lag d = 0 .. max_lag (1..64) and the unit steps e_0 = (0, 1), e_1 = (1, 0),
 // e_2 = (1, 1), e_3 = (1, -1), the pairs {p, p + d e_k} of set cells whose LOWER cell lies in the plane's rows [0, rows) -- the

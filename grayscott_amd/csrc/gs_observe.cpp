@@ -30,6 +30,10 @@
 //               indices global and adds the cells of equal pairs (gs_match_merge.h).  Single-process contexts only.
 //   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
 //               (row_records); ensembles fold on the device (gs_change_fold_k).
+//   regional observables  summaries and bit-quad counts of every region of rh x rw cells of a plane (gs_fields_region_summaries,
+//               gs_fields_region_morphology; gs_regions.hip): one launch per slab leaves a record or a set of counters per
+//               (plane, region) -- a region lies inside one slab, so nothing is staged and nothing is folded on the host --
+//               and the slabs' and ranks' region rows meet in the global [plane][region] layout (region_results).
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
@@ -593,6 +597,95 @@ size_t match_work_bytes(uint64_t entries, size_t cols) { return 3 * list_work_by
 void *match_work(void *scratch, uint64_t entries, size_t cols, int k)
 {
     return static_cast<unsigned char *>(scratch) + (size_t)k * list_work_bytes(entries, cols);
+}
+
+// ---- regional observables ------------------------------------------------------------------------------------------------
+// The region grid of gs_hip.h for a grid of rows x cols cells, or its refusal.  No handle is looked at.
+int32_t region_grid(uint64_t rows, uint64_t cols, int32_t rh, int32_t rw, uint64_t *rr, uint64_t *rc)
+{
+    if (rh < 1) return fail(GS_ERR_INVALID, "a region height of %d (at least 1)", rh);
+    if (rw < 16 || rw % 4 != 0) return fail(GS_ERR_INVALID, "a region width of %d (a multiple of 4, at least 16)", rw);
+    const uint64_t RR = rows / (uint64_t)rh + (rows % (uint64_t)rh ? 1 : 0), RC = cols / (uint64_t)rw + (cols % (uint64_t)rw ? 1 : 0);
+    if (RR != 0 && RC > (uint64_t)GS_REGIONS_MAX / RR)
+        return fail(GS_ERR_INVALID, "%llu x %llu regions (at most %u)", (unsigned long long)RR, (unsigned long long)RC,
+                    (unsigned)GS_REGIONS_MAX);
+    *rr = RR;
+    *rc = RC;
+    return GS_OK;
+}
+
+// What a regional call checks before any device work, in gs_hip.h's order: the region shape alone, then -- where the first
+// field can be read -- the region count of its grid; the handles themselves are check_planes'.
+int32_t check_regions(const gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw)
+{
+    uint64_t rr, rc;
+    GS_TRY(region_grid(0, 0, rh, rw, &rr, &rc));
+    if (n >= 1 && n <= 4 && fields[0] && fields[0]->ctx == ctx) GS_TRY(region_grid(fields[0]->rows, fields[0]->cols, rh, rw, &rr, &rc));
+    return GS_OK;
+}
+
+// Results per region of n planes of f0's shape over the WHOLE global grid, `elem` bytes each, as [plane][region row][region
+// column] into `all`: one launch per slab on its compute stream into the slab's scratch buffer -- zeroed first for counters;
+// `launch(slab, results, stream)` leaves results[(p * rr_slab + i) * RC + j] -- and, in a multi-process context, every rank's
+// results to every rank.  Every slab of the global grid must begin at a multiple of rh rows (the precedent of reduced
+// images): a region then lies inside one slab, slab k's regions are rows [start_k / rh, ...) of the region grid, no ghost
+// row is read and no row is staged.  Every rank reaches the same verdict.
+template <typename Launch>
+int32_t region_results(gs_ctx *ctx, const gs_field *f0, int32_t n, int32_t rh, uint64_t RR, uint64_t RC, size_t elem, bool zeroed,
+                       const char *what, unsigned char *all, Launch launch)
+{
+    const uint64_t q = (uint64_t)rh, S = (uint64_t)ctx->total_slabs(), R = f0->rows;
+    for (uint64_t k = 1; k < S; ++k)
+        if ((k * R / S) % q != 0)
+            return fail(GS_ERR_UNSUPPORTED, "slab %llu begins at row %llu, which is not a multiple of the region height %d "
+                                            "(a region may not straddle two slabs)",
+                        (unsigned long long)k, (unsigned long long)(k * R / S), rh);
+    const size_t nslab = ctx->slabs.size(), line = (size_t)RC * elem; // (line: one row of the region grid of one plane)
+    auto region_rows = [&](uint64_t rows) { return (size_t)((rows + q - 1) / q); };
+    size_t local_rr = 0;
+    for (const FieldSlab &fs : f0->s) local_rr += region_rows((uint64_t)fs.rows);
+    std::vector<unsigned char> gathered;
+    unsigned char *local = all; // one process: its region rows are the grid's
+    if (ctx->world > 1) {
+        gathered.resize((size_t)n * local_rr * line);
+        local = gathered.data();
+    }
+    size_t at = 0;
+    for (size_t i = 0; i < nslab; ++i) {
+        SlabRt &sl = ctx->slabs[i];
+        const size_t rrs = region_rows((uint64_t)f0->s[i].rows);
+        if (rrs == 0) continue;
+        GS_TRY(ensure_scratch(ctx, (int)i, (size_t)n * rrs * line, what));
+        GS_HIP(hipSetDevice(sl.device));
+        unsigned char *dev = static_cast<unsigned char *>(sl.scratch);
+        if (zeroed) GS_HIP(hipMemsetAsync(dev, 0, (size_t)n * rrs * line, sl.compute));
+        GS_HIP(launch(i, dev, sl.compute));
+        for (int32_t p = 0; p < n; ++p)
+            GS_HIP(hipMemcpyAsync(local + ((size_t)p * local_rr + at) * line, dev + (size_t)p * rrs * line, rrs * line,
+                                  hipMemcpyDeviceToHost, sl.compute));
+        at += rrs;
+    }
+    GS_TRY(sync_compute(ctx));
+    if (ctx->world == 1) return GS_OK;
+    const uint64_t L = (uint64_t)nslab;
+    std::vector<size_t> bytes((size_t)ctx->world, (size_t)0);
+    for (uint64_t k = 0; k < (uint64_t)ctx->world * L; ++k)
+        bytes[(size_t)(k / L)] += (size_t)n * region_rows(global_slab_rows(ctx, R, k)) * line;
+    if (bytes[(size_t)ctx->rank] != gathered.size())
+        return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
+    std::vector<unsigned char> blocks((size_t)n * (size_t)RR * line);
+    GS_TRY(exchange(ctx, gathered.data(), bytes, what, blocks.data()));
+    // rank blocks in rank order, each [plane][its region rows]: plane p's region rows in global order
+    for (int32_t p = 0; p < n; ++p) {
+        size_t from = 0, row = 0;
+        for (int r = 0; r < ctx->world; ++r) {
+            const size_t rrs = bytes[(size_t)r] / line / (size_t)n;
+            std::memcpy(all + ((size_t)p * (size_t)RR + row) * line, blocks.data() + from + (size_t)p * rrs * line, rrs * line);
+            from += (size_t)n * rrs * line;
+            row += rrs;
+        }
+    }
+    return GS_OK;
 }
 
 } // namespace
@@ -1437,6 +1530,70 @@ int32_t gs_component_match_view(const gs_component_match *match, const gs_compon
 int32_t gs_component_match_destroy(gs_component_match *match)
 {
     delete match;
+    return GS_OK;
+}
+
+int32_t gs_region_grid(uint64_t rows, uint64_t cols, int32_t rh, int32_t rw, uint64_t *rr, uint64_t *rc)
+{
+    if (!rr || !rc) return fail(GS_ERR_INVALID, "null argument");
+    return region_grid(rows, cols, rh, rw, rr, rc);
+}
+
+int32_t gs_fields_region_summaries(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, gs_summary *out)
+{
+    if (!ctx || !fields || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_regions(ctx, fields, n, rh, rw));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    uint64_t RR, RC;
+    GS_TRY(region_grid(f0->rows, f0->cols, rh, rw, &RR, &RC));
+    if (RR * RC == 0) return GS_OK; // an empty plane has no regions; the same shape on every rank: nobody exchanges anything
+    // a region's record is gs_summary's layout: the results land in `out` as they are
+    static_assert(sizeof(GsRegionSummary) == sizeof(gs_summary) && offsetof(GsRegionSummary, min) == offsetof(gs_summary, min) &&
+                      offsetof(GsRegionSummary, nonfinite) == offsetof(gs_summary, nonfinite),
+                  "region record layout");
+    return region_results(ctx, f0, n, rh, RR, RC, sizeof(GsRegionSummary), false, "region summary",
+                          reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
+        return gs_launch_region_summary(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw,
+                                        reinterpret_cast<GsRegionSummary *>(dev), s);
+    });
+}
+
+int32_t gs_fields_region_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, const float *thresholds,
+                                    const int32_t *above, int32_t nt, gs_morphology *out)
+{
+    if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_thresholds(thresholds, n, nt));
+    GS_TRY(check_regions(ctx, fields, n, rh, rw));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    uint64_t RR, RC;
+    GS_TRY(region_grid(f0->rows, f0->cols, rh, rw, &RR, &RC));
+    if (RR * RC == 0) return GS_OK;
+    // The counters land in `out` as they are -- six words per result, Q0's left zero by the launch: with up to 2^22 regions
+    // a buffer between the device and the caller's memory would be tens of MiB of freshly mapped pages in every call, whose
+    // first touch under the copy costs more than the launch (profiles/regions.md).
+    GS_TRY(region_results(ctx, f0, n, rh, RR, RC, (size_t)nt * sizeof(gs_morphology), true, "region morphology",
+                          reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
+        return gs_launch_region_quads(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, thresholds, above,
+                                      nt, max_groups(ctx), reinterpret_cast<unsigned long long *>(dev), s);
+    }));
+    const uint64_t q = (uint64_t)rh, w = (uint64_t)rw;
+    for (size_t p = 0; p < (size_t)n; ++p)
+        for (uint64_t i = 0; i < RR; ++i)
+            for (uint64_t j = 0; j < RC; ++j) {
+                // the region's own rows and columns: ragged in the last row and column of the region grid
+                const uint64_t h = std::min(q, f0->rows - i * q), c = std::min(w, f0->cols - j * w);
+                const size_t at = (p * (size_t)RR + (size_t)i) * (size_t)RC + (size_t)j;
+                for (size_t k = 0; k < (size_t)nt; ++k) {
+                    gs_morphology &m = out[at * (size_t)nt + k];
+                    m = from_counted(m.quads + 1, h, c);
+                }
+            }
     return GS_OK;
 }
 

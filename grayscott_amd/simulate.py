@@ -28,6 +28,16 @@ what it is without the option.
 Domain masks (``gs_ctx_set_mask``): ``--hip-mask FILE.npy`` (or ``FILE.npz`` with an array ``mask``) of the grid's shape
 makes the cells where it is nonzero walls.  It combines with every other option but the parameter map's, which it
 refuses.
+
+Regional observables (``gs_fields_region_summaries``, ``gs_fields_region_morphology``): ``--hip-regions RH[xRW]`` cuts the
+grid into regions of RH x RW cells (RW a multiple of 4, at least 16; one number: square) and writes, next to the output,
+``<stem>.regions.npz``: per observed image the summaries of U and V and the bit-quad counts of V (``--hip-region-threshold-v
+A[,B...]``, default 0.25, set above) and, if asked for, of U (``--hip-region-threshold-u``, set below) of every region, all
+formed on the device -- ``--hip-regions-every N`` observes every N-th image, the default is the last image alone.  With a
+parameter map the file also holds ``feed`` and ``kill``, the regions' means of the maps (numpy, float64): the file is then the
+phase diagram.  In a multi-process run rank 0 writes.  The two calls block: an observed image is waited for before the next
+steps are enqueued, so with ``--hip-regions-every 1`` no download overlaps the steps of the next image any more (the pipeline of
+two images in flight runs dry at every observed image); the default, the last image alone, costs nothing before the end.
 """
 from __future__ import annotations
 
@@ -60,7 +70,12 @@ def parse(argv=None):
     add_param_map_args(ap)
     add_mask_args(ap)
     add_image_args(ap)
-    return ap.parse_args(argv)
+    add_region_args(ap)
+    args = ap.parse_args(argv)
+    tu, tv = args.hip_region_threshold_u, args.hip_region_threshold_v or [0.25]
+    if tu is not None and len(tu) != len(tv):
+        ap.error(f"--hip-region-threshold-u wants as many thresholds as --hip-region-threshold-v ({len(tv)}), not {len(tu)}")
+    return args
 
 
 def add_backend_args(ap: argparse.ArgumentParser) -> None:
@@ -118,6 +133,115 @@ def add_image_args(ap: argparse.ArgumentParser) -> None:
     im.add_argument("--hip-image-reduce", type=_reduce_factor, default=1, metavar="F",
                     help="write every image averaged over F x F blocks on the device (1..64): matrix[nbimage, ceil(rows / F), "
                          "ceil(cols / F)], 1 / F^2 of the bytes; 1 = the full planes")
+
+
+def parse_regions(text: str):
+    """``RH[xRW]`` as (rh, rw): one number is a square region.  What the library asks of a region shape is checked here
+    too, so that a wrong flag fails before anything runs."""
+    try:
+        parts = [int(x) for x in text.lower().split("x")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"RH[xRW], two integers, not {text!r}") from None
+    if len(parts) not in (1, 2):
+        raise argparse.ArgumentTypeError(f"RH[xRW], not {text!r}")
+    rh, rw = parts[0], parts[-1]
+    if rh < 1 or rw < 16 or rw % 4 != 0:
+        raise argparse.ArgumentTypeError(f"a region of {rh} x {rw}: RH is at least 1, RW a multiple of 4 and at least 16")
+    return rh, rw
+
+
+def _threshold_list(text: str):
+    try:
+        values = [float(x) for x in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"1 to 4 numbers A[,B...], not {text!r}") from None
+    if not 1 <= len(values) <= 4 or any(np.isnan(v) for v in values):
+        raise argparse.ArgumentTypeError(f"1 to 4 numbers A[,B...], none NaN, not {text!r}")
+    return values
+
+
+def _positive(text: str) -> int:
+    try:
+        value = int(text)
+    except ValueError:
+        value = 0
+    if value < 1:
+        raise argparse.ArgumentTypeError(f"an integer of at least 1, not {text!r}")
+    return value
+
+
+def add_region_args(ap: argparse.ArgumentParser) -> None:
+    """The regional observables' options of the ``--hip-*`` group (simulate only)."""
+    rg = ap.add_argument_group("HIP backend: regional observables")
+    rg.add_argument("--hip-regions", type=parse_regions, default=None, metavar="RH[xRW]",
+                    help="summaries and bit-quad counts of every region of RH x RW cells, formed on the device, into <stem>.regions.npz")
+    rg.add_argument("--hip-regions-every", type=_positive, default=None, metavar="N",
+                    help="observe every N-th image (default: the last image alone)")
+    rg.add_argument("--hip-region-threshold-v", type=_threshold_list, default=None, metavar="A[,B...]",
+                    help="V is set above these thresholds (1..4; default 0.25)")
+    rg.add_argument("--hip-region-threshold-u", type=_threshold_list, default=None, metavar="A[,B...]",
+                    help="U is set below these thresholds (as many as V's; default: U's quads are not counted)")
+
+
+def regions_path(output: str) -> str:
+    """The regional observables' file next to the output file."""
+    return os.path.splitext(output)[0] + ".regions.npz"
+
+
+def region_means(values, shape, region) -> np.ndarray:
+    """The mean of ``values`` -- a [rows, cols] array, or a scalar for a uniform plane -- over every region of ``region`` =
+    (rh, rw) cells of a grid of ``shape``, in float64: (ceil(rows / rh), ceil(cols / rw)), ragged regions over their own cells."""
+    rows, cols = shape
+    rh, rw = region
+    a = np.broadcast_to(np.asarray(values, np.float64), (rows, cols))
+    row_edges, col_edges = np.arange(0, rows, rh), np.arange(0, cols, rw)
+    sums = np.add.reduceat(np.add.reduceat(a, row_edges, axis=0), col_edges, axis=1)
+    h = np.minimum(rh, rows - row_edges)
+    w = np.minimum(rw, cols - col_edges)
+    return sums / (h[:, None] * w[None, :])
+
+
+def regions_observed(image: int, images: int, every) -> bool:
+    """Is image ``image`` (1-based) of ``images`` one that ``--hip-regions-every`` observes?"""
+    return image == images if every is None else image % every == 0
+
+
+class RegionLog:
+    """What ``--hip-regions`` collects, one entry per observed image, and the file it becomes."""
+
+    SUMMARY_KEYS = ("sum", "sum_sq", "min", "max", "nonfinite")
+
+    def __init__(self, region, thresholds_v, thresholds_u):
+        self.region = region
+        self.thresholds_v = list(thresholds_v) if thresholds_v else [0.25]
+        self.thresholds_u = list(thresholds_u) if thresholds_u else None
+        if self.thresholds_u is not None and len(self.thresholds_u) != len(self.thresholds_v):
+            raise ValueError("--hip-region-threshold-u wants as many thresholds as --hip-region-threshold-v")
+        self.steps, self.rows = [], {}
+
+    def observe(self, species, step: int) -> None:
+        su, sv = species.region_summaries(self.region)
+        mu, mv = species.region_morphology(self.region, self.thresholds_v, self.thresholds_u)
+        self.steps.append(step)
+        for name, s in (("u", su), ("v", sv)):
+            for key in self.SUMMARY_KEYS:
+                self.rows.setdefault(f"{key}_{name}", []).append(getattr(s, key))
+        self.rows.setdefault("cells", []).append(sv.size)
+        self.rows.setdefault("quads_v", []).append(np.stack([m.quads for m in mv]))
+        if mu:
+            self.rows.setdefault("quads_u", []).append(np.stack([m.quads for m in mu]))
+
+    def save(self, path: str, shape, pmap=None) -> None:
+        out = {"region": np.array(self.region, np.int64), "shape": np.array(shape, np.int64), "steps": np.array(self.steps, np.int64),
+               "thresholds_v": np.array(self.thresholds_v, np.float32),
+               "thresholds_u": np.array(self.thresholds_u or [], np.float32)}
+        for key, rows in self.rows.items():
+            out[key] = rows[0] if key == "cells" else np.stack(rows)
+        if pmap is not None:
+            out["feed"] = region_means(pmap[0], shape, self.region)
+            out["kill"] = region_means(pmap[1], shape, self.region)
+        with open(path, "wb") as f:
+            np.savez(f, **out)
 
 
 def image_shape(args):
@@ -236,6 +360,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
         raise ValueError("--output-buffer must be at least 1")
     params = simulation_parameters(args)
     pmap = param_map(args, shape, params)
+    region = getattr(args, "hip_regions", None)
+    regions = RegionLog(region, getattr(args, "hip_region_threshold_v", None), getattr(args, "hip_region_threshold_u", None)) if region else None
     mask = domain_mask(args, shape)
     sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)
@@ -286,13 +412,16 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     t0 = time.perf_counter()
     pending = []                                            # images on their way from the device, oldest first (at most 2)
     try:
-        for _ in range(args.nbimage):
+        for index in range(1, args.nbimage + 1):
             image = free.get()
             if failed.is_set() or image is None:
                 break
             sim.prepare_steps(species, steps_per_image)     # enqueued; nothing here waits for the device
             species.write_result_view_after(image, reduce)  # this image: staged + copied behind those steps while we go on
             pending.append(image)
+            if regions is not None and regions_observed(index, args.nbimage, getattr(args, "hip_regions_every", None)):
+                # blocking: waits for this image's steps, and so for every image enqueued so far (the module's docstring)
+                regions.observe(species, index * steps_per_image)
             if len(pending) == 2:
                 # two images in flight (the library stages them in two buffers in turn): the host copy of the newer one
                 # overlaps the next steps AND the hand-over of the older one, so the PCIe link never idles between images
@@ -311,6 +440,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
         raise errors[0]
     if hasattr(out, "flush"):
         out.flush()
+    if regions is not None and getattr(args, "rank", 0) == 0:
+        regions.save(regions_path(args.output), shape, pmap)
     cells = shape[0] * shape[1]
     image_bytes = img_shape[0] * img_shape[1] * 4          # what really crossed the link per image
     info = {

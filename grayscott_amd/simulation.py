@@ -521,6 +521,155 @@ def morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"
     return [[Morphology.from_quads(out[i, k], thr[i * nt + k], above[i], rows * cols) for k in range(nt)] for i in range(n)]
 
 
+def region_shape(region) -> Tuple[int, int]:
+    """``(rh, rw)`` from a region shape given as a pair, or as one int for a square region."""
+    if np.isscalar(region):
+        return int(region), int(region)
+    rh, rw = region
+    return int(rh), int(rw)
+
+
+def region_grid(rows: int, cols: int, region) -> Tuple[int, int]:
+    """``gs_region_grid``: ``(RR, RC)``, the rows and columns of regions that ``region`` cuts a grid of ``rows`` x ``cols``
+    cells into (ragged ones at the lower and right edge kept), or the library's refusal of the region shape.  Pure."""
+    rh, rw = region_shape(region)
+    rr, rc = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    capi.check(capi.load().gs_region_grid(int(rows), int(cols), rh, rw, ctypes.byref(rr), ctypes.byref(rc)))
+    return int(rr.value), int(rc.value)
+
+
+def region_sizes(rows: int, cols: int, region, grid: Tuple[int, int]) -> np.ndarray:
+    """The number of cells of every region, ``(RR, RC)`` int64: ``rh * rw`` but in a ragged last row or column."""
+    rh, rw = region_shape(region)
+    h = np.minimum(rh, rows - rh * np.arange(grid[0], dtype=np.int64))
+    w = np.minimum(rw, cols - rw * np.arange(grid[1], dtype=np.int64))
+    return h[:, None] * w[None, :]
+
+
+@dataclass(frozen=True, eq=False)
+class RegionSummaries:
+    """The summaries of every region of one plane, computed on the device (``gs_fields_region_summaries``): arrays of shape
+    ``(RR, RC)``, entry (i, j) being bit for bit the ``Summary`` of a plane that holds region (i, j)'s cells alone.  ``region``
+    is ``(rh, rw)``, ``shape`` the plane's, ``size`` every region's number of cells."""
+
+    sum: np.ndarray
+    sum_sq: np.ndarray
+    min: np.ndarray
+    max: np.ndarray
+    nonfinite: np.ndarray
+    size: np.ndarray
+    region: Tuple[int, int]
+    shape: Tuple[int, int]
+
+    @classmethod
+    def from_records(cls, rec: np.ndarray, region, shape) -> "RegionSummaries":
+        """From ``(RR, RC)`` records of ``SUMMARY_DTYPE`` as the C ABI writes them."""
+        region, shape = region_shape(region), (int(shape[0]), int(shape[1]))
+        return cls(rec["sum"].copy(), rec["sum_sq"].copy(), rec["min"].copy(), rec["max"].copy(), rec["nonfinite"].copy(),
+                   region_sizes(shape[0], shape[1], region, rec.shape), region, shape)
+
+    @property
+    def cells(self) -> np.ndarray:
+        """Finite cells per region: the ones the sums, the mean and the variance cover."""
+        return self.size - self.nonfinite.astype(np.int64)
+
+    def mean(self) -> np.ndarray:
+        """Per region, as ``Summary.mean``: NaN where a region has no finite cell."""
+        cells = self.cells.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cells > 0, self.sum / cells, np.nan)
+
+    def variance(self) -> np.ndarray:
+        """Per region, the population variance of the finite cells from the two sums (the square of ``Summary.std``, before
+        its root): NaN where a region has no finite cell."""
+        cells = self.cells.astype(np.float64)
+        m = self.mean()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cells > 0, np.maximum(self.sum_sq / cells - m * m, 0.0), np.nan)
+
+    def at(self, i: int, j: int) -> Summary:
+        return Summary(float(self.sum[i, j]), float(self.sum_sq[i, j]), float(self.min[i, j]), float(self.max[i, j]),
+                       int(self.nonfinite[i, j]), int(self.size[i, j]))
+
+
+@dataclass(frozen=True, eq=False)
+class RegionMorphology:
+    """The bit-quad counts of every region of one thresholded plane, counted on the device
+    (``gs_fields_region_morphology``): ``quads`` of shape ``(RR, RC, 6)``, entry (i, j) being the ``Morphology.quads`` of a
+    plane that holds region (i, j)'s cells alone -- the region padded with its own ring of unset cells.  ``cells`` is every
+    region's number of cells; the derived arrays are ``quad_measures``' exact integers."""
+
+    quads: np.ndarray
+    threshold: float
+    above: bool
+    cells: np.ndarray
+    region: Tuple[int, int]
+    shape: Tuple[int, int]
+
+    @classmethod
+    def from_quads(cls, quads, threshold: float, above: bool, region, shape) -> "RegionMorphology":
+        quads = np.array(quads, np.uint64)
+        region, shape = region_shape(region), (int(shape[0]), int(shape[1]))
+        return cls(quads, float(threshold), bool(above), region_sizes(shape[0], shape[1], region, quads.shape[:2]), region, shape)
+
+    @property
+    def area(self) -> np.ndarray:
+        return quad_measures(self.quads)[0]
+
+    @property
+    def area_fraction(self) -> np.ndarray:
+        return self.area / self.cells
+
+    @property
+    def perimeter(self) -> np.ndarray:
+        return quad_measures(self.quads)[1]
+
+    @property
+    def euler4(self) -> np.ndarray:
+        return quad_measures(self.quads)[2]
+
+    @property
+    def euler8(self) -> np.ndarray:
+        return quad_measures(self.quads)[3]
+
+    def at(self, i: int, j: int) -> Morphology:
+        return Morphology.from_quads(self.quads[i, j], self.threshold, self.above, int(self.cells[i, j]))
+
+
+def region_summaries_fields(context: "HipContext", fields: Sequence["HipConcentration"], region) -> List[RegionSummaries]:
+    """``gs_fields_region_summaries``: the summaries of every region of 1..4 planes of one shape in one call (blocking;
+    collective in a multi-process context).  ``region`` is ``(rh, rw)`` or an int for a square region."""
+    n, (rh, rw) = len(fields), region_shape(region)
+    shape = fields[0].shape() if fields else (0, 0)
+    try:
+        grid = region_grid(shape[0], shape[1], (rh, rw))
+    except capi.GsError:
+        grid = (0, 0)  # (the call below refuses it, in the header's order)
+    out = np.zeros((max(n, 1),) + grid, SUMMARY_DTYPE)
+    capi.check(context._lib.gs_fields_region_summaries(context.handle, _handle_array(fields), n, rh, rw,
+                                                       out.ctypes.data_as(ctypes.POINTER(capi.GsSummary))))
+    return [RegionSummaries.from_records(out[i], (rh, rw), shape) for i in range(n)]
+
+
+def region_morphology_fields(context: "HipContext", fields: Sequence["HipConcentration"], region,
+                             thresholds: Sequence[Sequence[float]], above: Sequence[bool]) -> List[List[RegionMorphology]]:
+    """``gs_fields_region_morphology``: the bit-quad counts of every region of 1..4 planes of one shape in one call
+    (blocking; collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, one pass) with
+    the sense ``above[i]``.  Returns one list of ``RegionMorphology`` per plane, one entry per threshold."""
+    n, nt, thr, sense = _field_thresholds(fields, thresholds, above)
+    rh, rw = region_shape(region)
+    shape = fields[0].shape() if fields else (0, 0)
+    try:
+        grid = region_grid(shape[0], shape[1], (rh, rw))
+    except capi.GsError:
+        grid = (0, 0)
+    out = np.zeros((max(n, 1),) + grid + (max(nt, 1), 6), np.uint64)
+    capi.check(context._lib.gs_fields_region_morphology(context.handle, _handle_array(fields), n, rh, rw, thr, sense, nt,
+                                                        out.ctypes.data_as(ctypes.POINTER(capi.GsMorphology))))
+    return [[RegionMorphology.from_quads(out[i, :, :, k], thr[i * nt + k], above[i], (rh, rw), shape) for k in range(nt)]
+            for i in range(n)]
+
+
 @dataclass(frozen=True, eq=False)
 class Components:
     """The connected components of one thresholded plane, labelled on the device (``gs_fields_components``; the rule is
@@ -1085,6 +1234,17 @@ class HipConcentration:
         is set when it is above (``above``) or below the threshold."""
         return morphology_fields(context, [self], [thresholds], [above])[0]
 
+    def region_summaries(self, context: HipContext, region) -> RegionSummaries:
+        """The summary of every region of ``region`` = (rh, rw) cells (an int: square) of this plane, computed on the device
+        (``gs_fields_region_summaries``; blocking, collective in a multi-process context)."""
+        return region_summaries_fields(context, [self], region)[0]
+
+    def region_morphology(self, context: HipContext, region, thresholds, above: bool = True) -> List[RegionMorphology]:
+        """The bit-quad counts of every region of ``region`` = (rh, rw) cells (an int: square) of this plane thresholded at
+        each of ``thresholds`` (1..4, one pass), counted on the device (``gs_fields_region_morphology``; blocking, collective
+        in a multi-process context)."""
+        return region_morphology_fields(context, [self], region, [thresholds], [above])[0]
+
     def components(self, context: HipContext, thresholds, above: bool = True, connectivity: int = 8) -> List[Components]:
         """The connected components of this plane thresholded at each of ``thresholds`` (1..4) over the whole global grid,
         labelled on the device (``gs_fields_components``; blocking, collective in a multi-process context): a cell is set
@@ -1273,6 +1433,22 @@ class Species:
         the pattern where it is high and U where it is low, hence the default senses; without ``u_thresholds`` only V is
         looked at and the U list is empty."""
         return self._v_or_both(morphology_fields, u_thresholds, v_thresholds, (u_above, v_above))
+
+    def region_summaries(self, region) -> Tuple[RegionSummaries, RegionSummaries]:
+        """(U, V) summaries of every region of ``region`` = (rh, rw) cells (an int: square) of the current state in one call
+        (``gs_fields_region_summaries``; blocking, collective in a multi-process context)."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = region_summaries_fields(self._context, [in_u, in_v], region)
+        return u, v
+
+    def region_morphology(self, region, v_thresholds=(0.25,), u_thresholds=None, v_above: bool = True,
+                          u_above: bool = False) -> Tuple[List[RegionMorphology], List[RegionMorphology]]:
+        """(U, V) bit-quad counts of every region of the current state in one call (``gs_fields_region_morphology``;
+        blocking, collective in a multi-process context): one ``RegionMorphology`` per threshold, thresholds and senses as
+        for ``morphology``; without ``u_thresholds`` only V is looked at and the U list is empty."""
+        def observe(context, fields, thresholds, above):
+            return region_morphology_fields(context, fields, region, thresholds, above)
+        return self._v_or_both(observe, u_thresholds, v_thresholds, (u_above, v_above))
 
     def components(self, v_thresholds=(0.25,), u_thresholds=None,
                    connectivity: int = 8) -> Tuple[List[Components], List[Components]]:

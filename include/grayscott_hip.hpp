@@ -87,6 +87,12 @@ inline std::vector<float> uv_thresholds(const std::vector<float> &u_thresholds, 
     t.insert(t.end(), v_thresholds.begin(), v_thresholds.end());
     return t;
 }
+// The cells of region (i, j) of a grid of rows x cols cells cut into regions of rh x rw: fewer in a ragged last row or column.
+inline uint64_t region_cells(uint64_t rows, uint64_t cols, int32_t rh, int32_t rw, uint64_t i, uint64_t j)
+{
+    const uint64_t h = rows - i * (uint64_t)rh, w = cols - j * (uint64_t)rw;
+    return (h < (uint64_t)rh ? h : (uint64_t)rh) * (w < (uint64_t)rw ? w : (uint64_t)rw);
+}
 } // namespace detail
 
 // A plane's summary computed on the device (gs_summary): sum, sum of squares, min and max of its finite cells (fold order
@@ -181,6 +187,18 @@ struct Morphology {
     int64_t euler4() const { return ((int64_t)quads[1] - (int64_t)quads[3] + 2 * (int64_t)quads[5]) / 4; }
     int64_t euler8() const { return ((int64_t)quads[1] - (int64_t)quads[3] - 2 * (int64_t)quads[5]) / 4; }
 };
+
+// The results of every region of one plane (gs_fields_region_summaries, gs_fields_region_morphology; the rules are gs_hip.h's):
+// a region shape (rh, rw) cuts the plane into rr x rc regions, ragged ones at the lower and right edge kept, and `at(i, j)` is
+// bit for bit the whole-grid result of a plane that holds region (i, j)'s cells alone.
+template <typename T> struct Regions {
+    uint64_t rr = 0, rc = 0;
+    int32_t rh = 0, rw = 0;
+    std::vector<T> results; // rr * rc, region (i, j) at i * rc + j
+    const T &at(uint64_t i, uint64_t j) const { return results.at((std::size_t)(i * rc + j)); }
+};
+using RegionSummaries = Regions<Summary>;
+using RegionMorphology = Regions<Morphology>; // of one threshold
 
 // The connected components of one thresholded plane, labelled on the device (gs_fields_components; the rule is gs_hip.h's): a
 // cell is set by Morphology's rule, set cells are neighbours across a side or, under connectivity 8, also across a corner;
@@ -600,6 +618,56 @@ class Species {
             uv.first.push_back(Morphology::from_c(out[k], t[k], u_above, s[0] * s[1]));
             uv.second.push_back(Morphology::from_c(out[nt + k], t[nt + k], v_above, s[0] * s[1]));
         }
+        return uv;
+    }
+    // (U, V) summaries of every region of rh x rw cells of the current state, in one call (gs_fields_region_summaries;
+    // blocking, collective in a multi-process context)
+    std::pair<RegionSummaries, RegionSummaries> region_summaries(int32_t rh, int32_t rw)
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const Shape s = shape();
+        uint64_t rr = 0, rc = 0;
+        check(gs_region_grid(s[0], s[1], rh, rw, &rr, &rc));
+        const std::size_t regions = (std::size_t)(rr * rc);
+        std::vector<gs_summary> out(2 * regions + 1);
+        check(gs_fields_region_summaries(context_->get(), planes, 2, rh, rw, out.data()));
+        std::pair<RegionSummaries, RegionSummaries> uv;
+        RegionSummaries *both[2] = {&uv.first, &uv.second};
+        for (std::size_t p = 0; p < 2; ++p) {
+            *both[p] = RegionSummaries{rr, rc, rh, rw, {}};
+            for (std::size_t r = 0; r < regions; ++r)
+                both[p]->results.push_back(Summary::from_c(out[p * regions + r], detail::region_cells(s[0], s[1], rh, rw, r / rc, r % rc)));
+        }
+        return uv;
+    }
+    // (U, V) bit-quad counts of every region of rh x rw cells of the current state, in one call (gs_fields_region_morphology;
+    // blocking, collective in a multi-process context): one RegionMorphology per threshold, thresholds and senses as for
+    // morphology()
+    std::pair<std::vector<RegionMorphology>, std::vector<RegionMorphology>> region_morphology(int32_t rh, int32_t rw,
+                                                                                              const std::vector<float> &v_thresholds,
+                                                                                              const std::vector<float> &u_thresholds,
+                                                                                              bool v_above = true, bool u_above = false)
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t nt = v_thresholds.size();
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
+        const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
+        const Shape s = shape();
+        uint64_t rr = 0, rc = 0;
+        check(gs_region_grid(s[0], s[1], rh, rw, &rr, &rc));
+        const std::size_t regions = (std::size_t)(rr * rc);
+        std::vector<gs_morphology> out(2 * regions * nt + 1);
+        check(gs_fields_region_morphology(context_->get(), planes, 2, rh, rw, t.data(), sense, (int32_t)nt, out.data()));
+        std::pair<std::vector<RegionMorphology>, std::vector<RegionMorphology>> uv;
+        std::vector<RegionMorphology> *both[2] = {&uv.first, &uv.second};
+        for (std::size_t p = 0; p < 2; ++p)
+            for (std::size_t k = 0; k < nt; ++k) {
+                RegionMorphology m{rr, rc, rh, rw, {}};
+                for (std::size_t r = 0; r < regions; ++r)
+                    m.results.push_back(Morphology::from_c(out[(p * regions + r) * nt + k], t[p * nt + k], p ? v_above : u_above,
+                                                           detail::region_cells(s[0], s[1], rh, rw, r / rc, r % rc)));
+                both[p]->push_back(std::move(m));
+            }
         return uv;
     }
     // (U, V) connected components of the current state over the whole global grid, in one call (gs_fields_components; blocking,

@@ -644,6 +644,43 @@ int32_t gs_fields_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
 int32_t gs_members_morphology(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
                               const int32_t above[2], int32_t nt, gs_morphology *out);
 
+/* Regional observables computed on the device: the summary and the bit-quad counts of every REGION of one plane of the global
+ * grid -- which part of a parameter map's grid grew spots, which stripes, which died, which blew up -- without downloading
+ * the plane.  A region shape (rh, rw) cuts the global grid of R x C cells into RR = ceil(R / rh) by RC = ceil(C / rw) regions:
+ * region (i, j), of index i * RC + j, holds rows [i rh, min((i + 1) rh, R)) and columns [j rw, min((j + 1) rw, C)).  The last
+ * row and column of regions may be ragged; they are kept, never dropped.
+ * The rule that defines every result: a region's result is, bit for bit, what gs_fields_summarize / gs_fields_morphology
+ * return for a field that holds exactly that region's cells.
+ *   - summary: the fold order above with columns counted from the region's FIRST column -- lane l adds the region's columns
+ *     256 k + 4 l + j, the halving lane combine follows, then the region's rows are added in ascending order from +0.0.  min,
+ *     max, nonfinite, sub-normal cells and the sign of a zero extreme: as for the whole grid.
+ *   - morphology: the region's thresholded image is padded with its OWN ring of unset cells -- a region never sees its
+ *     neighbours' cells, as an ensemble member never sees its neighbours' rows.  A region of h x w cells has (h + 1)(w + 1)
+ *     quads in the six classes, which sum to that; the set rule is morphology's (NaN and equal-to-threshold cells unset).
+ *     The regions do not partition the quads of the global grid.
+ * Results are the same bits for any slab count, process count, step kernel or launch shape and do not depend on the
+ * boundary rule; with a domain mask attached wall cells count, as in the whole-grid calls.
+ *   gs_region_grid               *rr = RR and *rc = RC for a grid of rows x cols cells, or the refusal of a region shape.
+ *                                Pure: no handle, no device.
+ *   gs_fields_region_summaries   out[p * RR RC + i RC + j] for region (i, j) of fields[p], p < n (1..4 fields of one shape).
+ *   gs_fields_region_morphology  out[(p * RR RC + i RC + j) * nt + k] for region (i, j) of fields[p] thresholded at
+ *                                thresholds[p * nt + k] with the sense above[p], k < nt (1..4 thresholds per field, all counted
+ *                                in one pass over the plane); Q0 is the host's complement, as for the whole grid.
+ * Both wait once for enqueued work (as gs_fields_summarize: a persistent window launch that gave up is run again first), read
+ * every plane once with one launch per slab, block, and have no side effects (ghost rows, tuner, graphs and gs_stats are
+ * left as they are).  In a multi-process context they are collective, like gs_run, and every rank receives every region.
+ * Limits, all decided before any device work -- GS_ERR_INVALID: rw not a multiple of 4 or below 16 (a lane's four columns
+ * never straddle two regions); rh < 1; RR RC > GS_REGIONS_MAX (a cap on result memory: 128 MiB of summaries per plane); a
+ * null argument, nt outside 1..4 or a NaN threshold -- decided before any handle is looked at --; a null or foreign handle,
+ * mixed shapes, n outside 1..4.  GS_ERR_UNSUPPORTED, on every rank alike: a context of several slabs or processes in which
+ * some slab begins at a row that is no multiple of rh (as for gs_field_download_reduced: a region lies inside one slab, no
+ * ghost row is read and no row is staged).  An empty plane: GS_OK, nothing is written. */
+#define GS_REGIONS_MAX (1u << 22)
+int32_t gs_region_grid(uint64_t rows, uint64_t cols, int32_t rh, int32_t rw, uint64_t *rr, uint64_t *rc);
+int32_t gs_fields_region_summaries(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, gs_summary *out);
+int32_t gs_fields_region_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw,
+                                    const float *thresholds, const int32_t *above, int32_t nt, gs_morphology *out);
+
 /* Two-point correlations computed on the device: the two-point probability function of one plane of the WHOLE global grid
  * after thresholding -- for a lag vector, the number of cell pairs that far apart which are both set; from it the pattern's
  * wavelength and the direction of its stripes follow ("how far apart are the spots?") -- without downloading the plane.  For

@@ -81,6 +81,16 @@ pub struct gs_summary {
     pub nonfinite: u64,
 }
 
+/// `gs_morphology` (include/gs_hip.h): the bit-quad counts of one thresholded plane or region -- Q0, Q1, Q2, Q3, Q4, QD.  48 bytes.
+#[repr(C)]
+#[derive(Copy, Clone, Debug, Default)]
+pub struct gs_morphology {
+    pub quads: [u64; 6],
+}
+
+/// `GS_REGIONS_MAX` (include/gs_hip.h): the most regions a region shape may cut a grid into.
+pub const GS_REGIONS_MAX: u64 = 1 << 22;
+
 /// `gs_change` (include/gs_hip.h): how far one plane is from another -- sums of |d| and d * d and the largest |d| over the
 /// cells finite in both (d = a - b in f64), cells whose bits differ, cells not finite in either.  40 bytes.
 #[repr(C)]
@@ -188,6 +198,29 @@ extern "C" {
         first: u64,
         count: u64,
         out: *mut gs_summary,
+    ) -> i32;
+    /// Regional observables (gs_hip.h): `rr` x `rc` regions of `rh` x `rw` cells cut a grid of `rows` x `cols`; pure.
+    pub fn gs_region_grid(rows: u64, cols: u64, rh: i32, rw: i32, rr: *mut u64, rc: *mut u64) -> i32;
+    /// `out`: n x rr x rc records, region (i, j) of `fields[p]` at `p * rr * rc + i * rc + j`.
+    pub fn gs_fields_region_summaries(
+        ctx: *mut gs_ctx,
+        fields: *const *mut gs_field,
+        n: i32,
+        rh: i32,
+        rw: i32,
+        out: *mut gs_summary,
+    ) -> i32;
+    /// `thresholds`: n x nt, `above`: n senses; `out`: n x rr x rc x nt records.
+    pub fn gs_fields_region_morphology(
+        ctx: *mut gs_ctx,
+        fields: *const *mut gs_field,
+        n: i32,
+        rh: i32,
+        rw: i32,
+        thresholds: *const f32,
+        above: *const i32,
+        nt: i32,
+        out: *mut gs_morphology,
     ) -> i32;
     /// Pair i: `a[i]` against `b[i]`, n = 1..4 pairs of one shape; `out`: n records.
     pub fn gs_fields_compare(
