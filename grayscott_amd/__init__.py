@@ -27,9 +27,10 @@ from .simulation import (  # noqa: F401
     Snapshot,
     Species,
     Summary,
+    TimeStats,
     correlation_fields,
     pinned_empty,
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "correlation_fields", "pinned_empty"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]

@@ -72,6 +72,9 @@ UNITS = [
     ("gs_reduce.hip", "gs_reduce_k.o", []),
     # two planes compared (row records of |a - b| in f64, the ensembles' fold): the same float mode, sub-normal cells kept
     ("gs_change.hip", "gs_change_k.o", []),
+    # time statistics (per-cell f64 sums, f32 extremes and u32 crossing counters read, updated and written back per sample):
+    # the same float mode, a sub-normal sample counts as the value it is
+    ("gs_time_stats.hip", "gs_time_stats_k.o", []),
     # the host side (contexts and schedule, planes, kernel configuration, the window kernel's runtime, RCCL): only the
     # C ABI of include/gs_hip.h is visible outside the library
     ("gs_api.cpp", "gs_api.o", ["-x", "hip", "-fvisibility=hidden"]),
@@ -82,6 +85,7 @@ UNITS = [
     ("gs_ensemble.cpp", "gs_ensemble.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_attached.cpp", "gs_attached.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_observe.cpp", "gs_observe.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_time_stats.cpp", "gs_time_stats.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

@@ -26,6 +26,11 @@ GS_MATH_STRICT, GS_MATH_FUSED = 0, 1
 GS_KERNEL_AUTO, GS_KERNEL_SIMPLE, GS_KERNEL_STREAM, GS_KERNEL_TB, GS_KERNEL_LDS, GS_KERNEL_TILE, GS_KERNEL_WINDOW = 0, 1, 2, 3, 4, 5, 6
 GS_BOUNDARY_CLIPPED, GS_BOUNDARY_ZERO_HALO, GS_BOUNDARY_PERIODIC, GS_BOUNDARY_NEUMANN = 0, 1, 2, 3
 GS_UNIQUE_ID_BYTES = 128
+# time statistics (include/gs_hip.h): the groups of accumulators, the result planes and the raw accumulators
+GS_TSTAT_SUM, GS_TSTAT_SQUARES, GS_TSTAT_EXTREMES, GS_TSTAT_CROSSINGS = 1, 2, 4, 8
+GS_TSTAT_MEAN, GS_TSTAT_VARIANCE, GS_TSTAT_MIN, GS_TSTAT_MAX, GS_TSTAT_OCCUPANCY, GS_TSTAT_ARRIVAL = 0, 1, 2, 3, 4, 5
+(GS_TSTAT_RAW_SUM, GS_TSTAT_RAW_SQUARES, GS_TSTAT_RAW_MIN, GS_TSTAT_RAW_MAX, GS_TSTAT_RAW_SET_COUNT,
+ GS_TSTAT_RAW_FIRST_STAMP) = 0, 1, 2, 3, 4, 5
 
 # Every symbol include/gs_hip.h declares; tests check that the library exports them all.
 EXPORTS = (
@@ -56,6 +61,9 @@ EXPORTS = (
     "gs_fields_components", "gs_members_components",
     "gs_field_component_list", "gs_members_component_list", "gs_component_list_view", "gs_component_list_destroy",
     "gs_fields_match", "gs_members_match", "gs_component_match_view", "gs_component_match_destroy",
+    "gs_time_stats_create", "gs_time_stats_destroy", "gs_time_stats_reset", "gs_time_stats_accumulate", "gs_time_stats_samples",
+    "gs_time_stats_result", "gs_time_stats_download",
+    "gs_members_time_stats_create", "gs_members_time_stats_accumulate", "gs_members_time_stats_result",
 )
 
 
@@ -205,6 +213,7 @@ def load() -> ctypes.CDLL:
                       "(there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
     vp, i32, u64, f32 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_uint64, ctypes.c_float
+    u32 = ctypes.c_uint32
     P = ctypes.POINTER
     sig = {
         "gs_default_params": (None, [P(GsParams)]),
@@ -293,6 +302,16 @@ def load() -> ctypes.CDLL:
         "gs_component_match_destroy": (i32, [vp]),
         "gs_fields_correlation": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(u64)]),
         "gs_members_correlation": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(u64)]),
+        "gs_time_stats_create": (i32, [vp, P(vp), u64, u64, i32, u32, P(f32), P(i32)]),
+        "gs_time_stats_destroy": (i32, [vp, vp]),
+        "gs_time_stats_reset": (i32, [vp, vp]),
+        "gs_time_stats_accumulate": (i32, [vp, vp, P(vp), i32, u32]),
+        "gs_time_stats_samples": (i32, [vp, P(u64)]),
+        "gs_time_stats_result": (i32, [vp, vp, i32, i32, vp]),
+        "gs_time_stats_download": (i32, [vp, vp, i32, i32, vp]),
+        "gs_members_time_stats_create": (i32, [vp, P(vp), vp, u64, u64, u32, P(f32), P(i32)]),
+        "gs_members_time_stats_accumulate": (i32, [vp, vp, vp, u32]),
+        "gs_members_time_stats_result": (i32, [vp, vp, i32, i32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

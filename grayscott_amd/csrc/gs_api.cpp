@@ -573,6 +573,7 @@ int32_t gs_device_count(int32_t *out)
 int32_t gs_ctx_destroy(gs_ctx *ctx)
 {
     if (!ctx) return GS_OK;
+    destroy_time_stats(ctx);
     destroy_attached(ctx);
     destroy_scratch(ctx);
     for (auto &sl : ctx->slabs) {

@@ -6,6 +6,32 @@
 
 using namespace gsi;
 
+namespace gsi {
+
+int32_t plane_layout(const gs_ctx *ctx, uint64_t rows, uint64_t cols, PlaneLayout &out)
+{
+    const uint64_t S = (uint64_t)ctx->total_slabs();
+    // An empty grid is legal in the reference (ndarray holds zero-sized arrays and every step is a
+    // no-op on them); here it is a single slab with no rows or no columns that no kernel touches.
+    if (rows < S && !(rows == 0 && S == 1))
+        return fail(GS_ERR_INVALID, "%llu rows cannot be split over %llu slabs",
+                    (unsigned long long)rows, (unsigned long long)S);
+    const int pad = ctx->o.pitch_pad > 0 ? ((ctx->o.pitch_pad + 3) / 4) * 4 : 0;
+    out.pitch = (cols == 0 ? 64 : ((cols + 63) / 64) * 64) + (uint64_t)pad;
+    if (out.pitch > 0x7ffffff0ull) return fail(GS_ERR_UNSUPPORTED, "too many columns");
+    out.slabs.clear();
+    for (size_t i = 0; i < ctx->slabs.size(); ++i) {
+        const uint64_t k = (uint64_t)ctx->global_index((int)i);
+        const uint64_t r0 = k * rows / S, r1 = (k + 1) * rows / S;
+        if (r1 - r0 > 0x7ffffff0ull || (r1 - r0 + 2 * kGhostRows) * out.pitch > 0x7ffffff0ull * 4ull)
+            return fail(GS_ERR_UNSUPPORTED, "slab too large for 32-bit row indexing");
+        out.slabs.emplace_back(r0, r1 - r0);
+    }
+    return GS_OK;
+}
+
+} // namespace gsi
+
 extern "C" {
 
 int32_t gs_field_destroy(gs_ctx *ctx, gs_field *f)
@@ -25,15 +51,9 @@ int32_t gs_field_create(gs_ctx *ctx, gs_field **out, uint64_t rows, uint64_t col
 {
     if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
     *out = nullptr;
-    const uint64_t S = (uint64_t)ctx->total_slabs();
-    // An empty grid is legal in the reference (ndarray holds zero-sized arrays and every step is a
-    // no-op on them); here it is a single slab with no rows or no columns that no kernel touches.
-    if (rows < S && !(rows == 0 && S == 1))
-        return fail(GS_ERR_INVALID, "%llu rows cannot be split over %llu slabs",
-                    (unsigned long long)rows, (unsigned long long)S);
-    const int pad = ctx->o.pitch_pad > 0 ? ((ctx->o.pitch_pad + 3) / 4) * 4 : 0;
-    const uint64_t pitch = (cols == 0 ? 64 : ((cols + 63) / 64) * 64) + (uint64_t)pad;
-    if (pitch > 0x7ffffff0ull) return fail(GS_ERR_UNSUPPORTED, "too many columns");
+    PlaneLayout layout;
+    GS_TRY(plane_layout(ctx, rows, cols, layout));
+    const uint64_t pitch = layout.pitch;
     gs_field *f = new (std::nothrow) gs_field();
     if (!f) return fail(GS_ERR_NOMEM, "out of host memory");
     f->ctx = ctx;
@@ -42,15 +62,9 @@ int32_t gs_field_create(gs_ctx *ctx, gs_field **out, uint64_t rows, uint64_t col
     f->pitch = (int32_t)pitch;
     f->s.resize(ctx->slabs.size());
     for (size_t i = 0; i < ctx->slabs.size(); ++i) {
-        const uint64_t k = (uint64_t)ctx->global_index((int)i);
-        const uint64_t r0 = k * rows / S, r1 = (k + 1) * rows / S;
-        if (r1 - r0 > 0x7ffffff0ull || (r1 - r0 + 2 * kGhostRows) * pitch > 0x7ffffff0ull * 4ull) {
-            gs_field_destroy(ctx, f);
-            return fail(GS_ERR_UNSUPPORTED, "slab too large for 32-bit row indexing");
-        }
         FieldSlab &fs = f->s[i];
-        fs.g_row0 = r0;
-        fs.rows = (int32_t)(r1 - r0);
+        fs.g_row0 = layout.slabs[i].first;
+        fs.rows = (int32_t)layout.slabs[i].second;
         const size_t n = (size_t)(fs.rows + 2 * kGhostRows) * pitch + 2 * kGuardFloats;
         hipError_t e = hipSetDevice(ctx->slabs[i].device);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&fs.alloc), n * sizeof(float));

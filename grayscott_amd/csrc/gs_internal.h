@@ -16,6 +16,8 @@
 //                  gs_members_match), summaries and bit-quad counts per region of one grid (gs_fields_region_summaries,
 //                  gs_fields_region_morphology), comparisons of two states
 //                  (gs_fields_compare, gs_members_compare) and the device copies behind snapshots (gs_fields_copy, gs_members_copy)
+//   gs_time_stats.cpp time statistics: per-cell accumulators over the samples of a run, kept on the device (gs_time_stats_*,
+//                  gs_members_time_stats_*)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)
@@ -37,6 +39,7 @@
 #include <cstring>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace gsi {
@@ -220,6 +223,7 @@ struct gs_ctx {
         int32_t *seen = nullptr; // pinned, two words: the abort word as either image stream last saw it
     } win;
     int cu_count = 0; // compute units of the first slab's device
+    std::vector<struct gs_time_stats *> time_stats; // the time statistics made on this context and not destroyed yet (gs_time_stats.cpp)
     // The context's per-cell data (gs_attached.cpp), one kind at a time: a parameter map (gs_ctx_set_param_map: plane[0] = F,
     // plane[1] = F + K) or a domain mask (gs_ctx_set_mask: plane[0] = a u32 link word per cell, gs_cell.h: link_bit).  The
     // planes are owned by the context, in the field layout of the species with their ghost rows filled.  `gen` advances with
@@ -338,6 +342,15 @@ int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *la
 int32_t check_attached_shape(const gs_ctx *ctx, const gs_field *f);
 void destroy_attached(gs_ctx *ctx);
 
+// gs_fields.cpp: how a plane of rows x cols cells lies on this context -- the row pitch in floats and, per local slab, its first
+// global row and its rows -- or gs_field_create's refusals.  Whatever follows a field's rows (gs_time_stats) takes it from here.
+struct PlaneLayout {
+    uint64_t pitch = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> slabs; // (first global row, rows)
+};
+int32_t plane_layout(const gs_ctx *ctx, uint64_t rows, uint64_t cols, PlaneLayout &out);
+// gs_time_stats.cpp: the time statistics a context still owns, freed with it
+void destroy_time_stats(gs_ctx *ctx);
 // gs_fields.cpp: this process's rows of the image of `f` reduced by `factor` (>= 2) into `host`, on a context whose streams
 // are idle (the blocking download after its wait; resolve_window after a replay): through staging buffer 0, done on return.
 int32_t fetch_reduced(gs_ctx *ctx, gs_field *f, int32_t factor, float *host);

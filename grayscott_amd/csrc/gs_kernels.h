@@ -372,3 +372,25 @@ hipError_t gs_launch_piece_labels(const uint32_t *both_b, const uint32_t *both_a
 hipError_t gs_launch_match_pairs(const uint32_t *parent_b, const uint32_t *index_b, const uint32_t *parent_a, const uint32_t *index_a,
                                  const uint32_t *parent_p, const uint32_t *size_p, const uint32_t *counts, int64_t planes,
                                  int64_t rows, int32_t cols, GsMatchOverlap *overlaps, hipStream_t s);
+
+// Time statistics (gs_time_stats.hip; include/gs_hip.h: gs_time_stats_accumulate).  Per-cell accumulators over the samples of
+// np (1..4) planes of one shape -- rows [0, rows) of `pitch` floats, `cols` columns: plane y's are `plane_stride` elements
+// behind plane y - 1's in each accumulator array, rows of the planes' own pitch, no ghost rows.  An array whose group
+// (GS_TSTAT_SUM, _SQUARES, _EXTREMES, _CROSSINGS of gs_hip.h) is not selected is null and never touched.  t / flip: the set
+// rule of gs_plane_scan.h per plane.
+struct GsTstatAcc {
+    double *sum, *squares;
+    float *mn, *mx;
+    uint32_t *set_count, *first_stamp;
+    int64_t plane_stride;
+};
+// One sample of every plane added (rows may be 64-bit: an ensemble's members are one tall plane per species); at most
+// `max_groups` workgroups.
+hipError_t gs_launch_tstat_accumulate(const float *const *planes, int np, int64_t pitch, int64_t rows, int32_t cols, uint32_t groups,
+                                      const GsTstatAcc &acc, const float *t, const uint32_t *flip, uint32_t stamp,
+                                      int64_t max_groups, hipStream_t s);
+// The selected accumulators of np planes back to their reset values.
+hipError_t gs_launch_tstat_reset(int np, uint32_t groups, const GsTstatAcc &acc, hipStream_t s);
+// One result plane (`which`: GS_TSTAT_MEAN .. GS_TSTAT_ARRIVAL) of plane `plane` after n samples into out, rows of `pitch` floats.
+hipError_t gs_launch_tstat_result(int which, int plane, const GsTstatAcc &acc, int64_t pitch, int64_t rows, int32_t cols, uint64_t n,
+                                  float *out, hipStream_t s);

@@ -38,6 +38,14 @@ parameter map the file also holds ``feed`` and ``kill``, the regions' means of t
 phase diagram.  In a multi-process run rank 0 writes.  The two calls block: an observed image is waited for before the next
 steps are enqueued, so with ``--hip-regions-every 1`` no download overlaps the steps of the next image any more (the pipeline of
 two images in flight runs dry at every observed image); the default, the last image alone, costs nothing before the end.
+
+Time statistics (``gs_time_stats``): ``--hip-time-stats-every N`` samples U and V every N steps -- from step S on with
+``--hip-time-stats-from S`` (default N; 0: the initial state too), at steps S, S + N, ..., each stamped with its step count -- into per-cell accumulators on
+the device and writes, at the end, ``<stem>.timestats.npz``: ``samples``, ``steps`` and the planes ``mean_v``, ``var_v``,
+``min_v``, ``max_v`` (and ``_u``), with ``--hip-time-stats-threshold-v T`` also ``occupancy_v`` and ``arrival_v`` (V set above
+T; -1 where the front never arrived).  A sample waits for the steps enqueued before it and splits an image's steps where it
+falls between two images; the images are bit for bit what they are without the option.  In a multi-process run every rank
+writes its own rows, ``<stem>.timestats.rank<q>.npz`` with ``rows`` = its row range.
 """
 from __future__ import annotations
 
@@ -71,7 +79,9 @@ def parse(argv=None):
     add_mask_args(ap)
     add_image_args(ap)
     add_region_args(ap)
+    add_time_stats_args(ap)
     args = ap.parse_args(argv)
+    check_time_stats_args(ap, args, "hip_time_stats", "--hip-time-stats")
     tu, tv = args.hip_region_threshold_u, args.hip_region_threshold_v or [0.25]
     if tu is not None and len(tu) != len(tv):
         ap.error(f"--hip-region-threshold-u wants as many thresholds as --hip-region-threshold-v ({len(tv)}), not {len(tu)}")
@@ -181,6 +191,69 @@ def add_region_args(ap: argparse.ArgumentParser) -> None:
                     help="V is set above these thresholds (1..4; default 0.25)")
     rg.add_argument("--hip-region-threshold-u", type=_threshold_list, default=None, metavar="A[,B...]",
                     help="U is set below these thresholds (as many as V's; default: U's quads are not counted)")
+
+
+def add_time_stats_args(ap: argparse.ArgumentParser, prefix: str = "--hip-time-stats") -> None:
+    """The time statistics' options (``--hip-time-stats-*`` here, ``--time-stats-*`` in ``grayscott_amd.sweep``)."""
+    ts = ap.add_argument_group("HIP backend: time statistics")
+    ts.add_argument(f"{prefix}-every", type=int, default=0, metavar="N",
+                    help="sample U and V every N steps into per-cell accumulators on the device (<stem>.timestats.npz)")
+    ts.add_argument(f"{prefix}-from", type=int, default=None, metavar="S", help="the first sampled step (default N)")
+    ts.add_argument(f"{prefix}-threshold-v", type=float, default=None, metavar="T",
+                    help="also record for what share of the samples V was above T and at which step it first was")
+
+
+def check_time_stats_args(ap: argparse.ArgumentParser, args, name: str, flag: str) -> None:
+    """The refusals of the time statistics' options; leaves ``<name>_from`` filled in."""
+    every, start, t = (getattr(args, f"{name}_{k}") for k in ("every", "from", "threshold_v"))
+    if every < 0:
+        ap.error(f"{flag}-every must be at least 1 (0 = off)")
+    if not every and start is not None:
+        ap.error(f"{flag}-from needs {flag}-every")
+    if not every and t is not None:
+        ap.error(f"{flag}-threshold-v needs {flag}-every")
+    if start is not None and start < 0:
+        ap.error(f"{flag}-from must be at least 0")
+    if t is not None and t != t:
+        ap.error(f"{flag}-threshold-v must be a number")
+    if every and start is None:
+        setattr(args, f"{name}_from", every)
+
+
+def time_stats_path(output: str, rank: int = 0, world: int = 1) -> str:
+    """The time statistics' file next to the output file (one per rank in a multi-process run)."""
+    return os.path.splitext(output)[0] + (".timestats.npz" if world == 1 else f".timestats.rank{rank}.npz")
+
+
+def time_stats_steps(steps: int, every: int, start: int):
+    """The sampled steps of a run of ``steps`` steps: ``start``, ``start + every``, ... up to ``steps``."""
+    return list(range(start, steps + 1, every)) if every else []
+
+
+def time_stats_groups(threshold_v) -> tuple:
+    return ("sum", "squares", "extremes") + (("crossings",) if threshold_v is not None else ())
+
+
+def write_time_stats(path: str, samples: int, steps, planes: dict, extra: dict = None) -> None:
+    """``planes``: {"mean_v": array, ...} as the ``TimeStats`` result methods name them; everything goes into one .npz."""
+    with open(path, "wb") as f:
+        np.savez(f, samples=np.int64(samples), steps=np.asarray(steps, np.int64), **planes, **(extra or {}))
+
+
+TIME_STATS_PLANES = (("mean", "mean"), ("var", "variance"), ("min", "min"), ("max", "max"))
+TIME_STATS_CROSSING_PLANES = (("occupancy", "occupancy"), ("arrival", "arrival"))
+
+
+def time_stats_planes(stats, threshold_v, read) -> dict:
+    """Every plane the options ask for from a ``TimeStats``: ``read(plane)`` turns what a result method returns into an array."""
+    out = {}
+    for species in ("v", "u"):
+        for key, method in TIME_STATS_PLANES:
+            out[f"{key}_{species}"] = read(getattr(stats, method)(species))
+    if threshold_v is not None:
+        for key, method in TIME_STATS_CROSSING_PLANES:
+            out[f"{key}_v"] = read(getattr(stats, method)("v"))
+    return out
 
 
 def regions_path(output: str) -> str:
@@ -407,6 +480,17 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
             while full.get() is not None:
                 pass
 
+    ts_every = int(getattr(args, "hip_time_stats_every", 0) or 0)
+    ts_threshold = getattr(args, "hip_time_stats_threshold_v", None)
+    ts_from = getattr(args, "hip_time_stats_from", None)  # (0 is a step like any other: the initial state)
+    ts_at = time_stats_steps(args.nbimage * steps_per_image, ts_every, ts_every if ts_from is None else ts_from)
+    stats = species.time_stats(time_stats_groups(ts_threshold), v_threshold=ts_threshold) if ts_at else None
+    ts_next, ts_taken, done = 0, [], 0
+    if ts_at and ts_at[0] == 0:                             # the initial state is a sample too when asked for
+        stats.accumulate(0)
+        ts_taken.append(0)
+        ts_next = 1
+
     thread = threading.Thread(target=writer, daemon=True)
     thread.start()
     t0 = time.perf_counter()
@@ -416,7 +500,18 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
             image = free.get()
             if failed.is_set() or image is None:
                 break
-            sim.prepare_steps(species, steps_per_image)     # enqueued; nothing here waits for the device
+            if stats is None:
+                sim.prepare_steps(species, steps_per_image)  # enqueued; nothing here waits for the device
+            else:                                           # the same steps, cut where a sample falls
+                end = done + steps_per_image
+                while done < end:
+                    upto = min(end, ts_at[ts_next]) if ts_next < len(ts_at) else end
+                    sim.prepare_steps(species, upto - done)
+                    done = upto
+                    if ts_next < len(ts_at) and done == ts_at[ts_next]:
+                        stats.accumulate(done)              # waits for the steps, enqueues one launch, returns
+                        ts_taken.append(done)
+                        ts_next += 1
             species.write_result_view_after(image, reduce)  # this image: staged + copied behind those steps while we go on
             pending.append(image)
             if regions is not None and regions_observed(index, args.nbimage, getattr(args, "hip_regions_every", None)):
@@ -442,6 +537,17 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
         out.flush()
     if regions is not None and getattr(args, "rank", 0) == 0:
         regions.save(regions_path(args.output), shape, pmap)
+    if stats is not None:
+        def read(plane):
+            a = plane.make_scalar_view(ctx)
+            plane.destroy()
+            return a
+
+        planes = time_stats_planes(stats, ts_threshold, read) if stats.samples else {}
+        r0, r1 = species.in_out()[0].local_rows()
+        write_time_stats(time_stats_path(args.output, ctx.args.rank, ctx.args.world), stats.samples, ts_taken, planes,
+                         {"rows": np.array([r0, r1], np.int64), "threshold_v": np.float32(np.nan if ts_threshold is None else ts_threshold)})
+        stats.close()
     cells = shape[0] * shape[1]
     image_bytes = img_shape[0] * img_shape[1] * 4          # what really crossed the link per image
     info = {

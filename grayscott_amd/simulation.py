@@ -21,6 +21,7 @@ no Rust toolchain.  All arithmetic happens in ``libgs_hip.so``; there is no CPU 
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Callable, List, Optional, Sequence, Tuple
@@ -1341,6 +1342,156 @@ class Snapshot:
         self.v.destroy()
 
 
+class TimeStats:
+    """Per-cell statistics over the samples of a run, kept on the device (``gs_time_stats``, include/gs_hip.h): made by
+    ``Species.time_stats`` or ``Ensemble.time_stats``, fed with ``accumulate(stamp)`` between ``perform_steps`` calls.
+    ``groups`` names what is kept: ``"sum"`` (mean), ``"squares"`` (with ``"sum"``: variance), ``"extremes"`` (min, max),
+    ``"crossings"`` (occupancy, arrival; needs a threshold).  For a Species the result planes are ``HipConcentration``s --
+    every observable, reduced download and colour map applies to them --, for an ensemble numpy arrays of
+    ``[count, rows, cols]``.  No standard deviation is formed on the device: take ``np.sqrt`` of the variance read."""
+
+    GROUPS = {"sum": capi.GS_TSTAT_SUM, "squares": capi.GS_TSTAT_SQUARES, "extremes": capi.GS_TSTAT_EXTREMES,
+              "crossings": capi.GS_TSTAT_CROSSINGS}
+    RAW = {"sum": (capi.GS_TSTAT_RAW_SUM, np.float64), "squares": (capi.GS_TSTAT_RAW_SQUARES, np.float64),
+           "min": (capi.GS_TSTAT_RAW_MIN, np.float32), "max": (capi.GS_TSTAT_RAW_MAX, np.float32),
+           "set_count": (capi.GS_TSTAT_RAW_SET_COUNT, np.uint32), "first_stamp": (capi.GS_TSTAT_RAW_FIRST_STAMP, np.uint32)}
+    NEVER = 0xFFFFFFFF     # first_stamp of a cell that was never set; no sample may carry it
+
+    @classmethod
+    def group_bits(cls, groups) -> int:
+        """``groups`` as the C ABI takes them: an int, a name or a sequence of names."""
+        if isinstance(groups, (int, np.integer)):
+            return int(groups)
+        names = [groups] if isinstance(groups, str) else list(groups)
+        bits = 0
+        for name in names:
+            if name not in cls.GROUPS:
+                raise ValueError(f"unknown group {name!r}: one of {sorted(cls.GROUPS)}")
+            bits |= cls.GROUPS[name]
+        return bits
+
+    def __init__(self, context: "HipContext", source, groups, u_threshold=None, v_threshold=None, above=True,
+                 first: int = 0, count: Optional[int] = None):
+        self._ctx, self._source = context, source
+        self._h = ctypes.c_void_p()
+        self.groups = self.group_bits(groups)
+        thresholds = above_arr = None
+        if u_threshold is not None or v_threshold is not None:
+            # (a species whose threshold is not given is never set: nothing is above +inf)
+            t = [math.inf if x is None else float(x) for x in (u_threshold, v_threshold)]
+            senses = [above, above] if isinstance(above, (bool, int)) else list(above)
+            senses = [bool(senses[i]) if x is not None else True for i, x in enumerate((u_threshold, v_threshold))]
+            thresholds, above_arr = (ctypes.c_float * 2)(*t), (ctypes.c_int32 * 2)(*[int(a) for a in senses])
+        self._ensemble = isinstance(source, Ensemble)
+        lib = context._lib
+        if self._ensemble:
+            self._first, self._count = source._range(first, count)
+            self._shape = source.shape()
+            capi.check(lib.gs_members_time_stats_create(context.handle, ctypes.byref(self._h), source.handle, self._first,
+                                                        self._count, self.groups, thresholds, above_arr))
+        else:
+            self._shape = tuple(source.shape())
+            capi.check(lib.gs_time_stats_create(context.handle, ctypes.byref(self._h), self._shape[0], self._shape[1], 2,
+                                                self.groups, thresholds, above_arr))
+
+    @property
+    def handle(self):
+        if not self._h or not self._ctx._h:    # (the context owns the memory: closing it frees what is left)
+            raise GsError(capi.GS_ERR_INVALID, "time statistics already closed, or their context is")
+        return self._h
+
+    def accumulate(self, stamp: int) -> None:
+        """One sample of the source's current state, stamped ``stamp`` (the step count, say; any u32 but 0xffffffff).
+        Waits for the steps enqueued, enqueues one launch per slab and returns."""
+        lib, ctx = self._ctx._lib, self._ctx
+        if self._ensemble:
+            capi.check(lib.gs_members_time_stats_accumulate(ctx.handle, self.handle, self._source.handle, int(stamp)))
+        else:
+            in_u, in_v, _, _ = self._source.in_out()
+            capi.check(lib.gs_time_stats_accumulate(ctx.handle, self.handle, _handle_array([in_u, in_v]), 2, int(stamp)))
+
+    @property
+    def samples(self) -> int:
+        n = ctypes.c_uint64()
+        capi.check(self._ctx._lib.gs_time_stats_samples(self.handle, ctypes.byref(n)))
+        return int(n.value)
+
+    def reset(self) -> None:
+        """Back to a fresh object: every accumulator at its reset value, no samples."""
+        capi.check(self._ctx._lib.gs_time_stats_reset(self._ctx.handle, self.handle))
+
+    @staticmethod
+    def _plane(species: str) -> int:
+        if species not in ("u", "v"):
+            raise ValueError(f"species {species!r}: 'u' or 'v'")
+        return 0 if species == "u" else 1
+
+    def _result(self, species: str, which: int):
+        plane, ctx = self._plane(species), self._ctx
+        if self._ensemble:
+            out = np.empty((self._count,) + tuple(self._shape), np.float32)
+            capi.check(ctx._lib.gs_members_time_stats_result(ctx.handle, self.handle, plane, which,
+                                                             out.ctypes.data_as(ctypes.c_void_p)))
+            return out
+        out = HipConcentration(ctx, self._shape)
+        try:
+            capi.check(ctx._lib.gs_time_stats_result(ctx.handle, self.handle, plane, which, out.handle))
+        except GsError:
+            out.destroy()
+            raise
+        return out
+
+    def mean(self, species: str = "v"):
+        """sum / n, rounded once in f64, as f32."""
+        return self._result(species, capi.GS_TSTAT_MEAN)
+
+    def variance(self, species: str = "v"):
+        """max(squares / n - (sum / n)^2, 0) in f64, as f32 (a NaN stays NaN)."""
+        return self._result(species, capi.GS_TSTAT_VARIANCE)
+
+    def min(self, species: str = "v"):
+        return self._result(species, capi.GS_TSTAT_MIN)
+
+    def max(self, species: str = "v"):
+        """The largest sample of every cell: the trail of a moving spot."""
+        return self._result(species, capi.GS_TSTAT_MAX)
+
+    def occupancy(self, species: str = "v"):
+        """The share of the samples in which the cell was set (beyond its species' threshold)."""
+        return self._result(species, capi.GS_TSTAT_OCCUPANCY)
+
+    def arrival(self, species: str = "v"):
+        """The stamp of the first sample in which the cell was set, as f32; -1 where it never was."""
+        return self._result(species, capi.GS_TSTAT_ARRIVAL)
+
+    def raw(self, name: str, species: str = "v") -> np.ndarray:
+        """A raw accumulator -- ``sum``, ``squares`` (f64), ``min``, ``max`` (f32), ``set_count``, ``first_stamp`` (u32) -- of
+        this process's rows as a dense array: ``[rows, cols]``, or ``[count, rows, cols]`` for an ensemble."""
+        if name not in self.RAW:
+            raise ValueError(f"unknown accumulator {name!r}: one of {sorted(self.RAW)}")
+        raw, dtype = self.RAW[name]
+        if self._ensemble:
+            shape = (self._count,) + tuple(self._shape)
+        else:
+            r0, r1 = self._source.in_out()[0].local_rows()
+            shape = (r1 - r0, self._shape[1])
+        out = np.empty(shape, dtype)
+        capi.check(self._ctx._lib.gs_time_stats_download(self._ctx.handle, self.handle, self._plane(species), raw,
+                                                         out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def close(self) -> None:
+        if self._h and self._ctx._h:
+            self._ctx._lib.gs_time_stats_destroy(self._ctx._h, self._h)
+        self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class Species:
     """``Species<HipConcentration>``; ``Species.new`` = ``Species::new`` (mod.rs:36-59)."""
 
@@ -1499,6 +1650,13 @@ class Species:
         the next ``perform_steps`` continues from the snapshot's bits."""
         in_u, in_v, _, _ = self.in_out()
         copy_fields(self._context, [in_u, in_v], [snapshot.u, snapshot.v])
+
+    def time_stats(self, groups=("sum", "squares"), v_threshold=None, u_threshold=None, above=True) -> TimeStats:
+        """Per-cell statistics over the samples of this species' run, kept on the device (``gs_time_stats``): call
+        ``.accumulate(stamp)`` between ``perform_steps`` calls, read ``.mean("v")``, ``.variance("v")``, ``.max()``, ...
+        ``groups``: names out of sum, squares, extremes, crossings; crossings need ``v_threshold`` or ``u_threshold``
+        (``above``: set above the threshold, one sense or a (U, V) pair).  Works in every context, collective nowhere."""
+        return TimeStats(self._context, self, groups, u_threshold=u_threshold, v_threshold=v_threshold, above=above)
 
     def access_result(self, f: Callable):
         return f(self.v._pair[0], self._context)
@@ -1697,6 +1855,15 @@ class Ensemble:
         capi.check(self._ctx._lib.gs_members_compare(self._ctx.handle, self.handle, ref.handle, first, count,
                                                      out.ctypes.data_as(ctypes.POINTER(capi.GsChange))))
         return out
+
+    def time_stats(self, groups=("sum", "squares"), v_threshold=None, u_threshold=None, above=True, first: int = 0,
+                   count: Optional[int] = None) -> TimeStats:
+        """Per-cell statistics over the samples of members ``[first, first + count)``, kept on the device
+        (``gs_members_time_stats_create``; ``Species.time_stats`` for the arguments).  Members are sampled whether active
+        or retired -- a retired member repeats its state --, and every member's planes are bit for bit those of a lone
+        Species sampled in the same states.  The result methods return ``[count, rows, cols]`` numpy arrays."""
+        return TimeStats(self._ctx, self, groups, u_threshold=u_threshold, v_threshold=v_threshold, above=above, first=first,
+                         count=count)
 
     def set_active(self, mask, first: int = 0) -> None:
         """Active flags of members ``[first, first + len(mask))`` from a bool or uint8 array (``gs_members_set_active``;

@@ -94,6 +94,14 @@ keeps its meaning.  The JSON sidecar then carries ``steps_taken`` per member and
 ``<stem>.steady.npz`` gains ``steps_taken[members]``; the HDF5 file holds each member's V after its own ``steps_taken``
 steps -- bit for bit what that member is after as many steps in a run without the flag.  Without the flag every output file is
 what it was.
+
+``--time-stats-every N`` keeps per-cell statistics over time on the device (``Ensemble.time_stats``): U and V of every member
+are sampled every N steps -- from step S on with ``--time-stats-from S`` (default N), at steps S, S + N, ... -- into
+accumulators that never leave the device, and ``<output stem>.timestats.npz`` receives ``samples``, ``steps`` and, per member,
+the scalars ``var_v_mean``, ``var_v_max`` (0 for a member that stands still, not for one that pulsates or wanders) and
+``mean_v_mean``; unless ``--no-fields`` is given also the planes ``mean_v``, ``var_v``, ``min_v``, ``max_v`` (and ``_u``), each
+``[members, rows, cols]`` f32, and with ``--time-stats-threshold-v T`` ``occupancy_v`` and ``arrival_v``.  Retired members are
+sampled like the others: they repeat their state.
 """
 from __future__ import annotations
 
@@ -107,7 +115,8 @@ from typing import List, Tuple
 import numpy as np
 
 from . import hdf5_min
-from .simulate import add_backend_args, backend_args
+from .simulate import (add_backend_args, add_time_stats_args, backend_args, check_time_stats_args, time_stats_groups,
+                       time_stats_planes, time_stats_steps)
 from .simulation import COMPONENT_OVERLAP_DTYPE, COMPONENT_RECORD_DTYPE, Parameters, Simulation, pairs_total, quad_measures
 
 
@@ -210,8 +219,10 @@ def parse(argv=None):
     ap.add_argument("--steady-stop", action="store_true", help="end the run once every member is settled")
     ap.add_argument("--steady-retire", action="store_true",
                     help="retire every member at the check that finds it settled: it keeps its state and stops advancing")
+    add_time_stats_args(ap, "--time-stats")
     add_backend_args(ap)
     args = ap.parse_args(argv)
+    check_time_stats_args(ap, args, "time_stats", "--time-stats")
     if args.steady_every < 0:
         ap.error("--steady-every must be at least 1 (0 = off)")
     if not args.steady_tol >= 0.0:
@@ -296,6 +307,25 @@ def correlation_path(output: str) -> str:
 
 def steady_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".steady.npz"
+
+
+def time_stats_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".timestats.npz"
+
+
+def write_time_stats(path: str, samples: int, steps: List[int], planes: dict, with_planes: bool) -> None:
+    """``planes``: {"mean_v": [members, rows, cols], ...}.  Per member the scalars ``var_v_mean`` and ``var_v_max`` (a member
+    whose V stands still has both 0, one that pulsates or wanders does not) and ``mean_v_mean``, in float64; with
+    ``with_planes`` the planes themselves too."""
+    out = {"samples": np.int64(samples), "steps": np.asarray(steps, np.int64)}
+    if samples:
+        out["var_v_mean"] = planes["var_v"].mean(axis=(1, 2), dtype=np.float64)
+        out["var_v_max"] = planes["var_v"].max(axis=(1, 2)).astype(np.float64)
+        out["mean_v_mean"] = planes["mean_v"].mean(axis=(1, 2), dtype=np.float64)
+        if with_planes:
+            out.update(planes)
+    with open(path, "wb") as f:
+        np.savez(f, **out)
 
 
 def sample_steps(steps: int, every: int) -> List[int]:
@@ -422,15 +452,24 @@ def run(args) -> dict:
     comp_at = sample_steps(args.steps, args.components_every) if args.components_every else []
     spots_at = sample_steps(args.steps, args.spots_every) if args.spots_every else []
     track_at = sample_steps(args.steps, args.track_every) if args.track_every else []
+    tstat_at = time_stats_steps(args.steps, args.time_stats_every, args.time_stats_from)
+    stats = ens.time_stats(time_stats_groups(args.time_stats_threshold_v), v_threshold=args.time_stats_threshold_v) if tstat_at else None
+    tstat_taken = []
+    if tstat_at and tstat_at[0] == 0:
+        stats.accumulate(0)
+        tstat_taken.append(0)
     done, settled, taken = 0, None, None
-    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at or spots_at or track_at:
+    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at or spots_at or track_at or tstat_at:
         summaries, hists, changes, morphs, corrs, comps, spots, tracks = [], [], [], [], [], [], [], []
         snap = ens.snapshot() if steady_at else None
         last = ens.snapshot() if track_at else None  # (of its own: the steady checks move theirs at other steps)
         for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at) | set(comp_at)
-                         | set(spots_at) | set(track_at)):
+                         | set(spots_at) | set(track_at) | set(tstat_at) | ({args.steps} if tstat_at else set())):
             ens.prepare_steps(at - done)
             done = at
+            if at in tstat_at and at not in tstat_taken:
+                stats.accumulate(at)  # (waits for the steps; the accumulators stay on the device)
+                tstat_taken.append(at)
             if at in summary_at:
                 summaries.append(ens.summaries())  # (waits for the steps)
             if at in hist_at:
@@ -482,6 +521,10 @@ def run(args) -> dict:
         if corr_at:
             write_correlations(correlation_path(args.output), corr_at[:len(corrs)], corrs, args.corr_threshold_u,
                                args.corr_threshold_v, args.corr_lags, shape)
+        if tstat_at:
+            planes = time_stats_planes(stats, args.time_stats_threshold_v, lambda a: a) if stats.samples else {}
+            write_time_stats(time_stats_path(args.output), stats.samples, tstat_taken, planes, not args.no_fields)
+            stats.close()
         if steady_at:
             if args.steady_retire:
                 sim.context.sync()

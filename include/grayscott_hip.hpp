@@ -812,6 +812,7 @@ class Ensemble {
     std::size_t members() const { return members_; }
     Shape shape() const { return shape_; }
     gs_ensemble *raw() const { return e_; }
+    const Context &context() const { return ctx_; }
     void set_params(const std::vector<Parameters> &params)
     {
         std::vector<gs_params> c;
@@ -997,6 +998,108 @@ class Ensemble {
     gs_ensemble *e_ = nullptr;
     std::size_t members_;
     Shape shape_;
+};
+
+// Time statistics (gs_time_stats_*): per-cell accumulators over the samples of a run, kept on the device.  `groups` is a sum
+// of GS_TSTAT_SUM, _SQUARES, _EXTREMES, _CROSSINGS; crossings need a threshold per species (thresholds = {U's, V's}; above[i]:
+// set above it).  accumulate(stamp) between perform_steps calls; for a Species the result planes are HipConcentrations (every
+// observable, reduced download and colour map applies), for an Ensemble dense [count, rows, cols] host arrays.  No standard
+// deviation is formed on the device: take the square root of the variance read.
+class TimeStats {
+  public:
+    TimeStats(Species &species, uint32_t groups, const std::vector<float> &thresholds = {}, const std::vector<int32_t> &above = {})
+        : ctx_(species.context()), species_(&species), shape_(species.shape())
+    {
+        check_rule(groups, thresholds, above);
+        check(gs_time_stats_create(ctx_->get(), &ts_, shape_[0], shape_[1], 2, groups, thresholds.empty() ? nullptr : thresholds.data(),
+                                   above.empty() ? nullptr : above.data()));
+    }
+    TimeStats(Ensemble &ensemble, uint32_t groups, const std::vector<float> &thresholds = {}, const std::vector<int32_t> &above = {},
+              std::size_t first = 0, std::size_t count = (std::size_t)-1)
+        : ctx_(ensemble.context()), ensemble_(&ensemble), shape_(ensemble.shape()),
+          count_(count == (std::size_t)-1 ? ensemble.members() - first : count)
+    {
+        check_rule(groups, thresholds, above);
+        check(gs_members_time_stats_create(ctx_->get(), &ts_, ensemble.raw(), first, count_, groups,
+                                           thresholds.empty() ? nullptr : thresholds.data(), above.empty() ? nullptr : above.data()));
+    }
+    ~TimeStats()
+    {
+        if (ts_) gs_time_stats_destroy(ctx_->get(), ts_);
+    }
+    TimeStats(const TimeStats &) = delete;
+    TimeStats &operator=(const TimeStats &) = delete;
+    TimeStats(TimeStats &&o) noexcept
+        : ctx_(std::move(o.ctx_)), ts_(o.ts_), species_(o.species_), ensemble_(o.ensemble_), shape_(o.shape_), count_(o.count_)
+    {
+        o.ts_ = nullptr;
+    }
+    // one sample of the source's current state (waits for the steps enqueued, enqueues one launch per slab, returns)
+    void accumulate(uint32_t stamp)
+    {
+        if (ensemble_) {
+            check(gs_members_time_stats_accumulate(ctx_->get(), ts_, ensemble_->raw(), stamp));
+        } else {
+            gs_field *planes[2] = {species_->u().in().raw(), species_->v().in().raw()};
+            check(gs_time_stats_accumulate(ctx_->get(), ts_, planes, 2, stamp));
+        }
+    }
+    uint64_t samples() const
+    {
+        uint64_t n = 0;
+        check(gs_time_stats_samples(ts_, &n));
+        return n;
+    }
+    void reset() { check(gs_time_stats_reset(ctx_->get(), ts_)); }
+    // result plane `which` (GS_TSTAT_MEAN .. GS_TSTAT_ARRIVAL) of species 0 = U, 1 = V of a Species' statistics
+    HipConcentration result(int32_t species, int32_t which)
+    {
+        HipConcentration out = HipConcentration::default_(ctx_, shape_);
+        check(gs_time_stats_result(ctx_->get(), ts_, species, which, out.raw()));
+        return out;
+    }
+    HipConcentration mean(int32_t species = 1) { return result(species, GS_TSTAT_MEAN); }
+    HipConcentration variance(int32_t species = 1) { return result(species, GS_TSTAT_VARIANCE); }
+    HipConcentration min(int32_t species = 1) { return result(species, GS_TSTAT_MIN); }
+    HipConcentration max(int32_t species = 1) { return result(species, GS_TSTAT_MAX); }
+    HipConcentration occupancy(int32_t species = 1) { return result(species, GS_TSTAT_OCCUPANCY); }
+    HipConcentration arrival(int32_t species = 1) { return result(species, GS_TSTAT_ARRIVAL); }
+    // ... of an Ensemble's: [count, rows, cols]
+    std::vector<float> members_result(int32_t species, int32_t which)
+    {
+        std::vector<float> out(count_ * shape_[0] * shape_[1]);
+        check(gs_members_time_stats_result(ctx_->get(), ts_, species, which, out.data()));
+        return out;
+    }
+    // a raw accumulator (GS_TSTAT_RAW_SUM ..: T = double, float or uint32_t to match) of this process's rows, dense
+    template <typename T>
+    std::vector<T> raw(int32_t species, int32_t raw_plane)
+    {
+        const bool wide = raw_plane == GS_TSTAT_RAW_SUM || raw_plane == GS_TSTAT_RAW_SQUARES;
+        if (sizeof(T) != (wide ? 8u : 4u)) throw std::logic_error("TimeStats::raw: element type does not match the accumulator");
+        std::size_t rows = count_ * shape_[0];
+        if (species_) {
+            uint64_t r0 = 0, r1 = 0;
+            check(gs_field_local_rows(species_->u().in().raw(), &r0, &r1));
+            rows = (std::size_t)(r1 - r0);
+        }
+        std::vector<T> out(rows * shape_[1]);
+        check(gs_time_stats_download(ctx_->get(), ts_, species, raw_plane, out.data()));
+        return out;
+    }
+
+  private:
+    static void check_rule(uint32_t groups, const std::vector<float> &thresholds, const std::vector<int32_t> &above)
+    {
+        if ((groups & GS_TSTAT_CROSSINGS) && (thresholds.size() != 2 || above.size() != 2))
+            throw std::logic_error("TimeStats: crossings need two thresholds and two senses (U's, V's)");
+    }
+    Context ctx_;
+    gs_time_stats *ts_ = nullptr;
+    Species *species_ = nullptr;
+    Ensemble *ensemble_ = nullptr;
+    Shape shape_{};
+    std::size_t count_ = 1;
 };
 
 class Simulation {

@@ -945,6 +945,82 @@ int32_t gs_members_compare(gs_ctx *ctx, gs_ensemble *e, gs_ensemble *ref, uint64
 int32_t gs_fields_copy(gs_ctx *ctx, gs_field *const *dst, gs_field *const *src, int32_t n);
 int32_t gs_members_copy(gs_ctx *ctx, gs_ensemble *dst, gs_ensemble *src, uint64_t first, uint64_t count);
 
+/* Time statistics formed on the device: per-cell accumulators over the SAMPLES of a run -- is a cell steady, pulsating or
+ * chaotic (variance), what does the time-averaged field look like (mean), where has a spot been (maximum), when did the front
+ * arrive (first crossing of a threshold), for what share of the time was a cell inside a spot (occupancy) -- without
+ * downloading a frame.  A gs_time_stats follows 1..4 planes of one shape; each selected GROUP keeps accumulator planes per
+ * plane, and one call adds one sample x of every cell, in this order:
+ *   GS_TSTAT_SUM        sum (f64, reset +0.0):        sum = sum + (double)x
+ *   GS_TSTAT_SQUARES    squares (f64, reset +0.0):    squares = squares + (double)x * (double)x   (the product is exact in f64)
+ *   GS_TSTAT_EXTREMES   min, max (f32, reset +inf, -inf):   min = x < min ? x : min;  max = x > max ? x : max
+ *   GS_TSTAT_CROSSINGS  set_count (u32, reset 0), first_stamp (u32, reset 0xffffffff): if x is SET by morphology's rule against
+ *                       the plane's one threshold and sense (x > t, or x < t; one f32 comparison): set_count += 1, and
+ *                       first_stamp = stamp where it still holds 0xffffffff
+ * What follows: a NaN sample never replaces an extreme and is never set, but NaN and +-inf propagate into sum and squares --
+ * the visible sign of a blow-up; a zero never replaces an extreme zero of the other sign (the comparisons are strict); a
+ * sub-normal sample counts as the value it is; both sums are plain sequential f64 additions per cell, so any host restates
+ * them bit for bit (the sign and payload of a NaN are not specified).  Every cell is independent: the accumulators are the
+ * same bits for any slab count, process count, boundary rule or launch shape, and a member's are those of a lone Species
+ * sampled in the same states.
+ * Result planes (`which`), computed in f64 with every operation rounded once and converted to f32 at the end; n = samples:
+ *   GS_TSTAT_MEAN       (float)(sum / n)
+ *   GS_TSTAT_VARIANCE   d = squares / n - (sum / n) * (sum / n);  (float)(d > 0 ? d : 0), a NaN d stays NaN
+ *   GS_TSTAT_MIN, _MAX  the accumulator
+ *   GS_TSTAT_OCCUPANCY  (float)((double)set_count / n)
+ *   GS_TSTAT_ARRIVAL    (float)first_stamp, -1.0f where the cell was never set
+ * (no standard deviation is formed on the device: the hosts take the square root of what they read).
+ *   gs_time_stats_create      accumulators for n planes of rows x cols cells (the GLOBAL shape of the fields it will follow),
+ *                             one set per slab on that slab's device, rows of the fields' pitch, at their reset values.
+ *                             thresholds[n] and above[n] (above[i] != 0: set above the threshold) are needed with
+ *                             GS_TSTAT_CROSSINGS and ignored without.  No rank ever exchanges anything: the object works in
+ *                             every context that has fields, with a parameter map or a domain mask attached too.
+ *   gs_time_stats_accumulate  one sample of fields[0 .. n) (this context's, of the object's shape), stamped `stamp` (any u32
+ *                             but 0xffffffff; the hosts pass the step count): waits for enqueued work as the other
+ *                             observables do (a persistent window launch that gave up is run again first), enqueues one launch
+ *                             per slab on its compute stream and returns.  The fields, their ghost rows, the tuner, the graphs
+ *                             and gs_stats are left as they are.
+ *   gs_time_stats_samples     *n = samples since creation or the last reset.
+ *   gs_time_stats_result      result plane `which` of plane `plane` into `out` (this context's, of the object's shape), whose
+ *                             ghost rows go stale as after gs_fields_copy: an ordinary field for every observable, reduced
+ *                             download and colour map.
+ *   gs_time_stats_download    raw accumulator `raw` of plane `plane` as dense [rows, cols] of its own type (f64, f32 or u32)
+ *                             with the row coverage of gs_field_download: this process's rows.
+ *   gs_time_stats_reset       back to the reset values, samples = 0.
+ * result, download, reset and destroy wait for the enqueued samples before they act.  The object's memory is owned by its
+ * context: gs_time_stats_destroy frees it early, gs_ctx_destroy frees whatever is left, and a handle is dead once its context is.
+ * Ensembles: planes 0 / 1 = U / V of members [first, first + count) of an ensemble shaped like `like`, sampled from the newest
+ * slot whether active or retired (a retired member repeats its state).
+ *   gs_members_time_stats_create      thresholds[2] / above[2]: U's, V's.
+ *   gs_members_time_stats_accumulate  one sample of the object's members of `e` (this context's, shaped like `like`).
+ *   gs_members_time_stats_result      host[i * rows * cols ...] = result plane `which` of species `species` of member first + i.
+ * samples, download (dense [count * rows, cols]), reset and destroy are the calls above.
+ * GS_ERR_INVALID, decided before anything is allocated or launched: a null argument; groups 0 or with unknown bits;
+ * GS_TSTAT_CROSSINGS without thresholds, or a NaN threshold; n outside 1..4; fields of another context or shape, or another
+ * count than the object's; stamp == 0xffffffff; a `which` or `raw` whose group is not selected, or a plane outside the
+ * object's; a result before the first sample; members outside the ensemble; an object of the other form.  An ensemble on a
+ * context that refuses ensembles: that context's own error (GS_ERR_UNSUPPORTED).  An allocation failure: GS_ERR_NOMEM (or
+ * GS_ERR_HIP), and nothing is left behind. */
+#define GS_TSTAT_SUM 1u
+#define GS_TSTAT_SQUARES 2u
+#define GS_TSTAT_EXTREMES 4u
+#define GS_TSTAT_CROSSINGS 8u
+enum { GS_TSTAT_MEAN = 0, GS_TSTAT_VARIANCE = 1, GS_TSTAT_MIN = 2, GS_TSTAT_MAX = 3, GS_TSTAT_OCCUPANCY = 4, GS_TSTAT_ARRIVAL = 5 };
+enum { GS_TSTAT_RAW_SUM = 0, GS_TSTAT_RAW_SQUARES = 1, GS_TSTAT_RAW_MIN = 2, GS_TSTAT_RAW_MAX = 3, GS_TSTAT_RAW_SET_COUNT = 4,
+       GS_TSTAT_RAW_FIRST_STAMP = 5 };
+typedef struct gs_time_stats gs_time_stats; /* device memory owned by the context */
+int32_t gs_time_stats_create(gs_ctx *ctx, gs_time_stats **out, uint64_t rows, uint64_t cols, int32_t n, uint32_t groups,
+                             const float *thresholds, const int32_t *above);
+int32_t gs_time_stats_destroy(gs_ctx *ctx, gs_time_stats *ts);
+int32_t gs_time_stats_reset(gs_ctx *ctx, gs_time_stats *ts);
+int32_t gs_time_stats_accumulate(gs_ctx *ctx, gs_time_stats *ts, gs_field *const *fields, int32_t n, uint32_t stamp);
+int32_t gs_time_stats_samples(const gs_time_stats *ts, uint64_t *n);
+int32_t gs_time_stats_result(gs_ctx *ctx, gs_time_stats *ts, int32_t plane, int32_t which, gs_field *out);
+int32_t gs_time_stats_download(gs_ctx *ctx, gs_time_stats *ts, int32_t plane, int32_t raw, void *host);
+int32_t gs_members_time_stats_create(gs_ctx *ctx, gs_time_stats **out, gs_ensemble *like, uint64_t first, uint64_t count,
+                                     uint32_t groups, const float thresholds[2], const int32_t above[2]);
+int32_t gs_members_time_stats_accumulate(gs_ctx *ctx, gs_time_stats *ts, gs_ensemble *e, uint32_t stamp);
+int32_t gs_members_time_stats_result(gs_ctx *ctx, gs_time_stats *ts, int32_t species, int32_t which, float *host);
+
 /* Measurement hook, not for bindings (tools/rccl_under_load.py): the ghost-row exchange's transport on ONE GPU while the
  * caller keeps the chip busy or idle.  mode 0: a one-rank RCCL communicator, `messages` ncclSend / ncclRecv pairs of
  * `floats` f32 to itself in one group; mode 1: the same bytes as device-to-device copies (the in-process chain's route);

@@ -61,6 +61,31 @@ pub struct gs_component_match {
     _private: [u8; 0],
 }
 
+/// Time statistics (include/gs_hip.h): per-cell accumulators over the samples of a run; device memory.
+#[repr(C)]
+pub struct gs_time_stats {
+    _private: [u8; 0],
+}
+/// The groups of accumulators a `gs_time_stats` keeps (a sum of these) ...
+pub const GS_TSTAT_SUM: u32 = 1;
+pub const GS_TSTAT_SQUARES: u32 = 2;
+pub const GS_TSTAT_EXTREMES: u32 = 4;
+pub const GS_TSTAT_CROSSINGS: u32 = 8;
+/// ... its result planes (`which`) ...
+pub const GS_TSTAT_MEAN: i32 = 0;
+pub const GS_TSTAT_VARIANCE: i32 = 1;
+pub const GS_TSTAT_MIN: i32 = 2;
+pub const GS_TSTAT_MAX: i32 = 3;
+pub const GS_TSTAT_OCCUPANCY: i32 = 4;
+pub const GS_TSTAT_ARRIVAL: i32 = 5;
+/// ... and its raw accumulators (`raw`): f64, f64, f32, f32, u32, u32.
+pub const GS_TSTAT_RAW_SUM: i32 = 0;
+pub const GS_TSTAT_RAW_SQUARES: i32 = 1;
+pub const GS_TSTAT_RAW_MIN: i32 = 2;
+pub const GS_TSTAT_RAW_MAX: i32 = 3;
+pub const GS_TSTAT_RAW_SET_COUNT: i32 = 4;
+pub const GS_TSTAT_RAW_FIRST_STAMP: i32 = 5;
+
 /// A before-record and an after-record of a match that share `cells` grid cells (16 bytes).
 #[repr(C)]
 #[derive(Copy, Clone, Debug, Default, PartialEq, Eq)]
@@ -299,4 +324,39 @@ extern "C" {
     ) -> i32;
     /// Null: `GS_OK`.
     pub fn gs_component_match_destroy(m: *mut gs_component_match) -> i32;
+    /// Accumulators for `n` (1..4) planes of `rows` x `cols` cells; `thresholds[n]` / `above[n]` with `GS_TSTAT_CROSSINGS`.
+    pub fn gs_time_stats_create(
+        ctx: *mut gs_ctx,
+        out: *mut *mut gs_time_stats,
+        rows: u64,
+        cols: u64,
+        n: i32,
+        groups: u32,
+        thresholds: *const f32,
+        above: *const i32,
+    ) -> i32;
+    /// Null: `GS_OK`.
+    pub fn gs_time_stats_destroy(ctx: *mut gs_ctx, ts: *mut gs_time_stats) -> i32;
+    pub fn gs_time_stats_reset(ctx: *mut gs_ctx, ts: *mut gs_time_stats) -> i32;
+    /// One sample of `fields[0 .. n)`, stamped `stamp` (any u32 but 0xffffffff): enqueued, not waited for.
+    pub fn gs_time_stats_accumulate(ctx: *mut gs_ctx, ts: *mut gs_time_stats, fields: *const *mut gs_field, n: i32, stamp: u32) -> i32;
+    pub fn gs_time_stats_samples(ts: *const gs_time_stats, n: *mut u64) -> i32;
+    /// Result plane `which` of plane `plane` into `out`, a field of the same shape.
+    pub fn gs_time_stats_result(ctx: *mut gs_ctx, ts: *mut gs_time_stats, plane: i32, which: i32, out: *mut gs_field) -> i32;
+    /// Raw accumulator `raw` of plane `plane`: dense rows of this process, of the accumulator's own type.
+    pub fn gs_time_stats_download(ctx: *mut gs_ctx, ts: *mut gs_time_stats, plane: i32, raw: i32, host: *mut c_void) -> i32;
+    /// Planes 0 / 1 = U / V of members `[first, first + count)` of an ensemble shaped like `like`.
+    pub fn gs_members_time_stats_create(
+        ctx: *mut gs_ctx,
+        out: *mut *mut gs_time_stats,
+        like: *mut gs_ensemble,
+        first: u64,
+        count: u64,
+        groups: u32,
+        thresholds: *const f32,
+        above: *const i32,
+    ) -> i32;
+    pub fn gs_members_time_stats_accumulate(ctx: *mut gs_ctx, ts: *mut gs_time_stats, e: *mut gs_ensemble, stamp: u32) -> i32;
+    /// `host[count, rows, cols]`: result plane `which` of species `species` of every member.
+    pub fn gs_members_time_stats_result(ctx: *mut gs_ctx, ts: *mut gs_time_stats, species: i32, which: i32, host: *mut f32) -> i32;
 }
