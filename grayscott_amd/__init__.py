@@ -21,6 +21,7 @@ from .simulation import (  # noqa: F401
     Components,
     Morphology,
     Parameters,
+    RegionCorrelation,
     RegionMorphology,
     RegionSummaries,
     Simulation,
@@ -33,4 +34,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionCorrelation", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]

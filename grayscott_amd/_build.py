@@ -59,6 +59,8 @@ UNITS = [
     # two-point pair counts of thresholded planes (lags 0..64 along four directions, one pass for up to four thresholds):
     # the same float mode
     ("gs_correlation.hip", "gs_correlation_k.o", []),
+    # regional two-point pair counts (a region's border is a wall for pairs): the same float mode
+    ("gs_region_pairs.hip", "gs_region_pairs_k.o", []),
     # connected components of thresholded planes (union-find over a u32 parent per cell; tile, border, flatten and tally
     # launches): the same float mode
     ("gs_components.hip", "gs_components_k.o", []),

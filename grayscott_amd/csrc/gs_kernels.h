@@ -316,6 +316,14 @@ hipError_t gs_launch_pairs(const float *const *planes, const float *const *above
                            const int32_t *sense, int32_t nt, int32_t max_lag, int64_t max_groups, unsigned long long *out,
                            hipStream_t s);
 
+// Regional two-point pair counts (gs_region_pairs.hip; include/gs_hip.h: gs_fields_region_correlation).  Planes and regions
+// as for gs_launch_region_quads (no alignment is assumed), thresholds, senses and max_lag as for gs_launch_pairs.  The launch
+// adds the pairs of set cells that lie in ONE region -- nothing is above a region's first row or beside its columns -- to
+// out[((((p * rr + i) * rc + j) * nt + t) * 4 + k) * (max_lag + 1) + d], which must hold zeros.
+hipError_t gs_launch_region_pairs(const float *const *planes, int np, int64_t pitch, int64_t rows, int32_t cols, int32_t rh,
+                                  int32_t rw, const float *thresholds, const int32_t *sense, int32_t nt, int32_t max_lag,
+                                  int64_t max_groups, unsigned long long *out, hipStream_t s);
+
 // Connected components (gs_components.hip; include/gs_hip.h: gs_fields_components).  `planes` planes of rows x cols cells,
 // `stride` floats apart, rows `pitch` floats apart, thresholded at `threshold` with `sense` as for gs_launch_quads and
 // labelled under `connectivity` (4 or 8); a component never leaves its plane.  parent and size hold one u32 per cell of all

@@ -33,7 +33,8 @@
 //   regional observables  summaries and bit-quad counts of every region of rh x rw cells of a plane (gs_fields_region_summaries,
 //               gs_fields_region_morphology; gs_regions.hip): one launch per slab leaves a record or a set of counters per
 //               (plane, region) -- a region lies inside one slab, so nothing is staged and nothing is folded on the host --
-//               and the slabs' and ranks' region rows meet in the global [plane][region] layout (region_results).
+//               and the slabs' and ranks' region rows meet in the global [plane][region] layout (region_results).  The regions'
+//               two-point pair counts (gs_fields_region_correlation; gs_region_pairs.hip) travel the same way.
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
@@ -1595,6 +1596,32 @@ int32_t gs_fields_region_morphology(gs_ctx *ctx, gs_field *const *fields, int32_
                 }
             }
     return GS_OK;
+}
+
+int32_t gs_fields_region_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, const float *thresholds,
+                                     const int32_t *above, int32_t nt, int32_t max_lag, uint64_t *out)
+{
+    if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    uint64_t RR, RC;
+    GS_TRY(region_grid(0, 0, rh, rw, &RR, &RC)); // the region shape alone; no handle is looked at down to check_planes
+    GS_TRY(check_thresholds(thresholds, n, nt));
+    GS_TRY(check_max_lag(max_lag));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    GS_TRY(region_grid(f0->rows, f0->cols, rh, rw, &RR, &RC));
+    if (RR * RC == 0) return GS_OK; // an empty plane has no regions; the same shape on every rank: nobody exchanges anything
+    const uint64_t per_region = (uint64_t)nt * 4 * (uint64_t)(max_lag + 1); // (at most 1040: no product here can wrap)
+    if (RR * RC * per_region > (uint64_t)GS_REGION_PAIRS_MAX)
+        return fail(GS_ERR_INVALID, "%llu x %llu regions of %llu counters each (at most %u counters per field)",
+                    (unsigned long long)RR, (unsigned long long)RC, (unsigned long long)per_region, (unsigned)GS_REGION_PAIRS_MAX);
+    // the counters land in `out` as they are, as the bit quads' do
+    return region_results(ctx, f0, n, rh, RR, RC, (size_t)per_region * sizeof(uint64_t), true, "region correlation",
+                          reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
+        return gs_launch_region_pairs(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, thresholds, above,
+                                      nt, max_lag, max_groups(ctx), reinterpret_cast<unsigned long long *>(dev), s);
+    });
 }
 
 } // extern "C"

@@ -38,6 +38,9 @@ parameter map the file also holds ``feed`` and ``kill``, the regions' means of t
 phase diagram.  In a multi-process run rank 0 writes.  The two calls block: an observed image is waited for before the next
 steps are enqueued, so with ``--hip-regions-every 1`` no download overlaps the steps of the next image any more (the pipeline of
 two images in flight runs dry at every observed image); the default, the last image alone, costs nothing before the end.
+``--hip-region-corr-lags L`` (1..64; needs ``--hip-regions``) adds the regions' two-point pair counts
+(``gs_fields_region_correlation``, a region's border being a wall for pairs) at the same thresholds: ``pairs_v`` (and ``pairs_u``)
+as [samples, nt, RR, RC, 4, L + 1] and ``corr_lags`` = L -- the wavelength axis of the phase diagram.
 
 Time statistics (``gs_time_stats``): ``--hip-time-stats-every N`` samples U and V every N steps -- from step S on with
 ``--hip-time-stats-from S`` (default N; 0: the initial state too), at steps S, S + N, ..., each stamped with its step count -- into per-cell accumulators on
@@ -85,6 +88,8 @@ def parse(argv=None):
     tu, tv = args.hip_region_threshold_u, args.hip_region_threshold_v or [0.25]
     if tu is not None and len(tu) != len(tv):
         ap.error(f"--hip-region-threshold-u wants as many thresholds as --hip-region-threshold-v ({len(tv)}), not {len(tu)}")
+    if args.hip_region_corr_lags is not None and args.hip_regions is None:
+        ap.error("--hip-region-corr-lags needs --hip-regions")
     return args
 
 
@@ -170,6 +175,16 @@ def _threshold_list(text: str):
     return values
 
 
+def _lag_count(text: str) -> int:
+    try:
+        value = int(text)
+    except ValueError:
+        value = 0
+    if not 1 <= value <= 64:
+        raise argparse.ArgumentTypeError(f"a largest lag of 1 to 64, not {text!r}")
+    return value
+
+
 def _positive(text: str) -> int:
     try:
         value = int(text)
@@ -191,6 +206,8 @@ def add_region_args(ap: argparse.ArgumentParser) -> None:
                     help="V is set above these thresholds (1..4; default 0.25)")
     rg.add_argument("--hip-region-threshold-u", type=_threshold_list, default=None, metavar="A[,B...]",
                     help="U is set below these thresholds (as many as V's; default: U's quads are not counted)")
+    rg.add_argument("--hip-region-corr-lags", type=_lag_count, default=None, metavar="L",
+                    help="also the regions' two-point pair counts at lags 0..L (1..64) at the region thresholds (needs --hip-regions)")
 
 
 def add_time_stats_args(ap: argparse.ArgumentParser, prefix: str = "--hip-time-stats") -> None:
@@ -284,8 +301,9 @@ class RegionLog:
 
     SUMMARY_KEYS = ("sum", "sum_sq", "min", "max", "nonfinite")
 
-    def __init__(self, region, thresholds_v, thresholds_u):
+    def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None):
         self.region = region
+        self.corr_lags = corr_lags
         self.thresholds_v = list(thresholds_v) if thresholds_v else [0.25]
         self.thresholds_u = list(thresholds_u) if thresholds_u else None
         if self.thresholds_u is not None and len(self.thresholds_u) != len(self.thresholds_v):
@@ -303,11 +321,18 @@ class RegionLog:
         self.rows.setdefault("quads_v", []).append(np.stack([m.quads for m in mv]))
         if mu:
             self.rows.setdefault("quads_u", []).append(np.stack([m.quads for m in mu]))
+        if self.corr_lags is not None:
+            cu, cv = species.region_correlation(self.region, self.thresholds_v, self.thresholds_u, self.corr_lags)
+            self.rows.setdefault("pairs_v", []).append(np.stack([c.pairs for c in cv]))
+            if cu:
+                self.rows.setdefault("pairs_u", []).append(np.stack([c.pairs for c in cu]))
 
     def save(self, path: str, shape, pmap=None) -> None:
         out = {"region": np.array(self.region, np.int64), "shape": np.array(shape, np.int64), "steps": np.array(self.steps, np.int64),
                "thresholds_v": np.array(self.thresholds_v, np.float32),
                "thresholds_u": np.array(self.thresholds_u or [], np.float32)}
+        if self.corr_lags is not None:
+            out["corr_lags"] = np.array(self.corr_lags, np.int64)
         for key, rows in self.rows.items():
             out[key] = rows[0] if key == "cells" else np.stack(rows)
         if pmap is not None:
@@ -434,7 +459,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     params = simulation_parameters(args)
     pmap = param_map(args, shape, params)
     region = getattr(args, "hip_regions", None)
-    regions = RegionLog(region, getattr(args, "hip_region_threshold_v", None), getattr(args, "hip_region_threshold_u", None)) if region else None
+    regions = RegionLog(region, getattr(args, "hip_region_threshold_v", None), getattr(args, "hip_region_threshold_u", None),
+                        getattr(args, "hip_region_corr_lags", None)) if region else None
     mask = domain_mask(args, shape)
     sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)

@@ -1026,6 +1026,97 @@ def correlation_fields(context: "HipContext", fields: Sequence["HipConcentration
     return [[Correlation.from_pairs(out[i, k], thr[i * nt + k], above[i], rows, cols) for k in range(nt)] for i in range(n)]
 
 
+@dataclass(frozen=True, eq=False)
+class RegionCorrelation:
+    """The two-point pair counts of every region of one thresholded plane, counted on the device
+    (``gs_fields_region_correlation``): ``pairs`` of shape ``(RR, RC, 4, L + 1)``, entry (i, j) being the ``Correlation.pairs``
+    of a plane that holds region (i, j)'s cells alone -- a pair across a region border is never formed.  ``cells`` is every
+    region's number of cells; the derived arrays are ``Correlation``'s, region by region."""
+
+    pairs: np.ndarray
+    threshold: float
+    above: bool
+    cells: np.ndarray
+    region: Tuple[int, int]
+    shape: Tuple[int, int]
+
+    @classmethod
+    def from_pairs(cls, pairs, threshold: float, above: bool, region, shape) -> "RegionCorrelation":
+        pairs = np.array(pairs, np.uint64)
+        region, shape = region_shape(region), (int(shape[0]), int(shape[1]))
+        return cls(pairs, float(threshold), bool(above), region_sizes(shape[0], shape[1], region, pairs.shape[:2]), region, shape)
+
+    @property
+    def max_lag(self) -> int:
+        return self.pairs.shape[3] - 1
+
+    def totals(self) -> np.ndarray:
+        """The pairs that exist inside every region's own h x w cells, N_k(d), as int64 ``(RR, RC, 4, L + 1)``."""
+        rr, rc = self.pairs.shape[:2]
+        h = np.minimum(self.region[0], self.shape[0] - self.region[0] * np.arange(rr, dtype=np.int64))[:, None, None]
+        w = np.minimum(self.region[1], self.shape[1] - self.region[1] * np.arange(rc, dtype=np.int64))[None, :, None]
+        d = np.arange(self.max_lag + 1, dtype=np.int64)[None, None, :]
+        return np.stack([np.maximum(h - d * dr, 0) * np.maximum(w - d * abs(dc), 0) for dr, dc in CORRELATION_STEPS], axis=2)
+
+    def s2(self, k: int) -> np.ndarray:
+        """Per region, ``Correlation.s2(k)``: f64 ``(RR, RC, L + 1)``, NaN where no pair exists."""
+        total = self.totals()[:, :, k].astype(np.float64)
+        out = np.full(total.shape, np.nan)
+        np.divide(self.pairs[:, :, k].astype(np.float64), total, out=out, where=total > 0)
+        return out
+
+    def autocovariance(self, k: int) -> np.ndarray:
+        """Per region, ``Correlation.autocovariance(k)``: ``s2(k)`` minus the square of the region's set fraction."""
+        cells = self.cells.astype(np.float64)
+        fraction = np.full(cells.shape, np.nan)
+        np.divide(self.pairs[:, :, 0, 0].astype(np.float64), cells, out=fraction, where=cells > 0)
+        return self.s2(k) - (fraction ** 2)[:, :, None]
+
+    def _per_region(self, name: str, k: int) -> np.ndarray:
+        out = np.full(self.pairs.shape[:2], -1, np.int64)
+        for i, j in np.ndindex(out.shape):
+            found = getattr(self.at(i, j), name)(k)
+            out[i, j] = -1 if found is None else found
+        return out
+
+    def first_minimum(self, k: int) -> np.ndarray:
+        """Per region, ``Correlation.first_minimum(k)`` -- half the wavelength along e_k -- as int64, -1 where there is none."""
+        return self._per_region("first_minimum", k)
+
+    def first_maximum_after_minimum(self, k: int) -> np.ndarray:
+        """Per region, ``Correlation.first_maximum_after_minimum(k)`` -- the wavelength along e_k --, -1 where there is none."""
+        return self._per_region("first_maximum_after_minimum", k)
+
+    def at(self, i: int, j: int) -> Correlation:
+        h = min(self.region[0], self.shape[0] - self.region[0] * i)
+        w = min(self.region[1], self.shape[1] - self.region[1] * j)
+        return Correlation.from_pairs(self.pairs[i, j], self.threshold, self.above, h, w)
+
+
+def region_correlation_fields(context: "HipContext", fields: Sequence["HipConcentration"], region,
+                              thresholds: Sequence[Sequence[float]], above: Sequence[bool],
+                              max_lag: int = 32) -> List[List[RegionCorrelation]]:
+    """``gs_fields_region_correlation``: the two-point pair counts of every region of 1..4 planes of one shape in one call
+    (blocking; collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, one pass) with
+    the sense ``above[i]``, lags 0 .. ``max_lag`` (1..64).  Returns one list of ``RegionCorrelation`` per plane, one entry
+    per threshold."""
+    n, nt, thr, sense = _field_thresholds(fields, thresholds, above)
+    rh, rw = region_shape(region)
+    shape = fields[0].shape() if fields else (0, 0)
+    lags = max_lag + 1 if 1 <= max_lag <= 64 else 1
+    try:
+        grid = region_grid(shape[0], shape[1], (rh, rw))
+        if grid[0] * grid[1] * max(nt, 1) * 4 * lags > capi.GS_REGION_PAIRS_MAX:
+            grid = (0, 0)
+    except capi.GsError:
+        grid = (0, 0)  # (the call below refuses it, in the header's order)
+    out = np.zeros((max(n, 1),) + grid + (max(nt, 1), 4, lags), np.uint64)
+    capi.check(context._lib.gs_fields_region_correlation(context.handle, _handle_array(fields), n, rh, rw, thr, sense, nt,
+                                                         max_lag, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    return [[RegionCorrelation.from_pairs(out[i, :, :, k], thr[i * nt + k], above[i], (rh, rw), shape) for k in range(nt)]
+            for i in range(n)]
+
+
 def pinned_empty(shape: Sequence[int]) -> np.ndarray:
     """float32 array in page-locked host memory (``gs_host_alloc``) for overlapped downloads.
     The allocation is released when the last view of it is garbage-collected."""
@@ -1271,6 +1362,13 @@ class HipConcentration:
         ``max_lag`` along four directions over the whole global grid, counted on the device (``gs_fields_correlation``;
         blocking, collective in a multi-process context)."""
         return correlation_fields(context, [self], [thresholds], [above], max_lag)[0]
+
+    def region_correlation(self, context: HipContext, region, thresholds, max_lag: int = 32,
+                           above: bool = True) -> List[RegionCorrelation]:
+        """The two-point pair counts of every region of ``region`` = (rh, rw) cells (an int: square) of this plane thresholded
+        at each of ``thresholds`` (1..4, one pass), lags 0 .. ``max_lag``, a region's border being a wall for pairs, counted
+        on the device (``gs_fields_region_correlation``; blocking, collective in a multi-process context)."""
+        return region_correlation_fields(context, [self], region, [thresholds], [above], max_lag)[0]
 
     def change_from(self, context: HipContext, other: "HipConcentration") -> Change:
         """How far this plane is from ``other`` (this minus other, cell by cell in f64) over the whole global grid,
@@ -1633,6 +1731,16 @@ class Species:
         ``max_lag`` (1..64).  ``above`` = (U's sense, V's sense): V carries the pattern where it is high and U where it is
         low; without ``u_thresholds`` only V is looked at and the U list is empty."""
         return self._v_or_both(correlation_fields, u_thresholds, v_thresholds, above, max_lag)
+
+    def region_correlation(self, region, v_thresholds=(0.25,), u_thresholds=None, max_lag: int = 32,
+                           above: Tuple[bool, bool] = (False, True)) -> Tuple[List[RegionCorrelation], List[RegionCorrelation]]:
+        """(U, V) two-point pair counts of every region of the current state in one call (``gs_fields_region_correlation``;
+        blocking, collective in a multi-process context): one ``RegionCorrelation`` per threshold, the region shape as for
+        ``region_morphology``, thresholds, lags and senses as for ``correlation``; without ``u_thresholds`` only V is looked
+        at and the U list is empty."""
+        def observe(context, fields, thresholds, senses):
+            return region_correlation_fields(context, fields, region, thresholds, senses, max_lag)
+        return self._v_or_both(observe, u_thresholds, v_thresholds, above)
 
     def snapshot(self) -> Snapshot:
         """The current state copied into planes of its own on the device (``gs_fields_copy``; blocking)."""

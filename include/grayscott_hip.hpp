@@ -273,6 +273,9 @@ struct Correlation {
     // the length of d e_k in cells
     double distance(std::size_t k, std::size_t d) const { return (double)d * (k < 2 ? 1.0 : std::sqrt(2.0)); }
 };
+// of one threshold (gs_fields_region_correlation): `at(i, j)` has region (i, j)'s own rows and cols, a pair across a region
+// border is never formed
+using RegionCorrelation = Regions<Correlation>;
 
 struct Parameters {
     std::array<std::array<Precision, 3>, 3> weights{{{0.25f, 0.5f, 0.25f}, {0.5f, 0.0f, 0.5f}, {0.25f, 0.5f, 0.25f}}};
@@ -734,6 +737,40 @@ class Species {
             uv.first.push_back(Correlation::from_c(out.data() + k * 4 * lags, max_lag, t[k], u_above, s[0], s[1]));
             uv.second.push_back(Correlation::from_c(out.data() + (nt + k) * 4 * lags, max_lag, t[nt + k], v_above, s[0], s[1]));
         }
+        return uv;
+    }
+    // (U, V) two-point pair counts of every region of rh x rw cells of the current state, in one call
+    // (gs_fields_region_correlation; blocking, collective in a multi-process context): one RegionCorrelation per threshold, a
+    // region's border being a wall for pairs; thresholds, lags and senses as for correlation()
+    std::pair<std::vector<RegionCorrelation>, std::vector<RegionCorrelation>> region_correlation(int32_t rh, int32_t rw,
+                                                                                                 const std::vector<float> &v_thresholds,
+                                                                                                 const std::vector<float> &u_thresholds,
+                                                                                                 int32_t max_lag = 32, bool v_above = true,
+                                                                                                 bool u_above = false)
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t nt = v_thresholds.size(), lags = max_lag >= 1 && max_lag <= 64 ? (std::size_t)max_lag + 1 : 1;
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
+        const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
+        const Shape s = shape();
+        uint64_t rr = 0, rc = 0;
+        check(gs_region_grid(s[0], s[1], rh, rw, &rr, &rc));
+        // (a result over the cap is refused by the call; nothing that large is allocated for it)
+        const std::size_t regions = rr * rc * nt * 4 * lags <= (uint64_t)GS_REGION_PAIRS_MAX ? (std::size_t)(rr * rc) : 0;
+        std::vector<uint64_t> out(2 * regions * nt * 4 * lags + 1);
+        check(gs_fields_region_correlation(context_->get(), planes, 2, rh, rw, t.data(), sense, (int32_t)nt, max_lag, out.data()));
+        std::pair<std::vector<RegionCorrelation>, std::vector<RegionCorrelation>> uv;
+        std::vector<RegionCorrelation> *both[2] = {&uv.first, &uv.second};
+        for (std::size_t p = 0; p < 2; ++p)
+            for (std::size_t k = 0; k < nt; ++k) {
+                RegionCorrelation c{rr, rc, rh, rw, {}};
+                for (std::size_t r = 0; r < regions; ++r) {
+                    const uint64_t h = detail::region_cells(s[0], 1, rh, 1, r / rc, 0), w = detail::region_cells(1, s[1], 1, rw, 0, r % rc);
+                    c.results.push_back(Correlation::from_c(out.data() + ((p * regions + r) * nt + k) * 4 * lags, max_lag, t[p * nt + k],
+                                                            p ? v_above : u_above, h, w));
+                }
+                both[p]->push_back(std::move(c));
+            }
         return uv;
     }
     // the current state copied into planes of its own on the device (gs_fields_copy; blocking)

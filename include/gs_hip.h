@@ -681,6 +681,31 @@ int32_t gs_fields_region_summaries(gs_ctx *ctx, gs_field *const *fields, int32_t
 int32_t gs_fields_region_morphology(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw,
                                     const float *thresholds, const int32_t *above, int32_t nt, gs_morphology *out);
 
+/* Regional two-point correlations: the pair counts of gs_fields_correlation (below) of every region of the same region grid
+ * -- how far apart the spots or stripes of each part of a parameter map's grid are; the whole-grid counts of such a grid
+ * are a blend that belongs to no region.
+ *   gs_fields_region_correlation  out[((((p * RR + i) * RC + j) * nt + t) * 4 + k) * (L + 1) + d] is, bit for bit, what
+ *                                 gs_fields_correlation returns for a field that holds region (i, j)'s cells alone, for
+ *                                 direction k, lag d, and fields[p] thresholded at thresholds[p * nt + t] with the sense
+ *                                 above[p], L = max_lag.
+ * The set rule and the four unit steps are the whole-grid correlation's.  A region's border is a wall: a pair whose two
+ * cells lie in different regions is never formed, under every boundary rule.  A lag that does not fit the region, a ragged
+ * one included, counts 0; d = 0 is the region's area for all four k.  The number of pairs that exist in a region of h x w
+ * cells, N_k(d) = max(h - d dr, 0) max(w - d |dc|, 0), is the hosts' to compute.  The regions do not partition the pairs of
+ * the global grid.  With a domain mask attached wall cells count.
+ * The call follows its two twins above: one wait for enqueued work, one launch per slab, blocking, no side effects (ghost
+ * rows, tuner, graphs and gs_stats are left as they are), collective in a multi-process context with every rank receiving
+ * every region; an empty plane: GS_OK, nothing is written.  GS_ERR_INVALID, decided in this order: a null argument; rh or
+ * rw refused by gs_region_grid; nt outside 1..4; a NaN threshold; max_lag outside 1..64 -- all before any handle is looked
+ * at --; a null or foreign handle, mixed shapes, n outside 1..4; RR RC > GS_REGIONS_MAX; RR RC nt 4 (L + 1) >
+ * GS_REGION_PAIRS_MAX counters per field (a cap on result memory: 256 MiB per field).  GS_ERR_UNSUPPORTED, on every rank
+ * alike: some slab begins at a row that is no multiple of rh, as above -- a region lies inside one slab, so nothing is staged
+ * and no ghost row is read.
+ * Not done: regions of ensemble members; pairs wrapped under the periodic rule; lags beyond 64; regions that straddle slabs. */
+#define GS_REGION_PAIRS_MAX (1u << 25)
+int32_t gs_fields_region_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw,
+                                     const float *thresholds, const int32_t *above, int32_t nt, int32_t max_lag, uint64_t *out);
+
 /* Two-point correlations computed on the device: the two-point probability function of one plane of the WHOLE global grid
  * after thresholding -- for a lag vector, the number of cell pairs that far apart which are both set; from it the pattern's
  * wavelength and the direction of its stripes follow ("how far apart are the spots?") -- without downloading the plane.  For

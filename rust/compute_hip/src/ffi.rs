@@ -247,6 +247,20 @@ extern "C" {
         nt: i32,
         out: *mut gs_morphology,
     ) -> i32;
+    /// `thresholds`: n x nt, `above`: n senses; `out`: n x rr x rc x nt x 4 x (max_lag + 1) pair counts, a region's border
+    /// being a wall for pairs.
+    pub fn gs_fields_region_correlation(
+        ctx: *mut gs_ctx,
+        fields: *const *mut gs_field,
+        n: i32,
+        rh: i32,
+        rw: i32,
+        thresholds: *const f32,
+        above: *const i32,
+        nt: i32,
+        max_lag: i32,
+        out: *mut u64,
+    ) -> i32;
     /// Pair i: `a[i]` against `b[i]`, n = 1..4 pairs of one shape; `out`: n records.
     pub fn gs_fields_compare(
         ctx: *mut gs_ctx,
