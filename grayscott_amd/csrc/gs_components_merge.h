@@ -18,6 +18,8 @@
 // gs_match_merge.h) the caller also learns what became of every record handed in: where[base(s) + k] is the index in the
 // result of slab s's record k -- base(s) the number of records of the slabs before s -- or kCompUnset if the merged record
 // fell below min_size.
+// The host steps in front of it are here too: records_to_global_rows for a slab's records, which count rows from the slab's
+// first, and batch_records_to_planes for a batch of an ensemble's members, planes stacked one after the other.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -115,6 +117,32 @@ struct ListSeamRows { // of one slab, `cols` entries each: the index of the cell
 inline bool comp_first_cell_before(const gs_component_record &a, const gs_component_record &b)
 {
     return a.first_row != b.first_row ? a.first_row < b.first_row : a.first_col < b.first_col;
+}
+
+// rec[0 .. n): the records of a slab that begins at row g of the global grid, local rows to global rows.
+inline void records_to_global_rows(gs_component_record *rec, size_t n, uint64_t g)
+{
+    for (size_t k = 0; k < n; ++k) {
+        gs_component_record &r = rec[k];
+        r.first_row += (uint32_t)g;
+        r.row_min += (uint32_t)g;
+        r.row_max += (uint32_t)g;
+        r.sum_row += r.size * g;
+    }
+}
+
+// rec[0 .. n): the records of a batch of `planes` planes of `rows` rows each.  A record's plane follows from its first cell,
+// whose row becomes the row inside that plane; before[p] is the number of the batch's records in the planes before plane p
+// (planes + 1 entries: before[planes] == n).
+inline void batch_records_to_planes(gs_component_record *rec, size_t n, uint64_t rows, size_t planes, std::vector<uint64_t> &before)
+{
+    before.assign(planes + 1, (uint64_t)0);
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t plane_of = rec[k].first_row / rows;
+        rec[k].first_row = (uint32_t)(rec[k].first_row % rows);
+        before[(size_t)plane_of + 1] += 1;
+    }
+    for (size_t p = 0; p < planes; ++p) before[p + 1] += before[p];
 }
 
 // The slabs in ascending global row order; none is empty.  part[s]: slab s's records, n[s] of them.  connectivity: 4 or 8.

@@ -11,6 +11,7 @@
 //                  minus the records of the planes before).
 //   fold_overlaps  drops the marks, sorts by (before, after) and adds the cells of equal pairs: two pieces of one pair -- a
 //                  U against a bar --, and pieces cut by a seam, become ONE overlap.
+//   fold_batch_overlaps  cuts the raw overlaps of a batch of members into the batch's planes and maps and folds each plane's.
 // Integers throughout: the result does not depend on the order in which the pieces arrive.
 #pragma once
 #include <algorithm>
@@ -61,6 +62,25 @@ inline std::vector<gs_component_overlap> fold_overlaps(const gs_component_overla
     }
     out.resize(w);
     return out;
+}
+
+// raw[0 .. n): the raw overlaps of a batch of `planes` planes, indices as the batch counts its records.  The pieces come in
+// first-cell order, so plane after plane; a kept piece's plane is that of its before-record: before[p] (after[p]) is the
+// number of the batch's before-records (after-records) in the planes before plane p, planes + 1 entries each
+// (batch_records_to_planes).  Plane p's overlaps, with the indices of the plane's own two lists and folded, are added to the
+// end of `out`, and their number to count[p].
+inline void fold_batch_overlaps(gs_component_overlap *raw, size_t n, const uint64_t *before, const uint64_t *after, size_t planes,
+                                std::vector<gs_component_overlap> &out, uint64_t *count)
+{
+    size_t at = 0;
+    for (size_t p = 0; p < planes; ++p) {
+        const size_t from = at;
+        while (at < n && (raw[at].before == kCompUnset || raw[at].before < before[p + 1])) ++at;
+        map_overlaps(raw + from, at - from, nullptr, (int64_t)before[p], nullptr, (int64_t)after[p]);
+        const std::vector<gs_component_overlap> folded = fold_overlaps(raw + from, at - from);
+        out.insert(out.end(), folded.begin(), folded.end());
+        count[p] += folded.size();
+    }
 }
 
 } // namespace gsi

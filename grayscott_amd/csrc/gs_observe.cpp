@@ -6,13 +6,17 @@
 // gs_members_match) and comparisons of two states (gs_fields_compare, gs_members_compare).  All observe a field list with launches per slab on its
 // compute stream into that slab's scratch buffer, fetch what the launches left and combine it here on the host, after the
 // results of every slab -- and, in a multi-process context, of every rank (exchange) -- have met; an ensemble's members are
-// observed in one launch on slab 0.  Two shapes of result, each with one path:
-//   row records   one record per (plane, row), gathered in global row order and folded on the host (row_records): summaries,
-//                 comparisons.
+// observed in one launch on slab 0.  Three shapes of result, each with one path:
+//   banded results  results per (plane, band of rows), gathered as [plane][band] over slabs and ranks (band_results): a record
+//                 per row, folded here in ascending global row order -- summaries, comparisons --, or the regions' results.
 //   u64 counters  zeroed, added to by the launch (the plane scans of gs_plane_scan.h), fetched and added over slabs and ranks
 //                 (slab_counters; an ensemble's member range: member_counters) -- integers, so the order of the additions
 //                 does not show: histograms, morphology, correlations.  A stencil's rows above a slab's first row are staged
 //                 into the slab's scratch buffer behind the counters (stage_rows_above), never read from ghost rows.
+//   listed records  a record per component of a labelling: counted, read back, record memory sized exactly, filled, fetched
+//                 -- over a field's slab chain (ChainListing: the host joins what crosses a seam) or a batch of members
+//                 (BatchListing: the host takes the records apart by plane): component lists, both sides of a match.  The
+//                 host steps on plain arrays are in gs_components_merge.h and gs_match_merge.h, tested without a device.
 // Components keep a slab loop of their own (label memory, seam rows, the ranks' verdict) over the same small helpers.
 //   summaries   row records from gs_row_summary_k (gs_summary.hip); the field fold -- rows added in ascending global row
 //               order -- is done on the host.  Ensembles fold on the device (gs_summary_fold_k): two records per member travel.
@@ -29,11 +33,11 @@
 //               labelled from the two label arrays and one overlap written per piece (gs_match.hip); the host makes the
 //               indices global and adds the cells of equal pairs (gs_match_merge.h).  Single-process contexts only.
 //   comparisons row records from gs_row_change_k (gs_change.hip) of pairs of planes, gathered and folded like the summaries'
-//               (row_records); ensembles fold on the device (gs_change_fold_k).
+//               (band_results); ensembles fold on the device (gs_change_fold_k).
 //   regional observables  summaries and bit-quad counts of every region of rh x rw cells of a plane (gs_fields_region_summaries,
 //               gs_fields_region_morphology; gs_regions.hip): one launch per slab leaves a record or a set of counters per
 //               (plane, region) -- a region lies inside one slab, so nothing is staged and nothing is folded on the host --
-//               and the slabs' and ranks' region rows meet in the global [plane][region] layout (region_results).  The regions'
+//               and the slabs' and ranks' region rows meet in the global [plane][region] layout (band_results).  The regions'
 //               two-point pair counts (gs_fields_region_correlation; gs_region_pairs.hip) travel the same way.
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
@@ -158,55 +162,68 @@ int32_t exchange(gs_ctx *ctx, const void *mine, const std::vector<size_t> &bytes
     return GS_OK;
 }
 
-// Row records of n planes (or pairs of planes) of f0's shape over the WHOLE global grid, as [plane][global row]: one launch
-// per slab on its compute stream into the slab's scratch buffer (`launch(slab, rows, records, stream)` writes
-// records[p * rows + r]), and, in a multi-process context, every rank's records to every rank (rank q holds the rows of
-// global slabs [q L, (q + 1) L)).  What folds row records in
-// ascending global row order -- summaries, comparisons -- folds `all` plane by plane.
-template <typename Rec, typename Launch>
-int32_t row_records(gs_ctx *ctx, const gs_field *f0, int32_t n, const char *what, std::vector<Rec> &all, Launch launch)
+// Banded results of n planes (or pairs of planes) of f0's shape over the WHOLE global grid: a band is rh rows, and every band
+// of every plane has RC results of `elem` bytes, gathered as [plane][band][result] into `all` (n * RR * RC * elem bytes, RR
+// the bands of the grid).  One launch per slab on its compute stream into the slab's scratch buffer -- zeroed first for
+// counters; `launch(slab, results, stream)` leaves results[(p * bands_of_the_slab + i) * RC + j] -- and, in a multi-process
+// context, every rank's results to every rank (rank q holds the bands of global slabs [q L, (q + 1) L)).  Every slab of the
+// global grid must begin at a multiple of rh rows (the precedent of reduced images): a band then lies inside one slab, slab
+// k's bands are [start_k / rh, ...) of the grid's, no ghost row is read and no row is staged; every rank reaches the same
+// verdict.  Row records -- summaries, comparisons, which fold `all` plane by plane in ascending global row order -- are bands
+// of one row with one 32-byte result, for which that refusal cannot fire; regions are bands of rh rows with RC results.
+template <typename Launch>
+int32_t band_results(gs_ctx *ctx, const gs_field *f0, int32_t n, int32_t rh, uint64_t RR, uint64_t RC, size_t elem, bool zeroed,
+                     const char *what, unsigned char *all, Launch launch)
 {
-    static_assert(sizeof(Rec) == 32, "row record layout");
-    // records of this process's rows, [plane][local row]
-    const size_t nslab = ctx->slabs.size();
-    size_t local_rows = 0;
-    for (const FieldSlab &fs : f0->s) local_rows += (size_t)fs.rows;
-    std::vector<Rec> local((size_t)n * local_rows);
-    size_t row_at = 0;
+    const uint64_t q = (uint64_t)rh, S = (uint64_t)ctx->total_slabs(), R = f0->rows;
+    for (uint64_t k = 1; k < S; ++k)
+        if ((k * R / S) % q != 0)
+            return fail(GS_ERR_UNSUPPORTED, "slab %llu begins at row %llu, which is not a multiple of the region height %d "
+                                            "(a region may not straddle two slabs)",
+                        (unsigned long long)k, (unsigned long long)(k * R / S), rh);
+    const size_t nslab = ctx->slabs.size(), line = (size_t)RC * elem; // (line: one band of one plane)
+    auto bands_of = [&](uint64_t rows) { return (size_t)((rows + q - 1) / q); };
+    size_t local_bands = 0;
+    for (const FieldSlab &fs : f0->s) local_bands += bands_of((uint64_t)fs.rows);
+    std::vector<unsigned char> gathered;
+    unsigned char *local = all; // one process: its bands are the grid's
+    if (ctx->world > 1) {
+        gathered.resize((size_t)n * local_bands * line);
+        local = gathered.data();
+    }
+    size_t at = 0;
     for (size_t i = 0; i < nslab; ++i) {
         SlabRt &sl = ctx->slabs[i];
-        const size_t rows = (size_t)f0->s[i].rows;
-        GS_TRY(ensure_scratch(ctx, (int)i, (size_t)n * rows * sizeof(Rec), what));
+        const size_t nb = bands_of((uint64_t)f0->s[i].rows);
+        if (nb == 0) continue;
+        GS_TRY(ensure_scratch(ctx, (int)i, (size_t)n * nb * line, what));
         GS_HIP(hipSetDevice(sl.device));
-        Rec *rec = static_cast<Rec *>(sl.scratch);
-        GS_HIP(launch(i, (int64_t)rows, rec, sl.compute));
+        unsigned char *dev = static_cast<unsigned char *>(sl.scratch);
+        if (zeroed) GS_HIP(hipMemsetAsync(dev, 0, (size_t)n * nb * line, sl.compute));
+        GS_HIP(launch(i, dev, sl.compute));
         for (int32_t p = 0; p < n; ++p)
-            GS_HIP(hipMemcpyAsync(local.data() + (size_t)p * local_rows + row_at, rec + (size_t)p * rows, rows * sizeof(Rec),
+            GS_HIP(hipMemcpyAsync(local + ((size_t)p * local_bands + at) * line, dev + (size_t)p * nb * line, nb * line,
                                   hipMemcpyDeviceToHost, sl.compute));
-        row_at += rows;
+        at += nb;
     }
     GS_TRY(sync_compute(ctx));
-    if (ctx->world == 1) {
-        all.swap(local);
-        return GS_OK;
-    }
-    const uint64_t L = (uint64_t)nslab, R = f0->rows;
+    if (ctx->world == 1) return GS_OK;
+    const uint64_t L = (uint64_t)nslab;
     std::vector<size_t> bytes((size_t)ctx->world, (size_t)0);
     for (uint64_t k = 0; k < (uint64_t)ctx->world * L; ++k)
-        bytes[(size_t)(k / L)] += (size_t)n * (size_t)global_slab_rows(ctx, R, k) * sizeof(Rec);
-    if (bytes[(size_t)ctx->rank] != local.size() * sizeof(Rec))
+        bytes[(size_t)(k / L)] += (size_t)n * bands_of(global_slab_rows(ctx, R, k)) * line;
+    if (bytes[(size_t)ctx->rank] != gathered.size())
         return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
-    std::vector<Rec> blocks((size_t)n * (size_t)R);
-    GS_TRY(exchange(ctx, local.data(), bytes, what, blocks.data()));
-    // rank blocks in rank order, each [plane][its rows]: plane p's records in global row order
-    all.resize((size_t)n * (size_t)R);
+    std::vector<unsigned char> blocks((size_t)n * (size_t)RR * line);
+    GS_TRY(exchange(ctx, gathered.data(), bytes, what, blocks.data()));
+    // rank blocks in rank order, each [plane][its bands]: plane p's bands in global order
     for (int32_t p = 0; p < n; ++p) {
-        size_t at = 0, row = 0;
-        for (int q = 0; q < ctx->world; ++q) {
-            const size_t rows = bytes[(size_t)q] / sizeof(Rec) / (size_t)n;
-            std::memcpy(all.data() + (size_t)p * (size_t)R + row, blocks.data() + at + (size_t)p * rows, rows * sizeof(Rec));
-            at += (size_t)n * rows;
-            row += rows;
+        size_t from = 0, row = 0;
+        for (int r = 0; r < ctx->world; ++r) {
+            const size_t nb = bytes[(size_t)r] / line / (size_t)n;
+            std::memcpy(all + ((size_t)p * (size_t)RR + row) * line, blocks.data() + from + (size_t)p * nb * line, nb * line);
+            from += (size_t)n * nb * line;
+            row += nb;
         }
     }
     return GS_OK;
@@ -524,11 +541,38 @@ int32_t check_list_rule(float threshold, int32_t connectivity, uint64_t min_size
 }
 
 // rows * rows * cols or rows * cols * cols >= 2^64: a record's sum of row or column indices could wrap.
-bool list_sums_could_wrap(uint64_t rows, uint64_t cols)
+int32_t check_list_sums(uint64_t rows, uint64_t cols, bool members)
 {
     const unsigned __int128 cells = (unsigned __int128)rows * cols; // (< 2^128)
-    if (cells >> 64) return rows != 0 && cols != 0;
-    return ((cells * rows) >> 64) != 0 || ((cells * cols) >> 64) != 0;
+    if (cells >> 64 ? rows == 0 || cols == 0 : ((cells * rows) >> 64) == 0 && ((cells * cols) >> 64) == 0) return GS_OK;
+    return members ? fail(GS_ERR_UNSUPPORTED, "members of %llu x %llu cells: a sum of row or column indices could pass 2^64",
+                          (unsigned long long)rows, (unsigned long long)cols)
+                   : fail(GS_ERR_UNSUPPORTED, "a grid of %llu x %llu cells: a sum of row or column indices could pass 2^64",
+                          (unsigned long long)rows, (unsigned long long)cols);
+}
+
+// Labels are u32 cell indices: every slab of this process (gs_fields_components asks every rank's), every member.
+int32_t check_slab_labels(const gs_ctx *ctx, const gs_field *f)
+{
+    for (size_t i = 0; i < ctx->slabs.size(); ++i)
+        if ((uint64_t)f->s[i].rows * f->cols >= ((uint64_t)1 << 32))
+            return fail(GS_ERR_UNSUPPORTED, "slab %zu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab", i,
+                        (unsigned long long)f->s[i].rows, (unsigned long long)f->cols);
+    return GS_OK;
+}
+
+int32_t check_member_labels(uint64_t cells)
+{
+    if (cells >= ((uint64_t)1 << 32))
+        return fail(GS_ERR_UNSUPPORTED, "a member holds %llu cells: labels are 32-bit, fewer than 2^32 cells", (unsigned long long)cells);
+    return GS_OK;
+}
+
+// Batches of whole members in one block of label memory: as many of `count` as fit the budget, at least one.
+uint64_t member_batch(uint64_t cells, uint64_t count)
+{
+    const uint64_t batch = (uint64_t)GS_COMPONENTS_BATCH_BYTES / 8 / cells;
+    return batch < 1 ? 1 : (batch > count ? count : batch);
 }
 
 int32_t refuse_world(const gs_ctx *ctx, const char *what = "component lists")
@@ -600,6 +644,129 @@ void *match_work(void *scratch, uint64_t entries, size_t cols, int k)
     return static_cast<unsigned char *>(scratch) + (size_t)k * list_work_bytes(entries, cols);
 }
 
+// ---- listings: records behind a labelling ------------------------------------------------------------------------------
+// The listing of ONE labelling of a field over this process's slab chain: `labels` holds the labelling, a block per slab, and
+// slot k of every slab's scratch buffer is its work memory (match_work; a lone list has slot 0).  Three steps, which the
+// caller's two sync_compute keep apart; the launch that labels slab i is the caller's, in front of count(i), and so is the
+// device that is current.  In a chain a component that touches a slab's first or last row is listed whatever its size:
+// min_size comes after the merge.
+struct ChainListing {
+    gs_ctx *ctx;
+    const gs_field *f;
+    const LabelMemory &labels;
+    int k;
+    uint64_t min_size;
+    std::vector<uint32_t> selected;                     // per slab: the records it lists
+    std::vector<std::vector<gs_component_record>> part; // per slab: its records
+    std::vector<std::vector<uint32_t>> seam;            // per slab of a chain: the record indices of its first and its last row
+
+    ChainListing(gs_ctx *c, const gs_field *field, const LabelMemory &l, int slot, uint64_t least)
+        : ctx(c), f(field), labels(l), k(slot), min_size(least), selected(c->slabs.size(), 0u), part(c->slabs.size()), seam(c->slabs.size()) {}
+    bool chain() const { return ctx->slabs.size() > 1; }
+    uint64_t cells(size_t i) const { return (uint64_t)f->s[i].rows * f->cols; }
+    void *work(size_t i) const { return match_work(ctx->slabs[i].scratch, cells(i), (size_t)f->cols, k); }
+
+    // Slab i, not empty: the count, and selected[i] on its way back.
+    int32_t count(size_t i)
+    {
+        const LabelMemory::Block &lb = labels.blocks[i];
+        const GsListWork w = list_work(work(i), lb.marks);
+        GS_HIP(gs_launch_list_count(lb.parent, lb.size, 1, (int64_t)f->s[i].rows, (int32_t)f->cols, min_size, w, ctx->slabs[i].compute));
+        GS_HIP(hipMemcpyAsync(&selected[i], w.selected, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->slabs[i].compute));
+        return GS_OK;
+    }
+
+    // Slab i, not empty, after the sync_compute that brought selected[i]: exactly that many records in `memory`, filled, and
+    // on their way back with, in a chain, the two seam rows.
+    int32_t fill(size_t i, RecordMemory &memory)
+    {
+        const size_t cols = (size_t)f->cols;
+        if (chain()) seam[i].assign(2 * cols, kCompUnset);
+        if (selected[i] == 0) return GS_OK; // (no set cell in its first or last row either)
+        SlabRt &sl = ctx->slabs[i];
+        const LabelMemory::Block &lb = labels.blocks[i];
+        GsComponentRecord *records = nullptr;
+        GS_TRY(memory.add(sl.device, selected[i], &records));
+        part[i].resize(selected[i]);
+        uint32_t *seams = chain() ? list_seams(work(i), cells(i)) : nullptr;
+        GS_HIP(gs_launch_list_fill(lb.parent, lb.size, 1, (int64_t)f->s[i].rows, (int32_t)cols, min_size, list_work(work(i), lb.marks),
+                                   records, seams, sl.compute));
+        GS_HIP(hipMemcpyAsync(part[i].data(), records, part[i].size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
+        if (chain()) GS_HIP(hipMemcpyAsync(seam[i].data(), seams, 2 * cols * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+        return GS_OK;
+    }
+
+    // After the second sync_compute: rows global, and the slabs' records as the one plane of `list` -- a chain's joined across
+    // the seams, `where` then saying what became of every slab's record (merge_component_lists).
+    void finish(int32_t connectivity, gs_component_list *list, std::vector<uint32_t> *where = nullptr)
+    {
+        const size_t nslab = part.size(), cols = (size_t)f->cols;
+        for (size_t i = 0; i < nslab; ++i) records_to_global_rows(part[i].data(), part[i].size(), f->s[i].g_row0);
+        if (!chain()) {
+            list->records.swap(part[0]);
+        } else {
+            std::vector<const gs_component_record *> recs;
+            std::vector<size_t> counts;
+            std::vector<ListSeamRows> rows;
+            for (size_t i = 0; i < nslab; ++i) {
+                if (f->s[i].rows == 0) continue;
+                recs.push_back(part[i].data());
+                counts.push_back(part[i].size());
+                rows.push_back(ListSeamRows{seam[i].data(), seam[i].data() + cols});
+            }
+            list->records = merge_component_lists(recs.data(), counts.data(), rows.data(), recs.size(), cols, connectivity, min_size, where);
+        }
+        list->offsets[1] = list->records.size();
+    }
+};
+
+// The listing of ONE labelling of a batch of an ensemble's members on slab 0, the current device: `lb` holds the labelling of
+// up to `batch` members stacked one after the other, and slot k of slab 0's scratch buffer is its work memory.  The launch
+// that labels the batch's nb members is the caller's, in front of count(nb), and so is the synchronisation behind it.
+struct BatchListing {
+    gs_ctx *ctx;
+    const gs_ensemble *e;
+    const LabelMemory::Block &lb;
+    GsListWork work;
+    uint64_t min_size;
+    uint32_t selected = 0;                 // the records the batch lists
+    std::vector<gs_component_record> host; // the batch's records
+    std::vector<uint64_t> before;          // the batch's records in the planes before plane p (batch_records_to_planes)
+
+    BatchListing(gs_ctx *c, const gs_ensemble *ens, const LabelMemory::Block &block, uint64_t batch, int k, uint64_t least)
+        : ctx(c), e(ens), lb(block), work(list_work(match_work(c->slabs[0].scratch, batch * ens->rows * ens->cols, 0, k), nullptr)),
+          min_size(least) {}
+
+    // The count, and `selected` on its way back.
+    int32_t count(uint64_t nb)
+    {
+        hipStream_t s = ctx->slabs[0].compute;
+        GS_HIP(gs_launch_list_count(lb.parent, lb.size, (int64_t)nb, (int64_t)e->rows, (int32_t)e->cols, min_size, work, s));
+        GS_HIP(hipMemcpyAsync(&selected, work.selected, sizeof selected, hipMemcpyDeviceToHost, s));
+        return GS_OK;
+    }
+
+    // After the synchronisation that brought `selected`: exactly that many records in `memory` -- nothing for none --, filled
+    // and fetched; then the records to planes b0 .. b0 + nb of `list`, whose offsets hold counts until the caller sums them.
+    int32_t fill(uint64_t b0, uint64_t nb, RecordMemory &memory, gs_component_list *list)
+    {
+        host.resize(selected);
+        if (selected != 0) {
+            SlabRt &sl = ctx->slabs[0];
+            GsComponentRecord *records = nullptr;
+            GS_TRY(memory.add(sl.device, selected, &records));
+            GS_HIP(gs_launch_list_fill(lb.parent, lb.size, (int64_t)nb, (int64_t)e->rows, (int32_t)e->cols, min_size, work, records,
+                                       nullptr, sl.compute));
+            GS_HIP(hipMemcpyAsync(host.data(), records, host.size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
+            GS_HIP(hipStreamSynchronize(sl.compute));
+        }
+        batch_records_to_planes(host.data(), host.size(), e->rows, (size_t)nb, before);
+        for (size_t p = 0; p < (size_t)nb; ++p) list->offsets[(size_t)b0 + p + 1] += before[p + 1] - before[p];
+        list->records.insert(list->records.end(), host.begin(), host.end());
+        return GS_OK;
+    }
+};
+
 // ---- regional observables ------------------------------------------------------------------------------------------------
 // The region grid of gs_hip.h for a grid of rows x cols cells, or its refusal.  No handle is looked at.
 int32_t region_grid(uint64_t rows, uint64_t cols, int32_t rh, int32_t rw, uint64_t *rr, uint64_t *rc)
@@ -625,70 +792,6 @@ int32_t check_regions(const gs_ctx *ctx, gs_field *const *fields, int32_t n, int
     return GS_OK;
 }
 
-// Results per region of n planes of f0's shape over the WHOLE global grid, `elem` bytes each, as [plane][region row][region
-// column] into `all`: one launch per slab on its compute stream into the slab's scratch buffer -- zeroed first for counters;
-// `launch(slab, results, stream)` leaves results[(p * rr_slab + i) * RC + j] -- and, in a multi-process context, every rank's
-// results to every rank.  Every slab of the global grid must begin at a multiple of rh rows (the precedent of reduced
-// images): a region then lies inside one slab, slab k's regions are rows [start_k / rh, ...) of the region grid, no ghost
-// row is read and no row is staged.  Every rank reaches the same verdict.
-template <typename Launch>
-int32_t region_results(gs_ctx *ctx, const gs_field *f0, int32_t n, int32_t rh, uint64_t RR, uint64_t RC, size_t elem, bool zeroed,
-                       const char *what, unsigned char *all, Launch launch)
-{
-    const uint64_t q = (uint64_t)rh, S = (uint64_t)ctx->total_slabs(), R = f0->rows;
-    for (uint64_t k = 1; k < S; ++k)
-        if ((k * R / S) % q != 0)
-            return fail(GS_ERR_UNSUPPORTED, "slab %llu begins at row %llu, which is not a multiple of the region height %d "
-                                            "(a region may not straddle two slabs)",
-                        (unsigned long long)k, (unsigned long long)(k * R / S), rh);
-    const size_t nslab = ctx->slabs.size(), line = (size_t)RC * elem; // (line: one row of the region grid of one plane)
-    auto region_rows = [&](uint64_t rows) { return (size_t)((rows + q - 1) / q); };
-    size_t local_rr = 0;
-    for (const FieldSlab &fs : f0->s) local_rr += region_rows((uint64_t)fs.rows);
-    std::vector<unsigned char> gathered;
-    unsigned char *local = all; // one process: its region rows are the grid's
-    if (ctx->world > 1) {
-        gathered.resize((size_t)n * local_rr * line);
-        local = gathered.data();
-    }
-    size_t at = 0;
-    for (size_t i = 0; i < nslab; ++i) {
-        SlabRt &sl = ctx->slabs[i];
-        const size_t rrs = region_rows((uint64_t)f0->s[i].rows);
-        if (rrs == 0) continue;
-        GS_TRY(ensure_scratch(ctx, (int)i, (size_t)n * rrs * line, what));
-        GS_HIP(hipSetDevice(sl.device));
-        unsigned char *dev = static_cast<unsigned char *>(sl.scratch);
-        if (zeroed) GS_HIP(hipMemsetAsync(dev, 0, (size_t)n * rrs * line, sl.compute));
-        GS_HIP(launch(i, dev, sl.compute));
-        for (int32_t p = 0; p < n; ++p)
-            GS_HIP(hipMemcpyAsync(local + ((size_t)p * local_rr + at) * line, dev + (size_t)p * rrs * line, rrs * line,
-                                  hipMemcpyDeviceToHost, sl.compute));
-        at += rrs;
-    }
-    GS_TRY(sync_compute(ctx));
-    if (ctx->world == 1) return GS_OK;
-    const uint64_t L = (uint64_t)nslab;
-    std::vector<size_t> bytes((size_t)ctx->world, (size_t)0);
-    for (uint64_t k = 0; k < (uint64_t)ctx->world * L; ++k)
-        bytes[(size_t)(k / L)] += (size_t)n * region_rows(global_slab_rows(ctx, R, k)) * line;
-    if (bytes[(size_t)ctx->rank] != gathered.size())
-        return fail(GS_ERR_INVALID, "row partition disagrees with this process's slabs");
-    std::vector<unsigned char> blocks((size_t)n * (size_t)RR * line);
-    GS_TRY(exchange(ctx, gathered.data(), bytes, what, blocks.data()));
-    // rank blocks in rank order, each [plane][its region rows]: plane p's region rows in global order
-    for (int32_t p = 0; p < n; ++p) {
-        size_t from = 0, row = 0;
-        for (int r = 0; r < ctx->world; ++r) {
-            const size_t rrs = bytes[(size_t)r] / line / (size_t)n;
-            std::memcpy(all + ((size_t)p * (size_t)RR + row) * line, blocks.data() + from + (size_t)p * rrs * line, rrs * line);
-            from += (size_t)n * rrs * line;
-            row += rrs;
-        }
-    }
-    return GS_OK;
-}
-
 } // namespace
 
 extern "C" {
@@ -702,11 +805,13 @@ int32_t gs_fields_summarize(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_
         for (int32_t p = 0; p < n; ++p) out[p] = empty_summary();
         return GS_OK;
     }
-    std::vector<GsRowSummary> rec;
-    GS_TRY(row_records<GsRowSummary>(ctx, f0, n, "summary", rec, [&](size_t i, int64_t rows, GsRowSummary *dev, hipStream_t s) {
+    std::vector<GsRowSummary> rec((size_t)n * (size_t)f0->rows); // a row's record: a band of one row with one result
+    GS_TRY(band_results(ctx, f0, n, 1, f0->rows, 1, sizeof(GsRowSummary), false, "summary", reinterpret_cast<unsigned char *>(rec.data()),
+                        [&](size_t i, unsigned char *dev, hipStream_t s) {
         const float *planes[4];
         slab_planes(fields, n, i, planes);
-        return gs_launch_row_summary(planes, n, f0->pitch, rows, (int32_t)f0->cols, dev, s);
+        return gs_launch_row_summary(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols,
+                                     reinterpret_cast<GsRowSummary *>(dev), s);
     }));
     for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(rec.data() + (size_t)p * (size_t)f0->rows, (size_t)f0->rows);
     return GS_OK;
@@ -741,12 +846,14 @@ int32_t gs_fields_compare(gs_ctx *ctx, gs_field *const *a, gs_field *const *b, i
     const gs_field *f0 = a[0];
     for (int32_t p = 0; p < n; ++p) out[p] = no_change();
     if (f0->rows == 0 || f0->cols == 0) return GS_OK; // the same shape on every rank: nobody exchanges anything
-    std::vector<GsRowChange> rec;
-    GS_TRY(row_records<GsRowChange>(ctx, f0, n, "comparison", rec, [&](size_t i, int64_t rows, GsRowChange *dev, hipStream_t s) {
+    std::vector<GsRowChange> rec((size_t)n * (size_t)f0->rows); // as the summaries' rows
+    GS_TRY(band_results(ctx, f0, n, 1, f0->rows, 1, sizeof(GsRowChange), false, "comparison", reinterpret_cast<unsigned char *>(rec.data()),
+                        [&](size_t i, unsigned char *dev, hipStream_t s) {
         const float *pa[4], *pb[4];
         slab_planes(a, n, i, pa);
         slab_planes(b, n, i, pb);
-        return gs_launch_row_change(pa, pb, n, f0->pitch, rows, (int32_t)f0->cols, dev, s);
+        return gs_launch_row_change(pa, pb, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols,
+                                    reinterpret_cast<GsRowChange *>(dev), s);
     }));
     for (int32_t p = 0; p < n; ++p) out[p] = fold_rows(rec.data() + (size_t)p * (size_t)f0->rows, (size_t)f0->rows);
     return GS_OK;
@@ -1052,11 +1159,8 @@ int32_t gs_members_components(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
     const size_t passes = 2 * (size_t)nt, results = (size_t)count * passes;
     std::memset(out, 0, results * sizeof(gs_components));
     if (cells == 0 || count == 0) return GS_OK;
-    if (cells >= ((uint64_t)1 << 32))
-        return fail(GS_ERR_UNSUPPORTED, "a member holds %llu cells: labels are 32-bit, fewer than 2^32 cells", (unsigned long long)cells);
-    // batches of whole members in one block of label memory: as many as fit the budget, at least one
-    uint64_t batch = (uint64_t)GS_COMPONENTS_BATCH_BYTES / 8 / cells;
-    batch = batch < 1 ? 1 : (batch > count ? count : batch);
+    GS_TRY(check_member_labels(cells));
+    const uint64_t batch = member_batch(cells, count);
     SlabRt &sl = ctx->slabs[0];
     LabelMemory labels;
     GS_TRY(labels.add(sl.device, batch * cells));
@@ -1103,15 +1207,9 @@ int32_t gs_field_component_list(gs_ctx *ctx, gs_field *f, float threshold, int32
         *out = list.release();
         return GS_OK;
     }
-    if (list_sums_could_wrap(f->rows, f->cols))
-        return fail(GS_ERR_UNSUPPORTED, "a grid of %llu x %llu cells: a sum of row or column indices could pass 2^64",
-                    (unsigned long long)f->rows, (unsigned long long)f->cols);
+    GS_TRY(check_list_sums(f->rows, f->cols, false));
+    GS_TRY(check_slab_labels(ctx, f));
     const size_t nslab = ctx->slabs.size(), cols = (size_t)f->cols;
-    for (size_t i = 0; i < nslab; ++i)
-        if ((uint64_t)f->s[i].rows * (uint64_t)cols >= ((uint64_t)1 << 32))
-            return fail(GS_ERR_UNSUPPORTED, "slab %zu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab", i,
-                        (unsigned long long)f->s[i].rows, (unsigned long long)cols);
-    // In a chain a component that touches a slab's first or last row is listed whatever its size: min_size comes after the merge.
     const bool chain = nslab > 1;
     LabelMemory labels;
     for (size_t i = 0; i < nslab; ++i) {
@@ -1119,64 +1217,21 @@ int32_t gs_field_component_list(gs_ctx *ctx, gs_field *f, float threshold, int32
         GS_TRY(labels.add(ctx->slabs[i].device, cells, chain ? (cells + 31) / 32 : 0));
         GS_TRY(ensure_scratch(ctx, (int)i, list_work_bytes(cells, cols), "component list"));
     }
-    std::vector<uint32_t> selected(nslab, 0u);
+    ChainListing listing(ctx, f, labels, 0, min_size);
     for (size_t i = 0; i < nslab; ++i) {
         if (f->s[i].rows == 0) continue;
         SlabRt &sl = ctx->slabs[i];
-        const LabelMemory::Block &lb = labels.blocks[i];
         GS_HIP(hipSetDevice(sl.device));
         GS_HIP(gs_launch_component_labels(f->s[i].row0, 1, 0, f->pitch, (int64_t)f->s[i].rows, (int32_t)cols, threshold, above,
-                                          connectivity, lb.parent, lb.size, sl.compute));
-        const GsListWork work = list_work(sl.scratch, lb.marks);
-        GS_HIP(gs_launch_list_count(lb.parent, lb.size, 1, (int64_t)f->s[i].rows, (int32_t)cols, min_size, work, sl.compute));
-        GS_HIP(hipMemcpyAsync(&selected[i], work.selected, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+                                          connectivity, labels.blocks[i].parent, labels.blocks[i].size, sl.compute));
+        GS_TRY(listing.count(i));
     }
     GS_TRY(sync_compute(ctx)); // the one read-back: the record memory is sized exactly
     RecordMemory memory;
-    std::vector<std::vector<gs_component_record>> part(nslab);
-    std::vector<std::vector<uint32_t>> seam(nslab);
-    for (size_t i = 0; i < nslab; ++i) {
-        if (f->s[i].rows == 0) continue;
-        if (chain) seam[i].assign(2 * cols, kCompUnset);
-        if (selected[i] == 0) continue; // (no set cell in its first or last row either)
-        SlabRt &sl = ctx->slabs[i];
-        const LabelMemory::Block &lb = labels.blocks[i];
-        const uint64_t cells = (uint64_t)f->s[i].rows * (uint64_t)cols;
-        GsComponentRecord *records = nullptr;
-        GS_TRY(memory.add(sl.device, selected[i], &records));
-        part[i].resize(selected[i]);
-        uint32_t *seams = chain ? list_seams(sl.scratch, cells) : nullptr;
-        GS_HIP(gs_launch_list_fill(lb.parent, lb.size, 1, (int64_t)f->s[i].rows, (int32_t)cols, min_size, list_work(sl.scratch, lb.marks),
-                                   records, seams, sl.compute));
-        GS_HIP(hipMemcpyAsync(part[i].data(), records, part[i].size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
-        if (chain) GS_HIP(hipMemcpyAsync(seam[i].data(), seams, 2 * cols * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
-    }
+    for (size_t i = 0; i < nslab; ++i)
+        if (f->s[i].rows != 0) GS_TRY(listing.fill(i, memory));
     GS_TRY(sync_compute(ctx));
-    // local rows to rows of the global grid
-    for (size_t i = 0; i < nslab; ++i) {
-        const uint64_t g = f->s[i].g_row0;
-        for (gs_component_record &r : part[i]) {
-            r.first_row += (uint32_t)g;
-            r.row_min += (uint32_t)g;
-            r.row_max += (uint32_t)g;
-            r.sum_row += r.size * g;
-        }
-    }
-    if (!chain) {
-        list->records.swap(part[0]);
-    } else {
-        std::vector<const gs_component_record *> recs;
-        std::vector<size_t> counts;
-        std::vector<ListSeamRows> rows;
-        for (size_t i = 0; i < nslab; ++i) {
-            if (f->s[i].rows == 0) continue;
-            recs.push_back(part[i].data());
-            counts.push_back(part[i].size());
-            rows.push_back(ListSeamRows{seam[i].data(), seam[i].data() + cols});
-        }
-        list->records = merge_component_lists(recs.data(), counts.data(), rows.data(), recs.size(), cols, connectivity, min_size);
-    }
-    list->offsets[1] = list->records.size();
+    listing.finish(connectivity, list.get());
     *out = list.release();
     return GS_OK;
 }
@@ -1198,48 +1253,27 @@ int32_t gs_members_component_list(gs_ctx *ctx, gs_ensemble *e, uint64_t first, u
         *out = list.release();
         return GS_OK;
     }
-    if (cells >= ((uint64_t)1 << 32))
-        return fail(GS_ERR_UNSUPPORTED, "a member holds %llu cells: labels are 32-bit, fewer than 2^32 cells", (unsigned long long)cells);
-    if (list_sums_could_wrap(e->rows, e->cols))
-        return fail(GS_ERR_UNSUPPORTED, "members of %llu x %llu cells: a sum of row or column indices could pass 2^64",
-                    (unsigned long long)e->rows, (unsigned long long)e->cols);
+    GS_TRY(check_member_labels(cells));
+    GS_TRY(check_list_sums(e->rows, e->cols, true));
     // batches of whole members in one block of label memory, as gs_members_components takes them
-    uint64_t batch = (uint64_t)GS_COMPONENTS_BATCH_BYTES / 8 / cells;
-    batch = batch < 1 ? 1 : (batch > count ? count : batch);
+    const uint64_t batch = member_batch(cells, count);
     SlabRt &sl = ctx->slabs[0];
     LabelMemory labels;
     GS_TRY(labels.add(sl.device, batch * cells));
     GS_TRY(ensure_scratch(ctx, 0, list_work_bytes(batch * cells, 0), "component list"));
     GS_HIP(hipSetDevice(sl.device));
     const LabelMemory::Block &lb = labels.blocks[0];
-    const GsListWork work = list_work(sl.scratch, nullptr);
-    std::vector<gs_component_record> host;
+    BatchListing listing(ctx, e, lb, batch, 0, min_size);
     for (uint64_t b0 = 0; b0 < count; b0 += batch) {
         const uint64_t nb = count - b0 < batch ? count - b0 : batch;
         // each member a plane of its own, `cells` floats from one to the next: it never sees its neighbours' rows
         const float *plane = (species ? e->v[e->cur] : e->u[e->cur]) + (first + b0) * cells;
         GS_HIP(gs_launch_component_labels(plane, (int64_t)nb, (int64_t)cells, (int64_t)e->cols, (int64_t)e->rows, (int32_t)e->cols,
                                           threshold, above, connectivity, lb.parent, lb.size, sl.compute));
-        GS_HIP(gs_launch_list_count(lb.parent, lb.size, (int64_t)nb, (int64_t)e->rows, (int32_t)e->cols, min_size, work, sl.compute));
-        uint32_t selected = 0;
-        GS_HIP(hipMemcpyAsync(&selected, work.selected, sizeof selected, hipMemcpyDeviceToHost, sl.compute));
+        GS_TRY(listing.count(nb));
         GS_HIP(hipStreamSynchronize(sl.compute));
-        if (selected == 0) continue;
         RecordMemory memory; // (of this batch)
-        GsComponentRecord *records = nullptr;
-        GS_TRY(memory.add(sl.device, selected, &records));
-        host.resize(selected);
-        GS_HIP(gs_launch_list_fill(lb.parent, lb.size, (int64_t)nb, (int64_t)e->rows, (int32_t)e->cols, min_size, work, records, nullptr,
-                                   sl.compute));
-        GS_HIP(hipMemcpyAsync(host.data(), records, host.size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
-        GS_HIP(hipStreamSynchronize(sl.compute));
-        // the records come in first-cell order over the batch's planes, one after the other: a record's plane follows from its root
-        for (gs_component_record &r : host) {
-            const uint64_t plane_of = r.first_row / e->rows;
-            r.first_row = (uint32_t)(r.first_row % e->rows);
-            list->offsets[(size_t)(b0 + plane_of) + 1] += 1;
-        }
-        list->records.insert(list->records.end(), host.begin(), host.end());
+        GS_TRY(listing.fill(b0, nb, memory, list.get()));
     }
     for (size_t i = 0; i < (size_t)count; ++i) list->offsets[i + 1] += list->offsets[i];
     *out = list.release();
@@ -1285,14 +1319,9 @@ int32_t gs_fields_match(gs_ctx *ctx, gs_field *before, gs_field *after, float th
         *out = match.release();
         return GS_OK;
     }
-    if (list_sums_could_wrap(f->rows, f->cols))
-        return fail(GS_ERR_UNSUPPORTED, "a grid of %llu x %llu cells: a sum of row or column indices could pass 2^64",
-                    (unsigned long long)f->rows, (unsigned long long)f->cols);
+    GS_TRY(check_list_sums(f->rows, f->cols, false));
+    GS_TRY(check_slab_labels(ctx, f));
     const size_t nslab = ctx->slabs.size(), cols = (size_t)f->cols;
-    for (size_t i = 0; i < nslab; ++i)
-        if ((uint64_t)f->s[i].rows * (uint64_t)cols >= ((uint64_t)1 << 32))
-            return fail(GS_ERR_UNSUPPORTED, "slab %zu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab", i,
-                        (unsigned long long)f->s[i].rows, (unsigned long long)cols);
     const bool chain = nslab > 1;
     // label memory: 0 before, 1 after, 2 the pieces (no marks: a piece is listed whatever its size)
     LabelMemory labels[3];
@@ -1301,12 +1330,12 @@ int32_t gs_fields_match(gs_ctx *ctx, gs_field *before, gs_field *after, float th
         for (int k = 0; k < 3; ++k) GS_TRY(labels[k].add(ctx->slabs[i].device, cells, chain && k < 2 ? (cells + 31) / 32 : 0));
         GS_TRY(ensure_scratch(ctx, (int)i, match_work_bytes(cells, cols), "component match"));
     }
-    std::vector<uint32_t> selected(3 * nslab, 0u);
+    // (the pieces are counted as a list is; their records are the overlaps below)
+    ChainListing listing[3] = {{ctx, f, labels[0], 0, min_size}, {ctx, f, labels[1], 1, min_size}, {ctx, f, labels[2], 2, 1}};
     for (size_t i = 0; i < nslab; ++i) {
         if (f->s[i].rows == 0) continue;
         SlabRt &sl = ctx->slabs[i];
         const int64_t rows = (int64_t)f->s[i].rows;
-        const uint64_t cells = (uint64_t)rows * (uint64_t)cols;
         GS_HIP(hipSetDevice(sl.device));
         for (int k = 0; k < 3; ++k) {
             const LabelMemory::Block &lb = labels[k].blocks[i];
@@ -1316,80 +1345,32 @@ int32_t gs_fields_match(gs_ctx *ctx, gs_field *before, gs_field *after, float th
             else
                 GS_HIP(gs_launch_piece_labels(labels[0].blocks[i].parent, labels[1].blocks[i].parent, 1, rows, (int32_t)cols,
                                               connectivity, lb.parent, lb.size, sl.compute));
-            const GsListWork work = list_work(match_work(sl.scratch, cells, cols, k), lb.marks);
-            GS_HIP(gs_launch_list_count(lb.parent, lb.size, 1, rows, (int32_t)cols, k < 2 ? min_size : 1, work, sl.compute));
-            GS_HIP(hipMemcpyAsync(&selected[3 * i + (size_t)k], work.selected, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+            GS_TRY(listing[k].count(i));
         }
     }
     GS_TRY(sync_compute(ctx)); // the one read-back: record and overlap memory are sized exactly
     RecordMemory memory; // (the records and the overlaps)
-    std::vector<std::vector<gs_component_record>> part[2];
-    std::vector<std::vector<uint32_t>> seam[2];
     std::vector<std::vector<gs_component_overlap>> raw(nslab);
-    for (int k = 0; k < 2; ++k) part[k].resize(nslab), seam[k].resize(nslab);
     for (size_t i = 0; i < nslab; ++i) {
         if (f->s[i].rows == 0) continue;
         SlabRt &sl = ctx->slabs[i];
-        const int64_t rows = (int64_t)f->s[i].rows;
-        const uint64_t cells = (uint64_t)rows * (uint64_t)cols;
         GS_HIP(hipSetDevice(sl.device));
-        for (int k = 0; k < 2; ++k) {
-            if (chain) seam[k][i].assign(2 * cols, kCompUnset);
-            const uint32_t n = selected[3 * i + (size_t)k];
-            if (n == 0) continue; // (no set cell in its first or last row either)
-            const LabelMemory::Block &lb = labels[k].blocks[i];
-            void *w = match_work(sl.scratch, cells, cols, k);
-            GsComponentRecord *records = nullptr;
-            GS_TRY(memory.add(sl.device, n, &records));
-            part[k][i].resize(n);
-            uint32_t *seams = chain ? list_seams(w, cells) : nullptr;
-            GS_HIP(gs_launch_list_fill(lb.parent, lb.size, 1, rows, (int32_t)cols, min_size, list_work(w, lb.marks), records, seams,
-                                       sl.compute));
-            GS_HIP(hipMemcpyAsync(part[k][i].data(), records, (size_t)n * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
-            if (chain) GS_HIP(hipMemcpyAsync(seam[k][i].data(), seams, 2 * cols * sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
-        }
+        for (int k = 0; k < 2; ++k) GS_TRY(listing[k].fill(i, memory));
         // a piece names records only where both lists have some: otherwise every piece of the slab is dropped
-        const uint32_t np = selected[3 * i + 2];
-        if (np == 0 || selected[3 * i] == 0 || selected[3 * i + 1] == 0) continue;
+        const uint32_t np = listing[2].selected[i];
+        if (np == 0 || listing[0].selected[i] == 0 || listing[1].selected[i] == 0) continue;
         GsMatchOverlap *dev = nullptr;
         GS_TRY(memory.add(sl.device, np, &dev));
         raw[i].resize(np);
-        const GsListWork work = list_work(match_work(sl.scratch, cells, cols, 2), nullptr);
+        const GsListWork work = list_work(listing[2].work(i), nullptr);
         GS_HIP(gs_launch_match_pairs(labels[0].blocks[i].parent, labels[0].blocks[i].size, labels[1].blocks[i].parent,
                                      labels[1].blocks[i].size, labels[2].blocks[i].parent, labels[2].blocks[i].size, work.counts, 1,
-                                     rows, (int32_t)cols, dev, sl.compute));
+                                     (int64_t)f->s[i].rows, (int32_t)cols, dev, sl.compute));
         GS_HIP(hipMemcpyAsync(raw[i].data(), dev, (size_t)np * sizeof(gs_component_overlap), hipMemcpyDeviceToHost, sl.compute));
     }
     GS_TRY(sync_compute(ctx));
     std::vector<uint32_t> where[2];
-    for (int k = 0; k < 2; ++k) {
-        // local rows to rows of the global grid
-        for (size_t i = 0; i < nslab; ++i) {
-            const uint64_t g = f->s[i].g_row0;
-            for (gs_component_record &r : part[k][i]) {
-                r.first_row += (uint32_t)g;
-                r.row_min += (uint32_t)g;
-                r.row_max += (uint32_t)g;
-                r.sum_row += r.size * g;
-            }
-        }
-        if (!chain) {
-            lists[k]->records.swap(part[k][0]);
-        } else {
-            std::vector<const gs_component_record *> recs;
-            std::vector<size_t> counts;
-            std::vector<ListSeamRows> rows;
-            for (size_t i = 0; i < nslab; ++i) {
-                if (f->s[i].rows == 0) continue;
-                recs.push_back(part[k][i].data());
-                counts.push_back(part[k][i].size());
-                rows.push_back(ListSeamRows{seam[k][i].data(), seam[k][i].data() + cols});
-            }
-            lists[k]->records =
-                merge_component_lists(recs.data(), counts.data(), rows.data(), recs.size(), cols, connectivity, min_size, &where[k]);
-        }
-        lists[k]->offsets[1] = lists[k]->records.size();
-    }
+    for (int k = 0; k < 2; ++k) listing[k].finish(connectivity, lists[k], &where[k]);
     // slab-local record indices to those of the two lists; then one overlap per pair
     std::vector<gs_component_overlap> all;
     int64_t base[2] = {0, 0};
@@ -1397,7 +1378,7 @@ int32_t gs_fields_match(gs_ctx *ctx, gs_field *before, gs_field *after, float th
         if (chain)
             map_overlaps(raw[i].data(), raw[i].size(), where[0].data(), base[0], where[1].data(), base[1]);
         all.insert(all.end(), raw[i].begin(), raw[i].end());
-        for (int k = 0; k < 2; ++k) base[k] += (int64_t)selected[3 * i + (size_t)k];
+        for (int k = 0; k < 2; ++k) base[k] += (int64_t)listing[k].selected[i];
     }
     match->overlaps = fold_overlaps(all.data(), all.size());
     match->offsets[1] = match->overlaps.size();
@@ -1428,14 +1409,10 @@ int32_t gs_members_match(gs_ctx *ctx, gs_ensemble *before, gs_ensemble *after, u
         *out = match.release();
         return GS_OK;
     }
-    if (cells >= ((uint64_t)1 << 32))
-        return fail(GS_ERR_UNSUPPORTED, "a member holds %llu cells: labels are 32-bit, fewer than 2^32 cells", (unsigned long long)cells);
-    if (list_sums_could_wrap(e->rows, e->cols))
-        return fail(GS_ERR_UNSUPPORTED, "members of %llu x %llu cells: a sum of row or column indices could pass 2^64",
-                    (unsigned long long)e->rows, (unsigned long long)e->cols);
+    GS_TRY(check_member_labels(cells));
+    GS_TRY(check_list_sums(e->rows, e->cols, true));
     // batches of whole members, as gs_members_component_list takes them: each of the three labellings within the budget
-    uint64_t batch = (uint64_t)GS_COMPONENTS_BATCH_BYTES / 8 / cells;
-    batch = batch < 1 ? 1 : (batch > count ? count : batch);
+    const uint64_t batch = member_batch(cells, count);
     SlabRt &sl = ctx->slabs[0];
     LabelMemory labels; // blocks 0 before, 1 after, 2 the pieces
     for (int k = 0; k < 3; ++k) GS_TRY(labels.add(sl.device, batch * cells));
@@ -1443,16 +1420,14 @@ int32_t gs_members_match(gs_ctx *ctx, gs_ensemble *before, gs_ensemble *after, u
     GS_HIP(hipSetDevice(sl.device));
     const int64_t rows = (int64_t)e->rows;
     const int32_t cols = (int32_t)e->cols;
-    std::vector<gs_component_record> host;
+    // (the pieces are counted as a list is; their records are the overlaps below)
+    BatchListing listing[3] = {{ctx, e, labels.blocks[0], batch, 0, min_size}, {ctx, e, labels.blocks[1], batch, 1, min_size},
+                               {ctx, e, labels.blocks[2], batch, 2, 1}};
     std::vector<gs_component_overlap> raw;
-    std::vector<uint64_t> local[2]; // the records of the batch's planes before plane p, per list
     for (uint64_t b0 = 0; b0 < count; b0 += batch) {
         const uint64_t nb = count - b0 < batch ? count - b0 : batch;
-        uint32_t selected[3] = {0u, 0u, 0u};
-        GsListWork work[3];
         for (int k = 0; k < 3; ++k) {
             const LabelMemory::Block &lb = labels.blocks[(size_t)k];
-            work[k] = list_work(match_work(sl.scratch, batch * cells, 0, k), nullptr);
             if (k < 2) {
                 // each member a plane of its own, `cells` floats from one to the next: it never sees its neighbours' rows
                 const gs_ensemble *m = side[k];
@@ -1463,50 +1438,23 @@ int32_t gs_members_match(gs_ctx *ctx, gs_ensemble *before, gs_ensemble *after, u
                 GS_HIP(gs_launch_piece_labels(labels.blocks[0].parent, labels.blocks[1].parent, (int64_t)nb, rows, cols, connectivity,
                                               lb.parent, lb.size, sl.compute));
             }
-            GS_HIP(gs_launch_list_count(lb.parent, lb.size, (int64_t)nb, rows, cols, k < 2 ? min_size : 1, work[k], sl.compute));
-            GS_HIP(hipMemcpyAsync(&selected[k], work[k].selected, sizeof(uint32_t), hipMemcpyDeviceToHost, sl.compute));
+            GS_TRY(listing[k].count(nb));
         }
         GS_HIP(hipStreamSynchronize(sl.compute));
         RecordMemory memory; // (of this batch: the records and the overlaps)
-        for (int k = 0; k < 2; ++k) {
-            local[k].assign((size_t)nb + 1, (uint64_t)0);
-            if (selected[k] == 0) continue;
-            const LabelMemory::Block &lb = labels.blocks[(size_t)k];
-            GsComponentRecord *records = nullptr;
-            GS_TRY(memory.add(sl.device, selected[k], &records));
-            host.resize(selected[k]);
-            GS_HIP(gs_launch_list_fill(lb.parent, lb.size, (int64_t)nb, rows, cols, min_size, work[k], records, nullptr, sl.compute));
-            GS_HIP(hipMemcpyAsync(host.data(), records, host.size() * sizeof(gs_component_record), hipMemcpyDeviceToHost, sl.compute));
-            GS_HIP(hipStreamSynchronize(sl.compute));
-            // the records come in first-cell order over the batch's planes, one after the other: a record's plane follows from its root
-            for (gs_component_record &r : host) {
-                const uint64_t plane_of = r.first_row / e->rows;
-                r.first_row = (uint32_t)(r.first_row % e->rows);
-                lists[k]->offsets[(size_t)(b0 + plane_of) + 1] += 1;
-                local[k][(size_t)plane_of + 1] += 1;
-            }
-            for (size_t p = 0; p < (size_t)nb; ++p) local[k][p + 1] += local[k][p];
-            lists[k]->records.insert(lists[k]->records.end(), host.begin(), host.end());
-        }
-        if (selected[2] == 0 || selected[0] == 0 || selected[1] == 0) continue; // (no piece names a record)
+        for (int k = 0; k < 2; ++k) GS_TRY(listing[k].fill(b0, nb, memory, lists[k]));
+        const uint32_t np = listing[2].selected;
+        if (np == 0 || listing[0].selected == 0 || listing[1].selected == 0) continue; // (no piece names a record)
         GsMatchOverlap *dev = nullptr;
-        GS_TRY(memory.add(sl.device, selected[2], &dev));
-        raw.resize(selected[2]);
+        GS_TRY(memory.add(sl.device, np, &dev));
+        raw.resize(np);
         GS_HIP(gs_launch_match_pairs(labels.blocks[0].parent, labels.blocks[0].size, labels.blocks[1].parent, labels.blocks[1].size,
-                                     labels.blocks[2].parent, labels.blocks[2].size, work[2].counts, (int64_t)nb, rows, cols, dev,
+                                     labels.blocks[2].parent, labels.blocks[2].size, listing[2].work.counts, (int64_t)nb, rows, cols, dev,
                                      sl.compute));
         GS_HIP(hipMemcpyAsync(raw.data(), dev, raw.size() * sizeof(gs_component_overlap), hipMemcpyDeviceToHost, sl.compute));
         GS_HIP(hipStreamSynchronize(sl.compute));
-        // the pieces come in first-cell order, so plane after plane; a kept piece's plane is that of its before-record
-        size_t at = 0;
-        for (size_t p = 0; p < (size_t)nb; ++p) {
-            const size_t from = at;
-            while (at < raw.size() && (raw[at].before == kCompUnset || raw[at].before < local[0][p + 1])) ++at;
-            map_overlaps(raw.data() + from, at - from, nullptr, (int64_t)local[0][p], nullptr, (int64_t)local[1][p]);
-            const std::vector<gs_component_overlap> folded = fold_overlaps(raw.data() + from, at - from);
-            match->overlaps.insert(match->overlaps.end(), folded.begin(), folded.end());
-            match->offsets[(size_t)b0 + p + 1] += folded.size();
-        }
+        fold_batch_overlaps(raw.data(), raw.size(), listing[0].before.data(), listing[1].before.data(), (size_t)nb, match->overlaps,
+                            &match->offsets[(size_t)b0 + 1]);
     }
     for (size_t i = 0; i < (size_t)count; ++i) {
         for (gs_component_list *l : lists) l->offsets[i + 1] += l->offsets[i];
@@ -1553,8 +1501,8 @@ int32_t gs_fields_region_summaries(gs_ctx *ctx, gs_field *const *fields, int32_t
     static_assert(sizeof(GsRegionSummary) == sizeof(gs_summary) && offsetof(GsRegionSummary, min) == offsetof(gs_summary, min) &&
                       offsetof(GsRegionSummary, nonfinite) == offsetof(gs_summary, nonfinite),
                   "region record layout");
-    return region_results(ctx, f0, n, rh, RR, RC, sizeof(GsRegionSummary), false, "region summary",
-                          reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+    return band_results(ctx, f0, n, rh, RR, RC, sizeof(GsRegionSummary), false, "region summary",
+                        reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
         const float *planes[4];
         slab_planes(fields, n, i, planes);
         return gs_launch_region_summary(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw,
@@ -1576,8 +1524,8 @@ int32_t gs_fields_region_morphology(gs_ctx *ctx, gs_field *const *fields, int32_
     // The counters land in `out` as they are -- six words per result, Q0's left zero by the launch: with up to 2^22 regions
     // a buffer between the device and the caller's memory would be tens of MiB of freshly mapped pages in every call, whose
     // first touch under the copy costs more than the launch (profiles/regions.md).
-    GS_TRY(region_results(ctx, f0, n, rh, RR, RC, (size_t)nt * sizeof(gs_morphology), true, "region morphology",
-                          reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+    GS_TRY(band_results(ctx, f0, n, rh, RR, RC, (size_t)nt * sizeof(gs_morphology), true, "region morphology",
+                        reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
         const float *planes[4];
         slab_planes(fields, n, i, planes);
         return gs_launch_region_quads(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, thresholds, above,
@@ -1615,8 +1563,8 @@ int32_t gs_fields_region_correlation(gs_ctx *ctx, gs_field *const *fields, int32
         return fail(GS_ERR_INVALID, "%llu x %llu regions of %llu counters each (at most %u counters per field)",
                     (unsigned long long)RR, (unsigned long long)RC, (unsigned long long)per_region, (unsigned)GS_REGION_PAIRS_MAX);
     // the counters land in `out` as they are, as the bit quads' do
-    return region_results(ctx, f0, n, rh, RR, RC, (size_t)per_region * sizeof(uint64_t), true, "region correlation",
-                          reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+    return band_results(ctx, f0, n, rh, RR, RC, (size_t)per_region * sizeof(uint64_t), true, "region correlation",
+                        reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
         const float *planes[4];
         slab_planes(fields, n, i, planes);
         return gs_launch_region_pairs(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, thresholds, above,

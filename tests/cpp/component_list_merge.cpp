@@ -2,8 +2,11 @@
 // gs_field_component_list; grayscott_amd/csrc/gs_components_merge.h: merge_component_lists).  A small plane is cut into 1..5
 // slabs (one-row slabs included); every slab is labelled on the host with the find / unite of gs_unionfind.h as if it were
 // alone and lists what the device would: the components of at least min_size cells and, in a chain, every component that
-// touches the slab's first or last row, in first-cell order, with rows made global, and the record index of every cell of
-// those two rows.  The merge of these must equal the list of the whole plane, record for record.
+// touches the slab's first or last row, in first-cell order, rows counted from the slab's first as the device counts them,
+// and the record index of every cell of those two rows.  records_to_global_rows and then the merge of these must equal the
+// list of the whole plane, record for record.  A batch of 1..4 planes, some of them empty, stacked as an ensemble's members
+// are -- the records in first-cell order over the stack, the first cell's row counted over the stack -- must come apart
+// again into every plane's own list (batch_records_to_planes).
 // Exit status 0 and "ok" when everything agrees.  Stand-alone: it links nothing of the library.
 #include "../../grayscott_amd/csrc/gs_components_merge.h"
 #include "../../grayscott_amd/csrc/gs_unionfind.h"
@@ -22,7 +25,7 @@ struct Plane {
 };
 
 struct SlabList {
-    std::vector<gs_component_record> records; // rows global
+    std::vector<gs_component_record> records; // rows local to the slab
     std::vector<uint32_t> first_index, last_index;
 };
 
@@ -52,7 +55,7 @@ SlabList list_rows(const Plane &p, size_t r0, size_t r1, int connectivity, uint6
         if (parent[i] == kUfUnset) continue;
         const uint32_t root = gs_uf_find(parent.data(), (uint32_t)i);
         parent[i] = root;
-        const uint32_t r = (uint32_t)(r0 + i / cols), c = (uint32_t)(i % cols);
+        const uint32_t r = (uint32_t)(i / cols), c = (uint32_t)(i % cols);
         gs_component_record &x = rec[root];
         if (root == i) x = gs_component_record{0, 0, 0, r, c, r, r, c, c}; // (a root is its component's first cell)
         x.size += 1;
@@ -79,12 +82,53 @@ SlabList list_rows(const Plane &p, size_t r0, size_t r1, int connectivity, uint6
 
 int failures = 0;
 
+bool same_records(const std::vector<gs_component_record> &got, const std::vector<gs_component_record> &want)
+{
+    bool same = got.size() == want.size();
+    for (size_t i = 0; same && i < got.size(); ++i) {
+        const gs_component_record &a = got[i], &b = want[i];
+        same = a.size == b.size && a.sum_row == b.sum_row && a.sum_col == b.sum_col && a.first_row == b.first_row &&
+               a.first_col == b.first_col && a.row_min == b.row_min && a.row_max == b.row_max && a.col_min == b.col_min &&
+               a.col_max == b.col_max;
+    }
+    return same;
+}
+
+// The planes as one batch: every plane listed alone, its first cells' rows counted over the stack, one list after the other.
+void check_batch(const std::vector<Plane> &planes, int connectivity, uint64_t min_size, const std::string &what)
+{
+    const size_t rows = planes[0].rows;
+    std::vector<std::vector<gs_component_record>> want;
+    std::vector<gs_component_record> batch;
+    for (size_t p = 0; p < planes.size(); ++p) {
+        want.push_back(list_rows(planes[p], 0, rows, connectivity, min_size, false).records);
+        for (gs_component_record r : want[p]) {
+            r.first_row += (uint32_t)(p * rows);
+            batch.push_back(r);
+        }
+    }
+    std::vector<uint64_t> before;
+    gsi::batch_records_to_planes(batch.data(), batch.size(), rows, planes.size(), before);
+    bool same = before.size() == planes.size() + 1 && before[0] == 0 && before[planes.size()] == batch.size();
+    for (size_t p = 0; same && p < planes.size(); ++p) {
+        same = before[p + 1] - before[p] == want[p].size() && before[p + 1] <= batch.size();
+        if (same)
+            same = same_records(std::vector<gs_component_record>(batch.begin() + (long)before[p], batch.begin() + (long)before[p + 1]), want[p]);
+    }
+    if (same) return;
+    ++failures;
+    std::fprintf(stderr, "%s: a batch of %zu planes does not come apart into its planes' lists\n", what.c_str(), planes.size());
+}
+
 void check_merge(const Plane &p, const std::vector<size_t> &cuts /* first rows of the slabs, then rows */, int connectivity,
                  uint64_t min_size, const std::vector<gs_component_record> &want, const std::string &what)
 {
     const size_t nslab = cuts.size() - 1;
     std::vector<SlabList> slab;
-    for (size_t s = 0; s < nslab; ++s) slab.push_back(list_rows(p, cuts[s], cuts[s + 1], connectivity, min_size, nslab > 1));
+    for (size_t s = 0; s < nslab; ++s) {
+        slab.push_back(list_rows(p, cuts[s], cuts[s + 1], connectivity, min_size, nslab > 1));
+        gsi::records_to_global_rows(slab[s].records.data(), slab[s].records.size(), cuts[s]);
+    }
     std::vector<const gs_component_record *> part;
     std::vector<size_t> n;
     std::vector<gsi::ListSeamRows> seam;
@@ -95,14 +139,7 @@ void check_merge(const Plane &p, const std::vector<size_t> &cuts /* first rows o
     }
     const std::vector<gs_component_record> got =
         gsi::merge_component_lists(part.data(), n.data(), seam.data(), nslab, p.cols, connectivity, min_size);
-    bool same = got.size() == want.size();
-    for (size_t i = 0; same && i < got.size(); ++i) {
-        const gs_component_record &a = got[i], &b = want[i];
-        same = a.size == b.size && a.sum_row == b.sum_row && a.sum_col == b.sum_col && a.first_row == b.first_row &&
-               a.first_col == b.first_col && a.row_min == b.row_min && a.row_max == b.row_max && a.col_min == b.col_min &&
-               a.col_max == b.col_max;
-    }
-    if (same) return;
+    if (same_records(got, want)) return;
     ++failures;
     std::fprintf(stderr, "%s: %zu records, not the %zu of the whole plane, or other records\n", what.c_str(), got.size(), want.size());
 }
@@ -201,6 +238,17 @@ int main()
         for (const auto &shape : {std::pair<size_t, size_t>{5, 5}, {13, 21}, {30, 17}, {8, 64}})
             planes.push_back({"random " + std::to_string(density), random_plane(shape.first, shape.second, density, seed++)});
     for (const auto &np : planes) check_every_cut(np.second, np.first);
+    // batches of 1..4 planes of one shape: the first, the last, a middle one or every plane with no set cell; one-row planes
+    for (const auto &shape : {std::pair<size_t, size_t>{7, 9}, {1, 17}, {12, 5}})
+        for (size_t count = 1; count <= 4; ++count)
+            for (unsigned empty = 0; empty < (1u << count); ++empty) { // bit p: plane p has no set cell
+                std::vector<Plane> batch;
+                for (size_t p = 0; p < count; ++p)
+                    batch.push_back(random_plane(shape.first, shape.second, (empty >> p) & 1 ? -1.0 : 0.45, seed++));
+                for (int connectivity : {4, 8})
+                    for (const uint64_t min_size : {(uint64_t)1, (uint64_t)3})
+                        check_batch(batch, connectivity, min_size, "batch of " + std::to_string(count) + ", empty planes " + std::to_string(empty));
+            }
     if (failures) {
         std::fprintf(stderr, "%d failures\n", failures);
         return 1;

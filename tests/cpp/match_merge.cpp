@@ -5,6 +5,10 @@
 // -- the components of at least min_size cells and, in a chain, every one that touches the slab's first or last row -- and
 // leaves one raw overlap per piece, named through the piece's first cell, a dropped mark where a partner is not listed.  The
 // index map of the two list merges and the overlap fold of these must equal the match of the whole planes, overlap for overlap.
+// The slabs count rows from their own first row, as the device does; records_to_global_rows makes them global.  A batch of
+// 1..4 pairs of planes stacked as an ensemble's members are -- records, pieces and indices counted over the stack, planes
+// whose before-list or after-list is empty among them -- must come apart into every pair's own match (batch_records_to_planes,
+// fold_batch_overlaps).
 // Exit status 0 and "ok" when everything agrees.  Stand-alone: it links nothing of the library.
 #include "../../grayscott_amd/csrc/gs_match_merge.h"
 #include "../../grayscott_amd/csrc/gs_unionfind.h"
@@ -54,12 +58,12 @@ Labels label_rows(const std::vector<unsigned char> &set, size_t cols, size_t r0,
 }
 
 struct SlabList {
-    std::vector<gs_component_record> records; // rows global; only size and the first cell matter to the merge's order
+    std::vector<gs_component_record> records; // rows local to the slab; only size and the first cell matter to the merge's order
     std::vector<uint32_t> index;              // per cell's ROOT: the record index, or kCompUnset
     std::vector<uint32_t> first_index, last_index;
 };
 
-SlabList list_rows(const Labels &l, size_t cols, size_t r0, size_t rows, uint64_t min_size, bool open)
+SlabList list_rows(const Labels &l, size_t cols, size_t rows, uint64_t min_size, bool open)
 {
     const size_t total = rows * cols;
     std::vector<unsigned char> listed(total, 0);
@@ -70,7 +74,7 @@ SlabList list_rows(const Labels &l, size_t cols, size_t r0, size_t rows, uint64_
     for (size_t i = 0; i < total; ++i)
         if (l.parent[i] == i && (l.size[i] >= min_size || listed[i])) {
             out.index[i] = (uint32_t)out.records.size();
-            const uint32_t r = (uint32_t)(r0 + i / cols), c = (uint32_t)(i % cols);
+            const uint32_t r = (uint32_t)(i / cols), c = (uint32_t)(i % cols);
             out.records.push_back(gs_component_record{l.size[i], 0, 0, r, c, r, r, c, c});
         }
     for (size_t c = 0; c < cols; ++c) {
@@ -86,26 +90,34 @@ struct Match {
     std::vector<gs_component_overlap> overlaps;
 };
 
+// Rows [r0, r1) of the two planes as a slab of its own: both lists and the raw overlaps, as the slab counts rows and records.
+void match_rows(const Plane &b, const Plane &a, size_t r0, size_t r1, int connectivity, uint64_t min_size, bool chain, SlabList &lb,
+                SlabList &la, std::vector<gs_component_overlap> &raw)
+{
+    const size_t cols = b.cols, rows = r1 - r0;
+    std::vector<unsigned char> both(b.set.size());
+    for (size_t i = 0; i < both.size(); ++i) both[i] = b.set[i] && a.set[i];
+    const Labels xb = label_rows(b.set, cols, r0, r1, connectivity), xa = label_rows(a.set, cols, r0, r1, connectivity);
+    const Labels xp = label_rows(both, cols, r0, r1, connectivity);
+    lb = list_rows(xb, cols, rows, min_size, chain);
+    la = list_rows(xa, cols, rows, min_size, chain);
+    for (size_t i = 0; i < rows * cols; ++i) { // what gs_match_pairs_k writes, in first-cell order
+        if (xp.parent[i] != i) continue;
+        const uint32_t ib = lb.index[xb.parent[i]], ia = la.index[xa.parent[i]];
+        const bool listed = ib != gsi::kCompUnset && ia != gsi::kCompUnset;
+        raw.push_back(gs_component_overlap{listed ? ib : gsi::kCompUnset, listed ? ia : gsi::kCompUnset, xp.size[i]});
+    }
+}
+
 Match match_cut(const Plane &b, const Plane &a, const std::vector<size_t> &cuts, int connectivity, uint64_t min_size)
 {
     const size_t nslab = cuts.size() - 1, cols = b.cols;
-    const bool chain = nslab > 1;
-    std::vector<unsigned char> both(b.set.size());
-    for (size_t i = 0; i < both.size(); ++i) both[i] = b.set[i] && a.set[i];
-    std::vector<SlabList> lb, la;
+    std::vector<SlabList> lb(nslab), la(nslab);
     std::vector<std::vector<gs_component_overlap>> raw(nslab);
     for (size_t s = 0; s < nslab; ++s) {
-        const size_t r0 = cuts[s], rows = cuts[s + 1] - r0;
-        const Labels xb = label_rows(b.set, cols, r0, cuts[s + 1], connectivity), xa = label_rows(a.set, cols, r0, cuts[s + 1], connectivity);
-        const Labels xp = label_rows(both, cols, r0, cuts[s + 1], connectivity);
-        lb.push_back(list_rows(xb, cols, r0, rows, min_size, chain));
-        la.push_back(list_rows(xa, cols, r0, rows, min_size, chain));
-        for (size_t i = 0; i < rows * cols; ++i) { // what gs_match_pairs_k writes, in first-cell order
-            if (xp.parent[i] != i) continue;
-            const uint32_t ib = lb[s].index[xb.parent[i]], ia = la[s].index[xa.parent[i]];
-            const bool listed = ib != gsi::kCompUnset && ia != gsi::kCompUnset;
-            raw[s].push_back(gs_component_overlap{listed ? ib : gsi::kCompUnset, listed ? ia : gsi::kCompUnset, xp.size[i]});
-        }
+        match_rows(b, a, cuts[s], cuts[s + 1], connectivity, min_size, nslab > 1, lb[s], la[s], raw[s]);
+        gsi::records_to_global_rows(lb[s].records.data(), lb[s].records.size(), cuts[s]);
+        gsi::records_to_global_rows(la[s].records.data(), la[s].records.size(), cuts[s]);
     }
     Match m;
     std::vector<uint32_t> where[2];
@@ -188,6 +200,55 @@ void check_every_cut(const Plane &b, const Plane &a, const std::string &what)
         }
 }
 
+bool same_overlaps(const gs_component_overlap *x, size_t n, const std::vector<gs_component_overlap> &y)
+{
+    if (n != y.size()) return false;
+    for (size_t i = 0; i < n; ++i)
+        if (x[i].before != y[i].before || x[i].after != y[i].after || x[i].cells != y[i].cells) return false;
+    return true;
+}
+
+// The pairs as one batch: every pair matched alone; its records one list after the other with the first cells' rows counted
+// over the stack, its pieces with the indices of those stacked lists.
+void check_batch(const std::vector<std::pair<Plane, Plane>> &pairs, int connectivity, uint64_t min_size, const std::string &what)
+{
+    const size_t planes = pairs.size(), rows = pairs[0].first.rows;
+    std::vector<Match> want;
+    std::vector<gs_component_record> rec[2];
+    std::vector<gs_component_overlap> raw;
+    for (size_t p = 0; p < planes; ++p) {
+        SlabList l[2];
+        std::vector<gs_component_overlap> pieces;
+        match_rows(pairs[p].first, pairs[p].second, 0, rows, connectivity, min_size, false, l[0], l[1], pieces);
+        want.push_back(match_cut(pairs[p].first, pairs[p].second, {0, rows}, connectivity, min_size));
+        for (gs_component_overlap o : pieces) {
+            if (o.before != gsi::kCompUnset) o.before += (uint32_t)rec[0].size(), o.after += (uint32_t)rec[1].size();
+            raw.push_back(o);
+        }
+        for (int k = 0; k < 2; ++k)
+            for (gs_component_record r : l[k].records) {
+                r.first_row += (uint32_t)(p * rows);
+                rec[k].push_back(r);
+            }
+    }
+    std::vector<uint64_t> before[2];
+    for (int k = 0; k < 2; ++k) gsi::batch_records_to_planes(rec[k].data(), rec[k].size(), rows, planes, before[k]);
+    std::vector<gs_component_overlap> got;
+    std::vector<uint64_t> count(planes, 0);
+    gsi::fold_batch_overlaps(raw.data(), raw.size(), before[0].data(), before[1].data(), planes, got, count.data());
+    size_t at = 0;
+    bool same = true;
+    for (size_t p = 0; same && p < planes; ++p) {
+        same = at + count[p] <= got.size() && same_overlaps(got.data() + at, (size_t)count[p], want[p].overlaps) &&
+               before[0][p + 1] - before[0][p] == want[p].before.size() && before[1][p + 1] - before[1][p] == want[p].after.size();
+        at += (size_t)count[p];
+    }
+    if (same && at == got.size()) return;
+    ++failures;
+    std::fprintf(stderr, "%s, connectivity %d, min_size %llu: a batch of %zu pairs does not come apart into its pairs' matches\n",
+                 what.c_str(), connectivity, (unsigned long long)min_size, planes);
+}
+
 Plane blank(size_t rows, size_t cols) { return Plane{rows, cols, std::vector<unsigned char>(rows * cols, 0)}; }
 
 Plane random_plane(size_t rows, size_t cols, double density, unsigned seed)
@@ -248,6 +309,21 @@ int main()
             check_every_cut(b, a, "random " + std::to_string(density));
             check_every_cut(b, b, "random " + std::to_string(density) + " against itself");
         }
+    // batches of 1..4 pairs of one shape; bit p of `eb` (`ea`): pair p's before-plane (after-plane) has no set cell -- every
+    // choice, so the first, the last and neighbouring planes with an empty before-list or after-list; min_size 7 also empties
+    // lists of planes that have set cells, whose pieces are then all dropped marks
+    for (const auto &shape : {std::pair<size_t, size_t>{6, 9}, {1, 17}})
+        for (size_t count = 1; count <= 4; ++count)
+            for (unsigned eb = 0; eb < (1u << count); ++eb)
+                for (unsigned ea = 0; ea < (1u << count); ++ea) {
+                    std::vector<std::pair<Plane, Plane>> batch;
+                    for (size_t p = 0; p < count; ++p, seed += 2)
+                        batch.push_back({random_plane(shape.first, shape.second, (eb >> p) & 1 ? -1.0 : 0.55, seed),
+                                         random_plane(shape.first, shape.second, (ea >> p) & 1 ? -1.0 : 0.55, seed + 1)});
+                    for (int connectivity : {4, 8})
+                        for (const uint64_t min_size : {(uint64_t)1, (uint64_t)2, (uint64_t)7})
+                            check_batch(batch, connectivity, min_size, "batch, empty before " + std::to_string(eb) + ", after " + std::to_string(ea));
+                }
     if (failures) {
         std::fprintf(stderr, "%d failures\n", failures);
         return 1;

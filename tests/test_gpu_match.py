@@ -240,6 +240,40 @@ def test_ensemble_members_equal_lone_pairs_of_fields(built, members, shape):
     sim.context.close()
 
 
+def test_first_and_last_member_of_a_batch_with_an_empty_list(built):
+    """Three members of (16, 32) in one batch: member 0 has nothing set before, member 2 nothing set afterwards, so the batch's
+    first plane has no before-record and its last no after-record, and the records and pieces of the planes between must
+    still land in their own planes.  Ranges of one such member are batches whose before-list (after-list) is empty as a
+    whole: nothing is listed and no record memory is asked for.  All against the three lone pairs of fields."""
+    members, shape = 3, (16, 32)
+    sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
+    ens = sim.make_ensemble(shape, Parameters(), members=members)
+    before, after = member_planes(members, shape, 40)
+    before[0] = np.float32(0.125)
+    after[2] = np.float32(0.125)
+    ens.upload(None, before)
+    snap = ens.snapshot()
+    ens.upload(None, after)
+    fb, fa = HipConcentration(sim.context, shape), HipConcentration(sim.context, shape)
+    for conn, min_size in ((8, 1), (4, 3)):
+        got = ens.matches_since(snap, threshold=0.5, connectivity=conn, min_size=min_size)
+        assert len(got) == members
+        assert got[0].before.count == 0 and got[0].after.count > 0 and got[0].overlaps.shape == (0,)
+        assert got[2].after.count == 0 and got[2].before.count > 0 and got[2].overlaps.shape == (0,)
+        assert got[1].overlaps.shape[0] > 0
+        for i in range(members):
+            assert_match(got[i], ref.match(before[i], after[i], 0.5, True, conn, min_size), f"member {i}")
+            fb.upload(sim.context, before[i])
+            fa.upload(sim.context, after[i])
+            lone = fa.match(sim.context, fb, 0.5, True, conn, min_size)
+            assert same_match(lone, got[i]), f"member {i} as a pair of fields"
+            one = ens.matches_since(snap, i, 1, threshold=0.5, connectivity=conn, min_size=min_size)
+            assert len(one) == 1 and same_match(one[0], lone), f"member {i} as a batch of its own"
+    snap.destroy()
+    ens.destroy()
+    sim.context.close()
+
+
 def test_more_members_than_one_batch(built):
     """One member more than fit GS_COMPONENTS_BATCH_BYTES of label memory (8 bytes per cell and labelling): the last member is
     a batch of its own, and the offsets of the lists and of the overlaps run through."""
