@@ -22,6 +22,7 @@ from .simulation import (  # noqa: F401
     Morphology,
     Parameters,
     RegionCorrelation,
+    RegionHistogram,
     RegionMorphology,
     RegionSummaries,
     Simulation,
@@ -34,4 +35,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionCorrelation", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionCorrelation", "RegionHistogram", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]

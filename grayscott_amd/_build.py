@@ -61,6 +61,9 @@ UNITS = [
     ("gs_correlation.hip", "gs_correlation_k.o", []),
     # regional two-point pair counts (a region's border is a wall for pairs): the same float mode
     ("gs_region_pairs.hip", "gs_region_pairs_k.o", []),
+    # regional histograms (counts per tile of regions in LDS, flushed to the regions' u64 counters): the same float mode as
+    # gs_histogram.hip, a sub-normal cell is binned as it is
+    ("gs_region_hist.hip", "gs_region_hist_k.o", []),
     # connected components of thresholded planes (union-find over a u32 parent per cell; tile, border, flatten and tally
     # launches): the same float mode
     ("gs_components.hip", "gs_components_k.o", []),

@@ -6,7 +6,7 @@
 // slab layout shows in the result.
 //
 // Reading: as gs_row_summary_k does -- a wave owns a row at a time, its lanes read 16 B each, eight loads ahead of their use.
-// Counting: for each of the wave's loads of 64 cells the slot of the first lane is broadcast (readfirstlane), the lanes that
+// Counting (gs_hist_count.h: slot_of and count, shared with gs_region_hist.hip): for each of the wave's loads of 64 cells the slot of the first lane is broadcast (readfirstlane), the lanes that
 // hold the same slot are counted with one ballot, and only the OTHER lanes add 1 to their slot in LDS.  What the first
 // lane's slot gained goes to a run kept in scalar registers -- (slot, count) -- which is written to LDS when another slot
 // takes over.  On one-valued data (Species::new, and everything off the pattern: U exactly 1, V exactly 0) a wave so issues
@@ -17,6 +17,7 @@
 // Built with hipcc's default float mode (f32 denormals kept) and -ffp-contract=off, as gs_summary.hip is: the rule's
 // subtraction and multiplication are one f32 operation each, and a sub-normal cell or product is the value it is.
 #include "gs_kernels.h"
+#include "gs_hist_count.h"
 #include "gs_plane_scan.h"
 
 namespace {
@@ -35,59 +36,6 @@ struct GsHistArgs {
     int64_t groups;      // workgroups per plane
     unsigned long long *out; // [planes][bins + 3], zeroed by the caller
 };
-
-// The slot of one cell (gs_hip.h): [0, bins) the bins, bins = below, bins + 1 = above, bins + 2 = nan; bins + 3 for a
-// column outside the row.
-__device__ __forceinline__ int slot_of(float x, bool valid, float lo, float hi, float scale, int bins)
-{
-    const bool isnan = x != x, below = x < lo, above = x > hi;
-    const float in = (isnan || below || above) ? lo : x; // (keeps the conversion below defined; the slot is replaced)
-    const float t = (in - lo) * scale;
-    int b = (int)t;
-    b = b < bins - 1 ? b : bins - 1;
-    b = below ? bins : b;
-    b = above ? bins + 1 : b;
-    b = isnan ? bins + 2 : b;
-    return valid ? b : bins + 3;
-}
-
-// The wave's run: `n` cells that belong to slot `slot` and are not in LDS yet.  Both are wave-uniform.
-struct Run {
-    int slot, n;
-};
-
-// GS_HIST_FORM: the forms of `count` that were measured against the one that ships (0) -- 1: every lane adds 1 to its slot
-// in LDS; 2: the run only when all 64 lanes hold one slot, else every lane adds (profiles/histogram.md).
-#ifndef GS_HIST_FORM
-#define GS_HIST_FORM 0
-#endif
-
-// 64 cells, one per lane (every lane active): the lanes whose slot is the first lane's go to the run, the others to LDS.
-__device__ __forceinline__ void count(unsigned *h, Run &run, int s, int lane)
-{
-#if GS_HIST_FORM == 1
-    atomicAdd(&h[s], 1u);
-    (void)run;
-    (void)lane;
-    return;
-#endif
-    const int first = __builtin_amdgcn_readfirstlane(s);
-    const int same = __popcll(__ballot(s == first));
-#if GS_HIST_FORM == 2
-    if (same != 64) {
-        atomicAdd(&h[s], 1u);
-        return;
-    }
-#endif
-    if (s != first) atomicAdd(&h[s], 1u);
-    if (first == run.slot) {
-        run.n += same;
-    } else {
-        if (lane == 0) atomicAdd(&h[run.slot], (unsigned)run.n);
-        run.slot = first;
-        run.n = same;
-    }
-}
 
 // 1-D grid of planes x groups workgroups of 4 waves; dynamic LDS: (bins + 4) u32.
 template <bool VEC>

@@ -324,6 +324,14 @@ hipError_t gs_launch_region_pairs(const float *const *planes, int np, int64_t pi
                                   int32_t rw, const float *thresholds, const int32_t *sense, int32_t nt, int32_t max_lag,
                                   int64_t max_groups, unsigned long long *out, hipStream_t s);
 
+// Regional histograms (gs_region_hist.hip; include/gs_hip.h: gs_fields_region_histogram).  Planes of one slab and regions as
+// for gs_launch_region_quads; lo, hi, scale per plane and bins as for gs_launch_histogram.  The launch adds the cells of region
+// (i, j) of plane p, by the rule of gs_hip.h, to out[((p * rr + i) * rc + j) * (bins + 3) ...]: counts[bins], below, above,
+// nan.  `out` must hold zeros.  max_groups: as for gs_launch_histogram.
+hipError_t gs_launch_region_hist(const float *const *planes, int np, int64_t pitch, int64_t rows, int32_t cols, int32_t rh,
+                                 int32_t rw, const float *lo, const float *hi, const float *scale, int32_t bins,
+                                 int64_t max_groups, unsigned long long *out, hipStream_t s);
+
 // Connected components (gs_components.hip; include/gs_hip.h: gs_fields_components).  `planes` planes of rows x cols cells,
 // `stride` floats apart, rows `pitch` floats apart, thresholded at `threshold` with `sense` as for gs_launch_quads and
 // labelled under `connectivity` (4 or 8); a component never leaves its plane.  parent and size hold one u32 per cell of all

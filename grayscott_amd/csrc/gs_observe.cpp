@@ -39,6 +39,7 @@
 //               (plane, region) -- a region lies inside one slab, so nothing is staged and nothing is folded on the host --
 //               and the slabs' and ranks' region rows meet in the global [plane][region] layout (band_results).  The regions'
 //               two-point pair counts (gs_fields_region_correlation; gs_region_pairs.hip) travel the same way.
+//               The regions' histograms (gs_fields_region_histogram; gs_region_hist.hip) do too: bins + 3 counters per region.
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
@@ -1569,6 +1570,33 @@ int32_t gs_fields_region_correlation(gs_ctx *ctx, gs_field *const *fields, int32
         slab_planes(fields, n, i, planes);
         return gs_launch_region_pairs(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, thresholds, above,
                                       nt, max_lag, max_groups(ctx), reinterpret_cast<unsigned long long *>(dev), s);
+    });
+}
+
+int32_t gs_fields_region_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, const float *lo,
+                                   const float *hi, int32_t bins, uint64_t *out)
+{
+    if (!ctx || !fields || !lo || !hi || !out) return fail(GS_ERR_INVALID, "null argument");
+    uint64_t RR, RC;
+    GS_TRY(region_grid(0, 0, rh, rw, &RR, &RC)); // the region shape alone; no handle is looked at down to check_planes
+    // bins, then the ranges of fields 0 .. n - 1 (a count that is no 1..4 is check_planes' first refusal: no range is read)
+    float scale[4];
+    GS_TRY(check_ranges(lo, hi, n >= 1 && n <= 4 ? n : 0, bins, scale));
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    GS_TRY(region_grid(f0->rows, f0->cols, rh, rw, &RR, &RC));
+    if (RR * RC == 0) return GS_OK; // an empty plane has no regions; the same shape on every rank: nobody exchanges anything
+    const uint64_t per_region = (uint64_t)bins + 3; // (at most 4099: no product here can wrap)
+    if (RR * RC * per_region > (uint64_t)GS_REGION_HIST_MAX)
+        return fail(GS_ERR_INVALID, "%llu x %llu regions of %llu counters each (at most %u counters per field)",
+                    (unsigned long long)RR, (unsigned long long)RC, (unsigned long long)per_region, (unsigned)GS_REGION_HIST_MAX);
+    // the counters land in `out` as they are, as the bit quads' do
+    return band_results(ctx, f0, n, rh, RR, RC, (size_t)per_region * sizeof(uint64_t), true, "region histogram",
+                        reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
+        return gs_launch_region_hist(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, lo, hi, scale, bins,
+                                     max_groups(ctx), reinterpret_cast<unsigned long long *>(dev), s);
     });
 }
 

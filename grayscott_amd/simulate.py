@@ -41,6 +41,10 @@ two images in flight runs dry at every observed image); the default, the last im
 ``--hip-region-corr-lags L`` (1..64; needs ``--hip-regions``) adds the regions' two-point pair counts
 (``gs_fields_region_correlation``, a region's border being a wall for pairs) at the same thresholds: ``pairs_v`` (and ``pairs_u``)
 as [samples, nt, RR, RC, 4, L + 1] and ``corr_lags`` = L -- the wavelength axis of the phase diagram.
+``--hip-region-hist-bins B`` (1..4096; needs ``--hip-regions``) adds the regions' histograms (``gs_fields_region_histogram``):
+``hist_u`` and ``hist_v`` as [samples, RR, RC, B + 3] uint64 -- counts, then below, above, nan -- over
+``--hip-region-hist-range-u A:B`` and ``--hip-region-hist-range-v A:B`` (each 0:1 by default), with ``hist_bins``,
+``hist_range_u`` and ``hist_range_v``: any threshold, the median and the quantiles of every region, chosen after the run.
 
 Time statistics (``gs_time_stats``): ``--hip-time-stats-every N`` samples U and V every N steps -- from step S on with
 ``--hip-time-stats-from S`` (default N; 0: the initial state too), at steps S, S + N, ..., each stamped with its step count -- into per-cell accumulators on
@@ -90,6 +94,11 @@ def parse(argv=None):
         ap.error(f"--hip-region-threshold-u wants as many thresholds as --hip-region-threshold-v ({len(tv)}), not {len(tu)}")
     if args.hip_region_corr_lags is not None and args.hip_regions is None:
         ap.error("--hip-region-corr-lags needs --hip-regions")
+    if args.hip_region_hist_bins is not None and args.hip_regions is None:
+        ap.error("--hip-region-hist-bins needs --hip-regions")
+    for name in ("u", "v"):
+        if getattr(args, f"hip_region_hist_range_{name}") is not None and args.hip_region_hist_bins is None:
+            ap.error(f"--hip-region-hist-range-{name} needs --hip-region-hist-bins")
     return args
 
 
@@ -185,6 +194,26 @@ def _lag_count(text: str) -> int:
     return value
 
 
+def _bin_count(text: str) -> int:
+    try:
+        value = int(text)
+    except ValueError:
+        value = 0
+    if not 1 <= value <= 4096:
+        raise argparse.ArgumentTypeError(f"1 to 4096 bins, not {text!r}")
+    return value
+
+
+def _hist_range(text: str):
+    try:
+        lo, hi = (float(x) for x in text.split(":"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a range A:B, two numbers, not {text!r}") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo < hi):
+        raise argparse.ArgumentTypeError(f"a range A:B with A < B, both finite, not {text!r}")
+    return lo, hi
+
+
 def _positive(text: str) -> int:
     try:
         value = int(text)
@@ -208,6 +237,13 @@ def add_region_args(ap: argparse.ArgumentParser) -> None:
                     help="U is set below these thresholds (as many as V's; default: U's quads are not counted)")
     rg.add_argument("--hip-region-corr-lags", type=_lag_count, default=None, metavar="L",
                     help="also the regions' two-point pair counts at lags 0..L (1..64) at the region thresholds (needs --hip-regions)")
+    rg.add_argument("--hip-region-hist-bins", type=_bin_count, default=None, metavar="B",
+                    help="also the regions' histograms of U and V over B (1..4096) equal bins (needs --hip-regions)")
+    rg.add_argument("--hip-region-hist-range-u", type=_hist_range, default=None, metavar="A:B",
+                    help="the range of U's histograms (default 0:1; needs --hip-region-hist-bins)")
+    rg.add_argument("--hip-region-hist-range-v", type=_hist_range, default=None, metavar="A:B",
+                    help="the range of V's histograms (default 0:1; needs --hip-region-hist-bins); a negative A is written "
+                         "--hip-region-hist-range-v=A:B")
 
 
 def add_time_stats_args(ap: argparse.ArgumentParser, prefix: str = "--hip-time-stats") -> None:
@@ -296,14 +332,24 @@ def regions_observed(image: int, images: int, every) -> bool:
     return image == images if every is None else image % every == 0
 
 
+def region_hist_args(args):
+    """``RegionLog``'s ``hist`` from the ``--hip-region-hist-*`` options: None without ``--hip-region-hist-bins``."""
+    bins = getattr(args, "hip_region_hist_bins", None)
+    if bins is None:
+        return None
+    return bins, getattr(args, "hip_region_hist_range_u", None), getattr(args, "hip_region_hist_range_v", None)
+
+
 class RegionLog:
     """What ``--hip-regions`` collects, one entry per observed image, and the file it becomes."""
 
     SUMMARY_KEYS = ("sum", "sum_sq", "min", "max", "nonfinite")
 
-    def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None):
+    def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None, hist=None):
+        """``hist``: None, or (bins, U's (lo, hi), V's (lo, hi)) -- a range that is None is (0, 1)."""
         self.region = region
         self.corr_lags = corr_lags
+        self.hist = None if hist is None else (int(hist[0]), tuple(hist[1] or (0.0, 1.0)), tuple(hist[2] or (0.0, 1.0)))
         self.thresholds_v = list(thresholds_v) if thresholds_v else [0.25]
         self.thresholds_u = list(thresholds_u) if thresholds_u else None
         if self.thresholds_u is not None and len(self.thresholds_u) != len(self.thresholds_v):
@@ -326,6 +372,11 @@ class RegionLog:
             self.rows.setdefault("pairs_v", []).append(np.stack([c.pairs for c in cv]))
             if cu:
                 self.rows.setdefault("pairs_u", []).append(np.stack([c.pairs for c in cu]))
+        if self.hist is not None:
+            bins, u_range, v_range = self.hist
+            for name, h in zip(("u", "v"), species.region_histogram(self.region, bins, u_range, v_range)):
+                counters = np.concatenate([h.counts, np.stack([h.below, h.above, h.nan], axis=2)], axis=2)  # the C ABI's slots
+                self.rows.setdefault(f"hist_{name}", []).append(counters)
 
     def save(self, path: str, shape, pmap=None) -> None:
         out = {"region": np.array(self.region, np.int64), "shape": np.array(shape, np.int64), "steps": np.array(self.steps, np.int64),
@@ -333,6 +384,10 @@ class RegionLog:
                "thresholds_u": np.array(self.thresholds_u or [], np.float32)}
         if self.corr_lags is not None:
             out["corr_lags"] = np.array(self.corr_lags, np.int64)
+        if self.hist is not None:
+            out["hist_bins"] = np.array(self.hist[0], np.int64)
+            out["hist_range_u"] = np.array(self.hist[1], np.float64)
+            out["hist_range_v"] = np.array(self.hist[2], np.float64)
         for key, rows in self.rows.items():
             out[key] = rows[0] if key == "cells" else np.stack(rows)
         if pmap is not None:
@@ -460,7 +515,7 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     pmap = param_map(args, shape, params)
     region = getattr(args, "hip_regions", None)
     regions = RegionLog(region, getattr(args, "hip_region_threshold_v", None), getattr(args, "hip_region_threshold_u", None),
-                        getattr(args, "hip_region_corr_lags", None)) if region else None
+                        getattr(args, "hip_region_corr_lags", None), region_hist_args(args)) if region else None
     mask = domain_mask(args, shape)
     sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)

@@ -1117,6 +1117,92 @@ def region_correlation_fields(context: "HipContext", fields: Sequence["HipConcen
             for i in range(n)]
 
 
+@dataclass(frozen=True, eq=False)
+class RegionHistogram:
+    """The histograms of every region of one plane, counted on the device (``gs_fields_region_histogram``): ``counts`` of shape
+    ``(RR, RC, bins)``, ``below`` / ``above`` / ``nan`` of shape ``(RR, RC)``, entry (i, j) being bit for bit the ``Histogram``
+    of a plane that holds region (i, j)'s cells alone over ``[lo, hi]``.  ``cells`` is every region's number of cells -- the
+    sum of its counters --, ``region`` is ``(rh, rw)``, ``shape`` the plane's.  ``fraction_above`` and ``quantile`` are
+    ``Histogram``'s, region by region."""
+
+    counts: np.ndarray
+    below: np.ndarray
+    above: np.ndarray
+    nan: np.ndarray
+    lo: float
+    hi: float
+    cells: np.ndarray
+    region: Tuple[int, int]
+    shape: Tuple[int, int]
+
+    @classmethod
+    def from_counters(cls, c, lo: float, hi: float, region, shape) -> "RegionHistogram":
+        """From ``(RR, RC, bins + 3)`` counters as the C ABI writes them: per region counts, below, above, nan."""
+        c = np.asarray(c, np.uint64)
+        region, shape = region_shape(region), (int(shape[0]), int(shape[1]))
+        return cls(c[:, :, :-3].copy(), c[:, :, -3].copy(), c[:, :, -2].copy(), c[:, :, -1].copy(), float(lo), float(hi),
+                   region_sizes(shape[0], shape[1], region, c.shape[:2]), region, shape)
+
+    @property
+    def bins(self) -> int:
+        return self.counts.shape[2]
+
+    @property
+    def in_range(self) -> np.ndarray:
+        """Per region, the cells inside ``[lo, hi]``: the ones ``counts`` holds.  uint64 ``(RR, RC)``."""
+        return self.counts.sum(axis=2, dtype=np.uint64)
+
+    def edges(self) -> np.ndarray:
+        """``Histogram.edges``: the ``bins + 1`` nominal bin edges in f64, the same for every region."""
+        return self.lo + (self.hi - self.lo) * np.arange(self.bins + 1, dtype=np.float64) / self.bins
+
+    def fraction_above(self, x: float) -> np.ndarray:
+        """Per region, ``Histogram.fraction_above(x)``: f64 ``(RR, RC)``, NaN where no cell of the region is in range."""
+        total = self.in_range.astype(np.float64)
+        first = int(np.searchsorted(self.edges()[:-1], x, side="left"))
+        out = np.full(total.shape, np.nan)
+        np.divide(self.counts[:, :, first:].sum(axis=2, dtype=np.uint64).astype(np.float64), total, out=out, where=total > 0)
+        return out
+
+    def quantile(self, q: float) -> np.ndarray:
+        """Per region, ``Histogram.quantile(q)``: f64 ``(RR, RC)``, NaN where no cell of the region is in range."""
+        if not 0.0 <= q <= 1.0:
+            raise ValueError(f"quantile {q} outside [0, 1]")
+        total = self.in_range
+        need = np.maximum(1, np.ceil(q * total.astype(np.float64))).astype(np.uint64)
+        cum = np.cumsum(self.counts, axis=2, dtype=np.uint64)
+        index = (cum < need[:, :, None]).sum(axis=2)  # the first bin at which the cumulative count reaches `need`
+        return np.where(total > 0, self.edges()[np.minimum(index, self.bins - 1) + 1], np.nan)
+
+    def at(self, i: int, j: int) -> Histogram:
+        return Histogram(self.counts[i, j].copy(), int(self.below[i, j]), int(self.above[i, j]), int(self.nan[i, j]), self.lo,
+                         self.hi, int(self.cells[i, j]))
+
+
+def region_histogram_fields(context: "HipContext", fields: Sequence["HipConcentration"], region, bins: int,
+                            ranges: Sequence[Tuple[float, float]]) -> List[RegionHistogram]:
+    """``gs_fields_region_histogram``: the histograms of every region of 1..4 planes of one shape in one call (blocking;
+    collective in a multi-process context), plane i over ``ranges[i]`` with ``bins`` (1..4096) bins.  Returns one
+    ``RegionHistogram`` per plane."""
+    n, bins = len(fields), int(bins)
+    if len(ranges) != n:
+        raise ValueError("one (lo, hi) range per field")
+    rh, rw = region_shape(region)
+    shape = fields[0].shape() if fields else (0, 0)
+    slots = bins + 3 if 1 <= bins <= 4096 else 3
+    try:
+        grid = region_grid(shape[0], shape[1], (rh, rw))
+        if grid[0] * grid[1] * slots > capi.GS_REGION_HIST_MAX:
+            grid = (0, 0)
+    except capi.GsError:
+        grid = (0, 0)  # (the call below refuses it, in the header's order)
+    lo, hi = _f32_pairs(ranges)
+    out = np.zeros((max(n, 1),) + grid + (slots,), np.uint64)
+    capi.check(context._lib.gs_fields_region_histogram(context.handle, _handle_array(fields), n, rh, rw, lo, hi, bins,
+                                                       out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    return [RegionHistogram.from_counters(out[i], lo[i], hi[i], (rh, rw), shape) for i in range(n)]
+
+
 def pinned_empty(shape: Sequence[int]) -> np.ndarray:
     """float32 array in page-locked host memory (``gs_host_alloc``) for overlapped downloads.
     The allocation is released when the last view of it is garbage-collected."""
@@ -1369,6 +1455,13 @@ class HipConcentration:
         at each of ``thresholds`` (1..4, one pass), lags 0 .. ``max_lag``, a region's border being a wall for pairs, counted
         on the device (``gs_fields_region_correlation``; blocking, collective in a multi-process context)."""
         return region_correlation_fields(context, [self], region, [thresholds], [above], max_lag)[0]
+
+    def region_histogram(self, context: HipContext, region, bins: int = 256,
+                         range: Tuple[float, float] = (0.0, 1.0)) -> RegionHistogram:
+        """How the values of every region of ``region`` = (rh, rw) cells (an int: square) of this plane are distributed over
+        ``bins`` equal bins of ``range``, counted on the device (``gs_fields_region_histogram``; blocking, collective in a
+        multi-process context)."""
+        return region_histogram_fields(context, [self], region, bins, [range])[0]
 
     def change_from(self, context: HipContext, other: "HipConcentration") -> Change:
         """How far this plane is from ``other`` (this minus other, cell by cell in f64) over the whole global grid,
@@ -1741,6 +1834,15 @@ class Species:
         def observe(context, fields, thresholds, senses):
             return region_correlation_fields(context, fields, region, thresholds, senses, max_lag)
         return self._v_or_both(observe, u_thresholds, v_thresholds, above)
+
+    def region_histogram(self, region, bins: int = 256, u_range: Tuple[float, float] = (0.0, 1.0),
+                         v_range: Tuple[float, float] = (0.0, 1.0)) -> Tuple[RegionHistogram, RegionHistogram]:
+        """(U, V) histograms of every region of the current state in one call (``gs_fields_region_histogram``; blocking,
+        collective in a multi-process context): the region shape as for ``region_morphology``, ``bins`` equal bins of
+        ``u_range`` for U and of ``v_range`` for V."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = region_histogram_fields(self._context, [in_u, in_v], region, bins, [u_range, v_range])
+        return u, v
 
     def snapshot(self) -> Snapshot:
         """The current state copied into planes of its own on the device (``gs_fields_copy``; blocking)."""

@@ -276,6 +276,8 @@ struct Correlation {
 // of one threshold (gs_fields_region_correlation): `at(i, j)` has region (i, j)'s own rows and cols, a pair across a region
 // border is never formed
 using RegionCorrelation = Regions<Correlation>;
+// (gs_fields_region_histogram): `at(i, j)` is the Histogram of region (i, j)'s cells alone, its `size` the region's own cells
+using RegionHistogram = Regions<Histogram>;
 
 struct Parameters {
     std::array<std::array<Precision, 3>, 3> weights{{{0.25f, 0.5f, 0.25f}, {0.5f, 0.0f, 0.5f}, {0.25f, 0.5f, 0.25f}}};
@@ -771,6 +773,32 @@ class Species {
                 }
                 both[p]->push_back(std::move(c));
             }
+        return uv;
+    }
+    // (U, V) histograms of every region of rh x rw cells of the current state, in one call (gs_fields_region_histogram;
+    // blocking, collective in a multi-process context): `bins` equal bins of u_range for U and of v_range for V
+    std::pair<RegionHistogram, RegionHistogram> region_histogram(int32_t rh, int32_t rw, int32_t bins = 256,
+                                                                 std::array<float, 2> u_range = {0.0f, 1.0f},
+                                                                 std::array<float, 2> v_range = {0.0f, 1.0f})
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const float lo[2] = {u_range[0], v_range[0]}, hi[2] = {u_range[1], v_range[1]};
+        const std::size_t each = bins >= 1 && bins <= 4096 ? (std::size_t)bins + 3 : 3;
+        const Shape s = shape();
+        uint64_t rr = 0, rc = 0;
+        check(gs_region_grid(s[0], s[1], rh, rw, &rr, &rc));
+        // (a result over the cap is refused by the call; nothing that large is allocated for it)
+        const std::size_t regions = rr * rc * each <= (uint64_t)GS_REGION_HIST_MAX ? (std::size_t)(rr * rc) : 0;
+        std::vector<uint64_t> out(2 * regions * each + 1);
+        check(gs_fields_region_histogram(context_->get(), planes, 2, rh, rw, lo, hi, bins, out.data()));
+        std::pair<RegionHistogram, RegionHistogram> uv;
+        RegionHistogram *both[2] = {&uv.first, &uv.second};
+        for (std::size_t p = 0; p < 2; ++p) {
+            *both[p] = RegionHistogram{rr, rc, rh, rw, {}};
+            for (std::size_t r = 0; r < regions; ++r)
+                both[p]->results.push_back(Histogram::from_c(out.data() + (p * regions + r) * each, bins, lo[p], hi[p],
+                                                             detail::region_cells(s[0], s[1], rh, rw, r / rc, r % rc)));
+        }
         return uv;
     }
     // the current state copied into planes of its own on the device (gs_fields_copy; blocking)

@@ -706,6 +706,32 @@ int32_t gs_fields_region_morphology(gs_ctx *ctx, gs_field *const *fields, int32_
 int32_t gs_fields_region_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw,
                                      const float *thresholds, const int32_t *above, int32_t nt, int32_t max_lag, uint64_t *out);
 
+/* Regional histograms: the histogram of gs_fields_histogram (above) of every region of the same region grid -- what
+ * fraction of each part of a parameter map's grid lies above any x chosen after the run, its median and quantiles, and
+ * whether it is bimodal ("half spots, half background") where a summary's mean and variance cannot tell.
+ *   gs_fields_region_histogram  out[((p * RR + i) * RC + j) * (bins + 3) + s] is slot s -- counts[0 .. bins), then below,
+ *                               above, nan -- of region (i, j) of fields[p] and, bit for bit, what gs_fields_histogram
+ *                               returns for a field that holds that region's cells alone, with the range lo[p], hi[p] and
+ *                               the same bins.
+ * The binning rule is the whole-grid histogram's, word for word: scale formed once on the host in f32, the subtraction and
+ * the multiplication one f32 operation each, sub-normal cells and products kept, the last bin closed, -0.0 with lo == 0 in
+ * bin 0.  A region's bins + 3 counters sum to its number of cells, ragged regions in the last row and column of the region
+ * grid included; over all regions every slot sums to the whole-grid histogram's slot, because the regions partition the
+ * cells.  Counts are integers: the result is the same bits for any slab count, process count, step kernel or launch shape
+ * and does not depend on the boundary rule; with a domain mask attached wall cells count.
+ * The call follows its three twins above: one wait for enqueued work, one launch per slab, blocking, no side effects (ghost
+ * rows, tuner, graphs and gs_stats are left as they are), collective in a multi-process context with every rank receiving
+ * every region; an empty plane: GS_OK, nothing is written.  GS_ERR_INVALID, decided in this order: a null argument; rh or
+ * rw refused by gs_region_grid; bins outside 1..4096; the range refusals of gs_fields_histogram (lo or hi not finite,
+ * lo >= hi, hi - lo or scale not a finite, normal, positive f32) for fields 0 .. n - 1 when n is within 1..4 -- all before
+ * any handle is looked at --; a null or foreign handle, mixed shapes, n outside 1..4; RR RC > GS_REGIONS_MAX; RR RC
+ * (bins + 3) > GS_REGION_HIST_MAX counters per field (a cap on result memory: 256 MiB per field).  GS_ERR_UNSUPPORTED, on
+ * every rank alike: some slab begins at a row that is no multiple of rh, as above.
+ * Not done: regions of ensemble members; regions that straddle slabs. */
+#define GS_REGION_HIST_MAX (1u << 25)
+int32_t gs_fields_region_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, const float *lo,
+                                   const float *hi, int32_t bins, uint64_t *out);
+
 /* Two-point correlations computed on the device: the two-point probability function of one plane of the WHOLE global grid
  * after thresholding -- for a lag vector, the number of cell pairs that far apart which are both set; from it the pattern's
  * wavelength and the direction of its stripes follow ("how far apart are the spots?") -- without downloading the plane.  For

@@ -115,6 +115,8 @@ pub struct gs_morphology {
 
 /// `GS_REGIONS_MAX` (include/gs_hip.h): the most regions a region shape may cut a grid into.
 pub const GS_REGIONS_MAX: u64 = 1 << 22;
+/// `GS_REGION_HIST_MAX` (include/gs_hip.h): the most counters per field one regional histogram call returns.
+pub const GS_REGION_HIST_MAX: u64 = 1 << 25;
 
 /// `gs_change` (include/gs_hip.h): how far one plane is from another -- sums of |d| and d * d and the largest |d| over the
 /// cells finite in both (d = a - b in f64), cells whose bits differ, cells not finite in either.  40 bytes.
@@ -259,6 +261,19 @@ extern "C" {
         above: *const i32,
         nt: i32,
         max_lag: i32,
+        out: *mut u64,
+    ) -> i32;
+    /// `lo`, `hi`: n ranges; `out`: n x rr x rc x (bins + 3) counters -- counts, below, above, nan of every region,
+    /// at most `GS_REGION_HIST_MAX` per field.
+    pub fn gs_fields_region_histogram(
+        ctx: *mut gs_ctx,
+        fields: *const *mut gs_field,
+        n: i32,
+        rh: i32,
+        rw: i32,
+        lo: *const f32,
+        hi: *const f32,
+        bins: i32,
         out: *mut u64,
     ) -> i32;
     /// Pair i: `a[i]` against `b[i]`, n = 1..4 pairs of one shape; `out`: n records.
