@@ -67,6 +67,9 @@ UNITS = [
     # connected components of thresholded planes (union-find over a u32 parent per cell; tile, border, flatten and tally
     # launches): the same float mode
     ("gs_components.hip", "gs_components_k.o", []),
+    # regional connected components (the same labelling with the regions' borders as walls, a tally per region): the same
+    # float mode
+    ("gs_region_components.hip", "gs_region_components_k.o", []),
     # component lists: one record per component behind that labelling (count, scan, write, gather launches; integer atomics):
     # the same float mode
     ("gs_component_list.hip", "gs_component_list_k.o", []),

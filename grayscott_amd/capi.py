@@ -28,6 +28,7 @@ GS_BOUNDARY_CLIPPED, GS_BOUNDARY_ZERO_HALO, GS_BOUNDARY_PERIODIC, GS_BOUNDARY_NE
 GS_UNIQUE_ID_BYTES = 128
 GS_REGION_PAIRS_MAX = 1 << 25  # counters per field of one gs_fields_region_correlation call (include/gs_hip.h)
 GS_REGION_HIST_MAX = 1 << 25  # counters per field of one gs_fields_region_histogram call (include/gs_hip.h)
+GS_REGION_COMPONENTS_MAX = 1 << 20  # results per field of one gs_fields_region_components call (include/gs_hip.h)
 # time statistics (include/gs_hip.h): the groups of accumulators, the result planes and the raw accumulators
 GS_TSTAT_SUM, GS_TSTAT_SQUARES, GS_TSTAT_EXTREMES, GS_TSTAT_CROSSINGS = 1, 2, 4, 8
 GS_TSTAT_MEAN, GS_TSTAT_VARIANCE, GS_TSTAT_MIN, GS_TSTAT_MAX, GS_TSTAT_OCCUPANCY, GS_TSTAT_ARRIVAL = 0, 1, 2, 3, 4, 5
@@ -59,7 +60,7 @@ EXPORTS = (
     "gs_members_set_active", "gs_members_get_active",
     "gs_fields_morphology", "gs_members_morphology",
     "gs_region_grid", "gs_fields_region_summaries", "gs_fields_region_morphology", "gs_fields_region_correlation",
-    "gs_fields_region_histogram",
+    "gs_fields_region_histogram", "gs_fields_region_components",
     "gs_fields_correlation", "gs_members_correlation",
     "gs_fields_components", "gs_members_components",
     "gs_field_component_list", "gs_members_component_list", "gs_component_list_view", "gs_component_list_destroy",
@@ -296,6 +297,7 @@ def load() -> ctypes.CDLL:
         "gs_fields_region_correlation": (i32, [vp, P(vp), i32, i32, i32, P(f32), P(i32), i32, i32, P(u64)]),
         "gs_fields_region_histogram": (i32, [vp, P(vp), i32, i32, i32, P(f32), P(f32), i32, P(u64)]),
         "gs_fields_components": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(GsComponents)]),
+        "gs_fields_region_components": (i32, [vp, P(vp), i32, i32, i32, P(f32), P(i32), i32, i32, P(GsComponents)]),
         "gs_members_components": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(GsComponents)]),
         "gs_field_component_list": (i32, [vp, vp, f32, i32, i32, u64, P(vp)]),
         "gs_members_component_list": (i32, [vp, vp, u64, u64, i32, f32, i32, i32, u64, P(vp)]),

@@ -321,6 +321,18 @@ hipError_t gs_launch_component_labels(const float *plane, int64_t planes, int64_
     return e != hipSuccess ? e : hipGetLastError();
 }
 
+// The flatten launch alone, behind a labelling of another lattice of walls (gs_region_components.hip).
+hipError_t gs_launch_component_flatten(uint32_t *parent, uint32_t *size, uint64_t total, hipStream_t s)
+{
+    if (total == 0) return hipSuccess;
+    if (total >= (1ull << 32)) return hipErrorInvalidValue;
+    GsCompArgs a{};
+    a.parent = parent;
+    a.size = size;
+    hipLaunchKernelGGL(gs_comp_flatten_k, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, total);
+    return hipGetLastError();
+}
+
 hipError_t gs_launch_piece_labels(const uint32_t *both_b, const uint32_t *both_a, int64_t planes, int64_t rows, int32_t cols,
                                   int32_t connectivity, uint32_t *parent, uint32_t *size, hipStream_t s)
 {

@@ -350,6 +350,20 @@ hipError_t gs_launch_component_labels(const float *plane, int64_t planes, int64_
                                       float threshold, int32_t sense, int32_t connectivity, uint32_t *parent, uint32_t *size,
                                       hipStream_t s);
 
+// The flatten launch alone: every set entry of parent[0 .. total) gets its root, size[root] its cells (size[] holds zeros).
+hipError_t gs_launch_component_flatten(uint32_t *parent, uint32_t *size, uint64_t total, hipStream_t s);
+
+// Regional connected components (gs_region_components.hip; include/gs_hip.h: gs_fields_region_components).  One plane of one
+// slab -- a field's: rows that begin on 16 bytes, a pitch that is a multiple of 4 --, rows x cols < 2^32 cells, labelled as
+// gs_launch_component_labels labels it but with the borders of the regions of rh x rw cells (rw a multiple of 4) as walls;
+// every component then adds itself to the 35 counters of the region (i, j) it lies in, at out[(i * rc + j) * region_words
+// ...], which must hold zeros (rc = ceil(cols / rw); region_words >= 35: the results of several thresholds lie side by side).
+// parent, size and max_groups: as for gs_launch_components.
+hipError_t gs_launch_region_components(const float *plane, int64_t pitch, int64_t rows, int32_t cols, int32_t rh, int32_t rw,
+                                       float threshold, int32_t sense, int32_t connectivity, int64_t max_groups,
+                                       uint32_t *parent, uint32_t *size, int64_t region_words, unsigned long long *out,
+                                       hipStream_t s);
+
 // Component lists (gs_component_list.hip; include/gs_hip.h: gs_field_component_list), behind gs_launch_component_labels on the
 // same stream.  A record is gs_component_record's layout; first_row counts over all planes (plane * rows + row), the sums and
 // the box are the plane's own rows.  A component is listed if it has at least min_size cells or, with `open` (planes == 1: a

@@ -40,6 +40,9 @@
 //               and the slabs' and ranks' region rows meet in the global [plane][region] layout (band_results).  The regions'
 //               two-point pair counts (gs_fields_region_correlation; gs_region_pairs.hip) travel the same way.
 //               The regions' histograms (gs_fields_region_histogram; gs_region_hist.hip) do too: bins + 3 counters per region.
+//               The regions' components (gs_fields_region_components; gs_region_components.hip) are labelled slab by slab in
+//               label memory that lives for the call alone, the regions' borders as walls, and tallied per region into the
+//               same layout: nt results of 35 counters per region.
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
@@ -172,9 +175,8 @@ int32_t exchange(gs_ctx *ctx, const void *mine, const std::vector<size_t> &bytes
 // k's bands are [start_k / rh, ...) of the grid's, no ghost row is read and no row is staged; every rank reaches the same
 // verdict.  Row records -- summaries, comparisons, which fold `all` plane by plane in ascending global row order -- are bands
 // of one row with one 32-byte result, for which that refusal cannot fire; regions are bands of rh rows with RC results.
-template <typename Launch>
-int32_t band_results(gs_ctx *ctx, const gs_field *f0, int32_t n, int32_t rh, uint64_t RR, uint64_t RC, size_t elem, bool zeroed,
-                     const char *what, unsigned char *all, Launch launch)
+// band_results' refusal: every slab of the global grid begins at a multiple of rh rows, on every rank the same verdict.
+int32_t check_band_seams(const gs_ctx *ctx, const gs_field *f0, int32_t rh)
 {
     const uint64_t q = (uint64_t)rh, S = (uint64_t)ctx->total_slabs(), R = f0->rows;
     for (uint64_t k = 1; k < S; ++k)
@@ -182,6 +184,15 @@ int32_t band_results(gs_ctx *ctx, const gs_field *f0, int32_t n, int32_t rh, uin
             return fail(GS_ERR_UNSUPPORTED, "slab %llu begins at row %llu, which is not a multiple of the region height %d "
                                             "(a region may not straddle two slabs)",
                         (unsigned long long)k, (unsigned long long)(k * R / S), rh);
+    return GS_OK;
+}
+
+template <typename Launch>
+int32_t band_results(gs_ctx *ctx, const gs_field *f0, int32_t n, int32_t rh, uint64_t RR, uint64_t RC, size_t elem, bool zeroed,
+                     const char *what, unsigned char *all, Launch launch)
+{
+    GS_TRY(check_band_seams(ctx, f0, rh));
+    const uint64_t q = (uint64_t)rh, R = f0->rows;
     const size_t nslab = ctx->slabs.size(), line = (size_t)RC * elem; // (line: one band of one plane)
     auto bands_of = [&](uint64_t rows) { return (size_t)((rows + q - 1) / q); };
     size_t local_bands = 0;
@@ -1597,6 +1608,65 @@ int32_t gs_fields_region_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t
         slab_planes(fields, n, i, planes);
         return gs_launch_region_hist(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, lo, hi, scale, bins,
                                      max_groups(ctx), reinterpret_cast<unsigned long long *>(dev), s);
+    });
+}
+
+int32_t gs_fields_region_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw,
+                                    const float *thresholds, const int32_t *above, int32_t nt, int32_t connectivity,
+                                    gs_components *out)
+{
+    if (!ctx || !fields || !thresholds || !above || !out) return fail(GS_ERR_INVALID, "null argument");
+    uint64_t RR, RC;
+    GS_TRY(region_grid(0, 0, rh, rw, &RR, &RC)); // the region shape alone; no handle is looked at down to check_planes
+    GS_TRY(check_thresholds(thresholds, n, nt));
+    GS_TRY(check_connectivity(connectivity));
+    GS_TRY(check_planes(ctx, fields, n));
+    GS_TRY(check_regions(ctx, fields, n, rh, rw));
+    const gs_field *f0 = fields[0];
+    GS_TRY(region_grid(f0->rows, f0->cols, rh, rw, &RR, &RC));
+    if (RR * RC == 0) return GS_OK; // an empty plane has no regions; the same shape on every rank: nobody exchanges anything
+    if (RR * RC * (uint64_t)nt > (uint64_t)GS_REGION_COMPONENTS_MAX) // (at most 2^24: no product here can wrap)
+        return fail(GS_ERR_INVALID, "%llu x %llu regions of %d results each (at most %u results per field)", (unsigned long long)RR,
+                    (unsigned long long)RC, nt, (unsigned)GS_REGION_COMPONENTS_MAX);
+    // every slab of the global grid: every rank reaches the same verdicts
+    GS_TRY(check_band_seams(ctx, f0, rh));
+    const uint64_t S = (uint64_t)ctx->total_slabs();
+    for (uint64_t k = 0; k < S; ++k) {
+        const uint64_t rows = global_slab_rows(ctx, f0->rows, k);
+        if (rows > 0 && rows >= ((uint64_t)1 << 32) / f0->cols + ((((uint64_t)1 << 32) % f0->cols) ? 1 : 0))
+            return fail(GS_ERR_UNSUPPORTED, "slab %llu holds %llu x %llu cells: labels are 32-bit, fewer than 2^32 cells per slab",
+                        (unsigned long long)k, (unsigned long long)rows, (unsigned long long)f0->cols);
+    }
+    const size_t nslab = ctx->slabs.size();
+    LabelMemory labels;
+    int32_t had = GS_OK;
+    for (size_t i = 0; i < nslab && had == GS_OK; ++i)
+        had = labels.add(ctx->slabs[i].device, (uint64_t)f0->s[i].rows * f0->cols);
+    if (ctx->world > 1) { // the ranks agree on the verdict before anything else is exchanged: nobody waits for a rank that left
+        const uint64_t mine = had == GS_OK ? 0 : 1;
+        std::vector<uint64_t> verdicts((size_t)ctx->world);
+        GS_TRY(exchange(ctx, &mine, std::vector<size_t>((size_t)ctx->world, sizeof mine), "region components", verdicts.data()));
+        for (int q = 0; q < ctx->world && had == GS_OK; ++q)
+            if (verdicts[(size_t)q]) had = fail(GS_ERR_NOMEM, "rank %d could not have its label memory", q);
+    }
+    if (had != GS_OK) return had;
+    // the counters land in `out` as they are, as the bit quads' do: a region's nt results of 35 words side by side
+    static_assert(sizeof(gs_components) == kCompWords * sizeof(uint64_t), "gs_components is its counters");
+    const int64_t region_words = (int64_t)nt * (int64_t)kCompWords;
+    return band_results(ctx, f0, n, rh, RR, RC, (size_t)nt * sizeof(gs_components), true, "region components",
+                        reinterpret_cast<unsigned char *>(out), [&](size_t i, unsigned char *dev, hipStream_t s) {
+        // every (plane, threshold) in turn in the slab's label memory: the launches of one are complete before the next begin
+        const size_t line = (size_t)((f0->s[i].rows + (uint64_t)rh - 1) / (uint64_t)rh) * (size_t)RC * (size_t)region_words;
+        for (int32_t p = 0; p < n; ++p)
+            for (int32_t k = 0; k < nt; ++k) {
+                unsigned long long *res = reinterpret_cast<unsigned long long *>(dev) + (size_t)p * line + (size_t)k * kCompWords;
+                const hipError_t e = gs_launch_region_components(fields[p]->s[i].row0, f0->pitch, (int64_t)f0->s[i].rows,
+                                                                 (int32_t)f0->cols, rh, rw, thresholds[p * nt + k], above[p],
+                                                                 connectivity, max_groups(ctx), labels.blocks[i].parent,
+                                                                 labels.blocks[i].size, region_words, res, s);
+                if (e != hipSuccess) return e;
+            }
+        return hipSuccess;
     });
 }
 

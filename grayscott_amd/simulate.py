@@ -45,6 +45,10 @@ as [samples, nt, RR, RC, 4, L + 1] and ``corr_lags`` = L -- the wavelength axis 
 ``hist_u`` and ``hist_v`` as [samples, RR, RC, B + 3] uint64 -- counts, then below, above, nan -- over
 ``--hip-region-hist-range-u A:B`` and ``--hip-region-hist-range-v A:B`` (each 0:1 by default), with ``hist_bins``,
 ``hist_range_u`` and ``hist_range_v``: any threshold, the median and the quantiles of every region, chosen after the run.
+``--hip-region-components [4|8]`` (8 without a value; needs ``--hip-regions``) adds the regions' connected components
+(``gs_fields_region_components``, a region's border being a wall) at the same thresholds: ``components_v`` (and
+``components_u`` with ``--hip-region-threshold-u``) as [samples, nt, RR, RC, 35] uint64 -- components, set_cells, largest,
+by_size[32] -- and ``comp_connectivity``: how many spots every region holds, how large, and whether one percolates it.
 
 Time statistics (``gs_time_stats``): ``--hip-time-stats-every N`` samples U and V every N steps -- from step S on with
 ``--hip-time-stats-from S`` (default N; 0: the initial state too), at steps S, S + N, ..., each stamped with its step count -- into per-cell accumulators on
@@ -96,6 +100,8 @@ def parse(argv=None):
         ap.error("--hip-region-corr-lags needs --hip-regions")
     if args.hip_region_hist_bins is not None and args.hip_regions is None:
         ap.error("--hip-region-hist-bins needs --hip-regions")
+    if args.hip_region_components is not None and args.hip_regions is None:
+        ap.error("--hip-region-components needs --hip-regions")
     for name in ("u", "v"):
         if getattr(args, f"hip_region_hist_range_{name}") is not None and args.hip_region_hist_bins is None:
             ap.error(f"--hip-region-hist-range-{name} needs --hip-region-hist-bins")
@@ -239,6 +245,9 @@ def add_region_args(ap: argparse.ArgumentParser) -> None:
                     help="also the regions' two-point pair counts at lags 0..L (1..64) at the region thresholds (needs --hip-regions)")
     rg.add_argument("--hip-region-hist-bins", type=_bin_count, default=None, metavar="B",
                     help="also the regions' histograms of U and V over B (1..4096) equal bins (needs --hip-regions)")
+    rg.add_argument("--hip-region-components", type=int, choices=(4, 8), nargs="?", const=8, default=None, metavar="4|8",
+                    help="also the regions' connected components of V (and of U with --hip-region-threshold-u) at the region "
+                         "thresholds under connectivity 4 or 8 (8 without a value; needs --hip-regions)")
     rg.add_argument("--hip-region-hist-range-u", type=_hist_range, default=None, metavar="A:B",
                     help="the range of U's histograms (default 0:1; needs --hip-region-hist-bins)")
     rg.add_argument("--hip-region-hist-range-v", type=_hist_range, default=None, metavar="A:B",
@@ -345,9 +354,11 @@ class RegionLog:
 
     SUMMARY_KEYS = ("sum", "sum_sq", "min", "max", "nonfinite")
 
-    def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None, hist=None):
-        """``hist``: None, or (bins, U's (lo, hi), V's (lo, hi)) -- a range that is None is (0, 1)."""
+    def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None, hist=None, components=None):
+        """``hist``: None, or (bins, U's (lo, hi), V's (lo, hi)) -- a range that is None is (0, 1).  ``components``: None, or
+        the connectivity (4 or 8) of the regions' connected components."""
         self.region = region
+        self.components = None if components is None else int(components)
         self.corr_lags = corr_lags
         self.hist = None if hist is None else (int(hist[0]), tuple(hist[1] or (0.0, 1.0)), tuple(hist[2] or (0.0, 1.0)))
         self.thresholds_v = list(thresholds_v) if thresholds_v else [0.25]
@@ -377,6 +388,11 @@ class RegionLog:
             for name, h in zip(("u", "v"), species.region_histogram(self.region, bins, u_range, v_range)):
                 counters = np.concatenate([h.counts, np.stack([h.below, h.above, h.nan], axis=2)], axis=2)  # the C ABI's slots
                 self.rows.setdefault(f"hist_{name}", []).append(counters)
+        if self.components is not None:
+            cu, cv = species.region_components(self.region, self.thresholds_v, self.thresholds_u, connectivity=self.components)
+            self.rows.setdefault("components_v", []).append(np.stack([c.counters() for c in cv]))  # the C ABI's 35 words
+            if cu:
+                self.rows.setdefault("components_u", []).append(np.stack([c.counters() for c in cu]))
 
     def save(self, path: str, shape, pmap=None) -> None:
         out = {"region": np.array(self.region, np.int64), "shape": np.array(shape, np.int64), "steps": np.array(self.steps, np.int64),
@@ -388,6 +404,8 @@ class RegionLog:
             out["hist_bins"] = np.array(self.hist[0], np.int64)
             out["hist_range_u"] = np.array(self.hist[1], np.float64)
             out["hist_range_v"] = np.array(self.hist[2], np.float64)
+        if self.components is not None:
+            out["comp_connectivity"] = np.array(self.components, np.int64)
         for key, rows in self.rows.items():
             out[key] = rows[0] if key == "cells" else np.stack(rows)
         if pmap is not None:
@@ -515,7 +533,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     pmap = param_map(args, shape, params)
     region = getattr(args, "hip_regions", None)
     regions = RegionLog(region, getattr(args, "hip_region_threshold_v", None), getattr(args, "hip_region_threshold_u", None),
-                        getattr(args, "hip_region_corr_lags", None), region_hist_args(args)) if region else None
+                        getattr(args, "hip_region_corr_lags", None), region_hist_args(args),
+                        getattr(args, "hip_region_components", None)) if region else None
     mask = domain_mask(args, shape)
     sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)

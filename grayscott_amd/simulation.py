@@ -724,6 +724,81 @@ def components_fields(context: "HipContext", fields: Sequence["HipConcentration"
             for i in range(n)]
 
 
+@dataclass(frozen=True, eq=False)
+class RegionComponents:
+    """The connected components of every region of one thresholded plane, labelled on the device
+    (``gs_fields_region_components``): ``count``, ``set_cells`` and ``largest`` of shape ``(RR, RC)`` and ``by_size`` of shape
+    ``(RR, RC, 32)``, entry (i, j) being the ``Components`` of a plane that holds region (i, j)'s cells alone -- a region's
+    border is a wall, so a spot that straddles one counts once in every region it touches.  All exact integers."""
+
+    count: np.ndarray
+    set_cells: np.ndarray
+    largest: np.ndarray
+    by_size: np.ndarray
+    threshold: float
+    above: bool
+    connectivity: int
+    region: Tuple[int, int]
+    shape: Tuple[int, int]
+
+    @classmethod
+    def from_counters(cls, words, threshold: float, above: bool, connectivity: int, region, shape) -> "RegionComponents":
+        """From ``(RR, RC, 35)`` u64 words, a ``gs_components`` per region: components, set_cells, largest, by_size[32]."""
+        w = np.array(words, np.uint64)
+        return cls(w[..., 0].copy(), w[..., 1].copy(), w[..., 2].copy(), w[..., 3:].copy(), float(threshold), bool(above),
+                   int(connectivity), region_shape(region), (int(shape[0]), int(shape[1])))
+
+    def counters(self) -> np.ndarray:
+        """The ``(RR, RC, 35)`` u64 words the object was made from."""
+        return np.concatenate([self.count[..., None], self.set_cells[..., None], self.largest[..., None], self.by_size], axis=-1)
+
+    def mean_size(self) -> np.ndarray:
+        """Cells per component of every region; NaN where there is none."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.count > 0, self.set_cells / self.count, np.nan)
+
+    def largest_fraction(self) -> np.ndarray:
+        """The largest component's share of every region's set cells -- near 1 where one component percolates the region --;
+        NaN where none is set."""
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(self.set_cells > 0, self.largest / self.set_cells, np.nan)
+
+    def holes(self, region_morphology: "RegionMorphology") -> np.ndarray:
+        """Holes of every region's pattern: components minus the Euler number of the same connectivity, from a
+        ``RegionMorphology`` of the same plane, region shape, threshold and sense (another is refused)."""
+        m = region_morphology
+        if (np.float32(m.threshold) != np.float32(self.threshold) or bool(m.above) != self.above or m.region != self.region
+                or m.quads.shape[:2] != self.count.shape):
+            raise ValueError("a RegionMorphology of threshold %r (above=%r), regions %r for RegionComponents of threshold %r "
+                             "(above=%r), regions %r" % (m.threshold, m.above, m.region, self.threshold, self.above, self.region))
+        return self.count.astype(np.int64) - (m.euler8 if self.connectivity == 8 else m.euler4)
+
+    def at(self, i: int, j: int) -> Components:
+        return Components(int(self.count[i, j]), int(self.set_cells[i, j]), int(self.largest[i, j]), self.by_size[i, j].copy(),
+                          self.threshold, self.above, self.connectivity)
+
+
+def region_components_fields(context: "HipContext", fields: Sequence["HipConcentration"], region,
+                             thresholds: Sequence[Sequence[float]], above: Sequence[bool],
+                             connectivity: int = 8) -> List[List[RegionComponents]]:
+    """``gs_fields_region_components``: the connected components of every region of 1..4 planes of one shape in one call
+    (blocking; collective in a multi-process context) -- plane i at each of ``thresholds[i]`` (1..4 per plane, the same number
+    for every plane) with the sense ``above[i]`` under ``connectivity`` 4 or 8, a region's border being a wall.  Returns one
+    list of ``RegionComponents`` per plane, one entry per threshold."""
+    n, nt, thr, sense = _field_thresholds(fields, thresholds, above)
+    rh, rw = region_shape(region)
+    shape = fields[0].shape() if fields else (0, 0)
+    try:
+        grid = region_grid(shape[0], shape[1], (rh, rw))
+    except capi.GsError:
+        grid = (0, 0)  # (the call below refuses it, in the header's order)
+    out = np.zeros((max(n, 1),) + grid + (max(nt, 1), 35), np.uint64)
+    capi.check(context._lib.gs_fields_region_components(context.handle, _handle_array(fields), n, rh, rw, thr, sense, nt,
+                                                        int(connectivity), out.ctypes.data_as(ctypes.POINTER(capi.GsComponents))))
+    return [[RegionComponents.from_counters(out[i, :, :, k], thr[i * nt + k], above[i], connectivity, (rh, rw), shape)
+             for k in range(nt)] for i in range(n)]
+
+
 COMPONENT_RECORD_DTYPE = np.dtype([("size", np.uint64), ("sum_row", np.uint64), ("sum_col", np.uint64),
                                    ("first_row", np.uint32), ("first_col", np.uint32), ("row_min", np.uint32),
                                    ("row_max", np.uint32), ("col_min", np.uint32), ("col_max", np.uint32)])  # gs_component_record
@@ -1429,6 +1504,13 @@ class HipConcentration:
         when it is above (``above``) or below the threshold; ``connectivity`` 4 or 8."""
         return components_fields(context, [self], [thresholds], [above], connectivity)[0]
 
+    def region_components(self, context: HipContext, region, thresholds, above: bool = True,
+                          connectivity: int = 8) -> List[RegionComponents]:
+        """The connected components of every region of ``region`` = (rh, rw) cells (an int: square) of this plane thresholded
+        at each of ``thresholds`` (1..4), a region's border being a wall, labelled on the device
+        (``gs_fields_region_components``; blocking, collective in a multi-process context)."""
+        return region_components_fields(context, [self], region, [thresholds], [above], connectivity)[0]
+
     def component_list(self, context: HipContext, threshold: float, above: bool = True, connectivity: int = 8,
                        min_size: int = 1) -> ComponentList:
         """One record per connected component of at least ``min_size`` cells of this plane thresholded at ``threshold`` over
@@ -1799,6 +1881,16 @@ class Species:
         above its thresholds and U below, as ``morphology`` has it; without ``u_thresholds`` only V is looked at and the U
         list is empty."""
         return self._v_or_both(components_fields, u_thresholds, v_thresholds, (False, True), connectivity)
+
+    def region_components(self, region, v_thresholds=(0.25,), u_thresholds=None, v_above: bool = True, u_above: bool = False,
+                          connectivity: int = 8) -> Tuple[List[RegionComponents], List[RegionComponents]]:
+        """(U, V) connected components of every region of the current state in one call (``gs_fields_region_components``;
+        blocking, collective in a multi-process context): one ``RegionComponents`` per threshold, the region shape, thresholds
+        and senses as for ``region_morphology``, ``connectivity`` 4 or 8; without ``u_thresholds`` only V is looked at and the
+        U list is empty."""
+        def observe(context, fields, thresholds, above):
+            return region_components_fields(context, fields, region, thresholds, above, connectivity)
+        return self._v_or_both(observe, u_thresholds, v_thresholds, (u_above, v_above))
 
     def component_list(self, threshold: float = 0.25, species: str = "v", above: bool = True, connectivity: int = 8,
                        min_size: int = 1) -> ComponentList:

@@ -233,6 +233,8 @@ struct Components {
         return (int64_t)count - (connectivity == 8 ? m.euler8() : m.euler4());
     }
 };
+// (gs_fields_region_components): `at(i, j)` is the Components of region (i, j)'s cells alone -- a region's border is a wall
+using RegionComponents = Regions<Components>; // of one threshold
 
 // The two-point pair counts of one thresholded plane, counted on the device (gs_fields_correlation; the rule is gs_hip.h's):
 // pairs[k][d] is the number of cell pairs {p, p + d e_k}, d = 0 .. max_lag, inside the grid with both cells set, for the unit
@@ -693,6 +695,37 @@ class Species {
             uv.first.push_back(Components::from_c(out[k], t[k], false, connectivity));
             uv.second.push_back(Components::from_c(out[nt + k], t[nt + k], true, connectivity));
         }
+        return uv;
+    }
+    // (U, V) connected components of every region of rh x rw cells of the current state, in one call
+    // (gs_fields_region_components; blocking, collective in a multi-process context): one RegionComponents per threshold,
+    // thresholds and senses as for region_morphology(), a region's border being a wall; connectivity 4 or 8
+    std::pair<std::vector<RegionComponents>, std::vector<RegionComponents>> region_components(int32_t rh, int32_t rw,
+                                                                                              const std::vector<float> &v_thresholds,
+                                                                                              const std::vector<float> &u_thresholds,
+                                                                                              bool v_above = true, bool u_above = false,
+                                                                                              int32_t connectivity = 8)
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t nt = v_thresholds.size();
+        const std::vector<float> t = detail::uv_thresholds(u_thresholds, v_thresholds);
+        const int32_t sense[2] = {u_above ? 1 : 0, v_above ? 1 : 0};
+        const Shape s = shape();
+        uint64_t rr = 0, rc = 0;
+        check(gs_region_grid(s[0], s[1], rh, rw, &rr, &rc));
+        const std::size_t regions = (std::size_t)(rr * rc);
+        std::vector<gs_components> out(2 * regions * nt + 1);
+        check(gs_fields_region_components(context_->get(), planes, 2, rh, rw, t.data(), sense, (int32_t)nt, connectivity, out.data()));
+        std::pair<std::vector<RegionComponents>, std::vector<RegionComponents>> uv;
+        std::vector<RegionComponents> *both[2] = {&uv.first, &uv.second};
+        for (std::size_t p = 0; p < 2; ++p)
+            for (std::size_t k = 0; k < nt; ++k) {
+                RegionComponents c{rr, rc, rh, rw, {}};
+                for (std::size_t r = 0; r < regions; ++r)
+                    c.results.push_back(Components::from_c(out[(p * regions + r) * nt + k], t[p * nt + k], p ? v_above : u_above,
+                                                           connectivity));
+                both[p]->push_back(std::move(c));
+            }
         return uv;
     }
     // where the spots are: one record per connected component of at least min_size cells of species (0 = U, 1 = V) of the

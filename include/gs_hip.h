@@ -822,6 +822,39 @@ int32_t gs_fields_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, co
 int32_t gs_members_components(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
                               const int32_t above[2], int32_t nt, int32_t connectivity, gs_components *out);
 
+/* Regional connected components: the result of gs_fields_components of every region of the region grid of the regional
+ * observables above (gs_region_grid) -- how many spots each part of a parameter map's grid holds, how large they are and
+ * whether one component percolates its region (largest / set_cells), which a region's Euler number (components - holes)
+ * cannot say.  A whole-grid call on a mapped grid blends the regions: the spots of neighbouring regions join across borders.
+ *   gs_fields_region_components  out[((p * RR + i) * RC + j) * nt + k] is the result of region (i, j) of fields[p]
+ *                                thresholded at thresholds[p * nt + k] with the sense above[p] and, bit for bit, what
+ *                                gs_fields_components returns for a field that holds that region's cells alone, with the
+ *                                same threshold, sense and connectivity.
+ * A region's border is a WALL: two set cells in different regions are never neighbours, neither across a side nor across a
+ * corner, under every boundary rule; a spot that straddles a border counts once in every region it touches.  So over the
+ * regions set_cells sums to the whole grid's set_cells, the sum of components is at least the whole grid's, and with
+ * rh >= R and rw >= C (one region) the result is gs_fields_components' own.  The set rule is morphology's, word for word (a NaN
+ * cell and a cell equal to the threshold are not set, a sub-normal cell is the value it is); with a domain mask attached
+ * wall cells count.  All counters are integers: the same bits for any slab count, process count, step kernel or launch
+ * shape.
+ * A slab is labelled in place as gs_fields_components labels it, in label memory of 8 bytes per cell of the slab that lives
+ * for the call alone, with the regions' borders as walls; every component adds itself to the counters of its region.  A
+ * region lies inside one slab, so nothing is joined on the host.
+ * The call follows its four twins above: one wait for enqueued work (a window launch that gave up is run again first),
+ * blocking, no side effects (ghost rows, tuner, graphs and gs_stats are left as they are), collective in a multi-process
+ * context with every rank receiving every region; an empty plane: GS_OK, nothing is written.  GS_ERR_INVALID, decided in
+ * this order: a null argument; rh or rw refused by gs_region_grid; nt outside 1..4; a NaN threshold; a connectivity that is
+ * neither 4 nor 8 -- all before any handle is looked at --; a null or foreign handle, mixed shapes, n outside 1..4; RR RC >
+ * GS_REGIONS_MAX; RR RC nt > GS_REGION_COMPONENTS_MAX records per field (a cap on result memory: 280 MiB per field).
+ * GS_ERR_UNSUPPORTED, on every rank alike: some slab begins at a row that is no multiple of rh, as above; a slab of 2^32
+ * cells or more.  GS_ERR_NOMEM: as gs_fields_components returns it; in a multi-process context the ranks agree on it before
+ * anything else travels.
+ * Not done: regions of ensemble members; regions that straddle slabs; regional component lists. */
+#define GS_REGION_COMPONENTS_MAX (1u << 20)
+int32_t gs_fields_region_components(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw,
+                                    const float *thresholds, const int32_t *above, int32_t nt, int32_t connectivity,
+                                    gs_components *out);
+
 /* Component lists computed on the device: WHERE the spots of one plane of the WHOLE global grid are after thresholding -- one
  * record per connected component with its size, the sums of its cells' coordinates (the centroid), its first cell and its
  * bounding box -- without downloading the plane: whether a spot pattern is a lattice (distances between centroids), whether
