@@ -24,30 +24,14 @@ struct Run {
     int slot, n;
 };
 
-// GS_HIST_FORM: the forms of `count` that were measured against the one that ships (0) -- 1: every lane adds 1 to its slot
-// in LDS; 2: the run only when all 64 lanes hold one slot, else every lane adds (profiles/histogram.md).
-#ifndef GS_HIST_FORM
-#define GS_HIST_FORM 0
-#endif
-
 // 64 cells, one per lane (every lane active): the lanes whose slot is the first lane's go to the run, the others to LDS.
 // `s` is the index of the lane's word in `h`, whatever the kernel makes of it: a plane's slot, or region and slot together.
+// (Two other forms were measured and lost, profiles/histogram.md: every lane adds 1 to its slot in LDS; the run only when
+// all 64 lanes hold one slot, else every lane adds.  gs_experiments.h names the last commit that builds them.)
 __device__ __forceinline__ void count(unsigned *h, Run &run, int s, int lane)
 {
-#if GS_HIST_FORM == 1
-    atomicAdd(&h[s], 1u);
-    (void)run;
-    (void)lane;
-    return;
-#endif
     const int first = __builtin_amdgcn_readfirstlane(s);
     const int same = __popcll(__ballot(s == first));
-#if GS_HIST_FORM == 2
-    if (same != 64) {
-        atomicAdd(&h[s], 1u);
-        return;
-    }
-#endif
     if (s != first) atomicAdd(&h[s], 1u);
     if (first == run.slot) {
         run.n += same;

@@ -97,8 +97,10 @@ struct GsAttached {
 // gs_launch_window_*: one persistent launch for a whole gs_run on grids of ONE round of register-resident windows.
 // Every workgroup owns a rectangle of the grid (GsWindowDesc; the rectangles tile the grid) and keeps it plus a k-cell
 // apron in registers: `active` window rows (waves beyond them idle) x 128 columns.  Every k steps it stores the k-cell
-// ring of its owned cells into the exchange planes, raises its flag, waits for the flags of the workgroups whose
-// cells its apron covers (`nbr`) and loads its apron from their rings.  Exchange e uses the planes of parity e & 1.
+// ring of its owned cells into the exchange planes as granules {value, exchange number} and polls the granules of its
+// own apron cells until they carry that number.  Exchange e uses the planes of parity e & 1.  (The kernel reads neither
+// `nbr` nor `n_nbr`: the workgroups whose cells a window's apron covers are the planner's business: its neighbour
+// limit decides which tilings plan_windows accepts.)
 // The input planes are never written: a launch that gives up (abort set) has destroyed nothing.
 // Windows of one tile column share their height, and columns whose cells cost more (the grid's left and right edge
 // under the clipped rule) get lower windows, so that every workgroup's step takes the same time: they all wait for
@@ -113,14 +115,15 @@ struct GsWindowDesc {
 };
 struct GsWindowArgs {
     float *xu[2], *xv[2];      // exchange planes: local row 0, column 0; the field planes' pitch, at least the grid's rows
-    int32_t *flags;            // one per workgroup; a workgroup that has finished exchange e holds epoch + e + 1
+    int32_t *flags;            // two words per workgroup, diagnostics only: a wave that gave up leaves (wave, exchange) and
+                               // its polls there (resolve_window prints them); the exchange itself uses no flag
     int32_t *abort;            // sticky, 0 or the `seq` of the launch in which a poll ran out of patience (workgroups not
                                // co-resident): every workgroup of that launch and of every later one then leaves
     const GsWindowDesc *desc;  // one per workgroup (device memory)
     int32_t n_windows;
     int32_t steps;             // time steps of this launch (>= 1)
     int32_t k;                 // steps per exchange: even, 2 ... 8
-    int32_t epoch;             // flags left by earlier launches are <= epoch
+    int32_t epoch;             // exchange numbers left in the planes by earlier launches are <= epoch
     int32_t patience;          // polls before a workgroup gives up
     int32_t seq;               // this launch's number on its context (>= 1): what a workgroup that gives up leaves in *abort
 };

@@ -51,8 +51,8 @@ struct RowT { // [0] = column c-1, [1..CPL] = own columns, [CPL+1] = column c+CP
 // DPP instruction issues at half the VALU rate and, mixed into ordinary VALU code, costs the wave 3-5
 // issue slots; ds_bpermute_b32 goes through the LDS crossbar (no LDS memory, ~6 cycles per CU and
 // wave-instruction) and takes no VALU slot at all.  At 4 exchanges per row and level the crossbar is
-// ~40 % busy, so the exchange is free: +7 % at 16384^2 over the DPP form (GS_TB_XLANE=0, kept for A/B).
-#if GS_TB_XLANE
+// ~40 % busy, so the exchange is free: it measured +7 % at 16384^2 over the DPP form (wave shifts with bound_ctrl), which
+// round 1 had and which is retired (gs_experiments.h).
 __device__ __forceinline__ int lane_id() { return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); }
 // lane i receives lane i-1's `own` (lane 0: lane 63's)
 __device__ __forceinline__ float shift_from_prev_lane(float own)
@@ -66,17 +66,6 @@ __device__ __forceinline__ float shift_from_next_lane(float own)
     // register for both directions), and the crossbar takes the lane index modulo 64
     return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute((((lane_id() - 1) & 63) << 2) + 8, __builtin_bit_cast(int, own)));
 }
-#else
-// DPP wave shifts with bound_ctrl (0 for the lane without a source), no `old` operand.
-__device__ __forceinline__ float shift_from_prev_lane(float own)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, own), 0x138, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float shift_from_next_lane(float own)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, own), 0x130, 0xf, 0xf, true));
-}
-#endif
 
 template <int CPL>
 __device__ __forceinline__ RowT<CPL> widen_tb(const float (&u)[CPL], const float (&v)[CPL])
@@ -102,7 +91,7 @@ __device__ __forceinline__ void cells_interior(const GsStepArgs &a, const RowT<C
                                                float (&nu)[CPL], float (&nv)[CPL], const float *mf = nullptr,
                                                const float *mfk = nullptr)
 {
-    if constexpr (GS_TB_HSHARE && CPL > 1 && (FAST & 1) && !GS_MATH_FUSED) {
+    if constexpr (CPL > 1 && (FAST & 1) && !GS_MATH_FUSED) {
         float hu = 0.0f, hv = 0.0f; // the previous cell's right-hand tap
 #pragma unroll
         for (int k = 1; k <= CPL; ++k) {
@@ -258,9 +247,11 @@ __device__ __forceinline__ void cells_xshare(const GsStepArgs &a, const RowQ<2> 
 // the unit's first row) + per-lane byte offset (one VGPR for the whole march) + scalar byte offset of
 // the row: no 64-bit per-lane addresses to keep or to recompute per row.  The resource is raw (stride 0)
 // with the widest record count: the units never step outside their planes, so nothing relies on the
-// range check.  With them, the late fetch (GS_TB_LATE_FETCH, gs_experiments.h) and the edge path's column
-// masks kept as lane masks in SGPRs, the whole kernel entry -- general path included -- fits 126
+// range check.  With them, the late fetch (LATE in tb_march) and the edge path's column
+// masks kept as lane masks in SGPRs, the whole kernel entry -- general path included -- fitted 126
 // registers: 4 waves per SIMD instead of 3, +9 % at 16384^2 (profiles/archive/r02_sweeps.md, section 8).
+// (The cache-policy operand is 0 everywhere; sc1 on every access was a timing experiment,
+// profiles/archive/r03_sweeps.md, section 3.)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t plane_rsrc(const float *base)
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(base), 0, 0x7fffffff, 0x00020000);
@@ -269,13 +260,13 @@ template <int CPL>
 __device__ __forceinline__ void load_cols_buf(__amdgpu_buffer_rsrc_t r, int voff, int soff, float (&out)[CPL])
 {
     if constexpr (CPL == 4) {
-        const auto x = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, GS_TB_AUX_LOAD);
+        const auto x = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
         __builtin_memcpy(out, &x, sizeof x);
     } else if constexpr (CPL == 2) {
-        const auto x = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, GS_TB_AUX_LOAD);
+        const auto x = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 0);
         __builtin_memcpy(out, &x, sizeof x);
     } else {
-        const auto x = __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, GS_TB_AUX_LOAD);
+        const auto x = __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0);
         __builtin_memcpy(out, &x, sizeof x);
     }
 }
@@ -285,15 +276,15 @@ __device__ __forceinline__ void store_cols_buf(__amdgpu_buffer_rsrc_t r, int vof
     if constexpr (CPL == 4) {
         decltype(__builtin_amdgcn_raw_buffer_load_b128(r, 0, 0, 0)) x;
         __builtin_memcpy(&x, in, sizeof x);
-        __builtin_amdgcn_raw_buffer_store_b128(x, r, voff, soff, GS_TB_AUX_STORE);
+        __builtin_amdgcn_raw_buffer_store_b128(x, r, voff, soff, 0);
     } else if constexpr (CPL == 2) {
         decltype(__builtin_amdgcn_raw_buffer_load_b64(r, 0, 0, 0)) x;
         __builtin_memcpy(&x, in, sizeof x);
-        __builtin_amdgcn_raw_buffer_store_b64(x, r, voff, soff, GS_TB_AUX_STORE);
+        __builtin_amdgcn_raw_buffer_store_b64(x, r, voff, soff, 0);
     } else {
         decltype(__builtin_amdgcn_raw_buffer_load_b32(r, 0, 0, 0)) x;
         __builtin_memcpy(&x, in, sizeof x);
-        __builtin_amdgcn_raw_buffer_store_b32(x, r, voff, soff, GS_TB_AUX_STORE);
+        __builtin_amdgcn_raw_buffer_store_b32(x, r, voff, soff, 0);
     }
 }
 
@@ -362,7 +353,10 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
     // rows plus, on a slab seam, `ghost` rows of the neighbouring slab.
     const int row_lo = max(ur0 - K, a.top_present ? -a.ghost : 0);
     const int row_hi = min(ur1 + K - 1, a.bottom_present ? a.rows + a.ghost - 1 : a.rows - 1);
-    constexpr bool LATE = GS_TB_LATE_FETCH && K == 4 && CPL == 2;
+    // The K = 4 / 2-columns-per-lane march requests its next level-0 row at the END of a tick (2 rows in flight while the
+    // levels are computed, not 3): that kept the entry at 126 registers.  The other layouts keep the early request, which
+    // was worth 2-6 % where the occupancy did not change.
+    constexpr bool LATE = K == 4 && CPL == 2;
     // resources based at the unit's first input row (row_lo) / first output row (ur0): scalar row offsets
     // stay small and positive whatever the size of the plane
     const __amdgpu_buffer_rsrc_t ru = plane_rsrc(a.in_u + (ptrdiff_t)row_lo * pitch), rv = plane_rsrc(a.in_v + (ptrdiff_t)row_lo * pitch);
@@ -525,9 +519,6 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
         }
         // a new row of level j: its columns go to the board, for the neighbouring lanes
         auto put = [&](int j, int slot, const RowQ<CPL> &r) {
-#if GS_VS_ABLATE_HALO
-            return; // (timing experiment: no halo traffic at all; results are wrong)
-#endif
             if constexpr (XS) {
                 mine2[(j * 2 + slot) * kCrossLanes] = f2{r.u[1], r.v[1]};
             } else {
@@ -545,13 +536,8 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
         auto widened = [&](int j, int slot) {
             const float *b = mine + (j * 2 + slot) * kHaloRow;
             RowT<CPL> w;
-#if GS_VS_ABLATE_HALO
-            w.u[0] = R[j][slot].u[1]; w.v[0] = R[j][slot].v[1]; w.u[3] = R[j][slot].u[0]; w.v[3] = R[j][slot].v[0];
-            (void)b;
-#else
             w.u[0] = b[2 * kHaloArray - 1]; w.v[0] = b[3 * kHaloArray - 1]; // second column of lane - 1
             w.u[3] = b[1];                  w.v[3] = b[kHaloArray + 1];     // first column of lane + 1
-#endif
             w.u[1] = R[j][slot].u[0]; w.u[2] = R[j][slot].u[1]; w.v[1] = R[j][slot].v[0]; w.v[2] = R[j][slot].v[1];
             return w;
         };

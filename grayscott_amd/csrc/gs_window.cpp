@@ -120,7 +120,7 @@ int32_t ensure_window_rt(gs_ctx *ctx, const gs_field *f)
             if (p) GS_HIP(hipFree(p));
             p = nullptr;
         }
-        // granules {value, exchange number}: 8 bytes per cell (GS_WIN_TAGGED); zeroed: no cell may carry a number by chance
+        // granules {value, exchange number}: 8 bytes per cell; zeroed: no cell may carry a number by chance
         const size_t bytes = (size_t)(f->rows + 1) * (size_t)f->pitch * 2 * sizeof(float);
         for (auto &p : w.planes) {
             GS_HIP(hipMalloc(reinterpret_cast<void **>(&p), bytes));

@@ -25,7 +25,7 @@ namespace {
 // (8 bytes, one sc1 store) and polls the granules of its own apron cells with sc1 loads until they carry the number it
 // waits for -- the hand-off MI355X_MICROARCH.md prices as handoff-1to1; no drain, no flag, and no barrier: a wave
 // that has its apron goes on.  (Round 4's form -- ring, drain, barrier, flag, poll of the neighbours' flags, barrier,
-// apron loads -- is -DGS_WIN_TAGGED=0.)  Exchanges alternate between two sets of exchange planes, so a wave that is
+// apron loads -- is retired: gs_experiments.h names the last commit that builds it.)  Exchanges alternate between two sets of exchange planes, so a wave that is
 // one exchange ahead never overwrites what a neighbour still has to read.  The input planes are only read and the
 // output planes only written at the very end.  Every poll of the exchange is bounded: a wave that runs out of
 // patience (its neighbours are not resident: the GPU is shared with another long-running kernel) sets a sticky abort
@@ -44,7 +44,7 @@ constexpr int kWinWaves = 16;
 __host__ __device__ constexpr int win_rows(int rpw) { return kWinWaves * rpw; }
 // 2 buffers x 2 species x 16 waves x (first row, last row) x pitch
 __host__ __device__ constexpr size_t win_rows_floats() { return (size_t)2 * 2 * kWinWaves * 2 * kWinPitch; }
-// ... + one word per wave: the number of the step whose rows the wave has published (GS_WIN_PAIR_SYNC)
+// ... + one word per wave: the number of the step whose rows the wave has published
 __host__ __device__ constexpr size_t win_lds_bytes() { return (win_rows_floats() + kWinWaves) * sizeof(float); }
 
 // The S / SE / SW taps of the cells of row `z` with respect to the row `p` below it, in the slots cells_vshare (gs_march.h)
@@ -77,27 +77,6 @@ __device__ unsigned long long gs_win_trace[1024 * 8 * 8];
         }                                                                                                          \
     } while (0)
 #define GS_WIN_TRACE_AT(SLOT) do { } while (0)
-#elif defined(GS_WIN_TRACE) && GS_WIN_TRACE == 4
-// GS_WIN_TRACE=4 (tools/window_wave_budget.py): every wave adds up, in shader clocks, what it spends waiting for the waves above
-// and below it inside the steps (word 0; word 3: how many of those waits found the rows not there yet), between its last
-// step and its apron (word 1), and in all (word 2).
-#define GS_WIN_BUDGET 1
-#define GS_WIN_BUDGET_ADD(SLOT, V) do { if (lane == 0 && blockIdx.x < 256) atomicAdd(&gs_win_trace[(blockIdx.x * 16 + wave) * 4 + (SLOT)], (unsigned long long)(V)); } while (0)
-#define GS_WIN_STEP_AT(SLOT) do { } while (0)
-#define GS_WIN_TRACE_AT(SLOT) do { } while (0)
-#elif defined(GS_WIN_TRACE) && GS_WIN_TRACE == 3
-// GS_WIN_TRACE=3 (tools/window_wave_timeline.py): EVERY wave of the first 256 workgroups stamps three points of each of its last
-// four super-steps -- begins, steps done (before the ring stores), apron in -- and leaves the number of polls in the fourth word.
-#define GS_WIN_STEP_AT(SLOT) do { } while (0)
-#define GS_WIN_TRACE_AT(SLOT)                                                                                      \
-    do {                                                                                                           \
-        if (lane == 0 && wg < 256 && s >= supers - 4 && ((SLOT) == 0 || (SLOT) == 1 || (SLOT) == 4)) {             \
-            unsigned long long t_;                                                                                 \
-            asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory");                          \
-            gs_win_trace[((wg * 16 + wave) * 4 + ((s - (supers - 4)) & 3)) * 4 + ((SLOT) == 4 ? 2 : (SLOT))] = t_; \
-            if ((SLOT) == 4) gs_win_trace[((wg * 16 + wave) * 4 + ((s - (supers - 4)) & 3)) * 4 + 3] = (unsigned long long)trace_polls; \
-        }                                                                                                          \
-    } while (0)
 #elif defined(GS_WIN_TRACE)
 #define GS_WIN_STEP_AT(SLOT) do { } while (0)
 #define GS_WIN_TRACE_AT(SLOT)                                                                                      \
@@ -130,7 +109,6 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
     // row `which` (0 = first, 1 = last row of a wave's band) of wave w, species sp, buffer buf
     // (element of this lane's FIRST column; its second column is kWinHalf further on)
     auto row_of = [&](int buf, int sp, int w, int which) { return lds + ((((buf * 2 + sp) * kWinWaves + w) * 2 + which) * P) + 1 + lane; };
-#if GS_WIN_PAIR_SYNC
     // Waves wait for their two neighbours only: a wave says which step's rows it has published (one LDS word per wave, written
     // behind the rows: the LDS serves a wave's operations in order) and, where a barrier stood, polls the words of the waves
     // above and below.  Two buffers suffice as with the barrier: a wave overwrites the rows of step s at step s + 2, which it
@@ -145,40 +123,25 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
     };
     auto await = [&](int st) {
         bool waited = false;
-#if defined(GS_WIN_BUDGET)
-        const unsigned long long await_t0 = __builtin_amdgcn_s_memtime();
-#endif
         for (;;) {
             const int fa = said[wave > 0 ? wave - 1 : 0], fb = said[wave < kWinWaves - 1 ? wave + 1 : kWinWaves - 1];
             const int m = __builtin_amdgcn_readfirstlane(fa < fb ? fa : fb);
             if (m > st) {
-#if GS_WIN_PAIR_PRIO == 2
                 // the SIMD issues by priority, then age: left alone, its oldest wave runs a step ahead and its youngest finishes
                 // the super-step alone, at half the issue rate.  A wave that had to wait is ahead and steps back; one whose
-                // neighbours are a step further is behind and goes first.
-                if (waited) __builtin_amdgcn_s_setprio(GS_WIN_PRIO_AHEAD);
-                else if (m > st + 1) __builtin_amdgcn_s_setprio(GS_WIN_PRIO_BEHIND);
-                else __builtin_amdgcn_s_setprio(GS_WIN_PRIO_LEVEL);
-#endif
+                // neighbours are a step further is behind and goes first.  (Measured, profiles/r06_window_kernel.md (e), (f): 572-582 k
+                // against 539-545 k with the SIMD's own arbitration and 531 k with a rotation over a SIMD's four waves; other
+                // levels, 0 / 2 / 3 or two levels only, and a sleep between the polls of the words were slower too.)
+                constexpr int kPrioAhead = 0, kPrioLevel = 1, kPrioBehind = 3;
+                if (waited) __builtin_amdgcn_s_setprio(kPrioAhead);
+                else if (m > st + 1) __builtin_amdgcn_s_setprio(kPrioBehind);
+                else __builtin_amdgcn_s_setprio(kPrioLevel);
                 break;
             }
             waited = true;
-#if GS_WIN_PAIR_POLL_SLEEP > 0
-            __builtin_amdgcn_s_sleep(GS_WIN_PAIR_POLL_SLEEP);
-#endif
         }
-#if defined(GS_WIN_BUDGET)
-        GS_WIN_BUDGET_ADD(0, __builtin_amdgcn_s_memtime() - await_t0);
-        if (waited) GS_WIN_BUDGET_ADD(3, 1);
-#endif
         asm volatile("" ::: "memory");
     };
-#define GS_WIN_STEP_SYNC(ST) await(ST)
-#define GS_WIN_STEP_SAY(ST) announce(ST)
-#else
-#define GS_WIN_STEP_SYNC(ST) __syncthreads()
-#define GS_WIN_STEP_SAY(ST) do { } while (0)
-#endif
     // cells outside the grid are zeros and stay zeros: rows are wave-uniform (scalar tests), columns per lane
     bool col_in[2];
     uint32_t la[2], ra[2];
@@ -246,7 +209,7 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
         put(row_of(buf, 1, wave, 1), v[RPW - 1][0], v[RPW - 1][1]);
     };
     // A step: publish, the rows that need nothing from other waves (the other waves' rows arrive meanwhile), the wait
-    // for the waves above and below (GS_WIN_STEP_SYNC: their LDS words; the workgroup's barrier in the round-5 build), the
+    // for the waves above and below (await: their LDS words; the workgroup's barrier until round 5), the
     // rows above and below from LDS, the band's first and last row.  (Reads first and the publish for the next step
     // right before the barrier -- the LDS latency behind the middle rows -- was measured: the waves of a workgroup
     // drift apart, 418 k against 461 k at 1080 x 1920, profiles/r04_window_kernel.md.)
@@ -263,17 +226,8 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
             grow = __builtin_amdgcn_readfirstlane(grow);
         }
         GS_WIN_STEP_AT(0);
-#if GS_WIN_PAIR_SYNC && GS_WIN_PAIR_PRIO == 1
-        // (every step another of a SIMD's four waves goes first: SIMD = wave % 4)
-        switch (((wave >> 2) + step) & 3) {
-        case 0: __builtin_amdgcn_s_setprio(0); break;
-        case 1: __builtin_amdgcn_s_setprio(1); break;
-        case 2: __builtin_amdgcn_s_setprio(2); break;
-        default: __builtin_amdgcn_s_setprio(3); break;
-        }
-#endif
         publish(buf);
-        GS_WIN_STEP_SAY(step);
+        announce(step);
         auto shared_step = [&]() {
           if constexpr ((FAST & 5) == 5 && !GS_MATH_FUSED) {
             const RowT<2> first = widen(u[0], v[0]), second = widen(u[1], v[1]); // old rows 0 and 1: row 0 waits for the row above
@@ -288,7 +242,7 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
                 cur = next;
             }
             GS_WIN_STEP_AT(1);
-            GS_WIN_STEP_SYNC(step);
+            await(step);
             GS_WIN_STEP_AT(2);
             RowT<2> above, below;
             {
@@ -328,19 +282,15 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
         RowT<2> first = widen(u[0], v[0]);                 // old row 0
         RowT<2> second = widen(u[RPW > 1 ? 1 : 0], v[RPW > 1 ? 1 : 0]); // old row 1: needed again for row 0
         RowT<2> prev = first, cur = second;
-        // GS_WIN_LATE_ROW (gs_experiments.h): the last of the rows that need nothing from other waves is computed BEHIND
-        // the barrier, after the reads of the neighbouring waves' rows have been issued -- all 16 waves of the workgroup
-        // issue those reads at the same moment, and the LDS pipe serves them one after the other
-        constexpr int kLate = (GS_WIN_LATE_ROW && RPW >= 4) ? 1 : 0;
 #pragma unroll
-        for (int r = 1; r < RPW - 1 - kLate; ++r) {
+        for (int r = 1; r < RPW - 1; ++r) {
             const RowT<2> next = widen(u[r + 1], v[r + 1]); // old row r + 1 (not overwritten yet)
             update(r, prev, cur, next);
             prev = cur;
             cur = next;
         }
-        // now (kLate = 0): prev = old row RPW - 2, cur = old row RPW - 1 (RPW >= 3); RPW == 2: prev = old row 0, cur = old row 1
-        GS_WIN_STEP_SYNC(step);
+        // now: prev = old row RPW - 2, cur = old row RPW - 1 (RPW >= 3); RPW == 2: prev = old row 0, cur = old row 1
+        await(step);
         RowT<2> above, below;
         {
             // [0] = second column of lane - 1, [1] [2] = own columns, [3] = first column of lane + 1
@@ -349,12 +299,6 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
             get(row_of(buf, 1, wa, 1), above.v);
             get(row_of(buf, 0, wb, 0), below.u);
             get(row_of(buf, 1, wb, 0), below.v);
-        }
-        if constexpr (kLate) {
-            const RowT<2> next = widen(u[RPW - 1], v[RPW - 1]);
-            update(RPW - 2, prev, cur, next);
-            prev = cur;
-            cur = next;
         }
         if (RPW == 1) {
             update(0, above, first, below);
@@ -365,9 +309,6 @@ __device__ __forceinline__ void window_steps(const GsStepArgs &a, float *lds, in
     }
 }
 
-#undef GS_WIN_STEP_SYNC
-#undef GS_WIN_STEP_SAY
-
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t win_rsrc(const void *p)
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, 0x7fffffff, 0x00020000);
@@ -377,11 +318,11 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t win_rsrc(const void *p)
 // instantiation per kind of window (the kernel branches ONCE: with the branch inside the loop the compiler hoists the
 // loop-invariant values of every kind above it and the register file does not hold them all).
 // GS_WIN_TRACE (diagnostic builds, tools/window_timeline.py): wave 0 of every workgroup stamps the 100 MHz real-time
-// counter at seven points of each of its last 8 super-steps: start, steps done, ring stored and drained, barrier
-// passed, poll matched, barrier passed, apron loaded.
+// counter at seven points of each of its last 8 super-steps: start, steps done, ring stored (slots 2 and 3:
+// nothing lies between them), apron polled in (4), wave goes on (5 and 6, likewise); the tool reads all seven.
 
 template <int RPW, int EDGE, int FAST, int ZH>
-__device__ __forceinline__ void window_run(const GsStepArgs &a, const GsWindowArgs &x, const GsWindowDesc *d, int OH, int OW, float *lds,
+__device__ __forceinline__ void window_run(const GsStepArgs &a, const GsWindowArgs &x, int OH, int OW, float *lds,
                                            int *go, int wg, int gr, int gc, int wave, int lane, float (&u)[RPW][2], float (&v)[RPW][2])
 {
     // OH x OW: the cells this workgroup owns = window rows [K, K + OH) x window columns [K, K + OW)
@@ -389,22 +330,13 @@ __device__ __forceinline__ void window_run(const GsStepArgs &a, const GsWindowAr
     typedef float v2f __attribute__((ext_vector_type(2)));
     const int K = x.k, wc = 2 * lane; // wc: this lane's first window column
     int step = 0;
-#if defined(GS_WIN_BUDGET)
-    const unsigned long long run_t0 = __builtin_amdgcn_s_memtime();
-#endif
     const int supers = (x.steps + K - 1) / K;
     for (int s = 0; s < supers; ++s) {
-        int trace_polls = 0; // (GS_WIN_TRACE == 3)
-        (void)trace_polls;
         GS_WIN_TRACE_AT(0);
         // the short super-step first
         window_steps<RPW, EDGE, FAST, ZH>(a, lds, (s == 0 && x.steps % K) ? x.steps % K : K, step, gr, gc, wave, lane, u, v);
         GS_WIN_TRACE_AT(1);
         if (s == supers - 1) break;
-#if defined(GS_WIN_BUDGET)
-        const unsigned long long xchg_t0 = __builtin_amdgcn_s_memtime();
-#endif
-#if GS_WIN_TAGGED
         // ---- exchange s, data-tagged granules: ring out, then every lane polls the granules of its own apron cells ----
         // A granule is {value, tag}: 8 bytes, naturally aligned, written by ONE sc1 store (a lane's two columns: one 16-byte
         // store of two granules) and read by sc1 loads; the tag is the number of the exchange (epoch + s + 1: unique over
@@ -449,12 +381,12 @@ __device__ __forceinline__ void window_run(const GsStepArgs &a, const GsWindowAr
         bool failed = false;
         {
             int spins = 0;
-#if GS_WIN_FIRST_POLL_SLEEP > 0
             // The neighbours' stores need about half a microsecond to land, and a poll that comes too early costs a whole
             // round trip (1.8 us): every window waits that long before its first poll (496 k -> 508-522 k at 1080 x 1920; 8 ... 28
-            // units tried, 20-24 best; the edge windows polling at once, whose neighbours have stored when they arrive: 497-501 k).
-            if constexpr (EDGE == 0 || !GS_WIN_EDGE_POLLS_AT_ONCE) __builtin_amdgcn_s_sleep(GS_WIN_FIRST_POLL_SLEEP);
-#endif
+            // units tried, 20-24 best; the edge windows polling at once, whose neighbours have stored when they arrive: 497-501 k;
+            // a sleep between polls gained nothing: 648 k, inside the 640-658 k without, profiles/r06_window_kernel.md (f)).
+            constexpr int kFirstPollSleep = 20; // s_sleep units of 64 clocks
+            __builtin_amdgcn_s_sleep(kFirstPollSleep);
             for (;;) {
                 bool ok = true;
 #pragma unroll
@@ -475,25 +407,19 @@ __device__ __forceinline__ void window_run(const GsStepArgs &a, const GsWindowAr
                 // bounded: neighbours that are not resident never store (the GPU is shared with another long-running
                 // kernel); a workgroup of this launch that gave up says so in the abort word
                 if (++spins > x.patience || ((spins & 63) == 0 && __builtin_amdgcn_raw_buffer_load_b32(win_rsrc(x.abort), 0, 0, SC1) != 0)) { failed = true; break; }
-#if GS_WIN_POLL_SLEEP > 0
-                __builtin_amdgcn_s_sleep(GS_WIN_POLL_SLEEP);
-#endif
             }
-            trace_polls = spins + 1;
             if (failed && lane == 0) {
                 __builtin_amdgcn_raw_buffer_store_b32(x.seq, win_rsrc(x.abort), 0, 0, SC1);
                 // (diagnostics, read by resolve_window under GS_HIP_TRACE_TUNER: which wave of which workgroup ran out of patience
                 // at which exchange, after how many polls -- the flag words are not used by this form of the exchange)
                 __builtin_amdgcn_raw_buffer_store_b32((wave << 24) | (s & 0xffffff), win_rsrc(x.flags), wg * 8, 0, SC1);
                 __builtin_amdgcn_raw_buffer_store_b32(spins, win_rsrc(x.flags), wg * 8 + 4, 0, SC1);
-                *go = 0;
+                *go = 0; // (nothing reads the word behind the kernel's first barrier.  Without this store four of the window
+                         // kernels come out with other registers and 6-17 instructions fewer: a change to make with a
+                         // timing of its own, profiles/experiment_switches_refactor.md)
             }
         }
         GS_WIN_TRACE_AT(4);
-#if defined(GS_WIN_BUDGET)
-        GS_WIN_BUDGET_ADD(1, __builtin_amdgcn_s_memtime() - xchg_t0);
-#endif
-#if GS_WIN_PAIR_SYNC && GS_WIN_WAVES_LEAVE_ALONE
         // No barrier: a wave that has its apron goes on (inside the steps it waits for the waves above and below it only).  A
         // wave that gave up says that its rows will never come and ends; the others compute on with what they have -- the
         // launch is void -- until their own next exchange finds the abort word.  The exchange planes stay safe without the
@@ -510,82 +436,9 @@ __device__ __forceinline__ void window_run(const GsStepArgs &a, const GsWindowAr
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_endpgm(); // (the wave ends here: no way out of the loop for the compiler to keep values for)
         }
-#else
-        __syncthreads(); // (the waves agree: all go on or all leave)
-        if (!*go) return;
-#endif
         GS_WIN_TRACE_AT(5);
         GS_WIN_TRACE_AT(6);
-#else
-        // ---- exchange s: ring out, flag, poll, apron in -------------------------------------------------------
-        const __amdgpu_buffer_rsrc_t xu = win_rsrc(x.xu[s & 1]), xv = win_rsrc(x.xv[s & 1]);
-        const bool lane_owned = wc >= K && wc < K + OW && gc < a.cols;
-        const bool lane_ring = wc < 2 * K || wc >= OW;
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-            const int wr = wave * RPW + r; // wave-uniform
-            const bool row_owned = wr >= K && wr < K + OH && gr + r < a.rows;
-            const bool row_ring = wr < 2 * K || wr >= OH;
-            if (row_owned && lane_owned && (row_ring || lane_ring)) {
-                const int off = ((gr + r) * a.pitch + gc) * (int)sizeof(float);
-                const v2f su = {u[r][0], u[r][1]}, sv = {v[r][0], v[r][1]};
-                __builtin_amdgcn_raw_buffer_store_b64(su, xu, off, 0, SC1);
-                __builtin_amdgcn_raw_buffer_store_b64(sv, xv, off, 0, SC1);
-            }
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        GS_WIN_TRACE_AT(2);
-        __syncthreads();
-        GS_WIN_TRACE_AT(3);
-        if (wave == 0) {
-            const int target = x.epoch + s + 1;
-            if (lane == 0) __builtin_amdgcn_raw_buffer_store_b32(target, win_rsrc(x.flags), wg * 4, 0, SC1);
-            // one lane per workgroup whose cells this window's apron covers: one vector load polls them all
-            const bool watch = lane < d->n_nbr;
-            const int theirs = watch ? d->nbr[lane] : 0;
-            int ok = 1, spins = 0;
-            for (;;) {
-                const int seen = watch ? __builtin_amdgcn_raw_buffer_load_b32(win_rsrc(x.flags), theirs * 4, 0, SC1) : target;
-                if (!__builtin_amdgcn_ballot_w64(seen - target < 0)) break;
-                if (++spins > x.patience || __builtin_amdgcn_raw_buffer_load_b32(win_rsrc(x.abort), 0, 0, SC1) != 0) { ok = 0; break; }
-                __builtin_amdgcn_s_sleep(2);
-            }
-            if (lane == 0) {
-                // (the number of THIS launch: the launches before it ran to their end, what the host needs to know --
-                // a launch that finds the word set leaves at once, so only workgroups of one launch ever write it)
-                if (!ok) __builtin_amdgcn_raw_buffer_store_b32(x.seq, win_rsrc(x.abort), 0, 0, SC1);
-                *go = ok;
-            }
-        }
-        GS_WIN_TRACE_AT(4);
-        __syncthreads();
-        if (!*go) return; // (workgroup-uniform)
-        GS_WIN_TRACE_AT(5);
-        const bool lane_in = gc >= 0 && gc < a.cols;
-        const bool lane_apron = (wc < K || wc >= K + OW) && wc < 2 * K + OW && lane_in;
-#pragma unroll
-        for (int r = 0; r < RPW; ++r) {
-            const int wr = wave * RPW + r;
-            const bool row_in = gr + r >= 0 && gr + r < a.rows;
-            const bool row_apron = (wr < K || wr >= K + OH) && wr < 2 * K + OH;
-            if (row_in && ((row_apron && lane_in && wc < 2 * K + OW) || (lane_apron && wr < 2 * K + OH))) {
-                const int off = ((gr + r) * a.pitch + gc) * (int)sizeof(float);
-                const v2f fu = __builtin_amdgcn_raw_buffer_load_b64(xu, off, 0, SC1);
-                const v2f fv = __builtin_amdgcn_raw_buffer_load_b64(xv, off, 0, SC1);
-                const bool in1 = gc + 1 < a.cols;
-                u[r][0] = fu[0]; u[r][1] = in1 ? fu[1] : 0.0f;
-                v[r][0] = fv[0]; v[r][1] = in1 ? fv[1] : 0.0f;
-            }
-        }
-#if defined(GS_WIN_TRACE)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-        GS_WIN_TRACE_AT(6);
-#endif
     }
-#if defined(GS_WIN_BUDGET)
-    GS_WIN_BUDGET_ADD(2, __builtin_amdgcn_s_memtime() - run_t0);
-#endif
     // the cells this workgroup owns, where they lie in the grid (8-byte stores; a second column beyond `cols` lands in
     // the planes' padding columns, which nothing reads)
     if (wc >= K && wc < K + OW && gc < a.cols) {
@@ -622,10 +475,8 @@ __global__ __launch_bounds__(kWinWaves * 64) void GS_SUFFIX(gs_run_window_k)(GsS
     // word for the whole workgroup: waves that read it for themselves could disagree (a workgroup of this launch may
     // give up at any time) and a barrier below would wait for waves that have left.
     if (wave == 0 && lane == 0) go = __builtin_amdgcn_raw_buffer_load_b32(win_rsrc(x.abort), 0, 0, SC1) == 0;
-#if GS_WIN_PAIR_SYNC
     // (a wave beyond the window's rows in use has published its zeros for every step to come)
     if (lane == 0) ((__attribute__((address_space(3))) volatile int *)(lds + win_rows_floats()))[wave] = wave * RPW >= d->active ? 0x7fffffff : 0;
-#endif
     __syncthreads();
     if (!go) return; // (workgroup-uniform)
     // elements 0 and 65 of both arrays of this wave's published rows (window columns -2, -1, 128, 129) are never written by
@@ -637,34 +488,14 @@ __global__ __launch_bounds__(kWinWaves * 64) void GS_SUFFIX(gs_run_window_k)(GsS
             lds[(((b >> 1) * kWinWaves + wave) * 2 + (b & 1)) * kWinPitch + (lane & 1) * kWinHalf + (lane >> 1) * (kWinHalf - 1)] = 0.0f;
     if (wave * RPW >= H) {
         // A wave beyond the window's rows in use publishes zeros once (the last wave in use reads them as its row below)
-        // and (builds with barriers inside the run) then only keeps the workgroup's barrier count.
+        // and ends.
 #pragma unroll
         for (int b = 0; b < 8; ++b)
             { float *p = lds + (((b >> 1) * kWinWaves + wave) * 2 + (b & 1)) * kWinPitch + 1 + lane; p[0] = 0.0f; p[kWinHalf] = 0.0f; }
-#if GS_WIN_PAIR_SYNC
         __syncthreads(); // (the zeros are there before anybody reads them: no barrier inside the steps)
-#endif
-#if GS_WIN_PAIR_SYNC && GS_WIN_TAGGED && GS_WIN_WAVES_LEAVE_ALONE
-        return; // (no barrier left to keep count of)
-#endif
-        const int supers = (x.steps + K - 1) / K;
-        for (int s = 0; s < supers; ++s) {
-#if !GS_WIN_PAIR_SYNC
-            const int n = (s == 0 && x.steps % K) ? x.steps % K : K;
-            for (int i = 0; i < n; ++i) __syncthreads();
-#endif
-            if (s == supers - 1) break;
-#if !GS_WIN_TAGGED
-            __syncthreads();
-#endif
-            __syncthreads();
-            if (!go) return;
-        }
         return;
     }
-#if GS_WIN_PAIR_SYNC
     __syncthreads();
-#endif
     float u[RPW][2], v[RPW][2];
 #pragma unroll
     for (int r = 0; r < RPW; ++r) {
@@ -682,7 +513,7 @@ __global__ __launch_bounds__(kWinWaves * 64) void GS_SUFFIX(gs_run_window_k)(GsS
     const bool left = gc0 <= 0, right = gc0 + 2 * K + OW >= a.cols, ends = gr0 <= 0 || gr0 + H >= a.rows;
     const bool edge = left || right || ends;
     constexpr bool KINDS = (FAST & 1) && !GS_MATH_FUSED;
-#define GS_WIN_RUN(E, Z) window_run<RPW, E, FAST, Z>(a, x, d, OH, OW, lds, &go, wg, gr, gc, wave, lane, u, v)
+#define GS_WIN_RUN(E, Z) window_run<RPW, E, FAST, Z>(a, x, OH, OW, lds, &go, wg, gr, gc, wave, lane, u, v)
     // One branch per workgroup, one instantiation per kind of window (as gs_step_tb_k): the cheap kinds exist for the
     // clipped rule with the default side weights in the strict build; a grid narrower than one window, general
     // weights and the fused build take the general path in their edge windows.

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# Archived: f483d0f is the last commit that builds this tool's library (-DGS_WIN_TRACE=4), and the tool ran from tools/ there.
 """Where the waves of the persistent window kernel spend a launch (diagnostic build):
 
     python tools/ab_build.py winbudget -DGS_WIN_TRACE=4

@@ -1,4 +1,5 @@
 #!/usr/bin/env python3
+# Archived: f483d0f is the last commit that builds this tool's library (-DGS_WIN_TRACE=3), and the tool ran from tools/ there.
 """A super-step of the persistent window kernel, wave by wave (diagnostic build):
 
     python tools/ab_build.py winwavetrace -DGS_WIN_TRACE=3

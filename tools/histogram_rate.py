@@ -10,7 +10,8 @@ ensemble of 512 members of 64 x 128 (gs_members_histogram against gs_members_sum
 
     python tools/histogram_rate.py [--calls 9] [--bins 256] [--grids 16384x16384,4096x4096,1080x1920] [--no-ensemble] [--json FILE] [--md FILE]
 
-GS_HIP_LIBRARY=<a variant built with tools/ab_build.py NAME -DGS_HIST_FORM=n> times another form of the kernel.
+GS_HIP_LIBRARY=<a variant built with tools/ab_build.py> times another build of the kernel (the two forms of count() that
+profiles/histogram.md measured are retired: grayscott_amd/csrc/gs_experiments.h names the last commit that builds them).
 Needs the MI355X: there is no CPU path.
 """
 from __future__ import annotations
