@@ -1,9 +1,6 @@
 """Shared helpers for the parity tests (GPU side goes through the C ABI only)."""
 from __future__ import annotations
 
-import os
-import subprocess
-
 import numpy as np
 
 import oracle
@@ -93,64 +90,4 @@ def assert_bits_equal(got: np.ndarray, ref: np.ndarray, what: str):
             f"got {got[r, c]!r} ref {ref[r, c]!r}; max|d|={float(np.max(np.abs(got - ref)))}")
 
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_shm_transport() -> str:
-    """Compile the librccl test double (tests/cpp/shm_transport.cpp: the same eight nccl* entry points over shared-memory
-    mailboxes; host code only, hipcc for the HIP runtime headers) unless it is up to date; returns its path."""
-    from grayscott_amd import _build
-
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    lib = os.path.join(out_dir, "libshm_transport.so")
-    src = os.path.join(ROOT, "tests", "cpp", "shm_transport.cpp")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < os.path.getmtime(src):
-        subprocess.run([_build.hipcc(), "-O2", "-fPIC", "-shared", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                        src, "-o", lib, "-lrt", "-lpthread"], check=True)
-    return lib
-
-
-def join_ranks(rank, world, port, transport_lib, rows, local_slabs=1, own_device=False):
-    """What every worker of a multi-process test does first: the torchrun environment of rank ``rank`` of ``world``
-    (``transport_lib``, when given, takes librccl's place), the gloo bootstrap that carries the unique id, the ``HipArgs``
-    of a process with ``local_slabs`` slabs -- on device 0, or with ``own_device`` on device ``rank`` where the box has a
-    GPU per rank -- and this rank's rows [r0, r1) of a grid of ``rows`` rows.  Returns ``(args, (r0, r1))``."""
-    os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
-                      MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
-    if transport_lib:
-        os.environ["GS_RCCL_LIBRARY"] = transport_lib
-    from grayscott_amd import dist as gsd
-
-    info = gsd.bootstrap(backend="gloo", device="cpu")     # unique id travels over gloo
-    device = rank if own_device and capi.device_count() >= world else 0
-    args = HipArgs(devices=[device] * local_slabs, rank=info.rank, world=info.world, unique_id=info.unique_id)
-    slabs = world * local_slabs
-    r0 = gsd.slab_range(rows, slabs, rank * local_slabs)[0]
-    r1 = gsd.slab_range(rows, slabs, (rank + 1) * local_slabs - 1)[1]
-    return args, (r0, r1)
-
-
-_handed_out = set()
-
-
-def free_port() -> int:
-    """A port nobody listens on and that this test process has not handed out before: the kernel gives a closed
-    ephemeral port out again at once, and the rendezvous store of the previous test may still hold it (EADDRINUSE in
-    the next test's TCPStore, seen once on the GPU box)."""
-    import random
-    import socket
-
-    rng = random.Random(os.getpid() * 7919 + len(_handed_out))
-    for _ in range(200):
-        port = rng.randrange(20000, 45000)
-        if port in _handed_out:
-            continue
-        with socket.socket() as s:
-            try:
-                s.bind(("127.0.0.1", port))
-            except OSError:
-                continue
-        _handed_out.add(port)
-        return port
-    raise RuntimeError("no free port found")
+from .children import ROOT, build_shm_transport, free_port, join_ranks  # noqa: E402,F401  (tests start processes through tests/children.py)

@@ -7,16 +7,17 @@ from __future__ import annotations
 import ctypes
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, build_program, run_program
+
 HEADER = os.path.join(ROOT, "include", "gs_hip.h")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import codeobj  # noqa: E402
+
 
 SYMBOLS = ("gs_members_set_active", "gs_members_get_active")
 # listed family -> its twin
@@ -176,16 +177,10 @@ def test_sweep_retire_mask():
 
 
 def test_cpp_active_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "active_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "active_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("active_mirror", tmp_path)
     hpp = open(os.path.join(ROOT, "include", "grayscott_hip.hpp")).read()
     for name in ("void set_active(", "std::vector<uint8_t> active()", "std::vector<uint64_t> steps_taken()"):
         assert name in hpp, name
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_active.py)
-        r = subprocess.run([str(exe), "4", "8", "16", "5", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "4", "8", "16", "5", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

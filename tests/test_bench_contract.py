@@ -4,7 +4,7 @@ import glob
 import json
 import os
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT
 
 
 def test_recorded_bench_line_has_the_contract_keys():

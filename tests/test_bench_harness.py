@@ -4,17 +4,16 @@ stall, and the launcher path of `python bench.py --gpus N` (a torchrun CHILD, st
 a GPU; never an exec)."""
 import json
 import os
-import subprocess
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, run_program
 
 
 def _python(code, env=None, timeout=120):
     e = dict(os.environ)
     e.pop("WORLD_SIZE", None)
     e.update(env or {})
-    return subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=e, capture_output=True, text=True, timeout=timeout)
+    return run_program([sys.executable, "-c", code], cwd=ROOT, env=e, limit=timeout)
 
 
 def test_watchdog_ends_a_stage_that_exceeds_its_bound():
@@ -50,8 +49,8 @@ def test_gpus_n_without_torchrun_starts_a_torchrun_child():
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         e.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "0"],
-                       cwd=ROOT, env=e, capture_output=True, text=True, timeout=600)
+    r = run_program([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "0"],
+                    cwd=ROOT, env=e, limit=600)
     assert r.returncode != 0
     assert r.stderr.count("no GPU visible") >= 2, r.stderr[-2000:]
 

@@ -3,12 +3,12 @@ symbol include/gs_hip.h declares, and fails LOUDLY (no CPU fallback) without a G
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, run_program
+
 HEADER = os.path.join(ROOT, "include", "gs_hip.h")
 
 
@@ -36,7 +36,7 @@ def test_library_has_gfx950_code_object_and_no_oracle(built):
     blob = open(capi.LIB_PATH, "rb").read()
     assert b"gfx950" in blob
     assert b"gs_oracle" not in blob and b"gs_par_" not in blob  # the checker is never linked in
-    out = subprocess.run(["nm", "-D", "--defined-only", capi.LIB_PATH], capture_output=True, text=True).stdout
+    out = run_program(["nm", "-D", "--defined-only", capi.LIB_PATH]).stdout
     for n in declared_symbols():
         assert re.search(rf"\b{n}\b", out), n
 

@@ -5,14 +5,12 @@ build."""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import change_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, build_program, run_program
 
 SPECIALS = np.array([np.nan, np.inf, -np.inf, -0.0, 0.0, 1e-45, -1e-45, 1.1754942e-38, -3e-39, 3.4028235e38,
                      -3.4028235e38], np.float32)
@@ -174,13 +172,7 @@ def test_sweep_settled_steps():
 
 
 def test_cpp_change_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "change_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "change_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("change_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_change.py)
-        r = subprocess.run([str(exe), "3", "8", "16", "5", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "3", "8", "16", "5", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

@@ -5,7 +5,6 @@ stand-alone C++ program that checks the seam merge (plain and under sanitizers).
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,8 +12,7 @@ import pytest
 from tests import component_list_ref as ref
 from tests import components_ref
 from tests import morph_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, build_program, run_program
 
 
 def test_hand_counted_planes():
@@ -184,25 +182,13 @@ def test_list_seam_merge_on_the_host(tmp_path, sanitize):
     """tests/cpp/component_list_merge.cpp: planes cut into 1..5 slabs (one-row slabs included), each labelled on the host with
     the shared find / unite, through the merge function against the whole plane's list -- a stand-alone program, also built
     with the address and undefined-behaviour sanitizers."""
-    exe = tmp_path / "component_list_merge"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror"]
-    if sanitize:
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    cmd += [os.path.join(ROOT, "tests", "cpp", "component_list_merge.cpp"), "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    exe = build_program("component_list_merge", tmp_path, library=False, sanitize=sanitize)
+    r = run_program([str(exe)])
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr[-2000:]
 
 
 def test_cpp_component_list_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "component_list_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "component_list_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("component_list_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_component_list.py)
-        r = subprocess.run([str(exe), "3", "8", "16", "5", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "3", "8", "16", "5", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

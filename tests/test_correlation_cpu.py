@@ -6,15 +6,14 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 from tests import corr_ref, morph_ref
+from tests.children import ROOT, build_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gs_hip.h")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import codeobj  # noqa: E402
@@ -235,13 +234,7 @@ def test_pair_kernels_resources(built):
 
 
 def test_cpp_correlation_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "correlation_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "correlation_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("correlation_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_correlation.py)
-        r = subprocess.run([str(exe), "3", "8", "16", "5", "4", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "3", "8", "16", "5", "4", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

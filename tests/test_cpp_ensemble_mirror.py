@@ -4,29 +4,22 @@ CPU: the program compiles with plain g++ against gs_hip.h, links libgs_hip.so an
 GS_ERR_NO_DEVICE) without a GPU.  GPU: a sweep of members with their own feed and kill rates, run in two calls, equals a
 lone Species per member and the oracle, bit for bit."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import build_program, run_program
 
 
 @pytest.fixture(scope="module")
 def exe(built, tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpp") / "ensemble_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "ensemble_mirror.cpp"), "-o", str(out),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    out = build_program("ensemble_mirror", tmp_path_factory.mktemp("cpp"))
     return str(out)
 
 
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="only meaningful without a GPU")
 def test_cpp_ensemble_builds_and_fails_loudly_without_gpu(exe, tmp_path):
-    r = subprocess.run([exe, "4", "8", "16", "3", str(tmp_path / "o.bin")], capture_output=True, text=True)
+    r = run_program([exe, "4", "8", "16", "3", str(tmp_path / "o.bin")])
     assert r.returncode == 14 and "HipError" in r.stderr
 
 
@@ -37,7 +30,7 @@ def test_cpp_ensemble_matches_lone_species_and_oracle(exe, tmp_path, rows, cols)
 
     members, steps = 5, 41
     out = tmp_path / "o.bin"
-    r = subprocess.run([exe, str(members), str(rows), str(cols), str(steps), str(out)], capture_output=True, text=True)
+    r = run_program([exe, str(members), str(rows), str(cols), str(steps), str(out)])
     assert r.returncode == 0, r.stderr
     data = np.fromfile(out, np.float32).reshape(2, members, rows, cols)
     u0, v0 = oracle.init_species(rows, cols)

@@ -3,25 +3,17 @@
 CPU: the program compiles with plain g++ against gs_hip.h and links libgs_hip.so.  GPU: a map with F rising along the
 rows and k along the columns, then the map detached, both bit for bit against the mapped reference (tests/param_map_ref.py)."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from . import param_map_ref as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import build_program, run_program
 
 
 @pytest.fixture(scope="module")
 def exe(built, tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpp") / "param_map_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "param_map_mirror.cpp"), "-o", str(out),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    out = build_program("param_map_mirror", tmp_path_factory.mktemp("cpp"))
     return str(out)
 
 
@@ -36,7 +28,7 @@ def test_cpp_param_map_matches_the_reference(exe, tmp_path, rows, cols):
 
     steps = 37
     out = tmp_path / "o.bin"
-    r = subprocess.run([exe, str(rows), str(cols), str(steps), str(out)], capture_output=True, text=True)
+    r = run_program([exe, str(rows), str(cols), str(steps), str(out)])
     assert r.returncode == 0, r.stderr
     data = np.fromfile(out, np.float32).reshape(2, rows, cols)
     f32 = np.float32

@@ -3,31 +3,25 @@
 CPU: the program compiles with plain g++ against gs_hip.h, links libgs_hip.so and fails loudly without a GPU.  GPU: its
 planes -- a Species' and an ensemble's -- equal the Python binding's bit for bit."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import build_program, run_program
+
 BEFORE, EVERY, SAMPLES = 24, 8, 5
 
 
 @pytest.fixture(scope="module")
 def exe(built, tmp_path_factory):
-    out = tmp_path_factory.mktemp("cpp") / "time_stats_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "time_stats_mirror.cpp"), "-o", str(out),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    out = build_program("time_stats_mirror", tmp_path_factory.mktemp("cpp"))
     return str(out)
 
 
 def test_cpp_time_stats_mirror_builds_and_fails_loudly_without_gpu(exe, tmp_path):
     assert os.access(exe, os.X_OK)
     if not os.path.exists("/dev/kfd"):
-        r = subprocess.run([exe, "8", "16", "2", "2", "2", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([exe, "8", "16", "2", "2", "2", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr
 
 
@@ -37,7 +31,7 @@ def test_cpp_time_stats_match_the_python_binding(exe, tmp_path, rows, cols):
     from grayscott_amd import HipArgs, Parameters, Simulation
 
     out = tmp_path / "o.bin"
-    r = subprocess.run([exe, str(rows), str(cols), str(BEFORE), str(EVERY), str(SAMPLES), str(out)], capture_output=True, text=True)
+    r = run_program([exe, str(rows), str(cols), str(BEFORE), str(EVERY), str(SAMPLES), str(out)])
     assert r.returncode == 0, r.stderr
     data = open(out, "rb").read()
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))

@@ -15,9 +15,8 @@ import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, spawn_ranks
 
 
 def _free_port():
@@ -98,7 +97,7 @@ def test_ghost_row_protocol_over_gloo(tmp_path, world, rows, cols, steps):
 
     oracle.build()
     port = _free_port()
-    mp.spawn(_worker, args=(world, port, rows, cols, steps, str(tmp_path)), nprocs=world, join=True)
+    spawn_ranks(_worker, (world, port, rows, cols, steps, str(tmp_path)), world)
     assert (tmp_path / "ok").exists(), "distributed result differs from the single-domain oracle"
 
 

@@ -11,10 +11,12 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT
+
 HEADER = os.path.join(ROOT, "include", "gs_hip.h")
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import codeobj  # noqa: E402
+
 
 ENSEMBLE_SYMBOLS = {"gs_ensemble_create", "gs_ensemble_destroy", "gs_ensemble_shape", "gs_ensemble_set_params",
                     "gs_ensemble_seed", "gs_ensemble_upload", "gs_ensemble_download", "gs_ensemble_run"}

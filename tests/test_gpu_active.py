@@ -7,7 +7,6 @@ from __future__ import annotations
 import ctypes
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -18,9 +17,9 @@ from grayscott_amd import HipArgs, Parameters, Simulation, capi, hdf5_min
 
 from .helpers import assert_bits_equal, gpu_run, oracle_params, rule_run
 from .test_gpu_ensemble import PARAMS, member_fields
+from tests.children import ROOT, build_program, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RULES = [capi.GS_BOUNDARY_CLIPPED, capi.GS_BOUNDARY_ZERO_HALO, capi.GS_BOUNDARY_PERIODIC, capi.GS_BOUNDARY_NEUMANN]
 SHAPES = [(8, 16),     # resident, one cell per thread
           (13, 21),    # resident, ragged (273 cells: the last wave partly idle); cells % 4 != 0: the mirror's dword path
@@ -296,12 +295,9 @@ def test_refusals():
 
 
 def test_cpp_mirror(tmp_path):
-    exe, out = tmp_path / "active_mirror", tmp_path / "o.bin"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    subprocess.run(["g++", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "active_mirror.cpp"),
-                    "-o", str(exe), "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"], check=True)
+    exe, out = build_program("active_mirror", tmp_path), tmp_path / "o.bin"
     members, rows, cols, steps = 4, 8, 16, 5
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), str(steps), str(out)], capture_output=True, text=True, timeout=120)
+    r = run_program([str(exe), str(members), str(rows), str(cols), str(steps), str(out)])
     assert r.returncode == 0, r.stderr
     raw = open(out, "rb").read()
     cells = members * rows * cols
@@ -320,8 +316,7 @@ SWEEP = ["--feed", "0.02:0.04:2", "--kill", "0.06:0.07:2", "-r", "40", "-c", "64
 
 
 def run_sweep(out, extra):
-    r = subprocess.run([sys.executable, "-m", "grayscott_amd.sweep"] + SWEEP + extra + ["-o", str(out)], cwd=ROOT,
-                       capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-m", "grayscott_amd.sweep"] + SWEEP + extra + ["-o", str(out)], cwd=ROOT, limit=300)
     assert r.returncode == 0, r.stderr
 
 

@@ -29,8 +29,9 @@ import sys
 import numpy as np
 import pytest
 
+from tests.children import ROOT, build_shm_transport, free_port, spawn_ranks
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 CHUNK = 2048        # rows per block of generated data / per checksum
 STEPS_A, STEPS_B, SINGLE = 19, 8, 2   # 19 = a 3-step pass + 4 full passes; 8 = 2 full passes; 2 single steps
@@ -293,12 +294,6 @@ def test_two_slab_chain_2000_steps_of_a_developing_pattern(built):
 
 # ---- N processes over the transport double -------------------------------------------------------------
 
-def _free_port():
-    from tests.helpers import free_port
-
-    return free_port()
-
-
 def _worker(rank, world, port, rows, cols, local_slabs, out_dir, transport_lib):
     sys.path.insert(0, ROOT)
     os.environ.update(RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank), MASTER_ADDR="127.0.0.1",
@@ -378,23 +373,5 @@ def _worker(rank, world, port, rows, cols, local_slabs, out_dir, transport_lib):
     (4, 2, 65536, 32768),        # config 5: 8 slabs as 4 processes x 2 (the pool admits 6 GPU processes)
 ])
 def test_process_chain_full_size_vs_single_slab(tmp_path, built, world, local_slabs, rows, cols):
-    import torch.multiprocessing as mp
-
-    lib = _build_transport()
-    mp.spawn(_worker, args=(world, _free_port(), rows, cols, local_slabs, str(tmp_path), lib), nprocs=world, join=True)
+    spawn_ranks(_worker, (world, free_port(), rows, cols, local_slabs, str(tmp_path), build_shm_transport()), world, limit=900)
     assert open(tmp_path / "result.txt").read() == "ok"
-
-
-def _build_transport():
-    import subprocess
-
-    from grayscott_amd import _build
-
-    out_dir = os.path.join(ROOT, "tests", "_build")
-    os.makedirs(out_dir, exist_ok=True)
-    lib = os.path.join(out_dir, "libshm_transport.so")
-    src = os.path.join(ROOT, "tests", "cpp", "shm_transport.cpp")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < os.path.getmtime(src):
-        subprocess.run([_build.hipcc(), "-O2", "-fPIC", "-shared", "-std=c++17", "-x", "hip", "--offload-arch=gfx950",
-                        src, "-o", lib, "-lrt", "-lpthread"], check=True)
-    return lib

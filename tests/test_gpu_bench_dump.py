@@ -4,22 +4,21 @@ an independent replay with the single-step kernel (itself pinned to the CPU orac
 stands in for the oracle because bench.py's untimed warm-up alone is ~6e10 cell-steps on any grid below 2^24 cells."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from tests.children import ROOT, run_program
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(args, timeout=600):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GS_RCCL_LIBRARY"):
         e.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=e,
-                       capture_output=True, text=True, timeout=timeout)
+    r = run_program([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=e, limit=timeout)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
 

@@ -3,14 +3,14 @@
 steps and their inputs do not depend on --full)."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+from tests.children import ROOT, run_program
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 FULL_ONLY = ("verified", "single_step", "developed_pattern", "value_developed_pattern", "cpu_baseline",
              "energy_pJ_per_cell_step", "ranks", "peer_chain")
@@ -20,8 +20,7 @@ def _bench(args, timeout=600):
     e = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GS_RCCL_LIBRARY"):
         e.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=e,
-                       capture_output=True, text=True, timeout=timeout)
+    r = run_program([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=e, limit=timeout)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
 

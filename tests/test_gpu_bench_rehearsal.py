@@ -12,13 +12,13 @@ Multi-GPU spec: SURVEY.md section 8(e); precedent for overlapping sub-grids: com
 """
 import json
 import os
-import subprocess
 import sys
 
 import pytest
 
+from tests.children import ROOT, run_program
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(args, env=None, timeout=900):
@@ -26,8 +26,7 @@ def _bench(args, env=None, timeout=900):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "GS_RCCL_LIBRARY"):
         e.pop(k, None)
     e.update(env or {})
-    return subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=e,
-                          capture_output=True, text=True, timeout=timeout)
+    return run_program([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=e, limit=timeout)
 
 
 def test_gpus_2_rehearsal_without_torchrun_prints_a_verified_line(built):

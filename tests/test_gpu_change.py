@@ -2,8 +2,6 @@
 (tests/change_ref.py), bit for bit -- sums and the maximum as f64 bit patterns, equal counts --, and the device copies
 behind snapshots and restores (gs_fields_copy, gs_members_copy)."""
 import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,10 +9,10 @@ import pytest
 from grayscott_amd import HipArgs, HipConcentration, Parameters, Simulation, capi
 from grayscott_amd.simulation import CHANGE_DTYPE, compare_fields, copy_fields
 from tests import change_ref
+from tests.children import build_program, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 RULES = {"clipped": capi.GS_BOUNDARY_CLIPPED, "zero_halo": capi.GS_BOUNDARY_ZERO_HALO,
          "periodic": capi.GS_BOUNDARY_PERIODIC, "neumann": capi.GS_BOUNDARY_NEUMANN}
@@ -397,16 +395,10 @@ def test_sweep_steady_state(built, tmp_path):
 
 
 def test_cpp_mirror_changes(built, tmp_path):
-    exe = tmp_path / "change_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "change_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("change_mirror", tmp_path)
     members, rows, cols = 4, 72, 200
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "31", str(out)], capture_output=True, text=True)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "31", str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     n = 40 * (2 + 2 * members)

@@ -3,22 +3,14 @@ the global grid, bit for bit the single-process one; gs_fields_copy copies every
 followed by steps gives the single-process planes.  All ranks share device 0 through the shared-memory transport double
 (tests/cpp/shm_transport.cpp, built as tests/test_gpu_multiprocess.py builds it); the rows do not divide evenly."""
 import os
-import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+
+from tests.children import rank_session, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BEFORE, BETWEEN, AFTER = 6, 13, 8      # steps before the snapshot, between snapshot and comparison, after the restore
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
 
 
 def _scenario(sim, species, rec):
@@ -37,23 +29,15 @@ def _scenario(sim, species, rec):
 
 
 def _worker(rank, world, port, rows, cols, out_dir, transport_lib, local_slabs):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
-
-    from grayscott_amd import Parameters, Simulation
     from grayscott_amd.simulation import CHANGE_DTYPE
-    from tests.helpers import join_ranks, species_from_arrays, stress_fields
+    from tests.helpers import species_from_arrays, stress_fields
 
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, local_slabs)
-    sim = Simulation.new(Parameters(), args)
-    u0, v0 = stress_fields((rows, cols), 4)
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
-    rec = np.zeros(3, CHANGE_DTYPE)
-    u, v = _scenario(sim, species, rec)
-    np.savez(os.path.join(out_dir, f"rank{rank}.npz"), rec=rec, u=u, v=v, rows=np.array([r0, r1]))
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
+    with rank_session(rank, world, port, transport_lib, rows, local_slabs) as (sim, (r0, r1)):
+        u0, v0 = stress_fields((rows, cols), 4)
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
+        rec = np.zeros(3, CHANGE_DTYPE)
+        u, v = _scenario(sim, species, rec)
+        np.savez(os.path.join(out_dir, f"rank{rank}.npz"), rec=rec, u=u, v=v, rows=np.array([r0, r1]))
 
 
 @pytest.mark.parametrize("world,local_slabs", [(2, 1), (2, 2), (3, 1)])
@@ -64,8 +48,7 @@ def test_every_rank_gets_the_single_process_change(tmp_path, built, shm_transpor
     from tests.helpers import free_port, species_from_arrays, stress_fields
 
     rows, cols = 203, 333
-    mp.spawn(_worker, args=(world, free_port(), rows, cols, str(tmp_path), shm_transport, local_slabs),
-             nprocs=world, join=True)
+    spawn_ranks(_worker, (world, free_port(), rows, cols, str(tmp_path), shm_transport, local_slabs), world)
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
     u0, v0 = stress_fields((rows, cols), 4)
     species = species_from_arrays(sim, u0, v0)

@@ -2,7 +2,6 @@
 rule (tests/component_list_ref.py) on the same plane: every record equal, in the same order, everywhere."""
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,11 +10,11 @@ from grayscott_amd import ComponentList, HipArgs, HipConcentration, Parameters, 
 from tests import component_list_ref as ref
 from tests import components_ref
 from tests import morph_ref
+from tests.children import ROOT, build_program, run_program
 from tests.helpers import species_from_arrays, stress_fields
 from tests.observe_cases import seam_rows
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 T = components_ref.TILE_ROWS  # the labelling's tile height (kCompTileRows)
 
@@ -408,16 +407,10 @@ def test_sweep_records_spots_without_changing_the_fields(built, tmp_path):
 
 
 def test_cpp_mirror_component_lists(built, tmp_path):
-    exe = tmp_path / "component_list_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "component_list_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("component_list_mirror", tmp_path)
     members, rows, cols = 4, 72, 200
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "31", str(out)], capture_output=True, text=True)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "31", str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     lists, at = [], 0

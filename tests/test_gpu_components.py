@@ -1,8 +1,5 @@
 """Connected components on the device (gs_fields_components, gs_members_components) against the union-find restatement of
 their rule (tests/components_ref.py) on the same plane: every counter equal, everywhere."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -10,11 +7,11 @@ from grayscott_amd import Components, HipArgs, HipConcentration, Parameters, Sim
 from grayscott_amd.simulation import components_fields
 from tests import components_ref as ref
 from tests import morph_ref
+from tests.children import build_program, run_program
 from tests.helpers import species_from_arrays, stress_fields
 from tests.observe_cases import seam_rows
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 T = ref.TILE_ROWS  # the kernel's tile height (kCompTileRows), restated in tests/components_ref.py
 TV, TU = (0.25, 0.1, 0.05, 0.4), (0.5, 0.8, 0.3, 0.95)   # V is set above its thresholds, U below
@@ -373,16 +370,10 @@ def test_sweep_records_components_without_changing_the_fields(built, tmp_path):
 
 
 def test_cpp_mirror_components(built, tmp_path):
-    exe = tmp_path / "components_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "components_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("components_mirror", tmp_path)
     members, rows, cols = 4, 72, 200
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "31", str(out)], capture_output=True, text=True)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "31", str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     n = (2 + members) * 4 * 35

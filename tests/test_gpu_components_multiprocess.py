@@ -3,22 +3,14 @@ the global grid, equal to the single-process one -- right after the upload, when
 Every rank's seam rows and counters travel with the call and every rank does the same merge.  All ranks share device 0
 through the shared-memory transport double (tests/cpp/shm_transport.cpp, built as tests/test_gpu_multiprocess.py builds it)."""
 import os
-import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+
+from tests.children import rank_session, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TV, TU = (0.25, 0.1), (0.5, 0.8)
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
 
 
 def _planes(rows, cols, slabs):
@@ -46,27 +38,19 @@ def _words(species):
 
 
 def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, local_slabs):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
+    from tests.helpers import species_from_arrays
 
-    from grayscott_amd import Parameters, Simulation
-    from tests.helpers import join_ranks, species_from_arrays
-
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, local_slabs)
-    sim = Simulation.new(Parameters(), args)
-    u0, v0 = _planes(rows, cols, world * local_slabs)
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
-    before = sim.context.stats()
-    fresh = _words(species)                                   # right after the upload: ghost rows stale
-    assert sim.context.stats() == before
-    sim.perform_steps(species, steps)
-    before = sim.context.stats()
-    later = _words(species)
-    assert sim.context.stats() == before
-    np.save(os.path.join(out_dir, f"rank{rank}.npy"), np.concatenate([fresh, later]))
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
+    with rank_session(rank, world, port, transport_lib, rows, local_slabs) as (sim, (r0, r1)):
+        u0, v0 = _planes(rows, cols, world * local_slabs)
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
+        before = sim.context.stats()
+        fresh = _words(species)                                   # right after the upload: ghost rows stale
+        assert sim.context.stats() == before
+        sim.perform_steps(species, steps)
+        before = sim.context.stats()
+        later = _words(species)
+        assert sim.context.stats() == before
+        np.save(os.path.join(out_dir, f"rank{rank}.npy"), np.concatenate([fresh, later]))
 
 
 @pytest.mark.parametrize("world,local_slabs,rows,cols,steps", [
@@ -78,8 +62,7 @@ def test_every_rank_gets_the_single_process_components(tmp_path, built, shm_tran
     from tests import components_ref
     from tests.helpers import free_port, species_from_arrays
 
-    mp.spawn(_worker, args=(world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs),
-             nprocs=world, join=True)
+    spawn_ranks(_worker, (world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs), world)
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
     u0, v0 = _planes(rows, cols, world * local_slabs)
     species = species_from_arrays(sim, u0, v0)

@@ -1,18 +1,16 @@
 """Two-point pair counts on the device (gs_fields_correlation, gs_members_correlation) against the numpy restatement of
 their rule (tests/corr_ref.py) on the downloaded plane: every counter equal, everywhere."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from grayscott_amd import Correlation, HipArgs, HipConcentration, Parameters, Simulation, capi, correlation_fields
 from tests import corr_ref, morph_ref
+from tests.children import build_program, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 H = corr_ref.UNIT_ROWS  # the kernel's unit height (kPairRows in gs_correlation.hip), restated in tests/corr_ref.py
 TV, TU = (0.25, 0.1, 0.05, 0.4), (0.5, 0.8, 0.3, 0.95)   # V is set above its thresholds, U below
@@ -450,17 +448,10 @@ def test_sweep_records_correlations_without_changing_the_fields(built, tmp_path)
 
 
 def test_cpp_mirror_correlation(built, tmp_path):
-    exe = tmp_path / "correlation_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "correlation_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("correlation_mirror", tmp_path)
     members, rows, cols, lag = 4, 72, 200, 10
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "31", str(lag), str(out)], capture_output=True, text=True,
-                       timeout=120)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "31", str(lag), str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     n = (1 + members) * 4 * 4 * (lag + 1)

@@ -4,23 +4,14 @@ The pairs across a rank seam need the last L rows of the rank above: they travel
 refused on every rank.  All ranks share device 0 through the shared-memory transport double (tests/cpp/shm_transport.cpp,
 built as tests/test_gpu_multiprocess.py builds it)."""
 import os
-import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+
+from tests.children import rank_session, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TV, TU = (0.25, 0.1), (0.5, 0.8)
-LIMIT = 120  # seconds for the ranks of one case: every GPU step of this file runs under a time limit of its own
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
 
 
 def _planes(rows, cols):
@@ -38,48 +29,27 @@ def _pairs(species, lag):
 
 
 def _worker(rank, world, port, rows, cols, steps, lag, too_long, out_dir, transport_lib, local_slabs):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
+    from grayscott_amd import capi
+    from tests.helpers import species_from_arrays
 
-    from grayscott_amd import Parameters, Simulation, capi
-    from tests.helpers import join_ranks, species_from_arrays
-
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, local_slabs)
-    sim = Simulation.new(Parameters(), args)
-    u0, v0 = _planes(rows, cols)
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
-    before = sim.context.stats()
-    fresh = _pairs(species, lag)                              # right after the upload: ghost rows stale
-    assert sim.context.stats() == before
-    try:                                                      # a slab shorter than the lag: refused here as on every rank
-        _pairs(species, too_long)
-        refused = 0
-    except capi.GsError as e:
-        refused = e.code
-    sim.perform_steps(species, steps)
-    before = sim.context.stats()
-    later = _pairs(species, lag)
-    assert sim.context.stats() == before
-    alone = species.in_out()[1].correlation(sim.context, [TV[0]], lag)[0].pairs   # one plane alone: another collective call
-    np.save(os.path.join(out_dir, f"rank{rank}.npy"), np.concatenate([fresh, later, alone[None]]))
-    np.save(os.path.join(out_dir, f"refused{rank}.npy"), np.array([refused]))
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
-
-
-def _spawn(args, nprocs):
-    """The ranks, under one time limit: whoever is still running after LIMIT seconds is ended and the case fails."""
-    ctx = mp.spawn(_worker, args=args, nprocs=nprocs, join=False)
-    import time
-
-    end = time.monotonic() + LIMIT
-    while not ctx.join(timeout=1.0):
-        if time.monotonic() > end:
-            for p in ctx.processes:
-                if p.is_alive():
-                    p.terminate()
-            pytest.fail(f"the ranks did not end within {LIMIT} s")
+    with rank_session(rank, world, port, transport_lib, rows, local_slabs) as (sim, (r0, r1)):
+        u0, v0 = _planes(rows, cols)
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
+        before = sim.context.stats()
+        fresh = _pairs(species, lag)                              # right after the upload: ghost rows stale
+        assert sim.context.stats() == before
+        try:                                                      # a slab shorter than the lag: refused here as on every rank
+            _pairs(species, too_long)
+            refused = 0
+        except capi.GsError as e:
+            refused = e.code
+        sim.perform_steps(species, steps)
+        before = sim.context.stats()
+        later = _pairs(species, lag)
+        assert sim.context.stats() == before
+        alone = species.in_out()[1].correlation(sim.context, [TV[0]], lag)[0].pairs   # one plane alone: another collective call
+        np.save(os.path.join(out_dir, f"rank{rank}.npy"), np.concatenate([fresh, later, alone[None]]))
+        np.save(os.path.join(out_dir, f"refused{rank}.npy"), np.array([refused]))
 
 
 @pytest.mark.parametrize("world,local_slabs,rows,cols,steps,lag,too_long", [
@@ -93,7 +63,7 @@ def test_every_rank_gets_the_single_process_correlation(tmp_path, built, shm_tra
     from tests import corr_ref
     from tests.helpers import free_port, species_from_arrays
 
-    _spawn((world, free_port(), rows, cols, steps, lag, too_long, str(tmp_path), shm_transport, local_slabs), world)
+    spawn_ranks(_worker, (world, free_port(), rows, cols, steps, lag, too_long, str(tmp_path), shm_transport, local_slabs), world)
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
     u0, v0 = _planes(rows, cols)
     species = species_from_arrays(sim, u0, v0)

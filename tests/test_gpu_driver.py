@@ -5,6 +5,7 @@ import pytest
 import oracle
 from grayscott_amd import HipArgs, Parameters, Simulation, pinned_empty
 from grayscott_amd import simulate as driver
+from tests.children import run_program
 from tests.helpers import assert_bits_equal
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +52,6 @@ def test_driver_loop_writes_the_reference_container(built, tmp_path):
     """-o *.h5: dataset "matrix" [nbimage, rows, cols] f32 in [1, rows, cols] chunks (data/src/hdf5.rs:36-63),
     read back with our parser and, where an HDF5 installation exists, with the real h5dump."""
     import os
-    import subprocess
 
     from grayscott_amd import hdf5_min
 
@@ -66,10 +66,10 @@ def test_driver_loop_writes_the_reference_container(built, tmp_path):
         assert_bits_equal(np.asarray(data[i]), v, f"image {i}")
     h5dump = os.path.join(os.environ.get("HDF5_DIR", "/opt/conda"), "bin", "h5dump")
     if os.path.exists(h5dump):
-        header = subprocess.run([h5dump, "-p", "-H", str(out)], capture_output=True, text=True, check=True).stdout
+        header = run_program([h5dump, "-p", "-H", str(out)], check=True).stdout
         assert "CHUNKED ( 1, 64, 200 )" in header and "( 70, 64, 200 )" in header and "H5T_IEEE_F32LE" in header
         dump = tmp_path / "dump.bin"
-        subprocess.run([h5dump, "-d", "/matrix", "-b", "LE", "-o", str(dump), str(out)], capture_output=True, check=True)
+        run_program([h5dump, "-d", "/matrix", "-b", "LE", "-o", str(dump), str(out)], check=True)
         assert np.array_equal(np.fromfile(dump, "<f4").reshape(70, 64, 200), np.asarray(data))
 
 

@@ -5,8 +5,6 @@ from __future__ import annotations
 
 import ctypes
 import json
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,9 +15,9 @@ from grayscott_amd import HipArgs, Parameters, Simulation, capi, hdf5_min
 from grayscott_amd.simulation import STENCILS
 
 from .helpers import assert_bits_equal, gpu_run, oracle_params, stress_fields
+from tests.children import ROOT, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # six members with distinct (feed, kill, du, dv, dt), the defaults first
 PARAMS = [Parameters(),
@@ -218,9 +216,9 @@ def test_member_offsets_are_64_bit():
 def test_sweep_end_to_end(tmp_path):
     out = tmp_path / "sweep.h5"
     rows, cols, steps = 40, 64, 50
-    r = subprocess.run([sys.executable, "-m", "grayscott_amd.sweep", "--feed", "0.01:0.04:4", "--kill", "0.045:0.06:4",
-                        "-r", str(rows), "-c", str(cols), "-s", str(steps), "-o", str(out)],
-                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-m", "grayscott_amd.sweep", "--feed", "0.01:0.04:4", "--kill", "0.045:0.06:4",
+                     "-r", str(rows), "-c", str(cols), "-s", str(steps), "-o", str(out)],
+                    cwd=ROOT, limit=300)
     assert r.returncode == 0, r.stderr
     images = hdf5_min.read(str(out))
     side = json.load(open(tmp_path / "sweep.json"))

@@ -1,8 +1,6 @@
 """Histograms on the device (gs_fields_histogram, gs_members_histogram) against the numpy restatement of their binning rule
 (tests/hist_ref.py) on the downloaded plane: every counter equal."""
 import ctypes
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -10,10 +8,10 @@ import pytest
 from grayscott_amd import HipArgs, HipConcentration, Histogram, Parameters, Simulation, capi
 from grayscott_amd.simulation import histogram_fields
 from tests import hist_ref
+from tests.children import build_program, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 RULES = {"clipped": capi.GS_BOUNDARY_CLIPPED, "zero_halo": capi.GS_BOUNDARY_ZERO_HALO,
          "periodic": capi.GS_BOUNDARY_PERIODIC, "neumann": capi.GS_BOUNDARY_NEUMANN}
@@ -305,16 +303,10 @@ def test_sweep_records_histograms_without_changing_the_fields(built, tmp_path):
 
 
 def test_cpp_mirror_histograms(built, tmp_path):
-    exe = tmp_path / "histogram_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "histogram_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("histogram_mirror", tmp_path)
     members, rows, cols, bins = 4, 72, 200, 50
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "31", str(bins), str(out)], capture_output=True, text=True)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "31", str(bins), str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     n = (2 + 2 * members) * (bins + 3)

@@ -9,8 +9,6 @@ driver end to end.  The masks go through Simulation.set_mask, which uploads 0 an
 schedules and aimed wall layouts: tests/test_gpu_mask_property.py.  Two processes: tests/test_gpu_mask_multiprocess.py.)"""
 from __future__ import annotations
 
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -20,9 +18,9 @@ from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi
 
 from . import mask_ref as R
 from .helpers import assert_bits_equal, oracle_params, rule_run, species_from_arrays, stress_fields
+from tests.children import ROOT, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RULES = [capi.GS_BOUNDARY_CLIPPED, capi.GS_BOUNDARY_ZERO_HALO, capi.GS_BOUNDARY_PERIODIC, capi.GS_BOUNDARY_NEUMANN]
 RULE_SUFFIX = {0: "/mask", 1: "/mask", 2: "/periodic/mask", 3: "/neumann/mask"}
 
@@ -402,9 +400,9 @@ def test_simulate_with_a_mask(tmp_path):
     mask = R.maze((rows, cols), np.random.default_rng(8))
     np.save(tmp_path / "m.npy", mask)
     out = tmp_path / "out.npy"
-    r = subprocess.run([sys.executable, "-m", "grayscott_amd.simulate", "-r", str(rows), "-c", str(cols), "-n", str(images),
-                        "-e", str(extra), "-o", str(out), "--hip-devices", "0", "--hip-mask", str(tmp_path / "m.npy")],
-                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-m", "grayscott_amd.simulate", "-r", str(rows), "-c", str(cols), "-n", str(images),
+                     "-e", str(extra), "-o", str(out), "--hip-devices", "0", "--hip-mask", str(tmp_path / "m.npy")],
+                    cwd=ROOT, limit=300)
     assert r.returncode == 0, r.stderr[-2000:]
     got = np.load(out)
     u, v = oracle.init_species(rows, cols)

@@ -8,16 +8,14 @@ import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 from grayscott_amd import capi
 
 from . import mask_ref as R
 from .helpers import assert_bits_equal, stress_fields
-from .test_gpu_multiprocess import shm_transport  # noqa: F401  (the fixture: the librccl test double)
+from tests.children import ROOT, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, boundary):
@@ -59,7 +57,7 @@ def test_two_processes_over_the_shm_transport(tmp_path, built, shm_transport, bo
     from tests.helpers import free_port
 
     rows, cols, steps = 301, 517, 14     # the seam at row 150 crosses a wall line (rows 0, 4, ..., 148, 152)
-    mp.spawn(_worker, args=(2, free_port(), rows, cols, steps, str(tmp_path), shm_transport, boundary), nprocs=2, join=True)
+    spawn_ranks(_worker, (2, free_port(), rows, cols, steps, str(tmp_path), shm_transport, boundary), 2)
     u0, v0 = stress_fields((rows, cols), 32)
     mask = R.maze((rows, cols), np.random.default_rng(33))
     ref = R.run(u0, v0, steps + 3, mask, boundary=boundary)

@@ -3,8 +3,6 @@
 overlap equal, in the same order, everywhere.  Exact equality throughout."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -13,11 +11,11 @@ from grayscott_amd import ComponentMatch, HipArgs, HipConcentration, Parameters,
 from tests import component_list_ref
 from tests import components_ref
 from tests import match_ref as ref
+from tests.children import ROOT, build_program, rank_session, run_program, shm_transport, spawn_ranks  # noqa: F401
 from tests.helpers import species_from_arrays, stress_fields
 from tests.observe_cases import seam_rows
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 T = components_ref.TILE_ROWS  # the labelling's tile height (kCompTileRows)
 EVENT_NAMES = ("continued", "split", "merged", "born", "died")
@@ -444,16 +442,10 @@ def test_sweep_records_tracks_without_changing_the_fields(built, tmp_path):
 # ---- the C++ mirror ----------------------------------------------------------------------------------------------------------------
 
 def test_cpp_mirror_matches(built, tmp_path):
-    exe = tmp_path / "match_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "match_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("match_mirror", tmp_path)
     members, rows, cols = 4, 72, 200
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "300", str(out)], capture_output=True, text=True)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "300", str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     matches, at = [], 0
@@ -478,57 +470,29 @@ def test_cpp_mirror_matches(built, tmp_path):
 
 # ---- a multi-process context -----------------------------------------------------------------------------------------------------------
 
-LIMIT = 120  # seconds for the ranks: every GPU step of this file runs under a time limit of its own
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
-
-
 def _worker(rank, world, port, rows, cols, out_dir, transport_lib):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
+    from grayscott_amd import capi
+    from tests.helpers import species_from_arrays
 
-    from grayscott_amd import Parameters, Simulation, capi
-    from tests.helpers import join_ranks, species_from_arrays
-
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, 1)
-    sim = Simulation.new(Parameters(), args)
-    u0, v0 = stress_fields((rows, cols), 4)
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
-    snap = species.snapshot()
-    codes = []
-    for call in (lambda: species.match_since(snap, 0.25), lambda: species.in_out()[0].match(sim.context, snap.u, 0.5, False, 4, 2)):
-        try:
-            call()
-            codes.append(0)
-        except capi.GsError as e:
-            codes.append(e.code)
-    sim.perform_steps(species, 3)                               # the context goes on working, on every rank
-    np.save(os.path.join(out_dir, f"refused{rank}.npy"), np.array(codes))
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
+    with rank_session(rank, world, port, transport_lib, rows) as (sim, (r0, r1)):
+        u0, v0 = stress_fields((rows, cols), 4)
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
+        snap = species.snapshot()
+        codes = []
+        for call in (lambda: species.match_since(snap, 0.25), lambda: species.in_out()[0].match(sim.context, snap.u, 0.5, False, 4, 2)):
+            try:
+                call()
+                codes.append(0)
+            except capi.GsError as e:
+                codes.append(e.code)
+        sim.perform_steps(species, 3)                               # the context goes on working, on every rank
+        np.save(os.path.join(out_dir, f"refused{rank}.npy"), np.array(codes))
 
 
 def test_a_two_process_context_is_refused_on_both_ranks(tmp_path, built, shm_transport):
-    import time
-
-    import torch.multiprocessing as mp
-
     from tests.helpers import free_port
 
-    ctx = mp.spawn(_worker, args=(2, free_port(), 50, 333, str(tmp_path), shm_transport), nprocs=2, join=False)
-    end = time.monotonic() + LIMIT
-    while not ctx.join(timeout=1.0):
-        if time.monotonic() > end:
-            for p in ctx.processes:
-                if p.is_alive():
-                    p.terminate()
-            pytest.fail(f"the ranks did not end within {LIMIT} s")
+    spawn_ranks(_worker, (2, free_port(), 50, 333, str(tmp_path), shm_transport), 2)
     for rank in range(2):
         codes = list(np.load(tmp_path / f"refused{rank}.npy"))
         assert codes == [capi.GS_ERR_UNSUPPORTED] * 2, (rank, codes)

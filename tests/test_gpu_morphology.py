@@ -1,18 +1,15 @@
 """Bit-quad counts on the device (gs_fields_morphology, gs_members_morphology) against the numpy restatement of their rule
 (tests/morph_ref.py) on the downloaded plane: all six counters equal, everywhere."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from grayscott_amd import HipArgs, HipConcentration, Morphology, Parameters, Simulation, capi
 from grayscott_amd.simulation import morphology_fields, quad_measures
 from tests import morph_ref
+from tests.children import build_program, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 H = morph_ref.UNIT_ROWS  # the kernel's unit height (kQuadRows in gs_morphology.hip), restated in tests/morph_ref.py
 TV, TU = (0.25, 0.1, 0.05, 0.4), (0.5, 0.8, 0.3, 0.95)   # V is set above its thresholds, U below
@@ -355,16 +352,10 @@ def test_sweep_records_morphology_without_changing_the_fields(built, tmp_path):
 
 
 def test_cpp_mirror_morphology(built, tmp_path):
-    exe = tmp_path / "morphology_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "morphology_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("morphology_mirror", tmp_path)
     members, rows, cols = 4, 72, 200
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "31", str(out)], capture_output=True, text=True)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "31", str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     n = (1 + members) * 4 * 6

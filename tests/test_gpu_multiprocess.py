@@ -12,7 +12,6 @@ that ("duplicate GPU"), so there are two legs:
   local rows -- runs for real in N processes and is compared bit for bit with the oracle.
 """
 import os
-import subprocess
 import socket
 import sys
 
@@ -20,8 +19,9 @@ import numpy as np
 import pytest
 import torch.multiprocessing as mp
 
+from tests.children import ROOT, run_program, shm_transport, spawn_ranks  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _free_port():
@@ -65,14 +65,6 @@ def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, seed, 
     dist.barrier()
     sim.context.close()
     dist.destroy_process_group()
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    """The librccl test double (tests/cpp/shm_transport.cpp), compiled on first use."""
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
 
 
 def _selftest_worker(out_dir):
@@ -138,8 +130,7 @@ def test_shm_ranks_with_several_local_slabs(tmp_path, built, shm_transport, worl
 def _ranks_match_oracle(tmp_path, world, rows, cols, steps, transport_lib, seed, local_slabs=1):
     import oracle
 
-    mp.spawn(_worker, args=(world, _free_port(), rows, cols, steps, str(tmp_path), transport_lib, seed, local_slabs),
-             nprocs=world, join=True)
+    spawn_ranks(_worker, (world, _free_port(), rows, cols, steps, str(tmp_path), transport_lib, seed, local_slabs), world)
     skips = [p for p in os.listdir(tmp_path) if p.startswith("skip")]
     if skips:
         pytest.skip("RCCL refused the rank layout on this box: " + open(tmp_path / skips[0]).read()[:200])
@@ -170,7 +161,7 @@ def test_library_pairing_of_a_bench_rank_runs_on_one_gpu(tmp_path, built, order)
     # with it torch, before the worker runs)
     code = ("import sys; sys.path.insert(0, %r); from tests.pairing_worker import pairing_worker; "
             "pairing_worker(%r, %r, %d)" % (ROOT, str(tmp_path), order, _free_port()))
-    p = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True, timeout=900)
+    p = run_program([sys.executable, "-c", code], cwd=ROOT, limit=900)
     assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
     r = json.load(open(tmp_path / "result.json"))
     out = os.path.join(ROOT, "gpurun_out")

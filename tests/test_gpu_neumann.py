@@ -6,12 +6,10 @@ the refusals; and the simulate and sweep drivers end to end."""
 from __future__ import annotations
 
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 import oracle
 from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi, hdf5_min
@@ -19,10 +17,9 @@ from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi, hdf5_m
 from . import neumann_ref
 from .helpers import assert_bits_equal, gpu_run, oracle_params, species_from_arrays, stress_fields
 from .test_gpu_property import tb_cols_per_wave
-from .test_gpu_multiprocess import shm_transport  # noqa: F401  (the fixture: the librccl test double)
+from tests.children import ROOT, run_program, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = capi.GS_BOUNDARY_NEUMANN
 
 
@@ -132,7 +129,7 @@ def test_fair_progress_form(cpl, monkeypatch):
             "assert 'f/' in info[0] and info[0].split('@')[0].endswith('/neumann'), info\n"
             "assert gu.tobytes() == ru.tobytes() and gv.tobytes() == rv.tobytes(), info\n")
     env = dict(os.environ, GS_HIP_FAIR="1")
-    r = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-c", code], cwd=ROOT, env=env, limit=300)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
@@ -258,8 +255,7 @@ def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, local_
 def test_processes_over_the_shm_transport(tmp_path, built, shm_transport, world, local_slabs, rows, cols, steps):  # noqa: F811
     from tests.helpers import free_port
 
-    mp.spawn(_worker, args=(world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs),
-             nprocs=world, join=True)
+    spawn_ranks(_worker, (world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs), world)
     u0, v0 = stress_fields((rows, cols), 21)
     ref_u, ref_v = neumann_ref.run(u0, v0, steps + 3)
     assert is_neumann(open(tmp_path / "name").read())
@@ -365,8 +361,8 @@ def test_auto_takes_the_marching_kernel_where_the_window_kernel_would_run():
 # ---- the drivers end to end ------------------------------------------------------------------------------------------
 def test_simulate_end_to_end(tmp_path):
     out = tmp_path / "p.h5"
-    r = subprocess.run([sys.executable, "-m", "grayscott_amd.simulate", "--hip-boundary", "3", "-r", "64", "-c", "128",
-                        "-n", "3", "-e", "32", "-o", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-m", "grayscott_amd.simulate", "--hip-boundary", "3", "-r", "64", "-c", "128",
+                     "-n", "3", "-e", "32", "-o", str(out)], cwd=ROOT, limit=300)
     assert r.returncode == 0, r.stdout + r.stderr
     data = hdf5_min.read(str(out))
     assert data.shape == (3, 64, 128)
@@ -378,9 +374,9 @@ def test_simulate_end_to_end(tmp_path):
 
 def test_sweep_end_to_end(tmp_path):
     out = tmp_path / "s.h5"
-    r = subprocess.run([sys.executable, "-m", "grayscott_amd.sweep", "--feed", "0.02:0.03:2", "--kill", "0.05:0.06:2",
-                        "-r", "24", "-c", "40", "-s", "30", "--hip-boundary", "3", "-o", str(out)],
-                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-m", "grayscott_amd.sweep", "--feed", "0.02:0.03:2", "--kill", "0.05:0.06:2",
+                     "-r", "24", "-c", "40", "-s", "30", "--hip-boundary", "3", "-o", str(out)],
+                    cwd=ROOT, limit=300)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "/neumann" in r.stderr, r.stderr
     data = hdf5_min.read(str(out))

@@ -9,21 +9,18 @@ from __future__ import annotations
 
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
 
 from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi, hdf5_min
 
 from . import param_map_ref as R
 from .helpers import assert_bits_equal, species_from_arrays, stress_fields
-from .test_gpu_multiprocess import shm_transport  # noqa: F401  (the fixture: the librccl test double)
+from tests.children import ROOT, run_program, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RULES = [capi.GS_BOUNDARY_CLIPPED, capi.GS_BOUNDARY_ZERO_HALO, capi.GS_BOUNDARY_PERIODIC, capi.GS_BOUNDARY_NEUMANN]
 RULE_SUFFIX = {0: "/map", 1: "/map", 2: "/periodic/map", 3: "/neumann/map"}
 
@@ -199,7 +196,7 @@ def test_two_processes_over_the_shm_transport(tmp_path, built, shm_transport, bo
     from tests.helpers import free_port
 
     rows, cols, steps = 300, 517, 14
-    mp.spawn(_worker, args=(2, free_port(), rows, cols, steps, str(tmp_path), shm_transport, boundary), nprocs=2, join=True)
+    spawn_ranks(_worker, (2, free_port(), rows, cols, steps, str(tmp_path), shm_transport, boundary), 2)
     u0, v0 = stress_fields((rows, cols), 22)
     feed, kill = random_map((rows, cols), 23)
     ref = R.run(u0, v0, steps + 3, feed, kill, boundary=boundary)
@@ -400,9 +397,9 @@ def test_simulate_end_to_end(tmp_path):
     import oracle
 
     out = tmp_path / "m.h5"
-    r = subprocess.run([sys.executable, "-m", "grayscott_amd.simulate", "--hip-feed-map", "0.01:0.05", "--hip-kill-map",
-                        "0.045:0.065", "-r", "64", "-c", "128", "-n", "3", "-e", "16", "-o", str(out)],
-                       cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-m", "grayscott_amd.simulate", "--hip-feed-map", "0.01:0.05", "--hip-kill-map",
+                     "0.045:0.065", "-r", "64", "-c", "128", "-n", "3", "-e", "16", "-o", str(out)],
+                    cwd=ROOT, limit=300)
     assert r.returncode == 0, r.stdout + r.stderr
     data = hdf5_min.read(str(out))
     assert data.shape == (3, 64, 128)

@@ -13,6 +13,7 @@ import pytest
 
 import oracle
 from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi
+from tests.children import ROOT, run_program
 from tests.helpers import (STRESS_SHAPES, assert_bits_equal, gpu_run, oracle_params,
                            species_from_arrays, stress_fields)
 
@@ -1100,7 +1101,6 @@ def test_xcd_aware_unit_order_bit_exact():
     (GsStepArgs::xcd_m; groups of 8 x 16 workgroups).  The group size is read from the environment once per process,
     so a child process runs the marching kernel and the single-step kernel with groups of 8 x 2 and 8 x 3 -- small
     enough to permute the units of a 300 x 2000 grid -- against the oracle, every kind of unit included."""
-    import subprocess
     import sys
 
     code = r"""
@@ -1118,8 +1118,7 @@ for kernel, kw in ((capi.GS_KERNEL_TB, dict(fuse_steps=4, rows_per_block=8, cols
         assert_bits_equal(got_v, ref_v, f"V {info[0]} steps {steps}")
 print("ok")
 """
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     for m in ("2", "3"):
-        env = dict(os.environ, GS_HIP_XCD_M=m, GS_HIP_XCD_M_STREAM=m, PYTHONPATH=root)
-        r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        env = dict(os.environ, GS_HIP_XCD_M=m, GS_HIP_XCD_M_STREAM=m, PYTHONPATH=ROOT)
+        r = run_program([sys.executable, "-c", code], cwd=ROOT, env=env, limit=600)
         assert r.returncode == 0 and r.stdout.strip().endswith("ok"), (m, r.stdout[-2000:], r.stderr[-4000:])

@@ -4,8 +4,6 @@ translation invariance (which the clipped and zero-halo rules do not have, so a 
 it); ensembles against lone periodic Species; the refusals; and the simulate driver end to end."""
 from __future__ import annotations
 
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,9 +15,9 @@ from grayscott_amd import GsError, HipArgs, Parameters, Simulation, capi, hdf5_m
 from . import periodic_ref
 from .helpers import assert_bits_equal, gpu_run, oracle_params, species_from_arrays, stress_fields
 from .test_gpu_property import tb_cols_per_wave
+from tests.children import ROOT, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = capi.GS_BOUNDARY_PERIODIC
 
 
@@ -271,8 +269,8 @@ def test_auto_takes_the_marching_kernel_where_the_window_kernel_would_run():
 # ---- the driver end to end -------------------------------------------------------------------------------------------
 def test_simulate_end_to_end(tmp_path):
     out = tmp_path / "p.h5"
-    r = subprocess.run([sys.executable, "-m", "grayscott_amd.simulate", "--hip-boundary", "2", "-r", "64", "-c", "128",
-                        "-n", "3", "-e", "32", "-o", str(out)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_program([sys.executable, "-m", "grayscott_amd.simulate", "--hip-boundary", "2", "-r", "64", "-c", "128",
+                     "-n", "3", "-e", "32", "-o", str(out)], cwd=ROOT, limit=300)
     assert r.returncode == 0, r.stdout + r.stderr
     data = hdf5_min.read(str(out))
     assert data.shape == (3, 64, 128)

@@ -20,16 +20,13 @@ Every tool runs in a fresh process of its own, one after another; after an abort
 tool is started."""
 from __future__ import annotations
 
-import json
 import math
-import os
-import subprocess
-import sys
 
 import pytest
 
+from tests.children import run_rate_tool
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAN = float("nan")
 
 OBSERVABLE = ["--grids", "96x160", "--calls", "2"]
@@ -259,30 +256,16 @@ EXPECTED = {
 }
 
 
-_died = []  # the first tool whose process aborted, faulted or ran out of time: nothing is started after it
-
-
 def _same(a, b):
     return a == b or (isinstance(a, float) and isinstance(b, float) and math.isnan(a) and math.isnan(b))
 
 
 @pytest.mark.parametrize("tool", list(ARGS))
 def test_rate_tool_prints_what_it_printed_before(built, tmp_path, tool):
-    assert not _died, f"not started: {_died[0]} died before"
     want = EXPECTED[tool]
-    out_json, out_md = tmp_path / "out" / "rows.json", tmp_path / "table.md"
-    cmd = [sys.executable, os.path.join(ROOT, "tools", f"{tool}_rate.py")] + ARGS[tool] + ["--json", str(out_json), "--md", str(out_md)]
-    try:
-        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
-    except subprocess.TimeoutExpired:
-        _died.append(f"{tool} (timeout)")
-        raise
-    if r.returncode < 0 or r.returncode in (134, 139):
-        _died.append(f"{tool} (exit status {r.returncode})")
+    r, md, rows = run_rate_tool(tool, ARGS[tool], tmp_path)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
-    assert out_md.read_text().splitlines()[:2] == want["header"]
-    text = out_json.read_text()
-    rows = json.loads(text) if text.lstrip().startswith("[") else [json.loads(line) for line in text.splitlines()]
+    assert md[:2] == want["header"]
     assert len(rows) == len(want["rows"]), rows
     for got, (group, fixed) in zip(rows, want["rows"]):
         assert set(got) == set(fixed) | set(want["timed"][group]), (sorted(got), sorted(fixed), want["timed"][group])

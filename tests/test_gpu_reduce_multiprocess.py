@@ -3,63 +3,48 @@ and they are the matching rows of the single-process image, bit for bit; a (rows
 slab begins off a multiple of f is refused on every rank.  All ranks share device 0 through the shared-memory transport
 double (tests/cpp/shm_transport.cpp, built as tests/test_gpu_multiprocess.py builds it)."""
 import os
-import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+
+from tests.children import rank_session, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FACTORS = (2, 3, 4, 5, 8, 16, 64)
 
 
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
-
-
 def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, local_slabs):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
-
-    from grayscott_amd import Parameters, Simulation, capi
+    from grayscott_amd import capi
     from grayscott_amd.simulation import pinned_empty
     from tests import reduce_ref
-    from tests.helpers import join_ranks, species_from_arrays, stress_fields
+    from tests.helpers import species_from_arrays, stress_fields
 
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, local_slabs)
-    sim = Simulation.new(Parameters(), args)
-    S = world * local_slabs
-    u0, v0 = stress_fields((rows, cols), 4)
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
-    sim.perform_steps(species, steps)
-    in_v = species.in_out()[1]
-    out = {}
-    for f in FACTORS:
-        if not reduce_ref.slab_rule(rows, S, f):
-            codes = []
-            for call in (lambda: in_v.reduced_shape(f), lambda: species.make_result_view(reduce=f)):
-                try:
-                    call()
-                    codes.append(0)
-                except capi.GsError as e:
-                    codes.append(e.code)
-            out[f"refused{f}"] = np.array(codes)
-            continue
-        lo, hi = reduce_ref.local_rows(rows, S, rank * local_slabs, local_slabs, f)
-        assert in_v.reduced_shape(f) == (hi - lo, -(-cols // f)), (rank, f, in_v.reduced_shape(f))
-        out[f"blocking{f}"] = species.make_result_view(reduce=f)
-        image = pinned_empty((hi - lo, -(-cols // f)))
-        species.write_result_view_after(image, reduce=f)
-        sim.context.download_wait()
-        out[f"overlapped{f}"] = np.array(image)
-    np.savez(os.path.join(out_dir, f"rank{rank}.npz"), **out)
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
+    with rank_session(rank, world, port, transport_lib, rows, local_slabs) as (sim, (r0, r1)):
+        S = world * local_slabs
+        u0, v0 = stress_fields((rows, cols), 4)
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
+        sim.perform_steps(species, steps)
+        in_v = species.in_out()[1]
+        out = {}
+        for f in FACTORS:
+            if not reduce_ref.slab_rule(rows, S, f):
+                codes = []
+                for call in (lambda: in_v.reduced_shape(f), lambda: species.make_result_view(reduce=f)):
+                    try:
+                        call()
+                        codes.append(0)
+                    except capi.GsError as e:
+                        codes.append(e.code)
+                out[f"refused{f}"] = np.array(codes)
+                continue
+            lo, hi = reduce_ref.local_rows(rows, S, rank * local_slabs, local_slabs, f)
+            assert in_v.reduced_shape(f) == (hi - lo, -(-cols // f)), (rank, f, in_v.reduced_shape(f))
+            out[f"blocking{f}"] = species.make_result_view(reduce=f)
+            image = pinned_empty((hi - lo, -(-cols // f)))
+            species.write_result_view_after(image, reduce=f)
+            sim.context.download_wait()
+            out[f"overlapped{f}"] = np.array(image)
+        np.savez(os.path.join(out_dir, f"rank{rank}.npz"), **out)
 
 
 @pytest.mark.parametrize("world,local_slabs,rows,cols,steps", [
@@ -73,8 +58,7 @@ def test_each_rank_gets_its_rows_of_the_single_process_image(tmp_path, built, sh
     from tests import reduce_ref
     from tests.helpers import free_port, species_from_arrays, stress_fields
 
-    mp.spawn(_worker, args=(world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs),
-             nprocs=world, join=True)
+    spawn_ranks(_worker, (world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs), world)
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
     u0, v0 = stress_fields((rows, cols), 4)
     species = species_from_arrays(sim, u0, v0)

@@ -2,8 +2,6 @@
 (tests/region_components_ref.py): every region's counters are those of the whole-grid rule on that region's cells alone -- a
 region's border is a wall.  Everything is exact integer equality."""
 import functools
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,10 +10,10 @@ import pytest
 from grayscott_amd import HipArgs, HipConcentration, Parameters, RegionComponents, Simulation, capi, hdf5_min
 from grayscott_amd.simulation import components_fields, region_components_fields
 from tests import observe_cases, region_components_ref, regions_ref
+from tests.children import ROOT, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SHAPE = (37, 532)              # three tile rows and three tile columns of 16 x 256, both ragged
 # borders inside tiles with ragged last regions (5, 20), borders on the tile borders (16, 256), (7, 64), (16, 16), and one
@@ -298,7 +296,7 @@ def test_the_driver_records_the_components(built, tmp_path):
             "--hip-kill-map", "0.04:0.07", "--hip-regions", "16x32", "--hip-regions-every", "1", "--hip-region-threshold-v", "0.25,0.1"]
     region = (16, 32)
     with_flag, without = tmp_path / "with.h5", tmp_path / "without.h5"
-    r = subprocess.run(base + ["--hip-region-components", "4", "-o", str(with_flag)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r = run_program(base + ["--hip-region-components", "4", "-o", str(with_flag)], cwd=ROOT)
     assert r.returncode == 0, r.stderr
     images = hdf5_min.read(str(with_flag))
     z = np.load(tmp_path / "with.regions.npz")
@@ -308,7 +306,7 @@ def test_the_driver_records_the_components(built, tmp_path):
         for j, t in enumerate((0.25, 0.1)):
             assert np.array_equal(z["components_v"][k, j], region_components_ref.counters(images[k], region, t, True, 4)), (k, j)
     assert z["components_v"][..., 0].sum() > 0
-    r = subprocess.run(base + ["-o", str(without)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r = run_program(base + ["-o", str(without)], cwd=ROOT)
     assert r.returncode == 0, r.stderr
     old = np.load(tmp_path / "without.regions.npz")
     keys = {"region", "shape", "steps", "thresholds_v", "thresholds_u", "cells", "quads_v", "feed", "kill"}

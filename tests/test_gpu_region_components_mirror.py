@@ -1,33 +1,23 @@
 """The C++ mirror's regional connected components (include/grayscott_hip.hpp: Species::region_components) through
 tests/cpp/region_components_mirror.cpp, against the restatement on the planes the program downloaded and against the Python
 result on the same planes."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from tests import region_components_ref, regions_ref
+from tests.children import build_program, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_mirror_region_components(built, tmp_path):
     from grayscott_amd import HipArgs, Parameters, Simulation
     from tests.helpers import species_from_arrays
 
-    exe = tmp_path / "region_components_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "region_components_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("region_components_mirror", tmp_path)
     rows, cols, region, connectivity = 72, 200, (32, 64), 4
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(rows), str(cols), str(region[0]), str(region[1]), "31", str(connectivity), str(out)],
-                       capture_output=True, text=True, timeout=120)
+    r = run_program([str(exe), str(rows), str(cols), str(region[0]), str(region[1]), "31", str(connectivity), str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     rr, rc, nt = (int(x) for x in np.frombuffer(raw[:24], np.uint64))

@@ -3,25 +3,17 @@ every region, equal to the single-process result; a rank seam that is no multipl
 rank alike.  All ranks share device 0 through the shared-memory transport double (tests/cpp/shm_transport.cpp, built as
 tests/test_gpu_multiprocess.py builds it)."""
 import os
-import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+
+from tests.children import rank_session, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS, COLS, WORLD = 96, 300, 2
 TV, TU = (0.25, 0.1), (0.5, 0.8)
 ALIGNED = [((16, 64), 8), ((48, 256), 4)]      # region shapes whose rows the rank seam (row 48) is a multiple of, and a connectivity
 UNALIGNED = (32, 64)                           # ... and one that it is not
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
 
 
 def _planes():
@@ -40,33 +32,26 @@ def _results(species, region, connectivity):
 
 
 def _worker(rank, world, port, out_dir, transport_lib):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
+    from grayscott_amd import capi
+    from tests.helpers import species_from_arrays
 
-    from grayscott_amd import Parameters, Simulation, capi
-    from tests.helpers import join_ranks, species_from_arrays
-
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, ROWS)
-    sim = Simulation.new(Parameters(), args)
-    u0, v0 = _planes()
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(ROWS, COLS))
-    before = sim.context.stats()
-    got = {}
-    for k, (region, connectivity) in enumerate(ALIGNED):
-        for i, a in enumerate(_results(species, region, connectivity)):
-            got[f"r{k}_{i}"] = a
-    try:
-        species.region_components(UNALIGNED, TV, TU)
-        refused = 0
-    except capi.GsError as e:
-        refused = e.code
-    for i, a in enumerate(_results(species, *ALIGNED[0])):                 # the context goes on working
-        assert np.array_equal(a, got[f"r0_{i}"])
-    assert sim.context.stats() == before
-    np.savez(os.path.join(out_dir, f"rank{rank}.npz"), refused=np.array(refused), **got)
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
+    with rank_session(rank, world, port, transport_lib, ROWS) as (sim, (r0, r1)):
+        u0, v0 = _planes()
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(ROWS, COLS))
+        before = sim.context.stats()
+        got = {}
+        for k, (region, connectivity) in enumerate(ALIGNED):
+            for i, a in enumerate(_results(species, region, connectivity)):
+                got[f"r{k}_{i}"] = a
+        try:
+            species.region_components(UNALIGNED, TV, TU)
+            refused = 0
+        except capi.GsError as e:
+            refused = e.code
+        for i, a in enumerate(_results(species, *ALIGNED[0])):                 # the context goes on working
+            assert np.array_equal(a, got[f"r0_{i}"])
+        assert sim.context.stats() == before
+        np.savez(os.path.join(out_dir, f"rank{rank}.npz"), refused=np.array(refused), **got)
 
 
 def test_every_rank_gets_every_region(tmp_path, built, shm_transport):
@@ -74,7 +59,7 @@ def test_every_rank_gets_every_region(tmp_path, built, shm_transport):
     from tests import region_components_ref
     from tests.helpers import free_port, species_from_arrays
 
-    mp.spawn(_worker, args=(WORLD, free_port(), str(tmp_path), shm_transport), nprocs=WORLD, join=True)
+    spawn_ranks(_worker, (WORLD, free_port(), str(tmp_path), shm_transport), WORLD)
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
     u0, v0 = _planes()
     species = species_from_arrays(sim, u0, v0)

@@ -1,14 +1,10 @@
 """tools/region_components_rate.py at a small size: it runs through, and its table has every column filled (the host route
 where scipy is present)."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
+from tests.children import run_rate_tool
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_region_components_rate_runs_and_fills_its_table(built, tmp_path):
@@ -17,12 +13,8 @@ def test_region_components_rate_runs_and_fills_its_table(built, tmp_path):
         host = True
     except ImportError:
         host = False
-    md, js = tmp_path / "rc.md", tmp_path / "rc.json"
-    cmd = [sys.executable, os.path.join(ROOT, "tools", "region_components_rate.py"), "--grids", "256x512", "--regions", "64x64",
-           "--calls", "2", "--md", str(md), "--json", str(js)]
-    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r, lines, rows = run_rate_tool("region_components", ["--grids", "256x512", "--regions", "64x64", "--calls", "2"], tmp_path)
     assert r.returncode == 0, r.stderr
-    lines = md.read_text().splitlines()
     columns = lines[0].count("|") - 1
     assert columns == 10 and lines[1] == "|" + "---|" * columns and len(lines) == 2 + 3          # the inputs `new`, `random`, `full`
     for line in lines[2:]:
@@ -30,7 +22,6 @@ def test_region_components_rate_runs_and_fills_its_table(built, tmp_path):
         assert len(cells) == columns and all(cells) and "nan" not in line, line
         assert cells[:2] == ["256x512", "64x64"] and all(float(x) > 0 for x in cells[3:9]), line
         assert (float(cells[9]) > 0) if host else cells[9] == "-", line
-    rows = json.loads(js.read_text())
     assert [r["input"] for r in rows] == ["new", "random", "full"]
     assert rows[2]["components"] == 4 * 8 and rows[0]["components"] >= 1 and rows[1]["components"] > 4 * 8
     for row in rows:

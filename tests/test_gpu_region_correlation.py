@@ -2,8 +2,6 @@
 (tests/region_corr_ref.py): every region's counts are those of the whole-grid rule on that region's cells alone.  Everything
 is bit for bit."""
 import functools
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,10 +10,10 @@ import pytest
 from grayscott_amd import HipArgs, HipConcentration, Parameters, RegionCorrelation, Simulation, capi, hdf5_min
 from grayscott_amd.simulation import correlation_fields, region_correlation_fields
 from tests import corr_ref, region_corr_ref, regions_ref
+from tests.children import ROOT, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 H = corr_ref.UNIT_ROWS  # the pair kernels' unit height (kPairRows), restated in tests/corr_ref.py
 THRESHOLDS = [0.3, -1.5, 0.0, 2.0 ** -130]  # distinct, one of them sub-normal
@@ -261,7 +259,7 @@ def test_the_driver_records_the_pair_counts(built, tmp_path):
             "--hip-kill-map", "0.04:0.07", "--hip-regions", "16x32", "--hip-regions-every", "1", "--hip-region-threshold-v", "0.25,0.1"]
     region = (16, 32)
     with_flag, without = tmp_path / "with.h5", tmp_path / "without.h5"
-    r = subprocess.run(base + ["--hip-region-corr-lags", "8", "-o", str(with_flag)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r = run_program(base + ["--hip-region-corr-lags", "8", "-o", str(with_flag)], cwd=ROOT)
     assert r.returncode == 0, r.stderr
     images = hdf5_min.read(str(with_flag))
     z = np.load(tmp_path / "with.regions.npz")
@@ -269,7 +267,7 @@ def test_the_driver_records_the_pair_counts(built, tmp_path):
     assert z["pairs_v"].shape == (2, 2, 4, 4, 4, 9) and z["pairs_v"].dtype == np.uint64
     for k, t in enumerate((0.25, 0.1)):                                    # (the images are the V planes)
         assert np.array_equal(z["pairs_v"][-1, k], region_corr_ref.pairs(images[-1], region, t, True, 8)), t
-    r = subprocess.run(base + ["-o", str(without)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r = run_program(base + ["-o", str(without)], cwd=ROOT)
     assert r.returncode == 0, r.stderr
     old = np.load(tmp_path / "without.regions.npz")
     keys = {"region", "shape", "steps", "thresholds_v", "thresholds_u", "cells", "quads_v", "feed", "kill"}

@@ -1,29 +1,21 @@
 """tools/region_correlation_rate.py at a small size: it runs through, and its table has every column filled."""
-import json
-import os
-import subprocess
-import sys
-
 import pytest
 
+from tests.children import run_rate_tool
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_region_correlation_rate_runs_and_fills_its_table(built, tmp_path):
-    md, js = tmp_path / "rc.md", tmp_path / "rc.json"
-    cmd = [sys.executable, os.path.join(ROOT, "tools", "region_correlation_rate.py"), "--grids", "256x512", "--regions", "64x64",
-           "--lags", "16", "--calls", "2", "--md", str(md), "--json", str(js)]
-    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r, lines, rows = run_rate_tool("region_correlation", ["--grids", "256x512",
+                                                          "--regions", "64x64", "--lags", "16", "--calls", "2"], tmp_path)
     assert r.returncode == 0, r.stderr
-    lines = md.read_text().splitlines()
     columns = lines[0].count("|") - 1
     assert columns == 14 and lines[1] == "|" + "---|" * columns and len(lines) == 2 + 2          # the inputs `new` and `random`
     for line in lines[2:]:
         cells = [c.strip() for c in line.strip("|").split("|")]
         assert len(cells) == columns and all(cells) and "-" not in cells and "nan" not in line, line
         assert cells[:3] == ["256x512", "64x64", "16"] and all(float(x) > 0 for c in cells[4:] for x in c.split(" / ")), line
-    rows = json.loads(js.read_text())
     assert [r["input"] for r in rows] == ["new", "random"]
     for row in rows:
         for key in ("region_pairs1_ms", "region_pairs1_reused_ms", "pairs1_ms", "region_pairs4_ms", "region_pairs4_reused_ms", "pairs4_ms",

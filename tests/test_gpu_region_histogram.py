@@ -1,8 +1,6 @@
 """Regional histograms on the device (gs_fields_region_histogram) against their definition (tests/region_hist_ref.py): every
 region's counters are those of the whole-grid rule on that region's cells alone.  Everything is bit for bit."""
 import functools
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -11,10 +9,10 @@ import pytest
 from grayscott_amd import HipArgs, HipConcentration, Parameters, RegionHistogram, Simulation, capi, hdf5_min
 from grayscott_amd.simulation import histogram_fields, region_histogram_fields
 from tests import hist_ref, region_hist_ref, regions_ref
+from tests.children import ROOT, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 T = region_hist_ref.TILE_ROWS  # the kernel's row chunk (kTileRows), restated in tests/region_hist_ref.py
 SHAPE = (96, 301)              # the column count is no multiple of 4
@@ -283,8 +281,7 @@ def test_the_driver_records_the_histograms(built, tmp_path):
             "--hip-kill-map", "0.04:0.07", "--hip-regions", "16x32", "--hip-regions-every", "1", "--hip-region-threshold-v", "0.25,0.1"]
     region = (16, 32)
     with_flag, without = tmp_path / "with.h5", tmp_path / "without.h5"
-    r = subprocess.run(base + ["--hip-region-hist-bins", "32", "--hip-region-hist-range-v=-0.125:0.5", "-o", str(with_flag)], cwd=ROOT,
-                       capture_output=True, text=True, timeout=120)
+    r = run_program(base + ["--hip-region-hist-bins", "32", "--hip-region-hist-range-v=-0.125:0.5", "-o", str(with_flag)], cwd=ROOT)
     assert r.returncode == 0, r.stderr
     images = hdf5_min.read(str(with_flag))
     z = np.load(tmp_path / "with.regions.npz")
@@ -293,7 +290,7 @@ def test_the_driver_records_the_histograms(built, tmp_path):
     for k in range(2):                                                     # (the images are the V planes)
         assert np.array_equal(z["hist_v"][k], region_hist_ref.histograms(images[k], region, -0.125, 0.5, 32)), k
         assert np.array_equal(z["hist_u"][k].sum(axis=2).astype(np.int64), z["cells"]), k
-    r = subprocess.run(base + ["-o", str(without)], cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r = run_program(base + ["-o", str(without)], cwd=ROOT)
     assert r.returncode == 0, r.stderr
     old = np.load(tmp_path / "without.regions.npz")
     keys = {"region", "shape", "steps", "thresholds_v", "thresholds_u", "cells", "quads_v", "feed", "kill"}

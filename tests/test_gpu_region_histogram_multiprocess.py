@@ -3,25 +3,17 @@ region, equal to the single-process result; a rank seam that is no multiple of t
 alike.  All ranks share device 0 through the shared-memory transport double (tests/cpp/shm_transport.cpp, built as
 tests/test_gpu_multiprocess.py builds it)."""
 import os
-import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+
+from tests.children import rank_session, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ROWS, COLS, BINS = 96, 300, 100
 RANGE_U, RANGE_V = (0.0, 1.0), (-0.125, 0.5)
 ALIGNED = {2: [(16, 64), (48, 256)], 3: [(16, 64), (32, 320)]}     # region shapes whose rows every rank seam is a multiple of
 UNALIGNED = {2: (32, 64), 3: (24, 64)}                              # ... and one that a seam (48; 32) is not
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
 
 
 def _planes():
@@ -41,33 +33,26 @@ def _results(species, region):
 
 
 def _worker(rank, world, port, out_dir, transport_lib):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
+    from grayscott_amd import capi
+    from tests.helpers import species_from_arrays
 
-    from grayscott_amd import Parameters, Simulation, capi
-    from tests.helpers import join_ranks, species_from_arrays
-
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, ROWS)
-    sim = Simulation.new(Parameters(), args)
-    u0, v0 = _planes()
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(ROWS, COLS))
-    before = sim.context.stats()
-    got = {}
-    for k, region in enumerate(ALIGNED[world]):
-        for i, a in enumerate(_results(species, region)):
-            got[f"r{k}_{i}"] = a
-    try:
-        species.region_histogram(UNALIGNED[world], BINS, RANGE_U, RANGE_V)
-        refused = 0
-    except capi.GsError as e:
-        refused = e.code
-    for i, a in enumerate(_results(species, ALIGNED[world][0])):           # the context goes on working
-        assert np.array_equal(a, got[f"r0_{i}"])
-    assert sim.context.stats() == before
-    np.savez(os.path.join(out_dir, f"rank{rank}.npz"), refused=np.array(refused), **got)
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
+    with rank_session(rank, world, port, transport_lib, ROWS) as (sim, (r0, r1)):
+        u0, v0 = _planes()
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(ROWS, COLS))
+        before = sim.context.stats()
+        got = {}
+        for k, region in enumerate(ALIGNED[world]):
+            for i, a in enumerate(_results(species, region)):
+                got[f"r{k}_{i}"] = a
+        try:
+            species.region_histogram(UNALIGNED[world], BINS, RANGE_U, RANGE_V)
+            refused = 0
+        except capi.GsError as e:
+            refused = e.code
+        for i, a in enumerate(_results(species, ALIGNED[world][0])):           # the context goes on working
+            assert np.array_equal(a, got[f"r0_{i}"])
+        assert sim.context.stats() == before
+        np.savez(os.path.join(out_dir, f"rank{rank}.npz"), refused=np.array(refused), **got)
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -76,7 +61,7 @@ def test_every_rank_gets_every_region(tmp_path, built, shm_transport, world):
     from tests import region_hist_ref
     from tests.helpers import free_port, species_from_arrays
 
-    mp.spawn(_worker, args=(world, free_port(), str(tmp_path), shm_transport), nprocs=world, join=True)
+    spawn_ranks(_worker, (world, free_port(), str(tmp_path), shm_transport), world)
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
     u0, v0 = _planes()
     species = species_from_arrays(sim, u0, v0)

@@ -1,7 +1,5 @@
 """The simulate driver's regional observables (--hip-regions): <stem>.regions.npz against the restatement applied to the images
 of the HDF5 file, and its feed / kill arrays against the region means of the ramps."""
-import os
-import subprocess
 import sys
 
 import numpy as np
@@ -9,16 +7,16 @@ import pytest
 
 from grayscott_amd import hdf5_min, simulate
 from tests import regions_ref, summary_ref
+from tests.children import ROOT, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_the_driver_writes_the_phase_diagram(built, tmp_path):
     out = tmp_path / "run.h5"
     cmd = [sys.executable, "-m", "grayscott_amd.simulate", "-r", "64", "-c", "128", "-n", "3", "-e", "16", "--hip-feed-map", "0.01:0.06",
            "--hip-kill-map", "0.04:0.07", "--hip-regions", "16x32", "--hip-regions-every", "1", "-o", str(out)]
-    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=120)
+    r = run_program(cmd, cwd=ROOT)
     assert r.returncode == 0, r.stderr
     images = hdf5_min.read(str(out))
     assert images.shape == (3, 64, 128)

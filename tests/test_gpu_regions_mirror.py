@@ -1,29 +1,19 @@
 """The C++ mirror's regional observables (include/grayscott_hip.hpp: Species::region_summaries, Species::region_morphology)
 through tests/cpp/regions_mirror.cpp, against the restatement on the planes the program downloaded."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from tests import regions_ref
+from tests.children import build_program, run_program
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cpp_mirror_regions(built, tmp_path):
-    exe = tmp_path / "regions_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "regions_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("regions_mirror", tmp_path)
     rows, cols, region = 72, 200, (32, 64)
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(rows), str(cols), str(region[0]), str(region[1]), "31", str(out)], capture_output=True,
-                       text=True, timeout=120)
+    r = run_program([str(exe), str(rows), str(cols), str(region[0]), str(region[1]), "31", str(out)])
     assert r.returncode == 0, r.stderr
     raw = out.read_bytes()
     rr, rc = (int(x) for x in np.frombuffer(raw[:16], np.uint64))

@@ -1,17 +1,14 @@
 """Summaries on the device (gs_fields_summarize, gs_members_summarize) against the numpy restatement of their fold order
 (tests/summary_ref.py), bit for bit: sums as f64 bit patterns, min and max as values, equal counts."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
 from grayscott_amd import HipArgs, Parameters, Simulation, capi
 from tests import summary_ref
+from tests.children import build_program, run_program
 from tests.helpers import species_from_arrays, stress_fields
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 RULES = {"clipped": capi.GS_BOUNDARY_CLIPPED, "zero_halo": capi.GS_BOUNDARY_ZERO_HALO,
          "periodic": capi.GS_BOUNDARY_PERIODIC, "neumann": capi.GS_BOUNDARY_NEUMANN}
@@ -193,16 +190,10 @@ def test_sweep_records_summaries_without_changing_the_fields(built, tmp_path):
 
 
 def test_cpp_mirror_summaries(built, tmp_path):
-    exe = tmp_path / "summary_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "summary_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("summary_mirror", tmp_path)
     members, rows, cols = 4, 72, 200
     out = tmp_path / "o.bin"
-    r = subprocess.run([str(exe), str(members), str(rows), str(cols), "31", str(out)], capture_output=True, text=True)
+    r = run_program([str(exe), str(members), str(rows), str(cols), "31", str(out)])
     assert r.returncode == 0, r.stderr
     from grayscott_amd.simulation import SUMMARY_DTYPE
 

@@ -3,46 +3,30 @@ grid, bit for bit the single-process one.  All ranks share device 0 through the 
 (tests/cpp/shm_transport.cpp, built as tests/test_gpu_multiprocess.py builds it), whose messages hold at most 1 MiB: one
 grid's row records exceed that per rank, so the all-gather goes in chunks."""
 import os
-import sys
 
 import numpy as np
 import pytest
-import torch.multiprocessing as mp
+
+from tests.children import rank_session, shm_transport, spawn_ranks  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def shm_transport(built):
-    from tests.helpers import build_shm_transport
-
-    return build_shm_transport()
 
 
 def _worker(rank, world, port, rows, cols, steps, out_dir, transport_lib, local_slabs):
-    sys.path.insert(0, ROOT)
-    import torch.distributed as dist
-
-    from grayscott_amd import Parameters, Simulation
     from grayscott_amd.simulation import SUMMARY_DTYPE
-    from tests.helpers import join_ranks, species_from_arrays, stress_fields
+    from tests.helpers import species_from_arrays, stress_fields
 
-    args, (r0, r1) = join_ranks(rank, world, port, transport_lib, rows, local_slabs)
-    sim = Simulation.new(Parameters(), args)
-    u0, v0 = stress_fields((rows, cols), 4)
-    species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
-    sim.perform_steps(species, steps)
-    u, v = species.summary()
-    in_u = species.in_out()[0]
-    again = in_u.summary(sim.context)             # one plane alone: a second collective call
-    rec = np.zeros(3, SUMMARY_DTYPE)
-    for i, s in enumerate((u, v, again)):
-        rec[i] = (s.sum, s.sum_sq, s.min, s.max, s.nonfinite)
-    np.save(os.path.join(out_dir, f"rank{rank}.npy"), rec)
-    dist.barrier()
-    sim.context.close()
-    dist.destroy_process_group()
+    with rank_session(rank, world, port, transport_lib, rows, local_slabs) as (sim, (r0, r1)):
+        u0, v0 = stress_fields((rows, cols), 4)
+        species = species_from_arrays(sim, u0[r0:r1], v0[r0:r1], shape=(rows, cols))
+        sim.perform_steps(species, steps)
+        u, v = species.summary()
+        in_u = species.in_out()[0]
+        again = in_u.summary(sim.context)             # one plane alone: a second collective call
+        rec = np.zeros(3, SUMMARY_DTYPE)
+        for i, s in enumerate((u, v, again)):
+            rec[i] = (s.sum, s.sum_sq, s.min, s.max, s.nonfinite)
+        np.save(os.path.join(out_dir, f"rank{rank}.npy"), rec)
 
 
 @pytest.mark.parametrize("world,local_slabs,rows,cols,steps", [
@@ -56,8 +40,7 @@ def test_every_rank_gets_the_single_process_summary(tmp_path, built, shm_transpo
     from tests import summary_ref
     from tests.helpers import free_port, species_from_arrays, stress_fields
 
-    mp.spawn(_worker, args=(world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs),
-             nprocs=world, join=True)
+    spawn_ranks(_worker, (world, free_port(), rows, cols, steps, str(tmp_path), shm_transport, local_slabs), world)
     sim = Simulation.new(Parameters(), HipArgs(devices=[0]))
     u0, v0 = stress_fields((rows, cols), 4)
     species = species_from_arrays(sim, u0, v0)

@@ -1,12 +1,10 @@
 """tools/time_stats_rate.py run once at a tiny size: every row it promises is there, with the bytes the rule implies."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, run_rate_tool
 
 
 def test_bytes_per_cell():
@@ -19,16 +17,12 @@ def test_bytes_per_cell():
 
 @pytest.mark.gpu
 def test_the_tool_runs_at_a_tiny_size(built, tmp_path):
-    out, md = tmp_path / "rows.json", tmp_path / "table.md"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "time_stats_rate.py"), "--calls", "2", "--grids", "40x300",
-                        "--json", str(out), "--md", str(md)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    r, table, rows = run_rate_tool("time_stats", ["--calls", "2", "--grids", "40x300"], tmp_path, limit=300)
     assert r.returncode == 0, r.stderr[-2000:]
-    rows = json.load(open(out))
     assert [(x["grid"], x["planes"], x["groups"]) for x in rows] == \
         [("40x300", n, g) for n in (1, 2) for g in ("sum", "sum+squares", "extremes", "all")] + \
         [("512 x 64x128", 2, g) for g in ("sum", "sum+squares", "extremes", "all")]
     for x in rows:
         assert x["accumulate_device_ms"] > 0 and x["copy_ms"] > 0 and x["summary_device_ms"] > 0 and x["host_route_ms"] > 0
         assert x["bytes_per_cell_and_plane"] == {"sum": 20, "sum+squares": 36, "extremes": 20, "all": 68}[x["groups"]]
-    table = open(md).read().splitlines()
     assert table[0].startswith("| grid | planes | groups |") and len(table) == 2 + len(rows)

@@ -9,12 +9,13 @@ Without it, the byte-layout and round-trip tests below still run."""
 import ctypes
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 from grayscott_amd import hdf5_min
+
+from tests.children import run_program
 
 HDF5_DIR = os.environ.get("HDF5_DIR", "/opt/conda")
 H5DUMP = os.path.join(HDF5_DIR, "bin", "h5dump")
@@ -127,12 +128,12 @@ def test_h5dump_reads_our_files(tmp_path, n, layout):
     path, dump = str(tmp_path / "out.h5"), str(tmp_path / "dump.bin")
     shape = (n, 5, 7)
     ref = write(path, shape, layout=layout)
-    header = subprocess.run([H5DUMP, "-p", "-H", path], capture_output=True, text=True, check=True).stdout
+    header = run_program([H5DUMP, "-p", "-H", path], check=True).stdout
     assert 'DATASET "matrix"' in header and "H5T_IEEE_F32LE" in header
     assert f"( {n}, 5, 7 ) / ( {n}, 5, 7 )" in header
     assert ("CHUNKED ( 1, 5, 7 )" if layout == "chunked" else "CONTIGUOUS") in header
     if n:
-        subprocess.run([H5DUMP, "-d", "/matrix", "-b", "LE", "-o", dump, path], capture_output=True, check=True)
+        run_program([H5DUMP, "-d", "/matrix", "-b", "LE", "-o", dump, path], check=True)
         assert np.array_equal(np.fromfile(dump, "<f4").reshape(shape), ref)
 
 

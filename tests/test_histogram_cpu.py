@@ -4,14 +4,12 @@ device, the sweep's flags, the Histogram object's statistics, the Rust declarati
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import hist_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, build_program, run_program
 
 ONE = np.float32(1.0)
 # (lo, hi, bins): the defaults of U and V, one bin, an odd count on a range that is no power of two, the most bins, and a
@@ -177,13 +175,7 @@ def test_rust_ffi_declares_the_histogram_calls():
 
 
 def test_cpp_histogram_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "histogram_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "histogram_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("histogram_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_histogram.py)
-        r = subprocess.run([str(exe), "3", "8", "16", "5", "32", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "3", "8", "16", "5", "32", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

@@ -18,7 +18,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import codeobj  # noqa: E402
 

@@ -16,8 +16,8 @@ from grayscott_amd import capi, simulate
 
 from . import mask_ref as R
 from .helpers import rule_run, stress_fields
+from tests.children import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RULES = [R.CLIPPED, R.ZERO_HALO, R.PERIODIC, R.NEUMANN]
 
 

@@ -4,7 +4,6 @@ of the C ABI, the sweep driver's flags and writer, and the host side of the seam
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -12,8 +11,8 @@ import pytest
 from tests import component_list_ref
 from tests import components_ref
 from tests import match_ref as ref
+from tests.children import ROOT, build_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = components_ref.TILE_ROWS
 # the shapes of tests/test_gpu_match.py's planted planes
 GPU_SHAPES = [(1, 1), (2, 3), (5, 253), (3, 255), (4, 256), (3, 257), (2, 1023), (6, 1025),
@@ -360,25 +359,13 @@ def test_match_merge_on_the_host(tmp_path, sanitize):
     """tests/cpp/match_merge.cpp: pairs of planes cut into 1..5 slabs (one-row slabs included), each labelled on the host with
     the shared find / unite, through the index map of the list merge and the overlap fold against the whole planes' match -- a
     stand-alone program, also built with the address and undefined-behaviour sanitizers."""
-    exe = tmp_path / "match_merge"
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror"]
-    if sanitize:
-        cmd += ["-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-    cmd += [os.path.join(ROOT, "tests", "cpp", "match_merge.cpp"), "-o", str(exe)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    exe = build_program("match_merge", tmp_path, library=False, sanitize=sanitize)
+    r = run_program([str(exe)])
     assert r.returncode == 0 and r.stdout.strip() == "ok", r.stderr[-2000:]
 
 
 def test_cpp_match_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "match_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "match_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("match_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_match.py)
-        r = subprocess.run([str(exe), "3", "8", "16", "5", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "3", "8", "16", "5", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

@@ -16,8 +16,8 @@ from oracle import numpy_ref
 
 from . import neumann_ref
 from .helpers import stress_fields
+from tests.children import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import codeobj  # noqa: E402
 

@@ -18,8 +18,8 @@ from grayscott_amd import Parameters, capi, simulate
 
 from . import param_map_ref as R
 from .helpers import oracle_params, rule_run, stress_fields
+from tests.children import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RULES = [R.CLIPPED, R.ZERO_HALO, R.PERIODIC, R.NEUMANN]
 
 

@@ -9,7 +9,8 @@ import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT
+
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 import ratekit  # noqa: E402

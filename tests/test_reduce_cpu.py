@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from tests import reduce_ref
+from tests.children import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("gs_field_reduced_shape", "gs_field_download_reduced", "gs_field_download_reduced_async",
            "gs_field_colormap_reduced")
 FACTORS = (1, 2, 3, 4, 7, 64)

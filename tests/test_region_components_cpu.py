@@ -6,14 +6,13 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import components_ref, morph_ref, observe_cases, region_components_ref, regions_ref
+from tests.children import ROOT, build_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gs_hip.h")
 
 
@@ -209,13 +208,7 @@ def test_simulate_flags():
 
 # ---- the C++ mirror ----------------------------------------------------------------------------------------------------------
 def test_cpp_region_components_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "region_components_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "region_components_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("region_components_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_region_components_mirror.py)
-        r = subprocess.run([str(exe), "64", "128", "16", "32", "5", "8", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "64", "128", "16", "32", "5", "8", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

@@ -5,14 +5,13 @@ import ctypes
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import hist_ref, region_hist_ref, regions_ref
+from tests.children import ROOT, build_program, run_program
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "gs_hip.h")
 
 
@@ -208,13 +207,7 @@ def test_simulate_flags():
 
 # ---- the C++ mirror ----------------------------------------------------------------------------------------------------------
 def test_cpp_region_histogram_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "region_histogram_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "region_histogram_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("region_histogram_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_region_histogram_mirror.py)
-        r = subprocess.run([str(exe), "64", "128", "16", "32", "5", "64", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "64", "128", "16", "32", "5", "64", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

@@ -3,7 +3,6 @@ crops, gs_region_grid and the refusals that need no handle through the built lib
 results, and the driver's flags and region means."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -11,8 +10,7 @@ import pytest
 from grayscott_amd import Morphology, RegionMorphology, RegionSummaries, Summary, capi, simulate
 from grayscott_amd.simulation import quad_measures, region_grid, region_shape, region_sizes
 from tests import morph_ref, regions_ref, summary_ref
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, build_program, run_program
 
 
 def odd_plane(shape, seed):
@@ -162,13 +160,7 @@ def test_region_means_of_the_maps():
 
 # ---- the C++ mirror ----------------------------------------------------------------------------------------------------------
 def test_cpp_regions_mirror_builds_and_fails_loudly_without_gpu(built, tmp_path):
-    exe = tmp_path / "regions_mirror"
-    libdir = os.path.join(ROOT, "grayscott_amd")
-    cmd = ["g++", "-std=c++17", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "regions_mirror.cpp"), "-o", str(exe),
-           "-L", libdir, "-lgs_hip", f"-Wl,-rpath,{libdir}", "-Wl,-rpath,/opt/rocm/lib"]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
+    exe = build_program("regions_mirror", tmp_path)
     if not os.path.exists("/dev/kfd"):  # (with a GPU it runs in tests/test_gpu_regions_mirror.py)
-        r = subprocess.run([str(exe), "64", "128", "16", "32", "5", str(tmp_path / "o.bin")], capture_output=True, text=True)
+        r = run_program([str(exe), "64", "128", "16", "32", "5", str(tmp_path / "o.bin")])
         assert r.returncode == 14 and "HipError" in r.stderr

@@ -8,13 +8,13 @@ import json
 import os
 import re
 import shutil
-import subprocess
 
 import pytest
 
 from grayscott_amd import capi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.children import ROOT, run_program
+
 RUST = os.path.join(ROOT, "rust", "compute_hip")
 
 
@@ -121,7 +121,7 @@ def test_workspace_patch_applies_to_the_reference(tmp_path):
         os.makedirs(os.path.join(tmp_path, os.path.dirname(f)), exist_ok=True)
         with open(os.path.join(tmp_path, f), "w") as out:
             out.write("\n".join(pre) + "\n")
-    p = subprocess.run(["patch", "-p1", "--forward", "--fuzz=0", "-i", patch], cwd=tmp_path, capture_output=True, text=True)
+    p = run_program(["patch", "-p1", "--forward", "--fuzz=0", "-i", patch], cwd=tmp_path)
     assert p.returncode == 0 and "offset" not in p.stdout and "fuzz" not in p.stdout, p.stdout + p.stderr
     sel = _read(tmp_path, "compute/selector/src/lib.rs")
     assert sel.index('feature = "compute_hip"') < sel.index('feature = "compute_gpu_specialized"')

@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 from tests import time_stats_ref as ref
+from tests.children import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SYMBOLS = ("gs_time_stats_create", "gs_time_stats_destroy", "gs_time_stats_reset", "gs_time_stats_accumulate",
            "gs_time_stats_samples", "gs_time_stats_result", "gs_time_stats_download", "gs_members_time_stats_create",
            "gs_members_time_stats_accumulate", "gs_members_time_stats_result")
