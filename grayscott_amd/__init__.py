@@ -21,6 +21,7 @@ from .simulation import (  # noqa: F401
     Components,
     Morphology,
     Parameters,
+    RegionChange,
     RegionComponents,
     RegionCorrelation,
     RegionHistogram,
@@ -36,4 +37,4 @@ from .simulation import (  # noqa: F401
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionComponents", "RegionCorrelation", "RegionHistogram", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionChange", "RegionComponents", "RegionCorrelation", "RegionHistogram", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]

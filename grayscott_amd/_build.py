@@ -80,6 +80,8 @@ UNITS = [
     ("gs_reduce.hip", "gs_reduce_k.o", []),
     # two planes compared (row records of |a - b| in f64, the ensembles' fold): the same float mode, sub-normal cells kept
     ("gs_change.hip", "gs_change_k.o", []),
+    # regional state comparison (a wave per region, or row records and a fold): the same float mode as gs_change.hip
+    ("gs_region_change.hip", "gs_region_change_k.o", []),
     # time statistics (per-cell f64 sums, f32 extremes and u32 crossing counters read, updated and written back per sample):
     # the same float mode, a sub-normal sample counts as the value it is
     ("gs_time_stats.hip", "gs_time_stats_k.o", []),

@@ -29,6 +29,7 @@ GS_UNIQUE_ID_BYTES = 128
 GS_REGION_PAIRS_MAX = 1 << 25  # counters per field of one gs_fields_region_correlation call (include/gs_hip.h)
 GS_REGION_HIST_MAX = 1 << 25  # counters per field of one gs_fields_region_histogram call (include/gs_hip.h)
 GS_REGION_COMPONENTS_MAX = 1 << 20  # results per field of one gs_fields_region_components call (include/gs_hip.h)
+GS_REGION_CHANGE_RECORDS_MAX = 1 << 28  # bytes of row records per slab of one gs_fields_region_compare call (include/gs_hip.h)
 # time statistics (include/gs_hip.h): the groups of accumulators, the result planes and the raw accumulators
 GS_TSTAT_SUM, GS_TSTAT_SQUARES, GS_TSTAT_EXTREMES, GS_TSTAT_CROSSINGS = 1, 2, 4, 8
 GS_TSTAT_MEAN, GS_TSTAT_VARIANCE, GS_TSTAT_MIN, GS_TSTAT_MAX, GS_TSTAT_OCCUPANCY, GS_TSTAT_ARRIVAL = 0, 1, 2, 3, 4, 5
@@ -60,7 +61,7 @@ EXPORTS = (
     "gs_members_set_active", "gs_members_get_active",
     "gs_fields_morphology", "gs_members_morphology",
     "gs_region_grid", "gs_fields_region_summaries", "gs_fields_region_morphology", "gs_fields_region_correlation",
-    "gs_fields_region_histogram", "gs_fields_region_components",
+    "gs_fields_region_histogram", "gs_fields_region_components", "gs_fields_region_compare",
     "gs_fields_correlation", "gs_members_correlation",
     "gs_fields_components", "gs_members_components",
     "gs_field_component_list", "gs_members_component_list", "gs_component_list_view", "gs_component_list_destroy",
@@ -284,6 +285,7 @@ def load() -> ctypes.CDLL:
         "gs_field_download_reduced_async": (i32, [vp, vp, i32, vp]),
         "gs_field_colormap_reduced": (i32, [vp, vp, i32, f32, vp, i32, vp]),
         "gs_fields_compare": (i32, [vp, P(vp), P(vp), i32, P(GsChange)]),
+        "gs_fields_region_compare": (i32, [vp, P(vp), P(vp), i32, i32, i32, P(GsChange)]),
         "gs_members_compare": (i32, [vp, vp, vp, u64, u64, P(GsChange)]),
         "gs_fields_copy": (i32, [vp, P(vp), P(vp), i32]),
         "gs_members_copy": (i32, [vp, vp, vp, u64, u64]),

@@ -335,6 +335,24 @@ hipError_t gs_launch_region_hist(const float *const *planes, int np, int64_t pit
                                  int32_t rw, const float *lo, const float *hi, const float *scale, int32_t bins,
                                  int64_t max_groups, unsigned long long *out, hipStream_t s);
 
+// Regional state comparison (gs_region_change.hip; include/gs_hip.h: gs_fields_region_compare).  n (1..4) pairs (a[p], b[p])
+// of planes of one slab, all 16-byte aligned with a pitch that is a multiple of 4, and regions as for
+// gs_launch_region_summary.  The launch leaves out[(p * rr + i) * rc + j]: the whole change of region (i, j) of pair p -- d as
+// gs_launch_row_change forms it, the fold order of gs_hip.h with columns counted from the region's first column, the region's
+// rows added in ascending order from +0.0.  With `records` null a wave takes a whole region (the wave route; `out` needs no
+// initial contents); else `out` must hold zeros and `records` gs_region_change_record_bytes(...) bytes: the kernel leaves a
+// 16-byte record per (pair, row, region column) there and a second launch folds them (the record route).  The bits are the
+// same.  gs_region_change_wants_records: the library's choice between the two -- the record route where the region is at
+// least two bands high and the wave route's waves (rows of the region grid x groups of regions side by side in 256 columns)
+// number fewer than kRegionChangeWavesPerCu per compute unit.
+constexpr int kRegionChangeUnroll = 4;      // rows (narrow regions) or chunks of 256 columns (wide ones) of BOTH planes loaded before the adds
+constexpr int kRegionChangeBand = 16;       // rows of a unit of the record route
+constexpr int kRegionChangeWavesPerCu = 4;  // a wave on each of a CU's 4 SIMDs: from there on the wave route is the faster one (profiles/region_change.md)
+bool gs_region_change_wants_records(int64_t rows, int32_t cols, int32_t rh, int32_t rw, int cu_count);
+size_t gs_region_change_record_bytes(int n, int64_t rows, int32_t cols, int32_t rw);
+hipError_t gs_launch_region_change(const float *const *a, const float *const *b, int n, int64_t pitch, int64_t rows, int32_t cols,
+                                   int32_t rh, int32_t rw, GsChangeTotal *out, void *records, hipStream_t s);
+
 // Connected components (gs_components.hip; include/gs_hip.h: gs_fields_components).  `planes` planes of rows x cols cells,
 // `stride` floats apart, rows `pitch` floats apart, thresholded at `threshold` with `sense` as for gs_launch_quads and
 // labelled under `connectivity` (4 or 8); a component never leaves its plane.  parent and size hold one u32 per cell of all

@@ -43,12 +43,16 @@
 //               The regions' components (gs_fields_region_components; gs_region_components.hip) are labelled slab by slab in
 //               label memory that lives for the call alone, the regions' borders as walls, and tallied per region into the
 //               same layout: nt results of 35 counters per region.
+//               The regions' changes against a second field list (gs_fields_region_compare; gs_region_change.hip) travel as the
+//               summaries do: a gs_change per region, by a wave per region or through row records behind the slab's results.
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
 #include "gs_components_merge.h"
 #include "gs_match_merge.h"
 
+#include <cstdlib>
+#include <cstring>
 #include <memory>
 
 using namespace gsi;
@@ -1667,6 +1671,48 @@ int32_t gs_fields_region_components(gs_ctx *ctx, gs_field *const *fields, int32_
                 if (e != hipSuccess) return e;
             }
         return hipSuccess;
+    });
+}
+
+int32_t gs_fields_region_compare(gs_ctx *ctx, gs_field *const *a, gs_field *const *b, int32_t n, int32_t rh, int32_t rw, gs_change *out)
+{
+    if (!ctx || !a || !b || !out) return fail(GS_ERR_INVALID, "null argument");
+    uint64_t RR, RC;
+    GS_TRY(region_grid(0, 0, rh, rw, &RR, &RC)); // the region shape alone; no handle is looked at down to check_planes
+    // the route switch of gs_hip.h: read at every call, before any device work
+    int forced = 0; // 0: the library's choice, 1: records, 2: wave
+    if (const char *route = std::getenv("GS_HIP_REGION_CHANGE_ROUTE")) {
+        if (!std::strcmp(route, "records")) forced = 1;
+        else if (!std::strcmp(route, "wave")) forced = 2;
+        else if (*route) return fail(GS_ERR_INVALID, "GS_HIP_REGION_CHANGE_ROUTE=%s (records, wave or unset)", route);
+    }
+    GS_TRY(check_planes(ctx, a, n, b));
+    const gs_field *f0 = a[0];
+    GS_TRY(region_grid(f0->rows, f0->cols, rh, rw, &RR, &RC));
+    if (RR * RC == 0) return GS_OK; // an empty plane has no regions; the same shape on every rank: nobody exchanges anything
+    GS_TRY(check_band_seams(ctx, f0, rh)); // every rank reaches the same verdict before anybody allocates
+    // a region's result is gs_change's layout: the results land in `out` as they are.  The record route's records lie behind
+    // a slab's results in its scratch buffer, which is made large enough here: band_results then finds it so and keeps it.
+    static_assert(sizeof(GsChangeTotal) == sizeof(gs_change), "region result layout");
+    const size_t nslab = ctx->slabs.size();
+    std::vector<size_t> records_at(nslab, (size_t)0); // offset of a slab's records in its scratch buffer; 0: the wave route
+    for (size_t i = 0; i < nslab; ++i) {
+        const int64_t rows = (int64_t)f0->s[i].rows;
+        if (rows == 0) continue;
+        const bool want = forced == 1 || (forced == 0 && gs_region_change_wants_records(rows, (int32_t)f0->cols, rh, rw, ctx->cu_count));
+        const size_t rec_bytes = gs_region_change_record_bytes(n, rows, (int32_t)f0->cols, rw);
+        if (!want || rec_bytes > (size_t)GS_REGION_CHANGE_RECORDS_MAX) continue;
+        const size_t results = (size_t)n * (size_t)(((uint64_t)rows + (uint64_t)rh - 1) / (uint64_t)rh) * (size_t)RC * sizeof(gs_change);
+        records_at[i] = (results + 255) / 256 * 256;
+        GS_TRY(ensure_scratch(ctx, (int)i, records_at[i] + rec_bytes, "region comparison"));
+    }
+    return band_results(ctx, f0, n, rh, RR, RC, sizeof(gs_change), true, "region comparison", reinterpret_cast<unsigned char *>(out),
+                        [&](size_t i, unsigned char *dev, hipStream_t s) {
+        const float *pa[4], *pb[4];
+        slab_planes(a, n, i, pa);
+        slab_planes(b, n, i, pb);
+        return gs_launch_region_change(pa, pb, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw,
+                                       reinterpret_cast<GsChangeTotal *>(dev), records_at[i] ? dev + records_at[i] : nullptr, s);
     });
 }
 

@@ -49,6 +49,12 @@ as [samples, nt, RR, RC, 4, L + 1] and ``corr_lags`` = L -- the wavelength axis 
 (``gs_fields_region_components``, a region's border being a wall) at the same thresholds: ``components_v`` (and
 ``components_u`` with ``--hip-region-threshold-u``) as [samples, nt, RR, RC, 35] uint64 -- components, set_cells, largest,
 by_size[32] -- and ``comp_connectivity``: how many spots every region holds, how large, and whether one percolates it.
+``--hip-region-change`` (needs ``--hip-regions``) adds the regions' change over the last image interval
+(``gs_fields_region_compare``): image k against image k - 1 (the initial state for k = 1), the earlier state being a device
+snapshot that is taken only before an interval that ends in an observed image -- ``change_{sum_abs,sum_sq,max_abs,differing,
+nonfinite}_{u,v}`` as [samples, RR, RC] and ``change_steps``, the interval in steps.  ``--hip-region-steady-tol T`` (finite, at
+least 0; needs ``--hip-region-change``) adds ``steady`` [samples, RR, RC], bool: neither U nor V moved by more than T in any cell of
+the region and no cell is non-finite.  The run is not ended early on it.
 
 Time statistics (``gs_time_stats``): ``--hip-time-stats-every N`` samples U and V every N steps -- from step S on with
 ``--hip-time-stats-from S`` (default N; 0: the initial state too), at steps S, S + N, ..., each stamped with its step count -- into per-cell accumulators on
@@ -102,6 +108,10 @@ def parse(argv=None):
         ap.error("--hip-region-hist-bins needs --hip-regions")
     if args.hip_region_components is not None and args.hip_regions is None:
         ap.error("--hip-region-components needs --hip-regions")
+    if args.hip_region_change and args.hip_regions is None:
+        ap.error("--hip-region-change needs --hip-regions")
+    if args.hip_region_steady_tol is not None and not args.hip_region_change:
+        ap.error("--hip-region-steady-tol needs --hip-region-change")
     for name in ("u", "v"):
         if getattr(args, f"hip_region_hist_range_{name}") is not None and args.hip_region_hist_bins is None:
             ap.error(f"--hip-region-hist-range-{name} needs --hip-region-hist-bins")
@@ -220,6 +230,16 @@ def _hist_range(text: str):
     return lo, hi
 
 
+def _tolerance(text: str) -> float:
+    try:
+        value = float(text)
+    except ValueError:
+        value = -1.0
+    if not (np.isfinite(value) and value >= 0.0):
+        raise argparse.ArgumentTypeError(f"a finite tolerance of at least 0, not {text!r}")
+    return value
+
+
 def _positive(text: str) -> int:
     try:
         value = int(text)
@@ -248,6 +268,12 @@ def add_region_args(ap: argparse.ArgumentParser) -> None:
     rg.add_argument("--hip-region-components", type=int, choices=(4, 8), nargs="?", const=8, default=None, metavar="4|8",
                     help="also the regions' connected components of V (and of U with --hip-region-threshold-u) at the region "
                          "thresholds under connectivity 4 or 8 (8 without a value; needs --hip-regions)")
+    rg.add_argument("--hip-region-change", action="store_true",
+                    help="also the regions' change of U and V over the last image interval, against a device snapshot "
+                         "(needs --hip-regions)")
+    rg.add_argument("--hip-region-steady-tol", type=_tolerance, default=None, metavar="T",
+                    help="also `steady`: the regions in which neither U nor V moved by more than T over that interval "
+                         "(finite, at least 0; needs --hip-region-change)")
     rg.add_argument("--hip-region-hist-range-u", type=_hist_range, default=None, metavar="A:B",
                     help="the range of U's histograms (default 0:1; needs --hip-region-hist-bins)")
     rg.add_argument("--hip-region-hist-range-v", type=_hist_range, default=None, metavar="A:B",
@@ -353,11 +379,18 @@ class RegionLog:
     """What ``--hip-regions`` collects, one entry per observed image, and the file it becomes."""
 
     SUMMARY_KEYS = ("sum", "sum_sq", "min", "max", "nonfinite")
+    CHANGE_KEYS = ("sum_abs", "sum_sq", "max_abs", "differing", "nonfinite")
 
-    def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None, hist=None, components=None):
+    def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None, hist=None, components=None, change=False,
+                 steady_tol=None):
         """``hist``: None, or (bins, U's (lo, hi), V's (lo, hi)) -- a range that is None is (0, 1).  ``components``: None, or
-        the connectivity (4 or 8) of the regions' connected components."""
+        the connectivity (4 or 8) of the regions' connected components.  ``change``: also the regions' change over the last
+        image interval (``before_interval`` takes the earlier state); ``steady_tol``: None, or the tolerance of ``steady``."""
         self.region = region
+        self.change, self.change_steps, self.snapshot = bool(change), None, None
+        self.steady_tol = None if steady_tol is None else float(steady_tol)
+        if self.steady_tol is not None and not self.change:
+            raise ValueError("--hip-region-steady-tol needs --hip-region-change")
         self.components = None if components is None else int(components)
         self.corr_lags = corr_lags
         self.hist = None if hist is None else (int(hist[0]), tuple(hist[1] or (0.0, 1.0)), tuple(hist[2] or (0.0, 1.0)))
@@ -366,6 +399,22 @@ class RegionLog:
         if self.thresholds_u is not None and len(self.thresholds_u) != len(self.thresholds_v):
             raise ValueError("--hip-region-threshold-u wants as many thresholds as --hip-region-threshold-v")
         self.steps, self.rows = [], {}
+
+    def before_interval(self, species, steps: int) -> None:
+        """With ``change``: keep the current state on the device (blocking), to compare the state ``steps`` steps on with.
+        Called only before an interval that ends in an observed image."""
+        if not self.change:
+            return
+        if self.snapshot is None:
+            self.snapshot = species.snapshot()
+        else:
+            self.snapshot.update(species)
+        self.change_steps = int(steps)
+
+    def close(self) -> None:
+        if self.snapshot is not None:
+            self.snapshot.close()
+            self.snapshot = None
 
     def observe(self, species, step: int) -> None:
         su, sv = species.region_summaries(self.region)
@@ -393,6 +442,15 @@ class RegionLog:
             self.rows.setdefault("components_v", []).append(np.stack([c.counters() for c in cv]))  # the C ABI's 35 words
             if cu:
                 self.rows.setdefault("components_u", []).append(np.stack([c.counters() for c in cu]))
+        if self.change:
+            if self.snapshot is None:
+                raise RuntimeError("no earlier state to compare with: before_interval was not called")
+            du, dv = species.region_changes_since(self.snapshot, self.region)
+            for name, d in (("u", du), ("v", dv)):
+                for key in self.CHANGE_KEYS:
+                    self.rows.setdefault(f"change_{key}_{name}", []).append(getattr(d, key))
+            if self.steady_tol is not None:
+                self.rows.setdefault("steady", []).append(du.steady(self.steady_tol) & dv.steady(self.steady_tol))
 
     def save(self, path: str, shape, pmap=None) -> None:
         out = {"region": np.array(self.region, np.int64), "shape": np.array(shape, np.int64), "steps": np.array(self.steps, np.int64),
@@ -406,6 +464,10 @@ class RegionLog:
             out["hist_range_v"] = np.array(self.hist[2], np.float64)
         if self.components is not None:
             out["comp_connectivity"] = np.array(self.components, np.int64)
+        if self.change:
+            out["change_steps"] = np.array(self.change_steps or 0, np.int64)
+        if self.steady_tol is not None:
+            out["steady_tol"] = np.array(self.steady_tol, np.float64)
         for key, rows in self.rows.items():
             out[key] = rows[0] if key == "cells" else np.stack(rows)
         if pmap is not None:
@@ -534,7 +596,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     region = getattr(args, "hip_regions", None)
     regions = RegionLog(region, getattr(args, "hip_region_threshold_v", None), getattr(args, "hip_region_threshold_u", None),
                         getattr(args, "hip_region_corr_lags", None), region_hist_args(args),
-                        getattr(args, "hip_region_components", None)) if region else None
+                        getattr(args, "hip_region_components", None), getattr(args, "hip_region_change", False),
+                        getattr(args, "hip_region_steady_tol", None)) if region else None
     mask = domain_mask(args, shape)
     sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)
@@ -600,6 +663,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
             image = free.get()
             if failed.is_set() or image is None:
                 break
+            if regions is not None and regions_observed(index, args.nbimage, getattr(args, "hip_regions_every", None)):
+                regions.before_interval(species, steps_per_image)  # (--hip-region-change: blocking, a device copy)
             if stats is None:
                 sim.prepare_steps(species, steps_per_image)  # enqueued; nothing here waits for the device
             else:                                           # the same steps, cut where a sample falls
@@ -630,6 +695,8 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
         full.put(None)
         thread.join()
         ctx.sync()
+        if regions is not None:
+            regions.close()
     elapsed = time.perf_counter() - t0
     if errors:
         raise errors[0]

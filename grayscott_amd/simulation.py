@@ -637,6 +637,74 @@ class RegionMorphology:
         return Morphology.from_quads(self.quads[i, j], self.threshold, self.above, int(self.cells[i, j]))
 
 
+@dataclass(frozen=True, eq=False)
+class RegionChange:
+    """The change of every region of one plane against another of the same shape, computed on the device
+    (``gs_fields_region_compare``): arrays of shape ``(RR, RC)``, entry (i, j) being bit for bit the ``Change`` of two planes
+    that hold region (i, j)'s cells alone.  ``region`` is ``(rh, rw)``, ``shape`` the planes', ``size`` every region's
+    number of cells."""
+
+    sum_abs: np.ndarray
+    sum_sq: np.ndarray
+    max_abs: np.ndarray
+    differing: np.ndarray
+    nonfinite: np.ndarray
+    size: np.ndarray
+    region: Tuple[int, int]
+    shape: Tuple[int, int]
+
+    @classmethod
+    def from_records(cls, rec: np.ndarray, region, shape) -> "RegionChange":
+        """From ``(RR, RC)`` records of ``CHANGE_DTYPE`` as the C ABI writes them."""
+        region, shape = region_shape(region), (int(shape[0]), int(shape[1]))
+        return cls(rec["sum_abs"].copy(), rec["sum_sq"].copy(), rec["max_abs"].copy(), rec["differing"].copy(),
+                   rec["nonfinite"].copy(), region_sizes(shape[0], shape[1], region, rec.shape), region, shape)
+
+    @property
+    def comparable(self) -> np.ndarray:
+        """Cells per region where both planes are finite: the ones the sums and the maximum cover."""
+        return self.size - self.nonfinite.astype(np.int64)
+
+    def mean_abs(self) -> np.ndarray:
+        """Per region, as ``Change.mean_abs``: NaN where a region has no comparable cell."""
+        cells = self.comparable.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cells > 0, self.sum_abs / cells, np.nan)
+
+    def rms(self) -> np.ndarray:
+        """Per region, as ``Change.rms``: NaN where a region has no comparable cell."""
+        cells = self.comparable.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(cells > 0, np.sqrt(self.sum_sq / cells), np.nan)
+
+    def steady(self, tol: float) -> np.ndarray:
+        """Per region: no comparable cell moved by more than ``tol`` and every cell is comparable."""
+        return (self.max_abs <= float(tol)) & (self.nonfinite == 0)
+
+    def at(self, i: int, j: int) -> Change:
+        return Change(float(self.sum_abs[i, j]), float(self.sum_sq[i, j]), float(self.max_abs[i, j]), int(self.differing[i, j]),
+                      int(self.nonfinite[i, j]), int(self.size[i, j]))
+
+
+def region_compare_fields(context: "HipContext", a: Sequence["HipConcentration"], b: Sequence["HipConcentration"],
+                          region) -> List[RegionChange]:
+    """``gs_fields_region_compare``: the change of every region of plane ``a[i]`` against ``b[i]`` for 1..4 pairs of one
+    shape in one call (blocking; collective in a multi-process context).  ``region`` is ``(rh, rw)`` or an int for a square
+    region."""
+    if len(a) != len(b):
+        raise ValueError("one second plane per first plane")
+    n, (rh, rw) = len(a), region_shape(region)
+    shape = a[0].shape() if a else (0, 0)
+    try:
+        grid = region_grid(shape[0], shape[1], (rh, rw))
+    except capi.GsError:
+        grid = (0, 0)  # (the call below refuses it, in the header's order)
+    out = np.zeros((max(n, 1),) + grid, CHANGE_DTYPE)
+    capi.check(context._lib.gs_fields_region_compare(context.handle, _handle_array(a), _handle_array(b), n, rh, rw,
+                                                     out.ctypes.data_as(ctypes.POINTER(capi.GsChange))))
+    return [RegionChange.from_records(out[i], (rh, rw), shape) for i in range(n)]
+
+
 def region_summaries_fields(context: "HipContext", fields: Sequence["HipConcentration"], region) -> List[RegionSummaries]:
     """``gs_fields_region_summaries``: the summaries of every region of 1..4 planes of one shape in one call (blocking;
     collective in a multi-process context).  ``region`` is ``(rh, rw)`` or an int for a square region."""
@@ -1550,6 +1618,12 @@ class HipConcentration:
         computed on the device (``gs_fields_compare``; blocking, collective in a multi-process context)."""
         return compare_fields(context, [self], [other])[0]
 
+    def region_change_from(self, context: HipContext, other: "HipConcentration", region) -> RegionChange:
+        """How far every region of ``region`` = (rh, rw) cells (an int: square) of this plane is from the same region of
+        ``other`` (this minus other), computed on the device (``gs_fields_region_compare``; blocking, collective in a
+        multi-process context)."""
+        return region_compare_fields(context, [self], [other], region)[0]
+
     def destroy(self) -> None:
         if self._h and self._ctx._h:
             self._ctx._lib.gs_field_destroy(self._ctx._h, self._h)
@@ -1945,6 +2019,14 @@ class Species:
         (``gs_fields_compare``; blocking, collective in a multi-process context)."""
         in_u, in_v, _, _ = self.in_out()
         u, v = compare_fields(self._context, [in_u, in_v], [snapshot.u, snapshot.v])
+        return u, v
+
+    def region_changes_since(self, snapshot: Snapshot, region) -> Tuple[RegionChange, RegionChange]:
+        """(U, V): how far every region of the current state is from the same region of ``snapshot`` (current minus
+        snapshot), in one call (``gs_fields_region_compare``; blocking, collective in a multi-process context): the region
+        shape as for ``region_summaries``."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = region_compare_fields(self._context, [in_u, in_v], [snapshot.u, snapshot.v], region)
         return u, v
 
     def restore(self, snapshot: Snapshot) -> None:

@@ -235,6 +235,16 @@ struct Components {
 };
 // (gs_fields_region_components): `at(i, j)` is the Components of region (i, j)'s cells alone -- a region's border is a wall
 using RegionComponents = Regions<Components>; // of one threshold
+// (gs_fields_region_compare): `at(i, j)` is the Change of two planes that hold region (i, j)'s cells alone, `cells` the region's
+struct RegionChange : Regions<Change> {
+    // per region: no comparable cell moved by more than tol, and every cell is comparable
+    std::vector<bool> steady(double tol) const
+    {
+        std::vector<bool> out;
+        for (const Change &c : results) out.push_back(c.max_abs <= tol && c.nonfinite == 0);
+        return out;
+    }
+};
 
 // The two-point pair counts of one thresholded plane, counted on the device (gs_fields_correlation; the rule is gs_hip.h's):
 // pairs[k][d] is the number of cell pairs {p, p + d e_k}, d = 0 .. max_lag, inside the grid with both cells set, for the unit
@@ -850,6 +860,29 @@ class Species {
         check(gs_fields_compare(context_->get(), a, b, 2, out));
         const Shape s = shape();
         return {Change::from_c(out[0], s[0] * s[1]), Change::from_c(out[1], s[0] * s[1])};
+    }
+    // (U, V): how far every region of rh x rw cells of the current state is from the same region of the snapshot (current
+    // minus snapshot), in one call (gs_fields_region_compare; blocking, collective in a multi-process context)
+    std::pair<RegionChange, RegionChange> region_changes_since(const Snapshot &snap, int32_t rh, int32_t rw)
+    {
+        gs_field *a[2] = {u_.in().raw(), v_.in().raw()}, *b[2] = {snap.u_.raw(), snap.v_.raw()};
+        const Shape s = shape();
+        uint64_t rr = 0, rc = 0;
+        check(gs_region_grid(s[0], s[1], rh, rw, &rr, &rc));
+        const std::size_t regions = (std::size_t)(rr * rc);
+        std::vector<gs_change> out(2 * regions + 1);
+        check(gs_fields_region_compare(context_->get(), a, b, 2, rh, rw, out.data()));
+        std::pair<RegionChange, RegionChange> uv;
+        RegionChange *both[2] = {&uv.first, &uv.second};
+        for (std::size_t p = 0; p < 2; ++p) {
+            both[p]->rr = rr;
+            both[p]->rc = rc;
+            both[p]->rh = rh;
+            both[p]->rw = rw;
+            for (std::size_t r = 0; r < regions; ++r)
+                both[p]->results.push_back(Change::from_c(out[p * regions + r], detail::region_cells(s[0], s[1], rh, rw, r / rc, r % rc)));
+        }
+        return uv;
     }
     // go back to the snapshot: its planes are copied into the current in-planes (gs_fields_copy; blocking), and the next
     // perform_steps continues from the snapshot's bits

@@ -1029,6 +1029,42 @@ int32_t gs_members_compare(gs_ctx *ctx, gs_ensemble *e, gs_ensemble *ref, uint64
 int32_t gs_fields_copy(gs_ctx *ctx, gs_field *const *dst, gs_field *const *src, int32_t n);
 int32_t gs_members_copy(gs_ctx *ctx, gs_ensemble *dst, gs_ensemble *src, uint64_t first, uint64_t count);
 
+/* Regional state comparison: the change of every REGION of the region grid of gs_region_grid (above) between two planes of one
+ * shape -- which part of a parameter map's grid is steady, which pulsates, which is chaotic; the whole-grid comparison of such
+ * a grid blends them into one number that belongs to none -- without downloading either plane.
+ * The rule that defines every result is the regional family's: a region's result is, bit for bit, what gs_fields_compare
+ * returns for two fields that hold exactly that region's cells.  That is: d = (double)a - (double)b, comparable cells,
+ * `differing` and `nonfinite` as defined above; the summaries' fold order with columns counted from the region's FIRST
+ * column -- lane l adds the region's columns 256 k + 4 l + j --; the halving lane combine, in which the lanes past the
+ * region hold +0.0; the region's rows added in ascending order from +0.0.  max_abs and the two counts are order-free.
+ * Ragged last rows and columns of regions are kept.  The results are the same bits for any slab count, process count, step
+ * kernel, launch shape or route (below) and do not depend on the boundary rule; with a domain mask attached wall cells count.
+ *   gs_fields_region_compare  out[p * RR RC + i RC + j] is the change of region (i, j) of the pair (a[p], b[p]), p < n (1..4
+ *                             pairs, all planes of one shape on this context).  a[p] == b[p] is allowed: all zeros.
+ * The call waits once for enqueued work (as gs_fields_summarize: a persistent window launch that gave up is run again first),
+ * blocks, and has no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  In a multi-process context
+ * it is collective, like gs_run, and every rank receives every region.  An empty plane: GS_OK, nothing is written.
+ * Two routes compute the same bits, and the library chooses per slab from the slab's shape, the region shape and the device's
+ * compute-unit count alone:
+ *   wave     a wave takes a whole region (several narrow ones side by side in 256 columns) and adds its rows in registers:
+ *            no memory but the result.  Chosen for many small regions.
+ *   records  a wave takes a band of 16 rows of a region and leaves a 16-byte record per (row, region column); a second launch
+ *            adds every region's records in row order.  Chosen where a wave per region would leave the device underfilled:
+ *            a region at least 32 rows high AND fewer wave-route waves -- rows of the region grid x ceil(RC / s), s = the
+ *            regions that fit side by side in 256 columns, 1 from rw = 256 -- than 4 per compute unit (one per SIMD: with
+ *            that many the wave route measures faster, profiles/region_change.md).  Record memory, rows x RC x 16 bytes per pair and slab, comes from the context's
+ *            scratch buffer; where one slab's would exceed GS_REGION_CHANGE_RECORDS_MAX bytes the call takes the wave route.
+ * The environment variable GS_HIP_REGION_CHANGE_ROUTE, read at every call, forces a route for tests and measurements:
+ * `records` (still subject to that cap), `wave`; unset or empty: the library's choice; anything else: GS_ERR_INVALID.
+ * Refusals, all decided before any device work -- GS_ERR_INVALID, in this order: a null argument; an rh or rw that
+ * gs_region_grid refuses (both decided before any handle is looked at); a null or foreign handle, mixed shapes, n outside
+ * 1..4; RR RC > GS_REGIONS_MAX.  GS_ERR_UNSUPPORTED, on every rank alike: a context of several slabs or processes in which
+ * some slab begins at a row that is no multiple of rh (a region lies inside one slab).
+ * Not done: regions of ensemble members; regions that straddle slabs; ending a run early on the regions' verdict. */
+#define GS_REGION_CHANGE_RECORDS_MAX (1ull << 28)
+int32_t gs_fields_region_compare(gs_ctx *ctx, gs_field *const *a, gs_field *const *b, int32_t n, int32_t rh, int32_t rw,
+                                 gs_change *out);
+
 /* Time statistics formed on the device: per-cell accumulators over the SAMPLES of a run -- is a cell steady, pulsating or
  * chaotic (variance), what does the time-averaged field look like (mean), where has a spot been (maximum), when did the front
  * arrive (first crossing of a threshold), for what share of the time was a cell inside a spot (occupancy) -- without

@@ -284,6 +284,16 @@ extern "C" {
         n: i32,
         out: *mut gs_change,
     ) -> i32;
+    /// `out`: n x RR x RC records: the change of every region of rh x rw cells of a[p] against b[p].
+    pub fn gs_fields_region_compare(
+        ctx: *mut gs_ctx,
+        a: *const *mut gs_field,
+        b: *const *mut gs_field,
+        n: i32,
+        rh: i32,
+        rw: i32,
+        out: *mut gs_change,
+    ) -> i32;
     /// `out`: count x 2 records (U, V) of members first + i of `e` against the same members of `reference`.
     pub fn gs_members_compare(
         ctx: *mut gs_ctx,
