@@ -30,11 +30,13 @@ from .simulation import (  # noqa: F401
     Simulation,
     Snapshot,
     Species,
+    Spectrum,
     Summary,
     TimeStats,
     correlation_fields,
     pinned_empty,
+    spectrum_fields,
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionChange", "RegionComponents", "RegionCorrelation", "RegionHistogram", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Summary", "TimeStats", "correlation_fields", "pinned_empty"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionChange", "RegionComponents", "RegionCorrelation", "RegionHistogram", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Spectrum", "Summary", "TimeStats", "correlation_fields", "pinned_empty", "spectrum_fields"]

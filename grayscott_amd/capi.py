@@ -63,6 +63,7 @@ EXPORTS = (
     "gs_region_grid", "gs_fields_region_summaries", "gs_fields_region_morphology", "gs_fields_region_correlation",
     "gs_fields_region_histogram", "gs_fields_region_components", "gs_fields_region_compare",
     "gs_fields_correlation", "gs_members_correlation",
+    "gs_spectrum_tables", "gs_fields_spectrum", "gs_members_spectrum",
     "gs_fields_components", "gs_members_components",
     "gs_field_component_list", "gs_members_component_list", "gs_component_list_view", "gs_component_list_destroy",
     "gs_fields_match", "gs_members_match", "gs_component_match_view", "gs_component_match_destroy",
@@ -311,6 +312,9 @@ def load() -> ctypes.CDLL:
         "gs_component_match_destroy": (i32, [vp]),
         "gs_fields_correlation": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, i32, P(u64)]),
         "gs_members_correlation": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, i32, P(u64)]),
+        "gs_spectrum_tables": (i32, [i32, P(f32), P(f32)]),
+        "gs_fields_spectrum": (i32, [vp, P(vp), i32, i32, i32, P(ctypes.c_double), P(u64)]),
+        "gs_members_spectrum": (i32, [vp, vp, u64, u64, i32, i32, P(ctypes.c_double), P(u64)]),
         "gs_time_stats_create": (i32, [vp, P(vp), u64, u64, i32, u32, P(f32), P(i32)]),
         "gs_time_stats_destroy": (i32, [vp, vp]),
         "gs_time_stats_reset": (i32, [vp, vp]),

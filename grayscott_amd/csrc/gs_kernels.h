@@ -353,6 +353,19 @@ size_t gs_region_change_record_bytes(int n, int64_t rows, int32_t cols, int32_t 
 hipError_t gs_launch_region_change(const float *const *a, const float *const *b, int n, int64_t pitch, int64_t rows, int32_t cols,
                                    int32_t rh, int32_t rw, GsChangeTotal *out, void *records, hipStream_t s);
 
+// Power spectra (gs_spectrum.hip; include/gs_hip.h: gs_fields_spectrum).  np (1..4) planes of one shape repeated `repeat` times
+// `stride` floats apart (gs_plane_scan.h's set), tiles of `tile` (16, 32, 64, 128) cells a side anchored at row 0 and column
+// 0, `window` != 0: the window h[tile] is applied; w: the tile / 2 twiddles as (re, im) pairs.  The launches -- a workgroup
+// per segment of 16 tiles writes a record into `records` (gs_spectrum_record_bytes(...) bytes, no initial contents), a fold
+// adds a band's records -- leave out[plane * ceil(rows / tile) + band]: a result of gs_spectrum_result_bytes(tile) bytes, the
+// band's tile (tile / 2 + 1) f64 sums and the tiles {used, skipped} as u64; zeros for the band of the rows below the last
+// whole one.
+constexpr size_t gs_spectrum_result_bytes(int32_t tile) { return ((size_t)tile * (size_t)(tile / 2 + 1) + 2) * 8; }
+size_t gs_spectrum_record_bytes(int64_t planes, int64_t rows, int32_t cols, int32_t tile);
+hipError_t gs_launch_spectrum(const float *const *planes, int np, int64_t repeat, int64_t stride, int64_t pitch, int64_t rows,
+                              int32_t cols, int32_t tile, int32_t window, const float *h, const float *w, void *records,
+                              void *out, hipStream_t s);
+
 // Connected components (gs_components.hip; include/gs_hip.h: gs_fields_components).  `planes` planes of rows x cols cells,
 // `stride` floats apart, rows `pitch` floats apart, thresholded at `threshold` with `sense` as for gs_launch_quads and
 // labelled under `connectivity` (4 or 8); a component never leaves its plane.  parent and size hold one u32 per cell of all

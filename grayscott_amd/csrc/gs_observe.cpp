@@ -45,6 +45,9 @@
 //               same layout: nt results of 35 counters per region.
 //               The regions' changes against a second field list (gs_fields_region_compare; gs_region_change.hip) travel as the
 //               summaries do: a gs_change per region, by a wave per region or through row records behind the slab's results.
+//   power spectra  (gs_fields_spectrum, gs_members_spectrum; gs_spectrum.hip) a record per segment of 16 tiles behind the slab's
+//               results, added per band of T rows on the device: one result per band travels (band_results) and the host adds
+//               the bands in ascending global order; an ensemble's members are planes of one launch, their bands added here too.
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
@@ -808,9 +811,132 @@ int32_t check_regions(const gs_ctx *ctx, gs_field *const *fields, int32_t n, int
     return GS_OK;
 }
 
+// ---- power spectra ---------------------------------------------------------------------------------------------------------
+// The tile size and the window of a spectrum, or the refusal of gs_hip.h.  No handle is looked at.
+int32_t check_spectrum(int32_t tile, int32_t window)
+{
+    if (tile != 16 && tile != 32 && tile != 64 && tile != 128) return fail(GS_ERR_INVALID, "a tile of %d cells (16, 32, 64 or 128)", tile);
+    if (window != 0 && window != 1) return fail(GS_ERR_INVALID, "window %d (0: none, 1: periodic Hann)", window);
+    return GS_OK;
+}
+
+// The tables of gs_hip.h: formed in f64, rounded to f32.
+void spectrum_tables(int32_t tile, float *window, float *twiddle)
+{
+    const double step = 2.0 * 3.14159265358979323846 / (double)tile;
+    for (int32_t j = 0; window && j < tile; ++j) window[j] = (float)(0.5 - 0.5 * std::cos(step * (double)j));
+    for (int32_t k = 0; twiddle && k < tile / 2; ++k) {
+        twiddle[2 * k] = (float)std::cos(step * (double)k);
+        twiddle[2 * k + 1] = (float)-std::sin(step * (double)k);
+    }
+}
+
+// Band results (gs_spectrum_result_bytes each: the sums, then {used, skipped}) of `planes` planes, [plane][bands], into
+// power[plane][bins] and tiles[plane][2]: the first `whole` bands of a plane added in ascending order from +0.0.
+void fold_bands(const unsigned char *results, size_t planes, size_t bands, size_t whole, int32_t tile, double *power, uint64_t *tiles)
+{
+    const size_t bins = (size_t)tile * (size_t)(tile / 2 + 1), words = bins + 2;
+    for (size_t p = 0; p < planes; ++p) {
+        double *sum = power + p * bins;
+        std::fill(sum, sum + bins, 0.0);
+        tiles[2 * p] = tiles[2 * p + 1] = 0;
+        for (size_t b = 0; b < whole; ++b) {
+            const unsigned char *band = results + (p * bands + b) * words * 8;
+            const double *x = reinterpret_cast<const double *>(band);
+            const uint64_t *c = reinterpret_cast<const uint64_t *>(band) + bins;
+            for (size_t e = 0; e < bins; ++e) sum[e] = sum[e] + x[e];
+            tiles[2 * p] += c[0];
+            tiles[2 * p + 1] += c[1];
+        }
+    }
+}
+
 } // namespace
 
 extern "C" {
+
+int32_t gs_spectrum_tables(int32_t tile, float *window, float *twiddle)
+{
+    GS_TRY(check_spectrum(tile, 0));
+    spectrum_tables(tile, window, twiddle);
+    return GS_OK;
+}
+
+int32_t gs_fields_spectrum(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t tile, int32_t window, double *power,
+                           uint64_t *tiles)
+{
+    GS_TRY(check_spectrum(tile, window));
+    if (!power || !tiles) return fail(GS_ERR_INVALID, "null output");
+    if (!ctx || !fields) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    const size_t bins = (size_t)tile * (size_t)(tile / 2 + 1), elem = gs_spectrum_result_bytes(tile);
+    const uint64_t T = (uint64_t)tile, whole = f0->rows / T, RR = (f0->rows + T - 1) / T;
+    if (whole == 0 || f0->cols < T) { // no tile; the same shape on every rank: nobody exchanges anything
+        std::fill(power, power + (size_t)n * bins, 0.0);
+        std::fill(tiles, tiles + 2 * (size_t)n, (uint64_t)0);
+        return GS_OK;
+    }
+    GS_TRY(check_band_seams(ctx, f0, tile)); // every rank reaches the same verdict before anybody allocates
+    // a slab's segment records lie behind its band results in its scratch buffer, which is made large enough here:
+    // band_results then finds it so and keeps it (the regional comparison's precedent)
+    const size_t nslab = ctx->slabs.size();
+    std::vector<size_t> records_at(nslab, (size_t)0);
+    for (size_t i = 0; i < nslab; ++i) {
+        const uint64_t rows = (uint64_t)f0->s[i].rows;
+        if (rows == 0) continue;
+        const size_t results = (size_t)n * (size_t)((rows + T - 1) / T) * elem;
+        records_at[i] = (results + 255) / 256 * 256;
+        GS_TRY(ensure_scratch(ctx, (int)i, records_at[i] + gs_spectrum_record_bytes(n, (int64_t)rows, (int32_t)f0->cols, tile),
+                              "spectrum"));
+    }
+    float h[128], w[128];
+    spectrum_tables(tile, h, w);
+    std::vector<unsigned char> bands((size_t)n * (size_t)RR * elem);
+    GS_TRY(band_results(ctx, f0, n, tile, RR, 1, elem, false, "spectrum", bands.data(),
+                        [&](size_t i, unsigned char *dev, hipStream_t s) {
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
+        return gs_launch_spectrum(planes, n, 1, 0, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, tile, window, h, w,
+                                  dev + records_at[i], dev, s);
+    }));
+    fold_bands(bands.data(), (size_t)n, (size_t)RR, (size_t)whole, tile, power, tiles);
+    return GS_OK;
+}
+
+int32_t gs_members_spectrum(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, int32_t tile, int32_t window,
+                            double *power, uint64_t *tiles)
+{
+    GS_TRY(check_spectrum(tile, window));
+    if (!power || !tiles) return fail(GS_ERR_INVALID, "null output");
+    if (!ctx) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_members(ctx, e, first, count));
+    const size_t bins = (size_t)tile * (size_t)(tile / 2 + 1), elem = gs_spectrum_result_bytes(tile), planes_n = (size_t)(2 * count);
+    const uint64_t T = (uint64_t)tile, whole = e->rows / T, RR = (e->rows + T - 1) / T;
+    if (whole == 0 || e->cols < T) {
+        std::fill(power, power + planes_n * bins, 0.0);
+        std::fill(tiles, tiles + 2 * planes_n, (uint64_t)0);
+        return GS_OK;
+    }
+    const size_t out_bytes = planes_n * (size_t)RR * elem, records_at = (out_bytes + 255) / 256 * 256;
+    GS_TRY(ensure_scratch(ctx, 0, records_at + gs_spectrum_record_bytes((int64_t)planes_n, (int64_t)e->rows, (int32_t)e->cols, tile),
+                          "spectrum"));
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    unsigned char *dev = static_cast<unsigned char *>(sl.scratch);
+    float h[128], w[128];
+    spectrum_tables(tile, h, w);
+    // U and V of a member are two planes of the set, the next member's `cells` floats further on: plane 2 m + s
+    const float *planes[2];
+    member_planes(e, first, planes);
+    GS_HIP(gs_launch_spectrum(planes, 2, (int64_t)count, (int64_t)(e->rows * e->cols), (int64_t)e->cols, (int64_t)e->rows,
+                              (int32_t)e->cols, tile, window, h, w, dev + records_at, dev, sl.compute));
+    std::vector<unsigned char> bands(out_bytes);
+    GS_HIP(hipMemcpyAsync(bands.data(), dev, out_bytes, hipMemcpyDeviceToHost, sl.compute));
+    GS_HIP(hipStreamSynchronize(sl.compute));
+    fold_bands(bands.data(), planes_n, (size_t)RR, (size_t)whole, tile, power, tiles);
+    return GS_OK;
+}
 
 int32_t gs_fields_summarize(gs_ctx *ctx, gs_field *const *fields, int32_t n, gs_summary *out)
 {

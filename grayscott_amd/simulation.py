@@ -1169,6 +1169,156 @@ def correlation_fields(context: "HipContext", fields: Sequence["HipConcentration
     return [[Correlation.from_pairs(out[i, k], thr[i * nt + k], above[i], rows, cols) for k in range(nt)] for i in range(n)]
 
 
+SPECTRUM_TILES = (16, 32, 64, 128)
+SPECTRUM_WINDOWS = {"none": 0, "hann": 1}
+
+
+def spectrum_tables(tile: int) -> Tuple[np.ndarray, np.ndarray]:
+    """``gs_spectrum_tables``: the periodic Hann window ``h[tile]`` (f32) and the twiddles ``W[tile / 2]`` (complex64) that
+    the device uses (include/gs_hip.h); needs no device."""
+    h = np.zeros(tile, np.float32)
+    w = np.zeros(max(tile // 2, 1) * 2, np.float32)
+    f32p = ctypes.POINTER(ctypes.c_float)
+    capi.check(capi.load().gs_spectrum_tables(int(tile), h.ctypes.data_as(f32p), w.ctypes.data_as(f32p)))
+    return h, w.view(np.complex64)[:tile // 2]
+
+
+def _spectrum_window(window) -> int:
+    if isinstance(window, str):
+        return SPECTRUM_WINDOWS.get(window, -1)
+    return int(window)
+
+
+@dataclass(frozen=True, eq=False)
+class Spectrum:
+    """The tile-averaged power spectrum of one plane, summed on the device (``gs_fields_spectrum``; the rule is
+    include/gs_hip.h's): ``raw[kr, kc]`` is the sum over the whole ``tile`` x ``tile`` tiles of the plane that hold only
+    finite cells of |FFT2(window * (tile - its mean))|^2, kr < tile, kc <= tile / 2 (the other half is its mirror image),
+    ``tiles_used`` and ``tiles_skipped`` count those tiles and the ones left out.  Everything else is computed here.
+    Frequencies are in cycles per cell: f_r = kr / tile folded into [-1/2, 1/2), f_c = kc / tile."""
+
+    raw: np.ndarray
+    tile: int
+    window: int
+    tiles_used: int
+    tiles_skipped: int
+
+    @classmethod
+    def from_raw(cls, raw, tile: int, window, tiles=(1, 0)) -> "Spectrum":
+        tile = int(tile)
+        p = np.array(raw, np.float64).reshape(tile, tile // 2 + 1)
+        return cls(p, tile, _spectrum_window(window), int(tiles[0]), int(tiles[1]))
+
+    @property
+    def window_energy(self) -> float:
+        """The sum of (h_r h_c)^2 over a tile: tile^2 without a window."""
+        if not self.window:
+            return float(self.tile * self.tile)
+        h = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(self.tile) / self.tile)
+        return float(np.sum(h * h) ** 2)
+
+    @property
+    def power(self) -> np.ndarray:
+        """The mean over the tiles used, divided by the window's energy: f64 ``[tile, tile / 2 + 1]``; NaN without a tile."""
+        if self.tiles_used == 0:
+            return np.full(self.raw.shape, np.nan)
+        return self.raw / (self.tiles_used * self.window_energy)
+
+    def frequencies(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(f_r[tile], f_c[tile / 2 + 1]) in cycles per cell; f_r is signed."""
+        T = self.tile
+        k = np.arange(T)
+        return np.where(k < T // 2, k, k - T) / T, np.arange(T // 2 + 1) / T
+
+    def _rings(self) -> Tuple[np.ndarray, np.ndarray]:
+        fr, fc = self.frequencies()
+        ring = np.rint(self.tile * np.sqrt(fr[:, None] ** 2 + fc[None, :] ** 2)).astype(np.int64)
+        kc = np.arange(self.tile // 2 + 1)
+        weight = np.broadcast_to(np.where((kc > 0) & (kc < self.tile // 2), 2.0, 1.0), ring.shape)
+        return ring, weight
+
+    def radial(self) -> np.ndarray:
+        """S(|k|) on rings 0 .. tile / 2: ring round(tile sqrt(f_r^2 + f_c^2)) takes every bin with the weight 2 for
+        0 < kc < tile / 2 (the bin stands for its mirror image too), else 1; a ring's value is the weighted mean of its
+        bins, bins beyond the last ring are dropped."""
+        ring, weight = self._rings()
+        keep = ring <= self.tile // 2
+        n = self.tile // 2 + 1
+        total = np.bincount(ring[keep], weights=(weight * self.power)[keep], minlength=n)
+        return total / np.bincount(ring[keep], weights=weight[keep], minlength=n)
+
+    def peak_wavenumber(self) -> Optional[float]:
+        """The pattern's wavenumber in cycles per cell: the largest ring among 1 .. tile / 2 - 1 of ``radial``, refined by
+        a parabola through it and its neighbours; None for a flat spectrum (or none at all)."""
+        s = self.radial()
+        inner = s[1:self.tile // 2]
+        if not np.all(np.isfinite(s)) or not inner.max() > inner.min():
+            return None
+        k = 1 + int(np.argmax(inner))
+        a, b, c = s[k - 1], s[k], s[k + 1]
+        bend = a - 2.0 * b + c
+        shift = 0.5 * (a - c) / bend if bend < 0.0 else 0.0
+        return (k + min(max(shift, -0.5), 0.5)) / self.tile
+
+    def wavelength(self) -> Optional[float]:
+        """Cells per period: 1 / ``peak_wavenumber``; None where that is."""
+        k = self.peak_wavenumber()
+        return 1.0 / k if k else None
+
+    def _moments(self) -> Optional[Tuple[float, float, float]]:
+        k = self.peak_wavenumber()
+        if k is None:
+            return None
+        ring, weight = self._rings()
+        near = np.abs(ring - int(round(k * self.tile))) <= 1
+        fr, fc = self.frequencies()
+        w = np.where(near, weight * self.power, 0.0)
+        total = w.sum()
+        if not total > 0.0:
+            return None
+        # (a bin and its mirror image (-f_r, -f_c) have the same products: the half plane's moments are the plane's)
+        return (float((w * fr[:, None] ** 2).sum() / total), float((w * fc[None, :] ** 2).sum() / total),
+                float((w * fr[:, None] * fc[None, :]).sum() / total))
+
+    def orientation(self) -> Optional[float]:
+        """The direction of the pattern's wave vector in degrees in [0, 180), measured from the column axis towards the
+        row axis: 0 for a pattern that varies along a row (stripes that run down the columns), 90 for one that varies
+        down a column -- the principal axis of the power-weighted second moments of (f_r, f_c) over the peak ring +- 1."""
+        m = self._moments()
+        if m is None:
+            return None
+        rr, cc, rc = m
+        return float(np.degrees(0.5 * np.arctan2(2.0 * rc, cc - rr)) % 180.0)
+
+    def anisotropy(self) -> Optional[float]:
+        """0 for power spread evenly over the peak ring, 1 for a single direction: (l1 - l2) / (l1 + l2) of the eigenvalues
+        of those second moments."""
+        m = self._moments()
+        if m is None:
+            return None
+        rr, cc, rc = m
+        return float(np.hypot(cc - rr, 2.0 * rc) / (cc + rr)) if cc + rr > 0.0 else None
+
+
+def _spectrum_outputs(planes: int, tile: int):
+    t = tile if tile in SPECTRUM_TILES else 16  # (a refused tile: the call returns before it writes)
+    power = np.zeros((max(planes, 0), t, t // 2 + 1), np.float64)
+    tiles = np.zeros((max(planes, 0), 2), np.uint64)
+    return power, tiles
+
+
+def spectrum_fields(context: "HipContext", fields: Sequence["HipConcentration"], tile: int = 64, window="hann") -> List[Spectrum]:
+    """``gs_fields_spectrum``: the tile-averaged power spectra of 1..4 planes of one shape over the whole global grid in one
+    call (collective in a multi-process context) -- tiles of ``tile`` (16, 32, 64, 128) cells a side, ``window`` "hann" or
+    "none".  Returns one ``Spectrum`` per plane."""
+    n, tile, win = len(fields), int(tile), _spectrum_window(window)
+    power, tiles = _spectrum_outputs(n if 1 <= n <= 4 else 4, tile)
+    capi.check(context._lib.gs_fields_spectrum(context.handle, _handle_array(fields), n, tile, win,
+                                               power.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                               tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    return [Spectrum.from_raw(power[i], tile, win, tiles[i]) for i in range(n)]
+
+
 @dataclass(frozen=True, eq=False)
 class RegionCorrelation:
     """The two-point pair counts of every region of one thresholded plane, counted on the device
@@ -1599,6 +1749,12 @@ class HipConcentration:
         blocking, collective in a multi-process context)."""
         return correlation_fields(context, [self], [thresholds], [above], max_lag)[0]
 
+    def spectrum(self, context: HipContext, tile: int = 64, window="hann") -> Spectrum:
+        """The tile-averaged power spectrum of this plane over the whole global grid -- tiles of ``tile`` (16, 32, 64, 128)
+        cells a side, ``window`` "hann" or "none" --, summed on the device (``gs_fields_spectrum``; blocking, collective in
+        a multi-process context)."""
+        return spectrum_fields(context, [self], tile, window)[0]
+
     def region_correlation(self, context: HipContext, region, thresholds, max_lag: int = 32,
                            above: bool = True) -> List[RegionCorrelation]:
         """The two-point pair counts of every region of ``region`` = (rh, rw) cells (an int: square) of this plane thresholded
@@ -1991,6 +2147,13 @@ class Species:
         low; without ``u_thresholds`` only V is looked at and the U list is empty."""
         return self._v_or_both(correlation_fields, u_thresholds, v_thresholds, above, max_lag)
 
+    def spectrum(self, tile: int = 64, window="hann") -> Tuple[Spectrum, Spectrum]:
+        """(U, V) tile-averaged power spectra of the current state in one call (``gs_fields_spectrum``; blocking, collective
+        in a multi-process context): tiles of ``tile`` (16, 32, 64, 128) cells a side, ``window`` "hann" or "none"."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = spectrum_fields(self._context, [in_u, in_v], tile, window)
+        return u, v
+
     def region_correlation(self, region, v_thresholds=(0.25,), u_thresholds=None, max_lag: int = 32,
                            above: Tuple[bool, bool] = (False, True)) -> Tuple[List[RegionCorrelation], List[RegionCorrelation]]:
         """(U, V) two-point pair counts of every region of the current state in one call (``gs_fields_region_correlation``;
@@ -2214,6 +2377,19 @@ class Ensemble:
         capi.check(self._ctx._lib.gs_members_correlation(self._ctx.handle, self.handle, first, count, thr, sense, nt, max_lag,
                                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
         return out
+
+    def spectra(self, first: int = 0, count: Optional[int] = None, tile: int = 64, window="hann") -> Tuple[np.ndarray, np.ndarray]:
+        """Tile-averaged power spectra of members ``[first, first + count)`` summed on the device (``gs_members_spectrum``,
+        blocking): (``power``, ``tiles``) -- the raw f64 sums ``[count, 2, tile, tile / 2 + 1]`` and the ``uint64`` tile
+        counts ``[count, 2, 2]`` = {used, skipped}; axis 1: U, V -- bit for bit what ``Species.spectrum`` gives for a lone
+        Species in the member's state.  ``Spectrum.from_raw(power[m, s], tile, window, tiles[m, s])`` makes the object."""
+        first, count = self._range(first, count)
+        tile, win = int(tile), _spectrum_window(window)
+        power, tiles = _spectrum_outputs(2 * max(count, 0), tile)
+        capi.check(self._ctx._lib.gs_members_spectrum(self._ctx.handle, self.handle, first, count, tile, win,
+                                                       power.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                       tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return power.reshape((max(count, 0), 2) + power.shape[1:]), tiles.reshape(max(count, 0), 2, 2)
 
     def snapshot(self) -> "Ensemble":
         """An ensemble of the same shape and member count on the same context whose members hold this one's current states

@@ -102,6 +102,14 @@ the scalars ``var_v_mean``, ``var_v_max`` (0 for a member that stands still, not
 ``mean_v_mean``; unless ``--no-fields`` is given also the planes ``mean_v``, ``var_v``, ``min_v``, ``max_v`` (and ``_u``), each
 ``[members, rows, cols]`` f32, and with ``--time-stats-threshold-v T`` ``occupancy_v`` and ``arrival_v``.  Retired members are
 sampled like the others: they repeat their state.
+
+``--spectrum-every N`` records, at the steps of ``--summary-every`` again (every N steps and after the last one), the
+tile-averaged power spectra of every member summed on the device (``Ensemble.spectra``; the rule is include/gs_hip.h's) --
+"what is the pattern's wavelength?", with no threshold -- into ``<output stem>.spectrum.npz``.  ``--spectrum-tile T`` (16, 32,
+64 or 128; default 64) is the tile's side, ``--spectrum-window hann|none`` (default hann) the window.  The file holds
+``steps[samples]``, ``tile``, ``window``, ``power[samples, members, 2, T, T/2 + 1]`` (axis 2: U, V; the raw f64 sums),
+``tiles[samples, members, 2, 2]`` (last axis: tiles used, tiles skipped) and ``wavelength[samples, members, 2]`` in cells
+(``Spectrum.wavelength``; NaN for a flat spectrum).  It changes no state either and works with ``--no-fields``.
 """
 from __future__ import annotations
 
@@ -117,7 +125,8 @@ import numpy as np
 from . import hdf5_min
 from .simulate import (add_backend_args, add_time_stats_args, backend_args, check_time_stats_args, time_stats_groups,
                        time_stats_planes, time_stats_steps)
-from .simulation import COMPONENT_OVERLAP_DTYPE, COMPONENT_RECORD_DTYPE, Parameters, Simulation, pairs_total, quad_measures
+from .simulation import (COMPONENT_OVERLAP_DTYPE, COMPONENT_RECORD_DTYPE, SPECTRUM_TILES, SPECTRUM_WINDOWS, Parameters, Simulation,
+                         Spectrum, pairs_total, quad_measures)
 
 
 def value_range(text: str) -> List[float]:
@@ -219,9 +228,17 @@ def parse(argv=None):
     ap.add_argument("--steady-stop", action="store_true", help="end the run once every member is settled")
     ap.add_argument("--steady-retire", action="store_true",
                     help="retire every member at the check that finds it settled: it keeps its state and stops advancing")
+    ap.add_argument("--spectrum-every", type=int, default=0, metavar="N",
+                    help="record every member's power spectra every N steps and at the end (<output stem>.spectrum.npz)")
+    ap.add_argument("--spectrum-tile", type=int, default=64, choices=SPECTRUM_TILES, metavar="T",
+                    help="the side of the spectra's tiles: 16, 32, 64 (the default) or 128 cells")
+    ap.add_argument("--spectrum-window", default="hann", choices=sorted(SPECTRUM_WINDOWS),
+                    help="the window of a tile: hann (periodic Hann, the default) or none")
     add_time_stats_args(ap, "--time-stats")
     add_backend_args(ap)
     args = ap.parse_args(argv)
+    if args.spectrum_every < 0:
+        ap.error("--spectrum-every must be at least 1 (0 = off)")
     check_time_stats_args(ap, args, "time_stats", "--time-stats")
     if args.steady_every < 0:
         ap.error("--steady-every must be at least 1 (0 = off)")
@@ -412,6 +429,22 @@ def write_correlations(path: str, steps: List[int], samples: List[np.ndarray], t
              pairs=np.ascontiguousarray(np.stack(samples, axis=0)), pairs_total=pairs_total(shape[0], shape[1], max_lag))
 
 
+def spectrum_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".spectrum.npz"
+
+
+def write_spectra(path: str, steps: List[int], samples: List[tuple], tile: int, window: str) -> None:
+    power = np.stack([p for p, _ in samples], axis=0)  # [samples, members, 2, T, T/2 + 1]
+    tiles = np.stack([t for _, t in samples], axis=0)  # [samples, members, 2, 2]
+    wavelength = np.full(power.shape[:3], np.nan)
+    for at in np.ndindex(wavelength.shape):
+        found = Spectrum.from_raw(power[at], tile, window, tiles[at]).wavelength()
+        if found is not None:
+            wavelength[at] = found
+    np.savez(path, steps=np.asarray(steps, np.int64), tile=np.int64(tile), window=np.str_(window), power=power, tiles=tiles,
+             wavelength=wavelength)
+
+
 def settled_steps(steps: List[int], max_abs: np.ndarray, tol: float) -> np.ndarray:
     """``settled_step[members]``: the first of ``steps`` at which ``max_abs[member, sample]`` is at most ``tol`` for both U
     and V, else -1.  ``max_abs``: ``[members, samples, 2]``."""
@@ -452,6 +485,7 @@ def run(args) -> dict:
     comp_at = sample_steps(args.steps, args.components_every) if args.components_every else []
     spots_at = sample_steps(args.steps, args.spots_every) if args.spots_every else []
     track_at = sample_steps(args.steps, args.track_every) if args.track_every else []
+    spec_at = sample_steps(args.steps, args.spectrum_every) if args.spectrum_every else []
     tstat_at = time_stats_steps(args.steps, args.time_stats_every, args.time_stats_from)
     stats = ens.time_stats(time_stats_groups(args.time_stats_threshold_v), v_threshold=args.time_stats_threshold_v) if tstat_at else None
     tstat_taken = []
@@ -459,12 +493,12 @@ def run(args) -> dict:
         stats.accumulate(0)
         tstat_taken.append(0)
     done, settled, taken = 0, None, None
-    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at or spots_at or track_at or tstat_at:
-        summaries, hists, changes, morphs, corrs, comps, spots, tracks = [], [], [], [], [], [], [], []
+    if summary_at or hist_at or steady_at or morph_at or corr_at or comp_at or spots_at or track_at or tstat_at or spec_at:
+        summaries, hists, changes, morphs, corrs, comps, spots, tracks, spectra = [], [], [], [], [], [], [], [], []
         snap = ens.snapshot() if steady_at else None
         last = ens.snapshot() if track_at else None  # (of its own: the steady checks move theirs at other steps)
         for at in sorted(set(summary_at) | set(hist_at) | set(steady_at) | set(morph_at) | set(corr_at) | set(comp_at)
-                         | set(spots_at) | set(track_at) | set(tstat_at) | ({args.steps} if tstat_at else set())):
+                         | set(spots_at) | set(track_at) | set(spec_at) | set(tstat_at) | ({args.steps} if tstat_at else set())):
             ens.prepare_steps(at - done)
             done = at
             if at in tstat_at and at not in tstat_taken:
@@ -489,6 +523,8 @@ def run(args) -> dict:
             if at in corr_at:
                 corrs.append(ens.correlations(v_thresholds=args.corr_threshold_v, u_thresholds=args.corr_threshold_u,
                                               max_lag=args.corr_lags))
+            if at in spec_at:
+                spectra.append(ens.spectra(tile=args.spectrum_tile, window=args.spectrum_window))
             if at in steady_at:
                 changes.append(ens.changes_since(snap))
                 snap.copy_from(ens)
@@ -521,6 +557,8 @@ def run(args) -> dict:
         if corr_at:
             write_correlations(correlation_path(args.output), corr_at[:len(corrs)], corrs, args.corr_threshold_u,
                                args.corr_threshold_v, args.corr_lags, shape)
+        if spec_at:
+            write_spectra(spectrum_path(args.output), spec_at[:len(spectra)], spectra, args.spectrum_tile, args.spectrum_window)
         if tstat_at:
             planes = time_stats_planes(stats, args.time_stats_threshold_v, lambda a: a) if stats.samples else {}
             write_time_stats(time_stats_path(args.output), stats.samples, tstat_taken, planes, not args.no_fields)

@@ -285,6 +285,88 @@ struct Correlation {
     // the length of d e_k in cells
     double distance(std::size_t k, std::size_t d) const { return (double)d * (k < 2 ? 1.0 : std::sqrt(2.0)); }
 };
+
+// The tile-averaged power spectrum of one plane, summed on the device (gs_fields_spectrum; the rule is gs_hip.h's):
+// raw[kr * (tile / 2 + 1) + kc] is the sum over the whole tile x tile tiles that hold only finite cells of
+// |FFT2(window (tile - its mean))|^2, kr < tile, kc <= tile / 2; tiles_used and tiles_skipped count those tiles and the ones
+// left out.  What follows is computed from these sums; frequencies are in cycles per cell.
+struct Spectrum {
+    std::vector<double> raw;
+    int32_t tile = 0, window = 0; // window: 0 none, 1 periodic Hann
+    uint64_t tiles_used = 0, tiles_skipped = 0;
+    // `p`: [tile][tile / 2 + 1], `t`: {used, skipped} -- the layout of gs_fields_spectrum for one plane
+    static Spectrum from_c(const double *p, const uint64_t *t, int32_t tile, int32_t window)
+    {
+        Spectrum o;
+        o.raw.assign(p, p + (std::size_t)tile * (std::size_t)(tile / 2 + 1));
+        o.tile = tile;
+        o.window = window;
+        o.tiles_used = t[0];
+        o.tiles_skipped = t[1];
+        return o;
+    }
+    std::size_t bins() const { return (std::size_t)tile * (std::size_t)(tile / 2 + 1); }
+    // the sum of (h_r h_c)^2 over a tile: tile^2 without a window
+    double window_energy() const
+    {
+        if (!window) return (double)tile * (double)tile;
+        double e = 0.0;
+        for (int32_t j = 0; j < tile; ++j) {
+            const double h = 0.5 - 0.5 * std::cos(2.0 * 3.14159265358979323846 * (double)j / (double)tile);
+            e += h * h;
+        }
+        return e * e;
+    }
+    // the mean over the tiles used, divided by the window's energy; NaN without a tile
+    double power(std::size_t kr, std::size_t kc) const
+    {
+        return tiles_used ? raw[kr * (std::size_t)(tile / 2 + 1) + kc] / ((double)tiles_used * window_energy()) : std::nan("");
+    }
+    // S(|k|) on rings 0 .. tile / 2: ring round(tile sqrt(f_r^2 + f_c^2)), a bin weighing 2 for 0 < kc < tile / 2, else 1; bins
+    // beyond the last ring are dropped
+    std::vector<double> radial() const
+    {
+        const std::size_t half = (std::size_t)tile / 2;
+        std::vector<double> sum(half + 1, 0.0), weight(half + 1, 0.0);
+        for (std::size_t kr = 0; kr < (std::size_t)tile; ++kr)
+            for (std::size_t kc = 0; kc <= half; ++kc) {
+                const double fr = (kr < half ? (double)kr : (double)kr - (double)tile), fc = (double)kc;
+                const std::size_t ring = (std::size_t)std::nearbyint(std::sqrt(fr * fr + fc * fc));
+                if (ring > half) continue;
+                const double w = kc > 0 && kc < half ? 2.0 : 1.0;
+                sum[ring] += w * power(kr, kc);
+                weight[ring] += w;
+            }
+        for (std::size_t k = 0; k <= half; ++k) sum[k] /= weight[k];
+        return sum;
+    }
+    // the pattern's wavenumber in cycles per cell: the largest ring among 1 .. tile / 2 - 1, refined by a parabola through its
+    // neighbours; NaN for a flat spectrum (or none at all)
+    double peak_wavenumber() const
+    {
+        const std::vector<double> s = radial();
+        const std::size_t half = (std::size_t)tile / 2;
+        std::size_t k = 1;
+        double lo = s[1], hi = s[1];
+        for (std::size_t i = 0; i <= half; ++i)
+            if (!std::isfinite(s[i])) return std::nan("");
+        for (std::size_t i = 1; i < half; ++i) {
+            if (s[i] > hi) {
+                hi = s[i];
+                k = i;
+            }
+            if (s[i] < lo) lo = s[i];
+        }
+        if (!(hi > lo)) return std::nan("");
+        const double bend = s[k - 1] - 2.0 * s[k] + s[k + 1];
+        double shift = bend < 0.0 ? 0.5 * (s[k - 1] - s[k + 1]) / bend : 0.0;
+        shift = shift < -0.5 ? -0.5 : (shift > 0.5 ? 0.5 : shift);
+        return ((double)k + shift) / (double)tile;
+    }
+    // cells per period
+    double wavelength() const { return 1.0 / peak_wavenumber(); }
+};
+
 // of one threshold (gs_fields_region_correlation): `at(i, j)` has region (i, j)'s own rows and cols, a pair across a region
 // border is never formed
 using RegionCorrelation = Regions<Correlation>;
@@ -784,6 +866,19 @@ class Species {
         }
         return uv;
     }
+    // (U, V) tile-averaged power spectra of the current state over the whole global grid, in one call (gs_fields_spectrum;
+    // blocking, collective in a multi-process context): tiles of `tile` (16, 32, 64, 128) cells a side, with the periodic Hann
+    // window unless `hann` is false
+    std::pair<Spectrum, Spectrum> spectrum(int32_t tile = 64, bool hann = true)
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t t = tile == 16 || tile == 32 || tile == 64 || tile == 128 ? (std::size_t)tile : 16;
+        const std::size_t bins = t * (t / 2 + 1); // (a refused tile: the call returns before it writes)
+        std::vector<double> power(2 * bins);
+        uint64_t tiles[4] = {0, 0, 0, 0};
+        check(gs_fields_spectrum(context_->get(), planes, 2, tile, hann ? 1 : 0, power.data(), tiles));
+        return {Spectrum::from_c(power.data(), tiles, tile, hann ? 1 : 0), Spectrum::from_c(power.data() + bins, tiles + 2, tile, hann ? 1 : 0)};
+    }
     // (U, V) two-point pair counts of every region of rh x rw cells of the current state, in one call
     // (gs_fields_region_correlation; blocking, collective in a multi-process context): one RegionCorrelation per threshold, a
     // region's border being a wall for pairs; thresholds, lags and senses as for correlation()
@@ -1092,6 +1187,21 @@ class Ensemble {
             out.push_back(Correlation::from_c(c.data() + i * 4 * lags, max_lag, t[species * nt + j], sense[species] != 0, shape_[0],
                                               shape_[1]));
         }
+        return out;
+    }
+    // tile-averaged power spectra of members [first, first + count) from the newest state (gs_members_spectrum, blocking):
+    // element 2 i + s = species s (0 = U, 1 = V) of member first + i, what Species::spectrum gives for a lone Species in
+    // that state
+    std::vector<Spectrum> spectra(std::size_t first, std::size_t count, int32_t tile = 64, bool hann = true) const
+    {
+        const std::size_t t = tile == 16 || tile == 32 || tile == 64 || tile == 128 ? (std::size_t)tile : 16;
+        const std::size_t bins = t * (t / 2 + 1);
+        std::vector<double> power(2 * count * bins + 1);
+        std::vector<uint64_t> tiles(4 * count + 1);
+        check(gs_members_spectrum(ctx_->get(), e_, first, count, tile, hann ? 1 : 0, power.data(), tiles.data()));
+        std::vector<Spectrum> out;
+        for (std::size_t i = 0; i < 2 * count; ++i)
+            out.push_back(Spectrum::from_c(power.data() + i * bins, tiles.data() + 2 * i, tile, hann ? 1 : 0));
         return out;
     }
     // an ensemble of the same shape and member count on the same context whose members hold this one's current states

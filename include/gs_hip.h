@@ -765,12 +765,57 @@ int32_t gs_fields_region_histogram(gs_ctx *ctx, gs_field *const *fields, int32_t
  * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID: a null
  * argument, nt outside 1..4, a NaN threshold or max_lag outside 1..64 -- decided in this order before any handle is looked
  * at --, a null or foreign handle, mixed shapes, n outside 1..4, members outside the ensemble.
- * Not done: pairs wrapped under the periodic rule; the full 2-D lag window and lags beyond 64; real-valued autocorrelation
- * and spectra; cross-correlation of U with V; slabs shorter than L. */
+ * Not done: pairs wrapped under the periodic rule; the full 2-D lag window and lags beyond 64; real-valued autocorrelation;
+ * cross-correlation of U with V; slabs shorter than L. */
 int32_t gs_fields_correlation(gs_ctx *ctx, gs_field *const *fields, int32_t n, const float *thresholds, const int32_t *above,
                               int32_t nt, int32_t max_lag, uint64_t *out);
 int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const float *thresholds,
                                const int32_t above[2], int32_t nt, int32_t max_lag, uint64_t *out);
+
+/* Power spectra computed on the device: the tile-averaged structure factor of one plane of the WHOLE global grid -- from it the
+ * pattern's wavelength with sub-cell resolution and the orientation of stripes at any angle, with no threshold -- without
+ * downloading the plane.  For a plane x of R x C cells, a tile size T of 16, 32, 64 or 128 and window = 0 (none) or 1
+ * (periodic Hann):
+ *   - TILES are T x T cells, do not overlap and are anchored at global row 0 and column 0: band b is rows [b T, (b + 1) T),
+ *     tile (b, j) columns [j T, (j + 1) T) of band b.  Only tiles wholly inside the grid exist, floor(R / T) floor(C / T) of
+ *     them; the remaining rows and columns are not looked at.  Nothing wraps, under any boundary rule.
+ *   - TABLES, formed by the host in f64 and rounded to f32, handed out by gs_spectrum_tables (which needs no device):
+ *     h[j] = 0.5 - 0.5 cos(2 pi j / T), j < T, and W[k] = (cos(2 pi k / T), -sin(2 pi k / T)), k < T / 2.
+ *   - PER TILE, every f32 operation rounded on its own, no fused multiply-add:
+ *       1. a tile that holds a NaN or an infinity adds nothing and counts as skipped;
+ *       2. the mean: the cells added as f64, each row halved repeatedly -- p[0:T/2] + p[T/2:T], and so on down to one value --,
+ *          the T row sums halved likewise, m = (float)(sum / (double)(T T));
+ *       3. y = x - m in f32 and, with the window, y = (y h[r]) h[c];
+ *       4. every row, as complex numbers with zero imaginary part, through a radix-2 decimation-in-time transform: the input
+ *          permuted by bit reversal, then log2 T stages with half-sizes h = 1, 2, 4, ...; a butterfly with a = X[i],
+ *          b = X[i + h] and w = W[(i mod h) T / (2 h)] forms t = (b.re w.re - b.im w.im, b.re w.im + b.im w.re), then
+ *          X[i] = a + t and X[i + h] = a - t;
+ *       5. columns 0 .. T/2 of the result through the same transform along the rows' axis;
+ *       6. p[kr][kc] = re re + im im in f32, kr < T, kc <= T/2.
+ *   - THE FOLD, a function of (R, C, T) alone: a segment is up to 16 consecutive tiles [16 s, 16 s + 16) of one band, and its
+ *     record adds its tiles' p, as f64, one after another in ascending tile order from +0.0; a band's sum adds its segments'
+ *     records in ascending order from +0.0; the plane's result adds the band sums in ascending global band order from +0.0.
+ * The result is power[T][T/2 + 1] as f64, the raw sums -- the hosts do all normalisation (the mean over the tiles used, the
+ * window's energy, the radial average) --, and tiles[2] = {used, skipped}.  Sub-normal values are kept; overflow inside a
+ * tile propagates by IEEE rules.  A grid smaller than T on a side: GS_OK, all zeros.  The bits are the same for any slab
+ * count, process count or step kernel, and a member's are those of a lone Species in the same state.
+ *   gs_spectrum_tables   window[T] and twiddle[T / 2 pairs (re, im)] as above; either may be null.
+ *   gs_fields_spectrum   power[(i T + kr) (T/2 + 1) + kc] and tiles[2 i ..] for fields[i], i < n (1..4 fields of one shape):
+ *                        one wait for enqueued work (as gs_fields_summarize), per slab one launch over its segments and one
+ *                        that adds them per band; the host adds the bands.  A context in which some slab -- any rank's --
+ *                        begins at a row that is not a multiple of T: GS_ERR_UNSUPPORTED, on every rank alike.  In a
+ *                        multi-process context the call is collective, like gs_run, and every rank receives the global result.
+ *   gs_members_spectrum  the same layout with i = 2 m + s for species s of member first + m, m < count, from the newest slot:
+ *                        one launch over every member's segments.  Retired members are read like any other.
+ * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID: a tile
+ * or window outside the sets above or a null output -- decided before any handle is looked at --, a null or foreign handle,
+ * mixed shapes, n outside 1..4, members outside the ensemble.
+ * Not done: per-region spectra; the cross-spectrum of U with V; overlapping tiles; tiles that wrap. */
+int32_t gs_spectrum_tables(int32_t tile, float *window, float *twiddle);
+int32_t gs_fields_spectrum(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t tile, int32_t window, double *power,
+                           uint64_t *tiles);
+int32_t gs_members_spectrum(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, int32_t tile, int32_t window,
+                            double *power, uint64_t *tiles);
 
 /* Connected components computed on the device: how many spots one plane of the WHOLE global grid has after thresholding, and
  * how large they are -- what the bit quads cannot say, which give only components - holes -- without downloading the plane.

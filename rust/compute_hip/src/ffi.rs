@@ -226,6 +226,29 @@ extern "C" {
         count: u64,
         out: *mut gs_summary,
     ) -> i32;
+    /// Power spectra (gs_hip.h): the window `h[tile]` and the `tile / 2` twiddles as (re, im) pairs; pure.
+    pub fn gs_spectrum_tables(tile: i32, window: *mut f32, twiddle: *mut f32) -> i32;
+    /// `power[n][tile][tile / 2 + 1]` raw f64 sums over whole tiles and `tiles[n][2]` = {used, skipped}; `window`: 0 none, 1 Hann.
+    pub fn gs_fields_spectrum(
+        ctx: *mut gs_ctx,
+        fields: *const *mut gs_field,
+        n: i32,
+        tile: i32,
+        window: i32,
+        power: *mut f64,
+        tiles: *mut u64,
+    ) -> i32;
+    /// The same layout with index 2 m + s for species s of member `first + m`.
+    pub fn gs_members_spectrum(
+        ctx: *mut gs_ctx,
+        e: *mut gs_ensemble,
+        first: u64,
+        count: u64,
+        tile: i32,
+        window: i32,
+        power: *mut f64,
+        tiles: *mut u64,
+    ) -> i32;
     /// Regional observables (gs_hip.h): `rr` x `rc` regions of `rh` x `rw` cells cut a grid of `rows` x `cols`; pure.
     pub fn gs_region_grid(rows: u64, cols: u64, rh: i32, rw: i32, rr: *mut u64, rc: *mut u64) -> i32;
     /// `out`: n x rr x rc records, region (i, j) of `fields[p]` at `p * rr * rc + i * rc + j`.
