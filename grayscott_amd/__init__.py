@@ -26,6 +26,7 @@ from .simulation import (  # noqa: F401
     RegionCorrelation,
     RegionHistogram,
     RegionMorphology,
+    RegionSpectrum,
     RegionSummaries,
     Simulation,
     Snapshot,
@@ -35,8 +36,9 @@ from .simulation import (  # noqa: F401
     TimeStats,
     correlation_fields,
     pinned_empty,
+    region_spectrum_fields,
     spectrum_fields,
 )
 
 __all__ = ["capi", "GsError", "Change", "Correlation", "Ensemble", "Evolving", "HipArgs", "Histogram", "HipConcentration", "HipContext",
-           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionChange", "RegionComponents", "RegionCorrelation", "RegionHistogram", "RegionMorphology", "RegionSummaries", "Simulation", "Snapshot", "Species", "Spectrum", "Summary", "TimeStats", "correlation_fields", "pinned_empty", "spectrum_fields"]
+           "ComponentList", "ComponentMatch", "Components", "Morphology", "Parameters", "RegionChange", "RegionComponents", "RegionCorrelation", "RegionHistogram", "RegionMorphology", "RegionSpectrum", "RegionSummaries", "Simulation", "Snapshot", "Species", "Spectrum", "Summary", "TimeStats", "correlation_fields", "pinned_empty", "region_spectrum_fields", "spectrum_fields"]

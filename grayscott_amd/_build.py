@@ -85,6 +85,9 @@ UNITS = [
     # power spectra (f32 radix-2 transforms of tiles in LDS, f64 sums per segment of tiles and per band): the same float mode,
     # sub-normal values kept
     ("gs_spectrum.hip", "gs_spectrum_k.o", []),
+    # regional power spectra (the same tile body from gs_spectrum_tile.h, segments and bands counted inside a region, the
+    # fold per region): the same float mode as gs_spectrum.hip
+    ("gs_region_spectrum.hip", "gs_region_spectrum_k.o", []),
     # time statistics (per-cell f64 sums, f32 extremes and u32 crossing counters read, updated and written back per sample):
     # the same float mode, a sub-normal sample counts as the value it is
     ("gs_time_stats.hip", "gs_time_stats_k.o", []),

@@ -28,6 +28,8 @@ GS_BOUNDARY_CLIPPED, GS_BOUNDARY_ZERO_HALO, GS_BOUNDARY_PERIODIC, GS_BOUNDARY_NE
 GS_UNIQUE_ID_BYTES = 128
 GS_REGION_PAIRS_MAX = 1 << 25  # counters per field of one gs_fields_region_correlation call (include/gs_hip.h)
 GS_REGION_HIST_MAX = 1 << 25  # counters per field of one gs_fields_region_histogram call (include/gs_hip.h)
+GS_REGION_SPECTRUM_MAX = 1 << 25  # result words per field of one gs_fields_region_spectrum call (include/gs_hip.h)
+GS_REGION_SPECTRUM_RECORDS_MAX = 1 << 27  # segment-record words over the fields of one such call (include/gs_hip.h)
 GS_REGION_COMPONENTS_MAX = 1 << 20  # results per field of one gs_fields_region_components call (include/gs_hip.h)
 GS_REGION_CHANGE_RECORDS_MAX = 1 << 28  # bytes of row records per slab of one gs_fields_region_compare call (include/gs_hip.h)
 # time statistics (include/gs_hip.h): the groups of accumulators, the result planes and the raw accumulators
@@ -61,7 +63,7 @@ EXPORTS = (
     "gs_members_set_active", "gs_members_get_active",
     "gs_fields_morphology", "gs_members_morphology",
     "gs_region_grid", "gs_fields_region_summaries", "gs_fields_region_morphology", "gs_fields_region_correlation",
-    "gs_fields_region_histogram", "gs_fields_region_components", "gs_fields_region_compare",
+    "gs_fields_region_histogram", "gs_fields_region_components", "gs_fields_region_compare", "gs_fields_region_spectrum",
     "gs_fields_correlation", "gs_members_correlation",
     "gs_spectrum_tables", "gs_fields_spectrum", "gs_members_spectrum",
     "gs_fields_components", "gs_members_components",
@@ -315,6 +317,7 @@ def load() -> ctypes.CDLL:
         "gs_spectrum_tables": (i32, [i32, P(f32), P(f32)]),
         "gs_fields_spectrum": (i32, [vp, P(vp), i32, i32, i32, P(ctypes.c_double), P(u64)]),
         "gs_members_spectrum": (i32, [vp, vp, u64, u64, i32, i32, P(ctypes.c_double), P(u64)]),
+        "gs_fields_region_spectrum": (i32, [vp, P(vp), i32, i32, i32, i32, i32, P(ctypes.c_double), P(u64)]),
         "gs_time_stats_create": (i32, [vp, P(vp), u64, u64, i32, u32, P(f32), P(i32)]),
         "gs_time_stats_destroy": (i32, [vp, vp]),
         "gs_time_stats_reset": (i32, [vp, vp]),

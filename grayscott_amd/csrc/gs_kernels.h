@@ -366,6 +366,19 @@ hipError_t gs_launch_spectrum(const float *const *planes, int np, int64_t repeat
                               int32_t cols, int32_t tile, int32_t window, const float *h, const float *w, void *records,
                               void *out, hipStream_t s);
 
+// Regional power spectra (gs_region_spectrum.hip; include/gs_hip.h: gs_fields_region_spectrum).  np (1..4) planes of one slab
+// and regions of rh x rw cells as for gs_launch_region_quads, tile, window, h and w as for gs_launch_spectrum; tiles are
+// anchored at every region's first row and column.  The launches -- a workgroup per segment of 16 tiles of a band of a region
+// writes a record into `records` (np * gs_region_spectrum_records(rows, cols, ...) * gs_spectrum_result_bytes(tile) bytes, no
+// initial contents), a fold adds a region's records -- leave out[(p * rr + i) * rc + j], a result of
+// gs_spectrum_result_bytes(tile) bytes for every region of the slab: zeros where no tile fits.
+// gs_region_spectrum_records: the records of one plane of rows x cols cells -- over its regions, bands of the region times
+// segments of such a band.  A region grid's rows split at multiples of rh add up: the slabs' counts sum to the grid's.
+uint64_t gs_region_spectrum_records(uint64_t rows, uint64_t cols, int32_t rh, int32_t rw, int32_t tile);
+hipError_t gs_launch_region_spectrum(const float *const *planes, int np, int64_t pitch, int64_t rows, int32_t cols, int32_t rh,
+                                     int32_t rw, int32_t tile, int32_t window, const float *h, const float *w, void *records,
+                                     void *out, hipStream_t s);
+
 // Connected components (gs_components.hip; include/gs_hip.h: gs_fields_components).  `planes` planes of rows x cols cells,
 // `stride` floats apart, rows `pitch` floats apart, thresholded at `threshold` with `sense` as for gs_launch_quads and
 // labelled under `connectivity` (4 or 8); a component never leaves its plane.  parent and size hold one u32 per cell of all

@@ -48,6 +48,10 @@
 //   power spectra  (gs_fields_spectrum, gs_members_spectrum; gs_spectrum.hip) a record per segment of 16 tiles behind the slab's
 //               results, added per band of T rows on the device: one result per band travels (band_results) and the host adds
 //               the bands in ascending global order; an ensemble's members are planes of one launch, their bands added here too.
+//               The regions' spectra (gs_fields_region_spectrum; gs_region_spectrum.hip) travel as the regional observables
+//               do: a record per segment of a band of a region behind the slab's results, added per region on the device --
+//               a region lies inside one slab, so its result is complete -- and one result per region travels
+//               (band_results with bands of rh rows); the host only splits each into power and tile counts.
 // The device copies that make a state to compare with (gs_fields_copy, gs_members_copy: snapshots and restores) are here too.
 // No observation touches ghost rows, the tuner, graphs or the context's counters; a copy leaves its target as an upload does.
 #include "gs_internal.h"
@@ -1840,6 +1844,60 @@ int32_t gs_fields_region_compare(gs_ctx *ctx, gs_field *const *a, gs_field *cons
         return gs_launch_region_change(pa, pb, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw,
                                        reinterpret_cast<GsChangeTotal *>(dev), records_at[i] ? dev + records_at[i] : nullptr, s);
     });
+}
+
+int32_t gs_fields_region_spectrum(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, int32_t tile,
+                                  int32_t window, double *power, uint64_t *tiles)
+{
+    if (!power || !tiles) return fail(GS_ERR_INVALID, "null output");
+    GS_TRY(check_spectrum(tile, window));
+    uint64_t RR, RC;
+    GS_TRY(region_grid(0, 0, rh, rw, &RR, &RC)); // the region shape alone; no handle is looked at down to check_planes
+    if (!ctx || !fields) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(check_planes(ctx, fields, n));
+    const gs_field *f0 = fields[0];
+    GS_TRY(region_grid(f0->rows, f0->cols, rh, rw, &RR, &RC));
+    if (RR * RC == 0) return GS_OK; // an empty plane has no regions; the same shape on every rank: nobody exchanges anything
+    const size_t bins = (size_t)tile * (size_t)(tile / 2 + 1), words = bins + 2, elem = gs_spectrum_result_bytes(tile);
+    if (RR * RC * (uint64_t)words > (uint64_t)GS_REGION_SPECTRUM_MAX) // (at most 2^22 * 8322: no product here can wrap)
+        return fail(GS_ERR_INVALID, "%llu x %llu regions of %llu words each (at most %u words per field)", (unsigned long long)RR,
+                    (unsigned long long)RC, (unsigned long long)words, (unsigned)GS_REGION_SPECTRUM_MAX);
+    // the records of the global grid, whatever its slabs: every rank and every slab count reaches the same verdict
+    const uint64_t record_words = (uint64_t)n * gs_region_spectrum_records(f0->rows, f0->cols, rh, rw, tile) * (uint64_t)words;
+    if (record_words > (uint64_t)GS_REGION_SPECTRUM_RECORDS_MAX)
+        return fail(GS_ERR_INVALID, "%llu words of segment records over the %d fields (at most %llu)",
+                    (unsigned long long)record_words, n, (unsigned long long)GS_REGION_SPECTRUM_RECORDS_MAX);
+    GS_TRY(check_band_seams(ctx, f0, rh)); // every rank reaches the same verdict before anybody allocates
+    // a slab's segment records lie behind its regions' results in its scratch buffer, which is made large enough here:
+    // band_results then finds it so and keeps it (the regional comparison's precedent)
+    const size_t nslab = ctx->slabs.size();
+    std::vector<size_t> records_at(nslab, (size_t)0);
+    for (size_t i = 0; i < nslab; ++i) {
+        const uint64_t rows = (uint64_t)f0->s[i].rows;
+        if (rows == 0) continue;
+        const size_t results = (size_t)n * (size_t)((rows + (uint64_t)rh - 1) / (uint64_t)rh) * (size_t)RC * elem;
+        records_at[i] = (results + 255) / 256 * 256;
+        const size_t rec_bytes = (size_t)n * (size_t)gs_region_spectrum_records(rows, f0->cols, rh, rw, tile) * elem;
+        GS_TRY(ensure_scratch(ctx, (int)i, records_at[i] + rec_bytes, "region spectrum"));
+    }
+    float h[128], w[128];
+    spectrum_tables(tile, h, w);
+    std::vector<unsigned char> results((size_t)n * (size_t)RR * (size_t)RC * elem);
+    GS_TRY(band_results(ctx, f0, n, rh, RR, RC, elem, false, "region spectrum", results.data(),
+                        [&](size_t i, unsigned char *dev, hipStream_t s) {
+        const float *planes[4];
+        slab_planes(fields, n, i, planes);
+        return gs_launch_region_spectrum(planes, n, f0->pitch, (int64_t)f0->s[i].rows, (int32_t)f0->cols, rh, rw, tile, window, h,
+                                         w, dev + records_at[i], dev, s);
+    }));
+    // the device has finished every region: the host only takes each result apart
+    const size_t regions = (size_t)n * (size_t)RR * (size_t)RC;
+    for (size_t r = 0; r < regions; ++r) {
+        const unsigned char *from = results.data() + r * elem;
+        std::memcpy(power + r * bins, from, bins * 8);
+        std::memcpy(tiles + 2 * r, from + bins * 8, 16);
+    }
+    return GS_OK;
 }
 
 } // extern "C"

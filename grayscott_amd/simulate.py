@@ -55,6 +55,12 @@ snapshot that is taken only before an interval that ends in an observed image --
 nonfinite}_{u,v}`` as [samples, RR, RC] and ``change_steps``, the interval in steps.  ``--hip-region-steady-tol T`` (finite, at
 least 0; needs ``--hip-region-change``) adds ``steady`` [samples, RR, RC], bool: neither U nor V moved by more than T in any cell of
 the region and no cell is non-finite.  The run is not ended early on it.
+``--hip-region-spectrum-tile T`` (16, 32, 64 or 128; needs ``--hip-regions``) adds the regions' tile-averaged power spectra
+(``gs_fields_region_spectrum``, tiles anchored at every region's first row and column) under
+``--hip-region-spectrum-window hann|none`` (hann by default; needs the tile option): ``spectrum_u`` and ``spectrum_v`` as
+[samples, RR, RC, T, T/2 + 1] float64, the raw sums, ``spectrum_tiles_u`` and ``spectrum_tiles_v`` as [samples, RR, RC, 2]
+uint64 -- tiles used, skipped --, with ``spectrum_tile`` and ``spectrum_window``: the wavelength with sub-cell resolution and
+the stripes' orientation of every region, with no threshold (``RegionSpectrum.from_raw`` makes the object).
 
 Time statistics (``gs_time_stats``): ``--hip-time-stats-every N`` samples U and V every N steps -- from step S on with
 ``--hip-time-stats-from S`` (default N; 0: the initial state too), at steps S, S + N, ..., each stamped with its step count -- into per-cell accumulators on
@@ -110,6 +116,12 @@ def parse(argv=None):
         ap.error("--hip-region-components needs --hip-regions")
     if args.hip_region_change and args.hip_regions is None:
         ap.error("--hip-region-change needs --hip-regions")
+    if args.hip_region_spectrum_tile is not None and args.hip_regions is None:
+        ap.error("--hip-region-spectrum-tile needs --hip-regions")
+    if args.hip_region_spectrum_window is not None and args.hip_region_spectrum_tile is None:
+        ap.error("--hip-region-spectrum-window needs --hip-region-spectrum-tile")
+    if args.hip_region_spectrum_tile is not None and args.hip_region_spectrum_window is None:
+        args.hip_region_spectrum_window = "hann"
     if args.hip_region_steady_tol is not None and not args.hip_region_change:
         ap.error("--hip-region-steady-tol needs --hip-region-change")
     for name in ("u", "v"):
@@ -274,6 +286,11 @@ def add_region_args(ap: argparse.ArgumentParser) -> None:
     rg.add_argument("--hip-region-steady-tol", type=_tolerance, default=None, metavar="T",
                     help="also `steady`: the regions in which neither U nor V moved by more than T over that interval "
                          "(finite, at least 0; needs --hip-region-change)")
+    rg.add_argument("--hip-region-spectrum-tile", type=int, choices=(16, 32, 64, 128), default=None, metavar="T",
+                    help="also the regions' tile-averaged power spectra of U and V, tiles of T (16, 32, 64, 128) cells a side "
+                         "anchored at every region's first row and column (needs --hip-regions)")
+    rg.add_argument("--hip-region-spectrum-window", choices=("hann", "none"), default=None,
+                    help="the window of those tiles (default hann; needs --hip-region-spectrum-tile)")
     rg.add_argument("--hip-region-hist-range-u", type=_hist_range, default=None, metavar="A:B",
                     help="the range of U's histograms (default 0:1; needs --hip-region-hist-bins)")
     rg.add_argument("--hip-region-hist-range-v", type=_hist_range, default=None, metavar="A:B",
@@ -375,6 +392,14 @@ def region_hist_args(args):
     return bins, getattr(args, "hip_region_hist_range_u", None), getattr(args, "hip_region_hist_range_v", None)
 
 
+def region_spectrum_args(args):
+    """``RegionLog``'s ``spectrum`` from the ``--hip-region-spectrum-*`` options: None without the tile option."""
+    tile = getattr(args, "hip_region_spectrum_tile", None)
+    if tile is None:
+        return None
+    return tile, getattr(args, "hip_region_spectrum_window", None) or "hann"
+
+
 class RegionLog:
     """What ``--hip-regions`` collects, one entry per observed image, and the file it becomes."""
 
@@ -382,11 +407,13 @@ class RegionLog:
     CHANGE_KEYS = ("sum_abs", "sum_sq", "max_abs", "differing", "nonfinite")
 
     def __init__(self, region, thresholds_v, thresholds_u, corr_lags=None, hist=None, components=None, change=False,
-                 steady_tol=None):
+                 steady_tol=None, spectrum=None):
         """``hist``: None, or (bins, U's (lo, hi), V's (lo, hi)) -- a range that is None is (0, 1).  ``components``: None, or
         the connectivity (4 or 8) of the regions' connected components.  ``change``: also the regions' change over the last
-        image interval (``before_interval`` takes the earlier state); ``steady_tol``: None, or the tolerance of ``steady``."""
+        image interval (``before_interval`` takes the earlier state); ``steady_tol``: None, or the tolerance of ``steady``.
+        ``spectrum``: None, or (tile, "hann" or "none") of the regions' power spectra."""
         self.region = region
+        self.spectrum = None if spectrum is None else (int(spectrum[0]), str(spectrum[1]))
         self.change, self.change_steps, self.snapshot = bool(change), None, None
         self.steady_tol = None if steady_tol is None else float(steady_tol)
         if self.steady_tol is not None and not self.change:
@@ -442,6 +469,10 @@ class RegionLog:
             self.rows.setdefault("components_v", []).append(np.stack([c.counters() for c in cv]))  # the C ABI's 35 words
             if cu:
                 self.rows.setdefault("components_u", []).append(np.stack([c.counters() for c in cu]))
+        if self.spectrum is not None:
+            for name, sp in zip(("u", "v"), species.region_spectrum(self.region, *self.spectrum)):
+                self.rows.setdefault(f"spectrum_{name}", []).append(sp.raw)
+                self.rows.setdefault(f"spectrum_tiles_{name}", []).append(np.stack([sp.tiles_used, sp.tiles_skipped], axis=2))
         if self.change:
             if self.snapshot is None:
                 raise RuntimeError("no earlier state to compare with: before_interval was not called")
@@ -464,6 +495,9 @@ class RegionLog:
             out["hist_range_v"] = np.array(self.hist[2], np.float64)
         if self.components is not None:
             out["comp_connectivity"] = np.array(self.components, np.int64)
+        if self.spectrum is not None:
+            out["spectrum_tile"] = np.array(self.spectrum[0], np.int64)
+            out["spectrum_window"] = np.array(self.spectrum[1])
         if self.change:
             out["change_steps"] = np.array(self.change_steps or 0, np.int64)
         if self.steady_tol is not None:
@@ -597,7 +631,7 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
     regions = RegionLog(region, getattr(args, "hip_region_threshold_v", None), getattr(args, "hip_region_threshold_u", None),
                         getattr(args, "hip_region_corr_lags", None), region_hist_args(args),
                         getattr(args, "hip_region_components", None), getattr(args, "hip_region_change", False),
-                        getattr(args, "hip_region_steady_tol", None)) if region else None
+                        getattr(args, "hip_region_steady_tol", None), region_spectrum_args(args)) if region else None
     mask = domain_mask(args, shape)
     sim = Simulation.new(params, hip_args if hip_args is not None else backend_args(args))
     species = sim.make_species(shape)

@@ -1496,6 +1496,98 @@ def region_histogram_fields(context: "HipContext", fields: Sequence["HipConcentr
     return [RegionHistogram.from_counters(out[i], lo[i], hi[i], (rh, rw), shape) for i in range(n)]
 
 
+@dataclass(frozen=True, eq=False)
+class RegionSpectrum:
+    """The tile-averaged power spectra of every region of one plane, summed on the device (``gs_fields_region_spectrum``):
+    ``raw`` of shape ``(RR, RC, tile, tile / 2 + 1)``, ``tiles_used`` / ``tiles_skipped`` of shape ``(RR, RC)``, entry (i, j)
+    being bit for bit the ``Spectrum`` of a plane that holds region (i, j)'s cells alone -- tiles anchored at the region's
+    first row and column, a region in which no tile fits all zeros.  ``region`` is ``(rh, rw)``, ``shape`` the plane's.  The
+    array methods are ``Spectrum``'s, region by region, NaN where ``Spectrum``'s gives None."""
+
+    raw: np.ndarray
+    tiles_used: np.ndarray
+    tiles_skipped: np.ndarray
+    tile: int
+    window: int
+    region: Tuple[int, int]
+    shape: Tuple[int, int]
+
+    @classmethod
+    def from_raw(cls, raw, tiles, tile: int, window, region, shape) -> "RegionSpectrum":
+        """From ``(RR, RC, tile, tile / 2 + 1)`` sums and ``(RR, RC, 2)`` counts {used, skipped} as the C ABI writes them."""
+        tile = int(tile)
+        tiles = np.asarray(tiles, np.uint64)
+        rr, rc = tiles.shape[:2]
+        p = np.array(raw, np.float64).reshape(rr, rc, tile, tile // 2 + 1)
+        return cls(p, tiles[:, :, 0].copy(), tiles[:, :, 1].copy(), tile, _spectrum_window(window), region_shape(region),
+                   (int(shape[0]), int(shape[1])))
+
+    def at(self, i: int, j: int) -> Spectrum:
+        return Spectrum(self.raw[i, j].copy(), self.tile, self.window, int(self.tiles_used[i, j]), int(self.tiles_skipped[i, j]))
+
+    @property
+    def power(self) -> np.ndarray:
+        """Per region, ``Spectrum.power``: f64 ``(RR, RC, tile, tile / 2 + 1)``, NaN where a region used no tile."""
+        out = np.full(self.raw.shape, np.nan)
+        for i, j in np.ndindex(*self.tiles_used.shape):
+            out[i, j] = self.at(i, j).power
+        return out
+
+    def radial(self) -> np.ndarray:
+        """Per region, ``Spectrum.radial()``: f64 ``(RR, RC, tile / 2 + 1)``."""
+        out = np.full(self.tiles_used.shape + (self.tile // 2 + 1,), np.nan)
+        for i, j in np.ndindex(*self.tiles_used.shape):
+            out[i, j] = self.at(i, j).radial()
+        return out
+
+    def _each(self, method: str) -> np.ndarray:
+        out = np.full(self.tiles_used.shape, np.nan)
+        for i, j in np.ndindex(*self.tiles_used.shape):
+            value = getattr(self.at(i, j), method)()
+            if value is not None:
+                out[i, j] = value
+        return out
+
+    def peak_wavenumber(self) -> np.ndarray:
+        """Per region, ``Spectrum.peak_wavenumber()``: f64 ``(RR, RC)``, NaN where that is None."""
+        return self._each("peak_wavenumber")
+
+    def wavelength(self) -> np.ndarray:
+        """Per region, ``Spectrum.wavelength()``: f64 ``(RR, RC)``, NaN where that is None."""
+        return self._each("wavelength")
+
+    def orientation(self) -> np.ndarray:
+        """Per region, ``Spectrum.orientation()``: f64 ``(RR, RC)``, NaN where that is None."""
+        return self._each("orientation")
+
+    def anisotropy(self) -> np.ndarray:
+        """Per region, ``Spectrum.anisotropy()``: f64 ``(RR, RC)``, NaN where that is None."""
+        return self._each("anisotropy")
+
+
+def region_spectrum_fields(context: "HipContext", fields: Sequence["HipConcentration"], region, tile: int = 64,
+                           window="hann") -> List[RegionSpectrum]:
+    """``gs_fields_region_spectrum``: the tile-averaged power spectra of every region of 1..4 planes of one shape in one call
+    (blocking; collective in a multi-process context) -- tiles of ``tile`` (16, 32, 64, 128) cells a side anchored at every
+    region's first row and column, ``window`` "hann" or "none".  Returns one ``RegionSpectrum`` per plane."""
+    n, tile, win = len(fields), int(tile), _spectrum_window(window)
+    rh, rw = region_shape(region)
+    shape = fields[0].shape() if fields else (0, 0)
+    t = tile if tile in SPECTRUM_TILES else 16  # (a refused tile: the call returns before it writes)
+    try:
+        grid = region_grid(shape[0], shape[1], (rh, rw))
+        if grid[0] * grid[1] * (t * (t // 2 + 1) + 2) > capi.GS_REGION_SPECTRUM_MAX:
+            grid = (0, 0)
+    except capi.GsError:
+        grid = (0, 0)  # (the call below refuses it, in the header's order)
+    power = np.zeros((max(n, 1),) + grid + (t, t // 2 + 1), np.float64)
+    tiles = np.zeros((max(n, 1),) + grid + (2,), np.uint64)
+    capi.check(context._lib.gs_fields_region_spectrum(context.handle, _handle_array(fields), n, rh, rw, tile, win,
+                                                      power.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                      tiles.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+    return [RegionSpectrum.from_raw(power[i], tiles[i], tile, win, (rh, rw), shape) for i in range(n)]
+
+
 def pinned_empty(shape: Sequence[int]) -> np.ndarray:
     """float32 array in page-locked host memory (``gs_host_alloc``) for overlapped downloads.
     The allocation is released when the last view of it is garbage-collected."""
@@ -1768,6 +1860,12 @@ class HipConcentration:
         ``bins`` equal bins of ``range``, counted on the device (``gs_fields_region_histogram``; blocking, collective in a
         multi-process context)."""
         return region_histogram_fields(context, [self], region, bins, [range])[0]
+
+    def region_spectrum(self, context: HipContext, region, tile: int = 64, window="hann") -> RegionSpectrum:
+        """The tile-averaged power spectrum of every region of ``region`` = (rh, rw) cells (an int: square) of this plane --
+        tiles of ``tile`` cells a side anchored at the region's first row and column --, summed on the device
+        (``gs_fields_region_spectrum``; blocking, collective in a multi-process context)."""
+        return region_spectrum_fields(context, [self], region, tile, window)[0]
 
     def change_from(self, context: HipContext, other: "HipConcentration") -> Change:
         """How far this plane is from ``other`` (this minus other, cell by cell in f64) over the whole global grid,
@@ -2171,6 +2269,14 @@ class Species:
         ``u_range`` for U and of ``v_range`` for V."""
         in_u, in_v, _, _ = self.in_out()
         u, v = region_histogram_fields(self._context, [in_u, in_v], region, bins, [u_range, v_range])
+        return u, v
+
+    def region_spectrum(self, region, tile: int = 64, window="hann") -> Tuple[RegionSpectrum, RegionSpectrum]:
+        """(U, V) tile-averaged power spectra of every region of the current state in one call
+        (``gs_fields_region_spectrum``; blocking, collective in a multi-process context): the region shape as for
+        ``region_morphology``, tiles of ``tile`` cells a side anchored at every region's first row and column."""
+        in_u, in_v, _, _ = self.in_out()
+        u, v = region_spectrum_fields(self._context, [in_u, in_v], region, tile, window)
         return u, v
 
     def snapshot(self) -> Snapshot:

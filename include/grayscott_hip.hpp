@@ -372,6 +372,9 @@ struct Spectrum {
 using RegionCorrelation = Regions<Correlation>;
 // (gs_fields_region_histogram): `at(i, j)` is the Histogram of region (i, j)'s cells alone, its `size` the region's own cells
 using RegionHistogram = Regions<Histogram>;
+// (gs_fields_region_spectrum): `at(i, j)` is the Spectrum of region (i, j)'s cells alone, tiles anchored at the region's first
+// row and column; a region in which no tile fits has zeros and no tiles
+using RegionSpectrum = Regions<Spectrum>;
 
 struct Parameters {
     std::array<std::array<Precision, 3>, 3> weights{{{0.25f, 0.5f, 0.25f}, {0.5f, 0.0f, 0.5f}, {0.25f, 0.5f, 0.25f}}};
@@ -936,6 +939,31 @@ class Species {
             for (std::size_t r = 0; r < regions; ++r)
                 both[p]->results.push_back(Histogram::from_c(out.data() + (p * regions + r) * each, bins, lo[p], hi[p],
                                                              detail::region_cells(s[0], s[1], rh, rw, r / rc, r % rc)));
+        }
+        return uv;
+    }
+    // (U, V) tile-averaged power spectra of every region of rh x rw cells of the current state, in one call
+    // (gs_fields_region_spectrum; blocking, collective in a multi-process context): tile and window as for spectrum()
+    std::pair<RegionSpectrum, RegionSpectrum> region_spectrum(int32_t rh, int32_t rw, int32_t tile = 64, bool hann = true)
+    {
+        gs_field *planes[2] = {u_.in().raw(), v_.in().raw()};
+        const std::size_t t = tile == 16 || tile == 32 || tile == 64 || tile == 128 ? (std::size_t)tile : 16;
+        const std::size_t bins = t * (t / 2 + 1); // (a refused tile: the call returns before it writes)
+        const Shape s = shape();
+        uint64_t rr = 0, rc = 0;
+        check(gs_region_grid(s[0], s[1], rh, rw, &rr, &rc));
+        // (a result over the cap is refused by the call; nothing that large is allocated for it)
+        const std::size_t regions = rr * rc * (bins + 2) <= (uint64_t)GS_REGION_SPECTRUM_MAX ? (std::size_t)(rr * rc) : 0;
+        std::vector<double> power(2 * regions * bins + 1);
+        std::vector<uint64_t> tiles(4 * regions + 1);
+        check(gs_fields_region_spectrum(context_->get(), planes, 2, rh, rw, tile, hann ? 1 : 0, power.data(), tiles.data()));
+        std::pair<RegionSpectrum, RegionSpectrum> uv;
+        RegionSpectrum *both[2] = {&uv.first, &uv.second};
+        for (std::size_t p = 0; p < 2; ++p) {
+            *both[p] = RegionSpectrum{rr, rc, rh, rw, {}};
+            for (std::size_t r = 0; r < regions; ++r)
+                both[p]->results.push_back(Spectrum::from_c(power.data() + (p * regions + r) * bins, tiles.data() + 2 * (p * regions + r),
+                                                            tile, hann ? 1 : 0));
         }
         return uv;
     }

@@ -810,7 +810,8 @@ int32_t gs_members_correlation(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint
  * Both block and have no side effects (ghost rows, tuner, graphs and gs_stats are left as they are).  GS_ERR_INVALID: a tile
  * or window outside the sets above or a null output -- decided before any handle is looked at --, a null or foreign handle,
  * mixed shapes, n outside 1..4, members outside the ensemble.
- * Not done: per-region spectra; the cross-spectrum of U with V; overlapping tiles; tiles that wrap. */
+ * Not done: the cross-spectrum of U with V; overlapping tiles; tiles that wrap.
+ * (For per-region spectra see gs_fields_region_spectrum, below.) */
 int32_t gs_spectrum_tables(int32_t tile, float *window, float *twiddle);
 int32_t gs_fields_spectrum(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t tile, int32_t window, double *power,
                            uint64_t *tiles);
@@ -1109,6 +1110,45 @@ int32_t gs_members_copy(gs_ctx *ctx, gs_ensemble *dst, gs_ensemble *src, uint64_
 #define GS_REGION_CHANGE_RECORDS_MAX (1ull << 28)
 int32_t gs_fields_region_compare(gs_ctx *ctx, gs_field *const *a, gs_field *const *b, int32_t n, int32_t rh, int32_t rw,
                                  gs_change *out);
+
+/* Regional power spectra: the tile-averaged structure factor of gs_fields_spectrum (above) of every REGION of the region grid
+ * of gs_region_grid -- the wavelength, with sub-cell resolution and no threshold, and the orientation and anisotropy of the
+ * stripes of each part of a parameter map's grid; the whole-grid spectrum of such a grid is a blend that belongs to no region.
+ * For a region shape (rh, rw) that gs_region_grid accepts, a tile T of 16, 32, 64 or 128 and window 0 or 1, the rule is the
+ * regional family's: a region's result is, bit for bit, what gs_fields_spectrum returns for a field that holds exactly that
+ * region's cells.  That is:
+ *   - tiles are anchored at the region's first row and first column; a region of h x w cells has floor(h / T) floor(w / T)
+ *     tiles, its remaining rows and columns are not looked at (a NaN there changes nothing);
+ *   - a tile with a cell that is not finite is skipped and counted, in its own region only;
+ *   - the arithmetic per tile is gs_fields_spectrum's, word for word, with the same tables;
+ *   - the fold is per region: a segment is up to 16 consecutive tiles of one band of the region, counted from the region's
+ *     first tile, and its record adds its tiles' power in ascending tile order from +0.0; a band's sum adds its segments in
+ *     ascending order from +0.0; the region's result adds its band sums in ascending order from +0.0;
+ *   - a region in which no tile fits -- a ragged last region, or rh < T or rw < T -- gets zeros and {0, 0};
+ *   - a region's border is a wall for tiles: no tile straddles two regions.  rh and rw need not be multiples of T.
+ * The bits are the same for any slab count, process count, step kernel or launch shape and do not depend on the boundary
+ * rule; with a domain mask attached wall cells count.  Where rh and rw are multiples of T the regions partition the whole
+ * grid's tiles: the counts add up to gs_fields_spectrum's exactly, the power only to rounding (the fold orders differ).
+ *   gs_fields_region_spectrum  power[(((p RR + i) RC + j) T + kr) (T/2 + 1) + kc], the raw f64 sums, and
+ *                              tiles[((p RR + i) RC + j) 2 + {0: used, 1: skipped}] for region (i, j) of fields[p], p < n
+ *                              (1..4 fields of one shape).
+ * The call follows its regional twins: one wait for enqueued work (as gs_fields_summarize), per slab one launch over the
+ * regions' segments and one that adds them per region -- the device finishes every region, the host adds nothing --, blocking,
+ * no side effects (ghost rows, tuner, graphs and gs_stats are left as they are), collective in a multi-process context with
+ * every rank receiving every region; an empty plane: GS_OK, nothing is written.  GS_ERR_INVALID, decided in this order: a null
+ * output; a tile or window outside the sets above; rh or rw refused by gs_region_grid -- these three before any handle is
+ * looked at --; a null or foreign handle, mixed shapes, n outside 1..4; RR RC > GS_REGIONS_MAX; RR RC (T (T/2 + 1) + 2) >
+ * GS_REGION_SPECTRUM_MAX result words per field (a cap on result memory: 256 MiB per field); the words of segment records
+ * over the n fields -- n times the sum over the regions of (bands of the region) (segments of a band of the region)
+ * (T (T/2 + 1) + 2), computed from the global shape alone, so that every rank and every slab count reaches the same verdict
+ * -- > GS_REGION_SPECTRUM_RECORDS_MAX (a cap on scratch memory: 1 GiB).  GS_ERR_UNSUPPORTED, on every rank alike: some slab
+ * begins at a row that is no multiple of rh -- a region lies inside one slab, so nothing is staged and no ghost row is read;
+ * there is no condition on T at the seams.
+ * Not done: regions of ensemble members; regions that straddle slabs; overlapping tiles. */
+#define GS_REGION_SPECTRUM_MAX (1u << 25)
+#define GS_REGION_SPECTRUM_RECORDS_MAX (1ull << 27)
+int32_t gs_fields_region_spectrum(gs_ctx *ctx, gs_field *const *fields, int32_t n, int32_t rh, int32_t rw, int32_t tile,
+                                  int32_t window, double *power, uint64_t *tiles);
 
 /* Time statistics formed on the device: per-cell accumulators over the SAMPLES of a run -- is a cell steady, pulsating or
  * chaotic (variance), what does the time-averaged field look like (mean), where has a spot been (maximum), when did the front

@@ -117,6 +117,10 @@ pub struct gs_morphology {
 pub const GS_REGIONS_MAX: u64 = 1 << 22;
 /// `GS_REGION_HIST_MAX` (include/gs_hip.h): the most counters per field one regional histogram call returns.
 pub const GS_REGION_HIST_MAX: u64 = 1 << 25;
+/// `GS_REGION_SPECTRUM_MAX` (include/gs_hip.h): the most result words per field one regional spectrum call returns.
+pub const GS_REGION_SPECTRUM_MAX: u64 = 1 << 25;
+/// `GS_REGION_SPECTRUM_RECORDS_MAX` (include/gs_hip.h): the most segment-record words over the fields of one such call.
+pub const GS_REGION_SPECTRUM_RECORDS_MAX: u64 = 1 << 27;
 
 /// `gs_change` (include/gs_hip.h): how far one plane is from another -- sums of |d| and d * d and the largest |d| over the
 /// cells finite in both (d = a - b in f64), cells whose bits differ, cells not finite in either.  40 bytes.
@@ -298,6 +302,19 @@ extern "C" {
         hi: *const f32,
         bins: i32,
         out: *mut u64,
+    ) -> i32;
+    /// `power`: n x rr x rc x tile x (tile / 2 + 1) raw f64 sums, `tiles`: n x rr x rc x 2 counts {used, skipped} -- the
+    /// spectrum of every region's cells alone, at most `GS_REGION_SPECTRUM_MAX` words per field.
+    pub fn gs_fields_region_spectrum(
+        ctx: *mut gs_ctx,
+        fields: *const *mut gs_field,
+        n: i32,
+        rh: i32,
+        rw: i32,
+        tile: i32,
+        window: i32,
+        power: *mut f64,
+        tiles: *mut u64,
     ) -> i32;
     /// Pair i: `a[i]` against `b[i]`, n = 1..4 pairs of one shape; `out`: n records.
     pub fn gs_fields_compare(
