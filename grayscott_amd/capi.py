@@ -72,6 +72,7 @@ EXPORTS = (
     "gs_time_stats_create", "gs_time_stats_destroy", "gs_time_stats_reset", "gs_time_stats_accumulate", "gs_time_stats_samples",
     "gs_time_stats_result", "gs_time_stats_download",
     "gs_members_time_stats_create", "gs_members_time_stats_accumulate", "gs_members_time_stats_result",
+    "gs_ctx_quiet_stats",
 )
 
 
@@ -262,6 +263,7 @@ def load() -> ctypes.CDLL:
         "gs_field_colormap": (i32, [vp, vp, f32, vp, i32, vp]),
         "gs_ctx_stats": (i32, [vp, P(GsStats)]),
         "gs_ctx_set_pass_timing": (i32, [vp, i32]),
+        "gs_ctx_quiet_stats": (i32, [vp, P(u64)]),
         "gs_field_mark_written": (i32, [vp, vp]),
         "gs_rccl_selftest": (i32, [i32, u64]),
         "gs_runtime_info": (i32, [i32, ctypes.c_char_p, ctypes.c_size_t]),

@@ -185,6 +185,44 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
     hipError_t e;
     switch (kernel) {
     case GS_KERNEL_TB:
+        if (ctx->quiet.mode > 0 && !fused && at.kind == GS_ATTACH_NONE) {
+            // a full pass of run_steps' loop that may leave its units at rest alone (gs_kernels.h: GsQuiet)
+            gs_ctx::QuietRt &qr = ctx->quiet;
+            e = hipSuccess;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                GsQuiet q;
+                q.in = qr.words + (size_t)qr.in_slot * qr.cap;
+                q.out = qr.words + (size_t)(1 - qr.in_slot) * qr.cap;
+                q.skipped = qr.skipped;
+                q.mode = qr.mode;
+                q.cap = (int64_t)qr.cap;
+                q.need = 0;
+                q.launched = 0;
+                if (qr.mode == 1 && qr.words) // edge positions are never written: they stay "unknown"
+                    e = hipMemsetAsync(qr.words, 0, 2 * qr.cap * sizeof(uint32_t), stream);
+                if (e == hipSuccess) e = gs_launch_tb_strict(a, fuse, stream, &name, at, &q);
+                if (e != hipSuccess) break;
+                if (q.need > (int64_t)qr.cap && qr.mode == 1) { // nothing was launched: room for this geometry first
+                    if (qr.words) { GS_HIP(hipStreamSynchronize(stream)); GS_HIP(hipFree(qr.words)); qr.words = nullptr; qr.cap = 0; }
+                    GS_HIP(hipMalloc(&qr.words, 2 * (size_t)q.need * sizeof(uint32_t)));
+                    qr.cap = (size_t)q.need;
+                    if (!qr.skipped) {
+                        GS_HIP(hipMalloc(&qr.skipped, (size_t)kQuietCounters * kQuietCounterStride * sizeof(unsigned long long)));
+                        GS_HIP(hipMemset(qr.skipped, 0, (size_t)kQuietCounters * kQuietCounterStride * sizeof(unsigned long long)));
+                    }
+                    continue;
+                }
+                if (q.launched > 0) {
+                    qr.launched += (uint64_t)q.launched;
+                    qr.passes++;
+                    if (qr.mode == 3) qr.steady++;
+                } else {
+                    qr.refused = true;
+                }
+                break;
+            }
+            break;
+        }
         e = fused ? gs_launch_tb_fused(a, fuse, stream, &name, at) : gs_launch_tb_strict(a, fuse, stream, &name, at);
         break;
     case GS_KERNEL_SIMPLE:
@@ -623,6 +661,10 @@ int32_t gs_ctx_destroy(gs_ctx *ctx)
         if (ctx->win.desc) (void)hipFree(ctx->win.desc);
     }
     if (ctx->win.seen) (void)hipHostFree(ctx->win.seen);
+    if (!ctx->slabs.empty() && (ctx->quiet.words || ctx->quiet.skipped) && hipSetDevice(ctx->slabs[0].device) == hipSuccess) {
+        if (ctx->quiet.words) (void)hipFree(ctx->quiet.words);
+        if (ctx->quiet.skipped) (void)hipFree(ctx->quiet.skipped);
+    }
     if (ctx->graph_exec) (void)hipGraphExecDestroy(ctx->graph_exec);
     if (ctx->graph) (void)hipGraphDestroy(ctx->graph);
     if (ctx->band_join) (void)hipEventDestroy(ctx->band_join);
@@ -675,6 +717,7 @@ int32_t gs_ctx_create(gs_ctx **out, const gs_params *params, const gs_options *o
     if (opts) ctx->o = *opts; else gs_default_options(&ctx->o);
     ctx->rank = rank;
     ctx->world = world;
+    ctx->quiet.enabled = gs_env_int("GS_HIP_QUIET_UNITS", 1, 0, 1) != 0; // per context: one process may hold both kinds
     int32_t st = check_math(ctx->p, ctx->o.math);
     if (st == GS_OK && ctx->o.cols_per_lane != 0 && ctx->o.cols_per_lane != 1 && ctx->o.cols_per_lane != 2 &&
         ctx->o.cols_per_lane != 4)
@@ -945,10 +988,32 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
     const int kk = tuned_shape(ctx, u0, fuse) && ctx->tuner().tuned.k > 0 && ctx->tuner().tuned.k <= fuse ? ctx->tuner().tuned.k : fuse;
     const int V = bands_for(ctx, u0, kk);
     if (ctx->o.use_graph && single && V == 1 && kk > 1) GS_TRY(replay_graph_batches(r, kk));
+    // Units at rest (gs_kernels.h: GsQuiet): the full passes of this loop, one launch each, run the quiet entries where the
+    // call is eligible -- the first two of them compute everything and leave the words of both slots, the later ones skip.
+    // The layout and the planes are those of the whole loop (the tuner's trial passes are behind us and never skip);
+    // (1, +0) is a fixed point of the update only while every operand of it is finite.
+    gs_ctx::QuietRt &qr = ctx->quiet;
+    const gs_params &pp = ctx->p;
+    bool quiet = qr.enabled && single && V == 1 && !ctx->o.use_graph && !mapped && kk >= 2 && kk <= 4 &&
+                 ctx->o.math == GS_MATH_STRICT && (ctx->o.boundary == GS_BOUNDARY_CLIPPED || ctx->o.boundary == GS_BOUNDARY_ZERO_HALO) &&
+                 (ctx->o.kernel == GS_KERNEL_AUTO || ctx->o.kernel == GS_KERNEL_TB || ctx->o.kernel == GS_KERNEL_TILE ||
+                  ctx->o.kernel == GS_KERNEL_WINDOW) &&
+                 std::isfinite(pp.du) && std::isfinite(pp.dv) && std::isfinite(pp.feed) && std::isfinite(pp.kill) &&
+                 std::isfinite(pp.feed + pp.kill) && std::isfinite(pp.dt);
+    for (int i = 0; i < 9; ++i) quiet = quiet && std::isfinite(pp.w[i / 3][i % 3]);
+    qr.refused = false;
+    int quiet_pass = 0;
     const char *full_pass = nullptr;
     while (r.n < steps) {
         const int k = (steps - r.n) >= (uint64_t)kk ? kk : (int)(steps - r.n);
-        GS_TRY(r.advance(k == kk ? V : 1, k));
+        if (quiet && k == kk && !qr.refused) {
+            qr.mode = quiet_pass < 2 ? quiet_pass + 1 : 3;
+            qr.in_slot = r.in;
+            ++quiet_pass;
+        }
+        const int32_t st = r.advance(k == kk ? V : 1, k);
+        qr.mode = 0;
+        GS_TRY(st);
         if (k == kk) full_pass = ctx->last_kernel;
     }
     if (full_pass) ctx->last_kernel = full_pass; // gs_ctx_info names the full pass, not a remainder
@@ -1039,6 +1104,23 @@ int32_t gs_ctx_stats(gs_ctx *ctx, gs_stats *out)
             out->interior_ms = (float)interior;
             out->halo_exposed_ms = (float)exposed;
         }
+    }
+    return GS_OK;
+}
+
+int32_t gs_ctx_quiet_stats(gs_ctx *ctx, uint64_t out[4])
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(sync_all(ctx));
+    out[0] = ctx->quiet.launched;
+    out[1] = 0;
+    out[2] = ctx->quiet.passes;
+    out[3] = ctx->quiet.steady;
+    if (ctx->quiet.skipped) {
+        unsigned long long host[kQuietCounters * kQuietCounterStride];
+        GS_HIP(hipSetDevice(ctx->slabs[0].device));
+        GS_HIP(hipMemcpy(host, ctx->quiet.skipped, sizeof host, hipMemcpyDeviceToHost));
+        for (int i = 0; i < kQuietCounters; ++i) out[1] += host[i * kQuietCounterStride];
     }
     return GS_OK;
 }

@@ -60,6 +60,8 @@ __device__ __forceinline__ unsigned long long trace_now()
 //                         before the launch gives up (default 2^20, 2-3 s; tests set 1 to provoke it)
 //   GS_HIP_WINDOW_WAVES   "left,interior,right": waves in use per window of the left-most / inner / right-most tile column
 //                         of the persistent window kernel's tiling (gs_window.cpp: plan_windows)
+//   GS_HIP_QUIET_UNITS    0 = units at rest are recomputed like any other: the production entries run (default 1: the quiet
+//                         entries where a call is eligible); read when a context is created
 constexpr int kGsXcdGroupMax = 512; // 8 * 512 workgroups per renumbered group at most
 inline int gs_env_int(const char *name, int unset, int lo, int hi)
 {

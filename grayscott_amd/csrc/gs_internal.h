@@ -223,6 +223,19 @@ struct gs_ctx {
         int32_t *seen = nullptr; // pinned, two words: the abort word as either image stream last saw it
     } win;
     int cu_count = 0; // compute units of the first slab's device
+    // Units at rest (gs_kernels.h: GsQuiet).  The words are trusted only inside the loop of full passes
+    // of one run_steps call, which sets `mode` and `in_slot` around every pass it offers to the quiet entries; launch_rows
+    // hands them to the launcher and counts what it reports.  Nothing is carried from one call to the next.
+    struct QuietRt {
+        bool enabled = true;         // GS_HIP_QUIET_UNITS (read by gs_ctx_create)
+        uint32_t *words = nullptr;   // device: the words of slot 0, then of slot 1, `cap` each
+        size_t cap = 0;
+        unsigned long long *skipped = nullptr; // device: kQuietCounters counters, kQuietCounterStride words apart
+        int mode = 0;                // GsQuiet::mode of the pass being enqueued; 0 = a pass like any other
+        int in_slot = 0;             // the slot that pass reads
+        bool refused = false;        // the launcher ran the production entry instead (the geometry is not eligible)
+        uint64_t launched = 0, passes = 0, steady = 0; // gs_ctx_quiet_stats: units and passes of the quiet entries, mode-3 passes
+    } quiet;
     std::vector<struct gs_time_stats *> time_stats; // the time statistics made on this context and not destroyed yet (gs_time_stats.cpp)
     // The context's per-cell data (gs_attached.cpp), one kind at a time: a parameter map (gs_ctx_set_param_map: plane[0] = F,
     // plane[1] = F + K) or a domain mask (gs_ctx_set_mask: plane[0] = a u32 link word per cell, gs_cell.h: link_bit).  The

@@ -85,6 +85,26 @@ struct GsMapPlanes {
 struct GsMaskPlanes {
     const float *link;
 };
+// Units at rest (gs_step_tb_dx_qk): one word per unit position -- row chunk cc of range a, strip -- of
+// the planes a full pass reads (`in`) and of the ones it writes (`out`), at [cc * strips + strip]: kQuietRest = every cell
+// of the chunk's rows x the strip's output columns in that slot's planes is bitwise (U, V) = (1.0f, +0.0f), kQuietActive =
+// not so, 0 = unknown (edge positions, always).  The second argument of the quiet entries: GsStepArgs, and with it every
+// other kernel's code, stays as it is.  mode: 1 = the first full pass of a gs_run (no word is read; every interior unit
+// computes, checks what it stores and writes its word in `out`), 2 = the second (`in` is read: a unit whose own word
+// there says "active" writes "active" without a check), 3 = every later one (a unit whose nine positions in `in` and own
+// position in `out` are at rest leaves at once).  cap: the words each array holds.  The launcher hands this back with
+// `need` = the words the launch's geometry takes and `launched` = its units, or 0 when the launch is not one of the quiet
+// entries' (it then ran the production entry and touched no word); with need > cap in mode 1 it launches nothing.
+constexpr uint32_t kQuietRest = 1, kQuietActive = 2;
+constexpr int kQuietCounters = 64, kQuietCounterStride = 16; // the skipped-unit counters: 64 of them, 128 bytes apart
+struct GsQuiet {
+    const uint32_t *in;
+    uint32_t *out;
+    unsigned long long *skipped; // += 1 per skipping wave, at [(workgroup % kQuietCounters) * kQuietCounterStride]
+    int32_t mode;
+    int32_t pad;
+    int64_t cap, need, launched; // (host side only)
+};
 // What a context's per-cell data (a map or a mask, never both) is to the launchers of the simple, streaming and marching
 // kernels: the kernel set it selects -- GS_ATTACH_NONE: the uniform kernels -- and one slab's planes, local row 0, column 0:
 // the map's F and F + K, or the mask's link plane.  The launchers hand them to the kernels as GsMapPlanes / GsMaskPlanes.
@@ -171,7 +191,7 @@ struct GsEnsArgs {
     hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
     hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
     hipError_t gs_launch_resident_##SUFFIX(const GsStepArgs &a, int steps, hipStream_t s, const char **name); \
-    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
+    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at = GsAttached(), GsQuiet *quiet = nullptr); \
     hipError_t gs_launch_tile_##SUFFIX(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name); \
     hipError_t gs_launch_lds_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name);  \
     hipError_t gs_launch_window_##SUFFIX(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name); \
@@ -193,6 +213,8 @@ GS_DECLARE_LAUNCHERS(fused)
 // rule: the kernel set of the boundary rule, 0 = the clipped and zero-halo rules' kernels, 1 = the periodic rule's
 // (gs_step_tb_pk and kin), 2 = the zero-flux rule's (gs_step_tb_nk and kin).
 const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule = 0);
+// ... and of the quiet entries (gs_step_tb_dx_qk: GsQuiet) for k = 2, 3, 4 fused steps; nullptr otherwise.
+const void *gs_tb_quiet_kernel_strict(int k);
 // gs_launch_map_rates_*: fpk[i] = feed[i] + kill[i] over n floats, one f32 add in the flavour's float mode (strict: a
 // sub-normal sum is flushed, as the reference's DenormalsFlusher does).  gs_tb_map_kernel_*: the entry of the marching
 // kernel's map form (gs_step_tb_mk: its own translation unit, GS_TB_MAP_ONLY) for k fused steps, fast in {0, 3} (3: the

@@ -336,8 +336,16 @@ __host__ __device__ constexpr int tb_halo_floats(int k, bool cross) { return cro
 // levels' arithmetic.
 // MASK: the domain mask's form (gs_step_tb_wk), mp.feed = the link plane (a u32 word per cell in the species' layout):
 // fetch_map's loads of that one plane, the cells computed by cell_masked.
-template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false, bool MAP = false, bool MASK = false>
-__device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, int strip, int lane, const GsMapPlanes &mp,
+// CHECK (the quiet entries, gs_step_tb_dx_qk; the march with full difference sharing only): the march also reports whether
+// it stored anything but a cell at rest -- in the branch around the stores the lanes that store compare the bits of what
+// they store with (1.0f, +0.0f) and OR the lane masks of the comparisons.  What is gathered inside that branch is a value
+// per lane (the sacrificial lanes, which are off there, keep a stale one): the march has the two vector registers to spare
+// and no scalar ones -- the same masks gathered outside the branch, as scalars, spilled 26 to 29 of them, and the differing
+// bits gathered in one vector register outside it took K = 4 to 128 registers and 4 spills -- so the storing lanes are
+// asked once, at the end.  The return value: the lanes that hold a non-zero mask, 0 = every cell stored is at rest (0
+// without CHECK).
+template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false, bool MAP = false, bool MASK = false, bool CHECK = false>
+__device__ __forceinline__ unsigned long long tb_march(const GsStepArgs &a, int ur0, int ur1, int strip, int lane, const GsMapPlanes &mp,
                                          const FairBoard &fb GS_TRACE_PARAM)
 {
     constexpr int S = tb_sacrificial_lanes(K, CPL), W = tb_cols_per_wave(K, CPL);
@@ -491,6 +499,7 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
     constexpr bool VS = EDGE == 0 && (FAST & 5) == 5 && !GS_MATH_FUSED && CPL == 2;
     if constexpr (VS) {
         constexpr bool XS = (FAST & 8) != 0; // ... and across lanes (cells_xshare): only the left neighbour's second column is handed over
+        unsigned long long dirty = 0; // CHECK: lanes that stored a cell not at rest, as the storing lanes know them
         RowQ<CPL> R[K][2]; // own columns of the two newest rows of level j
         TapCarry<CPL> C[K];
 #pragma unroll
@@ -569,6 +578,12 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
                 } else if (store && store_ok) {
                     store_cols_buf<CPL>(wu, voff, (l0 - K - ur0) * pitch_bytes, nu);
                     store_cols_buf<CPL>(wv, voff, (l0 - K - ur0) * pitch_bytes, nv);
+                    if constexpr (CHECK) {
+#pragma unroll
+                        for (int e = 0; e < CPL; ++e)
+                            dirty |= __builtin_amdgcn_ballot_w64(__builtin_bit_cast(uint32_t, nu[e]) != 0x3f800000u) |
+                                     __builtin_amdgcn_ballot_w64(__builtin_bit_cast(uint32_t, nv[e]) != 0u);
+                    }
                 }
             }
             if constexpr (LATE) q[qs] = fetch(l0 + 3); // two rows in flight while the levels are computed
@@ -585,8 +600,9 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
 #pragma unroll
         for (int s6 = 0; s6 < 5; ++s6)
             if (t + s6 < nticks) vs_tick(t + s6, s6 & 1, (2 * K + s6) % 3, K, true);
-        return;
+        return CHECK ? __builtin_amdgcn_ballot_w64(store_ok && dirty != 0ull) : 0ull;
     }
+    static_assert(!CHECK || VS, "the check is built into the march with full difference sharing");
 
     RowT<CPL> w[K][3]; // w[j][slot]: level-j rows, newest in slot (tick % 3)
 #pragma unroll
@@ -669,6 +685,7 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
             }
         }
     }
+    return 0;
 }
 
 // WG: waves per workgroup.  4 independent waves, or all 16 of a CU with the progress board of tb_march<FAIR>.
@@ -676,9 +693,18 @@ __device__ __forceinline__ void tb_march(const GsStepArgs &a, int ur0, int ur1, 
 // NEU: the zero-flux rule's kernels (GsStepArgs::zero_halo = 3; gs_step_tb_nk and its kin).
 // MAP: the parameter map's forms (gs_step_tb_mk): 4-wave workgroups, no difference sharing.  MASK: the domain mask's
 // (gs_step_tb_wk), likewise; mp.feed is the link plane.
-template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false, bool MASK = false>
-__device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr})
+// QUIET: the quiet entries (gs_step_tb_dx_qk; gs_kernels.h: GsQuiet).  An interior unit reads the words of the nine
+// positions around it in the slot it reads and of its own position in the slot it writes -- once, a lane each -- and, in
+// mode 3 with all ten at rest, leaves: no loads, no arithmetic, no stores; its word stays.  Otherwise it marches as ever and
+// then writes its word: "active" without a look when its own input position was active (a developed pattern pays
+// nothing), else by the march's check of what it stored -- a unit at rest that a front enters is caught in the pass in
+// which that happens.  Edge units (first and last strip, chunks that touch the grid's first or last rows, the halves of
+// edge_split = 2) never read or write a word, so they and their inner neighbours always compute.
+template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false, bool MASK = false, bool QUIET = false>
+__device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
+                                        const GsQuiet &qa = GsQuiet{})
 {
+    static_assert(!QUIET || (WG == 4 && !PER && !NEU && !MAP && !MASK), "the quiet entries are 4-wave marches of the uniform kernels");
     static_assert(!MAP || (WG == 4 && (FAST & 4) == 0), "the map forms are 4-wave marches without difference sharing");
     static_assert(!MASK || (!MAP && WG == 4 && (FAST & 4) == 0), "the mask forms are 4-wave marches without difference sharing");
     // half_diff needs MODE.IEEE = 0: hwreg(HW_REG_MODE, offset 9, width 1).  The bit only governs
@@ -765,10 +791,12 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &
         }
     }
     int ur0, ur1;
+    int row_chunk = -1; // of range a, counted from its first rows
     if (chunk < chunks_a) {
         // the last chunks of the range first, then chunks 0, 1, 2, ... (bottom / top edge chunks)
         const int bf = min(a.bot_first, chunks_a);
         const int cc = chunk < bf ? chunks_a - 1 - chunk : chunk - bf;
+        row_chunk = cc;
         if (cc < a.big_chunks) {
             ur0 = a.ra0 + cc * rpu;
             ur1 = ur0 + rpu;
@@ -806,6 +834,36 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &
     // path with the rule's cell (ZH = 3): at every level, a row on the grid's top or bottom edge stands in for the missing
     // row and a cell in the first or last column for the missing column, so no row or column outside the grid is read.
     constexpr bool KINDS = (FAST & 1) && !GS_MATH_FUSED;
+    if constexpr (QUIET) {
+        if (!edge) { // wave-uniform
+            // (An interior unit has a chunk above and below it and a strip on either side: every index is a position's.
+            // The launcher sends only passes over range a here, whose half-height units are all edge units: `inner` holds.)
+            const bool inner = half < 0 && row_chunk >= 0;
+            const int pos = row_chunk * strips + strip;
+            uint32_t *const mine = inner ? qa.out + pos : nullptr; // this unit's word in the slot it writes
+            bool look = inner; // check what this unit stores
+            if (inner && qa.mode >= 2) {
+                const int nb = lane < 9 ? lane : 4;
+                uint32_t word = kQuietRest;
+                if (lane < 9) word = qa.in[pos + (nb / 3 - 1) * strips + (nb % 3 - 1)];
+                else if (lane == 9 && qa.mode == 3) word = qa.out[pos];
+                if (qa.mode == 3 && __builtin_amdgcn_ballot_w64(word != kQuietRest) == 0) {
+                    if (lane == 0)
+                        (void)__hip_atomic_fetch_add(qa.skipped + ((int)blockIdx.x % kQuietCounters) * kQuietCounterStride, 1ull,
+                                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    return;
+                }
+                look = __builtin_amdgcn_ballot_w64(lane == 4 && word == kQuietActive) == 0;
+            }
+            unsigned long long dirty = 1;
+            if (look)
+                dirty = tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK, true>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            else
+                tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            if (mine && lane == 0) *mine = dirty ? kQuietActive : kQuietRest;
+            return;
+        }
+    }
     if constexpr (PER) {
         if (!edge)
             tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
@@ -863,6 +921,13 @@ template <int K, int WG = 4>
 __global__ __launch_bounds__(WG * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_dx_k)(GsStepArgs a)
 {
     tb_unit<K, 15, 2, WG>(a);
+}
+// The quiet entries: gs_step_tb_dx_k's 4-wave form for full passes that leave units at rest alone (tb_unit<QUIET>; the
+// clipped and zero-halo rules).  Kernels of their own, so that the code of the ones above does not change.
+template <int K>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) void GS_SUFFIX(gs_step_tb_dx_qk)(GsStepArgs a, GsQuiet q)
+{
+    tb_unit<K, 15, 2, 4, false, false, false, false, true>(a, GsMapPlanes{nullptr, nullptr}, q);
 }
 // The periodic rule's forms of the three (GsStepArgs::zero_halo = 2): separate kernels, so that the code of the ones above
 // does not change.

@@ -550,8 +550,9 @@ int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, int kind
     return fn ? 1024 * tb_waves_of(fn) : 0;
 }
 
-hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at)
+hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at, GsQuiet *quiet)
 {
+    if (quiet) { quiet->need = 0; quiet->launched = 0; }
     // "cN": N columns per lane (4 = the wide layout); ".op": the variant specialised for the
     // default (Oono-Puri) side weights, with or without dt == 1
     // ".op.ds": ... and with full difference sharing (cells_vshare)
@@ -646,6 +647,13 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     static const int split_env = gs_env_int("GS_HIP_EDGE_SPLIT", -1, 0, 1);
     const long er = ((strips - 1) * W + tb_sacrificial_lanes(k, cpl) * cpl >= a.cols && strips >= 2) ? 2 : 1, ne = 1 + er;
     bool split = 4 * chunks * strips <= 5 * slots && rpu >= 2;
+    // Units at rest (GsQuiet, below): a pass that may skip is, on a grid mostly at rest, a launch of less than one round
+    // whose length is the edge units' march -- they never rest -- so they come as halves there as in every such launch.
+    // (The words are per chunk and strip, and edge units have none: the halves change nothing for them.)
+    const bool quiet_ok = !GS_MATH_FUSED && quiet && quiet->mode >= 1 && quiet->mode <= 3 && at.kind == GS_ATTACH_NONE && per == 0 &&
+                          fast == 15 && cpl == 2 && a.rb1 <= a.rb0 && !a.top_present && !a.bottom_present && rpu >= k && small >= k &&
+                          tiny >= k && chunks * strips <= 0x7fffffffL;
+    if (quiet_ok && quiet->mode == 3 && rpu >= 2) split = true;
     if (split_env >= 0) split = split_env != 0;
     long units = chunks * strips;
     args.edge_split = 1;
@@ -694,6 +702,24 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     args.xcd_m = xcd_env >= 0 ? xcd_env : (units >= 2 * slots ? 16 : 0);
     // the edge units at the head of the dispatch order stay dealt over all XCDs (they are the slow ones)
     args.xcd_first = (int32_t)(((chunks * ne * (args.edge_split == 2 ? 2 : 1) + 3) / 4 + 7) / 8 * 8);
+#if !GS_MATH_FUSED
+    // Units at rest (GsQuiet): the quiet entry in place of gs_step_tb_dx_k's 4-wave form where the geometry allows it -- a
+    // whole slab with the grid's edges above and below it as one row range, and every chunk but the last (an edge chunk) at
+    // least k rows high: the input window of an interior unit then lies within the chunks above and below its own and the
+    // strips left and right of it, the nine positions whose words it reads.  Same label: it is the same march.
+    if (quiet_ok) {
+        if (const void *qfn = gs_tb_quiet_kernel_strict(k)) {
+            quiet->need = chunks * strips;
+            if (quiet->need <= quiet->cap && quiet->in && quiet->out && quiet->skipped) {
+                GsQuiet q = *quiet;
+                void *qargs[] = {&args, &q};
+                quiet->launched = units;
+                return hipLaunchKernel(qfn, dim3((unsigned)blocks), dim3(256), qargs, 0, s);
+            }
+            if (quiet->mode == 1) return hipSuccess; // (the caller makes room and comes again)
+        }
+    }
+#endif
     return launch_attached(fn, blocks, args, at, s);
 }
 
@@ -812,6 +838,15 @@ static const void *tb_op_kernel(int k, int fast, int cpl, int wg)
 #undef GS_TB_CASES
 #undef GS_TB_CASE
 #undef GS_OP_FN
+}
+const void *gs_tb_quiet_kernel_strict(int k)
+{
+    switch (k) {
+    case 2: return GS_FN(gs_step_tb_dx_qk, 2);
+    case 3: return GS_FN(gs_step_tb_dx_qk, 3);
+    case 4: return GS_FN(gs_step_tb_dx_qk, 4);
+    default: return nullptr;
+    }
 }
 const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule)
 {

@@ -205,6 +205,14 @@ class HipContext:
         capi.check(self._lib.gs_ctx_stats(self.handle, ctypes.byref(st)))
         return {name: getattr(st, name) for name, _ in capi.GsStats._fields_ if name != "reserved"}
 
+    def quiet_stats(self) -> Tuple[int, int, int, int]:
+        """``gs_ctx_quiet_stats``: units launched by the passes that may leave units at rest alone, units among them
+        that left without computing, those passes, and the ones among them that could skip (the third and later full
+        passes of their ``gs_run``), all since the context was created."""
+        out = (ctypes.c_uint64 * 4)()
+        capi.check(self._lib.gs_ctx_quiet_stats(self.handle, out))
+        return int(out[0]), int(out[1]), int(out[2]), int(out[3])
+
     def set_pass_timing(self, passes: int) -> None:
         capi.check(self._lib.gs_ctx_set_pass_timing(self.handle, passes))
 

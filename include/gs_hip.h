@@ -57,6 +57,8 @@
  *                           of those it holds (0-3 the planes' own, 4 and up drawn), without probes
  *     GS_HIP_EDGE_KINDS     0 = edge units of the marching kernel all take the general path
  *     GS_HIP_EDGE_SPLIT     0 / 1 = never / always dispatch edge units as two half-height units
+ *     GS_HIP_QUIET_UNITS    0 = units of the marching kernel at rest are recomputed like any other (default 1: gs_run's full
+ *                           passes skip them where the call is eligible, gs_ctx_quiet_stats); read by gs_ctx_create
  *     GS_HIP_FAIR           0 / 1 = never / always run one-round launches as in-step 16-wave workgroups
  *     GS_HIP_FAIR_FROM      progress (0 ... 256) from which the in-step form steers wave priorities
  *     GS_HIP_XCD_M          0 = plain workgroup order, n = XCD-aware renumbering in groups of 8 n workgroups
@@ -481,6 +483,14 @@ int32_t gs_ctx_stats(gs_ctx *ctx, gs_stats *out);
 /* Time the next `passes` passes (0..4096; 0 = off) of every local slab of a slab chain with HIP events on
  * the halo and compute streams; gs_ctx_stats waits for them and reports the sums.  Waits for enqueued work. */
 int32_t gs_ctx_set_pass_timing(gs_ctx *ctx, int32_t passes);
+/* Units at rest.  (U, V) = (1.0f, +0.0f) is a fixed point of the update bit for bit, so a unit of the marching kernel --
+ * a wave's rows x columns of a pass -- whose whole input window and whose output rows hold nothing else is not
+ * recomputed by the full passes of a gs_run from the third on (single slab, one launch per pass, clipped or zero-halo
+ * rule, strict math, finite parameters, no map, no mask, no graph; GS_HIP_QUIET_UNITS=0 when the context is created
+ * switches it off).  The results are the same bits either way.  out[0] = units launched by the passes that took part,
+ * out[1] = units among them that left without computing, out[2] = those passes, out[3] = the ones among them that could
+ * skip (the third and later of their gs_run), all since the context was created.  Waits for enqueued work. */
+int32_t gs_ctx_quiet_stats(gs_ctx *ctx, uint64_t out[4]);
 
 /* Introspection for tests and the bench: name of the kernel variant last launched
  * ("tb-k4/strict@32x2" = 4 fused steps, strict math, tuned: 32-row units, 2 row bands; the periodic rule's kernels

@@ -33,6 +33,7 @@ def main():
         sim.perform_steps(sp, a.tune_steps)
     ctx = sim.context
     l0 = ctx.stats()["launches"]
+    q0 = ctx.quiet_stats()
     ctx.timer_start()
     for _ in range(a.calls):
         sim.prepare_steps(sp, a.steps)
@@ -43,6 +44,9 @@ def main():
                       "Mcells_steps_per_s": a.rows * a.cols * a.steps * a.calls / (ms * 1e-3) / 1e6,
                       "launches_per_call": (st["launches"] - l0) / a.calls, "ms_per_call": ms / a.calls,
                       "window_fallbacks": st["window_fallbacks"],
+                      # units at rest: [units launched by eligible passes, units skipped, eligible passes, passes that could skip]
+                      # of the timed calls
+                      "quiet_stats": [x - y for x, y in zip(ctx.quiet_stats(), q0)],
                       # the layout that ran: chosen by gs_run's tuner, or pinned through GS_HIP_ROWS_PER_BLOCK / _FUSE_STEPS / _COLS_PER_LANE
                       "tuned": ctx.get_tuned(a.rows, a.cols) if ctx.get_tuned(a.rows, a.cols)[0] else
                       (ctx.args.rows_per_block, ctx.args.fuse_steps, ctx.args.cols_per_lane, ctx.args.share_taps),
