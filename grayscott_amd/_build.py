@@ -45,6 +45,9 @@ UNITS = [
     # the domain mask's forms of the marching kernel (gs_step_tb_wk), likewise
     ("gs_step_kernels.hip", "gs_step_strict_mask.o", STRICT + ["-DGS_TB_MASK_ONLY=1"] + KERNEL_FLAGS),
     ("gs_step_kernels.hip", "gs_step_fused_mask.o", ["-DGS_MATH_FUSED=1", "-DGS_TB_MASK_ONLY=1"] + KERNEL_FLAGS),
+    # the noise forms of the marching kernel (gs_step_tb_zk), likewise
+    ("gs_step_kernels.hip", "gs_step_strict_noise.o", STRICT + ["-DGS_NOISE_ONLY=1"] + KERNEL_FLAGS),
+    ("gs_step_kernels.hip", "gs_step_fused_noise.o", ["-DGS_MATH_FUSED=1", "-DGS_NOISE_ONLY=1"] + KERNEL_FLAGS),
     ("gs_util_kernels.hip", "gs_util.o", []),
     # summaries of planes (row records, the ensembles' fold): hipcc's default float mode, sub-normal cells kept
     ("gs_summary.hip", "gs_summary_k.o", []),

@@ -56,6 +56,7 @@ EXPORTS = (
     "gs_ensemble_upload", "gs_ensemble_download", "gs_ensemble_run",
     "gs_ctx_set_param_map",
     "gs_ctx_set_mask",
+    "gs_ctx_set_noise", "gs_ctx_get_noise",
     "gs_fields_summarize", "gs_members_summarize",
     "gs_fields_histogram", "gs_members_histogram",
     "gs_field_reduced_shape", "gs_field_download_reduced", "gs_field_download_reduced_async", "gs_field_colormap_reduced",
@@ -131,6 +132,17 @@ class GsStats(ctypes.Structure):
         ("halo_exposed_ms", ctypes.c_float),
         ("reserved", ctypes.c_float),
         ("window_fallbacks", ctypes.c_uint64),
+    ]
+
+
+class GsNoise(ctypes.Structure):
+    """``gs_noise`` (include/gs_hip.h): the two sigmas, the seed and the index of the next step -- 24 bytes."""
+
+    _fields_ = [
+        ("sigma_u", ctypes.c_float),
+        ("sigma_v", ctypes.c_float),
+        ("seed", ctypes.c_uint64),
+        ("step", ctypes.c_uint64),
     ]
 
 
@@ -236,6 +248,8 @@ def load() -> ctypes.CDLL:
         "gs_ctx_set_params": (i32, [vp, P(GsParams)]),
         "gs_ctx_set_param_map": (i32, [vp, vp, vp]),
         "gs_ctx_set_mask": (i32, [vp, vp]),
+        "gs_ctx_set_noise": (i32, [vp, P(GsNoise)]),
+        "gs_ctx_get_noise": (i32, [vp, P(GsNoise), P(i32)]),
         "gs_field_create": (i32, [vp, P(vp), u64, u64]),
         "gs_field_destroy": (i32, [vp, vp]),
         "gs_field_shape": (i32, [vp, P(u64), P(u64)]),

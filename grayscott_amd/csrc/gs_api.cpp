@@ -180,7 +180,8 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
         return fail(GS_ERR_UNSUPPORTED, "only the temporally blocked kernel fuses steps");
     const bool fused = ctx->o.math == GS_MATH_FUSED;
     if (at.kind != GS_ATTACH_NONE && kernel == GS_KERNEL_LDS) // (gs_ctx_set_param_map / gs_ctx_set_mask refuse such a context first)
-        return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no %s form", at.kind == GS_ATTACH_MAP ? "parameter-map" : "domain-mask");
+        return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no %s form",
+                    at.kind == GS_ATTACH_MAP ? "parameter-map" : (at.kind == GS_ATTACH_MASK ? "domain-mask" : "noise"));
     const char *name = nullptr;
     hipError_t e;
     switch (kernel) {
@@ -283,14 +284,28 @@ GsStepArgs make_args(const gs_ctx *ctx, const gs_field *in_u, const gs_field *in
 }
 
 // The context's attachment as launch_rows takes it: its kind and its planes of local slab i, from row `row` on (a row
-// band's first row).  Without a map or a mask: GS_ATTACH_NONE, and the launchers run the uniform kernels.
-static GsAttached attached_at(const gs_ctx *ctx, int i, int row)
+// band's first row).  Without a map or a mask: GS_ATTACH_NONE, and the launchers run the uniform kernels.  Noise: the keys of
+// the next four steps -- the boundary-band and interior launches of one pass, every slab and every band get the same ones,
+// the counter moves when the pass has been enqueued (advance_noise) -- and the global row of row `row` of slab i of `like`.
+static GsAttached attached_at(const gs_ctx *ctx, const gs_field *like, int i, int row)
 {
     GsAttached at;
     at.kind = ctx->attached.kind;
     for (int j = 0; j < 2; ++j)
         if (const gs_field *f = ctx->attached.plane[j]) at.plane[j] = f->s[i].row0 + (ptrdiff_t)row * f->pitch;
+    if (at.kind == GS_ATTACH_NOISE) {
+        const gs_noise &n = ctx->attached.noise;
+        for (int j = 0; j < 4; ++j) at.noise.key[j] = noise_key(n.seed, n.step + (uint64_t)j);
+        at.noise.sigma_u = n.sigma_u;
+        at.noise.sigma_v = n.sigma_v;
+        at.noise.row0 = (uint32_t)(like->s[i].g_row0 + (uint64_t)row);
+    }
     return at;
+}
+// `steps` time steps have been enqueued on the context: the noise's step counter (gs_noise::step)
+static void advance_noise(gs_ctx *ctx, int steps)
+{
+    if (ctx->noisy()) ctx->attached.noise.step += (uint64_t)steps;
 }
 
 // ---- in-place row bands of a single slab -------------------------------------------------
@@ -372,7 +387,7 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         a.allow_fair = 0; // several launches share the chip
         const ptrdiff_t off = (ptrdiff_t)r0 * full.pitch;
         a.in_u += off; a.in_v += off; a.out_u += off; a.out_v += off;
-        const GsAttached at = attached_at(ctx, 0, r0);
+        const GsAttached at = attached_at(ctx, in_u, 0, r0);
         a.rows = r1 - r0;
         a.top_present = k > 0;
         a.bottom_present = k < V - 1;
@@ -400,6 +415,7 @@ int32_t step_bands(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u,
         GS_HIP(hipEventRecord(b.done[p], b.compute));
     }
     ctx->bands_active = true;
+    advance_noise(ctx, fuse);
     ctx->step_no++;
     ctx->passes++;
     ctx->steps_done += (uint64_t)fuse;
@@ -417,6 +433,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
     const int n_local = (int)ctx->slabs.size();
     const int S = ctx->total_slabs();
     if (in_u->rows == 0 || in_u->cols == 0) { // empty grid: every step is a no-op
+        advance_noise(ctx, fuse);
         ctx->step_no++;
         return GS_OK;
     }
@@ -428,7 +445,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
         GsStepArgs a = make_args(ctx, in_u, in_v, out_u, out_v, 0, fuse);
         a.ra0 = 0;
         a.ra1 = a.rows;
-        GS_TRY(launch_rows(ctx, a, sl.compute, fuse, attached_at(ctx, 0, 0)));
+        GS_TRY(launch_rows(ctx, a, sl.compute, fuse, attached_at(ctx, in_u, 0, 0)));
     } else {
         if (fuse > kGhostRows || fuse > min_slab_rows(ctx, in_u))
             return fail(GS_ERR_INVALID, "cannot fuse %d steps over slabs of %d rows", fuse, min_slab_rows(ctx, in_u));
@@ -446,7 +463,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             SlabRt &sl = ctx->slabs[i];
             GS_HIP(hipSetDevice(sl.device));
             GsStepArgs a = make_args(ctx, in_u, in_v, out_u, out_v, i, fuse);
-            const GsAttached at = attached_at(ctx, i, 0);
+            const GsAttached at = attached_at(ctx, in_u, i, 0);
             const int n = a.rows;
             // gs_ctx_set_pass_timing: events around this pass's halo-stream work and interior kernel
             const bool timed = sl.timed < ctx->pass_timing;
@@ -485,6 +502,7 @@ int32_t step_impl(gs_ctx *ctx, gs_field *in_u, gs_field *in_v, gs_field *out_u, 
             }
         }
     }
+    advance_noise(ctx, fuse);
     ctx->step_no++;
     ctx->passes++;
     ctx->steps_done += (uint64_t)fuse;

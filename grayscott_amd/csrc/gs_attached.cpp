@@ -6,19 +6,43 @@
 //     link plane: a u32 word per cell that says which of the cell's eight neighbours -- at the positions the boundary rule
 //     reads -- are walls, and whether the cell itself is one (gs_cell.h: link_bit).  The words are formed on the device
 //     once, at attach time, and the launchers run the mask forms of the step kernels (gs_*_wk) while the plane exists.
-// Both are planes in the field layout of the species with refreshed ghost rows, kept in gs_ctx::attached; its kind selects
-// the kernel set and, with it, the on-line tuner's state (gs_ctx::tuner): the uniform, the mapped and the masked kernels'
-// choices are kept apart.
+//   noise (gs_ctx_set_noise): a seeded stochastic increment per cell and step, a pure function of (seed, step, row, column).
+//     The context owns no plane: the sigmas, the seed and the step counter live in gs_ctx::attached.noise, and the launchers
+//     run the noise forms of the step kernels (gs_*_zk) with the step keys of each pass (noise_key).
+// The first two are planes in the field layout of the species with refreshed ghost rows, kept in gs_ctx::attached; its kind
+// selects the kernel set and, with it, the on-line tuner's state (gs_ctx::tuner): the uniform, the mapped, the masked and the
+// noise kernels' choices are kept apart.
 #include "gs_internal.h"
 
 namespace gsi {
 
-static const char *const kKindName[3] = {"", "parameter map", "domain mask"}; // [GsAttached::kind]
+static const char *const kKindName[GS_ATTACH_KINDS] = {"", "parameter map", "domain mask", "noise term"}; // [GsAttached::kind]
+static const char *const kKindShort[GS_ATTACH_KINDS] = {"", "map", "mask", "noise"};
+static const char *const kKindForm[GS_ATTACH_KINDS] = {"", "parameter-map", "domain-mask", "noise"};
+
+// Philox2x32-10 (include/gs_hip.h), the host's copy: the step keys.
+static void philox2x32(uint32_t c0, uint32_t c1, uint32_t k, uint32_t out[2])
+{
+    for (int i = 0; i < 10; ++i) {
+        const uint64_t p = (uint64_t)0xD256D193u * c0;
+        c0 = (uint32_t)(p >> 32) ^ k ^ c1;
+        c1 = (uint32_t)p;
+        k += 0x9E3779B9u;
+    }
+    out[0] = c0;
+    out[1] = c1;
+}
+uint32_t noise_key(uint64_t seed, uint64_t step)
+{
+    uint32_t x[2];
+    philox2x32((uint32_t)step, (uint32_t)(step >> 32), (uint32_t)seed, x);
+    return x[0] ^ (uint32_t)(seed >> 32);
+}
 
 // The attached planes' shape against the species' (gs_step / gs_run).
 int32_t check_attached_shape(const gs_ctx *ctx, const gs_field *f)
 {
-    if (ctx->attached.kind == GS_ATTACH_NONE) return GS_OK;
+    if (ctx->attached.kind == GS_ATTACH_NONE || ctx->attached.kind == GS_ATTACH_NOISE) return GS_OK; // (the noise has no planes)
     const gs_field *m = ctx->attached.plane[0];
     if (m->rows != f->rows || m->cols != f->cols || m->pitch != f->pitch)
         return fail(GS_ERR_INVALID, "the %s is [%llu,%llu], the species are [%llu,%llu]", kKindName[ctx->attached.kind],
@@ -35,18 +59,18 @@ void destroy_attached(gs_ctx *ctx)
     ctx->attached.kind = GS_ATTACH_NONE;
 }
 
-// What both `set` calls refuse before anything is touched: the other kind in force, a pinned kernel without a form for `kind`.
+// What the `set` calls refuse before anything is touched: the other kind in force, a pinned kernel without a form for `kind`.
 static int32_t refuse_attach(const gs_ctx *ctx, int kind)
 {
-    const int other = kind == GS_ATTACH_MAP ? GS_ATTACH_MASK : GS_ATTACH_MAP;
-    if (ctx->attached.kind == other)
+    const int other = ctx->attached.kind;
+    if (other != GS_ATTACH_NONE && other != kind)
         return fail(GS_ERR_UNSUPPORTED, "a %s and a %s cannot be attached together: detach the %s first", kKindName[kind], kKindName[other],
-                    other == GS_ATTACH_MAP ? "map" : "mask");
+                    kKindShort[other]);
     const int32_t k = ctx->o.kernel;
     if (k == GS_KERNEL_WINDOW || k == GS_KERNEL_LDS || k == GS_KERNEL_TILE)
         return fail(GS_ERR_UNSUPPORTED, "the %s kernel has no %s form",
                     k == GS_KERNEL_WINDOW ? "persistent window" : (k == GS_KERNEL_LDS ? "LDS-staged single-step" : "LDS-window (tile)"),
-                    kind == GS_ATTACH_MAP ? "parameter-map" : "domain-mask");
+                    kKindForm[kind]);
     return GS_OK;
 }
 
@@ -178,6 +202,32 @@ int32_t gs_ctx_set_mask(gs_ctx *ctx, gs_field *mask)
     if (st != GS_OK) destroy_attached(ctx); // a failure once the link plane exists leaves no mask attached
     ctx->attached.gen++;
     return st;
+}
+
+int32_t gs_ctx_set_noise(gs_ctx *ctx, const gs_noise *n)
+{
+    if (!ctx) return fail(GS_ERR_INVALID, "null context");
+    if (n) {
+        if (!std::isfinite(n->sigma_u) || !std::isfinite(n->sigma_v) || n->sigma_u < 0.0f || n->sigma_v < 0.0f)
+            return fail(GS_ERR_INVALID, "the noise's sigmas must be finite and >= 0 (got %g, %g)", (double)n->sigma_u, (double)n->sigma_v);
+        GS_TRY(refuse_attach(ctx, GS_ATTACH_NOISE));
+        if (ctx->o.use_graph)
+            return fail(GS_ERR_UNSUPPORTED, "noise cannot run with use_graph = 1: a replayed graph would replay its step keys");
+    }
+    GS_TRY(sync_all(ctx)); // (also runs again what a window launch that gave up left undone, without the noise)
+    if (!n) return detach(ctx, GS_ATTACH_NOISE);
+    ctx->attached.kind = GS_ATTACH_NOISE; // (nothing else is in force: refuse_attach; no planes to make)
+    ctx->attached.noise = *n;
+    ctx->attached.gen++;
+    return GS_OK;
+}
+
+int32_t gs_ctx_get_noise(const gs_ctx *ctx, gs_noise *out, int32_t *attached)
+{
+    if (!ctx || !attached) return fail(GS_ERR_INVALID, "null argument");
+    *attached = ctx->noisy() ? 1 : 0;
+    if (ctx->noisy() && out) *out = ctx->attached.noise;
+    return GS_OK;
 }
 
 } // extern "C"

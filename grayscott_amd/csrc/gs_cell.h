@@ -322,4 +322,59 @@ __device__ __forceinline__ void cell_masked(const GsStepArgs &a, const Row &m, c
     out_v = blend(self, v, nv);
 }
 
+// ---- noise (gs_ctx_set_noise; include/gs_hip.h holds the definition) -------------------------------------------------
+// Philox2x32-10 in plain C++ on vector registers, for N cells side by side: ten rounds of one 32 x 32 -> 64 bit multiply and
+// two XORs per cell; the round keys (k + i W) are wave-uniform.  The rounds stay a loop (the N cells inside it are unrolled and
+// hide each other's multiply latency): unrolled ten times into every level, cell kind and tick of the marching kernel, the
+// generator took the 4-level, 4-column forms past the size up to which the march's own loops unroll, and their row windows
+// went to scratch.
+template <int N>
+__device__ __forceinline__ void philox2x32(uint32_t (&c0)[N], uint32_t (&c1)[N], uint32_t k)
+{
+    // (two rounds per trip: the low word of a round's product is the next round's c1 where it stands, no register copy)
+#pragma nounroll
+    for (int i = 0; i < 5; ++i) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) {
+                const uint64_t p = (uint64_t)0xD256D193u * c0[e];
+                c0[e] = (uint32_t)(p >> 32) ^ k ^ c1[e];
+                c1[e] = (uint32_t)p;
+            }
+            k += 0x9E3779B9u;
+        }
+    }
+}
+// A draw as a value: the top 24 bits as a multiple of 2^-23 in [-1, 1).  Every operation is exact in f32.
+__device__ __forceinline__ float noise_xi(uint32_t x)
+{
+    return ((float)(int32_t)(x >> 8) - 8388608.0f) * 0x1p-23f;
+}
+// The noise form of the reaction update, for N cells of one row: (nu[e], nv[e]), the reference step's outputs for the cell at
+// global (row, col[e]), plus the step's increments -- per species one rounded multiply and one rounded add in the
+// translation unit's float mode, never contracted (the step kernels are built with -ffp-contract=off, and this is no
+// GS_TAP).  A species whose sigma is 0 is not touched (-0 stays -0); the tests on the sigmas are wave-uniform, and with both
+// zero no draw is made.
+template <int N>
+__device__ __forceinline__ void react_noise(const GsNoiseArgs &n, uint32_t key, uint32_t row, const uint32_t (&col)[N], float (&nu)[N],
+                                            float (&nv)[N])
+{
+    const bool su = n.sigma_u != 0.0f, sv = n.sigma_v != 0.0f;
+    if (su || sv) {
+        uint32_t x0[N], x1[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) { x0[e] = col[e]; x1[e] = row; }
+        philox2x32<N>(x0, x1, key);
+        if (su) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) nu[e] = nu[e] + n.sigma_u * noise_xi(x0[e]);
+        }
+        if (sv) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) nv[e] = nv[e] + n.sigma_v * noise_xi(x1[e]);
+        }
+    }
+}
+
 } // namespace

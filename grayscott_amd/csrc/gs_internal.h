@@ -6,8 +6,8 @@
 //   gs_window.cpp  the persistent window kernel's host side: tiling, exchange planes, give-up and replay
 //   gs_rccl.cpp    RCCL (loaded on first use), its self-test, gs_runtime_info, gs_last_error
 //   gs_ensemble.cpp ensembles: many grids of one shape, each with its own parameters, advanced in shared launches
-//   gs_attached.cpp a context's per-cell data: parameter maps (per-cell feed and kill rates, gs_ctx_set_param_map) and
-//                  domain masks (wall cells that block diffusion, gs_ctx_set_mask) on one grid
+//   gs_attached.cpp a context's per-cell data: parameter maps (per-cell feed and kill rates, gs_ctx_set_param_map),
+//                  domain masks (wall cells that block diffusion, gs_ctx_set_mask) and noise (gs_ctx_set_noise) on one grid
 //   gs_observe.cpp results formed on the device from planes and ensemble members: summaries (gs_fields_summarize,
 //                  gs_members_summarize), histograms (gs_fields_histogram, gs_members_histogram), bit-quad counts
 //                  (gs_fields_morphology, gs_members_morphology), two-point pair counts (gs_fields_correlation,
@@ -241,16 +241,20 @@ struct gs_ctx {
     // plane[1] = F + K) or a domain mask (gs_ctx_set_mask: plane[0] = a u32 link word per cell, gs_cell.h: link_bit).  The
     // planes are owned by the context, in the field layout of the species with their ghost rows filled.  `gen` advances with
     // every attachment, replacement and detachment of either kind (GraphKey).
+    // ... or a noise term (gs_ctx_set_noise): no planes, `noise` holds the sigmas, the seed and the index of the next step
+    // the context executes, which step_impl / step_bands advance with every pass they enqueue.
     struct Attached {
         int kind = GS_ATTACH_NONE;
         gs_field *plane[2] = {nullptr, nullptr};
         uint64_t gen = 0;
+        gs_noise noise{};
     } attached;
+    bool noisy() const { return attached.kind == GS_ATTACH_NOISE; }
     bool mapped() const { return attached.kind == GS_ATTACH_MAP; }
     bool masked() const { return attached.kind == GS_ATTACH_MASK; }
     // The simple, streaming and marching kernels run the kernel set of the attachment's kind, and the tuner keeps its
     // choices and tunings per kernel set: attaching and detaching select the state, nothing is copied.
-    TunerState tuner_of[3]; // [GsAttached::kind]
+    TunerState tuner_of[GS_ATTACH_KINDS]; // [GsAttached::kind]
     TunerState &tuner() { return tuner_of[attached.kind]; }
     const TunerState &tuner() const { return tuner_of[attached.kind]; }
     int total_slabs() const { return world * (int)slabs.size(); }
@@ -354,6 +358,8 @@ int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *la
 // gs_attached.cpp
 int32_t check_attached_shape(const gs_ctx *ctx, const gs_field *f);
 void destroy_attached(gs_ctx *ctx);
+// the noise's step key (include/gs_hip.h): key(s) for `seed`
+uint32_t noise_key(uint64_t seed, uint64_t step);
 
 // gs_fields.cpp: how a plane of rows x cols cells lies on this context -- the row pitch in floats and, per local slab, its first
 // global row and its rows -- or gs_field_create's refusals.  Whatever follows a field's rows (gs_time_stats) takes it from here.

@@ -105,13 +105,25 @@ struct GsQuiet {
     int32_t pad;
     int64_t cap, need, launched; // (host side only)
 };
-// What a context's per-cell data (a map or a mask, never both) is to the launchers of the simple, streaming and marching
-// kernels: the kernel set it selects -- GS_ATTACH_NONE: the uniform kernels -- and one slab's planes, local row 0, column 0:
-// the map's F and F + K, or the mask's link plane.  The launchers hand them to the kernels as GsMapPlanes / GsMaskPlanes.
-enum { GS_ATTACH_NONE = 0, GS_ATTACH_MAP = 1, GS_ATTACH_MASK = 2 };
+// Noise (gs_ctx_set_noise; include/gs_hip.h: the definition).  The second argument of the noise kernels (gs_*_zk): the step
+// keys of the pass -- level j (1 .. K) of a fused pass computes step step0 + j - 1 with key[j - 1]; a single step uses
+// key[0] --, the two sigmas and the global row of the slab's local row 0 (of a row band: of the band's first row), so that a
+// cell at local row r -- a ghost row's included -- draws at (row0 + r, column).  The noise has no planes.
+struct GsNoiseArgs {
+    uint32_t key[4];
+    float sigma_u, sigma_v;
+    uint32_t row0;
+    uint32_t pad;
+};
+// What a context's per-cell data (a map, a mask or a noise term, one at a time) is to the launchers of the simple, streaming
+// and marching kernels: the kernel set it selects -- GS_ATTACH_NONE: the uniform kernels -- and one slab's planes, local row
+// 0, column 0: the map's F and F + K, or the mask's link plane; the noise's keys, sigmas and first global row.  The launchers
+// hand them to the kernels as GsMapPlanes / GsMaskPlanes / GsNoiseArgs.
+enum { GS_ATTACH_NONE = 0, GS_ATTACH_MAP = 1, GS_ATTACH_MASK = 2, GS_ATTACH_NOISE = 3, GS_ATTACH_KINDS = 4 };
 struct GsAttached {
     int kind = GS_ATTACH_NONE;
     const float *plane[2] = {nullptr, nullptr};
+    GsNoiseArgs noise = {};
 };
 
 // gs_launch_window_*: one persistent launch for a whole gs_run on grids of ONE round of register-resident windows.
@@ -199,6 +211,7 @@ struct GsEnsArgs {
     hipError_t gs_launch_map_rates_##SUFFIX(const float *feed, const float *kill, float *fpk, size_t n, hipStream_t s); \
     const void *gs_tb_map_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                                \
     const void *gs_tb_mask_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                               \
+    const void *gs_tb_noise_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                              \
     hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
     hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name); \
     hipError_t gs_launch_ens_resident_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name); \
@@ -219,7 +232,8 @@ const void *gs_tb_quiet_kernel_strict(int k);
 // sub-normal sum is flushed, as the reference's DenormalsFlusher does).  gs_tb_map_kernel_*: the entry of the marching
 // kernel's map form (gs_step_tb_mk: its own translation unit, GS_TB_MAP_ONLY) for k fused steps, fast in {0, 3} (3: the
 // .op variant, strict only), cpl columns per lane and rule = rule_set(boundary); nullptr for a form that is not built.
-// gs_tb_mask_kernel_*: the same for the domain mask's forms (gs_step_tb_wk, GS_TB_MASK_ONLY).
+// gs_tb_mask_kernel_*: the same for the domain mask's forms (gs_step_tb_wk, GS_TB_MASK_ONLY), gs_tb_noise_kernel_*: for the
+// noise forms (gs_step_tb_zk, GS_NOISE_ONLY).
 
 // Plane utilities (math-agnostic, defined once in gs_util_kernels.hip).
 hipError_t gs_launch_colormap(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float scale,

@@ -344,9 +344,15 @@ __host__ __device__ constexpr int tb_halo_floats(int k, bool cross) { return cro
 // bits gathered in one vector register outside it took K = 4 to 128 registers and 4 spills -- so the storing lanes are
 // asked once, at the end.  The return value: the lanes that hold a non-zero mask, 0 = every cell stored is at rest (0
 // without CHECK).
-template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false, bool MAP = false, bool MASK = false, bool CHECK = false>
+// NOISE: the noise forms (gs_step_tb_zk, second argument GsNoiseArgs).  Every cell a level computes -- apron cells, cells in
+// a neighbouring slab's ghost rows -- gets react_noise with the key of that level's step (level j: nz.key[j - 1]) at its
+// global position: row nz.row0 + the local row, the lane's columns; under the periodic rule an edge unit's rows and columns
+// are the wrapped ones its loads read.  (A position outside the grid under the other rules draws something too: no cell
+// of the grid ever reads it.)
+template <int K, int EDGE, int FAST, int CPL, int ZH = -1, bool FAIR = false, bool MAP = false, bool MASK = false, bool CHECK = false,
+          bool NOISE = false>
 __device__ __forceinline__ unsigned long long tb_march(const GsStepArgs &a, int ur0, int ur1, int strip, int lane, const GsMapPlanes &mp,
-                                         const FairBoard &fb GS_TRACE_PARAM)
+                                         const FairBoard &fb GS_TRACE_PARAM, const GsNoiseArgs &nz = GsNoiseArgs{})
 {
     constexpr int S = tb_sacrificial_lanes(K, CPL), W = tb_cols_per_wave(K, CPL);
     const int c = strip * W + (lane - S) * CPL; // first column of this lane (may be negative)
@@ -673,6 +679,26 @@ __device__ __forceinline__ unsigned long long tb_march(const GsStepArgs &a, int 
                                 cell<EDGE, FAST, RowT<CPL>, ZH, MAP>(a, m, z, p, k + 1, mrow, prow, la[k], ra[k], nu[k], nv[k],
                                                                      MAP ? mf[k] : 0.0f, MAP ? mfk[k] : 0.0f);
                         }
+                        if constexpr (NOISE) {
+                            int gr = row; // wave-uniform
+                            if constexpr (PER) {
+                                if (gr < 0) gr += a.rows;
+                                if (gr >= a.rows) gr -= a.rows;
+                                if (gr < 0 || gr >= a.rows) { gr = row % a.rows; if (gr < 0) gr += a.rows; } // grids of fewer rows than K
+                            }
+                            uint32_t gcs[CPL];
+#pragma unroll
+                            for (int k = 0; k < CPL; ++k) {
+                                int gc = c + k;
+                                if constexpr (PER) {
+                                    gc = pc0 + k;
+                                    if (gc >= a.cols) gc -= a.cols;
+                                    if (gc >= a.cols) gc %= a.cols;
+                                }
+                                gcs[k] = (uint32_t)gc;
+                            }
+                            react_noise<CPL>(nz, nz.key[j - 1], nz.row0 + (uint32_t)gr, gcs, nu, nv);
+                        }
                         if (j < K) {
                             w[j][s3] = widen_tb<CPL>(nu, nv);
                         } else if (store_ok) {
@@ -700,10 +726,12 @@ __device__ __forceinline__ unsigned long long tb_march(const GsStepArgs &a, int 
 // nothing), else by the march's check of what it stored -- a unit at rest that a front enters is caught in the pass in
 // which that happens.  Edge units (first and last strip, chunks that touch the grid's first or last rows, the halves of
 // edge_split = 2) never read or write a word, so they and their inner neighbours always compute.
-template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false, bool MASK = false, bool QUIET = false>
+template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false, bool MASK = false, bool QUIET = false,
+          bool NOISE = false>
 __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
-                                        const GsQuiet &qa = GsQuiet{})
+                                        const GsQuiet &qa = GsQuiet{}, const GsNoiseArgs &nz = GsNoiseArgs{})
 {
+    static_assert(!NOISE || (!MAP && !MASK && !QUIET && WG == 4 && (FAST & 4) == 0), "the noise forms are 4-wave marches without difference sharing");
     static_assert(!QUIET || (WG == 4 && !PER && !NEU && !MAP && !MASK), "the quiet entries are 4-wave marches of the uniform kernels");
     static_assert(!MAP || (WG == 4 && (FAST & 4) == 0), "the map forms are 4-wave marches without difference sharing");
     static_assert(!MASK || (!MAP && WG == 4 && (FAST & 4) == 0), "the mask forms are 4-wave marches without difference sharing");
@@ -866,26 +894,26 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &
     }
     if constexpr (PER) {
         if (!edge)
-            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
         else
-            tb_march<K, 5, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 5, FAST, CPL, -1, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     } else if constexpr (NEU) {
         if (!edge)
-            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
         else
-            tb_march<K, 1, FAST, CPL, 3, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+            tb_march<K, 1, FAST, CPL, 3, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     } else if (!edge)
-        tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     else if (a.zero_halo) // (0 or 1 in these kernels: gs_launch_tb sends the other rules to gs_step_tb_pk / _nk)
-        tb_march<K, 1, FAST, CPL, 1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, 1, FAST, CPL, 1, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     else if (KINDS && a.edge_kinds && left && !right && !ends)
-        tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 2 : 1, FAST, CPL, 0, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     else if (KINDS && a.edge_kinds && right && !left && !ends)
-        tb_march<K, KINDS ? 3 : 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 3 : 1, FAST, CPL, 0, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     else if (KINDS && a.edge_kinds && ends && !left && !right)
-        tb_march<K, KINDS ? 4 : 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, KINDS ? 4 : 1, FAST, CPL, 0, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     else
-        tb_march<K, 1, FAST, CPL, 0, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
+        tb_march<K, 1, FAST, CPL, 0, FAIR, MAP, MASK, false, NOISE>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG, nz);
     if constexpr (FAIR) { if (lane == 0) fb.progress[wave] = 0x7fffffff; }
 #undef GS_TB_LEAVE
 #if defined(GS_TB_TRACE)
@@ -975,6 +1003,13 @@ template <int K, int FAST, int CPL, int RULE>
 __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_tb_wk)(GsStepArgs a, GsMaskPlanes mk)
 {
     tb_unit<K, FAST, CPL, 4, RULE == 1, RULE == 2, false, true>(a, GsMapPlanes{mk.link, nullptr});
+}
+// The noise forms (gs_ctx_set_noise; the keys, sigmas and first global row of GsNoiseArgs), with the parameters of the map
+// forms.
+template <int K, int FAST, int CPL, int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_tb_zk)(GsStepArgs a, GsNoiseArgs nz)
+{
+    tb_unit<K, FAST, CPL, 4, RULE == 1, RULE == 2, false, false, false, true>(a, GsMapPlanes{nullptr, nullptr}, GsQuiet{}, nz);
 }
 
 } // namespace

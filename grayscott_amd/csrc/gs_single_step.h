@@ -29,9 +29,9 @@ __device__ __forceinline__ bool simple_wall(const GsMaskPlanes &mk, ptrdiff_t o,
     return (reinterpret_cast<const uint32_t *>(mk.link)[o] >> bit) & 1u;
 }
 
-template <bool MAP = false, bool MASK = false>
+template <bool MAP = false, bool MASK = false, bool NOISE = false>
 __device__ __forceinline__ void simple_cell(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
-                                            const GsMaskPlanes &mk = GsMaskPlanes{nullptr})
+                                            const GsMaskPlanes &mk = GsMaskPlanes{nullptr}, const GsNoiseArgs &nz = GsNoiseArgs{})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -73,6 +73,13 @@ __device__ __forceinline__ void simple_cell(const GsStepArgs &a, const GsMapPlan
     float ou, ov;
     simple_react<MAP>(a, mp, o, u, v, acc_u, acc_v, ou, ov);
     if (MASK && simple_wall(mk, o, kWallSelf)) { ou = u; ov = v; }
+    if constexpr (NOISE) {
+        const uint32_t gc[1] = {(uint32_t)c};
+        float xu[1] = {ou}, xv[1] = {ov};
+        react_noise<1>(nz, nz.key[0], nz.row0 + (uint32_t)r, gc, xu, xv);
+        ou = xu[0];
+        ov = xv[0];
+    }
     a.out_u[o] = ou;
     a.out_v[o] = ov;
 }
@@ -80,9 +87,9 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_k)(GsStepArgs a)
 
 // The periodic rule (GsStepArgs::zero_halo = 2), literally: the nine taps of the zero-halo rule's interior cell, in its
 // order, with neighbour (r + i - 1, c + j - 1) read at ((r + i - 1) mod rows, (c + j - 1) mod cols).  A kernel of its own.
-template <bool MAP = false, bool MASK = false>
+template <bool MAP = false, bool MASK = false, bool NOISE = false>
 __device__ __forceinline__ void simple_cell_periodic(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
-                                                     const GsMaskPlanes &mk = GsMaskPlanes{nullptr})
+                                                     const GsMaskPlanes &mk = GsMaskPlanes{nullptr}, const GsNoiseArgs &nz = GsNoiseArgs{})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -108,6 +115,13 @@ __device__ __forceinline__ void simple_cell_periodic(const GsStepArgs &a, const 
     float ou, ov;
     simple_react<MAP>(a, mp, rows_at[1] + c, u, v, acc_u, acc_v, ou, ov);
     if (MASK && simple_wall(mk, rows_at[1] + c, kWallSelf)) { ou = u; ov = v; }
+    if constexpr (NOISE) {
+        const uint32_t gc[1] = {(uint32_t)c};
+        float xu[1] = {ou}, xv[1] = {ov};
+        react_noise<1>(nz, nz.key[0], nz.row0 + (uint32_t)r, gc, xu, xv);
+        ou = xu[0];
+        ov = xv[0];
+    }
     a.out_u[rows_at[1] + c] = ou;
     a.out_v[rows_at[1] + c] = ov;
 }
@@ -116,9 +130,9 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_pk)(GsStepArgs a
 // The zero-flux (Neumann) rule (GsStepArgs::zero_halo = 3), literally: the nine taps of the zero-halo rule's interior cell,
 // in its order, with neighbour (r + i - 1, c + j - 1) read at the nearest cell of the grid -- rows clamped at the global
 // edges only (a slab seam reads its ghost row), columns at 0 and cols - 1.  A kernel of its own.
-template <bool MAP = false, bool MASK = false>
+template <bool MAP = false, bool MASK = false, bool NOISE = false>
 __device__ __forceinline__ void simple_cell_neumann(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
-                                                    const GsMaskPlanes &mk = GsMaskPlanes{nullptr})
+                                                    const GsMaskPlanes &mk = GsMaskPlanes{nullptr}, const GsNoiseArgs &nz = GsNoiseArgs{})
 {
     const int bpr = (a.cols + 255) >> 8;
     const int slot = blockIdx.x / bpr;
@@ -144,6 +158,13 @@ __device__ __forceinline__ void simple_cell_neumann(const GsStepArgs &a, const G
     float ou, ov;
     simple_react<MAP>(a, mp, rows_at[1] + c, u, v, acc_u, acc_v, ou, ov);
     if (MASK && simple_wall(mk, rows_at[1] + c, kWallSelf)) { ou = u; ov = v; }
+    if constexpr (NOISE) {
+        const uint32_t gc[1] = {(uint32_t)c};
+        float xu[1] = {ou}, xv[1] = {ov};
+        react_noise<1>(nz, nz.key[0], nz.row0 + (uint32_t)r, gc, xu, xv);
+        ou = xu[0];
+        ov = xv[0];
+    }
     a.out_u[rows_at[1] + c] = ou;
     a.out_v[rows_at[1] + c] = ov;
 }
@@ -168,6 +189,18 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_wk)(GsStepArgs a
     else simple_cell<false, true>(a, none, mk);
 }
 
+// ... and the noise forms (the keys and sigmas of GsNoiseArgs, gs_ctx_set_noise): the reference cell, then react_noise at
+// the cell's global position.
+template <int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_zk)(GsStepArgs a, GsNoiseArgs nz)
+{
+    const GsMapPlanes none{nullptr, nullptr};
+    const GsMaskPlanes nomask{nullptr};
+    if constexpr (RULE == 1) simple_cell_periodic<false, false, true>(a, none, nomask, nz);
+    else if constexpr (RULE == 2) simple_cell_neumann<false, false, true>(a, none, nomask, nz);
+    else simple_cell<false, false, true>(a, none, nomask, nz);
+}
+
 // PER: a unit on an edge under the periodic rule (gs_step_stream_pk): rows and columns are read at their index modulo
 // the grid's (a lane whose four columns are not one aligned piece of a row after wrapping loads them one by one), and
 // every cell runs the interior code.  ZH: the boundary rule of the edge cells (cell<>; -1 = GsStepArgs::zero_halo, 3 = the
@@ -175,10 +208,11 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_simple_wk)(GsStepArgs a
 // cell itself -- the rows of the unit, this lane's four columns, the addresses of its stores -- one group ahead, like
 // the rows of the species.  MASK: the domain mask's form (gs_step_stream_wk): the link words of the cells, read like MAP's
 // rates (in mf), and every cell computed by cell_masked.
-template <int G, bool EDGE, bool PER = false, int ZH = -1, bool MAP = false, bool MASK = false>
+// NOISE: the noise form (gs_step_stream_zk): react_noise on every cell computed, at its global row and column.
+template <int G, bool EDGE, bool PER = false, int ZH = -1, bool MAP = false, bool MASK = false, bool NOISE = false>
 __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int c0, int lane,
                                       const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
-                                      const GsMaskPlanes &mkp = GsMaskPlanes{nullptr})
+                                      const GsMaskPlanes &mkp = GsMaskPlanes{nullptr}, const GsNoiseArgs &nz = GsNoiseArgs{})
 {
     const int c = c0 + lane * 4;
     LaneCtx lc;
@@ -300,6 +334,13 @@ __device__ __forceinline__ void march(const GsStepArgs &a, int ur0, int ur1, int
                     cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 2, mrow, prow, la[1], ra[1], nu.y, nv.y, mf[g].y, mk[g].y);
                     cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 3, mrow, prow, la[2], ra[2], nu.z, nv.z, mf[g].z, mk[g].z);
                     cell<E, 0, RowW, ZH, MAP>(a, q[g], q[g + 1], q[g + 2], 4, mrow, prow, la[3], ra[3], nu.w, nv.w, mf[g].w, mk[g].w);
+                }
+                if constexpr (NOISE) {
+                    const uint32_t gc[4] = {(uint32_t)c, (uint32_t)c + 1u, (uint32_t)c + 2u, (uint32_t)c + 3u};
+                    float xu[4] = {nu.x, nu.y, nu.z, nu.w}, xv[4] = {nv.x, nv.y, nv.z, nv.w};
+                    react_noise<4>(nz, nz.key[0], nz.row0 + (uint32_t)row, gc, xu, xv);
+                    nu = make_float4(xu[0], xu[1], xu[2], xu[3]);
+                    nv = make_float4(xv[0], xv[1], xv[2], xv[3]);
                 }
                 if (lc.lane_ok) {
                     *reinterpret_cast<float4 *>(ou) = nu;
@@ -511,6 +552,48 @@ __global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_wk)(GsStepArgs a
         march<G, true, false, 3, false, true>(a, ur0, ur1, c0, lane, none, mk);
     else
         march<G, true, false, -1, false, true>(a, ur0, ur1, c0, lane, none, mk);
+}
+
+// ... and the noise forms (GsNoiseArgs): the same units, react_noise behind every cell.
+template <int G, int RULE>
+__global__ __launch_bounds__(256) void GS_SUFFIX(gs_step_stream_zk)(GsStepArgs a, GsNoiseArgs nz)
+{
+    const GsMapPlanes none{nullptr, nullptr};
+    const GsMaskPlanes nomask{nullptr};
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int strips = (a.cols + 255) >> 8;
+    int block = (int)blockIdx.x;
+    if (a.xcd_m > 0) { // XCD-aware order (GsStepArgs::xcd_m)
+        const int per = 8 * a.xcd_m, g = block / per, o = block - g * per;
+        if ((g + 1) * per <= (int)gridDim.x) block = g * per + (o & 7) * a.xcd_m + (o >> 3);
+    }
+    const int unit = block * 4 + wave;
+    const int chunk = unit / strips;
+    const int strip = unit - chunk * strips;
+    const int rpu = a.rows_per_unit;
+    const int chunks_a = (a.ra1 - a.ra0 + rpu - 1) / rpu;
+    const int chunks_b = (a.rb1 - a.rb0 + rpu - 1) / rpu;
+    if (chunk >= chunks_a + chunks_b) return; // wave-uniform
+    int ur0, ur1;
+    if (chunk < chunks_a) {
+        ur0 = a.ra0 + chunk * rpu;
+        ur1 = min(ur0 + rpu, a.ra1);
+    } else {
+        ur0 = a.rb0 + (chunk - chunks_a) * rpu;
+        ur1 = min(ur0 + rpu, a.rb1);
+    }
+    const int c0 = strip << 8;
+    const bool edge = (c0 == 0) || (c0 + 256 >= a.cols) || (ur0 == 0 && !a.top_present) ||
+                      (ur1 == a.rows && !a.bottom_present);
+    if (!edge)
+        march<G, false, false, -1, false, false, true>(a, ur0, ur1, c0, lane, none, nomask, nz);
+    else if constexpr (RULE == 1)
+        march<G, true, true, -1, false, false, true>(a, ur0, ur1, c0, lane, none, nomask, nz);
+    else if constexpr (RULE == 2)
+        march<G, true, false, 3, false, false, true>(a, ur0, ur1, c0, lane, none, nomask, nz);
+    else
+        march<G, true, false, -1, false, false, true>(a, ur0, ur1, c0, lane, none, nomask, nz);
 }
 
 // ------------------------------------------------------------------------------------

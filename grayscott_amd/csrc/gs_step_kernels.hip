@@ -50,6 +50,10 @@
 //       every cell through cell_masked (a tap that reads a wall reads the cell's own value; a wall keeps its input), from
 //       the link words formed at attach time.  The marching forms, the same set as the map's, are built in a translation
 //       unit of their own (GS_TB_MASK_ONLY).  No difference sharing: a wall breaks it.
+//   ..._zk<..., RULE>  the noise forms (second argument GsNoiseArgs, gs_ctx_set_noise) of the same three kernels: the
+//       reference cell, then react_noise (gs_cell.h) -- a Philox2x32-10 draw at the cell's global (row, column) with the key
+//       of the level's step, one multiply and one add per species.  The marching forms, the same set as the map's, are built
+//       in a translation unit of their own (GS_NOISE_ONLY).  No difference sharing, no units at rest.
 //
 // This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
 // its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
@@ -102,9 +106,17 @@
 #define GS_MATH_NAME "strict"
 #endif
 
+// GS_NOISE_ONLY=1: ... and the noise forms (gs_step_tb_zk), through gs_tb_noise_kernel_<flavour>().
+#ifndef GS_NOISE_ONLY
+#define GS_NOISE_ONLY 0
+#endif
+#if GS_NOISE_ONLY && (GS_TB_OP_ONLY || GS_TB_MAP_ONLY || GS_TB_MASK_ONLY)
+#error "GS_NOISE_ONLY is a translation unit of its own"
+#endif
+
 #include "gs_cell.h"
 #include "gs_march.h"
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 #include "gs_single_step.h"
 #include "gs_lds_resident.h"
 #include "gs_ensemble.h"
@@ -125,7 +137,7 @@
 // periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
 static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
 
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 // Opt-in for more than 64 KB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize).  The attribute
 // belongs to the device function ON THE CURRENT DEVICE, so what has been set is remembered per (device,
 // function): a process that drives several GPUs (device_ids = 0, 1, ...; two contexts) opts in on each.
@@ -172,8 +184,8 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 
 #define GS_NAMES_OP(BASE, R) {GS_NAME(BASE, "", R), GS_NAME(BASE, ".op", R)}
 // ... per kind of attachment (GsAttached::kind): the uniform kernels' names, then the parameter map's kernel sets' (the same
-// rules, a "/map" suffix behind the rule's) and the domain mask's (a "/mask" suffix)
-#define GS_KINDS(M, BASE) {GS_RULES_OF(M, BASE, ""), GS_RULES_OF(M, BASE, "/map"), GS_RULES_OF(M, BASE, "/mask")}
+// rules, a "/map" suffix behind the rule's), the domain mask's (a "/mask" suffix) and the noise forms' (a "/noise" suffix)
+#define GS_KINDS(M, BASE) {GS_RULES_OF(M, BASE, ""), GS_RULES_OF(M, BASE, "/map"), GS_RULES_OF(M, BASE, "/mask"), GS_RULES_OF(M, BASE, "/noise")}
 #define GS_NAME1(BASE, R) GS_NAME(BASE, "", R)
 #define GS_PLAIN_FN(KER) reinterpret_cast<const void *>(&GS_SUFFIX(KER))
 // [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
@@ -183,27 +195,32 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 // The attachment as a launcher takes it: a known kind with its planes in place.
 static bool attached_ok(const GsAttached &at)
 {
-    return at.kind == GS_ATTACH_NONE || (at.kind == GS_ATTACH_MAP && at.plane[0] && at.plane[1]) || (at.kind == GS_ATTACH_MASK && at.plane[0]);
+    return at.kind == GS_ATTACH_NONE || (at.kind == GS_ATTACH_MAP && at.plane[0] && at.plane[1]) || (at.kind == GS_ATTACH_MASK && at.plane[0]) ||
+           at.kind == GS_ATTACH_NOISE;
 }
 // Launches entry `fn` of the attachment's kernel set (256-thread workgroups, no LDS): the uniform kernels take `args` alone,
-// the map's and the mask's forms the slab's planes as their second argument.
+// the map's and the mask's forms the slab's planes as their second argument, the noise forms the keys and sigmas.
 static hipError_t launch_attached(const void *fn, long blocks, GsStepArgs &args, const GsAttached &at, hipStream_t s)
 {
     GsMapPlanes mp{at.plane[0], at.plane[1]};
     GsMaskPlanes mk{at.plane[0]};
-    void *kargs[] = {&args, at.kind == GS_ATTACH_MAP ? static_cast<void *>(&mp) : static_cast<void *>(&mk)};
+    GsNoiseArgs nz = at.noise;
+    void *kargs[] = {&args, at.kind == GS_ATTACH_MAP     ? static_cast<void *>(&mp)
+                            : at.kind == GS_ATTACH_NOISE ? static_cast<void *>(&nz)
+                                                         : static_cast<void *>(&mk)};
     return hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(256), kargs, 0, s);
 }
 
 hipError_t GS_SUFFIX(gs_launch_simple)(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at)
 {
     // [kind][rule]: the periodic and zero-flux rules run kernels of their own, and so do the parameter map (gs_step_simple_mk)
-    // and the domain mask (gs_step_simple_wk)
-    static const char *const names[3][3] = GS_KINDS(GS_NAME1, "simple");
-    static const void *const fns[3][3] = {
+    // and the domain mask (gs_step_simple_wk); the noise forms are gs_step_simple_zk
+    static const char *const names[GS_ATTACH_KINDS][3] = GS_KINDS(GS_NAME1, "simple");
+    static const void *const fns[GS_ATTACH_KINDS][3] = {
         {GS_PLAIN_FN(gs_step_simple_k), GS_PLAIN_FN(gs_step_simple_pk), GS_PLAIN_FN(gs_step_simple_nk)},
         {GS_FN(gs_step_simple_mk, 0), GS_FN(gs_step_simple_mk, 1), GS_FN(gs_step_simple_mk, 2)},
-        {GS_FN(gs_step_simple_wk, 0), GS_FN(gs_step_simple_wk, 1), GS_FN(gs_step_simple_wk, 2)}};
+        {GS_FN(gs_step_simple_wk, 0), GS_FN(gs_step_simple_wk, 1), GS_FN(gs_step_simple_wk, 2)},
+        {GS_FN(gs_step_simple_zk, 0), GS_FN(gs_step_simple_zk, 1), GS_FN(gs_step_simple_zk, 2)}};
     if (!attached_ok(at)) return hipErrorInvalidValue;
     const int per = rule_set(a.zero_halo);
     if (name) *name = names[at.kind][per];
@@ -420,12 +437,13 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
 hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at)
 {
     // [kind][rule]: gs_step_stream_pk (the periodic rule, single slab) and _nk (the zero-flux rule), the parameter map's
-    // gs_step_stream_mk and the domain mask's gs_step_stream_wk
-    static const char *const names[3][3] = GS_KINDS(GS_NAME1, "stream-g2");
-    static const void *const fns[3][3] = {
+    // gs_step_stream_mk, the domain mask's gs_step_stream_wk and the noise forms gs_step_stream_zk
+    static const char *const names[GS_ATTACH_KINDS][3] = GS_KINDS(GS_NAME1, "stream-g2");
+    static const void *const fns[GS_ATTACH_KINDS][3] = {
         {GS_FN(gs_step_stream_k, 2), GS_FN(gs_step_stream_pk, 2), GS_FN(gs_step_stream_nk, 2)},
         {GS_FN(gs_step_stream_mk, 2, 0), GS_FN(gs_step_stream_mk, 2, 1), GS_FN(gs_step_stream_mk, 2, 2)},
-        {GS_FN(gs_step_stream_wk, 2, 0), GS_FN(gs_step_stream_wk, 2, 1), GS_FN(gs_step_stream_wk, 2, 2)}};
+        {GS_FN(gs_step_stream_wk, 2, 0), GS_FN(gs_step_stream_wk, 2, 1), GS_FN(gs_step_stream_wk, 2, 2)},
+        {GS_FN(gs_step_stream_zk, 2, 0), GS_FN(gs_step_stream_zk, 2, 1), GS_FN(gs_step_stream_zk, 2, 2)}};
     if (!attached_ok(at)) return hipErrorInvalidValue;
     const int per = rule_set(a.zero_halo);
     if (name) *name = names[at.kind][per];
@@ -530,6 +548,7 @@ static const void *tb_entry_of(int kind, int k, int fast, int cpl, int per)
 {
     return kind == GS_ATTACH_MAP    ? GS_SUFFIX(gs_tb_map_kernel)(k, fast, cpl, per)
            : kind == GS_ATTACH_MASK ? GS_SUFFIX(gs_tb_mask_kernel)(k, fast, cpl, per)
+           : kind == GS_ATTACH_NOISE ? GS_SUFFIX(gs_tb_noise_kernel)(k, fast, cpl, per)
                                     : tb_entry(k, fast, cpl, 4, per);
 }
 // ... and the variant that runs there for GsStepArgs::fast = `fast`.  The parameter map's and the domain mask's kernels:
@@ -544,7 +563,7 @@ static int tb_fast_of(int kind, int fast, int k, int cpl, int per)
 
 int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, int kind)
 {
-    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || kind < GS_ATTACH_NONE || kind > GS_ATTACH_MASK) return 0;
+    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || kind < GS_ATTACH_NONE || kind >= GS_ATTACH_KINDS) return 0;
     const int per = rule_set(boundary);
     const void *fn = tb_entry_of(kind, k, tb_fast_of(kind, fast, k, cpl, per), cpl, per);
     return fn ? 1024 * tb_waves_of(fn) : 0;
@@ -564,7 +583,7 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
 #define GS_TB_VARIANTS(B, R) {GS_NAME(B, "", R), GS_NAME(B, ".op", R), GS_NAME(B, ".op.ds", R), GS_NAME(B, ".op.dx", R)}
 #define GS_TB16_LAYOUTS(B, R) {GS_TB_VARIANTS(B "c1f", R), GS_TB_VARIANTS(B "c2f", R)}
     // [kind][rule][cpl 1, 2, 4][variant][k - 1]: the uniform kernels, the parameter map's (gs_step_tb_mk), the domain mask's (gs_step_tb_wk)
-    static const char *const names[3][3][3][4][4] = GS_KINDS(GS_TB_LAYOUTS, "tb-k");
+    static const char *const names[GS_ATTACH_KINDS][3][3][4][4] = GS_KINDS(GS_TB_LAYOUTS, "tb-k"); // (... and the noise forms, gs_step_tb_zk)
     static const char *const names16[3][2][4] = GS_RULES(GS_TB16_LAYOUTS, "tb-k4");  // [rule][cpl 1, 2][variant]
 #undef GS_TB16_LAYOUTS
 #undef GS_TB_VARIANTS
@@ -762,16 +781,16 @@ hipError_t GS_SUFFIX(gs_launch_map_rates)(const float *feed, const float *kill, 
     return hipGetLastError();
 }
 #undef GS_MAP_RATES_K
-#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
+#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 
-#if defined(GS_WIN_TRACE) && !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
+#if defined(GS_WIN_TRACE) && !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 extern "C" int32_t GS_SUFFIX(gs_debug_win_trace_read)(unsigned long long *dst)
 {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(gs_win_trace), sizeof(unsigned long long) * 1024 * 8 * 8) == hipSuccess ? 0 : -1;
 }
 #endif
 
-#if defined(GS_TB_TRACE) && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
+#if defined(GS_TB_TRACE) && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 // Copies the trace buffer of THIS translation unit's kernels out (diagnostic builds only).
 #if GS_TB_OP_ONLY
 extern "C" int32_t gs_debug_trace_read_op(unsigned long long *dst, int32_t units, int32_t clear)
@@ -854,7 +873,7 @@ const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule)
 }
 #endif
 
-#if GS_TB_MAP_ONLY || GS_TB_MASK_ONLY
+#if GS_TB_MAP_ONLY || GS_TB_MASK_ONLY || GS_NOISE_ONLY
 // Entry tables of the marching kernel's per-cell form KER (gs_step_tb_mk, gs_step_tb_wk), variant F (0: general, 3: .op):
 // [k - 1], [cpl 1, 2, 4][k - 1] and [rule][cpl 1, 2, 4][k - 1]
 #define GS_CELL_KS(KER, F, C, R) {GS_FN(KER, 1, F, C, R), GS_FN(KER, 2, F, C, R), GS_FN(KER, 3, F, C, R), GS_FN(KER, 4, F, C, R)}
@@ -900,6 +919,21 @@ const void *GS_SUFFIX(gs_tb_mask_kernel)(int k, int fast, int cpl, int rule)
         {GS_CELL_KS(gs_step_tb_wk, 3, 1, 0), GS_CELL_KS(gs_step_tb_wk, 3, 2, 0),
          {GS_FN(gs_step_tb_wk, 1, 3, 4, 0), GS_FN(gs_step_tb_wk, 2, 3, 4, 0), nullptr, nullptr}},
         GS_CELL_CPLS(gs_step_tb_wk, 3, 1), GS_CELL_CPLS(gs_step_tb_wk, 3, 2)};
+    return tb_cell_entry(general, op, k, fast, cpl, rule);
+#endif
+}
+#endif
+
+#if GS_NOISE_ONLY
+// Kernel entry of the marching kernel's noise form (gs_kernels.h: gs_tb_noise_kernel_*), the parameters of
+// gs_tb_map_kernel_*.
+const void *GS_SUFFIX(gs_tb_noise_kernel)(int k, int fast, int cpl, int rule)
+{
+    static const void *const general[3][3][4] = GS_CELL_RULES(gs_step_tb_zk, 0);
+#if GS_MATH_FUSED
+    return tb_cell_entry(general, nullptr, k, fast, cpl, rule);
+#else
+    static const void *const op[3][3][4] = GS_CELL_RULES(gs_step_tb_zk, 3);
     return tb_cell_entry(general, op, k, fast, cpl, rule);
 #endif
 }

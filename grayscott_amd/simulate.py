@@ -29,6 +29,11 @@ Domain masks (``gs_ctx_set_mask``): ``--hip-mask FILE.npy`` (or ``FILE.npz`` wit
 makes the cells where it is nonzero walls.  It combines with every other option but the parameter map's, which it
 refuses.
 
+Noise (``gs_ctx_set_noise``): ``--hip-noise SU[:SV]`` adds a seeded stochastic increment to every step -- ``sigma * xi`` per
+species, ``xi`` uniform on [-1, 1) and a pure function of (``--hip-noise-seed N``, step index, row, column); the run's first
+step has index ``--hip-noise-step S`` (default 0).  The result file is bit-reproducible from the command line, whatever
+kernel, fusion depth or slab count computes it.  Together with a parameter map or a mask the library refuses.
+
 Regional observables (``gs_fields_region_summaries``, ``gs_fields_region_morphology``): ``--hip-regions RH[xRW]`` cuts the
 grid into regions of RH x RW cells (RW a multiple of 4, at least 16; one number: square) and writes, next to the output,
 ``<stem>.regions.npz``: per observed image the summaries of U and V and the bit-quad counts of V (``--hip-region-threshold-v
@@ -100,6 +105,7 @@ def parse(argv=None):
     add_backend_args(ap)
     add_param_map_args(ap)
     add_mask_args(ap)
+    add_noise_args(ap)
     add_image_args(ap)
     add_region_args(ap)
     add_time_stats_args(ap)
@@ -167,6 +173,29 @@ def add_mask_args(ap: argparse.ArgumentParser) -> None:
     mk = ap.add_argument_group("HIP backend: domain mask")
     mk.add_argument("--hip-mask", default=None, metavar="FILE.npy",
                     help="walls where the array (.npy, or array `mask` of a .npz) is nonzero; not with a parameter map")
+
+
+def add_noise_args(ap: argparse.ArgumentParser) -> None:
+    """The noise term's options of the ``--hip-*`` group (simulate only)."""
+    nz = ap.add_argument_group("HIP backend: noise")
+    nz.add_argument("--hip-noise", default=None, metavar="SU[:SV]",
+                    help="seeded noise: sigma of U's and of V's increment per step (SV defaults to 0); not with a parameter map or a mask")
+    nz.add_argument("--hip-noise-seed", default=0, type=int, metavar="N", help="the noise's seed (u64, default 0)")
+    nz.add_argument("--hip-noise-step", default=0, type=int, metavar="S", help="index of the run's first step (u64, default 0)")
+
+
+def noise_term(args):
+    """``(sigma_u, sigma_v, seed, step)`` as ``--hip-noise`` and its companions ask for, or None."""
+    text = getattr(args, "hip_noise", None)
+    if text is None:
+        return None
+    try:
+        parts = [float(x) for x in str(text).split(":")]
+    except ValueError:
+        parts = []
+    if len(parts) not in (1, 2):
+        raise ValueError(f"--hip-noise wants SU or SU:SV, got {text!r}")
+    return parts[0], parts[1] if len(parts) == 2 else 0.0, int(getattr(args, "hip_noise_seed", 0) or 0), int(getattr(args, "hip_noise_step", 0) or 0)
 
 
 def _reduce_factor(text: str) -> int:
@@ -643,6 +672,9 @@ def run(args, hip_args: HipArgs | None = None, out=None) -> dict:
                 json.dump(pmap[2], f, indent=1)
     if mask is not None:
         sim.set_mask(mask)
+    noise = noise_term(args)
+    if noise is not None:   # (with a map or a mask attached the library refuses, and its message says which)
+        sim.set_noise(noise[0], noise[1], seed=noise[2], step=noise[3])
     if out is None and args.output.lower().endswith((".h5", ".hdf5")):
         out = hdf5_min.create(args.output, (args.nbimage,) + img_shape)   # dataset "matrix" (hdf5.rs:24)
     elif out is None:

@@ -2744,6 +2744,29 @@ class Simulation:
         """Detach the domain mask: every cell is fluid again."""
         capi.check(self.context._lib.gs_ctx_set_mask(self.context.handle, None))
 
+    def set_noise(self, sigma_u: float, sigma_v: float = 0.0, seed: int = 0, step: int = 0) -> None:
+        """Attach a noise term (``gs_ctx_set_noise``): from now on every step adds ``sigma * xi`` to each species, ``xi``
+        uniform on [-1, 1) (variance 1/3) and a pure function of (``seed``, step index, global row, global column), so a
+        run is bit-reproducible whatever kernel, fusion depth, slab or process count computes it.  ``step`` is the index
+        of the next step; it advances with every step enqueued on this context (``noise()`` reports it).  A species whose
+        sigma is 0 is not touched.  Collective in a multi-process run (every process passes the same values)."""
+        n = capi.GsNoise(float(sigma_u), float(sigma_v), int(seed) & 0xFFFFFFFFFFFFFFFF, int(step) & 0xFFFFFFFFFFFFFFFF)
+        capi.check(self.context._lib.gs_ctx_set_noise(self.context.handle, ctypes.byref(n)))
+
+    def clear_noise(self) -> None:
+        """Detach the noise term: every step is the deterministic reference step again."""
+        capi.check(self.context._lib.gs_ctx_set_noise(self.context.handle, None))
+
+    def noise(self) -> Optional[dict]:
+        """The noise term in force as ``{"sigma_u", "sigma_v", "seed", "step"}`` -- ``step``: the index of the next step --
+        or ``None`` when none is attached.  Saved with a snapshot, it continues the run exactly (``set_noise(**saved)``)."""
+        n = capi.GsNoise()
+        attached = ctypes.c_int32(0)
+        capi.check(self.context._lib.gs_ctx_get_noise(self.context.handle, ctypes.byref(n), ctypes.byref(attached)))
+        if not attached.value:
+            return None
+        return {"sigma_u": float(n.sigma_u), "sigma_v": float(n.sigma_v), "seed": int(n.seed), "step": int(n.step)}
+
     def perform_step(self, species: Species) -> None:
         """One ``gs_step`` then ``species.flip()`` -- the ``SimulateStep`` form (cpu.rs:21-42)."""
         in_u, in_v, out_u, out_v = species.in_out()

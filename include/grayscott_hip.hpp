@@ -1439,6 +1439,21 @@ class Simulation {
         check(gs_ctx_set_mask(context_->get(), m.raw()));
     }
     void clear_mask() const { check(gs_ctx_set_mask(context_->get(), nullptr)); }
+    // Noise (gs_ctx_set_noise): every step adds sigma * xi per species, xi uniform on [-1, 1) and a pure function of (seed,
+    // step index, global row, global column); `step` is the index of the next step.  noise() returns the term in force with
+    // the current step -- saved with a snapshot it continues the run exactly -- or nothing; clear_noise() detaches it.
+    void set_noise(float sigma_u, float sigma_v = 0.0f, uint64_t seed = 0, uint64_t step = 0) const
+    {
+        const gs_noise n{sigma_u, sigma_v, seed, step};
+        check(gs_ctx_set_noise(context_->get(), &n));
+    }
+    void clear_noise() const { check(gs_ctx_set_noise(context_->get(), nullptr)); }
+    bool noise(gs_noise *out) const
+    {
+        int32_t attached = 0;
+        check(gs_ctx_get_noise(context_->get(), out, &attached));
+        return attached != 0;
+    }
     const Context &context() const { return context_; }
     // an Ensemble of params.size() members (Species::new's pattern in each)
     Ensemble make_ensemble(Shape shape, const std::vector<Parameters> &params) const

@@ -293,6 +293,50 @@ int32_t gs_ctx_set_param_map(gs_ctx *ctx, gs_field *feed, gs_field *kill);
  * choices of the kernel set in force.  Ensembles ignore the mask; summaries include wall cells. */
 int32_t gs_ctx_set_mask(gs_ctx *ctx, gs_field *mask);
 
+/* Noise: a seeded, bit-reproducible stochastic term of the step.  While noise is attached, every step of gs_step / gs_run
+ * is the reference step followed, per cell and species, by one increment drawn from a counter-based generator: a pure
+ * function of (seed, step, global row, global column), so the bits do not depend on the kernel, the fusion depth, the
+ * columns per lane, the slab count or the process count.  The definition, all words u32:
+ *   Philox2x32-10, M = 0xD256D193, W = 0x9E3779B9.  One round:  (hi, lo) = M * c0 (the 64-bit product);
+ *     (c0, c1) <- (hi ^ k ^ c1, lo).  Ten rounds; before every round but the first, k += W.
+ *     philox(0, 0, 0) = (ff1dae59, 6cd10df2);  philox(ffffffff, ffffffff, ffffffff) = (2c3f628b, ab4fd7ad);
+ *     philox(243f6a88, 85a308d3, 13198a2e) = (dd7ce038, f62a4c12)                       [(c0, c1, k) -> result]
+ *   step key, formed on the host for the u64 seed and the u64 step index s:
+ *     key(s) = philox(c0 = (u32)s, c1 = (u32)(s >> 32), k = (u32)seed)[0] ^ (u32)(seed >> 32)
+ *   cell draw at global row r, global column c in step s:  (x0, x1) = philox(c0 = c, c1 = r, k = key(s));
+ *     x0 is U's draw, x1 is V's.  Under the periodic rule a cell computed at a wrapped position uses the wrapped (r, c).
+ *   value:  xi(x) = ((float)(int32_t)(x >> 8) - 8388608.0f) * 0x1p-23f  -- every operation exact in f32.
+ *   step:   with (nu, nv) the reference step's outputs for the cell, every operation of the contract unchanged,
+ *     out_u = nu + sigma_u * xi(x0),  out_v = nv + sigma_v * xi(x1):
+ *     one rounded f32 multiply and one rounded f32 add per species in the context's float mode (GS_MATH_STRICT flushes a
+ *     sub-normal product or sum), never contracted in either flavour -- GS_MATH_FUSED fuses only what it fuses without
+ *     noise.  A species whose sigma is 0.0f is not touched at all: its value is nu bit for bit, -0 stays -0.
+ * The increments are UNIFORM, not Gaussian: xi is uniform on the 2^24 multiples of 2^-23 in [-1, 1), variance 1/3, mean
+ * -2^-24.  Over many steps only the variance sigma^2 / 3 per step matters (Euler-Maruyama in the weak sense).  Nothing is
+ * clamped: additive noise can take V slightly below 0.
+ *   step : the index of the next step the context executes.  It advances by one per time step that gs_step or gs_run
+ *          enqueues on this context, whichever species they advance; gs_ctx_get_noise returns the current value.  A
+ *          snapshot of the planes plus the saved gs_noise continues a run exactly; gs_ctx_set_noise with the same seed and
+ *          an earlier step replays it.
+ * gs_ctx_set_noise(ctx, NULL) detaches the noise.  Sigmas must be finite and >= 0: GS_ERR_INVALID otherwise.  Both sigmas
+ * zero is legal and stays attached: the noise kernels run and give the uniform run's bits (the A/B for measuring cost).
+ * Noise is the third kind of a context's per-cell data, one kind in force at a time: with a parameter map or a domain mask
+ * attached the call returns GS_ERR_UNSUPPORTED, and gs_ctx_set_param_map / gs_ctx_set_mask refuse a context that has noise.
+ * A pinned GS_KERNEL_WINDOW, _LDS or _TILE: GS_ERR_UNSUPPORTED.  use_graph = 1: GS_ERR_UNSUPPORTED (a replayed graph would
+ * replay its step keys).  The call waits for enqueued work; in a multi-process run it is collective and every process
+ * passes the same struct.  With noise, gs_run runs the marching kernel at every grid size, gs_step the streaming one and a
+ * pinned GS_KERNEL_SIMPLE the simple one; their noise forms carry a "/noise" suffix in gs_ctx_info (e.g.
+ * "tb-k4c2/strict.op/noise") and share no differences.  The on-line tuner keeps noise runs apart from the other kernel sets;
+ * whatever it does, step s is computed with key(s).  Units at rest never apply.  Ensembles ignore the noise.
+ *   gs_ctx_get_noise : *out = the struct in force with the current step (untouched when none is), *attached = 0 / 1. */
+typedef struct gs_noise {
+    float sigma_u, sigma_v;
+    uint64_t seed;
+    uint64_t step;
+} gs_noise;
+int32_t gs_ctx_set_noise(gs_ctx *ctx, const gs_noise *n);
+int32_t gs_ctx_get_noise(const gs_ctx *ctx, gs_noise *out, int32_t *attached);
+
 /* Concentration::default / zeros / ones (concentration/mod.rs:205-218) = create (+ fill).
  * `rows`, `cols` are the GLOBAL shape; every process passes the same values. */
 int32_t gs_field_create(gs_ctx *ctx, gs_field **out, uint64_t rows, uint64_t cols);

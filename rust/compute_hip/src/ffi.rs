@@ -95,6 +95,16 @@ pub struct gs_component_overlap {
     pub cells: u64,
 }
 
+/// The noise term of a context (include/gs_hip.h: gs_ctx_set_noise): sigmas, seed, index of the next step (24 bytes).
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct gs_noise {
+    pub sigma_u: f32,
+    pub sigma_v: f32,
+    pub seed: u64,
+    pub step: u64,
+}
+
 /// A plane's summary computed on the device (32 bytes; fold order in include/gs_hip.h).
 #[repr(C)]
 #[derive(Copy, Clone, Debug, Default)]
@@ -152,6 +162,8 @@ extern "C" {
     pub fn gs_ctx_destroy(ctx: *mut gs_ctx) -> i32;
     pub fn gs_ctx_set_param_map(ctx: *mut gs_ctx, feed: *mut gs_field, kill: *mut gs_field) -> i32;
     pub fn gs_ctx_set_mask(ctx: *mut gs_ctx, mask: *mut gs_field) -> i32;
+    pub fn gs_ctx_set_noise(ctx: *mut gs_ctx, n: *const gs_noise) -> i32;
+    pub fn gs_ctx_get_noise(ctx: *const gs_ctx, out: *mut gs_noise, attached: *mut i32) -> i32;
     pub fn gs_field_create(ctx: *mut gs_ctx, out: *mut *mut gs_field, rows: u64, cols: u64) -> i32;
     pub fn gs_field_destroy(ctx: *mut gs_ctx, f: *mut gs_field) -> i32;
     pub fn gs_field_raw_shape(f: *const gs_field, raw_rows: *mut u64, pitch: *mut u64) -> i32;

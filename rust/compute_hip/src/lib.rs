@@ -333,6 +333,21 @@ impl Simulation {
         species.flip()
     }
 
+    /// Noise (`gs_ctx_set_noise`): every step adds `sigma * xi` per species, `xi` uniform on [-1, 1) and a pure function
+    /// of (seed, step index, global row, global column); `step` is the index of the next step.  `None` detaches it.
+    pub fn set_noise(&self, noise: Option<ffi::gs_noise>) -> Result<(), HipError> {
+        // SAFETY: plain FFI call on a live context; the struct is read before the call returns
+        check(unsafe { ffi::gs_ctx_set_noise(self.context.0, noise.as_ref().map_or(std::ptr::null(), |n| n as *const ffi::gs_noise)) })
+    }
+
+    /// The noise term in force with the current step counter (`gs_ctx_get_noise`), or `None`.
+    pub fn noise(&self) -> Result<Option<ffi::gs_noise>, HipError> {
+        let mut n = ffi::gs_noise { sigma_u: 0.0, sigma_v: 0.0, seed: 0, step: 0 };
+        let mut attached = 0i32;
+        check(unsafe { ffi::gs_ctx_get_noise(self.context.0, &mut n, &mut attached) })?;
+        Ok(if attached != 0 { Some(n) } else { None })
+    }
+
     /// Wait for the downloads enqueued by `write_scalar_view_after` (not for later steps)
     pub fn download_wait(&self) -> Result<(), HipError> {
         check(unsafe { ffi::gs_download_wait(self.context.0) })

@@ -248,7 +248,7 @@ def ensemble_against_sequential(members, rows, cols, steps, calls, sample, bound
 
 
 RULE_SET = {"/periodic": 1, "/neumann": 2}
-FORMS = {"map": "mk", "mask": "wk"}  # the attachment in a reported kernel name -> the infix of the entry's name
+FORMS = {"map": "mk", "mask": "wk", "noise": "zk"}  # the attachment in a reported kernel name -> the infix of the entry's name
 
 
 def entry_of(name, form):
