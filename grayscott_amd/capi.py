@@ -73,7 +73,7 @@ EXPORTS = (
     "gs_time_stats_create", "gs_time_stats_destroy", "gs_time_stats_reset", "gs_time_stats_accumulate", "gs_time_stats_samples",
     "gs_time_stats_result", "gs_time_stats_download",
     "gs_members_time_stats_create", "gs_members_time_stats_accumulate", "gs_members_time_stats_result",
-    "gs_ctx_quiet_stats",
+    "gs_ctx_quiet_stats", "gs_ctx_quiet_edge_stats",
 )
 
 
@@ -278,6 +278,7 @@ def load() -> ctypes.CDLL:
         "gs_ctx_stats": (i32, [vp, P(GsStats)]),
         "gs_ctx_set_pass_timing": (i32, [vp, i32]),
         "gs_ctx_quiet_stats": (i32, [vp, P(u64)]),
+        "gs_ctx_quiet_edge_stats": (i32, [vp, P(u64)]),
         "gs_field_mark_written": (i32, [vp, vp]),
         "gs_rccl_selftest": (i32, [i32, u64]),
         "gs_runtime_info": (i32, [i32, ctypes.c_char_p, ctypes.c_size_t]),

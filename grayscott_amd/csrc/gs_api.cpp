@@ -172,6 +172,21 @@ int32_t refresh_ghosts(gs_ctx *ctx, gs_field *f)
     return GS_OK;
 }
 
+// Units of edge positions that left without computing: the counts kept from earlier geometries plus the per-position
+// counters behind the words (gs_kernels.h: GsQuiet::edge_skips).  The caller has waited for the work enqueued.
+static int32_t quiet_edge_skips(gs_ctx *ctx, uint64_t *out)
+{
+    const gs_ctx::QuietRt &qr = ctx->quiet;
+    *out = qr.edge_skipped;
+    if (qr.words && qr.cap) {
+        std::vector<uint32_t> host(qr.cap);
+        GS_HIP(hipSetDevice(ctx->slabs[0].device));
+        GS_HIP(hipMemcpy(host.data(), qr.words + 2 * qr.cap, qr.cap * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (uint32_t n : host) *out += n;
+    }
+    return GS_OK;
+}
+
 int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fuse, const GsAttached &at)
 {
     int32_t kernel = ctx->o.kernel;
@@ -194,18 +209,29 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
                 GsQuiet q;
                 q.in = qr.words + (size_t)qr.in_slot * qr.cap;
                 q.out = qr.words + (size_t)(1 - qr.in_slot) * qr.cap;
+                q.edge_skips = qr.words + 2 * qr.cap; // (behind the two slots; zeroed when allocated, never by a pass)
                 q.skipped = qr.skipped;
                 q.mode = qr.mode;
                 q.cap = (int64_t)qr.cap;
                 q.need = 0;
                 q.launched = 0;
-                if (qr.mode == 1 && qr.words) // edge positions are never written: they stay "unknown"
+                q.edge_launched = 0;
+                if (qr.mode == 1 && qr.words) // words that no unit writes (edge positions under the zero-halo rule) stay "unknown"
                     e = hipMemsetAsync(qr.words, 0, 2 * qr.cap * sizeof(uint32_t), stream);
                 if (e == hipSuccess) e = gs_launch_tb_strict(a, fuse, stream, &name, at, &q);
                 if (e != hipSuccess) break;
                 if (q.need > (int64_t)qr.cap && qr.mode == 1) { // nothing was launched: room for this geometry first
-                    if (qr.words) { GS_HIP(hipStreamSynchronize(stream)); GS_HIP(hipFree(qr.words)); qr.words = nullptr; qr.cap = 0; }
-                    GS_HIP(hipMalloc(&qr.words, 2 * (size_t)q.need * sizeof(uint32_t)));
+                    if (qr.words) { // another geometry: its edge units' skip counts are kept, its words are not
+                        GS_HIP(hipStreamSynchronize(stream));
+                        uint64_t sum = 0;
+                        GS_TRY(quiet_edge_skips(ctx, &sum));
+                        qr.edge_skipped = sum;
+                        GS_HIP(hipFree(qr.words));
+                        qr.words = nullptr;
+                        qr.cap = 0;
+                    }
+                    GS_HIP(hipMalloc(&qr.words, 3 * (size_t)q.need * sizeof(uint32_t)));
+                    GS_HIP(hipMemset(qr.words, 0, 3 * (size_t)q.need * sizeof(uint32_t)));
                     qr.cap = (size_t)q.need;
                     if (!qr.skipped) {
                         GS_HIP(hipMalloc(&qr.skipped, (size_t)kQuietCounters * kQuietCounterStride * sizeof(unsigned long long)));
@@ -215,6 +241,7 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
                 }
                 if (q.launched > 0) {
                     qr.launched += (uint64_t)q.launched;
+                    qr.edge_launched += (uint64_t)q.edge_launched;
                     qr.passes++;
                     if (qr.mode == 3) qr.steady++;
                 } else {
@@ -1141,6 +1168,21 @@ int32_t gs_ctx_quiet_stats(gs_ctx *ctx, uint64_t out[4])
         for (int i = 0; i < kQuietCounters; ++i) out[1] += host[i * kQuietCounterStride];
     }
     return GS_OK;
+}
+
+int32_t gs_ctx_quiet_edge_stats(gs_ctx *ctx, uint64_t out[3])
+{
+    if (!ctx || !out) return fail(GS_ERR_INVALID, "null argument");
+    GS_TRY(sync_all(ctx));
+    out[0] = ctx->quiet.edge_launched;
+    out[1] = out[2] = 0;
+    if (ctx->quiet.skipped) {
+        unsigned long long host[kQuietCounters * kQuietCounterStride];
+        GS_HIP(hipSetDevice(ctx->slabs[0].device));
+        GS_HIP(hipMemcpy(host, ctx->quiet.skipped, sizeof host, hipMemcpyDeviceToHost));
+        for (int i = 0; i < kQuietCounters; ++i) out[2] += host[i * kQuietCounterStride + 2];
+    }
+    return gsi::quiet_edge_skips(ctx, &out[1]);
 }
 
 int32_t gs_ctx_info(const gs_ctx *ctx, char *kernel_name, size_t cap, uint64_t *launches)

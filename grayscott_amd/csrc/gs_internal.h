@@ -228,13 +228,15 @@ struct gs_ctx {
     // hands them to the launcher and counts what it reports.  Nothing is carried from one call to the next.
     struct QuietRt {
         bool enabled = true;         // GS_HIP_QUIET_UNITS (read by gs_ctx_create)
-        uint32_t *words = nullptr;   // device: the words of slot 0, then of slot 1, `cap` each
+        uint32_t *words = nullptr;   // device: the words of slot 0, of slot 1, then the edge units' skip counters, `cap` each
         size_t cap = 0;
-        unsigned long long *skipped = nullptr; // device: kQuietCounters counters, kQuietCounterStride words apart
+        unsigned long long *skipped = nullptr; // device: kQuietCounters lines of kQuietCounterStride words: skipped units [0] off the edges, [2] next to an edge position
         int mode = 0;                // GsQuiet::mode of the pass being enqueued; 0 = a pass like any other
         int in_slot = 0;             // the slot that pass reads
         bool refused = false;        // the launcher ran the production entry instead (the geometry is not eligible)
         uint64_t launched = 0, passes = 0, steady = 0; // gs_ctx_quiet_stats: units and passes of the quiet entries, mode-3 passes
+        uint64_t edge_launched = 0;  // gs_ctx_quiet_edge_stats: the units of edge positions among `launched`
+        uint64_t edge_skipped = 0;   // ... the skipped ones counted under earlier geometries (the counters go with the words)
     } quiet;
     std::vector<struct gs_time_stats *> time_stats; // the time statistics made on this context and not destroyed yet (gs_time_stats.cpp)
     // The context's per-cell data (gs_attached.cpp), one kind at a time: a parameter map (gs_ctx_set_param_map: plane[0] = F,

@@ -85,25 +85,42 @@ struct GsMapPlanes {
 struct GsMaskPlanes {
     const float *link;
 };
-// Units at rest (gs_step_tb_dx_qk): one word per unit position -- row chunk cc of range a, strip -- of
-// the planes a full pass reads (`in`) and of the ones it writes (`out`), at [cc * strips + strip]: kQuietRest = every cell
-// of the chunk's rows x the strip's output columns in that slot's planes is bitwise (U, V) = (1.0f, +0.0f), kQuietActive =
-// not so, 0 = unknown (edge positions, always).  The second argument of the quiet entries: GsStepArgs, and with it every
-// other kernel's code, stays as it is.  mode: 1 = the first full pass of a gs_run (no word is read; every interior unit
-// computes, checks what it stores and writes its word in `out`), 2 = the second (`in` is read: a unit whose own word
-// there says "active" writes "active" without a check), 3 = every later one (a unit whose nine positions in `in` and own
-// position in `out` are at rest leaves at once).  cap: the words each array holds.  The launcher hands this back with
-// `need` = the words the launch's geometry takes and `launched` = its units, or 0 when the launch is not one of the quiet
-// entries' (it then ran the production entry and touched no word); with need > cap in mode 1 it launches nothing.
+// Units at rest (gs_step_tb_dx_qk): two words per unit position -- row chunk cc of range a, strip -- of
+// the planes a full pass reads (`in`) and of the ones it writes (`out`), at [2 * (cc * strips + strip) + part]: part 0 / 1
+// = the upper / lower half of the chunk's rows, as an edge unit dispatched in two halves (edge_split = 2) divides them.
+// kQuietRest = every cell of the grid in that part's rows x the strip's output columns is bitwise (U, V) = (1.0f, +0.0f) in
+// that slot's planes (the padding columns a right-edge strip also stores count for nothing); kQuietActive and 0 (unknown)
+// claim nothing.  A whole unit writes both words and a half its own -- two halves of a position are two waves with no
+// order between them, so no word has two writers in a pass and none needs an atomic; a position is at rest when both
+// parts are.  A position outside the grid does not exist and counts as at rest: no tap reads it.
+// Edge positions (first and last strips, chunks that touch the grid's first or last rows) have words like any other under
+// the clipped rule: the reference accumulates weight * (tap - centre) over the taps that exist, every one of them +-0 in a
+// window at rest, so (1, +0) is a fixed point on the edges and in the corners as it is inside (finite weights).  Under
+// the zero-halo rule it is not -- a halo cell of 0 next to U = 1 is a tap of -1, those cells really change -- and there
+// an edge position's words stay 0: its units and their inner neighbours always compute.
+// The second argument of the quiet entries: GsStepArgs, and with it every other kernel's code, stays as it is.  mode: 1 =
+// the first full pass of a gs_run (no word is read; every unit computes and writes its words in `out`: an interior unit
+// after its march, by the march's check of what it stored; a unit of an edge position before it, "at rest" when every cell
+// of the input window of its march is), 2 = the second (`in` is read: a unit whose own part there says "active" writes
+// "active" without a look), 3 = every later one (a unit leaves at once when every part of the existing positions among
+// the nine around it is at rest in `in` and its own part -- a whole unit: both -- in `out`; the other half's word in
+// `out` is that half's to write in the same pass and is not read).  A half shorter than K rows, whose window reaches past
+// the other half into the next chunk, is covered: the nine positions hold it.  cap: the words each array holds.  The
+// launcher hands this back with `need` = the words the launch's geometry takes, `launched` = its units and `edge_launched`
+// = those of edge positions among them, or 0 when the launch is not one of the quiet entries' (it then ran the production
+// entry and touched no word); with need > cap in mode 1 it launches nothing.
 constexpr uint32_t kQuietRest = 1, kQuietActive = 2;
-constexpr int kQuietCounters = 64, kQuietCounterStride = 16; // the skipped-unit counters: 64 of them, 128 bytes apart
+constexpr int kQuietCounters = 64, kQuietCounterStride = 16; // the skipped-unit counters: 64 lines of them, 128 bytes apart
 struct GsQuiet {
     const uint32_t *in;
     uint32_t *out;
-    unsigned long long *skipped; // += 1 per skipping wave, at [(workgroup % kQuietCounters) * kQuietCounterStride]
+    uint32_t *edge_skips; // += 1 per skipping unit of an edge position, at the index of its word (no atomic: one writer)
+    // += 1 per skipping interior unit, at [(workgroup % kQuietCounters) * kQuietCounterStride + which]: which = 2 for a unit next
+    // to an edge position, 0 for a unit with interior positions all around it (tb_unit<QUIET>)
+    unsigned long long *skipped;
     int32_t mode;
     int32_t pad;
-    int64_t cap, need, launched; // (host side only)
+    int64_t cap, need, launched, edge_launched; // (host side only)
 };
 // Noise (gs_ctx_set_noise; include/gs_hip.h: the definition).  The second argument of the noise kernels (gs_*_zk): the step
 // keys of the pass -- level j (1 .. K) of a fused pass computes step step0 + j - 1 with key[j - 1]; a single step uses

@@ -719,13 +719,16 @@ __device__ __forceinline__ unsigned long long tb_march(const GsStepArgs &a, int 
 // NEU: the zero-flux rule's kernels (GsStepArgs::zero_halo = 3; gs_step_tb_nk and its kin).
 // MAP: the parameter map's forms (gs_step_tb_mk): 4-wave workgroups, no difference sharing.  MASK: the domain mask's
 // (gs_step_tb_wk), likewise; mp.feed is the link plane.
-// QUIET: the quiet entries (gs_step_tb_dx_qk; gs_kernels.h: GsQuiet).  An interior unit reads the words of the nine
-// positions around it in the slot it reads and of its own position in the slot it writes -- once, a lane each -- and, in
-// mode 3 with all ten at rest, leaves: no loads, no arithmetic, no stores; its word stays.  Otherwise it marches as ever and
-// then writes its word: "active" without a look when its own input position was active (a developed pattern pays
-// nothing), else by the march's check of what it stored -- a unit at rest that a front enters is caught in the pass in
-// which that happens.  Edge units (first and last strip, chunks that touch the grid's first or last rows, the halves of
-// edge_split = 2) never read or write a word, so they and their inner neighbours always compute.
+// QUIET: the quiet entries (gs_step_tb_dx_qk; gs_kernels.h: GsQuiet).  A unit reads the words -- two per position, one per
+// half -- of the nine positions around it in the slot it reads and of its own parts in the slot it writes -- once, a lane
+// each, a position outside the grid counting as at rest -- and, in mode 3 with all of them at rest, leaves: no loads, no
+// arithmetic, no stores; its words stay.  Otherwise a whole interior unit marches as ever and then writes its two words:
+// "active" without a look when its own input position was active (a developed pattern pays nothing), else by the march's
+// check of what it stored -- a unit at rest that a front enters is caught in the pass in which that happens.  A unit of an
+// edge position (first and last strips, chunks that touch the grid's first or last rows, both halves under edge_split =
+// 2) has words under the clipped rule and writes its own before it marches, from the nine positions or from the cells of
+// its input window (below); under the zero-halo rule it never reads or writes a word, so it and its inner neighbours
+// always compute.
 template <int K, int FAST, int CPL, int WG, bool PER = false, bool NEU = false, bool MAP = false, bool MASK = false, bool QUIET = false,
           bool NOISE = false>
 __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &mp = GsMapPlanes{nullptr, nullptr},
@@ -839,6 +842,7 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &
         ur0 = a.rb0 + (chunk - chunks_a) * rpu;
         ur1 = min(ur0 + rpu, a.rb1);
     }
+    const bool whole = half < 0 || ur1 - ur0 < 2; // (QUIET) the unit is all there is of its position: a one-row chunk has one half
     if (half >= 0) { // this unit is one half of its chunk's rows
         const int hh = (ur1 - ur0 + 1) >> 1;
         if (half == 0) ur1 = min(ur0 + hh, ur1);
@@ -863,21 +867,96 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &
     // row and a cell in the first or last column for the missing column, so no row or column outside the grid is read.
     constexpr bool KINDS = (FAST & 1) && !GS_MATH_FUSED;
     if constexpr (QUIET) {
+        typedef uint32_t word2 __attribute__((ext_vector_type(2))); // the words of a position: part 0, part 1
+        // (The launcher sends only passes over range a here: row_chunk is a chunk's.)
+        if ((edge || half >= 0) && !a.zero_halo) { // wave-uniform
+            // A unit of an edge position -- every half-height unit is one -- under the clipped rule (under the zero-halo rule
+            // it has no word and never rests).  Lanes 0..17: part (lane & 1) of neighbour lane >> 1 in the slot read; 18, 19:
+            // this unit's parts in the slot written; a position outside the grid is at rest, and so are the words a lane does
+            // not read.
+            const int pos = row_chunk * strips + strip;
+            const int nb = lane >> 1, part = lane & 1;
+            // (What is kept for later is kept per lane, in vector registers, and formed here: the march has no scalar register
+            // to spare, and the ones this block holds while the window is read are taken from it.  The empty asm statements
+            // of this block and of the interior branch below, and the wave's end in place of a `return`, only steer the
+            // register allocator; what they buy -- 126 vector registers at K = 4, nothing spilled -- is that of one compiler
+            // version and is held by tests/test_isa_quiet.py: a compiler update that makes that test fail lands here, and
+            // profiles/quiet_edges.md lists the forms that did not fit.)
+            int mine = 2 * pos + part, own = whole || part == half;
+            asm volatile("" : "+v"(mine), "+v"(own));
+            uint32_t word = kQuietRest;
+            if (qa.mode >= 2) {
+                const int rc = row_chunk + nb / 3 - 1, st = strip + nb % 3 - 1;
+                if (lane < 18) {
+                    if (rc >= 0 && rc < chunks_a && st >= 0 && st < strips) word = qa.in[2 * (rc * strips + st) + part];
+                } else if (lane < 20 && qa.mode == 3 && own) {
+                    word = qa.out[mine];
+                }
+            }
+            // The unit settles its word BEFORE it marches: the edge marches have no check built in, and a value kept across
+            // them is a register the march does not have (a look at the stored cells after the march: 4 vector and 4 scalar
+            // registers spilled at K = 4).  What it will store is at rest when the nine positions are, or else when every cell
+            // of the grid in its input window -- the rows and columns its march reads, K around its own and the sacrificial
+            // lanes' -- is (1.0f, +0.0f): a fixed point.  Anything else it calls active, which claims nothing: "at rest" is
+            // always the truth, "active" may be said of cells at rest next to a front.  So that such a word of a neighbour's
+            // does not keep a unit computing whose whole window rests, the window stands in for the nine positions there.
+            bool rest = qa.mode >= 2 && __builtin_amdgcn_ballot_w64(lane < 18 && word != kQuietRest) == 0;
+            const bool active = __builtin_amdgcn_ballot_w64(lane < 18 && nb == 4 && own && word == kQuietActive) != 0;
+            int settled = qa.mode == 3 && __builtin_amdgcn_ballot_w64(lane >= 18 && word != kQuietRest) == 0;
+            asm volatile("" : "+v"(settled));
+            if (!rest && !active) {
+                // The look at the window: the cells the march is about to load are loaded once more -- in the two full passes
+                // of a call by every edge unit, later only next to a front.  (A lane whose columns lie outside the grid looks
+                // at the grid's first / last column instead, which is in the window of such a strip: no lane sits out, every
+                // address is a cell's.)
+                const int c = strip * W + (lane - S) * CPL;
+                const int r0 = max(ur0 - K, 0), n = min(ur1 + K, a.rows) - r0;
+                uint32_t differ = 0u;
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) {
+                    const ptrdiff_t at = (ptrdiff_t)r0 * a.pitch + min(max(c + e, 0), a.cols - 1);
+                    const float *pu = a.in_u + at, *pv = a.in_v + at;
+                    for (int r = 0; r < n; ++r, pu += a.pitch, pv += a.pitch)
+                        differ |= (__builtin_bit_cast(uint32_t, *pu) ^ 0x3f800000u) | __builtin_bit_cast(uint32_t, *pv);
+                }
+                rest = __builtin_amdgcn_ballot_w64(differ != 0u) == 0;
+            }
+            if (rest && __builtin_amdgcn_readfirstlane(settled) != 0) {
+                // The unit leaves.  It is counted without an atomic -- the skip count of the interior units stays the one atomic
+                // site of the entry --: a counter per position and part behind the words, which no other wave of the pass
+                // touches.  (The wave ends HERE: a `return` is joined with the one behind the marches, and what this block
+                // needs then lives across them.  In a GS_TB_TRACE build it therefore leaves no trace record, like the interior
+                // units that leave by the `return` below: the record is written behind the marches.)
+                if (lane < 2 && own) qa.edge_skips[mine] += 1u;
+                __builtin_amdgcn_endpgm();
+            }
+            // lanes 0 and 1 write the word of part 0 / 1 where it is this unit's
+            if (lane < 2 && own) qa.out[mine] = rest ? kQuietRest : kQuietActive;
+        }
         if (!edge) { // wave-uniform
-            // (An interior unit has a chunk above and below it and a strip on either side: every index is a position's.
-            // The launcher sends only passes over range a here, whose half-height units are all edge units: `inner` holds.)
+            // (An interior unit has a chunk above and below it and a strip on either side: every index is a position's.  A
+            // half-height unit off the edges -- the upper half of a tall bottom chunk -- has settled its word above.)
             const bool inner = half < 0 && row_chunk >= 0;
             const int pos = row_chunk * strips + strip;
-            uint32_t *const mine = inner ? qa.out + pos : nullptr; // this unit's word in the slot it writes
+            uint32_t *mine = inner ? qa.out + 2 * pos : nullptr; // this unit's words in the slot it writes
+            asm volatile("" : "+s"(mine)); // (the address is formed here: two scalar registers across the march, not three)
             bool look = inner; // check what this unit stores
+            // which skip counter of the workgroup's line, per lane (a scalar kept to the skip below is one the march lacks):
+            // u64 0 = a unit with interior positions all around it (the ones that could rest before edge positions had words),
+            // u64 2 = an interior unit next to an edge position
+            int which = (strip == 1 || strip + 1 >= strips - er || row_chunk == 1 || row_chunk + 1 >= chunks_a - a.bot_first) ? 2 : 0;
+            asm volatile("" : "+v"(which));
             if (inner && qa.mode >= 2) {
                 const int nb = lane < 9 ? lane : 4;
-                uint32_t word = kQuietRest;
-                if (lane < 9) word = qa.in[pos + (nb / 3 - 1) * strips + (nb % 3 - 1)];
-                else if (lane == 9 && qa.mode == 3) word = qa.out[pos];
+                word2 w2 = {kQuietRest, kQuietRest};
+                if (lane < 9) w2 = reinterpret_cast<const word2 *>(qa.in)[pos + (nb / 3 - 1) * strips + (nb % 3 - 1)];
+                else if (lane == 9 && qa.mode == 3) w2 = reinterpret_cast<const word2 *>(qa.out)[pos];
+                // a position is at rest when both parts are, and active when either is
+                const uint32_t word = (w2.x == kQuietRest && w2.y == kQuietRest) ? kQuietRest
+                                    : ((w2.x == kQuietActive || w2.y == kQuietActive) ? kQuietActive : 0u);
                 if (qa.mode == 3 && __builtin_amdgcn_ballot_w64(word != kQuietRest) == 0) {
                     if (lane == 0)
-                        (void)__hip_atomic_fetch_add(qa.skipped + ((int)blockIdx.x % kQuietCounters) * kQuietCounterStride, 1ull,
+                        (void)__hip_atomic_fetch_add(qa.skipped + ((int)blockIdx.x % kQuietCounters) * kQuietCounterStride + which, 1ull,
                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     return;
                 }
@@ -888,7 +967,7 @@ __device__ __forceinline__ void tb_unit(const GsStepArgs &a, const GsMapPlanes &
                 dirty = tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK, true>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
             else
                 tb_march<K, 0, FAST, CPL, -1, FAIR, MAP, MASK>(a, ur0, ur1, strip, lane, mp, fb GS_TRACE_ARG);
-            if (mine && lane == 0) *mine = dirty ? kQuietActive : kQuietRest;
+            if (mine && lane == 0) mine[0] = mine[1] = dirty ? kQuietActive : kQuietRest; // a whole unit: both parts
             return;
         }
     }

@@ -668,10 +668,11 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     bool split = 4 * chunks * strips <= 5 * slots && rpu >= 2;
     // Units at rest (GsQuiet, below): a pass that may skip is, on a grid mostly at rest, a launch of less than one round
     // whose length is the edge units' march -- they never rest -- so they come as halves there as in every such launch.
-    // (The words are per chunk and strip, and edge units have none: the halves change nothing for them.)
+    // (Every position has a word per half, and a whole unit writes both: the passes of a call agree on the layout whether
+    // their edge units come whole or as halves.)
     const bool quiet_ok = !GS_MATH_FUSED && quiet && quiet->mode >= 1 && quiet->mode <= 3 && at.kind == GS_ATTACH_NONE && per == 0 &&
                           fast == 15 && cpl == 2 && a.rb1 <= a.rb0 && !a.top_present && !a.bottom_present && rpu >= k && small >= k &&
-                          tiny >= k && chunks * strips <= 0x7fffffffL;
+                          tiny >= k && 2 * chunks * strips <= 0x7fffffffL;
     if (quiet_ok && quiet->mode == 3 && rpu >= 2) split = true;
     if (split_env >= 0) split = split_env != 0;
     long units = chunks * strips;
@@ -728,11 +729,15 @@ hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, co
     // strips left and right of it, the nine positions whose words it reads.  Same label: it is the same march.
     if (quiet_ok) {
         if (const void *qfn = gs_tb_quiet_kernel_strict(k)) {
-            quiet->need = chunks * strips;
-            if (quiet->need <= quiet->cap && quiet->in && quiet->out && quiet->skipped) {
+            quiet->need = 2 * chunks * strips; // a word per position and half
+            if (quiet->need <= quiet->cap && quiet->in && quiet->out && quiet->edge_skips && quiet->skipped) {
                 GsQuiet q = *quiet;
                 void *qargs[] = {&args, &q};
                 quiet->launched = units;
+                // ... of them units of edge positions: the outer strips of every chunk and every strip of the chunks that
+                // touch the grid's first or last rows (the top chunk and the last `bot`), halves counted one each
+                const long ends = bot + 1 < chunks ? bot + 1 : chunks, inner = strips <= ne ? 0 : (chunks - ends) * (strips - ne);
+                quiet->edge_launched = split ? units - inner : chunks * strips - inner;
                 return hipLaunchKernel(qfn, dim3((unsigned)blocks), dim3(256), qargs, 0, s);
             }
             if (quiet->mode == 1) return hipSuccess; // (the caller makes room and comes again)

@@ -213,6 +213,14 @@ class HipContext:
         capi.check(self._lib.gs_ctx_quiet_stats(self.handle, out))
         return int(out[0]), int(out[1]), int(out[2]), int(out[3])
 
+    def quiet_edge_stats(self) -> Tuple[int, int, int]:
+        """``gs_ctx_quiet_edge_stats``: the units of edge positions among the units launched by those passes (a half-height
+        unit counts as one), the ones among them that left without computing, and the interior units next to an edge
+        position that did -- ``quiet_stats()[1]`` counts the skipped units with interior positions all around them."""
+        out = (ctypes.c_uint64 * 3)()
+        capi.check(self._lib.gs_ctx_quiet_edge_stats(self.handle, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def set_pass_timing(self, passes: int) -> None:
         capi.check(self._lib.gs_ctx_set_pass_timing(self.handle, passes))
 

@@ -533,8 +533,19 @@ int32_t gs_ctx_set_pass_timing(gs_ctx *ctx, int32_t passes);
  * rule, strict math, finite parameters, no map, no mask, no graph; GS_HIP_QUIET_UNITS=0 when the context is created
  * switches it off).  The results are the same bits either way.  out[0] = units launched by the passes that took part,
  * out[1] = units among them that left without computing, out[2] = those passes, out[3] = the ones among them that could
- * skip (the third and later of their gs_run), all since the context was created.  Waits for enqueued work. */
+ * skip (the third and later of their gs_run), all since the context was created.  Waits for enqueued work.
+ * out[0] counts every unit.  out[1] counts what it always counted: the units with interior positions all around them -- no
+ * unit position of the nine is on an edge of the grid.  The others are counted by gs_ctx_quiet_edge_stats. */
 int32_t gs_ctx_quiet_stats(gs_ctx *ctx, uint64_t out[4]);
+/* ... and the units on the grid's edges among them: the first and last strips of columns and the row chunks that touch the
+ * grid's first or last rows, each half of such a position counting as a unit where the pass dispatched it as two halves.
+ * Under the clipped rule they rest like any other unit (a neighbour outside the grid does not exist: no tap reads it);
+ * under the zero-halo rule they never do (a halo of 0 next to U = 1 is a tap of -1), and neither do the interior units next
+ * to them.  out[0] = units of edge positions launched by the passes that took part (included in gs_ctx_quiet_stats'
+ * out[0]), out[1] = the ones among them that left without computing (by halves: a whole unit of an edge position that
+ * leaves -- GS_HIP_EDGE_SPLIT=0, a chunk of one row -- counts as its two), out[2] = the interior units next to an edge position
+ * that left without computing (neither is included in gs_ctx_quiet_stats' out[1]).  Waits for enqueued work. */
+int32_t gs_ctx_quiet_edge_stats(gs_ctx *ctx, uint64_t out[3]);
 
 /* Introspection for tests and the bench: name of the kernel variant last launched
  * ("tb-k4/strict@32x2" = 4 fused steps, strict math, tuned: 32-row units, 2 row bands; the periodic rule's kernels

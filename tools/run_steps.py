@@ -34,6 +34,7 @@ def main():
     ctx = sim.context
     l0 = ctx.stats()["launches"]
     q0 = ctx.quiet_stats()
+    e0 = ctx.quiet_edge_stats()
     ctx.timer_start()
     for _ in range(a.calls):
         sim.prepare_steps(sp, a.steps)
@@ -47,6 +48,8 @@ def main():
                       # units at rest: [units launched by eligible passes, units skipped, eligible passes, passes that could skip]
                       # of the timed calls
                       "quiet_stats": [x - y for x, y in zip(ctx.quiet_stats(), q0)],
+                      # ... [units of edge positions among those launched, the ones skipped, interior units next to an edge skipped]
+                      "quiet_edge_stats": [x - y for x, y in zip(ctx.quiet_edge_stats(), e0)],
                       # the layout that ran: chosen by gs_run's tuner, or pinned through GS_HIP_ROWS_PER_BLOCK / _FUSE_STEPS / _COLS_PER_LANE
                       "tuned": ctx.get_tuned(a.rows, a.cols) if ctx.get_tuned(a.rows, a.cols)[0] else
                       (ctx.args.rows_per_block, ctx.args.fuse_steps, ctx.args.cols_per_lane, ctx.args.share_taps),
