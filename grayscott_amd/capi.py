@@ -62,6 +62,7 @@ EXPORTS = (
     "gs_field_reduced_shape", "gs_field_download_reduced", "gs_field_download_reduced_async", "gs_field_colormap_reduced",
     "gs_fields_compare", "gs_members_compare", "gs_fields_copy", "gs_members_copy",
     "gs_members_set_active", "gs_members_get_active",
+    "gs_members_set_noise", "gs_members_get_noise", "gs_members_clear_noise",
     "gs_fields_morphology", "gs_members_morphology",
     "gs_region_grid", "gs_fields_region_summaries", "gs_fields_region_morphology", "gs_fields_region_correlation",
     "gs_fields_region_histogram", "gs_fields_region_components", "gs_fields_region_compare", "gs_fields_region_spectrum",
@@ -311,6 +312,9 @@ def load() -> ctypes.CDLL:
         "gs_members_copy": (i32, [vp, vp, vp, u64, u64]),
         "gs_members_set_active": (i32, [vp, vp, u64, u64, vp]),
         "gs_members_get_active": (i32, [vp, vp, u64, u64, vp, vp, P(u64)]),
+        "gs_members_set_noise": (i32, [vp, vp, u64, u64, vp, u64]),
+        "gs_members_get_noise": (i32, [vp, vp, u64, u64, vp, P(i32)]),
+        "gs_members_clear_noise": (i32, [vp, vp]),
         "gs_fields_morphology": (i32, [vp, P(vp), i32, P(f32), P(i32), i32, P(GsMorphology)]),
         "gs_members_morphology": (i32, [vp, vp, u64, u64, P(f32), P(i32), i32, P(GsMorphology)]),
         "gs_region_grid": (i32, [u64, u64, i32, i32, P(u64), P(u64)]),

@@ -376,5 +376,35 @@ __device__ __forceinline__ void react_noise(const GsNoiseArgs &n, uint32_t key, 
         }
     }
 }
+// ... for N cells of one column in N rows (a lane's cells in an LDS window, gs_lds_resident.h): cell e draws at (row[e], col).
+template <int N>
+__device__ __forceinline__ void react_noise(const GsNoiseArgs &n, uint32_t key, const uint32_t (&row)[N], uint32_t col, float (&nu)[N],
+                                            float (&nv)[N])
+{
+    const bool su = n.sigma_u != 0.0f, sv = n.sigma_v != 0.0f;
+    if (su || sv) {
+        uint32_t x0[N], x1[N];
+#pragma unroll
+        for (int e = 0; e < N; ++e) { x0[e] = col; x1[e] = row[e]; }
+        philox2x32<N>(x0, x1, key);
+        if (su) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) nu[e] = nu[e] + n.sigma_u * noise_xi(x0[e]);
+        }
+        if (sv) {
+#pragma unroll
+            for (int e = 0; e < N; ++e) nv[e] = nv[e] + n.sigma_v * noise_xi(x1[e]);
+        }
+    }
+}
+// The step key formed on the device (the ensemble kernels' noise forms, whose launches run many steps of many members):
+// include/gs_hip.h's key(s) for a member's seed -- ten rounds on wave-uniform words, scalar instructions, once per step.
+// gs_attached.cpp's noise_key is the definition; tests compare the two through the kernels' results.
+__device__ __forceinline__ uint32_t noise_key_uniform(uint32_t seed_lo, uint32_t seed_hi, uint64_t step)
+{
+    uint32_t c0[1] = {(uint32_t)step}, c1[1] = {(uint32_t)(step >> 32)};
+    philox2x32<1>(c0, c1, seed_lo);
+    return __builtin_amdgcn_readfirstlane(c0[0] ^ seed_hi);
+}
 
 } // namespace

@@ -6,6 +6,9 @@
 // kernels and a device list of their indices.  `cur` flips for the whole ensemble, so an inactive member must read the same
 // through either slot: before its first launch a run copies every inactive member whose newest slot has changed since the
 // last run (retired, or written while inactive) into the other slot, in one launch of gs_members_mirror_k.
+// Noise (gs_members_set_noise): a second device table, one GsEnsNoise per member, and the noise forms of the two kernels
+// (gs_ens_resident_z*, gs_ens_tile_z*), which take the table, the nullable list of active members and the ensemble's
+// run_steps; a member's step index is run_steps plus its offset in the table (gs_internal.h: gs_ensemble::noise).
 #include "gs_internal.h"
 
 using namespace gsi;
@@ -50,8 +53,17 @@ void free_planes(gs_ensemble *e)
     if (e->params) (void)hipFree(e->params);
     if (e->active_list) (void)hipFree(e->active_list);
     if (e->mirror_list) (void)hipFree(e->mirror_list);
+    if (e->noise_table) (void)hipFree(e->noise_table);
     e->params = nullptr;
     e->active_list = e->mirror_list = nullptr;
+    e->noise_table = nullptr;
+}
+
+uint64_t noise_offset(const GsEnsNoise &n) { return (uint64_t)n.offset_hi << 32 | n.offset_lo; }
+void set_noise_offset(GsEnsNoise &n, uint64_t offset)
+{
+    n.offset_lo = (uint32_t)offset;
+    n.offset_hi = (uint32_t)(offset >> 32);
 }
 
 // What a run does first when members are inactive: slot cur of every stale member into slot cur ^ 1, in one launch behind
@@ -250,6 +262,9 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
     if (running == 0) return GS_OK; // nobody advances: no launch, no flip
     if (listed) GS_TRY(mirror_stale(e, sl));
     const uint32_t *list = e->active_list;
+    // With noise attached: the noise forms, one per kernel whether or not a list is in use (GsEnsNoiseArgs::list).
+    const bool noisy = !e->noise.empty();
+    GsEnsNoiseArgs z{e->noise_table, listed ? list : nullptr, 0};
     // The launchers split at kGsEnsMaxGroups workgroups; a `members` above 2^31 goes in slices here.
     auto for_slices = [&](auto &&launch) -> int32_t {
         for (uint64_t m0 = 0; m0 < running; m0 += 0x40000000ull) {
@@ -276,7 +291,11 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
             a.in_v = e->v[e->cur];
             a.out_u = e->u[e->cur ^ 1];
             a.out_v = e->v[e->cur ^ 1];
+            z.step0 = e->run_steps;
             GS_TRY(for_slices([&](const GsEnsArgs &s) {
+                if (noisy)
+                    return fused ? gs_launch_ens_resident_noise_fused(s, z, n, e->fast, sl.compute, &name)
+                                 : gs_launch_ens_resident_noise_strict(s, z, n, e->fast, sl.compute, &name);
                 if (listed)
                     return fused ? gs_launch_ens_resident_listed_fused(s, list, n, e->fast, sl.compute, &name)
                                  : gs_launch_ens_resident_listed_strict(s, list, n, e->fast, sl.compute, &name);
@@ -303,7 +322,11 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
         a.in_v = e->v[e->cur];
         a.out_u = e->u[e->cur ^ 1];
         a.out_v = e->v[e->cur ^ 1];
+        z.step0 = e->run_steps;
         GS_TRY(for_slices([&](const GsEnsArgs &s) {
+            if (noisy)
+                return fused ? gs_launch_ens_tile_noise_fused(s, z, n, shape, e->fast, sl.compute, &name)
+                             : gs_launch_ens_tile_noise_strict(s, z, n, shape, e->fast, sl.compute, &name);
             if (listed)
                 return fused ? gs_launch_ens_tile_listed_fused(s, list, n, shape, e->fast, sl.compute, &name)
                              : gs_launch_ens_tile_listed_strict(s, list, n, shape, e->fast, sl.compute, &name);
@@ -352,6 +375,7 @@ int32_t gs_members_set_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
             return fail(err == hipErrorOutOfMemory ? GS_ERR_NOMEM : GS_ERR_HIP, "active list allocation failed: %s", hipGetErrorString(err));
         }
     }
+    bool noise_moved = false;
     for (uint64_t i = 0; i < count; ++i) {
         const uint64_t m = first + i;
         const uint8_t want = active[i] ? 1 : 0;
@@ -360,6 +384,10 @@ int32_t gs_members_set_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
         if (want) { // reactivated: its newest slot is valid as it is; the steps it sat out are settled
             e->active_count++;
             e->missed[m] += e->run_steps - e->retired_at[m];
+            if (!e->noise.empty()) { // ... and its noise goes on from the step it stopped at
+                set_noise_offset(e->noise[m], noise_offset(e->noise[m]) - (e->run_steps - e->retired_at[m]));
+                noise_moved = true;
+            }
             e->stale_count -= e->stale[m];
             e->stale[m] = 0;
         } else { // retired: the other slot holds an older state (or none) until the next run mirrors it
@@ -372,6 +400,7 @@ int32_t gs_members_set_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
     for (uint64_t i = 0; i < e->members; ++i)
         if (e->active[i]) list.push_back((uint32_t)i);
     if (!list.empty()) GS_HIP(hipMemcpy(e->active_list, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    if (noise_moved) GS_HIP(hipMemcpy(e->noise_table, e->noise.data(), e->noise.size() * sizeof(GsEnsNoise), hipMemcpyHostToDevice));
     return GS_OK;
 }
 
@@ -390,6 +419,81 @@ int32_t gs_members_get_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint6
             steps_taken[i] = untouched ? e->run_steps : e->run_steps - e->missed[m] - (on ? 0 : e->run_steps - e->retired_at[m]);
     }
     if (active_total) *active_total = untouched ? e->members : e->active_count;
+    return GS_OK;
+}
+
+int32_t gs_members_set_noise(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const gs_noise *noise, uint64_t entries)
+{
+    GS_TRY(check_ensemble(ctx, e));
+    if (!noise) return fail(GS_ERR_INVALID, "null noise");
+    GS_TRY(check_member_range(e, first, count));
+    if (entries != 1 && entries != count)
+        return fail(GS_ERR_INVALID, "%llu noise structs for %llu members (1 or one per member)", (unsigned long long)entries,
+                    (unsigned long long)count);
+    for (uint64_t i = 0; i < entries; ++i)
+        if (!(std::isfinite(noise[i].sigma_u) && std::isfinite(noise[i].sigma_v) && noise[i].sigma_u >= 0.0f && noise[i].sigma_v >= 0.0f))
+            return fail(GS_ERR_INVALID, "the noise's sigmas must be finite and >= 0 (entry %llu: %g, %g)", (unsigned long long)i,
+                        (double)noise[i].sigma_u, (double)noise[i].sigma_v);
+    if (e->members > 0x80000000ull)
+        return fail(GS_ERR_UNSUPPORTED, "noise on more than 2^31 members (the noise kernels take the list of active members, 32-bit indices)");
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    GS_HIP(hipStreamSynchronize(sl.compute)); // launches in flight read the table
+    if (!e->noise_table) {
+        const hipError_t err = hipMalloc(reinterpret_cast<void **>(&e->noise_table), (size_t)e->members * sizeof(GsEnsNoise));
+        if (err != hipSuccess) {
+            e->noise_table = nullptr;
+            return fail(err == hipErrorOutOfMemory ? GS_ERR_NOMEM : GS_ERR_HIP, "noise table allocation failed: %s", hipGetErrorString(err));
+        }
+    }
+    if (e->noise.empty()) { // the first call attaches: members never named hold sigmas 0, seed 0 and step 0 from here on
+        try {
+            e->noise.assign((size_t)e->members, GsEnsNoise{});
+        } catch (const std::bad_alloc &) {
+            return fail(GS_ERR_NOMEM, "out of host memory");
+        }
+        for (uint64_t m = 0; m < e->members; ++m) set_noise_offset(e->noise[m], 0 - e->noise_clock(m));
+    }
+    for (uint64_t i = 0; i < count; ++i) {
+        const gs_noise &n = noise[entries == 1 ? 0 : i];
+        GsEnsNoise &q = e->noise[first + i];
+        q.sigma_u = n.sigma_u;
+        q.sigma_v = n.sigma_v;
+        q.seed_lo = (uint32_t)n.seed;
+        q.seed_hi = (uint32_t)(n.seed >> 32);
+        set_noise_offset(q, n.step - e->noise_clock(first + i));
+    }
+    GS_HIP(hipMemcpy(e->noise_table, e->noise.data(), e->noise.size() * sizeof(GsEnsNoise), hipMemcpyHostToDevice));
+    return GS_OK;
+}
+
+int32_t gs_members_get_noise(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, gs_noise *out, int32_t *attached)
+{
+    GS_TRY(check_ensemble(ctx, e));
+    if (!out && !attached) return fail(GS_ERR_INVALID, "null outputs");
+    GS_TRY(check_member_range(e, first, count));
+    if (attached) *attached = e->noise.empty() ? 0 : 1;
+    if (e->noise.empty() || !out) return GS_OK;
+    for (uint64_t i = 0; i < count; ++i) {
+        const GsEnsNoise &q = e->noise[first + i];
+        out[i].sigma_u = q.sigma_u;
+        out[i].sigma_v = q.sigma_v;
+        out[i].seed = (uint64_t)q.seed_hi << 32 | q.seed_lo;
+        out[i].step = e->noise_clock(first + i) + noise_offset(q);
+    }
+    return GS_OK;
+}
+
+int32_t gs_members_clear_noise(gs_ctx *ctx, gs_ensemble *e)
+{
+    GS_TRY(check_ensemble(ctx, e));
+    if (e->noise.empty()) return GS_OK;
+    SlabRt &sl = ctx->slabs[0];
+    GS_HIP(hipSetDevice(sl.device));
+    GS_HIP(hipStreamSynchronize(sl.compute)); // launches in flight read the table
+    (void)hipFree(e->noise_table);
+    e->noise_table = nullptr;
+    std::vector<GsEnsNoise>().swap(e->noise);
     return GS_OK;
 }
 

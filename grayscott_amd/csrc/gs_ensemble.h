@@ -16,6 +16,14 @@
 // active set (gs_members_set_active).  The grid covers the ACTIVE members only, and a workgroup takes its member from a
 // device list of their indices (u32, ascending; the kernels' second argument) with one scalar load, where its twin
 // computes it from the workgroup index: the member stays wave-uniform.  GsEnsArgs::first is then a position in the list.
+// Noise forms (gs_ens_resident_zk / _zpk / _znk, gs_ens_tile_zk / _zpk / _znk; gs_members_set_noise): the same bodies with
+// react_noise (gs_cell.h) on the outputs of every cell a step computes inside the member -- the apron cells of a window at
+// every level included -- before the value is published to LDS or stored.  A cell draws at its member-local (row, column),
+// under the periodic rule at the wrapped one, with the key of the member's own step: the member's seed, sigmas and step
+// offset come from a second device table (GsEnsNoise, one s_load_dwordx8), the key is formed on the device once per step
+// from wave-uniform words (noise_key_uniform).  The second argument, GsEnsNoiseArgs, carries a nullable list of active
+// members: one form serves ensembles with and without an active set.  Built in the noise translation units (GS_NOISE_ONLY)
+// only: the other objects hold none of them.
 // Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED and the GS_SUFFIX / GS_TAP
 // macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
 #pragma once
@@ -50,20 +58,55 @@ __device__ __forceinline__ GsStepArgs ens_member_args(const GsEnsArgs &e, int64_
     return a;
 }
 
+typedef __attribute__((address_space(4))) const GsEnsNoise GsEnsNoiseConst;
+// The noise of member `member` at the first step of a launch (scalar loads: member is wave-uniform).
+__device__ __forceinline__ MemberNoise ens_member_noise(const GsEnsNoiseArgs &z, int64_t member)
+{
+    GsEnsNoiseConst *q = (GsEnsNoiseConst *)z.table + member;
+    MemberNoise mn;
+    mn.sigma_u = q->sigma_u;
+    mn.sigma_v = q->sigma_v;
+    mn.seed_lo = q->seed_lo;
+    mn.seed_hi = q->seed_hi;
+    mn.step = z.step0 + ((uint64_t)q->offset_hi << 32 | q->offset_lo);
+    return mn;
+}
+
 // Resident form.  The LDS layout and the step loop are gs_run_resident_k's: 4 planes of (rows + 2) x (cols + 2) floats
 // with a ring of zeros, thread t owning cells t, t + blockDim.x, ... (CPT of them at most).  The host sizes the
 // workgroup to the waves the member's cells need (an 8 x 16 member: 2 waves), so small members share a CU.
 // (The body is a macro so that the kernel of the clipped and zero-halo rules keeps its code: as a function called from two
-// kernels it compiled one instruction apart.)  MEMBER: the workgroup's member, GS_ENS_MEMBER_OF_GROUP or GS_ENS_MEMBER_LISTED.
+// kernels it compiled one instruction apart.)  MEMBER: the workgroup's member, GS_ENS_MEMBER_OF_GROUP or GS_ENS_MEMBER_LISTED,
+// or GS_ENS_MEMBER_NOISE in the noise forms (NZ = 1), whose hooks GS_ENS_NZ_*_1 stand where the others' expand to nothing.
 typedef __attribute__((address_space(4))) const uint32_t GsEnsListConst;
 // The member of workgroup (or window group) G of a launch: counted from GsEnsArgs::first, or entry first + G of the list of
 // active members (one s_load_dword: G is wave-uniform).
 #define GS_ENS_MEMBER_OF_GROUP(G) (e.first + (int64_t)(G))
 #define GS_ENS_MEMBER_LISTED(G) ((int64_t)((GsEnsListConst *)list)[e.first + (int64_t)(G)])
-#define GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, MEMBER)                                                                          \
+#define GS_ENS_MEMBER_NOISE(G) (z.list ? (int64_t)((GsEnsListConst *)z.list)[e.first + (int64_t)(G)] : e.first + (int64_t)(G))
+// the member's noise, once per workgroup
+#define GS_ENS_NZ_MEMBER_0(M)
+#define GS_ENS_NZ_MEMBER_1(M) const MemberNoise mn = ens_member_noise(z, M);
+// the key of step s, once per step
+#define GS_ENS_NZ_STEP_0
+#define GS_ENS_NZ_STEP_1 const uint32_t zkey = member_key(mn, s);
+// a cell's draw at its member coordinates (rc[k], unpacked inside the step loop: see the ring's remark below)
+#define GS_ENS_NZ_CELL_0(k)
+#define GS_ENS_NZ_CELL_1(k)                                                                                                  \
+    {                                                                                                                        \
+        int x = rc[k];                                                                                                       \
+        asm volatile("" : "+v"(x));                                                                                          \
+        const uint32_t zr[1] = {(uint32_t)(x >> 16)};                                                                        \
+        float zu[1] = {nu}, zv[1] = {nv};                                                                                    \
+        member_noise<1>(mn, zkey, zr, (uint32_t)(x & 0xffff), zu, zv);                                                          \
+        nu = zu[0];                                                                                                          \
+        nv = zv[0];                                                                                                          \
+    }
+#define GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, MEMBER, NZ)                                                                        \
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); /* half_diff: MODE.IEEE = 0 */             \
     extern __shared__ float lds[];                                                                                           \
     const GsStepArgs a = ens_member_args(e, MEMBER);                                                                         \
+    GS_ENS_NZ_MEMBER_##NZ(MEMBER)                                                                                            \
     const int cells = a.rows * a.cols, cols = a.cols, P = cols + 2, plane = (a.rows + 2) * P;                                \
     const int nthreads = (int)blockDim.x;                                                                                    \
     for (int i = threadIdx.x; i < 4 * plane; i += nthreads) lds[i] = 0.0f; /* the rings (and everything else) */             \
@@ -78,7 +121,7 @@ _Pragma("unroll")                                                               
         const int r = live[k] ? idx / cols : 0, c = live[k] ? idx - r * cols : 0;                                            \
         o[k] = (r + 1) * P + c + 1;                                                                                          \
         if (ZH == 0) border_weights(a, r, c, E[k]);                                                                          \
-        if constexpr (ZH >= 2) rc[k] = r << 16 | c;                                                                          \
+        if constexpr (ZH >= 2 || NZ) rc[k] = r << 16 | c;                                                                    \
         if (live[k]) {                                                                                                       \
             lds[o[k]] = a.in_u[idx];                                                                                         \
             lds[2 * plane + o[k]] = a.in_v[idx];                                                                             \
@@ -98,6 +141,7 @@ _Pragma("unroll")                                                               
     for (int s = 0; s < steps; ++s) {                                                                                        \
         const float *su = lds + cur * plane, *sv = lds + (2 + cur) * plane;                                                  \
         float *du = lds + (cur ^ 1) * plane, *dv = lds + (2 + (cur ^ 1)) * plane;                                            \
+        GS_ENS_NZ_STEP_##NZ                                                                                                  \
 _Pragma("unroll")                                                                                                            \
         for (int k = 0; k < CPT; ++k) {                                                                                      \
             if (!live[k]) continue;                                                                                          \
@@ -113,6 +157,7 @@ _Pragma("unroll")                                                               
                 cell_border<FAST>(a, E[k], R[0], R[1], R[2], nu, nv);                                                        \
             else                                                                                                             \
                 cell<false, FAST, Row3>(a, R[0], R[1], R[2], 1, true, true, 0u, 0u, nu, nv);                                 \
+            GS_ENS_NZ_CELL_##NZ(k)                                                                                           \
             du[o[k]] = nu;                                                                                                   \
             dv[o[k]] = nv;                                                                                                   \
             if constexpr (ZH >= 2) {                                                                                         \
@@ -147,46 +192,76 @@ _Pragma("unroll")                                                               
 template <int CPT, int FAST, int ZH>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_k)(GsEnsArgs e, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, GS_ENS_MEMBER_OF_GROUP(blockIdx.x))
+    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, GS_ENS_MEMBER_OF_GROUP(blockIdx.x), 0)
 }
 // The periodic rule's instances (GsEnsArgs::zero_halo = 2), kernels of their own name.
 template <int CPT, int FAST>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_pk)(GsEnsArgs e, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, 2, GS_ENS_MEMBER_OF_GROUP(blockIdx.x))
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 2, GS_ENS_MEMBER_OF_GROUP(blockIdx.x), 0)
 }
 // The zero-flux rule's instances (GsEnsArgs::zero_halo = 3), kernels of their own name.
 template <int CPT, int FAST>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_nk)(GsEnsArgs e, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, 3, GS_ENS_MEMBER_OF_GROUP(blockIdx.x))
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 3, GS_ENS_MEMBER_OF_GROUP(blockIdx.x), 0)
 }
 // The listed forms: the member from the list of active members (the second argument).
 template <int CPT, int FAST, int ZH>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_lk)(GsEnsArgs e, const uint32_t *list, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, GS_ENS_MEMBER_LISTED(blockIdx.x))
+    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, GS_ENS_MEMBER_LISTED(blockIdx.x), 0)
 }
 template <int CPT, int FAST>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_lpk)(GsEnsArgs e, const uint32_t *list, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, 2, GS_ENS_MEMBER_LISTED(blockIdx.x))
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 2, GS_ENS_MEMBER_LISTED(blockIdx.x), 0)
 }
 template <int CPT, int FAST>
 __global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_lnk)(GsEnsArgs e, const uint32_t *list, int steps, int to_out)
 {
-    GS_ENS_RESIDENT_BODY(CPT, FAST, 3, GS_ENS_MEMBER_LISTED(blockIdx.x))
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 3, GS_ENS_MEMBER_LISTED(blockIdx.x), 0)
+}
+// The noise forms: the member's noise from the table of the second argument, the member from its nullable list.
+template <int CPT, int FAST, int ZH>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_zk)(GsEnsArgs e, GsEnsNoiseArgs z, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, ZH, GS_ENS_MEMBER_NOISE(blockIdx.x), 1)
+}
+template <int CPT, int FAST>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_zpk)(GsEnsArgs e, GsEnsNoiseArgs z, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 2, GS_ENS_MEMBER_NOISE(blockIdx.x), 1)
+}
+template <int CPT, int FAST>
+__global__ __launch_bounds__(1024) void GS_SUFFIX(gs_ens_resident_znk)(GsEnsArgs e, GsEnsNoiseArgs z, int steps, int to_out)
+{
+    GS_ENS_RESIDENT_BODY(CPT, FAST, 3, GS_ENS_MEMBER_NOISE(blockIdx.x), 1)
 }
 #undef GS_ENS_RESIDENT_BODY
+#undef GS_ENS_NZ_MEMBER_0
+#undef GS_ENS_NZ_MEMBER_1
+#undef GS_ENS_NZ_STEP_0
+#undef GS_ENS_NZ_STEP_1
+#undef GS_ENS_NZ_CELL_0
+#undef GS_ENS_NZ_CELL_1
 
 // Windowed form: gs_run_tile_k's load, K steps (tile_steps) and store, for window `blockIdx.x % windows` of member
 // `first + blockIdx.x / windows`.
 // (The body is a macro, like the resident form's, so that gs_ens_tile_k keeps its code beside its listed twin.)
-#define GS_ENS_TILE_BODY(RPW, FAST, MEMBER)                                                                                  \
+// (NZ = 1, the noise form: the member's noise, and tile_steps' NOISE = 1 with it as its last argument)
+#define GS_ENS_TILE_NZ_MEMBER_0(M)
+#define GS_ENS_TILE_NZ_MEMBER_1(M) const MemberNoise mn = ens_member_noise(z, M);
+#define GS_ENS_TILE_NZ_T_0
+#define GS_ENS_TILE_NZ_T_1 , 1
+#define GS_ENS_TILE_NZ_A_0
+#define GS_ENS_TILE_NZ_A_1 , mn
+#define GS_ENS_TILE_BODY(RPW, FAST, MEMBER, NZ)                                                                               \
     if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); /* half_diff: MODE.IEEE = 0 */             \
     extern __shared__ float lds[];                                                                                           \
     const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;                                \
     const GsStepArgs a = ens_member_args(e, MEMBER(m));                                                                      \
+    GS_ENS_TILE_NZ_MEMBER_##NZ(MEMBER(m))                                                                                    \
     constexpr int H = tile_rows(RPW);                                                                                        \
     const int lane = threadIdx.x & 63;                                                                                       \
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);                                                       \
@@ -208,11 +283,11 @@ _Pragma("unroll")                                                               
     const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;                                \
     /* (a.zero_halo is 0 or 1 here: the periodic rule runs gs_ens_tile_pk) */                                                \
     if (!edge)                                                                                                               \
-        tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);                                               \
+        tile_steps<RPW, false, FAST, -1 GS_ENS_TILE_NZ_T_##NZ>(a, lds, K, gr, gc, wave, lane, u, v GS_ENS_TILE_NZ_A_##NZ);   \
     else if (a.zero_halo)                                                                                                    \
-        tile_steps<RPW, true, FAST, 1>(a, lds, K, gr, gc, wave, lane, u, v);                                                 \
+        tile_steps<RPW, true, FAST, 1 GS_ENS_TILE_NZ_T_##NZ>(a, lds, K, gr, gc, wave, lane, u, v GS_ENS_TILE_NZ_A_##NZ);     \
     else                                                                                                                     \
-        tile_steps<RPW, true, FAST, 0>(a, lds, K, gr, gc, wave, lane, u, v);                                                 \
+        tile_steps<RPW, true, FAST, 0 GS_ENS_TILE_NZ_T_##NZ>(a, lds, K, gr, gc, wave, lane, u, v GS_ENS_TILE_NZ_A_##NZ);     \
     /* store the window shrunk by K, where it lies in the member */                                                          \
     if (lane >= K && lane < kTileCols - K && gc < a.cols) {                                                                  \
 _Pragma("unroll")                                                                                                            \
@@ -228,14 +303,25 @@ _Pragma("unroll")                                                               
 template <int RPW, int FAST>
 __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_k)(GsEnsArgs e, int K, int windows)
 {
-    GS_ENS_TILE_BODY(RPW, FAST, GS_ENS_MEMBER_OF_GROUP)
+    GS_ENS_TILE_BODY(RPW, FAST, GS_ENS_MEMBER_OF_GROUP, 0)
 }
 template <int RPW, int FAST>
 __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_lk)(GsEnsArgs e, const uint32_t *list, int K, int windows)
 {
-    GS_ENS_TILE_BODY(RPW, FAST, GS_ENS_MEMBER_LISTED)
+    GS_ENS_TILE_BODY(RPW, FAST, GS_ENS_MEMBER_LISTED, 0)
+}
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_zk)(GsEnsArgs e, GsEnsNoiseArgs z, int K, int windows)
+{
+    GS_ENS_TILE_BODY(RPW, FAST, GS_ENS_MEMBER_NOISE, 1)
 }
 #undef GS_ENS_TILE_BODY
+#undef GS_ENS_TILE_NZ_MEMBER_0
+#undef GS_ENS_TILE_NZ_MEMBER_1
+#undef GS_ENS_TILE_NZ_T_0
+#undef GS_ENS_TILE_NZ_T_1
+#undef GS_ENS_TILE_NZ_A_0
+#undef GS_ENS_TILE_NZ_A_1
 
 // The periodic rule's windowed form (GsEnsArgs::zero_halo = 2): tile_window_periodic for window `blockIdx.x % windows`
 // of member `first + blockIdx.x / windows`; a window wraps around its own member only.
@@ -276,7 +362,27 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_lnk)(Gs
     const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
     tile_window_neumann<RPW, FAST>(ens_member_args(e, GS_ENS_MEMBER_LISTED(m)), lds, K, win);
 }
+// The noise forms of the two: the windows' cells draw at wrapped coordinates under the periodic rule.
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_zpk)(GsEnsArgs e, GsEnsNoiseArgs z, int K, int windows)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
+    const int64_t member = GS_ENS_MEMBER_NOISE(m);
+    tile_window_periodic<RPW, FAST, true>(ens_member_args(e, member), lds, K, win, ens_member_noise(z, member));
+}
+template <int RPW, int FAST>
+__global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_ens_tile_znk)(GsEnsArgs e, GsEnsNoiseArgs z, int K, int windows)
+{
+    if ((FAST & 1) && !GS_MATH_FUSED) __builtin_amdgcn_s_setreg(1 | (9 << 6), 0); // half_diff: MODE.IEEE = 0
+    extern __shared__ float lds[];
+    const int m = (int)(blockIdx.x / (unsigned)windows), win = (int)blockIdx.x - m * windows;
+    const int64_t member = GS_ENS_MEMBER_NOISE(m);
+    tile_window_neumann<RPW, FAST, true>(ens_member_args(e, member), lds, K, win, ens_member_noise(z, member));
+}
 #undef GS_ENS_MEMBER_OF_GROUP
 #undef GS_ENS_MEMBER_LISTED
+#undef GS_ENS_MEMBER_NOISE
 
 } // namespace

@@ -292,6 +292,13 @@ struct gs_ensemble {
     uint32_t *active_list = nullptr;  // device: indices of the active members, ascending (active_count entries)
     uint32_t *mirror_list = nullptr;  // device: room for `members` indices of members to mirror
     bool all_active() const { return active.empty() || active_count == members; }
+    // Noise (gs_members_set_noise).  `noise` stays empty until the first call: gs_ensemble_run then launches the kernels of
+    // an ensemble without noise.  A member's step index is clock(m) + offset, with clock(m) = run_steps while it is active
+    // and retired_at[m] while it is not (u64, wrapping): the kernels add the launch's run_steps to the offset, so a member
+    // that comes back gets the steps it sat out taken off its offset, and nothing is uploaded per launch.
+    std::vector<GsEnsNoise> noise;    // per member, the device table's layout (sigmas, seed, offset)
+    GsEnsNoise *noise_table = nullptr; // device: members entries
+    uint64_t noise_clock(uint64_t m) const { return active.empty() || active[m] ? run_steps : retired_at[m]; }
 };
 
 struct gs_field {

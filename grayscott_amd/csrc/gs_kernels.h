@@ -212,6 +212,24 @@ struct GsEnsArgs {
     int32_t rows, cols;
     int32_t zero_halo;         // gs_boundary: 0 clipped, 1 zero halo, 2 periodic, 3 zero flux
 };
+// Noise of an ensemble (gs_members_set_noise; include/gs_hip.h): one entry per member in a device table beside GsEnsParams,
+// read with scalar loads.  The member's step index at a launch is GsEnsNoiseArgs::step0 + step_offset (u64, wrapping):
+// step0 is the ensemble's run_steps when the launch is enqueued, so nothing is uploaded per launch; the host adjusts the
+// offsets when a member's noise is set and when a retired member comes back (the steps it sat out).
+struct GsEnsNoise {
+    float sigma_u, sigma_v;
+    uint32_t seed_lo, seed_hi;
+    uint32_t offset_lo, offset_hi;
+    uint32_t pad[2]; // 32 B per member: one s_load_dwordx8
+};
+// The second argument of the ensemble kernels' noise forms (gs_ens_resident_z*, gs_ens_tile_z*).  list: the device list of
+// the active members' indices, as the listed forms take it, or nullptr when every member runs (GsEnsArgs::first then counts
+// members, else positions in the list): one wave-uniform branch, no listed twins.
+struct GsEnsNoiseArgs {
+    const GsEnsNoise *table; // members entries (device)
+    const uint32_t *list;
+    uint64_t step0;
+};
 
 // Launchers, one set per arithmetic flavour (see gs_math in include/gs_hip.h).  Each
 // returns the hipError_t of the launch.  `name` receives a static kernel-variant label.  `at` (simple, stream and
@@ -232,7 +250,9 @@ struct GsEnsArgs {
     hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
     hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name); \
     hipError_t gs_launch_ens_resident_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name); \
-    hipError_t gs_launch_ens_tile_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name);
+    hipError_t gs_launch_ens_tile_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name); \
+    hipError_t gs_launch_ens_resident_noise_##SUFFIX(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int steps, int fast, hipStream_t s, const char **name); \
+    hipError_t gs_launch_ens_tile_noise_##SUFFIX(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int k, int shape, int fast, hipStream_t s, const char **name);
 
 GS_DECLARE_LAUNCHERS(strict)
 GS_DECLARE_LAUNCHERS(fused)

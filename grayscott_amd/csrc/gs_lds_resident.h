@@ -242,6 +242,29 @@ __host__ __device__ constexpr int tile_rows(int rpw) { return kTileWaves * rpw; 
 // 2 buffers x 2 species x (rows + the rows above and below the window) x pitch
 __host__ __device__ constexpr size_t tile_lds_bytes(int rpw) { return (size_t)4 * (tile_rows(rpw) + 2) * kTilePitch * sizeof(float); }
 
+// A member's noise as the noise forms of the ensemble kernels carry it (gs_ensemble.h: ens_member_noise), wave-uniform words
+// from scalar loads: the sigmas, the seed and the member's step index at the launch's first step.
+struct MemberNoise {
+    float sigma_u, sigma_v;
+    uint32_t seed_lo, seed_hi;
+    uint64_t step;
+};
+// The key of the member's step `mn.step + s`: formed once per step, and only for a member that draws (a scalar branch).
+__device__ __forceinline__ uint32_t member_key(const MemberNoise &mn, int s)
+{
+    return mn.sigma_u != 0.0f || mn.sigma_v != 0.0f ? noise_key_uniform(mn.seed_lo, mn.seed_hi, mn.step + (uint64_t)s) : 0u;
+}
+// react_noise for a lane's N cells (row[e], col) with that key.
+template <int N>
+__device__ __forceinline__ void member_noise(const MemberNoise &mn, uint32_t key, const uint32_t (&row)[N], uint32_t col,
+                                             float (&nu)[N], float (&nv)[N])
+{
+    GsNoiseArgs nz{};
+    nz.sigma_u = mn.sigma_u;
+    nz.sigma_v = mn.sigma_v;
+    react_noise<N>(nz, key, row, col, nu, nv);
+}
+
 // K steps of a window.  EDGE: the window touches the grid's border.  Its cells outside the grid are zeros
 // and stay zeros; with the zero-halo rule (ZH = 1) that IS the rule and every cell runs the interior code;
 // with the clipped rule (ZH = 0) every cell runs cell_border with its own weights.  (The general flavour of
@@ -250,9 +273,13 @@ __host__ __device__ constexpr size_t tile_lds_bytes(int rpw) { return (size_t)4 
 // rule (ZH = 3) a cell in the grid's first / last column reads its own column in place of the missing one (a per-lane
 // LDS offset) and a cell in its first / last row its own row in place of the missing one (wave-uniform), at every step:
 // the cells outside the grid are never read by a cell inside it.
-template <int RPW, bool EDGE, int FAST, int ZH>
+// NOISE (the ensemble kernels' noise forms, gs_ens_tile_z*): 1 = react_noise on every cell a level computes, apron cells
+// included, at its member coordinates (gr + i, gc) with the key of that level's step, before the value is published -- a
+// cell outside the member draws too and is zeroed like its reference value; 2 = the periodic rule's windows, whose cells
+// draw at their coordinates modulo the member's, so that the copies a window holds of a small member stay equal.
+template <int RPW, bool EDGE, int FAST, int ZH, int NOISE = 0>
 __device__ __forceinline__ void tile_steps(const GsStepArgs &a, float *lds, int K, int gr, int gc, int wave, int lane,
-                                           float (&u)[RPW], float (&v)[RPW])
+                                           float (&u)[RPW], float (&v)[RPW], const MemberNoise &mn = MemberNoise{})
 {
     constexpr int H = tile_rows(RPW), P = kTilePitch, plane = (H + 2) * P; // plane: one species of one buffer
     // element (buffer b, species s, window row r, window column c) = (2 b + s) * plane + (r + 1) * P + c + 1;
@@ -286,6 +313,18 @@ __device__ __forceinline__ void tile_steps(const GsStepArgs &a, float *lds, int 
 #pragma unroll
     for (int i = 0; i < RPW; ++i) { lds[o + i * P] = u[i]; lds[plane + o + i * P] = v[i]; }
     __syncthreads();
+    [[maybe_unused]] uint32_t zrow[RPW], zcol = 0; // NOISE: where this lane's cells draw (rows are wave-uniform)
+    if constexpr (NOISE != 0) {
+        int c = gc;
+        if constexpr (NOISE == 2) { c %= a.cols; if (c < 0) c += a.cols; }
+        zcol = (uint32_t)c;
+#pragma unroll
+        for (int i = 0; i < RPW; ++i) {
+            int r = gr + i;
+            if constexpr (NOISE == 2) { r %= a.rows; if (r < 0) r += a.rows; }
+            zrow[i] = (uint32_t)r;
+        }
+    }
     int cur = 0;
     for (int s = 1; s <= K; ++s) {
         const float *su = lds + cur * 2 * plane + o, *sv = su + plane;
@@ -314,6 +353,7 @@ __device__ __forceinline__ void tile_steps(const GsStepArgs &a, float *lds, int 
             else
                 cell<false, FAST, Row3>(a, R[i], R[i + 1], R[i + 2], 1, true, true, 0u, 0u, nu[i], nv[i]);
         }
+        if constexpr (NOISE != 0) member_noise<RPW>(mn, member_key(mn, s - 1), zrow, zcol, nu, nv);
 #pragma unroll
         for (int i = 0; i < RPW; ++i) { u[i] = inside[i] ? nu[i] : 0.0f; v[i] = inside[i] ? nv[i] : 0.0f; }
         if (s < K) { // publish for the next step (the other buffer: no wave can still be reading it)
@@ -376,8 +416,8 @@ __global__ __launch_bounds__(kTileWaves * 64) void GS_SUFFIX(gs_run_tile_k)(GsSt
 // The periodic rule's form (GsStepArgs::zero_halo = 2) of window `win`: every cell of the window is loaded from its
 // coordinates modulo the grid's -- a window that crosses an edge holds a piece of the periodic extension of the grid, on
 // small grids the grid several times over -- and every cell runs the interior code (tile_steps<EDGE = false>).
-template <int RPW, int FAST>
-__device__ __forceinline__ void tile_window_periodic(const GsStepArgs &a, float *lds, int K, int win)
+template <int RPW, int FAST, bool NOISE = false>
+__device__ __forceinline__ void tile_window_periodic(const GsStepArgs &a, float *lds, int K, int win, const MemberNoise &mn = MemberNoise{})
 {
     constexpr int H = tile_rows(RPW);
     const int lane = threadIdx.x & 63;
@@ -398,7 +438,10 @@ __device__ __forceinline__ void tile_window_periodic(const GsStepArgs &a, float 
         u[i] = a.in_u[g];
         v[i] = a.in_v[g];
     }
-    tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
+    if constexpr (NOISE)
+        tile_steps<RPW, false, FAST, -1, 2>(a, lds, K, gr, gc, wave, lane, u, v, mn);
+    else
+        tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
     // store the window shrunk by K, where it lies in the grid
     if (lane >= K && lane < kTileCols - K && gc < a.cols) {
 #pragma unroll
@@ -414,8 +457,8 @@ __device__ __forceinline__ void tile_window_periodic(const GsStepArgs &a, float 
 }
 // The zero-flux rule's form (GsStepArgs::zero_halo = 3) of window `win`: gs_run_tile_k's load, steps and store, with the
 // rule's edge windows (tile_steps<ZH = 3>).
-template <int RPW, int FAST>
-__device__ __forceinline__ void tile_window_neumann(const GsStepArgs &a, float *lds, int K, int win)
+template <int RPW, int FAST, bool NOISE = false>
+__device__ __forceinline__ void tile_window_neumann(const GsStepArgs &a, float *lds, int K, int win, const MemberNoise &mn = MemberNoise{})
 {
     constexpr int H = tile_rows(RPW);
     const int lane = threadIdx.x & 63;
@@ -436,7 +479,12 @@ __device__ __forceinline__ void tile_window_neumann(const GsStepArgs &a, float *
         v[i] = in ? a.in_v[g] : 0.0f;
     }
     const bool edge = gr0 <= 0 || gc0 <= 0 || gr0 + H >= a.rows || gc0 + kTileCols >= a.cols;
-    if (!edge)
+    if constexpr (NOISE) {
+        if (!edge)
+            tile_steps<RPW, false, FAST, -1, 1>(a, lds, K, gr, gc, wave, lane, u, v, mn);
+        else
+            tile_steps<RPW, true, FAST, 3, 1>(a, lds, K, gr, gc, wave, lane, u, v, mn);
+    } else if (!edge)
         tile_steps<RPW, false, FAST, -1>(a, lds, K, gr, gc, wave, lane, u, v);
     else
         tile_steps<RPW, true, FAST, 3>(a, lds, K, gr, gc, wave, lane, u, v);

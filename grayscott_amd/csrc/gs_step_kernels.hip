@@ -54,6 +54,9 @@
 //       reference cell, then react_noise (gs_cell.h) -- a Philox2x32-10 draw at the cell's global (row, column) with the key
 //       of the level's step, one multiply and one add per species.  The marching forms, the same set as the map's, are built
 //       in a translation unit of their own (GS_NOISE_ONLY).  No difference sharing, no units at rest.
+//   gs_ens_resident_z*, gs_ens_tile_z*  the noise forms of the two ensemble kernels (second argument GsEnsNoiseArgs,
+//       gs_members_set_noise; gs_ensemble.h): a seed, sigmas and a step counter per member, the step key formed on the
+//       device.  Built in the noise translation units too, with their launchers (gs_launch_ens_*_noise_*).
 //
 // This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
 // its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
@@ -122,6 +125,12 @@
 #include "gs_ensemble.h"
 #include "gs_window_kernel.h"
 #endif
+#if GS_NOISE_ONLY
+// ... and the noise forms of the ensemble kernels (gs_ens_resident_z*, gs_ens_tile_z*: gs_ensemble.h), whose launchers are
+// below; nothing else of the two headers is instantiated here.
+#include "gs_lds_resident.h"
+#include "gs_ensemble.h"
+#endif
 
 // Launch tables.  GS_FN: the entry of a kernel instance.  kOp: the FAST argument of the ".op" variant (the fused build
 // has none: its launchers reduce `fast` to 0).  GS_NAME: the name a launcher reports for kernel family BASE, variant V
@@ -137,7 +146,8 @@
 // periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
 static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
 
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
+// (the kernels' own translation unit and the noise forms': both launch kernels with dynamic LDS)
 // Opt-in for more than 64 KB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize).  The attribute
 // belongs to the device function ON THE CURRENT DEVICE, so what has been set is remembered per (device,
 // function): a process that drives several GPUs (device_ids = 0, 1, ...; two contexts) opts in on each.
@@ -171,7 +181,7 @@ static hipError_t ensure_dyn_lds(const void *fn, size_t bytes)
 }
 // What the table above keys on, for the unit test of the key (tests/test_capi_cpu.py): 1 when (device, fn
 // slot, bytes) is new, and it is recorded; 0 when a launch on that device would skip the call.
-#if !GS_MATH_FUSED
+#if !GS_MATH_FUSED && !GS_NOISE_ONLY
 extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t bytes)
 {
     static const char slots[16] = {0};
@@ -191,6 +201,9 @@ extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t by
 // [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
 #define GS_TILE_NAMES(BASE, R) {GS_NAMES_OP(BASE "tile32x64", R), GS_NAMES_OP(BASE "tile16x64", R), GS_NAMES_OP(BASE "tile64x64", R)}
 #define GS_TILE_FNS(KER) {{GS_FN(KER, 2, 0), GS_FN(KER, 2, kOp)}, {GS_FN(KER, 1, 0), GS_FN(KER, 1, kOp)}, {GS_FN(KER, 4, 0), GS_FN(KER, 4, kOp)}}
+#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
+
+#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 
 // The attachment as a launcher takes it: a known kind with its planes in place.
 static bool attached_ok(const GsAttached &at)
@@ -930,6 +943,86 @@ const void *GS_SUFFIX(gs_tb_mask_kernel)(int k, int fast, int cpl, int rule)
 #endif
 
 #if GS_NOISE_ONLY
+// The noise forms of the ensemble kernels (gs_members_set_noise; gs_ensemble.h): launch_ens_resident's and launch_ens_tile's
+// checks, shapes and splits, the kernels gs_ens_resident_z* / gs_ens_tile_z* with GsEnsNoiseArgs as their second argument.
+// The name carries "/noise" behind the rule's suffix, and "/listed" behind that when z.list is set.
+hipError_t GS_SUFFIX(gs_launch_ens_resident_noise)(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int steps, int fast, hipStream_t s,
+                                                   const char **name)
+{
+    static const char *const names[2][3][2] = {GS_RULES_OF(GS_NAMES_OP, "ensemble-resident", "/noise"),
+                                               GS_RULES_OF(GS_NAMES_OP, "ensemble-resident", "/noise/listed")};
+    // [rule][variant][cells per thread: 1, 2, 4, 8]; the clipped rule has no 8-cell form (gs_ens_resident_cpt)
+#define GS_CPT_FNS(KER, ...) {GS_FN(KER, 1, __VA_ARGS__), GS_FN(KER, 2, __VA_ARGS__), GS_FN(KER, 4, __VA_ARGS__), GS_FN(KER, 8, __VA_ARGS__)}
+    static const void *const fns[4][2][4] = {
+        {{GS_FN(gs_ens_resident_zk, 1, 0, 0), GS_FN(gs_ens_resident_zk, 2, 0, 0), GS_FN(gs_ens_resident_zk, 4, 0, 0), nullptr},
+         {GS_FN(gs_ens_resident_zk, 1, kOp, 0), GS_FN(gs_ens_resident_zk, 2, kOp, 0), GS_FN(gs_ens_resident_zk, 4, kOp, 0), nullptr}},
+        {GS_CPT_FNS(gs_ens_resident_zk, 0, 1), GS_CPT_FNS(gs_ens_resident_zk, kOp, 1)},
+        {GS_CPT_FNS(gs_ens_resident_zpk, 0), GS_CPT_FNS(gs_ens_resident_zpk, kOp)},
+        {GS_CPT_FNS(gs_ens_resident_znk, 0), GS_CPT_FNS(gs_ens_resident_znk, kOp)}};
+#undef GS_CPT_FNS
+    const long cells = (long)e.rows * e.cols;
+    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0 || !z.table) return hipErrorInvalidValue;
+    const long threads = cells >= 1024 ? 1024 : ((cells + 63) / 64) * 64; // the waves that hold cells
+    const int cpt = gs_ens_resident_cpt(e.rows, e.cols, e.zero_halo);
+    const size_t lds = (size_t)4 * (e.rows + 2) * (e.cols + 2) * sizeof(float);
+    if (!cpt || lds > kGsEnsResidentMaxLds) return hipErrorInvalidValue;
+    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
+    const int zh = e.zero_halo >= 2 && e.zero_halo <= 3 ? e.zero_halo : (e.zero_halo ? 1 : 0); // gs_boundary
+    if (name) *name = names[z.list ? 1 : 0][rule_set(zh)][fast ? 1 : 0];
+    const void *fn = fns[zh][fast ? 1 : 0][__builtin_ctz(cpt)];
+    if (!fn) return hipErrorInvalidValue;
+    { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
+        const hipError_t err = ensure_dyn_lds(fn, lds);
+        if (err != hipSuccess) return err;
+    }
+    int to_out = steps & 1;
+    GsEnsNoiseArgs nz = z;
+    for (long m0 = 0; m0 < e.members; m0 += kGsEnsMaxGroups) {
+        GsEnsArgs args = e;
+        args.first = e.first + m0;
+        args.members = (int32_t)(e.members - m0 < kGsEnsMaxGroups ? e.members - m0 : kGsEnsMaxGroups);
+        void *kargs[] = {&args, &nz, &steps, &to_out};
+        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)args.members), dim3((unsigned)threads), kargs, lds, s);
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+hipError_t GS_SUFFIX(gs_launch_ens_tile_noise)(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int k, int shape, int fast, hipStream_t s,
+                                               const char **name)
+{
+    static const char *const names[2][3][3][2] = {GS_RULES_OF(GS_TILE_NAMES, "ensemble-", "/noise"),
+                                                  GS_RULES_OF(GS_TILE_NAMES, "ensemble-", "/noise/listed")};
+    static const void *const fns[3][3][2] = {GS_TILE_FNS(gs_ens_tile_zk), GS_TILE_FNS(gs_ens_tile_zpk), GS_TILE_FNS(gs_ens_tile_znk)};
+    static const int rpw[3] = {2, 1, 4};
+    const int per = rule_set(e.zero_halo);
+    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]) ||
+        !z.table)
+        return hipErrorInvalidValue;
+    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
+    if (name) *name = names[z.list ? 1 : 0][per][shape][fast ? 1 : 0];
+    const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
+    const long windows = ((e.rows + ho - 1) / ho) * ((e.cols + wo - 1) / wo);
+    if (windows > kGsEnsMaxGroups) return hipErrorInvalidConfiguration;
+    const void *fn = fns[per][shape][fast ? 1 : 0];
+    const size_t lds = tile_lds_bytes(rpw[shape]);
+    {
+        const hipError_t err = ensure_dyn_lds(fn, lds);
+        if (err != hipSuccess) return err;
+    }
+    const long per_launch = kGsEnsMaxGroups / windows; // members per launch
+    int wins = (int)windows;
+    GsEnsNoiseArgs nz = z;
+    for (long m0 = 0; m0 < e.members; m0 += per_launch) {
+        GsEnsArgs args = e;
+        args.first = e.first + m0;
+        args.members = (int32_t)(e.members - m0 < per_launch ? e.members - m0 : per_launch);
+        void *kargs[] = {&args, &nz, &k, &wins};
+        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)(args.members * windows)), dim3(kTileWaves * 64), kargs, lds, s);
+        if (err != hipSuccess) return err;
+    }
+    return hipSuccess;
+}
+
 // Kernel entry of the marching kernel's noise form (gs_kernels.h: gs_tb_noise_kernel_*), the parameters of
 // gs_tb_map_kernel_*.
 const void *GS_SUFFIX(gs_tb_noise_kernel)(int k, int fast, int cpl, int rule)

@@ -298,6 +298,8 @@ def summarize_fields(context: "HipContext", fields: Sequence["HipConcentration"]
 
 # ``gs_change`` as a numpy record: what ``Ensemble.changes_since`` returns (40 bytes, the C layout, filled in place).
 CHANGE_DTYPE = np.dtype([("sum_abs", "<f8"), ("sum_sq", "<f8"), ("max_abs", "<f8"), ("differing", "<u8"), ("nonfinite", "<u8")])
+# gs_noise's layout (24 bytes): what Ensemble.set_noise sends and Ensemble.noise returns, one record per member
+NOISE_DTYPE = np.dtype([("sigma_u", "<f4"), ("sigma_v", "<f4"), ("seed", "<u8"), ("step", "<u8")])
 
 
 @dataclass(frozen=True)
@@ -2602,6 +2604,37 @@ class Ensemble:
     def active_count(self) -> int:
         """How many members of the whole ensemble are active."""
         return int(self._get_active(0, 1, False, False)[2])
+
+    def set_noise(self, sigma_u, sigma_v=0.0, seed=0, step=0, first: int = 0, count: Optional[int] = None) -> None:
+        """Noise of members ``[first, first + count)`` (``gs_members_set_noise``; blocking): scalars or per-member arrays,
+        broadcast against each other.  From now on every step of such a member adds ``sigma * xi`` to each species, drawn
+        with the member's own ``seed`` at the member's own step index, which starts at ``step`` and advances with the steps
+        that member takes -- member i is bit for bit a lone Species with ``Simulation.set_noise`` of the same values.  The
+        first call attaches noise to the ensemble (members never named: sigmas 0, seed 0, step 0); the context's own noise
+        never touches an ensemble."""
+        first, count = self._range(first, count)
+        n = np.zeros(max(count, 0), NOISE_DTYPE)
+        n["sigma_u"], n["sigma_v"] = sigma_u, sigma_v
+        for name, value in (("seed", seed), ("step", step)):  # any Python or numpy integers, taken modulo 2^64
+            words = np.broadcast_to(np.asarray(value, dtype=object), n.shape)
+            n[name] = np.array([int(x) & 0xFFFFFFFFFFFFFFFF for x in words], np.uint64)
+        capi.check(self._ctx._lib.gs_members_set_noise(self._ctx.handle, self.handle, first, count,
+                                                        n.ctypes.data_as(ctypes.c_void_p), n.size))
+
+    def noise(self, first: int = 0, count: Optional[int] = None) -> Optional[np.ndarray]:
+        """The noise of members ``[first, first + count)`` as a structured array (``NOISE_DTYPE``: sigma_u, sigma_v, seed and
+        step -- the member's NEXT step index; a retired member's stands still), or ``None`` when the ensemble has none.
+        Saved with a snapshot of the members, the records continue a run exactly."""
+        first, count = self._range(first, count)
+        n = np.zeros(max(count, 0), NOISE_DTYPE)
+        attached = ctypes.c_int32(0)
+        capi.check(self._ctx._lib.gs_members_get_noise(self._ctx.handle, self.handle, first, count,
+                                                        n.ctypes.data_as(ctypes.c_void_p), ctypes.byref(attached)))
+        return n if attached.value else None
+
+    def clear_noise(self) -> None:
+        """Detach the ensemble's noise: the next run launches the kernels of an ensemble without noise."""
+        capi.check(self._ctx._lib.gs_members_clear_noise(self._ctx.handle, self.handle))
 
     def prepare_steps(self, steps: int) -> None:
         """Enqueue ``steps`` steps of every active member and return (``gs_ensemble_run``); ``context.sync()`` waits."""

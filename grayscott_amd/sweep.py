@@ -110,6 +110,16 @@ tile-averaged power spectra of every member summed on the device (``Ensemble.spe
 ``steps[samples]``, ``tile``, ``window``, ``power[samples, members, 2, T, T/2 + 1]`` (axis 2: U, V; the raw f64 sums),
 ``tiles[samples, members, 2, 2]`` (last axis: tiles used, tiles skipped) and ``wavelength[samples, members, 2]`` in cells
 (``Spectrum.wavelength``; NaN for a flat spectrum).  It changes no state either and works with ``--no-fields``.
+
+``--noise SU[:SV]`` makes the run stochastic (``Ensemble.set_noise``; the definition is include/gs_hip.h's): every step adds
+``SU * xi`` to U and ``SV * xi`` to V (SV defaults to 0), ``xi`` uniform on [-1, 1).  ``--realisations R`` (default 1) turns
+every (feed, kill) point into R members: member ``point * R + r``, ``point`` in the kill-major order above, runs with seed
+``N + r``, ``N`` from ``--noise-seed N`` (default 0), from step 0.  The same seeds at every point are deliberate: common
+random numbers across the map, so that neighbouring points differ by their parameters and not by their draws.  A run is
+reproducible to the byte.  The JSON sidecar gains ``realisation`` and ``noise_seed`` per member and ``noise`` (sigma_u,
+sigma_v, seed, realisations) at top level.  ``--realisations`` above 1 needs ``--noise``.  ``--steady-retire`` and every
+``--*-every`` observable work on noisy members as they are: a retired member keeps its step counter.  Without the three flags
+every output file is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -151,6 +161,18 @@ def value_pair(text: str) -> Tuple[float, float]:
     return a, b
 
 
+def sigma_pair(text: str) -> Tuple[float, float]:
+    """``SU[:SV]`` -> (SU, SV): two finite sigmas, none below 0; SV defaults to 0."""
+    parts = text.split(":")
+    try:
+        out = [float(x) for x in parts]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected SU[:SV], got {text!r}")
+    if not 1 <= len(out) <= 2 or not all(0.0 <= x < float("inf") for x in out):
+        raise argparse.ArgumentTypeError(f"one or two finite sigmas that are at least 0, got {text!r}")
+    return out[0], (out[1] if len(out) == 2 else 0.0)
+
+
 def threshold_list(text: str) -> List[float]:
     """``A[,B,...]`` -> 1 to 4 thresholds, none of them NaN."""
     try:
@@ -167,7 +189,8 @@ THRESHOLDED = (("components", "comp"), ("morphology", "morph"), ("correlation", 
 
 
 def parse(argv=None):
-    ap = argparse.ArgumentParser(prog="sweep", description="Gray-Scott parameter sweep, one ensemble member per (feed, kill)")
+    ap = argparse.ArgumentParser(prog="sweep", description="Gray-Scott parameter sweep, one ensemble member per (feed, kill) "
+                                                           "-- with --noise, --realisations of them")
     ap.add_argument("--feed", type=value_range, required=True, metavar="A:B:N", help="feed rates")
     ap.add_argument("--kill", type=value_range, required=True, metavar="A:B:N", help="kill rates")
     ap.add_argument("-s", "--steps", type=int, default=1000, help="steps per member")
@@ -234,9 +257,18 @@ def parse(argv=None):
                     help="the side of the spectra's tiles: 16, 32, 64 (the default) or 128 cells")
     ap.add_argument("--spectrum-window", default="hann", choices=sorted(SPECTRUM_WINDOWS),
                     help="the window of a tile: hann (periodic Hann, the default) or none")
+    ap.add_argument("--noise", type=sigma_pair, default=None, metavar="SU[:SV]",
+                    help="per-step noise amplitudes of U and V (SV defaults to 0): every member runs with noise")
+    ap.add_argument("--noise-seed", type=int, default=0, metavar="N", help="realisation r of every point runs with seed N + r (default 0)")
+    ap.add_argument("--realisations", type=int, default=1, metavar="R",
+                    help="members per (feed, kill) point, each with its own seed (default 1; more need --noise)")
     add_time_stats_args(ap, "--time-stats")
     add_backend_args(ap)
     args = ap.parse_args(argv)
+    if args.realisations < 1:
+        ap.error("--realisations must be at least 1")
+    if args.realisations > 1 and args.noise is None:
+        ap.error("--realisations above 1 needs --noise: without it the members of a point would be copies")
     if args.spectrum_every < 0:
         ap.error("--spectrum-every must be at least 1 (0 = off)")
     check_time_stats_args(ap, args, "time_stats", "--time-stats")
@@ -288,8 +320,17 @@ def parse(argv=None):
 
 
 def members(args) -> List[Tuple[int, float, float]]:
-    """(index, feed, kill) of every member, kill-major."""
-    return [(i * len(args.feed) + j, f, k) for i, k in enumerate(args.kill) for j, f in enumerate(args.feed)]
+    """(index, feed, kill) of every member: the points kill-major, ``--realisations`` members per point side by side."""
+    reps = getattr(args, "realisations", 1)
+    return [((i * len(args.feed) + j) * reps + r, f, k) for i, k in enumerate(args.kill) for j, f in enumerate(args.feed)
+            for r in range(reps)]
+
+
+def member_seeds(args) -> List[Tuple[int, int]]:
+    """(realisation, seed) of every member, in the order of ``members``: realisation r of every point has seed
+    ``--noise-seed`` + r (modulo 2^64) -- common random numbers across the map."""
+    reps = getattr(args, "realisations", 1)
+    return [(i % reps, (args.noise_seed + i % reps) & 0xFFFFFFFFFFFFFFFF) for i in range(len(args.feed) * len(args.kill) * reps)]
 
 
 def member_params(args) -> List[Parameters]:
@@ -476,6 +517,8 @@ def run(args) -> dict:
     params = member_params(args)
     sim = Simulation.new(params[0], backend_args(args))
     ens = sim.make_ensemble(shape, params)
+    if args.noise is not None:
+        ens.set_noise(args.noise[0], args.noise[1], seed=np.array([seed for _, seed in member_seeds(args)], np.uint64))
     t0 = time.perf_counter()
     summary_at = sample_steps(args.steps, args.summary_every) if args.summary_every else []
     hist_at = sample_steps(args.steps, args.histogram_every) if args.histogram_every else []
@@ -590,7 +633,13 @@ def run(args) -> dict:
         if taken is not None:
             for m in listed:
                 m["steps_taken"] = int(taken[m["index"]])
-        json.dump({"shape": list(shape), "steps": done, "members": listed}, f, indent=1)
+        top = {"shape": list(shape), "steps": done, "members": listed}
+        if args.noise is not None:
+            for m, (r, seed) in zip(listed, member_seeds(args)):
+                m["realisation"], m["noise_seed"] = r, seed
+            top["noise"] = {"sigma_u": args.noise[0], "sigma_v": args.noise[1], "seed": args.noise_seed,
+                            "realisations": args.realisations}
+        json.dump(top, f, indent=1)
     kernel, _ = sim.context.info()
     ens.destroy()
     sim.context.close()

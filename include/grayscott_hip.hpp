@@ -1111,6 +1111,29 @@ class Ensemble {
         check(gs_members_get_active(ctx_->get(), e_, 0, members_, nullptr, out.data(), nullptr));
         return out;
     }
+    // noise of members [first, first + noise.size()) (gs_members_set_noise, blocking), one struct per member: its sigmas,
+    // its seed and the index of its next step, which advances with the steps that member takes.  The first call attaches
+    // noise to the ensemble (members never named: sigmas 0, seed 0, step 0); Simulation::set_noise never touches an ensemble
+    void set_noise(const std::vector<gs_noise> &noise, std::size_t first = 0)
+    {
+        check(gs_members_set_noise(ctx_->get(), e_, first, noise.size(), noise.data(), noise.size()));
+    }
+    // ... and one struct for all of members [first, first + count)
+    void set_noise(const gs_noise &noise, std::size_t first, std::size_t count)
+    {
+        check(gs_members_set_noise(ctx_->get(), e_, first, count, &noise, 1));
+    }
+    // every member's struct with its current step; empty when the ensemble has no noise (gs_members_get_noise)
+    std::vector<gs_noise> noise() const
+    {
+        std::vector<gs_noise> out(members_);
+        int32_t attached = 0;
+        check(gs_members_get_noise(ctx_->get(), e_, 0, members_, out.data(), &attached));
+        if (!attached) out.clear();
+        return out;
+    }
+    // detach: the next run launches the kernels of an ensemble without noise
+    void clear_noise() { check(gs_members_clear_noise(ctx_->get(), e_)); }
     // summaries of members [first, first + count) from the newest state (gs_members_summarize, blocking): element
     // 2 i = U, 2 i + 1 = V of member first + i, bit for bit what Species::summary gives for a lone Species in that state
     std::vector<Summary> summaries(std::size_t first, std::size_t count) const

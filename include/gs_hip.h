@@ -327,7 +327,8 @@ int32_t gs_ctx_set_mask(gs_ctx *ctx, gs_field *mask);
  * passes the same struct.  With noise, gs_run runs the marching kernel at every grid size, gs_step the streaming one and a
  * pinned GS_KERNEL_SIMPLE the simple one; their noise forms carry a "/noise" suffix in gs_ctx_info (e.g.
  * "tb-k4c2/strict.op/noise") and share no differences.  The on-line tuner keeps noise runs apart from the other kernel sets;
- * whatever it does, step s is computed with key(s).  Units at rest never apply.  Ensembles ignore the noise.
+ * whatever it does, step s is computed with key(s).  Units at rest never apply.  Ensembles ignore the
+ * context's noise; see gs_members_set_noise.
  *   gs_ctx_get_noise : *out = the struct in force with the current step (untouched when none is), *attached = 0 / 1. */
 typedef struct gs_noise {
     float sigma_u, sigma_v;
@@ -606,6 +607,44 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps);
 int32_t gs_members_set_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const uint8_t *active);
 int32_t gs_members_get_active(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, uint8_t *active, uint64_t *steps_taken,
                               uint64_t *active_total);
+
+/* Noise of an ensemble: many realisations in shared launches.  Noise is attached to an ENSEMBLE, per member: every member
+ * has its own gs_noise -- sigmas, seed and step counter; the context's noise (gs_ctx_set_noise) does not touch ensembles.
+ * The generator, the step key, the draw, xi and the two operations per species are those defined under gs_ctx_set_noise, to
+ * the bit: after any sequence of gs_ensemble_run calls, member i of an ensemble with noise is bit for bit what gs_run makes
+ * of a lone Species on a context with member i's parameters, member i's initial state and member i's gs_noise attached,
+ * after member i's own step count -- under all four boundary rules, in both math flavours, in both ensemble forms
+ * (resident, windowed) and with or without an active set.
+ *   gs_members_set_noise    noise[i] for member first + i, i < count, when entries == count; noise[0] for all of them when
+ *                           entries == 1.  The first call attaches noise to the ensemble: members never named hold sigmas
+ *                           0, seed 0 and step 0.  Later calls overwrite the named members only.  Blocking: it waits for
+ *                           enqueued work.
+ *   gs_members_get_noise    out[i] = member first + i's struct with its CURRENT step, *attached = 0 / 1 for the ensemble;
+ *                           `out` is untouched when it is 0.  Either may be NULL, not both.  No device work: steps that are
+ *                           enqueued count as taken, as in gs_members_get_active.
+ *   gs_members_clear_noise  detaches: the next run launches exactly the kernels of an ensemble without noise.
+ * Coordinates: a cell draws at its member-local (row, column); under the periodic rule a cell computed at a wrapped
+ * position draws at the wrapped one.  Cells outside a member are zeros, unread or ring copies, as the rule says, and never
+ * a source of noise.
+ * Step counters: a member's counter starts at its gs_noise.step and advances by one per step THAT MEMBER takes -- a retired
+ * member keeps its counter and goes on from it when it is reactivated.  The counter is u64 and wraps.  gs_members_copy
+ * copies no noise, as it copies no step counts: a gs_members_copy into another ensemble plus the structs read back with
+ * gs_members_get_noise continue a run exactly.
+ * Zero sigmas: a member whose sigmas are both 0 has the bits of the plain run, a species whose sigma is 0 is not touched (-0
+ * stays -0); the noise kernels run all the same (the A/B for measuring cost).  The multiply and the add are never
+ * contracted in either flavour; GS_MATH_STRICT flushes sub-normal products and sums.
+ * With noise attached gs_ensemble_run runs the noise forms of the two ensemble kernels, members of the same sizes in the
+ * same form: gs_ctx_info names them with "/noise" behind the rule's suffix, and "/listed" behind that while a proper subset
+ * of the members is active ("ensemble-resident/strict.op/noise", "ensemble-tile32x64/strict/periodic/noise/listed").  The
+ * step key is formed on the device, once per step and member.
+ * GS_ERR_INVALID, all decided before any device work: a null or foreign handle, members outside the ensemble, a null
+ * `noise`, `entries` neither 1 nor `count`, a sigma that is negative or not finite (set_noise); both outputs null
+ * (get_noise).  GS_ERR_UNSUPPORTED: set_noise on an ensemble of more than 2^31 members (the noise kernels take the list of
+ * active members, which holds 32-bit indices).  Noise together with parameter maps or masks does not exist: ensembles have
+ * neither. */
+int32_t gs_members_set_noise(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, const gs_noise *noise, uint64_t entries);
+int32_t gs_members_get_noise(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, gs_noise *out, int32_t *attached);
+int32_t gs_members_clear_noise(gs_ctx *ctx, gs_ensemble *e);
 
 /* Summaries computed on the device: for one plane of the WHOLE global grid, the sum and sum of squares of its finite
  * cells, their minimum and maximum, and the count of non-finite cells (NaN, +-inf) -- without downloading the plane.
