@@ -94,6 +94,9 @@ UNITS = [
     # time statistics (per-cell f64 sums, f32 extremes and u32 crossing counters read, updated and written back per sample):
     # the same float mode, a sub-normal sample counts as the value it is
     ("gs_time_stats.hip", "gs_time_stats_k.o", []),
+    # bundle statistics (the same accumulators across the members of a bundle, kept in registers; only results are written):
+    # the same float mode, a sub-normal value counts as the value it is
+    ("gs_bundle_stats.hip", "gs_bundle_stats_k.o", []),
     # the host side (contexts and schedule, planes, kernel configuration, the window kernel's runtime, RCCL): only the
     # C ABI of include/gs_hip.h is visible outside the library
     ("gs_api.cpp", "gs_api.o", ["-x", "hip", "-fvisibility=hidden"]),
@@ -105,6 +108,7 @@ UNITS = [
     ("gs_attached.cpp", "gs_attached.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_observe.cpp", "gs_observe.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_time_stats.cpp", "gs_time_stats.o", ["-x", "hip", "-fvisibility=hidden"]),
+    ("gs_bundle_stats.cpp", "gs_bundle_stats.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

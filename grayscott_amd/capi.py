@@ -74,6 +74,7 @@ EXPORTS = (
     "gs_time_stats_create", "gs_time_stats_destroy", "gs_time_stats_reset", "gs_time_stats_accumulate", "gs_time_stats_samples",
     "gs_time_stats_result", "gs_time_stats_download",
     "gs_members_time_stats_create", "gs_members_time_stats_accumulate", "gs_members_time_stats_result",
+    "gs_members_bundle_stats",
     "gs_ctx_quiet_stats", "gs_ctx_quiet_edge_stats",
 )
 
@@ -349,6 +350,7 @@ def load() -> ctypes.CDLL:
         "gs_members_time_stats_create": (i32, [vp, P(vp), vp, u64, u64, u32, P(f32), P(i32)]),
         "gs_members_time_stats_accumulate": (i32, [vp, vp, vp, u32]),
         "gs_members_time_stats_result": (i32, [vp, vp, i32, i32, vp]),
+        "gs_members_bundle_stats": (i32, [vp, vp, u64, u64, u64, P(i32), i32, P(f32), P(i32), P(vp), u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError here = header/library mismatch

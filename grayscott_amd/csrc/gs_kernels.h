@@ -544,3 +544,11 @@ hipError_t gs_launch_tstat_reset(int np, uint32_t groups, const GsTstatAcc &acc,
 // One result plane (`which`: GS_TSTAT_MEAN .. GS_TSTAT_ARRIVAL) of plane `plane` after n samples into out, rows of `pitch` floats.
 hipError_t gs_launch_tstat_result(int which, int plane, const GsTstatAcc &acc, int64_t pitch, int64_t rows, int32_t cols, uint64_t n,
                                   float *out, hipStream_t s);
+
+// ---- statistics across the members of a bundle (gs_bundle_stats.hip) ------------------------------------------------------
+// `bundles` bundles of `span` consecutive dense members of `cells` floats each, U from in[0] and V from in[1] (the first
+// bundle's first member): result plane w (GS_TSTAT_MEAN .. GS_TSTAT_OCCUPANCY) of bundle b of species sp goes to
+// out[sp][w] + b * cells where out[sp][w] is not null (the same w for both species).  t / flip: the set rule of
+// gs_plane_scan.h per species, read for the occupancy alone.  One launch per 65535 bundles.
+hipError_t gs_launch_bundle_stats(const float *const in[2], float *const out[2][5], int64_t cells, int64_t span, int64_t bundles,
+                                  const float t[2], const uint32_t flip[2], hipStream_t s);

@@ -2549,6 +2549,53 @@ class Ensemble:
         return TimeStats(self._ctx, self, groups, u_threshold=u_threshold, v_threshold=v_threshold, above=above, first=first,
                          count=count)
 
+    BUNDLE_RESULTS = {"mean": capi.GS_TSTAT_MEAN, "variance": capi.GS_TSTAT_VARIANCE, "min": capi.GS_TSTAT_MIN,
+                      "max": capi.GS_TSTAT_MAX, "occupancy": capi.GS_TSTAT_OCCUPANCY}
+
+    def bundle_stats(self, span: int, which=("mean", "variance"), v_threshold=None, u_threshold=None, above=True,
+                     first: int = 0, count: Optional[int] = None, out: Optional[dict] = None, out_first: int = 0) -> dict:
+        """Per-cell statistics ACROSS members, formed on the device in one pass (``gs_members_bundle_stats``, blocking): every
+        run of ``span`` consecutive members of ``[first, first + count)`` is a bundle -- the realisations of one parameter
+        point, say -- and result ``name`` of bundle ``b`` becomes member ``out_first + b`` of the ensemble ``out[name]``, U
+        from the members' U and V from their V.  ``which`` names the results: ``"mean"``, ``"variance"``, ``"min"``,
+        ``"max"``, ``"occupancy"`` (the share of the members in which the cell is beyond its species' threshold; a species
+        without a threshold is never set).  The accumulators and formulas are those of ``TimeStats`` with member ``j`` in
+        the place of sample ``j``: a bundle's planes are bit for bit the time statistics of a lone Species sampled through
+        the members' states.  Members are read whether active or retired.  Without ``out`` the result ensembles are made
+        here with ``count / span`` members; like ``snapshot()`` they carry the context's parameters.  Returns ``{name:
+        Ensemble}``: every ensemble observable applies to a mean field or a probability map without a download."""
+        names = [which] if isinstance(which, str) else list(which)
+        for name in names:
+            if name not in self.BUNDLE_RESULTS:
+                raise ValueError(f"unknown result {name!r}: one of {sorted(self.BUNDLE_RESULTS)}")
+        first, count = self._range(first, count)
+        span = int(span)
+        thresholds = above_arr = None
+        if u_threshold is not None or v_threshold is not None:
+            # (a species whose threshold is not given is never set: nothing is above +inf)
+            t = [math.inf if x is None else float(x) for x in (u_threshold, v_threshold)]
+            senses = [above, above] if isinstance(above, (bool, int)) else list(above)
+            senses = [bool(senses[i]) if x is not None else True for i, x in enumerate((u_threshold, v_threshold))]
+            thresholds, above_arr = (ctypes.c_float * 2)(*t), (ctypes.c_int32 * 2)(*[int(a) for a in senses])
+        made = []
+        if out is None:
+            bundles = count // span if span > 0 else 0
+            out = {}
+            for name in names:
+                if name not in out:
+                    out[name] = Ensemble(self._ctx, max(int(out_first) + bundles, 1), self._shape)
+                    made.append(out[name])
+        codes = (ctypes.c_int32 * max(len(names), 1))(*[self.BUNDLE_RESULTS[name] for name in names])
+        targets = (ctypes.c_void_p * max(len(names), 1))(*[out[name].handle.value for name in names])
+        try:
+            capi.check(self._ctx._lib.gs_members_bundle_stats(self._ctx.handle, self.handle, first, count, span, codes, len(names),
+                                                              thresholds, above_arr, targets, int(out_first)))
+        except GsError:
+            for e in made:
+                e.destroy()
+            raise
+        return {name: out[name] for name in names}
+
     def set_active(self, mask, first: int = 0) -> None:
         """Active flags of members ``[first, first + len(mask))`` from a bool or uint8 array (``gs_members_set_active``;
         blocking): ``prepare_steps`` advances the active members only, an inactive member keeps its state -- every reader

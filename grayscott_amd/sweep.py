@@ -120,6 +120,15 @@ reproducible to the byte.  The JSON sidecar gains ``realisation`` and ``noise_se
 sigma_v, seed, realisations) at top level.  ``--realisations`` above 1 needs ``--noise``.  ``--steady-retire`` and every
 ``--*-every`` observable work on noisy members as they are: a retired member keeps its step counter.  Without the three flags
 every output file is byte for byte what it was.
+
+``--bundle-stats`` forms, after the last step, the ensemble average of every (feed, kill) point on the device
+(``Ensemble.bundle_stats``; the definition is include/gs_hip.h's): the ``--realisations R`` members of a point are a bundle, and
+``<output stem>.bundles.npz`` receives ``mean_u``, ``mean_v``, ``variance_u``, ``variance_v``, ``min_v`` and ``max_v``, each
+``[points, rows, cols]`` f32 with the points in the kill-major order above -- the per-cell statistics across the realisations --
+and ``feed[points]``, ``kill[points]`` and ``span`` (= R).  ``--bundle-threshold-v T`` adds ``occupancy_v``, the share of the
+realisations in which the cell's V is above T: the probability that it lies inside a spot.  Retired members count with the
+state they hold.  It works with ``--no-fields``, the JSON sidecar names the file under ``bundle_stats``, and without the flag
+every output file is byte for byte what it was.
 """
 from __future__ import annotations
 
@@ -262,9 +271,18 @@ def parse(argv=None):
     ap.add_argument("--noise-seed", type=int, default=0, metavar="N", help="realisation r of every point runs with seed N + r (default 0)")
     ap.add_argument("--realisations", type=int, default=1, metavar="R",
                     help="members per (feed, kill) point, each with its own seed (default 1; more need --noise)")
+    ap.add_argument("--bundle-stats", action="store_true",
+                    help="after the last step, per-cell mean, variance and range across the --realisations of every point "
+                         "(<output stem>.bundles.npz)")
+    ap.add_argument("--bundle-threshold-v", type=float, default=None, metavar="T",
+                    help="with --bundle-stats: also the share of a point's realisations in which V is above T (occupancy_v)")
     add_time_stats_args(ap, "--time-stats")
     add_backend_args(ap)
     args = ap.parse_args(argv)
+    if args.bundle_threshold_v is not None and not args.bundle_stats:
+        ap.error("--bundle-threshold-v needs --bundle-stats")
+    if args.bundle_threshold_v is not None and args.bundle_threshold_v != args.bundle_threshold_v:
+        ap.error("--bundle-threshold-v must be a number")
     if args.realisations < 1:
         ap.error("--realisations must be at least 1")
     if args.realisations > 1 and args.noise is None:
@@ -369,6 +387,27 @@ def steady_path(output: str) -> str:
 
 def time_stats_path(output: str) -> str:
     return os.path.splitext(output)[0] + ".timestats.npz"
+
+
+def bundles_path(output: str) -> str:
+    return os.path.splitext(output)[0] + ".bundles.npz"
+
+
+BUNDLE_PLANES = (("mean", "u"), ("mean", "v"), ("variance", "u"), ("variance", "v"), ("min", "v"), ("max", "v"))
+
+
+def bundle_results(threshold_v) -> Tuple[str, ...]:
+    """The results ``--bundle-stats`` asks ``Ensemble.bundle_stats`` for."""
+    return ("mean", "variance", "min", "max") + (("occupancy",) if threshold_v is not None else ())
+
+
+def write_bundles(path: str, results: dict, threshold_v, feed, kill, span: int, view) -> None:
+    """``results``: {name: what holds the planes of every point}; ``view(x, species)`` reads them as ``[points, rows, cols]``."""
+    planes = BUNDLE_PLANES + ((("occupancy", "v"),) if threshold_v is not None else ())
+    out = {f"{name}_{species}": np.asarray(view(results[name], species), np.float32) for name, species in planes}
+    out.update(feed=np.asarray(feed, np.float64), kill=np.asarray(kill, np.float64), span=np.int64(span))
+    with open(path, "wb") as f:
+        np.savez(f, **out)
 
 
 def write_time_stats(path: str, samples: int, steps: List[int], planes: dict, with_planes: bool) -> None:
@@ -617,6 +656,14 @@ def run(args) -> dict:
         ens.perform_steps(args.steps)
         done = args.steps
     elapsed = time.perf_counter() - t0
+    if args.bundle_stats:
+        results = ens.bundle_stats(args.realisations, bundle_results(args.bundle_threshold_v), v_threshold=args.bundle_threshold_v)
+        points = members(args)[::args.realisations]
+        write_bundles(bundles_path(args.output), results, args.bundle_threshold_v, [f for _, f, _ in points],
+                      [k for _, _, k in points], args.realisations,
+                      lambda e, species: e.u_views() if species == "u" else e.result_views())
+        for e in results.values():
+            e.destroy()
     if not args.no_fields:
         out = hdf5_min.create(args.output, (len(params),) + shape)
         per_chunk = max(1, (256 << 20) // (4 * shape[0] * shape[1]))  # download in pieces of ~256 MB
@@ -639,6 +686,9 @@ def run(args) -> dict:
                 m["realisation"], m["noise_seed"] = r, seed
             top["noise"] = {"sigma_u": args.noise[0], "sigma_v": args.noise[1], "seed": args.noise_seed,
                             "realisations": args.realisations}
+        if args.bundle_stats:
+            top["bundle_stats"] = {"file": os.path.basename(bundles_path(args.output)), "span": args.realisations,
+                                   "threshold_v": args.bundle_threshold_v}
         json.dump(top, f, indent=1)
     kernel, _ = sim.context.info()
     ens.destroy()

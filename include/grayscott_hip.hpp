@@ -1279,6 +1279,30 @@ class Ensemble {
         for (const gs_change &x : c) out.push_back(Change::from_c(x, shape_[0] * shape_[1]));
         return out;
     }
+    // per-cell statistics ACROSS members (gs_members_bundle_stats, blocking): every run of `span` consecutive members of
+    // [first, first + count) is a bundle, and result which[i] (GS_TSTAT_MEAN .. GS_TSTAT_OCCUPANCY) of bundle b becomes
+    // member b of the i-th ensemble returned -- count / span members, the context's parameters, as snapshot() --, U from the
+    // members' U and V from their V: bit for bit the time statistics of a lone Species sampled through the members' states.
+    // The occupancy needs thresholds = {U's, V's} and above = {U's, V's} (set above it)
+    std::vector<Ensemble> bundle_stats(std::size_t span, const std::vector<int32_t> &which, const std::vector<float> &thresholds = {},
+                                       const std::vector<int32_t> &above = {}, std::size_t first = 0,
+                                       std::size_t count = (std::size_t)-1) const
+    {
+        if (count == (std::size_t)-1) count = members_ - first;
+        if ((!thresholds.empty() && thresholds.size() != 2) || above.size() != thresholds.size())
+            throw HipError(GS_ERR_INVALID, "bundle statistics: thresholds and above are {U's, V's}, or both empty");
+        const std::size_t bundles = span ? count / span : 0;
+        std::vector<Ensemble> out;
+        std::vector<gs_ensemble *> raw;
+        for (std::size_t i = 0; i < which.size(); ++i) {
+            out.push_back(Ensemble(ctx_, bundles ? bundles : 1, shape_));
+            raw.push_back(out.back().e_);
+        }
+        check(gs_members_bundle_stats(ctx_->get(), e_, first, count, span, which.data(), (int32_t)which.size(),
+                                      thresholds.empty() ? nullptr : thresholds.data(), above.empty() ? nullptr : above.data(),
+                                      raw.data(), 0));
+        return out;
+    }
 
   private:
     // all members zero, every member with the context's parameters (snapshot)

@@ -1330,6 +1330,46 @@ int32_t gs_members_time_stats_create(gs_ctx *ctx, gs_time_stats **out, gs_ensemb
 int32_t gs_members_time_stats_accumulate(gs_ctx *ctx, gs_time_stats *ts, gs_ensemble *e, uint32_t stamp);
 int32_t gs_members_time_stats_result(gs_ctx *ctx, gs_time_stats *ts, int32_t species, int32_t which, float *host);
 
+/* Bundle statistics: per-cell statistics ACROSS ensemble members, formed on the device in one pass -- the ensemble average
+ * of R realisations of one parameter point (mean), the spread between them (variance), the envelope (min, max) and the
+ * probability that a cell lies inside a spot, P(V > t) (occupancy) -- without downloading a member.
+ * Members [first, first + count) of `e` form count / span BUNDLES: bundle b holds members first + b span + j, j < span.
+ * For every bundle, species (U, V) and cell the accumulators are those of the time statistics above, member j in the place
+ * of sample j, visited in ascending j:
+ *   sum (f64, from +0.0):        sum = sum + (double)x
+ *   squares (f64, from +0.0):    squares = squares + (double)x * (double)x
+ *   min, max (f32, from +inf, -inf):   min = x < min ? x : min;  max = x > max ? x : max   (strict: a NaN never replaces an
+ *                                extreme, nor does a zero one of the other sign)
+ *   set_count (u32, from 0):     + 1 where x is SET by morphology's rule against the species' threshold and sense (x > t, or
+ *                                x < t; one f32 comparison)
+ * Both sums are plain sequential f64 additions in member order, and that order is the contract: a span is never split over
+ * lanes, waves or launches and added up again.  A sub-normal value counts as the value it is.
+ * Result planes use the GS_TSTAT_* codes and the formulas of gs_time_stats_result with n = span -- GS_TSTAT_MEAN, _VARIANCE,
+ * _MIN, _MAX, _OCCUPANCY; each in f64 with every operation rounded once, converted to f32 at the end.  GS_TSTAT_ARRIVAL has
+ * no meaning across members.  It follows: a bundle's result is bit for bit (the sign and payload of a NaN aside) the time
+ * statistics of a lone Species, or of a one-member ensemble, sampled through the bundle's members' states in ascending order.
+ *   gs_members_bundle_stats  which[0 .. n): n distinct result codes, n in 1..5.  Result which[i] of bundle b is written into
+ *                            member out_first + b of out[i]: its U plane from the members' U, its V plane from their V.
+ *                            It is written as gs_members_copy writes a member: into the newest slot, and an inactive member
+ *                            of out[i] is mirrored into its other slot before out[i]'s next run.  Active flags, step counts,
+ *                            parameters and noise of out[i] are untouched, and its other members keep their bits: out[i] is
+ *                            an ordinary ensemble for every observable above.  thresholds[2] / above[2] are U's and V's;
+ *                            they are needed with GS_TSTAT_OCCUPANCY and ignored (may be null) without it.  Members are
+ *                            read from the newest slot whether active or retired, as the time statistics read them.
+ * The call waits for enqueued work as the other member observables do, blocks, and has no side effects on the tuner, the
+ * graphs or gs_stats.  count == 0: GS_OK, nothing is written.
+ * GS_ERR_INVALID, decided in this order before anything is launched: a null argument; span == 0, or count no multiple of
+ * span; members outside `e`; n outside 1..5; an unknown or repeated code, or GS_TSTAT_ARRIVAL; the occupancy without
+ * thresholds, or a NaN threshold; an out[i] that is null, `e` itself, named twice, of another context or shape, or with
+ * fewer than out_first + count / span members.  A context that refuses ensembles: that context's own error
+ * (GS_ERR_UNSUPPORTED).
+ * Not done: bundles of members that are not consecutive; weights per member; a bundle's accumulators for the caller; medians
+ * and other quantiles.  One bundle of tiny members with a huge span is one lane per four cells by contract, and is slow: the
+ * parallelism is cells x bundles, never the span. */
+int32_t gs_members_bundle_stats(gs_ctx *ctx, gs_ensemble *e, uint64_t first, uint64_t count, uint64_t span, const int32_t *which,
+                                int32_t n, const float thresholds[2], const int32_t above[2], gs_ensemble *const *out,
+                                uint64_t out_first);
+
 /* Measurement hook, not for bindings (tools/rccl_under_load.py): the ghost-row exchange's transport on ONE GPU while the
  * caller keeps the chip busy or idle.  mode 0: a one-rank RCCL communicator, `messages` ncclSend / ncclRecv pairs of
  * `floats` f32 to itself in one group; mode 1: the same bytes as device-to-device copies (the in-process chain's route);

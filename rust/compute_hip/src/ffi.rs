@@ -450,4 +450,20 @@ extern "C" {
     pub fn gs_members_time_stats_accumulate(ctx: *mut gs_ctx, ts: *mut gs_time_stats, e: *mut gs_ensemble, stamp: u32) -> i32;
     /// `host[count, rows, cols]`: result plane `which` of species `species` of every member.
     pub fn gs_members_time_stats_result(ctx: *mut gs_ctx, ts: *mut gs_time_stats, species: i32, which: i32, host: *mut f32) -> i32;
+    /// Per-cell statistics across members: every run of `span` members of `[first, first + count)` is a bundle, and result
+    /// `which[i]` (`GS_TSTAT_MEAN` .. `GS_TSTAT_OCCUPANCY`) of bundle `b` is written into member `out_first + b` of `out[i]`.
+    /// `thresholds[2]` / `above[2]` (U's, V's) are needed with the occupancy and may be null without it.
+    pub fn gs_members_bundle_stats(
+        ctx: *mut gs_ctx,
+        e: *mut gs_ensemble,
+        first: u64,
+        count: u64,
+        span: u64,
+        which: *const i32,
+        n: i32,
+        thresholds: *const f32,
+        above: *const i32,
+        out: *const *mut gs_ensemble,
+        out_first: u64,
+    ) -> i32;
 }
