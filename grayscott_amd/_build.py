@@ -1,6 +1,7 @@
 """In-tree build of ``libgs_hip.so`` with hipcc for gfx950 (no cmake, no JIT cache).
 
-The step kernels are compiled twice from one source (``gs_step_kernels.hip``):
+The step kernels are five sources (``gs_step_kernels.hip`` and ``gs_step_{op,map,mask,noise}.hip``), each compiled once
+per arithmetic flavour (the ``.op`` unit: strict only), nine objects in all:
 
 * strict: ``-DGS_MATH_FUSED=0`` with f32 denormal mode "flush results, keep inputs"
   (``-fdenormal-fp-math-f32=preserve-sign,ieee`` -> ``.amdhsa_float_denorm_mode_32 1``),
@@ -37,17 +38,17 @@ UNITS = [
     # (source, object, extra flags)
     ("gs_step_kernels.hip", "gs_step_strict.o", STRICT + KERNEL_FLAGS),
     # the parameter-specialised strict variants: their own translation unit, compiled in parallel
-    ("gs_step_kernels.hip", "gs_step_strict_op.o", STRICT + ["-DGS_TB_OP_ONLY=1"] + KERNEL_FLAGS),
+    ("gs_step_op.hip", "gs_step_strict_op.o", STRICT + KERNEL_FLAGS),
     ("gs_step_kernels.hip", "gs_step_fused.o", ["-DGS_MATH_FUSED=1"] + KERNEL_FLAGS),
     # the parameter map's forms of the marching kernel (gs_step_tb_mk), one translation unit per flavour
-    ("gs_step_kernels.hip", "gs_step_strict_map.o", STRICT + ["-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
-    ("gs_step_kernels.hip", "gs_step_fused_map.o", ["-DGS_MATH_FUSED=1", "-DGS_TB_MAP_ONLY=1"] + KERNEL_FLAGS),
+    ("gs_step_map.hip", "gs_step_strict_map.o", STRICT + KERNEL_FLAGS),
+    ("gs_step_map.hip", "gs_step_fused_map.o", ["-DGS_MATH_FUSED=1"] + KERNEL_FLAGS),
     # the domain mask's forms of the marching kernel (gs_step_tb_wk), likewise
-    ("gs_step_kernels.hip", "gs_step_strict_mask.o", STRICT + ["-DGS_TB_MASK_ONLY=1"] + KERNEL_FLAGS),
-    ("gs_step_kernels.hip", "gs_step_fused_mask.o", ["-DGS_MATH_FUSED=1", "-DGS_TB_MASK_ONLY=1"] + KERNEL_FLAGS),
-    # the noise forms of the marching kernel (gs_step_tb_zk), likewise
-    ("gs_step_kernels.hip", "gs_step_strict_noise.o", STRICT + ["-DGS_NOISE_ONLY=1"] + KERNEL_FLAGS),
-    ("gs_step_kernels.hip", "gs_step_fused_noise.o", ["-DGS_MATH_FUSED=1", "-DGS_NOISE_ONLY=1"] + KERNEL_FLAGS),
+    ("gs_step_mask.hip", "gs_step_strict_mask.o", STRICT + KERNEL_FLAGS),
+    ("gs_step_mask.hip", "gs_step_fused_mask.o", ["-DGS_MATH_FUSED=1"] + KERNEL_FLAGS),
+    # the noise forms of the marching kernel (gs_step_tb_zk) and of the ensemble kernels, likewise
+    ("gs_step_noise.hip", "gs_step_strict_noise.o", STRICT + KERNEL_FLAGS),
+    ("gs_step_noise.hip", "gs_step_fused_noise.o", ["-DGS_MATH_FUSED=1"] + KERNEL_FLAGS),
     ("gs_util_kernels.hip", "gs_util.o", []),
     # summaries of planes (row records, the ensembles' fold): hipcc's default float mode, sub-normal cells kept
     ("gs_summary.hip", "gs_summary_k.o", []),
@@ -109,6 +110,8 @@ UNITS = [
     ("gs_observe.cpp", "gs_observe.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_time_stats.cpp", "gs_time_stats.o", ["-x", "hip", "-fvisibility=hidden"]),
     ("gs_bundle_stats.cpp", "gs_bundle_stats.o", ["-x", "hip", "-fvisibility=hidden"]),
+    # the opt-in table for more than 64 KB of dynamic LDS, shared by the step kernels' launchers
+    ("gs_dyn_lds.cpp", "gs_dyn_lds.o", ["-x", "hip", "-fvisibility=hidden"]),
 ]
 
 

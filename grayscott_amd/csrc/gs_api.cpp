@@ -194,6 +194,7 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
     if (fuse > 1 && kernel != GS_KERNEL_TB)
         return fail(GS_ERR_UNSUPPORTED, "only the temporally blocked kernel fuses steps");
     const bool fused = ctx->o.math == GS_MATH_FUSED;
+    const GsLaunchers &launch = gs_launchers(ctx->o.math);
     if (at.kind != GS_ATTACH_NONE && kernel == GS_KERNEL_LDS) // (gs_ctx_set_param_map / gs_ctx_set_mask refuse such a context first)
         return fail(GS_ERR_UNSUPPORTED, "the LDS-staged single-step kernel has no %s form",
                     at.kind == GS_ATTACH_MAP ? "parameter-map" : (at.kind == GS_ATTACH_MASK ? "domain-mask" : "noise"));
@@ -218,7 +219,7 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
                 q.edge_launched = 0;
                 if (qr.mode == 1 && qr.words) // words that no unit writes (edge positions under the zero-halo rule) stay "unknown"
                     e = hipMemsetAsync(qr.words, 0, 2 * qr.cap * sizeof(uint32_t), stream);
-                if (e == hipSuccess) e = gs_launch_tb_strict(a, fuse, stream, &name, at, &q);
+                if (e == hipSuccess) e = launch.tb(a, fuse, stream, &name, at, &q);
                 if (e != hipSuccess) break;
                 if (q.need > (int64_t)qr.cap && qr.mode == 1) { // nothing was launched: room for this geometry first
                     if (qr.words) { // another geometry: its edge units' skip counts are kept, its words are not
@@ -251,16 +252,16 @@ int32_t launch_rows(gs_ctx *ctx, const GsStepArgs &a, hipStream_t stream, int fu
             }
             break;
         }
-        e = fused ? gs_launch_tb_fused(a, fuse, stream, &name, at) : gs_launch_tb_strict(a, fuse, stream, &name, at);
+        e = launch.tb(a, fuse, stream, &name, at, nullptr);
         break;
     case GS_KERNEL_SIMPLE:
-        e = fused ? gs_launch_simple_fused(a, stream, &name, at) : gs_launch_simple_strict(a, stream, &name, at);
+        e = launch.simple(a, stream, &name, at);
         break;
     case GS_KERNEL_STREAM:
-        e = fused ? gs_launch_stream_fused(a, stream, &name, at) : gs_launch_stream_strict(a, stream, &name, at);
+        e = launch.stream(a, stream, &name, at);
         break;
     case GS_KERNEL_LDS:
-        e = fused ? gs_launch_lds_fused(a, stream, &name) : gs_launch_lds_strict(a, stream, &name);
+        e = launch.lds(a, stream, &name);
         break;
     default:
         return fail(GS_ERR_UNSUPPORTED, "kernel variant %d is not built", kernel);
@@ -931,8 +932,7 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
             const int n = left > 0x40000000ull ? 0x40000000 : (int)left;
             GsStepArgs a = make_args(ctx, r.u[slot], r.v[slot], r.u[1 - slot], r.v[1 - slot], 0, 1);
             const char *name = nullptr;
-            const hipError_t e = ctx->o.math == GS_MATH_FUSED ? gs_launch_resident_fused(a, n, sl.compute, &name)
-                                                               : gs_launch_resident_strict(a, n, sl.compute, &name);
+            const hipError_t e = gs_launchers(ctx->o.math).resident(a, n, sl.compute, &name);
             if (e != hipSuccess) return fail(GS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
             ctx->last_kernel = name;
             ctx->launches++;
@@ -1001,8 +1001,7 @@ int32_t run_steps(gs_ctx *ctx, gs_field *u0, gs_field *v0, gs_field *u1, gs_fiel
             const int n = left % (uint64_t)kmax ? (int)(left % (uint64_t)kmax) : kmax;
             GsStepArgs a = make_args(ctx, r.u[slot], r.v[slot], r.u[1 - slot], r.v[1 - slot], 0, 1);
             const char *name = nullptr;
-            const hipError_t e = ctx->o.math == GS_MATH_FUSED ? gs_launch_tile_fused(a, n, shape, sl.compute, &name)
-                                                               : gs_launch_tile_strict(a, n, shape, sl.compute, &name);
+            const hipError_t e = gs_launchers(ctx->o.math).tile(a, n, shape, sl.compute, &name);
             if (e != hipSuccess) return fail(GS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
             if (!full_name || n == kmax) full_name = name;
             ctx->launches++;

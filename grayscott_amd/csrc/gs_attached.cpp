@@ -168,11 +168,9 @@ int32_t gs_ctx_set_param_map(gs_ctx *ctx, gs_field *feed, gs_field *kill)
     GS_TRY(ensure_planes(ctx, GS_ATTACH_MAP, feed, 2, "parameter map planes"));
     // F as the caller's plane holds it, F + K one add per float
     gs_field *const *plane = ctx->attached.plane;
-    const bool fused = ctx->o.math == GS_MATH_FUSED;
     GS_TRY(fill_planes(ctx, plane, 2, [&](size_t i, SlabRt &sl, size_t n) -> int32_t {
         GS_TRY(copy_block(plane[0], feed, i, sl, n));
-        const hipError_t e = fused ? gs_launch_map_rates_fused(feed->s[i].alloc, kill->s[i].alloc, plane[1]->s[i].alloc, n, sl.compute)
-                                   : gs_launch_map_rates_strict(feed->s[i].alloc, kill->s[i].alloc, plane[1]->s[i].alloc, n, sl.compute);
+        const hipError_t e = gs_launchers(ctx->o.math).map_rates(feed->s[i].alloc, kill->s[i].alloc, plane[1]->s[i].alloc, n, sl.compute);
         if (e != hipSuccess) return fail(GS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
         return GS_OK;
     }));

@@ -1,7 +1,7 @@
 // gs_cell.h -- the per-cell arithmetic every kernel shares: react (the reaction update), half_diff / zero_minus (single
 // instructions the compiler must not touch), the general and the cheap edge flavours of cell<>, lane-shift helpers.
-// Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED / GS_TB_OP_ONLY and the
-// GS_SUFFIX / GS_TAP macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
+// Part of the gfx950 step kernels: included by every one of their translation units behind gs_step_flavour.h (GS_MATH_FUSED,
+// GS_SUFFIX, GS_TAP), once per arithmetic flavour; not a header to include elsewhere.
 #pragma once
 
 namespace {

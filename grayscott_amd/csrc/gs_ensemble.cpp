@@ -246,7 +246,7 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
     if (steps == 0) return GS_OK;
     SlabRt &sl = ctx->slabs[0];
     GS_HIP(hipSetDevice(sl.device));
-    const bool fused = ctx->o.math == GS_MATH_FUSED;
+    const GsLaunchers &launch = gs_launchers(ctx->o.math);
     GsEnsArgs a;
     std::memset(&a, 0, sizeof a);
     a.params = e->params;
@@ -255,23 +255,23 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
     a.rows = (int32_t)e->rows;
     a.cols = (int32_t)e->cols;
     a.zero_halo = ctx->o.boundary; // gs_boundary: 0, 1, 2 or 3 (gs_ctx_create admits no other value)
-    // With an active set: the members that run, through the listed launchers and the list of their indices (GsEnsArgs::first
+    // With an active set: the members that run, through the launchers' listed forms and the list of their indices (GsEnsArgs::first
     // is then a position in the list); with every member active, today's launchers exactly.
     const bool listed = !e->all_active();
     const uint64_t running = listed ? e->active_count : e->members;
     if (running == 0) return GS_OK; // nobody advances: no launch, no flip
     if (listed) GS_TRY(mirror_stale(e, sl));
-    const uint32_t *list = e->active_list;
+    const uint32_t *list = listed ? e->active_list : nullptr; // (allocated before a member can be inactive)
     // With noise attached: the noise forms, one per kernel whether or not a list is in use (GsEnsNoiseArgs::list).
     const bool noisy = !e->noise.empty();
-    GsEnsNoiseArgs z{e->noise_table, listed ? list : nullptr, 0};
+    GsEnsNoiseArgs z{e->noise_table, list, 0};
     // The launchers split at kGsEnsMaxGroups workgroups; a `members` above 2^31 goes in slices here.
-    auto for_slices = [&](auto &&launch) -> int32_t {
+    auto for_slices = [&](auto &&launch_slice) -> int32_t {
         for (uint64_t m0 = 0; m0 < running; m0 += 0x40000000ull) {
             GsEnsArgs s = a;
             s.first = (int64_t)m0;
             s.members = (int32_t)std::min<uint64_t>(running - m0, 0x40000000ull);
-            const hipError_t err = launch(s);
+            const hipError_t err = launch_slice(s);
             if (err != hipSuccess) return fail(GS_ERR_HIP, "ensemble kernel launch failed: %s", hipGetErrorString(err));
         }
         return GS_OK;
@@ -293,14 +293,8 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
             a.out_v = e->v[e->cur ^ 1];
             z.step0 = e->run_steps;
             GS_TRY(for_slices([&](const GsEnsArgs &s) {
-                if (noisy)
-                    return fused ? gs_launch_ens_resident_noise_fused(s, z, n, e->fast, sl.compute, &name)
-                                 : gs_launch_ens_resident_noise_strict(s, z, n, e->fast, sl.compute, &name);
-                if (listed)
-                    return fused ? gs_launch_ens_resident_listed_fused(s, list, n, e->fast, sl.compute, &name)
-                                 : gs_launch_ens_resident_listed_strict(s, list, n, e->fast, sl.compute, &name);
-                return fused ? gs_launch_ens_resident_fused(s, n, e->fast, sl.compute, &name)
-                             : gs_launch_ens_resident_strict(s, n, e->fast, sl.compute, &name);
+                return noisy ? launch.ens_resident_noise(s, z, n, e->fast, sl.compute, &name)
+                             : launch.ens_resident(s, list, n, e->fast, sl.compute, &name);
             }));
             ctx->last_kernel = name;
             ctx->launches++;
@@ -324,14 +318,8 @@ int32_t gs_ensemble_run(gs_ctx *ctx, gs_ensemble *e, uint64_t steps)
         a.out_v = e->v[e->cur ^ 1];
         z.step0 = e->run_steps;
         GS_TRY(for_slices([&](const GsEnsArgs &s) {
-            if (noisy)
-                return fused ? gs_launch_ens_tile_noise_fused(s, z, n, shape, e->fast, sl.compute, &name)
-                             : gs_launch_ens_tile_noise_strict(s, z, n, shape, e->fast, sl.compute, &name);
-            if (listed)
-                return fused ? gs_launch_ens_tile_listed_fused(s, list, n, shape, e->fast, sl.compute, &name)
-                             : gs_launch_ens_tile_listed_strict(s, list, n, shape, e->fast, sl.compute, &name);
-            return fused ? gs_launch_ens_tile_fused(s, n, shape, e->fast, sl.compute, &name)
-                         : gs_launch_ens_tile_strict(s, n, shape, e->fast, sl.compute, &name);
+            return noisy ? launch.ens_tile_noise(s, z, n, shape, e->fast, sl.compute, &name)
+                         : launch.ens_tile(s, list, n, shape, e->fast, sl.compute, &name);
         }));
         if (!full_name || n == kmax) full_name = name;
         ctx->launches++;

@@ -22,10 +22,11 @@
 // under the periodic rule at the wrapped one, with the key of the member's own step: the member's seed, sigmas and step
 // offset come from a second device table (GsEnsNoise, one s_load_dwordx8), the key is formed on the device once per step
 // from wave-uniform words (noise_key_uniform).  The second argument, GsEnsNoiseArgs, carries a nullable list of active
-// members: one form serves ensembles with and without an active set.  Built in the noise translation units (GS_NOISE_ONLY)
+// members: one form serves ensembles with and without an active set.  Built in the noise translation units (gs_step_noise.hip)
 // only: the other objects hold none of them.
-// Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED and the GS_SUFFIX / GS_TAP
-// macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
+// Part of the gfx950 step kernels: included by gs_step_kernels.hip (the plain and listed forms) and gs_step_noise.hip (the
+// noise forms) behind gs_step_flavour.h (GS_MATH_FUSED, GS_SUFFIX, GS_TAP) and gs_lds_resident.h, once per arithmetic
+// flavour; the launchers' shared bodies are in gs_ens_launch.h.  Not a header to include elsewhere.
 #pragma once
 
 namespace {

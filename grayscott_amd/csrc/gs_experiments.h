@@ -7,6 +7,8 @@
 // (2) Run-time GS_HIP_* environment switches read by the launchers (A/B timing of launch policies, traces).
 //     They never change results -- every combination is bit-identical and covered by the GPU parity suite --
 //     and are documented for users in include/gs_hip.h ("Environment").
+// Besides the switches, part (1) holds what a GS_TB_TRACE build needs beside its buffer: the stamp macros and the body of the
+// host-side readers (gs_trace_read).
 #pragma once
 #include <cstdlib>
 
@@ -38,6 +40,19 @@ __device__ __forceinline__ unsigned long long trace_now()
 #define GS_TRACE_AT(COND, SLOT) do { if (COND) ts[SLOT] = trace_now(); } while (0)
 #define GS_TRACE_PARAM , unsigned long long (&ts)[5] /* tb_march's extra parameter ... */
 #define GS_TRACE_ARG , ts                            /* ... and what gs_step_tb_k passes for it */
+// Copies the trace buffer of THIS translation unit's kernels out: the body of gs_debug_trace_read_<flavour> (the main unit)
+// and gs_debug_trace_read_op (gs_step_op.hip).
+static inline int32_t gs_trace_read(unsigned long long *dst, int32_t units, int32_t clear)
+{
+    if (units > kTraceUnits) units = kTraceUnits;
+    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(gs_trace_buf), (size_t)units * kTraceWords * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (clear) {
+        void *p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(gs_trace_buf)) != hipSuccess) return -1;
+        if (hipMemset(p, 0, (size_t)units * kTraceWords * sizeof(unsigned long long)) != hipSuccess) return -1;
+    }
+    return 0;
+}
 #else
 #define GS_TRACE_AT(COND, SLOT) do { } while (0)
 #define GS_TRACE_PARAM

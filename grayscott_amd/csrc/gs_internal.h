@@ -18,6 +18,7 @@
 //                  (gs_fields_compare, gs_members_compare) and the device copies behind snapshots (gs_fields_copy, gs_members_copy)
 //   gs_time_stats.cpp time statistics: per-cell accumulators over the samples of a run, kept on the device (gs_time_stats_*,
 //                  gs_members_time_stats_*)
+//   gs_dyn_lds.cpp the step kernels' launchers' opt-in table for more than 64 KB of dynamic LDS (gs_kernels.h: gs_ensure_dyn_lds)
 //   (reduced result images -- gs_field_download_reduced and kin -- live in gs_fields.cpp beside the full-size downloads)
 #pragma once
 // (the host-side translation units are compiled with -fvisibility=hidden: only the C ABI leaves the library)

@@ -1,5 +1,5 @@
 // gs_kernels.h -- host/device contract between the host side (gs_api.cpp, gs_tuner.cpp, gs_window.cpp, gs_fields.cpp,
-// gs_attached.cpp) and the gfx950 kernels.
+// gs_attached.cpp, gs_ensemble.cpp, gs_dyn_lds.cpp) and the gfx950 kernels.
 //
 // One "plane" is a row-major f32 array of one species in one slot for one row slab:
 //   element (r, c) of the slab, r in [-ghost, rows + ghost) (rows outside [0, rows) = ghost rows),
@@ -207,7 +207,7 @@ struct GsEnsArgs {
     float *out_u, *out_v;
     const GsEnsParams *params; // members entries (device)
     int64_t first;             // member of workgroup 0 of this launch (launches are split at kGsEnsMaxGroups); the listed
-                               // forms (gs_launch_ens_*_listed_*): its position in the list of active members
+                               // forms (a launch with a `list`): its position in the list of active members
     int32_t members;           // members in this launch
     int32_t rows, cols;
     int32_t zero_halo;         // gs_boundary: 0 clipped, 1 zero halo, 2 periodic, 3 zero flux
@@ -231,46 +231,45 @@ struct GsEnsNoiseArgs {
     uint64_t step0;
 };
 
-// Launchers, one set per arithmetic flavour (see gs_math in include/gs_hip.h).  Each
-// returns the hipError_t of the launch.  `name` receives a static kernel-variant label.  `at` (simple, stream and
-// marching kernels): the slab's attachment -- the launch then runs the kernel set of its kind.
-#define GS_DECLARE_LAUNCHERS(SUFFIX)                                                           \
-    hipError_t gs_launch_simple_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
-    hipError_t gs_launch_stream_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at = GsAttached()); \
-    hipError_t gs_launch_resident_##SUFFIX(const GsStepArgs &a, int steps, hipStream_t s, const char **name); \
-    hipError_t gs_launch_tb_##SUFFIX(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at = GsAttached(), GsQuiet *quiet = nullptr); \
-    hipError_t gs_launch_tile_##SUFFIX(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name); \
-    hipError_t gs_launch_lds_##SUFFIX(const GsStepArgs &a, hipStream_t s, const char **name);  \
-    hipError_t gs_launch_window_##SUFFIX(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name); \
-    int gs_tb_wave_slots_##SUFFIX(int k, int fast, int cpl, int boundary, int kind = GS_ATTACH_NONE); \
-    hipError_t gs_launch_map_rates_##SUFFIX(const float *feed, const float *kill, float *fpk, size_t n, hipStream_t s); \
-    const void *gs_tb_map_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                                \
-    const void *gs_tb_mask_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                               \
-    const void *gs_tb_noise_kernel_##SUFFIX(int k, int fast, int cpl, int rule);                              \
-    hipError_t gs_launch_ens_resident_##SUFFIX(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name); \
-    hipError_t gs_launch_ens_tile_##SUFFIX(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name); \
-    hipError_t gs_launch_ens_resident_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name); \
-    hipError_t gs_launch_ens_tile_listed_##SUFFIX(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name); \
-    hipError_t gs_launch_ens_resident_noise_##SUFFIX(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int steps, int fast, hipStream_t s, const char **name); \
-    hipError_t gs_launch_ens_tile_noise_##SUFFIX(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int k, int shape, int fast, hipStream_t s, const char **name);
-
-GS_DECLARE_LAUNCHERS(strict)
-GS_DECLARE_LAUNCHERS(fused)
+// Launchers, one table per arithmetic flavour (gs_math in include/gs_hip.h), defined by the step kernels' main unit
+// (gs_step_kernels.hip).  Each launcher returns the hipError_t of the launch.  `name` receives a static kernel-variant
+// label.  `at` (simple, stream and marching kernels): the slab's attachment -- the launch then runs the kernel set of its
+// kind.  `quiet`: GsQuiet, or nullptr.  `list` (ensembles): the device list of the active members' indices, or nullptr when
+// every member runs.  map_rates: fpk[i] = feed[i] + kill[i] over n floats, one f32 add in the flavour's float mode (strict: a
+// sub-normal sum is flushed, as the reference's DenormalsFlusher does).
+struct GsLaunchers {
+    hipError_t (*simple)(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at);
+    hipError_t (*stream)(const GsStepArgs &a, hipStream_t s, const char **name, const GsAttached &at);
+    hipError_t (*resident)(const GsStepArgs &a, int steps, hipStream_t s, const char **name);
+    hipError_t (*tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at, GsQuiet *quiet);
+    hipError_t (*tile)(const GsStepArgs &a, int k, int shape, hipStream_t s, const char **name);
+    hipError_t (*lds)(const GsStepArgs &a, hipStream_t s, const char **name);
+    hipError_t (*window)(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name);
+    int (*tb_wave_slots)(int k, int fast, int cpl, int boundary, int kind);
+    hipError_t (*map_rates)(const float *feed, const float *kill, float *fpk, size_t n, hipStream_t s);
+    hipError_t (*ens_resident)(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name);
+    hipError_t (*ens_tile)(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name);
+    hipError_t (*ens_resident_noise)(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int steps, int fast, hipStream_t s, const char **name);
+    hipError_t (*ens_tile_noise)(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int k, int shape, int fast, hipStream_t s, const char **name);
+};
+extern const GsLaunchers gs_launchers_strict, gs_launchers_fused;
+// The launchers of flavour `math` (gs_math: GS_MATH_FUSED = 1, else strict).
+inline const GsLaunchers &gs_launchers(int math) { return math == 1 ? gs_launchers_fused : gs_launchers_strict; }
 
 // Entry points of the parameter-specialised temporal-blocking kernels (strict flavour only; their
-// own translation unit, see gs_step_kernels.hip: GS_TB_OP_ONLY).  nullptr for an unknown variant.
+// own translation unit, gs_step_op.hip).  nullptr for an unknown variant.
 // wg: waves per workgroup, 4 or 16 (the fair-progress form of one-round launches: K = 4, cpl 1 or 2 only);
 // rule: the kernel set of the boundary rule, 0 = the clipped and zero-halo rules' kernels, 1 = the periodic rule's
 // (gs_step_tb_pk and kin), 2 = the zero-flux rule's (gs_step_tb_nk and kin).
 const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule = 0);
 // ... and of the quiet entries (gs_step_tb_dx_qk: GsQuiet) for k = 2, 3, 4 fused steps; nullptr otherwise.
 const void *gs_tb_quiet_kernel_strict(int k);
-// gs_launch_map_rates_*: fpk[i] = feed[i] + kill[i] over n floats, one f32 add in the flavour's float mode (strict: a
-// sub-normal sum is flushed, as the reference's DenormalsFlusher does).  gs_tb_map_kernel_*: the entry of the marching
-// kernel's map form (gs_step_tb_mk: its own translation unit, GS_TB_MAP_ONLY) for k fused steps, fast in {0, 3} (3: the
-// .op variant, strict only), cpl columns per lane and rule = rule_set(boundary); nullptr for a form that is not built.
-// gs_tb_mask_kernel_*: the same for the domain mask's forms (gs_step_tb_wk, GS_TB_MASK_ONLY), gs_tb_noise_kernel_*: for the
-// noise forms (gs_step_tb_zk, GS_NOISE_ONLY).
+// (The map, mask and noise units' entry queries, gs_tb_{map,mask,noise}_kernel_<flavour>, are declared per flavour in
+// gs_step_flavour.h.)
+
+// Opt-in for more than 64 KB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize) of kernel entry `fn` on the current
+// device, made once per (device, function) and size: what every launcher with dynamic LDS calls first (gs_dyn_lds.cpp).
+hipError_t gs_ensure_dyn_lds(const void *fn, size_t bytes);
 
 // Plane utilities (math-agnostic, defined once in gs_util_kernels.hip).
 hipError_t gs_launch_colormap(const float *row0, int32_t pitch, int32_t rows, int32_t cols, float scale,

@@ -1,7 +1,8 @@
 // gs_lds_resident.h -- small and mid-size grids: the whole run in one launch with the grid resident in LDS
 // (gs_run_resident_k), and up to 8 steps per launch on LDS-resident windows (gs_run_tile_k).
-// Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED / GS_TB_OP_ONLY and the
-// GS_SUFFIX / GS_TAP macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
+// Part of the gfx950 step kernels: included by gs_step_kernels.hip and, for the ensemble kernels' noise forms, by
+// gs_step_noise.hip, behind gs_step_flavour.h (GS_MATH_FUSED, GS_SUFFIX, GS_TAP) and gs_cell.h, once per arithmetic flavour;
+// not a header to include elsewhere.
 #pragma once
 
 namespace {

@@ -1,7 +1,8 @@
 // gs_march.h -- the production kernel of gs_run: temporal blocking, K <= 4 time steps per launch, K register-resident
 // time levels per wave; the variant with full difference sharing and the halo board in LDS memory; 4- and 16-wave forms.
-// Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED / GS_TB_OP_ONLY and the
-// GS_SUFFIX / GS_TAP macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
+// Part of the gfx950 step kernels: included by every one of their translation units behind gs_step_flavour.h (GS_MATH_FUSED,
+// GS_SUFFIX, GS_TAP) and gs_cell.h, once per arithmetic flavour -- each instantiates its own forms; not a header to include
+// elsewhere.
 #pragma once
 
 namespace {

@@ -1,7 +1,7 @@
 // gs_single_step.h -- one step per launch: the one-thread-per-cell cross-check kernel, the streaming kernel of gs_step
 // (HBM-bound: the leg north_star asks the rocprof evidence for) and the LDS-staged alternative.
-// Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED / GS_TB_OP_ONLY and the
-// GS_SUFFIX / GS_TAP macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
+// Part of the gfx950 step kernels: included by their main unit, gs_step_kernels.hip, behind gs_step_flavour.h (GS_MATH_FUSED,
+// GS_SUFFIX, GS_TAP) and gs_cell.h, once per arithmetic flavour; not a header to include elsewhere.
 #pragma once
 
 namespace {

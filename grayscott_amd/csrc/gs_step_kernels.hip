@@ -1,18 +1,15 @@
-// gs_step_kernels.hip -- gfx950 (CDNA4, wave64) kernels for the Gray-Scott time step.
+// gs_step_kernels.hip -- gfx950 (CDNA4, wave64) kernels for the Gray-Scott time step: the main translation unit of the step
+// kernels (gs_step_flavour.h lists the others) -- the simple, streaming, resident, tile, window, LDS-staged and marching
+// kernels' general variants, the ensemble kernels' plain and listed forms, and the launchers of all step kernels but the
+// ensembles' noise forms (gs_step_noise.hip), handed to the host side as one table per flavour (gs_kernels.h: GsLaunchers).
 //
 // Arithmetic spec: compute_naive::Simulation::perform_step,
-// /root/reference/compute/naive/src/lib.rs:42-83 -- for every cell, a row-major fold
+// compute/naive/src/lib.rs:42-83 -- for every cell, a row-major fold
 //     acc = acc + w[i][j] * (elem - centre)
 // over the 3x3 window CLIPPED to the grid, weights indexed from the window's top-left
 // corner (:57-71), then the reaction update (:74-79).  Each reference operation is one
-// rounded f32 operation here, in the same order; this file is compiled with
-// -ffp-contract=off so the compiler never fuses.  It is compiled twice:
-//   GS_MATH_FUSED=0 ("strict"): taps are sub, mul, add; f32 denormal mode = flush results,
-//       keep inputs (-fdenormal-fp-math-f32=preserve-sign,ieee -> FP_DENORM 1), which is
-//       MXCSR.FTZ without DAZ, i.e. the reference's DenormalsFlusher
-//       (compute/shared/src/lib.rs:161-180).
-//   GS_MATH_FUSED=1 ("fused"):  taps are sub, fma; denormals kept.  Exact for weights that
-//       are 0 or a power of two whenever the product is a normal number.
+// rounded f32 operation here, in the same order; the step kernels' units are compiled with
+// -ffp-contract=off so the compiler never fuses, each once per arithmetic flavour (gs_step_flavour.h: GS_MATH_FUSED).
 //
 // Facts the kernels rely on (derived from the spec, checked by tests/test_oracle_kat.py):
 //   * the centre tap contributes w * (u - u) = +0 and acc is never -0, so it is skipped;
@@ -44,166 +41,44 @@
 //       streaming and marching kernels, one instance per kernel set of a boundary rule (RULE = rule_set()): the reaction
 //       takes F[r, c] and F[r, c] + K[r, c] of the cell it updates (react's map form); the Laplacian is the rule's own.  The
 //       marching kernel's map forms (K = 1..4, 1, 2 and 4 columns per lane, the general variant and, strict only, .op) are
-//       built in a translation unit of their own (GS_TB_MAP_ONLY).  The difference-sharing, fair-progress, tile, resident,
+//       built in a translation unit of their own (gs_step_map.hip).  The difference-sharing, fair-progress, tile, resident,
 //       window, LDS-staged and ensemble kernels have none.
 //   ..._wk<..., RULE>  the domain mask's forms (second argument GsMaskPlanes, gs_ctx_set_mask) of the same three kernels:
 //       every cell through cell_masked (a tap that reads a wall reads the cell's own value; a wall keeps its input), from
 //       the link words formed at attach time.  The marching forms, the same set as the map's, are built in a translation
-//       unit of their own (GS_TB_MASK_ONLY).  No difference sharing: a wall breaks it.
+//       unit of their own (gs_step_mask.hip).  No difference sharing: a wall breaks it.
 //   ..._zk<..., RULE>  the noise forms (second argument GsNoiseArgs, gs_ctx_set_noise) of the same three kernels: the
 //       reference cell, then react_noise (gs_cell.h) -- a Philox2x32-10 draw at the cell's global (row, column) with the key
 //       of the level's step, one multiply and one add per species.  The marching forms, the same set as the map's, are built
-//       in a translation unit of their own (GS_NOISE_ONLY).  No difference sharing, no units at rest.
+//       in a translation unit of their own (gs_step_noise.hip).  No difference sharing, no units at rest.
 //   gs_ens_resident_z*, gs_ens_tile_z*  the noise forms of the two ensemble kernels (second argument GsEnsNoiseArgs,
 //       gs_members_set_noise; gs_ensemble.h): a seed, sigmas and a step counter per member, the step key formed on the
 //       device.  Built in the noise translation units too, with their launchers (gs_launch_ens_*_noise_*).
 //
-// This file sets the flavour macros, includes the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h (gs_step_tb_k and
-// its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged), gs_lds_resident.h (resident
-// and LDS-window kernels), gs_window_kernel.h (the persistent window kernel) -- and holds their launchers.  The launchers
-// of the simple, streaming and marching kernels take the slab's attachment (GsAttached: none, a parameter map or a domain
-// mask), index one table of names and one of entries by its kind, and hand its planes on as the kernel's second argument.
-// Build-time switches of A/B and diagnostic builds (none is set in the shipped build) and the run-time
-// GS_HIP_* switches of the launchers live in gs_experiments.h.
-#include "gs_kernels.h"
-#include "gs_experiments.h"
+// This file includes the flavour macros (gs_step_flavour.h) and the kernels -- gs_cell.h (per-cell arithmetic), gs_march.h
+// (gs_step_tb_k and its variant with full difference sharing), gs_single_step.h (simple / stream / LDS-staged),
+// gs_lds_resident.h (resident and LDS-window kernels), gs_window_kernel.h (the persistent window kernel) -- and holds their
+// launchers.  The launchers of the simple, streaming and marching kernels take the slab's attachment (GsAttached: none, a
+// parameter map, a domain mask or noise), index one table of names and one of entries by its kind, and hand its planes on
+// as the kernel's second argument.  Build-time switches of diagnostic builds (none is set in the shipped build) and the
+// run-time GS_HIP_* switches of the launchers live in gs_experiments.h.
+#include "gs_step_flavour.h"
 #include <cstdio>
-#include <cstdlib>
 #include <mutex>
-
-#ifndef GS_MATH_FUSED
-#error "compile with -DGS_MATH_FUSED=0 or 1"
-#endif
-// GS_TB_OP_ONLY=1: this translation unit provides nothing but the parameter-specialised (".op")
-// instances of gs_step_tb_k and of its periodic form, through gs_tb_op_kernel_strict() (built apart from the
-// rest so that the translation units compile in parallel; grayscott_amd/_build.py).
-#ifndef GS_TB_OP_ONLY
-#define GS_TB_OP_ONLY 0
-#endif
-#if GS_TB_OP_ONLY && GS_MATH_FUSED
-#error "the fused build has no specialised variants"
-#endif
-// GS_TB_MAP_ONLY=1: this translation unit provides nothing but the parameter map's forms of gs_step_tb_k
-// (gs_step_tb_mk), through gs_tb_map_kernel_<flavour>(), in either flavour.
-#ifndef GS_TB_MAP_ONLY
-#define GS_TB_MAP_ONLY 0
-#endif
-#if GS_TB_OP_ONLY && GS_TB_MAP_ONLY
-#error "GS_TB_OP_ONLY and GS_TB_MAP_ONLY are translation units of their own"
-#endif
-// GS_TB_MASK_ONLY=1: ... and the domain mask's forms (gs_step_tb_wk), through gs_tb_mask_kernel_<flavour>().
-#ifndef GS_TB_MASK_ONLY
-#define GS_TB_MASK_ONLY 0
-#endif
-#if GS_TB_MASK_ONLY && (GS_TB_OP_ONLY || GS_TB_MAP_ONLY)
-#error "GS_TB_MASK_ONLY is a translation unit of its own"
-#endif
-
-#if GS_MATH_FUSED
-#define GS_SUFFIX(x) x##_fused
-#define GS_TAP(acc, w, s, c) (acc) = __builtin_fmaf((w), (s) - (c), (acc))
-#define GS_MATH_NAME "fused"
-#else
-#define GS_SUFFIX(x) x##_strict
-#define GS_TAP(acc, w, s, c) (acc) = (acc) + (w) * ((s) - (c))
-#define GS_MATH_NAME "strict"
-#endif
-
-// GS_NOISE_ONLY=1: ... and the noise forms (gs_step_tb_zk), through gs_tb_noise_kernel_<flavour>().
-#ifndef GS_NOISE_ONLY
-#define GS_NOISE_ONLY 0
-#endif
-#if GS_NOISE_ONLY && (GS_TB_OP_ONLY || GS_TB_MAP_ONLY || GS_TB_MASK_ONLY)
-#error "GS_NOISE_ONLY is a translation unit of its own"
-#endif
 
 #include "gs_cell.h"
 #include "gs_march.h"
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 #include "gs_single_step.h"
 #include "gs_lds_resident.h"
 #include "gs_ensemble.h"
 #include "gs_window_kernel.h"
-#endif
-#if GS_NOISE_ONLY
-// ... and the noise forms of the ensemble kernels (gs_ens_resident_z*, gs_ens_tile_z*: gs_ensemble.h), whose launchers are
-// below; nothing else of the two headers is instantiated here.
-#include "gs_lds_resident.h"
-#include "gs_ensemble.h"
-#endif
+#include "gs_ens_launch.h"
 
-// Launch tables.  GS_FN: the entry of a kernel instance.  kOp: the FAST argument of the ".op" variant (the fused build
-// has none: its launchers reduce `fast` to 0).  GS_NAME: the name a launcher reports for kernel family BASE, variant V
-// ("", ".op", ...) under the boundary rule of suffix R; GS_RULES: a table of such names per kernel set of a rule ("" for
-// the clipped and zero-halo rules, which share their kernels, then "/periodic" and "/neumann") from one macro M(BASE, R),
-// indexed by rule_set().
-#define GS_FN(KER, ...) reinterpret_cast<const void *>(&GS_SUFFIX(KER)<__VA_ARGS__>)
-[[maybe_unused]] constexpr int kOp = GS_MATH_FUSED ? 0 : 3;
-#define GS_NAME(BASE, V, R) BASE "/" GS_MATH_NAME V R
-#define GS_RULES_OF(M, BASE, A) {M(BASE, A), M(BASE, "/periodic" A), M(BASE, "/neumann" A)}
-#define GS_RULES(M, BASE) GS_RULES_OF(M, BASE, "")
-// The kernel set of boundary rule `boundary` (gs_boundary): 0 = the clipped and zero-halo rules' kernels (*_k), 1 = the
-// periodic rule's (*_pk), 2 = the zero-flux rule's (*_nk).
-static inline int rule_set(int boundary) { return boundary == 2 ? 1 : (boundary == 3 ? 2 : 0); }
-
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
-// (the kernels' own translation unit and the noise forms': both launch kernels with dynamic LDS)
-// Opt-in for more than 64 KB of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize).  The attribute
-// belongs to the device function ON THE CURRENT DEVICE, so what has been set is remembered per (device,
-// function): a process that drives several GPUs (device_ids = 0, 1, ...; two contexts) opts in on each.
-// Contexts on different threads launch through here: the table has a lock, like tb_waves_of's.
-static bool dyn_lds_seen(int device, const void *fn, int bytes, bool record)
-{
-    struct Entry { int device; const void *fn; int bytes; };
-    static Entry table[256];
-    static int n = 0;
-    static std::mutex lock;
-    std::lock_guard<std::mutex> guard(lock);
-    for (int i = 0; i < n; ++i)
-        if (table[i].device == device && table[i].fn == fn) {
-            if (table[i].bytes >= bytes) return true;
-            if (record) table[i].bytes = bytes;
-            return false;
-        }
-    if (record && n < 256) table[n++] = Entry{device, fn, bytes};
-    return false;
-}
-static hipError_t ensure_dyn_lds(const void *fn, size_t bytes)
-{
-    if (bytes <= 64 * 1024) return hipSuccess;
-    int device = 0;
-    hipError_t e = hipGetDevice(&device);
-    if (e != hipSuccess) return e;
-    if (dyn_lds_seen(device, fn, (int)bytes, false)) return hipSuccess;
-    e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) (void)dyn_lds_seen(device, fn, (int)bytes, true);
-    return e;
-}
-// What the table above keys on, for the unit test of the key (tests/test_capi_cpu.py): 1 when (device, fn
-// slot, bytes) is new, and it is recorded; 0 when a launch on that device would skip the call.
-#if !GS_MATH_FUSED && !GS_NOISE_ONLY
-extern "C" int32_t gs_debug_dyn_lds_key(int32_t device, int32_t slot, int32_t bytes)
-{
-    static const char slots[16] = {0};
-    if (slot < 0 || slot >= 16) return -1;
-    if (dyn_lds_seen(-1000 - device, &slots[slot], bytes, false)) return 0;
-    (void)dyn_lds_seen(-1000 - device, &slots[slot], bytes, true);
-    return 1;
-}
-#endif
-
-#define GS_NAMES_OP(BASE, R) {GS_NAME(BASE, "", R), GS_NAME(BASE, ".op", R)}
-// ... per kind of attachment (GsAttached::kind): the uniform kernels' names, then the parameter map's kernel sets' (the same
-// rules, a "/map" suffix behind the rule's), the domain mask's (a "/mask" suffix) and the noise forms' (a "/noise" suffix)
+// A table of names (gs_step_flavour.h: GS_RULES_OF) per kind of attachment (GsAttached::kind): the uniform kernels' names,
+// then the parameter map's kernel sets' (the same rules, a "/map" suffix behind the rule's), the domain mask's (a "/mask"
+// suffix) and the noise forms' (a "/noise" suffix)
 #define GS_KINDS(M, BASE) {GS_RULES_OF(M, BASE, ""), GS_RULES_OF(M, BASE, "/map"), GS_RULES_OF(M, BASE, "/mask"), GS_RULES_OF(M, BASE, "/noise")}
 #define GS_NAME1(BASE, R) GS_NAME(BASE, "", R)
-#define GS_PLAIN_FN(KER) reinterpret_cast<const void *>(&GS_SUFFIX(KER))
-// [shape: 32 x 64, 16 x 64, 64 x 64][variant] of the LDS-window kernels, BASE "" or "ensemble-"
-#define GS_TILE_NAMES(BASE, R) {GS_NAMES_OP(BASE "tile32x64", R), GS_NAMES_OP(BASE "tile16x64", R), GS_NAMES_OP(BASE "tile64x64", R)}
-#define GS_TILE_FNS(KER) {{GS_FN(KER, 2, 0), GS_FN(KER, 2, kOp)}, {GS_FN(KER, 1, 0), GS_FN(KER, 1, kOp)}, {GS_FN(KER, 4, 0), GS_FN(KER, 4, kOp)}}
-#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY
-
-#if !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 
 // The attachment as a launcher takes it: a known kind with its planes in place.
 static bool attached_ok(const GsAttached &at)
@@ -267,7 +142,7 @@ hipError_t GS_SUFFIX(gs_launch_resident)(const GsStepArgs &a, int steps, hipStre
     const void *fn = fns[zh][fast ? 1 : 0];
     const size_t lds = (size_t)4 * (a.rows + 2) * (a.cols + 2) * sizeof(float); // <= 74 KB (1 x 1536 cells)
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
-        const hipError_t e = ensure_dyn_lds(fn, lds > 64 * 1024 ? (size_t)80 * 1024 : lds);
+        const hipError_t e = gs_ensure_dyn_lds(fn, lds > 64 * 1024 ? (size_t)80 * 1024 : lds);
         if (e != hipSuccess) return e;
     }
     GsStepArgs args = a;
@@ -301,7 +176,7 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
     static const int lds_floor = gs_env_int("GS_HIP_TILE_LDS_FLOOR", 0, 0, 160 * 1024);
     if (lds < (size_t)lds_floor) lds = (size_t)lds_floor; // experiment: limit the workgroups per CU
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
-        const hipError_t e = ensure_dyn_lds(fn, lds);
+        const hipError_t e = gs_ensure_dyn_lds(fn, lds);
         if (e != hipSuccess) return e;
     }
     GsStepArgs args = a;
@@ -309,16 +184,9 @@ hipError_t GS_SUFFIX(gs_launch_tile)(const GsStepArgs &a, int k, int shape, hipS
     return hipLaunchKernel(fn, dim3((unsigned)tiles), dim3(kTileWaves * 64), kargs, lds, s);
 }
 
-// One persistent launch of gs_run_window_k: `x.steps` time steps of a single slab, in-planes -> out-planes.
-// rpw: rows per wave (a window is at most 16 rpw rows x 128 columns); x.desc holds the caller's tiling of the grid.
-// Ensembles (gs_ensemble.h).  `fast` = 3 when EVERY member has side weights 0.5 and dt == 1 (strict only), else 0.
-// Launches are split so that none dispatches more than kGsEnsMaxGroups workgroups.
-// Resident form: `steps` time steps of every member in one launch; the result is stored in the out-planes when steps is
-// odd, else back in the in-planes.
-// `list` (the listed forms, gs_ensemble.h): device list of the active members' indices -- the launch covers entries
-// [e.first, e.first + e.members) of it and runs the kernels' listed twins, named with a "/listed" suffix; nullptr: members
-// [e.first, e.first + e.members) themselves.
-static hipError_t launch_ens_resident(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name)
+// Ensembles (gs_ensemble.h): gs_ens_launch.h's bodies over the plain kernels and, with `list` (device list of the active
+// members' indices), over their listed twins, named with a "/listed" suffix.
+hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s, const char **name)
 {
     static const char *const names[2][3][2] = {GS_RULES(GS_NAMES_OP, "ensemble-resident"), GS_RULES_OF(GS_NAMES_OP, "ensemble-resident", "/listed")};
     // [rule][variant][cells per thread: 1, 2, 4, 8]; the clipped rule has no 8-cell form (gs_ens_resident_cpt)
@@ -333,86 +201,18 @@ static hipError_t launch_ens_resident(const GsEnsArgs &e, const uint32_t *list, 
                                                 GS_ENS_RESIDENT_FNS(gs_ens_resident_lk, gs_ens_resident_lpk, gs_ens_resident_lnk)};
 #undef GS_ENS_RESIDENT_FNS
 #undef GS_CPT_FNS
-    const long cells = (long)e.rows * e.cols;
-    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0) return hipErrorInvalidValue;
-    const long threads = cells >= 1024 ? 1024 : ((cells + 63) / 64) * 64; // the waves that hold cells
-    const int cpt = gs_ens_resident_cpt(e.rows, e.cols, e.zero_halo);
-    const size_t lds = (size_t)4 * (e.rows + 2) * (e.cols + 2) * sizeof(float);
-    if (!cpt || lds > kGsEnsResidentMaxLds) return hipErrorInvalidValue;
-    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    const int zh = e.zero_halo >= 2 && e.zero_halo <= 3 ? e.zero_halo : (e.zero_halo ? 1 : 0); // gs_boundary
-    if (name) *name = names[list ? 1 : 0][rule_set(zh)][fast ? 1 : 0];
-    const void *fn = fns[list ? 1 : 0][zh][fast ? 1 : 0][__builtin_ctz(cpt)];
-    if (!fn) return hipErrorInvalidValue;
-    { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
-        const hipError_t err = ensure_dyn_lds(fn, lds);
-        if (err != hipSuccess) return err;
-    }
-    int to_out = steps & 1;
-    for (long m0 = 0; m0 < e.members; m0 += kGsEnsMaxGroups) {
-        GsEnsArgs args = e;
-        args.first = e.first + m0;
-        args.members = (int32_t)(e.members - m0 < kGsEnsMaxGroups ? e.members - m0 : kGsEnsMaxGroups);
-        void *kargs[] = {&args, &steps, &to_out}, *largs[] = {&args, &list, &steps, &to_out};
-        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)args.members), dim3((unsigned)threads), list ? largs : kargs, lds, s);
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
+    return ens_launch_resident(e, names[list ? 1 : 0], fns[list ? 1 : 0], list ? &list : nullptr, steps, fast, s, name);
 }
-hipError_t GS_SUFFIX(gs_launch_ens_resident)(const GsEnsArgs &e, int steps, int fast, hipStream_t s, const char **name)
-{
-    return launch_ens_resident(e, nullptr, steps, fast, s, name);
-}
-hipError_t GS_SUFFIX(gs_launch_ens_resident_listed)(const GsEnsArgs &e, const uint32_t *list, int steps, int fast, hipStream_t s,
-                                                    const char **name)
-{
-    return list ? launch_ens_resident(e, list, steps, fast, s, name) : hipErrorInvalidValue;
-}
-
-// Windowed form: K <= kGsTileMaxSteps steps of every member (in-planes -> out-planes); `shape` as gs_launch_tile's; `list` as
-// the resident form's.
-static hipError_t launch_ens_tile(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name)
+hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s, const char **name)
 {
     static const char *const names[2][3][3][2] = {GS_RULES(GS_TILE_NAMES, "ensemble-"), GS_RULES_OF(GS_TILE_NAMES, "ensemble-", "/listed")};
     static const void *const fns[2][3][3][2] = {{GS_TILE_FNS(gs_ens_tile_k), GS_TILE_FNS(gs_ens_tile_pk), GS_TILE_FNS(gs_ens_tile_nk)},
                                                 {GS_TILE_FNS(gs_ens_tile_lk), GS_TILE_FNS(gs_ens_tile_lpk), GS_TILE_FNS(gs_ens_tile_lnk)}};
-    static const int rpw[3] = {2, 1, 4};
-    const int per = rule_set(e.zero_halo); // the periodic and zero-flux rules: gs_ens_tile_pk / _nk
-    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]))
-        return hipErrorInvalidValue;
-    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    if (name) *name = names[list ? 1 : 0][per][shape][fast ? 1 : 0];
-    const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
-    const long windows = ((e.rows + ho - 1) / ho) * ((e.cols + wo - 1) / wo);
-    if (windows > kGsEnsMaxGroups) return hipErrorInvalidConfiguration;
-    const void *fn = fns[list ? 1 : 0][per][shape][fast ? 1 : 0];
-    const size_t lds = tile_lds_bytes(rpw[shape]);
-    {
-        const hipError_t err = ensure_dyn_lds(fn, lds);
-        if (err != hipSuccess) return err;
-    }
-    const long per_launch = kGsEnsMaxGroups / windows; // members per launch
-    int wins = (int)windows;
-    for (long m0 = 0; m0 < e.members; m0 += per_launch) {
-        GsEnsArgs args = e;
-        args.first = e.first + m0;
-        args.members = (int32_t)(e.members - m0 < per_launch ? e.members - m0 : per_launch);
-        void *kargs[] = {&args, &k, &wins}, *largs[] = {&args, &list, &k, &wins};
-        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)(args.members * windows)), dim3(kTileWaves * 64), list ? largs : kargs, lds, s);
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
-}
-hipError_t GS_SUFFIX(gs_launch_ens_tile)(const GsEnsArgs &e, int k, int shape, int fast, hipStream_t s, const char **name)
-{
-    return launch_ens_tile(e, nullptr, k, shape, fast, s, name);
-}
-hipError_t GS_SUFFIX(gs_launch_ens_tile_listed)(const GsEnsArgs &e, const uint32_t *list, int k, int shape, int fast, hipStream_t s,
-                                                const char **name)
-{
-    return list ? launch_ens_tile(e, list, k, shape, fast, s, name) : hipErrorInvalidValue;
+    return ens_launch_tile(e, names[list ? 1 : 0], fns[list ? 1 : 0], list ? &list : nullptr, k, shape, fast, s, name);
 }
 
+// One persistent launch of gs_run_window_k: `x.steps` time steps of a single slab, in-planes -> out-planes.
+// rpw: rows per wave (a window is at most 16 rpw rows x 128 columns); x.desc holds the caller's tiling of the grid.
 hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &x, int rpw, hipStream_t s, const char **name)
 {
     // (5 rows per wave: 80-row windows.  The 96-row form of round 4 -- 6 rows per wave, 12 cells per lane -- spilled 43
@@ -438,7 +238,7 @@ hipError_t GS_SUFFIX(gs_launch_window)(const GsStepArgs &a, const GsWindowArgs &
 #undef GS_WIN_FN
     const size_t lds = win_lds_bytes();
     { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
-        const hipError_t e = ensure_dyn_lds(fn, lds);
+        const hipError_t e = gs_ensure_dyn_lds(fn, lds);
         if (e != hipSuccess) return e;
     }
     GsStepArgs args = a;
@@ -477,7 +277,6 @@ hipError_t GS_SUFFIX(gs_launch_stream)(const GsStepArgs &a, hipStream_t s, const
     return launch_attached(fns[at.kind][per], blocks, args, at, s);
 }
 
-// K fused steps over the row ranges of GsStepArgs; on slab seams the ghost rows must be K deep.
 // Kernel entry for k fused steps, specialisation `fast` (already reduced to {0, 1, 3}) and cpl columns per lane; `per`:
 // the kernel set of the boundary rule (rule_set: 1 = the periodic rule's gs_step_tb_pk, 2 = the zero-flux rule's _nk).
 static const void *tb_entry(int k, int fast, int cpl, int wg = 4, int per = 0)
@@ -554,8 +353,6 @@ static int tb_reduce_fast(int fast, int k = 0, int cpl = 0, int wg = 4, int per 
     return fast & 3;
 }
 
-// Wave slots of the chip for the kernel entry a launch with these parameters would use (the tuner's
-// "a launch of exactly r rounds" candidates, gs_tuner.cpp); 0 = no such entry.  `boundary`: gs_boundary.
 // Kernel entry of the marching kernel in the kernel set of an attachment of `kind` (4-wave workgroups; `fast` reduced).
 static const void *tb_entry_of(int kind, int k, int fast, int cpl, int per)
 {
@@ -574,6 +371,8 @@ static int tb_fast_of(int kind, int fast, int k, int cpl, int per)
     return f && !tb_entry_of(kind, k, f, cpl, per) ? 0 : f;
 }
 
+// Wave slots of the chip for the kernel entry a launch with these parameters would use (the tuner's
+// "a launch of exactly r rounds" candidates, gs_tuner.cpp); 0 = no such entry.  `boundary`: gs_boundary.
 int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, int kind)
 {
     if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || kind < GS_ATTACH_NONE || kind >= GS_ATTACH_KINDS) return 0;
@@ -582,6 +381,7 @@ int GS_SUFFIX(gs_tb_wave_slots)(int k, int fast, int cpl, int boundary, int kind
     return fn ? 1024 * tb_waves_of(fn) : 0;
 }
 
+// K fused steps over the row ranges of GsStepArgs; on slab seams the ghost rows must be K deep.
 hipError_t GS_SUFFIX(gs_launch_tb)(const GsStepArgs &a, int k, hipStream_t s, const char **name, const GsAttached &at, GsQuiet *quiet)
 {
     if (quiet) { quiet->need = 0; quiet->launched = 0; }
@@ -799,240 +599,25 @@ hipError_t GS_SUFFIX(gs_launch_map_rates)(const float *feed, const float *kill, 
     return hipGetLastError();
 }
 #undef GS_MAP_RATES_K
-#endif // !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
 
-#if defined(GS_WIN_TRACE) && !GS_TB_OP_ONLY && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
+// The launchers of this flavour, as the host side takes them (gs_kernels.h: gs_launchers).  Host pass only: the compiler
+// would emit a constant of namespace scope for the device too, where the functions it names do not exist.
+#if !defined(__HIP_DEVICE_COMPILE__)
+const GsLaunchers GS_SUFFIX(gs_launchers) = {
+    GS_SUFFIX(gs_launch_simple),       GS_SUFFIX(gs_launch_stream),   GS_SUFFIX(gs_launch_resident),
+    GS_SUFFIX(gs_launch_tb),           GS_SUFFIX(gs_launch_tile),     GS_SUFFIX(gs_launch_lds),
+    GS_SUFFIX(gs_launch_window),       GS_SUFFIX(gs_tb_wave_slots),   GS_SUFFIX(gs_launch_map_rates),
+    GS_SUFFIX(gs_launch_ens_resident), GS_SUFFIX(gs_launch_ens_tile), GS_SUFFIX(gs_launch_ens_resident_noise),
+    GS_SUFFIX(gs_launch_ens_tile_noise)};
+#endif
+
+#if defined(GS_WIN_TRACE)
 extern "C" int32_t GS_SUFFIX(gs_debug_win_trace_read)(unsigned long long *dst)
 {
     return hipMemcpyFromSymbol(dst, HIP_SYMBOL(gs_win_trace), sizeof(unsigned long long) * 1024 * 8 * 8) == hipSuccess ? 0 : -1;
 }
 #endif
 
-#if defined(GS_TB_TRACE) && !GS_TB_MAP_ONLY && !GS_TB_MASK_ONLY && !GS_NOISE_ONLY
-// Copies the trace buffer of THIS translation unit's kernels out (diagnostic builds only).
-#if GS_TB_OP_ONLY
-extern "C" int32_t gs_debug_trace_read_op(unsigned long long *dst, int32_t units, int32_t clear)
-#else
-extern "C" int32_t GS_SUFFIX(gs_debug_trace_read)(unsigned long long *dst, int32_t units, int32_t clear)
-#endif
-{
-    if (units > kTraceUnits) units = kTraceUnits;
-    if (hipMemcpyFromSymbol(dst, HIP_SYMBOL(gs_trace_buf), (size_t)units * kTraceWords * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (clear) {
-        void *p = nullptr;
-        if (hipGetSymbolAddress(&p, HIP_SYMBOL(gs_trace_buf)) != hipSuccess) return -1;
-        if (hipMemset(p, 0, (size_t)units * kTraceWords * sizeof(unsigned long long)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-#endif
-
-#if GS_TB_OP_ONLY
-// Kernel entry of the specialised variant for K fused steps, `fast` in {1, 3} (GsStepArgs::fast)
-// and `cpl` columns per lane; RULE: the kernel set of the boundary rule (1 = the periodic rule's form, 2 = the zero-flux
-// rule's).
-template <int RULE>
-static const void *tb_op_kernel(int k, int fast, int cpl, int wg)
-{
-#define GS_OP_FN(KER, ...) (RULE == 1 ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_pk)<__VA_ARGS__>) \
-                            : RULE == 2 ? reinterpret_cast<const void *>(&GS_SUFFIX(KER##_nk)<__VA_ARGS__>) \
-                                        : reinterpret_cast<const void *>(&GS_SUFFIX(KER##_k)<__VA_ARGS__>))
-    if (fast == 7) { // full difference sharing: 2 columns per lane
-        if (cpl != 2) return nullptr;
-        if (wg == 16) return k == 4 ? GS_OP_FN(gs_step_tb_ds, 4, 16) : nullptr;
-        switch (k) {
-        case 2: return GS_OP_FN(gs_step_tb_ds, 2);
-        case 3: return GS_OP_FN(gs_step_tb_ds, 3);
-        case 4: return GS_OP_FN(gs_step_tb_ds, 4);
-        default: return nullptr;
-        }
-    }
-    if (fast == 15) { // ... and across lanes
-        if (cpl != 2) return nullptr;
-        if (wg == 16) return k == 4 ? GS_OP_FN(gs_step_tb_dx, 4, 16) : nullptr;
-        switch (k) {
-        case 2: return GS_OP_FN(gs_step_tb_dx, 2);
-        case 3: return GS_OP_FN(gs_step_tb_dx, 3);
-        case 4: return GS_OP_FN(gs_step_tb_dx, 4);
-        default: return nullptr;
-        }
-    }
-    if (wg == 16) {
-        if (k != 4 || (cpl != 1 && cpl != 2) || (fast != 1 && fast != 3)) return nullptr;
-        if (fast == 1)
-            return cpl == 1 ? GS_OP_FN(gs_step_tb, 4, 1, 1, 16) : GS_OP_FN(gs_step_tb, 4, 1, 2, 16);
-        return cpl == 1 ? GS_OP_FN(gs_step_tb, 4, 3, 1, 16) : GS_OP_FN(gs_step_tb, 4, 3, 2, 16);
-    }
-#define GS_TB_CASE(KK, FF, CC)                                                                  \
-    case ((KK) * 4 + (FF)) * 8 + (CC): return GS_OP_FN(gs_step_tb, KK, FF, CC);
-#define GS_TB_CASES(FF, CC) GS_TB_CASE(1, FF, CC) GS_TB_CASE(2, FF, CC) GS_TB_CASE(3, FF, CC) GS_TB_CASE(4, FF, CC)
-    switch ((k * 4 + fast) * 8 + cpl) {
-        GS_TB_CASES(1, 4) GS_TB_CASES(3, 4)
-        GS_TB_CASES(1, 2) GS_TB_CASES(3, 2)
-        GS_TB_CASES(1, 1) GS_TB_CASES(3, 1)
-    default: return nullptr;
-    }
-#undef GS_TB_CASES
-#undef GS_TB_CASE
-#undef GS_OP_FN
-}
-const void *gs_tb_quiet_kernel_strict(int k)
-{
-    switch (k) {
-    case 2: return GS_FN(gs_step_tb_dx_qk, 2);
-    case 3: return GS_FN(gs_step_tb_dx_qk, 3);
-    case 4: return GS_FN(gs_step_tb_dx_qk, 4);
-    default: return nullptr;
-    }
-}
-const void *gs_tb_op_kernel_strict(int k, int fast, int cpl, int wg, int rule)
-{
-    return rule == 1 ? tb_op_kernel<1>(k, fast, cpl, wg) : (rule == 2 ? tb_op_kernel<2>(k, fast, cpl, wg) : tb_op_kernel<0>(k, fast, cpl, wg));
-}
-#endif
-
-#if GS_TB_MAP_ONLY || GS_TB_MASK_ONLY || GS_NOISE_ONLY
-// Entry tables of the marching kernel's per-cell form KER (gs_step_tb_mk, gs_step_tb_wk), variant F (0: general, 3: .op):
-// [k - 1], [cpl 1, 2, 4][k - 1] and [rule][cpl 1, 2, 4][k - 1]
-#define GS_CELL_KS(KER, F, C, R) {GS_FN(KER, 1, F, C, R), GS_FN(KER, 2, F, C, R), GS_FN(KER, 3, F, C, R), GS_FN(KER, 4, F, C, R)}
-#define GS_CELL_CPLS(KER, F, R) {GS_CELL_KS(KER, F, 1, R), GS_CELL_KS(KER, F, 2, R), GS_CELL_KS(KER, F, 4, R)}
-#define GS_CELL_RULES(KER, F) {GS_CELL_CPLS(KER, F, 0), GS_CELL_CPLS(KER, F, 1), GS_CELL_CPLS(KER, F, 2)}
-// ... and the entry for K = 1..4 fused steps, `fast` 0 (general) or 3 (.op: side weights 0.5, dt == 1; `op` is nullptr in the
-// fused flavour, which has none), 1, 2 or 4 columns per lane, `rule` the kernel set of the boundary rule (rule_set);
-// nullptr for a form that is not built.
-static const void *tb_cell_entry(const void *const (*general)[3][4], const void *const (*op)[3][4], int k, int fast, int cpl, int rule)
-{
-    if (k < 1 || k > 4 || (cpl != 1 && cpl != 2 && cpl != 4) || rule < 0 || rule > 2) return nullptr;
-    const void *const(*table)[3][4] = fast == 0 ? general : (fast == 3 ? op : nullptr);
-    return table ? table[rule][cpl == 4 ? 2 : cpl - 1][k - 1] : nullptr;
-}
-#endif
-
-#if GS_TB_MAP_ONLY
-// Kernel entry of the marching kernel's parameter-map form (gs_kernels.h: gs_tb_map_kernel_*).
-const void *GS_SUFFIX(gs_tb_map_kernel)(int k, int fast, int cpl, int rule)
-{
-    static const void *const general[3][3][4] = GS_CELL_RULES(gs_step_tb_mk, 0);
-#if GS_MATH_FUSED
-    return tb_cell_entry(general, nullptr, k, fast, cpl, rule);
-#else
-    static const void *const op[3][3][4] = GS_CELL_RULES(gs_step_tb_mk, 3);
-    return tb_cell_entry(general, op, k, fast, cpl, rule);
-#endif
-}
-#endif
-
-#if GS_TB_MASK_ONLY
-// Kernel entry of the marching kernel's domain-mask form (gs_kernels.h: gs_tb_mask_kernel_*), the parameters of
-// gs_tb_map_kernel_*.  Not built: the .op form of the clipped and zero-halo rules' kernels with 4 columns per lane and 3 or
-// 4 fused steps -- the selects of their left and right edge cells on top of the masks' keep a stack frame in scratch;
-// gs_launch_tb runs the general form there.
-const void *GS_SUFFIX(gs_tb_mask_kernel)(int k, int fast, int cpl, int rule)
-{
-    static const void *const general[3][3][4] = GS_CELL_RULES(gs_step_tb_wk, 0);
-#if GS_MATH_FUSED
-    return tb_cell_entry(general, nullptr, k, fast, cpl, rule);
-#else
-    static const void *const op[3][3][4] = {
-        {GS_CELL_KS(gs_step_tb_wk, 3, 1, 0), GS_CELL_KS(gs_step_tb_wk, 3, 2, 0),
-         {GS_FN(gs_step_tb_wk, 1, 3, 4, 0), GS_FN(gs_step_tb_wk, 2, 3, 4, 0), nullptr, nullptr}},
-        GS_CELL_CPLS(gs_step_tb_wk, 3, 1), GS_CELL_CPLS(gs_step_tb_wk, 3, 2)};
-    return tb_cell_entry(general, op, k, fast, cpl, rule);
-#endif
-}
-#endif
-
-#if GS_NOISE_ONLY
-// The noise forms of the ensemble kernels (gs_members_set_noise; gs_ensemble.h): launch_ens_resident's and launch_ens_tile's
-// checks, shapes and splits, the kernels gs_ens_resident_z* / gs_ens_tile_z* with GsEnsNoiseArgs as their second argument.
-// The name carries "/noise" behind the rule's suffix, and "/listed" behind that when z.list is set.
-hipError_t GS_SUFFIX(gs_launch_ens_resident_noise)(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int steps, int fast, hipStream_t s,
-                                                   const char **name)
-{
-    static const char *const names[2][3][2] = {GS_RULES_OF(GS_NAMES_OP, "ensemble-resident", "/noise"),
-                                               GS_RULES_OF(GS_NAMES_OP, "ensemble-resident", "/noise/listed")};
-    // [rule][variant][cells per thread: 1, 2, 4, 8]; the clipped rule has no 8-cell form (gs_ens_resident_cpt)
-#define GS_CPT_FNS(KER, ...) {GS_FN(KER, 1, __VA_ARGS__), GS_FN(KER, 2, __VA_ARGS__), GS_FN(KER, 4, __VA_ARGS__), GS_FN(KER, 8, __VA_ARGS__)}
-    static const void *const fns[4][2][4] = {
-        {{GS_FN(gs_ens_resident_zk, 1, 0, 0), GS_FN(gs_ens_resident_zk, 2, 0, 0), GS_FN(gs_ens_resident_zk, 4, 0, 0), nullptr},
-         {GS_FN(gs_ens_resident_zk, 1, kOp, 0), GS_FN(gs_ens_resident_zk, 2, kOp, 0), GS_FN(gs_ens_resident_zk, 4, kOp, 0), nullptr}},
-        {GS_CPT_FNS(gs_ens_resident_zk, 0, 1), GS_CPT_FNS(gs_ens_resident_zk, kOp, 1)},
-        {GS_CPT_FNS(gs_ens_resident_zpk, 0), GS_CPT_FNS(gs_ens_resident_zpk, kOp)},
-        {GS_CPT_FNS(gs_ens_resident_znk, 0), GS_CPT_FNS(gs_ens_resident_znk, kOp)}};
-#undef GS_CPT_FNS
-    const long cells = (long)e.rows * e.cols;
-    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || steps < 0 || !z.table) return hipErrorInvalidValue;
-    const long threads = cells >= 1024 ? 1024 : ((cells + 63) / 64) * 64; // the waves that hold cells
-    const int cpt = gs_ens_resident_cpt(e.rows, e.cols, e.zero_halo);
-    const size_t lds = (size_t)4 * (e.rows + 2) * (e.cols + 2) * sizeof(float);
-    if (!cpt || lds > kGsEnsResidentMaxLds) return hipErrorInvalidValue;
-    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    const int zh = e.zero_halo >= 2 && e.zero_halo <= 3 ? e.zero_halo : (e.zero_halo ? 1 : 0); // gs_boundary
-    if (name) *name = names[z.list ? 1 : 0][rule_set(zh)][fast ? 1 : 0];
-    const void *fn = fns[zh][fast ? 1 : 0][__builtin_ctz(cpt)];
-    if (!fn) return hipErrorInvalidValue;
-    { // more than 64 KB of dynamic LDS needs the opt-in, per device and device function
-        const hipError_t err = ensure_dyn_lds(fn, lds);
-        if (err != hipSuccess) return err;
-    }
-    int to_out = steps & 1;
-    GsEnsNoiseArgs nz = z;
-    for (long m0 = 0; m0 < e.members; m0 += kGsEnsMaxGroups) {
-        GsEnsArgs args = e;
-        args.first = e.first + m0;
-        args.members = (int32_t)(e.members - m0 < kGsEnsMaxGroups ? e.members - m0 : kGsEnsMaxGroups);
-        void *kargs[] = {&args, &nz, &steps, &to_out};
-        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)args.members), dim3((unsigned)threads), kargs, lds, s);
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
-}
-hipError_t GS_SUFFIX(gs_launch_ens_tile_noise)(const GsEnsArgs &e, const GsEnsNoiseArgs &z, int k, int shape, int fast, hipStream_t s,
-                                               const char **name)
-{
-    static const char *const names[2][3][3][2] = {GS_RULES_OF(GS_TILE_NAMES, "ensemble-", "/noise"),
-                                                  GS_RULES_OF(GS_TILE_NAMES, "ensemble-", "/noise/listed")};
-    static const void *const fns[3][3][2] = {GS_TILE_FNS(gs_ens_tile_zk), GS_TILE_FNS(gs_ens_tile_zpk), GS_TILE_FNS(gs_ens_tile_znk)};
-    static const int rpw[3] = {2, 1, 4};
-    const int per = rule_set(e.zero_halo);
-    if (e.rows <= 0 || e.cols <= 0 || e.members < 0 || k < 1 || k > kTileMaxK || shape < 0 || shape > 2 || 2 * k >= tile_rows(rpw[shape]) ||
-        !z.table)
-        return hipErrorInvalidValue;
-    fast = GS_MATH_FUSED ? 0 : (fast == 3 ? 3 : 0);
-    if (name) *name = names[z.list ? 1 : 0][per][shape][fast ? 1 : 0];
-    const long ho = tile_rows(rpw[shape]) - 2 * k, wo = kTileCols - 2 * k;
-    const long windows = ((e.rows + ho - 1) / ho) * ((e.cols + wo - 1) / wo);
-    if (windows > kGsEnsMaxGroups) return hipErrorInvalidConfiguration;
-    const void *fn = fns[per][shape][fast ? 1 : 0];
-    const size_t lds = tile_lds_bytes(rpw[shape]);
-    {
-        const hipError_t err = ensure_dyn_lds(fn, lds);
-        if (err != hipSuccess) return err;
-    }
-    const long per_launch = kGsEnsMaxGroups / windows; // members per launch
-    int wins = (int)windows;
-    GsEnsNoiseArgs nz = z;
-    for (long m0 = 0; m0 < e.members; m0 += per_launch) {
-        GsEnsArgs args = e;
-        args.first = e.first + m0;
-        args.members = (int32_t)(e.members - m0 < per_launch ? e.members - m0 : per_launch);
-        void *kargs[] = {&args, &nz, &k, &wins};
-        const hipError_t err = hipLaunchKernel(fn, dim3((unsigned)(args.members * windows)), dim3(kTileWaves * 64), kargs, lds, s);
-        if (err != hipSuccess) return err;
-    }
-    return hipSuccess;
-}
-
-// Kernel entry of the marching kernel's noise form (gs_kernels.h: gs_tb_noise_kernel_*), the parameters of
-// gs_tb_map_kernel_*.
-const void *GS_SUFFIX(gs_tb_noise_kernel)(int k, int fast, int cpl, int rule)
-{
-    static const void *const general[3][3][4] = GS_CELL_RULES(gs_step_tb_zk, 0);
-#if GS_MATH_FUSED
-    return tb_cell_entry(general, nullptr, k, fast, cpl, rule);
-#else
-    static const void *const op[3][3][4] = GS_CELL_RULES(gs_step_tb_zk, 3);
-    return tb_cell_entry(general, op, k, fast, cpl, rule);
-#endif
-}
+#if defined(GS_TB_TRACE)
+extern "C" int32_t GS_SUFFIX(gs_debug_trace_read)(unsigned long long *dst, int32_t units, int32_t clear) { return gs_trace_read(dst, units, clear); }
 #endif

@@ -56,8 +56,7 @@ int fast_of(const gs_ctx *ctx)
 // Writes up to `max` heights (the single-round one first); returns their number.
 int fit_heights(const gs_ctx *ctx, int32_t rows, int32_t cols, int fuse, int cpl, int fast, int *out, int max, bool partial)
 {
-    const int slots = ctx->o.math == GS_MATH_FUSED ? gs_tb_wave_slots_fused(fuse, fast, cpl, ctx->o.boundary, ctx->attached.kind)
-                                                     : gs_tb_wave_slots_strict(fuse, fast, cpl, ctx->o.boundary, ctx->attached.kind);
+    const int slots = gs_launchers(ctx->o.math).tb_wave_slots(fuse, fast, cpl, ctx->o.boundary, ctx->attached.kind);
     const long strips = tb_strips(cols, fuse, cpl);
     if (slots <= 0 || strips <= 0) return 0;
     const long per_round = slots / strips; // chunks per round

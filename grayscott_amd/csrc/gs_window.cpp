@@ -283,8 +283,7 @@ int32_t run_window(gs_ctx *ctx, Run &r, uint64_t steps, bool forced, int32_t *la
         x.patience = gs_env_int("GS_HIP_WINDOW_PATIENCE", 1 << 20, 1, 1 << 30); // polls of 2-3 us each: 2-3 s
         x.seq = ++w.seq;
         const char *name = nullptr;
-        const hipError_t e = ctx->o.math == GS_MATH_FUSED ? gs_launch_window_fused(a, x, w.plan_rpw, sl.compute, &name)
-                                                           : gs_launch_window_strict(a, x, w.plan_rpw, sl.compute, &name);
+        const hipError_t e = gs_launchers(ctx->o.math).window(a, x, w.plan_rpw, sl.compute, &name);
         if (e != hipSuccess) return fail(GS_ERR_HIP, "kernel launch failed: %s", hipGetErrorString(e));
         const int supers = (n + w.plan_k - 1) / w.plan_k;
         w.epoch += supers;

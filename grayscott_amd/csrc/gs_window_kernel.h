@@ -1,7 +1,7 @@
 // gs_window_kernel.h -- grids of one round of register-resident windows (the reference's default 1080 x 1920): the whole
 // gs_run in one persistent launch, aprons traded between workgroups inside it (gs_run_window_k).
-// Part of the gfx950 step kernels: included by gs_step_kernels.hip (which sets GS_MATH_FUSED / GS_TB_OP_ONLY and the
-// GS_SUFFIX / GS_TAP macros) inside one translation unit per arithmetic flavour; not a header to include elsewhere.
+// Part of the gfx950 step kernels: included by their main unit, gs_step_kernels.hip, behind gs_step_flavour.h (GS_MATH_FUSED,
+// GS_SUFFIX, GS_TAP) and gs_cell.h, once per arithmetic flavour; not a header to include elsewhere.
 #pragma once
 
 namespace {

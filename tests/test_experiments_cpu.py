@@ -4,8 +4,8 @@ import re
 
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "grayscott_amd", "csrc")
 HEADER = "gs_experiments.h"
-# what _build.py sets per translation unit of gs_step_kernels.hip: the build, not experiments
-SELECTORS = {"GS_MATH_FUSED", "GS_TB_OP_ONLY", "GS_TB_MAP_ONLY", "GS_TB_MASK_ONLY", "GS_SUFFIX"}
+# what _build.py sets per translation unit of the step kernels (gs_step_flavour.h): the build, not experiments
+SELECTORS = {"GS_MATH_FUSED", "GS_SUFFIX"}
 
 
 def _sources():
@@ -48,3 +48,9 @@ def test_every_tested_switch_is_listed():
                 if macro not in known:
                     strays.append(f"{name}: {macro}")
     assert not strays, f"switches tested in an #if that {HEADER} neither defaults nor documents: {sorted(set(strays))}"
+
+
+def test_no_macro_selects_a_translation_unit():
+    """Every translation unit of the step kernels has a source file of its own: no `*_ONLY` macro anywhere under csrc/."""
+    hits = sorted(f"{name}: {m}" for name, text in _sources().items() for m in set(re.findall(r"\b\w+_ONLY\b", text)))
+    assert not hits, hits

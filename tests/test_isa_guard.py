@@ -41,9 +41,15 @@ def fused(kernels):
 
 def test_every_translation_unit_is_there(kernels):
     names = set(kernels)
-    # one kernel of each translation unit: strict, strict parameter-specialised, fused, utilities
+    # one kernel of each translation unit: strict, strict parameter-specialised, fused, utilities, then the map, mask and
+    # noise units of either flavour (the noise units: a marching and an ensemble kernel)
     for probe in ("gs_step_stream_k_strict<2>", "gs_step_tb_dx_k_strict<4, 4>", "gs_step_stream_k_fused<2>",
-                  "gs_fill_rect_k"):
+                  "gs_fill_rect_k",
+                  "gs_step_tb_mk_strict<4, 3, 2, 0>", "gs_step_tb_mk_fused<4, 0, 2, 0>",
+                  "gs_step_tb_wk_strict<4, 3, 2, 0>", "gs_step_tb_wk_fused<4, 0, 2, 0>",
+                  "gs_step_tb_zk_strict<4, 3, 2, 0>", "gs_step_tb_zk_fused<4, 0, 2, 0>",
+                  "gs_ens_tile_zk_strict<2, 3>(GsEnsArgs, GsEnsNoiseArgs, int, int)",
+                  "gs_ens_tile_zk_fused<2, 0>(GsEnsArgs, GsEnsNoiseArgs, int, int)"):
         assert probe in names, (probe, sorted(names))
     assert len(strict(kernels)) >= 60 and len(fused(kernels)) >= 20
 
